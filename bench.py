@@ -2,7 +2,11 @@
 """Benchmark of the hot path on BASELINE.json's metric:
 Mrays/s (+ achieved HBM GB/s) for a 1024^2 camera over a 256^3 mock GRMHD snapshot.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step computed (image, sample_num, sample_flags) as DIR/<name>.npy, for comparing
+two builds output for output; the inputs are the same from run to run. Non-finite intensities are written as 0 and flagged in
+DIR/image_nonfinite.npy (dump_outputs).
 
 A "step" is one complete render (camera -> geodesics -> sampling -> coefficients -> transfer ->
 image in HBM) of the 1024^2 example_simulation camera over the 256^3 mock snapshot, both synthetic
@@ -134,6 +138,52 @@ def relative_distance(got, want):
             "same_nonfinite_and_nonpositive_pixels": bool(np.array_equal(np.isfinite(got) & (got > 0.0), np.isfinite(want) & (want > 0.0)))}
 
 
+DUMP_LIMIT = 64 << 20     # --dump-outputs: bytes of all files together, at most
+DUMP_SEED = 20240607      # ... and the seed of the pixel sample taken when the outputs are larger than that
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs DIR: the arrays a caller of the timed path receives from its last step, one DIR/<name>.npy each, in float64
+    (intensities as computed; counts and flags converted, exactly). Every array has its pixels along the last axis. Every value
+    written is finite: a floating-point array's NaN / +inf / -inf entries (the image of a ray that ends with fallback_nan, say)
+    are written as 0 and flagged in DIR/<name>_nonfinite.npy (float32: 0 finite, 1 NaN, 2 +inf, 3 -inf), written for every
+    such array, so that two runs leave the same files. When they all hold more than DUMP_LIMIT bytes together, each is cut to
+    the same fraction of its pixels, drawn with DUMP_SEED (the same pixels for arrays of one length, and from run to run), and
+    the indices go beside it as DIR/<name>_pixels.npy."""
+    out = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = np.asarray(a)
+        if a.dtype.kind == "f":
+            code = np.zeros(a.shape, dtype=np.float32)
+            code[np.isnan(a)] = 1.0
+            code[np.isposinf(a)] = 2.0
+            code[np.isneginf(a)] = 3.0
+            out[name] = np.where(np.isfinite(a), a, 0.0).astype(np.float64)
+            out[f"{name}_nonfinite"] = code
+        else:
+            out[name] = a.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    headers = 256 * 2 * len(out)   # (.npy headers, with room to spare)
+    full = sum(a.nbytes for a in out.values())
+    fraction = 1.0
+    if full + headers > DUMP_LIMIT:
+        with_index = sum(a.nbytes + 8 * a.shape[-1] for a in out.values())
+        fraction = (DUMP_LIMIT - headers) / with_index
+    written = {}
+    for name, a in out.items():
+        n = a.shape[-1]
+        if fraction < 1.0:
+            pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, int(n * fraction), replace=False))
+            a = np.ascontiguousarray(a[..., pick])
+            np.save(os.path.join(directory, f"{name}_pixels.npy"), pick.astype(np.float64))
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+        written[name] = list(a.shape)
+    nonfinite = {name: int(np.count_nonzero(a)) for name, a in out.items() if name.endswith("_nonfinite")}
+    return {"dir": directory, "arrays": written, "pixel_fraction": fraction, "nonfinite_values": nonfinite}
+
+
 def pipelined_series(args, params, grids, image, sample_num, flags, device):
     """--workload series8_pipelined: frame n renders on this thread while a second host thread hands snapshot n + 1 to bl_set_grid (same
     geometry: its cells go up beside the render and take effect with the next one). The clock runs from the first bl_set_grid to the
@@ -195,6 +245,8 @@ def pipelined_series(args, params, grids, image, sample_num, flags, device):
             "frames_reused_geodesics": [s[0] for s in stats], "shade_ms": [round(s[1], 2) for s in stats], "geodesic_ms": [round(s[2], 2) for s in stats],
             "frames_equal_the_unpipelined_series_bit_for_bit": same, "differing_values_per_frame": differing,
         }
+        if args.dump_outputs:
+            line["dumped_outputs"] = dump_outputs(args.dump_outputs, dict(image=images[-1].cpu().numpy()))
     print(json.dumps(line), flush=True)
 
 
@@ -256,6 +308,9 @@ def series_workload(args):
         last_stats = st
         # the last frame again with its geodesics integrated afresh: the same frame?
         reused_image, reused_num = image.clone(), sample_num.clone()
+        if args.dump_outputs:
+            dumped = dump_outputs(args.dump_outputs, dict(image=image.cpu().numpy(), sample_num=sample_num.cpu().numpy(),
+                                                          sample_flags=flags.cpu().numpy()))
         ctx.set_geodesic_reuse(False)
         fresh = ctx.render_device(image.data_ptr(), n_rays, sample_num_ptr=sample_num.data_ptr(), sample_flags_ptr=flags.data_ptr())
         torch.cuda.synchronize()
@@ -286,6 +341,8 @@ def series_workload(args):
         "hbm_frac_algorithmic_whole_pipeline": (256.0 * gathers + 13.0 * n_rays) / (ms_later * 1.0e-3) / 1.0e9 / HBM_PEAK_GBS,
         "switches": int(last_stats.switches),
     }
+    if args.dump_outputs:
+        line["dumped_outputs"] = dumped
     shade_ms = line["frames_2_to_8"]["kernel_ms_mean"]["shade"]
     line["roofline"] = {"bound": "hbm", "kernel": "coefficient kernel of frames 2 ... 8", "achieved": (256.0 * gathers + 13.0 * n_rays) / (shade_ms * 1.0e-3) / 1.0e9,
                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": (256.0 * gathers + 13.0 * n_rays) / (shade_ms * 1.0e-3) / 1.0e9 / HBM_PEAK_GBS, "traffic": None}
@@ -370,6 +427,11 @@ def other_workload(args):
                 samples += st.n_samples
         elapsed = time.perf_counter() - t0
         st = (out[0] if name == "adaptive2048" else out)["stats"]
+        dumped = None
+        if args.dump_outputs:   # (inside the context: the pinned buffers are its own)
+            levels = out if name == "adaptive2048" else [out]
+            dumped = dump_outputs(args.dump_outputs, {f"{key}{'' if len(levels) == 1 else f'_level{n}'}": level[key]
+                                                      for n, level in enumerate(levels) for key in ("image", "sample_num", "sample_flags")})
     rays_per_step = rays / args.steps
     line = {
         "metric": "Mrays/sec + achieved HBM GB/s", "value": rays / elapsed / 1.0e6, "unit": "Mrays/s", "n_gpus": 1, "steps": args.steps,
@@ -389,6 +451,8 @@ def other_workload(args):
                             "frac": algorithmic / (ms["shade"] * 1.0e-3) / 1.0e9 / HBM_PEAK_GBS, "traffic": None}
     else:
         line["roofline"] = None   # no grid is read (formula mode): what bounds the frame is instruction issue, see profiles/README.md
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     print(json.dumps(line), flush=True)
 
 
@@ -464,7 +528,12 @@ def main():
                          "alone and reports whether the assembled frame equals it bit for bit. A rehearsal of the code path, not a measurement")
     ap.add_argument("--workload", choices=["benchmark"] + sorted(OTHER_WORKLOADS), default="benchmark",
                     help="BASELINE.json's other configurations at their own sizes on one GPU (same JSON schema, not the driver's line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (float64, at most 64 MB in all; "
+                         "N > 1: the frame rank 0 gathers)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.workload != "benchmark":
         if args.gpus != 1:
             raise SystemExit("bench.py --workload: the other configurations are timed on one GPU")
@@ -567,6 +636,7 @@ def main():
         ms = dict(geodesic=0.0, locate=0.0, shade=0.0, transfer=0.0, wall=0.0)
         launches = 0
         stats = None
+        gathered = None
         for _ in range(args.steps):
             stats = step()
             ms["geodesic"] += stats.ms_geodesic
@@ -575,7 +645,7 @@ def main():
             ms["wall"] += stats.ms_wall
             ms["transfer"] += stats.ms_transfer
             launches += stats.launches_shade
-            gather_image()
+            gathered = gather_image()
         fence()
         elapsed = time.perf_counter() - t0
         per_rank = [elapsed]
@@ -593,9 +663,17 @@ def main():
         shade_ms_per_launch = ms["shade"] / max(launches, 1)
         bytes_per_launch = stats.algorithmic_bytes / max(stats.launches_shade, 1)
         return dict(elapsed=elapsed, per_rank=per_rank, ms=ms, stats=stats, totals=totals, shade_ms_per_launch=shade_ms_per_launch,
-                    bytes_per_launch=bytes_per_launch, tier_ran="tolerant" if stats.arithmetic == 1 else "exact")
+                    bytes_per_launch=bytes_per_launch, tier_ran="tolerant" if stats.arithmetic == 1 else "exact", gathered=gathered)
 
     main_run = timed(args.arithmetic)
+    outputs = None
+    if args.dump_outputs:
+        # what the last timed step left, copied before anything else renders into the same buffers (or gathers into the same pool)
+        if not distributed:
+            outputs = dict(image=image[:, :n_rays].cpu().numpy(), sample_num=sample_num[:n_rays].cpu().numpy(),
+                           sample_flags=flags[:n_rays].cpu().numpy())
+        elif rank == 0:
+            outputs = dict(image=main_run["gathered"].cpu().numpy())
     exact_run = timed("exact") if args.arithmetic == "tolerant" else None
     tier_distance = None
     if exact_run is not None:
@@ -759,6 +837,8 @@ def main():
                 "sample_num_bit_exact": bool(np.array_equal(gpu_num, cpu["sample_num"])),
             }
             line["parity_vs_oracle_on_sample"].update(relative_distance(gpu_img, cpu["image"][0]))
+        if outputs is not None:
+            line["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(line), flush=True)
 
     ctx.close()
