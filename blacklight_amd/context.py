@@ -118,7 +118,10 @@ class Context:
 
     def set_geodesic_reuse(self, on=True):
         """Geodesics once per series (default on): a root-level render of an unchanged camera shades the sample records the last one
-        left in HBM instead of integrating its rays again (bl_set_geodesic_reuse; stats.geodesics_reused says which way it went)."""
+        left in HBM instead of integrating its rays again (bl_set_geodesic_reuse; stats.geodesics_reused says which way it went). A frame of
+        more than one chunk is kept from the second render of its camera on, in a record store beside one chunk's shading arrays (the scratch
+        the first render allocated, re-partitioned): the third and later frames reuse. Located samples of such frames, and anything under set_overlap(True), are
+        not kept."""
         self._check(self._lib.bl_set_geodesic_reuse(self._ctx, 1 if on else 0))
 
     def set_caller_stream(self, stream=None, enabled=True):

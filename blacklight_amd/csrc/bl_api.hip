@@ -1115,9 +1115,10 @@ int bl_set_geodesic_reuse(bl_ctx *ctx, int on) {
   ctx->geodesic_reuse = on ? 1 : 0;
   if (!on && ctx->device != BL_DEVICE_NONE) {   // what was kept goes back to the device
     (void)hipSetDevice(ctx->device);
-    ctx->resident.valid = ctx->resident.located_valid = false;
+    DropResident(ctx);
     ctx->resident.parked = false;
     ctx->resident.store.Free();
+    ctx->resident.pending = false;
   }
   return BL_OK;
 }

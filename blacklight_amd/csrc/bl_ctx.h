@@ -247,7 +247,8 @@ struct bl_ctx {
     }
   };
   ChunkSlot slot[2];
-  // bl_set_geodesic_reuse: the root level's geodesics as its last render left them. The buffers are the ones scratch set 0 and the
+  // bl_set_geodesic_reuse: the root level's geodesics as its last render left them (in one chunk, or in the kept layout below). The
+  // buffers are the ones scratch set 0 and the
   // per-ray arrays below point at (`parked` false) or, while a render of another level works there, set aside in `store`
   // (`parked` true: that render allocates its own, which are set aside in turn when the root level comes back - two sets of
   // buffers that change places, no copy).
@@ -260,6 +261,30 @@ struct bl_ctx {
     int tail_policy = BL_TAIL_WIDE;
     unsigned long long n_parked = 0, n_flagged = 0;
     unsigned long long counters[BL_CNT_TOTAL] = {};   // scratch set 0's counters as the geodesic (and locate) stage left them
+    // Kept layout (a root level of more than one chunk): scratch set 0 is re-partitioned, nothing allocated. Its shading arrays serve one
+    // chunk at a time with `record_capacity` entries; the store that holds every chunk's records is a list of segments - the record
+    // arrays themselves and the tails of the shading arrays beyond `record_capacity` entries. One entry per chunk of the render that
+    // integrated them: its first ray, its segment and where its records start there, its counters as its kernels left them. Empty: one
+    // chunk, `counters` above.
+    struct Segment {
+      BlSampleHot *hot = nullptr;
+      BlSampleCold *cold = nullptr;   // (null: interleaved, the cold half follows each hot one)
+      double *sample_t = nullptr;
+      size_t capacity = 0;            // records
+    };
+    struct Chunk {
+      long long begin = 0;
+      int segment = 0;
+      size_t record_base = 0;
+      unsigned long long counters[BL_CNT_TOTAL] = {};
+    };
+    std::vector<Segment> segments;
+    std::vector<Chunk> chunks;
+    // A root-level render of more than one chunk whose records were not kept: its key and the records it used (including the
+    // partly filled blocks). The next render with this key integrates in the kept layout, with a store sized from that count.
+    bool pending = false;
+    std::vector<unsigned char> pending_key;
+    unsigned long long pending_records = 0;
     struct Buffers {
       DeviceBuffer<BlSampleHot> records_hot;
       DeviceBuffer<BlSampleCold> records_cold;
@@ -271,14 +296,15 @@ struct bl_ctx {
       DeviceBuffer<int> ray_sample_num, ray_skipped, ray_rows;
       DeviceBuffer<unsigned char> ray_flags;
       DeviceBuffer<long long> ray_out_index, ray_offset;
+      ChunkSlot slot;   // kept layout: the whole of scratch set 0 is set aside (its shading arrays hold part of the store)
       uint64_t Bytes() const {
-        return records_hot.count * sizeof(BlSampleHot) + records_cold.count * sizeof(BlSampleCold) + sample_t.count * sizeof(double) + located.count * sizeof(BlLocated)
+        return slot.Bytes() + records_hot.count * sizeof(BlSampleHot) + records_cold.count * sizeof(BlSampleCold) + sample_t.count * sizeof(double) + located.count * sizeof(BlLocated)
             + located_tag.count * sizeof(unsigned long long) + anchors.count * sizeof(unsigned int) + (ray_kt.count + ray_factor.count) * sizeof(double)
             + (ray_sample_num.count + ray_skipped.count + ray_rows.count) * sizeof(int) + ray_flags.count + (ray_out_index.count + ray_offset.count) * sizeof(long long);
       }
       void Free() {
         records_hot.Free(); records_cold.Free(); sample_t.Free(); located.Free(); located_tag.Free(); anchors.Free(); ray_kt.Free(); ray_factor.Free();
-        ray_sample_num.Free(); ray_skipped.Free(); ray_rows.Free(); ray_flags.Free(); ray_out_index.Free(); ray_offset.Free();
+        ray_sample_num.Free(); ray_skipped.Free(); ray_rows.Free(); ray_flags.Free(); ray_out_index.Free(); ray_offset.Free(); slot.Free();
       }
     } store;
   } resident;
@@ -325,6 +351,7 @@ namespace blhost {
 inline void Warn(bl_ctx *ctx, const std::string &message) { ctx->warnings += "Warning: " + message + "\n"; }
 int Fail(bl_ctx *ctx, const Failure &failure);   // sets bl_last_error (or the global error when ctx is null), returns the code
 void EnsureStreams(bl_ctx *ctx);
+void DropResident(bl_ctx *ctx);   // the root level's kept geodesics go (bl_render.hip)
 }  // namespace blhost
 
 #endif  // BLACKLIGHT_AMD_BL_CTX_H_

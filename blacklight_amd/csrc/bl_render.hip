@@ -10,6 +10,7 @@
 #include <sys/stat.h>
 
 #include <thread>
+#include <type_traits>
 
 #include "bl_ctx.h"
 
@@ -172,6 +173,9 @@ struct RenderJob {
   bool keepable = false;      // root level, geodesics integrated here: what this render leaves may serve the next (bl_set_geodesic_reuse)
   bool reuse = false;         // the resident records of an earlier render of this camera are shaded again: no geodesic stage
   bool reuse_located = false; // ... and its located samples: no locate kernel
+  bool reuse_chunks = false;  // ... and they are in the kept layout: the chunks of the render that integrated them, one after another
+  bool kept = false;          // integrating in the kept layout: every chunk's records side by side in a store (bl_ctx::ResidentGeodesics)
+  bool kept_spilled = false;  // ... the store ran out before the last ray: the remaining chunks overwrite it from its start, nothing is kept
   bool raster = false;        // large host outputs (many image rows): rays in pixel order, so that a chunk is a range of columns of
                               // every row and goes to the caller's buffer while the next chunk renders (DownloadChunk)
   bool chunk_downloads = false;   // ... and this call does download chunk by chunk (more than one chunk, or a first chunk that left rays)
@@ -194,6 +198,13 @@ struct RenderJob {
   uint64_t bytes_per_record = 0;
   size_t record_capacity = 0;
   long long record_gate = 0;
+  // kept layout: the chunk being bound - its segment of the store, where its records start there, its capacity and gate
+  // (record_capacity is then the shading arrays' capacity)
+  size_t chunk_base = 0, chunk_capacity = 0;
+  int chunk_segment = 0;
+  long long chunk_gate = 0, kept_least = 0;
+  std::vector<bl_ctx::ResidentGeodesics::Segment> segments;   // kept layout: the store (PlanKeptLayout)
+  std::vector<bl_ctx::ResidentGeodesics::Chunk> kept_chunks;
   int n_slots = 1, geo_grid = 1, geo_waves_per_cu = 1;
   // outputs (device pointers: the caller's, or staging)
   double *image = nullptr, *cam_pos = nullptr, *cam_dir = nullptr, *render_out = nullptr;
@@ -460,15 +471,20 @@ void BuildReuseKeys(RenderJob &job) {
 }
 
 // The root level's buffers and the other levels' change places (bl_ctx::ResidentGeodesics)
+// (kept layout: the whole of scratch set 0 - its shading arrays hold part of the store)
 void SwapResidentBuffers(bl_ctx *ctx) {
   bl_ctx::ResidentGeodesics::Buffers &st = ctx->resident.store;
   bl_ctx::ChunkSlot &sl = ctx->slot[0];
-  std::swap(st.records_hot, sl.d_records_hot);
-  std::swap(st.records_cold, sl.d_records_cold);
-  std::swap(st.sample_t, sl.d_sample_t);
-  std::swap(st.located, sl.d_located);
-  std::swap(st.located_tag, sl.d_located_tag);
-  std::swap(st.anchors, sl.d_anchors);
+  if (!ctx->resident.chunks.empty()) {
+    std::swap(st.slot, sl);
+  } else {
+    std::swap(st.records_hot, sl.d_records_hot);
+    std::swap(st.records_cold, sl.d_records_cold);
+    std::swap(st.sample_t, sl.d_sample_t);
+    std::swap(st.located, sl.d_located);
+    std::swap(st.located_tag, sl.d_located_tag);
+    std::swap(st.anchors, sl.d_anchors);
+  }
   std::swap(st.ray_kt, ctx->d_ray_kt);
   std::swap(st.ray_factor, ctx->d_ray_factor);
   std::swap(st.ray_sample_num, ctx->d_ray_sample_num);
@@ -480,14 +496,21 @@ void SwapResidentBuffers(bl_ctx *ctx) {
   ctx->resident.parked = !ctx->resident.parked;
 }
 
-void DropResident(bl_ctx *ctx) {
+}  // namespace
+
+void blhost::DropResident(bl_ctx *ctx) {
   bl_ctx::ResidentGeodesics &res = ctx->resident;
   if (res.valid && res.parked) {   // the buffers set aside are the root level's: back to the device
     res.store.Free();
     res.parked = false;
   }
+  // (kept layout in place: the store is scratch set 0's own memory, which is scratch again)
   res.valid = res.located_valid = false;
+  res.chunks.clear();
+  res.segments.clear();
 }
+
+namespace {
 
 // Which way this render goes: over the resident records (a root-level render of the same camera left them), or integrating its
 // own - in scratch set 0 as ever, with the resident records of the root level, if any, set aside first
@@ -499,15 +522,27 @@ void DecideReuse(RenderJob &job) {
   job.reuse = job.keepable && job.allow_reuse && res.valid && res.key == job.geo_key;
   if (job.reuse) {
     if (res.parked) SwapResidentBuffers(ctx);
-    job.reuse_located = job.simulation && !job.locate_inside && !job.slow && res.located_valid && res.located_key == job.located_key;
+    job.reuse_chunks = !res.chunks.empty();
+    // (kept layout: the located samples lived in one chunk's arrays and are gone)
+    job.reuse_located = !job.reuse_chunks && job.simulation && !job.locate_inside && !job.slow && res.located_valid && res.located_key == job.located_key;
     job.geo_save = false;   // (the render that integrated them wrote the file: geodesic_checkpoint.cpp is called once per run of the program)
   } else if (res.valid) {
     if (job.keepable) DropResident(ctx);            // another camera: this render's records take their place
     else if (!res.parked) SwapResidentBuffers(ctx);   // another level: it works in buffers of its own
   }
+  // The render after one of this camera that took several chunks and kept nothing: integrated in the kept layout (PlanScratch decides
+  // whether it fits). Not with two scratch sets, nor where a checkpoint is written from the chunks' records.
+  job.kept = job.keepable && !job.reuse && res.pending && res.pending_key == job.geo_key && ctx->overlap_chunks == 0 && !job.geo_save && !job.sample_save;
 }
 
-// After a render that integrated the root level's geodesics in one chunk: what it left is the resident set
+// What the shading stage adds to a chunk's counters: cleared, so that a render over the kept records counts it again
+void ClearShadingCounters(unsigned long long *counters) {
+  for (int c : {BL_CNT_GATHERS, BL_CNT_UNDEFINED, BL_CNT_INTERP_FAILED, BL_CNT_REDO}) counters[c] = 0ull;
+  for (int c = BL_CNT_COUNT; c < BL_CNT_COUNT + 12; c++) counters[c] = 0ull;   // the transfer kernel's statistics, debug counters
+}
+
+// After a render that integrated the root level's geodesics in one chunk, or in the kept layout: what it left is the resident set.
+// After one of several chunks that kept nothing: the pending entry that has the next render of this camera integrate in the kept layout.
 void KeepResident(RenderJob &job) {
   bl_ctx *ctx = job.ctx;
   bl_ctx::ResidentGeodesics &res = ctx->resident;
@@ -515,7 +550,40 @@ void KeepResident(RenderJob &job) {
   const unsigned long long *hc = ctx->host_counters;   // scratch set 0's, as CollectChunk read them
   if (job.keepable && !job.reuse) {
     res.valid = false;
-    if (job.n_chunks != 1 || job.n_slots != 1) return;   // (the chunks overwrote one another's records: recomputed next time)
+    if (job.kept && !job.kept_spilled) {
+      res.valid = true;
+      res.parked = false;
+      res.pending = false;
+      res.key = job.geo_key;
+      res.record_capacity = job.record_capacity;
+      res.segments = job.segments;
+      res.tail_policy = job.park ? BL_TAIL_QUAD : BL_TAIL_WIDE;
+      res.n_parked = job.total_parked;
+      res.n_flagged = job.total_flagged;
+      res.chunks = job.kept_chunks;
+      for (bl_ctx::ResidentGeodesics::Chunk &chunk : res.chunks) ClearShadingCounters(chunk.counters);
+      if (ctx->debug_counters) {
+        unsigned long long store = 0;
+        for (const bl_ctx::ResidentGeodesics::Segment &seg : res.segments) store += seg.capacity;
+        std::fprintf(stderr, "kept layout: %zu chunks, store %llu records in %zu segments, shading arrays %zu records\n", res.chunks.size(), store,
+                     res.segments.size(), res.record_capacity);
+      }
+      res.located_valid = false;   // (located samples live in one chunk's arrays: located again every frame)
+      return;
+    }
+    if (job.n_chunks != 1 || job.n_slots != 1) {   // (the chunks overwrote one another's records: recomputed next time)
+      res.pending = ctx->overlap_chunks == 0 && !job.geo_save && !job.sample_save;
+      if (res.pending) {
+        // (a store that ran short: sized from what this render used, and larger than the last time)
+        const unsigned long long grown = job.kept_spilled ? res.pending_records + res.pending_records / 8 : 0ull;
+        res.pending_key = job.geo_key;
+        res.pending_records = std::max<unsigned long long>(job.total_records, grown);
+      }
+      return;
+    }
+    res.pending = false;
+    res.chunks.clear();
+    res.segments.clear();
     res.valid = true;
     res.parked = false;
     res.key = job.geo_key;
@@ -524,7 +592,7 @@ void KeepResident(RenderJob &job) {
     res.n_parked = job.total_parked;
     res.n_flagged = job.total_flagged;
     std::memcpy(res.counters, hc, sizeof res.counters);
-  } else if (!(job.reuse && located_here && !job.reuse_located)) {
+  } else if (!(job.reuse && !job.reuse_chunks && located_here && !job.reuse_located)) {
     return;
   }
   // (here: a render that integrated the geodesics, or one that located the resident samples on a new geometry)
@@ -533,6 +601,163 @@ void KeepResident(RenderJob &job) {
   for (int c : {BL_CNT_GATHERS, BL_CNT_UNDEFINED, BL_CNT_INTERP_FAILED}) res.counters[c] = located_here ? hc[c] : 0ull;
   res.counters[BL_CNT_REDO] = 0ull;
   for (int c = BL_CNT_COUNT; c < BL_CNT_COUNT + 12; c++) res.counters[c] = 0ull;   // the transfer kernel's statistics, debug counters
+}
+
+// ---- kept layout (DecideReuse: the render after one of this camera that took several chunks). Scratch set 0 as the earlier render
+// allocated it is re-partitioned - nothing is freed or allocated: its shading arrays take one chunk's `record_capacity` entries, and the
+// store that takes every chunk's records is a list of segments, the record arrays and the tails of the shading arrays beyond those
+// entries. The earlier render filled the same memory, so the scratch cap holds as it did then. The store has to hold:
+//   - the records the earlier render used (ResidentGeodesics::pending_records: emitted records and the partly filled blocks of its chunks);
+//   - the reservations of the rays in flight when the last chunk starts: ray_max_steps for every lane of the stepper's grid;
+//   - a block of BL_RECORD_BLOCK per wave for every chunk (the part of each wave's last block the stepper leaves unfilled), and at the end
+//     of every segment what is too little for one more chunk.
+// Chunk c's records go to its segment + base_c, its gate is the smaller of the shading arrays' capacity and what is left of the segment,
+// less a block per wave (PlaceKeptChunk, BindChunk): the stepper's reservations keep what it allocates under both, so neither can be
+// overrun. A chunk starts in the next segment where what is left of this one cannot take the grid's first fill (a gate below that closes
+// at once, a few rays long). Where no segment is left for a chunk, the kept layout ends for the render (kept_spilled: the rest overwrite segment 0 from its
+// start, as every multi-chunk render did before; nothing is kept). The stepper's grid is held to lanes whose reservations are at most an
+// sixteenth of the records: it runs in this render only, and a smaller in-flight reservation is a smaller store. False where no partition
+// of what scratch set 0 holds gives the store beside a shading set that takes the grid's first fill within 16 chunks: the render is
+// planned as any other.
+bool PlanKeptLayout(RenderJob &job, long long max_grid, long long quad_waves, int waves_per_cu) {
+  using Segment = bl_ctx::ResidentGeodesics::Segment;
+  bl_ctx *ctx = job.ctx;
+  bl_ctx::ChunkSlot &sl = ctx->slot[0];
+  const size_t n_nu = static_cast<size_t>(job.n_nu);
+  const uint64_t record_bytes = sizeof(BlSampleHot) + sizeof(BlSampleCold) + (job.need_time ? sizeof(double) : 0);
+  // the record arrays as they are (segment 0)
+  Segment first;
+  first.hot = sl.d_records_hot.ptr;
+  first.cold = job.interleaved ? nullptr : sl.d_records_cold.ptr;
+  first.sample_t = job.need_time ? sl.d_sample_t.ptr : nullptr;
+  first.capacity = job.interleaved ? sl.d_records_hot.count / 2 : std::min(sl.d_records_hot.count, sl.d_records_cold.count);
+  if (job.need_time) first.capacity = std::min(first.capacity, sl.d_sample_t.count);
+  // the shading arrays this render uses (EnsureScratchOnce): where they start, their bytes, their bytes per record
+  struct Part {
+    unsigned char *base;
+    uint64_t bytes, per_record;
+  };
+  std::vector<Part> parts;
+  uint64_t shading_cap = std::numeric_limits<uint64_t>::max();
+  auto use = [&](auto &buffer, size_t per_record) {
+    using T = std::remove_reference_t<decltype(*buffer.ptr)>;
+    parts.push_back({reinterpret_cast<unsigned char *>(buffer.ptr), buffer.count * sizeof(T), per_record * sizeof(T)});
+    shading_cap = std::min<uint64_t>(shading_cap, buffer.count / per_record);
+  };
+  if (job.simulation && !job.locate_inside) { use(sl.d_located, 1); use(sl.d_located_tag, 1); }
+  if (job.freq_split) use(sl.d_freq_inputs, 1);
+  else if (!ctx->polarized) use(sl.d_transfer, n_nu);
+  if (job.composed) use(sl.d_composed, 1);
+  if (job.tau_row) use(sl.d_tau_inc, n_nu);
+  if (job.aux && !job.rows_only) use(sl.d_aux, 1);
+  if (job.slow) use(sl.d_slow_frac, 1);
+  if (ctx->polarized) {
+    use(sl.d_pol_samples, 1);
+    if (job.matrix_transport) use(sl.d_pol_matrix, BL_POL_MATRIX_DOUBLES);
+    use(sl.d_pol_coeffs, n_nu * 4);
+    use(sl.d_coef_inputs, 1);
+    if (job.pol_coefficients_inside) use(sl.d_have_flags, 1);
+  }
+  if (job.coef_split) use(sl.d_coef_inputs, 1);
+  if (job.block_interp && !job.locate_inside) use(sl.d_anchors, 8);
+  shading_cap = std::min<uint64_t>(shading_cap, (1ull << 32) - (1ull << 22));   // (32-bit indices: PlanScratch)
+
+  const uint64_t records = ctx->resident.pending_records;
+  const uint64_t steps = static_cast<uint64_t>(job.max_steps);
+  const uint64_t per_wave = BL_RECORD_BLOCK + 64ull * steps;
+  const long long grid = std::max<long long>(1, std::min<long long>(max_grid, static_cast<long long>(records / 16 / (64ull * steps))));
+  const uint64_t in_flight = static_cast<uint64_t>(grid) * 64ull * steps;
+  const uint64_t blocks = static_cast<uint64_t>(grid + quad_waves) * BL_RECORD_BLOCK;
+  const uint64_t least = static_cast<uint64_t>(grid) * per_wave + static_cast<uint64_t>(quad_waves) * BL_RECORD_BLOCK;   // the grid's first fill
+  // (a chunk whose gate cannot take the grid's first fill closes at once, a few rays long: the rest of a segment below that is left
+  // unused - PlaceKeptChunk - and a segment smaller than that is no segment)
+  const uint64_t useful = least;
+  if (first.hot == nullptr || first.capacity < least || shading_cap == std::numeric_limits<uint64_t>::max() || shading_cap < least) return false;
+  // the segments with the shading arrays at `shading` entries (a multiple of 64: every tail starts 64-byte aligned)
+  auto segments_for = [&](uint64_t shading) {
+    std::vector<Segment> out{first};
+    for (const Part &part : parts) {
+      const uint64_t offset = shading * part.per_record;
+      const uint64_t n = part.bytes > offset ? (part.bytes - offset) / record_bytes : 0;
+      if (n < useful) continue;
+      Segment seg;
+      unsigned char *at = part.base + offset;
+      seg.hot = reinterpret_cast<BlSampleHot *>(at);
+      seg.cold = job.interleaved ? nullptr : reinterpret_cast<BlSampleCold *>(at + n * sizeof(BlSampleHot));
+      seg.sample_t = job.need_time ? reinterpret_cast<double *>(at + n * (sizeof(BlSampleHot) + sizeof(BlSampleCold))) : nullptr;
+      seg.capacity = static_cast<size_t>(n);
+      out.push_back(seg);
+    }
+    return out;
+  };
+  auto room = [&](const std::vector<Segment> &segs) {   // records the segments take, less what the end of each may leave unused
+    uint64_t total = 0;
+    for (const Segment &seg : segs) total += seg.capacity - std::min<uint64_t>(seg.capacity, useful);
+    return total;
+  };
+  for (uint64_t n_chunks = 2; n_chunks <= 16; n_chunks++) {
+    // the largest shading capacity whose segments hold the store (fewer entries: longer tails)
+    uint64_t lo = least, hi = shading_cap & ~63ull;
+    if (hi < lo) return false;
+    auto need = [&](const std::vector<Segment> &segs) { return records + in_flight + (n_chunks + 1 + segs.size()) * blocks; };
+    if (room(segments_for(lo)) < need(segments_for(lo))) return false;
+    while (hi - lo > 64) {
+      const uint64_t mid = ((lo + hi) / 2) & ~63ull;
+      const std::vector<Segment> segs = segments_for(mid);
+      if (room(segs) >= need(segs)) lo = mid;
+      else hi = mid;
+    }
+    {
+      const std::vector<Segment> segs = segments_for(hi);
+      if (room(segs) >= need(segs)) lo = hi;
+    }
+    const uint64_t shading = lo;
+    // (a chunk closes its gate with the reservations of its rays in flight counted: it allocates at least its gate less those; a
+    // segment's end can cut one chunk short)
+    const std::vector<Segment> segs = segments_for(shading);
+    const uint64_t per_chunk = shading - blocks - in_flight;
+    if (per_chunk == 0 || (records + per_chunk - 1) / per_chunk + segs.size() - 1 > n_chunks) continue;
+    job.n_slots = 1;
+    job.segments = segs;
+    job.record_capacity = static_cast<size_t>(shading);
+    job.record_gate = static_cast<long long>(shading - blocks);
+    job.chunk_capacity = job.record_capacity;
+    job.chunk_gate = job.record_gate;
+    job.geo_grid = static_cast<int>(grid);
+    job.geo_waves_per_cu = waves_per_cu;
+    job.quad_grid = static_cast<int>(quad_waves);
+    job.park_capacity = job.park ? ((ctx->switches & BL_SWITCH_QUAD_EVERY_RAY) ? static_cast<size_t>(job.n_rays) : static_cast<size_t>(grid) * 64) : 0;
+    job.split_long = false;   // (planned for calls one chunk is sure to take)
+    job.kept_least = static_cast<long long>(least);
+    return true;
+  }
+  return false;
+}
+
+// Where the next chunk of a kept-layout render goes: segment `segment` from `base` on, or the next segment with room for a ray
+void PlaceKeptChunk(RenderJob &job, int segment, size_t base) {
+  const long long blocks = static_cast<long long>(job.geo_grid + job.quad_grid) * BL_RECORD_BLOCK;
+  while (!job.kept_spilled) {
+    if (segment >= static_cast<int>(job.segments.size())) {
+      job.kept_spilled = true;   // the store is full: this chunk and the rest overwrite segment 0 from the start, as without the kept layout
+      break;
+    }
+    const size_t capacity = job.segments[segment].capacity;
+    const size_t cap = std::min(job.record_capacity, capacity - std::min(base, capacity));
+    if (static_cast<long long>(cap) >= job.kept_least) {   // (the grid's first fill: PlanKeptLayout)
+      job.chunk_segment = segment;
+      job.chunk_base = base;
+      job.chunk_capacity = cap;
+      job.chunk_gate = static_cast<long long>(cap) - blocks;
+      return;
+    }
+    segment++;
+    base = 0;
+  }
+  job.chunk_segment = 0;
+  job.chunk_base = 0;
+  job.chunk_capacity = std::min(job.record_capacity, job.segments[0].capacity);
+  job.chunk_gate = static_cast<long long>(job.chunk_capacity) - blocks;
 }
 
 // ---- scratch: what a sample record costs, how many fit, how many persistent waves trace rays into them
@@ -556,6 +781,9 @@ void PlanScratch(RenderJob &job) {
     job.n_slots = 1;
     job.record_capacity = ctx->resident.record_capacity;
     job.record_gate = static_cast<long long>(job.record_capacity);
+    if (job.reuse_chunks) job.segments = ctx->resident.segments;
+    job.chunk_capacity = job.record_capacity;
+    job.chunk_gate = job.record_gate;
     job.geo_grid = 1;
     job.park = job.split_long = false;
     job.park_capacity = 0;
@@ -589,6 +817,8 @@ void PlanScratch(RenderJob &job) {
       : (job.split_long ? 64ll * 4 : 0);   // (split: at most 64 compute units, sized below)
   const uint64_t worst_case = static_cast<uint64_t>(job.n_rays) * job.max_steps + static_cast<uint64_t>(max_grid + quad_waves) * BL_RECORD_BLOCK;
   const uint64_t fixed = per_ray * static_cast<uint64_t>(job.n_rays);
+  if (job.kept && PlanKeptLayout(job, max_grid, quad_waves, waves_per_cu)) return;
+  job.kept = false;   // (it does not fit: planned as any render, nothing kept)
   auto capacity_for = [&](int n_slots) -> uint64_t {
     const uint64_t overhead = fixed + n_slots * per_slot_fixed;
     if (budget <= overhead) return 0;
@@ -617,6 +847,8 @@ void PlanScratch(RenderJob &job) {
     throw Failure{BL_E_ARG, "Scratch budget too small: the sample records of a single ray (ray_max_steps of them) do not fit (bl_set_scratch_limit)."};
   job.record_capacity = static_cast<size_t>(capacity);
   job.record_gate = gate;
+  job.chunk_capacity = job.record_capacity;
+  job.chunk_gate = gate;
   job.geo_grid = static_cast<int>(grid);
   job.geo_waves_per_cu = waves_per_cu;
   job.quad_grid = static_cast<int>(quad_waves);
@@ -685,9 +917,13 @@ void EnsureScratchOnce(RenderJob &job) {
   bl_ctx *ctx = job.ctx;
   const size_t cap = job.record_capacity;
   const size_t n_nu = static_cast<size_t>(job.n_nu);
+  // kept layout: the record arrays and the tails of the others are the store, left as they are (PlanKeptLayout planned within what
+  // scratch set 0 holds: none of the arrays below grows)
+  const bool store = job.kept || job.reuse_chunks;
   for (int k = 0; k < job.n_slots; k++) {
     bl_ctx::ChunkSlot &sl = ctx->slot[k];
-    if (job.interleaved) {
+    if (store) {
+    } else if (job.interleaved) {
       sl.d_records_hot.Ensure(2 * cap);
     } else {
       sl.d_records_hot.Ensure(cap);
@@ -704,7 +940,7 @@ void EnsureScratchOnce(RenderJob &job) {
     if (job.tau_row) sl.d_tau_inc.Ensure(cap * n_nu);
     sl.d_counters.Ensure(BL_CNT_TOTAL);
     if (job.aux && !job.rows_only) sl.d_aux.Ensure(cap);   // (rows_only: nobody writes or reads the 96-byte records)
-    if (job.need_time) sl.d_sample_t.Ensure(cap);
+    if (job.need_time && !store) sl.d_sample_t.Ensure(cap);
     if (job.slow) sl.d_slow_frac.Ensure(cap);
     if (ctx->polarized) {
       sl.d_pol_samples.Ensure(cap);
@@ -886,8 +1122,6 @@ void BuildTraceArgs(RenderJob &job) {
   }
   ta.pixel_map = job.d_pixel_map;
   ta.block_locs = job.d_block_locs;
-  ta.record_capacity = static_cast<long long>(job.record_capacity);
-  ta.record_gate = job.record_gate;
   ta.camera_pos = job.cam_pos;
   ta.camera_dir = job.cam_dir;
   ta.ray_start_stride = job.n_rays;
@@ -1223,10 +1457,22 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   // The halves of a sample record (position + id | momentum + length): side by side in one array where every reader wants both
   // (the fused tolerant kernel: 64 contiguous bytes per lane for the geodesic kernel's scattered stores), in two arrays where
   // the locate kernel reads positions only
-  ta.records_hot = sl.d_records_hot.ptr;
-  ta.records_cold = job.interleaved ? reinterpret_cast<BlSampleCold *>(sl.d_records_hot.ptr + 1) : sl.d_records_cold.ptr;
+  // (kept layout: the chunk's records start at chunk_base in the store; every index the kernels see - record slots, ray_offset rows,
+  // counters - stays relative to the chunk, so the shading arrays are the same one-chunk arrays for every chunk)
   ta.record_stride = job.interleaved ? 2 : 1;
-  ta.sample_t = job.need_time ? sl.d_sample_t.ptr : nullptr;
+  if (job.kept || job.reuse_chunks) {
+    const bl_ctx::ResidentGeodesics::Segment &seg = job.segments[job.chunk_segment];
+    const size_t base = job.chunk_base;
+    ta.records_hot = seg.hot + base * ta.record_stride;
+    ta.records_cold = job.interleaved ? reinterpret_cast<BlSampleCold *>(ta.records_hot + 1) : seg.cold + base;
+    ta.sample_t = job.need_time ? seg.sample_t + base : nullptr;
+  } else {
+    ta.records_hot = sl.d_records_hot.ptr;
+    ta.records_cold = job.interleaved ? reinterpret_cast<BlSampleCold *>(sl.d_records_hot.ptr + 1) : sl.d_records_cold.ptr;
+    ta.sample_t = job.need_time ? sl.d_sample_t.ptr : nullptr;
+  }
+  ta.record_capacity = static_cast<long long>(job.chunk_capacity);
+  ta.record_gate = job.chunk_gate;
   ta.counters = sl.d_counters.ptr;
   ta.ray_kt = ctx->d_ray_kt.ptr + begin;
   ta.ray_factor = ctx->d_ray_factor.ptr + begin;
@@ -1503,7 +1749,7 @@ void SaveChunkSampling(RenderJob &job, int k, long long begin, int rays) {
   std::vector<unsigned char> ray_flags(rays);
   std::vector<long long> ray_out(rays);
   if (n_written > 0) {
-    Check(hipMemcpy(hot.data(), sl.d_records_hot.ptr, hot.size() * sizeof(BlSampleHot), hipMemcpyDeviceToHost), "checkpoint download");
+    Check(hipMemcpy(hot.data(), job.ta.records_hot, hot.size() * sizeof(BlSampleHot), hipMemcpyDeviceToHost), "checkpoint download");
     Check(hipMemcpy(located.data(), sl.d_located.ptr, n_written * sizeof(BlLocated), hipMemcpyDeviceToHost), "checkpoint download");
     if (!job.fast) Check(hipMemcpy(tags.data(), sl.d_located_tag.ptr, n_written * sizeof(unsigned long long), hipMemcpyDeviceToHost), "checkpoint download");
     if (job.block_interp) Check(hipMemcpy(anchors.data(), sl.d_anchors.ptr, anchors.size() * sizeof(unsigned int), hipMemcpyDeviceToHost), "checkpoint download");
@@ -1774,6 +2020,16 @@ void CollectChunk(RenderJob &job, int k) {
 void DownloadChunk(RenderJob &job, long long begin, long long count);
 hipError_t DownloadColumns(const RenderJob &job, long long begin, long long count, int threads);
 
+// A chunk of the rays [begin, begin + done) is complete (CollectChunk has waited for its kernels): large host outputs leave now
+void ChunkOutputs(RenderJob &job, long long begin, long long done) {
+  if (job.raster && job.n_slots == 1 && (job.chunk_downloads || begin + done < job.n_rays) && job.download_status.size() < 4000) {
+    job.chunk_downloads = true;
+    DownloadChunk(job, begin, done);
+  } else if (job.chunk_downloads) {
+    Check(DownloadColumns(job, begin, done, 1), "download of a chunk's outputs");
+  }
+}
+
 // ---- all chunks of the call
 void RunChunks(RenderJob &job) {
   bl_ctx *ctx = job.ctx;
@@ -1786,28 +2042,44 @@ void RunChunks(RenderJob &job) {
   if (job.reuse) {
     // Shade the resident records again: the per-ray rows and the records are where the stepper left them; the counters go back to
     // what they were when it ended (and when the locate kernel ended, if its samples are kept too). The caller's camera_pos /
-    // camera_dir - a pure function of the pixel - are written again by the kernel that wrote them then.
+    // camera_dir - a pure function of the pixel - are written again by the kernel that wrote them then. Kept layout: chunk by chunk,
+    // each at its place in the store with its own counters, through the one-chunk shading arrays.
     bl_ctx::ChunkSlot &sl = ctx->slot[0];
+    const bl_ctx::ResidentGeodesics &res = ctx->resident;
     hipEvent_t *e = SlotEvents(job, 0);
+    job.chunk_segment = 0;
+    job.chunk_base = 0;
     BindChunk(job, 0, 0, static_cast<int>(job.n_rays));
     if (job.cam_pos != nullptr || job.cam_dir != nullptr) Check(bl_launch_ray_init(&job.ta, ctx->params.ray_integrator, stream), "ray start kernel launch");
-    unsigned long long *staged = ctx->host_counters + BL_CNT_TOTAL;   // (pinned; the second set's half: a reuse render has one set)
-    std::memcpy(staged, ctx->resident.counters, BL_CNT_TOTAL * sizeof(unsigned long long));
-    if (!job.reuse_located)
-      for (int c : {BL_CNT_GATHERS, BL_CNT_UNDEFINED, BL_CNT_INTERP_FAILED}) staged[c] = 0ull;
-    Check(hipMemcpyAsync(sl.d_counters.ptr, staged, BL_CNT_TOTAL * sizeof(unsigned long long), hipMemcpyHostToDevice, stream), "counter upload");
-    Check(hipEventRecord(e[0], stream), "event");
-    Check(hipEventRecord(e[1], stream), "event");
-    job.in_flight[0].busy = true;
-    job.in_flight[0].begin = 0;
-    job.in_flight[0].rays = static_cast<int>(job.n_rays);
-    job.in_flight[0].done = job.n_rays;
-    LaunchShadingStage(job, 0, false, stream);
-    if (job.sample_save) {
-      Check(hipStreamSynchronize(stream), "kernel execution");
-      SaveChunkSampling(job, 0, 0, static_cast<int>(job.n_rays));
+    const size_t n_kept = job.reuse_chunks ? res.chunks.size() : 1;
+    for (size_t c = 0; c < n_kept; c++) {
+      const long long begin = job.reuse_chunks ? res.chunks[c].begin : 0;
+      const int rays = static_cast<int>(job.n_rays - begin);
+      const unsigned long long *counters = job.reuse_chunks ? res.chunks[c].counters : res.counters;
+      job.chunk_segment = job.reuse_chunks ? res.chunks[c].segment : 0;
+      job.chunk_base = job.reuse_chunks ? res.chunks[c].record_base : 0;
+      // (pinned; the second set's half: a reuse render has one set. The previous chunk's upload from it has completed: CollectChunk below.)
+      unsigned long long *staged = ctx->host_counters + BL_CNT_TOTAL;
+      std::memcpy(staged, counters, BL_CNT_TOTAL * sizeof(unsigned long long));
+      if (!job.reuse_located)
+        for (int n : {BL_CNT_GATHERS, BL_CNT_UNDEFINED, BL_CNT_INTERP_FAILED}) staged[n] = 0ull;
+      Check(hipMemcpyAsync(sl.d_counters.ptr, staged, BL_CNT_TOTAL * sizeof(unsigned long long), hipMemcpyHostToDevice, stream), "counter upload");
+      Check(hipEventRecord(e[0], stream), "event");
+      Check(hipEventRecord(e[1], stream), "event");
+      job.in_flight[0].busy = true;
+      job.in_flight[0].begin = begin;
+      job.in_flight[0].rays = rays;
+      job.in_flight[0].done = job.reuse_chunks ? static_cast<long long>(std::min<unsigned long long>(counters[BL_CNT_NEXT_RAY], static_cast<unsigned long long>(rays)))
+                                               : job.n_rays;
+      const long long done = job.in_flight[0].done;
+      LaunchShadingStage(job, 0, false, stream);
+      if (job.sample_save) {
+        Check(hipStreamSynchronize(stream), "kernel execution");
+        SaveChunkSampling(job, 0, begin, static_cast<int>(done));
+      }
+      CollectChunk(job, 0);
+      ChunkOutputs(job, begin, done);
     }
-    CollectChunk(job, 0);
     Check(hipEventRecord(ev_end, stream), "event");
     Check(hipStreamSynchronize(stream), "kernel execution");
     return;
@@ -1822,10 +2094,13 @@ void RunChunks(RenderJob &job) {
     return Failure{BL_E_ARG, "Scratch budget too small: no ray fits the sample record buffers (bl_set_scratch_limit)."};
   };
   long long begin = 0;
+  int kept_segment = 0;   // kept layout: where the next chunk's records start in the store
+  size_t kept_base = 0;
   for (int c = 0; begin < n_rays; c++) {
     const int k = c % job.n_slots;
     const int rays = static_cast<int>(n_rays - begin);
     CollectChunk(job, k);   // the chunk that used this scratch set before (two chunks back when there are two sets)
+    if (job.kept) PlaceKeptChunk(job, kept_segment, kept_base);
     LaunchGeodesicStage(job, k, begin, rays, stream_geo);
     long long done;
     if (job.n_slots == 2) {
@@ -1843,18 +2118,23 @@ void RunChunks(RenderJob &job) {
       if (job.sample_save) SaveChunkSampling(job, k, begin, static_cast<int>(WaitGeodesicStage(job, k, stream_geo)));
       CollectChunk(job, k);
       done = job.in_flight[k].done;
+      if (job.kept && !job.kept_spilled) {   // (one scratch set: the counters CollectChunk read are this chunk's as its kernels left them)
+        bl_ctx::ResidentGeodesics::Chunk chunk;
+        chunk.begin = begin;
+        chunk.segment = job.chunk_segment;
+        chunk.record_base = job.chunk_base;
+        std::memcpy(chunk.counters, ctx->host_counters, sizeof chunk.counters);
+        job.kept_chunks.push_back(chunk);
+        kept_segment = job.chunk_segment;
+        kept_base = job.chunk_base + static_cast<size_t>(ctx->host_counters[BL_CNT_RECORDS]);
+      }
     }
     if (done <= 0) throw no_progress();
     // (the split is planned for calls one chunk is sure to take - PlanScratch - but the band's reservations are counted twice for a
     // moment, and a frame whose rays all use every step they may can see the gate close on that: the marked rays of a second chunk
     // would be lost. Rendered again with one stepper instead.)
     if (job.split_long && done < rays) throw SplitIncomplete{};
-    if (job.raster && job.n_slots == 1 && (job.chunk_downloads || begin + done < n_rays) && job.download_status.size() < 4000) {
-      job.chunk_downloads = true;
-      DownloadChunk(job, begin, done);   // (the chunk is complete: CollectChunk has waited for its kernels)
-    } else if (job.chunk_downloads) {
-      Check(DownloadColumns(job, begin, done, 1), "download of a chunk's outputs");
-    }
+    ChunkOutputs(job, begin, done);
     begin += done;
   }
   const int oldest = job.n_chunks % job.n_slots;   // chunks are collected in order: the next one to collect sits on this set

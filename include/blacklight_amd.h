@@ -419,7 +419,13 @@ BL_API int bl_set_caller_stream(bl_ctx *ctx, void *stream, int enabled);
  * (blacklight.cpp:93-94 against :178-250), and - while the mesh does not change and slow light is off - locates the samples on the
  * grid once (`first_time`, radiation_integrator.cpp:693-704); per snapshot it only reads the cells, evaluates the coefficients and
  * integrates. on != 0 (default): a root-level bl_render whose rays fit one chunk leaves its sample records (64 B per sample: 48 GB
- * for the 1024^2 benchmark camera) and per-ray rows in HBM; the next root-level bl_render of this context with the SAME camera -
+ * for the 1024^2 benchmark camera) and per-ray rows in HBM. A frame of more than one chunk (a 1024^2 full-Stokes frame, 64 frequencies,
+ * 2048^2) keeps nothing the first time; the next render of that camera integrates again, with the scratch it already holds
+ * re-partitioned (nothing allocated) into a record store for the whole frame beside shading arrays for one chunk, and the renders after
+ * it shade the kept chunks one after another (bl_stats.n_chunks as that render had them) - reuse from the third frame on. Where no such
+ * partition holds the frame's records, the frames integrate as before. Not kept there: located samples (located again every frame), anything under
+ * bl_set_overlap(1), and no render that writes a geodesic or sample checkpoint integrates into the store. The next root-level
+ * bl_render of this context with the SAME camera -
  * same parameters, pixel map, record layout, tail policy - after a new bl_set_grid / bl_slow_light_read shades those records again
  * instead of launching the stepper (bl_stats.geodesics_reused = 1, launches_geodesic = 0), and where a locate kernel of its own
  * ran, skips that too when the grid's geometry is bit for bit the one it located the samples on (bl_stats.sampling_reused).
