@@ -109,6 +109,8 @@ def lib():
     L.bl_set_reproducible.argtypes = [C.c_void_p, C.c_int]
     L.bl_set_tail_policy.argtypes = [C.c_void_p, C.c_int]
     L.bl_set_geodesic_reuse.argtypes = [C.c_void_p, C.c_int]
+    L.bl_set_electron_models.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.bl_num_electron_models.argtypes = [C.c_void_p]
     L.bl_host_alloc.argtypes = [C.c_void_p, C.c_size_t]
     L.bl_host_alloc.restype = C.c_void_p
     L.bl_host_free.argtypes = [C.c_void_p, C.c_void_p]

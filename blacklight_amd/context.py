@@ -124,6 +124,27 @@ class Context:
         not kept."""
         self._check(self._lib.bl_set_geodesic_reuse(self._ctx, 1 if on else 0))
 
+    def set_electron_models(self, rat_high, rat_low=1.0):
+        """Render several electron-temperature models (R_high / R_low pairs) in one render (bl_set_electron_models). Scalars or
+        sequences, broadcast against each other; an empty sequence clears them (the parameter block's pair again). The image then
+        holds the models one after another (render()["image_by_model"]: (n_models, n_q, n_rays)); geodesics stay resident."""
+        high, low = np.broadcast_arrays(np.atleast_1d(np.asarray(rat_high, dtype=np.float64)),
+                                        np.atleast_1d(np.asarray(rat_low, dtype=np.float64)))
+        high = np.ascontiguousarray(high)
+        low = np.ascontiguousarray(low)
+        self._check(self._lib.bl_set_electron_models(self._ctx, int(high.size), low.ctypes.data_as(C.c_void_p),
+                                                     high.ctypes.data_as(C.c_void_p)))
+        self._electron_models = [(float(h), float(lo)) for h, lo in zip(high, low)]
+
+    @property
+    def electron_models(self):
+        """The (rat_high, rat_low) pairs set_electron_models() set; [] when the parameter block's pair is rendered."""
+        return list(getattr(self, "_electron_models", []))
+
+    @property
+    def num_electron_models(self):
+        return self._lib.bl_num_electron_models(self._ctx)
+
     def set_caller_stream(self, stream=None, enabled=True):
         """Every later render starts behind the work queued so far on `stream` (a raw hipStream_t handle, e.g.
         torch.cuda.current_stream().cuda_stream; None / 0: the NULL stream) - bl_set_caller_stream."""
@@ -244,8 +265,9 @@ class Context:
             rendering = np.empty((n_render, 3, n_rays))
             d.render = rendering.ctypes.data_as(C.c_void_p)
         self._check(self._lib.bl_render(self._ctx, C.byref(d)))
-        return dict(image=image, sample_num=sample_num, sample_flags=sample_flags,
-                    camera_pos=camera_pos, camera_dir=camera_dir, rendering=rendering, stats=self.stats)
+        n_models = max(1, self.num_electron_models)
+        return dict(image=image, image_by_model=image.reshape(n_models, n_q // n_models, n_rays), sample_num=sample_num,
+                    sample_flags=sample_flags, camera_pos=camera_pos, camera_dir=camera_dir, rendering=rendering, stats=self.stats)
 
     # ------------------------------------------------------------------ host steps of the reference loop
     def adaptive_refine(self, level, image, block_locs=None):

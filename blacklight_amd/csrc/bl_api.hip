@@ -335,6 +335,28 @@ int Fail(bl_ctx *ctx, const Failure &failure) {
     g_global_error = text;
   return failure.code;
 }
+
+// Why n electron models cannot be rendered by this context (nullptr: they can). bl_set_electron_models and bl_render's plan both ask.
+const char *ElectronModelsRefusal(const bl_ctx *ctx, int n) {
+  const bl_params &p = ctx->params;
+  if (n <= 0) return nullptr;
+  if (p.model_type != BL_MODEL_SIMULATION) return "Electron models: formula mode has no electron temperature (model_type = formula).";
+  if (ctx->polarized) return "Electron models: polarized runs render one electron model (image_polarization = true).";
+  if (p.plasma_model == BL_PLASMA_CODE_KAPPA) return "Electron models: plasma_model = code_kappa takes the electron temperature from the grid, not from R_high / R_low.";
+  if (p.slow_light_on) return "Electron models: slow light renders one electron model (slow_light_on = true).";
+  if (n >= 2 && p.adaptive_max_level > 0)
+    return "Electron models: adaptive refinement reads one image; n >= 2 models need adaptive_max_level = 0.";
+  if (n >= 2 && ctx->render_num_images > 0) {   // (renderings come out once: only those no model enters)
+    bool theta_e = p.cut_theta_e_min >= 0.0 || p.cut_theta_e_max >= 0.0;
+    for (int i = 0; i < ctx->render_num_images; i++)
+      for (int f = 0; f < p.render_num_features[i]; f++)
+        if (p.render_quantity[i][f] == 3) theta_e = true;
+    if (theta_e)
+      return "Electron models: a rendering that reads Theta_e, or a Theta_e cut beside renderings, differs between models; n >= 2 "
+             "models render renderings that no model enters only.";
+  }
+  return nullptr;
+}
 }  // namespace blhost
 
 extern "C" {
@@ -1079,7 +1101,26 @@ int bl_set_snapshot(bl_ctx *ctx, int snapshot) {
 
 int bl_render_num_images(const bl_ctx *ctx) { return ctx != nullptr ? ctx->render_num_images : 0; }
 
-int bl_image_num_quantities(const bl_ctx *ctx) { return ctx != nullptr ? ctx->image_num_quantities : -1; }
+int bl_image_num_quantities(const bl_ctx *ctx) {
+  if (ctx == nullptr) return -1;
+  return ctx->image_num_quantities * std::max<int>(1, static_cast<int>(ctx->model_rat_low.size()));
+}
+
+int bl_set_electron_models(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high) {
+  if (ctx == nullptr) return BL_E_ARG;
+  if (n < 0 || n > BL_MAX_ELECTRON_MODELS || (n > 0 && (rat_low == nullptr || rat_high == nullptr)))
+    return Fail(ctx, Failure{BL_E_ARG, "bl_set_electron_models needs 0 <= n <= " + std::to_string(BL_MAX_ELECTRON_MODELS) + " and both ratio arrays."});
+  for (int m = 0; m < n; m++)
+    if (!std::isfinite(rat_low[m]) || !std::isfinite(rat_high[m]))
+      return Fail(ctx, Failure{BL_E_ARG, "bl_set_electron_models: model " + std::to_string(m) + " has a ratio that is not finite."});
+  if (const char *why = ElectronModelsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
+  std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: they do not depend on the model)
+  ctx->model_rat_low.assign(rat_low, rat_low + n);
+  ctx->model_rat_high.assign(rat_high, rat_high + n);
+  return BL_OK;
+}
+
+int bl_num_electron_models(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->model_rat_low.size()) : -1; }
 
 int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out) {
   if (ctx == nullptr || out == nullptr) return BL_E_ARG;

@@ -368,6 +368,10 @@ struct alignas(16) BlFreqInputs {
   double s_length;              // delta lambda in cm at unit frequency
   double pad;
 };
+// ... and with several electron models in one pass (BlShadeArgs::freq_split = 2, BlTransferArgs::n_models): the same 64 bytes hold
+// what no model enters - (flag, x at unit frequency and unit 1 / (k T_e)), (h s_nu, s_j), (s_length, 1 / beta^2), (K0 p / rho, 0) -
+// and bl_transfer_freq_kernel forms each model's 1 / (k T_e) = (K1_m + K2_m / beta^2 + K3 d) / (K0 (p / rho) d), d = 1 + 1 / beta^2.
+#define BL_TRANSFER_MAX_MODELS 16
 
 // Polarized runs: what the per-frequency coefficient formulas need of a sample (simulation_coefficients.cpp:458-698),
 // left by the coefficient kernel for bl_polarized_coefficients_kernel, one per sample record. 64 bytes.
@@ -408,7 +412,8 @@ struct BlShadeArgs {
   unsigned long long *located_tag;   // [record capacity]: cell | status << 32 | time slice << 40
   BlFreqInputs *freq_inputs;         // [sample row] when freq_split
   int coef_split;                    // exact tier, plain images, n_nu >= 4: BlCoefInputs for bl_coefficients_freq_kernel instead of the frequency loop
-  int freq_split;                    // tolerant tier, n_nu >= 4: per-sample factors instead of per-frequency transfer records
+  int freq_split;                    // tolerant tier, n_nu >= 4: per-sample factors instead of per-frequency transfer records;
+                                     // 2: electron models in one pass - the factors' model-free layout (BlFreqInputs)
   int tag_in_record;                 // tolerant tier: the tag is written into BlLocated::ph instead (32 bytes per sample, one stream)
   int lds_table_bytes;        // size of the coordinate tables the locate kernel stages in LDS; 0: searched in HBM
   int samples_renormalised;   // records come from a geodesic checkpoint: momenta as stored, no renormalisation per sample
@@ -486,6 +491,8 @@ struct BlTransferArgs {
   const double2 *composed;    // composed transfer maps (BlShadeArgs::composed): [ray_offset + segment], ray_rows[ray] of them per ray; `transfer` by record
   const int *ray_rows;
   const BlFreqInputs *freq_inputs;            // bl_transfer_freq_kernel
+  int n_models;                               // ... > 0: electron models in one pass, one lane per (ray, model, frequency), image row m n_nu + l
+  double model_k1[BL_TRANSFER_MAX_MODELS], model_k2[BL_TRANSFER_MAX_MODELS], model_k3;   // ... R_high g1, R_low g1 of model m; n_e / n_i g2
   long long n_rays_total;
   double *image;              // [n_q][n_rays_total]; rows 0..n_nu-1 = I_nu
   int *out_sample_num;        // [n_rays_total] or null

@@ -335,6 +335,8 @@ int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const i
                        const double *image, uint8_t *refine_flags, int32_t *n_refined, int32_t *next_locs) {
   bl_ctx *ctx = const_cast<bl_ctx *>(ctx_const);
   if (ctx == nullptr || image == nullptr || refine_flags == nullptr || n_refined == nullptr) return BL_E_ARG;
+  if (bl_num_electron_models(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more electron models (bl_set_electron_models).");
   const bl_params &p = *bl_internal_params(ctx);
   *n_refined = 0;
   if (p.adaptive_max_level <= 0 || level >= p.adaptive_max_level) {   // radiation_adaptive.cpp:22-23
@@ -404,6 +406,8 @@ int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const i
 
 int bl_write_output(bl_ctx *ctx, const char *path_override, const bl_output_desc *d) {
   if (ctx == nullptr || d == nullptr) return BL_E_ARG;
+  if (bl_num_electron_models(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no electron-model axis (bl_set_electron_models with n >= 2).");
   if (d->level[0].image == nullptr && bl_image_num_quantities(ctx) > 0) return bl_internal_fail(ctx, BL_E_ARG, "bl_write_output needs the root image.");
   const bl_params &p = *bl_internal_params(ctx);
   const bl_camera_frame &frame = *bl_internal_frame(ctx);

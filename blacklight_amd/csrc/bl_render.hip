@@ -192,6 +192,10 @@ struct RenderJob {
   size_t park_capacity = 0;
   int quad_grid = 0;          // waves of bl_geodesic_quad_kernel
   int n_nu = 0, n_q = 0, max_steps = 0;
+  // bl_set_electron_models: n_models pairs (0: the parameter block's), n_q_model image rows each (n_q = n_models x n_q_model);
+  // the shading stage runs once per model over the chunk's samples (model_passes)
+  int n_models = 0, n_q_model = 0, model_passes = 1;
+  bool models_one_pass = false;   // ... or all of them in one pass: one gather, one lane per (ray, model, frequency) in the transfer kernel
   long long n_rays = 0, level_pixels = 0;
   size_t redo_capacity = 0;
   // scratch
@@ -244,6 +248,24 @@ struct RenderJob {
 
 hipEvent_t *SlotEvents(RenderJob &job, int k) { return job.ctx->events.data() + static_cast<size_t>(k) * kEventsPerChunk; }
 
+// Electron model m of bl_set_electron_models into the argument blocks: its pair where the coefficient kernels read R_low / R_high
+// (the exact tier's BlPlasmaDevice, the tolerant tier's fast_k[1], fast_k[2] folded as BuildShadeArgs folds the parameter block's)
+// and its rows of the image. Without models nothing changes.
+void BindElectronModel(RenderJob &job, int m) {
+  bl_ctx *ctx = job.ctx;
+  if (job.n_models == 0 || job.models_one_pass) return;   // (one pass: the transfer kernel has every model's constants, BuildTransferArgs)
+  const bl_params &p = ctx->params;
+  const double rat_low = ctx->model_rat_low[m], rat_high = ctx->model_rat_high[m];
+  job.sa.plasma.plasma_rat_low = rat_low;
+  job.sa.plasma.plasma_rat_high = rat_high;
+  if (job.fast) {
+    const double g1 = p.plasma_use_p != 0 ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_i - 1.0);
+    job.sa.fast_k[1] = rat_high * g1;
+    job.sa.fast_k[2] = rat_low * g1;
+  }
+  job.xa.image = job.image + static_cast<size_t>(m) * job.n_q_model * static_cast<size_t>(job.n_rays);
+}
+
 // ---- plan: validation of the call, the path it takes
 void PlanJob(RenderJob &job) {
   bl_ctx *ctx = job.ctx;
@@ -267,8 +289,12 @@ void PlanJob(RenderJob &job) {
       Warn(ctx, "Unpolarized kappa-distribution electrons: kappa_aa_high_i, which the reference leaves uninitialised here, is (3 / kappa)^4.75 + 0.6.");
     ctx->kappa_warned = true;
   }
+  job.n_models = static_cast<int>(ctx->model_rat_low.size());
+  if (const char *why = ElectronModelsRefusal(ctx, job.n_models)) throw Failure{BL_E_UNSUPPORTED, why};
   job.n_nu = p.image_num_frequencies;
-  job.n_q = ctx->image_num_quantities;
+  job.n_q_model = ctx->image_num_quantities;
+  job.n_q = job.n_q_model * std::max(1, job.n_models);
+  job.model_passes = std::max(1, job.n_models);
   job.max_steps = p.ray_max_steps;
   job.n_rays = d->n_rays;
   job.aux = ctx->aux_images.any != 0;
@@ -328,6 +354,15 @@ void PlanJob(RenderJob &job) {
   // Several frequencies in the fast path: per-sample factors (BlFreqInputs) instead of per-frequency transfer records,
   // evaluated by bl_transfer_freq_kernel with one lane per ray and frequency
   job.freq_split = job.fast && job.n_nu >= 4 && p.plasma_power_frac == 0.0 && !job.tau_row;   // (the factors are the thermal formulas')
+  // Electron models in one pass: where the factors would apply, the image holds intensities only and no Theta_e cut decides differently
+  // between models, a sample's row holds what no model enters (BlFreqInputs) and the transfer kernel forms each model's 1 / (k T_e)
+  // (everything else: one shading pass per model over the shared samples, LaunchShadingStage)
+  job.models_one_pass = job.n_models >= 2 && job.fast && p.plasma_power_frac == 0.0 && !job.tau_row && !job.aux && ctx->render_num_images == 0
+      && p.cut_theta_e_min < 0.0 && p.cut_theta_e_max < 0.0;
+  if (job.models_one_pass) {
+    job.freq_split = true;
+    job.model_passes = 1;
+  }
   // Plain images of a spherical Kerr-Schild simulation with fallback values beyond the grid: nothing is recorded of the steps that
   // lie in the empty shell between the grid's outer edge and the camera's sphere (both tiers; the samples count as ever)
   job.skip_shell = job.simulation && !job.aux && !ctx->polarized && !job.slow && !job.geo_load && !job.geo_save && !job.sample_save
@@ -411,8 +446,9 @@ void PlanJob(RenderJob &job) {
   // order - not the 8 x 8 tiles, centre first, that make chunks drain faster - so that what a chunk finishes is a range of columns,
   // downloaded while the next chunk renders (the image rows of a 4096^2 x 64 frame are 8.6 GB: 0.7 s of PCIe that used to follow the
   // last kernel)
-  job.raster = !d->outputs_on_device && d->level == 0 && d->pixel_map == nullptr && job.n_q >= 8
-      && static_cast<uint64_t>(job.n_q) * static_cast<uint64_t>(job.n_rays) * sizeof(double) >= (256ull << 20) && !job.geo_load && !job.geo_save && !job.sample_save;
+  // (one electron model's rows decide: the trace order is part of the resident geodesics' key, which the models must not change)
+  job.raster = !d->outputs_on_device && d->level == 0 && d->pixel_map == nullptr && job.n_q_model >= 8
+      && static_cast<uint64_t>(job.n_q_model) * static_cast<uint64_t>(job.n_rays) * sizeof(double) >= (256ull << 20) && !job.geo_load && !job.geo_save && !job.sample_save;
 }
 
 // ---- geodesics once per series (bl_set_geodesic_reuse; reference: blacklight.cpp:93-94 against its run loop :178-250, and the
@@ -1371,7 +1407,7 @@ void BuildShadeArgs(RenderJob &job) {
   sa.aux_record_unused = job.rows_only ? 1 : 0;
   for (int mu = 0; mu < 4; mu++) sa.cam_x[mu] = ctx->frame.cam_x[mu];
   sa.tag_in_record = job.fast ? 1 : 0;
-  sa.freq_split = job.freq_split ? 1 : 0;
+  sa.freq_split = job.freq_split ? (job.models_one_pass ? 2 : 1) : 0;
   sa.coef_split = job.coef_split ? 1 : 0;
   sa.redo_capacity = (job.fast || job.fast_formula || ctx->polarized) ? job.redo_capacity : 0;
 
@@ -1423,6 +1459,19 @@ void BuildTransferArgs(RenderJob &job) {
   xa.lane_transfer = (ctx->switches & BL_SWITCH_LANE_TRANSFER) ? 1 : 0;
   xa.n_rays_total = job.n_rays;
   xa.image = job.image;
+  xa.n_models = 0;
+  if (job.models_one_pass) {   // every model's R_high / R_low folded as BuildShadeArgs folds the parameter block's (fast_k[1..3])
+    static_assert(BL_TRANSFER_MAX_MODELS == BL_MAX_ELECTRON_MODELS, "model constants");
+    const bool use_p = p.plasma_use_p != 0;
+    const double g1 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_i - 1.0);
+    const double g2 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_e - 1.0);
+    xa.n_models = job.n_models;
+    for (int m = 0; m < job.n_models; m++) {
+      xa.model_k1[m] = ctx->model_rat_high[m] * g1;
+      xa.model_k2[m] = ctx->model_rat_low[m] * g1;
+    }
+    xa.model_k3 = p.plasma_ne_ni * g2;
+  }
   xa.out_sample_num = job.out_num;
   xa.out_flags = job.out_flags;
   xa.aux_images = ctx->aux_images;
@@ -1922,36 +1971,45 @@ void LaunchShadingStage(RenderJob &job, int k, bool geodesic_beside, hipStream_t
   if (job.simulation && !job.locate_inside && !job.reuse_located)
     Check(bl_launch_locate(&sa, geodesic_beside ? job.locate_grid_shared : job.locate_grid_alone, ctx->lds_table_bytes, stream), "locate kernel launch");
   Check(hipEventRecord(e[3], stream), "event");
-  coefficient_kernel();
-  // The transport matrices - memory - on the second stream beside the per-frequency coefficient kernel - arithmetic: both read what
-  // bl_shade_polarized2_kernel left, neither reads the other. (The coefficient kernel's workgroups fill the device first, so the
-  // matrices overlap its last quarter only: 276 -> 270 ms per 1024^2 frame, 1.10 -> 1.08 s at 2048^2 adaptive; a smaller grid for the
-  // coefficient kernel or a priority stream for the matrices move the split, not the sum. BLACKLIGHT_AMD_POLARIZED_OVERLAP=0: in sequence.)
-  // (one scratch set: with two, the second stream carries the next chunk's geodesic stage, and the matrices would queue behind it)
-  // (with the coefficients evaluated inside the coefficient kernel there is nothing left beside which to build them: in sequence)
-  const bool matrices_beside = ctx->polarized && job.matrix_transport && job.n_slots == 1 && ctx->stream_geo != stream && !job.pol_coefficients_inside;
-  const int polcoef_grid = ctx->num_cus * 20;
-  if (matrices_beside) {
-    // (the frames of the samples without coefficients first: the matrices read them)
-    Check(bl_launch_polarized_coefficients_parts(&sa, polcoef_grid, 2, stream), "polarized frame kernel launch");
-    Check(hipEventRecord(e[10], stream), "event");
-    Check(hipStreamWaitEvent(ctx->stream_geo, e[10], 0), "stream wait");
-    Check(bl_launch_transport_matrices(&xa, ctx->num_cus, ctx->stream_geo), "transport matrix kernel launch");
-    Check(hipEventRecord(e[11], ctx->stream_geo), "event");
-  }
-  if (ctx->polarized) Check(bl_launch_polarized_coefficients_parts(&sa, polcoef_grid, job.pol_coefficients_inside ? 2 : (matrices_beside ? 0 : 1), stream), "polarized coefficient kernel launch");
-  if (job.coef_split) Check(bl_launch_coefficients_freq(&sa, ctx->num_cus * 16, stream), "per-frequency coefficient kernel launch");
-  Check(hipEventRecord(e[4], stream), "event");
-  Check(job.aux ? bl_launch_transfer_aux(&xa, stream)
-                : (job.freq_split ? bl_launch_transfer_freq(&xa, stream) : (job.composed ? bl_launch_transfer_composed(&xa, stream) : bl_launch_transfer(&xa, stream))),
-        "transfer kernel launch");
-  if (job.tau_row) Check(bl_launch_tau(&xa, stream), "optical-depth kernel launch");
-  if (ctx->polarized && matrices_beside) {
-    Check(hipStreamWaitEvent(stream, e[11], 0), "stream wait");
-    Check(bl_launch_transfer_polarized_rays(&xa, stream), "polarized transfer kernel launch");
-  } else if (ctx->polarized) {
-    Check(job.matrix_transport ? bl_launch_transfer_polarized_matrix(&xa, ctx->num_cus, stream) : bl_launch_transfer_polarized(&xa, stream),
-          "polarized transfer kernel launch");
+  for (int m = 0; m < job.model_passes; m++) {
+    if (m > 0) {   // what the shading stage adds to the chunk's counters starts again from zero (ClearShadingCounters)
+      unsigned long long *c = sl.d_counters.ptr;
+      Check(hipMemsetAsync(c + BL_CNT_GATHERS, 0, sizeof *c, stream), "counter reset");
+      Check(hipMemsetAsync(c + BL_CNT_UNDEFINED, 0, 3 * sizeof *c, stream), "counter reset");   // (UNDEFINED, INTERP_FAILED, REDO)
+      Check(hipMemsetAsync(c + BL_CNT_COUNT, 0, 12 * sizeof *c, stream), "counter reset");
+    }
+    BindElectronModel(job, m);
+    coefficient_kernel();
+    // The transport matrices - memory - on the second stream beside the per-frequency coefficient kernel - arithmetic: both read what
+    // bl_shade_polarized2_kernel left, neither reads the other. (The coefficient kernel's workgroups fill the device first, so the
+    // matrices overlap its last quarter only: 276 -> 270 ms per 1024^2 frame, 1.10 -> 1.08 s at 2048^2 adaptive; a smaller grid for the
+    // coefficient kernel or a priority stream for the matrices move the split, not the sum. BLACKLIGHT_AMD_POLARIZED_OVERLAP=0: in sequence.)
+    // (one scratch set: with two, the second stream carries the next chunk's geodesic stage, and the matrices would queue behind it)
+    // (with the coefficients evaluated inside the coefficient kernel there is nothing left beside which to build them: in sequence)
+    const bool matrices_beside = ctx->polarized && job.matrix_transport && job.n_slots == 1 && ctx->stream_geo != stream && !job.pol_coefficients_inside;
+    const int polcoef_grid = ctx->num_cus * 20;
+    if (matrices_beside) {
+      // (the frames of the samples without coefficients first: the matrices read them)
+      Check(bl_launch_polarized_coefficients_parts(&sa, polcoef_grid, 2, stream), "polarized frame kernel launch");
+      Check(hipEventRecord(e[10], stream), "event");
+      Check(hipStreamWaitEvent(ctx->stream_geo, e[10], 0), "stream wait");
+      Check(bl_launch_transport_matrices(&xa, ctx->num_cus, ctx->stream_geo), "transport matrix kernel launch");
+      Check(hipEventRecord(e[11], ctx->stream_geo), "event");
+    }
+    if (ctx->polarized) Check(bl_launch_polarized_coefficients_parts(&sa, polcoef_grid, job.pol_coefficients_inside ? 2 : (matrices_beside ? 0 : 1), stream), "polarized coefficient kernel launch");
+    if (job.coef_split) Check(bl_launch_coefficients_freq(&sa, ctx->num_cus * 16, stream), "per-frequency coefficient kernel launch");
+    Check(hipEventRecord(e[4], stream), "event");
+    Check(job.aux ? bl_launch_transfer_aux(&xa, stream)
+                  : (job.freq_split ? bl_launch_transfer_freq(&xa, stream) : (job.composed ? bl_launch_transfer_composed(&xa, stream) : bl_launch_transfer(&xa, stream))),
+          "transfer kernel launch");
+    if (job.tau_row) Check(bl_launch_tau(&xa, stream), "optical-depth kernel launch");
+    if (ctx->polarized && matrices_beside) {
+      Check(hipStreamWaitEvent(stream, e[11], 0), "stream wait");
+      Check(bl_launch_transfer_polarized_rays(&xa, stream), "polarized transfer kernel launch");
+    } else if (ctx->polarized) {
+      Check(job.matrix_transport ? bl_launch_transfer_polarized_matrix(&xa, ctx->num_cus, stream) : bl_launch_transfer_polarized(&xa, stream),
+            "polarized transfer kernel launch");
+    }
   }
   Check(hipEventRecord(e[5], stream), "event");
   Check(hipMemcpyAsync(ctx->host_counters + static_cast<size_t>(k) * BL_CNT_TOTAL, sl.d_counters.ptr, BL_CNT_TOTAL * sizeof(unsigned long long),
@@ -2247,8 +2305,8 @@ void FinishStats(RenderJob &job) {
   st.launches_locate = (job.simulation && !job.locate_inside && !job.reuse_located) ? job.n_chunks : 0;
   st.geodesics_reused = job.reuse ? 1 : 0;
   st.sampling_reused = job.reuse_located ? 1 : 0;
-  st.launches_shade = job.n_chunks;
-  st.launches_transfer = job.n_chunks;
+  st.launches_shade = job.n_chunks * job.model_passes;
+  st.launches_transfer = job.n_chunks * job.model_passes;
   st.n_samples = static_cast<int64_t>(job.total_samples);
   st.n_samples_emitted = static_cast<int64_t>(job.total_records);
   st.n_gathers = static_cast<int64_t>(job.total_gathers);

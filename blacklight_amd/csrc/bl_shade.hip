@@ -221,6 +221,19 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
       double2 *dst = reinterpret_cast<double2 *>(P.freq_inputs + row);
       if (!sh.have_coefficients) {
         dst[0] = make_double2(0.0, 0.0);
+      } else if (P.freq_split == 2) {
+        // electron models in one pass: the row no model enters (BlFreqInputs), from the exact state. k T_e = K0 (p / rho) d / N:
+        // 1 / beta^2 from the cell's beta_inv, K0 p / rho = k T_e N / d with N, d of the parameter block's pair (fast_k)
+        const double beta_inv = sh.cell[6];
+        const double bi2 = beta_inv * beta_inv, dd = 1.0 + bi2;
+        const double nn = P.fast_k[1] + P.fast_k[2] * bi2 + P.fast_k[3] * dd;
+        const double nu_s_cgs = 2.0 / 9.0 * sh.nu_c_cgs * sh.theta_e * sh.theta_e * sh.sin_theta_b;
+        const double s_nu = sh.nu_fluid_over_nu * momentum_factor;
+        dst[0] = make_double2(1.0, s_nu / nu_s_cgs * sh.kb_tt_e_cgs * sh.kb_tt_e_cgs);
+        dst[1] = make_double2(kH * s_nu, P.plasma.plasma_thermal_frac * sh.n_e_cgs * kE * kE * sh.nu_c_cgs * (1.0 / kC)
+                                  * (kSqrt2 * kPi / 27.0) * sh.sin_theta_b / (s_nu * s_nu));
+        dst[2] = make_double2(delta_lambda * P.x_unit / momentum_factor, bi2);
+        dst[3] = make_double2(sh.kb_tt_e_cgs * nn / dd, 0.0);
       } else {
         const double nu_s_cgs = 2.0 / 9.0 * sh.nu_c_cgs * sh.theta_e * sh.theta_e * sh.sin_theta_b;
         const double s_nu = sh.nu_fluid_over_nu * momentum_factor;

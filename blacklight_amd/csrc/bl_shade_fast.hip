@@ -29,6 +29,7 @@ __device__ __forceinline__ bool fast_shade_sample(const BlShadeArgs &P, const do
   // what the loop over frequencies needs
   bool have = false;
   double nu_ratio = 0.0, n_e_cgs = 0.0, kb_tt_e_cgs = 0.0, k_u_inv = 0.0, b_sin = 0.0, b_sin_inv = 0.0;
+  double model_bi2 = 0.0, model_kt_tot = 0.0;   // electron models in one pass (freq_split = 2): 1 / beta^2, K0 p / rho
   const double rho = pr[0], pgas = pr[1], uu1 = pr[2], uu2 = pr[3], uu3 = pr[4], bb1 = pr[5], bb2 = pr[6], bb3 = pr[7];
   if (status != kSampleCut) {
     // ---- Kerr-Schild scalars (radiation_geometry.cpp:18-25, :138-262)
@@ -139,6 +140,8 @@ __device__ __forceinline__ bool fast_shade_sample(const BlShadeArgs &P, const do
       const double bi2 = beta_inv * beta_inv;
       const double dd = 1.0 + bi2;
       kb_tt_e_cgs = P.fast_k[0] * (pgas * rho_inv) * (dd * fastmath::rcp(P.fast_k[1] + P.fast_k[2] * bi2 + P.fast_k[3] * dd));
+      model_bi2 = bi2;
+      model_kt_tot = P.fast_k[0] * (pgas * rho_inv);
     }
     // ---- cell cuts (:361-375): decided here unless a value sits within the guard band of an active threshold
     bool cell_cut = false, undecided = !cartesian && pp2 == 0.0;   // (on the polar axis of the spherical coordinates: the exact kernel's business)
@@ -210,6 +213,14 @@ __device__ __forceinline__ bool fast_shade_sample(const BlShadeArgs &P, const do
   const double s_j = P.fast_k[5] * (rho * b_sin) * (s_nu_inv * s_nu_inv);
   if (kGeneral) n_e_cgs = P.fast_k[6] * rho;   // (the power-law terms below)
   const double s_length = delta_lambda * P.x_unit * momentum_factor_inv;                          // unpolarized.cpp:75-76
+  if (P.freq_split == 2) {   // electron models in one pass: the row no model enters (BlFreqInputs)
+    double2 *dst = reinterpret_cast<double2 *>(P.freq_inputs + row);
+    dst[0] = make_double2(have ? 1.0 : 0.0, have ? s_nu * b_sin_inv * P.fast_k[4] : 0.0);
+    dst[1] = make_double2(kH * s_nu, s_j);
+    dst[2] = make_double2(s_length, model_bi2);
+    dst[3] = make_double2(model_kt_tot, 0.0);
+    return true;
+  }
   if (P.freq_split) {   // several frequencies: the factors go to bl_transfer_freq_kernel, one lane per ray and frequency
     double2 *dst = reinterpret_cast<double2 *>(P.freq_inputs + row);
     dst[0] = make_double2(have ? 1.0 : 0.0, s_1_2);

@@ -533,7 +533,8 @@ __device__ __forceinline__ bool trilinear(const float4 (&lo)[8], const float4 (&
 template <bool kSpinZero, bool kFactors = false>
 __device__ __forceinline__ double2 shade(const BlSpacetime &st, const double (&K)[6], double freq, double freq_inv, double x_unit, int cut_mask,
                                          uint32_t cut_table, const float pr[8], double x, double y, double z, double kx, double ky, double kz, double kt,
-                                         double momentum_factor, double delta_lambda, bool *have_out, bool *undecided_out, double2 (*factors)[4] = nullptr) {
+                                         double momentum_factor, double delta_lambda, bool *have_out, bool *undecided_out, double2 (*factors)[4] = nullptr,
+                                         bool model_rows = false) {
   const double bh_m = st.bh_m;
   const double bh_a = kSpinZero ? 0.0 : st.bh_a;
   const double a2 = bh_a * bh_a;
@@ -654,6 +655,13 @@ __device__ __forceinline__ double2 shade(const BlSpacetime &st, const double (&K
     const double s_1_3 = cbrt_k(s_x);
     const double s_1_6 = sqrt_k(s_1_3);
     const double s_nu_inv = -k_u_inv * mf_inv;
+    if (model_rows) {   // (wave-uniform) electron models in one pass: nothing of R_high / R_low in the row (BlFreqInputs)
+      (*factors)[0] = make_double2(have ? 1.0 : 0.0, s_nu * b_sin_inv * K[4]);
+      (*factors)[1] = make_double2(KS(kH) * s_nu, K[5] * (rho * b_sin) * (s_nu_inv * s_nu_inv));
+      (*factors)[2] = make_double2(delta_lambda * x_unit * mf_inv, bi2);
+      (*factors)[3] = make_double2(K[0] * (pgas * rho_inv), 0.0);
+      return make_double2(1.0, 0.0);
+    }
     (*factors)[0] = make_double2(have ? 1.0 : 0.0, s_1_6 * s_1_3);   // flag 1: factors follow; 0: nothing to add (cut cell, no field)
     (*factors)[1] = make_double2(s_1_3, s_1_6);
     (*factors)[2] = make_double2(KS(kH) * s_nu * kte_inv, K[5] * (rho * b_sin) * (s_nu_inv * s_nu_inv));
@@ -746,6 +754,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   const double camera_r = P.cuts.camera_r;
   const double band = P.fast_angle_band;
   const double K[6] = {P.fast_k[0], P.fast_k[1], P.fast_k[2], P.fast_k[3], P.fast_k[4], P.fast_k[5]};
+  const bool model_rows = P.freq_split == 2;
   const double freq = uniform_value(P.frequencies[0]);
   const double freq_inv = uniform_value(fastmath::rcp(freq));
   const double x_unit = P.x_unit;
@@ -858,7 +867,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     if (kFactors) factors[0] = factors[1] = factors[2] = factors[3] = make_double2(0.0, 0.0);
     if (interp)
       rec = shade<kSpinZero, kFactors>(st, K, freq, freq_inv, x_unit, cut_mask, cut_table, pr, p.h0.x, p.h0.y, p.h1.x, p.c0.x, p.c0.y, p.c1.x, kt, momentum_factor,
-                                       -p.c1.y, &have, &undecided_cut, kFactors ? &factors : nullptr);
+                                       -p.c1.y, &have, &undecided_cut, kFactors ? &factors : nullptr, kFactors && model_rows);
     // a sample off the grid has fallback primitives without a field (no coefficients: I <- I) or NaN ones (I <- I + NaN,
     // simulation_sampling.cpp:377-384); a cut sample has none either
     const bool defer = interp && (undecided_cut || near_midpoint || (p.loc.status & kPlainUndecided) != 0u);

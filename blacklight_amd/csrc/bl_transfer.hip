@@ -15,17 +15,22 @@
 // (a, c) from the sample's factors (BlFreqInputs; the lanes of one ray read the same 64 bytes) and the lane's own frequency,
 // and applies I <- a I + c at once. The per-frequency transfer records (16 bytes per sample and frequency: 1.5 TB written
 // and read per 1024^2 x 64-frequency frame) do not exist on this path; the exact second pass leaves the same factors.
+// With electron models in one pass (P.n_models > 0, wave-uniform) a lane is a (ray, model, frequency): the rows hold what no model
+// enters (BlFreqInputs), and the lane forms its model's 1 / (k T_e) per sample before the same step.
 __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int slot = (int)(t / P.n_nu);
-  const int l = (int)(t % P.n_nu);
+  const bool models = P.n_models > 0;
+  const int channels = models ? P.n_models * P.n_nu : P.n_nu;
+  const int slot = (int)(t / channels);
+  const int channel = (int)(t % channels);   // m n_nu + l: the image row
+  const int l = channel % P.n_nu;
   unsigned long long samples = 0ull, flagged = 0ull;
   int max_num = 0;
   if (slot < bl_rays_done(P.counters, P.chunk_rays)) {
     const int num = P.ray_sample_num[slot];
     const bool flag = P.ray_flags[slot] != 0;
     const long long out_index = P.ray_out_index[slot];
-    if (l == 0) {
+    if (channel == 0) {
       const int all = num + (P.ray_skipped != nullptr ? P.ray_skipped[slot] : 0);
       samples = (unsigned long long)all;
       flagged = flag ? 1ull : 0ull;
@@ -49,21 +54,34 @@ __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P)
       const double2 *in = reinterpret_cast<const double2 *>(P.freq_inputs + (size_t)P.ray_offset[slot]);
       const double kThird = fastmath::resident_constant(1.0 / 3.0), kInvPlanck = fastmath::resident_constant(kC * kC / (2.0 * kH));
       const double kRoot = fastmath::resident_constant(kPow2_11_12), kThin = fastmath::resident_constant(0x1p-10);
+      const int m = channel / P.n_nu;
+      const double mk1 = models ? P.model_k1[m] : 0.0, mk2 = models ? P.model_k2[m] : 0.0, mk3 = P.model_k3;
       for (int n = num - 1; n >= 0; n--) {   // reference sample order is reversed integration order (geodesics.cpp:832-840)
         const double2 q0 = in[4 * (size_t)n], q1 = in[4 * (size_t)n + 1], q2 = in[4 * (size_t)n + 2], q3 = in[4 * (size_t)n + 3];
         // bl_shade_fast_kernel's frequency loop (simulation_coefficients.cpp:464-523, unpolarized.cpp:74-110) as one straight line for
         // the sample that has coefficients, a thin step and h nu << k T_e - nearly every one: no expm1, no division, no branch; the
         // rest is selected or, where it needs an exponential of its own, redone behind a branch
         const bool have = q0.x == 1.0;
-        const double xx_1_3 = q1.x * f_1_3;
-        const double var_c = q0.y * f_1_2 + kRoot * (q1.y * f_1_6);
-        const double j_val = q2.y * f_inv2 * fastmath::exp(-xx_1_3, exp_c) * var_c * var_c;
-        const double xp = q2.x * f;
+        double s_1_3 = q1.x, s_1_6 = q1.y, s_1_2 = q0.y, s_planck = q2.x, s_j = q2.y, s_length = q3.x;
+        if (models) {   // this model's 1 / (k T_e) (the fused kernel's kte_inv), then the sample's roots at unit frequency
+          const double bi2 = q2.y, dd = 1.0 + bi2;
+          const double kte_inv = (mk1 + mk2 * bi2 + mk3 * dd) * fastmath::rcp(q3.x * dd);
+          s_1_3 = fastmath::cbrt(q0.y * (kte_inv * kte_inv));
+          s_1_6 = bl_sqrt_g(s_1_3);
+          s_1_2 = s_1_6 * s_1_3;
+          s_planck = q1.x * kte_inv;
+          s_j = q1.y;
+          s_length = q2.x;
+        }
+        const double xx_1_3 = s_1_3 * f_1_3;
+        const double var_c = s_1_2 * f_1_2 + kRoot * (s_1_6 * f_1_6);
+        const double j_val = s_j * f_inv2 * fastmath::exp(-xx_1_3, exp_c) * var_c * var_c;
+        const double xp = s_planck * f;
         double planck = xp * (1.0 + 0.5 * xp * (1.0 + kThird * xp * (1.0 + 0.25 * xp)));
         if (__builtin_expect(have && !(xp < kThin), 0)) planck = fastmath::expm1(xp);
         double alpha_val = j_val * (planck * kInvPlanck);
         if (alpha_val * alpha_val <= 0x1p-1024) alpha_val = 0.0;
-        const double delta_lambda_cgs = q3.x * f_inv;
+        const double delta_lambda_cgs = s_length * f_inv;
         const double delta_tau = alpha_val * delta_lambda_cgs;
         // optically thin step: expm1(-t) = -t p(t), p = 1 - t/2 (1 - t/3 (1 - t/4)) to 2^-53: a = 1 - t p, c = j dl p
         const double p = 1.0 - 0.5 * delta_tau * (1.0 - kThird * delta_tau * (1.0 - 0.25 * delta_tau));
@@ -86,7 +104,7 @@ __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P)
         intensity = __builtin_fma(a, intensity, c);
       }
     }
-    P.image[(size_t)l * P.n_rays_total + out_index] = intensity * (f * f * f);   // unpolarized.cpp:206-207
+    P.image[(size_t)channel * P.n_rays_total + out_index] = intensity * (f * f * f);   // unpolarized.cpp:206-207
   }
   // statistics: wave reduce, one atomic per wave
   for (int offset = 32; offset > 0; offset >>= 1) {
@@ -344,7 +362,7 @@ __global__ void __launch_bounds__(64) bl_transfer_aux_kernel(BlTransferArgs P) {
 }
 
 extern "C" hipError_t bl_launch_transfer_freq(const BlTransferArgs *args, hipStream_t stream) {
-  const long long lanes = (long long)args->chunk_rays * args->n_nu;
+  const long long lanes = (long long)args->chunk_rays * args->n_nu * (args->n_models > 0 ? args->n_models : 1);
   hipLaunchKernelGGL(bl_transfer_freq_kernel, dim3((unsigned int)((lanes + 255) / 256)), dim3(256), 0, stream, *args);
   return hipGetLastError();
 }

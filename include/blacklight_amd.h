@@ -297,6 +297,9 @@ typedef struct bl_stats {
   int32_t geodesics_reused;   /* 1: the sample records of an earlier render of the same camera were shaded again - no ray was
                                  integrated (launches_geodesic = 0, ms_geodesic = 0); bl_set_geodesic_reuse                              */
   int32_t sampling_reused;    /* 1: ... and the located samples too (same grid geometry: no locate kernel ran, launches_locate = 0)     */
+  /* Several electron models (bl_set_electron_models) where they cannot share one pass: launches_shade / launches_transfer count one
+     shading pass per model and chunk; n_gathers, n_deferred and the sample counts are those of one pass (every pass has the same
+     samples); ms_shade runs from the first coefficient kernel to the last one, ms_transfer is the last transfer kernel's. */
 } bl_stats;
 
 /* Measurement switches: environment variables BLACKLIGHT_AMD_<NAME>, read ONCE by bl_init (never during a render) and echoed in
@@ -353,6 +356,20 @@ BL_API int bl_shift_grid_slices(bl_ctx *ctx, int count);
 BL_API int bl_set_snapshot(bl_ctx *ctx, int snapshot);
 /* Number of image rows n_q and their offsets (radiation_integrator.cpp:436-520). */
 BL_API int bl_image_num_quantities(const bl_ctx *ctx);
+/* Electron-temperature models (the R_high / R_low prescription: plasma_rat_high, plasma_rat_low) rendered by one bl_render.
+ * n = 0 (what a context starts with): the parameter block's own pair. 1 <= n <= BL_MAX_ELECTRON_MODELS: n (R_low, R_high) pairs,
+ * finite; bl_image_num_quantities is then n times the single-model count and image row m * n_q + q is row q of model m
+ * (sample_num, sample_flags and renderings come out once). Geodesics and located samples do not depend on the model: changing the
+ * models between renders keeps them (bl_set_geodesic_reuse). Refused (BL_E_UNSUPPORTED): formula mode, polarized runs,
+ * plasma_model = code_kappa, slow light, and with n >= 2 adaptive_max_level > 0 and renderings that a model enters (a Theta_e
+ * feature, or a Theta_e cut beside renderings) - as are bl_adaptive_refine and bl_write_output while n >= 2 (refinement reads one
+ * image; the reference's files have no model axis). The tolerant tier's plain intensity images without a Theta_e cut render n >= 2
+ * models in one pass: one gather and coefficient kernel, one transfer lane per (ray, model, frequency) - each model within the tier's
+ * tolerance of its exact image. Everything else runs one shading pass per model over the shared samples: each model's image is what
+ * a render with that pair in the parameter block gives (the same bits in the exact tier and under bl_set_reproducible). */
+#define BL_MAX_ELECTRON_MODELS 16
+BL_API int bl_set_electron_models(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high);
+BL_API int bl_num_electron_models(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own model */
 /* Number of false-colour renderings bl_render produces (render_num_images; 0 in formula mode). */
 BL_API int bl_render_num_images(const bl_ctx *ctx);
 BL_API int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out);
