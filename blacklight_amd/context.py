@@ -145,6 +145,74 @@ class Context:
     def num_electron_models(self):
         return self._lib.bl_num_electron_models(self._ctx)
 
+    def set_density_units(self, rho_cgs):
+        """Render several density units (simulation_rho_cgs values, g / cm^3) in one render (bl_set_density_units). A scalar or a
+        sequence; an empty sequence clears them (the parameter block's unit again). The image then holds, for every electron model,
+        its units one after another (render()["image_by_unit"]: (n_models, n_units, n_q, n_rays)); geodesics stay resident."""
+        units = np.ascontiguousarray(np.atleast_1d(np.asarray(rho_cgs, dtype=np.float64)).ravel())
+        self._check(self._lib.bl_set_density_units(self._ctx, int(units.size), units.ctypes.data_as(C.c_void_p)))
+        self._density_units = [float(u) for u in units]
+
+    @property
+    def density_units(self):
+        """The simulation_rho_cgs values set_density_units() set; [] when the parameter block's unit is rendered."""
+        return list(getattr(self, "_density_units", []))
+
+    @property
+    def num_density_units(self):
+        return self._lib.bl_num_density_units(self._ctx)
+
+    def fit_density_unit(self, target_jy, distance_pc, lo, hi, frequency=0, rtol=1.0e-3, per_render=16):
+        """The density unit (simulation_rho_cgs) in [lo, hi] at which the root image's total flux (flux.total_flux_jy) at image
+        frequency `frequency` is target_jy to within rtol. Each step renders `per_render` units log-spaced over the bracket in one
+        render - geodesics stay resident, so every render after the first is a shading stage only - and keeps the adjacent pair whose
+        fluxes straddle the target. With several electron models set, each model is fitted in turn. The context's models and units
+        are restored on exit. Returns (rho_cgs, flux_jy, renders): floats, or lists by model with several models."""
+        from . import flux as _flux
+        if not (0.0 < lo < hi) or not np.isfinite(hi):
+            raise ValueError(f"fit_density_unit needs 0 < lo < hi, finite (got {lo}, {hi})")
+        if not 2 <= per_render <= 16:
+            raise ValueError("fit_density_unit: 2 <= per_render <= 16 (BL_MAX_DENSITY_UNITS)")
+        if not (target_jy > 0.0 and rtol > 0.0):
+            raise ValueError("fit_density_unit needs target_jy > 0 and rtol > 0")
+        models, units = self.electron_models, self.density_units
+        renders = 0
+
+        def fit_one():
+            nonlocal renders
+            a, b = float(lo), float(hi)
+            for _ in range(64):
+                trial = np.geomspace(a, b, per_render)
+                trial[0], trial[-1] = a, b   # (the bracket's own ends, not their rounded logarithms)
+                self.set_density_units(trial)
+                got = self.render()
+                renders += 1
+                fluxes = np.array([_flux.total_flux_jy(got["image_by_unit"][0, u], self.params, distance_pc, frequency)
+                                   for u in range(per_render)])
+                best = int(np.nanargmin(np.abs(fluxes - target_jy))) if np.isfinite(fluxes).any() else -1
+                if best >= 0 and abs(fluxes[best] - target_jy) <= rtol * target_jy:
+                    return float(trial[best]), float(fluxes[best])
+                straddle = [k for k in range(per_render - 1) if (fluxes[k] - target_jy) * (fluxes[k + 1] - target_jy) <= 0.0]
+                if not straddle:
+                    raise ValueError(f"fit_density_unit: [{a:.6g}, {b:.6g}] g/cm^3 does not bracket {target_jy:.6g} Jy "
+                                     f"(fluxes found: {np.nanmin(fluxes):.6g} .. {np.nanmax(fluxes):.6g} Jy)")
+                a, b = float(trial[straddle[0]]), float(trial[straddle[0] + 1])
+            raise RuntimeError(f"fit_density_unit: no unit within rtol = {rtol} of {target_jy} Jy after {renders} renders")
+
+        try:
+            if len(models) >= 2:
+                found = []
+                for high, low in models:
+                    self.set_electron_models(high, rat_low=low)
+                    found.append(fit_one())
+                return [u for u, _ in found], [f for _, f in found], renders
+            rho, flux = fit_one()
+            return rho, flux, renders
+        finally:
+            self.set_density_units([])
+            self.set_electron_models([h for h, _ in models], rat_low=[lo_ for _, lo_ in models])
+            self.set_density_units(units)
+
     def set_caller_stream(self, stream=None, enabled=True):
         """Every later render starts behind the work queued so far on `stream` (a raw hipStream_t handle, e.g.
         torch.cuda.current_stream().cuda_stream; None / 0: the NULL stream) - bl_set_caller_stream."""
@@ -265,8 +333,9 @@ class Context:
             rendering = np.empty((n_render, 3, n_rays))
             d.render = rendering.ctypes.data_as(C.c_void_p)
         self._check(self._lib.bl_render(self._ctx, C.byref(d)))
-        n_models = max(1, self.num_electron_models)
-        return dict(image=image, image_by_model=image.reshape(n_models, n_q // n_models, n_rays), sample_num=sample_num,
+        n_models, n_units = max(1, self.num_electron_models), max(1, self.num_density_units)
+        return dict(image=image, image_by_model=image.reshape(n_models, n_q // n_models, n_rays),
+                    image_by_unit=image.reshape(n_models, n_units, n_q // (n_models * n_units), n_rays), sample_num=sample_num,
                     sample_flags=sample_flags, camera_pos=camera_pos, camera_dir=camera_dir, rendering=rendering, stats=self.stats)
 
     # ------------------------------------------------------------------ host steps of the reference loop

@@ -357,6 +357,31 @@ const char *ElectronModelsRefusal(const bl_ctx *ctx, int n) {
   }
   return nullptr;
 }
+
+// Why n density units cannot be rendered by this context (nullptr: they can). bl_set_density_units and bl_render's plan both ask.
+// (The unit scales rho, n_e, p_gas and B in cgs - simulation_coefficients.cpp:237-239, :361-375 - and nothing else a rendering reads.)
+const char *DensityUnitsRefusal(const bl_ctx *ctx, int n) {
+  const bl_params &p = ctx->params;
+  if (n <= 0) return nullptr;
+  if (p.model_type != BL_MODEL_SIMULATION) return "Density units: formula mode has no density (model_type = formula).";
+  if (ctx->polarized) return "Density units: polarized runs render one density unit (image_polarization = true).";
+  if (p.slow_light_on) return "Density units: slow light renders one density unit (slow_light_on = true).";
+  if (n >= 2 && p.adaptive_max_level > 0)
+    return "Density units: adaptive refinement reads one image; n >= 2 units need adaptive_max_level = 0.";
+  if (n >= 2 && ctx->render_num_images > 0) {   // (renderings come out once: only those no unit enters)
+    bool unit_cut = p.cut_rho_min >= 0.0 || p.cut_rho_max >= 0.0 || p.cut_n_e_min >= 0.0 || p.cut_n_e_max >= 0.0
+        || p.cut_p_gas_min >= 0.0 || p.cut_p_gas_max >= 0.0 || p.cut_b_min >= 0.0 || p.cut_b_max >= 0.0;
+    for (int i = 0; i < ctx->render_num_images; i++)
+      for (int f = 0; f < p.render_num_features[i]; f++) {
+        const int q = p.render_quantity[i][f];   // (bl_params.cpp: rho, n_e, p_gas, Theta_e, B, sigma, beta_inverse)
+        if (q == 0 || q == 1 || q == 2 || q == 4) unit_cut = true;
+      }
+    if (unit_cut)
+      return "Density units: a rendering that reads rho, n_e, p_gas or B, or a rho, n_e, p_gas or B cut beside renderings, differs "
+             "between units; n >= 2 units render renderings that no unit enters only.";
+  }
+  return nullptr;
+}
 }  // namespace blhost
 
 extern "C" {
@@ -1103,7 +1128,8 @@ int bl_render_num_images(const bl_ctx *ctx) { return ctx != nullptr ? ctx->rende
 
 int bl_image_num_quantities(const bl_ctx *ctx) {
   if (ctx == nullptr) return -1;
-  return ctx->image_num_quantities * std::max<int>(1, static_cast<int>(ctx->model_rat_low.size()));
+  return ctx->image_num_quantities * std::max<int>(1, static_cast<int>(ctx->model_rat_low.size()))
+      * std::max<int>(1, static_cast<int>(ctx->density_units.size()));
 }
 
 int bl_set_electron_models(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high) {
@@ -1121,6 +1147,21 @@ int bl_set_electron_models(bl_ctx *ctx, int n, const double *rat_low, const doub
 }
 
 int bl_num_electron_models(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->model_rat_low.size()) : -1; }
+
+int bl_set_density_units(bl_ctx *ctx, int n, const double *rho_cgs) {
+  if (ctx == nullptr) return BL_E_ARG;
+  if (n < 0 || n > BL_MAX_DENSITY_UNITS || (n > 0 && rho_cgs == nullptr))
+    return Fail(ctx, Failure{BL_E_ARG, "bl_set_density_units needs 0 <= n <= " + std::to_string(BL_MAX_DENSITY_UNITS) + " and the array of units."});
+  for (int u = 0; u < n; u++)
+    if (!std::isfinite(rho_cgs[u]) || !(rho_cgs[u] > 0.0))
+      return Fail(ctx, Failure{BL_E_ARG, "bl_set_density_units: unit " + std::to_string(u) + " is not a finite value > 0."});
+  if (const char *why = DensityUnitsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
+  std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: they do not depend on the unit)
+  ctx->density_units.assign(rho_cgs, rho_cgs + n);
+  return BL_OK;
+}
+
+int bl_num_density_units(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->density_units.size()) : -1; }
 
 int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out) {
   if (ctx == nullptr || out == nullptr) return BL_E_ARG;

@@ -149,8 +149,9 @@ struct bl_ctx {
   double guard_band = 1.0e-9;         // tolerant tier: relative half-width around a cut threshold left to the exact kernel
 
   // image rows (radiation_integrator.cpp:436-520)
-  int image_num_quantities = 0;      // of one electron model (bl_image_num_quantities: times the number of models)
+  int image_num_quantities = 0;      // of one electron model and unit (bl_image_num_quantities: times the number of each)
   std::vector<double> model_rat_low, model_rat_high;   // bl_set_electron_models(); empty: the parameter block's pair
+  std::vector<double> density_units;  // bl_set_density_units(): simulation_rho_cgs values; empty: the parameter block's
   BlAuxImages aux_images{};          // which image rows exist; .any = an auxiliary image or a rendering is requested
   int render_num_images = 0;         // false-colour renderings (0 in formula mode)
   DeviceBuffer<BlRenderDevice> d_render_params;
@@ -354,6 +355,7 @@ int Fail(bl_ctx *ctx, const Failure &failure);   // sets bl_last_error (or the g
 void EnsureStreams(bl_ctx *ctx);
 void DropResident(bl_ctx *ctx);   // the root level's kept geodesics go (bl_render.hip)
 const char *ElectronModelsRefusal(const bl_ctx *ctx, int n);   // bl_set_electron_models (bl_api.hip)
+const char *DensityUnitsRefusal(const bl_ctx *ctx, int n);     // bl_set_density_units (bl_api.hip)
 }  // namespace blhost
 
 #endif  // BLACKLIGHT_AMD_BL_CTX_H_

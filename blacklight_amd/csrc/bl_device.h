@@ -372,6 +372,9 @@ struct alignas(16) BlFreqInputs {
 // what no model enters - (flag, x at unit frequency and unit 1 / (k T_e)), (h s_nu, s_j), (s_length, 1 / beta^2), (K0 p / rho, 0) -
 // and bl_transfer_freq_kernel forms each model's 1 / (k T_e) = (K1_m + K2_m / beta^2 + K3 d) / (K0 (p / rho) d), d = 1 + 1 / beta^2.
 #define BL_TRANSFER_MAX_MODELS 16
+// ... and with density units (BlTransferArgs::n_units): the row is the unit the render folded (RenderJob::base_rho); unit u scales x at
+// unit frequency (~ 1 / b_unit) by unit_x[u] and s_j (~ d_unit b_unit) by unit_j[u]. Nothing else in the row depends on the unit.
+#define BL_TRANSFER_MAX_UNITS 16
 
 // Polarized runs: what the per-frequency coefficient formulas need of a sample (simulation_coefficients.cpp:458-698),
 // left by the coefficient kernel for bl_polarized_coefficients_kernel, one per sample record. 64 bytes.
@@ -493,6 +496,8 @@ struct BlTransferArgs {
   const BlFreqInputs *freq_inputs;            // bl_transfer_freq_kernel
   int n_models;                               // ... > 0: electron models in one pass, one lane per (ray, model, frequency), image row m n_nu + l
   double model_k1[BL_TRANSFER_MAX_MODELS], model_k2[BL_TRANSFER_MAX_MODELS], model_k3;   // ... R_high g1, R_low g1 of model m; n_e / n_i g2
+  int n_units;                                // ... > 0 (with n_models > 0): density units too, a lane per (ray, model, unit, frequency), row (m n_units + u) n_nu + l
+  double unit_x[BL_TRANSFER_MAX_UNITS], unit_j[BL_TRANSFER_MAX_UNITS];   // ... unit u's factors on x at unit frequency and on s_j
   long long n_rays_total;
   double *image;              // [n_q][n_rays_total]; rows 0..n_nu-1 = I_nu
   int *out_sample_num;        // [n_rays_total] or null

@@ -192,10 +192,13 @@ struct RenderJob {
   size_t park_capacity = 0;
   int quad_grid = 0;          // waves of bl_geodesic_quad_kernel
   int n_nu = 0, n_q = 0, max_steps = 0;
-  // bl_set_electron_models: n_models pairs (0: the parameter block's), n_q_model image rows each (n_q = n_models x n_q_model);
-  // the shading stage runs once per model over the chunk's samples (model_passes)
-  int n_models = 0, n_q_model = 0, model_passes = 1;
-  bool models_one_pass = false;   // ... or all of them in one pass: one gather, one lane per (ray, model, frequency) in the transfer kernel
+  // bl_set_electron_models / bl_set_density_units: n_models pairs, n_units units (0: the parameter block's), a variant is a (model,
+  // unit) with n_q_model image rows (n_q = max(1, n_models) x max(1, n_units) x n_q_model, model-major); the shading stage runs once
+  // per variant over the chunk's samples (variant_passes)
+  int n_models = 0, n_units = 0, n_q_model = 0, variant_passes = 1;
+  bool variants_one_pass = false;   // ... or all of them in one pass: one gather, one lane per (ray, model, unit, frequency) in the transfer kernel
+  double base_rho = 0.0;            // the unit BuildShadeArgs folds: the one set unit, else the parameter block's (one pass: the rows' unit)
+  int n_cold = 1;                   // BlShadeCold blocks on the device: one per unit where the passes' cut thresholds differ (BindVariant)
   long long n_rays = 0, level_pixels = 0;
   size_t redo_capacity = 0;
   // scratch
@@ -248,22 +251,63 @@ struct RenderJob {
 
 hipEvent_t *SlotEvents(RenderJob &job, int k) { return job.ctx->events.data() + static_cast<size_t>(k) * kEventsPerChunk; }
 
-// Electron model m of bl_set_electron_models into the argument blocks: its pair where the coefficient kernels read R_low / R_high
-// (the exact tier's BlPlasmaDevice, the tolerant tier's fast_k[1], fast_k[2] folded as BuildShadeArgs folds the parameter block's)
-// and its rows of the image. Without models nothing changes.
-void BindElectronModel(RenderJob &job, int m) {
-  bl_ctx *ctx = job.ctx;
-  if (job.n_models == 0 || job.models_one_pass) return;   // (one pass: the transfer kernel has every model's constants, BuildTransferArgs)
+// A density unit (simulation_rho_cgs) and the electron model in pl.plasma_rat_low / _high into what the coefficient kernels read:
+// BlPlasmaDevice's units (simulation_coefficients.cpp:237-239) and the tolerant tier's constants fast_k. BuildShadeArgs folds the
+// render's, BindVariant each variant's - one arithmetic, so that a variant has the bits of a fresh render with that unit and pair.
+void FoldUnits(const bl_ctx *ctx, double rho_cgs, BlPlasmaDevice &pl, double (&fast_k)[8]) {
   const bl_params &p = ctx->params;
-  const double rat_low = ctx->model_rat_low[m], rat_high = ctx->model_rat_high[m];
-  job.sa.plasma.plasma_rat_low = rat_low;
-  job.sa.plasma.plasma_rat_high = rat_high;
-  if (job.fast) {
-    const double g1 = p.plasma_use_p != 0 ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_i - 1.0);
-    job.sa.fast_k[1] = rat_high * g1;
-    job.sa.fast_k[2] = rat_low * g1;
+  pl.d_unit = rho_cgs;
+  pl.e_unit = pl.d_unit * kC * kC;
+  pl.b_unit = blm_sqrt(4.0 * kPi * pl.e_unit);
+  const bool use_p = p.plasma_use_p != 0;
+  const double g0 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma - 1.0);
+  const double g1 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_i - 1.0);
+  const double g2 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_e - 1.0);
+  const double n_e_per_rho = pl.d_unit / (p.plasma_mu * kMp * (1.0 + 1.0 / p.plasma_ne_ni));
+  const double nu_c_over_b = kE * pl.b_unit / (2.0 * kPi * kMe * kC);
+  fast_k[0] = (1.0 + p.plasma_ne_ni) * p.plasma_mu * kMp * pl.e_unit / pl.d_unit * g0;
+  fast_k[1] = pl.plasma_rat_high * g1;
+  fast_k[2] = pl.plasma_rat_low * g1;
+  fast_k[3] = p.plasma_ne_ni * g2;
+  fast_k[4] = (kMe * kC * kC) * (kMe * kC * kC) * 4.5 / nu_c_over_b;
+  fast_k[5] = ctx->plasma_thermal_frac * n_e_per_rho * kE * kE * nu_c_over_b / kC * (kSqrt2 * kPi / 27.0);
+  fast_k[6] = n_e_per_rho;
+  fast_k[7] = nu_c_over_b;
+}
+
+// ... and the tolerant tier's cell cut thresholds, which it compares in code units (rho, rho for n_e, p, k T_e for Theta_e, |b| in
+// code units; sigma and 1 / beta have none): scaled once here by pl's units; the guard band is relative and scales with them
+void FoldFastCuts(const bl_ctx *ctx, const BlPlasmaDevice &pl, BlShadeCold &cold) {
+  const bl_params &p = ctx->params;
+  const double cuts[14] = {p.cut_rho_min, p.cut_rho_max, p.cut_n_e_min, p.cut_n_e_max, p.cut_p_gas_min, p.cut_p_gas_max,
+                           p.cut_theta_e_min, p.cut_theta_e_max, p.cut_b_min, p.cut_b_max, p.cut_sigma_min, p.cut_sigma_max,
+                           p.cut_beta_inverse_min, p.cut_beta_inverse_max};
+  for (int c = 0; c < 14; c++) {
+    const bool active = cuts[c] >= 0.0;
+    const double n_e_per_rho = pl.d_unit / (p.plasma_mu * kMp * (1.0 + 1.0 / p.plasma_ne_ni));
+    const double to_code[7] = {1.0 / pl.d_unit, 1.0 / n_e_per_rho, 1.0 / pl.e_unit, kMe * kC * kC, 1.0 / pl.b_unit, 1.0, 1.0};
+    const double scaled = cuts[c] * to_code[c >> 1];
+    cold.fast_cut[c] = active ? scaled : 0.0;
+    cold.fast_cut_lo[c] = active ? scaled * (1.0 - ctx->guard_band) : 0.0;
+    cold.fast_cut_hi[c] = active ? scaled * (1.0 + ctx->guard_band) : 0.0;
   }
-  job.xa.image = job.image + static_cast<size_t>(m) * job.n_q_model * static_cast<size_t>(job.n_rays);
+}
+
+// Variant v = m * max(1, n_units) + u of bl_set_electron_models x bl_set_density_units into the argument blocks: model m's pair
+// where the coefficient kernels read R_low / R_high, unit u folded as BuildShadeArgs folds the render's (FoldUnits), the cut
+// thresholds of unit u (its BlShadeCold, uploaded by BuildShadeArgs), and the variant's rows of the image. With neither models nor
+// two units there is one variant, the one BuildShadeArgs folded: nothing changes.
+void BindVariant(RenderJob &job, int v) {
+  bl_ctx *ctx = job.ctx;
+  if (job.variants_one_pass || (job.n_models == 0 && job.n_units <= 1)) return;   // (one pass: the transfer kernel has every variant's constants, BuildTransferArgs)
+  const bl_params &p = ctx->params;
+  const int n_u = std::max(1, job.n_units), m = v / n_u, u = v % n_u;
+  BlPlasmaDevice &pl = job.sa.plasma;
+  pl.plasma_rat_low = job.n_models > 0 ? ctx->model_rat_low[m] : p.plasma_rat_low;
+  pl.plasma_rat_high = job.n_models > 0 ? ctx->model_rat_high[m] : p.plasma_rat_high;
+  FoldUnits(ctx, job.n_units > 0 ? ctx->density_units[u] : p.simulation_rho_cgs, pl, job.sa.fast_k);
+  job.sa.cold = ctx->d_shade_cold.ptr + (job.n_cold > 1 ? u : 0);
+  job.xa.image = job.image + static_cast<size_t>(v) * job.n_q_model * static_cast<size_t>(job.n_rays);
 }
 
 // ---- plan: validation of the call, the path it takes
@@ -291,10 +335,13 @@ void PlanJob(RenderJob &job) {
   }
   job.n_models = static_cast<int>(ctx->model_rat_low.size());
   if (const char *why = ElectronModelsRefusal(ctx, job.n_models)) throw Failure{BL_E_UNSUPPORTED, why};
+  job.n_units = static_cast<int>(ctx->density_units.size());
+  if (const char *why = DensityUnitsRefusal(ctx, job.n_units)) throw Failure{BL_E_UNSUPPORTED, why};
+  job.base_rho = job.n_units == 1 ? ctx->density_units[0] : p.simulation_rho_cgs;
   job.n_nu = p.image_num_frequencies;
   job.n_q_model = ctx->image_num_quantities;
-  job.n_q = job.n_q_model * std::max(1, job.n_models);
-  job.model_passes = std::max(1, job.n_models);
+  job.variant_passes = std::max(1, job.n_models) * std::max(1, job.n_units);
+  job.n_q = job.n_q_model * job.variant_passes;
   job.max_steps = p.ray_max_steps;
   job.n_rays = d->n_rays;
   job.aux = ctx->aux_images.any != 0;
@@ -354,15 +401,21 @@ void PlanJob(RenderJob &job) {
   // Several frequencies in the fast path: per-sample factors (BlFreqInputs) instead of per-frequency transfer records,
   // evaluated by bl_transfer_freq_kernel with one lane per ray and frequency
   job.freq_split = job.fast && job.n_nu >= 4 && p.plasma_power_frac == 0.0 && !job.tau_row;   // (the factors are the thermal formulas')
-  // Electron models in one pass: where the factors would apply, the image holds intensities only and no Theta_e cut decides differently
-  // between models, a sample's row holds what no model enters (BlFreqInputs) and the transfer kernel forms each model's 1 / (k T_e)
-  // (everything else: one shading pass per model over the shared samples, LaunchShadingStage)
-  job.models_one_pass = job.n_models >= 2 && job.fast && p.plasma_power_frac == 0.0 && !job.tau_row && !job.aux && ctx->render_num_images == 0
-      && p.cut_theta_e_min < 0.0 && p.cut_theta_e_max < 0.0;
-  if (job.models_one_pass) {
+  // Electron models and density units in one pass: where the factors would apply, the image holds intensities only and no Theta_e cut
+  // decides differently between models - nor, with two units or more, a rho, n_e, p_gas or B cut between units - a sample's row holds
+  // what no model enters (BlFreqInputs, built with base_rho) and the transfer kernel forms each model's 1 / (k T_e) and scales the row
+  // to each unit (everything else: one shading pass per variant over the shared samples, LaunchShadingStage)
+  const bool unit_cut = p.cut_rho_min >= 0.0 || p.cut_rho_max >= 0.0 || p.cut_n_e_min >= 0.0 || p.cut_n_e_max >= 0.0
+      || p.cut_p_gas_min >= 0.0 || p.cut_p_gas_max >= 0.0 || p.cut_b_min >= 0.0 || p.cut_b_max >= 0.0;
+  job.variants_one_pass = job.variant_passes >= 2 && job.fast && p.plasma_power_frac == 0.0 && !job.tau_row && !job.aux && ctx->render_num_images == 0
+      && p.cut_theta_e_min < 0.0 && p.cut_theta_e_max < 0.0 && !(job.n_units >= 2 && unit_cut)
+      && !(job.n_units >= 2 && job.n_rays * job.n_nu * job.variant_passes >= (1ll << 31));   // (the transfer kernel's lanes of a chunk fit one grid)
+  if (job.variants_one_pass) {
     job.freq_split = true;
-    job.model_passes = 1;
+    job.variant_passes = 1;
   }
+  // (the passes of two units or more compare the cut thresholds of their own unit: one BlShadeCold each)
+  job.n_cold = job.simulation && job.variant_passes >= 2 && job.n_units >= 2 ? job.n_units : 1;
   // Plain images of a spherical Kerr-Schild simulation with fallback values beyond the grid: nothing is recorded of the steps that
   // lie in the empty shell between the grid's outer edge and the camera's sphere (both tiers; the samples count as ever)
   job.skip_shell = job.simulation && !job.aux && !ctx->polarized && !job.slow && !job.geo_load && !job.geo_save && !job.sample_save
@@ -446,7 +499,7 @@ void PlanJob(RenderJob &job) {
   // order - not the 8 x 8 tiles, centre first, that make chunks drain faster - so that what a chunk finishes is a range of columns,
   // downloaded while the next chunk renders (the image rows of a 4096^2 x 64 frame are 8.6 GB: 0.7 s of PCIe that used to follow the
   // last kernel)
-  // (one electron model's rows decide: the trace order is part of the resident geodesics' key, which the models must not change)
+  // (one variant's rows decide: the trace order is part of the resident geodesics' key, which the models and units must not change)
   job.raster = !d->outputs_on_device && d->level == 0 && d->pixel_map == nullptr && job.n_q_model >= 8
       && static_cast<uint64_t>(job.n_q_model) * static_cast<uint64_t>(job.n_rays) * sizeof(double) >= (256ull << 20) && !job.geo_load && !job.geo_save && !job.sample_save;
 }
@@ -1299,14 +1352,12 @@ void BuildShadeArgs(RenderJob &job) {
   sa.plasma.fallback_nan = p.fallback_nan;   // (formula mode too: a flagged ray's coefficients are NaN there as well, formula_coefficients.cpp:51-59)
   if (job.simulation) {
     BlPlasmaDevice &pl = sa.plasma;
-    pl.d_unit = p.simulation_rho_cgs;                       // simulation_coefficients.cpp:237-239
-    pl.e_unit = pl.d_unit * kC * kC;
-    pl.b_unit = blm_sqrt(4.0 * kPi * pl.e_unit);
     pl.plasma_mu = p.plasma_mu;
     pl.plasma_ne_ni = p.plasma_ne_ni;
     pl.plasma_rat_low = p.plasma_rat_low;
     pl.plasma_rat_high = p.plasma_rat_high;
     pl.plasma_thermal_frac = ctx->plasma_thermal_frac;
+    FoldUnits(ctx, job.base_rho, pl, sa.fast_k);            // simulation_coefficients.cpp:237-239 (bl_set_density_units: BindVariant)
     FillElectronConstants(job, pl, cold);
     cold.plasma_gamma = ctx->grid_meta.plasma_gamma;
     cold.plasma_gamma_i = ctx->grid_meta.plasma_gamma_i;
@@ -1346,31 +1397,8 @@ void BuildShadeArgs(RenderJob &job) {
         const bool active = cuts[c] >= 0.0;
         if (active) pl.cut_mask |= 1 << c;
         if (active) pl.any_cell_cut = 1;
-        // the fast kernels compare in code units (rho, rho for n_e, p, k T_e for Theta_e, |b| in code units; sigma and 1 / beta have
-        // none): the thresholds are scaled once here, the guard band is relative and scales with them
-        const double n_e_per_rho = pl.d_unit / (p.plasma_mu * kMp * (1.0 + 1.0 / p.plasma_ne_ni));
-        const double to_code[7] = {1.0 / pl.d_unit, 1.0 / n_e_per_rho, 1.0 / pl.e_unit, kMe * kC * kC, 1.0 / pl.b_unit, 1.0, 1.0};
-        const double scaled = cuts[c] * to_code[c >> 1];
-        cold.fast_cut[c] = active ? scaled : 0.0;
-        cold.fast_cut_lo[c] = active ? scaled * (1.0 - ctx->guard_band) : 0.0;
-        cold.fast_cut_hi[c] = active ? scaled * (1.0 + ctx->guard_band) : 0.0;
       }
-      {
-        const bool use_p = p.plasma_use_p != 0;
-        const double g0 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma - 1.0);
-        const double g1 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_i - 1.0);
-        const double g2 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_e - 1.0);
-        const double n_e_per_rho = pl.d_unit / (p.plasma_mu * kMp * (1.0 + 1.0 / p.plasma_ne_ni));
-        const double nu_c_over_b = kE * pl.b_unit / (2.0 * kPi * kMe * kC);
-        sa.fast_k[0] = (1.0 + p.plasma_ne_ni) * p.plasma_mu * kMp * pl.e_unit / pl.d_unit * g0;
-        sa.fast_k[1] = p.plasma_rat_high * g1;
-        sa.fast_k[2] = p.plasma_rat_low * g1;
-        sa.fast_k[3] = p.plasma_ne_ni * g2;
-        sa.fast_k[4] = (kMe * kC * kC) * (kMe * kC * kC) * 4.5 / nu_c_over_b;
-        sa.fast_k[5] = ctx->plasma_thermal_frac * n_e_per_rho * kE * kE * nu_c_over_b / kC * (kSqrt2 * kPi / 27.0);
-        sa.fast_k[6] = n_e_per_rho;
-        sa.fast_k[7] = nu_c_over_b;
-      }
+      FoldFastCuts(ctx, pl, cold);   // (the fast kernels' thresholds in code units)
       sa.fast_angle_band = std::max(1.0e-12, ctx->guard_band > 1.0e-8 ? ctx->guard_band : 0.0);   // (the debug switch widens both kinds of band)
     }
     sa.grid = ctx->grid_dev;
@@ -1388,13 +1416,28 @@ void BuildShadeArgs(RenderJob &job) {
   }
   sa.samples_renormalised = job.geo_load ? 1 : 0;
   sa.general_locate = (ctx->switches & BL_SWITCH_GENERAL_LOCATE) ? 1 : 0;
+  // One block per unit where the passes of two units or more compare their own cut thresholds (job.n_cold; BindVariant points at its
+  // unit's): the render's block with the thresholds refolded, byte for byte otherwise
+  std::vector<unsigned char> colds(job.n_cold * sizeof(BlShadeCold));
+  for (int u = 0; u < job.n_cold; u++) {
+    std::memcpy(colds.data() + u * sizeof(BlShadeCold), &cold, sizeof(BlShadeCold));
+    if (job.n_cold > 1) {
+      BlShadeCold unit_cold;
+      std::memcpy(static_cast<void *>(&unit_cold), &cold, sizeof(BlShadeCold));
+      BlPlasmaDevice unit_pl = sa.plasma;
+      double unit_k[8];
+      FoldUnits(ctx, ctx->density_units[u], unit_pl, unit_k);
+      FoldFastCuts(ctx, unit_pl, unit_cold);
+      std::memcpy(colds.data() + u * sizeof(BlShadeCold), &unit_cold, sizeof(BlShadeCold));
+    }
+  }
   // (uploaded when it differs from what the device holds: a frame loop uploads it once and waits for nothing here)
-  if (ctx->shade_cold_host.size() != sizeof(BlShadeCold) || std::memcmp(ctx->shade_cold_host.data(), &cold, sizeof(BlShadeCold)) != 0) {
-    ctx->d_shade_cold.Ensure(1);
+  if (ctx->shade_cold_host != colds) {
+    ctx->d_shade_cold.Ensure(job.n_cold);
     ctx->shade_cold_host.clear();   // (what the device holds is unknown until the copy has completed)
-    Check(hipMemcpyAsync(ctx->d_shade_cold.ptr, &cold, sizeof(BlShadeCold), hipMemcpyHostToDevice, stream), "shade parameter upload");
+    Check(hipMemcpyAsync(ctx->d_shade_cold.ptr, colds.data(), colds.size(), hipMemcpyHostToDevice, stream), "shade parameter upload");
     Check(hipStreamSynchronize(stream), "shade parameter upload");
-    ctx->shade_cold_host.assign(reinterpret_cast<const unsigned char *>(&cold), reinterpret_cast<const unsigned char *>(&cold) + sizeof(BlShadeCold));
+    ctx->shade_cold_host = colds;
   }
   sa.cold = ctx->d_shade_cold.ptr;
   sa.frequencies = ctx->d_freq.ptr;
@@ -1407,7 +1450,7 @@ void BuildShadeArgs(RenderJob &job) {
   sa.aux_record_unused = job.rows_only ? 1 : 0;
   for (int mu = 0; mu < 4; mu++) sa.cam_x[mu] = ctx->frame.cam_x[mu];
   sa.tag_in_record = job.fast ? 1 : 0;
-  sa.freq_split = job.freq_split ? (job.models_one_pass ? 2 : 1) : 0;
+  sa.freq_split = job.freq_split ? (job.variants_one_pass ? 2 : 1) : 0;
   sa.coef_split = job.coef_split ? 1 : 0;
   sa.redo_capacity = (job.fast || job.fast_formula || ctx->polarized) ? job.redo_capacity : 0;
 
@@ -1460,17 +1503,33 @@ void BuildTransferArgs(RenderJob &job) {
   xa.n_rays_total = job.n_rays;
   xa.image = job.image;
   xa.n_models = 0;
-  if (job.models_one_pass) {   // every model's R_high / R_low folded as BuildShadeArgs folds the parameter block's (fast_k[1..3])
+  xa.n_units = 0;
+  if (job.variants_one_pass) {   // every model's R_high / R_low folded as BuildShadeArgs folds the parameter block's (fast_k[1..3])
     static_assert(BL_TRANSFER_MAX_MODELS == BL_MAX_ELECTRON_MODELS, "model constants");
+    static_assert(BL_TRANSFER_MAX_UNITS == BL_MAX_DENSITY_UNITS, "unit constants");
     const bool use_p = p.plasma_use_p != 0;
     const double g1 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_i - 1.0);
     const double g2 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_e - 1.0);
-    xa.n_models = job.n_models;
-    for (int m = 0; m < job.n_models; m++) {
-      xa.model_k1[m] = ctx->model_rat_high[m] * g1;
-      xa.model_k2[m] = ctx->model_rat_low[m] * g1;
+    xa.n_models = std::max(1, job.n_models);   // (no models set: the parameter block's pair is model 0)
+    for (int m = 0; m < xa.n_models; m++) {
+      xa.model_k1[m] = (job.n_models > 0 ? ctx->model_rat_high[m] : p.plasma_rat_high) * g1;
+      xa.model_k2[m] = (job.n_models > 0 ? ctx->model_rat_low[m] : p.plasma_rat_low) * g1;
     }
     xa.model_k3 = p.plasma_ne_ni * g2;
+    // Two units or more: the rows hold base_rho's x at unit frequency (1 / b_unit: x = nu / nu_s, nu_s ~ nu_c ~ |b| b_unit) and s_j
+    // (d_unit b_unit: n_e nu_c); unit u scales them by b_unit(base) / b_unit(u) and d_u b_unit(u) / (d_base b_unit(base)), with the
+    // units of FoldUnits. (One unit is base_rho itself: the rows are that unit's.)
+    if (job.n_units >= 2) {
+      BlPlasmaDevice base{}, unit{};
+      double k[8];
+      FoldUnits(ctx, job.base_rho, base, k);
+      xa.n_units = job.n_units;
+      for (int u = 0; u < job.n_units; u++) {
+        FoldUnits(ctx, ctx->density_units[u], unit, k);
+        xa.unit_x[u] = base.b_unit / unit.b_unit;
+        xa.unit_j[u] = (unit.d_unit * unit.b_unit) / (base.d_unit * base.b_unit);
+      }
+    }
   }
   xa.out_sample_num = job.out_num;
   xa.out_flags = job.out_flags;
@@ -1971,14 +2030,14 @@ void LaunchShadingStage(RenderJob &job, int k, bool geodesic_beside, hipStream_t
   if (job.simulation && !job.locate_inside && !job.reuse_located)
     Check(bl_launch_locate(&sa, geodesic_beside ? job.locate_grid_shared : job.locate_grid_alone, ctx->lds_table_bytes, stream), "locate kernel launch");
   Check(hipEventRecord(e[3], stream), "event");
-  for (int m = 0; m < job.model_passes; m++) {
-    if (m > 0) {   // what the shading stage adds to the chunk's counters starts again from zero (ClearShadingCounters)
+  for (int v = 0; v < job.variant_passes; v++) {
+    if (v > 0) {   // what the shading stage adds to the chunk's counters starts again from zero (ClearShadingCounters)
       unsigned long long *c = sl.d_counters.ptr;
       Check(hipMemsetAsync(c + BL_CNT_GATHERS, 0, sizeof *c, stream), "counter reset");
       Check(hipMemsetAsync(c + BL_CNT_UNDEFINED, 0, 3 * sizeof *c, stream), "counter reset");   // (UNDEFINED, INTERP_FAILED, REDO)
       Check(hipMemsetAsync(c + BL_CNT_COUNT, 0, 12 * sizeof *c, stream), "counter reset");
     }
-    BindElectronModel(job, m);
+    BindVariant(job, v);
     coefficient_kernel();
     // The transport matrices - memory - on the second stream beside the per-frequency coefficient kernel - arithmetic: both read what
     // bl_shade_polarized2_kernel left, neither reads the other. (The coefficient kernel's workgroups fill the device first, so the
@@ -2305,8 +2364,8 @@ void FinishStats(RenderJob &job) {
   st.launches_locate = (job.simulation && !job.locate_inside && !job.reuse_located) ? job.n_chunks : 0;
   st.geodesics_reused = job.reuse ? 1 : 0;
   st.sampling_reused = job.reuse_located ? 1 : 0;
-  st.launches_shade = job.n_chunks * job.model_passes;
-  st.launches_transfer = job.n_chunks * job.model_passes;
+  st.launches_shade = job.n_chunks * job.variant_passes;
+  st.launches_transfer = job.n_chunks * job.variant_passes;
   st.n_samples = static_cast<int64_t>(job.total_samples);
   st.n_samples_emitted = static_cast<int64_t>(job.total_records);
   st.n_gathers = static_cast<int64_t>(job.total_gathers);

@@ -3,7 +3,8 @@
 //   bl_transfer_kernel       one lane per (ray, frequency): replays the per-sample records far -> near in the reference's
 //                            order and scales by nu^3.   (unpolarized.cpp:71-110, :200-208)
 //   bl_transfer_quad_kernel  tolerant tier, one frequency: four lanes per ray, affine maps composed by a DPP scan
-//   bl_transfer_freq_kernel  tolerant tier, several frequencies: records built from per-sample factors on the fly
+//   bl_transfer_freq_kernel  tolerant tier, several frequencies - or electron models and density units in one pass: records
+//                            built from per-sample factors on the fly
 //   bl_transfer_aux_kernel   image_light and the nine auxiliary images.   (unpolarized.cpp:113-196)
 //   bl_tau_kernel            optical depth beside the intensities in the tolerant tier
 #include "bl_kernel_util.h"
@@ -16,13 +17,16 @@
 // and applies I <- a I + c at once. The per-frequency transfer records (16 bytes per sample and frequency: 1.5 TB written
 // and read per 1024^2 x 64-frequency frame) do not exist on this path; the exact second pass leaves the same factors.
 // With electron models in one pass (P.n_models > 0, wave-uniform) a lane is a (ray, model, frequency): the rows hold what no model
-// enters (BlFreqInputs), and the lane forms its model's 1 / (k T_e) per sample before the same step.
+// enters (BlFreqInputs), and the lane forms its model's 1 / (k T_e) per sample before the same step. With density units as well
+// (P.n_units > 0) a lane is a (ray, model, unit, frequency), and its unit scales the row's x at unit frequency and s_j (unit_x,
+// unit_j), folded into the lane's frequency terms once: no work per sample. (Without units the factors are 1.0: the same bits.)
 __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool models = P.n_models > 0;
-  const int channels = models ? P.n_models * P.n_nu : P.n_nu;
+  const int n_units = P.n_units > 0 ? P.n_units : 1;
+  const int channels = models ? P.n_models * n_units * P.n_nu : P.n_nu;
   const int slot = (int)(t / channels);
-  const int channel = (int)(t % channels);   // m n_nu + l: the image row
+  const int channel = (int)(t % channels);   // (m n_units + u) n_nu + l: the image row
   const int l = channel % P.n_nu;
   unsigned long long samples = 0ull, flagged = 0ull;
   int max_num = 0;
@@ -44,9 +48,14 @@ __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P)
     if (P.fallback_nan && flag) {
       intensity = num > 0 ? nan : 0.0;   // every sample of a flagged ray carries NaN primitives (simulation_sampling.cpp:211-216)
     } else {
-      const double f_1_2 = bl_sqrt_g(f), f_1_3 = fastmath::cbrt(f);
+      const int variant = channel / P.n_nu, m = variant / n_units, u = variant - m * n_units;
+      // Unit u's factors where no sample register holds them: x at unit frequency enters only as x f, so unit_x is a factor on the
+      // frequency of the x terms (f_1_2, f_1_3, f_1_6), and s_j only as s_j f^-2, so unit_j is one on f_inv2 (without units: 1.0)
+      const double ux = P.n_units > 0 ? P.unit_x[u] : 1.0, uj = P.n_units > 0 ? P.unit_j[u] : 1.0;
+      const double f_x = f * ux;
+      const double f_1_2 = bl_sqrt_g(f_x), f_1_3 = fastmath::cbrt(f_x);
       const double f_1_6 = bl_sqrt_g(f_1_3), f_inv = fastmath::rcp(f);
-      const double f_inv2 = f_inv * f_inv;
+      const double f_inv2 = f_inv * f_inv * uj;
       // (one exponential per sample and frequency is most of this loop: its constants stay in scalar registers across it)
       double exp_c[15];
 #pragma unroll
@@ -54,7 +63,6 @@ __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P)
       const double2 *in = reinterpret_cast<const double2 *>(P.freq_inputs + (size_t)P.ray_offset[slot]);
       const double kThird = fastmath::resident_constant(1.0 / 3.0), kInvPlanck = fastmath::resident_constant(kC * kC / (2.0 * kH));
       const double kRoot = fastmath::resident_constant(kPow2_11_12), kThin = fastmath::resident_constant(0x1p-10);
-      const int m = channel / P.n_nu;
       const double mk1 = models ? P.model_k1[m] : 0.0, mk2 = models ? P.model_k2[m] : 0.0, mk3 = P.model_k3;
       for (int n = num - 1; n >= 0; n--) {   // reference sample order is reversed integration order (geodesics.cpp:832-840)
         const double2 q0 = in[4 * (size_t)n], q1 = in[4 * (size_t)n + 1], q2 = in[4 * (size_t)n + 2], q3 = in[4 * (size_t)n + 3];
@@ -362,7 +370,7 @@ __global__ void __launch_bounds__(64) bl_transfer_aux_kernel(BlTransferArgs P) {
 }
 
 extern "C" hipError_t bl_launch_transfer_freq(const BlTransferArgs *args, hipStream_t stream) {
-  const long long lanes = (long long)args->chunk_rays * args->n_nu * (args->n_models > 0 ? args->n_models : 1);
+  const long long lanes = (long long)args->chunk_rays * args->n_nu * (args->n_models > 0 ? args->n_models * (args->n_units > 0 ? args->n_units : 1) : 1);
   hipLaunchKernelGGL(bl_transfer_freq_kernel, dim3((unsigned int)((lanes + 255) / 256)), dim3(256), 0, stream, *args);
   return hipGetLastError();
 }

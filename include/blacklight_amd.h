@@ -300,6 +300,8 @@ typedef struct bl_stats {
   /* Several electron models (bl_set_electron_models) where they cannot share one pass: launches_shade / launches_transfer count one
      shading pass per model and chunk; n_gathers, n_deferred and the sample counts are those of one pass (every pass has the same
      samples); ms_shade runs from the first coefficient kernel to the last one, ms_transfer is the last transfer kernel's. */
+  /* ... and density units (bl_set_density_units) likewise: one shading pass per (model, unit) and chunk, n_chunks * M * U launches;
+     where every variant shares one pass, n_chunks. */
 } bl_stats;
 
 /* Measurement switches: environment variables BLACKLIGHT_AMD_<NAME>, read ONCE by bl_init (never during a render) and echoed in
@@ -370,6 +372,22 @@ BL_API int bl_image_num_quantities(const bl_ctx *ctx);
 #define BL_MAX_ELECTRON_MODELS 16
 BL_API int bl_set_electron_models(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high);
 BL_API int bl_num_electron_models(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own model */
+/* Density units (simulation_rho_cgs, the code density in g / cm^3; simulation_coefficients.cpp:237-239) rendered by one bl_render -
+ * the normalisation a flux fit tunes. n = 0 (what a context starts with): the parameter block's own unit. 1 <= n <=
+ * BL_MAX_DENSITY_UNITS: n absolute values of simulation_rho_cgs, each finite and > 0. With M = max(1, electron models) and
+ * U = max(1, n), bl_image_num_quantities is M * U times the single-render count and image row (m * U + u) * n_q + q is row q of
+ * model m at unit u (model-major; sample_num, sample_flags and renderings come out once). Geodesics and located samples do not
+ * depend on the unit: changing the units between renders keeps them. Refused (BL_E_UNSUPPORTED): formula mode, polarized runs,
+ * slow light, and with n >= 2 adaptive_max_level > 0 and renderings that a unit enters (a rho, n_e, p_gas or B feature, or a cut
+ * on rho, n_e, p_gas or B beside renderings) - as are bl_adaptive_refine and bl_write_output while n >= 2. n = 1 renders that
+ * value instead of the parameter block's. The tolerant tier's plain intensity images without a Theta_e cut - and, with n >= 2,
+ * without a cut on rho, n_e, p_gas or B - render every (model, unit) in one pass: one gather and coefficient kernel, one transfer
+ * lane per (ray, model, unit, frequency), each within the tier's tolerance of its exact image. Everything else runs one shading pass per (model, unit) over the shared samples: each variant's
+ * image is what a render with that unit (and pair) in the parameter block gives (the same bits in the exact tier and under
+ * bl_set_reproducible). */
+#define BL_MAX_DENSITY_UNITS 16
+BL_API int bl_set_density_units(bl_ctx *ctx, int n, const double *rho_cgs);
+BL_API int bl_num_density_units(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own unit; -1: no context */
 /* Number of false-colour renderings bl_render produces (render_num_images; 0 in formula mode). */
 BL_API int bl_render_num_images(const bl_ctx *ctx);
 BL_API int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out);
