@@ -398,7 +398,10 @@ BL_API int bl_frequencies(const bl_ctx *ctx, double *out, int n);
  * reference's own windows of it, asserted at 1e-10 per pixel: tests/test_gpu_window_1024.py, test_gpu_configs_at_size.py) is used between the sampled primitives and the transfer record of a sample -
  * fused multiply-adds, lighter exp / expm1 / cbrt, the fluid-frame angle and frequency as invariants instead of through the tetrad
  * of simulation_coefficients.cpp:398-455, transport matrices in polarized runs. Ray-step counts, flags, cell indices, NaN masks and
- * every cut decision are those of the exact tier. Configurations the tier has no kernel for run in exact arithmetic regardless -
+ * every cut decision are those of the exact tier. Where a pixel's accumulator I / nu^3 reaches the bottom of the normal range - its
+ * samples' emission then passes through a subnormal exp(-x^(1/3)), whose unit 2^-1074 the exact tier carries as well - the bound is
+ * absolute instead: |I - I_exact| <= max(1e-10 |I_exact|, 2^-1022 nu^3), and only there may one tier's pixel be zero where the
+ * other's is a subnormal accumulator (tests/test_gpu_variant_edges.py). Configurations the tier has no kernel for run in exact arithmetic regardless -
  * bl_stats.arithmetic reports the tier that ran. BL_ARITH_EXACT: every operation in the reference's order with the pinned math
  * library - images equal the reference's bit for bit (tier-B goldens), at 0.57 of the tolerant tier's speed on the benchmark frame.
  * (Rounds 1 - 4 started contexts in the exact tier; the parity suite pins it through the environment variable, tests/conftest.py.) */

@@ -1801,7 +1801,8 @@ void GeodesicConnection(const Oracle &o, double x, double y, double z, double co
 // stride between frequencies, zero on entry.
 void SimulationCoefficientsOne(const Oracle &o, const double pos[4], const double kcov_in[4],
                                const Prims &s, double momentum_factor, double *j, double *alpha,
-                               int stride, double cell[num_cell_values], double *const pol[6] = nullptr) {
+                               int stride, double cell[num_cell_values], double *const pol[6] = nullptr,
+                               double *kte_out = nullptr) {
   const bl_params &p = *o.p;
   double d_unit = p.simulation_rho_cgs;  // :237-239
   double e_unit = d_unit * Physics::c * Physics::c;
@@ -1904,6 +1905,7 @@ void SimulationCoefficientsOne(const Oracle &o, const double pos[4], const doubl
   if (not (p.image_light or p.image_emission or p.image_tau or p.image_emission_ave or p.image_tau_int))
     return;
   if (bb1_sim == 0.0 and bb2_sim == 0.0 and bb3_sim == 0.0) return;  // :394
+  if (kte_out != nullptr) *kte_out = kb_tt_e_cgs;   // (blo_dump_coefficients::kte: the samples that get coefficients)
 
   CoordinateJacobian(o, x1, x2, x3, jacobian);  // :398-408
   double ucon[4] = {};
@@ -2972,6 +2974,12 @@ const char *blo_build_info(void) {
 int blo_render(const bl_params *p, const bl_grid_desc *g, const bl_render_desc *d,
                bl_camera_frame *frame, double *frequencies, blo_extra *extra, char *err,
                size_t err_len) {
+  return blo_render_dump(p, g, d, frame, frequencies, extra, nullptr, err, err_len);
+}
+
+int blo_render_dump(const bl_params *p, const bl_grid_desc *g, const bl_render_desc *d,
+                    bl_camera_frame *frame, double *frequencies, blo_extra *extra,
+                    const blo_dump_coefficients *dump, char *err, size_t err_len) {
   if (p == nullptr || d == nullptr) return BL_E_ARG;
   if (d->outputs_on_device) return Fail(err, err_len, "oracle works on host memory only", BL_E_ARG);
   Oracle o{};
@@ -3057,6 +3065,10 @@ int blo_render(const bl_params *p, const bl_grid_desc *g, const bl_render_desc *
         std::memcpy(extra->dump_len, b.sample_len.data(), sizeof(double) * sample_num);
         extra->dump_num = sample_num;
       }
+      const bool dump_coefficients = dump != nullptr && extra != nullptr && extra->dump_ray == ray;
+      double *const dump_kte = dump_coefficients ? dump->kte : nullptr;
+      if (dump_kte != nullptr)
+        for (int n = 0; n < sample_num; n++) dump_kte[n] = std::numeric_limits<double>::quiet_NaN();
 
       // coefficients: zero-initialised like j_i.Zero() / alpha_i.Zero(), cell_values NaN
       for (int l = 0; l < nf; l++)
@@ -3109,7 +3121,8 @@ int blo_render(const bl_params *p, const bl_grid_desc *g, const bl_render_desc *
             for (int c = 0; c < 6; c++) b.sample_ub[6 * n + c] = ub[c];
           }
           SimulationCoefficientsOne(o, &b.sample_pos[4 * n], &b.sample_dir[4 * n], s, factor,
-                                    &b.j_i[n], &b.alpha_i[n], max_steps, cell, o.image_polarization ? pol : nullptr);
+                                    &b.j_i[n], &b.alpha_i[n], max_steps, cell, o.image_polarization ? pol : nullptr,
+                                    dump_kte != nullptr ? &dump_kte[n] : nullptr);
           for (int a = 0; a < num_cell_values; a++) b.cell_values[a * static_cast<size_t>(max_steps) + n] = cell[a];
         }
         if (block_state.extrap[0]) { count_0++; val_0 = std::max(val_0, block_state.extrap_val[0]); }   // :553-575
@@ -3126,6 +3139,15 @@ int blo_render(const bl_params *p, const bl_grid_desc *g, const bl_render_desc *
           for (int n = 0; n < sample_num; n++)
             FormulaCoefficientsOne(o, &b.sample_pos[4 * n], &b.sample_dir[4 * n], factor, &b.j_i[n],
                                    &b.alpha_i[n], max_steps);
+      }
+      if (dump_coefficients) {   // frequency 0's coefficients and optical depths as IntegrateUnpolarizedOne forms them
+        const double x_unit = Physics::gg_msun * o.mass_msun / (Physics::c * Physics::c);
+        for (int n = 0; n < sample_num; n++) {
+          const double delta_lambda_cgs = b.sample_len[n] * x_unit / (o.image_frequencies[0] * factor);
+          if (dump->j != nullptr) dump->j[n] = b.j_i[n];
+          if (dump->alpha != nullptr) dump->alpha[n] = b.alpha_i[n];
+          if (dump->dtau != nullptr) dump->dtau[n] = b.alpha_i[n] * delta_lambda_cgs;
+        }
       }
       if (o.image_polarization)
         IntegratePolarizedOne(o, b, sample_num, max_steps, factor, cpos, cdir, image_col.data());

@@ -49,11 +49,24 @@ typedef struct blo_extra {
   int32_t define_kappa_aa_high_i;
 } blo_extra;
 
+/* Optional, beside blo_extra::dump_ray (blo_render_dump): that ray's per-sample k T_e (erg), j_nu, alpha_nu and delta tau = alpha_nu
+   delta lambda_cgs at frequency 0, in the order of dump_pos; buffers sized ray_max_steps, each may be NULL. Samples without
+   coefficients (cut, off the grid, zero field, a flagged ray) keep j_nu = alpha_nu = 0 as the integration sees them, and k T_e = NaN:
+   k T_e is that of the samples that reach the coefficients (simulation_coefficients.cpp:394), whose j_nu = 0 only where it
+   underflows. A struct of its own, not fields of blo_extra, so that callers built against blo_extra's layout keep working. */
+typedef struct blo_dump_coefficients {
+  double *kte, *j, *alpha, *dtau;
+} blo_dump_coefficients;
+
 /* Same contract as bl_render() with host pointers (d->outputs_on_device must be 0). g may be NULL
  * in formula mode. frame (optional) receives the camera frame. */
 int blo_render(const bl_params *p, const bl_grid_desc *g, const bl_render_desc *d,
                bl_camera_frame *frame, double *frequencies, blo_extra *extra, char *err,
                size_t err_len);
+/* blo_render() that also fills dump (may be NULL) for the ray extra->dump_ray */
+int blo_render_dump(const bl_params *p, const bl_grid_desc *g, const bl_render_desc *d,
+                    bl_camera_frame *frame, double *frequencies, blo_extra *extra,
+                    const blo_dump_coefficients *dump, char *err, size_t err_len);
 
 /* number of image rows for these parameters (radiation_integrator.cpp:436-520) */
 int blo_image_num_quantities(const bl_params *p);

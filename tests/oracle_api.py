@@ -25,6 +25,10 @@ class Extra(C.Structure):
     ]
 
 
+class DumpCoefficients(C.Structure):   # blo_dump_coefficients
+    _fields_ = [("kte", C.c_void_p), ("j", C.c_void_p), ("alpha", C.c_void_p), ("dtau", C.c_void_p)]
+
+
 def _host_has_fma():
     try:
         with open("/proc/cpuinfo") as f:
@@ -62,7 +66,9 @@ def render(params_ptr, grid_desc, desc_cls, camera_frame_cls, *, n_rays, level=0
     """Run the oracle. Returns dict(image, sample_num, sample_flags, frame, frequencies, extra...).
     n_render > 0: also the false-colour renderings, (n_render, 3, n_rays).
     slow = dict(grids=[bl_grid_desc, ...] latest first, times=[...], snapshot_time=t): slow light.
-    define_kappa: unpolarized kappa-distribution electrons with kappa_aa_high_i as in polarized runs (blo_extra)."""
+    define_kappa: unpolarized kappa-distribution electrons with kappa_aa_high_i as in polarized runs (blo_extra).
+    dump_ray >= 0 (buffers of max_steps samples): out["dump"] holds that ray's samples in reference order - pos, dir, len, and at
+    frequency 0 kte (k T_e in erg; NaN for samples without coefficients), j, alpha (j_nu, alpha_nu) and dtau (alpha_nu delta lambda_cgs)."""
     L = load(variant)
     n_q = L.blo_image_num_quantities(params_ptr)
     image = np.zeros((max(n_q, 1), n_rays), dtype=np.float64)
@@ -105,10 +111,11 @@ def render(params_ptr, grid_desc, desc_cls, camera_frame_cls, *, n_rays, level=0
     extra.dump_ray = dump_ray
     dump = None
     if dump_ray >= 0:
-        dump = dict(pos=np.zeros((max_steps, 4)), dir=np.zeros((max_steps, 4)), len=np.zeros(max_steps))
-        extra.dump_pos = dump["pos"].ctypes.data_as(C.c_void_p)
-        extra.dump_dir = dump["dir"].ctypes.data_as(C.c_void_p)
-        extra.dump_len = dump["len"].ctypes.data_as(C.c_void_p)
+        dump = dict(pos=np.zeros((max_steps, 4)), dir=np.zeros((max_steps, 4)), len=np.zeros(max_steps),
+                    kte=np.zeros(max_steps), j=np.zeros(max_steps), alpha=np.zeros(max_steps), dtau=np.zeros(max_steps))
+        for name in ("pos", "dir", "len"):
+            setattr(extra, f"dump_{name}", dump[name].ctypes.data_as(C.c_void_p))
+        coefficients = DumpCoefficients(*[dump[name].ctypes.data_as(C.c_void_p) for name in ("kte", "j", "alpha", "dtau")])
     if slow is not None:
         grid_ptrs = (C.c_void_p * len(slow["grids"]))(*[C.addressof(g) for g in slow["grids"]])
         times = np.ascontiguousarray(slow["times"], dtype=np.float64)
@@ -119,8 +126,12 @@ def render(params_ptr, grid_desc, desc_cls, camera_frame_cls, *, n_rays, level=0
         extra.slow_snapshot_time = float(slow["snapshot_time"])
     err = C.create_string_buffer(1024)
     grid_ptr = C.byref(grid_desc) if grid_desc is not None else None
-    rc = L.blo_render(params_ptr, grid_ptr, C.byref(d), C.byref(frame),
-                      freqs.ctypes.data_as(C.c_void_p), C.byref(extra), err, C.c_size_t(len(err)))
+    if dump is not None:
+        rc = L.blo_render_dump(params_ptr, grid_ptr, C.byref(d), C.byref(frame), freqs.ctypes.data_as(C.c_void_p), C.byref(extra),
+                               C.byref(coefficients), err, C.c_size_t(len(err)))
+    else:
+        rc = L.blo_render(params_ptr, grid_ptr, C.byref(d), C.byref(frame),
+                          freqs.ctypes.data_as(C.c_void_p), C.byref(extra), err, C.c_size_t(len(err)))
     if rc != 0:
         raise RuntimeError(f"oracle failed ({rc}): {err.value.decode()}")
     out = dict(image=image[:n_q], sample_num=sample_num, sample_flags=sample_flags, frame=frame,
@@ -130,5 +141,5 @@ def render(params_ptr, grid_desc, desc_cls, camera_frame_cls, *, n_rays, level=0
                slow_count=list(extra.slow_count), slow_val=list(extra.slow_val))
     if dump is not None:
         n = extra.dump_num
-        out["dump"] = dict(pos=dump["pos"][:n], dir=dump["dir"][:n], len=dump["len"][:n])
+        out["dump"] = {name: arr[:n] for name, arr in dump.items()}
     return out
