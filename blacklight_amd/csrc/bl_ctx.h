@@ -236,16 +236,20 @@ struct bl_ctx {
     DeviceBuffer<unsigned char> d_have_flags;      // ... where bl_shade_polarized2_kernel evaluates the coefficients itself: which records have them
     DeviceBuffer<unsigned long long> d_redo;       // tolerant tier: records left to the exact coefficient kernel
     DeviceBuffer<double> d_tau_inc;                // tolerant tier with an optical-depth image: alpha x length per sample and frequency
+    DeviceBuffer<unsigned long long> d_xcd_state;  // trace order per XCD: queue heads, list lengths, cursors (BlTraceArgs::xcd_state)
+    DeviceBuffer<unsigned int> d_xcd_lists;        // ... the record lists, BL_XCD_QUEUES of them
     uint64_t Bytes() const {
       return d_records_hot.count * sizeof(BlSampleHot) + d_records_cold.count * sizeof(BlSampleCold) + d_located.count * sizeof(BlLocated)
           + d_located_tag.count * sizeof(unsigned long long) + (d_transfer.count + d_composed.count) * sizeof(double2) + d_parked.count * sizeof(double) + d_aux.count * sizeof(BlAuxSample)
           + (d_sample_t.count + d_slow_frac.count + d_pol_matrix.count + d_tau_inc.count) * sizeof(double) + d_pol_samples.count * sizeof(BlPolSample)
           + d_freq_inputs.count * sizeof(BlFreqInputs) + d_pol_coeffs.count * sizeof(double2) + d_anchors.count * sizeof(unsigned int)
-          + d_coef_inputs.count * sizeof(BlCoefInputs) + d_redo.count * sizeof(unsigned long long) + d_have_flags.count;
+          + d_coef_inputs.count * sizeof(BlCoefInputs) + d_redo.count * sizeof(unsigned long long) + d_have_flags.count
+          + d_xcd_state.count * sizeof(unsigned long long) + d_xcd_lists.count * sizeof(unsigned int);
     }
     void Free() {
       d_have_flags.Free(); d_redo.Free(); d_tau_inc.Free(); d_aux.Free(); d_sample_t.Free(); d_slow_frac.Free(); d_pol_samples.Free(); d_pol_matrix.Free(); d_freq_inputs.Free(); d_pol_coeffs.Free(); d_coef_inputs.Free(); d_anchors.Free();
       d_records_hot.Free(); d_records_cold.Free(); d_located.Free(); d_located_tag.Free(); d_transfer.Free(); d_composed.Free(); d_parked.Free(); d_counters.Free();
+      d_xcd_state.Free(); d_xcd_lists.Free();
     }
   };
   ChunkSlot slot[2];
@@ -256,6 +260,7 @@ struct bl_ctx {
   // buffers that change places, no copy).
   struct ResidentGeodesics {
     bool valid = false, parked = false;
+    bool super_tiles = false;                 // the tile order the records were traced in (bl_render.hip: BuildTraceArgs)
     bool located_valid = false;               // ... and d_located / d_located_tag / d_anchors hold the samples as located on `geometry`
     std::vector<unsigned char> key;           // everything the records depend on (bl_render.hip: GeodesicKey)
     std::vector<unsigned char> located_key;   // ... and the located samples besides (LocatedKey)
@@ -325,6 +330,7 @@ struct bl_ctx {
   DeviceBuffer<double> d_freq;
   DeviceBuffer<int> d_pixel_map, d_block_locs, d_tile_order;
   int tile_order_res = 0;
+  bool tile_order_xcd = false;   // d_tile_order in super-tiles of 8 x 8 tiles (the trace order per XCD, bl_render.hip) or tile by tile
   DeviceBuffer<BlShadeCold> d_shade_cold;
   std::vector<unsigned char> shade_cold_host;   // the bytes d_shade_cold holds (BuildShadeArgs uploads on change only)
   // host-output staging

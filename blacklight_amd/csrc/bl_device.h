@@ -55,6 +55,9 @@ static_assert(sizeof(BlLocated) == 32, "located sample must be 32 bytes");
 // Record slots a wave of the geodesic kernel reserves at a time (one global atomic per block); the
 // record buffers hold one spare block per launched wave on top of chunk_rays * ray_max_steps.
 #define BL_RECORD_BLOCK 1024
+#define BL_XCD_QUEUES 8        // trace order per XCD (BlTraceArgs::xcd_state): one queue and one record list per XCD
+#define BL_XCD_RUN 4096        // ... rays dealt to a queue at a time: a 64 x 64-pixel super-tile of the tile order
+#define BL_XCD_BATCH 16        // ... groups of 64 records bl_shade_fused2_kernel claims from a list at a time
 // Marker for "optically thick: I <- b" in the transfer record (exp(-dtau) is never negative)
 #define BL_THICK_MARK (-1.0)
 // ... and in the tolerant tier's affine records (a, c) of I <- a I + c: a = -0.0. An optically thick step's intensity REPLACES what lies
@@ -332,6 +335,19 @@ struct BlTraceArgs {
   // bl_geodesic_kernel passes a marked ray over, bl_geodesic_quad_kernel steps the parked ones on a stream whose CU mask the
   // other stream's excludes. split_b_hi = 0: no split.
   double split_b_lo, split_b_hi;
+  // Trace order per XCD (off: BL_SWITCH_FLAT_ORDER; bl_render.hip: XcdOrderApplies). The chunk's traversal indices are dealt to BL_XCD_QUEUES queues in runs
+  // of BL_XCD_RUN (a 64 x 64-pixel super-tile of the tile order): run m is queue m % BL_XCD_QUEUES's. A wave refills from the
+  // queue of the XCD it runs on (HW_REG_XCC_ID) and from the others once that one is dry, and lists every block of record slots it
+  // takes - as its aligned groups of 64 records - in that XCD's list, which bl_shade_fused2_kernel walks on the same XCD: the
+  // records shaded side by side on one XCD are then those of neighbouring rays, whose gathers share cells in its L2. Placement
+  // changes only speed. xcd_state: [0, 8) queue heads (rays handed out, by queue), [8, 16) list lengths (groups), [16, 24) the
+  // coefficient kernel's cursors into the lists, [24] waves that have ended; xcd_lists: BL_XCD_QUEUES lists of xcd_list_capacity
+  // group indices (record index / 64). Null: one queue, no lists - BL_CNT_NEXT_RAY is the head. With the queues BL_CNT_NEXT_RAY
+  // is written by the last wave to end: the rays before the first one no queue handed out (a gate that closed leaves the others
+  // to be traced again by the next chunk; only the rays before it are transferred).
+  unsigned long long *xcd_state;
+  unsigned int *xcd_lists;
+  long long xcd_list_capacity;
 };
 #define BL_RAY_START_FIELDS 17
 // A parked ray (BlTraceArgs::parked): everything bl_geodesic_kernel holds of a ray between two steps, BL_PARK_DOUBLES doubles
@@ -429,6 +445,12 @@ struct BlShadeArgs {
   int undefined_edge;         // bl_set_undefined_policy(BL_UNDEFINED_EDGE): samples where the reference reads past its arrays use the edge
   const unsigned long long *counters_in;
   unsigned long long *counters;
+  // bl_shade_fused2_kernel: the record lists of the geodesic kernel's trace order per XCD (BlTraceArgs::xcd_state), walked in
+  // groups of 64 records from the list of the XCD a wave runs on and from the others once that one is done; the cursors
+  // (xcd_state[16, 24)) are zero at the launch. Null: the records in one grid-stride walk.
+  unsigned long long *xcd_state;
+  const unsigned int *xcd_lists;
+  long long xcd_list_capacity;
   const double *ray_kt, *ray_factor;
   const long long *ray_offset;   // [chunk_rays]: sample n of ray q has row ray_offset[q] + n in transfer, aux, pol_samples, freq_inputs, ...
   const double *frequencies;  // device [n_nu]

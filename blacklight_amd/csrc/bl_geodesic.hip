@@ -52,6 +52,17 @@ __device__ __forceinline__ long long traversal_to_ray(long long q, int res, cons
   return m2 * res + m1;
 }
 
+// Trace order per XCD (BlTraceArgs::xcd_state): run m of BL_XCD_RUN traversal indices of the chunk is queue m % BL_XCD_QUEUES's.
+// Position j of queue r, and how many rays of a chunk queue r holds.
+__device__ __forceinline__ unsigned long long xcd_traversal(int r, long long j) {
+  return (unsigned long long)(((j / BL_XCD_RUN) * BL_XCD_QUEUES + r) * BL_XCD_RUN + j % BL_XCD_RUN);
+}
+__device__ __forceinline__ long long xcd_queue_rays(int chunk_rays, int r) {
+  const long long round = (long long)BL_XCD_RUN * BL_XCD_QUEUES;
+  const long long full = chunk_rays / round, rest = chunk_rays - full * round - (long long)r * BL_XCD_RUN;
+  return full * BL_XCD_RUN + (rest < 0 ? 0 : (rest < BL_XCD_RUN ? rest : BL_XCD_RUN));
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -181,6 +192,12 @@ __global__ void __launch_bounds__(64, BL_GEO_ONE_WAVE(kIntegrator, kTime, kSpinZ
     park_lds[4] = 0;
   }
   if (kPark) __syncthreads();   // (lane 0's words before any lane reads them; one s_barrier on a one-wave workgroup, executed once)
+  // BlTraceArgs::xcd_state: the queues this wave has found dry, counted from its own XCD's (the refilling leader's; read and written
+  // through the LDS address space, volatile, as park_word)
+  __shared__ int xcd_lds_word[1];
+  typedef volatile __attribute__((address_space(3))) int *XcdWord;
+  const XcdWord xcd_lds = (XcdWord)xcd_lds_word;
+  if (lane_here() == 0) xcd_lds[0] = 0;
 #ifdef BL_GEO_STATS
   // per lane: step attempts, accepted steps, samples emitted; per wave (lane 0): loop iterations, emission iterations, refills,
   // lane-iterations with a ray
@@ -217,11 +234,28 @@ __global__ void __launch_bounds__(64, BL_GEO_ONE_WAVE(kIntegrator, kTime, kSpinZ
         admitted = count - (int)refused;
         // the first refusal closes the gate for every wave (a large constant on the counter: every later reservation is over)
         long long give_back = -(refused * (long long)per_ray) + ((refused > 0 && over < kGateClosed / 2) ? kGateClosed : 0);
-        if (admitted > 0) {
+        if (admitted > 0 && P.xcd_state == nullptr) {
           base = atomicAdd(&P.counters[BL_CNT_NEXT_RAY], (unsigned long long)admitted);
           long long beyond = (long long)(base + (unsigned long long)admitted) - (long long)P.chunk_rays;   // past the end of the queue
           beyond = beyond < 0 ? 0 : (beyond < (long long)admitted ? beyond : (long long)admitted);
           give_back -= beyond * (long long)per_ray;
+        } else if (admitted > 0) {
+          // Trace order per XCD (BlTraceArgs::xcd_state): this XCD's queue, then the next one that still has rays (where the wave
+          // last found some: xcd_lds). base = first position in queue r | rays got << 40 | r << 48; none got: every queue is dry.
+          const int own = xcd_here();
+          long long got = 0;
+          for (int t = xcd_lds[0]; t < BL_XCD_QUEUES && got == 0; t++) {
+            const int r = (own + t) & (BL_XCD_QUEUES - 1);
+            const long long n_r = xcd_queue_rays(P.chunk_rays, r);
+            const long long b = n_r > 0 ? (long long)atomicAdd(&P.xcd_state[r], (unsigned long long)admitted) : 0;
+            if (b < n_r) {
+              got = n_r - b < (long long)admitted ? n_r - b : (long long)admitted;
+              base = (unsigned long long)b | ((unsigned long long)got << 40) | ((unsigned long long)r << 48);
+            } else {
+              xcd_lds[0] = t + 1;
+            }
+          }
+          give_back -= ((long long)admitted - got) * (long long)per_ray;
         }
         if (give_back != 0) atomicAdd(&P.counters[BL_CNT_COMMITTED], (unsigned long long)give_back);
       }
@@ -230,8 +264,16 @@ __global__ void __launch_bounds__(64, BL_GEO_ONE_WAVE(kIntegrator, kTime, kSpinZ
       admitted = __builtin_amdgcn_readlane(admitted, leader);
       if (need) {
         const int rank = __popcll(need_mask & ((1ull << lane) - 1ull));
-        const unsigned long long q = base + (unsigned long long)rank;
-        if (rank >= admitted || q >= (unsigned long long)P.chunk_rays) {
+        unsigned long long q = base + (unsigned long long)rank;
+        bool wait = false;   // (trace order per XCD: no ray for this lane in this pass, but a queue may still have some)
+        if (P.xcd_state != nullptr) {
+          const int got = (int)((base >> 40) & 0xffull);
+          q = xcd_traversal((int)(base >> 48), (long long)(base & 0xffffffffffull) + rank);
+          wait = rank < admitted && rank >= got && got > 0;
+          q = rank < got ? q : ~0ull;
+        }
+        if (wait) {
+        } else if (rank >= admitted || q >= (unsigned long long)P.chunk_rays) {
           exhausted = true;   // no slots for this lane's ray, or no ray left in the queue
         } else {
           have_ray = true;
@@ -591,6 +633,20 @@ __global__ void __launch_bounds__(64, BL_GEO_ONE_WAVE(kIntegrator, kTime, kSpinZ
         new_base = (long long)fetched;
         block_next = new_base + ((long long)total - remaining);
         block_end = (long long)(fetched + grab);
+        if (P.xcd_lists != nullptr) {
+          // trace order per XCD: the block's groups of 64 records go to this XCD's list (BlTraceArgs::xcd_state)
+          const int list = xcd_here();
+          const unsigned int groups = (unsigned int)(grab >> 6);
+          const int lane = lane_here();
+          unsigned long long at = 0ull;
+          if (lane == 0) at = atomicAdd(&P.xcd_state[BL_XCD_QUEUES + list], (unsigned long long)groups);
+          at = ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(at >> 32)) << 32)
+              | (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)at);
+          for (unsigned int g = (unsigned int)lane; g < groups; g += 64u) {
+            if (at + g < (unsigned long long)P.xcd_list_capacity) P.xcd_lists[(size_t)list * (size_t)P.xcd_list_capacity + at + g] = (unsigned int)(fetched >> 6) + g;
+            else atomicExch(&P.counters[BL_CNT_OVERFLOW], 1ull);   // (cannot happen: a list holds every group of the capacity)
+          }
+        }
         if (block_end > P.record_capacity) {
           // cannot happen with capacity = chunk_rays * ray_max_steps + one block per wave; flagged for the host
           atomicExch(&P.counters[BL_CNT_OVERFLOW], 1ull);
@@ -707,6 +763,29 @@ __global__ void __launch_bounds__(64, BL_GEO_ONE_WAVE(kIntegrator, kTime, kSpinZ
       P.ray_offset[slot] = (long long)atomicAdd(&P.counters[BL_CNT_SAMPLES], (unsigned long long)rows);
       atomicAdd(&P.counters[BL_CNT_COMMITTED], (unsigned long long)(-(long long)(P.ray_max_steps - (sample_num - (kShell ? skipped : 0)))));
       have_ray = false;
+    }
+  }
+  if (P.xcd_state != nullptr) {
+    // Trace order per XCD: the last wave to end writes BL_CNT_NEXT_RAY - the first traversal index no queue handed out (the
+    // chunk's rays when every queue ran dry). Every wave's claims have returned before it counts itself out.
+    __threadfence();
+    const int lane = lane_here();
+    unsigned long long ended = 0ull;
+    if (lane == 0) ended = atomicAdd(&P.xcd_state[3 * BL_XCD_QUEUES], 1ull);
+    ended = (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)ended);
+    if (ended + 1ull == (unsigned long long)gridDim.x * (blockDim.x / 64u)) {
+      long long first = P.chunk_rays;
+      if (lane < BL_XCD_QUEUES) {
+        const long long head = (long long)__hip_atomic_load(&P.xcd_state[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (head < xcd_queue_rays(P.chunk_rays, lane)) first = (long long)xcd_traversal(lane, head);
+      }
+      long long done = P.chunk_rays;
+      for (int r = 0; r < BL_XCD_QUEUES; r++) {
+        const long long f = ((long long)(unsigned int)__builtin_amdgcn_readlane((int)(first >> 32), r) << 32)
+            | (long long)(unsigned int)__builtin_amdgcn_readlane((int)first, r);
+        done = f < done ? f : done;
+      }
+      if (lane == 0) atomicExch(&P.counters[BL_CNT_NEXT_RAY], (unsigned long long)done);
     }
   }
 #ifdef BL_GEO_STATS

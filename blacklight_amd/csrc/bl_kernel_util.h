@@ -92,4 +92,16 @@ __device__ __forceinline__ const Args &kernel_arguments_in_place() {
 #endif
 }
 
+// The XCD the calling wave runs on (0 ... 7 on MI355X; HW_REG_XCC_ID). For placement only - which L2 a wave's reads go through:
+// code that reads it must stay correct whatever it returns. Read again where it is needed instead of held in a register.
+__device__ __forceinline__ int xcd_here() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int x;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(x));
+  return x & 7;
+#else
+  return 0;
+#endif
+}
+
 }  // namespace

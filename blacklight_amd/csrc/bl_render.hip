@@ -176,6 +176,8 @@ struct RenderJob {
   bool reuse_chunks = false;  // ... and they are in the kept layout: the chunks of the render that integrated them, one after another
   bool kept = false;          // integrating in the kept layout: every chunk's records side by side in a store (bl_ctx::ResidentGeodesics)
   bool kept_spilled = false;  // ... the store ran out before the last ray: the remaining chunks overwrite it from its start, nothing is kept
+  bool xcd_order = false;     // trace order per XCD (BlTraceArgs::xcd_state, XcdOrderApplies)
+  bool super_tiles = false;   // ... the tile order in super-tiles (BuildTraceArgs)
   bool raster = false;        // large host outputs (many image rows): rays in pixel order, so that a chunk is a range of columns of
                               // every row and goes to the caller's buffer while the next chunk renders (DownloadChunk)
   bool chunk_downloads = false;   // ... and this call does download chunk by chunk (more than one chunk, or a first chunk that left rays)
@@ -639,6 +641,7 @@ void KeepResident(RenderJob &job) {
   const unsigned long long *hc = ctx->host_counters;   // scratch set 0's, as CollectChunk read them
   if (job.keepable && !job.reuse) {
     res.valid = false;
+    res.super_tiles = job.super_tiles;
     if (job.kept && !job.kept_spilled) {
       res.valid = true;
       res.parked = false;
@@ -849,11 +852,27 @@ void PlaceKeptChunk(RenderJob &job, int segment, size_t base) {
   job.chunk_gate = static_cast<long long>(job.chunk_capacity) - blocks;
 }
 
+// Trace order per XCD (BlTraceArgs::xcd_state; BL_SWITCH_FLAT_ORDER turns it off, docs/notebook.md section 6: the coefficient
+// kernel's L2 hits 21 -> 43 %, its fabric fetch -25 %, its time -1.65 ms): rays dealt to one queue per XCD in 64 x 64-pixel super-tiles, the records of an XCD's waves listed for the coefficient kernel's waves on the same XCD, whose
+// gathers then share cells in that XCD's L2. For the kernel that walks the lists (bl_shade_fused2_kernel), a full root frame in
+// tile order (the order swizzle_tiles gives), and geodesics integrated here into one scratch set by bl_geodesic_kernel alone - every
+// other consumer of the records keeps the flat walk, and kept or loaded geodesics keep the one queue. (One scratch set: a chunk
+// whose gate closed leaves rays that a queue did hand out to the next chunk, and these must not be written over while this chunk is
+// still being shaded.)
+bool XcdOrderApplies(const RenderJob &job) {
+  const bl_ctx *ctx = job.ctx;
+  const bl_params &p = ctx->params;
+  return job.fused2 && !job.freq_split && !(ctx->switches & BL_SWITCH_FLAT_ORDER)
+      && job.d->level == 0 && job.d->pixel_map == nullptr && p.camera_resolution % 8 == 0 && job.n_rays == job.level_pixels && !job.raster
+      && !job.reuse && !job.reuse_chunks && !job.kept && !job.geo_load && !job.geo_save && !job.sample_save && !job.park && !job.split_long;
+}
+
 // ---- scratch: what a sample record costs, how many fit, how many persistent waves trace rays into them
 void PlanScratch(RenderJob &job) {
   bl_ctx *ctx = job.ctx;
   const bl_params &p = ctx->params;
   const int n_nu = job.n_nu;
+  job.xcd_order = XcdOrderApplies(job);
   // per sample record (the arrays indexed by record slot) and per kept sample (the arrays indexed by ray_offset + n: never
   // more than records)
   job.bytes_per_record = sizeof(BlSampleHot) + sizeof(BlSampleCold)
@@ -864,7 +883,9 @@ void PlanScratch(RenderJob &job) {
       + (ctx->polarized ? sizeof(BlPolSample) + sizeof(BlCoefInputs) + 4 * sizeof(double2) * n_nu + (job.pol_coefficients_inside ? 1 : 0) : 0)
       + (job.coef_split ? sizeof(BlCoefInputs) : 0)
       + (job.matrix_transport ? BL_POL_MATRIX_DOUBLES * sizeof(double) : 0)
-      + ((job.block_interp && !job.locate_inside) ? 8 * sizeof(unsigned int) : 0);
+      + ((job.block_interp && !job.locate_inside) ? 8 * sizeof(unsigned int) : 0)
+      + (job.xcd_order ? 1 : 0);   // (the record lists: BL_XCD_QUEUES x 4 bytes per 64 records; counted before the plan below can
+                                   // still drop the order - a chunk or more, parked rays - which then leaves that byte unused)
   if (job.reuse) {
     // over the resident records: the scratch set as the render that integrated them sized it, no stepper, nothing parked
     job.n_slots = 1;
@@ -945,6 +966,9 @@ void PlanScratch(RenderJob &job) {
   job.park_capacity = job.park ? (park_every_ray ? static_cast<size_t>(job.n_rays) : static_cast<size_t>(grid) * 64) : 0;
   // (the split is decided once for all rays of the call: only where one chunk is sure to take them all)
   if (job.split_long && (job.n_slots != 1 || capacity < worst_case)) job.split_long = false;
+  // (... and so is the trace order per XCD: a gate that closed would leave rays some queue had handed out to the next chunk, to be
+  // traced twice - correct, bl_rays_done, but the counts and the kept layout's sizes would include them)
+  if (job.n_slots != 1 || capacity < worst_case) job.xcd_order = false;
   if (job.split_long) {
     // Which rays. Alone in a wave a ray of the benchmark camera takes 3.2 ms at b = 5.20 M, 2.3 ... 2.9 ms between 4.9 and 5.18, 2.3 ms
     // at 5.23 and 1.8 ms at 5.3 (tools/gpu_ray_length_by_radius.py): the band reaches 0.03 M beyond the critical curve and inwards
@@ -983,6 +1007,7 @@ void PlanScratch(RenderJob &job) {
     job.park_capacity = static_cast<size_t>(job.n_rays);
     job.quad_grid = job.split_cus * 4;
   }
+  if (job.n_slots != 1 || job.park || job.split_long) job.xcd_order = false;
 }
 
 void EnsureScratchOnce(RenderJob &job);
@@ -1025,6 +1050,10 @@ void EnsureScratchOnce(RenderJob &job) {
     if (job.freq_split) sl.d_freq_inputs.Ensure(cap);   // instead of the transfer records
     else if (!ctx->polarized) sl.d_transfer.Ensure(cap * n_nu);   // (polarized runs: the eight coefficients of a sample side by side, d_pol_coeffs)
     if (job.composed) sl.d_composed.Ensure(cap);
+    if (job.xcd_order) {
+      sl.d_xcd_state.Ensure(4 * BL_XCD_QUEUES);
+      sl.d_xcd_lists.Ensure(BL_XCD_QUEUES * (cap / 64 + 1));
+    }
     if (job.park || job.split_long) sl.d_parked.Ensure(job.park_capacity * BL_PARK_DOUBLES);
     if (job.tau_row) sl.d_tau_inc.Ensure(cap * n_nu);
     sl.d_counters.Ensure(BL_CNT_TOTAL);
@@ -1190,22 +1219,37 @@ void BuildTraceArgs(RenderJob &job) {
   // the centre (photon ring, disc) are the long ones, the periphery is short; a chunk that ends on short
   // rays drains its persistent waves quickly (measured: geodesic kernel 33.9 -> 29.4 ms per frame at four
   // chunks), and waves of similar ray lengths also diverge less in the transfer kernel.
+  // With the trace order per XCD (job.xcd_order) the unit of that order is a super-tile of 8 x 8 tiles (64 x 64 pixels, its tiles
+  // row by row: BL_XCD_RUN rays), super-tiles centre first, dealt to its queues round-robin (BlTraceArgs::xcd_state), so that every
+  // queue has its share of the long rays near the centre and of the short ones further out. A render over resident records
+  // (job.reuse) uses the order of the render that integrated them: its ray slots must name the same pixels.
   ta.tile_order = nullptr;
+  job.super_tiles = false;
   if (ta.swizzle_tiles > 0) {
-    if (ctx->tile_order_res != p.camera_resolution) {
+    const bool super_tiles = job.reuse ? ctx->resident.super_tiles : job.xcd_order;
+    job.super_tiles = super_tiles;
+    if (ctx->tile_order_res != p.camera_resolution || ctx->tile_order_xcd != super_tiles) {
       const int tiles_per_row = p.camera_resolution / 8;
       const int n_tiles = tiles_per_row * tiles_per_row;
+      const int unit = super_tiles ? 8 : 1;   // (tiles per side of the unit)
       std::vector<int> order(n_tiles);
       for (int t = 0; t < n_tiles; t++) order[t] = t;
-      const double centre = 0.5 * (tiles_per_row - 1);
-      auto dist2 = [&](int t) {
-        double dy = t / tiles_per_row - centre, dx = t % tiles_per_row - centre;
+      const int units_per_row = (tiles_per_row + unit - 1) / unit;
+      const double centre = 0.5 * (units_per_row - 1);
+      auto unit_index = [&](int t) { return (t / tiles_per_row / unit) * units_per_row + t % tiles_per_row / unit; };
+      auto unit_dist2 = [&](int t) {
+        const int u = unit_index(t);
+        const double dy = u / units_per_row - centre, dx = u % units_per_row - centre;
         return dx * dx + dy * dy;
       };
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return dist2(a) < dist2(b); });
+      std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+        const double da = unit_dist2(a), db = unit_dist2(b);
+        return da != db ? da < db : unit_index(a) < unit_index(b);
+      });
       ctx->d_tile_order.Ensure(n_tiles);
       Check(hipMemcpy(ctx->d_tile_order.ptr, order.data(), n_tiles * sizeof(int), hipMemcpyHostToDevice), "tile order upload");
       ctx->tile_order_res = p.camera_resolution;
+      ctx->tile_order_xcd = super_tiles;
     }
     ta.tile_order = ctx->d_tile_order.ptr;
   }
@@ -1601,12 +1645,18 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   ta.park_age = job.max_steps / 8;
   ta.quad_first_round = ctx->num_cus * 4;
   ta.park_always = (job.park && (ctx->switches & BL_SWITCH_QUAD_EVERY_RAY)) ? 1 : 0;
+  ta.xcd_state = job.xcd_order ? sl.d_xcd_state.ptr : nullptr;
+  ta.xcd_lists = job.xcd_order ? sl.d_xcd_lists.ptr : nullptr;
+  ta.xcd_list_capacity = job.xcd_order ? static_cast<long long>(job.record_capacity / 64 + 1) : 0;
   ta.ray_flags = ctx->d_ray_flags.ptr + begin;
   ta.ray_out_index = ctx->d_ray_out_index.ptr + begin;
   ta.ray_offset = ctx->d_ray_offset.ptr + begin;
   ta.ray_start = job.geo_load ? nullptr : ctx->d_ray_start.ptr + begin;
   sa.records_hot = ta.records_hot;
   sa.records_cold = ta.records_cold;
+  sa.xcd_state = ta.xcd_state;
+  sa.xcd_lists = ta.xcd_lists;
+  sa.xcd_list_capacity = ta.xcd_list_capacity;
   sa.record_stride = ta.record_stride;
   sa.located = (job.simulation && !job.locate_inside) ? sl.d_located.ptr : nullptr;
   sa.located_tag = (job.simulation && !job.locate_inside) ? sl.d_located_tag.ptr : nullptr;
@@ -1975,6 +2025,7 @@ void LaunchGeodesicStage(RenderJob &job, int k, long long begin, int rays, hipSt
   hipEvent_t *e = SlotEvents(job, k);
   BindChunk(job, k, begin, rays);
   Check(hipMemsetAsync(sl.d_counters.ptr, 0, BL_CNT_TOTAL * sizeof(unsigned long long), stream_geo), "counter reset");
+  if (job.xcd_order) Check(hipMemsetAsync(sl.d_xcd_state.ptr, 0, 4 * BL_XCD_QUEUES * sizeof(unsigned long long), stream_geo), "counter reset");
   Check(hipEventRecord(e[0], stream_geo), "event");
   job.in_flight[k].busy = true;
   job.in_flight[k].begin = begin;
@@ -2019,6 +2070,8 @@ void LaunchShadingStage(RenderJob &job, int k, bool geodesic_beside, hipStream_t
   BlShadeArgs &sa = job.sa;
   BlTransferArgs &xa = job.xa;
   auto coefficient_kernel = [&]() {
+    // (the list walk's cursors: every pass of the coefficient kernel walks the lists from their starts)
+    if (sa.xcd_state != nullptr) Check(hipMemsetAsync(sa.xcd_state + 2 * BL_XCD_QUEUES, 0, BL_XCD_QUEUES * sizeof(unsigned long long), stream), "counter reset");
     if (job.fast) Check(bl_launch_shade_fast(&sa, job.shade_grid, stream), "coefficient kernel launch");
     else if (job.fast_formula) Check(bl_launch_shade_formula_fast(&sa, ctx->num_cus * 4 * 4, stream), "coefficient kernel launch");
     else if (job.exact_fused) Check(bl_launch_shade_exact2(&sa, job.shade_grid, stream), "coefficient kernel launch");
@@ -2388,6 +2441,7 @@ void FinishStats(RenderJob &job) {
   st.fused_variant = job.fused2 ? 2 : (job.exact_fused ? 3 : (job.pol_fused ? 4 : 0));
   st.n_parked = static_cast<int64_t>(job.reuse ? ctx->resident.n_parked : job.total_parked);
   st.composed_maps = job.composed ? 1 : 0;
+  st.xcd_order = job.xcd_order ? 1 : 0;
   st.tail_policy = job.reuse ? ctx->resident.tail_policy : (job.park ? BL_TAIL_QUAD : (job.split_long ? BL_TAIL_SPLIT : BL_TAIL_WIDE));
   ctx->stats = st;
   if (ctx->debug_counters) {   // kernels built with -DBL_GEO_STATS fill these

@@ -766,13 +766,67 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   unsigned long long gathers_wave = 0ull;   // (wave-uniform: counted with ballots)
 
-  // Records are addressed from a wave-uniform base that advances by one grid stride per iteration (scalar arithmetic) plus the
-  // lane's own constant 32-bit offset; a position beyond the last record reads the base's record and comes back dead.
+  // A wave's 64 lanes take 64 consecutive records: lane l record first + l, `first` wave-uniform (scalar arithmetic) and the lane's
+  // byte offset constant; a position beyond the last record reads the wave's first record and comes back dead. Which 64: one grid
+  // stride on per iteration, or (BlShadeArgs::xcd_lists) the next group of the record list of the XCD the wave runs on.
   const char *records = reinterpret_cast<const char *>(P.records_hot);
-  const uint32_t lane_index = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t lane_bytes = lane_index << 6;
-  uint32_t base_index = first_record;   // record index of lane 0 of block 0 for the sample `prev` ... (wave-uniform)
+  const uint32_t lane_in_wave = threadIdx.x & 63u;
+  const uint32_t lane_bytes = lane_in_wave << 6;
+  const uint32_t wave_offset = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * blockDim.x + (threadIdx.x & ~63u)));
+  uint32_t base_index = first_record;   // record index of lane 0 of block 0 for the sample `next` ... (wave-uniform, grid-stride walk)
   auto record_base = [&](uint32_t first) { return records + ((size_t)(first < last ? first : last) << 6); };
+  // The list walk: batches of BL_XCD_BATCH groups claimed with one atomic on a list's cursor, lane b of `batch` holding group b.
+  // The claim for the next batch is made when a batch begins and its groups are read one group later, so that neither the
+  // atomic nor the read is waited for where it is used. A list that has nothing left passes the wave on to the next one.
+  const bool by_list = P.xcd_lists != nullptr;
+  constexpr uint32_t kNoRecords = 0xffffffc0u;   // (beyond any record: first + lane >= n_records)
+  int list = by_list ? xcd_here() : 0, tried = 0;          // (wave-uniform)
+  int batch_n = 0, batch_at = 0, next_n = 0;                // ...
+  bool claim_pending = false;                               // ...
+  uint32_t batch = 0u, next_batch = 0u;                     // lane b < batch_n: group b of the batch
+  unsigned long long claim = 0ull;                          // the pending claim's first position (lane 0)
+  auto claim_issue = [&]() __attribute__((always_inline)) {
+    if ((threadIdx.x & 63u) == 0u) claim = atomicAdd(&P.xcd_state[2 * BL_XCD_QUEUES + list], (unsigned long long)BL_XCD_BATCH);
+    claim_pending = true;
+  };
+  auto claim_read = [&]() __attribute__((always_inline)) {
+    // (what a claim found; past a list's end, claims on the next lists until one has groups left or all have been tried)
+    unsigned long long at = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(claim >> 32), 0) << 32)
+        | (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)claim, 0);
+    unsigned long long length = P.xcd_state[BL_XCD_QUEUES + list];
+    while (at >= length && tried < BL_XCD_QUEUES - 1) {
+      tried++;
+      list = (list + 1) & (BL_XCD_QUEUES - 1);
+      claim_issue();
+      at = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(claim >> 32), 0) << 32)
+          | (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)claim, 0);
+      length = P.xcd_state[BL_XCD_QUEUES + list];
+    }
+    next_n = at < length ? (int)(length - at < (unsigned long long)BL_XCD_BATCH ? length - at : (unsigned long long)BL_XCD_BATCH) : 0;
+    next_batch = (int)lane_in_wave < next_n ? P.xcd_lists[(size_t)list * (size_t)P.xcd_list_capacity + at + lane_in_wave] : 0u;
+    claim_pending = false;
+  };
+  // the wave's first record for the next iteration's `next`
+  auto walk_next = [&]() __attribute__((always_inline)) -> uint32_t {
+    if (!by_list) {
+      const uint32_t first = base_index + wave_offset;
+      base_index += stride;
+      return first;
+    }
+    if (claim_pending && (batch_at >= 1 || batch_at >= batch_n)) claim_read();
+    if (batch_at >= batch_n) {
+      batch = next_batch;
+      batch_n = next_n;
+      batch_at = 0;
+      next_n = 0;
+      if (batch_n > 0) claim_issue();
+    }
+    if (batch_n == 0) return kNoRecords;
+    const uint32_t group = (uint32_t)__builtin_amdgcn_readlane((int)batch, batch_at);
+    batch_at++;
+    return group << 6;
+  };
+  if (by_list) claim_issue();
   // Three slots take the roles prev -> next -> cur -> prev in turn, and the loop body is written out once per assignment of roles:
   // a sample's registers stay where its requests landed from its first iteration to its last, instead of moving down the pipeline
   // with 46 copies an iteration (the compiler does not unroll a loop whose exit is a wave vote by itself).
@@ -781,6 +835,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     Located loc;
     double kt, factor;        // per-ray constants, requested with the cells
     long long row;
+    uint32_t first;           // record of the wave's lane 0 (wave-uniform)
     bool in;
   };
   Slot s0, s1, s2;
@@ -797,16 +852,18 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
 #pragma unroll
   for (int c = 0; c < 8; c++) lo[c] = hi[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   // (32-bit record indices: the launcher keeps n_records + 3 strides below 2^32)
-  s1.in = first_record + lane_index < n_records;
+  s0.first = kNoRecords;
+  s1.first = walk_next();
+  s1.in = s1.first + lane_in_wave < n_records;
   {
-    const double2 *rec = reinterpret_cast<const double2 *>(record_base(first_record) + (size_t)(s1.in ? lane_bytes : 0u));
+    const double2 *rec = reinterpret_cast<const double2 *>(record_base(s1.first) + (size_t)(s1.in ? lane_bytes : 0u));
     s1.h0 = rec[0];
     s1.h1 = rec[1];
     s1.h1.y = s1.in ? s1.h1.y : __longlong_as_double((long long)BL_DEAD_RAY);
   }
   s1.loc = locate<kSpinZero, kRefined>(st, G, camera_r, band, (uint32_t)__double_as_longlong(s1.h1.y) != BL_DEAD_RAY, s1.h0.x, s1.h0.y, s1.h1.x);
-  // p (`prev`) is sample base_index - stride + lane_index (none in the first iteration), c (`cur`) base_index + lane_index, x (`next`)
-  // one stride on
+  // p (`prev`) is record p.first + lane (none in the first iteration), c (`cur`) c.first + lane, x (`next`) the wave's next 64
+  // (walk_next)
   // (kRefined) the wave's samples for the exact pass, collected in LDS behind the tables and handed to the list 64 at a time
   uint32_t *deferred_here = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(lds) + (kRefined ? P.grid.fused_lds_bytes : 0)) + (kRefined ? (threadIdx.x >> 6) * 128u : 0u);
   uint32_t n_deferred_here = 0u;   // (wave-uniform)
@@ -825,10 +882,10 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     const uint32_t status = p.loc.status & 0xffu;
     const bool interp = status == (uint32_t)kSampleInterp;
     // the position record of `next`: the oldest request of the iteration, used at its end
-    const uint32_t next_first = base_index + stride;
-    x.in = next_first + lane_index < n_records;
+    x.first = walk_next();
+    x.in = x.first + lane_in_wave < n_records;
     {
-      const double2 *rec = reinterpret_cast<const double2 *>(record_base(next_first) + (size_t)(x.in ? lane_bytes : 0u));
+      const double2 *rec = reinterpret_cast<const double2 *>(record_base(x.first) + (size_t)(x.in ? lane_bytes : 0u));
       x.h0 = rec[0];
       x.h1 = rec[1];
     }
@@ -845,7 +902,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     gathers_wave += (unsigned long long)__popcll(__ballot(interp));
     fused2::gather_issue(cells, c.loc.cell_bytes, (c.loc.status & 0xffu) == (uint32_t)kSampleInterp, row_bytes, plane_bytes, lo, hi);
     {
-      const double2 *rec = reinterpret_cast<const double2 *>(record_base(base_index) + (size_t)(c.in ? lane_bytes : 0u));
+      const double2 *rec = reinterpret_cast<const double2 *>(record_base(c.first) + (size_t)(c.in ? lane_bytes : 0u));
       c.c0 = rec[2];
       c.c1 = rec[3];
     }
@@ -927,7 +984,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
         if (__builtin_amdgcn_inverse_ballot_w64(last_lanes) && live) P.composed[(size_t)(row_first + (long long)n)] = make_double2(a, c);
       } else {
         // a row with a sample for the exact kernel or a thick step: its samples' own records, by record index, and rows that say so
-        const uint32_t record = base_index - stride + lane_index;
+        const uint32_t record = p.first + lane_in_wave;
         if (live && !defer) P.transfer[record] = rec;
         const unsigned long long last_lanes = (first >> 1) | 0x8000800080008000ull;
         const uint32_t lane = threadIdx.x & 63u;
@@ -946,7 +1003,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
       const unsigned long long waiting = __ballot(live && defer);
       if (__builtin_expect(waiting != 0ull, 0)) {
         const uint32_t lane = threadIdx.x & 63u;
-        if (live && defer) deferred_here[n_deferred_here + (uint32_t)__popcll(waiting & ((1ull << lane) - 1ull))] = base_index - stride + lane_index;
+        if (live && defer) deferred_here[n_deferred_here + (uint32_t)__popcll(waiting & ((1ull << lane) - 1ull))] = p.first + lane_in_wave;
         n_deferred_here += (uint32_t)__popcll(waiting);
         if (n_deferred_here >= 64u) {
           n_deferred_here -= 64u;
@@ -957,12 +1014,11 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
       KernArgs args = kernargs();
       unsigned long long *counters = args->counters;
       const unsigned long long at = atomicAdd(&counters[BL_CNT_REDO], 1ull);
-      if (at < args->redo_capacity) args->redo_list[at] = (unsigned long long)(base_index - stride + lane_index);
+      if (at < args->redo_capacity) args->redo_list[at] = (unsigned long long)(p.first + lane_in_wave);
     }
     // ---- the search for `next`
     x.loc = locate<kSpinZero, kRefined>(st, G, camera_r, band, x.in && (uint32_t)__double_as_longlong(x.h1.y) != BL_DEAD_RAY, x.h0.x, x.h0.y, x.h1.x);
     x.h1.y = x.in ? x.h1.y : __longlong_as_double((long long)BL_DEAD_RAY);
-    base_index = next_first;
   };
   for (;;) {
     if (!__any(s0.in || s1.in)) break;

@@ -297,6 +297,7 @@ typedef struct bl_stats {
   int32_t geodesics_reused;   /* 1: the sample records of an earlier render of the same camera were shaded again - no ray was
                                  integrated (launches_geodesic = 0, ms_geodesic = 0); bl_set_geodesic_reuse                              */
   int32_t sampling_reused;    /* 1: ... and the located samples too (same grid geometry: no locate kernel ran, launches_locate = 0)     */
+  int32_t xcd_order;          /* 1: the rays were traced and their records shaded in the trace order per XCD (BL_SWITCH_FLAT_ORDER: 0) */
   /* Several electron models (bl_set_electron_models) where they cannot share one pass: launches_shade / launches_transfer count one
      shading pass per model and chunk; n_gathers, n_deferred and the sample counts are those of one pass (every pass has the same
      samples); ms_shade runs from the first coefficient kernel to the last one, ms_transfer is the last transfer kernel's. */
@@ -316,7 +317,9 @@ typedef struct bl_stats {
 #define BL_SWITCH_NO_FUSED_LOCATE (1u << 6)                 /* a locate kernel + bl_shade_fast_kernel / bl_shade_exact_kernel   */
 #define BL_SWITCH_SAMPLE_RECORDS (1u << 8)                  /* tolerant tier: one transfer record per sample where composed maps apply */
 #define BL_SWITCH_QUAD_EVERY_RAY (1u << 11)                 /* every ray parked before its first step: all stepping in bl_geodesic_quad_kernel */
-/* (Eight switches. Rounds 3 - 5 had eight more for experiments the measurements buried - a second pre-fused2 kernel, pre-gathered
+#define BL_SWITCH_FLAT_ORDER (1u << 12)                     /* one ray queue, tile by tile, and the records in one grid-stride walk
+                                                               where the trace order per XCD applies (bl_stats.xcd_order)           */
+/* (Nine switches. Rounds 3 - 5 had eight more for experiments the measurements buried - a second pre-fused2 kernel, pre-gathered
  * cell bricks, the coefficient kernel beside a chunk's last rays, repacked tails - and for what bl_set_tail_policy now says; their
  * numbers are in docs/notebook.md, their code in the history.) */
 
