@@ -115,6 +115,8 @@ def lib():
     L.bl_num_electron_models.argtypes = [C.c_void_p]
     L.bl_set_density_units.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.bl_num_density_units.argtypes = [C.c_void_p]
+    L.bl_set_polarized_variants.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bl_num_polarized_variants.argtypes = [C.c_void_p]
     L.bl_host_alloc.argtypes = [C.c_void_p, C.c_size_t]
     L.bl_host_alloc.restype = C.c_void_p
     L.bl_host_free.argtypes = [C.c_void_p, C.c_void_p]

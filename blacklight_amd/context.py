@@ -5,6 +5,7 @@ construct once from the input parameters, hand over the grid once per snapshot, 
 level per call. All computation happens in libblacklight_amd.so on the GPU.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -213,6 +214,117 @@ class Context:
             self.set_electron_models([h for h, _ in models], rat_low=[lo_ for _, lo_ in models])
             self.set_density_units(units)
 
+    def set_polarized_variants(self, rat_high, rho_cgs, rat_low=1.0):
+        """Render several (R_high, R_low, simulation_rho_cgs) triples of a polarized run in one render (bl_set_polarized_variants):
+        a list of triples, not a product - scalars or sequences, broadcast against each other; empty sequences clear them (the
+        parameter block's pair and unit again). The image then holds the variants one after another
+        (render()["image_by_variant"]: (n_variants, n_q, n_rays)); geodesics stay resident."""
+        high, unit, low = np.broadcast_arrays(np.atleast_1d(np.asarray(rat_high, dtype=np.float64)),
+                                              np.atleast_1d(np.asarray(rho_cgs, dtype=np.float64)),
+                                              np.atleast_1d(np.asarray(rat_low, dtype=np.float64)))
+        high, unit, low = (np.ascontiguousarray(a.ravel()) for a in (high, unit, low))
+        self._check(self._lib.bl_set_polarized_variants(self._ctx, int(high.size), low.ctypes.data_as(C.c_void_p),
+                                                        high.ctypes.data_as(C.c_void_p), unit.ctypes.data_as(C.c_void_p)))
+        self._polarized_variants = [(float(h), float(lo), float(u)) for h, lo, u in zip(high, low, unit)]
+
+    @property
+    def polarized_variants(self):
+        """The (rat_high, rat_low, rho_cgs) triples set_polarized_variants() set; [] when the parameter block's are rendered."""
+        held = list(getattr(self, "_polarized_variants", []))
+        if len(held) != self.num_polarized_variants:   # (set behind this object's back, through the C interface)
+            raise RuntimeError("polarized_variants: the context holds variants that set_polarized_variants() did not set")
+        return held
+
+    @property
+    def num_polarized_variants(self):
+        return self._lib.bl_num_polarized_variants(self._ctx)
+
+    def fit_density_units_polarized(self, pairs, target_jy, distance_pc, lo, hi, frequency=0, rtol=1.0e-3):
+        """For every (rat_high, rat_low) pair of a polarized run, the density unit in [lo, hi] at which the root image's Stokes-I flux
+        (flux.stokes_flux_jy) at image frequency `frequency` is target_jy to within rtol. All pairs advance together: every render
+        carries each unfinished pair's current trial units as variants (up to 16 per render; more trials than that take another
+        render of the same step) - the bracket's two ends first, then secant steps in log rho and log flux, falling back to
+        bisection where a step leaves the bracket or shrinks it by less than half. The context's variants are restored on exit.
+        Returns ([(rho_cgs, flux_jy, m_net, v_net) per pair], renders)."""
+        from . import flux as _flux
+        pairs = [(float(h), float(l)) for h, l in pairs]
+        if not pairs:
+            raise ValueError("fit_density_units_polarized needs at least one (rat_high, rat_low) pair")
+        if not (0.0 < lo < hi) or not np.isfinite(hi):
+            raise ValueError(f"fit_density_units_polarized needs 0 < lo < hi, finite (got {lo}, {hi})")
+        if not (target_jy > 0.0 and rtol > 0.0):
+            raise ValueError("fit_density_units_polarized needs target_jy > 0 and rtol > 0")
+        saved = self.polarized_variants
+        renders = 0
+
+        def evaluate(trials):   # [(pair index, rho)] -> [(I, Q, U, V) in Jy]
+            nonlocal renders
+            out = []
+            for start in range(0, len(trials), 16):
+                part = trials[start:start + 16]
+                self.set_polarized_variants([pairs[k][0] for k, _ in part], [rho for _, rho in part], rat_low=[pairs[k][1] for k, _ in part])
+                got = self.render()
+                renders += 1
+                out += [_flux.stokes_flux_jy(got["image_by_variant"][v], self.params, distance_pc, frequency) for v in range(len(part))]
+            return out
+
+        try:
+            n = len(pairs)
+            found = [None] * n
+            # the bracket's ends: (log rho, log I) of both, for every pair
+            ends = evaluate([(k, float(lo)) for k in range(n)] + [(k, float(hi)) for k in range(n)])
+            a = [[math.log(lo), ends[k]] for k in range(n)]
+            b = [[math.log(hi), ends[n + k]] for k in range(n)]
+            bisect = [False] * n
+            log_target = math.log(target_jy)
+
+            def close(stokes):
+                return abs(stokes[0] - target_jy) <= rtol * target_jy
+
+            def result(rho, stokes):
+                m_net, v_net, _ = _flux.net_polarization(stokes)
+                return (float(rho), float(stokes[0]), m_net, v_net)
+
+            for k in range(n):
+                fa, fb = a[k][1][0], b[k][1][0]
+                if close(a[k][1]):
+                    found[k] = result(lo, a[k][1])
+                elif close(b[k][1]):
+                    found[k] = result(hi, b[k][1])
+                elif not (fa - target_jy) * (fb - target_jy) < 0.0:
+                    raise ValueError(f"fit_density_units_polarized: [{lo:.6g}, {hi:.6g}] g/cm^3 does not bracket {target_jy:.6g} Jy for the pair "
+                                     f"{pairs[k]} (fluxes at the ends: {fa:.6g}, {fb:.6g} Jy)")
+            for _ in range(64):
+                todo = [k for k in range(n) if found[k] is None]
+                if not todo:
+                    break
+                trials = []
+                for k in todo:
+                    xa, xb = a[k][0], b[k][0]
+                    ia, ib = a[k][1][0], b[k][1][0]
+                    x = 0.5 * (xa + xb)
+                    if not bisect[k] and ia > 0.0 and ib > 0.0 and ia != ib:
+                        la, lb = math.log(ia), math.log(ib)
+                        secant = xa + (log_target - la) * (xb - xa) / (lb - la)
+                        if min(xa, xb) < secant < max(xa, xb):
+                            x = secant
+                    trials.append((k, math.exp(x)))
+                for (k, rho), stokes in zip(trials, evaluate(trials)):
+                    if close(stokes):
+                        found[k] = result(rho, stokes)
+                        continue
+                    x, width = math.log(rho), abs(b[k][0] - a[k][0])
+                    if (stokes[0] - target_jy) * (a[k][1][0] - target_jy) > 0.0:
+                        a[k] = [x, stokes]
+                    else:
+                        b[k] = [x, stokes]
+                    bisect[k] = abs(b[k][0] - a[k][0]) > 0.5 * width   # (a secant step that hardly moved the bracket: halve it next)
+            if any(f is None for f in found):
+                raise RuntimeError(f"fit_density_units_polarized: no unit within rtol = {rtol} of {target_jy} Jy after {renders} renders")
+            return found, renders
+        finally:
+            self.set_polarized_variants([h for h, _, _ in saved], [u for _, _, u in saved], rat_low=[l for _, l, _ in saved])
+
     def set_caller_stream(self, stream=None, enabled=True):
         """Every later render starts behind the work queued so far on `stream` (a raw hipStream_t handle, e.g.
         torch.cuda.current_stream().cuda_stream; None / 0: the NULL stream) - bl_set_caller_stream."""
@@ -334,7 +446,9 @@ class Context:
             d.render = rendering.ctypes.data_as(C.c_void_p)
         self._check(self._lib.bl_render(self._ctx, C.byref(d)))
         n_models, n_units = max(1, self.num_electron_models), max(1, self.num_density_units)
+        n_variants = max(1, self.num_polarized_variants)
         return dict(image=image, image_by_model=image.reshape(n_models, n_q // n_models, n_rays),
+                    image_by_variant=image.reshape(n_variants, n_q // n_variants, n_rays),
                     image_by_unit=image.reshape(n_models, n_units, n_q // (n_models * n_units), n_rays), sample_num=sample_num,
                     sample_flags=sample_flags, camera_pos=camera_pos, camera_dir=camera_dir, rendering=rendering, stats=self.stats)
 

@@ -382,6 +382,23 @@ const char *DensityUnitsRefusal(const bl_ctx *ctx, int n) {
   }
   return nullptr;
 }
+
+// Why n polarized variants cannot be rendered by this context (nullptr: they can). bl_set_polarized_variants and bl_render's plan both ask.
+const char *PolarizedVariantsRefusal(const bl_ctx *ctx, int n) {
+  const bl_params &p = ctx->params;
+  if (n <= 0) return nullptr;
+  if (p.model_type != BL_MODEL_SIMULATION)
+    return "Polarized variants: formula mode has neither an electron temperature nor a density (model_type = formula).";
+  if (!ctx->polarized)
+    return "Polarized variants: the context is not polarized (image_polarization = false); bl_set_electron_models and "
+           "bl_set_density_units render the variants of an unpolarized run.";
+  if (p.slow_light_on) return "Polarized variants: slow light renders one variant (slow_light_on = true).";
+  if (n >= 2 && p.adaptive_max_level > 0)
+    return "Polarized variants: adaptive refinement reads one image; n >= 2 variants need adaptive_max_level = 0.";
+  if (n >= 2 && ctx->render_num_images > 0)
+    return "Polarized variants: renderings come out once; n >= 2 variants need render_num_images = 0.";
+  return nullptr;
+}
 }  // namespace blhost
 
 extern "C" {
@@ -1129,7 +1146,7 @@ int bl_render_num_images(const bl_ctx *ctx) { return ctx != nullptr ? ctx->rende
 int bl_image_num_quantities(const bl_ctx *ctx) {
   if (ctx == nullptr) return -1;
   return ctx->image_num_quantities * std::max<int>(1, static_cast<int>(ctx->model_rat_low.size()))
-      * std::max<int>(1, static_cast<int>(ctx->density_units.size()));
+      * std::max<int>(1, static_cast<int>(ctx->density_units.size())) * std::max<int>(1, static_cast<int>(ctx->pol_rho.size()));
 }
 
 int bl_set_electron_models(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high) {
@@ -1162,6 +1179,26 @@ int bl_set_density_units(bl_ctx *ctx, int n, const double *rho_cgs) {
 }
 
 int bl_num_density_units(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->density_units.size()) : -1; }
+
+int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs) {
+  if (ctx == nullptr) return BL_E_ARG;
+  if (n < 0 || n > BL_MAX_POLARIZED_VARIANTS || (n > 0 && (rat_low == nullptr || rat_high == nullptr || rho_cgs == nullptr)))
+    return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants needs 0 <= n <= " + std::to_string(BL_MAX_POLARIZED_VARIANTS) + " and the three arrays."});
+  for (int v = 0; v < n; v++) {
+    if (!std::isfinite(rat_low[v]) || !std::isfinite(rat_high[v]))
+      return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants: variant " + std::to_string(v) + " has a non-finite R_low or R_high."});
+    if (!std::isfinite(rho_cgs[v]) || !(rho_cgs[v] > 0.0))
+      return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants: the unit of variant " + std::to_string(v) + " is not a finite value > 0."});
+  }
+  if (const char *why = PolarizedVariantsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
+  std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: no variant enters them)
+  ctx->pol_rat_low.assign(rat_low, rat_low + n);
+  ctx->pol_rat_high.assign(rat_high, rat_high + n);
+  ctx->pol_rho.assign(rho_cgs, rho_cgs + n);
+  return BL_OK;
+}
+
+int bl_num_polarized_variants(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->pol_rho.size()) : -1; }
 
 int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out) {
   if (ctx == nullptr || out == nullptr) return BL_E_ARG;
@@ -1313,7 +1350,7 @@ void bl_free(bl_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   ctx->d_cells.Free(); ctx->d_kappa.Free(); ctx->d_coords.Free(); ctx->d_buckets.Free(); ctx->slot[0].Free(); ctx->slot[1].Free();
   ctx->d_freq.Free(); ctx->d_pixel_map.Free();
-  ctx->d_block_locs.Free(); ctx->d_tile_order.Free(); ctx->d_render_params.Free(); ctx->d_render.Free(); ctx->d_shade_cold.Free(); ctx->d_image.Free(); ctx->d_camera_pos.Free(); ctx->d_camera_dir.Free();
+  ctx->d_block_locs.Free(); ctx->d_tile_order.Free(); ctx->d_render_params.Free(); ctx->d_render.Free(); ctx->d_shade_cold.Free(); ctx->d_pol_variant_table.Free(); ctx->d_image.Free(); ctx->d_camera_pos.Free(); ctx->d_camera_dir.Free();
   ctx->d_out_sample_num.Free(); ctx->d_out_flags.Free();
   for (auto &e : ctx->events)
     if (e != nullptr) (void)hipEventDestroy(e);

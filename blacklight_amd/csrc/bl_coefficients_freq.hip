@@ -21,7 +21,20 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
   const BlShadeArgs &P = kThermalOnly ? P_at_entry : kernel_arguments_in_place<BlShadeArgs>();
   const unsigned long long n_records = P.counters_in[BL_CNT_RECORDS];
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-  for (unsigned long long idx = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; idx < n_records; idx += stride) {
+  // Polarized variants in one pass (P.pol_variants > 0, uniform per launch): a wave per (64 records, variant), the variants of a group
+  // of records in consecutive waves - a wave's lanes share their variant, so its five constants are scalar operands, and the waves
+  // of a group read the same 64 rows (4 KiB, from L2 after the first). Otherwise a lane per record, as ever.
+  const unsigned int n_var = P.pol_variants > 0 ? (unsigned int)P.pol_variants : 1u;
+  const unsigned long long n_items = n_var > 1u ? ((n_records + 63ull) >> 6) * 64ull * n_var : n_records;
+  for (unsigned long long item = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; item < n_items; item += stride) {
+    unsigned long long idx = item;
+    unsigned int v = 0u;
+    if (n_var > 1u) {
+      const unsigned long long wave = item >> 6;
+      v = (unsigned int)__builtin_amdgcn_readfirstlane((int)(wave % n_var));
+      idx = (wave / n_var) * 64ull + (item & 63ull);
+      if (idx >= n_records) continue;
+    }
     const unsigned long long tag = reinterpret_cast<const unsigned long long *>(P.records_hot + (idx) * P.record_stride)[3];   // (ray, n)
     const uint32_t ray = (uint32_t)tag;
     if (ray == BL_DEAD_RAY) continue;
@@ -35,6 +48,18 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
     sh.nu_c_cgs = ci.nu_c_cgs;
     sh.theta_e = ci.theta_e;
     sh.kb_tt_e_cgs = ci.kb_tt_e_cgs;
+    if (P.pol_variants > 0 && sh.have_coefficients) {
+      // the row holds (rho, p_gas) and b_mu b^mu: this variant's scalars by the functions sample_finish_simulation() forms them with
+      const BlPolVariant &pv = P.pol_variant_table[v];
+      const double rho = (double)__int_as_float(__double2loint(ci.n_e_cgs)), pgas = (double)__int_as_float(__double2hiint(ci.n_e_cgs));
+      const double b_sq = ci.nu_c_cgs;
+      const PlasmaCgs cgs = plasma_density_cgs(P.plasma, pv.d_unit, pv.e_unit, rho, pgas);
+      sh.n_e_cgs = cgs.n_e_cgs;
+      sh.nu_c_cgs = plasma_cyclotron_frequency(plasma_field_cgs(b_sq, pv.b_unit));
+      sh.theta_e = sh.kb_tt_e_cgs = __longlong_as_double(0x7ff8000000000000ll);
+      if (P.plasma.plasma_thermal_frac != 0.0)
+        plasma_electron_temperature(P, pv.rat_high, pv.rat_low, plasma_beta_inverse(b_sq, pgas), cgs, &sh.theta_e, &sh.kb_tt_e_cgs);
+    }
     // :453-455 from cos^2: the same operations the coefficient kernel applies to the same value
     sh.cos2_theta_b = ci.cos2_theta_b;
     sh.sin2_theta_b = 1.0 - ci.cos2_theta_b;
@@ -49,7 +74,7 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
         else bl_cyl_bessel_k012(1.0 / sh.theta_e, &sh.kk_0, &sh.kk_1, &sh.kk_2);
       }
     }
-    const size_t at = ((size_t)P.ray_offset[ray] + n) * P.n_nu;
+    const size_t at = (((size_t)P.ray_offset[ray] + n) * n_var + v) * P.n_nu;
     for (int l = 0; l < P.n_nu; l++) {
       const double freq = P.frequencies[l];
       double j_val = 0.0, alpha_val = 0.0;

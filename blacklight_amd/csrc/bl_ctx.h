@@ -152,6 +152,7 @@ struct bl_ctx {
   int image_num_quantities = 0;      // of one electron model and unit (bl_image_num_quantities: times the number of each)
   std::vector<double> model_rat_low, model_rat_high;   // bl_set_electron_models(); empty: the parameter block's pair
   std::vector<double> density_units;  // bl_set_density_units(): simulation_rho_cgs values; empty: the parameter block's
+  std::vector<double> pol_rat_low, pol_rat_high, pol_rho;   // bl_set_polarized_variants(): (R_low, R_high, simulation_rho_cgs) triples; empty: the parameter block's
   BlAuxImages aux_images{};          // which image rows exist; .any = an auxiliary image or a rendering is requested
   int render_num_images = 0;         // false-colour renderings (0 in formula mode)
   DeviceBuffer<BlRenderDevice> d_render_params;
@@ -231,6 +232,7 @@ struct bl_ctx {
     DeviceBuffer<double> d_pol_matrix;             // tolerant tier: 12 doubles per sample
     DeviceBuffer<BlFreqInputs> d_freq_inputs;      // tolerant tier, several frequencies
     DeviceBuffer<double2> d_pol_coeffs;
+    DeviceBuffer<double2> d_pol_variant_coeffs;    // polarized variants in one pass: [sample row][variant][n_nu][4] instead of d_pol_coeffs
     DeviceBuffer<unsigned int> d_anchors;          // inter-block interpolation: eight anchor cells per record
     DeviceBuffer<BlCoefInputs> d_coef_inputs;      // polarized runs: coefficient kernel -> polarized coefficient kernel
     DeviceBuffer<unsigned char> d_have_flags;      // ... where bl_shade_polarized2_kernel evaluates the coefficients itself: which records have them
@@ -242,12 +244,12 @@ struct bl_ctx {
       return d_records_hot.count * sizeof(BlSampleHot) + d_records_cold.count * sizeof(BlSampleCold) + d_located.count * sizeof(BlLocated)
           + d_located_tag.count * sizeof(unsigned long long) + (d_transfer.count + d_composed.count) * sizeof(double2) + d_parked.count * sizeof(double) + d_aux.count * sizeof(BlAuxSample)
           + (d_sample_t.count + d_slow_frac.count + d_pol_matrix.count + d_tau_inc.count) * sizeof(double) + d_pol_samples.count * sizeof(BlPolSample)
-          + d_freq_inputs.count * sizeof(BlFreqInputs) + d_pol_coeffs.count * sizeof(double2) + d_anchors.count * sizeof(unsigned int)
+          + d_freq_inputs.count * sizeof(BlFreqInputs) + (d_pol_coeffs.count + d_pol_variant_coeffs.count) * sizeof(double2) + d_anchors.count * sizeof(unsigned int)
           + d_coef_inputs.count * sizeof(BlCoefInputs) + d_redo.count * sizeof(unsigned long long) + d_have_flags.count
           + d_xcd_state.count * sizeof(unsigned long long) + d_xcd_lists.count * sizeof(unsigned int);
     }
     void Free() {
-      d_have_flags.Free(); d_redo.Free(); d_tau_inc.Free(); d_aux.Free(); d_sample_t.Free(); d_slow_frac.Free(); d_pol_samples.Free(); d_pol_matrix.Free(); d_freq_inputs.Free(); d_pol_coeffs.Free(); d_coef_inputs.Free(); d_anchors.Free();
+      d_have_flags.Free(); d_redo.Free(); d_tau_inc.Free(); d_aux.Free(); d_sample_t.Free(); d_slow_frac.Free(); d_pol_samples.Free(); d_pol_matrix.Free(); d_freq_inputs.Free(); d_pol_coeffs.Free(); d_pol_variant_coeffs.Free(); d_coef_inputs.Free(); d_anchors.Free();
       d_records_hot.Free(); d_records_cold.Free(); d_located.Free(); d_located_tag.Free(); d_transfer.Free(); d_composed.Free(); d_parked.Free(); d_counters.Free();
       d_xcd_state.Free(); d_xcd_lists.Free();
     }
@@ -332,6 +334,8 @@ struct bl_ctx {
   int tile_order_res = 0;
   bool tile_order_xcd = false;   // d_tile_order in super-tiles of 8 x 8 tiles (the trace order per XCD, bl_render.hip) or tile by tile
   DeviceBuffer<BlShadeCold> d_shade_cold;
+  DeviceBuffer<BlPolVariant> d_pol_variant_table;   // polarized variants in one pass: every variant's folded constants (BuildShadeArgs)
+  std::vector<unsigned char> pol_variant_host;   // the bytes d_pol_variant_table holds
   std::vector<unsigned char> shade_cold_host;   // the bytes d_shade_cold holds (BuildShadeArgs uploads on change only)
   // host-output staging
   DeviceBuffer<double> d_image, d_camera_pos, d_camera_dir;
@@ -362,6 +366,7 @@ void EnsureStreams(bl_ctx *ctx);
 void DropResident(bl_ctx *ctx);   // the root level's kept geodesics go (bl_render.hip)
 const char *ElectronModelsRefusal(const bl_ctx *ctx, int n);   // bl_set_electron_models (bl_api.hip)
 const char *DensityUnitsRefusal(const bl_ctx *ctx, int n);     // bl_set_density_units (bl_api.hip)
+const char *PolarizedVariantsRefusal(const bl_ctx *ctx, int n);   // bl_set_polarized_variants (bl_api.hip)
 }  // namespace blhost
 
 #endif  // BLACKLIGHT_AMD_BL_CTX_H_

@@ -402,6 +402,17 @@ struct alignas(16) BlCoefInputs {
   double have_coefficients;  // 1: the sample has coefficients; 0: j = alpha = rho = 0 at every frequency
 };
 
+// ... and with several polarized variants in one pass (bl_set_polarized_variants, BlShadeArgs::pol_variants > 0) the row of a sample
+// with coefficients holds what no variant enters: n_e_cgs = the cell's rho and p_gas (two floats), nu_c_cgs = b_mu b^mu in code units,
+// theta_e = kb_tt_e_cgs = 0; bl_polarized_coefficients_kernel forms n_e, nu_c, Theta_e and k T_e of every variant from them and the
+// variant's folded constants below (rows of samples without coefficients are as ever: bl_polarized_frame_kernel reads them).
+#define BL_POL_MAX_VARIANTS 16
+struct alignas(16) BlPolVariant {
+  double d_unit, e_unit, b_unit;   // FoldUnits of the variant's simulation_rho_cgs
+  double rat_high, rat_low;
+  double pad;
+};
+
 // Slow light (slow_light_on): the time slices the reader holds (simulation_reader.cpp:211-303), latest
 // first, all on the geometry of BlGridDevice. n = 0: off.
 struct BlSlowDevice {
@@ -468,6 +479,9 @@ struct BlShadeArgs {
   double2 *pol_coeffs;        // [sample row][n_nu][4]: (j_I, alpha_I), (j_Q, j_V), (alpha_Q, alpha_V), (rho_Q, rho_V) - one 64-byte record, half a
                               // cache line, for the lane of the sequential kernels that walks the ray (polarized runs have no `transfer` array)
   BlCoefInputs *coef_inputs;  // [record capacity]: coefficient kernel -> polarized coefficient kernel
+  int pol_variants;           // > 0: polarized variants in one pass - coef_inputs rows in their variant-free layout (BlPolVariant), and
+                              // bl_polarized_coefficients_kernel with a wave per (64 records, variant): pol_coeffs[(sample row * pol_variants + v)][n_nu][4]
+  const BlPolVariant *pol_variant_table;   // device [pol_variants]
   unsigned char *have_flags;  // [record capacity] or null: bl_shade_polarized2_kernel<..., kCoefficients> evaluates the coefficients itself and
                               // says here which records have them (bl_polarized_frame_kernel: the others' frames)
   unsigned int *anchors;      // inter-block interpolation: [record capacity][8] cells of the eight anchors, else null
@@ -493,6 +507,8 @@ struct BlTransferArgs {
   const BlPolSample *pol_samples;
   const double2 *pol_coeffs;
   double *pol_matrix;                      // tolerant tier: [sample row][BL_POL_MATRIX_DOUBLES] (bl_polarized.hip)
+  int pol_variants, pol_variant_rows;      // polarized variants in one pass: > 0, a lane per (ray, variant) in the polarized transfer kernels, variant v's
+                                           // coefficients in pol_coeffs[(sample row * pol_variants + v)][n_nu][4], its image rows from v * pol_variant_rows
   const double *camera_pos, *camera_dir;   // [n_rays_total][4] by output index: initial position, momentum
   BlSpacetime st;
   int simulation_coord, rotation_split;

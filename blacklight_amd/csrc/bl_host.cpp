@@ -339,6 +339,8 @@ int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const i
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more electron models (bl_set_electron_models).");
   if (bl_num_density_units(ctx) >= 2)
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more density units (bl_set_density_units).");
+  if (bl_num_polarized_variants(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more polarized variants (bl_set_polarized_variants).");
   const bl_params &p = *bl_internal_params(ctx);
   *n_refined = 0;
   if (p.adaptive_max_level <= 0 || level >= p.adaptive_max_level) {   // radiation_adaptive.cpp:22-23
@@ -412,6 +414,8 @@ int bl_write_output(bl_ctx *ctx, const char *path_override, const bl_output_desc
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no electron-model axis (bl_set_electron_models with n >= 2).");
   if (bl_num_density_units(ctx) >= 2)
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no density-unit axis (bl_set_density_units with n >= 2).");
+  if (bl_num_polarized_variants(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no variant axis (bl_set_polarized_variants with n >= 2).");
   if (d->level[0].image == nullptr && bl_image_num_quantities(ctx) > 0) return bl_internal_fail(ctx, BL_E_ARG, "bl_write_output needs the root image.");
   const bl_params &p = *bl_internal_params(ctx);
   const bl_camera_frame &frame = *bl_internal_frame(ctx);

@@ -453,20 +453,27 @@ __global__ void __launch_bounds__(64) bl_transfer_polarized_kernel(BlTransferArg
   // wave touches 64 consecutive doubles): 32 KiB per wave, which leaves the registers to N, N_temp and the step
   __shared__ double connection_lds[64 * 64];
   double *connection_old = connection_lds + threadIdx.x;
-  const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+  // (polarized variants in one pass, uniform per launch: a lane per (ray, variant), the variants of a ray in neighbouring lanes - they
+  // read the same samples, each its own coefficients and image rows; what a lane does for its ray and variant is what it does for a ray)
+  const int n_var = P.pol_variants > 0 ? P.pol_variants : 1;
+  const long long lane = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int slot = (int)(n_var > 1 ? lane / n_var : lane), variant = (int)(n_var > 1 ? lane % n_var : 0);
   if (slot >= bl_rays_done(P.counters, P.chunk_rays)) return;
   const BlSpacetime st = P.st;
   const int num = P.ray_sample_num[slot];
   const long long out_index = P.ray_out_index[slot];
   const double momentum_factor = P.ray_factor[slot];
   const size_t row = (size_t)P.n_rays_total;
-  double *img = P.image + out_index;
+  double *img = P.image + out_index + (size_t)variant * P.pol_variant_rows * row;
   const BlPolSample *samples = P.pol_samples + (size_t)P.ray_offset[slot];
-  const double2 *pc = P.pol_coeffs + (size_t)P.ray_offset[slot] * P.n_nu * 4;
+  const size_t nu_stride = (size_t)P.n_nu * n_var;   // (sample, frequency) pairs from one sample's coefficients to the next's
+  const double2 *pc = P.pol_coeffs + ((size_t)P.ray_offset[slot] * n_var + variant) * P.n_nu * 4;
   for (int l = 0; l < P.n_nu; l++) {
     const double freq = P.frequencies[l];
     if (num <= 0) {   // :94-96: nothing integrated; rows stay as the auxiliary kernel zeroed them
       for (int a = 0; a < 4; a++) img[(size_t)(4 * l + a) * row] = 0.0;
+      // (the auxiliary kernel zeroes the rows of one variant: with several in one pass, a variant's optical-depth row here)
+      if (n_var > 1 && P.aux_images.polarized_rows_only && P.aux_images.image_tau) img[(size_t)(P.aux_images.offset_tau + l) * row] = 0.0;
       continue;
     }
     // N is carried from sample to sample. N_temp is not: after a sample it is what from_stokes made of that sample's final
@@ -497,7 +504,7 @@ __global__ void __launch_bounds__(64) bl_transfer_polarized_kernel(BlTransferArg
       const double x1 = s.x[0], x2 = s.x[1], x3 = s.x[2];
       Coupling c;
       {
-        const size_t at = (size_t)rec * P.n_nu + l;
+        const size_t at = (size_t)rec * nu_stride + l;
         const double2 c0 = pc[at * 4 + 0], c1 = pc[at * 4 + 1], c2 = pc[at * 4 + 2], c3 = pc[at * 4 + 3];
         c.j_s[0] = c0.x; c.j_s[1] = c1.x; c.j_s[2] = 0.0; c.j_s[3] = c1.y;
         c.alpha_s[0] = c0.y; c.alpha_s[1] = c2.x; c.alpha_s[2] = 0.0; c.alpha_s[3] = c2.y;
@@ -588,7 +595,7 @@ __global__ void __launch_bounds__(64) bl_transfer_polarized_kernel(BlTransferArg
 }
 
 extern "C" hipError_t bl_launch_transfer_polarized(const BlTransferArgs *args, hipStream_t stream) {
-  const int grid = (args->chunk_rays + 63) / 64;
+  const int grid = (int)(((long long)args->chunk_rays * (args->pol_variants > 0 ? args->pol_variants : 1) + 63) / 64);   // (the plan keeps the lanes below 2^31)
   hipLaunchKernelGGL(bl_transfer_polarized_kernel, dim3(grid), dim3(64), 0, stream, *args);
   return hipGetLastError();
 }
@@ -932,17 +939,22 @@ __global__ void __launch_bounds__(256, 2) bl_transport_matrix_kernel(BlTransferA
 // camera's tetrad (:875-939) through the same projection algebra, and nu^3 (:942-949).
 __global__ void __launch_bounds__(64, 2) bl_transfer_polarized_matrix_kernel(BlTransferArgs P) {
   using namespace fastpol;
-  const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+  // (polarized variants in one pass, uniform per launch: a lane per (ray, variant), the variants of a ray in neighbouring lanes - they
+  // read the same 96-byte matrices, each its own coefficients and image rows)
+  const int n_var = P.pol_variants > 0 ? P.pol_variants : 1;
+  const long long lane = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int slot = (int)(n_var > 1 ? lane / n_var : lane), variant = (int)(n_var > 1 ? lane % n_var : 0);
   if (slot >= bl_rays_done(P.counters, P.chunk_rays)) return;
   const BlSpacetime st = P.st;
   const int num = P.ray_sample_num[slot];
   const long long out_index = P.ray_out_index[slot];
   const double momentum_factor = P.ray_factor[slot];
   const size_t row = (size_t)P.n_rays_total;
-  double *img = P.image + out_index;
+  double *img = P.image + out_index + (size_t)variant * P.pol_variant_rows * row;
   const BlPolSample *samples = P.pol_samples + (size_t)P.ray_offset[slot];
   const double *matrices = P.pol_matrix + (size_t)P.ray_offset[slot] * BL_POL_MATRIX_DOUBLES;
-  const double2 *pc = P.pol_coeffs + (size_t)P.ray_offset[slot] * P.n_nu * 4;
+  const size_t nu_stride = (size_t)P.n_nu * n_var;   // (sample, frequency) pairs from one sample's coefficients to the next's
+  const double2 *pc = P.pol_coeffs + ((size_t)P.ray_offset[slot] * n_var + variant) * P.n_nu * 4;
   // the last sample's second half step and the camera projection do not depend on the frequency
   double m_cam[10];
   if (num > 0) {
@@ -983,6 +995,8 @@ __global__ void __launch_bounds__(64, 2) bl_transfer_polarized_matrix_kernel(BlT
     const double freq = P.frequencies[l];
     if (num <= 0) {   // :94-96
       for (int a = 0; a < 4; a++) img[(size_t)(4 * l + a) * row] = 0.0;
+      // (the auxiliary kernel zeroes the rows of one variant: with several in one pass, a variant's optical-depth row here)
+      if (n_var > 1 && P.aux_images.polarized_rows_only && P.aux_images.image_tau) img[(size_t)(P.aux_images.offset_tau + l) * row] = 0.0;
       continue;
     }
     double ss_end[4] = {0.0, 0.0, 0.0, 0.0}, tau = 0.0;
@@ -993,7 +1007,7 @@ __global__ void __launch_bounds__(64, 2) bl_transfer_polarized_matrix_kernel(BlT
     {
       const double2 *mq = reinterpret_cast<const double2 *>(matrices + (size_t)(num - 1) * BL_POL_MATRIX_DOUBLES);
       n0 = mq[0]; n1 = mq[1]; n2 = mq[2]; n3 = mq[3]; n4 = mq[4]; n5 = mq[5];
-      const size_t at = (size_t)(num - 1) * P.n_nu + l;
+      const size_t at = (size_t)(num - 1) * nu_stride + l;
       nc0 = pc[at * 4 + 0]; nc1 = pc[at * 4 + 1]; nc2 = pc[at * 4 + 2]; nc3 = pc[at * 4 + 3];
     }
     for (int rec = num - 1; rec >= 0; rec--) {
@@ -1007,7 +1021,7 @@ __global__ void __launch_bounds__(64, 2) bl_transfer_polarized_matrix_kernel(BlT
         const int next = rec > 0 ? rec - 1 : 0;
         const double2 *mq = reinterpret_cast<const double2 *>(matrices + (size_t)next * BL_POL_MATRIX_DOUBLES);
         n0 = mq[0]; n1 = mq[1]; n2 = mq[2]; n3 = mq[3]; n4 = mq[4]; n5 = mq[5];
-        const size_t at = (size_t)next * P.n_nu + l;
+        const size_t at = (size_t)next * nu_stride + l;
         nc0 = pc[at * 4 + 0]; nc1 = pc[at * 4 + 1]; nc2 = pc[at * 4 + 2]; nc3 = pc[at * 4 + 3];
       }
       double ss_start[4];
@@ -1035,7 +1049,7 @@ extern "C" hipError_t bl_launch_transport_matrices(const BlTransferArgs *args, i
   return hipGetLastError();
 }
 extern "C" hipError_t bl_launch_transfer_polarized_rays(const BlTransferArgs *args, hipStream_t stream) {
-  const int grid = (args->chunk_rays + 63) / 64;
+  const int grid = (int)(((long long)args->chunk_rays * (args->pol_variants > 0 ? args->pol_variants : 1) + 63) / 64);   // (the plan keeps the lanes below 2^31)
   hipLaunchKernelGGL(bl_transfer_polarized_matrix_kernel, dim3(grid), dim3(64), 0, stream, *args);
   return hipGetLastError();
 }

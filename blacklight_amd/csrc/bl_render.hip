@@ -200,6 +200,11 @@ struct RenderJob {
   int n_models = 0, n_units = 0, n_q_model = 0, variant_passes = 1;
   bool variants_one_pass = false;   // ... or all of them in one pass: one gather, one lane per (ray, model, unit, frequency) in the transfer kernel
   double base_rho = 0.0;            // the unit BuildShadeArgs folds: the one set unit, else the parameter block's (one pass: the rows' unit)
+  // bl_set_polarized_variants: n_pol (R_low, R_high, unit) triples of a polarized run (0: the parameter block's; never beside models or
+  // units, which refuse polarized runs) - one shading pass each (variant_passes), or pol_one_pass: the coefficient kernel and the
+  // transport matrices once per chunk, bl_polarized_coefficients_kernel and the polarized transfer kernels with a variant axis
+  int n_pol = 0;
+  bool pol_one_pass = false;
   int n_cold = 1;                   // BlShadeCold blocks on the device: one per unit where the passes' cut thresholds differ (BindVariant)
   long long n_rays = 0, level_pixels = 0;
   size_t redo_capacity = 0;
@@ -301,6 +306,15 @@ void FoldFastCuts(const bl_ctx *ctx, const BlPlasmaDevice &pl, BlShadeCold &cold
 // two units there is one variant, the one BuildShadeArgs folded: nothing changes.
 void BindVariant(RenderJob &job, int v) {
   bl_ctx *ctx = job.ctx;
+  if (job.n_pol >= 2) {   // (one triple is the one BuildShadeArgs folded)
+    if (job.pol_one_pass) return;   // (BuildShadeArgs folded the first triple, whose cut decisions are every variant's; the table has the others)
+    BlPlasmaDevice &pl = job.sa.plasma;
+    pl.plasma_rat_low = ctx->pol_rat_low[v];
+    pl.plasma_rat_high = ctx->pol_rat_high[v];
+    FoldUnits(ctx, ctx->pol_rho[v], pl, job.sa.fast_k);
+    job.xa.image = job.image + static_cast<size_t>(v) * job.n_q_model * static_cast<size_t>(job.n_rays);
+    return;
+  }
   if (job.variants_one_pass || (job.n_models == 0 && job.n_units <= 1)) return;   // (one pass: the transfer kernel has every variant's constants, BuildTransferArgs)
   const bl_params &p = ctx->params;
   const int n_u = std::max(1, job.n_units), m = v / n_u, u = v % n_u;
@@ -340,9 +354,12 @@ void PlanJob(RenderJob &job) {
   job.n_units = static_cast<int>(ctx->density_units.size());
   if (const char *why = DensityUnitsRefusal(ctx, job.n_units)) throw Failure{BL_E_UNSUPPORTED, why};
   job.base_rho = job.n_units == 1 ? ctx->density_units[0] : p.simulation_rho_cgs;
+  job.n_pol = static_cast<int>(ctx->pol_rho.size());
+  if (const char *why = PolarizedVariantsRefusal(ctx, job.n_pol)) throw Failure{BL_E_UNSUPPORTED, why};
+  if (job.n_pol >= 1) job.base_rho = ctx->pol_rho[0];   // (one triple: rendered as a fresh render with it in the parameter block)
   job.n_nu = p.image_num_frequencies;
   job.n_q_model = ctx->image_num_quantities;
-  job.variant_passes = std::max(1, job.n_models) * std::max(1, job.n_units);
+  job.variant_passes = std::max(1, job.n_models) * std::max(1, job.n_units) * std::max(1, job.n_pol);
   job.n_q = job.n_q_model * job.variant_passes;
   job.max_steps = p.ray_max_steps;
   job.n_rays = d->n_rays;
@@ -497,6 +514,23 @@ void PlanJob(RenderJob &job) {
       || AI.image_emission || AI.image_lambda_ave || AI.image_emission_ave || AI.image_tau_int || AI.image_crossings);
   // configuration 4's case: no BlCoefInputs through HBM, no bl_polarized_coefficients_kernel launch (bl_shade_fused.hip: kCoefficients)
   job.pol_coefficients_inside = job.pol_fused && job.n_nu == 1 && job.rows_only && p.plasma_power_frac == 0.0 && p.plasma_kappa_frac == 0.0 && ctx->st.bh_a == 0.0;
+  // Polarized variants in one pass: where no decision differs between them - a rho, n_e, p_gas or B cut only with one unit, a Theta_e
+  // cut only with one unit and one pair (the units reach Theta_e through roundings), Stokes rows and the optical-depth row only (the
+  // rows the polarized transfer kernels write), Theta_e from R_high / R_low (code_kappa: passes) - and the lanes of a chunk fit one grid
+  if (job.n_pol >= 2) {
+    bool same_units = true, same_pairs = true;
+    for (int v = 1; v < job.n_pol; v++) {
+      same_units = same_units && ctx->pol_rho[v] == ctx->pol_rho[0];
+      same_pairs = same_pairs && ctx->pol_rat_low[v] == ctx->pol_rat_low[0] && ctx->pol_rat_high[v] == ctx->pol_rat_high[0];
+    }
+    const bool theta_e_cut = p.cut_theta_e_min >= 0.0 || p.cut_theta_e_max >= 0.0;
+    job.pol_one_pass = job.rows_only && p.plasma_model != BL_PLASMA_CODE_KAPPA && !(unit_cut && !same_units)
+        && !(theta_e_cut && !(same_units && same_pairs)) && job.n_rays * job.n_pol < (1ll << 31);
+    if (job.pol_one_pass) {
+      job.variant_passes = 1;
+      job.pol_coefficients_inside = false;   // (the samples go through the 64-byte row, which is where the variants part)
+    }
+  }
   // Host outputs of a quarter of a GiB and more in eight rows or more (configuration 5: 64 frequencies): the rays are traced in pixel
   // order - not the 8 x 8 tiles, centre first, that make chunks drain faster - so that what a chunk finishes is a range of columns,
   // downloaded while the next chunk renders (the image rows of a 4096^2 x 64 frame are 8.6 GB: 0.7 s of PCIe that used to follow the
@@ -746,7 +780,7 @@ bool PlanKeptLayout(RenderJob &job, long long max_grid, long long quad_waves, in
   if (ctx->polarized) {
     use(sl.d_pol_samples, 1);
     if (job.matrix_transport) use(sl.d_pol_matrix, BL_POL_MATRIX_DOUBLES);
-    use(sl.d_pol_coeffs, n_nu * 4);
+    if (!job.pol_one_pass) use(sl.d_pol_coeffs, n_nu * 4);   // (one pass: d_pol_variant_coeffs, which stays out of the store - EnsureScratchOnce)
     use(sl.d_coef_inputs, 1);
     if (job.pol_coefficients_inside) use(sl.d_have_flags, 1);
   }
@@ -880,7 +914,9 @@ void PlanScratch(RenderJob &job) {
       + (job.freq_split ? sizeof(BlFreqInputs) : (ctx->polarized ? 0 : sizeof(double2) * n_nu)) + (job.tau_row ? sizeof(double) * n_nu : 0)
       + (job.composed ? sizeof(double2) : 0)
       + ((job.aux && !job.rows_only) ? sizeof(BlAuxSample) : 0) + (job.need_time ? sizeof(double) : 0) + (job.slow ? sizeof(double) : 0)
-      + (ctx->polarized ? sizeof(BlPolSample) + sizeof(BlCoefInputs) + 4 * sizeof(double2) * n_nu + (job.pol_coefficients_inside ? 1 : 0) : 0)
+      // (polarized variants in one pass: every variant's coefficients, in an array of their own - d_pol_variant_coeffs - instead of d_pol_coeffs)
+      + (ctx->polarized ? sizeof(BlPolSample) + sizeof(BlCoefInputs) + 4 * sizeof(double2) * n_nu * (job.pol_one_pass ? job.n_pol : 1)
+                              + (job.pol_coefficients_inside ? 1 : 0) : 0)
       + (job.coef_split ? sizeof(BlCoefInputs) : 0)
       + (job.matrix_transport ? BL_POL_MATRIX_DOUBLES * sizeof(double) : 0)
       + ((job.block_interp && !job.locate_inside) ? 8 * sizeof(unsigned int) : 0)
@@ -890,6 +926,17 @@ void PlanScratch(RenderJob &job) {
     // over the resident records: the scratch set as the render that integrated them sized it, no stepper, nothing parked
     job.n_slots = 1;
     job.record_capacity = ctx->resident.record_capacity;
+    // (polarized variants in one pass: the one array that grows with the number of variants must fit under the scratch limit beside
+    // what the set holds - else one shading pass per variant over the resident records, which needs nothing more)
+    if (job.pol_one_pass) {
+      const bl_ctx::ChunkSlot &sl = ctx->slot[0];
+      const uint64_t wanted = static_cast<uint64_t>(job.record_capacity) * n_nu * 4 * job.n_pol * sizeof(double2);
+      const uint64_t have = sl.d_pol_variant_coeffs.count * sizeof(double2);
+      if (wanted > have && sl.Bytes() - have + wanted > ctx->scratch_limit) {
+        job.pol_one_pass = false;
+        job.variant_passes = job.n_pol;
+      }
+    }
     job.record_gate = static_cast<long long>(job.record_capacity);
     if (job.reuse_chunks) job.segments = ctx->resident.segments;
     job.chunk_capacity = job.record_capacity;
@@ -1063,7 +1110,10 @@ void EnsureScratchOnce(RenderJob &job) {
     if (ctx->polarized) {
       sl.d_pol_samples.Ensure(cap);
       if (job.matrix_transport) sl.d_pol_matrix.Ensure(cap * BL_POL_MATRIX_DOUBLES);
-      sl.d_pol_coeffs.Ensure(cap * n_nu * 4);
+      if (!job.pol_one_pass) sl.d_pol_coeffs.Ensure(cap * n_nu * 4);
+      // (polarized variants in one pass: not a part of the kept layout's store - PlanKeptLayout - so that a render over resident
+      // records may have more variants than the one that integrated them)
+      if (job.pol_one_pass) sl.d_pol_variant_coeffs.Ensure(cap * n_nu * 4 * static_cast<size_t>(job.n_pol));
       sl.d_coef_inputs.Ensure(cap);
       if (job.pol_coefficients_inside) sl.d_have_flags.Ensure(cap);
     }
@@ -1398,8 +1448,8 @@ void BuildShadeArgs(RenderJob &job) {
     BlPlasmaDevice &pl = sa.plasma;
     pl.plasma_mu = p.plasma_mu;
     pl.plasma_ne_ni = p.plasma_ne_ni;
-    pl.plasma_rat_low = p.plasma_rat_low;
-    pl.plasma_rat_high = p.plasma_rat_high;
+    pl.plasma_rat_low = job.n_pol >= 1 ? ctx->pol_rat_low[0] : p.plasma_rat_low;     // (bl_set_polarized_variants: the first triple, BindVariant the others)
+    pl.plasma_rat_high = job.n_pol >= 1 ? ctx->pol_rat_high[0] : p.plasma_rat_high;
     pl.plasma_thermal_frac = ctx->plasma_thermal_frac;
     FoldUnits(ctx, job.base_rho, pl, sa.fast_k);            // simulation_coefficients.cpp:237-239 (bl_set_density_units: BindVariant)
     FillElectronConstants(job, pl, cold);
@@ -1484,6 +1534,33 @@ void BuildShadeArgs(RenderJob &job) {
     ctx->shade_cold_host = colds;
   }
   sa.cold = ctx->d_shade_cold.ptr;
+  // Polarized variants in one pass: every triple folded as the render's own is (FoldUnits), for bl_polarized_coefficients_kernel
+  sa.pol_variants = 0;
+  sa.pol_variant_table = nullptr;
+  if (job.pol_one_pass) {
+    static_assert(BL_POL_MAX_VARIANTS == BL_MAX_POLARIZED_VARIANTS, "variant constants");
+    std::vector<BlPolVariant> table(job.n_pol);
+    for (int v = 0; v < job.n_pol; v++) {
+      BlPlasmaDevice variant_pl = sa.plasma;
+      double variant_k[8];
+      variant_pl.plasma_rat_low = ctx->pol_rat_low[v];
+      variant_pl.plasma_rat_high = ctx->pol_rat_high[v];
+      FoldUnits(ctx, ctx->pol_rho[v], variant_pl, variant_k);
+      table[v] = BlPolVariant{variant_pl.d_unit, variant_pl.e_unit, variant_pl.b_unit, variant_pl.plasma_rat_high, variant_pl.plasma_rat_low, 0.0};
+    }
+    // (uploaded when it differs from what the device holds, as the cold block above: a fit's renders wait here only when their units change)
+    std::vector<unsigned char> bytes(table.size() * sizeof(BlPolVariant));
+    std::memcpy(bytes.data(), table.data(), bytes.size());
+    if (ctx->pol_variant_host != bytes) {
+      ctx->d_pol_variant_table.Ensure(BL_POL_MAX_VARIANTS);
+      ctx->pol_variant_host.clear();
+      Check(hipMemcpyAsync(ctx->d_pol_variant_table.ptr, bytes.data(), bytes.size(), hipMemcpyHostToDevice, stream), "variant table upload");
+      Check(hipStreamSynchronize(stream), "variant table upload");
+      ctx->pol_variant_host = bytes;
+    }
+    sa.pol_variants = job.n_pol;
+    sa.pol_variant_table = ctx->d_pol_variant_table.ptr;
+  }
   sa.frequencies = ctx->d_freq.ptr;
   sa.n_nu = job.n_nu;
   sa.ray_max_steps = job.max_steps;
@@ -1548,6 +1625,8 @@ void BuildTransferArgs(RenderJob &job) {
   xa.image = job.image;
   xa.n_models = 0;
   xa.n_units = 0;
+  xa.pol_variants = job.pol_one_pass ? job.n_pol : 0;
+  xa.pol_variant_rows = job.n_q_model;
   if (job.variants_one_pass) {   // every model's R_high / R_low folded as BuildShadeArgs folds the parameter block's (fast_k[1..3])
     static_assert(BL_TRANSFER_MAX_MODELS == BL_MAX_ELECTRON_MODELS, "model constants");
     static_assert(BL_TRANSFER_MAX_UNITS == BL_MAX_DENSITY_UNITS, "unit constants");
@@ -1682,7 +1761,7 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   }
   xa.chunk_rays = rays;
   xa.counters = sl.d_counters.ptr;
-  xa.transfer = ctx->polarized ? sl.d_pol_coeffs.ptr : sl.d_transfer.ptr;
+  xa.transfer = ctx->polarized ? (job.pol_one_pass ? sl.d_pol_variant_coeffs.ptr : sl.d_pol_coeffs.ptr) : sl.d_transfer.ptr;   // (one pass: rows_only, never read)
   xa.ja_stride = ctx->polarized ? 4 : 1;
   xa.composed = sa.composed;
   xa.ray_rows = ta.ray_rows;
@@ -1702,6 +1781,7 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
     sa.pol_coeffs = sl.d_pol_coeffs.ptr;
     xa.pol_samples = sl.d_pol_samples.ptr;
     xa.pol_coeffs = sl.d_pol_coeffs.ptr;
+    if (job.pol_one_pass) sa.pol_coeffs = sl.d_pol_variant_coeffs.ptr, xa.pol_coeffs = sl.d_pol_variant_coeffs.ptr;
     xa.pol_matrix = job.matrix_transport ? sl.d_pol_matrix.ptr : nullptr;
   }
 }
@@ -2417,7 +2497,7 @@ void FinishStats(RenderJob &job) {
   st.launches_locate = (job.simulation && !job.locate_inside && !job.reuse_located) ? job.n_chunks : 0;
   st.geodesics_reused = job.reuse ? 1 : 0;
   st.sampling_reused = job.reuse_located ? 1 : 0;
-  st.launches_shade = job.n_chunks * job.variant_passes;
+  st.launches_shade = job.n_chunks * job.variant_passes;   // (polarized variants in one pass: the coefficient kernel once per chunk)
   st.launches_transfer = job.n_chunks * job.variant_passes;
   st.n_samples = static_cast<int64_t>(job.total_samples);
   st.n_samples_emitted = static_cast<int64_t>(job.total_records);

@@ -140,6 +140,7 @@ struct SampleShade {
   double nu_fluid_over_nu;     // -k_mu u^mu (fluid-frame frequency per unit camera frequency*factor)
   double n_e_cgs, nu_c_cgs, theta_e, sin_theta_b, kb_tt_e_cgs;   // simulation
   double cos_theta_b, sin2_theta_b, cos2_theta_b, cos_sign;       // polarized coefficients only
+  double b_sq;                 // b_mu b^mu in code units (polarized variants in one pass: write_polarized_inputs)
   double theta_e_096, kk_0, kk_1, kk_2;   // polarized, thermal: theta_e^0.96 and K_0,1,2(1 / theta_e) - the same at every frequency
   double n_n0_fluid, fu[4];                                       // formula
   bool have_cell;              // cell_values recorded (simulation_coefficients.cpp:377-387)
@@ -1005,6 +1006,44 @@ __device__ __forceinline__ void sample_primitives_slow(const BlShadeArgs &P, int
   }
 }
 
+// What a density unit and an electron model make of a cell's rho, p_gas, b_mu b^mu and 1 / beta (simulation_coefficients.cpp:
+// 274-289, :333-348, :465): the only place they enter a sample. sample_finish_simulation() calls these with the render's units and
+// pair; bl_polarized_coefficients_kernel, with several polarized variants in one pass, calls them again per variant on the same
+// operands - the same operations in the same order, so the same bits as a render with that variant in the parameter block.
+struct PlasmaCgs {
+  double rho_cgs, pgas_cgs, n_e_cgs;
+};
+__device__ __forceinline__ PlasmaCgs plasma_density_cgs(const BlPlasmaDevice &pl, double d_unit, double e_unit, double rho, double pgas) {
+  PlasmaCgs c;
+  c.rho_cgs = rho * d_unit;
+  c.pgas_cgs = pgas * e_unit;
+  // The quotients below have operands that are products of single-precision grid values (zero, or
+  // 1e-45 .. 3e38 in magnitude) and unit constants: far inside the range where bl_div_g() is the IEEE
+  // quotient (bl_geometry.h). Quotients that involve results of exp() keep the plain division.
+  const double n_cgs = bl_div_g(c.rho_cgs, pl.plasma_mu * kMp);
+  c.n_e_cgs = bl_div_g(n_cgs, 1.0 + 1.0 / pl.plasma_ne_ni);
+  return c;
+}
+__device__ __forceinline__ double plasma_field_cgs(double b_sq, double b_unit) { return bl_sqrt_g(b_sq) * b_unit; }
+__device__ __forceinline__ double plasma_beta_inverse(double b_sq, double pgas) { return bl_div_g(b_sq, 2.0 * pgas); }
+__device__ __forceinline__ double plasma_cyclotron_frequency(double bb_cgs) { return bl_div_g(kE * bb_cgs, 2.0 * kPi * kMe * kC); }
+// electron temperature, T_i/T_e(beta) model (:333-348); plasma_thermal_frac != 0 and not plasma_model = code_kappa
+__device__ __forceinline__ void plasma_electron_temperature(const BlShadeArgs &P, double rat_high, double rat_low, double beta_inv, const PlasmaCgs &c,
+                                                            double *theta_e_out, double *kb_tt_e_cgs_out) {
+  const BlPlasmaDevice &pl = P.plasma;
+  double kb_tt_e_cgs;
+  double tti_tte = bl_div_g(rat_high + rat_low * beta_inv * beta_inv, 1.0 + beta_inv * beta_inv);
+  double kb_tt_tot_cgs = bl_div_g(pl.plasma_mu * kMp * c.pgas_cgs, c.rho_cgs);
+  if (pl.plasma_use_p) {
+    kb_tt_e_cgs = bl_div_g(1.0 + pl.plasma_ne_ni, tti_tte + pl.plasma_ne_ni) * kb_tt_tot_cgs;
+  } else {
+    kb_tt_e_cgs = (1.0 + pl.plasma_ne_ni) * kb_tt_tot_cgs / (P.cold->plasma_gamma - 1.0);
+    kb_tt_e_cgs /= tti_tte / (P.cold->plasma_gamma_i - 1.0) + pl.plasma_ne_ni / (P.cold->plasma_gamma_e - 1.0);
+  }
+  *kb_tt_e_cgs_out = kb_tt_e_cgs;
+  *theta_e_out = bl_div_g(kb_tt_e_cgs, kMe * kC * kC);
+}
+
 // Simulation mode: the frequency-independent part of CalculateSimulationCoefficients
 // (simulation_coefficients.cpp:253-455). kExtended: the instantiation that also knows plasma_model = code_kappa.
 template <bool kExtended, bool kSksCurved>
@@ -1023,13 +1062,8 @@ __device__ __forceinline__ void sample_finish_simulation(const BlShadeArgs &P, c
   const double rho = pr[0], pgas = pr[1];
   const double uu1 = pr[2], uu2 = pr[3], uu3 = pr[4];
   const double bb1 = pr[5], bb2 = pr[6], bb3 = pr[7];
-  const double rho_cgs = rho * pl.d_unit;
-  const double pgas_cgs = pgas * pl.e_unit;
-  // The quotients below have operands that are products of single-precision grid values (zero, or
-  // 1e-45 .. 3e38 in magnitude) and unit constants: far inside the range where bl_div_g() is the IEEE
-  // quotient (bl_geometry.h). Quotients that involve results of exp() keep the plain division.
-  const double n_cgs = bl_div_g(rho_cgs, pl.plasma_mu * kMp);
-  const double n_e_cgs = bl_div_g(n_cgs, 1.0 + 1.0 / pl.plasma_ne_ni);
+  const PlasmaCgs cgs = plasma_density_cgs(pl, pl.d_unit, pl.e_unit, rho, pgas);
+  const double rho_cgs = cgs.rho_cgs, pgas_cgs = cgs.pgas_cgs, n_e_cgs = cgs.n_e_cgs;
 
   // Velocity and field in simulation coordinates (:292-330). In SKS the metric is sparse
   // (radiation_geometry.cpp:462-489, :543-571); sums that the reference runs over all 16 entries
@@ -1113,9 +1147,9 @@ __device__ __forceinline__ void sample_finish_simulation(const BlShadeArgs &P, c
       b_sq += acc * bcon_sim[mu];
     }
   }
-  const double bb_cgs = bl_sqrt_g(b_sq) * pl.b_unit;
+  const double bb_cgs = plasma_field_cgs(b_sq, pl.b_unit);
   const double sigma_cut = b_sq / rho;
-  const double beta_inv = bl_div_g(b_sq, 2.0 * pgas);
+  const double beta_inv = plasma_beta_inverse(b_sq, pgas);
 
   // electron temperature, T_i/T_e(beta) model (:333-348)
   double theta_e = __longlong_as_double(0x7ff8000000000000ll);
@@ -1131,15 +1165,7 @@ __device__ __forceinline__ void sample_finish_simulation(const BlShadeArgs &P, c
       kb_tt_e_cgs = theta_e * kMe * kC * kC;
     }
   } else if (pl.plasma_thermal_frac != 0.0) {
-    double tti_tte = bl_div_g(pl.plasma_rat_high + pl.plasma_rat_low * beta_inv * beta_inv, 1.0 + beta_inv * beta_inv);
-    double kb_tt_tot_cgs = bl_div_g(pl.plasma_mu * kMp * pgas_cgs, rho_cgs);
-    if (pl.plasma_use_p) {
-      kb_tt_e_cgs = bl_div_g(1.0 + pl.plasma_ne_ni, tti_tte + pl.plasma_ne_ni) * kb_tt_tot_cgs;
-    } else {
-      kb_tt_e_cgs = (1.0 + pl.plasma_ne_ni) * kb_tt_tot_cgs / (P.cold->plasma_gamma - 1.0);
-      kb_tt_e_cgs /= tti_tte / (P.cold->plasma_gamma_i - 1.0) + pl.plasma_ne_ni / (P.cold->plasma_gamma_e - 1.0);
-    }
-    theta_e = bl_div_g(kb_tt_e_cgs, kMe * kC * kC);
+    plasma_electron_temperature(P, pl.plasma_rat_high, pl.plasma_rat_low, beta_inv, cgs, &theta_e, &kb_tt_e_cgs);
   }
 
   // cell cuts (:361-375); all thresholds negative = disabled is the common case
@@ -1236,7 +1262,8 @@ __device__ __forceinline__ void sample_finish_simulation(const BlShadeArgs &P, c
   out->have_coefficients = true;
   out->nu_fluid_over_nu = nu_sum;
   out->n_e_cgs = n_e_cgs;
-  out->nu_c_cgs = bl_div_g(kE * bb_cgs, 2.0 * kPi * kMe * kC);
+  out->nu_c_cgs = plasma_cyclotron_frequency(bb_cgs);
+  out->b_sq = b_sq;
   out->theta_e = theta_e;
   out->sin_theta_b = bl_sqrt_g(sin2_theta_b);
   out->kb_tt_e_cgs = kb_tt_e_cgs;
@@ -1532,7 +1559,19 @@ __device__ __forceinline__ void write_polarized_inputs(const BlShadeArgs &P, uns
   ps->x[0] = x1; ps->x[1] = x2; ps->x[2] = x3;
   ps->delta_lambda = delta_lambda;
   BlCoefInputs ci;
-  if (sh.have_coefficients) {
+  if (sh.have_coefficients && P.pol_variants > 0) {
+    // several polarized variants in one pass (wave-uniform): what no variant enters, in the fields the variants' values have
+    // otherwise - rho and p_gas as the cell's two floats, b_mu b^mu - from which bl_polarized_coefficients_kernel forms every
+    // variant's n_e, nu_c, Theta_e and k T_e (plasma_density_cgs and the functions beside it)
+    ci.nu_fluid_over_nu = sh.nu_fluid_over_nu;
+    ci.n_e_cgs = __hiloint2double(__float_as_int(pr[1]), __float_as_int(pr[0]));
+    ci.nu_c_cgs = sh.b_sq;
+    ci.theta_e = 0.0;
+    ci.kb_tt_e_cgs = 0.0;
+    ci.cos2_theta_b = sh.cos2_theta_b;
+    ci.cos_sign = sh.cos_sign;
+    ci.have_coefficients = 1.0;
+  } else if (sh.have_coefficients) {
     ci.nu_fluid_over_nu = sh.nu_fluid_over_nu;
     ci.n_e_cgs = sh.n_e_cgs;
     ci.nu_c_cgs = sh.nu_c_cgs;

@@ -37,3 +37,18 @@ def total_flux_jy(image_rows, params, distance_pc, frequency=0):
     if intensity.size == 0 or np.isnan(intensity).all():
         return math.nan
     return float(np.nanmean(intensity)) * camera_solid_angle(params, distance_pc) / JY_CGS
+
+
+def stokes_flux_jy(image_rows, params, distance_pc, frequency=0):
+    """(I, Q, U, V) in Jy of a polarized root-level image at the image's frequency number `frequency`: rows 4 f .. 4 f + 3 of
+    image_rows (n_q, n_pixels), each summed as total_flux_jy sums a row - the mean over the pixels that are not NaN in that row."""
+    rows = np.asarray(image_rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[0] < 4 * frequency + 4:
+        raise ValueError(f"stokes flux: image rows {rows.shape} hold no Stokes rows of frequency {frequency}")
+    return tuple(total_flux_jy(rows[4 * frequency + s], params, distance_pc) for s in range(4))
+
+
+def net_polarization(stokes):
+    """(m_net, v_net, evpa_rad) = (hypot(Q, U) / I, V / I, atan2(U, Q) / 2) of the fluxes (I, Q, U, V) stokes_flux_jy returns."""
+    i, q, u, v = (float(x) for x in stokes)
+    return math.hypot(q, u) / i, v / i, 0.5 * math.atan2(u, q)

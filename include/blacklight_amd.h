@@ -391,6 +391,26 @@ BL_API int bl_num_electron_models(const bl_ctx *ctx);   /* 0 = unset: the parame
 #define BL_MAX_DENSITY_UNITS 16
 BL_API int bl_set_density_units(bl_ctx *ctx, int n, const double *rho_cgs);
 BL_API int bl_num_density_units(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own unit; -1: no context */
+/* Polarized variants: (R_low, R_high, simulation_rho_cgs) triples rendered by one bl_render of a polarized run - the door the two calls
+ * above keep shut (they refuse image_polarization = true). A list of triples, not a product: after a flux fit every pair has a unit
+ * of its own. n = 0 (what a context starts with): the parameter block's own pair and unit. 1 <= n <= BL_MAX_POLARIZED_VARIANTS:
+ * bl_image_num_quantities is n times the single-render count and image row v * n_q + q is row q (rows 4 l + (I, Q, U, V), ...) of
+ * variant v; sample_num, sample_flags and the camera outputs come out once. BL_E_ARG: n out of range, a null array with n > 0, a
+ * non-finite R_low or R_high, a unit that is not finite and > 0. Refused (BL_E_UNSUPPORTED): a context that is not polarized (use
+ * bl_set_electron_models / bl_set_density_units there), formula mode, slow light, and with n >= 2 adaptive_max_level > 0 and
+ * render_num_images > 0 - as are bl_adaptive_refine and bl_write_output while n >= 2. A refused call changes nothing. With
+ * plasma_model = code_kappa the pairs are unused, the units are not. Geodesics and located samples do not depend on the variants:
+ * changing them between renders keeps what is resident (bl_stats.geodesics_reused).
+ * Every variant's rows are the bits of a render with that triple in the parameter block, in the exact tier and - under
+ * bl_set_reproducible, and wherever the polarized tolerant path repeats itself - in the tolerant one. n = 1 plans as that render does.
+ * n >= 2 renders in ONE PASS where no decision differs between variants - Stokes rows and the optical-depth row only (no other
+ * auxiliary row), Theta_e from R_high / R_low, a cut on rho, n_e, p_gas or B only if all units are equal, a Theta_e cut only if all triples are
+ * equal: the gather, fluid frame and tetrad once per chunk (bl_stats.launches_shade = n_chunks), the transport matrices once, a
+ * coefficient-kernel wave per (64 samples, variant) and a transfer lane per (ray, variant). Everything else: one shading pass per
+ * variant over the shared samples (launches_shade = n_chunks * n). */
+#define BL_MAX_POLARIZED_VARIANTS 16
+BL_API int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs);
+BL_API int bl_num_polarized_variants(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own pair and unit; -1: no context */
 /* Number of false-colour renderings bl_render produces (render_num_images; 0 in formula mode). */
 BL_API int bl_render_num_images(const bl_ctx *ctx);
 BL_API int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out);
