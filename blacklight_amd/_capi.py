@@ -31,6 +31,15 @@ class GridDesc(C.Structure):
     ]
 
 
+BL_MAX_SWEEP = 16
+
+
+class Sweep(C.Structure):
+    """bl_sweep: the sweep_rat_low / sweep_rat_high / sweep_rho_cgs lists of a .input file, kept beside the parameter block."""
+    _fields_ = [("n_rat_low", C.c_int32), ("n_rat_high", C.c_int32), ("n_rho_cgs", C.c_int32), ("reserved", C.c_int32),
+                ("rat_low", C.c_double * BL_MAX_SWEEP), ("rat_high", C.c_double * BL_MAX_SWEEP), ("rho_cgs", C.c_double * BL_MAX_SWEEP)]
+
+
 class CameraFrame(C.Structure):
     _fields_ = [(name, C.c_double * 4) for name in
                 ("cam_x", "u_con", "u_cov", "norm_con", "norm_con_c", "hor_con_c", "vert_con_c")] + \
@@ -100,6 +109,13 @@ def lib():
     L.bl_params_read_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
     L.bl_params_get.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.bl_params_get_string.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t]
+    L.bl_params_set_line_sweep.argtypes = [C.c_void_p, C.POINTER(Sweep), C.c_char_p, C.c_char_p, C.c_size_t]
+    L.bl_params_read_file_sweep.argtypes = [C.c_void_p, C.POINTER(Sweep), C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+    L.bl_sweep_resolve.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Sweep), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+    L.bl_apply_sweep.argtypes = [C.c_void_p, C.POINTER(Sweep)]
+    L.bl_num_variants.argtypes = [C.c_void_p]
+    L.bl_write_output_variant.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(OutputDesc), C.c_int]
+    L.bl_variant_output_path.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.bl_init.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     L.bl_set_grid.argtypes = [C.c_void_p, C.POINTER(GridDesc)]
     L.bl_image_num_quantities.argtypes = [C.c_void_p]

@@ -26,6 +26,45 @@ class Context:
         self._grid_keepalive = None
         self.n_freq = int(params.get("image_num_frequencies"))
         self.resolution = int(params.get("camera_resolution"))
+        if getattr(params, "has_sweep", False):   # sweep_* keys of the .input grammar: the same call the command-line driver makes
+            try:
+                self.apply_sweep(params)
+            except Exception:
+                self.close()
+                raise
+
+    @classmethod
+    def from_input(cls, path, device: int = -1):
+        """A context from a .input file, its sweep keys applied (what bin/blacklight_amd sets up); .params.num_runs counts the snapshots."""
+        return cls(Params.from_file(path), device=device)
+
+    def apply_sweep(self, params=None):
+        """bl_apply_sweep: the sweep_rat_low / sweep_rat_high / sweep_rho_cgs lists of `params` (default: this context's) as electron
+        models and density units, or as polarized triples. An empty sweep changes nothing."""
+        params = params or self.params
+        if not params.has_sweep:
+            return
+        polarized, low, high, rho = params.resolved_sweep()
+        self._check(self._lib.bl_apply_sweep(self._ctx, C.byref(params.sweep)))
+        if polarized:
+            self._polarized_variants = [(h, lo, u) for h, lo, u in zip(high, low, rho)]
+        else:
+            if low:
+                self._electron_models = [(h, lo) for h, lo in zip(high, low)]
+            if rho:
+                self._density_units = list(rho)
+
+    @property
+    def num_variants(self):
+        """Images one render produces (bl_num_variants): models x units, or polarized triples."""
+        return self._lib.bl_num_variants(self._ctx)
+
+    def variant_output_path(self, snapshot=0, variant=0):
+        """The file name write_output(variant=...) uses without `path` (bl_variant_output_path): output_file, the file number of a
+        series, and a tag .mMMuUU / .vVV in front of the extension when the context renders several variants."""
+        buf = C.create_string_buffer(4096)
+        self._check(self._lib.bl_variant_output_path(self._ctx, int(snapshot), int(variant), buf, len(buf)))
+        return buf.value.decode()
 
     def close(self):
         if self._ctx:
@@ -508,8 +547,10 @@ class Context:
             out["block_locs"] = nxt
             levels.append(out)
 
-    def write_output(self, levels, path=None, snapshot=0):
-        """OutputWriter::Write (reference output_writer.cpp:169-274); `levels` as from render_adaptive."""
+    def write_output(self, levels, path=None, snapshot=0, variant=None):
+        """OutputWriter::Write (reference output_writer.cpp:169-274); `levels` as from render_adaptive. variant = v: image v of a
+        render of several variants ([render()]: the rows of all of them) as a file of its own (bl_write_output_variant) - what a
+        context with that variant in its parameter block writes; without `path` the name is variant_output_path(snapshot, v)."""
         d = _capi.OutputDesc()
         d.adaptive_num_levels = len(levels) - 1
         d.snapshot = snapshot
@@ -533,7 +574,11 @@ class Context:
                 camera = np.ascontiguousarray(camera, dtype=np.float64)
                 keep.append(camera)
                 d.level[index].camera = camera.ctypes.data_as(C.c_void_p)
-        self._check(self._lib.bl_write_output(self._ctx, None if path is None else str(path).encode(), C.byref(d)))
+        target = None if path is None else str(path).encode()
+        if variant is None:
+            self._check(self._lib.bl_write_output(self._ctx, target, C.byref(d)))
+        else:
+            self._check(self._lib.bl_write_output_variant(self._ctx, target, C.byref(d), int(variant)))
 
     def render_device(self, image_ptr, n_rays, level=0, pixel_map=None, sample_num_ptr=0, sample_flags_ptr=0,
                       block_locs=None, camera_pos_ptr=0, camera_dir_ptr=0, render_ptr=0):

@@ -408,41 +408,66 @@ int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const i
   return BL_OK;
 }
 
-int bl_write_output(bl_ctx *ctx, const char *path_override, const bl_output_desc *d) {
-  if (ctx == nullptr || d == nullptr) return BL_E_ARG;
-  if (bl_num_electron_models(ctx) >= 2)
-    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no electron-model axis (bl_set_electron_models with n >= 2).");
-  if (bl_num_density_units(ctx) >= 2)
-    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no density-unit axis (bl_set_density_units with n >= 2).");
-  if (bl_num_polarized_variants(ctx) >= 2)
-    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no variant axis (bl_set_polarized_variants with n >= 2).");
+}  // extern "C"
+
+namespace {
+
+// The file's name (output_writer.cpp:283-316 for a series) and, for one image of several, its tag (include/blacklight_amd.h)
+int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, std::string *path) {
+  const bl_params &p = *bl_internal_params(ctx);
+  if (!p.has[BL_P_output_file]) return bl_internal_fail(ctx, BL_E_MISSING, "OutputWriter unable to find all needed values in input file.");
+  *path = p.output_file.s;
+  if (p.model_type == BL_MODEL_SIMULATION && p.simulation_multiple) {
+    int file_number = snapshot + (p.slow_light_on ? p.slow_offset : p.simulation_start);
+    if (!FormatFilename(p.output_file.s, file_number, path))
+      return bl_internal_fail(ctx, BL_E_INPUT, "Invalid output_file for multiple runs.");
+  }
+  if (n_variants < 2) return BL_OK;
+  char tag[32];
+  if (bl_num_polarized_variants(ctx) >= 1) {
+    std::snprintf(tag, sizeof tag, ".v%02d", variant);
+  } else {
+    const int n_units = std::max(1, bl_num_density_units(ctx));
+    std::snprintf(tag, sizeof tag, ".m%02du%02d", variant / n_units, variant % n_units);
+  }
+  const std::string::size_type slash = path->find_last_of('/');
+  const std::string::size_type dot = path->find_last_of('.');
+  if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) path->append(tag);
+  else path->insert(dot, tag);
+  return BL_OK;
+}
+
+// "Error: ...\n" -> the message alone (what bl_internal_fail wraps again)
+std::string MessageOf(std::string text) {
+  if (text.compare(0, 7, "Error: ") == 0) text.erase(0, 7);
+  if (!text.empty() && text.back() == '\n') text.pop_back();
+  return text;
+}
+
+// bl_write_output and bl_write_output_variant: image `variant` of the n_variants the root level's rows hold
+int WriteOutput(bl_ctx *ctx, const char *path_override, const bl_output_desc *d, int variant, int n_variants) {
   if (d->level[0].image == nullptr && bl_image_num_quantities(ctx) > 0) return bl_internal_fail(ctx, BL_E_ARG, "bl_write_output needs the root image.");
   const bl_params &p = *bl_internal_params(ctx);
   const bl_camera_frame &frame = *bl_internal_frame(ctx);
   int n_nu = 0;
   const double *frequencies = bl_internal_frequencies(ctx, &n_nu);
   const int res = p.camera_resolution;
-  const int n_q = bl_image_num_quantities(ctx);
+  const int n_q = bl_image_num_quantities(ctx) / n_variants;
   const size_t n_pix = static_cast<size_t>(res) * res;
 
   std::string path;
   if (path_override != nullptr && path_override[0] != '\0') {
     path = path_override;
   } else {
-    if (!p.has[BL_P_output_file]) return bl_internal_fail(ctx, BL_E_MISSING, "OutputWriter unable to find all needed values in input file.");
-    path = p.output_file.s;
-    if (p.model_type == BL_MODEL_SIMULATION && p.simulation_multiple) {
-      int file_number = d->snapshot + (p.slow_light_on ? p.slow_offset : p.simulation_start);
-      if (!FormatFilename(p.output_file.s, file_number, &path))
-        return bl_internal_fail(ctx, BL_E_INPUT, "Invalid output_file for multiple runs.");
-    }
+    const int rc = OutputPath(ctx, d->snapshot, variant, n_variants, &path);
+    if (rc != BL_OK) return rc;
   }
   std::ofstream stream(path, std::ios_base::out | std::ios_base::binary);
   if (!stream.is_open()) return bl_internal_fail(ctx, BL_E_INPUT, "Could not open output file.");
 
   if (bl_render_num_images(ctx) > 0 && p.output_format != BL_OUTPUT_NPZ)
     return bl_internal_fail(ctx, BL_E_INPUT, "Only npz outputs support rendering.");
-  const double *image0 = d->level[0].image;
+  const double *image0 = d->level[0].image == nullptr ? nullptr : d->level[0].image + static_cast<size_t>(variant) * n_q * n_pix;
   if (p.output_format == BL_OUTPUT_RAW && p.model_type == BL_MODEL_SIMULATION && p.image_light && p.has[BL_P_image_polarization]
       && p.image_polarization)   // output_writer.cpp:64-70
     return bl_internal_fail(ctx, BL_E_INPUT, "Only npz or npy outputs support polarization.");
@@ -677,6 +702,72 @@ int bl_write_output(bl_ctx *ctx, const char *path_override, const bl_output_desc
   for (const Bytes &h : central_headers) put(h.data(), h.size());
   put(end.data(), end.size());
   return (written && stream.good()) ? BL_OK : bl_internal_fail(ctx, BL_E_INPUT, "Could not write output file.");
+}
+
+}  // namespace
+
+extern "C" {
+
+int bl_write_output(bl_ctx *ctx, const char *path_override, const bl_output_desc *d) {
+  if (ctx == nullptr || d == nullptr) return BL_E_ARG;
+  if (bl_num_electron_models(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no electron-model axis (bl_set_electron_models with n >= 2).");
+  if (bl_num_density_units(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no density-unit axis (bl_set_density_units with n >= 2).");
+  if (bl_num_polarized_variants(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no variant axis (bl_set_polarized_variants with n >= 2).");
+  return WriteOutput(ctx, path_override, d, 0, 1);
+}
+
+int bl_num_variants(const bl_ctx *ctx) {
+  if (ctx == nullptr) return -1;
+  return std::max(1, bl_num_electron_models(ctx)) * std::max(1, bl_num_density_units(ctx)) * std::max(1, bl_num_polarized_variants(ctx));
+}
+
+int bl_write_output_variant(bl_ctx *ctx, const char *path_override, const bl_output_desc *d, int variant) {
+  if (ctx == nullptr || d == nullptr) return BL_E_ARG;
+  const int n_variants = bl_num_variants(ctx);
+  if (variant < 0 || variant >= n_variants)
+    return bl_internal_fail(ctx, BL_E_ARG, ("bl_write_output_variant: variant " + std::to_string(variant) + " outside 0 .. " + std::to_string(n_variants - 1) + ".").c_str());
+  if (n_variants >= 2 && d->adaptive_num_levels != 0)
+    return bl_internal_fail(ctx, BL_E_ARG, "bl_write_output_variant: a render of several variants has no adaptive levels.");
+  return WriteOutput(ctx, path_override, d, variant, n_variants);
+}
+
+int bl_variant_output_path(bl_ctx *ctx, int snapshot, int variant, char *buf, size_t len) {
+  if (ctx == nullptr || buf == nullptr) return BL_E_ARG;
+  const int n_variants = bl_num_variants(ctx);
+  if (variant < 0 || variant >= n_variants)
+    return bl_internal_fail(ctx, BL_E_ARG, ("bl_variant_output_path: variant " + std::to_string(variant) + " outside 0 .. " + std::to_string(n_variants - 1) + ".").c_str());
+  std::string path;
+  const int rc = OutputPath(ctx, snapshot, variant, n_variants, &path);
+  if (rc != BL_OK) return rc;
+  if (path.size() + 1 > len) return bl_internal_fail(ctx, BL_E_ARG, "bl_variant_output_path: the buffer is too short for the name.");
+  std::memcpy(buf, path.c_str(), path.size() + 1);
+  return BL_OK;
+}
+
+int bl_apply_sweep(bl_ctx *ctx, const bl_sweep *sweep) {
+  if (ctx == nullptr || sweep == nullptr) return BL_E_ARG;
+  bl_sweep s;
+  int polarized = 0;
+  char err[512] = "";
+  if (bl_sweep_resolve(sweep, bl_internal_params(ctx), &s, &polarized, err, sizeof err) != BL_OK) {
+    return bl_internal_fail(ctx, BL_E_INPUT, MessageOf(err).c_str());
+  }
+  if (s.n_rat_low == 0 && s.n_rho_cgs == 0) return BL_OK;
+  if (polarized) return bl_set_polarized_variants(ctx, s.n_rho_cgs, s.rat_low, s.rat_high, s.rho_cgs);
+  int rc = BL_OK;
+  if (s.n_rat_low > 0) rc = bl_set_electron_models(ctx, s.n_rat_low, s.rat_low, s.rat_high);
+  if (rc == BL_OK && s.n_rho_cgs > 0) {
+    rc = bl_set_density_units(ctx, s.n_rho_cgs, s.rho_cgs);
+    if (rc != BL_OK && s.n_rat_low > 0) {   // neither list stays behind a refusal of the second
+      const std::string why = bl_last_error(ctx);
+      bl_set_electron_models(ctx, 0, nullptr, nullptr);
+      bl_internal_fail(ctx, rc, MessageOf(why).c_str());
+    }
+  }
+  return rc;
 }
 
 }  // extern "C"

@@ -180,7 +180,7 @@ struct LevelShare {
 
 int main(int argc, char *argv[]) {
   double time_start = Now();
-  double time_geodesic = 0.0, time_read = 0.0, time_sample = 0.0, time_image = 0.0, time_render = 0.0;
+  double time_geodesic = 0.0, time_read = 0.0, time_sample = 0.0, time_image = 0.0, time_render = 0.0, time_write = 0.0;
   if (argc != 2) {
     std::cout << "Error: Must give a single input file.\n";
     return 1;
@@ -188,7 +188,8 @@ int main(int argc, char *argv[]) {
   static bl_params params;
   char err[1024] = "";
   int num_runs = 1;
-  if (bl_params_read_file(&params, argv[1], &num_runs, err, sizeof err) != BL_OK) {
+  static bl_sweep sweep;   // sweep_rat_low / sweep_rat_high / sweep_rho_cgs: several images per snapshot, one file each
+  if (bl_params_read_file_sweep(&params, &sweep, argv[1], &num_runs, err, sizeof err) != BL_OK) {
     std::cout << err;
     return 1;
   }
@@ -227,11 +228,17 @@ int main(int argc, char *argv[]) {
     // in either tier (one transfer record per sample, 1.5 % of a frame), so that two runs of one input take the same decisions -
     // as the reference's do across thread counts. And so are runs over several devices: a frame and its tiles are then the same bits.
     if (params.adaptive_max_level > 0 || n_devices > 1) bl_set_reproducible(contexts[dev], 1);
+    // the sweep on every device: a device's share of the frame then holds the rows of all variants, like the frame does
+    if (bl_apply_sweep(contexts[dev], &sweep) != BL_OK) {
+      std::cout << bl_last_error(contexts[dev]);
+      return 1;
+    }
   }
   bl_ctx *ctx = contexts[0];
   const bool simulation = params.model_type == BL_MODEL_SIMULATION;
   const int res = params.camera_resolution;
-  const int n_q = bl_image_num_quantities(ctx);
+  const int n_q = bl_image_num_quantities(ctx);   // rows of one render: those of every variant of a sweep, one after another
+  const int n_variants = bl_num_variants(ctx);
   const int bs = params.adaptive_max_level > 0 ? params.adaptive_block_size : 1;
   const bool want_camera = params.has[BL_P_output_camera] && params.output_camera && params.output_format == BL_OUTPUT_NPZ;
 
@@ -320,7 +327,7 @@ int main(int argc, char *argv[]) {
         cameras.push_back(std::move(root_camera));
         renders.push_back(std::move(root_render));
       } else {
-        const bool pin = level == 0 && num_runs > 1;
+        const bool pin = level == 0 && (num_runs > 1 || n_variants > 1);
         images.emplace_back(ctx, static_cast<size_t>(n_q) * n_rays, pin);
         cameras.emplace_back(ctx, want_camera ? static_cast<size_t>(n_rays) * 4 : 0, pin);
         renders.emplace_back(ctx, static_cast<size_t>(n_render) * 3 * n_rays, pin);
@@ -487,10 +494,21 @@ int main(int argc, char *argv[]) {
       out.level[l].camera = want_camera ? cameras[l].data() : nullptr;
       out.level[l].render = n_render > 0 ? renders[l].data() : nullptr;
     }
-    if (bl_write_output(ctx, nullptr, &out) != BL_OK) {
-      std::cout << bl_last_error(ctx);
-      return 1;
+    double t_write = Now();
+    if (n_variants == 1) {
+      if (bl_write_output(ctx, nullptr, &out) != BL_OK) {
+        std::cout << bl_last_error(ctx);
+        return 1;
+      }
+    } else {
+      // one file of the reference's layout per variant, from the rows where the render left them
+      for (int variant = 0; variant < n_variants; variant++)
+        if (bl_write_output_variant(ctx, nullptr, &out, variant) != BL_OK) {
+          std::cout << bl_last_error(ctx);
+          return 1;
+        }
     }
+    time_write += Now() - t_write;
     have_root = true;
     root_image = std::move(images[0]);   // (kept for the next run)
     root_camera = std::move(cameras[0]);
@@ -500,6 +518,8 @@ int main(int argc, char *argv[]) {
   root_camera.Free();
   root_render.Free();
   bl_stats last_stats{};
+  const int n_models = bl_num_electron_models(contexts[0]), n_units = bl_num_density_units(contexts[0]);
+  const bool triples = bl_num_polarized_variants(contexts[0]) > 0;
   bl_get_stats(contexts[0], &last_stats);   // (of the last root-level... of the last render of the first device: the tier is the context's)
   for (bl_ctx *c : contexts) bl_free(c);
 
@@ -518,5 +538,12 @@ int main(int argc, char *argv[]) {
   std::cout << "blacklight_amd: " << (last_stats.arithmetic == BL_ARITH_TOLERANT ? "tolerant" : "exact") << " arithmetic tier"
             << (last_stats.arithmetic == BL_ARITH_TOLERANT ? (last_stats.composed_maps ? ", composed transfer maps (equal from run to run to rounding)" : ", bit-reproducible") : "")
             << (last_stats.geodesics_reused ? "; geodesics integrated once for the series" : "") << " (BLACKLIGHT_AMD_ARITHMETIC=exact|tolerant)\n";
+  // (and, only with sweep keys in the input file, one line on what each snapshot's single render was written out as)
+  if (sweep.n_rat_low > 0 || sweep.n_rho_cgs > 0) {
+    std::cout << "blacklight_amd: sweep of " << n_variants << " variants per snapshot (";
+    if (triples) std::cout << n_variants << " polarized triples";
+    else std::cout << std::max(1, n_models) << " electron models x " << std::max(1, n_units) << " density units";
+    std::cout << "), one file each; writing outputs: " << time_write << " s\n";
+  }
   return 0;
 }

@@ -6,7 +6,9 @@
 // key=value, unknown keys are fatal, booleans are exactly true/false, angles are given in degrees,
 // numbers are parsed with std::stod / std::stoi / std::stof semantics (leading number, trailing
 // text ignored). Error texts are the reference's.
+#include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -287,7 +289,69 @@ void ReadRender(bl_params *p, const std::string &key, const std::string &val) {
   throw ParseFailure{"Unknown key (render_" + key + ") in input file."};
 }
 
-void SetKeyValue(bl_params *p, const std::string &key, const std::string &val) {
+// sweep_rat_low / sweep_rat_high / sweep_rho_cgs: "a,b,c" (an extension: the reference has no lists). Stricter than the scalar keys:
+// every entry is a whole number text - nothing is left of it after the conversion -, none is empty, at most BL_MAX_SWEEP of them.
+int ReadList(const std::string &key, const std::string &val, bool unit, double *out) {
+  int count = 0;
+  for (size_t at = 0; at <= val.size();) {
+    const size_t comma = std::min(val.find(',', at), val.size());
+    const std::string entry = val.substr(at, comma - at);
+    if (entry.empty()) throw ParseFailure{"Empty entry in list (" + key + ") in input file."};
+    char *end = nullptr;
+    const double x = std::strtod(entry.c_str(), &end);
+    if (end == entry.c_str() || *end != '\0') throw ParseFailure{"Invalid number (" + entry + ") in list (" + key + ") in input file."};
+    if (unit && !(std::isfinite(x) && x > 0.0))
+      throw ParseFailure{"Invalid density unit (" + entry + ") in list (" + key + ") in input file: must be finite and positive."};
+    if (count >= BL_MAX_SWEEP)
+      throw ParseFailure{"Too many entries in list (" + key + ") in input file: at most " + std::to_string(BL_MAX_SWEEP) + " for this build."};
+    out[count++] = x;
+    at = comma + 1;
+  }
+  return count;
+}
+
+// The sweep keys go beside the parameter block (bl_sweep), never into it; false: not a sweep key
+bool SetSweepKey(bl_sweep *s, const std::string &key, const std::string &val) {
+  if (key == "sweep_rat_low") s->n_rat_low = ReadList(key, val, false, s->rat_low);
+  else if (key == "sweep_rat_high") s->n_rat_high = ReadList(key, val, false, s->rat_high);
+  else if (key == "sweep_rho_cgs") s->n_rho_cgs = ReadList(key, val, true, s->rho_cgs);
+  else return false;
+  return true;
+}
+
+bool IsPolarized(const bl_params &p) {
+  return p.model_type == BL_MODEL_SIMULATION && p.image_light && p.has[BL_P_image_polarization] && p.image_polarization;
+}
+
+// What the three lists mean together (include/blacklight_amd.h, bl_sweep_resolve)
+void ResolveSweep(const bl_sweep &s, const bl_params &p, bl_sweep *out, int *polarized) {
+  if (s.n_rat_low < 0 || s.n_rat_high < 0 || s.n_rho_cgs < 0 || s.n_rat_low > BL_MAX_SWEEP || s.n_rat_high > BL_MAX_SWEEP
+      || s.n_rho_cgs > BL_MAX_SWEEP)
+    throw ParseFailure{"Too many entries in a sweep list: at most " + std::to_string(BL_MAX_SWEEP) + " for this build."};
+  if (s.n_rat_low != s.n_rat_high)
+    throw ParseFailure{"sweep_rat_low and sweep_rat_high must have the same number of entries (" + std::to_string(s.n_rat_low) + " and "
+                       + std::to_string(s.n_rat_high) + ") in input file."};
+  const bool pol = IsPolarized(p);
+  if (polarized != nullptr) *polarized = pol ? 1 : 0;
+  bl_sweep r = s;
+  if (pol && (s.n_rat_low > 0 || s.n_rho_cgs > 0)) {
+    const int n_pairs = s.n_rat_low, n_units = s.n_rho_cgs;
+    if (n_pairs > 0 && n_units > 1 && n_units != n_pairs)
+      throw ParseFailure{"sweep_rho_cgs must have one entry or as many as sweep_rat_high (" + std::to_string(n_units) + " and "
+                         + std::to_string(n_pairs) + ") with image_polarization in input file."};
+    const int n = n_pairs > 0 ? n_pairs : n_units;
+    for (int v = 0; v < n; v++) {
+      r.rat_low[v] = n_pairs > 0 ? s.rat_low[v] : p.plasma_rat_low;
+      r.rat_high[v] = n_pairs > 0 ? s.rat_high[v] : p.plasma_rat_high;
+      r.rho_cgs[v] = n_units == 0 ? p.simulation_rho_cgs : s.rho_cgs[n_units == 1 ? 0 : v];
+    }
+    r.n_rat_low = r.n_rat_high = r.n_rho_cgs = n;
+  }
+  if (out != nullptr) *out = r;
+}
+
+void SetKeyValue(bl_params *p, bl_sweep *sweep, const std::string &key, const std::string &val) {
+  if (key.compare(0, 6, "sweep_") == 0 && SetSweepKey(sweep, key, val)) return;
   // Compound keys first
   if (key == "cut_plane_origin") return ReadTriple(val, p, BL_P_cut_plane_origin_x);
   if (key == "cut_plane_normal") return ReadTriple(val, p, BL_P_cut_plane_normal_x);
@@ -335,7 +399,7 @@ void SetKeyValue(bl_params *p, const std::string &key, const std::string &val) {
   throw ParseFailure{"Unknown key (" + key + ") in input file."};
 }
 
-void ParseLine(bl_params *p, std::string line) {
+void ParseLine(bl_params *p, bl_sweep *sweep, std::string line) {
   std::string stripped;
   stripped.reserve(line.size());
   for (unsigned char c : line)
@@ -345,7 +409,7 @@ void ParseLine(bl_params *p, std::string line) {
   if (stripped.empty()) return;
   pos = stripped.find('=');
   if (pos == std::string::npos) throw ParseFailure{"Invalid assignment in input file."};
-  SetKeyValue(p, stripped.substr(0, pos), stripped.substr(pos + 1));
+  SetKeyValue(p, sweep, stripped.substr(0, pos), stripped.substr(pos + 1));
 }
 
 }  // namespace
@@ -358,10 +422,11 @@ void bl_params_clear(bl_params *p) {
 
 size_t bl_params_sizeof(void) { return sizeof(bl_params); }
 
-int bl_params_set_line(bl_params *p, const char *line, char *err, size_t err_len) {
+int bl_params_set_line_sweep(bl_params *p, bl_sweep *sweep, const char *line, char *err, size_t err_len) {
   if (p == nullptr || line == nullptr) return BL_E_ARG;
+  bl_sweep unused = {};   // (no sweep asked for: the keys are accepted and validated all the same)
   try {
-    ParseLine(p, line);
+    ParseLine(p, sweep != nullptr ? sweep : &unused, line);
   } catch (const ParseFailure &failure) {
     SetError(err, err_len, failure.message);
     return BL_E_INPUT;
@@ -369,16 +434,24 @@ int bl_params_set_line(bl_params *p, const char *line, char *err, size_t err_len
   return BL_OK;
 }
 
-int bl_params_read_file(bl_params *p, const char *path, int *num_runs, char *err, size_t err_len) {
+int bl_params_set_line(bl_params *p, const char *line, char *err, size_t err_len) {
+  return bl_params_set_line_sweep(p, nullptr, line, err, err_len);
+}
+
+int bl_params_read_file_sweep(bl_params *p, bl_sweep *sweep, const char *path, int *num_runs, char *err, size_t err_len) {
   if (p == nullptr || path == nullptr) return BL_E_ARG;
   bl_params_clear(p);
+  bl_sweep local = {};
+  if (sweep == nullptr) sweep = &local;
+  *sweep = bl_sweep{};
   std::ifstream stream(path);
   if (!stream.is_open()) {
     SetError(err, err_len, "Could not open input file.");
     return BL_E_INPUT;
   }
   try {
-    for (std::string line; std::getline(stream, line);) ParseLine(p, line);
+    for (std::string line; std::getline(stream, line);) ParseLine(p, sweep, line);
+    ResolveSweep(*sweep, *p, nullptr, nullptr);   // the lists against each other, once the whole file is known
   } catch (const ParseFailure &failure) {
     SetError(err, err_len, failure.message);
     return BL_E_INPUT;
@@ -407,6 +480,21 @@ int bl_params_read_file(bl_params *p, const char *path, int *num_runs, char *err
     }
   }
   if (num_runs != nullptr) *num_runs = runs;
+  return BL_OK;
+}
+
+int bl_params_read_file(bl_params *p, const char *path, int *num_runs, char *err, size_t err_len) {
+  return bl_params_read_file_sweep(p, nullptr, path, num_runs, err, err_len);
+}
+
+int bl_sweep_resolve(const bl_sweep *sweep, const bl_params *p, bl_sweep *resolved, int *polarized, char *err, size_t err_len) {
+  if (sweep == nullptr || p == nullptr) return BL_E_ARG;
+  try {
+    ResolveSweep(*sweep, *p, resolved, polarized);
+  } catch (const ParseFailure &failure) {
+    SetError(err, err_len, failure.message);
+    return BL_E_INPUT;
+  }
   return BL_OK;
 }
 

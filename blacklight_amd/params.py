@@ -22,6 +22,7 @@ class Params:
         L = _capi.lib()
         self._buf = C.create_string_buffer(L.bl_params_sizeof())
         L.bl_params_clear(self._buf)
+        self._sweep = _capi.Sweep()   # the sweep_* keys: lists beside the block (bl_sweep), never in it
         self.num_runs = 1
 
     @property
@@ -34,7 +35,7 @@ class Params:
         self = cls()
         err = C.create_string_buffer(1024)
         runs = C.c_int(1)
-        rc = _capi.lib().bl_params_read_file(self._buf, str(path).encode(), C.byref(runs), err, len(err))
+        rc = _capi.lib().bl_params_read_file_sweep(self._buf, C.byref(self._sweep), str(path).encode(), C.byref(runs), err, len(err))
         if rc != 0:
             raise _capi.BlacklightError(rc, err.value.decode())
         self.num_runs = runs.value
@@ -56,7 +57,7 @@ class Params:
 
     def set_line(self, line):
         err = C.create_string_buffer(1024)
-        rc = _capi.lib().bl_params_set_line(self._buf, line.encode(), err, len(err))
+        rc = _capi.lib().bl_params_set_line_sweep(self._buf, C.byref(self._sweep), line.encode(), err, len(err))
         if rc != 0:
             raise _capi.BlacklightError(rc, err.value.decode())
 
@@ -71,8 +72,43 @@ class Params:
     def copy(self):
         other = Params()
         C.memmove(other._buf, self._buf, len(self._buf))
+        C.memmove(C.byref(other._sweep), C.byref(self._sweep), C.sizeof(_capi.Sweep))
         other.num_runs = self.num_runs
         return other
+
+    # ------------------------------------------------------------------ sweeps (sweep_rat_low, sweep_rat_high, sweep_rho_cgs)
+    @property
+    def sweep(self):
+        """The bl_sweep filled by the sweep_* keys (what Context applies: bl_apply_sweep)."""
+        return self._sweep
+
+    @property
+    def sweep_rat_low(self):
+        return [float(x) for x in self._sweep.rat_low[:self._sweep.n_rat_low]]
+
+    @property
+    def sweep_rat_high(self):
+        return [float(x) for x in self._sweep.rat_high[:self._sweep.n_rat_high]]
+
+    @property
+    def sweep_rho_cgs(self):
+        return [float(x) for x in self._sweep.rho_cgs[:self._sweep.n_rho_cgs]]
+
+    @property
+    def has_sweep(self):
+        return self._sweep.n_rat_low > 0 or self._sweep.n_rat_high > 0 or self._sweep.n_rho_cgs > 0
+
+    def resolved_sweep(self):
+        """The lists as the setters receive them (bl_sweep_resolve): (polarized, rat_low, rat_high, rho_cgs). A polarized block's
+        three lists have the number of triples; raises BlacklightError where the lists do not fit each other."""
+        out = _capi.Sweep()
+        polarized = C.c_int(0)
+        err = C.create_string_buffer(1024)
+        rc = _capi.lib().bl_sweep_resolve(C.byref(self._sweep), self.ptr, C.byref(out), C.byref(polarized), err, len(err))
+        if rc != 0:
+            raise _capi.BlacklightError(rc, err.value.decode())
+        return (bool(polarized.value), [float(x) for x in out.rat_low[:out.n_rat_low]], [float(x) for x in out.rat_high[:out.n_rat_high]],
+                [float(x) for x in out.rho_cgs[:out.n_rho_cgs]])
 
     def has(self, key):
         present = C.c_int(0)

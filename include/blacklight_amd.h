@@ -174,6 +174,34 @@ BL_API int bl_params_read_file(bl_params *p, const char *path, int *num_runs, ch
 BL_API int bl_params_get(const bl_params *p, const char *key, double *value, int *present);
 BL_API int bl_params_get_string(const bl_params *p, const char *key, char *out, size_t out_len);
 
+/* ------------------------------------------------------------------ sweeps written in the .input file
+ * Three keys the reference does not have; a file without them parses exactly as before, and they never enter bl_params:
+ *     sweep_rat_low  = 1, 1, 1          (R_low, R_high) pairs: two lists of equal length
+ *     sweep_rat_high = 10, 40, 160
+ *     sweep_rho_cgs  = 1e-16, 2e-16     density units (simulation_rho_cgs values), each finite and > 0
+ * At most BL_MAX_SWEEP entries per list; an entry is a whole number text ("1e-16", not "1e-16g"), none is empty.
+ * image_polarization = false: the pairs are electron models (bl_set_electron_models), the units density units
+ *   (bl_set_density_units); the image is their product, model-major. Either list may be absent: the block's own value.
+ * image_polarization = true: (R_low, R_high, unit) triples (bl_set_polarized_variants). sweep_rho_cgs has the pairs' length, or
+ *   one entry (every pair at that unit), or is absent (every pair at the block's simulation_rho_cgs); units without pairs: the
+ *   block's pair at each unit.
+ * bl_params_set_line / bl_params_read_file accept and validate the keys and drop their values; the two calls below keep them.
+ * n_* = 0: key absent. Errors (BL_E_INPUT, "Error: ...\n"): an empty entry, a text that is not a number, a unit that is not finite
+ * and > 0, more than BL_MAX_SWEEP entries - when the line is read; lists whose lengths do not fit each other - at the end of
+ * bl_params_read_file*, in bl_sweep_resolve and in bl_apply_sweep. What the setters refuse (formula mode, slow light, code_kappa
+ * for pairs, adaptive runs, renderings a variant enters, a ratio that is not finite) is refused by them, in their words. */
+#define BL_MAX_SWEEP 16
+typedef struct bl_sweep {
+  int32_t n_rat_low, n_rat_high, n_rho_cgs;
+  int32_t reserved;
+  double rat_low[BL_MAX_SWEEP], rat_high[BL_MAX_SWEEP], rho_cgs[BL_MAX_SWEEP];
+} bl_sweep;
+BL_API int bl_params_set_line_sweep(bl_params *p, bl_sweep *sweep, const char *line, char *err, size_t err_len);
+BL_API int bl_params_read_file_sweep(bl_params *p, bl_sweep *sweep, const char *path, int *num_runs, char *err, size_t err_len);
+/* The lists as the setters will receive them. Unpolarized block: *resolved = *sweep. Polarized block (*polarized = 1) with any
+ * list given: all three lists of *resolved have the number of triples, filled by the rule above. resolved, polarized may be NULL. */
+BL_API int bl_sweep_resolve(const bl_sweep *sweep, const bl_params *p, bl_sweep *resolved, int *polarized, char *err, size_t err_len);
+
 /* ------------------------------------------------------------------ grid view
  * What RadiationIntegrator::ObtainGridData() takes from SimulationReader
  * (simulation_sampling.cpp:26-95). All pointers are host pointers borrowed for the duration of
@@ -411,6 +439,13 @@ BL_API int bl_num_density_units(const bl_ctx *ctx);   /* 0 = unset: the paramete
 #define BL_MAX_POLARIZED_VARIANTS 16
 BL_API int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs);
 BL_API int bl_num_polarized_variants(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own pair and unit; -1: no context */
+/* The sweep of a .input file onto a context: bl_sweep_resolve against the context's parameters, then bl_set_polarized_variants
+ * (polarized) or bl_set_electron_models and / or bl_set_density_units - one rule for the command-line driver, a bound reference
+ * main() and Python. An empty sweep makes no call (what the context holds stays). On failure (bl_last_error: the resolver's text or
+ * the refusing setter's) the context holds no model or unit the call brought. */
+BL_API int bl_apply_sweep(bl_ctx *ctx, const bl_sweep *sweep);
+/* Images one bl_render produces: max(1, electron models) * max(1, density units) * max(1, polarized variants); -1: no context. */
+BL_API int bl_num_variants(const bl_ctx *ctx);
 /* Number of false-colour renderings bl_render produces (render_num_images; 0 in formula mode). */
 BL_API int bl_render_num_images(const bl_ctx *ctx);
 BL_API int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out);
@@ -569,6 +604,25 @@ typedef struct bl_output_desc {
   int32_t snapshot;            /* run index, for output_file with {Nd} when simulation_multiple */
 } bl_output_desc;
 BL_API int bl_write_output(bl_ctx *ctx, const char *path_override, const bl_output_desc *d);
+/* One variant of a sweep as a file of the reference's layout. d->level[0].image holds all V = bl_num_variants(ctx) images as
+ * bl_render wrote them (V * n_q rows); `variant` counts in the image's own order: m * U + u for models x units, v for polarized
+ * triples (BL_E_ARG outside 0 .. V - 1, and for adaptive levels, which a sweep cannot have). The file is what bl_write_output writes
+ * from rows variant * n_q ... (variant + 1) * n_q - 1 in a context with that variant's plasma_rat_low, plasma_rat_high and
+ * simulation_rho_cgs in its parameter block, byte for byte in all three formats, ZIP64 rules included: NO record of the reference's
+ * files carries one of those three values (mass_msun, width, frequency, adaptive_*, positions / directions, the image rows and
+ * renderings are all there is), so the files of a sweep differ in their image rows and nothing else; camera records and renderings
+ * are the render's single copies, in every file. Rows are written from where the caller holds them. V = 1: variant must be 0 and
+ * the call is bl_write_output. Works on a BL_DEVICE_NONE context.
+ * Name: path_override if given, else bl_variant_output_path. */
+BL_API int bl_write_output_variant(bl_ctx *ctx, const char *path_override, const bl_output_desc *d, int variant);
+/* The name bl_write_output_variant gives the file of run `snapshot` and `variant`: output_file - with the file number where
+ * bl_write_output formats one (simulation_multiple) - and, when V >= 2, a tag in front of the extension (the last '.' of the last path
+ * component; appended where there is none):
+ *     .mMMuUU   electron model MM (two digits, from 00) at density unit UU; both always present, 00 for a list that is not set
+ *     .vVV      polarized triple VV
+ * image.npz -> image.m00u00.npz, image.m00u01.npz, ... image.m02u01.npz: names sort in variant order. V = 1: no tag.
+ * BL_E_ARG: variant outside 0 .. V - 1, or buf too short; BL_E_MISSING / BL_E_INPUT as bl_write_output. */
+BL_API int bl_variant_output_path(bl_ctx *ctx, int snapshot, int variant, char *buf, size_t len);
 
 /* Library self-description: "gfx950;hip" etc. Lets a loader verify the HIP path is the one built. */
 BL_API const char *bl_build_info(void);
