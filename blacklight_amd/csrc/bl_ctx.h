@@ -94,6 +94,7 @@ struct DeviceBuffer {
     return *this;
   }
   ~DeviceBuffer() { Free(); }
+  uint64_t Bytes() const { return count * sizeof(T); }
   void Free() {
     if (ptr != nullptr) (void)hipFree(ptr);
     ptr = nullptr;
@@ -240,21 +241,29 @@ struct bl_ctx {
     DeviceBuffer<double> d_tau_inc;                // tolerant tier with an optical-depth image: alpha x length per sample and frequency
     DeviceBuffer<unsigned long long> d_xcd_state;  // trace order per XCD: queue heads, list lengths, cursors (BlTraceArgs::xcd_state)
     DeviceBuffer<unsigned int> d_xcd_lists;        // ... the record lists, BL_XCD_QUEUES of them
+    // Every buffer of the set, once: what Bytes() and Free() fold over (a new buffer is declared above and named here)
+    template <typename Slot, typename F>
+    static void ForEach(Slot &s, F &&f) {
+      f(s.d_records_hot); f(s.d_records_cold); f(s.d_located); f(s.d_located_tag); f(s.d_transfer); f(s.d_composed); f(s.d_parked); f(s.d_counters);
+      f(s.d_aux); f(s.d_sample_t); f(s.d_slow_frac); f(s.d_pol_samples); f(s.d_pol_matrix); f(s.d_freq_inputs); f(s.d_pol_coeffs); f(s.d_pol_variant_coeffs);
+      f(s.d_anchors); f(s.d_coef_inputs); f(s.d_have_flags); f(s.d_redo); f(s.d_tau_inc); f(s.d_xcd_state); f(s.d_xcd_lists);
+    }
     uint64_t Bytes() const {
-      return d_records_hot.count * sizeof(BlSampleHot) + d_records_cold.count * sizeof(BlSampleCold) + d_located.count * sizeof(BlLocated)
-          + d_located_tag.count * sizeof(unsigned long long) + (d_transfer.count + d_composed.count) * sizeof(double2) + d_parked.count * sizeof(double) + d_aux.count * sizeof(BlAuxSample)
-          + (d_sample_t.count + d_slow_frac.count + d_pol_matrix.count + d_tau_inc.count) * sizeof(double) + d_pol_samples.count * sizeof(BlPolSample)
-          + d_freq_inputs.count * sizeof(BlFreqInputs) + (d_pol_coeffs.count + d_pol_variant_coeffs.count) * sizeof(double2) + d_anchors.count * sizeof(unsigned int)
-          + d_coef_inputs.count * sizeof(BlCoefInputs) + d_redo.count * sizeof(unsigned long long) + d_have_flags.count
-          + d_xcd_state.count * sizeof(unsigned long long) + d_xcd_lists.count * sizeof(unsigned int);
+      uint64_t bytes = 0;
+      ForEach(*this, [&bytes](const auto &buffer) { bytes += buffer.Bytes(); });
+      return bytes - d_counters.Bytes();   // (the counters never were in this sum, which enters the scratch budget - PlanScratch - and so the capacities)
     }
-    void Free() {
-      d_have_flags.Free(); d_redo.Free(); d_tau_inc.Free(); d_aux.Free(); d_sample_t.Free(); d_slow_frac.Free(); d_pol_samples.Free(); d_pol_matrix.Free(); d_freq_inputs.Free(); d_pol_coeffs.Free(); d_pol_variant_coeffs.Free(); d_coef_inputs.Free(); d_anchors.Free();
-      d_records_hot.Free(); d_records_cold.Free(); d_located.Free(); d_located_tag.Free(); d_transfer.Free(); d_composed.Free(); d_parked.Free(); d_counters.Free();
-      d_xcd_state.Free(); d_xcd_lists.Free();
-    }
+    void Free() { ForEach(*this, [](auto &buffer) { buffer.Free(); }); }
   };
   ChunkSlot slot[2];
+  // per ray of a bl_render call (indexed by traversal position; a chunk's kernels get pointers to its first ray): the arrays set aside with the resident records
+  struct RayArrays {
+    DeviceBuffer<double> kt, factor;
+    DeviceBuffer<int> sample_num, skipped, rows;
+    DeviceBuffer<unsigned char> flags;
+    DeviceBuffer<long long> out_index, offset;
+    uint64_t Bytes() const { return kt.Bytes() + factor.Bytes() + sample_num.Bytes() + skipped.Bytes() + rows.Bytes() + flags.Bytes() + out_index.Bytes() + offset.Bytes(); }
+  };
   // bl_set_geodesic_reuse: the root level's geodesics as its last render left them (in one chunk, or in the kept layout below). The
   // buffers are the ones scratch set 0 and the
   // per-ray arrays below point at (`parked` false) or, while a render of another level works there, set aside in `store`
@@ -301,34 +310,16 @@ struct bl_ctx {
       DeviceBuffer<BlLocated> located;
       DeviceBuffer<unsigned long long> located_tag;
       DeviceBuffer<unsigned int> anchors;
-      DeviceBuffer<double> ray_kt, ray_factor;
-      DeviceBuffer<int> ray_sample_num, ray_skipped, ray_rows;
-      DeviceBuffer<unsigned char> ray_flags;
-      DeviceBuffer<long long> ray_out_index, ray_offset;
+      RayArrays rays;
       ChunkSlot slot;   // kept layout: the whole of scratch set 0 is set aside (its shading arrays hold part of the store)
-      uint64_t Bytes() const {
-        return slot.Bytes() + records_hot.count * sizeof(BlSampleHot) + records_cold.count * sizeof(BlSampleCold) + sample_t.count * sizeof(double) + located.count * sizeof(BlLocated)
-            + located_tag.count * sizeof(unsigned long long) + anchors.count * sizeof(unsigned int) + (ray_kt.count + ray_factor.count) * sizeof(double)
-            + (ray_sample_num.count + ray_skipped.count + ray_rows.count) * sizeof(int) + ray_flags.count + (ray_out_index.count + ray_offset.count) * sizeof(long long);
-      }
-      void Free() {
-        records_hot.Free(); records_cold.Free(); sample_t.Free(); located.Free(); located_tag.Free(); anchors.Free(); ray_kt.Free(); ray_factor.Free();
-        ray_sample_num.Free(); ray_skipped.Free(); ray_rows.Free(); ray_flags.Free(); ray_out_index.Free(); ray_offset.Free(); slot.Free();
-      }
+      void Free() { *this = Buffers{}; }   // (every buffer's move assignment gives its memory back)
     } store;
   } resident;
   int geodesic_reuse = 1;             // bl_set_geodesic_reuse()
   unsigned long long grid_geometry = 0;   // hash of the grid's geometry as bl_set_grid last saw it (block table, coordinates, look-up tables)
-  // per ray of a bl_render call (indexed by traversal position; a chunk's kernels get pointers to its first ray)
-  DeviceBuffer<double> d_ray_kt, d_ray_factor;
-  DeviceBuffer<double> d_ray_start;              // BL_RAY_START_FIELDS rows: start state of every ray (bl_ray_init_kernel -> geodesic kernel)
-  DeviceBuffer<int> d_ray_sample_num, d_ray_skipped, d_ray_rows;
-  DeviceBuffer<unsigned char> d_ray_flags;
-  DeviceBuffer<long long> d_ray_out_index, d_ray_offset;
-  uint64_t RayBytes() const {
-    return (d_ray_kt.count + d_ray_factor.count + d_ray_start.count) * sizeof(double) + (d_ray_sample_num.count + d_ray_skipped.count + d_ray_rows.count) * sizeof(int) + d_ray_flags.count
-        + (d_ray_out_index.count + d_ray_offset.count) * sizeof(long long);
-  }
+  RayArrays rays;
+  DeviceBuffer<double> d_ray_start;              // BL_RAY_START_FIELDS rows: start state of every ray (bl_ray_init_kernel -> geodesic kernel); never set aside
+  uint64_t RayBytes() const { return rays.Bytes() + d_ray_start.Bytes(); }
   DeviceBuffer<double> d_freq;
   DeviceBuffer<int> d_pixel_map, d_block_locs, d_tile_order;
   int tile_order_res = 0;

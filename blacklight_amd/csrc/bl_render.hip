@@ -148,6 +148,20 @@ struct CheckpointSave {
 struct SplitIncomplete {};   // BL_TAIL_SPLIT: the chunk ended before its last ray (RunChunks)
 struct ReuseImpossible {};   // scratch for a render over the resident records could not be allocated beside them (EnsureScratch)
 
+// Which of a scratch set's optional arrays (bl_ctx::ChunkSlot) a render uses: decided in one place (UsedArrays), read by the plan, the
+// kept layout, the allocation and the binding. The first two rows: arrays with a fixed number of entries per record (ForEachRecordArray).
+struct ArrayUse {
+  bool located = false, freq_inputs = false, transfer = false, composed = false, tau_inc = false, aux = false, slow_frac = false;
+  bool pol = false, pol_matrix = false, pol_coeffs = false, pol_variant_coeffs = false, coef_inputs = false, have_flags = false, anchors = false;
+  bool sample_t = false, redo = false, xcd = false, parked = false;
+  unsigned int Mask() const {   // (BLACKLIGHT_AMD_DEBUG_COUNTERS: bit 0 = located ... bit 17 = parked)
+    unsigned int mask = 0, bit = 0;
+    for (bool flag : {located, freq_inputs, transfer, composed, tau_inc, aux, slow_frac, pol, pol_matrix, pol_coeffs, pol_variant_coeffs, coef_inputs,
+                      have_flags, anchors, sample_t, redo, xcd, parked}) mask |= (flag ? 1u : 0u) << bit++;
+    return mask;
+  }
+};
+
 // Everything one bl_render call decides before its first kernel, and what its chunks add up to
 struct RenderJob {
   bl_ctx *ctx = nullptr;
@@ -209,6 +223,7 @@ struct RenderJob {
   long long n_rays = 0, level_pixels = 0;
   size_t redo_capacity = 0;
   // scratch
+  ArrayUse use;
   uint64_t bytes_per_record = 0;
   size_t record_capacity = 0;
   long long record_gate = 0;
@@ -326,6 +341,13 @@ void BindVariant(RenderJob &job, int v) {
   job.xa.image = job.image + static_cast<size_t>(v) * job.n_q_model * static_cast<size_t>(job.n_rays);
 }
 
+bool GeometricCut(const bl_params &p) {   // an optional geometric cut is set
+  return p.cut_omit_near || p.cut_omit_far || p.cut_omit_in >= 0.0 || p.cut_omit_out >= 0.0 || p.cut_midplane_theta != 0.0 || p.cut_midplane_z != 0.0 || p.cut_plane;
+}
+bool PerSampleRows(const BlAuxImages &rows) {   // an image row made of every sample's auxiliary record
+  return rows.image_time || rows.image_length || rows.image_lambda || rows.image_emission || rows.image_lambda_ave || rows.image_emission_ave || rows.image_tau_int || rows.image_crossings;
+}
+
 // ---- plan: validation of the call, the path it takes
 void PlanJob(RenderJob &job) {
   bl_ctx *ctx = job.ctx;
@@ -399,8 +421,7 @@ void PlanJob(RenderJob &job) {
   // (an optical-depth image as the only auxiliary row is the plain path plus one sum per ray: not an auxiliary run below)
   const BlAuxImages &rows = ctx->aux_images;
   const bool tau_only = job.aux && !ctx->polarized && p.image_light && rows.image_tau && ctx->render_num_images == 0 && !job.geo_load && !job.geo_save
-      && !(rows.image_time || rows.image_length || rows.image_lambda || rows.image_emission || rows.image_lambda_ave || rows.image_emission_ave
-           || rows.image_tau_int || rows.image_crossings);
+      && !PerSampleRows(rows);
   // (inter-block interpolation and slow light: bl_shade_fast_kernel behind their locate kernels, primitives by the exact tier's sampling)
   job.fast = ctx->arithmetic == BL_ARITH_TOLERANT && job.simulation && (!job.aux || tau_only) && !ctx->polarized && !(job.slow && job.block_interp)
       && p.plasma_kappa_frac == 0.0 && p.plasma_model != BL_PLASMA_CODE_KAPPA
@@ -412,7 +433,7 @@ void PlanJob(RenderJob &job) {
   }
   // ... formula mode has a fast kernel of its own (plain images, no optional geometric cut)
   job.fast_formula = ctx->arithmetic == BL_ARITH_TOLERANT && !job.simulation && !job.aux
-      && !(p.cut_omit_near || p.cut_omit_far || p.cut_omit_in >= 0.0 || p.cut_omit_out >= 0.0 || p.cut_midplane_theta != 0.0 || p.cut_midplane_z != 0.0 || p.cut_plane);
+      && !GeometricCut(p);
   // ... and the per-frequency coefficient kernel of polarized runs (frame, transport and coupling stay exact)
   job.tolerant_polarized = ctx->arithmetic == BL_ARITH_TOLERANT && ctx->polarized;
   // ... and transport matrices (bl_transport_matrix_kernel) instead of the ray-sequential tensor transport, in curved spacetimes
@@ -453,7 +474,7 @@ void PlanJob(RenderJob &job) {
       : !job.freq_split && !records_every_sample && !job.skip_shell && bl_fused2_refined_applicable(&ctx->grid_dev, job.n_nu, job.n_rays) != 0;
   job.fused2 = job.fast && !job.tau_row && !job.slow && fused2_grid && !ctx->grid_dev.fmks && p.simulation_interp && p.plasma_power_frac == 0.0
       && p.simulation_coord == BL_COORD_SKS   // (its locate step is the spherical one: Cartesian grids go through the locate kernel)
-      && !(p.cut_omit_near || p.cut_omit_far || p.cut_omit_in >= 0.0 || p.cut_omit_out >= 0.0 || p.cut_midplane_theta != 0.0 || p.cut_midplane_z != 0.0 || p.cut_plane)
+      && !GeometricCut(p)
       && !job.sample_save && !(ctx->switches & (BL_SWITCH_NO_FUSED_LOCATE | BL_SWITCH_SPLIT_RECORDS))   // (a sample checkpoint is made of the located samples)
       && !job.geo_load && !job.geo_save;  // (interleaved records whose momenta are not renormalised yet)
   // The exact tier's plain image at one frequency over such a grid: the locate step inside bl_shade_exact2_kernel (bit-identical
@@ -461,7 +482,7 @@ void PlanJob(RenderJob &job) {
   job.exact_fused = !job.fast && job.simulation && !job.aux && !ctx->polarized && !job.slow && !job.block_interp && job.n_nu == 1
       && p.plasma_kappa_frac == 0.0 && p.plasma_power_frac == 0.0 && p.plasma_model != BL_PLASMA_CODE_KAPPA && !p.ray_flat
       && ctx->plasma_thermal_frac != 0.0 && !ctx->grid_dev.fmks && p.simulation_interp && p.simulation_coord == BL_COORD_SKS
-      && !(p.cut_omit_near || p.cut_omit_far || p.cut_omit_in >= 0.0 || p.cut_omit_out >= 0.0 || p.cut_midplane_theta != 0.0 || p.cut_midplane_z != 0.0 || p.cut_plane)
+      && !GeometricCut(p)
       && !job.geo_load && !job.geo_save && !job.sample_save && !(ctx->switches & (BL_SWITCH_NO_FUSED_LOCATE | BL_SWITCH_SPLIT_RECORDS))
       && (ctx->grid_dev.n_blocks == 0 ? bl_fused2_applicable(&ctx->grid_dev, job.n_nu, job.n_rays) != 0 : bl_polarized2_refined_applicable(&ctx->grid_dev, job.n_rays) != 0);
   // Polarized runs over such a grid: the frame-and-inputs kernel with the locate step inside (bit-identical to bl_locate_plain_kernel +
@@ -469,7 +490,7 @@ void PlanJob(RenderJob &job) {
   // (... or a mesh with refinement whose tables the tolerant tier's fused kernel takes: the polarized kernel's locate step knows them too)
   job.pol_fused = ctx->polarized && job.simulation && !job.slow && !job.block_interp && p.plasma_model != BL_PLASMA_CODE_KAPPA && !p.ray_flat
       && !ctx->grid_dev.fmks && p.simulation_interp && p.simulation_coord == BL_COORD_SKS
-      && !(p.cut_omit_near || p.cut_omit_far || p.cut_omit_in >= 0.0 || p.cut_omit_out >= 0.0 || p.cut_midplane_theta != 0.0 || p.cut_midplane_z != 0.0 || p.cut_plane)
+      && !GeometricCut(p)
       && !job.geo_load && !job.geo_save && !job.sample_save && !job.need_time && !(ctx->switches & (BL_SWITCH_NO_FUSED_LOCATE | BL_SWITCH_SPLIT_RECORDS))
       && (ctx->grid_dev.n_blocks == 0 ? bl_fused2_applicable(&ctx->grid_dev, 1, job.n_rays) != 0 : bl_polarized2_refined_applicable(&ctx->grid_dev, job.n_rays) != 0);
   job.interleaved = (job.fused2 || job.exact_fused || job.pol_fused || !job.simulation) && !job.geo_load && !job.geo_save && !job.sample_save && !(ctx->switches & BL_SWITCH_SPLIT_RECORDS);
@@ -509,9 +530,7 @@ void PlanJob(RenderJob &job) {
     for (int n_f = 0; n_f < p.render_num_features[n_i]; n_f++)
       if (p.render_type[n_i][n_f] == BL_RENDER_FILL) fill_present = true;
   job.fill_present = fill_present;
-  const BlAuxImages &AI = ctx->aux_images;
-  job.rows_only = ctx->polarized && ctx->render_num_images == 0 && !fill_present && !(AI.image_time || AI.image_length || AI.image_lambda
-      || AI.image_emission || AI.image_lambda_ave || AI.image_emission_ave || AI.image_tau_int || AI.image_crossings);
+  job.rows_only = ctx->polarized && ctx->render_num_images == 0 && !fill_present && !PerSampleRows(rows);
   // configuration 4's case: no BlCoefInputs through HBM, no bl_polarized_coefficients_kernel launch (bl_shade_fused.hip: kCoefficients)
   job.pol_coefficients_inside = job.pol_fused && job.n_nu == 1 && job.rows_only && p.plasma_power_frac == 0.0 && p.plasma_kappa_frac == 0.0 && ctx->st.bh_a == 0.0;
   // Polarized variants in one pass: where no decision differs between them - a rho, n_e, p_gas or B cut only with one unit, a Theta_e
@@ -610,14 +629,7 @@ void SwapResidentBuffers(bl_ctx *ctx) {
     std::swap(st.located_tag, sl.d_located_tag);
     std::swap(st.anchors, sl.d_anchors);
   }
-  std::swap(st.ray_kt, ctx->d_ray_kt);
-  std::swap(st.ray_factor, ctx->d_ray_factor);
-  std::swap(st.ray_sample_num, ctx->d_ray_sample_num);
-  std::swap(st.ray_skipped, ctx->d_ray_skipped);
-  std::swap(st.ray_rows, ctx->d_ray_rows);
-  std::swap(st.ray_flags, ctx->d_ray_flags);
-  std::swap(st.ray_out_index, ctx->d_ray_out_index);
-  std::swap(st.ray_offset, ctx->d_ray_offset);
+  std::swap(st.rays, ctx->rays);
   ctx->resident.parked = !ctx->resident.parked;
 }
 
@@ -673,6 +685,9 @@ void KeepResident(RenderJob &job) {
   bl_ctx::ResidentGeodesics &res = ctx->resident;
   const bool located_here = job.simulation && !job.locate_inside && !job.slow;
   const unsigned long long *hc = ctx->host_counters;   // scratch set 0's, as CollectChunk read them
+  if (ctx->debug_counters)
+    std::fprintf(stderr, "scratch plan: bytes_per_record %llu, record_capacity %zu, record_gate %lld, geo_grid %d, n_slots %d, arrays 0x%05x\n", static_cast<unsigned long long>(job.bytes_per_record),
+                 job.record_capacity, job.record_gate, job.geo_grid, job.n_slots, job.use.Mask());
   if (job.keepable && !job.reuse) {
     res.valid = false;
     res.super_tiles = job.super_tiles;
@@ -729,6 +744,53 @@ void KeepResident(RenderJob &job) {
   for (int c = BL_CNT_COUNT; c < BL_CNT_COUNT + 12; c++) res.counters[c] = 0ull;   // the transfer kernel's statistics, debug counters
 }
 
+// ---- which arrays: decided where PlanScratch begins and again after whatever it and bl_render still drop
+ArrayUse UsedArrays(const RenderJob &job) {
+  ArrayUse use;
+  const bool polarized = use.pol = job.ctx->polarized;
+  use.located = job.simulation && !job.locate_inside;   // (locate step inside the coefficient kernel: no located samples in HBM)
+  use.freq_inputs = job.freq_split;                     // ... instead of the transfer records
+  use.transfer = !job.freq_split && !polarized;         // (polarized runs: the eight coefficients of a sample side by side, d_pol_coeffs)
+  use.composed = job.composed;
+  use.tau_inc = job.tau_row;
+  use.aux = job.aux && !job.rows_only;                  // (rows_only: nobody writes or reads the 96-byte records)
+  use.slow_frac = job.slow;
+  use.pol_matrix = polarized && job.matrix_transport;
+  use.pol_coeffs = polarized && !job.pol_one_pass;
+  use.pol_variant_coeffs = polarized && job.pol_one_pass;   // polarized variants in one pass: every variant's coefficients, instead of d_pol_coeffs
+  use.coef_inputs = polarized || job.coef_split;
+  use.have_flags = polarized && job.pol_coefficients_inside;
+  use.anchors = job.block_interp && !job.locate_inside;   // (locate step inside: the exact pass keeps a sample's anchors in registers)
+  use.sample_t = job.need_time;
+  use.redo = job.fast || job.fast_formula || polarized;   // (polarized runs: the samples whose frame bl_polarized_frame_kernel builds)
+  use.xcd = job.xcd_order;
+  use.parked = job.park || job.split_long;
+  return use;
+}
+
+// The arrays of scratch set `sl` with a fixed number of entries per sample record that the render uses, in the order the kept layout lists
+// their tails: visit(buffer, entries per record, whether its tail may hold part of the kept layout's store - not d_pol_variant_coeffs, so that
+// a render over resident records may have more variants than the one that integrated them). The records and d_sample_t are the callers'.
+template <typename Slot, typename Visitor>
+void ForEachRecordArray(const RenderJob &job, Slot &sl, Visitor &&visit) {
+  const ArrayUse &use = job.use;
+  const size_t n_nu = static_cast<size_t>(job.n_nu);
+  if (use.located) visit(sl.d_located, 1, true), visit(sl.d_located_tag, 1, true);
+  if (use.freq_inputs) visit(sl.d_freq_inputs, 1, true);
+  if (use.transfer) visit(sl.d_transfer, n_nu, true);
+  if (use.composed) visit(sl.d_composed, 1, true);
+  if (use.tau_inc) visit(sl.d_tau_inc, n_nu, true);
+  if (use.aux) visit(sl.d_aux, 1, true);
+  if (use.slow_frac) visit(sl.d_slow_frac, 1, true);
+  if (use.pol) visit(sl.d_pol_samples, 1, true);
+  if (use.pol_matrix) visit(sl.d_pol_matrix, BL_POL_MATRIX_DOUBLES, true);
+  if (use.pol_coeffs) visit(sl.d_pol_coeffs, n_nu * 4, true);
+  if (use.pol_variant_coeffs) visit(sl.d_pol_variant_coeffs, n_nu * 4 * static_cast<size_t>(job.n_pol), false);
+  if (use.coef_inputs) visit(sl.d_coef_inputs, 1, true);
+  if (use.have_flags) visit(sl.d_have_flags, 1, true);
+  if (use.anchors) visit(sl.d_anchors, 8, true);
+}
+
 // ---- kept layout (DecideReuse: the render after one of this camera that took several chunks). Scratch set 0 as the earlier render
 // allocated it is re-partitioned - nothing is freed or allocated: its shading arrays take one chunk's `record_capacity` entries, and the
 // store that takes every chunk's records is a list of segments, the record arrays and the tails of the shading arrays beyond those
@@ -749,7 +811,6 @@ bool PlanKeptLayout(RenderJob &job, long long max_grid, long long quad_waves, in
   using Segment = bl_ctx::ResidentGeodesics::Segment;
   bl_ctx *ctx = job.ctx;
   bl_ctx::ChunkSlot &sl = ctx->slot[0];
-  const size_t n_nu = static_cast<size_t>(job.n_nu);
   const uint64_t record_bytes = sizeof(BlSampleHot) + sizeof(BlSampleCold) + (job.need_time ? sizeof(double) : 0);
   // the record arrays as they are (segment 0)
   Segment first;
@@ -758,34 +819,18 @@ bool PlanKeptLayout(RenderJob &job, long long max_grid, long long quad_waves, in
   first.sample_t = job.need_time ? sl.d_sample_t.ptr : nullptr;
   first.capacity = job.interleaved ? sl.d_records_hot.count / 2 : std::min(sl.d_records_hot.count, sl.d_records_cold.count);
   if (job.need_time) first.capacity = std::min(first.capacity, sl.d_sample_t.count);
-  // the shading arrays this render uses (EnsureScratchOnce): where they start, their bytes, their bytes per record
+  // the shading arrays this render uses whose tails may hold the store: where they start, their bytes, their bytes per record
   struct Part {
     unsigned char *base;
     uint64_t bytes, per_record;
   };
   std::vector<Part> parts;
   uint64_t shading_cap = std::numeric_limits<uint64_t>::max();
-  auto use = [&](auto &buffer, size_t per_record) {
-    using T = std::remove_reference_t<decltype(*buffer.ptr)>;
-    parts.push_back({reinterpret_cast<unsigned char *>(buffer.ptr), buffer.count * sizeof(T), per_record * sizeof(T)});
+  ForEachRecordArray(job, sl, [&](auto &buffer, size_t per_record, bool may_store) {
+    if (!may_store) return;
+    parts.push_back({reinterpret_cast<unsigned char *>(buffer.ptr), buffer.Bytes(), per_record * sizeof(*buffer.ptr)});
     shading_cap = std::min<uint64_t>(shading_cap, buffer.count / per_record);
-  };
-  if (job.simulation && !job.locate_inside) { use(sl.d_located, 1); use(sl.d_located_tag, 1); }
-  if (job.freq_split) use(sl.d_freq_inputs, 1);
-  else if (!ctx->polarized) use(sl.d_transfer, n_nu);
-  if (job.composed) use(sl.d_composed, 1);
-  if (job.tau_row) use(sl.d_tau_inc, n_nu);
-  if (job.aux && !job.rows_only) use(sl.d_aux, 1);
-  if (job.slow) use(sl.d_slow_frac, 1);
-  if (ctx->polarized) {
-    use(sl.d_pol_samples, 1);
-    if (job.matrix_transport) use(sl.d_pol_matrix, BL_POL_MATRIX_DOUBLES);
-    if (!job.pol_one_pass) use(sl.d_pol_coeffs, n_nu * 4);   // (one pass: d_pol_variant_coeffs, which stays out of the store - EnsureScratchOnce)
-    use(sl.d_coef_inputs, 1);
-    if (job.pol_coefficients_inside) use(sl.d_have_flags, 1);
-  }
-  if (job.coef_split) use(sl.d_coef_inputs, 1);
-  if (job.block_interp && !job.locate_inside) use(sl.d_anchors, 8);
+  });
   shading_cap = std::min<uint64_t>(shading_cap, (1ull << 32) - (1ull << 22));   // (32-bit indices: PlanScratch)
 
   const uint64_t records = ctx->resident.pending_records;
@@ -907,21 +952,14 @@ void PlanScratch(RenderJob &job) {
   const bl_params &p = ctx->params;
   const int n_nu = job.n_nu;
   job.xcd_order = XcdOrderApplies(job);
-  // per sample record (the arrays indexed by record slot) and per kept sample (the arrays indexed by ray_offset + n: never
-  // more than records)
-  job.bytes_per_record = sizeof(BlSampleHot) + sizeof(BlSampleCold)
-      + ((job.simulation && !job.locate_inside) ? sizeof(BlLocated) + sizeof(unsigned long long) : 0)
-      + (job.freq_split ? sizeof(BlFreqInputs) : (ctx->polarized ? 0 : sizeof(double2) * n_nu)) + (job.tau_row ? sizeof(double) * n_nu : 0)
-      + (job.composed ? sizeof(double2) : 0)
-      + ((job.aux && !job.rows_only) ? sizeof(BlAuxSample) : 0) + (job.need_time ? sizeof(double) : 0) + (job.slow ? sizeof(double) : 0)
-      // (polarized variants in one pass: every variant's coefficients, in an array of their own - d_pol_variant_coeffs - instead of d_pol_coeffs)
-      + (ctx->polarized ? sizeof(BlPolSample) + sizeof(BlCoefInputs) + 4 * sizeof(double2) * n_nu * (job.pol_one_pass ? job.n_pol : 1)
-                              + (job.pol_coefficients_inside ? 1 : 0) : 0)
-      + (job.coef_split ? sizeof(BlCoefInputs) : 0)
-      + (job.matrix_transport ? BL_POL_MATRIX_DOUBLES * sizeof(double) : 0)
-      + ((job.block_interp && !job.locate_inside) ? 8 * sizeof(unsigned int) : 0)
-      + (job.xcd_order ? 1 : 0);   // (the record lists: BL_XCD_QUEUES x 4 bytes per 64 records; counted before the plan below can
-                                   // still drop the order - a chunk or more, parked rays - which then leaves that byte unused)
+  job.use = UsedArrays(job);
+  // per sample record (the arrays indexed by record slot) and per kept sample (the arrays indexed by ray_offset + n: never more than records)
+  job.bytes_per_record = sizeof(BlSampleHot) + sizeof(BlSampleCold);   // the two halves of a record
+  ForEachRecordArray(job, ctx->slot[0], [&job](const auto &buffer, size_t per_record, bool) { job.bytes_per_record += per_record * sizeof(*buffer.ptr); });
+  if (job.use.sample_t) job.bytes_per_record += sizeof(double);
+  // (the record lists: BL_XCD_QUEUES x 4 bytes per 64 records; counted before the plan below can still drop the order - a chunk or more,
+  // parked rays - which then leaves that byte unused)
+  if (job.use.xcd) job.bytes_per_record += 1;
   if (job.reuse) {
     // over the resident records: the scratch set as the render that integrated them sized it, no stepper, nothing parked
     job.n_slots = 1;
@@ -947,7 +985,7 @@ void PlanScratch(RenderJob &job) {
     job.quad_grid = 0;
     return;
   }
-  const uint64_t per_slot_fixed = ((job.fast || job.fast_formula || ctx->polarized) ? job.redo_capacity * sizeof(unsigned long long) : 0) + BL_CNT_TOTAL * sizeof(unsigned long long);
+  const uint64_t per_slot_fixed = (job.use.redo ? job.redo_capacity * sizeof(unsigned long long) : 0) + BL_CNT_TOTAL * sizeof(unsigned long long);   // d_redo, d_counters
   const bool park_every_ray = job.park && (ctx->switches & BL_SWITCH_QUAD_EVERY_RAY) != 0;
   const uint64_t per_ray = (2 + (job.geo_load ? 0 : BL_RAY_START_FIELDS) + (park_every_ray ? BL_PARK_DOUBLES : 0)) * sizeof(double) + (job.skip_shell ? 2 : 1) * sizeof(int) + 1 + 2 * sizeof(long long);
   // The budget is capped by what the device can actually give: 90 % of (free memory + what this context already holds
@@ -1077,59 +1115,30 @@ void EnsureScratch(RenderJob &job) {
 void EnsureScratchOnce(RenderJob &job) {
   bl_ctx *ctx = job.ctx;
   const size_t cap = job.record_capacity;
-  const size_t n_nu = static_cast<size_t>(job.n_nu);
   // kept layout: the record arrays and the tails of the others are the store, left as they are (PlanKeptLayout planned within what
   // scratch set 0 holds: none of the arrays below grows)
   const bool store = job.kept || job.reuse_chunks;
   for (int k = 0; k < job.n_slots; k++) {
     bl_ctx::ChunkSlot &sl = ctx->slot[k];
-    if (store) {
-    } else if (job.interleaved) {
-      sl.d_records_hot.Ensure(2 * cap);
-    } else {
-      sl.d_records_hot.Ensure(cap);
-      sl.d_records_cold.Ensure(cap);
+    if (!store) {
+      sl.d_records_hot.Ensure(job.interleaved ? 2 * cap : cap);
+      if (!job.interleaved) sl.d_records_cold.Ensure(cap);
+      if (job.use.sample_t) sl.d_sample_t.Ensure(cap);
     }
-    if (job.simulation && !job.locate_inside) {
-      sl.d_located.Ensure(cap);
-      sl.d_located_tag.Ensure(cap);
-    }
-    if (job.freq_split) sl.d_freq_inputs.Ensure(cap);   // instead of the transfer records
-    else if (!ctx->polarized) sl.d_transfer.Ensure(cap * n_nu);   // (polarized runs: the eight coefficients of a sample side by side, d_pol_coeffs)
-    if (job.composed) sl.d_composed.Ensure(cap);
-    if (job.xcd_order) {
+    ForEachRecordArray(job, sl, [cap](auto &buffer, size_t per_record, bool) { buffer.Ensure(cap * per_record); });
+    if (job.use.xcd) {
       sl.d_xcd_state.Ensure(4 * BL_XCD_QUEUES);
       sl.d_xcd_lists.Ensure(BL_XCD_QUEUES * (cap / 64 + 1));
     }
-    if (job.park || job.split_long) sl.d_parked.Ensure(job.park_capacity * BL_PARK_DOUBLES);
-    if (job.tau_row) sl.d_tau_inc.Ensure(cap * n_nu);
+    if (job.use.parked) sl.d_parked.Ensure(job.park_capacity * BL_PARK_DOUBLES);
     sl.d_counters.Ensure(BL_CNT_TOTAL);
-    if (job.aux && !job.rows_only) sl.d_aux.Ensure(cap);   // (rows_only: nobody writes or reads the 96-byte records)
-    if (job.need_time && !store) sl.d_sample_t.Ensure(cap);
-    if (job.slow) sl.d_slow_frac.Ensure(cap);
-    if (ctx->polarized) {
-      sl.d_pol_samples.Ensure(cap);
-      if (job.matrix_transport) sl.d_pol_matrix.Ensure(cap * BL_POL_MATRIX_DOUBLES);
-      if (!job.pol_one_pass) sl.d_pol_coeffs.Ensure(cap * n_nu * 4);
-      // (polarized variants in one pass: not a part of the kept layout's store - PlanKeptLayout - so that a render over resident
-      // records may have more variants than the one that integrated them)
-      if (job.pol_one_pass) sl.d_pol_variant_coeffs.Ensure(cap * n_nu * 4 * static_cast<size_t>(job.n_pol));
-      sl.d_coef_inputs.Ensure(cap);
-      if (job.pol_coefficients_inside) sl.d_have_flags.Ensure(cap);
-    }
-    if (job.coef_split) sl.d_coef_inputs.Ensure(cap);
-    if (job.block_interp && !job.locate_inside) sl.d_anchors.Ensure(cap * 8);   // (locate step inside: the exact pass keeps a sample's anchors in registers)
-    if (job.fast || job.fast_formula || ctx->polarized) sl.d_redo.Ensure(job.redo_capacity);   // polarized runs: the samples whose frame bl_polarized_frame_kernel builds
+    if (job.use.redo) sl.d_redo.Ensure(job.redo_capacity);
   }
   const size_t n_rays = static_cast<size_t>(job.n_rays);
-  ctx->d_ray_kt.Ensure(n_rays);
-  ctx->d_ray_factor.Ensure(n_rays);
-  ctx->d_ray_sample_num.Ensure(n_rays);
-  if (job.skip_shell) ctx->d_ray_skipped.Ensure(n_rays);
-  if (job.composed) ctx->d_ray_rows.Ensure(n_rays);
-  ctx->d_ray_flags.Ensure(n_rays);
-  ctx->d_ray_out_index.Ensure(n_rays);
-  ctx->d_ray_offset.Ensure(n_rays);
+  auto ensure = [n_rays](auto &...buffer) { (buffer.Ensure(n_rays), ...); };
+  ensure(ctx->rays.kt, ctx->rays.factor, ctx->rays.sample_num, ctx->rays.flags, ctx->rays.out_index, ctx->rays.offset);
+  if (job.skip_shell) ctx->rays.skipped.Ensure(n_rays);
+  if (job.composed) ctx->rays.rows.Ensure(n_rays);
   if (!job.geo_load) ctx->d_ray_start.Ensure(n_rays * BL_RAY_START_FIELDS);
   EnsureRenderResources(ctx);
 }
@@ -1441,8 +1450,7 @@ void BuildShadeArgs(RenderJob &job) {
   cold.plane_normal[2] = p.cut_plane_normal_z;
   for (int mu = 0; mu < 4; mu++) cold.cam_x[mu] = ctx->frame.cam_x[mu];
   sa.cuts.camera_r = p.camera_r;
-  sa.cuts.any_optional = (p.cut_omit_near || p.cut_omit_far || p.cut_omit_in >= 0.0 || p.cut_omit_out >= 0.0
-                          || p.cut_midplane_theta != 0.0 || p.cut_midplane_z != 0.0 || p.cut_plane) ? 1 : 0;
+  sa.cuts.any_optional = GeometricCut(p) ? 1 : 0;
   sa.plasma.fallback_nan = p.fallback_nan;   // (formula mode too: a flagged ray's coefficients are NaN there as well, formula_coefficients.cpp:51-59)
   if (job.simulation) {
     BlPlasmaDevice &pl = sa.plasma;
@@ -1573,7 +1581,7 @@ void BuildShadeArgs(RenderJob &job) {
   sa.tag_in_record = job.fast ? 1 : 0;
   sa.freq_split = job.freq_split ? (job.variants_one_pass ? 2 : 1) : 0;
   sa.coef_split = job.coef_split ? 1 : 0;
-  sa.redo_capacity = (job.fast || job.fast_formula || ctx->polarized) ? job.redo_capacity : 0;
+  sa.redo_capacity = job.use.redo ? job.redo_capacity : 0;
 
   job.snapshot_time = job.slow ? p.slow_t_start + p.slow_dt * ctx->snapshot : 0.0;   // simulation_reader.cpp:214
   if (job.slow) {
@@ -1680,6 +1688,7 @@ void BuildTransferArgs(RenderJob &job) {
 void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   bl_ctx *ctx = job.ctx;
   bl_ctx::ChunkSlot &sl = ctx->slot[k];
+  const ArrayUse &use = job.use;
   BlTraceArgs &ta = job.ta;
   BlShadeArgs &sa = job.sa;
   BlTransferArgs &xa = job.xa;
@@ -1696,22 +1705,22 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
     const size_t base = job.chunk_base;
     ta.records_hot = seg.hot + base * ta.record_stride;
     ta.records_cold = job.interleaved ? reinterpret_cast<BlSampleCold *>(ta.records_hot + 1) : seg.cold + base;
-    ta.sample_t = job.need_time ? seg.sample_t + base : nullptr;
+    ta.sample_t = use.sample_t ? seg.sample_t + base : nullptr;
   } else {
     ta.records_hot = sl.d_records_hot.ptr;
     ta.records_cold = job.interleaved ? reinterpret_cast<BlSampleCold *>(sl.d_records_hot.ptr + 1) : sl.d_records_cold.ptr;
-    ta.sample_t = job.need_time ? sl.d_sample_t.ptr : nullptr;
+    ta.sample_t = use.sample_t ? sl.d_sample_t.ptr : nullptr;
   }
   ta.record_capacity = static_cast<long long>(job.chunk_capacity);
   ta.record_gate = job.chunk_gate;
   ta.counters = sl.d_counters.ptr;
-  ta.ray_kt = ctx->d_ray_kt.ptr + begin;
-  ta.ray_factor = ctx->d_ray_factor.ptr + begin;
-  ta.ray_sample_num = ctx->d_ray_sample_num.ptr + begin;
-  ta.ray_skipped = job.skip_shell ? ctx->d_ray_skipped.ptr + begin : nullptr;
+  ta.ray_kt = ctx->rays.kt.ptr + begin;
+  ta.ray_factor = ctx->rays.factor.ptr + begin;
+  ta.ray_sample_num = ctx->rays.sample_num.ptr + begin;
+  ta.ray_skipped = job.skip_shell ? ctx->rays.skipped.ptr + begin : nullptr;
   ta.segment_rows = job.composed ? 1 : 0;
-  ta.ray_rows = job.composed ? ctx->d_ray_rows.ptr + begin : nullptr;
-  ta.parked = (job.park || job.split_long) ? sl.d_parked.ptr : nullptr;
+  ta.ray_rows = job.composed ? ctx->rays.rows.ptr + begin : nullptr;
+  ta.parked = use.parked ? sl.d_parked.ptr : nullptr;
   ta.split_b_lo = ta.split_b_hi = 0.0;
   if (job.split_long) {
     ta.split_b_lo = job.split_b_lo;
@@ -1724,12 +1733,12 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   ta.park_age = job.max_steps / 8;
   ta.quad_first_round = ctx->num_cus * 4;
   ta.park_always = (job.park && (ctx->switches & BL_SWITCH_QUAD_EVERY_RAY)) ? 1 : 0;
-  ta.xcd_state = job.xcd_order ? sl.d_xcd_state.ptr : nullptr;
-  ta.xcd_lists = job.xcd_order ? sl.d_xcd_lists.ptr : nullptr;
-  ta.xcd_list_capacity = job.xcd_order ? static_cast<long long>(job.record_capacity / 64 + 1) : 0;
-  ta.ray_flags = ctx->d_ray_flags.ptr + begin;
-  ta.ray_out_index = ctx->d_ray_out_index.ptr + begin;
-  ta.ray_offset = ctx->d_ray_offset.ptr + begin;
+  ta.xcd_state = use.xcd ? sl.d_xcd_state.ptr : nullptr;
+  ta.xcd_lists = use.xcd ? sl.d_xcd_lists.ptr : nullptr;
+  ta.xcd_list_capacity = use.xcd ? static_cast<long long>(job.record_capacity / 64 + 1) : 0;
+  ta.ray_flags = ctx->rays.flags.ptr + begin;
+  ta.ray_out_index = ctx->rays.out_index.ptr + begin;
+  ta.ray_offset = ctx->rays.offset.ptr + begin;
   ta.ray_start = job.geo_load ? nullptr : ctx->d_ray_start.ptr + begin;
   sa.records_hot = ta.records_hot;
   sa.records_cold = ta.records_cold;
@@ -1737,32 +1746,33 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   sa.xcd_lists = ta.xcd_lists;
   sa.xcd_list_capacity = ta.xcd_list_capacity;
   sa.record_stride = ta.record_stride;
-  sa.located = (job.simulation && !job.locate_inside) ? sl.d_located.ptr : nullptr;
-  sa.located_tag = (job.simulation && !job.locate_inside) ? sl.d_located_tag.ptr : nullptr;
-  sa.freq_inputs = job.freq_split ? sl.d_freq_inputs.ptr : nullptr;
+  sa.located = use.located ? sl.d_located.ptr : nullptr;
+  sa.located_tag = use.located ? sl.d_located_tag.ptr : nullptr;
+  sa.freq_inputs = use.freq_inputs ? sl.d_freq_inputs.ptr : nullptr;
   sa.counters_in = sl.d_counters.ptr;
   sa.counters = sl.d_counters.ptr;
   sa.ray_kt = ta.ray_kt;
   sa.ray_factor = ta.ray_factor;
   sa.ray_offset = ta.ray_offset;
   sa.ray_flags = ta.ray_flags;
-  sa.transfer = ctx->polarized ? nullptr : sl.d_transfer.ptr;
-  sa.composed = job.composed ? sl.d_composed.ptr : nullptr;
-  sa.tau_inc = job.tau_row ? sl.d_tau_inc.ptr : nullptr;
-  sa.aux = (job.aux && !job.rows_only) ? sl.d_aux.ptr : nullptr;
+  sa.transfer = use.pol ? nullptr : sl.d_transfer.ptr;   // (with per-sample factors instead: whatever an earlier render left, never read)
+  sa.composed = use.composed ? sl.d_composed.ptr : nullptr;
+  sa.tau_inc = use.tau_inc ? sl.d_tau_inc.ptr : nullptr;
+  sa.aux = use.aux ? sl.d_aux.ptr : nullptr;
   sa.sample_t = ta.sample_t;
-  sa.coef_inputs = (job.coef_split || ctx->polarized) ? sl.d_coef_inputs.ptr : nullptr;
-  sa.have_flags = job.pol_coefficients_inside ? sl.d_have_flags.ptr : nullptr;
-  sa.anchors = (job.block_interp && !job.locate_inside) ? sl.d_anchors.ptr : nullptr;
-  sa.redo_list = (job.fast || job.fast_formula || ctx->polarized) ? sl.d_redo.ptr : nullptr;
-  if (job.slow) {
+  sa.coef_inputs = use.coef_inputs ? sl.d_coef_inputs.ptr : nullptr;
+  sa.have_flags = use.have_flags ? sl.d_have_flags.ptr : nullptr;
+  sa.anchors = use.anchors ? sl.d_anchors.ptr : nullptr;
+  sa.redo_list = use.redo ? sl.d_redo.ptr : nullptr;
+  if (use.slow_frac) {
     sa.slow.frac = sl.d_slow_frac.ptr;
     sa.slow.ray_extrap = ctx->d_ray_extrap.ptr + begin;
   }
   xa.chunk_rays = rays;
   xa.counters = sl.d_counters.ptr;
-  xa.transfer = ctx->polarized ? (job.pol_one_pass ? sl.d_pol_variant_coeffs.ptr : sl.d_pol_coeffs.ptr) : sl.d_transfer.ptr;   // (one pass: rows_only, never read)
-  xa.ja_stride = ctx->polarized ? 4 : 1;
+  double2 *pol_coeffs = use.pol_variant_coeffs ? sl.d_pol_variant_coeffs.ptr : sl.d_pol_coeffs.ptr;
+  xa.transfer = use.pol ? pol_coeffs : sl.d_transfer.ptr;   // (one pass: rows_only, never read)
+  xa.ja_stride = use.pol ? 4 : 1;
   xa.composed = sa.composed;
   xa.ray_rows = ta.ray_rows;
   xa.tau_inc = sa.tau_inc;
@@ -1776,13 +1786,10 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   xa.ray_factor = ta.ray_factor;
   xa.stats = sl.d_counters.ptr + BL_CNT_COUNT;
   xa.aux = sa.aux;
-  if (ctx->polarized) {
-    sa.pol_samples = sl.d_pol_samples.ptr;
-    sa.pol_coeffs = sl.d_pol_coeffs.ptr;
-    xa.pol_samples = sl.d_pol_samples.ptr;
-    xa.pol_coeffs = sl.d_pol_coeffs.ptr;
-    if (job.pol_one_pass) sa.pol_coeffs = sl.d_pol_variant_coeffs.ptr, xa.pol_coeffs = sl.d_pol_variant_coeffs.ptr;
-    xa.pol_matrix = job.matrix_transport ? sl.d_pol_matrix.ptr : nullptr;
+  if (use.pol) {
+    xa.pol_samples = sa.pol_samples = sl.d_pol_samples.ptr;
+    xa.pol_coeffs = sa.pol_coeffs = pol_coeffs;
+    xa.pol_matrix = use.pol_matrix ? sl.d_pol_matrix.ptr : nullptr;
   }
 }
 
@@ -1845,12 +1852,12 @@ long long LoadChunkFromCheckpoint(RenderJob &job, int k, long long begin, int ra
     Check(hipMemcpy(sl.d_records_cold.ptr, cold.data(), n_loaded * sizeof(BlSampleCold), hipMemcpyHostToDevice), "checkpoint upload");
     Check(hipMemcpy(sl.d_sample_t.ptr, sample_t.data(), n_loaded * sizeof(double), hipMemcpyHostToDevice), "checkpoint upload");
   }
-  Check(hipMemcpy(ctx->d_ray_kt.ptr + begin, ray_kt.data(), taken * sizeof(double), hipMemcpyHostToDevice), "checkpoint upload");
-  Check(hipMemcpy(ctx->d_ray_factor.ptr + begin, ray_factor.data(), taken * sizeof(double), hipMemcpyHostToDevice), "checkpoint upload");
-  Check(hipMemcpy(ctx->d_ray_sample_num.ptr + begin, ray_num.data(), taken * sizeof(int), hipMemcpyHostToDevice), "checkpoint upload");
-  Check(hipMemcpy(ctx->d_ray_flags.ptr + begin, ray_flags.data(), taken, hipMemcpyHostToDevice), "checkpoint upload");
-  Check(hipMemcpy(ctx->d_ray_out_index.ptr + begin, ray_out.data(), taken * sizeof(long long), hipMemcpyHostToDevice), "checkpoint upload");
-  Check(hipMemcpy(ctx->d_ray_offset.ptr + begin, ray_offset.data(), taken * sizeof(long long), hipMemcpyHostToDevice), "checkpoint upload");
+  Check(hipMemcpy(ctx->rays.kt.ptr + begin, ray_kt.data(), taken * sizeof(double), hipMemcpyHostToDevice), "checkpoint upload");
+  Check(hipMemcpy(ctx->rays.factor.ptr + begin, ray_factor.data(), taken * sizeof(double), hipMemcpyHostToDevice), "checkpoint upload");
+  Check(hipMemcpy(ctx->rays.sample_num.ptr + begin, ray_num.data(), taken * sizeof(int), hipMemcpyHostToDevice), "checkpoint upload");
+  Check(hipMemcpy(ctx->rays.flags.ptr + begin, ray_flags.data(), taken, hipMemcpyHostToDevice), "checkpoint upload");
+  Check(hipMemcpy(ctx->rays.out_index.ptr + begin, ray_out.data(), taken * sizeof(long long), hipMemcpyHostToDevice), "checkpoint upload");
+  Check(hipMemcpy(ctx->rays.offset.ptr + begin, ray_offset.data(), taken * sizeof(long long), hipMemcpyHostToDevice), "checkpoint upload");
   Check(hipMemcpy(sl.d_counters.ptr + BL_CNT_RECORDS, &n_loaded, sizeof n_loaded, hipMemcpyHostToDevice), "checkpoint upload");
   Check(hipMemcpy(sl.d_counters.ptr + BL_CNT_NEXT_RAY, &n_taken, sizeof n_taken, hipMemcpyHostToDevice), "checkpoint upload");
   return taken;
@@ -1874,11 +1881,11 @@ void SaveChunkRecords(RenderJob &job, int k, long long begin, int rays) {
     Check(hipMemcpy(cold.data(), sl.d_records_cold.ptr, n_written * sizeof(BlSampleCold), hipMemcpyDeviceToHost), "checkpoint download");
     Check(hipMemcpy(sample_t.data(), sl.d_sample_t.ptr, n_written * sizeof(double), hipMemcpyDeviceToHost), "checkpoint download");
   }
-  Check(hipMemcpy(ray_kt.data(), ctx->d_ray_kt.ptr + begin, rays * sizeof(double), hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_factor.data(), ctx->d_ray_factor.ptr + begin, rays * sizeof(double), hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_num.data(), ctx->d_ray_sample_num.ptr + begin, rays * sizeof(int), hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_flags.data(), ctx->d_ray_flags.ptr + begin, rays, hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_out.data(), ctx->d_ray_out_index.ptr + begin, rays * sizeof(long long), hipMemcpyDeviceToHost), "checkpoint download");
+  Check(hipMemcpy(ray_kt.data(), ctx->rays.kt.ptr + begin, rays * sizeof(double), hipMemcpyDeviceToHost), "checkpoint download");
+  Check(hipMemcpy(ray_factor.data(), ctx->rays.factor.ptr + begin, rays * sizeof(double), hipMemcpyDeviceToHost), "checkpoint download");
+  Check(hipMemcpy(ray_num.data(), ctx->rays.sample_num.ptr + begin, rays * sizeof(int), hipMemcpyDeviceToHost), "checkpoint download");
+  Check(hipMemcpy(ray_flags.data(), ctx->rays.flags.ptr + begin, rays, hipMemcpyDeviceToHost), "checkpoint download");
+  Check(hipMemcpy(ray_out.data(), ctx->rays.out_index.ptr + begin, rays * sizeof(long long), hipMemcpyDeviceToHost), "checkpoint download");
   if (save.sample_num.empty()) {
     save.sample_num.assign(job.n_rays, 0);
     save.flags.assign(job.n_rays, 0);
@@ -1992,9 +1999,9 @@ void SaveChunkSampling(RenderJob &job, int k, long long begin, int rays) {
     if (!job.fast) Check(hipMemcpy(tags.data(), sl.d_located_tag.ptr, n_written * sizeof(unsigned long long), hipMemcpyDeviceToHost), "checkpoint download");
     if (job.block_interp) Check(hipMemcpy(anchors.data(), sl.d_anchors.ptr, anchors.size() * sizeof(unsigned int), hipMemcpyDeviceToHost), "checkpoint download");
   }
-  Check(hipMemcpy(ray_num.data(), ctx->d_ray_sample_num.ptr + begin, rays * sizeof(int), hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_flags.data(), ctx->d_ray_flags.ptr + begin, rays, hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_out.data(), ctx->d_ray_out_index.ptr + begin, rays * sizeof(long long), hipMemcpyDeviceToHost), "checkpoint download");
+  Check(hipMemcpy(ray_num.data(), ctx->rays.sample_num.ptr + begin, rays * sizeof(int), hipMemcpyDeviceToHost), "checkpoint download");
+  Check(hipMemcpy(ray_flags.data(), ctx->rays.flags.ptr + begin, rays, hipMemcpyDeviceToHost), "checkpoint download");
+  Check(hipMemcpy(ray_out.data(), ctx->rays.out_index.ptr + begin, rays * sizeof(long long), hipMemcpyDeviceToHost), "checkpoint download");
   if (out.sample_num.empty()) {
     out.per_sample = job.block_interp ? 32 : 4;
     out.sample_num.assign(job.n_rays, 0);
@@ -2639,6 +2646,7 @@ extern "C" int bl_render(bl_ctx *ctx, const bl_render_desc *d) {
           job.park_capacity = 0;
           job.quad_grid = 0;
         }
+        job.use = UsedArrays(job);   // (less what the plan dropped: one pass over the polarized variants, the order per XCD, parked rays)
         EnsureScratch(job);
         StageInputsAndOutputs(job);
         BuildTraceArgs(job);
