@@ -245,26 +245,22 @@ __global__ void bl_debug_math_kernel(int op, long long n, const double *x, const
 }
 
 
-// frames: 1 the per-frequency coefficients, then the frames of the samples without coefficients; 0 the coefficients only; 2 the frames only
-extern "C" hipError_t bl_launch_polarized_coefficients_parts(const BlShadeArgs *args, int grid, int frames, hipStream_t stream) {
-  if (frames == 2) {
-    hipLaunchKernelGGL(bl_polarized_frame_kernel, dim3(grid), dim3(256), 0, stream, *args);
-    return hipGetLastError();
-  }
-  // (simulation_coefficients<kExtended> also holds the unpolarized kappa terms: never in a polarized run)
+// The per-frequency coefficients of a polarized run's samples (simulation_coefficients<kExtended> also holds the unpolarized kappa
+// terms: never in a polarized run), and the frames of its samples without coefficients
+// (the exact tier's formulas in either tier: the polarized step amplifies last-place differences of the coefficients by orders of
+// magnitude in optically and Faraday thick cells - docs/notebook.md - so a tolerant kernel here moved rows with the reference's own
+// conditioning; it was a measurement switch until round 6)
+extern "C" hipError_t bl_launch_polarized_coefficients(const BlShadeArgs *args, const KernelPlan::PerFrequency &plan, int grid, hipStream_t stream) {
   const bool thermal_only = args->plasma.power_frac == 0.0 && args->plasma.kappa_unpolarized == 0 && args->plasma.kappa_frac_zero != 0;
-#define BL_LAUNCH_PC(T, O) hipLaunchKernelGGL((bl_polarized_coefficients_kernel<T, O>), dim3(grid), dim3(256), 0, stream, *args)
-  // (the exact tier's formulas in either tier: the polarized step amplifies last-place differences of the coefficients by orders of
-  // magnitude in optically and Faraday thick cells - docs/notebook.md - so a tolerant kernel here moved rows with the reference's own
-  // conditioning; it was a measurement switch until round 6)
-  if (thermal_only) BL_LAUNCH_PC(false, true);
-  else BL_LAUNCH_PC(false, false);
-#undef BL_LAUNCH_PC
-  if (frames == 1) hipLaunchKernelGGL(bl_polarized_frame_kernel, dim3(grid), dim3(256), 0, stream, *args);
+  if (!plan.polarized_coefficients || plan.thermal_only != thermal_only || args->pol_samples == nullptr) return hipErrorInvalidValue;
+  void (*kernel)(BlShadeArgs) = plan.thermal_only ? bl_polarized_coefficients_kernel<false, true> : bl_polarized_coefficients_kernel<false, false>;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, *args);
   return hipGetLastError();
 }
-extern "C" hipError_t bl_launch_polarized_coefficients(const BlShadeArgs *args, int grid, hipStream_t stream) {
-  return bl_launch_polarized_coefficients_parts(args, grid, 1, stream);
+extern "C" hipError_t bl_launch_polarized_frames(const BlShadeArgs *args, int grid, hipStream_t stream) {
+  if (args->pol_samples == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(bl_polarized_frame_kernel, dim3(grid), dim3(256), 0, stream, *args);
+  return hipGetLastError();
 }
 
 extern "C" hipError_t bl_launch_debug_math(int op, long long n, const double *x, const double *y, double *out, hipStream_t stream) {
@@ -273,12 +269,9 @@ extern "C" hipError_t bl_launch_debug_math(int op, long long n, const double *x,
   return hipGetLastError();
 }
 
+// (one instantiation: the extended formulas evaluate to the plain ones' bits where no power law or entropy is asked for)
 extern "C" hipError_t bl_launch_coefficients_freq(const BlShadeArgs *args, int grid, hipStream_t stream) {
-  // (the instantiation bl_launch_shade chose for the coefficient kernel: power-law electrons only in the extended one)
-  const bool extended = args->plasma.power_frac != 0.0 || args->plasma.code_kappa != 0 || args->slow.n > 0 || args->anchors != nullptr
-      || args->plasma.kappa_unpolarized != 0;
-  (void)extended;   // (one instantiation: the extended formulas evaluate to the plain ones' bits where no power law or entropy is asked for)
+  if (args->coef_inputs == nullptr || !args->coef_split) return hipErrorInvalidValue;
   hipLaunchKernelGGL(bl_coefficients_freq_kernel<true>, dim3(grid), dim3(256), 0, stream, *args);
   return hipGetLastError();
 }
-

@@ -25,30 +25,30 @@
 #include "bl_device.h"
 #include "bl_internal.h"
 
-extern "C" hipError_t bl_launch_ray_init(const BlTraceArgs *args, int integrator, hipStream_t stream);
-extern "C" hipError_t bl_launch_geodesic(const BlTraceArgs *args, int integrator, int grid, hipStream_t stream, int lds_pad);
-extern "C" hipError_t bl_launch_geodesic_quad(const BlTraceArgs *args, int grid, hipStream_t stream, int lds_pad);
+// The launch wrappers (at the end of each kernel file): each takes its part of the render's KernelPlan (bl_kernel_plan.h), maps it to a
+// kernel through one selector per kernel family, and returns hipErrorInvalidValue where the argument block disagrees with the choice
+extern "C" hipError_t bl_launch_ray_init(const BlTraceArgs *args, const KernelPlan::Geodesic &plan, hipStream_t stream);
+extern "C" hipError_t bl_launch_geodesic(const BlTraceArgs *args, const KernelPlan::Geodesic &plan, int grid, hipStream_t stream, int lds_pad);
+extern "C" int bl_geodesic_occupancy(const KernelPlan::Geodesic &plan);
+extern "C" hipError_t bl_launch_geodesic_quad(const BlTraceArgs *args, const KernelPlan::Quad &plan, int grid, hipStream_t stream, int lds_pad);
 extern "C" hipError_t bl_launch_split_long(const BlTraceArgs *args, hipStream_t stream);
-extern "C" int bl_geodesic_occupancy(int integrator, int with_time, int spin_zero, int shell);
-extern "C" hipError_t bl_launch_locate(const BlShadeArgs *args, int grid, int lds_bytes, hipStream_t stream);
-extern "C" hipError_t bl_launch_shade(const BlShadeArgs *args, int model, int grid, hipStream_t stream);
-extern "C" hipError_t bl_launch_shade_fast(const BlShadeArgs *args, int grid, hipStream_t stream);
+extern "C" hipError_t bl_launch_locate(const BlShadeArgs *args, const KernelPlan::Locate &plan, int grid, int lds_bytes, hipStream_t stream);
+extern "C" hipError_t bl_launch_shade(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream);   // kShade, kExact
+extern "C" hipError_t bl_launch_shade_fast(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream);
+extern "C" hipError_t bl_launch_shade_formula_fast(const BlShadeArgs *args, int grid, hipStream_t stream);
+extern "C" hipError_t bl_launch_shade_fused2(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream);
+extern "C" hipError_t bl_launch_shade_exact2(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream);
+extern "C" hipError_t bl_launch_shade_polarized2(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream);
+extern "C" hipError_t bl_launch_shade_redo(const BlShadeArgs *args, const KernelPlan::Redo &plan, int grid, hipStream_t stream);
 extern "C" int bl_fused2_applicable(const BlGridDevice *grid, int n_nu, long long n_rays);
 extern "C" int bl_fused2_refined_applicable(const BlGridDevice *grid, int n_nu, long long n_rays);
 extern "C" int bl_polarized2_refined_applicable(const BlGridDevice *grid, long long n_rays);
-extern "C" hipError_t bl_launch_transfer_composed(const BlTransferArgs *args, hipStream_t stream);
-extern "C" hipError_t bl_launch_shade_exact2(const BlShadeArgs *args, int grid, hipStream_t stream);
-extern "C" hipError_t bl_launch_shade_polarized2(const BlShadeArgs *args, int grid, hipStream_t stream);
-extern "C" hipError_t bl_launch_shade_formula_fast(const BlShadeArgs *args, int grid, hipStream_t stream);
-extern "C" hipError_t bl_launch_polarized_coefficients(const BlShadeArgs *args, int grid, hipStream_t stream);
-extern "C" hipError_t bl_launch_polarized_coefficients_parts(const BlShadeArgs *args, int grid, int frames, hipStream_t stream);
-extern "C" hipError_t bl_launch_transfer(const BlTransferArgs *args, hipStream_t stream);
-extern "C" hipError_t bl_launch_tau(const BlTransferArgs *args, hipStream_t stream);
-extern "C" hipError_t bl_launch_transfer_freq(const BlTransferArgs *args, hipStream_t stream);
+extern "C" hipError_t bl_launch_polarized_coefficients(const BlShadeArgs *args, const KernelPlan::PerFrequency &plan, int grid, hipStream_t stream);
+extern "C" hipError_t bl_launch_polarized_frames(const BlShadeArgs *args, int grid, hipStream_t stream);
 extern "C" hipError_t bl_launch_coefficients_freq(const BlShadeArgs *args, int grid, hipStream_t stream);
-extern "C" hipError_t bl_launch_transfer_aux(const BlTransferArgs *args, hipStream_t stream);
+extern "C" hipError_t bl_launch_transfer(const BlTransferArgs *args, const KernelPlan::Transfer &plan, hipStream_t stream);
+extern "C" hipError_t bl_launch_tau(const BlTransferArgs *args, hipStream_t stream);
 extern "C" hipError_t bl_launch_transfer_polarized(const BlTransferArgs *args, hipStream_t stream);
-extern "C" hipError_t bl_launch_transfer_polarized_matrix(const BlTransferArgs *args, int num_cus, hipStream_t stream);
 extern "C" hipError_t bl_launch_transport_matrices(const BlTransferArgs *args, int num_cus, hipStream_t stream);
 extern "C" hipError_t bl_launch_transfer_polarized_rays(const BlTransferArgs *args, hipStream_t stream);
 extern "C" hipError_t bl_launch_debug_math(int op, long long n, const double *x, const double *y, double *out, hipStream_t stream);

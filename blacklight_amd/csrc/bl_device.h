@@ -24,6 +24,7 @@
 
 #include "bl_camera.h"
 #include "bl_geometry.h"
+#include "bl_kernel_plan.h"
 
 // One emitted geodesic sample (geodesic_pos/dir/len entries of the reference, geodesics.cpp:250-293), before the
 // per-sample momentum renormalisation of :352-371, in two 32-byte halves kept in two arrays: the locate kernel

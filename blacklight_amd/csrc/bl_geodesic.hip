@@ -839,8 +839,10 @@ __global__ void __launch_bounds__(256) bl_split_long_kernel(BlTraceArgs P) {
 }
 
 // =================================================================================================
-// Launch wrappers (called from bl_api.hip)
+// Launch wrappers (called from bl_render.hip)
 // =================================================================================================
+using BlTraceKernel = void (*)(BlTraceArgs);
+
 extern "C" hipError_t bl_launch_split_long(const BlTraceArgs *args, hipStream_t stream) {
   if (args->parked == nullptr || args->ray_start == nullptr) return hipErrorInvalidValue;
   hipLaunchKernelGGL(bl_split_long_kernel, dim3((args->chunk_rays + 255) / 256), dim3(256), 0, stream, *args);
@@ -848,68 +850,49 @@ extern "C" hipError_t bl_launch_split_long(const BlTraceArgs *args, hipStream_t 
 }
 
 // Start states of the rays [chunk_begin, chunk_begin + chunk_rays) (bl_ray_init_kernel)
-extern "C" hipError_t bl_launch_ray_init(const BlTraceArgs *args, int integrator, hipStream_t stream) {
-  const bool spin_zero = args->st.bh_a == 0.0;
-  const int grid = (args->chunk_rays + 255) / 256;
-  const bool dp = integrator == BL_INTEGRATOR_DP;
-  if (dp && spin_zero) hipLaunchKernelGGL((bl_ray_init_kernel<true, true>), dim3(grid), dim3(256), 0, stream, *args);
-  else if (dp) hipLaunchKernelGGL((bl_ray_init_kernel<true, false>), dim3(grid), dim3(256), 0, stream, *args);
-  else hipLaunchKernelGGL((bl_ray_init_kernel<false, false>), dim3(grid), dim3(256), 0, stream, *args);
+extern "C" hipError_t bl_launch_ray_init(const BlTraceArgs *args, const KernelPlan::Geodesic &plan, hipStream_t stream) {
+  const bool dp = plan.integrator == BL_INTEGRATOR_DP;
+  if (plan.spin_zero && (!dp || args->st.bh_a != 0.0)) return hipErrorInvalidValue;
+  BlTraceKernel kernel = dp ? (plan.spin_zero ? bl_ray_init_kernel<true, true> : bl_ray_init_kernel<true, false>) : bl_ray_init_kernel<false, false>;
+  hipLaunchKernelGGL(kernel, dim3((args->chunk_rays + 255) / 256), dim3(256), 0, stream, *args);
   return hipGetLastError();
 }
 
-// One expression per instantiation of the geodesic kernel. Dormand-Prince (the default, and what every BASELINE configuration uses):
-// sample times x zero spin x empty shell, the last two only without sample times. The fixed-step steppers have the general
-// instantiation with and without sample times only (zero spin runs through the general formulas, bit for bit the same; bl_render.hip
-// leaves the shell's steps recorded for them).
-#define BL_GEODESIC_CASES(I, DO)                                                      \
-  do {                                                                                \
-    if (with_time && spin_zero) DO((bl_geodesic_kernel<I, true, true, false>));       \
-    else if (with_time) DO((bl_geodesic_kernel<I, true, false, false>));              \
-    else if (spin_zero && shell) DO((bl_geodesic_kernel<I, false, true, true>));      \
-    else if (spin_zero) DO((bl_geodesic_kernel<I, false, true, false>));              \
-    else if (shell) DO((bl_geodesic_kernel<I, false, false, true>));                  \
-    else DO((bl_geodesic_kernel<I, false, false, false>));                            \
-  } while (0)
-#define BL_GEODESIC_CASES_FIXED_STEP(I, DO)                                           \
-  do {                                                                                \
-    if (with_time) DO((bl_geodesic_kernel<I, true, false, false>));                   \
-    else DO((bl_geodesic_kernel<I, false, false, false>));                            \
-  } while (0)
+// The geodesic kernel's instantiations, each named once. Dormand-Prince (the default, and what every BASELINE configuration uses):
+// sample times x zero spin x empty shell, the last only without sample times. The fixed-step steppers have the general instantiation
+// with and without sample times only (zero spin runs through the general formulas, bit for bit the same; bl_render.hip leaves the
+// shell's steps recorded for them). nullptr: no such instantiation.
+template <int kIntegrator>
+static BlTraceKernel fixed_step_kernel(const KernelPlan::Geodesic &g) {
+  if (g.spin_zero || g.shell) return nullptr;
+  return g.with_time ? bl_geodesic_kernel<kIntegrator, true, false, false> : bl_geodesic_kernel<kIntegrator, false, false, false>;
+}
+static BlTraceKernel geodesic_kernel(const KernelPlan::Geodesic &g) {
+  constexpr int kDp = BL_INTEGRATOR_DP;
+  if (g.integrator == BL_INTEGRATOR_RK4) return fixed_step_kernel<BL_INTEGRATOR_RK4>(g);
+  if (g.integrator != kDp) return fixed_step_kernel<BL_INTEGRATOR_RK2>(g);
+  if (g.with_time) return g.shell ? nullptr : (g.spin_zero ? bl_geodesic_kernel<kDp, true, true, false> : bl_geodesic_kernel<kDp, true, false, false>);
+  if (g.spin_zero) return g.shell ? bl_geodesic_kernel<kDp, false, true, true> : bl_geodesic_kernel<kDp, false, true, false>;
+  return g.shell ? bl_geodesic_kernel<kDp, false, false, true> : bl_geodesic_kernel<kDp, false, false, false>;
+}
 
 // lds_pad: bytes of LDS a workgroup (= a wave) reserves without using them - 39 KiB keeps a CU to four waves, one per SIMD, where the
 // dispatcher would otherwise fill a CU's eight slots before the next CU's first (BL_TAIL_SPLIT: a CU mask that leaves a shader engine
 // one CU and another two makes it do that, and a wave that shares its SIMD steps its rays at half the speed)
-extern "C" hipError_t bl_launch_geodesic(const BlTraceArgs *args, int integrator, int grid, hipStream_t stream, int lds_pad) {
-  const bool with_time = args->sample_t != nullptr;
-  const bool spin_zero = args->st.bh_a == 0.0;   // also true for -0.0: the instantiation never reads bh_a
-  const bool shell = args->ray_skipped != nullptr;
-  if (shell && (with_time || integrator != BL_INTEGRATOR_DP)) return hipErrorInvalidValue;
-#define BL_LAUNCH_G(K) hipLaunchKernelGGL(K, dim3(grid), dim3(64), lds_pad, stream, *args)
-  switch (integrator) {
-    case BL_INTEGRATOR_DP: BL_GEODESIC_CASES(BL_INTEGRATOR_DP, BL_LAUNCH_G); break;
-    case BL_INTEGRATOR_RK4: BL_GEODESIC_CASES_FIXED_STEP(BL_INTEGRATOR_RK4, BL_LAUNCH_G); break;
-    default: BL_GEODESIC_CASES_FIXED_STEP(BL_INTEGRATOR_RK2, BL_LAUNCH_G); break;
-  }
-#undef BL_LAUNCH_G
+extern "C" hipError_t bl_launch_geodesic(const BlTraceArgs *args, const KernelPlan::Geodesic &plan, int grid, hipStream_t stream, int lds_pad) {
+  BlTraceKernel kernel = geodesic_kernel(plan);
+  // (the block has to agree with the choice: sample times, the skipped steps' counts, and zero spin - also true for -0.0: the
+  // instantiation never reads bh_a)
+  if (kernel == nullptr || (args->sample_t != nullptr) != plan.with_time || (args->ray_skipped != nullptr) != plan.shell
+      || (plan.spin_zero && args->st.bh_a != 0.0)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds_pad, stream, *args);
   return hipGetLastError();
 }
 
 // Workgroups (= waves) of the geodesic kernel one CU holds: the persistent grid is this many per CU
-extern "C" int bl_geodesic_occupancy(int integrator, int with_time_flag, int spin_zero_flag, int shell_flag) {
+extern "C" int bl_geodesic_occupancy(const KernelPlan::Geodesic &plan) {
   int blocks = 0;
-  hipError_t err = hipSuccess;
-  const bool with_time = with_time_flag != 0, spin_zero = spin_zero_flag != 0, shell = shell_flag != 0;
-#define BL_OCCUPANCY_G(K) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, K, 64, 0)
-  switch (integrator) {
-    case BL_INTEGRATOR_DP: BL_GEODESIC_CASES(BL_INTEGRATOR_DP, BL_OCCUPANCY_G); break;
-    case BL_INTEGRATOR_RK4: BL_GEODESIC_CASES_FIXED_STEP(BL_INTEGRATOR_RK4, BL_OCCUPANCY_G); break;
-    default: BL_GEODESIC_CASES_FIXED_STEP(BL_INTEGRATOR_RK2, BL_OCCUPANCY_G); break;
-  }
-#undef BL_OCCUPANCY_G
-#undef BL_GEODESIC_CASES
-#undef BL_GEODESIC_CASES_FIXED_STEP
-  if (err != hipSuccess || blocks < 1) blocks = 4;
+  BlTraceKernel kernel = geodesic_kernel(plan);
+  if (kernel == nullptr || hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, 64, 0) != hipSuccess || blocks < 1) blocks = 4;
   return blocks;
 }
-

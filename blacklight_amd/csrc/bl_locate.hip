@@ -237,21 +237,28 @@ __global__ void __launch_bounds__(256, 4) bl_locate_plain_kernel(const BlShadeAr
 // =================================================================================================
 // Launch wrapper (called from bl_render.hip)
 // =================================================================================================
+// The locate kernels' instantiations, each named once. The common case has a kernel of its own (bl_locate_plain_kernel: same located
+// samples). The general kernel has one instantiation for any spin - bit for bit the same at a = 0, bl_geometry.h "zero spin": the paths
+// with zero spin known at compile time are the common ones, bl_locate_plain_kernel and the coefficient kernels with the locate step
+// inside. nullptr: no such instantiation (tables in HBM: a merged grid without slow light only).
+static void (*locate_kernel(const KernelPlan::Locate &l))(BlShadeArgs) {
+  if (l.kind == KernelPlan::Locate::kPlain) return l.spin_zero ? bl_locate_plain_kernel<true> : bl_locate_plain_kernel<false>;
+  if (l.kind != KernelPlan::Locate::kGeneral || l.spin_zero) return nullptr;
+  if (l.tables_in_hbm) return (l.refined || l.slow) ? nullptr : bl_locate_kernel<false, false, false, true>;
+  if (l.refined) return l.slow ? bl_locate_kernel<true, true, false> : bl_locate_kernel<true, false, false>;
+  return l.slow ? bl_locate_kernel<false, true, false> : bl_locate_kernel<false, false, false>;
+}
+
 // Locate kernel (simulation mode only); lds_bytes = size of the coordinate tables it stages in LDS
-extern "C" hipError_t bl_launch_locate(const BlShadeArgs *args, int grid, int lds_bytes, hipStream_t stream) {
-  const bool refined = args->grid.n_blocks > 0, slow = args->slow.n > 0;
-  const bool spin_zero = args->st.bh_a == 0.0;
-  // the common case has a kernel of its own (bl_locate_plain_kernel): same located samples
-  const bool plain = !refined && !slow && lds_bytes > 0 && !args->grid.fmks && args->plasma.simulation_interp && !args->cuts.any_optional
-      && args->plasma.simulation_coord == BL_COORD_SKS && args->anchors == nullptr && !args->general_locate;
-  if (plain) {
-    if (spin_zero) hipLaunchKernelGGL((bl_locate_plain_kernel<true>), dim3(grid), dim3(256), lds_bytes, stream, *args);
-    else hipLaunchKernelGGL((bl_locate_plain_kernel<false>), dim3(grid), dim3(256), lds_bytes, stream, *args);
-    return hipGetLastError();
-  }
-  // (one instantiation for any spin - bit for bit the same at a = 0, bl_geometry.h "zero spin": the paths with zero spin known at
-  // compile time are the common ones, bl_locate_plain_kernel above and the coefficient kernels with the locate step inside)
-  if (refined) {
+extern "C" hipError_t bl_launch_locate(const BlShadeArgs *args, const KernelPlan::Locate &plan, int grid, int lds_bytes, hipStream_t stream) {
+  void (*kernel)(BlShadeArgs) = locate_kernel(plan);
+  // (the block has to agree with the choice: the mesh, the time slices, where the tables are, zero spin; the plain kernel knows neither
+  // anchors nor the general search)
+  const bool plain = plan.kind == KernelPlan::Locate::kPlain;
+  if (kernel == nullptr || args->located == nullptr || plan.refined != (args->grid.n_blocks > 0) || plan.slow != (args->slow.n > 0)
+      || (plan.spin_zero && args->st.bh_a != 0.0) || (!plan.refined && plan.tables_in_hbm != (lds_bytes == 0))
+      || (plain && (plan.refined || plan.slow || args->anchors != nullptr || args->general_locate))) return hipErrorInvalidValue;
+  if (plan.refined) {
     // Tables that fit four times into a compute unit's LDS (36 KiB): 256-lane workgroups. Larger ones (up to BL_LOCATE_REFINED_LDS): one
     // 1 024-lane workgroup to a compute unit, one round of them. Beyond that the tables are searched where they lie in HBM
     // (refined_lds_bytes = 0). Behind the tables: the waves' lists of samples that wait for FindNearbyInds, 1 KiB each.
@@ -262,17 +269,13 @@ extern "C" hipError_t bl_launch_locate(const BlShadeArgs *args, int grid, int ld
     // (`grid` counts 256-lane workgroups: sixteen to a compute unit when the kernel runs alone - then one large workgroup per unit - or one
     // to a unit beside the next chunk's stepper - then as many lanes as that)
     const dim3 blocks(four_to_a_unit ? grid : (grid >= 1024 ? grid / 16 : (grid >= 4 ? grid / 4 : 1)));
-    const void *kernel = slow ? reinterpret_cast<const void *>(&bl_locate_kernel<true, true, false>) : reinterpret_cast<const void *>(&bl_locate_kernel<true, false, false>);
     if (bytes > 64 * 1024) {
-      const hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BL_LOCATE_REFINED_LDS + 16 * 1024);
+      const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BL_LOCATE_REFINED_LDS + 16 * 1024);
       if (err != hipSuccess) return err;
     }
-    if (slow) hipLaunchKernelGGL((bl_locate_kernel<true, true, false>), blocks, dim3(lanes), bytes, stream, *args);
-    else hipLaunchKernelGGL((bl_locate_kernel<true, false, false>), blocks, dim3(lanes), bytes, stream, *args);
+    hipLaunchKernelGGL(kernel, blocks, dim3(lanes), bytes, stream, *args);
+  } else {   // (a merged grid with tables beyond the LDS budget searches them in HBM: lds_bytes = 0)
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds_bytes, stream, *args);
   }
-  else if (lds_bytes == 0)   // merged grid with tables beyond the LDS budget (not with slow light: its instantiation needs them in LDS)
-    hipLaunchKernelGGL((bl_locate_kernel<false, false, false, true>), dim3(grid), dim3(256), 0, stream, *args);
-  else if (slow) hipLaunchKernelGGL((bl_locate_kernel<false, true, false>), dim3(grid), dim3(256), lds_bytes, stream, *args);
-  else hipLaunchKernelGGL((bl_locate_kernel<false, false, false>), dim3(grid), dim3(256), lds_bytes, stream, *args);
   return hipGetLastError();
 }

@@ -1045,16 +1045,13 @@ __global__ void __launch_bounds__(64, 2) bl_transfer_polarized_matrix_kernel(BlT
 
 // (the two halves apart: the matrices need the samples' geometry only and may be built beside the per-frequency coefficient kernel)
 extern "C" hipError_t bl_launch_transport_matrices(const BlTransferArgs *args, int num_cus, hipStream_t stream) {
+  if (args->pol_matrix == nullptr) return hipErrorInvalidValue;
   hipLaunchKernelGGL(bl_transport_matrix_kernel, dim3(num_cus * 2 * 4), dim3(256), 0, stream, *args);
   return hipGetLastError();
 }
 extern "C" hipError_t bl_launch_transfer_polarized_rays(const BlTransferArgs *args, hipStream_t stream) {
+  if (args->pol_matrix == nullptr) return hipErrorInvalidValue;
   const int grid = (int)(((long long)args->chunk_rays * (args->pol_variants > 0 ? args->pol_variants : 1) + 63) / 64);   // (the plan keeps the lanes below 2^31)
   hipLaunchKernelGGL(bl_transfer_polarized_matrix_kernel, dim3(grid), dim3(64), 0, stream, *args);
   return hipGetLastError();
-}
-extern "C" hipError_t bl_launch_transfer_polarized_matrix(const BlTransferArgs *args, int num_cus, hipStream_t stream) {
-  const hipError_t err = bl_launch_transport_matrices(args, num_cus, stream);
-  if (err != hipSuccess) return err;
-  return bl_launch_transfer_polarized_rays(args, stream);
 }

@@ -224,6 +224,7 @@ struct RenderJob {
   size_t redo_capacity = 0;
   // scratch
   ArrayUse use;
+  KernelPlan kernels;   // which instantiation every stage launches (PlanKernels)
   uint64_t bytes_per_record = 0;
   size_t record_capacity = 0;
   long long record_gate = 0;
@@ -270,6 +271,46 @@ struct RenderJob {
     std::vector<uint8_t> nan, fallback;     // [sample]
   } sampling;
 };
+
+// BLACKLIGHT_AMD_DEBUG_COUNTERS: every stage's choice as family name and template arguments, on one line
+std::string DescribeKernels(const KernelPlan &k) {
+  auto args = [](std::initializer_list<int> values) {
+    std::string text = "<";
+    for (int v : values) text += (text.size() > 1 ? "," : "") + std::to_string(v);
+    return text + ">";
+  };
+  const KernelPlan::Shade &c = k.shade;
+  std::string shade;
+  switch (c.family) {
+    case KernelPlan::Shade::kShade: shade = "shade" + args({c.model, c.aux, c.extended, c.sks, c.polarized, 0}); break;
+    case KernelPlan::Shade::kExact: shade = "exact" + args({c.spin_zero}); break;
+    case KernelPlan::Shade::kFast: shade = "fast" + args({c.spin_zero, c.mode}); break;
+    case KernelPlan::Shade::kFormulaFast: shade = "formula_fast"; break;
+    case KernelPlan::Shade::kFused2: shade = "fused2" + args({c.spin_zero, c.composed, c.factors, c.refined}); break;
+    case KernelPlan::Shade::kExact2: shade = "exact2" + args({c.spin_zero}); break;
+    case KernelPlan::Shade::kPolarized2: shade = "polarized2" + args({c.spin_zero, c.records, c.coefficients}); break;
+  }
+  const KernelPlan::Geodesic &g = k.geodesic;
+  static const char *const integrators[] = {"DP", "RK4", "RK2"};
+  static_assert(BL_INTEGRATOR_DP == 0 && BL_INTEGRATOR_RK4 == 1 && BL_INTEGRATOR_RK2 == 2, "integrator names");
+  std::string text = "shade=" + shade;
+  text += " redo=" + (k.redo.run ? args({k.redo.model, k.redo.extended, k.redo.sks, k.redo.spin_zero}) + "+" + std::to_string(k.redo.table_bytes) : std::string("none"));
+  if (k.freq.polarized_coefficients) text += " polarized_coefficients=" + args({0, k.freq.thermal_only});
+  if (k.freq.polarized_frames) text += " polarized_frames";
+  if (k.freq.coefficients_freq) text += " coefficients_freq=<1>";
+  static const char *const transfers[] = {"aux", "freq", "composed", "quad", "lane"};
+  text += std::string(" transfer=") + transfers[k.transfer.kind] + (k.transfer.kind == KernelPlan::Transfer::kLane ? args({k.transfer.affine}) : "") + (k.transfer.tau ? "+tau" : "");
+  static const char *const routes[] = {"", " polarized=tensor", " polarized=matrix", " polarized=matrices_beside"};
+  text += routes[k.polarized];
+  const KernelPlan::Locate &l = k.locate;
+  text += " locate=" + (l.kind == KernelPlan::Locate::kNone ? std::string("none")
+                        : l.kind == KernelPlan::Locate::kPlain ? "plain" + args({l.spin_zero}) : "general" + args({l.refined, l.slow, 0, l.tables_in_hbm}));
+  text += " geodesic=" + (g.source == KernelPlan::Geodesic::kResident ? std::string("none")
+                          : g.source == KernelPlan::Geodesic::kCheckpoint ? std::string("checkpoint")
+                          : std::string("<") + integrators[g.integrator > 2 || g.integrator < 0 ? 2 : g.integrator] + "," + std::to_string(g.with_time) + "," + std::to_string(g.spin_zero) + "," + std::to_string(g.shell) + ">");
+  if (k.quad.park || k.quad.split) text += std::string(k.quad.split ? " split+quad=" : " quad=") + args({k.quad.spin_zero});
+  return text;
+}
 
 hipEvent_t *SlotEvents(RenderJob &job, int k) { return job.ctx->events.data() + static_cast<size_t>(k) * kEventsPerChunk; }
 
@@ -472,26 +513,26 @@ void PlanJob(RenderJob &job) {
   const bool fused2_grid = ctx->grid_dev.n_blocks == 0
       ? ctx->lds_table_bytes > 0 && bl_fused2_applicable(&ctx->grid_dev, job.freq_split ? 1 : job.n_nu, job.n_rays) != 0
       : !job.freq_split && !records_every_sample && !job.skip_shell && bl_fused2_refined_applicable(&ctx->grid_dev, job.n_nu, job.n_rays) != 0;
-  job.fused2 = job.fast && !job.tau_row && !job.slow && fused2_grid && !ctx->grid_dev.fmks && p.simulation_interp && p.plasma_power_frac == 0.0
-      && p.simulation_coord == BL_COORD_SKS   // (its locate step is the spherical one: Cartesian grids go through the locate kernel)
-      && !GeometricCut(p)
-      && !job.sample_save && !(ctx->switches & (BL_SWITCH_NO_FUSED_LOCATE | BL_SWITCH_SPLIT_RECORDS))   // (a sample checkpoint is made of the located samples)
-      && !job.geo_load && !job.geo_save;  // (interleaved records whose momenta are not renormalised yet)
+  // What the three kernels with the locate step inside ask for alike: a simulation on a spherical Kerr-Schild grid (their locate step is
+  // the spherical one: Cartesian grids go through the locate kernel, FMKS grids too), trilinear sampling, one time slice, no optional
+  // geometric cut, no geodesic checkpoint loaded or saved (interleaved records whose momenta are not renormalised yet), no sample
+  // checkpoint (it is made of the located samples), neither measurement switch
+  const bool locate_inside_possible = job.simulation && !job.slow && !ctx->grid_dev.fmks && p.simulation_interp && p.simulation_coord == BL_COORD_SKS
+      && !GeometricCut(p) && !job.geo_load && !job.geo_save && !job.sample_save && !(ctx->switches & (BL_SWITCH_NO_FUSED_LOCATE | BL_SWITCH_SPLIT_RECORDS));
+  // (its own: the tolerant tier's scope - only this one reads job.fast, which leaves it plain images and so no sample times - without
+  // the optical-depth row and power-law electrons; it alone takes inter-block interpolation, which its grid predicate decides)
+  job.fused2 = locate_inside_possible && job.fast && !job.tau_row && fused2_grid && p.plasma_power_frac == 0.0;
   // The exact tier's plain image at one frequency over such a grid: the locate step inside bl_shade_exact2_kernel (bit-identical
-  // to bl_locate_plain_kernel + bl_shade_exact_kernel, whose conditions these are)
-  job.exact_fused = !job.fast && job.simulation && !job.aux && !ctx->polarized && !job.slow && !job.block_interp && job.n_nu == 1
+  // to bl_locate_plain_kernel + bl_shade_exact_kernel, whose conditions these are: job.fast's electrons, restated because it is off)
+  job.exact_fused = locate_inside_possible && !job.fast && !job.aux && !ctx->polarized && !job.block_interp && job.n_nu == 1
       && p.plasma_kappa_frac == 0.0 && p.plasma_power_frac == 0.0 && p.plasma_model != BL_PLASMA_CODE_KAPPA && !p.ray_flat
-      && ctx->plasma_thermal_frac != 0.0 && !ctx->grid_dev.fmks && p.simulation_interp && p.simulation_coord == BL_COORD_SKS
-      && !GeometricCut(p)
-      && !job.geo_load && !job.geo_save && !job.sample_save && !(ctx->switches & (BL_SWITCH_NO_FUSED_LOCATE | BL_SWITCH_SPLIT_RECORDS))
+      && ctx->plasma_thermal_frac != 0.0
       && (ctx->grid_dev.n_blocks == 0 ? bl_fused2_applicable(&ctx->grid_dev, job.n_nu, job.n_rays) != 0 : bl_polarized2_refined_applicable(&ctx->grid_dev, job.n_rays) != 0);
   // Polarized runs over such a grid: the frame-and-inputs kernel with the locate step inside (bit-identical to bl_locate_plain_kernel +
   // bl_shade_kernel<polarized>, whose conditions these are; electron entropy from the grid is a ninth value it does not gather)
   // (... or a mesh with refinement whose tables the tolerant tier's fused kernel takes: the polarized kernel's locate step knows them too)
-  job.pol_fused = ctx->polarized && job.simulation && !job.slow && !job.block_interp && p.plasma_model != BL_PLASMA_CODE_KAPPA && !p.ray_flat
-      && !ctx->grid_dev.fmks && p.simulation_interp && p.simulation_coord == BL_COORD_SKS
-      && !GeometricCut(p)
-      && !job.geo_load && !job.geo_save && !job.sample_save && !job.need_time && !(ctx->switches & (BL_SWITCH_NO_FUSED_LOCATE | BL_SWITCH_SPLIT_RECORDS))
+  // (only this one tests need_time: its runs may carry auxiliary rows - image_time - which the other two exclude altogether)
+  job.pol_fused = locate_inside_possible && ctx->polarized && !job.block_interp && p.plasma_model != BL_PLASMA_CODE_KAPPA && !p.ray_flat && !job.need_time
       && (ctx->grid_dev.n_blocks == 0 ? bl_fused2_applicable(&ctx->grid_dev, 1, job.n_rays) != 0 : bl_polarized2_refined_applicable(&ctx->grid_dev, job.n_rays) != 0);
   job.interleaved = (job.fused2 || job.exact_fused || job.pol_fused || !job.simulation) && !job.geo_load && !job.geo_save && !job.sample_save && !(ctx->switches & BL_SWITCH_SPLIT_RECORDS);
   job.locate_inside = job.fused2 || job.exact_fused || job.pol_fused;
@@ -688,6 +729,7 @@ void KeepResident(RenderJob &job) {
   if (ctx->debug_counters)
     std::fprintf(stderr, "scratch plan: bytes_per_record %llu, record_capacity %zu, record_gate %lld, geo_grid %d, n_slots %d, arrays 0x%05x\n", static_cast<unsigned long long>(job.bytes_per_record),
                  job.record_capacity, job.record_gate, job.geo_grid, job.n_slots, job.use.Mask());
+  if (ctx->debug_counters) std::fprintf(stderr, "kernels: %s\n", DescribeKernels(job.kernels).c_str());
   if (job.keepable && !job.reuse) {
     res.valid = false;
     res.super_tiles = job.super_tiles;
@@ -946,6 +988,20 @@ bool XcdOrderApplies(const RenderJob &job) {
       && !job.reuse && !job.reuse_chunks && !job.kept && !job.geo_load && !job.geo_save && !job.sample_save && !job.park && !job.split_long;
 }
 
+// The geodesic stage's instantiation: decided here for PlanScratch - the persistent grid is sized by its occupancy - and for PlanKernels
+KernelPlan::Geodesic PlanGeodesicKernel(const RenderJob &job) {
+  const bl_ctx *ctx = job.ctx;
+  KernelPlan::Geodesic g;
+  g.source = job.reuse ? KernelPlan::Geodesic::kResident : (job.geo_load ? KernelPlan::Geodesic::kCheckpoint : KernelPlan::Geodesic::kStepper);
+  g.integrator = ctx->params.ray_integrator;
+  g.with_time = job.need_time;
+  // (zero spin at compile time - also true for -0.0 - in the Dormand-Prince stepper only: the fixed-step steppers run it through the
+  // general formulas, bit for bit the same; the empty shell: job.skip_shell asks for Dormand-Prince and no sample times)
+  g.spin_zero = g.integrator == BL_INTEGRATOR_DP && ctx->st.bh_a == 0.0;
+  g.shell = job.skip_shell;
+  return g;
+}
+
 // ---- scratch: what a sample record costs, how many fit, how many persistent waves trace rays into them
 void PlanScratch(RenderJob &job) {
   bl_ctx *ctx = job.ctx;
@@ -1000,7 +1056,7 @@ void PlanScratch(RenderJob &job) {
       if (available < budget) budget = available;
     }
   }
-  const int waves_per_cu = bl_geodesic_occupancy(p.ray_integrator, job.need_time ? 1 : 0, ctx->st.bh_a == 0.0 ? 1 : 0, job.skip_shell ? 1 : 0);
+  const int waves_per_cu = bl_geodesic_occupancy(PlanGeodesicKernel(job));
   // No more lanes than half the rays: a lane that traces one ray only leaves its wave idling behind the longest of 64 rays, and
   // with fewer waves per SIMD each of them is faster - an eighth of the benchmark frame (131 072 rays) takes 4.3 ms on 1 024 waves,
   // 4.7 to 5.3 ms on 2 048 (and the coefficient kernel 5.0 instead of 5.2 ms over the more compact records)
@@ -1093,6 +1149,106 @@ void PlanScratch(RenderJob &job) {
     job.quad_grid = job.split_cus * 4;
   }
   if (job.n_slots != 1 || job.park || job.split_long) job.xcd_order = false;
+}
+
+// ---- which kernels: the one place where the plan's flags turn into template arguments (KernelPlan, bl_kernel_plan.h). Runs behind the
+// plan, the scratch decision and UsedArrays, so that it sees what they dropped; reads flags and parameters, never the argument blocks'
+// pointers - those follow from job.use, and the launch wrappers check that they agree with what is chosen here.
+void PlanKernels(RenderJob &job) {
+  const bl_ctx *ctx = job.ctx;
+  const bl_params &p = ctx->params;
+  const ArrayUse &use = job.use;
+  KernelPlan &k = job.kernels;
+  k = KernelPlan{};
+  const bool spin_zero = ctx->st.bh_a == 0.0;
+  const bool refined = job.simulation && ctx->grid_dev.n_blocks > 0;
+  const bool slices = job.slow && p.slow_chunk_size > 0;
+  const bool sks = p.simulation_coord != BL_COORD_CKS;   // (FMKS: everything but the cell search treats the grid as sks, BuildShadeArgs)
+  const bool power_law = job.simulation && p.plasma_power_frac != 0.0;
+  k.geodesic = PlanGeodesicKernel(job);
+  k.quad.park = job.park;
+  k.quad.split = job.split_long;
+  k.quad.spin_zero = spin_zero;
+  if (job.simulation && !job.locate_inside && !job.reuse_located) {
+    // the common case has a kernel of its own: one grid with its tables in LDS, spherical, trilinear, no optional geometric cut
+    const bool plain = !refined && !slices && ctx->lds_table_bytes > 0 && !ctx->grid_dev.fmks && p.simulation_interp && !GeometricCut(p) && sks
+        && !use.anchors && !(ctx->switches & BL_SWITCH_GENERAL_LOCATE);
+    k.locate.kind = plain ? KernelPlan::Locate::kPlain : KernelPlan::Locate::kGeneral;
+    k.locate.spin_zero = plain && spin_zero;
+    k.locate.refined = refined;
+    k.locate.slow = slices;
+    k.locate.tables_in_hbm = !plain && !refined && ctx->lds_table_bytes == 0;
+  }
+  KernelPlan::Shade &c = k.shade;
+  c.model = p.model_type;
+  if (job.fused2) {
+    c.family = KernelPlan::Shade::kFused2;
+    c.spin_zero = spin_zero;
+    c.refined = refined;   // (a mesh: one frequency and composed maps, PlanJob - the wrapper refuses anything else)
+    c.factors = job.freq_split;
+    c.composed = job.composed;
+  } else if (job.fast) {
+    // power laws, Cartesian grids and an optical-depth image go through the general instantiation; inter-block interpolation and slow
+    // light through the ones that also know anchor cells and time slices
+    c.family = KernelPlan::Shade::kFast;
+    c.mode = slices ? 3 : (use.anchors ? 2 : ((power_law || job.tau_row || !sks) ? 1 : 0));
+    c.spin_zero = c.mode == 0 && spin_zero;
+  } else if (job.fast_formula) {
+    c.family = KernelPlan::Shade::kFormulaFast;
+  } else if (job.exact_fused) {
+    c.family = KernelPlan::Shade::kExact2;
+    c.spin_zero = spin_zero;
+  } else if (job.pol_fused) {
+    c.family = KernelPlan::Shade::kPolarized2;
+    c.spin_zero = spin_zero;
+    c.records = !job.rows_only;
+    c.coefficients = job.pol_coefficients_inside;
+  } else if (!job.simulation) {
+    c.aux = use.aux;
+  } else {
+    const bool sks_curved = sks && !ctx->st.ray_flat;
+    c.polarized = ctx->polarized;
+    c.aux = ctx->polarized || use.aux;   // (a polarized run is an auxiliary-image run whether or not it keeps BlAuxSample records)
+    c.extended = ctx->polarized || power_law || p.plasma_model == BL_PLASMA_CODE_KAPPA || slices || use.anchors || p.plasma_kappa_frac != 0.0;
+    c.sks = ctx->polarized && sks_curved;
+    // plain image of a spherical Kerr-Schild simulation in a curved spacetime: the software-pipelined kernel
+    if (!c.aux && !c.extended && sks_curved) {
+      c.family = KernelPlan::Shade::kExact;
+      c.spin_zero = spin_zero;
+    }
+  }
+  if (job.fast || job.fast_formula) {   // the exact second pass over the records the tolerant kernel listed
+    KernelPlan::Redo &r = k.redo;
+    r.run = true;
+    r.model = p.model_type;
+    if (job.simulation) {
+      // (behind the fused kernel the extended instantiation is the one that knows the anchor cells of inter-block interpolation)
+      r.extended = job.fused2 ? job.block_interp : (!sks || power_law || job.tau_row || use.anchors || slices);
+      r.sks = job.fused2 || sks;
+      r.spin_zero = !r.extended && spin_zero;
+      const int tables = ctx->grid_dev.refined_lds_bytes;   // (the mesh's tables in LDS, if they are small enough)
+      r.table_bytes = (r.extended && job.fused2 && refined && tables > 0 && tables <= BL_REDO_TABLES_LDS) ? tables : 0;
+    }
+  }
+  k.freq.polarized_frames = ctx->polarized;
+  k.freq.polarized_coefficients = ctx->polarized && !job.pol_coefficients_inside;
+  k.freq.thermal_only = ctx->polarized && p.plasma_power_frac == 0.0 && p.plasma_kappa_frac == 0.0;
+  k.freq.coefficients_freq = job.coef_split;
+  k.transfer.affine = job.fast || job.fast_formula;
+  k.transfer.tau = job.tau_row;
+  k.transfer.kind = job.aux ? KernelPlan::Transfer::kAux
+      : job.freq_split ? KernelPlan::Transfer::kFreq
+      : job.composed ? KernelPlan::Transfer::kComposed
+      : (k.transfer.affine && job.n_nu == 1 && !(ctx->switches & BL_SWITCH_LANE_TRANSFER)) ? KernelPlan::Transfer::kQuad : KernelPlan::Transfer::kLane;
+  // The transport matrices - memory - on the second stream beside the per-frequency coefficient kernel - arithmetic: both read what
+  // the coefficient kernel left, neither reads the other. (The coefficient kernel's workgroups fill the device first, so the
+  // matrices overlap its last quarter only: 276 -> 270 ms per 1024^2 frame, 1.10 -> 1.08 s at 2048^2 adaptive; a smaller grid for the
+  // coefficient kernel or a priority stream for the matrices move the split, not the sum.)
+  // (one scratch set: with two, the second stream carries the next chunk's geodesic stage, and the matrices would queue behind it)
+  // (with the coefficients evaluated inside the coefficient kernel there is nothing left beside which to build them: in sequence)
+  if (ctx->polarized)
+    k.polarized = !job.matrix_transport ? KernelPlan::kTensor
+        : (job.n_slots == 1 && !job.pol_coefficients_inside) ? KernelPlan::kMatricesBeside : KernelPlan::kMatrix;
 }
 
 void EnsureScratchOnce(RenderJob &job);
@@ -2118,11 +2274,11 @@ void LaunchGeodesicStage(RenderJob &job, int k, long long begin, int rays, hipSt
   job.in_flight[k].begin = begin;
   job.in_flight[k].rays = rays;
   job.in_flight[k].done = -1;
-  if (job.geo_load) {
+  if (job.kernels.geodesic.source == KernelPlan::Geodesic::kCheckpoint) {
     Check(hipStreamSynchronize(stream_geo), "kernel execution");   // the counters are reset before the host writes two of them
     job.in_flight[k].done = LoadChunkFromCheckpoint(job, k, begin, rays);
   } else {
-    if (job.split_long) {
+    if (job.kernels.quad.split) {
       // the band's rays parked; then the two steppers side by side on disjoint compute units, and the stage ends with both
       hipEvent_t *ev = SlotEvents(job, k);
       Check(bl_launch_split_long(&job.ta, stream_geo), "split kernel launch");
@@ -2133,16 +2289,16 @@ void LaunchGeodesicStage(RenderJob &job, int k, long long begin, int rays, hipSt
       const int per_simd = std::max(1, (std::min(job.geo_grid, (rays + 63) / 64) + ctx->num_cus * 4 - 1) / (ctx->num_cus * 4));
       const int wide_grid = std::min(std::min(job.geo_grid, (rays + 63) / 64), (ctx->num_cus - job.split_cus) * 4 * per_simd);
       const int pad = per_simd == 1 ? ctx->split_lds_pad : 0;
-      Check(bl_launch_geodesic(&job.ta, ctx->params.ray_integrator, std::max(wide_grid, 1), ctx->stream_most, pad), "geodesic kernel launch");
-      Check(bl_launch_geodesic_quad(&job.ta, job.quad_grid, ctx->stream_few, ctx->split_lds_pad), "geodesic quad kernel launch");
+      Check(bl_launch_geodesic(&job.ta, job.kernels.geodesic, std::max(wide_grid, 1), ctx->stream_most, pad), "geodesic kernel launch");
+      Check(bl_launch_geodesic_quad(&job.ta, job.kernels.quad, job.quad_grid, ctx->stream_few, ctx->split_lds_pad), "geodesic quad kernel launch");
       Check(hipEventRecord(ev[8], ctx->stream_most), "event");
       Check(hipEventRecord(ev[9], ctx->stream_few), "event");
       Check(hipStreamWaitEvent(stream_geo, ev[8], 0), "stream wait");
       Check(hipStreamWaitEvent(stream_geo, ev[9], 0), "stream wait");
     } else
-    Check(bl_launch_geodesic(&job.ta, ctx->params.ray_integrator, std::min(job.geo_grid, (rays + 63) / 64), stream_geo, 0), "geodesic kernel launch");
+    Check(bl_launch_geodesic(&job.ta, job.kernels.geodesic, std::min(job.geo_grid, (rays + 63) / 64), stream_geo, 0), "geodesic kernel launch");
     // the rays it parked, sixteen to a wave, a wave per SIMD (waves that find none end at once)
-    if (job.park) Check(bl_launch_geodesic_quad(&job.ta, job.quad_grid, stream_geo, 0), "geodesic quad kernel launch");
+    if (job.kernels.quad.park) Check(bl_launch_geodesic_quad(&job.ta, job.kernels.quad, job.quad_grid, stream_geo, 0), "geodesic quad kernel launch");
   }
   Check(hipEventRecord(e[1], stream_geo), "event");
 }
@@ -2156,19 +2312,29 @@ void LaunchShadingStage(RenderJob &job, int k, bool geodesic_beside, hipStream_t
   BindChunk(job, k, job.in_flight[k].begin, job.in_flight[k].rays);
   BlShadeArgs &sa = job.sa;
   BlTransferArgs &xa = job.xa;
+  const KernelPlan &plan = job.kernels;
   auto coefficient_kernel = [&]() {
     // (the list walk's cursors: every pass of the coefficient kernel walks the lists from their starts)
     if (sa.xcd_state != nullptr) Check(hipMemsetAsync(sa.xcd_state + 2 * BL_XCD_QUEUES, 0, BL_XCD_QUEUES * sizeof(unsigned long long), stream), "counter reset");
-    if (job.fast) Check(bl_launch_shade_fast(&sa, job.shade_grid, stream), "coefficient kernel launch");
-    else if (job.fast_formula) Check(bl_launch_shade_formula_fast(&sa, ctx->num_cus * 4 * 4, stream), "coefficient kernel launch");
-    else if (job.exact_fused) Check(bl_launch_shade_exact2(&sa, job.shade_grid, stream), "coefficient kernel launch");
-    else if (job.pol_fused) Check(bl_launch_shade_polarized2(&sa, job.shade_grid, stream), "coefficient kernel launch");
-    else Check(bl_launch_shade(&sa, p.model_type, job.shade_grid, stream), "coefficient kernel launch");
+    hipError_t err = hipErrorInvalidValue;
+    switch (plan.shade.family) {
+      case KernelPlan::Shade::kShade:
+      case KernelPlan::Shade::kExact: err = bl_launch_shade(&sa, plan.shade, job.shade_grid, stream); break;
+      case KernelPlan::Shade::kFast: err = bl_launch_shade_fast(&sa, plan.shade, job.shade_grid, stream); break;
+      case KernelPlan::Shade::kFormulaFast: err = bl_launch_shade_formula_fast(&sa, ctx->num_cus * 4 * 4, stream); break;
+      case KernelPlan::Shade::kFused2: err = bl_launch_shade_fused2(&sa, plan.shade, job.shade_grid, stream); break;
+      case KernelPlan::Shade::kExact2: err = bl_launch_shade_exact2(&sa, plan.shade, job.shade_grid, stream); break;
+      case KernelPlan::Shade::kPolarized2: err = bl_launch_shade_polarized2(&sa, plan.shade, job.shade_grid, stream); break;
+    }
+    Check(err, "coefficient kernel launch");
+    // (the exact tier's kernel over the records the tolerant kernel deferred)
+    if (plan.redo.run)
+      Check(bl_launch_shade_redo(&sa, plan.redo, plan.shade.family == KernelPlan::Shade::kFormulaFast ? ctx->num_cus * 4 * 4 : job.shade_grid, stream), "coefficient kernel launch");
   };
   Check(hipStreamWaitEvent(stream, e[1], 0), "stream wait");
   Check(hipEventRecord(e[2], stream), "event");
-  if (job.simulation && !job.locate_inside && !job.reuse_located)
-    Check(bl_launch_locate(&sa, geodesic_beside ? job.locate_grid_shared : job.locate_grid_alone, ctx->lds_table_bytes, stream), "locate kernel launch");
+  if (plan.locate.kind != KernelPlan::Locate::kNone)
+    Check(bl_launch_locate(&sa, plan.locate, geodesic_beside ? job.locate_grid_shared : job.locate_grid_alone, ctx->lds_table_bytes, stream), "locate kernel launch");
   Check(hipEventRecord(e[3], stream), "event");
   for (int v = 0; v < job.variant_passes; v++) {
     if (v > 0) {   // what the shading stage adds to the chunk's counters starts again from zero (ClearShadingCounters)
@@ -2179,35 +2345,31 @@ void LaunchShadingStage(RenderJob &job, int k, bool geodesic_beside, hipStream_t
     }
     BindVariant(job, v);
     coefficient_kernel();
-    // The transport matrices - memory - on the second stream beside the per-frequency coefficient kernel - arithmetic: both read what
-    // bl_shade_polarized2_kernel left, neither reads the other. (The coefficient kernel's workgroups fill the device first, so the
-    // matrices overlap its last quarter only: 276 -> 270 ms per 1024^2 frame, 1.10 -> 1.08 s at 2048^2 adaptive; a smaller grid for the
-    // coefficient kernel or a priority stream for the matrices move the split, not the sum. BLACKLIGHT_AMD_POLARIZED_OVERLAP=0: in sequence.)
-    // (one scratch set: with two, the second stream carries the next chunk's geodesic stage, and the matrices would queue behind it)
-    // (with the coefficients evaluated inside the coefficient kernel there is nothing left beside which to build them: in sequence)
-    const bool matrices_beside = ctx->polarized && job.matrix_transport && job.n_slots == 1 && ctx->stream_geo != stream && !job.pol_coefficients_inside;
+    // (the shading stream is never the context's second one: KernelPlan::kMatricesBeside builds the matrices there, PlanKernels)
+    const bool matrices_beside = plan.polarized == KernelPlan::kMatricesBeside;
     const int polcoef_grid = ctx->num_cus * 20;
     if (matrices_beside) {
       // (the frames of the samples without coefficients first: the matrices read them)
-      Check(bl_launch_polarized_coefficients_parts(&sa, polcoef_grid, 2, stream), "polarized frame kernel launch");
+      Check(bl_launch_polarized_frames(&sa, polcoef_grid, stream), "polarized frame kernel launch");
       Check(hipEventRecord(e[10], stream), "event");
       Check(hipStreamWaitEvent(ctx->stream_geo, e[10], 0), "stream wait");
       Check(bl_launch_transport_matrices(&xa, ctx->num_cus, ctx->stream_geo), "transport matrix kernel launch");
       Check(hipEventRecord(e[11], ctx->stream_geo), "event");
     }
-    if (ctx->polarized) Check(bl_launch_polarized_coefficients_parts(&sa, polcoef_grid, job.pol_coefficients_inside ? 2 : (matrices_beside ? 0 : 1), stream), "polarized coefficient kernel launch");
-    if (job.coef_split) Check(bl_launch_coefficients_freq(&sa, ctx->num_cus * 16, stream), "per-frequency coefficient kernel launch");
+    if (plan.freq.polarized_coefficients) Check(bl_launch_polarized_coefficients(&sa, plan.freq, polcoef_grid, stream), "polarized coefficient kernel launch");
+    if (plan.freq.polarized_frames && !matrices_beside) Check(bl_launch_polarized_frames(&sa, polcoef_grid, stream), "polarized frame kernel launch");
+    if (plan.freq.coefficients_freq) Check(bl_launch_coefficients_freq(&sa, ctx->num_cus * 16, stream), "per-frequency coefficient kernel launch");
     Check(hipEventRecord(e[4], stream), "event");
-    Check(job.aux ? bl_launch_transfer_aux(&xa, stream)
-                  : (job.freq_split ? bl_launch_transfer_freq(&xa, stream) : (job.composed ? bl_launch_transfer_composed(&xa, stream) : bl_launch_transfer(&xa, stream))),
-          "transfer kernel launch");
-    if (job.tau_row) Check(bl_launch_tau(&xa, stream), "optical-depth kernel launch");
-    if (ctx->polarized && matrices_beside) {
-      Check(hipStreamWaitEvent(stream, e[11], 0), "stream wait");
-      Check(bl_launch_transfer_polarized_rays(&xa, stream), "polarized transfer kernel launch");
-    } else if (ctx->polarized) {
-      Check(job.matrix_transport ? bl_launch_transfer_polarized_matrix(&xa, ctx->num_cus, stream) : bl_launch_transfer_polarized(&xa, stream),
-            "polarized transfer kernel launch");
+    Check(bl_launch_transfer(&xa, plan.transfer, stream), "transfer kernel launch");
+    if (plan.transfer.tau) Check(bl_launch_tau(&xa, stream), "optical-depth kernel launch");
+    switch (plan.polarized) {
+      case KernelPlan::kUnpolarized: break;
+      case KernelPlan::kTensor: Check(bl_launch_transfer_polarized(&xa, stream), "polarized transfer kernel launch"); break;
+      case KernelPlan::kMatrix: Check(bl_launch_transport_matrices(&xa, ctx->num_cus, stream), "polarized transfer kernel launch");   // fall through
+      case KernelPlan::kMatricesBeside:
+        if (matrices_beside) Check(hipStreamWaitEvent(stream, e[11], 0), "stream wait");
+        Check(bl_launch_transfer_polarized_rays(&xa, stream), "polarized transfer kernel launch");
+        break;
     }
   }
   Check(hipEventRecord(e[5], stream), "event");
@@ -2307,7 +2469,7 @@ void RunChunks(RenderJob &job) {
     job.chunk_segment = 0;
     job.chunk_base = 0;
     BindChunk(job, 0, 0, static_cast<int>(job.n_rays));
-    if (job.cam_pos != nullptr || job.cam_dir != nullptr) Check(bl_launch_ray_init(&job.ta, ctx->params.ray_integrator, stream), "ray start kernel launch");
+    if (job.cam_pos != nullptr || job.cam_dir != nullptr) Check(bl_launch_ray_init(&job.ta, job.kernels.geodesic, stream), "ray start kernel launch");
     const size_t n_kept = job.reuse_chunks ? res.chunks.size() : 1;
     for (size_t c = 0; c < n_kept; c++) {
       const long long begin = job.reuse_chunks ? res.chunks[c].begin : 0;
@@ -2344,7 +2506,7 @@ void RunChunks(RenderJob &job) {
   if (!job.geo_load) {
     // start states of every ray of the call, once (bl_ray_init_kernel; the geodesic kernel of each chunk reads its share)
     BindChunk(job, 0, 0, static_cast<int>(job.n_rays));
-    Check(bl_launch_ray_init(&job.ta, ctx->params.ray_integrator, stream_geo), "ray start kernel launch");
+    Check(bl_launch_ray_init(&job.ta, job.kernels.geodesic, stream_geo), "ray start kernel launch");
   }
   const long long n_rays = job.n_rays;
   auto no_progress = []() {
@@ -2500,8 +2662,9 @@ void FinishStats(RenderJob &job) {
   bl_stats st{};
   st.n_rays = job.n_rays;
   st.n_chunks = job.n_chunks;
-  st.launches_geodesic = job.reuse ? 0 : job.n_chunks;
-  st.launches_locate = (job.simulation && !job.locate_inside && !job.reuse_located) ? job.n_chunks : 0;
+  const KernelPlan &plan = job.kernels;
+  st.launches_geodesic = plan.geodesic.source == KernelPlan::Geodesic::kResident ? 0 : job.n_chunks;
+  st.launches_locate = plan.locate.kind != KernelPlan::Locate::kNone ? job.n_chunks : 0;
   st.geodesics_reused = job.reuse ? 1 : 0;
   st.sampling_reused = job.reuse_located ? 1 : 0;
   st.launches_shade = job.n_chunks * job.variant_passes;   // (polarized variants in one pass: the coefficient kernel once per chunk)
@@ -2525,7 +2688,7 @@ void FinishStats(RenderJob &job) {
   st.n_deferred = static_cast<int64_t>(job.total_redo);
   st.n_undefined = static_cast<int64_t>(job.total_undefined);
   st.switches = ctx->switches;
-  st.fused_variant = job.fused2 ? 2 : (job.exact_fused ? 3 : (job.pol_fused ? 4 : 0));
+  st.fused_variant = plan.shade.family == KernelPlan::Shade::kFused2 ? 2 : (plan.shade.family == KernelPlan::Shade::kExact2 ? 3 : (plan.shade.family == KernelPlan::Shade::kPolarized2 ? 4 : 0));
   st.n_parked = static_cast<int64_t>(job.reuse ? ctx->resident.n_parked : job.total_parked);
   st.composed_maps = job.composed ? 1 : 0;
   st.xcd_order = job.xcd_order ? 1 : 0;
@@ -2647,6 +2810,7 @@ extern "C" int bl_render(bl_ctx *ctx, const bl_render_desc *d) {
           job.quad_grid = 0;
         }
         job.use = UsedArrays(job);   // (less what the plan dropped: one pass over the polarized variants, the order per XCD, parked rays)
+        PlanKernels(job);
         EnsureScratch(job);
         StageInputsAndOutputs(job);
         BuildTraceArgs(job);

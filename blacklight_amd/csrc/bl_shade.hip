@@ -397,61 +397,62 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact_kernel(const BlShadeArg
 // =================================================================================================
 // Launch wrappers (called from bl_render.hip)
 // =================================================================================================
-// Coefficient kernel
-extern "C" hipError_t bl_launch_shade(const BlShadeArgs *args, int model, int grid, hipStream_t stream) {
-  const bool aux = args->aux != nullptr;
-  const bool power = args->plasma.power_frac != 0.0 || args->plasma.code_kappa != 0 || args->slow.n > 0 || args->pol_samples != nullptr
-      || args->anchors != nullptr || args->plasma.kappa_unpolarized != 0;
-  // the benchmark path - plain image of a spherical Kerr-Schild simulation in a curved spacetime - has its own
-  // instantiation with those two facts known at compile time (62.4 instead of 64.4 ms per 1024^2 frame)
-  const bool sks_curved = args->plasma.simulation_coord == BL_COORD_SKS && !args->st.ray_flat;
-  const bool spin_zero = args->st.bh_a == 0.0;
-#define BL_LAUNCH_S(M, A, W) hipLaunchKernelGGL((bl_shade_kernel<M, A, W, false, false, false>), dim3(grid), dim3(256), 0, stream, *args)
-  if (model == BL_MODEL_SIMULATION) {
-    // (a polarized run is an auxiliary-image run whether or not it keeps BlAuxSample records: BlShadeArgs::aux_record_unused)
-    // polarized run: frame and coefficient inputs per sample, no frequency loop (the grids bl_shade_polarized2_kernel does not take)
-    if (args->pol_samples != nullptr && sks_curved)
-      hipLaunchKernelGGL((bl_shade_kernel<BL_MODEL_SIMULATION, true, true, true, true, false>), dim3(grid), dim3(256), 0, stream, *args);
-    else if (args->pol_samples != nullptr)
-      hipLaunchKernelGGL((bl_shade_kernel<BL_MODEL_SIMULATION, true, true, false, true, false>), dim3(grid), dim3(256), 0, stream, *args);
-    else if (aux && power) BL_LAUNCH_S(BL_MODEL_SIMULATION, true, true);
-    else if (aux) BL_LAUNCH_S(BL_MODEL_SIMULATION, true, false);
-    else if (power) BL_LAUNCH_S(BL_MODEL_SIMULATION, false, true);
-    else if (sks_curved) {   // plain image of a spherical Kerr-Schild simulation in a curved spacetime: the software-pipelined kernel
-      if (spin_zero) hipLaunchKernelGGL((bl_shade_exact_kernel<true>), dim3(grid), dim3(256), 0, stream, *args);
-      else hipLaunchKernelGGL((bl_shade_exact_kernel<false>), dim3(grid), dim3(256), 0, stream, *args);
-    }
-    else BL_LAUNCH_S(BL_MODEL_SIMULATION, false, false);
-  } else {
-    if (aux) BL_LAUNCH_S(BL_MODEL_FORMULA, true, false);
-    else BL_LAUNCH_S(BL_MODEL_FORMULA, false, false);
+using BlShadeKernel = void (*)(BlShadeArgs);
+
+// bl_shade_kernel's instantiations of the first pass and bl_shade_exact_kernel's, each named once. nullptr: no such instantiation.
+//   - polarized runs (the grids bl_shade_polarized2_kernel does not take): frame and coefficient inputs per sample, no frequency loop;
+//     auxiliary-image runs whether or not they keep BlAuxSample records (BlShadeArgs::aux_record_unused), extended, sks known or not
+//   - the benchmark path of the exact tier - plain image of a spherical Kerr-Schild simulation in a curved spacetime, thermal
+//     electrons - is the software-pipelined bl_shade_exact_kernel (62.4 instead of 64.4 ms per 1024^2 frame)
+//   - formula mode: plain or auxiliary
+static BlShadeKernel shade_kernel(const KernelPlan::Shade &c) {
+  constexpr int kSim = BL_MODEL_SIMULATION, kFormula = BL_MODEL_FORMULA;
+  if (c.family == KernelPlan::Shade::kExact) return c.spin_zero ? bl_shade_exact_kernel<true> : bl_shade_exact_kernel<false>;
+  if (c.family != KernelPlan::Shade::kShade || c.spin_zero) return nullptr;
+  if (c.polarized) {
+    if (c.model != kSim || !c.aux || !c.extended) return nullptr;
+    return c.sks ? bl_shade_kernel<kSim, true, true, true, true, false> : bl_shade_kernel<kSim, true, true, false, true, false>;
   }
-#undef BL_LAUNCH_S
+  if (c.sks) return nullptr;
+  if (c.model == kFormula) {
+    if (c.extended) return nullptr;
+    return c.aux ? bl_shade_kernel<kFormula, true, false, false, false, false> : bl_shade_kernel<kFormula, false, false, false, false, false>;
+  }
+  if (c.aux) return c.extended ? bl_shade_kernel<kSim, true, true, false, false, false> : bl_shade_kernel<kSim, true, false, false, false, false>;
+  return c.extended ? bl_shade_kernel<kSim, false, true, false, false, false> : bl_shade_kernel<kSim, false, false, false, false, false>;
+}
+
+// Coefficient kernel
+extern "C" hipError_t bl_launch_shade(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream) {
+  BlShadeKernel kernel = shade_kernel(plan);
+  const bool simulation = plan.model == BL_MODEL_SIMULATION;
+  if (kernel == nullptr || (simulation && args->located == nullptr) || (plan.spin_zero && args->st.bh_a != 0.0)
+      || plan.polarized != (args->pol_samples != nullptr) || (!plan.polarized && plan.aux != (args->aux != nullptr))
+      || (!plan.extended && (args->anchors != nullptr || args->slow.n > 0))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, *args);
   return hipGetLastError();
 }
 
-// Second pass of the tolerant tier (bl_shade_fast.hip launches it behind its kernels): bl_shade_kernel<..., kRedo> over the records
-// the tolerant kernel listed. Its extended instantiation knows power laws, its general one Cartesian grids.
-extern "C" hipError_t bl_launch_shade_redo(const BlShadeArgs *args, int model, int grid, hipStream_t stream) {
-  if (model == BL_MODEL_FORMULA) {
-    hipLaunchKernelGGL((bl_shade_kernel<BL_MODEL_FORMULA, false, false, false, false, false, true>), dim3(grid), dim3(256), 0, stream, *args);
-    return hipGetLastError();
-  }
-  const bool spin_zero = args->st.bh_a == 0.0;
-  const bool fused = args->located == nullptr;
-  const bool cartesian = !fused && args->plasma.simulation_coord == BL_COORD_CKS;
-  // (the extended instantiation; behind the fused kernel it is the one that knows the anchor cells of inter-block interpolation)
-  const bool power_law = fused ? args->grid.block_interp != 0
-                               : (args->plasma.power_frac != 0.0 || args->tau_inc != nullptr || args->anchors != nullptr || args->slow.n > 0);
-  // (the common case - behind a kernel with the locate step inside - knows zero spin at compile time)
-  // (behind the fused kernel over a mesh with inter-block interpolation: room for the mesh's tables in LDS, if they are small enough)
-  const size_t tables = (fused && args->grid.n_blocks > 0 && args->grid.refined_lds_bytes > 0 && args->grid.refined_lds_bytes <= BL_REDO_TABLES_LDS)
-      ? (size_t)args->grid.refined_lds_bytes : 0;
-#define BL_LAUNCH_R(EXTENDED, SKS) hipLaunchKernelGGL((bl_shade_kernel<BL_MODEL_SIMULATION, false, EXTENDED, SKS, false, false, true>), dim3(grid), dim3(256), (EXTENDED) ? tables : 0, stream, *args)
-  if (cartesian) BL_LAUNCH_R(true, false);
-  else if (power_law) BL_LAUNCH_R(true, true);
-  else if (spin_zero) hipLaunchKernelGGL((bl_shade_kernel<BL_MODEL_SIMULATION, false, false, true, false, true, true>), dim3(grid), dim3(256), 0, stream, *args);
-  else BL_LAUNCH_R(false, true);
-#undef BL_LAUNCH_R
+// Second pass of the tolerant tier (launched behind its kernels): bl_shade_kernel<..., kRedo> over the records the tolerant kernel
+// listed. Its extended instantiation knows power laws and, behind the fused kernel, the anchor cells of inter-block interpolation; its
+// general one Cartesian grids; the common case - behind a kernel with the locate step inside - knows zero spin at compile time.
+static BlShadeKernel shade_redo_kernel(const KernelPlan::Redo &r) {
+  constexpr int kSim = BL_MODEL_SIMULATION;
+  if (r.model == BL_MODEL_FORMULA)
+    return (r.extended || r.sks || r.spin_zero) ? nullptr : bl_shade_kernel<BL_MODEL_FORMULA, false, false, false, false, false, true>;
+  if (r.extended) return r.spin_zero ? nullptr : (r.sks ? bl_shade_kernel<kSim, false, true, true, false, false, true> : bl_shade_kernel<kSim, false, true, false, false, false, true>);
+  if (!r.sks) return nullptr;
+  return r.spin_zero ? bl_shade_kernel<kSim, false, false, true, false, true, true> : bl_shade_kernel<kSim, false, false, true, false, false, true>;
+}
+
+extern "C" hipError_t bl_launch_shade_redo(const BlShadeArgs *args, const KernelPlan::Redo &plan, int grid, hipStream_t stream) {
+  BlShadeKernel kernel = shade_redo_kernel(plan);
+  // (table_bytes: behind the fused kernel over a mesh with inter-block interpolation, room for the mesh's tables in LDS - the kernel
+  // looks for them there under the same condition)
+  const bool tables_fit = args->located == nullptr && args->grid.n_blocks > 0 && args->grid.refined_lds_bytes > 0 && args->grid.refined_lds_bytes <= BL_REDO_TABLES_LDS;
+  if (!plan.run || kernel == nullptr || args->redo_list == nullptr || (plan.spin_zero && args->st.bh_a != 0.0)
+      || plan.table_bytes != (plan.extended && tables_fit ? args->grid.refined_lds_bytes : 0)
+      || (!plan.extended && (args->tau_inc != nullptr || args->anchors != nullptr || args->slow.n > 0))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), (size_t)plan.table_bytes, stream, *args);
   return hipGetLastError();
 }

@@ -578,37 +578,36 @@ __global__ void __launch_bounds__(256, 4) bl_shade_formula_fast_kernel(const BlS
 // =================================================================================================
 // Launch wrappers (called from bl_render.hip)
 // =================================================================================================
-// The exact tier's kernel over the records a tolerant kernel deferred (bl_shade.hip)
-extern "C" hipError_t bl_launch_shade_redo(const BlShadeArgs *args, int model, int grid, hipStream_t stream);
-extern "C" hipError_t bl_launch_shade_fused2(const BlShadeArgs *args, int grid, hipStream_t stream);   // bl_shade_fused.hip
-
-// Tolerant tier in formula mode: the fast kernel, then the exact kernel over the records it deferred
+// Tolerant tier in formula mode: the fast kernel; the exact kernel over the records it deferred follows (bl_launch_shade_redo)
 extern "C" hipError_t bl_launch_shade_formula_fast(const BlShadeArgs *args, int grid, hipStream_t stream) {
+  if (args->redo_list == nullptr) return hipErrorInvalidValue;
   hipLaunchKernelGGL(bl_shade_formula_fast_kernel, dim3(grid), dim3(256), 0, stream, *args);
-  return bl_launch_shade_redo(args, BL_MODEL_FORMULA, grid, stream);
+  return hipGetLastError();
 }
 
-// Tolerant tier, simulations: the fast coefficient kernel, then the exact kernel over the records it deferred
-extern "C" hipError_t bl_launch_shade_fast(const BlShadeArgs *args, int grid, hipStream_t stream) {
-  const bool spin_zero = args->st.bh_a == 0.0;
-  if (args->located == nullptr) {   // no locate kernel ran: the kernel with the locate step inside (bl_shade_fused.hip)
-    const hipError_t err = bl_launch_shade_fused2(args, grid, stream);
-    if (err != hipSuccess) return err;
-    return bl_launch_shade_redo(args, BL_MODEL_SIMULATION, grid, stream);
+// bl_shade_fast_kernel's instantiations, each named once: mode 0 the plain one (zero spin known or not); 1 the general one - power
+// laws, Cartesian grids, an optical-depth image; 2 the one that also knows the anchor cells of inter-block interpolation; 3 ... and
+// the time slices of slow light
+static void (*shade_fast_kernel(const KernelPlan::Shade &c))(BlShadeArgs) {
+  if (c.family != KernelPlan::Shade::kFast || (c.spin_zero && c.mode != 0)) return nullptr;
+  switch (c.mode) {
+    case 0: return c.spin_zero ? bl_shade_fast_kernel<true, 0> : bl_shade_fast_kernel<false, 0>;
+    case 1: return bl_shade_fast_kernel<false, 1>;
+    case 2: return bl_shade_fast_kernel<false, 2>;
+    case 3: return bl_shade_fast_kernel<false, 3>;
+    default: return nullptr;
   }
+}
+
+// Tolerant tier, simulations behind a locate kernel: the fast coefficient kernel (the exact second pass follows: bl_launch_shade_redo)
+extern "C" hipError_t bl_launch_shade_fast(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream) {
+  void (*kernel)(BlShadeArgs) = shade_fast_kernel(plan);
+  // (the block has to agree with the choice: located samples, and nothing the mode does not know)
+  if (kernel == nullptr || args->located == nullptr || args->redo_list == nullptr || (plan.spin_zero && args->st.bh_a != 0.0)
+      || (args->slow.n > 0) != (plan.mode == 3) || (plan.mode < 2 && args->anchors != nullptr)
+      || (plan.mode == 0 && (args->tau_inc != nullptr || args->plasma.power_frac != 0.0 || args->plasma.simulation_coord == BL_COORD_CKS)))
+    return hipErrorInvalidValue;
   const size_t lds = (44 + 5 * args->n_nu + (args->slow.n > 0 ? args->slow.n : 0)) * sizeof(double);
-  // power laws, Cartesian grids and an optical-depth image go through the general instantiation; inter-block interpolation and slow light
-  // through the one that also knows anchor cells and time slices
-  const bool slices = args->anchors != nullptr || args->slow.n > 0;
-  const bool general = args->plasma.power_frac != 0.0 || args->tau_inc != nullptr || args->plasma.simulation_coord == BL_COORD_CKS;
-#define BL_LAUNCH_F(SPIN, MODE) hipLaunchKernelGGL((bl_shade_fast_kernel<SPIN, MODE>), dim3(grid), dim3(256), lds, stream, *args)
-  if (slices) {
-    if (args->slow.n > 0) BL_LAUNCH_F(false, 3); else BL_LAUNCH_F(false, 2);
-  } else if (general) {
-    BL_LAUNCH_F(false, 1);
-  } else {
-    if (spin_zero) BL_LAUNCH_F(true, 0); else BL_LAUNCH_F(false, 0);
-  }
-#undef BL_LAUNCH_F
-  return bl_launch_shade_redo(args, BL_MODEL_SIMULATION, grid, stream);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, *args);
+  return hipGetLastError();
 }

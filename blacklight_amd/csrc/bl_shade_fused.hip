@@ -1515,44 +1515,51 @@ __global__ void __launch_bounds__(256, 2) bl_shade_polarized2_kernel(const BlSha
   if ((threadIdx.x & 63) == 0 && gathers_wave != 0ull) atomicAdd(&P.counters[BL_CNT_GATHERS], gathers_wave);
 }
 
-extern "C" hipError_t bl_launch_shade_polarized2(const BlShadeArgs *args, int grid, hipStream_t stream) {
-  const BlGridDevice &g = args->grid;
-  // (a mesh with refinement: the fused kernel's tables without its 48 doubles of cut thresholds - bl_polarized2_refined_applicable)
-  const size_t lds = g.n_blocks > 0 ? (size_t)g.fused_lds_bytes - 48 * sizeof(double) : 64 * (size_t)(g.n[0] + g.n[1] + g.n[2]);
-  if (args->pol_samples == nullptr || args->coef_inputs == nullptr) return hipErrorInvalidValue;
-  const bool spin_zero = args->st.bh_a == 0.0, records = args->aux_record_unused == 0;
-  if (records && args->aux == nullptr) return hipErrorInvalidValue;
-  const bool inside = args->have_flags != nullptr && !records && spin_zero;   // (bl_render.hip: one frequency, thermal electrons only, no spin)
-  if (lds > 64 * 1024) {   // (two 256-lane workgroups to a compute unit: up to 76 KiB each)
-    const void *kernel = inside ? reinterpret_cast<const void *>(&bl_shade_polarized2_kernel<true, false, true>)
-        : (spin_zero ? (records ? reinterpret_cast<const void *>(&bl_shade_polarized2_kernel<true, true>) : reinterpret_cast<const void *>(&bl_shade_polarized2_kernel<true, false>))
-                     : (records ? reinterpret_cast<const void *>(&bl_shade_polarized2_kernel<false, true>) : reinterpret_cast<const void *>(&bl_shade_polarized2_kernel<false, false>)));
-    const hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 76 * 1024);
+using BlShadeKernel = void (*)(BlShadeArgs);
+
+// Dynamic LDS of the kernels with the locate step inside: the coordinate tables - one block: 64 bytes per cell row of each axis; a mesh
+// with refinement: as staged (BlGridDevice::fused_lds_bytes) - behind the tolerant kernel's 48 doubles of cut thresholds, which the exact
+// and the polarized kernel do without
+static size_t fused_tables_lds(const BlGridDevice &g, bool thresholds) {
+  const size_t tables = g.n_blocks > 0 ? (size_t)g.fused_lds_bytes - 48 * sizeof(double) : 64 * (size_t)(g.n[0] + g.n[1] + g.n[2]);
+  return tables + (thresholds ? 48 * sizeof(double) : 0);
+}
+
+// The launch through the one pointer, behind the request for more dynamic LDS than a launch gets unasked (raise_to bytes; 0: none)
+static hipError_t launch_with_lds(BlShadeKernel kernel, dim3 blocks, dim3 lanes, size_t lds, int raise_to, hipStream_t stream, const BlShadeArgs *args) {
+  if (raise_to > 0) {
+    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, raise_to);
     if (err != hipSuccess) return err;
   }
-#define BL_LAUNCH_P2(S, A) hipLaunchKernelGGL((bl_shade_polarized2_kernel<S, A>), dim3(grid), dim3(256), lds, stream, *args)
-  if (inside) {
-    hipLaunchKernelGGL((bl_shade_polarized2_kernel<true, false, true>), dim3(grid), dim3(256), lds, stream, *args);
-  } else if (spin_zero && records) BL_LAUNCH_P2(true, true);
-  else if (spin_zero) BL_LAUNCH_P2(true, false);
-  else if (records) BL_LAUNCH_P2(false, true);
-  else BL_LAUNCH_P2(false, false);
-#undef BL_LAUNCH_P2
+  hipLaunchKernelGGL(kernel, blocks, lanes, lds, stream, *args);
   return hipGetLastError();
 }
 
+// bl_shade_polarized2_kernel<spin_zero, records, coefficients>: with or without BlAuxSample records; the polarized coefficients
+// evaluated inside only without records and with zero spin (the plan: one frequency, thermal electrons only)
+static BlShadeKernel shade_polarized2_kernel(const KernelPlan::Shade &c) {
+  if (c.family != KernelPlan::Shade::kPolarized2) return nullptr;
+  if (c.coefficients) return (c.spin_zero && !c.records) ? bl_shade_polarized2_kernel<true, false, true> : nullptr;
+  if (c.spin_zero) return c.records ? bl_shade_polarized2_kernel<true, true> : bl_shade_polarized2_kernel<true, false>;
+  return c.records ? bl_shade_polarized2_kernel<false, true> : bl_shade_polarized2_kernel<false, false>;
+}
+
+extern "C" hipError_t bl_launch_shade_polarized2(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream) {
+  BlShadeKernel kernel = shade_polarized2_kernel(plan);
+  if (kernel == nullptr || args->located != nullptr || args->pol_samples == nullptr || args->coef_inputs == nullptr) return hipErrorInvalidValue;
+  if (plan.records != (args->aux_record_unused == 0) || (plan.records && args->aux == nullptr) || plan.coefficients != (args->have_flags != nullptr)
+      || (plan.spin_zero && args->st.bh_a != 0.0)) return hipErrorInvalidValue;
+  // (a mesh's tables, two 256-lane workgroups to a compute unit: up to 76 KiB each - bl_polarized2_refined_applicable)
+  const size_t lds = fused_tables_lds(args->grid, false);
+  return launch_with_lds(kernel, dim3(grid), dim3(256), lds, lds > 64 * 1024 ? 76 * 1024 : 0, stream, args);
+}
+
 // (the exact tier's use of the fused kernel: one frequency, plain image; bl_render.hip checks the rest with bl_fused2_applicable)
-extern "C" hipError_t bl_launch_shade_exact2(const BlShadeArgs *args, int grid, hipStream_t stream) {
-  const BlGridDevice &g = args->grid;
-  const size_t lds = g.n_blocks > 0 ? (size_t)g.fused_lds_bytes - 48 * sizeof(double) : 64 * (size_t)(g.n[0] + g.n[1] + g.n[2]);
-  if (lds > 64 * 1024) {   // (a mesh's tables, two workgroups to a compute unit: bl_polarized2_refined_applicable)
-    const void *kernel = args->st.bh_a == 0.0 ? reinterpret_cast<const void *>(&bl_shade_exact2_kernel<true>) : reinterpret_cast<const void *>(&bl_shade_exact2_kernel<false>);
-    const hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 76 * 1024);
-    if (err != hipSuccess) return err;
-  }
-  if (args->st.bh_a == 0.0) hipLaunchKernelGGL((bl_shade_exact2_kernel<true>), dim3(grid), dim3(256), lds, stream, *args);
-  else hipLaunchKernelGGL((bl_shade_exact2_kernel<false>), dim3(grid), dim3(256), lds, stream, *args);
-  return hipGetLastError();
+extern "C" hipError_t bl_launch_shade_exact2(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream) {
+  if (plan.family != KernelPlan::Shade::kExact2 || args->located != nullptr || (plan.spin_zero && args->st.bh_a != 0.0)) return hipErrorInvalidValue;
+  BlShadeKernel kernel = plan.spin_zero ? bl_shade_exact2_kernel<true> : bl_shade_exact2_kernel<false>;
+  const size_t lds = fused_tables_lds(args->grid, false);   // (a mesh's tables: two workgroups to a compute unit, as the polarized kernel)
+  return launch_with_lds(kernel, dim3(grid), dim3(256), lds, lds > 64 * 1024 ? 76 * 1024 : 0, stream, args);
 }
 
 // Whether a render can take this kernel (the caller has checked what the locate step inside needs, one frequency without the
@@ -1568,8 +1575,7 @@ extern "C" int bl_fused2_applicable(const BlGridDevice *grid, int n_nu, long lon
   const unsigned long long n_cells = (unsigned long long)g.n[0] * g.n[1] * g.n[2];
   if (n_cells * 32ull >= (1ull << 32) || (unsigned long long)g.n[1] * g.n[2] >= (1ull << 24) || g.n[0] >= (1 << 24)) return 0;
   if (g.stride_row != g.n[0] || g.stride_plane != g.n[0] * g.n[1]) return 0;
-  const size_t lds = 48 * sizeof(double) + 64 * (size_t)(g.n[0] + g.n[1] + g.n[2]);
-  return lds <= 64u * 1024u ? 1 : 0;
+  return fused_tables_lds(g, true) <= 64u * 1024u ? 1 : 0;
 }
 
 // The polarized kernel over a mesh with refinement: the same tables (widths for reciprocals), 256-lane workgroups two to a compute unit
@@ -1587,36 +1593,33 @@ extern "C" int bl_fused2_refined_applicable(const BlGridDevice *grid, int n_nu, 
   return (grid->n_blocks > 0 && grid->fused_lds_bytes > 0 && n_nu == 1 && n_rays < (1ll << 29)) ? 1 : 0;
 }
 
-extern "C" hipError_t bl_launch_shade_fused2(const BlShadeArgs *args, int grid, hipStream_t stream) {
-  const BlGridDevice &g = args->grid;
-  if (g.n_blocks > 0) {
-    if (args->composed == nullptr || args->freq_split || g.fused_lds_bytes <= 0) return hipErrorInvalidValue;
-    const void *kernel = args->st.bh_a == 0.0 ? reinterpret_cast<const void *>(&bl_shade_fused2_kernel<true, true, false, true>)
-                                              : reinterpret_cast<const void *>(&bl_shade_fused2_kernel<false, true, false, true>);
-    if (g.fused_lds_bytes + 4096 > 64 * 1024) {   // (more dynamic LDS than a launch gets unasked: up to BL_FUSED_REFINED_LDS of the compute unit's 160 KiB)
-      const hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BL_FUSED_REFINED_LDS + 4096);
-      if (err != hipSuccess) return err;
-    }
-    // Tables that fit twice into a compute unit's LDS: 256-lane workgroups as for one block (`grid` of them). Larger ones: one 512-lane
-    // workgroup to a compute unit, and one round of them (a workgroup's LDS is free for the next only when its last wave has ended:
-    // with several rounds every round's tail idles seven waves; measured 29.6 against 27.5 ms on the mesh that fits either way)
-    const bool two_to_a_unit = g.fused_lds_bytes <= 76 * 1024;
-    const dim3 blocks(two_to_a_unit ? grid : (grid >= 8 ? grid / 8 : 1)), lanes(two_to_a_unit ? 256 : 512);
-    const size_t lds_bytes = (size_t)g.fused_lds_bytes + (size_t)(lanes.x / 64) * 512;   // (+ the waves' lists of samples for the exact pass)
-    if (args->st.bh_a == 0.0) hipLaunchKernelGGL((bl_shade_fused2_kernel<true, true, false, true>), blocks, lanes, lds_bytes, stream, *args);
-    else hipLaunchKernelGGL((bl_shade_fused2_kernel<false, true, false, true>), blocks, lanes, lds_bytes, stream, *args);
-    return hipGetLastError();
+// bl_shade_fused2_kernel<spin_zero, composed, factors, refined>: one block - transfer records or composed maps, or the per-sample
+// factors of several frequencies; a mesh with refinement - one frequency and composed maps only
+static BlShadeKernel shade_fused2_kernel(const KernelPlan::Shade &c) {
+  if (c.family != KernelPlan::Shade::kFused2) return nullptr;
+  if (c.refined) {
+    if (!c.composed || c.factors) return nullptr;
+    return c.spin_zero ? bl_shade_fused2_kernel<true, true, false, true> : bl_shade_fused2_kernel<false, true, false, true>;
   }
-  const size_t lds = 48 * sizeof(double) + 64 * (size_t)(g.n[0] + g.n[1] + g.n[2]);
-  const bool spin_zero = args->st.bh_a == 0.0, composed = args->composed != nullptr;
-#define BL_LAUNCH_F2(S, C) hipLaunchKernelGGL((bl_shade_fused2_kernel<S, C>), dim3(grid), dim3(256), lds, stream, *args)
-  if (args->freq_split) {
-    if (spin_zero) hipLaunchKernelGGL((bl_shade_fused2_kernel<true, false, true>), dim3(grid), dim3(256), lds, stream, *args);
-    else hipLaunchKernelGGL((bl_shade_fused2_kernel<false, false, true>), dim3(grid), dim3(256), lds, stream, *args);
-  } else if (spin_zero && composed) BL_LAUNCH_F2(true, true);
-  else if (spin_zero) BL_LAUNCH_F2(true, false);
-  else if (composed) BL_LAUNCH_F2(false, true);
-  else BL_LAUNCH_F2(false, false);
-#undef BL_LAUNCH_F2
-  return hipGetLastError();
+  if (c.factors) return c.composed ? nullptr : (c.spin_zero ? bl_shade_fused2_kernel<true, false, true> : bl_shade_fused2_kernel<false, false, true>);
+  if (c.spin_zero) return c.composed ? bl_shade_fused2_kernel<true, true> : bl_shade_fused2_kernel<true, false>;
+  return c.composed ? bl_shade_fused2_kernel<false, true> : bl_shade_fused2_kernel<false, false>;
+}
+
+// (the exact second pass follows: bl_launch_shade_redo)
+extern "C" hipError_t bl_launch_shade_fused2(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream) {
+  const BlGridDevice &g = args->grid;
+  BlShadeKernel kernel = shade_fused2_kernel(plan);
+  if (kernel == nullptr || args->located != nullptr || args->redo_list == nullptr || plan.refined != (g.n_blocks > 0)
+      || plan.composed != (args->composed != nullptr) || plan.factors != (args->freq_split != 0) || (plan.spin_zero && args->st.bh_a != 0.0)
+      || (plan.refined && g.fused_lds_bytes <= 0)) return hipErrorInvalidValue;
+  if (!plan.refined) return launch_with_lds(kernel, dim3(grid), dim3(256), fused_tables_lds(g, true), 0, stream, args);   // (at most 64 KiB: bl_fused2_applicable)
+  // Tables that fit twice into a compute unit's LDS: 256-lane workgroups as for one block (`grid` of them). Larger ones: one 512-lane
+  // workgroup to a compute unit, and one round of them (a workgroup's LDS is free for the next only when its last wave has ended:
+  // with several rounds every round's tail idles seven waves; measured 29.6 against 27.5 ms on the mesh that fits either way)
+  const bool two_to_a_unit = g.fused_lds_bytes <= 76 * 1024;
+  const dim3 blocks(two_to_a_unit ? grid : (grid >= 8 ? grid / 8 : 1)), lanes(two_to_a_unit ? 256 : 512);
+  // (+ the waves' lists of samples for the exact pass; up to BL_FUSED_REFINED_LDS of the compute unit's 160 KiB)
+  const size_t lds_bytes = fused_tables_lds(g, true) + (size_t)(lanes.x / 64) * 512;
+  return launch_with_lds(kernel, blocks, lanes, lds_bytes, g.fused_lds_bytes + 4096 > 64 * 1024 ? BL_FUSED_REFINED_LDS + 4096 : 0, stream, args);
 }

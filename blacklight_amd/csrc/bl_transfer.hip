@@ -369,18 +369,6 @@ __global__ void __launch_bounds__(64) bl_transfer_aux_kernel(BlTransferArgs P) {
   }
 }
 
-extern "C" hipError_t bl_launch_transfer_freq(const BlTransferArgs *args, hipStream_t stream) {
-  const long long lanes = (long long)args->chunk_rays * args->n_nu * (args->n_models > 0 ? args->n_models * (args->n_units > 0 ? args->n_units : 1) : 1);
-  hipLaunchKernelGGL(bl_transfer_freq_kernel, dim3((unsigned int)((lanes + 255) / 256)), dim3(256), 0, stream, *args);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t bl_launch_transfer_aux(const BlTransferArgs *args, hipStream_t stream) {
-  int grid = (args->chunk_rays + 63) / 64;
-  hipLaunchKernelGGL(bl_transfer_aux_kernel, dim3(grid), dim3(64), 0, stream, *args);
-  return hipGetLastError();
-}
-
 // Optical depth beside the intensities in the tolerant tier: tau(ray, frequency) = sum of alpha x length over the ray's samples, far
 // -> near as the reference adds them (unpolarized.cpp:63-151), from the increments the fast coefficient kernel left
 __global__ void __launch_bounds__(256) bl_tau_kernel(BlTransferArgs P) {
@@ -550,18 +538,35 @@ __global__ void __launch_bounds__(256) bl_transfer_composed_kernel(BlTransferArg
   }
 }
 
-extern "C" hipError_t bl_launch_transfer_composed(const BlTransferArgs *args, hipStream_t stream) {
-  hipLaunchKernelGGL(bl_transfer_composed_kernel, dim3((args->chunk_rays + 255) / 256), dim3(256), 0, stream, *args);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t bl_launch_transfer(const BlTransferArgs *args, hipStream_t stream) {
-  int grid = (int)(((long long)args->chunk_rays * args->n_nu + 255) / 256);
-  if (args->affine && args->n_nu == 1 && !args->lane_transfer) {
-    hipLaunchKernelGGL(bl_transfer_quad_kernel, dim3((int)(((long long)args->chunk_rays * 4 + 255) / 256)), dim3(256), 0, stream, *args);
-    return hipGetLastError();
+// The transfer kernel of the plan: grid, workgroup and kernel per kind (no dynamic LDS)
+extern "C" hipError_t bl_launch_transfer(const BlTransferArgs *args, const KernelPlan::Transfer &plan, hipStream_t stream) {
+  using Transfer = KernelPlan::Transfer;
+  const long long rays = args->chunk_rays;
+  void (*kernel)(BlTransferArgs) = nullptr;
+  long long lanes = rays * args->n_nu;   // a lane per ray and frequency
+  int block = 256;
+  switch (plan.kind) {
+    case Transfer::kAux:
+      if (args->aux == nullptr && !args->aux_images.polarized_rows_only) return hipErrorInvalidValue;
+      kernel = bl_transfer_aux_kernel, lanes = rays, block = 64;
+      break;
+    case Transfer::kFreq:   // ... and model and unit
+      if (args->freq_inputs == nullptr) return hipErrorInvalidValue;
+      kernel = bl_transfer_freq_kernel, lanes *= args->n_models > 0 ? args->n_models * (args->n_units > 0 ? args->n_units : 1) : 1;
+      break;
+    case Transfer::kComposed:
+      if (args->composed == nullptr || !plan.affine) return hipErrorInvalidValue;
+      kernel = bl_transfer_composed_kernel, lanes = rays;
+      break;
+    case Transfer::kQuad:   // four lanes per ray
+      if (!plan.affine || args->n_nu != 1 || args->lane_transfer) return hipErrorInvalidValue;
+      kernel = bl_transfer_quad_kernel, lanes = rays * 4;
+      break;
+    case Transfer::kLane:
+      kernel = plan.affine ? bl_transfer_kernel<true> : bl_transfer_kernel<false>;
+      break;
   }
-  if (args->affine) hipLaunchKernelGGL(bl_transfer_kernel<true>, dim3(grid), dim3(256), 0, stream, *args);
-  else hipLaunchKernelGGL(bl_transfer_kernel<false>, dim3(grid), dim3(256), 0, stream, *args);
+  if (plan.affine != (args->affine != 0)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, dim3((unsigned int)((lanes + block - 1) / block)), dim3(block), 0, stream, *args);
   return hipGetLastError();
 }
