@@ -347,7 +347,7 @@ const char *ElectronModelsRefusal(const bl_ctx *ctx, int n) {
   if (n >= 2 && p.adaptive_max_level > 0)
     return "Electron models: adaptive refinement reads one image; n >= 2 models need adaptive_max_level = 0.";
   if (n >= 2 && ctx->render_num_images > 0) {   // (renderings come out once: only those no model enters)
-    bool theta_e = p.cut_theta_e_min >= 0.0 || p.cut_theta_e_max >= 0.0;
+    bool theta_e = ThetaECut(p);
     for (int i = 0; i < ctx->render_num_images; i++)
       for (int f = 0; f < p.render_num_features[i]; f++)
         if (p.render_quantity[i][f] == 3) theta_e = true;
@@ -369,8 +369,7 @@ const char *DensityUnitsRefusal(const bl_ctx *ctx, int n) {
   if (n >= 2 && p.adaptive_max_level > 0)
     return "Density units: adaptive refinement reads one image; n >= 2 units need adaptive_max_level = 0.";
   if (n >= 2 && ctx->render_num_images > 0) {   // (renderings come out once: only those no unit enters)
-    bool unit_cut = p.cut_rho_min >= 0.0 || p.cut_rho_max >= 0.0 || p.cut_n_e_min >= 0.0 || p.cut_n_e_max >= 0.0
-        || p.cut_p_gas_min >= 0.0 || p.cut_p_gas_max >= 0.0 || p.cut_b_min >= 0.0 || p.cut_b_max >= 0.0;
+    bool unit_cut = UnitCut(p);
     for (int i = 0; i < ctx->render_num_images; i++)
       for (int f = 0; f < p.render_num_features[i]; f++) {
         const int q = p.render_quantity[i][f];   // (bl_params.cpp: rho, n_e, p_gas, Theta_e, B, sigma, beta_inverse)
@@ -398,6 +397,18 @@ const char *PolarizedVariantsRefusal(const bl_ctx *ctx, int n) {
   if (n >= 2 && ctx->render_num_images > 0)
     return "Polarized variants: renderings come out once; n >= 2 variants need render_num_images = 0.";
   return nullptr;
+}
+
+// The variants of a render, in image-row order: the triples, else models x units, model-major, with the parameter block's pair and
+// unit where an axis is not set. The one reader of what the three setters stored.
+Variants ResolveVariants(const bl_ctx *ctx) {
+  const bl_params &p = ctx->params;
+  const std::vector<Variant> own = {{p.plasma_rat_low, p.plasma_rat_high, p.simulation_rho_cgs}};
+  Variants v{ctx->triples, static_cast<int>(ctx->models.size()), static_cast<int>(ctx->units.size()), static_cast<int>(ctx->triples.size())};
+  if (v.n_pol == 0)
+    for (const Variant &model : v.n_models > 0 ? ctx->models : own)
+      for (const Variant &unit : v.n_units > 0 ? ctx->units : own) v.list.push_back({model.rat_low, model.rat_high, unit.rho});
+  return v;
 }
 }  // namespace blhost
 
@@ -1144,10 +1155,10 @@ int bl_set_snapshot(bl_ctx *ctx, int snapshot) {
 int bl_render_num_images(const bl_ctx *ctx) { return ctx != nullptr ? ctx->render_num_images : 0; }
 
 int bl_image_num_quantities(const bl_ctx *ctx) {
-  if (ctx == nullptr) return -1;
-  return ctx->image_num_quantities * std::max<int>(1, static_cast<int>(ctx->model_rat_low.size()))
-      * std::max<int>(1, static_cast<int>(ctx->density_units.size())) * std::max<int>(1, static_cast<int>(ctx->pol_rho.size()));
+  return ctx != nullptr ? ctx->image_num_quantities * bl_num_variants(ctx) : -1;
 }
+
+int bl_num_variants(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ResolveVariants(ctx).list.size()) : -1; }
 
 int bl_set_electron_models(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high) {
   if (ctx == nullptr) return BL_E_ARG;
@@ -1158,12 +1169,12 @@ int bl_set_electron_models(bl_ctx *ctx, int n, const double *rat_low, const doub
       return Fail(ctx, Failure{BL_E_ARG, "bl_set_electron_models: model " + std::to_string(m) + " has a ratio that is not finite."});
   if (const char *why = ElectronModelsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
   std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: they do not depend on the model)
-  ctx->model_rat_low.assign(rat_low, rat_low + n);
-  ctx->model_rat_high.assign(rat_high, rat_high + n);
+  ctx->models.resize(n);
+  for (int m = 0; m < n; m++) ctx->models[m] = {rat_low[m], rat_high[m], 0.0};
   return BL_OK;
 }
 
-int bl_num_electron_models(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->model_rat_low.size()) : -1; }
+int bl_num_electron_models(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->models.size()) : -1; }
 
 int bl_set_density_units(bl_ctx *ctx, int n, const double *rho_cgs) {
   if (ctx == nullptr) return BL_E_ARG;
@@ -1174,11 +1185,12 @@ int bl_set_density_units(bl_ctx *ctx, int n, const double *rho_cgs) {
       return Fail(ctx, Failure{BL_E_ARG, "bl_set_density_units: unit " + std::to_string(u) + " is not a finite value > 0."});
   if (const char *why = DensityUnitsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
   std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: they do not depend on the unit)
-  ctx->density_units.assign(rho_cgs, rho_cgs + n);
+  ctx->units.resize(n);
+  for (int u = 0; u < n; u++) ctx->units[u] = {0.0, 0.0, rho_cgs[u]};
   return BL_OK;
 }
 
-int bl_num_density_units(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->density_units.size()) : -1; }
+int bl_num_density_units(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->units.size()) : -1; }
 
 int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs) {
   if (ctx == nullptr) return BL_E_ARG;
@@ -1192,13 +1204,12 @@ int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const d
   }
   if (const char *why = PolarizedVariantsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
   std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: no variant enters them)
-  ctx->pol_rat_low.assign(rat_low, rat_low + n);
-  ctx->pol_rat_high.assign(rat_high, rat_high + n);
-  ctx->pol_rho.assign(rho_cgs, rho_cgs + n);
+  ctx->triples.resize(n);
+  for (int v = 0; v < n; v++) ctx->triples[v] = {rat_low[v], rat_high[v], rho_cgs[v]};
   return BL_OK;
 }
 
-int bl_num_polarized_variants(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->pol_rho.size()) : -1; }
+int bl_num_polarized_variants(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->triples.size()) : -1; }
 
 int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out) {
   if (ctx == nullptr || out == nullptr) return BL_E_ARG;

@@ -117,6 +117,14 @@ inline void Check(hipError_t err, const char *what) {
 }  // namespace blhost
 using namespace blhost;
 
+// One image of a render: an electron model (R_low, R_high) and a density unit (simulation_rho_cgs). Variants: a render's, in image-row
+// order and never empty (ResolveVariants), with the number of models, units and polarized triples as set - 0: the parameter block's.
+struct Variant { double rat_low, rat_high, rho; };
+struct Variants {
+  std::vector<Variant> list;
+  int n_models, n_units, n_pol;
+};
+
 struct bl_ctx {
   bl_params params;
   bl_camera_frame frame;
@@ -151,9 +159,9 @@ struct bl_ctx {
 
   // image rows (radiation_integrator.cpp:436-520)
   int image_num_quantities = 0;      // of one electron model and unit (bl_image_num_quantities: times the number of each)
-  std::vector<double> model_rat_low, model_rat_high;   // bl_set_electron_models(); empty: the parameter block's pair
-  std::vector<double> density_units;  // bl_set_density_units(): simulation_rho_cgs values; empty: the parameter block's
-  std::vector<double> pol_rat_low, pol_rat_high, pol_rho;   // bl_set_polarized_variants(): (R_low, R_high, simulation_rho_cgs) triples; empty: the parameter block's
+  // what the three setters stored, empty: the parameter block's - bl_set_electron_models() pairs (rho unused), bl_set_density_units()
+  // units (the pair unused), bl_set_polarized_variants() triples; read through ResolveVariants only
+  std::vector<Variant> models, units, triples;
   BlAuxImages aux_images{};          // which image rows exist; .any = an auxiliary image or a rendering is requested
   int render_num_images = 0;         // false-colour renderings (0 in formula mode)
   DeviceBuffer<BlRenderDevice> d_render_params;
@@ -355,6 +363,12 @@ inline void Warn(bl_ctx *ctx, const std::string &message) { ctx->warnings += "Wa
 int Fail(bl_ctx *ctx, const Failure &failure);   // sets bl_last_error (or the global error when ctx is null), returns the code
 void EnsureStreams(bl_ctx *ctx);
 void DropResident(bl_ctx *ctx);   // the root level's kept geodesics go (bl_render.hip)
+Variants ResolveVariants(const bl_ctx *ctx);   // (bl_api.hip) what bl_render's plan, bl_num_variants and bl_image_num_quantities read
+inline bool UnitCut(const bl_params &p) {   // a cut the density unit enters is set: rho, n_e, p_gas or B
+  return p.cut_rho_min >= 0.0 || p.cut_rho_max >= 0.0 || p.cut_n_e_min >= 0.0 || p.cut_n_e_max >= 0.0 || p.cut_p_gas_min >= 0.0 || p.cut_p_gas_max >= 0.0
+      || p.cut_b_min >= 0.0 || p.cut_b_max >= 0.0;
+}
+inline bool ThetaECut(const bl_params &p) { return p.cut_theta_e_min >= 0.0 || p.cut_theta_e_max >= 0.0; }
 const char *ElectronModelsRefusal(const bl_ctx *ctx, int n);   // bl_set_electron_models (bl_api.hip)
 const char *DensityUnitsRefusal(const bl_ctx *ctx, int n);     // bl_set_density_units (bl_api.hip)
 const char *PolarizedVariantsRefusal(const bl_ctx *ctx, int n);   // bl_set_polarized_variants (bl_api.hip)

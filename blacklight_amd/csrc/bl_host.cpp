@@ -719,11 +719,6 @@ int bl_write_output(bl_ctx *ctx, const char *path_override, const bl_output_desc
   return WriteOutput(ctx, path_override, d, 0, 1);
 }
 
-int bl_num_variants(const bl_ctx *ctx) {
-  if (ctx == nullptr) return -1;
-  return std::max(1, bl_num_electron_models(ctx)) * std::max(1, bl_num_density_units(ctx)) * std::max(1, bl_num_polarized_variants(ctx));
-}
-
 int bl_write_output_variant(bl_ctx *ctx, const char *path_override, const bl_output_desc *d, int variant) {
   if (ctx == nullptr || d == nullptr) return BL_E_ARG;
   const int n_variants = bl_num_variants(ctx);

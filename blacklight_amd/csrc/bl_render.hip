@@ -208,16 +208,14 @@ struct RenderJob {
   size_t park_capacity = 0;
   int quad_grid = 0;          // waves of bl_geodesic_quad_kernel
   int n_nu = 0, n_q = 0, max_steps = 0;
-  // bl_set_electron_models / bl_set_density_units: n_models pairs, n_units units (0: the parameter block's), a variant is a (model,
-  // unit) with n_q_model image rows (n_q = max(1, n_models) x max(1, n_units) x n_q_model, model-major); the shading stage runs once
-  // per variant over the chunk's samples (variant_passes)
-  int n_models = 0, n_units = 0, n_q_model = 0, variant_passes = 1;
+  // The render's variants (ResolveVariants: models x units, model-major, or the triples of a polarized run), each with n_q_model image
+  // rows (n_q = variants x n_q_model); the shading stage runs once per variant over the chunk's samples (variant_passes)
+  Variants variants;
+  int n_q_model = 0, variant_passes = 1;
   bool variants_one_pass = false;   // ... or all of them in one pass: one gather, one lane per (ray, model, unit, frequency) in the transfer kernel
-  double base_rho = 0.0;            // the unit BuildShadeArgs folds: the one set unit, else the parameter block's (one pass: the rows' unit)
-  // bl_set_polarized_variants: n_pol (R_low, R_high, unit) triples of a polarized run (0: the parameter block's; never beside models or
-  // units, which refuse polarized runs) - one shading pass each (variant_passes), or pol_one_pass: the coefficient kernel and the
-  // transport matrices once per chunk, bl_polarized_coefficients_kernel and the polarized transfer kernels with a variant axis
-  int n_pol = 0;
+  double base_rho = 0.0, base_rat_low = 0.0, base_rat_high = 0.0;   // what BuildShadeArgs folds (PlanJob; one pass: the rows' unit and pair)
+  // ... or pol_one_pass, the triples': the coefficient kernel and the transport matrices once per chunk,
+  // bl_polarized_coefficients_kernel and the polarized transfer kernels with a variant axis
   bool pol_one_pass = false;
   int n_cold = 1;                   // BlShadeCold blocks on the device: one per unit where the passes' cut thresholds differ (BindVariant)
   long long n_rays = 0, level_pixels = 0;
@@ -356,29 +354,18 @@ void FoldFastCuts(const bl_ctx *ctx, const BlPlasmaDevice &pl, BlShadeCold &cold
   }
 }
 
-// Variant v = m * max(1, n_units) + u of bl_set_electron_models x bl_set_density_units into the argument blocks: model m's pair
-// where the coefficient kernels read R_low / R_high, unit u folded as BuildShadeArgs folds the render's (FoldUnits), the cut
-// thresholds of unit u (its BlShadeCold, uploaded by BuildShadeArgs), and the variant's rows of the image. With neither models nor
-// two units there is one variant, the one BuildShadeArgs folded: nothing changes.
+// Variant v of the render into the argument blocks: its pair where the coefficient kernels read R_low / R_high, its unit folded as
+// BuildShadeArgs folds the render's (FoldUnits), the cut thresholds of its unit (its BlShadeCold, uploaded by BuildShadeArgs), and its
+// rows of the image. Nothing to do with one variant - the one BuildShadeArgs folded - or where one pass has them all: the transfer
+// kernel has every variant's constants (BuildTransferArgs), the polarized coefficient kernel its table (BuildShadeArgs).
 void BindVariant(RenderJob &job, int v) {
-  bl_ctx *ctx = job.ctx;
-  if (job.n_pol >= 2) {   // (one triple is the one BuildShadeArgs folded)
-    if (job.pol_one_pass) return;   // (BuildShadeArgs folded the first triple, whose cut decisions are every variant's; the table has the others)
-    BlPlasmaDevice &pl = job.sa.plasma;
-    pl.plasma_rat_low = ctx->pol_rat_low[v];
-    pl.plasma_rat_high = ctx->pol_rat_high[v];
-    FoldUnits(ctx, ctx->pol_rho[v], pl, job.sa.fast_k);
-    job.xa.image = job.image + static_cast<size_t>(v) * job.n_q_model * static_cast<size_t>(job.n_rays);
-    return;
-  }
-  if (job.variants_one_pass || (job.n_models == 0 && job.n_units <= 1)) return;   // (one pass: the transfer kernel has every variant's constants, BuildTransferArgs)
-  const bl_params &p = ctx->params;
-  const int n_u = std::max(1, job.n_units), m = v / n_u, u = v % n_u;
+  if (job.variants.list.size() == 1 || job.variants_one_pass || job.pol_one_pass) return;
+  const Variant &variant = job.variants.list[v];
   BlPlasmaDevice &pl = job.sa.plasma;
-  pl.plasma_rat_low = job.n_models > 0 ? ctx->model_rat_low[m] : p.plasma_rat_low;
-  pl.plasma_rat_high = job.n_models > 0 ? ctx->model_rat_high[m] : p.plasma_rat_high;
-  FoldUnits(ctx, job.n_units > 0 ? ctx->density_units[u] : p.simulation_rho_cgs, pl, job.sa.fast_k);
-  job.sa.cold = ctx->d_shade_cold.ptr + (job.n_cold > 1 ? u : 0);
+  pl.plasma_rat_low = variant.rat_low;
+  pl.plasma_rat_high = variant.rat_high;
+  FoldUnits(job.ctx, variant.rho, pl, job.sa.fast_k);
+  job.sa.cold = job.ctx->d_shade_cold.ptr + (job.n_cold > 1 ? v % job.variants.n_units : 0);
   job.xa.image = job.image + static_cast<size_t>(v) * job.n_q_model * static_cast<size_t>(job.n_rays);
 }
 
@@ -412,17 +399,23 @@ void PlanJob(RenderJob &job) {
       Warn(ctx, "Unpolarized kappa-distribution electrons: kappa_aa_high_i, which the reference leaves uninitialised here, is (3 / kappa)^4.75 + 0.6.");
     ctx->kappa_warned = true;
   }
-  job.n_models = static_cast<int>(ctx->model_rat_low.size());
-  if (const char *why = ElectronModelsRefusal(ctx, job.n_models)) throw Failure{BL_E_UNSUPPORTED, why};
-  job.n_units = static_cast<int>(ctx->density_units.size());
-  if (const char *why = DensityUnitsRefusal(ctx, job.n_units)) throw Failure{BL_E_UNSUPPORTED, why};
-  job.base_rho = job.n_units == 1 ? ctx->density_units[0] : p.simulation_rho_cgs;
-  job.n_pol = static_cast<int>(ctx->pol_rho.size());
-  if (const char *why = PolarizedVariantsRefusal(ctx, job.n_pol)) throw Failure{BL_E_UNSUPPORTED, why};
-  if (job.n_pol >= 1) job.base_rho = ctx->pol_rho[0];   // (one triple: rendered as a fresh render with it in the parameter block)
+  job.variants = ResolveVariants(ctx);
+  const Variants &vs = job.variants;
+  if (const char *why = ElectronModelsRefusal(ctx, vs.n_models)) throw Failure{BL_E_UNSUPPORTED, why};
+  if (const char *why = DensityUnitsRefusal(ctx, vs.n_units)) throw Failure{BL_E_UNSUPPORTED, why};
+  if (const char *why = PolarizedVariantsRefusal(ctx, vs.n_pol)) throw Failure{BL_E_UNSUPPORTED, why};
+  // What BuildShadeArgs folds before a variant is bound: the first variant - one variant is a fresh render with it in the parameter
+  // block, and the first triple's cut decisions are every triple's in one pass. But several (model, unit) variants keep the parameter
+  // block's pair, and two or more units its unit too (so base_rho is the one set unit, the first triple's, else the parameter block's):
+  // the one-pass rows are built with them - the exact second pass divides the pair out again, the transfer kernel rescales by unit_x and
+  // unit_j - so another base changes roundings, and the unit the bytes of the BlShadeCold block that shade_cold_host is compared with.
+  const Variant &first = vs.list[0];
+  job.base_rho = first.rho, job.base_rat_low = first.rat_low, job.base_rat_high = first.rat_high;
+  if (vs.n_pol == 0 && vs.list.size() >= 2) job.base_rat_low = p.plasma_rat_low, job.base_rat_high = p.plasma_rat_high;
+  if (vs.n_units >= 2) job.base_rho = p.simulation_rho_cgs;
   job.n_nu = p.image_num_frequencies;
   job.n_q_model = ctx->image_num_quantities;
-  job.variant_passes = std::max(1, job.n_models) * std::max(1, job.n_units) * std::max(1, job.n_pol);
+  job.variant_passes = static_cast<int>(vs.list.size());
   job.n_q = job.n_q_model * job.variant_passes;
   job.max_steps = p.ray_max_steps;
   job.n_rays = d->n_rays;
@@ -486,17 +479,15 @@ void PlanJob(RenderJob &job) {
   // decides differently between models - nor, with two units or more, a rho, n_e, p_gas or B cut between units - a sample's row holds
   // what no model enters (BlFreqInputs, built with base_rho) and the transfer kernel forms each model's 1 / (k T_e) and scales the row
   // to each unit (everything else: one shading pass per variant over the shared samples, LaunchShadingStage)
-  const bool unit_cut = p.cut_rho_min >= 0.0 || p.cut_rho_max >= 0.0 || p.cut_n_e_min >= 0.0 || p.cut_n_e_max >= 0.0
-      || p.cut_p_gas_min >= 0.0 || p.cut_p_gas_max >= 0.0 || p.cut_b_min >= 0.0 || p.cut_b_max >= 0.0;
   job.variants_one_pass = job.variant_passes >= 2 && job.fast && p.plasma_power_frac == 0.0 && !job.tau_row && !job.aux && ctx->render_num_images == 0
-      && p.cut_theta_e_min < 0.0 && p.cut_theta_e_max < 0.0 && !(job.n_units >= 2 && unit_cut)
-      && !(job.n_units >= 2 && job.n_rays * job.n_nu * job.variant_passes >= (1ll << 31));   // (the transfer kernel's lanes of a chunk fit one grid)
+      && !ThetaECut(p) && !(vs.n_units >= 2 && UnitCut(p))
+      && !(vs.n_units >= 2 && job.n_rays * job.n_nu * job.variant_passes >= (1ll << 31));   // (the transfer kernel's lanes of a chunk fit one grid)
   if (job.variants_one_pass) {
     job.freq_split = true;
     job.variant_passes = 1;
   }
   // (the passes of two units or more compare the cut thresholds of their own unit: one BlShadeCold each)
-  job.n_cold = job.simulation && job.variant_passes >= 2 && job.n_units >= 2 ? job.n_units : 1;
+  job.n_cold = job.simulation && job.variant_passes >= 2 && vs.n_units >= 2 ? vs.n_units : 1;
   // Plain images of a spherical Kerr-Schild simulation with fallback values beyond the grid: nothing is recorded of the steps that
   // lie in the empty shell between the grid's outer edge and the camera's sphere (both tiers; the samples count as ever)
   job.skip_shell = job.simulation && !job.aux && !ctx->polarized && !job.slow && !job.geo_load && !job.geo_save && !job.sample_save
@@ -577,15 +568,14 @@ void PlanJob(RenderJob &job) {
   // Polarized variants in one pass: where no decision differs between them - a rho, n_e, p_gas or B cut only with one unit, a Theta_e
   // cut only with one unit and one pair (the units reach Theta_e through roundings), Stokes rows and the optical-depth row only (the
   // rows the polarized transfer kernels write), Theta_e from R_high / R_low (code_kappa: passes) - and the lanes of a chunk fit one grid
-  if (job.n_pol >= 2) {
+  if (vs.n_pol >= 2) {
     bool same_units = true, same_pairs = true;
-    for (int v = 1; v < job.n_pol; v++) {
-      same_units = same_units && ctx->pol_rho[v] == ctx->pol_rho[0];
-      same_pairs = same_pairs && ctx->pol_rat_low[v] == ctx->pol_rat_low[0] && ctx->pol_rat_high[v] == ctx->pol_rat_high[0];
+    for (const Variant &v : vs.list) {
+      same_units = same_units && v.rho == first.rho;
+      same_pairs = same_pairs && v.rat_low == first.rat_low && v.rat_high == first.rat_high;
     }
-    const bool theta_e_cut = p.cut_theta_e_min >= 0.0 || p.cut_theta_e_max >= 0.0;
-    job.pol_one_pass = job.rows_only && p.plasma_model != BL_PLASMA_CODE_KAPPA && !(unit_cut && !same_units)
-        && !(theta_e_cut && !(same_units && same_pairs)) && job.n_rays * job.n_pol < (1ll << 31);
+    job.pol_one_pass = job.rows_only && p.plasma_model != BL_PLASMA_CODE_KAPPA && !(UnitCut(p) && !same_units)
+        && !(ThetaECut(p) && !(same_units && same_pairs)) && job.n_rays * vs.n_pol < (1ll << 31);
     if (job.pol_one_pass) {
       job.variant_passes = 1;
       job.pol_coefficients_inside = false;   // (the samples go through the 64-byte row, which is where the variants part)
@@ -827,7 +817,7 @@ void ForEachRecordArray(const RenderJob &job, Slot &sl, Visitor &&visit) {
   if (use.pol) visit(sl.d_pol_samples, 1, true);
   if (use.pol_matrix) visit(sl.d_pol_matrix, BL_POL_MATRIX_DOUBLES, true);
   if (use.pol_coeffs) visit(sl.d_pol_coeffs, n_nu * 4, true);
-  if (use.pol_variant_coeffs) visit(sl.d_pol_variant_coeffs, n_nu * 4 * static_cast<size_t>(job.n_pol), false);
+  if (use.pol_variant_coeffs) visit(sl.d_pol_variant_coeffs, n_nu * 4 * static_cast<size_t>(job.variants.n_pol), false);
   if (use.coef_inputs) visit(sl.d_coef_inputs, 1, true);
   if (use.have_flags) visit(sl.d_have_flags, 1, true);
   if (use.anchors) visit(sl.d_anchors, 8, true);
@@ -1024,11 +1014,11 @@ void PlanScratch(RenderJob &job) {
     // what the set holds - else one shading pass per variant over the resident records, which needs nothing more)
     if (job.pol_one_pass) {
       const bl_ctx::ChunkSlot &sl = ctx->slot[0];
-      const uint64_t wanted = static_cast<uint64_t>(job.record_capacity) * n_nu * 4 * job.n_pol * sizeof(double2);
+      const uint64_t wanted = static_cast<uint64_t>(job.record_capacity) * n_nu * 4 * job.variants.n_pol * sizeof(double2);
       const uint64_t have = sl.d_pol_variant_coeffs.count * sizeof(double2);
       if (wanted > have && sl.Bytes() - have + wanted > ctx->scratch_limit) {
         job.pol_one_pass = false;
-        job.variant_passes = job.n_pol;
+        job.variant_passes = job.variants.n_pol;
       }
     }
     job.record_gate = static_cast<long long>(job.record_capacity);
@@ -1612,10 +1602,10 @@ void BuildShadeArgs(RenderJob &job) {
     BlPlasmaDevice &pl = sa.plasma;
     pl.plasma_mu = p.plasma_mu;
     pl.plasma_ne_ni = p.plasma_ne_ni;
-    pl.plasma_rat_low = job.n_pol >= 1 ? ctx->pol_rat_low[0] : p.plasma_rat_low;     // (bl_set_polarized_variants: the first triple, BindVariant the others)
-    pl.plasma_rat_high = job.n_pol >= 1 ? ctx->pol_rat_high[0] : p.plasma_rat_high;
+    pl.plasma_rat_low = job.base_rat_low;     // (the render's base, PlanJob; BindVariant each variant's)
+    pl.plasma_rat_high = job.base_rat_high;
     pl.plasma_thermal_frac = ctx->plasma_thermal_frac;
-    FoldUnits(ctx, job.base_rho, pl, sa.fast_k);            // simulation_coefficients.cpp:237-239 (bl_set_density_units: BindVariant)
+    FoldUnits(ctx, job.base_rho, pl, sa.fast_k);            // simulation_coefficients.cpp:237-239
     FillElectronConstants(job, pl, cold);
     cold.plasma_gamma = ctx->grid_meta.plasma_gamma;
     cold.plasma_gamma_i = ctx->grid_meta.plasma_gamma_i;
@@ -1684,7 +1674,7 @@ void BuildShadeArgs(RenderJob &job) {
       std::memcpy(static_cast<void *>(&unit_cold), &cold, sizeof(BlShadeCold));
       BlPlasmaDevice unit_pl = sa.plasma;
       double unit_k[8];
-      FoldUnits(ctx, ctx->density_units[u], unit_pl, unit_k);
+      FoldUnits(ctx, job.variants.list[u].rho, unit_pl, unit_k);   // (model-major: the first model's variants are the units)
       FoldFastCuts(ctx, unit_pl, unit_cold);
       std::memcpy(colds.data() + u * sizeof(BlShadeCold), &unit_cold, sizeof(BlShadeCold));
     }
@@ -1703,14 +1693,14 @@ void BuildShadeArgs(RenderJob &job) {
   sa.pol_variant_table = nullptr;
   if (job.pol_one_pass) {
     static_assert(BL_POL_MAX_VARIANTS == BL_MAX_POLARIZED_VARIANTS, "variant constants");
-    std::vector<BlPolVariant> table(job.n_pol);
-    for (int v = 0; v < job.n_pol; v++) {
+    std::vector<BlPolVariant> table;
+    for (const Variant &variant : job.variants.list) {
       BlPlasmaDevice variant_pl = sa.plasma;
       double variant_k[8];
-      variant_pl.plasma_rat_low = ctx->pol_rat_low[v];
-      variant_pl.plasma_rat_high = ctx->pol_rat_high[v];
-      FoldUnits(ctx, ctx->pol_rho[v], variant_pl, variant_k);
-      table[v] = BlPolVariant{variant_pl.d_unit, variant_pl.e_unit, variant_pl.b_unit, variant_pl.plasma_rat_high, variant_pl.plasma_rat_low, 0.0};
+      variant_pl.plasma_rat_low = variant.rat_low;
+      variant_pl.plasma_rat_high = variant.rat_high;
+      FoldUnits(ctx, variant.rho, variant_pl, variant_k);
+      table.push_back(BlPolVariant{variant_pl.d_unit, variant_pl.e_unit, variant_pl.b_unit, variant_pl.plasma_rat_high, variant_pl.plasma_rat_low, 0.0});
     }
     // (uploaded when it differs from what the device holds, as the cold block above: a fit's renders wait here only when their units change)
     std::vector<unsigned char> bytes(table.size() * sizeof(BlPolVariant));
@@ -1722,7 +1712,7 @@ void BuildShadeArgs(RenderJob &job) {
       Check(hipStreamSynchronize(stream), "variant table upload");
       ctx->pol_variant_host = bytes;
     }
-    sa.pol_variants = job.n_pol;
+    sa.pol_variants = job.variants.n_pol;
     sa.pol_variant_table = ctx->d_pol_variant_table.ptr;
   }
   sa.frequencies = ctx->d_freq.ptr;
@@ -1789,7 +1779,7 @@ void BuildTransferArgs(RenderJob &job) {
   xa.image = job.image;
   xa.n_models = 0;
   xa.n_units = 0;
-  xa.pol_variants = job.pol_one_pass ? job.n_pol : 0;
+  xa.pol_variants = job.pol_one_pass ? job.variants.n_pol : 0;
   xa.pol_variant_rows = job.n_q_model;
   if (job.variants_one_pass) {   // every model's R_high / R_low folded as BuildShadeArgs folds the parameter block's (fast_k[1..3])
     static_assert(BL_TRANSFER_MAX_MODELS == BL_MAX_ELECTRON_MODELS, "model constants");
@@ -1797,22 +1787,24 @@ void BuildTransferArgs(RenderJob &job) {
     const bool use_p = p.plasma_use_p != 0;
     const double g1 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_i - 1.0);
     const double g2 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_e - 1.0);
-    xa.n_models = std::max(1, job.n_models);   // (no models set: the parameter block's pair is model 0)
+    const Variants &vs = job.variants;
+    const int n_u = std::max(1, vs.n_units);   // (model-major: model m's variants start at m n_u, the first model's are the units)
+    xa.n_models = static_cast<int>(vs.list.size()) / n_u;   // (no models set: the parameter block's pair is model 0)
     for (int m = 0; m < xa.n_models; m++) {
-      xa.model_k1[m] = (job.n_models > 0 ? ctx->model_rat_high[m] : p.plasma_rat_high) * g1;
-      xa.model_k2[m] = (job.n_models > 0 ? ctx->model_rat_low[m] : p.plasma_rat_low) * g1;
+      xa.model_k1[m] = vs.list[m * n_u].rat_high * g1;
+      xa.model_k2[m] = vs.list[m * n_u].rat_low * g1;
     }
     xa.model_k3 = p.plasma_ne_ni * g2;
     // Two units or more: the rows hold base_rho's x at unit frequency (1 / b_unit: x = nu / nu_s, nu_s ~ nu_c ~ |b| b_unit) and s_j
     // (d_unit b_unit: n_e nu_c); unit u scales them by b_unit(base) / b_unit(u) and d_u b_unit(u) / (d_base b_unit(base)), with the
     // units of FoldUnits. (One unit is base_rho itself: the rows are that unit's.)
-    if (job.n_units >= 2) {
+    if (vs.n_units >= 2) {
       BlPlasmaDevice base{}, unit{};
       double k[8];
       FoldUnits(ctx, job.base_rho, base, k);
-      xa.n_units = job.n_units;
-      for (int u = 0; u < job.n_units; u++) {
-        FoldUnits(ctx, ctx->density_units[u], unit, k);
+      xa.n_units = vs.n_units;
+      for (int u = 0; u < vs.n_units; u++) {
+        FoldUnits(ctx, vs.list[u].rho, unit, k);
         xa.unit_x[u] = base.b_unit / unit.b_unit;
         xa.unit_j[u] = (unit.d_unit * unit.b_unit) / (base.d_unit * base.b_unit);
       }
@@ -2437,7 +2429,7 @@ void CollectChunk(RenderJob &job, int k) {
 }
 
 void DownloadChunk(RenderJob &job, long long begin, long long count);
-hipError_t DownloadColumns(const RenderJob &job, long long begin, long long count, int threads);
+hipError_t DownloadColumns(const RenderJob &job, long long begin, long long count);
 
 // A chunk of the rays [begin, begin + done) is complete (CollectChunk has waited for its kernels): large host outputs leave now
 void ChunkOutputs(RenderJob &job, long long begin, long long done) {
@@ -2445,7 +2437,7 @@ void ChunkOutputs(RenderJob &job, long long begin, long long done) {
     job.chunk_downloads = true;
     DownloadChunk(job, begin, done);
   } else if (job.chunk_downloads) {
-    Check(DownloadColumns(job, begin, done, 1), "download of a chunk's outputs");
+    Check(DownloadColumns(job, begin, done), "download of a chunk's outputs");
   }
 }
 
@@ -2564,62 +2556,19 @@ void RunChunks(RenderJob &job) {
 }
 
 // ---- results to the caller's host memory
-// Memory the runtime can copy into without staging (hipHostMalloc - bl_host_alloc - or hipHostRegister)
-bool IsPinnedHost(const void *p) {
-  hipPointerAttribute_t attr{};
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();   // (plain malloc memory is "invalid value" to the runtime)
-    return false;
-  }
-  return attr.type == hipMemoryTypeHost;
-}
-
-// `rows` rows of `width` bytes each, device -> host, both sides with a pitch. Pinned destination: one copy at the link's rate. Pageable:
-// the runtime stages such a copy through a buffer of its own at ~16 GB/s per calling thread (measured: 537 MB of image rows in
-// 33.7 ms, round 5); `threads` host threads, each with a share of the rows (or of the bytes of a single row), overlap their stagings.
-hipError_t CopyToHost(int device, void *dst, size_t dst_pitch, const void *src, size_t src_pitch, size_t width, size_t rows, int threads) {
-  if (width == 0 || rows == 0) return hipSuccess;
-  if (dst_pitch == width && src_pitch == width) {   // contiguous: one long row, cut anywhere
-    width *= rows;
-    rows = 1;
-    dst_pitch = src_pitch = width;
-  }
-  const size_t total = width * rows;
-  if (IsPinnedHost(dst) || threads <= 1 || total < (32ull << 20)) return hipMemcpy2D(dst, dst_pitch, src, src_pitch, width, rows, hipMemcpyDeviceToHost);
-  std::vector<hipError_t> status(threads, hipSuccess);
-  std::vector<std::thread> workers;
-  for (int t = 0; t < threads; t++) {
-    workers.emplace_back([=, &status]() {
-      status[t] = hipSetDevice(device);
-      if (status[t] != hipSuccess) return;
-      if (rows == 1) {   // shares of the bytes, on 4 KiB boundaries
-        const size_t share = ((width + threads - 1) / threads + 4095) / 4096 * 4096;
-        const size_t first = std::min(width, share * t), last = std::min(width, share * (t + 1));
-        if (last > first) status[t] = hipMemcpy(static_cast<char *>(dst) + first, static_cast<const char *>(src) + first, last - first, hipMemcpyDeviceToHost);
-      } else {
-        const size_t first = rows * t / threads, last = rows * (t + 1) / threads;
-        if (last > first)
-          status[t] = hipMemcpy2D(static_cast<char *>(dst) + first * dst_pitch, dst_pitch, static_cast<const char *>(src) + first * src_pitch, src_pitch, width, last - first,
-                                  hipMemcpyDeviceToHost);
-      }
-    });
-  }
-  for (std::thread &w : workers) w.join();
-  for (hipError_t e : status)
-    if (e != hipSuccess) return e;
-  return hipSuccess;
-}
-
-// The outputs of the rays [begin, begin + count) of the call - columns of every row - with `threads` host threads
-hipError_t DownloadColumns(const RenderJob &job, long long begin, long long count, int threads) {
+// The outputs of the rays [begin, begin + count) of the call: columns of every row, device -> host, both sides with a pitch. A pinned
+// destination takes the copy at the link's rate; into pageable memory the runtime stages it through a buffer of its own (~16 GB/s;
+// several host threads brought nothing - measured, 4 threads 41.6 ms against 33.7 for 537 MB: the pages' first touch is what it waits for)
+hipError_t DownloadColumns(const RenderJob &job, long long begin, long long count) {
   bl_ctx *ctx = job.ctx;
   const bl_render_desc *d = job.d;
   const size_t n_rays = static_cast<size_t>(job.n_rays), first = static_cast<size_t>(begin), n = static_cast<size_t>(count);
   hipError_t err = hipSuccess;
   auto rows = [&](void *dst, const void *src, size_t element, size_t n_rows) {   // [n_rows][n_rays] arrays of `element` bytes
-    if (dst == nullptr || err != hipSuccess) return;
-    err = CopyToHost(ctx->device, static_cast<char *>(dst) + first * element, n_rays * element, static_cast<const char *>(src) + first * element, n_rays * element, n * element, n_rows,
-                     threads);
+    if (dst == nullptr || err != hipSuccess || n == 0 || n_rows == 0) return;
+    size_t width = n * element, pitch = n_rays * element;
+    if (width == pitch) width *= n_rows, n_rows = 1, pitch = width;   // contiguous: one long row
+    err = hipMemcpy2D(static_cast<char *>(dst) + first * element, pitch, static_cast<const char *>(src) + first * element, pitch, width, n_rows, hipMemcpyDeviceToHost);
   };
   if (job.n_q > 0) rows(d->image, job.image, sizeof(double), static_cast<size_t>(job.n_q));
   rows(d->sample_num, job.out_num, sizeof(int), 1);
@@ -2639,7 +2588,7 @@ void DownloadChunk(RenderJob &job, long long begin, long long count) {
   const int device = job.ctx->device;
   job.downloads.emplace_back([=]() {
     *status = hipSetDevice(device);
-    if (*status == hipSuccess) *status = DownloadColumns(*const_job, begin, count, 1);
+    if (*status == hipSuccess) *status = DownloadColumns(*const_job, begin, count);
   });
 }
 
@@ -2652,7 +2601,7 @@ void DownloadOutputs(RenderJob &job) {
     for (hipError_t e : job.download_status) Check(e, "download of a chunk's outputs");
     return;
   }
-  Check(DownloadColumns(job, 0, job.n_rays, 1), "download of the outputs");   // (pageable memory: several threads bring nothing - measured, 4 threads 41.6 ms against 33.7 for 537 MB: the pages' first touch is what it waits for)
+  Check(DownloadColumns(job, 0, job.n_rays), "download of the outputs");
 }
 
 // bl_stats of the call, and the reference's warning about rays that ended unexpectedly (geodesics.cpp:389-394)

@@ -534,8 +534,8 @@ BL_API int bl_set_caller_stream(bl_ctx *ctx, void *stream, int enabled);
 BL_API int bl_set_geodesic_reuse(bl_ctx *ctx, int on);
 /* Host memory the device copies into at the link's rate (pinned: hipHostMalloc). bl_render recognises such buffers among the pointers
  * of bl_render_desc - and any the caller pinned itself (hipHostRegister) - and downloads into them with one asynchronous-engine copy
- * (537 MB of image rows: ~10 ms) where pageable memory goes through the runtime's staging buffer (~16 GB/s per thread; bl_render
- * then splits the copy over four host threads). Large results in many rows (eight image rows or more, a quarter of a GiB or more)
+ * (537 MB of image rows: ~10 ms) where pageable memory goes through the runtime's staging buffer (~16 GB/s: 34 ms; more host
+ * threads bring nothing, the pages' first touch is what such a copy waits for). Large results in many rows (eight image rows or more, a quarter of a GiB or more)
  * leave chunk by chunk while the next chunk renders, whichever kind of memory receives them. NULL when the allocation fails or
  * the context is host-only: fall back to malloc. Free with bl_host_free (NULL is fine). */
 BL_API void *bl_host_alloc(bl_ctx *ctx, size_t bytes);
