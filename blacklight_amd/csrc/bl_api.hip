@@ -741,8 +741,10 @@ void UploadMergedGrid(bl_ctx *ctx, const bl_grid_desc *g) {
     }
     ctx->grid_dev = dev;
     {
-      // The locate kernel stages the tables in LDS when they fit 60 KiB (up to ~640 cells per axis); larger grids
-      // are searched in the same tables where they lie in HBM (lds_table_bytes = 0).
+      // The locate kernel stages the tables in LDS when they fit 60 KiB: faces and centres as doubles and max(512, 8 n) 16-bit buckets
+      // per axis, 32 n + 8 bytes for an axis of 64 cells or more - about 640 cells on each of three axes, or 1 847 on one beside two
+      // of eight. (The kernels with the locate step inside have a budget of their own: 1 018 cells summed over the axes,
+      // bl_fused2_applicable.) Larger grids are searched in the same tables where they lie in HBM (lds_table_bytes = 0).
       size_t bytes = 0;
       for (int a = 0; a < 3; a++) bytes += (2 * static_cast<size_t>(n[a]) + 1) * sizeof(double) + static_cast<size_t>(dev.n_bucket[a]) * sizeof(unsigned short);
       ctx->lds_table_bytes = bytes > 60 * 1024 ? 0 : static_cast<int>((bytes + 15) / 16 * 16);

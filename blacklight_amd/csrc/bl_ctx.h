@@ -40,6 +40,10 @@ extern "C" hipError_t bl_launch_shade_fused2(const BlShadeArgs *args, const Kern
 extern "C" hipError_t bl_launch_shade_exact2(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream);
 extern "C" hipError_t bl_launch_shade_polarized2(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream);
 extern "C" hipError_t bl_launch_shade_redo(const BlShadeArgs *args, const KernelPlan::Redo &plan, int grid, hipStream_t stream);
+// (where each stage that finds cells reads the coordinate tables, and its launch: what the wrappers above launch from, TableLaunch)
+extern "C" void bl_locate_tables(const BlShadeArgs *args, const KernelPlan::Locate &plan, int grid, int lds_bytes, TableLaunch *out);
+extern "C" void bl_shade_inside_tables(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, TableLaunch *out);   // kFused2, kExact2, kPolarized2
+extern "C" void bl_shade_redo_tables(const BlShadeArgs *args, const KernelPlan::Redo &plan, int grid, TableLaunch *out);
 extern "C" int bl_fused2_applicable(const BlGridDevice *grid, int n_nu, long long n_rays);
 extern "C" int bl_fused2_refined_applicable(const BlGridDevice *grid, int n_nu, long long n_rays);
 extern "C" int bl_polarized2_refined_applicable(const BlGridDevice *grid, long long n_rays);

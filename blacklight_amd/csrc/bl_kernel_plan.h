@@ -55,4 +55,18 @@ struct KernelPlan {
   enum PolarizedRoute { kUnpolarized, kTensor, kMatrix, kMatricesBeside } polarized = kUnpolarized;
 };
 
+// Where a stage that finds a sample's cell reads the grid's coordinate tables, and the launch that follows from their size. One helper
+// beside each launch wrapper fills it (bl_locate_tables, bl_shade_inside_tables, bl_shade_redo_tables); the wrapper launches from what the
+// helper returned and the `tables:` debug line prints the same values (DescribeTables, bl_render.hip).
+struct TableLaunch {
+  // kNone: the stage does not run or finds no cells; kLds: tables staged in LDS; kHbm: searched where they lie in HBM; kLocated: the
+  // stage reads the samples a locate kernel left
+  enum Where { kNone, kLds, kHbm, kLocated } where = kNone;
+  int table_bytes = 0;     // kLds: bytes of tables staged
+  size_t lds_bytes = 0;    // dynamic LDS of the launch: the tables and what lies behind them
+  int raise_to = 0;        // > 0: hipFuncAttributeMaxDynamicSharedMemorySize asked for before the launch
+  int lanes = 256, blocks = 0;
+  int grid = 0;            // the count of 256-lane workgroups the render asked for, from which `blocks` follows
+};
+
 #endif  // BLACKLIGHT_AMD_BL_KERNEL_PLAN_H_

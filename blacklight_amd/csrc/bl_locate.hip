@@ -249,6 +249,31 @@ static void (*locate_kernel(const KernelPlan::Locate &l))(BlShadeArgs) {
   return l.slow ? bl_locate_kernel<false, true, false> : bl_locate_kernel<false, false, false>;
 }
 
+// Where the locate kernel reads the tables and the launch that follows (lds_bytes: the merged grid's tables, bl_ctx::lds_table_bytes).
+// A mesh with refinement - tables that fit four times into a compute unit's LDS (36 KiB): 256-lane workgroups. Larger ones (up to
+// BL_LOCATE_REFINED_LDS): one 1 024-lane workgroup to a compute unit, one round of them. Beyond that the tables are searched where they
+// lie in HBM (refined_lds_bytes = 0). Behind the tables: the waves' lists of samples that wait for FindNearbyInds, 1 KiB each.
+extern "C" void bl_locate_tables(const BlShadeArgs *args, const KernelPlan::Locate &plan, int grid, int lds_bytes, TableLaunch *out) {
+  TableLaunch t;
+  t.grid = grid;
+  if (plan.refined) {
+    t.table_bytes = args->general_locate ? 0 : args->grid.refined_lds_bytes;
+    const bool four_to_a_unit = t.table_bytes <= 36 * 1024;
+    t.lanes = four_to_a_unit ? 256 : 1024;
+    t.lds_bytes = (size_t)(t.table_bytes + 7) / 8 * 8 + (size_t)(t.lanes / 64) * 1024;
+    // (`grid` counts 256-lane workgroups: sixteen to a compute unit when the kernel runs alone - then one large workgroup per unit - or one
+    // to a unit beside the next chunk's stepper - then as many lanes as that)
+    t.blocks = four_to_a_unit ? grid : (grid >= 1024 ? grid / 16 : (grid >= 4 ? grid / 4 : 1));
+    t.raise_to = t.lds_bytes > 64 * 1024 ? BL_LOCATE_REFINED_LDS + 16 * 1024 : 0;
+  } else {   // (a merged grid with tables beyond the LDS budget searches them in HBM: lds_bytes = 0)
+    t.table_bytes = lds_bytes;
+    t.lds_bytes = (size_t)lds_bytes;
+    t.blocks = grid;
+  }
+  t.where = t.table_bytes > 0 ? TableLaunch::kLds : TableLaunch::kHbm;
+  *out = t;
+}
+
 // Locate kernel (simulation mode only); lds_bytes = size of the coordinate tables it stages in LDS
 extern "C" hipError_t bl_launch_locate(const BlShadeArgs *args, const KernelPlan::Locate &plan, int grid, int lds_bytes, hipStream_t stream) {
   void (*kernel)(BlShadeArgs) = locate_kernel(plan);
@@ -258,24 +283,12 @@ extern "C" hipError_t bl_launch_locate(const BlShadeArgs *args, const KernelPlan
   if (kernel == nullptr || args->located == nullptr || plan.refined != (args->grid.n_blocks > 0) || plan.slow != (args->slow.n > 0)
       || (plan.spin_zero && args->st.bh_a != 0.0) || (!plan.refined && plan.tables_in_hbm != (lds_bytes == 0))
       || (plain && (plan.refined || plan.slow || args->anchors != nullptr || args->general_locate))) return hipErrorInvalidValue;
-  if (plan.refined) {
-    // Tables that fit four times into a compute unit's LDS (36 KiB): 256-lane workgroups. Larger ones (up to BL_LOCATE_REFINED_LDS): one
-    // 1 024-lane workgroup to a compute unit, one round of them. Beyond that the tables are searched where they lie in HBM
-    // (refined_lds_bytes = 0). Behind the tables: the waves' lists of samples that wait for FindNearbyInds, 1 KiB each.
-    const int table_bytes = args->general_locate ? 0 : args->grid.refined_lds_bytes;
-    const bool four_to_a_unit = table_bytes <= 36 * 1024;
-    const int lanes = four_to_a_unit ? 256 : 1024;
-    const size_t bytes = (size_t)(table_bytes + 7) / 8 * 8 + (size_t)(lanes / 64) * 1024;
-    // (`grid` counts 256-lane workgroups: sixteen to a compute unit when the kernel runs alone - then one large workgroup per unit - or one
-    // to a unit beside the next chunk's stepper - then as many lanes as that)
-    const dim3 blocks(four_to_a_unit ? grid : (grid >= 1024 ? grid / 16 : (grid >= 4 ? grid / 4 : 1)));
-    if (bytes > 64 * 1024) {
-      const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BL_LOCATE_REFINED_LDS + 16 * 1024);
-      if (err != hipSuccess) return err;
-    }
-    hipLaunchKernelGGL(kernel, blocks, dim3(lanes), bytes, stream, *args);
-  } else {   // (a merged grid with tables beyond the LDS budget searches them in HBM: lds_bytes = 0)
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds_bytes, stream, *args);
+  TableLaunch t;
+  bl_locate_tables(args, plan, grid, lds_bytes, &t);
+  if (t.raise_to > 0) {
+    const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, t.raise_to);
+    if (err != hipSuccess) return err;
   }
+  hipLaunchKernelGGL(kernel, dim3(t.blocks), dim3(t.lanes), t.lds_bytes, stream, *args);
   return hipGetLastError();
 }

@@ -257,6 +257,9 @@ struct RenderJob {
   float ms_geo = 0.0f, ms_locate = 0.0f, ms_shade = 0.0f, ms_transfer = 0.0f;
   unsigned long long total_samples = 0, total_flagged = 0, total_records = 0, total_gathers = 0, total_redo = 0, total_undefined = 0, total_parked = 0, max_num = 0;
   unsigned long long debug_counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // (BLACKLIGHT_AMD_DEBUG_COUNTERS: the tables and launch of the locate kernel - the first chunk's and the last one's, which differ
+  // when chunks overlap - of the coefficient kernel and of the exact second pass)
+  TableLaunch tables_locate, tables_locate_last, tables_inside, tables_redo;
   CheckpointSave save;
   // checkpoint_sample_save: where every kept sample of the level sits on the grid, by pixel and reversed sample index
   bool sample_save = false;
@@ -308,6 +311,25 @@ std::string DescribeKernels(const KernelPlan &k) {
                           : std::string("<") + integrators[g.integrator > 2 || g.integrator < 0 ? 2 : g.integrator] + "," + std::to_string(g.with_time) + "," + std::to_string(g.spin_zero) + "," + std::to_string(g.shell) + ">");
   if (k.quad.park || k.quad.split) text += std::string(k.quad.split ? " split+quad=" : " quad=") + args({k.quad.spin_zero});
   return text;
+}
+
+// ... and where each stage that finds cells read the coordinate tables, with the launch that followed (the launch wrappers' own
+// values: TableLaunch). lds:<bytes of tables>x<lanes>@<workgroups>/<256-lane workgroups asked for>, hbm, located or none; the locate
+// kernel's last launch behind a comma where its workgroups differ from the first's (overlapping chunks)
+std::string DescribeTables(const TableLaunch &locate, const TableLaunch &locate_last, const TableLaunch &inside, const TableLaunch &redo) {
+  auto shape = [](const TableLaunch &t) { return "x" + std::to_string(t.lanes) + "@" + std::to_string(t.blocks) + "/" + std::to_string(t.grid); };
+  auto stage = [&](const TableLaunch &t, bool with_shape) -> std::string {
+    switch (t.where) {
+      case TableLaunch::kNone: return "none";
+      case TableLaunch::kLocated: return "located";
+      case TableLaunch::kHbm: return "hbm" + (with_shape ? shape(t) : std::string());
+      case TableLaunch::kLds: return "lds:" + std::to_string(t.table_bytes) + (with_shape ? shape(t) : std::string());
+    }
+    return "none";
+  };
+  const bool differs = locate_last.blocks != locate.blocks || locate_last.grid != locate.grid;
+  return "locate=" + stage(locate, true) + (differs ? ",@" + std::to_string(locate_last.blocks) + "/" + std::to_string(locate_last.grid) : std::string())
+      + " fused=" + stage(inside, true) + " redo=" + stage(redo, false);
 }
 
 hipEvent_t *SlotEvents(RenderJob &job, int k) { return job.ctx->events.data() + static_cast<size_t>(k) * kEventsPerChunk; }
@@ -720,6 +742,7 @@ void KeepResident(RenderJob &job) {
     std::fprintf(stderr, "scratch plan: bytes_per_record %llu, record_capacity %zu, record_gate %lld, geo_grid %d, n_slots %d, arrays 0x%05x\n", static_cast<unsigned long long>(job.bytes_per_record),
                  job.record_capacity, job.record_gate, job.geo_grid, job.n_slots, job.use.Mask());
   if (ctx->debug_counters) std::fprintf(stderr, "kernels: %s\n", DescribeKernels(job.kernels).c_str());
+  if (ctx->debug_counters) std::fprintf(stderr, "tables: %s\n", DescribeTables(job.tables_locate, job.tables_locate_last, job.tables_inside, job.tables_redo).c_str());
   if (job.keepable && !job.reuse) {
     res.valid = false;
     res.super_tiles = job.super_tiles;
@@ -2319,14 +2342,24 @@ void LaunchShadingStage(RenderJob &job, int k, bool geodesic_beside, hipStream_t
       case KernelPlan::Shade::kPolarized2: err = bl_launch_shade_polarized2(&sa, plan.shade, job.shade_grid, stream); break;
     }
     Check(err, "coefficient kernel launch");
+    if (ctx->debug_counters && job.locate_inside) bl_shade_inside_tables(&sa, plan.shade, job.shade_grid, &job.tables_inside);
     // (the exact tier's kernel over the records the tolerant kernel deferred)
-    if (plan.redo.run)
-      Check(bl_launch_shade_redo(&sa, plan.redo, plan.shade.family == KernelPlan::Shade::kFormulaFast ? ctx->num_cus * 4 * 4 : job.shade_grid, stream), "coefficient kernel launch");
+    if (plan.redo.run) {
+      const int redo_grid = plan.shade.family == KernelPlan::Shade::kFormulaFast ? ctx->num_cus * 4 * 4 : job.shade_grid;
+      Check(bl_launch_shade_redo(&sa, plan.redo, redo_grid, stream), "coefficient kernel launch");
+      if (ctx->debug_counters) bl_shade_redo_tables(&sa, plan.redo, redo_grid, &job.tables_redo);
+    }
   };
   Check(hipStreamWaitEvent(stream, e[1], 0), "stream wait");
   Check(hipEventRecord(e[2], stream), "event");
-  if (plan.locate.kind != KernelPlan::Locate::kNone)
-    Check(bl_launch_locate(&sa, plan.locate, geodesic_beside ? job.locate_grid_shared : job.locate_grid_alone, ctx->lds_table_bytes, stream), "locate kernel launch");
+  if (plan.locate.kind != KernelPlan::Locate::kNone) {
+    const int locate_grid = geodesic_beside ? job.locate_grid_shared : job.locate_grid_alone;
+    Check(bl_launch_locate(&sa, plan.locate, locate_grid, ctx->lds_table_bytes, stream), "locate kernel launch");
+    if (ctx->debug_counters) {
+      bl_locate_tables(&sa, plan.locate, locate_grid, ctx->lds_table_bytes, &job.tables_locate_last);
+      if (job.tables_locate.where == TableLaunch::kNone) job.tables_locate = job.tables_locate_last;
+    }
+  }
   Check(hipEventRecord(e[3], stream), "event");
   for (int v = 0; v < job.variant_passes; v++) {
     if (v > 0) {   // what the shading stage adds to the chunk's counters starts again from zero (ClearShadingCounters)

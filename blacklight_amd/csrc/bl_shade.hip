@@ -445,14 +445,28 @@ static BlShadeKernel shade_redo_kernel(const KernelPlan::Redo &r) {
   return r.spin_zero ? bl_shade_kernel<kSim, false, false, true, false, true, true> : bl_shade_kernel<kSim, false, false, true, false, false, true>;
 }
 
+// Where the second pass finds its cells: behind a locate kernel it reads the located samples; behind a kernel with the locate step
+// inside it locates the listed samples itself, on the tables in HBM - or, over a mesh with inter-block interpolation, on the mesh's
+// tables in LDS where they fit BL_REDO_TABLES_LDS (the kernel looks for them there under the same condition)
+extern "C" void bl_shade_redo_tables(const BlShadeArgs *args, const KernelPlan::Redo &plan, int grid, TableLaunch *out) {
+  TableLaunch t;
+  t.grid = t.blocks = grid;
+  if (plan.run && plan.model == BL_MODEL_SIMULATION) {
+    const bool tables_fit = args->located == nullptr && args->grid.n_blocks > 0 && args->grid.refined_lds_bytes > 0 && args->grid.refined_lds_bytes <= BL_REDO_TABLES_LDS;
+    t.table_bytes = plan.extended && tables_fit ? args->grid.refined_lds_bytes : 0;
+    t.lds_bytes = (size_t)t.table_bytes;
+    t.where = args->located != nullptr ? TableLaunch::kLocated : (t.table_bytes > 0 ? TableLaunch::kLds : TableLaunch::kHbm);
+  }
+  *out = t;
+}
+
 extern "C" hipError_t bl_launch_shade_redo(const BlShadeArgs *args, const KernelPlan::Redo &plan, int grid, hipStream_t stream) {
   BlShadeKernel kernel = shade_redo_kernel(plan);
-  // (table_bytes: behind the fused kernel over a mesh with inter-block interpolation, room for the mesh's tables in LDS - the kernel
-  // looks for them there under the same condition)
-  const bool tables_fit = args->located == nullptr && args->grid.n_blocks > 0 && args->grid.refined_lds_bytes > 0 && args->grid.refined_lds_bytes <= BL_REDO_TABLES_LDS;
+  TableLaunch t;
+  bl_shade_redo_tables(args, plan, grid, &t);
   if (!plan.run || kernel == nullptr || args->redo_list == nullptr || (plan.spin_zero && args->st.bh_a != 0.0)
-      || plan.table_bytes != (plan.extended && tables_fit ? args->grid.refined_lds_bytes : 0)
+      || plan.table_bytes != t.table_bytes
       || (!plan.extended && (args->tau_inc != nullptr || args->anchors != nullptr || args->slow.n > 0))) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), (size_t)plan.table_bytes, stream, *args);
+  hipLaunchKernelGGL(kernel, dim3(t.blocks), dim3(t.lanes), t.lds_bytes, stream, *args);
   return hipGetLastError();
 }

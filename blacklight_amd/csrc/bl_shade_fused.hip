@@ -1535,6 +1535,41 @@ static hipError_t launch_with_lds(BlShadeKernel kernel, dim3 blocks, dim3 lanes,
   return hipGetLastError();
 }
 
+static hipError_t launch_with_lds(BlShadeKernel kernel, const TableLaunch &t, hipStream_t stream, const BlShadeArgs *args) {
+  return launch_with_lds(kernel, dim3(t.blocks), dim3(t.lanes), t.lds_bytes, t.raise_to, stream, args);
+}
+
+// The tables and the launch of the three kernels with the locate step inside (`grid`: 256-lane workgroups). They always stage the
+// tables in LDS - the render chooses them only where those fit: bl_fused2_applicable, bl_fused2_refined_applicable,
+// bl_polarized2_refined_applicable.
+//   - the exact and the polarized kernel: a mesh's tables with two 256-lane workgroups to a compute unit, up to 76 KiB each
+//   - the tolerant kernel over one block: at most 64 KiB (bl_fused2_applicable); over a mesh whose tables fit twice into a compute
+//     unit's LDS: 256-lane workgroups as for one block (`grid` of them). Larger ones: one 512-lane workgroup to a compute unit, and one
+//     round of them (a workgroup's LDS is free for the next only when its last wave has ended: with several rounds every round's tail
+//     idles seven waves; measured 29.6 against 27.5 ms on the mesh that fits either way). Behind the tables: the waves' lists of
+//     samples for the exact pass; up to BL_FUSED_REFINED_LDS of the compute unit's 160 KiB
+extern "C" void bl_shade_inside_tables(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, TableLaunch *out) {
+  const BlGridDevice &g = args->grid;
+  TableLaunch t;
+  t.grid = grid;
+  t.where = TableLaunch::kLds;
+  t.blocks = grid;
+  if (plan.family != KernelPlan::Shade::kFused2) {
+    t.lds_bytes = fused_tables_lds(g, false);
+    t.raise_to = t.lds_bytes > 64 * 1024 ? 76 * 1024 : 0;
+  } else if (!plan.refined) {
+    t.lds_bytes = fused_tables_lds(g, true);
+  } else {
+    const bool two_to_a_unit = g.fused_lds_bytes <= 76 * 1024;
+    t.blocks = two_to_a_unit ? grid : (grid >= 8 ? grid / 8 : 1);
+    t.lanes = two_to_a_unit ? 256 : 512;
+    t.lds_bytes = fused_tables_lds(g, true) + (size_t)(t.lanes / 64) * 512;
+    t.raise_to = g.fused_lds_bytes + 4096 > 64 * 1024 ? BL_FUSED_REFINED_LDS + 4096 : 0;
+  }
+  t.table_bytes = (int)fused_tables_lds(g, plan.family == KernelPlan::Shade::kFused2);
+  *out = t;
+}
+
 // bl_shade_polarized2_kernel<spin_zero, records, coefficients>: with or without BlAuxSample records; the polarized coefficients
 // evaluated inside only without records and with zero spin (the plan: one frequency, thermal electrons only)
 static BlShadeKernel shade_polarized2_kernel(const KernelPlan::Shade &c) {
@@ -1549,17 +1584,18 @@ extern "C" hipError_t bl_launch_shade_polarized2(const BlShadeArgs *args, const 
   if (kernel == nullptr || args->located != nullptr || args->pol_samples == nullptr || args->coef_inputs == nullptr) return hipErrorInvalidValue;
   if (plan.records != (args->aux_record_unused == 0) || (plan.records && args->aux == nullptr) || plan.coefficients != (args->have_flags != nullptr)
       || (plan.spin_zero && args->st.bh_a != 0.0)) return hipErrorInvalidValue;
-  // (a mesh's tables, two 256-lane workgroups to a compute unit: up to 76 KiB each - bl_polarized2_refined_applicable)
-  const size_t lds = fused_tables_lds(args->grid, false);
-  return launch_with_lds(kernel, dim3(grid), dim3(256), lds, lds > 64 * 1024 ? 76 * 1024 : 0, stream, args);
+  TableLaunch t;
+  bl_shade_inside_tables(args, plan, grid, &t);
+  return launch_with_lds(kernel, t, stream, args);
 }
 
 // (the exact tier's use of the fused kernel: one frequency, plain image; bl_render.hip checks the rest with bl_fused2_applicable)
 extern "C" hipError_t bl_launch_shade_exact2(const BlShadeArgs *args, const KernelPlan::Shade &plan, int grid, hipStream_t stream) {
   if (plan.family != KernelPlan::Shade::kExact2 || args->located != nullptr || (plan.spin_zero && args->st.bh_a != 0.0)) return hipErrorInvalidValue;
   BlShadeKernel kernel = plan.spin_zero ? bl_shade_exact2_kernel<true> : bl_shade_exact2_kernel<false>;
-  const size_t lds = fused_tables_lds(args->grid, false);   // (a mesh's tables: two workgroups to a compute unit, as the polarized kernel)
-  return launch_with_lds(kernel, dim3(grid), dim3(256), lds, lds > 64 * 1024 ? 76 * 1024 : 0, stream, args);
+  TableLaunch t;
+  bl_shade_inside_tables(args, plan, grid, &t);
+  return launch_with_lds(kernel, t, stream, args);
 }
 
 // Whether a render can take this kernel (the caller has checked what the locate step inside needs, one frequency without the
@@ -1613,13 +1649,7 @@ extern "C" hipError_t bl_launch_shade_fused2(const BlShadeArgs *args, const Kern
   if (kernel == nullptr || args->located != nullptr || args->redo_list == nullptr || plan.refined != (g.n_blocks > 0)
       || plan.composed != (args->composed != nullptr) || plan.factors != (args->freq_split != 0) || (plan.spin_zero && args->st.bh_a != 0.0)
       || (plan.refined && g.fused_lds_bytes <= 0)) return hipErrorInvalidValue;
-  if (!plan.refined) return launch_with_lds(kernel, dim3(grid), dim3(256), fused_tables_lds(g, true), 0, stream, args);   // (at most 64 KiB: bl_fused2_applicable)
-  // Tables that fit twice into a compute unit's LDS: 256-lane workgroups as for one block (`grid` of them). Larger ones: one 512-lane
-  // workgroup to a compute unit, and one round of them (a workgroup's LDS is free for the next only when its last wave has ended:
-  // with several rounds every round's tail idles seven waves; measured 29.6 against 27.5 ms on the mesh that fits either way)
-  const bool two_to_a_unit = g.fused_lds_bytes <= 76 * 1024;
-  const dim3 blocks(two_to_a_unit ? grid : (grid >= 8 ? grid / 8 : 1)), lanes(two_to_a_unit ? 256 : 512);
-  // (+ the waves' lists of samples for the exact pass; up to BL_FUSED_REFINED_LDS of the compute unit's 160 KiB)
-  const size_t lds_bytes = fused_tables_lds(g, true) + (size_t)(lanes.x / 64) * 512;
-  return launch_with_lds(kernel, blocks, lanes, lds_bytes, g.fused_lds_bytes + 4096 > 64 * 1024 ? BL_FUSED_REFINED_LDS + 4096 : 0, stream, args);
+  TableLaunch t;
+  bl_shade_inside_tables(args, plan, grid, &t);
+  return launch_with_lds(kernel, t, stream, args);
 }
