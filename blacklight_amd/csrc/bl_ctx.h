@@ -1,6 +1,7 @@
 // bl_ctx.h - the context behind the C-ABI handle (include/blacklight_amd.h) and the few helpers the host-side
-// translation units of the HIP path share: bl_api.hip (construction, validation, grid upload, settings) and
-// bl_render.hip (bl_render: chunk planning, kernel pipeline, geodesic checkpoints, statistics). Internal, hidden visibility.
+// translation units of the HIP path share: bl_api.hip (construction, validation, grid upload, settings),
+// bl_render.hip (bl_render: chunk planning, kernel pipeline, statistics) and bl_checkpoint.cpp (the checkpoint files and their
+// conversions, host code only). Internal, hidden visibility.
 #ifndef BLACKLIGHT_AMD_BL_CTX_H_
 #define BLACKLIGHT_AMD_BL_CTX_H_
 #include <hip/hip_runtime.h>

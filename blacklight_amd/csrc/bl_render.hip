@@ -1,18 +1,16 @@
 // bl_render.hip - bl_render(): the reference's GeodesicIntegrator::Integrate() + RadiationIntegrator::Integrate() for one
 // level of rays (src/blacklight.cpp:93-94, 203-204) as a pipeline of HIP kernels over chunks of rays, and what hangs off
-// it: geodesic checkpoints (geodesic_checkpoint.cpp:28-108), statistics, the reference's warning texts.
+// it: when checkpoints are read and written and what of a chunk is copied for them (the files themselves: bl_checkpoint.cpp),
+// statistics, the reference's warning texts.
 //
 // One call = plan (which kernels, what a sample costs in HBM) -> scratch -> kernel arguments -> chunks -> outputs.
 // A chunk is not sized on the host: every scratch array has one entry per sample record (or per kept sample), a scratch set
 // holds `record_capacity` of each, and the geodesic kernel hands out rays only while the records of the rays in flight
 // are sure to fit (BlTraceArgs::record_gate). What it did not get to is the next chunk. The benchmark frame - 704 samples
 // per ray where ray_max_steps allows 2 000 - is one chunk this way; sized for the worst case it was two.
-#include <sys/stat.h>
-
 #include <thread>
-#include <type_traits>
 
-#include "bl_ctx.h"
+#include "bl_checkpoint.h"
 
 namespace {
 
@@ -49,101 +47,6 @@ void EnsureRenderResources(bl_ctx *ctx) {
     Check(hipHostMalloc(reinterpret_cast<void **>(&ctx->host_counters), 2 * BL_CNT_TOTAL * sizeof(unsigned long long), hipHostMallocDefault),
           "hipHostMalloc");
 }
-
-// ---- geodesic checkpoints (geodesic_checkpoint.cpp:28-108, file_io.cpp:65-127): 7 x 4 doubles of camera frame, then Arrays
-// - five int32 dimensions n1 ... n5 (fastest first) followed by the data - of camera_pos (n_pix, 4), camera_dir (n_pix, 4),
-// image_frequencies, momentum_factors (n_pix), the int geodesic_num_steps, sample_flags (n_pix, bool), sample_num (n_pix, int),
-// sample_pos (n_pix, n_steps, 4), sample_dir (n_pix, n_steps, 4), sample_len (n_pix, n_steps); root level only.
-template <typename T>
-void ReadCheckpointArray(std::ifstream &in, std::vector<T> *data, int dims[5]) {
-  in.read(reinterpret_cast<char *>(dims), 5 * sizeof(int));
-  size_t count = 1;
-  for (int a = 0; a < 5; a++) count *= static_cast<size_t>(std::max(dims[a], 1));
-  if (!in || count > (1ull << 36) / sizeof(T)) throw Failure{BL_E_INPUT, "Geodesic checkpoint file is damaged."};
-  data->resize(count);
-  in.read(reinterpret_cast<char *>(data->data()), static_cast<std::streamsize>(count * sizeof(T)));
-  if (!in) throw Failure{BL_E_INPUT, "Geodesic checkpoint file is damaged."};
-}
-
-std::shared_ptr<const bl_ctx::Checkpoint> ReadGeodesicCheckpoint(const bl_params &p) {
-  std::ifstream in(p.checkpoint_geodesic_file.s, std::ios_base::in | std::ios_base::binary);
-  if (!in.is_open()) throw Failure{BL_E_INPUT, "Could not open geodesic checkpoint file."};
-  auto loaded = std::make_shared<bl_ctx::Checkpoint>();
-  bl_ctx::Checkpoint &c = *loaded;
-  for (double (&v)[4] : c.frame) in.read(reinterpret_cast<char *>(v), 4 * sizeof(double));
-  const size_t n_pix = static_cast<size_t>(p.camera_resolution) * p.camera_resolution;
-  int dims[5];
-  std::vector<double> &frequencies = c.frequencies;
-  ReadCheckpointArray(in, &c.camera_pos, dims);
-  ReadCheckpointArray(in, &c.camera_dir, dims);
-  ReadCheckpointArray(in, &frequencies, dims);
-  ReadCheckpointArray(in, &c.factors, dims);
-  in.read(reinterpret_cast<char *>(&c.num_steps), sizeof(int));
-  ReadCheckpointArray(in, &c.flags, dims);
-  ReadCheckpointArray(in, &c.sample_num, dims);
-  ReadCheckpointArray(in, &c.pos, dims);
-  ReadCheckpointArray(in, &c.dir, dims);
-  ReadCheckpointArray(in, &c.len, dims);
-  const size_t steps = static_cast<size_t>(std::max(c.num_steps, 0));
-  if (c.camera_pos.size() != 4 * n_pix || c.camera_dir.size() != 4 * n_pix || c.factors.size() != n_pix || c.flags.size() != n_pix
-      || c.sample_num.size() != n_pix || c.pos.size() != n_pix * steps * 4 || c.dir.size() != n_pix * steps * 4
-      || c.len.size() != n_pix * steps || static_cast<int>(frequencies.size()) != p.image_num_frequencies || c.num_steps > p.ray_max_steps)
-    throw Failure{BL_E_INPUT, "Geodesic checkpoint does not match this camera (resolution, frequencies or ray_max_steps)."};
-  for (size_t m = 0; m < n_pix; m++)
-    if (c.sample_num[m] < 0 || c.sample_num[m] > c.num_steps) throw Failure{BL_E_INPUT, "Geodesic checkpoint file is damaged."};
-  return loaded;
-}
-
-// LoadGeodesics() for this context. The file's contents are shared between the contexts of a process that load the same file for the
-// same camera (path, size, modification time, resolution, frequencies, ray_max_steps): the table holds weak references, so the
-// memory goes when the last context that uses it does.
-void LoadGeodesicCheckpoint(bl_ctx *ctx) {
-  static std::mutex table_lock;
-  static std::map<std::string, std::weak_ptr<const bl_ctx::Checkpoint>> table;
-  const bl_params &p = ctx->params;
-  struct stat info {};
-  std::string key = p.checkpoint_geodesic_file.s;
-  if (stat(p.checkpoint_geodesic_file.s, &info) == 0)
-    key += "|" + std::to_string(static_cast<long long>(info.st_size)) + "|" + std::to_string(static_cast<long long>(info.st_mtim.tv_sec)) + "."
-        + std::to_string(static_cast<long long>(info.st_mtim.tv_nsec)) + "|" + std::to_string(static_cast<long long>(info.st_ctim.tv_sec)) + "."
-        + std::to_string(static_cast<long long>(info.st_ctim.tv_nsec)) + "|" + std::to_string(static_cast<long long>(info.st_ino));   // (a file rewritten in place within a second is another file)
-  key += "|" + std::to_string(p.camera_resolution) + "|" + std::to_string(p.image_num_frequencies) + "|" + std::to_string(p.ray_max_steps);
-  // (The table's lock covers the look-up only. Two contexts that ask for the same file for the first time at the same moment both read
-  // it - tens of GB at 1024^2 - and the second keeps the first one's copy; a context that loads another file never waits behind them.)
-  std::shared_ptr<const bl_ctx::Checkpoint> loaded;
-  {
-    std::lock_guard<std::mutex> guard(table_lock);
-    loaded = table[key].lock();
-  }
-  if (!loaded) {
-    std::shared_ptr<const bl_ctx::Checkpoint> mine = ReadGeodesicCheckpoint(p);
-    std::lock_guard<std::mutex> guard(table_lock);
-    loaded = table[key].lock();
-    if (!loaded) {
-      loaded = mine;
-      table[key] = loaded;
-    }
-  }
-  bl_camera_frame &f = ctx->frame;
-  double *vectors[7] = {f.cam_x, f.u_con, f.u_cov, f.norm_con, f.norm_con_c, f.hor_con_c, f.vert_con_c};
-  for (int v = 0; v < 7; v++) std::memcpy(vectors[v], loaded->frame[v], 4 * sizeof(double));
-  ctx->frequencies = loaded->frequencies;   // LoadGeodesics() replaces what InitializeCamera() would have computed
-  ctx->checkpoint = loaded;
-}
-
-template <typename T>
-void WriteCheckpointHeader(std::ofstream &out, int n1, int n2, int n3) {
-  const int dims[5] = {n1, n2, n3, 1, 1};
-  out.write(reinterpret_cast<const char *>(dims), sizeof dims);
-}
-
-// A geodesic checkpoint being assembled: samples of every pixel, far -> near, packed
-struct CheckpointSave {
-  std::vector<int32_t> sample_num;
-  std::vector<uint8_t> flags;
-  std::vector<double> factors, pos, dir, len;
-  std::vector<size_t> offset;
-};
 
 struct SplitIncomplete {};   // BL_TAIL_SPLIT: the chunk ended before its last ray (RunChunks)
 struct ReuseImpossible {};   // scratch for a render over the resident records could not be allocated beside them (EnsureScratch)
@@ -260,17 +163,11 @@ struct RenderJob {
   // (BLACKLIGHT_AMD_DEBUG_COUNTERS: the tables and launch of the locate kernel - the first chunk's and the last one's, which differ
   // when chunks overlap - of the coefficient kernel and of the exact second pass)
   TableLaunch tables_locate, tables_locate_last, tables_inside, tables_redo;
+  // checkpoints (bl_checkpoint.h): the two files being assembled chunk by chunk
+  bool sample_save = false;     // checkpoint_sample_save: where every kept sample of the level sits on the grid
+  bool no_checkpoint = true;    // !geo_load && !geo_save && !sample_save: the chunks' records and located samples never meet the host
   CheckpointSave save;
-  // checkpoint_sample_save: where every kept sample of the level sits on the grid, by pixel and reversed sample index
-  bool sample_save = false;
-  struct SampleSave {
-    int per_sample = 4;                     // indices per sample: 4, or 8 x 4 with inter-block interpolation
-    std::vector<int32_t> sample_num;        // [pixel]
-    std::vector<size_t> offset;             // [pixel]: first entry of the pixel in the packed arrays below
-    std::vector<int32_t> inds;              // [sample][per_sample]
-    std::vector<double> fracs;              // [sample][3] (trilinear sampling)
-    std::vector<uint8_t> nan, fallback;     // [sample]
-  } sampling;
+  SampleSave sampling;
 };
 
 // BLACKLIGHT_AMD_DEBUG_COUNTERS: every stage's choice as family name and template arguments, on one line
@@ -471,6 +368,7 @@ void PlanJob(RenderJob &job) {
   job.sample_save = job.simulation && p.checkpoint_sample_save && d->level == 0 && !ctx->sample_checkpoint_saved;
   if (job.sample_save && (d->pixel_map != nullptr || job.n_rays != job.level_pixels))
     throw Failure{BL_E_ARG, "checkpoint_sample_save needs the whole root camera in one bl_render call."};
+  job.no_checkpoint = !job.geo_load && !job.geo_save && !job.sample_save;
   // Tolerant tier: plain unpolarized images of a simulation with thermal (and power-law) electrons in a curved
   // spacetime have the fast coefficient kernel; every other configuration is rendered in exact arithmetic whatever
   // bl_set_arithmetic() asked for (bl_stats.arithmetic says which tier ran)
@@ -512,7 +410,7 @@ void PlanJob(RenderJob &job) {
   job.n_cold = job.simulation && job.variant_passes >= 2 && vs.n_units >= 2 ? vs.n_units : 1;
   // Plain images of a spherical Kerr-Schild simulation with fallback values beyond the grid: nothing is recorded of the steps that
   // lie in the empty shell between the grid's outer edge and the camera's sphere (both tiers; the samples count as ever)
-  job.skip_shell = job.simulation && !job.aux && !ctx->polarized && !job.slow && !job.geo_load && !job.geo_save && !job.sample_save
+  job.skip_shell = job.simulation && !job.aux && !ctx->polarized && !job.slow && job.no_checkpoint
       && !job.need_time && p.simulation_coord == BL_COORD_SKS && !ctx->grid_dev.fmks && !p.fallback_nan && ctx->grid_outer_x1 > 0.0
       && p.ray_integrator == BL_INTEGRATOR_DP   // (the fixed-step steppers have no instantiation for it: bl_launch_geodesic)
       && ctx->grid_outer_x1 < p.camera_r && !(ctx->switches & BL_SWITCH_RECORD_EVERY_STEP);
@@ -531,7 +429,7 @@ void PlanJob(RenderJob &job) {
   // geometric cut, no geodesic checkpoint loaded or saved (interleaved records whose momenta are not renormalised yet), no sample
   // checkpoint (it is made of the located samples), neither measurement switch
   const bool locate_inside_possible = job.simulation && !job.slow && !ctx->grid_dev.fmks && p.simulation_interp && p.simulation_coord == BL_COORD_SKS
-      && !GeometricCut(p) && !job.geo_load && !job.geo_save && !job.sample_save && !(ctx->switches & (BL_SWITCH_NO_FUSED_LOCATE | BL_SWITCH_SPLIT_RECORDS));
+      && !GeometricCut(p) && job.no_checkpoint && !(ctx->switches & (BL_SWITCH_NO_FUSED_LOCATE | BL_SWITCH_SPLIT_RECORDS));
   // (its own: the tolerant tier's scope - only this one reads job.fast, which leaves it plain images and so no sample times - without
   // the optical-depth row and power-law electrons; it alone takes inter-block interpolation, which its grid predicate decides)
   job.fused2 = locate_inside_possible && job.fast && !job.tau_row && fused2_grid && p.plasma_power_frac == 0.0;
@@ -547,7 +445,7 @@ void PlanJob(RenderJob &job) {
   // (only this one tests need_time: its runs may carry auxiliary rows - image_time - which the other two exclude altogether)
   job.pol_fused = locate_inside_possible && ctx->polarized && !job.block_interp && p.plasma_model != BL_PLASMA_CODE_KAPPA && !p.ray_flat && !job.need_time
       && (ctx->grid_dev.n_blocks == 0 ? bl_fused2_applicable(&ctx->grid_dev, 1, job.n_rays) != 0 : bl_polarized2_refined_applicable(&ctx->grid_dev, job.n_rays) != 0);
-  job.interleaved = (job.fused2 || job.exact_fused || job.pol_fused || !job.simulation) && !job.geo_load && !job.geo_save && !job.sample_save && !(ctx->switches & BL_SWITCH_SPLIT_RECORDS);
+  job.interleaved = (job.fused2 || job.exact_fused || job.pol_fused || !job.simulation) && job.no_checkpoint && !(ctx->switches & BL_SWITCH_SPLIT_RECORDS);
   job.locate_inside = job.fused2 || job.exact_fused || job.pol_fused;
   // The benchmark's kernel also composes the affine maps of a ray's neighbouring samples before they leave it (the geodesic kernel
   // numbers the segments: BlTraceArgs::segment_rows)
@@ -609,7 +507,7 @@ void PlanJob(RenderJob &job) {
   // last kernel)
   // (one variant's rows decide: the trace order is part of the resident geodesics' key, which the models and units must not change)
   job.raster = !d->outputs_on_device && d->level == 0 && d->pixel_map == nullptr && job.n_q_model >= 8
-      && static_cast<uint64_t>(job.n_q_model) * static_cast<uint64_t>(job.n_rays) * sizeof(double) >= (256ull << 20) && !job.geo_load && !job.geo_save && !job.sample_save;
+      && static_cast<uint64_t>(job.n_q_model) * static_cast<uint64_t>(job.n_rays) * sizeof(double) >= (256ull << 20) && job.no_checkpoint;
 }
 
 // ---- geodesics once per series (bl_set_geodesic_reuse; reference: blacklight.cpp:93-94 against its run loop :178-250, and the
@@ -716,6 +614,7 @@ void DecideReuse(RenderJob &job) {
     // (kept layout: the located samples lived in one chunk's arrays and are gone)
     job.reuse_located = !job.reuse_chunks && job.simulation && !job.locate_inside && !job.slow && res.located_valid && res.located_key == job.located_key;
     job.geo_save = false;   // (the render that integrated them wrote the file: geodesic_checkpoint.cpp is called once per run of the program)
+    job.no_checkpoint = !job.geo_load && !job.sample_save;
   } else if (res.valid) {
     if (job.keepable) DropResident(ctx);            // another camera: this render's records take their place
     else if (!res.parked) SwapResidentBuffers(ctx);   // another level: it works in buffers of its own
@@ -998,7 +897,7 @@ bool XcdOrderApplies(const RenderJob &job) {
   const bl_params &p = ctx->params;
   return job.fused2 && !job.freq_split && !(ctx->switches & BL_SWITCH_FLAT_ORDER)
       && job.d->level == 0 && job.d->pixel_map == nullptr && p.camera_resolution % 8 == 0 && job.n_rays == job.level_pixels && !job.raster
-      && !job.reuse && !job.reuse_chunks && !job.kept && !job.geo_load && !job.geo_save && !job.sample_save && !job.park && !job.split_long;
+      && !job.reuse && !job.reuse_chunks && !job.kept && job.no_checkpoint && !job.park && !job.split_long;
 }
 
 // The geodesic stage's instantiation: decided here for PlanScratch - the persistent grid is sized by its occupancy - and for PlanKernels
@@ -1357,15 +1256,10 @@ void StageInputsAndOutputs(RenderJob &job) {
   }
   if (job.geo_load && (job.cam_pos != nullptr || job.cam_dir != nullptr)) {   // camera_pos / camera_dir come from the file as well
     if (ctx->caller_stream_set) Check(hipStreamSynchronize(ctx->caller_stream), "caller's stream");   // (blocking copies below: no stream orders them)
-    std::vector<double> rows(static_cast<size_t>(n_rays) * 4);
     for (int which = 0; which < 2; which++) {
       double *target = which == 0 ? job.cam_pos : job.cam_dir;
       if (target == nullptr) continue;
-      const std::vector<double> &source = which == 0 ? ctx->checkpoint->camera_pos : ctx->checkpoint->camera_dir;
-      for (long long ray = 0; ray < n_rays; ray++) {
-        const size_t m = d->pixel_map != nullptr ? static_cast<size_t>(d->pixel_map[ray]) : static_cast<size_t>(ray);
-        for (int mu = 0; mu < 4; mu++) rows[4 * ray + mu] = source[4 * m + mu];
-      }
+      const std::vector<double> rows = GatherCameraRows(which == 0 ? ctx->checkpoint->camera_pos : ctx->checkpoint->camera_dir, d->pixel_map, n_rays);
       Check(hipMemcpy(target, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice), "checkpoint upload");
     }
   }
@@ -1964,316 +1858,84 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   }
 }
 
-// LoadGeodesics(): the chunk's sample records come from the file instead of the geodesic kernel. The file holds them
-// far -> near (ReverseGeodesics) with the renormalised momentum; records are near -> far, so sample n of a ray is entry
-// num - 1 - n, and len = -sample_len. Takes as many of the rays [begin, begin + rays) as the record buffers hold and
-// returns how many.
+// ---- checkpoints: what of a chunk crosses between device and host for them (the conversions and the files: bl_checkpoint.cpp)
+// LoadGeodesics(): the chunk's sample records come from the file instead of the geodesic kernel - as many of the rays
+// [begin, begin + rays) as the record buffers hold. Returns how many.
 long long LoadChunkFromCheckpoint(RenderJob &job, int k, long long begin, int rays) {
   bl_ctx *ctx = job.ctx;
-  const bl_render_desc *d = job.d;
   bl_ctx::ChunkSlot &sl = ctx->slot[k];
-  const bl_ctx::Checkpoint &ck = *ctx->checkpoint;
-  const size_t steps = static_cast<size_t>(ck.num_steps);
-  size_t total = 0;
-  int taken = 0;
-  for (; taken < rays; taken++) {
-    const long long ray = begin + taken;
-    const size_t m = d->pixel_map != nullptr ? static_cast<size_t>(d->pixel_map[ray]) : static_cast<size_t>(ray);
-    const size_t num = static_cast<size_t>(ck.sample_num[m]);
-    if (total + num > static_cast<size_t>(job.record_gate)) break;
-    total += num;
-  }
-  if (taken == 0) throw Failure{BL_E_ARG, "Scratch budget too small for the samples of one checkpointed ray (bl_set_scratch_limit)."};
-  std::vector<BlSampleHot> hot;
-  std::vector<BlSampleCold> cold;
-  std::vector<double> sample_t, ray_kt(taken), ray_factor(taken);
-  std::vector<int> ray_num(taken);
-  std::vector<unsigned char> ray_flags(taken);
-  std::vector<long long> ray_out(taken), ray_offset(taken);
-  hot.reserve(total);
-  cold.reserve(total);
-  sample_t.reserve(total);
-  for (int q = 0; q < taken; q++) {
-    const long long ray = begin + q;
-    const size_t m = d->pixel_map != nullptr ? static_cast<size_t>(d->pixel_map[ray]) : static_cast<size_t>(ray);
-    const int num = ck.sample_num[m];
-    ray_kt[q] = ck.camera_dir[4 * m];
-    ray_factor[q] = ck.factors[m];
-    ray_num[q] = num;
-    ray_flags[q] = ck.flags[m];
-    ray_out[q] = ray;
-    ray_offset[q] = static_cast<long long>(hot.size());
-    for (int n = 0; n < num; n++) {
-      const size_t at = m * steps + static_cast<size_t>(num - 1 - n);
-      BlSampleHot h;
-      h.x = ck.pos[4 * at + 1]; h.y = ck.pos[4 * at + 2]; h.z = ck.pos[4 * at + 3];
-      h.ray = static_cast<uint32_t>(q);
-      h.n = static_cast<uint32_t>(n);
-      BlSampleCold c;
-      c.kx = ck.dir[4 * at + 1]; c.ky = ck.dir[4 * at + 2]; c.kz = ck.dir[4 * at + 3];
-      c.len = -ck.len[at];
-      hot.push_back(h);
-      cold.push_back(c);
-      sample_t.push_back(ck.pos[4 * at]);
-    }
-  }
-  const unsigned long long n_loaded = hot.size(), n_taken = static_cast<unsigned long long>(taken);
-  if (n_loaded > 0) {
-    Check(hipMemcpy(sl.d_records_hot.ptr, hot.data(), n_loaded * sizeof(BlSampleHot), hipMemcpyHostToDevice), "checkpoint upload");
-    Check(hipMemcpy(sl.d_records_cold.ptr, cold.data(), n_loaded * sizeof(BlSampleCold), hipMemcpyHostToDevice), "checkpoint upload");
-    Check(hipMemcpy(sl.d_sample_t.ptr, sample_t.data(), n_loaded * sizeof(double), hipMemcpyHostToDevice), "checkpoint upload");
-  }
-  Check(hipMemcpy(ctx->rays.kt.ptr + begin, ray_kt.data(), taken * sizeof(double), hipMemcpyHostToDevice), "checkpoint upload");
-  Check(hipMemcpy(ctx->rays.factor.ptr + begin, ray_factor.data(), taken * sizeof(double), hipMemcpyHostToDevice), "checkpoint upload");
-  Check(hipMemcpy(ctx->rays.sample_num.ptr + begin, ray_num.data(), taken * sizeof(int), hipMemcpyHostToDevice), "checkpoint upload");
-  Check(hipMemcpy(ctx->rays.flags.ptr + begin, ray_flags.data(), taken, hipMemcpyHostToDevice), "checkpoint upload");
-  Check(hipMemcpy(ctx->rays.out_index.ptr + begin, ray_out.data(), taken * sizeof(long long), hipMemcpyHostToDevice), "checkpoint upload");
-  Check(hipMemcpy(ctx->rays.offset.ptr + begin, ray_offset.data(), taken * sizeof(long long), hipMemcpyHostToDevice), "checkpoint upload");
+  const HostChunk chunk = ChunkFromCheckpoint(*ctx->checkpoint, job.d->pixel_map, begin, rays, job.record_gate);
+  const unsigned long long n_loaded = chunk.hot.size(), n_taken = chunk.sample_num.size();
+  auto upload = [](auto *target, const auto &rows) {
+    if (!rows.empty()) Check(hipMemcpy(target, rows.data(), rows.size() * sizeof rows[0], hipMemcpyHostToDevice), "checkpoint upload");
+  };
+  upload(sl.d_records_hot.ptr, chunk.hot);
+  upload(sl.d_records_cold.ptr, chunk.cold);
+  upload(sl.d_sample_t.ptr, chunk.sample_t);
+  upload(ctx->rays.kt.ptr + begin, chunk.kt);
+  upload(ctx->rays.factor.ptr + begin, chunk.factor);
+  upload(ctx->rays.sample_num.ptr + begin, chunk.sample_num);
+  upload(ctx->rays.flags.ptr + begin, chunk.flags);
+  upload(ctx->rays.out_index.ptr + begin, chunk.out_index);
+  upload(ctx->rays.offset.ptr + begin, chunk.offset);
   Check(hipMemcpy(sl.d_counters.ptr + BL_CNT_RECORDS, &n_loaded, sizeof n_loaded, hipMemcpyHostToDevice), "checkpoint upload");
   Check(hipMemcpy(sl.d_counters.ptr + BL_CNT_NEXT_RAY, &n_taken, sizeof n_taken, hipMemcpyHostToDevice), "checkpoint upload");
-  return taken;
+  return static_cast<long long>(n_taken);
 }
 
-// SaveGeodesics(), first half: bring a chunk's records back while its scratch set still holds them
-void SaveChunkRecords(RenderJob &job, int k, long long begin, int rays) {
+template <typename T>
+void DownloadRows(std::vector<T> *rows, const T *source, size_t count) {
+  rows->resize(count);
+  if (count > 0) Check(hipMemcpy(rows->data(), source, count * sizeof(T), hipMemcpyDeviceToHost), "checkpoint download");
+}
+
+// SaveGeodesics() and SaveSampling(), first halves: what a finished chunk adds to the files, brought back while scratch set k holds it
+void SaveChunk(RenderJob &job, int k, long long begin, long long done) {
+  if (!job.geo_save && !job.sample_save) return;
   bl_ctx *ctx = job.ctx;
   bl_ctx::ChunkSlot &sl = ctx->slot[k];
-  CheckpointSave &save = job.save;
+  Check(hipStreamSynchronize(ctx->stream), "kernel execution");
   unsigned long long n_written = 0;
   Check(hipMemcpy(&n_written, sl.d_counters.ptr + BL_CNT_RECORDS, sizeof n_written, hipMemcpyDeviceToHost), "checkpoint download");
-  std::vector<BlSampleHot> hot(n_written);
-  std::vector<BlSampleCold> cold(n_written);
-  std::vector<double> sample_t(n_written), ray_kt(rays), ray_factor(rays);
-  std::vector<int> ray_num(rays);
-  std::vector<unsigned char> ray_flags(rays);
-  std::vector<long long> ray_out(rays);
-  if (n_written > 0) {
-    Check(hipMemcpy(hot.data(), sl.d_records_hot.ptr, n_written * sizeof(BlSampleHot), hipMemcpyDeviceToHost), "checkpoint download");
-    Check(hipMemcpy(cold.data(), sl.d_records_cold.ptr, n_written * sizeof(BlSampleCold), hipMemcpyDeviceToHost), "checkpoint download");
-    Check(hipMemcpy(sample_t.data(), sl.d_sample_t.ptr, n_written * sizeof(double), hipMemcpyDeviceToHost), "checkpoint download");
+  HostChunk chunk;
+  DownloadRows(&chunk.kt, ctx->rays.kt.ptr + begin, done);
+  DownloadRows(&chunk.factor, ctx->rays.factor.ptr + begin, done);
+  DownloadRows(&chunk.sample_num, ctx->rays.sample_num.ptr + begin, done);
+  DownloadRows(&chunk.flags, ctx->rays.flags.ptr + begin, done);
+  DownloadRows(&chunk.out_index, ctx->rays.out_index.ptr + begin, done);
+  if (job.geo_save) {
+    DownloadRows(&chunk.hot, sl.d_records_hot.ptr, n_written);
+    DownloadRows(&chunk.cold, sl.d_records_cold.ptr, n_written);
+    DownloadRows(&chunk.sample_t, sl.d_sample_t.ptr, n_written);
+    AddChunkToCheckpoint(chunk, ctx->st, job.n_rays, &job.save);
   }
-  Check(hipMemcpy(ray_kt.data(), ctx->rays.kt.ptr + begin, rays * sizeof(double), hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_factor.data(), ctx->rays.factor.ptr + begin, rays * sizeof(double), hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_num.data(), ctx->rays.sample_num.ptr + begin, rays * sizeof(int), hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_flags.data(), ctx->rays.flags.ptr + begin, rays, hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_out.data(), ctx->rays.out_index.ptr + begin, rays * sizeof(long long), hipMemcpyDeviceToHost), "checkpoint download");
-  if (save.sample_num.empty()) {
-    save.sample_num.assign(job.n_rays, 0);
-    save.flags.assign(job.n_rays, 0);
-    save.factors.assign(job.n_rays, 0.0);
-    save.offset.assign(job.n_rays, 0);
-  }
-  std::vector<size_t> slot_offset(rays);
-  for (int q = 0; q < rays; q++) {
-    const size_t m = static_cast<size_t>(ray_out[q]);
-    save.sample_num[m] = ray_num[q];
-    save.flags[m] = ray_flags[q];
-    save.factors[m] = ray_factor[q];
-    save.offset[m] = save.len.size();
-    slot_offset[q] = save.len.size();
-    save.pos.resize(save.pos.size() + 4 * static_cast<size_t>(ray_num[q]));
-    save.dir.resize(save.dir.size() + 4 * static_cast<size_t>(ray_num[q]));
-    save.len.resize(save.len.size() + static_cast<size_t>(ray_num[q]));
-  }
-  for (unsigned long long r = 0; r < n_written; r++) {
-    const BlSampleHot &h = hot[r];
-    if (h.ray == BL_DEAD_RAY) continue;
-    const int num = ray_num[h.ray];
-    if (static_cast<int>(h.n) >= num) continue;
-    const BlSampleCold &c = cold[r];
-    // ReverseGeodesics (geodesics.cpp:820-842) behind the per-sample renormalisation (:352-371)
-    const size_t at = slot_offset[h.ray] + static_cast<size_t>(num - 1 - static_cast<int>(h.n));
-    const double kt = ray_kt[h.ray];
-    const double factor = bl_renormalization_factor(ctx->st, h.x, h.y, h.z, kt, c.kx, c.ky, c.kz);
-    save.pos[4 * at] = sample_t[r]; save.pos[4 * at + 1] = h.x; save.pos[4 * at + 2] = h.y; save.pos[4 * at + 3] = h.z;
-    save.dir[4 * at] = kt; save.dir[4 * at + 1] = c.kx * factor; save.dir[4 * at + 2] = c.ky * factor; save.dir[4 * at + 3] = c.kz * factor;
-    save.len[at] = -c.len;
+  if (job.sample_save) {
+    std::vector<BlLocated> located;
+    std::vector<unsigned long long> tags(n_written);
+    std::vector<unsigned int> anchors;
+    DownloadRows(&chunk.hot, job.ta.records_hot, n_written * (job.interleaved ? 2 : 1));
+    DownloadRows(&located, sl.d_located.ptr, n_written);
+    if (!job.fast) DownloadRows(&tags, sl.d_located_tag.ptr, n_written);
+    if (job.block_interp) DownloadRows(&anchors, sl.d_anchors.ptr, n_written * 8);
+    AddChunkToSampleSave(chunk, located, tags, anchors, job.interleaved, job.fast, job.block_interp, ctx->params, ctx->grid_dev, ctx->merged_blocks,
+                         ctx->merged_block_at, job.n_rays, &job.sampling);
   }
 }
 
-// SaveGeodesics(), second half (geodesic_checkpoint.cpp:28-59)
-void WriteGeodesicCheckpoint(RenderJob &job) {
+// ... second halves, behind the last chunk
+void WriteCheckpoints(RenderJob &job) {
   bl_ctx *ctx = job.ctx;
   const bl_params &p = ctx->params;
-  const CheckpointSave &save = job.save;
-  const long long n_rays = job.n_rays;
-  std::vector<double> camera_pos(static_cast<size_t>(n_rays) * 4), camera_dir(static_cast<size_t>(n_rays) * 4);
-  Check(hipMemcpy(camera_pos.data(), job.cam_pos, camera_pos.size() * sizeof(double), hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(camera_dir.data(), job.cam_dir, camera_dir.size() * sizeof(double), hipMemcpyDeviceToHost), "checkpoint download");
-  std::ofstream out(p.checkpoint_geodesic_file.s, std::ios_base::out | std::ios_base::binary);
-  if (!out.is_open()) throw Failure{BL_E_INPUT, "Could not open geodesic checkpoint file."};
-  const bl_camera_frame &f = ctx->frame;
-  const double *vectors[7] = {f.cam_x, f.u_con, f.u_cov, f.norm_con, f.norm_con_c, f.hor_con_c, f.vert_con_c};
-  for (const double *v : vectors) out.write(reinterpret_cast<const char *>(v), 4 * sizeof(double));
-  const int n_pix = static_cast<int>(n_rays);
-  const int n_nu = job.n_nu;
-  int num_steps = 0;
-  for (int32_t num : save.sample_num) num_steps = std::max(num_steps, static_cast<int>(num));
-  WriteCheckpointHeader<double>(out, 4, n_pix, 1);
-  out.write(reinterpret_cast<const char *>(camera_pos.data()), static_cast<std::streamsize>(camera_pos.size() * sizeof(double)));
-  WriteCheckpointHeader<double>(out, 4, n_pix, 1);
-  out.write(reinterpret_cast<const char *>(camera_dir.data()), static_cast<std::streamsize>(camera_dir.size() * sizeof(double)));
-  WriteCheckpointHeader<double>(out, n_nu, 1, 1);
-  out.write(reinterpret_cast<const char *>(ctx->frequencies.data()), static_cast<std::streamsize>(n_nu * sizeof(double)));
-  WriteCheckpointHeader<double>(out, n_pix, 1, 1);
-  out.write(reinterpret_cast<const char *>(save.factors.data()), static_cast<std::streamsize>(save.factors.size() * sizeof(double)));
-  out.write(reinterpret_cast<const char *>(&num_steps), sizeof(int));
-  WriteCheckpointHeader<uint8_t>(out, n_pix, 1, 1);
-  out.write(reinterpret_cast<const char *>(save.flags.data()), static_cast<std::streamsize>(save.flags.size()));
-  WriteCheckpointHeader<int32_t>(out, n_pix, 1, 1);
-  out.write(reinterpret_cast<const char *>(save.sample_num.data()), static_cast<std::streamsize>(save.sample_num.size() * sizeof(int32_t)));
-  // sample_pos, sample_dir (n_pix, n_steps, 4) and sample_len (n_pix, n_steps): a pixel's samples, then zeros (the
-  // reference leaves the tail of sample_pos / sample_dir as allocated; nothing reads it)
-  std::vector<double> row(static_cast<size_t>(num_steps) * 4);
-  for (int which = 0; which < 2; which++) {
-    const std::vector<double> &source = which == 0 ? save.pos : save.dir;
-    WriteCheckpointHeader<double>(out, 4, num_steps, n_pix);
-    for (int m = 0; m < n_pix; m++) {
-      std::fill(row.begin(), row.end(), 0.0);
-      std::copy(source.begin() + 4 * save.offset[m], source.begin() + 4 * (save.offset[m] + save.sample_num[m]), row.begin());
-      out.write(reinterpret_cast<const char *>(row.data()), static_cast<std::streamsize>(row.size() * sizeof(double)));
-    }
+  if (job.geo_save) {
+    std::vector<double> camera_pos, camera_dir;
+    DownloadRows(&camera_pos, job.cam_pos, static_cast<size_t>(job.n_rays) * 4);
+    DownloadRows(&camera_dir, job.cam_dir, static_cast<size_t>(job.n_rays) * 4);
+    WriteGeodesicCheckpoint(p.checkpoint_geodesic_file.s, ctx->frame, ctx->frequencies.data(), job.n_nu, camera_pos, camera_dir, job.save);
   }
-  WriteCheckpointHeader<double>(out, num_steps, n_pix, 1);
-  row.resize(num_steps);
-  for (int m = 0; m < n_pix; m++) {
-    std::fill(row.begin(), row.end(), 0.0);
-    std::copy(save.len.begin() + save.offset[m], save.len.begin() + save.offset[m] + save.sample_num[m], row.begin());
-    out.write(reinterpret_cast<const char *>(row.data()), static_cast<std::streamsize>(row.size() * sizeof(double)));
+  if (job.sample_save) {
+    WriteSampleCheckpoint(p.checkpoint_sample_file.s, job.sampling, job.block_interp, p.simulation_interp != 0);
+    ctx->sample_checkpoint_saved = true;
   }
-  if (!out) throw Failure{BL_E_INPUT, "Could not write geodesic checkpoint file."};
-}
-
-// SaveSampling(), first half: a chunk's located samples, while its scratch set still holds them, as the reference keeps them -
-// sample_inds (MeshBlock, k, j, i of the nearest cell or of the lower corner; eight of them with inter-block interpolation),
-// sample_fracs (f_k, f_j, f_i), sample_nan, sample_fallback (simulation_sampling.cpp:205-216, :377-384, :427-549) - by pixel
-// and by the reversed sample index of ReverseGeodesics.
-void SaveChunkSampling(RenderJob &job, int k, long long begin, int rays) {
-  bl_ctx *ctx = job.ctx;
-  const bl_params &p = ctx->params;
-  bl_ctx::ChunkSlot &sl = ctx->slot[k];
-  RenderJob::SampleSave &out = job.sampling;
-  const BlGridDevice &g = ctx->grid_dev;
-  unsigned long long n_written = 0;
-  Check(hipMemcpy(&n_written, sl.d_counters.ptr + BL_CNT_RECORDS, sizeof n_written, hipMemcpyDeviceToHost), "checkpoint download");
-  const size_t stride = static_cast<size_t>(job.interleaved ? 2 : 1);
-  std::vector<BlSampleHot> hot(n_written * stride);
-  std::vector<BlLocated> located(n_written);
-  std::vector<unsigned long long> tags(n_written);
-  std::vector<unsigned int> anchors(job.block_interp ? n_written * 8 : 0);
-  std::vector<int> ray_num(rays);
-  std::vector<unsigned char> ray_flags(rays);
-  std::vector<long long> ray_out(rays);
-  if (n_written > 0) {
-    Check(hipMemcpy(hot.data(), job.ta.records_hot, hot.size() * sizeof(BlSampleHot), hipMemcpyDeviceToHost), "checkpoint download");
-    Check(hipMemcpy(located.data(), sl.d_located.ptr, n_written * sizeof(BlLocated), hipMemcpyDeviceToHost), "checkpoint download");
-    if (!job.fast) Check(hipMemcpy(tags.data(), sl.d_located_tag.ptr, n_written * sizeof(unsigned long long), hipMemcpyDeviceToHost), "checkpoint download");
-    if (job.block_interp) Check(hipMemcpy(anchors.data(), sl.d_anchors.ptr, anchors.size() * sizeof(unsigned int), hipMemcpyDeviceToHost), "checkpoint download");
-  }
-  Check(hipMemcpy(ray_num.data(), ctx->rays.sample_num.ptr + begin, rays * sizeof(int), hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_flags.data(), ctx->rays.flags.ptr + begin, rays, hipMemcpyDeviceToHost), "checkpoint download");
-  Check(hipMemcpy(ray_out.data(), ctx->rays.out_index.ptr + begin, rays * sizeof(long long), hipMemcpyDeviceToHost), "checkpoint download");
-  if (out.sample_num.empty()) {
-    out.per_sample = job.block_interp ? 32 : 4;
-    out.sample_num.assign(job.n_rays, 0);
-    out.offset.assign(job.n_rays, 0);
-  }
-  std::vector<size_t> slot_offset(rays);
-  for (int q = 0; q < rays; q++) {
-    const size_t m = static_cast<size_t>(ray_out[q]);
-    const size_t num = static_cast<size_t>(ray_num[q]);
-    out.sample_num[m] = ray_num[q];
-    out.offset[m] = slot_offset[q] = out.nan.size();
-    out.inds.resize(out.inds.size() + num * out.per_sample, 0);
-    if (p.simulation_interp) out.fracs.resize(out.fracs.size() + num * 3, 0.0);
-    out.nan.resize(out.nan.size() + num, 0);
-    out.fallback.resize(out.fallback.size() + num, 0);
-  }
-  // a cell of the HBM arrays as the reference names it: MeshBlock of the file, then k, j, i inside the block
-  const size_t block_cells = static_cast<size_t>(g.nb[0]) * g.nb[1] * g.nb[2];
-  auto name_cell = [&](unsigned int cell, int32_t *dst) {
-    if (g.n_blocks > 0) {   // cells kept by MeshBlock
-      const size_t b = cell / block_cells, rest = cell % block_cells;
-      dst[0] = static_cast<int32_t>(b);
-      dst[1] = static_cast<int32_t>(rest / g.stride_plane);
-      dst[2] = static_cast<int32_t>(rest % g.stride_plane / g.stride_row);
-      dst[3] = static_cast<int32_t>(rest % g.stride_row);
-    } else {                // equal blocks merged into one array (one block: itself)
-      const int i = static_cast<int>(cell % g.n[0]), j = static_cast<int>(cell / g.n[0] % g.n[1]), kk = static_cast<int>(cell / (static_cast<size_t>(g.n[0]) * g.n[1]));
-      const int at = ((kk / g.nb[2]) * ctx->merged_blocks[1] + j / g.nb[1]) * ctx->merged_blocks[0] + i / g.nb[0];
-      dst[0] = ctx->merged_block_at.empty() ? 0 : ctx->merged_block_at[at];
-      dst[1] = kk % g.nb[2];
-      dst[2] = j % g.nb[1];
-      dst[3] = i % g.nb[0];
-    }
-  };
-  for (unsigned long long r = 0; r < n_written; r++) {
-    const BlSampleHot &h = hot[r * stride];
-    if (h.ray == BL_DEAD_RAY) continue;
-    const int num = ray_num[h.ray];
-    if (static_cast<int>(h.n) >= num) continue;
-    const size_t at = slot_offset[h.ray] + static_cast<size_t>(num - 1 - static_cast<int>(h.n));
-    if (p.fallback_nan && ray_flags[h.ray] != 0) {   // a poorly terminated geodesic samples NaN everywhere (:211-216)
-      out.nan[at] = 1;
-      continue;
-    }
-    unsigned long long tag = tags[r];
-    if (job.fast) std::memcpy(&tag, &located[r].ph, sizeof tag);   // tolerant tier: the tag rides in the azimuth's slot
-    const int status = static_cast<int>(tag >> 32) & 0xff;
-    if (status == 2) {                 // off the grid (:377-384)
-      (p.fallback_nan ? out.nan : out.fallback)[at] = 1;
-    } else if (status == 3 || status == 4) {   // nearest cell | lower corner of the trilinear stencil
-      name_cell(static_cast<unsigned int>(tag), &out.inds[at * out.per_sample]);
-    } else if (status == 6) {          // inter-block interpolation: the eight anchors (:541)
-      for (int c = 0; c < 8; c++) name_cell(anchors[r * 8 + c], &out.inds[at * out.per_sample + 4 * c]);
-    }
-    if (p.simulation_interp && (status == 4 || status == 6)) {
-      out.fracs[3 * at] = located[r].f_k;
-      out.fracs[3 * at + 1] = located[r].f_j;
-      out.fracs[3 * at + 2] = located[r].f_i;
-    }
-  }
-}
-
-// SaveSampling(), second half (sample_checkpoint.cpp:22-46): four Arrays (file_io.cpp:65-76: five int32 extents, fastest first,
-// then the data). Entries the reference never writes - beyond a pixel's samples, cut samples, samples off the grid - are
-// whatever its allocator held there; zeros here.
-void WriteSampleCheckpoint(RenderJob &job) {
-  bl_ctx *ctx = job.ctx;
-  const bl_params &p = ctx->params;
-  const RenderJob::SampleSave &sv = job.sampling;
-  std::ofstream out(p.checkpoint_sample_file.s, std::ios_base::out | std::ios_base::binary);
-  if (!out.is_open()) throw Failure{BL_E_INPUT, "Could not open sample checkpoint file."};
-  const int n_pix = static_cast<int>(job.n_rays);
-  int num_steps = 0;
-  for (int32_t num : sv.sample_num) num_steps = std::max(num_steps, static_cast<int>(num));
-  auto write_rows = [&](const auto &packed, int per_sample) {
-    using T = typename std::decay<decltype(packed)>::type::value_type;
-    std::vector<T> row(static_cast<size_t>(num_steps) * per_sample);
-    for (int m = 0; m < n_pix; m++) {
-      std::fill(row.begin(), row.end(), T(0));
-      const size_t first = sv.offset[m] * per_sample, count = static_cast<size_t>(sv.sample_num[m]) * per_sample;
-      std::copy(packed.begin() + first, packed.begin() + first + count, row.begin());
-      out.write(reinterpret_cast<const char *>(row.data()), static_cast<std::streamsize>(row.size() * sizeof(T)));
-    }
-  };
-  if (job.block_interp) {
-    const int dims[5] = {4, 8, num_steps, n_pix, 1};
-    out.write(reinterpret_cast<const char *>(dims), sizeof dims);
-  } else {
-    WriteCheckpointHeader<int32_t>(out, 4, num_steps, n_pix);
-  }
-  write_rows(sv.inds, sv.per_sample);
-  if (p.simulation_interp) {
-    WriteCheckpointHeader<double>(out, 3, num_steps, n_pix);
-    write_rows(sv.fracs, 3);
-  }
-  WriteCheckpointHeader<uint8_t>(out, num_steps, n_pix, 1);
-  write_rows(sv.nan, 1);
-  WriteCheckpointHeader<uint8_t>(out, num_steps, n_pix, 1);
-  write_rows(sv.fallback, 1);
-  if (!out) throw Failure{BL_E_INPUT, "Could not write sample checkpoint file."};
-  ctx->sample_checkpoint_saved = true;
 }
 
 // ---- a chunk, first half: the geodesic stage on stream_geo into scratch set k (the set must be free)
@@ -2517,10 +2179,7 @@ void RunChunks(RenderJob &job) {
                                                : job.n_rays;
       const long long done = job.in_flight[0].done;
       LaunchShadingStage(job, 0, false, stream);
-      if (job.sample_save) {
-        Check(hipStreamSynchronize(stream), "kernel execution");
-        SaveChunkSampling(job, 0, begin, static_cast<int>(done));
-      }
+      SaveChunk(job, 0, begin, done);
       CollectChunk(job, 0);
       ChunkOutputs(job, begin, done);
     }
@@ -2552,14 +2211,10 @@ void RunChunks(RenderJob &job) {
       // soon as its geodesic kernel ends, and its shading goes to the other stream without waiting for anything else.
       done = WaitGeodesicStage(job, k, stream_geo);
       LaunchShadingStage(job, k, begin + done < n_rays, stream);
-      if (job.geo_save || job.sample_save) Check(hipStreamSynchronize(stream), "kernel execution");
-      if (job.geo_save) SaveChunkRecords(job, k, begin, static_cast<int>(done));
-      if (job.sample_save) SaveChunkSampling(job, k, begin, static_cast<int>(done));
+      SaveChunk(job, k, begin, done);
     } else {
       LaunchShadingStage(job, k, false, stream);
-      if (job.geo_save || job.sample_save) Check(hipStreamSynchronize(stream), "kernel execution");
-      if (job.geo_save) SaveChunkRecords(job, k, begin, static_cast<int>(WaitGeodesicStage(job, k, stream_geo)));
-      if (job.sample_save) SaveChunkSampling(job, k, begin, static_cast<int>(WaitGeodesicStage(job, k, stream_geo)));
+      if (job.geo_save || job.sample_save) SaveChunk(job, k, begin, WaitGeodesicStage(job, k, stream_geo));
       CollectChunk(job, k);
       done = job.in_flight[k].done;
       if (job.kept && !job.kept_spilled) {   // (one scratch set: the counters CollectChunk read are this chunk's as its kernels left them)
@@ -2799,8 +2454,7 @@ extern "C" int bl_render(bl_ctx *ctx, const bl_render_desc *d) {
         BuildShadeArgs(job);
         BuildTransferArgs(job);
         RunChunks(job);
-        if (job.geo_save) WriteGeodesicCheckpoint(job);
-        if (job.sample_save) WriteSampleCheckpoint(job);
+        WriteCheckpoints(job);
         DownloadOutputs(job);
         FinishStats(job);
         KeepResident(job);

@@ -168,8 +168,10 @@ def test_checkpoint_subsets_and_damaged_files(built_library, expected, tmp_path)
     path = os.path.join(READER_DIR, "geodesic_formula.ckpt")
     subset = np.random.default_rng(3).permutation(64)[:20].astype(np.int32)
     with _context(expected, "formula", checkpoint_geodesic_load="true", checkpoint_geodesic_file=path) as ctx:
-        part = ctx.render(pixel_map=subset)
+        part = ctx.render(pixel_map=subset, want_camera=True)
         assert gu.same_bits(part["image"], _want(expected, "formula")[:, subset]).all()
+        ref = read_checkpoint(path)   # ... and the camera's rows are the file's, gathered through the map
+        assert gu.same_bits(part["camera_pos"], ref["camera_pos"][subset]).all() and gu.same_bits(part["camera_dir"], ref["camera_dir"][subset]).all()
         with pytest.raises(BlacklightError, match="does not hold"):
             ctx.render(pixel_map=np.array([3, 64], dtype=np.int32))
     with _context(expected, "formula", checkpoint_geodesic_save="true", checkpoint_geodesic_file=str(tmp_path / "part.ckpt")) as ctx:
