@@ -40,6 +40,11 @@ class Sweep(C.Structure):
                 ("rat_low", C.c_double * BL_MAX_SWEEP), ("rat_high", C.c_double * BL_MAX_SWEEP), ("rho_cgs", C.c_double * BL_MAX_SWEEP)]
 
 
+class SweepCuts(C.Structure):
+    """bl_sweep_cuts: the sweep_cut_sigma_max list of a .input file, beside bl_sweep (whose size is part of the ABI)."""
+    _fields_ = [("n_sigma_max", C.c_int32), ("reserved", C.c_int32), ("sigma_max", C.c_double * BL_MAX_SWEEP)]
+
+
 class CameraFrame(C.Structure):
     _fields_ = [(name, C.c_double * 4) for name in
                 ("cam_x", "u_con", "u_cov", "norm_con", "norm_con_c", "hor_con_c", "vert_con_c")] + \
@@ -113,6 +118,9 @@ def lib():
     L.bl_params_read_file_sweep.argtypes = [C.c_void_p, C.POINTER(Sweep), C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
     L.bl_sweep_resolve.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Sweep), C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
     L.bl_apply_sweep.argtypes = [C.c_void_p, C.POINTER(Sweep)]
+    L.bl_params_set_line_sweeps.argtypes = [C.c_void_p, C.POINTER(Sweep), C.POINTER(SweepCuts), C.c_char_p, C.c_char_p, C.c_size_t]
+    L.bl_params_read_file_sweeps.argtypes = [C.c_void_p, C.POINTER(Sweep), C.POINTER(SweepCuts), C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+    L.bl_apply_sweeps.argtypes = [C.c_void_p, C.POINTER(Sweep), C.POINTER(SweepCuts)]
     L.bl_num_variants.argtypes = [C.c_void_p]
     L.bl_write_output_variant.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(OutputDesc), C.c_int]
     L.bl_variant_output_path.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
@@ -133,6 +141,8 @@ def lib():
     L.bl_num_density_units.argtypes = [C.c_void_p]
     L.bl_set_polarized_variants.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bl_num_polarized_variants.argtypes = [C.c_void_p]
+    L.bl_set_sigma_cuts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.bl_num_sigma_cuts.argtypes = [C.c_void_p]
     L.bl_host_alloc.argtypes = [C.c_void_p, C.c_size_t]
     L.bl_host_alloc.restype = C.c_void_p
     L.bl_host_free.argtypes = [C.c_void_p, C.c_void_p]

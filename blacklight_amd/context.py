@@ -39,13 +39,16 @@ class Context:
         return cls(Params.from_file(path), device=device)
 
     def apply_sweep(self, params=None):
-        """bl_apply_sweep: the sweep_rat_low / sweep_rat_high / sweep_rho_cgs lists of `params` (default: this context's) as electron
-        models and density units, or as polarized triples. An empty sweep changes nothing."""
+        """bl_apply_sweeps: the sweep_rat_low / sweep_rat_high / sweep_rho_cgs lists of `params` (default: this context's) as electron
+        models and density units, or as polarized triples, and its sweep_cut_sigma_max list as sigma cuts. An empty sweep changes
+        nothing."""
         params = params or self.params
         if not params.has_sweep:
             return
         polarized, low, high, rho = params.resolved_sweep()
-        self._check(self._lib.bl_apply_sweep(self._ctx, C.byref(params.sweep)))
+        self._check(self._lib.bl_apply_sweeps(self._ctx, C.byref(params.sweep), C.byref(params.sweep_cuts)))
+        if params.sweep_cut_sigma_max:
+            self._sigma_cuts = params.sweep_cut_sigma_max
         if polarized:
             self._polarized_variants = [(h, lo, u) for h, lo, u in zip(high, low, rho)]
         else:
@@ -56,12 +59,12 @@ class Context:
 
     @property
     def num_variants(self):
-        """Images one render produces (bl_num_variants): models x units, or polarized triples."""
+        """Images one render produces (bl_num_variants): models x units x sigma cuts, or polarized triples."""
         return self._lib.bl_num_variants(self._ctx)
 
     def variant_output_path(self, snapshot=0, variant=0):
         """The file name write_output(variant=...) uses without `path` (bl_variant_output_path): output_file, the file number of a
-        series, and a tag .mMMuUU / .vVV in front of the extension when the context renders several variants."""
+        series, and a tag .mMMuUU (.mMMuUUsSS with sigma cuts set) / .vVV in front of the extension when the context renders several variants."""
         buf = C.create_string_buffer(4096)
         self._check(self._lib.bl_variant_output_path(self._ctx, int(snapshot), int(variant), buf, len(buf)))
         return buf.value.decode()
@@ -201,6 +204,24 @@ class Context:
     @property
     def num_density_units(self):
         return self._lib.bl_num_density_units(self._ctx)
+
+    def set_sigma_cuts(self, sigma_max):
+        """Render several sigma cuts (cut_sigma_max values: cells with sigma = b.b / rho above the value are left out, a negative
+        value switches the cut off) in one render (bl_set_sigma_cuts). A scalar or a sequence; an empty sequence clears them (the
+        parameter block's cut_sigma_max again). The image then holds, for every electron model and density unit, its cuts one after
+        another (render()["image_by_cut"]: (n_models, n_units, n_cuts, n_q, n_rays)); geodesics stay resident."""
+        cuts = np.ascontiguousarray(np.atleast_1d(np.asarray(sigma_max, dtype=np.float64)).ravel())
+        self._check(self._lib.bl_set_sigma_cuts(self._ctx, int(cuts.size), cuts.ctypes.data_as(C.c_void_p)))
+        self._sigma_cuts = [float(c) for c in cuts]
+
+    @property
+    def sigma_cuts(self):
+        """The cut_sigma_max values set_sigma_cuts() set; [] when the parameter block's cut is rendered."""
+        return list(getattr(self, "_sigma_cuts", []))
+
+    @property
+    def num_sigma_cuts(self):
+        return self._lib.bl_num_sigma_cuts(self._ctx)
 
     def fit_density_unit(self, target_jy, distance_pc, lo, hi, frequency=0, rtol=1.0e-3, per_render=16):
         """The density unit (simulation_rho_cgs) in [lo, hi] at which the root image's total flux (flux.total_flux_jy) at image
@@ -486,9 +507,11 @@ class Context:
         self._check(self._lib.bl_render(self._ctx, C.byref(d)))
         n_models, n_units = max(1, self.num_electron_models), max(1, self.num_density_units)
         n_variants = max(1, self.num_polarized_variants)
+        n_cuts = max(1, self.num_sigma_cuts)
         return dict(image=image, image_by_model=image.reshape(n_models, n_q // n_models, n_rays),
                     image_by_variant=image.reshape(n_variants, n_q // n_variants, n_rays),
-                    image_by_unit=image.reshape(n_models, n_units, n_q // (n_models * n_units), n_rays), sample_num=sample_num,
+                    image_by_unit=image.reshape(n_models, n_units, n_q // (n_models * n_units), n_rays),
+                    image_by_cut=image.reshape(n_models, n_units, n_cuts, n_q // (n_models * n_units * n_cuts), n_rays), sample_num=sample_num,
                     sample_flags=sample_flags, camera_pos=camera_pos, camera_dir=camera_dir, rendering=rendering, stats=self.stats)
 
     # ------------------------------------------------------------------ host steps of the reference loop

@@ -399,15 +399,34 @@ const char *PolarizedVariantsRefusal(const bl_ctx *ctx, int n) {
   return nullptr;
 }
 
-// The variants of a render, in image-row order: the triples, else models x units, model-major, with the parameter block's pair and
-// unit where an axis is not set. The one reader of what the three setters stored.
+// Why n sigma cuts cannot be rendered by this context (nullptr: they can). bl_set_sigma_cuts and bl_render's plan both ask.
+// (A cell the cut removes has no coefficients and no cell values: it drops out of a rendering, which comes out once.)
+const char *SigmaCutsRefusal(const bl_ctx *ctx, int n) {
+  const bl_params &p = ctx->params;
+  if (n <= 0) return nullptr;
+  if (p.model_type != BL_MODEL_SIMULATION) return "Sigma cuts: formula mode has no magnetisation (model_type = formula).";
+  if (ctx->polarized) return "Sigma cuts: the polarized axis is not built yet; polarized runs render one sigma cut (image_polarization = true).";
+  if (p.slow_light_on) return "Sigma cuts: slow light renders one sigma cut (slow_light_on = true).";
+  if (n >= 2 && p.adaptive_max_level > 0)
+    return "Sigma cuts: adaptive refinement reads one image; n >= 2 cuts need adaptive_max_level = 0.";
+  if (n >= 2 && ctx->render_num_images > 0)
+    return "Sigma cuts: a cut cell drops out of a rendering, and renderings come out once; n >= 2 cuts need render_num_images = 0.";
+  return nullptr;
+}
+
+// The variants of a render, in image-row order: the triples, else models x units x sigma cuts, model-major, then unit, then cut, with
+// the parameter block's pair, unit and cut_sigma_max where an axis is not set. The one reader of what the four setters stored.
 Variants ResolveVariants(const bl_ctx *ctx) {
   const bl_params &p = ctx->params;
-  const std::vector<Variant> own = {{p.plasma_rat_low, p.plasma_rat_high, p.simulation_rho_cgs}};
-  Variants v{ctx->triples, static_cast<int>(ctx->models.size()), static_cast<int>(ctx->units.size()), static_cast<int>(ctx->triples.size())};
+  const std::vector<Variant> own = {{p.plasma_rat_low, p.plasma_rat_high, p.simulation_rho_cgs, p.cut_sigma_max}};
+  const std::vector<double> own_cut = {p.cut_sigma_max};
+  Variants v{ctx->triples, static_cast<int>(ctx->models.size()), static_cast<int>(ctx->units.size()), static_cast<int>(ctx->triples.size()),
+             static_cast<int>(ctx->sigma_cuts.size())};
+  for (Variant &triple : v.list) triple.sigma_max = p.cut_sigma_max;
   if (v.n_pol == 0)
     for (const Variant &model : v.n_models > 0 ? ctx->models : own)
-      for (const Variant &unit : v.n_units > 0 ? ctx->units : own) v.list.push_back({model.rat_low, model.rat_high, unit.rho});
+      for (const Variant &unit : v.n_units > 0 ? ctx->units : own)
+        for (const double sigma_max : v.n_cuts > 0 ? ctx->sigma_cuts : own_cut) v.list.push_back({model.rat_low, model.rat_high, unit.rho, sigma_max});
   return v;
 }
 }  // namespace blhost
@@ -1172,7 +1191,7 @@ int bl_set_electron_models(bl_ctx *ctx, int n, const double *rat_low, const doub
   if (const char *why = ElectronModelsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
   std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: they do not depend on the model)
   ctx->models.resize(n);
-  for (int m = 0; m < n; m++) ctx->models[m] = {rat_low[m], rat_high[m], 0.0};
+  for (int m = 0; m < n; m++) ctx->models[m] = {rat_low[m], rat_high[m], 0.0, 0.0};
   return BL_OK;
 }
 
@@ -1188,7 +1207,7 @@ int bl_set_density_units(bl_ctx *ctx, int n, const double *rho_cgs) {
   if (const char *why = DensityUnitsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
   std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: they do not depend on the unit)
   ctx->units.resize(n);
-  for (int u = 0; u < n; u++) ctx->units[u] = {0.0, 0.0, rho_cgs[u]};
+  for (int u = 0; u < n; u++) ctx->units[u] = {0.0, 0.0, rho_cgs[u], 0.0};
   return BL_OK;
 }
 
@@ -1207,11 +1226,26 @@ int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const d
   if (const char *why = PolarizedVariantsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
   std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: no variant enters them)
   ctx->triples.resize(n);
-  for (int v = 0; v < n; v++) ctx->triples[v] = {rat_low[v], rat_high[v], rho_cgs[v]};
+  for (int v = 0; v < n; v++) ctx->triples[v] = {rat_low[v], rat_high[v], rho_cgs[v], 0.0};
   return BL_OK;
 }
 
 int bl_num_polarized_variants(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->triples.size()) : -1; }
+
+int bl_set_sigma_cuts(bl_ctx *ctx, int n, const double *sigma_max) {
+  if (ctx == nullptr) return BL_E_ARG;
+  if (n < 0 || n > BL_MAX_SIGMA_CUTS || (n > 0 && sigma_max == nullptr))
+    return Fail(ctx, Failure{BL_E_ARG, "bl_set_sigma_cuts needs 0 <= n <= " + std::to_string(BL_MAX_SIGMA_CUTS) + " and the array of cuts."});
+  for (int s = 0; s < n; s++)
+    if (!std::isfinite(sigma_max[s]))
+      return Fail(ctx, Failure{BL_E_ARG, "bl_set_sigma_cuts: cut " + std::to_string(s) + " is not finite."});
+  if (const char *why = SigmaCutsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
+  std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: they do not depend on the cut)
+  ctx->sigma_cuts.assign(sigma_max, sigma_max + n);
+  return BL_OK;
+}
+
+int bl_num_sigma_cuts(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->sigma_cuts.size()) : -1; }
 
 int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out) {
   if (ctx == nullptr || out == nullptr) return BL_E_ARG;

@@ -122,12 +122,13 @@ inline void Check(hipError_t err, const char *what) {
 }  // namespace blhost
 using namespace blhost;
 
-// One image of a render: an electron model (R_low, R_high) and a density unit (simulation_rho_cgs). Variants: a render's, in image-row
-// order and never empty (ResolveVariants), with the number of models, units and polarized triples as set - 0: the parameter block's.
-struct Variant { double rat_low, rat_high, rho; };
+// One image of a render: an electron model (R_low, R_high), a density unit (simulation_rho_cgs) and a sigma cut (cut_sigma_max).
+// Variants: a render's, in image-row order and never empty (ResolveVariants), with the number of models, units, polarized triples
+// and sigma cuts as set - 0: the parameter block's.
+struct Variant { double rat_low, rat_high, rho, sigma_max; };
 struct Variants {
   std::vector<Variant> list;
-  int n_models, n_units, n_pol;
+  int n_models, n_units, n_pol, n_cuts;
 };
 
 struct bl_ctx {
@@ -164,9 +165,10 @@ struct bl_ctx {
 
   // image rows (radiation_integrator.cpp:436-520)
   int image_num_quantities = 0;      // of one electron model and unit (bl_image_num_quantities: times the number of each)
-  // what the three setters stored, empty: the parameter block's - bl_set_electron_models() pairs (rho unused), bl_set_density_units()
-  // units (the pair unused), bl_set_polarized_variants() triples; read through ResolveVariants only
+  // what the four setters stored, empty: the parameter block's - bl_set_electron_models() pairs (rho unused), bl_set_density_units()
+  // units (the pair unused), bl_set_polarized_variants() triples, bl_set_sigma_cuts() thresholds; read through ResolveVariants only
   std::vector<Variant> models, units, triples;
+  std::vector<double> sigma_cuts;
   BlAuxImages aux_images{};          // which image rows exist; .any = an auxiliary image or a rendering is requested
   int render_num_images = 0;         // false-colour renderings (0 in formula mode)
   DeviceBuffer<BlRenderDevice> d_render_params;
@@ -377,6 +379,7 @@ inline bool ThetaECut(const bl_params &p) { return p.cut_theta_e_min >= 0.0 || p
 const char *ElectronModelsRefusal(const bl_ctx *ctx, int n);   // bl_set_electron_models (bl_api.hip)
 const char *DensityUnitsRefusal(const bl_ctx *ctx, int n);     // bl_set_density_units (bl_api.hip)
 const char *PolarizedVariantsRefusal(const bl_ctx *ctx, int n);   // bl_set_polarized_variants (bl_api.hip)
+const char *SigmaCutsRefusal(const bl_ctx *ctx, int n);        // bl_set_sigma_cuts (bl_api.hip)
 }  // namespace blhost
 
 #endif  // BLACKLIGHT_AMD_BL_CTX_H_

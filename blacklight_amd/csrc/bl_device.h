@@ -386,12 +386,18 @@ struct alignas(16) BlFreqInputs {
   double pad;
 };
 // ... and with several electron models in one pass (BlShadeArgs::freq_split = 2, BlTransferArgs::n_models): the same 64 bytes hold
-// what no model enters - (flag, x at unit frequency and unit 1 / (k T_e)), (h s_nu, s_j), (s_length, 1 / beta^2), (K0 p / rho, 0) -
+// what no model enters - (flag, x at unit frequency and unit 1 / (k T_e)), (h s_nu, s_j), (s_length, 1 / beta^2), (K0 p / rho, sigma) -
 // and bl_transfer_freq_kernel forms each model's 1 / (k T_e) = (K1_m + K2_m / beta^2 + K3 d) / (K0 (p / rho) d), d = 1 + 1 / beta^2.
 #define BL_TRANSFER_MAX_MODELS 16
 // ... and with density units (BlTransferArgs::n_units): the row is the unit the render folded (RenderJob::base_rho); unit u scales x at
 // unit frequency (~ 1 / b_unit) by unit_x[u] and s_j (~ d_unit b_unit) by unit_j[u]. Nothing else in the row depends on the unit.
 #define BL_TRANSFER_MAX_UNITS 16
+// ... and with sigma cuts (BlTransferArgs::n_cuts): the coefficient kernels ran with the sigma upper cut off, the row's last double is
+// the sample's sigma = b.b / rho in code units (every writer of the model-free row stores it), and cut s leaves out the samples with
+// sigma > sigma_max[s]. The tolerant kernels leave a sample whose sigma lies in the guard band of any threshold to the exact pass
+// (BlShadeArgs::sigma_band_lo / _hi), whose row holds the exact tier's sigma.
+#define BL_TRANSFER_MAX_CUTS 16
+#define BL_SHADE_MAX_SIGMA_CUTS 16
 
 // Polarized runs: what the per-frequency coefficient formulas need of a sample (simulation_coefficients.cpp:458-698),
 // left by the coefficient kernel for bl_polarized_coefficients_kernel, one per sample record. 64 bytes.
@@ -500,6 +506,10 @@ struct BlShadeArgs {
   int aux_need_length;
   int aux_record_unused;      // BlAuxImages::polarized_rows_only: nobody reads the BlAuxSample records
   double cam_x[4];
+  // sigma cuts in one pass (freq_split = 2; 0: none): the guard band around each threshold - a sample of the tolerant kernels whose
+  // sigma lies in one of them is the exact pass's. Read wave-uniform; an empty band (lo > hi) for a switched-off threshold.
+  int n_sigma_bands;
+  double sigma_band_lo[BL_SHADE_MAX_SIGMA_CUTS], sigma_band_hi[BL_SHADE_MAX_SIGMA_CUTS];
 };
 
 // Kernel arguments: transfer kernel
@@ -537,6 +547,8 @@ struct BlTransferArgs {
   double model_k1[BL_TRANSFER_MAX_MODELS], model_k2[BL_TRANSFER_MAX_MODELS], model_k3;   // ... R_high g1, R_low g1 of model m; n_e / n_i g2
   int n_units;                                // ... > 0 (with n_models > 0): density units too, a lane per (ray, model, unit, frequency), row (m n_units + u) n_nu + l
   double unit_x[BL_TRANSFER_MAX_UNITS], unit_j[BL_TRANSFER_MAX_UNITS];   // ... unit u's factors on x at unit frequency and on s_j
+  int n_cuts;                                 // ... > 0 (with n_models > 0): sigma cuts too, a lane per (ray, model, unit, cut, frequency), row ((m n_units + u) n_cuts + s) n_nu + l
+  double sigma_max[BL_TRANSFER_MAX_CUTS];     // ... cut s leaves out the samples whose row's sigma is > sigma_max[s] (+inf: off)
   long long n_rays_total;
   double *image;              // [n_q][n_rays_total]; rows 0..n_nu-1 = I_nu
   int *out_sample_num;        // [n_rays_total] or null

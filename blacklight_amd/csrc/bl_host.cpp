@@ -341,6 +341,8 @@ int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const i
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more density units (bl_set_density_units).");
   if (bl_num_polarized_variants(ctx) >= 2)
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more polarized variants (bl_set_polarized_variants).");
+  if (bl_num_sigma_cuts(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more sigma cuts (bl_set_sigma_cuts).");
   const bl_params &p = *bl_internal_params(ctx);
   *n_refined = 0;
   if (p.adaptive_max_level <= 0 || level >= p.adaptive_max_level) {   // radiation_adaptive.cpp:22-23
@@ -427,8 +429,10 @@ int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, std::stri
   if (bl_num_polarized_variants(ctx) >= 1) {
     std::snprintf(tag, sizeof tag, ".v%02d", variant);
   } else {
-    const int n_units = std::max(1, bl_num_density_units(ctx));
-    std::snprintf(tag, sizeof tag, ".m%02du%02d", variant / n_units, variant % n_units);
+    // (variant = (m U + u) S + s; the cut's tag only where cuts are set: names without cuts are as ever)
+    const int n_units = std::max(1, bl_num_density_units(ctx)), n_cuts = bl_num_sigma_cuts(ctx), pair = variant / std::max(1, n_cuts);
+    if (n_cuts >= 1) std::snprintf(tag, sizeof tag, ".m%02du%02ds%02d", pair / n_units, pair % n_units, variant % n_cuts);
+    else std::snprintf(tag, sizeof tag, ".m%02du%02d", pair / n_units, pair % n_units);
   }
   const std::string::size_type slash = path->find_last_of('/');
   const std::string::size_type dot = path->find_last_of('.');
@@ -716,6 +720,8 @@ int bl_write_output(bl_ctx *ctx, const char *path_override, const bl_output_desc
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no density-unit axis (bl_set_density_units with n >= 2).");
   if (bl_num_polarized_variants(ctx) >= 2)
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no variant axis (bl_set_polarized_variants with n >= 2).");
+  if (bl_num_sigma_cuts(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no sigma-cut axis (bl_set_sigma_cuts with n >= 2).");
   return WriteOutput(ctx, path_override, d, 0, 1);
 }
 
@@ -761,6 +767,25 @@ int bl_apply_sweep(bl_ctx *ctx, const bl_sweep *sweep) {
       bl_set_electron_models(ctx, 0, nullptr, nullptr);
       bl_internal_fail(ctx, rc, MessageOf(why).c_str());
     }
+  }
+  return rc;
+}
+
+int bl_apply_sweeps(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts) {
+  if (ctx == nullptr || sweep == nullptr) return BL_E_ARG;
+  if (cuts != nullptr && (cuts->n_sigma_max < 0 || cuts->n_sigma_max > BL_MAX_SWEEP))
+    return bl_internal_fail(ctx, BL_E_INPUT, ("Too many entries in a sweep list: at most " + std::to_string(BL_MAX_SWEEP) + " for this build.").c_str());
+  int rc = bl_apply_sweep(ctx, sweep);
+  if (rc != BL_OK || cuts == nullptr || cuts->n_sigma_max == 0) return rc;
+  rc = bl_set_sigma_cuts(ctx, cuts->n_sigma_max, cuts->sigma_max);
+  if (rc != BL_OK) {   // no list of this call stays behind a refusal of the cuts
+    const std::string why = bl_last_error(ctx);
+    int polarized = 0;
+    (void)bl_sweep_resolve(sweep, bl_internal_params(ctx), nullptr, &polarized, nullptr, 0);
+    if (polarized && (sweep->n_rat_low > 0 || sweep->n_rho_cgs > 0)) bl_set_polarized_variants(ctx, 0, nullptr, nullptr, nullptr);
+    if (!polarized && sweep->n_rat_low > 0) bl_set_electron_models(ctx, 0, nullptr, nullptr);
+    if (!polarized && sweep->n_rho_cgs > 0) bl_set_density_units(ctx, 0, nullptr);
+    bl_internal_fail(ctx, rc, MessageOf(why).c_str());
   }
   return rc;
 }

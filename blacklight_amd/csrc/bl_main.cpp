@@ -189,7 +189,8 @@ int main(int argc, char *argv[]) {
   char err[1024] = "";
   int num_runs = 1;
   static bl_sweep sweep;   // sweep_rat_low / sweep_rat_high / sweep_rho_cgs: several images per snapshot, one file each
-  if (bl_params_read_file_sweep(&params, &sweep, argv[1], &num_runs, err, sizeof err) != BL_OK) {
+  static bl_sweep_cuts sweep_cuts;   // ... and sweep_cut_sigma_max, an axis of its own
+  if (bl_params_read_file_sweeps(&params, &sweep, &sweep_cuts, argv[1], &num_runs, err, sizeof err) != BL_OK) {
     std::cout << err;
     return 1;
   }
@@ -229,7 +230,7 @@ int main(int argc, char *argv[]) {
     // as the reference's do across thread counts. And so are runs over several devices: a frame and its tiles are then the same bits.
     if (params.adaptive_max_level > 0 || n_devices > 1) bl_set_reproducible(contexts[dev], 1);
     // the sweep on every device: a device's share of the frame then holds the rows of all variants, like the frame does
-    if (bl_apply_sweep(contexts[dev], &sweep) != BL_OK) {
+    if (bl_apply_sweeps(contexts[dev], &sweep, &sweep_cuts) != BL_OK) {
       std::cout << bl_last_error(contexts[dev]);
       return 1;
     }
@@ -518,7 +519,7 @@ int main(int argc, char *argv[]) {
   root_camera.Free();
   root_render.Free();
   bl_stats last_stats{};
-  const int n_models = bl_num_electron_models(contexts[0]), n_units = bl_num_density_units(contexts[0]);
+  const int n_models = bl_num_electron_models(contexts[0]), n_units = bl_num_density_units(contexts[0]), n_cuts = bl_num_sigma_cuts(contexts[0]);
   const bool triples = bl_num_polarized_variants(contexts[0]) > 0;
   bl_get_stats(contexts[0], &last_stats);   // (of the last root-level... of the last render of the first device: the tier is the context's)
   for (bl_ctx *c : contexts) bl_free(c);
@@ -539,10 +540,11 @@ int main(int argc, char *argv[]) {
             << (last_stats.arithmetic == BL_ARITH_TOLERANT ? (last_stats.composed_maps ? ", composed transfer maps (equal from run to run to rounding)" : ", bit-reproducible") : "")
             << (last_stats.geodesics_reused ? "; geodesics integrated once for the series" : "") << " (BLACKLIGHT_AMD_ARITHMETIC=exact|tolerant)\n";
   // (and, only with sweep keys in the input file, one line on what each snapshot's single render was written out as)
-  if (sweep.n_rat_low > 0 || sweep.n_rho_cgs > 0) {
+  if (sweep.n_rat_low > 0 || sweep.n_rho_cgs > 0 || sweep_cuts.n_sigma_max > 0) {
     std::cout << "blacklight_amd: sweep of " << n_variants << " variants per snapshot (";
     if (triples) std::cout << n_variants << " polarized triples";
     else std::cout << std::max(1, n_models) << " electron models x " << std::max(1, n_units) << " density units";
+    if (n_cuts > 0) std::cout << " x " << n_cuts << " sigma cuts";
     std::cout << "), one file each; writing outputs: " << time_write << " s\n";
   }
   return 0;

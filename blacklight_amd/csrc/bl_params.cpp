@@ -289,9 +289,10 @@ void ReadRender(bl_params *p, const std::string &key, const std::string &val) {
   throw ParseFailure{"Unknown key (render_" + key + ") in input file."};
 }
 
-// sweep_rat_low / sweep_rat_high / sweep_rho_cgs: "a,b,c" (an extension: the reference has no lists). Stricter than the scalar keys:
+// sweep_rat_low / sweep_rat_high / sweep_rho_cgs / sweep_cut_sigma_max: "a,b,c" (an extension: the reference has no lists). Stricter than the scalar keys:
 // every entry is a whole number text - nothing is left of it after the conversion -, none is empty, at most BL_MAX_SWEEP of them.
-int ReadList(const std::string &key, const std::string &val, bool unit, double *out) {
+enum ListKind { kNumbers, kUnits, kSigmaCuts };
+int ReadList(const std::string &key, const std::string &val, ListKind kind, double *out) {
   int count = 0;
   for (size_t at = 0; at <= val.size();) {
     const size_t comma = std::min(val.find(',', at), val.size());
@@ -300,8 +301,10 @@ int ReadList(const std::string &key, const std::string &val, bool unit, double *
     char *end = nullptr;
     const double x = std::strtod(entry.c_str(), &end);
     if (end == entry.c_str() || *end != '\0') throw ParseFailure{"Invalid number (" + entry + ") in list (" + key + ") in input file."};
-    if (unit && !(std::isfinite(x) && x > 0.0))
+    if (kind == kUnits && !(std::isfinite(x) && x > 0.0))
       throw ParseFailure{"Invalid density unit (" + entry + ") in list (" + key + ") in input file: must be finite and positive."};
+    if (kind == kSigmaCuts && !std::isfinite(x))
+      throw ParseFailure{"Invalid sigma cut (" + entry + ") in list (" + key + ") in input file: must be finite."};
     if (count >= BL_MAX_SWEEP)
       throw ParseFailure{"Too many entries in list (" + key + ") in input file: at most " + std::to_string(BL_MAX_SWEEP) + " for this build."};
     out[count++] = x;
@@ -310,11 +313,12 @@ int ReadList(const std::string &key, const std::string &val, bool unit, double *
   return count;
 }
 
-// The sweep keys go beside the parameter block (bl_sweep), never into it; false: not a sweep key
-bool SetSweepKey(bl_sweep *s, const std::string &key, const std::string &val) {
-  if (key == "sweep_rat_low") s->n_rat_low = ReadList(key, val, false, s->rat_low);
-  else if (key == "sweep_rat_high") s->n_rat_high = ReadList(key, val, false, s->rat_high);
-  else if (key == "sweep_rho_cgs") s->n_rho_cgs = ReadList(key, val, true, s->rho_cgs);
+// The sweep keys go beside the parameter block (bl_sweep, bl_sweep_cuts), never into it; false: not a sweep key
+bool SetSweepKey(bl_sweep *s, bl_sweep_cuts *c, const std::string &key, const std::string &val) {
+  if (key == "sweep_rat_low") s->n_rat_low = ReadList(key, val, kNumbers, s->rat_low);
+  else if (key == "sweep_rat_high") s->n_rat_high = ReadList(key, val, kNumbers, s->rat_high);
+  else if (key == "sweep_rho_cgs") s->n_rho_cgs = ReadList(key, val, kUnits, s->rho_cgs);
+  else if (key == "sweep_cut_sigma_max") c->n_sigma_max = ReadList(key, val, kSigmaCuts, c->sigma_max);
   else return false;
   return true;
 }
@@ -350,8 +354,8 @@ void ResolveSweep(const bl_sweep &s, const bl_params &p, bl_sweep *out, int *pol
   if (out != nullptr) *out = r;
 }
 
-void SetKeyValue(bl_params *p, bl_sweep *sweep, const std::string &key, const std::string &val) {
-  if (key.compare(0, 6, "sweep_") == 0 && SetSweepKey(sweep, key, val)) return;
+void SetKeyValue(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, const std::string &key, const std::string &val) {
+  if (key.compare(0, 6, "sweep_") == 0 && SetSweepKey(sweep, cuts, key, val)) return;
   // Compound keys first
   if (key == "cut_plane_origin") return ReadTriple(val, p, BL_P_cut_plane_origin_x);
   if (key == "cut_plane_normal") return ReadTriple(val, p, BL_P_cut_plane_normal_x);
@@ -399,7 +403,7 @@ void SetKeyValue(bl_params *p, bl_sweep *sweep, const std::string &key, const st
   throw ParseFailure{"Unknown key (" + key + ") in input file."};
 }
 
-void ParseLine(bl_params *p, bl_sweep *sweep, std::string line) {
+void ParseLine(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, std::string line) {
   std::string stripped;
   stripped.reserve(line.size());
   for (unsigned char c : line)
@@ -409,7 +413,7 @@ void ParseLine(bl_params *p, bl_sweep *sweep, std::string line) {
   if (stripped.empty()) return;
   pos = stripped.find('=');
   if (pos == std::string::npos) throw ParseFailure{"Invalid assignment in input file."};
-  SetKeyValue(p, sweep, stripped.substr(0, pos), stripped.substr(pos + 1));
+  SetKeyValue(p, sweep, cuts, stripped.substr(0, pos), stripped.substr(pos + 1));
 }
 
 }  // namespace
@@ -422,11 +426,12 @@ void bl_params_clear(bl_params *p) {
 
 size_t bl_params_sizeof(void) { return sizeof(bl_params); }
 
-int bl_params_set_line_sweep(bl_params *p, bl_sweep *sweep, const char *line, char *err, size_t err_len) {
+int bl_params_set_line_sweeps(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, const char *line, char *err, size_t err_len) {
   if (p == nullptr || line == nullptr) return BL_E_ARG;
   bl_sweep unused = {};   // (no sweep asked for: the keys are accepted and validated all the same)
+  bl_sweep_cuts unused_cuts = {};
   try {
-    ParseLine(p, sweep != nullptr ? sweep : &unused, line);
+    ParseLine(p, sweep != nullptr ? sweep : &unused, cuts != nullptr ? cuts : &unused_cuts, line);
   } catch (const ParseFailure &failure) {
     SetError(err, err_len, failure.message);
     return BL_E_INPUT;
@@ -434,23 +439,34 @@ int bl_params_set_line_sweep(bl_params *p, bl_sweep *sweep, const char *line, ch
   return BL_OK;
 }
 
+int bl_params_set_line_sweep(bl_params *p, bl_sweep *sweep, const char *line, char *err, size_t err_len) {
+  return bl_params_set_line_sweeps(p, sweep, nullptr, line, err, err_len);
+}
+
 int bl_params_set_line(bl_params *p, const char *line, char *err, size_t err_len) {
   return bl_params_set_line_sweep(p, nullptr, line, err, err_len);
 }
 
 int bl_params_read_file_sweep(bl_params *p, bl_sweep *sweep, const char *path, int *num_runs, char *err, size_t err_len) {
+  return bl_params_read_file_sweeps(p, sweep, nullptr, path, num_runs, err, err_len);
+}
+
+int bl_params_read_file_sweeps(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, const char *path, int *num_runs, char *err, size_t err_len) {
   if (p == nullptr || path == nullptr) return BL_E_ARG;
   bl_params_clear(p);
   bl_sweep local = {};
+  bl_sweep_cuts local_cuts = {};
   if (sweep == nullptr) sweep = &local;
+  if (cuts == nullptr) cuts = &local_cuts;
   *sweep = bl_sweep{};
+  *cuts = bl_sweep_cuts{};
   std::ifstream stream(path);
   if (!stream.is_open()) {
     SetError(err, err_len, "Could not open input file.");
     return BL_E_INPUT;
   }
   try {
-    for (std::string line; std::getline(stream, line);) ParseLine(p, sweep, line);
+    for (std::string line; std::getline(stream, line);) ParseLine(p, sweep, cuts, line);
     ResolveSweep(*sweep, *p, nullptr, nullptr);   // the lists against each other, once the whole file is known
   } catch (const ParseFailure &failure) {
     SetError(err, err_len, failure.message);

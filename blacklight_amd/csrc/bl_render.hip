@@ -111,16 +111,18 @@ struct RenderJob {
   size_t park_capacity = 0;
   int quad_grid = 0;          // waves of bl_geodesic_quad_kernel
   int n_nu = 0, n_q = 0, max_steps = 0;
-  // The render's variants (ResolveVariants: models x units, model-major, or the triples of a polarized run), each with n_q_model image
+  // The render's variants (ResolveVariants: models x units x sigma cuts, model-major, or the triples of a polarized run), each with n_q_model image
   // rows (n_q = variants x n_q_model); the shading stage runs once per variant over the chunk's samples (variant_passes)
   Variants variants;
   int n_q_model = 0, variant_passes = 1;
-  bool variants_one_pass = false;   // ... or all of them in one pass: one gather, one lane per (ray, model, unit, frequency) in the transfer kernel
+  bool variants_one_pass = false;   // ... or all of them in one pass: one gather, one lane per (ray, model, unit, cut, frequency) in the transfer kernel
   double base_rho = 0.0, base_rat_low = 0.0, base_rat_high = 0.0;   // what BuildShadeArgs folds (PlanJob; one pass: the rows' unit and pair)
+  double base_sigma_max = -1.0;     // ... and its cut_sigma_max (one pass over two cuts or more: off, the transfer kernel compares each lane's)
   // ... or pol_one_pass, the triples': the coefficient kernel and the transport matrices once per chunk,
   // bl_polarized_coefficients_kernel and the polarized transfer kernels with a variant axis
   bool pol_one_pass = false;
-  int n_cold = 1;                   // BlShadeCold blocks on the device: one per unit where the passes' cut thresholds differ (BindVariant)
+  int n_cold = 1;                   // BlShadeCold blocks on the device: one per (unit, sigma cut) where the passes' cut thresholds differ (BindVariant)
+  int cold_units = 1, cold_cuts = 1;   // ... n_cold = cold_units x cold_cuts, an axis of one where the passes do not differ along it
   long long n_rays = 0, level_pixels = 0;
   size_t redo_capacity = 0;
   // scratch
@@ -257,10 +259,11 @@ void FoldUnits(const bl_ctx *ctx, double rho_cgs, BlPlasmaDevice &pl, double (&f
 
 // ... and the tolerant tier's cell cut thresholds, which it compares in code units (rho, rho for n_e, p, k T_e for Theta_e, |b| in
 // code units; sigma and 1 / beta have none): scaled once here by pl's units; the guard band is relative and scales with them
-void FoldFastCuts(const bl_ctx *ctx, const BlPlasmaDevice &pl, BlShadeCold &cold) {
+// (sigma_max: the pass's cut_sigma_max - the render's, or a variant's under bl_set_sigma_cuts)
+void FoldFastCuts(const bl_ctx *ctx, const BlPlasmaDevice &pl, BlShadeCold &cold, double sigma_max) {
   const bl_params &p = ctx->params;
   const double cuts[14] = {p.cut_rho_min, p.cut_rho_max, p.cut_n_e_min, p.cut_n_e_max, p.cut_p_gas_min, p.cut_p_gas_max,
-                           p.cut_theta_e_min, p.cut_theta_e_max, p.cut_b_min, p.cut_b_max, p.cut_sigma_min, p.cut_sigma_max,
+                           p.cut_theta_e_min, p.cut_theta_e_max, p.cut_b_min, p.cut_b_max, p.cut_sigma_min, sigma_max,
                            p.cut_beta_inverse_min, p.cut_beta_inverse_max};
   for (int c = 0; c < 14; c++) {
     const bool active = cuts[c] >= 0.0;
@@ -274,9 +277,10 @@ void FoldFastCuts(const bl_ctx *ctx, const BlPlasmaDevice &pl, BlShadeCold &cold
 }
 
 // Variant v of the render into the argument blocks: its pair where the coefficient kernels read R_low / R_high, its unit folded as
-// BuildShadeArgs folds the render's (FoldUnits), the cut thresholds of its unit (its BlShadeCold, uploaded by BuildShadeArgs), and its
-// rows of the image. Nothing to do with one variant - the one BuildShadeArgs folded - or where one pass has them all: the transfer
-// kernel has every variant's constants (BuildTransferArgs), the polarized coefficient kernel its table (BuildShadeArgs).
+// BuildShadeArgs folds the render's (FoldUnits), the cut thresholds of its unit and its sigma cut (its BlShadeCold, uploaded by
+// BuildShadeArgs; the cut's bit of the mask, which a negative value switches off), and its rows of the image. Nothing to do with one
+// variant - the one BuildShadeArgs folded - or where one pass has them all: the transfer kernel has every variant's constants
+// (BuildTransferArgs), the polarized coefficient kernel its table (BuildShadeArgs).
 void BindVariant(RenderJob &job, int v) {
   if (job.variants.list.size() == 1 || job.variants_one_pass || job.pol_one_pass) return;
   const Variant &variant = job.variants.list[v];
@@ -284,7 +288,11 @@ void BindVariant(RenderJob &job, int v) {
   pl.plasma_rat_low = variant.rat_low;
   pl.plasma_rat_high = variant.rat_high;
   FoldUnits(job.ctx, variant.rho, pl, job.sa.fast_k);
-  job.sa.cold = job.ctx->d_shade_cold.ptr + (job.n_cold > 1 ? v % job.variants.n_units : 0);
+  const int n_s = std::max(1, job.variants.n_cuts), n_u = std::max(1, job.variants.n_units);   // (v = (m n_u + u) n_s + s)
+  const int u = (v / n_s) % n_u, s = v % n_s;
+  job.sa.cold = job.ctx->d_shade_cold.ptr + ((job.cold_units > 1 ? u : 0) * job.cold_cuts + (job.cold_cuts > 1 ? s : 0));
+  pl.cut_mask = (pl.cut_mask & ~(1 << 11)) | (variant.sigma_max >= 0.0 ? 1 << 11 : 0);   // (bit 11: cut_sigma_max, FoldFastCuts' order)
+  pl.any_cell_cut = pl.cut_mask != 0 ? 1 : 0;
   job.xa.image = job.image + static_cast<size_t>(v) * job.n_q_model * static_cast<size_t>(job.n_rays);
 }
 
@@ -323,6 +331,7 @@ void PlanJob(RenderJob &job) {
   if (const char *why = ElectronModelsRefusal(ctx, vs.n_models)) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = DensityUnitsRefusal(ctx, vs.n_units)) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = PolarizedVariantsRefusal(ctx, vs.n_pol)) throw Failure{BL_E_UNSUPPORTED, why};
+  if (const char *why = SigmaCutsRefusal(ctx, vs.n_cuts)) throw Failure{BL_E_UNSUPPORTED, why};
   // What BuildShadeArgs folds before a variant is bound: the first variant - one variant is a fresh render with it in the parameter
   // block, and the first triple's cut decisions are every triple's in one pass. But several (model, unit) variants keep the parameter
   // block's pair, and two or more units its unit too (so base_rho is the one set unit, the first triple's, else the parameter block's):
@@ -332,6 +341,7 @@ void PlanJob(RenderJob &job) {
   job.base_rho = first.rho, job.base_rat_low = first.rat_low, job.base_rat_high = first.rat_high;
   if (vs.n_pol == 0 && vs.list.size() >= 2) job.base_rat_low = p.plasma_rat_low, job.base_rat_high = p.plasma_rat_high;
   if (vs.n_units >= 2) job.base_rho = p.simulation_rho_cgs;
+  job.base_sigma_max = first.sigma_max;   // (one cut: every variant's; passes: BindVariant each variant's; one pass over several: off, below)
   job.n_nu = p.image_num_frequencies;
   job.n_q_model = ctx->image_num_quantities;
   job.variant_passes = static_cast<int>(vs.list.size());
@@ -401,13 +411,21 @@ void PlanJob(RenderJob &job) {
   // to each unit (everything else: one shading pass per variant over the shared samples, LaunchShadingStage)
   job.variants_one_pass = job.variant_passes >= 2 && job.fast && p.plasma_power_frac == 0.0 && !job.tau_row && !job.aux && ctx->render_num_images == 0
       && !ThetaECut(p) && !(vs.n_units >= 2 && UnitCut(p))
-      && !(vs.n_units >= 2 && job.n_rays * job.n_nu * job.variant_passes >= (1ll << 31));   // (the transfer kernel's lanes of a chunk fit one grid)
+      && !((vs.n_units >= 2 || vs.n_cuts >= 2) && job.n_rays * job.n_nu * job.variant_passes >= (1ll << 31));   // (the transfer kernel's lanes of a chunk fit one grid)
   if (job.variants_one_pass) {
     job.freq_split = true;
     job.variant_passes = 1;
+    // Two sigma cuts or more: the coefficient kernels run with the sigma upper cut off and leave every sample's sigma in its row; a
+    // transfer lane compares it with its own threshold (BuildTransferArgs), and the tolerant kernels leave a sample whose sigma lies
+    // in the guard band of any of the thresholds to the exact pass (BuildShadeArgs: BlShadeArgs::sigma_band_lo / _hi)
+    if (vs.n_cuts >= 2) job.base_sigma_max = -1.0;
   }
-  // (the passes of two units or more compare the cut thresholds of their own unit: one BlShadeCold each)
-  job.n_cold = job.simulation && job.variant_passes >= 2 && vs.n_units >= 2 ? vs.n_units : 1;
+  // (the passes of two units or more compare the cut thresholds of their own unit, those of two sigma cuts or more their own
+  // cut_sigma_max: one BlShadeCold per (unit, cut))
+  const bool cold_per_pass = job.simulation && job.variant_passes >= 2;
+  job.cold_units = cold_per_pass && vs.n_units >= 2 ? vs.n_units : 1;
+  job.cold_cuts = cold_per_pass && vs.n_cuts >= 2 ? vs.n_cuts : 1;
+  job.n_cold = job.cold_units * job.cold_cuts;
   // Plain images of a spherical Kerr-Schild simulation with fallback values beyond the grid: nothing is recorded of the steps that
   // lie in the empty shell between the grid's outer edge and the camera's sphere (both tiers; the samples count as ever)
   job.skip_shell = job.simulation && !job.aux && !ctx->polarized && !job.slow && job.no_checkpoint
@@ -1550,11 +1568,11 @@ void BuildShadeArgs(RenderJob &job) {
     cold.cut_p_gas_min = lower(p.cut_p_gas_min); cold.cut_p_gas_max = upper(p.cut_p_gas_max);
     cold.cut_theta_e_min = lower(p.cut_theta_e_min); cold.cut_theta_e_max = upper(p.cut_theta_e_max);
     cold.cut_b_min = lower(p.cut_b_min); cold.cut_b_max = upper(p.cut_b_max);
-    cold.cut_sigma_min = lower(p.cut_sigma_min); cold.cut_sigma_max = upper(p.cut_sigma_max);
+    cold.cut_sigma_min = lower(p.cut_sigma_min); cold.cut_sigma_max = upper(job.base_sigma_max);   // (the render's: PlanJob)
     cold.cut_beta_inverse_min = lower(p.cut_beta_inverse_min); cold.cut_beta_inverse_max = upper(p.cut_beta_inverse_max);
     {
       const double cuts[14] = {p.cut_rho_min, p.cut_rho_max, p.cut_n_e_min, p.cut_n_e_max, p.cut_p_gas_min, p.cut_p_gas_max,
-                               p.cut_theta_e_min, p.cut_theta_e_max, p.cut_b_min, p.cut_b_max, p.cut_sigma_min, p.cut_sigma_max,
+                               p.cut_theta_e_min, p.cut_theta_e_max, p.cut_b_min, p.cut_b_max, p.cut_sigma_min, job.base_sigma_max,
                                p.cut_beta_inverse_min, p.cut_beta_inverse_max};
       pl.cut_mask = 0;
       pl.any_cell_cut = 0;
@@ -1563,7 +1581,19 @@ void BuildShadeArgs(RenderJob &job) {
         if (active) pl.cut_mask |= 1 << c;
         if (active) pl.any_cell_cut = 1;
       }
-      FoldFastCuts(ctx, pl, cold);   // (the fast kernels' thresholds in code units)
+      FoldFastCuts(ctx, pl, cold, job.base_sigma_max);   // (the fast kernels' thresholds in code units)
+      // Sigma cuts in one pass: the guard band of every threshold, folded as FoldFastCuts folds one (sigma has no unit); a
+      // switched-off threshold has an empty band
+      sa.n_sigma_bands = 0;
+      if (job.variants_one_pass && job.variants.n_cuts >= 2) {
+        static_assert(BL_SHADE_MAX_SIGMA_CUTS == BL_MAX_SIGMA_CUTS, "sigma cut bands");
+        sa.n_sigma_bands = job.variants.n_cuts;
+        for (int s = 0; s < job.variants.n_cuts; s++) {
+          const double cut = job.variants.list[s].sigma_max;   // (the first (model, unit)'s variants are the cuts)
+          sa.sigma_band_lo[s] = cut >= 0.0 ? cut * (1.0 - ctx->guard_band) : kInf;
+          sa.sigma_band_hi[s] = cut >= 0.0 ? cut * (1.0 + ctx->guard_band) : -kInf;
+        }
+      }
       sa.fast_angle_band = std::max(1.0e-12, ctx->guard_band > 1.0e-8 ? ctx->guard_band : 0.0);   // (the debug switch widens both kinds of band)
     }
     sa.grid = ctx->grid_dev;
@@ -1581,19 +1611,25 @@ void BuildShadeArgs(RenderJob &job) {
   }
   sa.samples_renormalised = job.geo_load ? 1 : 0;
   sa.general_locate = (ctx->switches & BL_SWITCH_GENERAL_LOCATE) ? 1 : 0;
-  // One block per unit where the passes of two units or more compare their own cut thresholds (job.n_cold; BindVariant points at its
-  // unit's): the render's block with the thresholds refolded, byte for byte otherwise
+  // One block per (unit, sigma cut) where the passes of two units or more compare their own cut thresholds and those of two cuts or
+  // more their own cut_sigma_max (job.n_cold; BindVariant points at its variant's): the render's block with the thresholds refolded,
+  // byte for byte otherwise
   std::vector<unsigned char> colds(job.n_cold * sizeof(BlShadeCold));
-  for (int u = 0; u < job.n_cold; u++) {
-    std::memcpy(colds.data() + u * sizeof(BlShadeCold), &cold, sizeof(BlShadeCold));
+  for (int b = 0; b < job.n_cold; b++) {
+    std::memcpy(colds.data() + b * sizeof(BlShadeCold), &cold, sizeof(BlShadeCold));
     if (job.n_cold > 1) {
+      // (model-major, then unit, then cut: the first model's variants are the (unit, cut) pairs)
+      const int n_s = std::max(1, job.variants.n_cuts), u = b / job.cold_cuts, s = b % job.cold_cuts;
+      const Variant &variant = job.variants.list[(job.cold_units > 1 ? u : 0) * n_s + (job.cold_cuts > 1 ? s : 0)];
       BlShadeCold unit_cold;
       std::memcpy(static_cast<void *>(&unit_cold), &cold, sizeof(BlShadeCold));
       BlPlasmaDevice unit_pl = sa.plasma;
       double unit_k[8];
-      FoldUnits(ctx, job.variants.list[u].rho, unit_pl, unit_k);   // (model-major: the first model's variants are the units)
-      FoldFastCuts(ctx, unit_pl, unit_cold);
-      std::memcpy(colds.data() + u * sizeof(BlShadeCold), &unit_cold, sizeof(BlShadeCold));
+      FoldUnits(ctx, job.cold_units > 1 ? variant.rho : job.base_rho, unit_pl, unit_k);
+      const double sigma_max = job.cold_cuts > 1 ? variant.sigma_max : job.base_sigma_max;
+      unit_cold.cut_sigma_max = sigma_max >= 0.0 ? sigma_max : std::numeric_limits<double>::infinity();
+      FoldFastCuts(ctx, unit_pl, unit_cold, sigma_max);
+      std::memcpy(colds.data() + b * sizeof(BlShadeCold), &unit_cold, sizeof(BlShadeCold));
     }
   }
   // (uploaded when it differs from what the device holds: a frame loop uploads it once and waits for nothing here)
@@ -1696,6 +1732,7 @@ void BuildTransferArgs(RenderJob &job) {
   xa.image = job.image;
   xa.n_models = 0;
   xa.n_units = 0;
+  xa.n_cuts = 0;
   xa.pol_variants = job.pol_one_pass ? job.variants.n_pol : 0;
   xa.pol_variant_rows = job.n_q_model;
   if (job.variants_one_pass) {   // every model's R_high / R_low folded as BuildShadeArgs folds the parameter block's (fast_k[1..3])
@@ -1705,11 +1742,12 @@ void BuildTransferArgs(RenderJob &job) {
     const double g1 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_i - 1.0);
     const double g2 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_e - 1.0);
     const Variants &vs = job.variants;
-    const int n_u = std::max(1, vs.n_units);   // (model-major: model m's variants start at m n_u, the first model's are the units)
-    xa.n_models = static_cast<int>(vs.list.size()) / n_u;   // (no models set: the parameter block's pair is model 0)
+    // (model-major, then unit, then cut: model m's variants start at m n_u n_s, the first model's are the (unit, cut) pairs)
+    const int n_u = std::max(1, vs.n_units), n_s = std::max(1, vs.n_cuts);
+    xa.n_models = static_cast<int>(vs.list.size()) / (n_u * n_s);   // (no models set: the parameter block's pair is model 0)
     for (int m = 0; m < xa.n_models; m++) {
-      xa.model_k1[m] = vs.list[m * n_u].rat_high * g1;
-      xa.model_k2[m] = vs.list[m * n_u].rat_low * g1;
+      xa.model_k1[m] = vs.list[m * n_u * n_s].rat_high * g1;
+      xa.model_k2[m] = vs.list[m * n_u * n_s].rat_low * g1;
     }
     xa.model_k3 = p.plasma_ne_ni * g2;
     // Two units or more: the rows hold base_rho's x at unit frequency (1 / b_unit: x = nu / nu_s, nu_s ~ nu_c ~ |b| b_unit) and s_j
@@ -1721,10 +1759,18 @@ void BuildTransferArgs(RenderJob &job) {
       FoldUnits(ctx, job.base_rho, base, k);
       xa.n_units = vs.n_units;
       for (int u = 0; u < vs.n_units; u++) {
-        FoldUnits(ctx, vs.list[u].rho, unit, k);
+        FoldUnits(ctx, vs.list[u * n_s].rho, unit, k);
         xa.unit_x[u] = base.b_unit / unit.b_unit;
         xa.unit_j[u] = (unit.d_unit * unit.b_unit) / (base.d_unit * base.b_unit);
       }
+    }
+    // Two sigma cuts or more: the rows carry every sample's sigma (the coefficient kernels ran with the upper cut off); cut s leaves
+    // out the samples with sigma > sigma_max[s], +inf where it is switched off
+    if (vs.n_cuts >= 2) {
+      static_assert(BL_TRANSFER_MAX_CUTS == BL_MAX_SIGMA_CUTS, "sigma cut constants");
+      xa.n_cuts = vs.n_cuts;
+      for (int c = 0; c < vs.n_cuts; c++)
+        xa.sigma_max[c] = vs.list[c].sigma_max >= 0.0 ? vs.list[c].sigma_max : std::numeric_limits<double>::infinity();
     }
   }
   xa.out_sample_num = job.out_num;

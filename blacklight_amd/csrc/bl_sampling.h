@@ -1050,7 +1050,8 @@ template <bool kExtended, bool kSksCurved>
 __device__ __forceinline__ void sample_finish_simulation(const BlShadeArgs &P, const BlSpacetime &st,
                                                          const BlKerrSchild &ks, double cth, double ph_unwrapped,
                                                          const float pr[8], float kappa_f, const double kcov[4],
-                                                         int need_coefficients, SampleShade *out, BlPolSample *pol_out) {
+                                                         int need_coefficients, SampleShade *out, BlPolSample *pol_out,
+                                                         double *sigma_out = nullptr) {
   const BlPlasmaDevice &pl = P.plasma;
   const double bh_a = st.bh_a, bh_m = st.bh_m;
   const double r = ks.r, r2 = ks.r2, a2 = ks.a2;
@@ -1189,6 +1190,9 @@ __device__ __forceinline__ void sample_finish_simulation(const BlShadeArgs &P, c
   out->cell[3] = theta_e;
   out->cell[4] = bb_cgs;
   out->cell[5] = sigma_cut;
+  // (sigma cuts in one pass: the exact second pass leaves sigma in the sample's model-free row - stored here, where its last use was,
+  // so that it is not one more value held across the coefficient arithmetic below)
+  if (sigma_out != nullptr) *sigma_out = sigma_cut;
   out->cell[6] = beta_inv;
   if (need_coefficients == 0 || no_field) return;   // :389-395
 

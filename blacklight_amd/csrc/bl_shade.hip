@@ -189,7 +189,8 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
       if (kModel == BL_MODEL_SIMULATION)
         sample_finish_simulation<kExtended, kSksCurved>(P, st, ks, x3 / ks.r, ph, pr, kappa_f, kcov,
                                             kAux ? P.aux_need_coefficients : 1, &sh,
-                                            kPolarized ? P.pol_samples + row : nullptr);
+                                            kPolarized ? P.pol_samples + row : nullptr,
+                                            kRedo && P.freq_split == 2 ? &P.freq_inputs[row].pad : nullptr);
       else if (!(kAux && nan_ray))
         shade_formula(P, st, ks.r, x1, x2, x3, &sh);
     }
@@ -233,7 +234,7 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
         dst[1] = make_double2(kH * s_nu, P.plasma.plasma_thermal_frac * sh.n_e_cgs * kE * kE * sh.nu_c_cgs * (1.0 / kC)
                                   * (kSqrt2 * kPi / 27.0) * sh.sin_theta_b / (s_nu * s_nu));
         dst[2] = make_double2(delta_lambda * P.x_unit / momentum_factor, bi2);
-        dst[3] = make_double2(sh.kb_tt_e_cgs * nn / dd, 0.0);
+        reinterpret_cast<double *>(dst)[6] = sh.kb_tt_e_cgs * nn / dd;   // (the row's last double is the sample's sigma: sample_finish_simulation)
       } else {
         const double nu_s_cgs = 2.0 / 9.0 * sh.nu_c_cgs * sh.theta_e * sh.theta_e * sh.sin_theta_b;
         const double s_nu = sh.nu_fluid_over_nu * momentum_factor;

@@ -29,7 +29,7 @@ __device__ __forceinline__ bool fast_shade_sample(const BlShadeArgs &P, const do
   // what the loop over frequencies needs
   bool have = false;
   double nu_ratio = 0.0, n_e_cgs = 0.0, kb_tt_e_cgs = 0.0, k_u_inv = 0.0, b_sin = 0.0, b_sin_inv = 0.0;
-  double model_bi2 = 0.0, model_kt_tot = 0.0;   // electron models in one pass (freq_split = 2): 1 / beta^2, K0 p / rho
+  double model_bi2 = 0.0, model_kt_tot = 0.0, model_sigma = 0.0;   // electron models in one pass (freq_split = 2): 1 / beta^2, K0 p / rho, sigma
   const double rho = pr[0], pgas = pr[1], uu1 = pr[2], uu2 = pr[3], uu3 = pr[4], bb1 = pr[5], bb2 = pr[6], bb3 = pr[7];
   if (status != kSampleCut) {
     // ---- Kerr-Schild scalars (radiation_geometry.cpp:18-25, :138-262)
@@ -142,6 +142,7 @@ __device__ __forceinline__ bool fast_shade_sample(const BlShadeArgs &P, const do
       kb_tt_e_cgs = P.fast_k[0] * (pgas * rho_inv) * (dd * fastmath::rcp(P.fast_k[1] + P.fast_k[2] * bi2 + P.fast_k[3] * dd));
       model_bi2 = bi2;
       model_kt_tot = P.fast_k[0] * (pgas * rho_inv);
+      model_sigma = sigma_cut;
     }
     // ---- cell cuts (:361-375): decided here unless a value sits within the guard band of an active threshold
     bool cell_cut = false, undecided = !cartesian && pp2 == 0.0;   // (on the polar axis of the spherical coordinates: the exact kernel's business)
@@ -165,6 +166,10 @@ __device__ __forceinline__ bool fast_shade_sample(const BlShadeArgs &P, const do
           }
         }
     }
+    // (sigma cuts in one pass, wave-uniform: the upper cut is off above, the transfer kernel's lanes compare the row's sigma with
+    // their thresholds - inside the guard band of any of them the exact pass writes the row)
+    if (P.freq_split == 2)
+      for (int s = 0; s < P.n_sigma_bands; s++) undecided = undecided | ((sigma_cut >= P.sigma_band_lo[s]) & (sigma_cut <= P.sigma_band_hi[s]));
     if (undecided) return false;   // bl_shade_kernel<..., kRedo> writes this sample's records
     const bool no_field = bb1 == 0.0 && bb2 == 0.0 && bb3 == 0.0;   // :394
     if (!cell_cut && !no_field) {
@@ -218,7 +223,7 @@ __device__ __forceinline__ bool fast_shade_sample(const BlShadeArgs &P, const do
     dst[0] = make_double2(have ? 1.0 : 0.0, have ? s_nu * b_sin_inv * P.fast_k[4] : 0.0);
     dst[1] = make_double2(kH * s_nu, s_j);
     dst[2] = make_double2(s_length, model_bi2);
-    dst[3] = make_double2(model_kt_tot, 0.0);
+    dst[3] = make_double2(model_kt_tot, model_sigma);
     return true;
   }
   if (P.freq_split) {   // several frequencies: the factors go to bl_transfer_freq_kernel, one lane per ray and frequency

@@ -530,11 +530,15 @@ __device__ __forceinline__ bool trilinear(const float4 (&lo)[8], const float4 (&
 // is left once everything that does not depend on the frequency has been evaluated (BlFreqInputs) - for bl_transfer_freq_kernel,
 // and stores them itself (in row factors_row of `factors`; -1 for a sample the caller has already left to the exact kernel: eight
 // more live doubles across the caller's loop are eight too many).
+// sigma_bands (model_rows with sigma cuts in one pass, BlShadeArgs::n_sigma_bands; wave-uniform): the sigma upper cut is off here, the
+// row carries sigma for the transfer kernel's lanes to compare, and a sample whose sigma lies in the guard band of any of the
+// thresholds is undecided - the exact pass writes its row.
 template <bool kSpinZero, bool kFactors = false>
 __device__ __forceinline__ double2 shade(const BlSpacetime &st, const double (&K)[6], double freq, double freq_inv, double x_unit, int cut_mask,
                                          uint32_t cut_table, const float pr[8], double x, double y, double z, double kx, double ky, double kz, double kt,
                                          double momentum_factor, double delta_lambda, bool *have_out, bool *undecided_out, double2 (*factors)[4] = nullptr,
-                                         bool model_rows = false) {
+                                         bool model_rows = false, int sigma_bands = 0, const double *sigma_band_lo = nullptr,
+                                         const double *sigma_band_hi = nullptr) {
   const double bh_m = st.bh_m;
   const double bh_a = kSpinZero ? 0.0 : st.bh_a;
   const double a2 = bh_a * bh_a;
@@ -634,6 +638,8 @@ __device__ __forceinline__ double2 shade(const BlSpacetime &st, const double (&K
         undecided = undecided | ((q >= b_lo.x) & (q <= b_lo.y)) | ((q >= b_hi.x) & (q <= b_hi.y));
       }
   }
+  if (kFactors)
+    for (int s = 0; s < sigma_bands; s++) undecided = undecided | ((sigma_cut >= sigma_band_lo[s]) & (sigma_cut <= sigma_band_hi[s]));
   const bool no_field = bb1 == 0.0 && bb2 == 0.0 && bb3 == 0.0;   // :394
   const bool have = !cell_cut && !no_field;
   *have_out = have;
@@ -659,7 +665,7 @@ __device__ __forceinline__ double2 shade(const BlSpacetime &st, const double (&K
       (*factors)[0] = make_double2(have ? 1.0 : 0.0, s_nu * b_sin_inv * K[4]);
       (*factors)[1] = make_double2(KS(kH) * s_nu, K[5] * (rho * b_sin) * (s_nu_inv * s_nu_inv));
       (*factors)[2] = make_double2(delta_lambda * x_unit * mf_inv, bi2);
-      (*factors)[3] = make_double2(K[0] * (pgas * rho_inv), 0.0);
+      (*factors)[3] = make_double2(K[0] * (pgas * rho_inv), sigma_cut);
       return make_double2(1.0, 0.0);
     }
     (*factors)[0] = make_double2(have ? 1.0 : 0.0, s_1_6 * s_1_3);   // flag 1: factors follow; 0: nothing to add (cut cell, no field)
@@ -924,7 +930,8 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     if (kFactors) factors[0] = factors[1] = factors[2] = factors[3] = make_double2(0.0, 0.0);
     if (interp)
       rec = shade<kSpinZero, kFactors>(st, K, freq, freq_inv, x_unit, cut_mask, cut_table, pr, p.h0.x, p.h0.y, p.h1.x, p.c0.x, p.c0.y, p.c1.x, kt, momentum_factor,
-                                       -p.c1.y, &have, &undecided_cut, kFactors ? &factors : nullptr, kFactors && model_rows);
+                                       -p.c1.y, &have, &undecided_cut, kFactors ? &factors : nullptr, kFactors && model_rows,
+                                       kFactors ? P.n_sigma_bands : 0, P.sigma_band_lo, P.sigma_band_hi);
     // a sample off the grid has fallback primitives without a field (no coefficients: I <- I) or NaN ones (I <- I + NaN,
     // simulation_sampling.cpp:377-384); a cut sample has none either
     const bool defer = interp && (undecided_cut || near_midpoint || (p.loc.status & kPlainUndecided) != 0u);

@@ -7,6 +7,8 @@
 //                            built from per-sample factors on the fly
 //   bl_transfer_aux_kernel   image_light and the nine auxiliary images.   (unpolarized.cpp:113-196)
 //   bl_tau_kernel            optical depth beside the intensities in the tolerant tier
+#include <type_traits>
+
 #include "bl_kernel_util.h"
 
 #pragma clang fp contract(fast)
@@ -20,13 +22,17 @@
 // enters (BlFreqInputs), and the lane forms its model's 1 / (k T_e) per sample before the same step. With density units as well
 // (P.n_units > 0) a lane is a (ray, model, unit, frequency), and its unit scales the row's x at unit frequency and s_j (unit_x,
 // unit_j), folded into the lane's frequency terms once: no work per sample. (Without units the factors are 1.0: the same bits.)
+// With sigma cuts as well (P.n_cuts > 0) a lane is a (ray, model, unit, cut, frequency): the rows carry the sample's sigma, and the
+// lane leaves out the samples above its own threshold - one compare per sample. (Without cuts the threshold is +inf, against which no
+// sigma compares greater - NaN included, as in the reference: the same decisions.)
 __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool models = P.n_models > 0;
   const int n_units = P.n_units > 0 ? P.n_units : 1;
-  const int channels = models ? P.n_models * n_units * P.n_nu : P.n_nu;
+  const int n_cuts = P.n_cuts > 0 ? P.n_cuts : 1;
+  const int channels = models ? P.n_models * n_units * n_cuts * P.n_nu : P.n_nu;
   const int slot = (int)(t / channels);
-  const int channel = (int)(t % channels);   // (m n_units + u) n_nu + l: the image row
+  const int channel = (int)(t % channels);   // ((m n_units + u) n_cuts + s) n_nu + l: the image row
   const int l = channel % P.n_nu;
   unsigned long long samples = 0ull, flagged = 0ull;
   int max_num = 0;
@@ -48,69 +54,78 @@ __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P)
     if (P.fallback_nan && flag) {
       intensity = num > 0 ? nan : 0.0;   // every sample of a flagged ray carries NaN primitives (simulation_sampling.cpp:211-216)
     } else {
-      const int variant = channel / P.n_nu, m = variant / n_units, u = variant - m * n_units;
-      // Unit u's factors where no sample register holds them: x at unit frequency enters only as x f, so unit_x is a factor on the
-      // frequency of the x terms (f_1_2, f_1_3, f_1_6), and s_j only as s_j f^-2, so unit_j is one on f_inv2 (without units: 1.0)
-      const double ux = P.n_units > 0 ? P.unit_x[u] : 1.0, uj = P.n_units > 0 ? P.unit_j[u] : 1.0;
-      const double f_x = f * ux;
-      const double f_1_2 = bl_sqrt_g(f_x), f_1_3 = fastmath::cbrt(f_x);
-      const double f_1_6 = bl_sqrt_g(f_1_3), f_inv = fastmath::rcp(f);
-      const double f_inv2 = f_inv * f_inv * uj;
-      // (one exponential per sample and frequency is most of this loop: its constants stay in scalar registers across it)
-      double exp_c[15];
-#pragma unroll
-      for (int i = 0; i < 15; i++) exp_c[i] = fastmath::resident_constant(fastmath::kExpConstants[i]);
-      const double2 *in = reinterpret_cast<const double2 *>(P.freq_inputs + (size_t)P.ray_offset[slot]);
-      const double kThird = fastmath::resident_constant(1.0 / 3.0), kInvPlanck = fastmath::resident_constant(kC * kC / (2.0 * kH));
-      const double kRoot = fastmath::resident_constant(kPow2_11_12), kThin = fastmath::resident_constant(0x1p-10);
-      const double mk1 = models ? P.model_k1[m] : 0.0, mk2 = models ? P.model_k2[m] : 0.0, mk3 = P.model_k3;
-      for (int n = num - 1; n >= 0; n--) {   // reference sample order is reversed integration order (geodesics.cpp:832-840)
-        const double2 q0 = in[4 * (size_t)n], q1 = in[4 * (size_t)n + 1], q2 = in[4 * (size_t)n + 2], q3 = in[4 * (size_t)n + 3];
-        // bl_shade_fast_kernel's frequency loop (simulation_coefficients.cpp:464-523, unpolarized.cpp:74-110) as one straight line for
-        // the sample that has coefficients, a thin step and h nu << k T_e - nearly every one: no expm1, no division, no branch; the
-        // rest is selected or, where it needs an exponential of its own, redone behind a branch
-        const bool have = q0.x == 1.0;
-        double s_1_3 = q1.x, s_1_6 = q1.y, s_1_2 = q0.y, s_planck = q2.x, s_j = q2.y, s_length = q3.x;
-        if (models) {   // this model's 1 / (k T_e) (the fused kernel's kte_inv), then the sample's roots at unit frequency
-          const double bi2 = q2.y, dd = 1.0 + bi2;
-          const double kte_inv = (mk1 + mk2 * bi2 + mk3 * dd) * fastmath::rcp(q3.x * dd);
-          s_1_3 = fastmath::cbrt(q0.y * (kte_inv * kte_inv));
-          s_1_6 = bl_sqrt_g(s_1_3);
-          s_1_2 = s_1_6 * s_1_3;
-          s_planck = q1.x * kte_inv;
-          s_j = q1.y;
-          s_length = q2.x;
-        }
-        const double xx_1_3 = s_1_3 * f_1_3;
-        const double var_c = s_1_2 * f_1_2 + kRoot * (s_1_6 * f_1_6);
-        const double j_val = s_j * f_inv2 * fastmath::exp(-xx_1_3, exp_c) * var_c * var_c;
-        const double xp = s_planck * f;
-        double planck = xp * (1.0 + 0.5 * xp * (1.0 + kThird * xp * (1.0 + 0.25 * xp)));
-        if (__builtin_expect(have && !(xp < kThin), 0)) planck = fastmath::expm1(xp);
-        double alpha_val = j_val * (planck * kInvPlanck);
-        if (alpha_val * alpha_val <= 0x1p-1024) alpha_val = 0.0;
-        const double delta_lambda_cgs = s_length * f_inv;
-        const double delta_tau = alpha_val * delta_lambda_cgs;
-        // optically thin step: expm1(-t) = -t p(t), p = 1 - t/2 (1 - t/3 (1 - t/4)) to 2^-53: a = 1 - t p, c = j dl p
-        const double p = 1.0 - 0.5 * delta_tau * (1.0 - kThird * delta_tau * (1.0 - 0.25 * delta_tau));
-        const bool absorbing = alpha_val > 0.0;
-        double a = absorbing ? 1.0 - delta_tau * p : 1.0, c = j_val * delta_lambda_cgs * (absorbing ? p : 1.0);
-        if (__builtin_expect(have && absorbing && !(delta_tau < kThin), 0)) {
-          const double ss = j_val * fastmath::rcp(alpha_val);
-          if (delta_tau <= kDeltaTauMax) {
-            const double e1 = fastmath::expm1(-delta_tau);
-            a = 1.0 + e1;
-            c = -ss * e1;
-          } else {
-            a = 0.0;
-            c = ss;
-            intensity = 0.0;   // the thick step's intensity replaces what lies behind it, a NaN included (unpolarized.cpp:103-104)
+      // (the ray's walk twice, behind a wave-uniform branch: the one without sigma cuts is the code it was - a render that does not use
+      // the axis does not pay for it - the other holds the lane's threshold and one compare more per sample)
+      auto walk = [&](auto with_cuts) {
+        constexpr bool kCuts = decltype(with_cuts)::value;
+        const int variant = channel / P.n_nu, pair = kCuts ? variant / P.n_cuts : variant, m = pair / n_units, u = pair - m * n_units;
+        const double sigma_max = kCuts ? P.sigma_max[variant - pair * P.n_cuts] : 0.0;
+        // Unit u's factors where no sample register holds them: x at unit frequency enters only as x f, so unit_x is a factor on the
+        // frequency of the x terms (f_1_2, f_1_3, f_1_6), and s_j only as s_j f^-2, so unit_j is one on f_inv2 (without units: 1.0)
+        const double ux = P.n_units > 0 ? P.unit_x[u] : 1.0, uj = P.n_units > 0 ? P.unit_j[u] : 1.0;
+        const double f_x = f * ux;
+        const double f_1_2 = bl_sqrt_g(f_x), f_1_3 = fastmath::cbrt(f_x);
+        const double f_1_6 = bl_sqrt_g(f_1_3), f_inv = fastmath::rcp(f);
+        const double f_inv2 = f_inv * f_inv * uj;
+        // (one exponential per sample and frequency is most of this loop: its constants stay in scalar registers across it)
+        double exp_c[15];
+  #pragma unroll
+        for (int i = 0; i < 15; i++) exp_c[i] = fastmath::resident_constant(fastmath::kExpConstants[i]);
+        const double2 *in = reinterpret_cast<const double2 *>(P.freq_inputs + (size_t)P.ray_offset[slot]);
+        const double kThird = fastmath::resident_constant(1.0 / 3.0), kInvPlanck = fastmath::resident_constant(kC * kC / (2.0 * kH));
+        const double kRoot = fastmath::resident_constant(kPow2_11_12), kThin = fastmath::resident_constant(0x1p-10);
+        const double mk1 = models ? P.model_k1[m] : 0.0, mk2 = models ? P.model_k2[m] : 0.0, mk3 = P.model_k3;
+        for (int n = num - 1; n >= 0; n--) {   // reference sample order is reversed integration order (geodesics.cpp:832-840)
+          const double2 q0 = in[4 * (size_t)n], q1 = in[4 * (size_t)n + 1], q2 = in[4 * (size_t)n + 2], q3 = in[4 * (size_t)n + 3];
+          // bl_shade_fast_kernel's frequency loop (simulation_coefficients.cpp:464-523, unpolarized.cpp:74-110) as one straight line for
+          // the sample that has coefficients, a thin step and h nu << k T_e - nearly every one: no expm1, no division, no branch; the
+          // rest is selected or, where it needs an exponential of its own, redone behind a branch
+          bool have = q0.x == 1.0;
+          double s_1_3 = q1.x, s_1_6 = q1.y, s_1_2 = q0.y, s_planck = q2.x, s_j = q2.y, s_length = q3.x;
+          if (models) {   // this model's 1 / (k T_e) (the fused kernel's kte_inv), then the sample's roots at unit frequency
+            const double bi2 = q2.y, dd = 1.0 + bi2;
+            const double kte_inv = (mk1 + mk2 * bi2 + mk3 * dd) * fastmath::rcp(q3.x * dd);
+            s_1_3 = fastmath::cbrt(q0.y * (kte_inv * kte_inv));
+            s_1_6 = bl_sqrt_g(s_1_3);
+            s_1_2 = s_1_6 * s_1_3;
+            s_planck = q1.x * kte_inv;
+            s_j = q1.y;
+            s_length = q2.x;
+            if (kCuts) have = have && !(q3.y > sigma_max);   // (the row's sigma)
           }
+          const double xx_1_3 = s_1_3 * f_1_3;
+          const double var_c = s_1_2 * f_1_2 + kRoot * (s_1_6 * f_1_6);
+          const double j_val = s_j * f_inv2 * fastmath::exp(-xx_1_3, exp_c) * var_c * var_c;
+          const double xp = s_planck * f;
+          double planck = xp * (1.0 + 0.5 * xp * (1.0 + kThird * xp * (1.0 + 0.25 * xp)));
+          if (__builtin_expect(have && !(xp < kThin), 0)) planck = fastmath::expm1(xp);
+          double alpha_val = j_val * (planck * kInvPlanck);
+          if (alpha_val * alpha_val <= 0x1p-1024) alpha_val = 0.0;
+          const double delta_lambda_cgs = s_length * f_inv;
+          const double delta_tau = alpha_val * delta_lambda_cgs;
+          // optically thin step: expm1(-t) = -t p(t), p = 1 - t/2 (1 - t/3 (1 - t/4)) to 2^-53: a = 1 - t p, c = j dl p
+          const double p = 1.0 - 0.5 * delta_tau * (1.0 - kThird * delta_tau * (1.0 - 0.25 * delta_tau));
+          const bool absorbing = alpha_val > 0.0;
+          double a = absorbing ? 1.0 - delta_tau * p : 1.0, c = j_val * delta_lambda_cgs * (absorbing ? p : 1.0);
+          if (__builtin_expect(have && absorbing && !(delta_tau < kThin), 0)) {
+            const double ss = j_val * fastmath::rcp(alpha_val);
+            if (delta_tau <= kDeltaTauMax) {
+              const double e1 = fastmath::expm1(-delta_tau);
+              a = 1.0 + e1;
+              c = -ss * e1;
+            } else {
+              a = 0.0;
+              c = ss;
+              intensity = 0.0;   // the thick step's intensity replaces what lies behind it, a NaN included (unpolarized.cpp:103-104)
+            }
+          }
+          a = have ? a : 1.0;
+          c = have ? c : (q0.x == 2.0 ? nan : 0.0);   // (2: NaN primitives off the grid, simulation_sampling.cpp:377-384; 0: nothing to add)
+          intensity = __builtin_fma(a, intensity, c);
         }
-        a = have ? a : 1.0;
-        c = have ? c : (q0.x == 2.0 ? nan : 0.0);   // (2: NaN primitives off the grid, simulation_sampling.cpp:377-384; 0: nothing to add)
-        intensity = __builtin_fma(a, intensity, c);
-      }
+      };
+      if (P.n_cuts > 0) walk(std::true_type{});
+      else walk(std::false_type{});
     }
     P.image[(size_t)channel * P.n_rays_total + out_index] = intensity * (f * f * f);   // unpolarized.cpp:206-207
   }
@@ -552,7 +567,7 @@ extern "C" hipError_t bl_launch_transfer(const BlTransferArgs *args, const Kerne
       break;
     case Transfer::kFreq:   // ... and model and unit
       if (args->freq_inputs == nullptr) return hipErrorInvalidValue;
-      kernel = bl_transfer_freq_kernel, lanes *= args->n_models > 0 ? args->n_models * (args->n_units > 0 ? args->n_units : 1) : 1;
+      kernel = bl_transfer_freq_kernel, lanes *= args->n_models > 0 ? args->n_models * (args->n_units > 0 ? args->n_units : 1) * (args->n_cuts > 0 ? args->n_cuts : 1) : 1;
       break;
     case Transfer::kComposed:
       if (args->composed == nullptr || !plan.affine) return hipErrorInvalidValue;

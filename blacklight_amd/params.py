@@ -23,6 +23,7 @@ class Params:
         self._buf = C.create_string_buffer(L.bl_params_sizeof())
         L.bl_params_clear(self._buf)
         self._sweep = _capi.Sweep()   # the sweep_* keys: lists beside the block (bl_sweep), never in it
+        self._sweep_cuts = _capi.SweepCuts()   # ... sweep_cut_sigma_max (bl_sweep_cuts)
         self.num_runs = 1
 
     @property
@@ -35,7 +36,8 @@ class Params:
         self = cls()
         err = C.create_string_buffer(1024)
         runs = C.c_int(1)
-        rc = _capi.lib().bl_params_read_file_sweep(self._buf, C.byref(self._sweep), str(path).encode(), C.byref(runs), err, len(err))
+        rc = _capi.lib().bl_params_read_file_sweeps(self._buf, C.byref(self._sweep), C.byref(self._sweep_cuts), str(path).encode(), C.byref(runs), err,
+                                                    len(err))
         if rc != 0:
             raise _capi.BlacklightError(rc, err.value.decode())
         self.num_runs = runs.value
@@ -57,7 +59,7 @@ class Params:
 
     def set_line(self, line):
         err = C.create_string_buffer(1024)
-        rc = _capi.lib().bl_params_set_line_sweep(self._buf, C.byref(self._sweep), line.encode(), err, len(err))
+        rc = _capi.lib().bl_params_set_line_sweeps(self._buf, C.byref(self._sweep), C.byref(self._sweep_cuts), line.encode(), err, len(err))
         if rc != 0:
             raise _capi.BlacklightError(rc, err.value.decode())
 
@@ -73,10 +75,11 @@ class Params:
         other = Params()
         C.memmove(other._buf, self._buf, len(self._buf))
         C.memmove(C.byref(other._sweep), C.byref(self._sweep), C.sizeof(_capi.Sweep))
+        C.memmove(C.byref(other._sweep_cuts), C.byref(self._sweep_cuts), C.sizeof(_capi.SweepCuts))
         other.num_runs = self.num_runs
         return other
 
-    # ------------------------------------------------------------------ sweeps (sweep_rat_low, sweep_rat_high, sweep_rho_cgs)
+    # ------------------------------------------------------------------ sweeps (sweep_rat_low, sweep_rat_high, sweep_rho_cgs, sweep_cut_sigma_max)
     @property
     def sweep(self):
         """The bl_sweep filled by the sweep_* keys (what Context applies: bl_apply_sweep)."""
@@ -95,8 +98,17 @@ class Params:
         return [float(x) for x in self._sweep.rho_cgs[:self._sweep.n_rho_cgs]]
 
     @property
+    def sweep_cuts(self):
+        """The bl_sweep_cuts filled by sweep_cut_sigma_max (what Context applies beside the sweep: bl_apply_sweeps)."""
+        return self._sweep_cuts
+
+    @property
+    def sweep_cut_sigma_max(self):
+        return [float(x) for x in self._sweep_cuts.sigma_max[:self._sweep_cuts.n_sigma_max]]
+
+    @property
     def has_sweep(self):
-        return self._sweep.n_rat_low > 0 or self._sweep.n_rat_high > 0 or self._sweep.n_rho_cgs > 0
+        return self._sweep.n_rat_low > 0 or self._sweep.n_rat_high > 0 or self._sweep.n_rho_cgs > 0 or self._sweep_cuts.n_sigma_max > 0
 
     def resolved_sweep(self):
         """The lists as the setters receive them (bl_sweep_resolve): (polarized, rat_low, rat_high, rho_cgs). A polarized block's

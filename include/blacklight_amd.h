@@ -175,7 +175,7 @@ BL_API int bl_params_get(const bl_params *p, const char *key, double *value, int
 BL_API int bl_params_get_string(const bl_params *p, const char *key, char *out, size_t out_len);
 
 /* ------------------------------------------------------------------ sweeps written in the .input file
- * Three keys the reference does not have; a file without them parses exactly as before, and they never enter bl_params:
+ * Four keys the reference does not have; a file without them parses exactly as before, and they never enter bl_params:
  *     sweep_rat_low  = 1, 1, 1          (R_low, R_high) pairs: two lists of equal length
  *     sweep_rat_high = 10, 40, 160
  *     sweep_rho_cgs  = 1e-16, 2e-16     density units (simulation_rho_cgs values), each finite and > 0
@@ -201,6 +201,18 @@ BL_API int bl_params_read_file_sweep(bl_params *p, bl_sweep *sweep, const char *
 /* The lists as the setters will receive them. Unpolarized block: *resolved = *sweep. Polarized block (*polarized = 1) with any
  * list given: all three lists of *resolved have the number of triples, filled by the rule above. resolved, polarized may be NULL. */
 BL_API int bl_sweep_resolve(const bl_sweep *sweep, const bl_params *p, bl_sweep *resolved, int *polarized, char *err, size_t err_len);
+/* The fourth key, beside bl_sweep (whose size is part of the ABI):
+ *     sweep_cut_sigma_max = 1, 3, 10, -1     sigma cuts (cut_sigma_max values; negative: the cut off), each finite
+ * The same list forms and error texts with the key's name, and one of its own: "Invalid sigma cut (<text>) in list
+ * (sweep_cut_sigma_max) in input file: must be finite." The cuts are an axis of their own (bl_set_sigma_cuts): the image is
+ * models x units x cuts. The calls above accept and validate the key and drop its value; the two below keep it (sweep, cuts may
+ * be NULL: dropped). */
+typedef struct bl_sweep_cuts {
+  int32_t n_sigma_max, reserved;
+  double sigma_max[BL_MAX_SWEEP];
+} bl_sweep_cuts;
+BL_API int bl_params_set_line_sweeps(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, const char *line, char *err, size_t err_len);
+BL_API int bl_params_read_file_sweeps(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, const char *path, int *num_runs, char *err, size_t err_len);
 
 /* ------------------------------------------------------------------ grid view
  * What RadiationIntegrator::ObtainGridData() takes from SimulationReader
@@ -331,6 +343,8 @@ typedef struct bl_stats {
      samples); ms_shade runs from the first coefficient kernel to the last one, ms_transfer is the last transfer kernel's. */
   /* ... and density units (bl_set_density_units) likewise: one shading pass per (model, unit) and chunk, n_chunks * M * U launches;
      where every variant shares one pass, n_chunks. */
+  /* ... and sigma cuts (bl_set_sigma_cuts): one shading pass per (model, unit, cut) and chunk, n_chunks * M * U * S launches; where
+     every variant shares one pass, n_chunks whatever S is. */
 } bl_stats;
 
 /* Measurement switches: environment variables BLACKLIGHT_AMD_<NAME>, read ONCE by bl_init (never during a render) and echoed in
@@ -439,12 +453,35 @@ BL_API int bl_num_density_units(const bl_ctx *ctx);   /* 0 = unset: the paramete
 #define BL_MAX_POLARIZED_VARIANTS 16
 BL_API int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs);
 BL_API int bl_num_polarized_variants(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own pair and unit; -1: no context */
+/* Sigma cuts (cut_sigma_max, the magnetisation above which a cell is left out: sigma = b.b / rho in code units,
+ * simulation_coefficients.cpp:361-375) rendered by one bl_render - the standard way to take the jet funnel out of an image. n = 0
+ * (what a context starts with): the parameter block's own cut_sigma_max. 1 <= n <= BL_MAX_SIGMA_CUTS: n values with the reference's
+ * meaning - a value >= 0 cuts cells with sigma > value, a negative value switches the cut off - each finite (BL_E_ARG otherwise).
+ * With M = max(1, electron models), U = max(1, density units) and S = max(1, n), bl_image_num_quantities is M * U * S times the
+ * single-render count and image row ((m * U + u) * S + s) * n_q + q is row q of model m at unit u under cut s; sample_num and
+ * sample_flags come out once. Geodesics and located samples do not depend on the cut: changing the cuts between renders keeps
+ * them. n = 1 renders that value instead of the parameter block's and plans as a fresh render with it. Refused
+ * (BL_E_UNSUPPORTED): formula mode, polarized runs (the polarized axis is not built yet), slow light, and with n >= 2
+ * adaptive_max_level > 0 and render_num_images > 0 (a cut cell drops out of a rendering) - as are bl_adaptive_refine and
+ * bl_write_output while n >= 2. A refused call changes nothing. Where the tolerant tier renders models and units in one pass it
+ * renders the cuts there too: the coefficient kernels run with the sigma upper cut off and leave every sample's sigma in its row,
+ * and a transfer lane per (ray, model, unit, cut, frequency) compares it with the lane's threshold (bl_stats.launches_shade =
+ * n_chunks whatever S is) - each variant within the tier's tolerance of its exact image. Everything else runs one shading pass per
+ * variant over the shared samples: each variant's rows are the bits of a render with that value in the parameter block, in the
+ * exact tier and under bl_set_reproducible. */
+#define BL_MAX_SIGMA_CUTS 16
+BL_API int bl_set_sigma_cuts(bl_ctx *ctx, int n, const double *sigma_max);
+BL_API int bl_num_sigma_cuts(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own cut_sigma_max; -1: no context */
 /* The sweep of a .input file onto a context: bl_sweep_resolve against the context's parameters, then bl_set_polarized_variants
  * (polarized) or bl_set_electron_models and / or bl_set_density_units - one rule for the command-line driver, a bound reference
  * main() and Python. An empty sweep makes no call (what the context holds stays). On failure (bl_last_error: the resolver's text or
  * the refusing setter's) the context holds no model or unit the call brought. */
 BL_API int bl_apply_sweep(bl_ctx *ctx, const bl_sweep *sweep);
-/* Images one bl_render produces: max(1, electron models) * max(1, density units) * max(1, polarized variants); -1: no context. */
+/* ... and with the sigma cuts of the file (bl_set_sigma_cuts after the calls above; cuts may be NULL or empty: bl_apply_sweep). On
+ * failure the context holds no model, unit or cut the call brought. */
+BL_API int bl_apply_sweeps(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts);
+/* Images one bl_render produces: max(1, electron models) * max(1, density units) * max(1, sigma cuts) * max(1, polarized variants);
+ * -1: no context. */
 BL_API int bl_num_variants(const bl_ctx *ctx);
 /* Number of false-colour renderings bl_render produces (render_num_images; 0 in formula mode). */
 BL_API int bl_render_num_images(const bl_ctx *ctx);
@@ -619,6 +656,7 @@ BL_API int bl_write_output_variant(bl_ctx *ctx, const char *path_override, const
  * bl_write_output formats one (simulation_multiple) - and, when V >= 2, a tag in front of the extension (the last '.' of the last path
  * component; appended where there is none):
  *     .mMMuUU   electron model MM (two digits, from 00) at density unit UU; both always present, 00 for a list that is not set
+ *     .mMMuUUsSS  ... under sigma cut SS, where sigma cuts are set (bl_set_sigma_cuts): names without cuts are as above
  *     .vVV      polarized triple VV
  * image.npz -> image.m00u00.npz, image.m00u01.npz, ... image.m02u01.npz: names sort in variant order. V = 1: no tag.
  * BL_E_ARG: variant outside 0 .. V - 1, or buf too short; BL_E_MISSING / BL_E_INPUT as bl_write_output. */
