@@ -140,6 +140,7 @@ def lib():
     L.bl_set_density_units.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.bl_num_density_units.argtypes = [C.c_void_p]
     L.bl_set_polarized_variants.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bl_set_polarized_variants_sigma.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bl_num_polarized_variants.argtypes = [C.c_void_p]
     L.bl_set_sigma_cuts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.bl_num_sigma_cuts.argtypes = [C.c_void_p]

@@ -51,6 +51,7 @@ class Context:
             self._sigma_cuts = params.sweep_cut_sigma_max
         if polarized:
             self._polarized_variants = [(h, lo, u) for h, lo, u in zip(high, low, rho)]
+            self._polarized_cuts = None   # (bl_set_polarized_variants: the parameter block's cut for every triple)
         else:
             if low:
                 self._electron_models = [(h, lo) for h, lo in zip(high, low)]
@@ -274,18 +275,28 @@ class Context:
             self.set_electron_models([h for h, _ in models], rat_low=[lo_ for _, lo_ in models])
             self.set_density_units(units)
 
-    def set_polarized_variants(self, rat_high, rho_cgs, rat_low=1.0):
+    def set_polarized_variants(self, rat_high, rho_cgs, rat_low=1.0, sigma_max=None):
         """Render several (R_high, R_low, simulation_rho_cgs) triples of a polarized run in one render (bl_set_polarized_variants):
         a list of triples, not a product - scalars or sequences, broadcast against each other; empty sequences clear them (the
         parameter block's pair and unit again). The image then holds the variants one after another
-        (render()["image_by_variant"]: (n_variants, n_q, n_rays)); geodesics stay resident."""
+        (render()["image_by_variant"]: (n_variants, n_q, n_rays)); geodesics stay resident.
+        sigma_max: a sigma cut for every variant (bl_set_polarized_variants_sigma) - a scalar, or one cut_sigma_max value per
+        variant (a negative value switches the cut off); None: the parameter block's own cut_sigma_max for all of them."""
         high, unit, low = np.broadcast_arrays(np.atleast_1d(np.asarray(rat_high, dtype=np.float64)),
                                               np.atleast_1d(np.asarray(rho_cgs, dtype=np.float64)),
                                               np.atleast_1d(np.asarray(rat_low, dtype=np.float64)))
         high, unit, low = (np.ascontiguousarray(a.ravel()) for a in (high, unit, low))
-        self._check(self._lib.bl_set_polarized_variants(self._ctx, int(high.size), low.ctypes.data_as(C.c_void_p),
-                                                        high.ctypes.data_as(C.c_void_p), unit.ctypes.data_as(C.c_void_p)))
+        cuts = None
+        if sigma_max is not None:
+            cuts = np.atleast_1d(np.asarray(sigma_max, dtype=np.float64)).ravel()
+            if cuts.size not in (1, high.size):
+                raise ValueError(f"set_polarized_variants: sigma_max needs a scalar or one value per variant (got {cuts.size} for {high.size} variants)")
+            cuts = np.ascontiguousarray(np.broadcast_to(cuts, high.shape))
+        self._check(self._lib.bl_set_polarized_variants_sigma(self._ctx, int(high.size), low.ctypes.data_as(C.c_void_p),
+                                                              high.ctypes.data_as(C.c_void_p), unit.ctypes.data_as(C.c_void_p),
+                                                              cuts.ctypes.data_as(C.c_void_p) if cuts is not None else None))
         self._polarized_variants = [(float(h), float(lo), float(u)) for h, lo, u in zip(high, low, unit)]
+        self._polarized_cuts = [float(c) for c in cuts] if cuts is not None and high.size > 0 else None
 
     @property
     def polarized_variants(self):
@@ -296,6 +307,13 @@ class Context:
         return held
 
     @property
+    def polarized_cuts(self):
+        """The variants' sigma cuts set_polarized_variants(sigma_max=...) set, one per variant; None when every variant is rendered
+        under the parameter block's own cut_sigma_max."""
+        held = getattr(self, "_polarized_cuts", None)
+        return list(held) if held is not None else None
+
+    @property
     def num_polarized_variants(self):
         return self._lib.bl_num_polarized_variants(self._ctx)
 
@@ -304,7 +322,8 @@ class Context:
         (flux.stokes_flux_jy) at image frequency `frequency` is target_jy to within rtol. All pairs advance together: every render
         carries each unfinished pair's current trial units as variants (up to 16 per render; more trials than that take another
         render of the same step) - the bracket's two ends first, then secant steps in log rho and log flux, falling back to
-        bisection where a step leaves the bracket or shrinks it by less than half. The context's variants are restored on exit.
+        bisection where a step leaves the bracket or shrinks it by less than half. The trials are rendered under the parameter
+        block's own cut_sigma_max; the context's variants, and their sigma cuts if they had any, are restored on exit.
         Returns ([(rho_cgs, flux_jy, m_net, v_net) per pair], renders)."""
         from . import flux as _flux
         pairs = [(float(h), float(l)) for h, l in pairs]
@@ -314,7 +333,7 @@ class Context:
             raise ValueError(f"fit_density_units_polarized needs 0 < lo < hi, finite (got {lo}, {hi})")
         if not (target_jy > 0.0 and rtol > 0.0):
             raise ValueError("fit_density_units_polarized needs target_jy > 0 and rtol > 0")
-        saved = self.polarized_variants
+        saved, saved_cuts = self.polarized_variants, self.polarized_cuts
         renders = 0
 
         def evaluate(trials):   # [(pair index, rho)] -> [(I, Q, U, V) in Jy]
@@ -383,7 +402,7 @@ class Context:
                 raise RuntimeError(f"fit_density_units_polarized: no unit within rtol = {rtol} of {target_jy} Jy after {renders} renders")
             return found, renders
         finally:
-            self.set_polarized_variants([h for h, _, _ in saved], [u for _, _, u in saved], rat_low=[l for _, l, _ in saved])
+            self.set_polarized_variants([h for h, _, _ in saved], [u for _, _, u in saved], rat_low=[l for _, l, _ in saved], sigma_max=saved_cuts)
 
     def set_caller_stream(self, stream=None, enabled=True):
         """Every later render starts behind the work queued so far on `stream` (a raw hipStream_t handle, e.g.

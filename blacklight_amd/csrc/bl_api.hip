@@ -414,15 +414,17 @@ const char *SigmaCutsRefusal(const bl_ctx *ctx, int n) {
   return nullptr;
 }
 
-// The variants of a render, in image-row order: the triples, else models x units x sigma cuts, model-major, then unit, then cut, with
-// the parameter block's pair, unit and cut_sigma_max where an axis is not set. The one reader of what the four setters stored.
+// The variants of a render, in image-row order: the triples (each with its own cut_sigma_max where bl_set_polarized_variants_sigma gave
+// one), else models x units x sigma cuts, model-major, then unit, then cut, with the parameter block's pair, unit and cut_sigma_max
+// where an axis is not set. The one reader of what the four setters stored.
 Variants ResolveVariants(const bl_ctx *ctx) {
   const bl_params &p = ctx->params;
   const std::vector<Variant> own = {{p.plasma_rat_low, p.plasma_rat_high, p.simulation_rho_cgs, p.cut_sigma_max}};
   const std::vector<double> own_cut = {p.cut_sigma_max};
   Variants v{ctx->triples, static_cast<int>(ctx->models.size()), static_cast<int>(ctx->units.size()), static_cast<int>(ctx->triples.size()),
              static_cast<int>(ctx->sigma_cuts.size())};
-  for (Variant &triple : v.list) triple.sigma_max = p.cut_sigma_max;
+  if (!ctx->triples_cut)
+    for (Variant &triple : v.list) triple.sigma_max = p.cut_sigma_max;
   if (v.n_pol == 0)
     for (const Variant &model : v.n_models > 0 ? ctx->models : own)
       for (const Variant &unit : v.n_units > 0 ? ctx->units : own)
@@ -1213,7 +1215,7 @@ int bl_set_density_units(bl_ctx *ctx, int n, const double *rho_cgs) {
 
 int bl_num_density_units(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->units.size()) : -1; }
 
-int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs) {
+int bl_set_polarized_variants_sigma(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs, const double *sigma_max) {
   if (ctx == nullptr) return BL_E_ARG;
   if (n < 0 || n > BL_MAX_POLARIZED_VARIANTS || (n > 0 && (rat_low == nullptr || rat_high == nullptr || rho_cgs == nullptr)))
     return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants needs 0 <= n <= " + std::to_string(BL_MAX_POLARIZED_VARIANTS) + " and the three arrays."});
@@ -1222,12 +1224,19 @@ int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const d
       return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants: variant " + std::to_string(v) + " has a non-finite R_low or R_high."});
     if (!std::isfinite(rho_cgs[v]) || !(rho_cgs[v] > 0.0))
       return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants: the unit of variant " + std::to_string(v) + " is not a finite value > 0."});
+    if (sigma_max != nullptr && !std::isfinite(sigma_max[v]))
+      return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants_sigma: the sigma cut of variant " + std::to_string(v) + " is not finite."});
   }
   if (const char *why = PolarizedVariantsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
   std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: no variant enters them)
   ctx->triples.resize(n);
-  for (int v = 0; v < n; v++) ctx->triples[v] = {rat_low[v], rat_high[v], rho_cgs[v], 0.0};
+  for (int v = 0; v < n; v++) ctx->triples[v] = {rat_low[v], rat_high[v], rho_cgs[v], sigma_max != nullptr ? sigma_max[v] : 0.0};
+  ctx->triples_cut = n > 0 && sigma_max != nullptr;
   return BL_OK;
+}
+
+int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs) {
+  return bl_set_polarized_variants_sigma(ctx, n, rat_low, rat_high, rho_cgs, nullptr);
 }
 
 int bl_num_polarized_variants(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->triples.size()) : -1; }

@@ -53,6 +53,9 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
       const BlPolVariant &pv = P.pol_variant_table[v];
       const double rho = (double)__int_as_float(__double2loint(ci.n_e_cgs)), pgas = (double)__int_as_float(__double2hiint(ci.n_e_cgs));
       const double b_sq = ci.nu_c_cgs;
+      // the variant's sigma cut (simulation_coefficients.cpp:361-375; wave-uniform threshold, +inf where there is none to compare):
+      // sample_finish_simulation()'s quotient of its operands, and a cut cell's zeros at every frequency
+      if (pv.sigma_max != __longlong_as_double(0x7ff0000000000000ll) && b_sq / rho > pv.sigma_max) sh.have_coefficients = false;
       const PlasmaCgs cgs = plasma_density_cgs(P.plasma, pv.d_unit, pv.e_unit, rho, pgas);
       sh.n_e_cgs = cgs.n_e_cgs;
       sh.nu_c_cgs = plasma_cyclotron_frequency(plasma_field_cgs(b_sq, pv.b_unit));

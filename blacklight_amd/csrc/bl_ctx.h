@@ -168,6 +168,7 @@ struct bl_ctx {
   // what the four setters stored, empty: the parameter block's - bl_set_electron_models() pairs (rho unused), bl_set_density_units()
   // units (the pair unused), bl_set_polarized_variants() triples, bl_set_sigma_cuts() thresholds; read through ResolveVariants only
   std::vector<Variant> models, units, triples;
+  bool triples_cut = false;          // the triples carry a cut_sigma_max each (bl_set_polarized_variants_sigma); else the parameter block's
   std::vector<double> sigma_cuts;
   BlAuxImages aux_images{};          // which image rows exist; .any = an auxiliary image or a rendering is requested
   int render_num_images = 0;         // false-colour renderings (0 in formula mode)

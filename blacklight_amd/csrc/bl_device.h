@@ -412,12 +412,14 @@ struct alignas(16) BlCoefInputs {
 // ... and with several polarized variants in one pass (bl_set_polarized_variants, BlShadeArgs::pol_variants > 0) the row of a sample
 // with coefficients holds what no variant enters: n_e_cgs = the cell's rho and p_gas (two floats), nu_c_cgs = b_mu b^mu in code units,
 // theta_e = kb_tt_e_cgs = 0; bl_polarized_coefficients_kernel forms n_e, nu_c, Theta_e and k T_e of every variant from them and the
-// variant's folded constants below (rows of samples without coefficients are as ever: bl_polarized_frame_kernel reads them).
+// variant's folded constants below (rows of samples without coefficients are as ever: bl_polarized_frame_kernel reads them) - and
+// with a sigma cut per variant (bl_set_polarized_variants_sigma) decides each variant's cut from the same two values.
 #define BL_POL_MAX_VARIANTS 16
 struct alignas(16) BlPolVariant {
   double d_unit, e_unit, b_unit;   // FoldUnits of the variant's simulation_rho_cgs
   double rat_high, rat_low;
-  double pad;
+  double sigma_max;                // the variant's cut_sigma_max where the variants' cuts differ: no coefficients for a sample with
+                                   // b.b / rho above it; +inf: no cut here (off, or equal for all and decided in the shared pass)
 };
 
 // Slow light (slow_light_on): the time slices the reader holds (simulation_reader.cpp:211-303), latest

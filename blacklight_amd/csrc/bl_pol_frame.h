@@ -140,6 +140,12 @@ __device__ inline void tetrad_frame(const double ucon[4], const double ucov[4], 
 }
 
 // polarized.cpp:163-265 for one sample: k^mu = g^{mu nu} k_nu and rows 1, 2 of the fluid tetrad (bl_polarized_frame_kernel)
+// MUST STAY BIT-EQUAL to the frame sample_finish_simulation() hands over (bl_sampling.h: its kcon and tetrad_build rows 1, 2) for the
+// same sampled values. With a sigma cut per polarized variant in one pass (bl_set_polarized_variants_sigma) the variants share one
+// BlPolSample: a sample that one variant cuts keeps the coefficient kernel's frame, where a fresh render with that cut takes this
+// function's - and every variant is promised a fresh render's bits. The two are different text (plain `/` and sums over all sixteen
+// metric entries here; bl_recip / bl_div_r and sums over the non-zero entries there); tests/test_gpu_polarized_cuts.py holds them
+// equal (one triple under cuts from 0 to off). An edit to either that changes a rounding breaks that feature.
 static __device__ __forceinline__ void sample_frame(const BlSpacetime &st, int coord, double x1, double x2, double x3, const double kcov[4],
                                           const float uu[3], const float bb[3], BlPolSample *out) {
   double gcov[4][4], gcon[4][4];

@@ -117,12 +117,14 @@ struct RenderJob {
   int n_q_model = 0, variant_passes = 1;
   bool variants_one_pass = false;   // ... or all of them in one pass: one gather, one lane per (ray, model, unit, cut, frequency) in the transfer kernel
   double base_rho = 0.0, base_rat_low = 0.0, base_rat_high = 0.0;   // what BuildShadeArgs folds (PlanJob; one pass: the rows' unit and pair)
-  double base_sigma_max = -1.0;     // ... and its cut_sigma_max (one pass over two cuts or more: off, the transfer kernel compares each lane's)
+  double base_sigma_max = -1.0;     // ... and its cut_sigma_max (one pass over cuts that differ: off - the transfer kernel compares each lane's, the
+                                    // polarized coefficient kernel each variant's)
   // ... or pol_one_pass, the triples': the coefficient kernel and the transport matrices once per chunk,
   // bl_polarized_coefficients_kernel and the polarized transfer kernels with a variant axis
   bool pol_one_pass = false;
   int n_cold = 1;                   // BlShadeCold blocks on the device: one per (unit, sigma cut) where the passes' cut thresholds differ (BindVariant)
   int cold_units = 1, cold_cuts = 1;   // ... n_cold = cold_units x cold_cuts, an axis of one where the passes do not differ along it
+                                       // (polarized variants with cuts that differ: cold_cuts = the variants, each with its own)
   long long n_rays = 0, level_pixels = 0;
   size_t redo_capacity = 0;
   // scratch
@@ -289,7 +291,7 @@ void BindVariant(RenderJob &job, int v) {
   pl.plasma_rat_high = variant.rat_high;
   FoldUnits(job.ctx, variant.rho, pl, job.sa.fast_k);
   const int n_s = std::max(1, job.variants.n_cuts), n_u = std::max(1, job.variants.n_units);   // (v = (m n_u + u) n_s + s)
-  const int u = (v / n_s) % n_u, s = v % n_s;
+  const int u = (v / n_s) % n_u, s = job.variants.n_pol > 0 ? v : v % n_s;   // (polarized variants: a cut each, PlanVariantCuts)
   job.sa.cold = job.ctx->d_shade_cold.ptr + ((job.cold_units > 1 ? u : 0) * job.cold_cuts + (job.cold_cuts > 1 ? s : 0));
   pl.cut_mask = (pl.cut_mask & ~(1 << 11)) | (variant.sigma_max >= 0.0 ? 1 << 11 : 0);   // (bit 11: cut_sigma_max, FoldFastCuts' order)
   pl.any_cell_cut = pl.cut_mask != 0 ? 1 : 0;
@@ -301,6 +303,34 @@ bool GeometricCut(const bl_params &p) {   // an optional geometric cut is set
 }
 bool PerSampleRows(const BlAuxImages &rows) {   // an image row made of every sample's auxiliary record
   return rows.image_time || rows.image_length || rows.image_lambda || rows.image_emission || rows.image_lambda_ave || rows.image_emission_ave || rows.image_tau_int || rows.image_crossings;
+}
+
+// Where the variants' sigma cuts are compared, once the plan knows whether the variants share a pass (PlanJob; PlanScratch again where
+// it takes the polarized one pass back).
+void PlanVariantCuts(RenderJob &job) {
+  const Variants &vs = job.variants;
+  const Variant &first = vs.list[0];
+  bool cuts_differ = false;   // (as bits: -1 and -2 both switch the cut off, and are still not "the same render")
+  for (const Variant &v : vs.list) cuts_differ = cuts_differ || std::memcmp(&v.sigma_max, &first.sigma_max, sizeof(double)) != 0;
+  // One cut: every variant's, in the shared pass or in every pass. Passes: BindVariant each variant's.
+  job.base_sigma_max = first.sigma_max;
+  // One pass over two sigma cuts or more: the coefficient kernels run with the sigma upper cut off and leave every sample's sigma in
+  // its row; a transfer lane compares it with its own threshold (BuildTransferArgs), and the tolerant kernels leave a sample whose
+  // sigma lies in the guard band of any of the thresholds to the exact pass (BuildShadeArgs: BlShadeArgs::sigma_band_lo / _hi)
+  if (job.variants_one_pass && vs.n_cuts >= 2) job.base_sigma_max = -1.0;
+  // Polarized variants in one pass whose cuts differ: the frame-and-inputs kernel runs with the sigma upper cut off - every other cut
+  // is decided there as ever - and bl_polarized_coefficients_kernel compares b.b / rho of the sample's row with its variant's
+  // threshold (BuildShadeArgs: BlPolVariant::sigma_max). That kernel is the exact tier's in both tiers, and the row's b.b and rho are
+  // the exact tier's bits in both (no polarized frame-and-inputs kernel has tolerant arithmetic): no guard band. Equal cuts stay in
+  // the shared pass.
+  if (job.pol_one_pass && cuts_differ) job.base_sigma_max = -1.0;
+  // (the passes of two units or more compare the cut thresholds of their own unit, those of two sigma cuts or more - or of polarized
+  // variants whose cuts differ - their own cut_sigma_max: one BlShadeCold per (unit, cut))
+  const bool cold_per_pass = job.simulation && job.variant_passes >= 2;
+  job.cold_units = cold_per_pass && vs.n_units >= 2 ? vs.n_units : 1;
+  job.cold_cuts = cold_per_pass && vs.n_cuts >= 2 ? vs.n_cuts : 1;
+  if (cold_per_pass && vs.n_pol >= 2 && cuts_differ) job.cold_cuts = vs.n_pol;
+  job.n_cold = job.cold_units * job.cold_cuts;
 }
 
 // ---- plan: validation of the call, the path it takes
@@ -341,7 +371,6 @@ void PlanJob(RenderJob &job) {
   job.base_rho = first.rho, job.base_rat_low = first.rat_low, job.base_rat_high = first.rat_high;
   if (vs.n_pol == 0 && vs.list.size() >= 2) job.base_rat_low = p.plasma_rat_low, job.base_rat_high = p.plasma_rat_high;
   if (vs.n_units >= 2) job.base_rho = p.simulation_rho_cgs;
-  job.base_sigma_max = first.sigma_max;   // (one cut: every variant's; passes: BindVariant each variant's; one pass over several: off, below)
   job.n_nu = p.image_num_frequencies;
   job.n_q_model = ctx->image_num_quantities;
   job.variant_passes = static_cast<int>(vs.list.size());
@@ -415,17 +444,7 @@ void PlanJob(RenderJob &job) {
   if (job.variants_one_pass) {
     job.freq_split = true;
     job.variant_passes = 1;
-    // Two sigma cuts or more: the coefficient kernels run with the sigma upper cut off and leave every sample's sigma in its row; a
-    // transfer lane compares it with its own threshold (BuildTransferArgs), and the tolerant kernels leave a sample whose sigma lies
-    // in the guard band of any of the thresholds to the exact pass (BuildShadeArgs: BlShadeArgs::sigma_band_lo / _hi)
-    if (vs.n_cuts >= 2) job.base_sigma_max = -1.0;
   }
-  // (the passes of two units or more compare the cut thresholds of their own unit, those of two sigma cuts or more their own
-  // cut_sigma_max: one BlShadeCold per (unit, cut))
-  const bool cold_per_pass = job.simulation && job.variant_passes >= 2;
-  job.cold_units = cold_per_pass && vs.n_units >= 2 ? vs.n_units : 1;
-  job.cold_cuts = cold_per_pass && vs.n_cuts >= 2 ? vs.n_cuts : 1;
-  job.n_cold = job.cold_units * job.cold_cuts;
   // Plain images of a spherical Kerr-Schild simulation with fallback values beyond the grid: nothing is recorded of the steps that
   // lie in the empty shell between the grid's outer edge and the camera's sphere (both tiers; the samples count as ever)
   job.skip_shell = job.simulation && !job.aux && !ctx->polarized && !job.slow && job.no_checkpoint
@@ -519,6 +538,7 @@ void PlanJob(RenderJob &job) {
       job.pol_coefficients_inside = false;   // (the samples go through the 64-byte row, which is where the variants part)
     }
   }
+  PlanVariantCuts(job);
   // Host outputs of a quarter of a GiB and more in eight rows or more (configuration 5: 64 frequencies): the rays are traced in pixel
   // order - not the 8 x 8 tiles, centre first, that make chunks drain faster - so that what a chunk finishes is a range of columns,
   // downloaded while the next chunk renders (the image rows of a 4096^2 x 64 frame are 8.6 GB: 0.7 s of PCIe that used to follow the
@@ -959,6 +979,7 @@ void PlanScratch(RenderJob &job) {
       if (wanted > have && sl.Bytes() - have + wanted > ctx->scratch_limit) {
         job.pol_one_pass = false;
         job.variant_passes = job.variants.n_pol;
+        PlanVariantCuts(job);   // (each pass its own variant's cut)
       }
     }
     job.record_gate = static_cast<long long>(job.record_capacity);
@@ -1653,7 +1674,10 @@ void BuildShadeArgs(RenderJob &job) {
       variant_pl.plasma_rat_low = variant.rat_low;
       variant_pl.plasma_rat_high = variant.rat_high;
       FoldUnits(ctx, variant.rho, variant_pl, variant_k);
-      table.push_back(BlPolVariant{variant_pl.d_unit, variant_pl.e_unit, variant_pl.b_unit, variant_pl.plasma_rat_high, variant_pl.plasma_rat_low, 0.0});
+      // (the variant's threshold where the shared pass ran with the sigma upper cut off - PlanVariantCuts - else +inf: nothing to compare)
+      const bool cut_here = job.base_sigma_max < 0.0 && variant.sigma_max >= 0.0;
+      table.push_back(BlPolVariant{variant_pl.d_unit, variant_pl.e_unit, variant_pl.b_unit, variant_pl.plasma_rat_high, variant_pl.plasma_rat_low,
+                                   cut_here ? variant.sigma_max : std::numeric_limits<double>::infinity()});
     }
     // (uploaded when it differs from what the device holds, as the cold block above: a fit's renders wait here only when their units change)
     std::vector<unsigned char> bytes(table.size() * sizeof(BlPolVariant));

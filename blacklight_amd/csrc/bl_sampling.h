@@ -1277,6 +1277,9 @@ __device__ __forceinline__ void sample_finish_simulation(const BlShadeArgs &P, c
   out->cos_theta_b = bl_sqrt_g(cos2_theta_b) * (k_b_tet >= 0.0 ? 1.0 : -1.0);   // :455
   if (kExtended && pol_out != nullptr) {
     // polarized.cpp:163-265 rebuilds k^mu and this tetrad from the same sampled values: hand them over
+    // MUST STAY BIT-EQUAL to bl_pol::sample_frame() (bl_pol_frame.h) on the same sampled values: with a sigma cut per polarized
+    // variant in one pass, a sample that one variant cuts keeps this frame, where a fresh render with that cut takes that function's
+    // (see the comment there; tests/test_gpu_polarized_cuts.py holds the two equal)
     for (int mu = 0; mu < 4; mu++) {
       pol_out->kcon[mu] = kcon[mu];
       pol_out->e1[mu] = tetrad[1][mu];

@@ -449,9 +449,24 @@ BL_API int bl_num_density_units(const bl_ctx *ctx);   /* 0 = unset: the paramete
  * auxiliary row), Theta_e from R_high / R_low, a cut on rho, n_e, p_gas or B only if all units are equal, a Theta_e cut only if all triples are
  * equal: the gather, fluid frame and tetrad once per chunk (bl_stats.launches_shade = n_chunks), the transport matrices once, a
  * coefficient-kernel wave per (64 samples, variant) and a transfer lane per (ray, variant). Everything else: one shading pass per
- * variant over the shared samples (launches_shade = n_chunks * n). */
+ * variant over the shared samples (launches_shade = n_chunks * n).
+ * bl_set_polarized_variants is bl_set_polarized_variants_sigma (below) with sigma_max = NULL: every variant is rendered under the
+ * parameter block's own cut_sigma_max, and the cuts an earlier call of that function set are gone. */
 #define BL_MAX_POLARIZED_VARIANTS 16
 BL_API int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs);
+/* ... with a sigma cut each: (R_low, R_high, simulation_rho_cgs, cut_sigma_max) quadruples, a list like the triples and not a
+ * product. sigma_max[v] has the reference's meaning - a value >= 0 cuts cells with sigma = b.b / rho > value, a negative value
+ * switches the cut off - and must be finite (BL_E_ARG, with the variant's index in the text; the call changes nothing).
+ * sigma_max = NULL is exactly bl_set_polarized_variants. Everything else - the range of n, the other arrays, the refusals, image
+ * rows, bl_num_variants, bl_num_polarized_variants, the .vNN tags of bl_write_output_variant - is as for the triples: a cut adds no
+ * rows, it changes what variant v is. Every variant's rows are still the bits of a render with that quadruple in the parameter
+ * block. Where the triples render in one pass the quadruples do too, whatever their cuts: with cuts that differ the shared
+ * frame-and-inputs kernel runs with the sigma upper cut off and bl_polarized_coefficients_kernel, which has the cell's rho and
+ * b.b in the sample's row, leaves a (sample, variant) with sigma above the variant's threshold without coefficients. Where the
+ * render takes one shading pass per variant, each pass compares its own variant's cut. The cuts are no part of what the resident
+ * geodesics depend on. */
+BL_API int bl_set_polarized_variants_sigma(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs,
+                                           const double *sigma_max);
 BL_API int bl_num_polarized_variants(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own pair and unit; -1: no context */
 /* Sigma cuts (cut_sigma_max, the magnetisation above which a cell is left out: sigma = b.b / rho in code units,
  * simulation_coefficients.cpp:361-375) rendered by one bl_render - the standard way to take the jet funnel out of an image. n = 0
@@ -468,7 +483,8 @@ BL_API int bl_num_polarized_variants(const bl_ctx *ctx);   /* 0 = unset: the par
  * and a transfer lane per (ray, model, unit, cut, frequency) compares it with the lane's threshold (bl_stats.launches_shade =
  * n_chunks whatever S is) - each variant within the tier's tolerance of its exact image. Everything else runs one shading pass per
  * variant over the shared samples: each variant's rows are the bits of a render with that value in the parameter block, in the
- * exact tier and under bl_set_reproducible. */
+ * exact tier and under bl_set_reproducible. A polarized run takes its cuts with its variants, one per variant:
+ * bl_set_polarized_variants_sigma. */
 #define BL_MAX_SIGMA_CUTS 16
 BL_API int bl_set_sigma_cuts(bl_ctx *ctx, int n, const double *sigma_max);
 BL_API int bl_num_sigma_cuts(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own cut_sigma_max; -1: no context */
@@ -480,8 +496,8 @@ BL_API int bl_apply_sweep(bl_ctx *ctx, const bl_sweep *sweep);
 /* ... and with the sigma cuts of the file (bl_set_sigma_cuts after the calls above; cuts may be NULL or empty: bl_apply_sweep). On
  * failure the context holds no model, unit or cut the call brought. */
 BL_API int bl_apply_sweeps(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts);
-/* Images one bl_render produces: max(1, electron models) * max(1, density units) * max(1, sigma cuts) * max(1, polarized variants);
- * -1: no context. */
+/* Images one bl_render produces: max(1, electron models) * max(1, density units) * max(1, sigma cuts) * max(1, polarized variants)
+ * - a polarized variant's own sigma cut (bl_set_polarized_variants_sigma) is part of the variant and adds no image; -1: no context. */
 BL_API int bl_num_variants(const bl_ctx *ctx);
 /* Number of false-colour renderings bl_render produces (render_num_images; 0 in formula mode). */
 BL_API int bl_render_num_images(const bl_ctx *ctx);
