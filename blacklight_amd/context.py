@@ -139,6 +139,32 @@ class Context:
         self._check(self._lib.bl_debug_math(self._ctx, int(op), x.size, x.ctypes.data, yp, out.ctypes.data))
         return out
 
+    def debug_locate_angles(self, points, spin, x2f, x2v, x3f, x3v):
+        """The tolerant locate step's theta and phi of `points` ([m, 3] Cartesian Kerr-Schild) against an angular lattice (faces and centres
+        of theta and of phi), relative to the centre of the guessed cell ("local") and by acos / atan2 ("global"): bl_debug_math ops 40
+        (spin 0) and 41. Returns {"local": ..., "global": ...}, each a dict of arrays over the points: cell_th, cell_ph (the anchor cells),
+        frac_th, frac_ph, margin (the smallest signed distance to anything compared), undecided, guess_th, guess_ph."""
+        import numpy as np
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        m = points.shape[0]
+        lattice = np.concatenate([np.asarray(v, dtype=np.float64).ravel() for v in (x2f, x2v, x3f, x3v)])
+        n_th, n_ph = np.asarray(x2v).size, np.asarray(x3v).size
+        if lattice.size != 2 * (n_th + n_ph) + 2:
+            raise ValueError("faces must hold one value more than centres")
+        n = max(16 * m, lattice.size)
+        x = np.zeros(n)
+        x[:4] = (m, float(spin), n_th, n_ph)
+        x[4:4 + 3 * m] = points.T.ravel()
+        y = np.zeros(n)
+        y[:lattice.size] = lattice
+        rows = self.debug_math(40 if float(spin) == 0.0 else 41, x, y)[:16 * m].reshape(16, m)
+        names = ("cell_th", "cell_ph", "frac_th", "frac_ph", "margin", "undecided", "guess_th", "guess_ph")
+        out = {}
+        for half, key in enumerate(("local", "global")):
+            out[key] = {name: (rows[8 * half + q] if name.startswith(("frac", "margin")) else rows[8 * half + q].astype(np.int64))
+                        for q, name in enumerate(names)}
+        return out
+
     def set_undefined_policy(self, policy):
         """"refuse" (default), "edge" (samples where the reference reads past its arrays), "kappa" (unpolarized kappa-distribution
         electrons, whose absorptivity the reference computes from an uninitialised constant), or "edge,kappa" (bl_set_undefined_policy)."""

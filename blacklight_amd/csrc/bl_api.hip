@@ -446,7 +446,8 @@ int bl_init(const bl_params *p, int device, bl_ctx **out) {
         {"BLACKLIGHT_AMD_RECORD_EVERY_STEP", BL_SWITCH_RECORD_EVERY_STEP},
         {"BLACKLIGHT_AMD_GENERAL_LOCATE", BL_SWITCH_GENERAL_LOCATE}, {"BLACKLIGHT_AMD_LANE_TRANSFER", BL_SWITCH_LANE_TRANSFER},
         {"BLACKLIGHT_AMD_NO_FUSED_LOCATE", BL_SWITCH_NO_FUSED_LOCATE}, {"BLACKLIGHT_AMD_SAMPLE_RECORDS", BL_SWITCH_SAMPLE_RECORDS},
-        {"BLACKLIGHT_AMD_QUAD_EVERY_RAY", BL_SWITCH_QUAD_EVERY_RAY}, {"BLACKLIGHT_AMD_FLAT_ORDER", BL_SWITCH_FLAT_ORDER}};
+        {"BLACKLIGHT_AMD_QUAD_EVERY_RAY", BL_SWITCH_QUAD_EVERY_RAY}, {"BLACKLIGHT_AMD_FLAT_ORDER", BL_SWITCH_FLAT_ORDER},
+        {"BLACKLIGHT_AMD_GLOBAL_ANGLES", BL_SWITCH_GLOBAL_ANGLES}};
     for (const auto &sw : kSwitches)
       if (std::getenv(sw.name) != nullptr) ctx->switches |= sw.bit;
     ctx->debug_counters = std::getenv("BLACKLIGHT_AMD_DEBUG_COUNTERS") != nullptr;
@@ -691,6 +692,20 @@ void UploadMergedGrid(bl_ctx *ctx, const bl_grid_desc *g) {
       off_v[a] = coords.size();
       coords.insert(coords.end(), xv[a], xv[a] + n[a]);
     }
+    // cosine and sine of every theta and phi centre, and how far a cell reaches from its centre: what the tolerant coefficient kernel's
+    // angles relative to the cell centre ask for (bl_local_angles.h)
+    size_t off_trig[2];
+    double angle_reach = 0.0;
+    for (int a = 1; a < 3; a++) {
+      off_trig[a - 1] = coords.size();
+      for (int c = 0; c < n[a]; c++) {
+        double sine, cosine;
+        bl_sincos(xv[a][c], &sine, &cosine);
+        coords.push_back(cosine);
+        coords.push_back(sine);
+        angle_reach = std::max(angle_reach, std::max(xv[a][c] - xf[a][c], xf[a][c + 1] - xv[a][c]));
+      }
+    }
     ctx->d_coords.Ensure(coords.size());
     Check(hipMemcpy(ctx->d_coords.ptr, coords.data(), coords.size() * sizeof(double), hipMemcpyHostToDevice), "coordinate upload");
     // bucket tables for the cell search
@@ -740,6 +755,13 @@ void UploadMergedGrid(bl_ctx *ctx, const bl_grid_desc *g) {
       dev.bucket[a] = ctx->d_buckets.ptr + off_b[a];
       dev.n[a] = n[a];
       dev.nb[a] = nb_cells[a];
+    }
+    dev.angle_trig[0] = ctx->d_coords.ptr + off_trig[0];
+    dev.angle_trig[1] = ctx->d_coords.ptr + off_trig[1];
+    dev.angle_reach = angle_reach;
+    for (int a = 1; a < 3; a++) {
+      dev.angle_guess[2 * a - 2] = static_cast<float>(dev.cell_x0[a]);
+      dev.angle_guess[2 * a - 1] = static_cast<float>(dev.cell_inv_w[a]);
     }
     if (ctx->params.simulation_coord == BL_COORD_FMKS) {
       // FMKS grid (simulation_sampling.cpp:66-73): native coordinates above, plus the reader's map and bounds
@@ -1361,6 +1383,13 @@ int bl_set_scratch_limit(bl_ctx *ctx, uint64_t bytes) {
 int bl_debug_math(bl_ctx *ctx, int op, int64_t n, const double *x, const double *y, double *out) {
   if (ctx == nullptr || x == nullptr || out == nullptr || n <= 0) return BL_E_ARG;
   try {
+    if (op == 40 || op == 41) {   // the locate step's angles of m points against a lattice: the arrays must hold the layout the header gives
+      if (y == nullptr || n < 4) throw Failure{BL_E_ARG, "bl_debug_math: ops 40 and 41 take the lattice in y."};
+      const double m = x[0], n_th = x[2], n_ph = x[3];
+      if (!(m >= 1.0 && n_th >= 2.0 && n_ph >= 2.0 && n_th <= 65535.0 && n_ph <= 65535.0) || m != std::floor(m) || n_th != std::floor(n_th) || n_ph != std::floor(n_ph)
+          || 16.0 * m > static_cast<double>(n) || 2.0 * (n_th + n_ph) + 2.0 > static_cast<double>(n))
+        throw Failure{BL_E_ARG, "bl_debug_math: ops 40 and 41 need n >= 16 m and n >= 2 (n_th + n_ph) + 2."};
+    }
     if (ctx->device == BL_DEVICE_NONE) throw Failure{BL_E_DEVICE, "Host-only context: no HIP device selected."};
     Check(hipSetDevice(ctx->device), "hipSetDevice");
     EnsureStreams(ctx);

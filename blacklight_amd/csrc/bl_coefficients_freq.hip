@@ -187,11 +187,97 @@ __global__ void __launch_bounds__(256) bl_polarized_frame_kernel(const BlShadeAr
 
 
 
+// Diagnostics (bl_debug_math op 40 / 41: spin zero / any spin): the locate step's theta and phi of given points against a given angular
+// lattice, both ways - relative to the centre of the guessed cell (bl_local_angles.h: the functions bl_shade_fused2_kernel calls) and by the
+// tier's acos / atan2 with the face and centre comparisons of fused2::axis_lookup.
+// What this runs of the kernel: direction, angle_guess, make_row, offset_from_centre and lookup of bl_local_angles.h, with the centre's sine
+// and cosine from the device's bl_sincos (the pinned library: the host table's bits) and the guess-to-cell step restated. The host-made table,
+// the rows' place in LDS and fused2::read_angle_row are exercised by the frame tests only. The "global" half is a restatement too -
+// fastmath::acos / atan2, which the kernel's acos_k / atan2_k restate, with axis_lookup's margins and anchor rule - not fused2::locate itself.
+//   x = [m, a, n_th, n_ph, xs[m], ys[m], zs[m]],  y = [xf_th[n_th + 1], xv_th[n_th], xf_ph[n_ph + 1], xv_ph[n_ph]],  out = [16][m]:
+//   rows 0 - 7 local: anchor cell in theta, in phi, fraction in theta, in phi, smallest margin, undecided (margin <= 1e-12), guessed cell in
+//   theta, in phi;  rows 8 - 15 the same from the global angles.
+#pragma clang fp contract(fast)
+#include "bl_local_angles.h"
+template <bool kSpinZero>
+__device__ void debug_locate_angles(long long i, long long m, double a, int n_th, int n_ph, const double *x, const double *y, double *out) {
+  const double *xf[2] = {y, y + 2 * n_th + 1}, *xv[2] = {y + n_th + 1, y + 2 * n_th + 1 + n_ph + 1};
+  const int n[2] = {n_th, n_ph};
+  const double px = x[4 + i], py = x[4 + m + i], pz = x[4 + 2 * m + i], band = 1.0e-12;
+  BlSpacetime st{};
+  st.bh_a = a;
+  double r2;
+  const double r = bl_radial_coordinate2<kSpinZero>(st, px, py, pz, &r2);
+  const double r_inv = 1.0 / r;
+  {   // relative to the cell centre
+    const local_angles::Direction u = local_angles::direction<kSpinZero>(a, r, r_inv, px, py, pz);
+    const float guess[2] = {local_angles::angle_guess<false>((float)u.sin_th, (float)u.cos_th), local_angles::angle_guess<true>((float)u.sin_ph, (float)u.cos_ph)};
+    const double sines[2] = {u.sin_th, u.sin_ph}, cosines[2] = {u.cos_th, u.cos_ph};
+    double margin = 1.0;
+    for (int q = 0; q < 2; q++) {
+      const float x0 = (float)xf[q][0], inv_w = (float)((double)n[q] / (xf[q][n[q]] - xf[q][0]));
+      int c = (int)((guess[q] - x0) * inv_w);
+      c = c < 0 ? 0 : (c > n[q] - 1 ? n[q] - 1 : c);
+      double sin_c, cos_c;
+      bl_sincos(xv[q][c], &sin_c, &cos_c);
+      const local_angles::AngleRow at_c = local_angles::make_row(xf[q], xv[q], cos_c, sin_c, c, n[q], q == 0 ? kPi : 2.0 * kPi);
+      double frac, mq;
+      uint32_t shift;
+      local_angles::lookup(at_c, local_angles::offset_from_centre(sines[q], cosines[q], at_c.cos_c, at_c.sin_c), &frac, &shift, &mq);
+      margin = q == 0 ? mq : (margin < mq ? margin : mq);   // (as the kernel takes it: a NaN - phi on the polar axis - stays)
+      out[(0 + q) * m + i] = (double)(c - (int)shift);
+      out[(2 + q) * m + i] = frac;
+      out[(6 + q) * m + i] = (double)c;
+    }
+    out[4 * m + i] = margin;
+    out[5 * m + i] = margin > band ? 0.0 : 1.0;
+  }
+  {   // global angles
+    double cth = pz * r_inv;
+    cth = __builtin_fma(__builtin_fma(-r, cth, pz), r_inv, cth);
+    const double th = fastmath::acos(cth);
+    const double ph_unwrapped = kSpinZero ? fastmath::atan2(py, px) : fastmath::atan2(py, px) - fastmath::atan2(a, r);
+    const double two_pi = 2.0 * kPi;
+    double ph = ph_unwrapped + (ph_unwrapped < 0.0 ? two_pi : 0.0);
+    const double ph_once = ph;
+    ph -= ph >= two_pi ? two_pi : 0.0;
+    const double angle[2] = {th, ph};
+    double margin = __builtin_fabs(ph_unwrapped);
+    const double e1 = __builtin_fabs(ph_once - two_pi);
+    margin = margin < e1 ? margin : e1;
+    for (int q = 0; q < 2; q++) {
+      int c = (int)((angle[q] - xf[q][0]) * ((double)n[q] / (xf[q][n[q]] - xf[q][0])));
+      c = c < 0 ? 0 : (c > n[q] - 1 ? n[q] - 1 : c);
+      const bool ge = angle[q] >= xv[q][c];
+      const int anchor = ge ? (c == n[q] - 1 ? c - 1 : c) : (c == 0 ? 0 : c - 1);
+      const double frac = (angle[q] - xv[q][anchor]) * (1.0 / (xv[q][anchor + 1] - xv[q][anchor]));
+      const double d_lo = angle[q] - xf[q][c], d_hi = xf[q][c + 1] - angle[q], d_c = __builtin_fabs(angle[q] - xv[q][c]);
+      double mq = d_lo < d_hi ? d_lo : d_hi;
+      mq = mq < d_c ? mq : d_c;
+      margin = mq < margin ? mq : margin;
+      margin = mq == mq ? margin : -1.0;
+      out[(8 + q) * m + i] = (double)anchor;
+      out[(10 + q) * m + i] = frac;
+      out[(14 + q) * m + i] = (double)c;
+    }
+    out[12 * m + i] = margin;
+    out[13 * m + i] = margin > band ? 0.0 : 1.0;
+  }
+}
+#pragma clang fp contract(off)
+
 // Diagnostics: apply one device math function element-wise (bl_debug_math). Lets the tests compare the
 // device build of blmath.h and the exact-arithmetic devices of bl_geometry.h with the host, bit for bit.
 __global__ void bl_debug_math_kernel(int op, long long n, const double *x, const double *y, double *out) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  if (op == 40 || op == 41) {   // (the layout above: the caller - bl_debug_math - has checked that x, y and out hold it)
+    const long long m = (long long)x[0];
+    if (i >= m) return;
+    if (op == 40) debug_locate_angles<true>(i, m, 0.0, (int)x[2], (int)x[3], x, y, out);
+    else debug_locate_angles<false>(i, m, x[1], (int)x[2], (int)x[3], x, y, out);
+    return;
+  }
   const double a = x[i], b = y != nullptr ? y[i] : 0.0;
   double r = 0.0, s_unused, c_unused;
   switch (op) {

@@ -97,6 +97,10 @@ enum BlCounter {
 // ... and of the exact second pass behind the fused kernel (256-lane workgroups, two to a compute unit, 8 KiB of anchor rows beside)
 #define BL_REDO_TABLES_LDS (48 * 1024)
 
+// Theta and phi relative to the centre of the guessed cell (bl_local_angles.h): how far a point of an angular cell may lie from the
+// cell's centre for the arcsine's series to hold its bound - the plan's condition on BlGridDevice::angle_reach
+constexpr double kLocalAngleReach = 1.0 / 16.0;
+
 struct BlGridDevice {
   const float *cells;        // [n_k][n_j][n_i][8]
   const float *kappa;        // [n_k][n_j][n_i] electron entropy (plasma_model = code_kappa), else null
@@ -115,6 +119,11 @@ struct BlGridDevice {
   int log_uniform, full_sphere;
   float log_l0, log_inv_w;
   double r_face_in, r_face_out;
+  // ... and for theta and phi relative to the centre of the guessed cell (bl_local_angles.h): (cos, sin) of every theta and phi centre,
+  // and the largest distance of a point of an angular cell from that cell's centre (the plan: at most local_angles::kAngleReach)
+  const double *angle_trig[2];   // [n[1]][2], [n[2]][2]
+  double angle_reach;
+  float angle_guess[4];          // cell_x0[1], cell_inv_w[1], cell_x0[2], cell_inv_w[2] in single precision: the cell guess of those angles
   int n[3];                  // n_i, n_j, n_k of the (merged) global grid
   int nb[3];                 // cells per block along each axis (= n for a single block)
   int stride_row, stride_plane;   // cells between j- and k-neighbours in `cells` / `kappa`
@@ -463,6 +472,8 @@ struct BlShadeArgs {
   double2 *composed;          // [segment row], or null: one transfer record per sample
   int general_locate;         // measurement switch (bl_stats.switches): the general locate kernel where the plain one applies; refined tables in HBM
   int undefined_edge;         // bl_set_undefined_policy(BL_UNDEFINED_EDGE): samples where the reference reads past its arrays use the edge
+  int local_angles;           // bl_shade_fused2_kernel over one block: theta and phi relative to the centre of the guessed cell (bl_local_angles.h;
+                              // the plan: angular cells within the series' reach, not BL_SWITCH_GLOBAL_ANGLES); 0: acos / atan2
   const unsigned long long *counters_in;
   unsigned long long *counters;
   // bl_shade_fused2_kernel: the record lists of the geodesic kernel's trace order per XCD (BlTraceArgs::xcd_state), walked in

@@ -94,6 +94,7 @@ struct RenderJob {
   bool kept = false;          // integrating in the kept layout: every chunk's records side by side in a store (bl_ctx::ResidentGeodesics)
   bool kept_spilled = false;  // ... the store ran out before the last ray: the remaining chunks overwrite it from its start, nothing is kept
   bool xcd_order = false;     // trace order per XCD (BlTraceArgs::xcd_state, XcdOrderApplies)
+  bool local_angles = false;  // fused2 over one block: theta and phi relative to the centre of the guessed cell (BlShadeArgs::local_angles)
   bool super_tiles = false;   // ... the tile order in super-tiles (BuildTraceArgs)
   bool raster = false;        // large host outputs (many image rows): rays in pixel order, so that a chunk is a range of columns of
                               // every row and goes to the caller's buffer while the next chunk renders (DownloadChunk)
@@ -470,6 +471,9 @@ void PlanJob(RenderJob &job) {
   // (its own: the tolerant tier's scope - only this one reads job.fast, which leaves it plain images and so no sample times - without
   // the optical-depth row and power-law electrons; it alone takes inter-block interpolation, which its grid predicate decides)
   job.fused2 = locate_inside_possible && job.fast && !job.tau_row && fused2_grid && p.plasma_power_frac == 0.0;
+  // ... with theta and phi relative to the centre of the guessed cell where the series behind them reaches every point of every angular
+  // cell (bl_local_angles.h: 1 / 16 rad from the centre; one block - the mesh with refinement keeps acos / atan2)
+  job.local_angles = job.fused2 && ctx->grid_dev.n_blocks == 0 && ctx->grid_dev.angle_trig[0] != nullptr && ctx->grid_dev.angle_reach <= kLocalAngleReach && !(ctx->switches & BL_SWITCH_GLOBAL_ANGLES);
   // The exact tier's plain image at one frequency over such a grid: the locate step inside bl_shade_exact2_kernel (bit-identical
   // to bl_locate_plain_kernel + bl_shade_exact_kernel, whose conditions these are: job.fast's electrons, restated because it is off)
   job.exact_fused = locate_inside_possible && !job.fast && !job.aux && !ctx->polarized && !job.block_interp && job.n_nu == 1
@@ -1632,6 +1636,7 @@ void BuildShadeArgs(RenderJob &job) {
   }
   sa.samples_renormalised = job.geo_load ? 1 : 0;
   sa.general_locate = (ctx->switches & BL_SWITCH_GENERAL_LOCATE) ? 1 : 0;
+  sa.local_angles = job.local_angles ? 1 : 0;
   // One block per (unit, sigma cut) where the passes of two units or more compare their own cut thresholds and those of two cuts or
   // more their own cut_sigma_max (job.n_cold; BindVariant points at its variant's): the render's block with the thresholds refolded,
   // byte for byte otherwise
@@ -2399,6 +2404,7 @@ void FinishStats(RenderJob &job) {
   st.n_parked = static_cast<int64_t>(job.reuse ? ctx->resident.n_parked : job.total_parked);
   st.composed_maps = job.composed ? 1 : 0;
   st.xcd_order = job.xcd_order ? 1 : 0;
+  st.local_angles = job.local_angles ? 1 : 0;
   st.tail_policy = job.reuse ? ctx->resident.tail_policy : (job.park ? BL_TAIL_QUAD : (job.split_long ? BL_TAIL_SPLIT : BL_TAIL_WIDE));
   ctx->stats = st;
   if (ctx->debug_counters) {   // kernels built with -DBL_GEO_STATS fill these

@@ -28,6 +28,8 @@
 
 #pragma clang fp contract(fast)
 
+#include "bl_local_angles.h"
+
 namespace fused2 {
 
 // One cell of one axis, as the search wants it (LDS, 64 bytes)
@@ -101,11 +103,8 @@ __device__ __forceinline__ double expm1_k(double x) {
 }
 // 1 / sqrt(x) for finite x > 0 from v_rsq_f64 (2^-26) and ONE Newton step: 4e-16, which is what the tier's reciprocal has as well
 // (bl_fastmath.h's rsqrt takes two: a quarter of its instructions for a last place this kernel's results never show)
-__device__ __forceinline__ double rsqrt_k(double x) {
-  const double y = __builtin_amdgcn_rsq(x);
-  const double e = __builtin_fma(-0.5 * x * y, y, 0.5);
-  return __builtin_fma(y, e, y);
-}
+// (local_angles::rsqrt1: the one definition, in the header the diagnostics kernel shares)
+__device__ __forceinline__ double rsqrt_k(double x) { return local_angles::rsqrt1(x); }
 __device__ __forceinline__ double sqrt_k(double x) { return x > 0.0 ? x * rsqrt_k(x) : 0.0; }
 __device__ __forceinline__ double cbrt_k(double x) {
   const int e = __builtin_amdgcn_frexp_exp(x);
@@ -220,11 +219,14 @@ struct GridScalars {
 // what lets a row's address be computed with one shift-and-add). Device code only; the host pass sees stubs.
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 #if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ v2u lds_read_pair(uint32_t addr) { return *(const __attribute__((address_space(3))) v2u *)addr; }
 __device__ __forceinline__ v2d lds_read2(uint32_t addr) { return *(const __attribute__((address_space(3))) v2d *)addr; }
 __device__ __forceinline__ v4u lds_read_bits(uint32_t addr) { return *(const __attribute__((address_space(3))) v4u *)addr; }
 __device__ __forceinline__ uint32_t lds_address(const void *p) { return (uint32_t)(const __attribute__((address_space(3))) char *)p; }
 #else
+__device__ __forceinline__ v2u lds_read_pair(uint32_t) { return v2u{0u, 0u}; }
 __device__ __forceinline__ v2d lds_read2(uint32_t) { return v2d{0.0, 0.0}; }
 __device__ __forceinline__ v4u lds_read_bits(uint32_t) { return v4u{0u, 0u, 0u, 0u}; }
 __device__ __forceinline__ uint32_t lds_address(const void *) { return 0u; }
@@ -233,9 +235,10 @@ __device__ __forceinline__ uint32_t lds_address(const void *) { return 0u; }
 // The row tables of the three axes, one after the other (r, theta, phi), built by the workgroup from the grid's face and centre
 // tables. kReciprocal: the anchor's width enters as its reciprocal (tolerant tier: the fraction is one multiplication); otherwise
 // as the width itself, xv[c + 1] - xv[c] - the divisor of the exact tier's quotient, from the same subtraction.
+// (n_axes = 1: r alone - theta and phi relative to the cell centre have rows of their own, stage_angle_rows)
 template <bool kReciprocal>
-__device__ __forceinline__ void stage_axis_rows(const BlGridDevice &g, AxisRow *rows) {
-  for (int a = 0; a < 3; a++) {
+__device__ __forceinline__ void stage_axis_rows(const BlGridDevice &g, AxisRow *rows, int n_axes = 3) {
+  for (int a = 0; a < n_axes; a++) {
     const int n = g.n[a];
     const double *xf = g.xf[a], *xv = g.xv[a];
     for (int c = threadIdx.x; c < n; c += blockDim.x) {
@@ -255,6 +258,30 @@ __device__ __forceinline__ void stage_axis_rows(const BlGridDevice &g, AxisRow *
     }
     rows += n;
   }
+}
+// The theta and phi rows of the angles relative to the cell centre (local_angles::AngleRow, in the places of the AxisRows)
+__device__ __forceinline__ void stage_angle_rows(const BlGridDevice &g, AxisRow *rows) {
+  static_assert(sizeof(local_angles::AngleRow) == sizeof(AxisRow), "the tables' size does not depend on the rows' kind");
+  local_angles::AngleRow *at = reinterpret_cast<local_angles::AngleRow *>(rows + g.n[0]);
+  for (int a = 1; a < 3; a++) {
+    const int n = g.n[a];
+    for (int c = threadIdx.x; c < n; c += blockDim.x) at[c] = local_angles::make_row(g.xf[a], g.xv[a], g.angle_trig[a - 1][2 * c], g.angle_trig[a - 1][2 * c + 1], c, n, a == 1 ? kPi : 2.0 * kPi);
+    at += n;
+  }
+}
+__device__ __forceinline__ local_angles::AngleRow read_angle_row(uint32_t row_addr) {
+  const v2d trig = lds_read2(row_addr), faces = lds_read2(row_addr + 16u), inv_w = lds_read2(row_addr + 32u);
+  const v2u shift = lds_read_pair(row_addr + 48u);
+  local_angles::AngleRow row;
+  row.cos_c = trig.x;
+  row.sin_c = trig.y;
+  row.lo = faces.x;
+  row.hi = faces.y;
+  row.inv_w_ge = inv_w.x;
+  row.inv_w_lt = inv_w.y;
+  row.shift_ge = shift.x;
+  row.shift_lt = shift.y;
+  return row;
 }
 __device__ __forceinline__ GridScalars grid_scalars(const BlGridDevice &g, uint32_t lds_rows) {
   GridScalars G;
@@ -379,8 +406,13 @@ __device__ __forceinline__ void axis_lookup(uint32_t row_addr, double s, double 
 // three rows, and the cell is guessed and confirmed in those. A wrong box names a block whose rows do not hold the coordinate: the
 // row's faces fail to confirm it (blocks do not overlap, so rows that do confirm all three coordinates are the sample's block's),
 // and the sample is left to the exact kernel like any other the margins do not decide.
+// `local` (a runtime argument: one block; wave-uniform, the plan's choice - BlShadeArgs::local_angles): theta and phi relative to the centre of the guessed cell
+// (bl_local_angles.h) instead of acos_k / atan2_k. The same decisions from fewer instructions: the faces and the centre are compared with
+// d = angle - centre, the fraction is d / width + the anchor's shift; the seam of phi at 0 / 2 pi is the outer face of the first and
+// the last phi cell (the sine of a difference has no seam).
 template <bool kSpinZero, bool kRefined = false>
-__device__ __forceinline__ Located locate(const BlSpacetime &st, const GridScalars &G, double camera_r, double band, bool live, double x, double y, double z) {
+__device__ __forceinline__ Located locate(const BlSpacetime &st, const GridScalars &G, double camera_r, double band, bool live, double x, double y, double z,
+                                          bool local = false) {
   x = live ? x : 1.0;
   y = live ? y : 1.0;
   z = live ? z : 1.0;
@@ -398,67 +430,88 @@ __device__ __forceinline__ Located locate(const BlSpacetime &st, const GridScala
   const double r = sqrt_with_reciprocal(r2, &r_inv);
   const bool cut = r > camera_r;                                   // simulation_sampling.cpp:238-243
   const bool off_grid = r < G.r_in || r > G.r_out;                 // :352-394 (theta and phi cover the sphere)
-  // ConvertFromCKS (radiation_geometry.cpp:37-57) with the tier's inverse trigonometric functions
-  // (cos theta = z / r: the product with the reciprocal, corrected once by its residual, is the correctly rounded quotient - the
-  // exact tier's argument bit for bit - in all but a few cases in a million; the arccosine amplifies what is left by 1 / sin theta)
-  double cth = z * r_inv;
-  cth = __builtin_fma(__builtin_fma(-r, cth, z), r_inv, cth);
-  const double th = acos_k(cth);
-  double ph = kSpinZero ? atan2_k(y, x) : atan2_k(y, x) - atan2_k(st.bh_a, r);
-  const double ph_unwrapped = ph;
-  const double two_pi = KS(2.0 * kPi);
-  ph += ph < 0.0 ? two_pi : 0.0;
-  const double ph_once = ph;
-  ph -= ph >= two_pi ? two_pi : 0.0;
-  // guessed cells
   const float log2_r = __builtin_amdgcn_logf((float)r);
   int gi, gj, gk;
-  uint32_t rows_r = G.lds_r, rows_th = G.lds_th, rows_ph = G.lds_ph, block_bytes = 0u;
-  if (kRefined) {
-    int bi = (int)((log2_r - G.box_l0) * G.box_linv);
-    int bj = (int)((th - G.box_th_x0) * G.box_th_inv_w);
-    int bk = (int)((ph - G.box_ph_x0) * G.box_ph_inv_w);
-    bi = bi < 0 ? 0 : (bi > G.n_box_i1 ? G.n_box_i1 : bi);
-    bj = bj < 0 ? 0 : (bj > G.n_box_j1 ? G.n_box_j1 : bj);
-    bk = bk < 0 ? 0 : (bk > G.n_box_k1 ? G.n_box_k1 : bk);
-    const v4u desc = lds_read_bits(G.lds_desc + ((__umul24(__umul24((uint32_t)bk, G.n_box_j) + (uint32_t)bj, G.n_box_i) + (uint32_t)bi) << 4));
-    block_bytes = desc.x;
-    const v4u head_r = lds_read_bits(desc.y);
-    const v2d head_th = lds_read2(desc.z), head_ph = lds_read2(desc.w);
-    rows_r = desc.y + 16u;
-    rows_th = desc.z + 16u;
-    rows_ph = desc.w + 16u;
-    gi = (int)((log2_r - __uint_as_float(head_r.x)) * __uint_as_float(head_r.y));
-    gj = (int)((th - head_th.x) * head_th.y);
-    gk = (int)((ph - head_ph.x) * head_ph.y);
-  } else {
+  double f_i, f_j, f_k, m_i, c_i, m;
+  uint32_t di, dj, dk, block_bytes = 0u;
+  bool beyond_the_block = false;
+  if (!kRefined && local) {
+    const local_angles::Direction u = local_angles::direction<kSpinZero>(st.bh_a, r, r_inv, x, y, z);
+    const float th_guess = local_angles::angle_guess<false>((float)u.sin_th, (float)u.cos_th);
+    const float ph_guess = local_angles::angle_guess<true>((float)u.sin_ph, (float)u.cos_ph);
     gi = (int)((log2_r - G.r_l0) * G.r_linv);
-    gj = (int)((th - G.th_x0) * G.th_inv_w);
-    gk = (int)((ph - G.ph_x0) * G.ph_inv_w);
+    KernArgs args = kernargs();   // (the guess's origin and cells per radian: read here, not held across the loop)
+    gj = (int)((th_guess - args->grid.angle_guess[0]) * args->grid.angle_guess[1]);
+    gk = (int)((ph_guess - args->grid.angle_guess[2]) * args->grid.angle_guess[3]);
+    gi = gi < 0 ? 0 : (gi > G.n_i1 ? G.n_i1 : gi);
+    gj = gj < 0 ? 0 : (gj > G.n_j1 ? G.n_j1 : gj);
+    gk = gk < 0 ? 0 : (gk > G.n_k1 ? G.n_k1 : gk);
+    const local_angles::AngleRow row_j = read_angle_row(G.lds_th + ((uint32_t)gj << 6)), row_k = read_angle_row(G.lds_ph + ((uint32_t)gk << 6));
+    axis_lookup(G.lds_r + ((uint32_t)gi << 6), r, &f_i, &di, &m_i, &c_i);
+    double m_j, m_k;
+    local_angles::lookup(row_j, local_angles::offset_from_centre(u.sin_th, u.cos_th, row_j.cos_c, row_j.sin_c), &f_j, &dj, &m_j);
+    local_angles::lookup(row_k, local_angles::offset_from_centre(u.sin_ph, u.cos_ph, row_k.cos_c, row_k.sin_c), &f_k, &dk, &m_k);
+    m = m_j < m_k ? m_j : m_k;   // (on the polar axis phi is NaN: the comparison is false and m is NaN, which no band lets pass)
+  } else {
+    // ConvertFromCKS (radiation_geometry.cpp:37-57) with the tier's inverse trigonometric functions
+    // (cos theta = z / r: the product with the reciprocal, corrected once by its residual, is the correctly rounded quotient - the
+    // exact tier's argument bit for bit - in all but a few cases in a million; the arccosine amplifies what is left by 1 / sin theta)
+    double cth = z * r_inv;
+    cth = __builtin_fma(__builtin_fma(-r, cth, z), r_inv, cth);
+    const double th = acos_k(cth);
+    double ph = kSpinZero ? atan2_k(y, x) : atan2_k(y, x) - atan2_k(st.bh_a, r);
+    const double ph_unwrapped = ph;
+    const double two_pi = KS(2.0 * kPi);
+    ph += ph < 0.0 ? two_pi : 0.0;
+    const double ph_once = ph;
+    ph -= ph >= two_pi ? two_pi : 0.0;
+    // guessed cells
+    uint32_t rows_r = G.lds_r, rows_th = G.lds_th, rows_ph = G.lds_ph;
+    if (kRefined) {
+      int bi = (int)((log2_r - G.box_l0) * G.box_linv);
+      int bj = (int)((th - G.box_th_x0) * G.box_th_inv_w);
+      int bk = (int)((ph - G.box_ph_x0) * G.box_ph_inv_w);
+      bi = bi < 0 ? 0 : (bi > G.n_box_i1 ? G.n_box_i1 : bi);
+      bj = bj < 0 ? 0 : (bj > G.n_box_j1 ? G.n_box_j1 : bj);
+      bk = bk < 0 ? 0 : (bk > G.n_box_k1 ? G.n_box_k1 : bk);
+      const v4u desc = lds_read_bits(G.lds_desc + ((__umul24(__umul24((uint32_t)bk, G.n_box_j) + (uint32_t)bj, G.n_box_i) + (uint32_t)bi) << 4));
+      block_bytes = desc.x;
+      const v4u head_r = lds_read_bits(desc.y);
+      const v2d head_th = lds_read2(desc.z), head_ph = lds_read2(desc.w);
+      rows_r = desc.y + 16u;
+      rows_th = desc.z + 16u;
+      rows_ph = desc.w + 16u;
+      gi = (int)((log2_r - __uint_as_float(head_r.x)) * __uint_as_float(head_r.y));
+      gj = (int)((th - head_th.x) * head_th.y);
+      gk = (int)((ph - head_ph.x) * head_ph.y);
+    } else {
+      gi = (int)((log2_r - G.r_l0) * G.r_linv);
+      gj = (int)((th - G.th_x0) * G.th_inv_w);
+      gk = (int)((ph - G.ph_x0) * G.ph_inv_w);
+    }
+    gi = gi < 0 ? 0 : (gi > G.n_i1 ? G.n_i1 : gi);
+    gj = gj < 0 ? 0 : (gj > G.n_j1 ? G.n_j1 : gj);
+    gk = gk < 0 ? 0 : (gk > G.n_k1 ? G.n_k1 : gk);
+    double m_j, m_k, c_j, c_k;
+    bool up_i = false, up_j = false, up_k = false;
+    axis_lookup(rows_r + ((uint32_t)gi << 6), r, &f_i, &di, &m_i, &c_i, kRefined ? &up_i : nullptr);
+    axis_lookup(rows_th + ((uint32_t)gj << 6), th, &f_j, &dj, &m_j, &c_j, kRefined ? &up_j : nullptr);
+    axis_lookup(rows_ph + ((uint32_t)gk << 6), ph, &f_k, &dk, &m_k, &c_k, kRefined ? &up_k : nullptr);
+    // Inter-block interpolation (simulation_sampling.cpp:505-546): the anchor is c or c - 1 by the centre alone, also at a block's ends, and
+    // the cell beyond the block is another block's (FindNearbyInds). The row's anchor shift says where that happens - above the last
+    // cell's centre it is 1 (the plain rule steps back), below the first cell's it is 0 (it stays): such a sample is the exact pass's.
+    // Every other sample has all eight anchors in its own block and the plain rule's anchor and fraction (locate_sample_refined).
+    beyond_the_block = kRefined && G.block_interp != 0 && ((up_i ? di == 1u : di == 0u) || (up_j ? dj == 1u : dj == 0u) || (up_k ? dk == 1u : dk == 0u));
+    // theta, phi: the tier's own angles, so every value they are compared with must be further away than the band
+    m = m_j < m_k ? m_j : m_k;
+    m = m < c_j ? m : c_j;
+    m = m < c_k ? m : c_k;
+    const double e0 = __builtin_fabs(ph_unwrapped), e1 = __builtin_fabs(ph_once - two_pi);
+    m = m < e0 ? m : e0;
+    m = m < e1 ? m : e1;
   }
-  gi = gi < 0 ? 0 : (gi > G.n_i1 ? G.n_i1 : gi);
-  gj = gj < 0 ? 0 : (gj > G.n_j1 ? G.n_j1 : gj);
-  gk = gk < 0 ? 0 : (gk > G.n_k1 ? G.n_k1 : gk);
-  double f_i, f_j, f_k, m_i, m_j, m_k, c_i, c_j, c_k;
-  uint32_t di, dj, dk;
-  bool up_i = false, up_j = false, up_k = false;
-  axis_lookup(rows_r + ((uint32_t)gi << 6), r, &f_i, &di, &m_i, &c_i, kRefined ? &up_i : nullptr);
-  axis_lookup(rows_th + ((uint32_t)gj << 6), th, &f_j, &dj, &m_j, &c_j, kRefined ? &up_j : nullptr);
-  axis_lookup(rows_ph + ((uint32_t)gk << 6), ph, &f_k, &dk, &m_k, &c_k, kRefined ? &up_k : nullptr);
-  // Inter-block interpolation (simulation_sampling.cpp:505-546): the anchor is c or c - 1 by the centre alone, also at a block's ends, and
-  // the cell beyond the block is another block's (FindNearbyInds). The row's anchor shift says where that happens - above the last
-  // cell's centre it is 1 (the plain rule steps back), below the first cell's it is 0 (it stays): such a sample is the exact pass's.
-  // Every other sample has all eight anchors in its own block and the plain rule's anchor and fraction (locate_sample_refined).
-  const bool beyond_the_block = kRefined && G.block_interp != 0 && ((up_i ? di == 1u : di == 0u) || (up_j ? dj == 1u : dj == 0u) || (up_k ? dk == 1u : dk == 0u));
   // r is the exact tier's r: its cell is confirmed exactly (first c with xf[c + 1] >= r: xf[c] < r <= xf[c + 1]; m_i is
   // min(r - xf[c], xf[c + 1] - r)) - except on a face itself, where the signed minimum is zero either way: left to the exact pass
-  // theta, phi: the tier's own angles, so every value they are compared with must be further away than the band
-  double m = m_j < m_k ? m_j : m_k;
-  m = m < c_j ? m : c_j;
-  m = m < c_k ? m : c_k;
-  const double e0 = __builtin_fabs(ph_unwrapped), e1 = __builtin_fabs(ph_once - two_pi);
-  m = m < e0 ? m : e0;
-  m = m < e1 ? m : e1;
   const bool sampled = live && !cut && !off_grid;
   const bool undecided = sampled && (!(m > band) || !(m_i > 0.0) || beyond_the_block);
   Located out;
@@ -745,7 +798,10 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
       lds[i] = value;
     }
     if (kRefined) stage_refined_rows<true>(P.grid, reinterpret_cast<char *>(lds + 48), lds_base + 48u * 8u);
-    else stage_axis_rows<true>(P.grid, reinterpret_cast<AxisRow *>(lds + 48));
+    else if (P.local_angles) {
+      stage_axis_rows<true>(P.grid, reinterpret_cast<AxisRow *>(lds + 48), 1);
+      stage_angle_rows(P.grid, reinterpret_cast<AxisRow *>(lds + 48));
+    } else stage_axis_rows<true>(P.grid, reinterpret_cast<AxisRow *>(lds + 48));
   }
   __syncthreads();
   const uint32_t n_records = (uint32_t)P.counters_in[BL_CNT_RECORDS];   // (a scratch set holds fewer than 2^32 records)
@@ -759,6 +815,11 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   const int cut_mask = P.plasma.cut_mask;
   const double camera_r = P.cuts.camera_r;
   const double band = P.fast_angle_band;
+#if defined(BLV_ANGLES)   // (static profiles of one path alone - tools/isa_profile.py --flags "-DBLV_ANGLES=1": local, 2: global; never built into the library)
+  const bool local_angles = !kRefined && BLV_ANGLES == 1;
+#else
+  const bool local_angles = !kRefined && P.local_angles != 0;
+#endif
   const double K[6] = {P.fast_k[0], P.fast_k[1], P.fast_k[2], P.fast_k[3], P.fast_k[4], P.fast_k[5]};
   const bool model_rows = P.freq_split == 2;
   const double freq = uniform_value(P.frequencies[0]);
@@ -867,7 +928,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     s1.h1 = rec[1];
     s1.h1.y = s1.in ? s1.h1.y : __longlong_as_double((long long)BL_DEAD_RAY);
   }
-  s1.loc = locate<kSpinZero, kRefined>(st, G, camera_r, band, (uint32_t)__double_as_longlong(s1.h1.y) != BL_DEAD_RAY, s1.h0.x, s1.h0.y, s1.h1.x);
+  s1.loc = locate<kSpinZero, kRefined>(st, G, camera_r, band, (uint32_t)__double_as_longlong(s1.h1.y) != BL_DEAD_RAY, s1.h0.x, s1.h0.y, s1.h1.x, local_angles);
   // p (`prev`) is record p.first + lane (none in the first iteration), c (`cur`) c.first + lane, x (`next`) the wave's next 64
   // (walk_next)
   // (kRefined) the wave's samples for the exact pass, collected in LDS behind the tables and handed to the list 64 at a time
@@ -1024,7 +1085,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
       if (at < args->redo_capacity) args->redo_list[at] = (unsigned long long)(p.first + lane_in_wave);
     }
     // ---- the search for `next`
-    x.loc = locate<kSpinZero, kRefined>(st, G, camera_r, band, x.in && (uint32_t)__double_as_longlong(x.h1.y) != BL_DEAD_RAY, x.h0.x, x.h0.y, x.h1.x);
+    x.loc = locate<kSpinZero, kRefined>(st, G, camera_r, band, x.in && (uint32_t)__double_as_longlong(x.h1.y) != BL_DEAD_RAY, x.h0.x, x.h0.y, x.h1.x, local_angles);
     x.h1.y = x.in ? x.h1.y : __longlong_as_double((long long)BL_DEAD_RAY);
   };
   for (;;) {

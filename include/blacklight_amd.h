@@ -338,6 +338,8 @@ typedef struct bl_stats {
                                  integrated (launches_geodesic = 0, ms_geodesic = 0); bl_set_geodesic_reuse                              */
   int32_t sampling_reused;    /* 1: ... and the located samples too (same grid geometry: no locate kernel ran, launches_locate = 0)     */
   int32_t xcd_order;          /* 1: the rays were traced and their records shaded in the trace order per XCD (BL_SWITCH_FLAT_ORDER: 0) */
+  int32_t local_angles;       /* 1: bl_shade_fused2_kernel took theta and phi relative to the centre of the guessed cell; 0: acos / atan2
+                                 (angular cells beyond the series' reach, a mesh with refinement, BL_SWITCH_GLOBAL_ANGLES, another kernel) */
   /* Several electron models (bl_set_electron_models) where they cannot share one pass: launches_shade / launches_transfer count one
      shading pass per model and chunk; n_gathers, n_deferred and the sample counts are those of one pass (every pass has the same
      samples); ms_shade runs from the first coefficient kernel to the last one, ms_transfer is the last transfer kernel's. */
@@ -361,7 +363,9 @@ typedef struct bl_stats {
 #define BL_SWITCH_QUAD_EVERY_RAY (1u << 11)                 /* every ray parked before its first step: all stepping in bl_geodesic_quad_kernel */
 #define BL_SWITCH_FLAT_ORDER (1u << 12)                     /* one ray queue, tile by tile, and the records in one grid-stride walk
                                                                where the trace order per XCD applies (bl_stats.xcd_order)           */
-/* (Nine switches. Rounds 3 - 5 had eight more for experiments the measurements buried - a second pre-fused2 kernel, pre-gathered
+#define BL_SWITCH_GLOBAL_ANGLES (1u << 13)                  /* tolerant coefficient kernel: theta and phi by acos / atan2 where the
+                                                               angles relative to the cell centre apply (bl_stats.local_angles)     */
+/* (Ten switches. Rounds 3 - 5 had eight more for experiments the measurements buried - a second pre-fused2 kernel, pre-gathered
  * cell bricks, the coefficient kernel beside a chunk's last rays, repacked tails - and for what bl_set_tail_policy now says; their
  * numbers are in docs/notebook.md, their code in the history.) */
 
@@ -605,7 +609,13 @@ BL_API int bl_render(bl_ctx *ctx, const bl_render_desc *d);
  * op: 0 exp, 1 expm1, 2 log, 3 cbrt, 4 sin, 5 cos, 6 acos, 7 atan, 8 atan2(x, y), 9 pow(x, y),
  * 10 hypot (blmath.h), 11 bl_hypot_g, 12 bl_sqrt_g, 13 bl_div_g(x, y) (bl_geometry.h), 14 sqrt, 15 x / y,
  * 16 sincos -> sin, 17 sincos -> cos; 38 bl_pow_neg_fifth (the step controller's x^(-1/5), blmath.h). Used by the tests to compare the
- * device arithmetic with the host's. */
+ * device arithmetic with the host's.
+ * 40 (spin zero), 41 (any spin): not element-wise - the tolerant locate step's theta and phi of m points against an angular lattice,
+ * relative to the centre of the guessed cell (what bl_shade_fused2_kernel computes where bl_stats.local_angles says so) and by acos /
+ * atan2. x = [m, a, n_th, n_ph, xs[m], ys[m], zs[m]], y = [x2f[n_th + 1], x2v[n_th], x3f[n_ph + 1], x3v[n_ph]], both padded to n;
+ * n >= 16 m and n >= 2 (n_th + n_ph) + 2; out = [16][m]: rows 0 - 7 relative to the centre - anchor cell in theta, in phi, fraction
+ * in theta, in phi, smallest signed margin, undecided (margin <= 1e-12), guessed cell in theta, in phi - rows 8 - 15 the same from
+ * acos / atan2. */
 BL_API int bl_debug_math(bl_ctx *ctx, int op, int64_t n, const double *x, const double *y, double *out);
 /* Tolerant tier, tests only: relative half-width of the band around an active cell cut threshold inside which the cut
  * decision of a sample is left to the exact kernel (default 1e-9; the tolerant arithmetic is good to ~1e-13). A wide band
