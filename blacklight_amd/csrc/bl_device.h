@@ -474,6 +474,8 @@ struct BlShadeArgs {
   int undefined_edge;         // bl_set_undefined_policy(BL_UNDEFINED_EDGE): samples where the reference reads past its arrays use the edge
   int local_angles;           // bl_shade_fused2_kernel over one block: theta and phi relative to the centre of the guessed cell (bl_local_angles.h;
                               // the plan: angular cells within the series' reach, not BL_SWITCH_GLOBAL_ANGLES); 0: acos / atan2
+  int general_cuts;           // measurement switch (bl_stats.switches): bl_shade_fused2_kernel's general cut block where cut_sigma_max is the only
+                              // active threshold and its short form applies (fused2::cut_selection)
   const unsigned long long *counters_in;
   unsigned long long *counters;
   // bl_shade_fused2_kernel: the record lists of the geodesic kernel's trace order per XCD (BlTraceArgs::xcd_state), walked in

@@ -1637,6 +1637,7 @@ void BuildShadeArgs(RenderJob &job) {
   sa.samples_renormalised = job.geo_load ? 1 : 0;
   sa.general_locate = (ctx->switches & BL_SWITCH_GENERAL_LOCATE) ? 1 : 0;
   sa.local_angles = job.local_angles ? 1 : 0;
+  sa.general_cuts = (ctx->switches & BL_SWITCH_GENERAL_CUTS) ? 1 : 0;
   // One block per (unit, sigma cut) where the passes of two units or more compare their own cut thresholds and those of two cuts or
   // more their own cut_sigma_max (job.n_cold; BindVariant points at its variant's): the render's block with the thresholds refolded,
   // byte for byte otherwise

@@ -30,6 +30,8 @@
 
 #include "bl_local_angles.h"
 
+#include <type_traits>
+
 namespace fused2 {
 
 // One cell of one axis, as the search wants it (LDS, 64 bytes)
@@ -410,7 +412,13 @@ __device__ __forceinline__ void axis_lookup(uint32_t row_addr, double s, double 
 // (bl_local_angles.h) instead of acos_k / atan2_k. The same decisions from fewer instructions: the faces and the centre are compared with
 // d = angle - centre, the fraction is d / width + the anchor's shift; the seam of phi at 0 / 2 pi is the outer face of the first and
 // the last phi cell (the sine of a difference has no seam).
-template <bool kSpinZero, bool kRefined = false>
+// kAngles: kAnglesEither - `local` chooses (the kernel's prologue); kAnglesLocal / kAnglesGlobal - one path alone, whatever `local` says
+// (the kernel's two loops). The one path still sits behind a branch, on a scalar that is always set and that the optimiser cannot see
+// through, with a side never taken that leaves the sample undecided: as a basic block of its own it is compiled as it was behind the
+// branch on `local` - in one block with the search around it every one-block instantiation needs scratch memory (12 to 164 bytes a
+// lane, measured with and without a second loop). Two scalar instructions per sample.
+enum { kAnglesEither, kAnglesGlobal, kAnglesLocal };
+template <bool kSpinZero, bool kRefined = false, int kAngles = kAnglesEither>
 __device__ __forceinline__ Located locate(const BlSpacetime &st, const GridScalars &G, double camera_r, double band, bool live, double x, double y, double z,
                                           bool local = false) {
   x = live ? x : 1.0;
@@ -435,7 +443,13 @@ __device__ __forceinline__ Located locate(const BlSpacetime &st, const GridScala
   double f_i, f_j, f_k, m_i, c_i, m;
   uint32_t di, dj, dk, block_bytes = 0u;
   bool beyond_the_block = false;
-  if (!kRefined && local) {
+  bool take = local;
+  if (!kRefined && kAngles != kAnglesEither) {
+    int always = 1;
+    asm volatile("" : "+s"(always));
+    take = always != 0;
+  }
+  if (!kRefined && kAngles != kAnglesGlobal && take) {
     const local_angles::Direction u = local_angles::direction<kSpinZero>(st.bh_a, r, r_inv, x, y, z);
     const float th_guess = local_angles::angle_guess<false>((float)u.sin_th, (float)u.cos_th);
     const float ph_guess = local_angles::angle_guess<true>((float)u.sin_ph, (float)u.cos_ph);
@@ -452,6 +466,11 @@ __device__ __forceinline__ Located locate(const BlSpacetime &st, const GridScala
     local_angles::lookup(row_j, local_angles::offset_from_centre(u.sin_th, u.cos_th, row_j.cos_c, row_j.sin_c), &f_j, &dj, &m_j);
     local_angles::lookup(row_k, local_angles::offset_from_centre(u.sin_ph, u.cos_ph, row_k.cos_c, row_k.sin_c), &f_k, &dk, &m_k);
     m = m_j < m_k ? m_j : m_k;   // (on the polar axis phi is NaN: the comparison is false and m is NaN, which no band lets pass)
+  } else if (kAngles == kAnglesLocal || (kAngles == kAnglesGlobal && !kRefined && !take)) {   // (never taken)
+    gi = gj = gk = 0;
+    di = dj = dk = 0u;
+    f_i = f_j = f_k = m_i = c_i = 0.0;
+    m = __longlong_as_double(0x7ff8000000000000ll);
   } else {
     // ConvertFromCKS (radiation_geometry.cpp:37-57) with the tier's inverse trigonometric functions
     // (cos theta = z / r: the product with the reciprocal, corrected once by its residual, is the correctly rounded quotient - the
@@ -559,18 +578,29 @@ __device__ __forceinline__ bool trilinear(const float4 (&lo)[8], const float4 (&
       }
     }
   }
-  bool near_midpoint = false;
+  // The 29 bits below a float's last place, as a distance from the start of the window around the midpoint (0x10000000 -+ window;
+  // a value below the window wraps to more than 2^31), times eight: the shift drops the bits above the 29 and the subtraction rides
+  // with it. One minimum per window size - 2048 for rho and p_gas, 4096 for the rest - and one comparison each.
+  uint32_t nearest[2] = {0xffffffffu, 0xffffffffu};
 #pragma unroll
   for (int q = 0; q < 8; q++) {
-    const uint32_t below = (uint32_t)__double_as_longlong(val[q]) & 0x1fffffffu;
     const uint32_t window = q < 2 ? 2048u : 4096u;
-    near_midpoint = near_midpoint | ((below - (0x10000000u - window)) <= 2u * window);
+    const uint32_t from_start = ((uint32_t)__double_as_longlong(val[q]) << 3) - ((0x10000000u - window) << 3);
+    nearest[q < 2 ? 0 : 1] = nearest[q < 2 ? 0 : 1] < from_start ? nearest[q < 2 ? 0 : 1] : from_start;
   }
+  const bool near_midpoint = (nearest[0] <= (2u * 2048u) << 3) | (nearest[1] <= (2u * 4096u) << 3);
   if (val[0] <= 0.0) val[0] = (double)first[0];   // simulation_sampling.cpp:822-825
   if (val[1] <= 0.0) val[1] = (double)first[1];
 #pragma unroll
   for (int q = 0; q < 8; q++) pr[q] = (float)val[q];   // :830-839
   return near_midpoint;
+}
+
+constexpr int kCutsSigmaMaxOnly = 1 << 16;   // (no bit of a mask of the fourteen thresholds)
+// What shade() takes as cut_mask: the thresholds' mask, or kCutsSigmaMaxOnly where cut_sigma_max (bit 11) is the only active one and
+// the measurement switch (BlShadeArgs::general_cuts) does not ask for the general block. Wave-uniform, once per kernel.
+__device__ __forceinline__ int cut_selection(int cut_mask, int general_cuts) {
+  return cut_mask == (1 << 11) && general_cuts == 0 ? kCutsSigmaMaxOnly : cut_mask;
 }
 
 // fast_shade_sample() (bl_shade_fast.hip) for one frequency, thermal electrons, spherical Kerr-Schild simulation, as one straight
@@ -677,8 +707,14 @@ __device__ __forceinline__ double2 shade(const BlSpacetime &st, const double (&K
   // coefficients need is 1 / (k T_e): one reciprocal; k T_e itself only where a Theta_e cut looks at it
   const double kte_inv = (K[1] + K[2] * bi2 + K[3] * dd) * fastmath::rcp(K[0] * (pgas * rho_inv) * dd);
   // ---- cell cuts (:361-375): decided here unless a value sits within the guard band of an active threshold
+  // cut_mask (wave-uniform, the kernel's prologue: cut_selection): kCutsSigmaMaxOnly - one upper threshold on sigma, the common case -
+  // takes the threshold and its band alone; any other set of active thresholds, by its mask, the general block behind it.
   bool cell_cut = false, undecided = pp2 == 0.0;   // (on the polar axis: the exact kernel's business)
-  if (cut_mask != 0) {
+  if (cut_mask == kCutsSigmaMaxOnly) {
+    const v2d t = lds_read2(cut_table + 48u * 5u), b_hi = lds_read2(cut_table + 48u * 5u + 32u);
+    cell_cut = sigma_cut > t.y;
+    undecided = undecided | ((sigma_cut >= b_hi.x) & (sigma_cut <= b_hi.y));
+  } else if (__builtin_expect(cut_mask != 0, 0)) {
     const double bb = (cut_mask & 0x300) ? sqrt_k(b_sq) : 0.0;   // only the field-strength cuts need |b| itself
     const double kb_tt_e = (cut_mask & 0xc0) ? fastmath::rcp(kte_inv) : 0.0;
     const double value[7] = {rho, rho, pgas, kb_tt_e, bb, sigma_cut, beta_inv};   // against thresholds in these units
@@ -812,7 +848,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   const BlSpacetime st = P.st;
   const GridScalars G = kRefined ? grid_scalars_refined(P.grid, lds_base + 48u * 8u) : grid_scalars(P.grid, lds_base + 48u * 8u);
   const uint32_t cut_table = lds_base;
-  const int cut_mask = P.plasma.cut_mask;
+  const int cut_mask = cut_selection(P.plasma.cut_mask, P.general_cuts);
   const double camera_r = P.cuts.camera_r;
   const double band = P.fast_angle_band;
 #if defined(BLV_ANGLES)   // (static profiles of one path alone - tools/isa_profile.py --flags "-DBLV_ANGLES=1": local, 2: global; never built into the library)
@@ -942,7 +978,8 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     at = (unsigned long long)__builtin_amdgcn_readfirstlane((int)(at >> 32)) << 32 | (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)at);
     if (lane < count && at + lane < args->redo_capacity) args->redo_list[at + lane] = (unsigned long long)deferred_here[first + lane];
   };
-  auto iteration = [&](Slot &p, Slot &c, Slot &x) __attribute__((always_inline)) {
+  // kLocal (std::true_type / std::false_type): the angle path of the search, a constant of the loop the body is written into
+  auto iteration = [&](Slot &p, Slot &c, Slot &x, auto kLocal) __attribute__((always_inline)) {
     const uint32_t ray = (uint32_t)__double_as_longlong(p.h1.y);
     const bool live = ray != BL_DEAD_RAY;
     const uint32_t n = (uint32_t)(((unsigned long long)__double_as_longlong(p.h1.y)) >> 32);
@@ -1085,17 +1122,28 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
       if (at < args->redo_capacity) args->redo_list[at] = (unsigned long long)(p.first + lane_in_wave);
     }
     // ---- the search for `next`
-    x.loc = locate<kSpinZero, kRefined>(st, G, camera_r, band, x.in && (uint32_t)__double_as_longlong(x.h1.y) != BL_DEAD_RAY, x.h0.x, x.h0.y, x.h1.x, local_angles);
+    x.loc = locate<kSpinZero, kRefined, decltype(kLocal)::value ? kAnglesLocal : kAnglesGlobal>(st, G, camera_r, band, x.in && (uint32_t)__double_as_longlong(x.h1.y) != BL_DEAD_RAY,
+                                                                                               x.h0.x, x.h0.y, x.h1.x, local_angles);
     x.h1.y = x.in ? x.h1.y : __longlong_as_double((long long)BL_DEAD_RAY);
   };
-  for (;;) {
-    if (!__any(s0.in || s1.in)) break;
-    iteration(s0, s1, s2);
-    if (!__any(s1.in || s2.in)) break;
-    iteration(s1, s2, s0);
-    if (!__any(s2.in || s0.in)) break;
-    iteration(s2, s0, s1);
-  }
+  // One loop per angle path, chosen here once (wave-uniform): a loop holds the instructions of the path its waves execute and
+  // nothing of the other, which is 500 instructions less for the instruction cache to hold per three samples.
+  auto loop = [&](auto kLocal) __attribute__((always_inline)) {
+    for (;;) {
+      if (!__any(s0.in || s1.in)) break;
+      iteration(s0, s1, s2, kLocal);
+      if (!__any(s1.in || s2.in)) break;
+      iteration(s1, s2, s0, kLocal);
+      if (!__any(s2.in || s0.in)) break;
+      iteration(s2, s0, s1, kLocal);
+    }
+  };
+#if defined(BLV_ANGLES)
+  loop(std::integral_constant<bool, !kRefined && BLV_ANGLES == 1>{});
+#else
+  if (!kRefined && local_angles) loop(std::integral_constant<bool, !kRefined>{});
+  else loop(std::false_type{});
+#endif
   if (kRefined && n_deferred_here != 0u) hand_over_deferred(0u, n_deferred_here);
   if ((threadIdx.x & 63) == 0 && gathers_wave != 0ull) atomicAdd(&P.counters[BL_CNT_GATHERS], gathers_wave);
 }

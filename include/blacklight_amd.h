@@ -365,7 +365,9 @@ typedef struct bl_stats {
                                                                where the trace order per XCD applies (bl_stats.xcd_order)           */
 #define BL_SWITCH_GLOBAL_ANGLES (1u << 13)                  /* tolerant coefficient kernel: theta and phi by acos / atan2 where the
                                                                angles relative to the cell centre apply (bl_stats.local_angles)     */
-/* (Ten switches. Rounds 3 - 5 had eight more for experiments the measurements buried - a second pre-fused2 kernel, pre-gathered
+#define BL_SWITCH_GENERAL_CUTS (1u << 14)                   /* tolerant coefficient kernel: the general block of cell cuts where
+                                                               cut_sigma_max is the only active threshold (its short form)         */
+/* (Eleven switches. Rounds 3 - 5 had eight more for experiments the measurements buried - a second pre-fused2 kernel, pre-gathered
  * cell bricks, the coefficient kernel beside a chunk's last rays, repacked tails - and for what bl_set_tail_policy now says; their
  * numbers are in docs/notebook.md, their code in the history.) */
 

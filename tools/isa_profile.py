@@ -82,7 +82,7 @@ def main():
         extra = sys.argv[sys.argv.index("--flags") + 1].split()
         args = [a for a in args if a != sys.argv[sys.argv.index("--flags") + 1]]
     src, pattern = args[0], args[1]
-    out = f"/tmp/bl_isa_{os.path.basename(src)}.s"
+    out = f"/tmp/bl_isa_{os.path.basename(src)}_{os.getpid()}.s"
     subprocess.run(["hipcc", "-S", "--offload-device-only", "--offload-arch=gfx950", "-std=c++17", "-O3", "-ffp-contract=off", "-mllvm",
                     "-disable-machine-licm", "-gline-tables-only", f"-I{REPO}/include", f"-I{CSRC}", os.path.join(CSRC, src), "-o", out] + extra,
                    check=True, capture_output=True)
