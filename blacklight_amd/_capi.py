@@ -45,6 +45,14 @@ class SweepCuts(C.Structure):
     _fields_ = [("n_sigma_max", C.c_int32), ("reserved", C.c_int32), ("sigma_max", C.c_double * BL_MAX_SWEEP)]
 
 
+class SweepCameras(C.Structure):
+    """bl_sweep_cameras: the sweep_camera_th / sweep_camera_ph lists of a .input file (degrees), beside bl_sweep and bl_sweep_cuts."""
+    _fields_ = [("n_th", C.c_int32), ("n_ph", C.c_int32), ("th", C.c_double * BL_MAX_SWEEP), ("ph", C.c_double * BL_MAX_SWEEP)]
+
+
+BL_MAX_CAMERAS = 16
+
+
 class CameraFrame(C.Structure):
     _fields_ = [(name, C.c_double * 4) for name in
                 ("cam_x", "u_con", "u_cov", "norm_con", "norm_con_c", "hor_con_c", "vert_con_c")] + \
@@ -91,7 +99,7 @@ class Stats(C.Structure):
         ("arithmetic", C.c_int32), ("n_deferred", C.c_int64), ("n_undefined", C.c_int64),
         ("switches", C.c_uint32), ("fused_variant", C.c_int32), ("n_parked", C.c_int64),
         ("composed_maps", C.c_int32), ("tail_policy", C.c_int32), ("geodesics_reused", C.c_int32), ("sampling_reused", C.c_int32),
-        ("xcd_order", C.c_int32), ("local_angles", C.c_int32),
+        ("xcd_order", C.c_int32), ("local_angles", C.c_int32), ("n_cameras", C.c_int32),
     ]
 
 
@@ -121,6 +129,19 @@ def lib():
     L.bl_params_set_line_sweeps.argtypes = [C.c_void_p, C.POINTER(Sweep), C.POINTER(SweepCuts), C.c_char_p, C.c_char_p, C.c_size_t]
     L.bl_params_read_file_sweeps.argtypes = [C.c_void_p, C.POINTER(Sweep), C.POINTER(SweepCuts), C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
     L.bl_apply_sweeps.argtypes = [C.c_void_p, C.POINTER(Sweep), C.POINTER(SweepCuts)]
+    L.bl_params_set_line_sweeps_cameras.argtypes = [C.c_void_p, C.POINTER(Sweep), C.POINTER(SweepCuts), C.POINTER(SweepCameras), C.c_char_p, C.c_char_p,
+                                                    C.c_size_t]
+    L.bl_params_read_file_sweeps_cameras.argtypes = [C.c_void_p, C.POINTER(Sweep), C.POINTER(SweepCuts), C.POINTER(SweepCameras), C.c_char_p,
+                                                     C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+    L.bl_sweep_cameras_resolve.argtypes = [C.POINTER(SweepCameras), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                           C.c_char_p, C.c_size_t]
+    L.bl_apply_sweeps_cameras.argtypes = [C.c_void_p, C.POINTER(Sweep), C.POINTER(SweepCuts), C.POINTER(SweepCameras)]
+    L.bl_set_cameras.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.bl_num_cameras.argtypes = [C.c_void_p]
+    L.bl_cameras_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.bl_camera_frame_get_camera.argtypes = [C.c_void_p, C.c_int, C.POINTER(CameraFrame)]
+    L.bl_write_output_camera.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(OutputDesc), C.c_int, C.c_int]
+    L.bl_camera_output_path.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.bl_num_variants.argtypes = [C.c_void_p]
     L.bl_write_output_variant.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(OutputDesc), C.c_int]
     L.bl_variant_output_path.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]

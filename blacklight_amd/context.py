@@ -40,13 +40,13 @@ class Context:
 
     def apply_sweep(self, params=None):
         """bl_apply_sweeps: the sweep_rat_low / sweep_rat_high / sweep_rho_cgs lists of `params` (default: this context's) as electron
-        models and density units, or as polarized triples, and its sweep_cut_sigma_max list as sigma cuts. An empty sweep changes
-        nothing."""
+        models and density units, or as polarized triples, its sweep_cut_sigma_max list as sigma cuts and its sweep_camera_th /
+        sweep_camera_ph lists as cameras (bl_apply_sweeps_cameras). An empty sweep changes nothing."""
         params = params or self.params
         if not params.has_sweep:
             return
         polarized, low, high, rho = params.resolved_sweep()
-        self._check(self._lib.bl_apply_sweeps(self._ctx, C.byref(params.sweep), C.byref(params.sweep_cuts)))
+        self._check(self._lib.bl_apply_sweeps_cameras(self._ctx, C.byref(params.sweep), C.byref(params.sweep_cuts), C.byref(params.sweep_camera_lists)))
         if params.sweep_cut_sigma_max:
             self._sigma_cuts = params.sweep_cut_sigma_max
         if polarized:
@@ -63,12 +63,51 @@ class Context:
         """Images one render produces (bl_num_variants): models x units x sigma cuts, or polarized triples."""
         return self._lib.bl_num_variants(self._ctx)
 
-    def variant_output_path(self, snapshot=0, variant=0):
-        """The file name write_output(variant=...) uses without `path` (bl_variant_output_path): output_file, the file number of a
-        series, and a tag .mMMuUU (.mMMuUUsSS with sigma cuts set) / .vVV in front of the extension when the context renders several variants."""
+    def variant_output_path(self, snapshot=0, variant=0, camera=0):
+        """The file name write_output(variant=..., camera=...) uses without `path` (bl_camera_output_path): output_file, the file number
+        of a series, and in front of the extension a tag .mMMuUU (.mMMuUUsSS with sigma cuts set) / .vVV when the context renders
+        several variants, with .cCC in front of it when it renders several cameras (image.c01m00u02.npz)."""
         buf = C.create_string_buffer(4096)
-        self._check(self._lib.bl_variant_output_path(self._ctx, int(snapshot), int(variant), buf, len(buf)))
+        self._check(self._lib.bl_camera_output_path(self._ctx, int(snapshot), int(camera), int(variant), buf, len(buf)))
         return buf.value.decode()
+
+    # ------------------------------------------------------------------ cameras
+    def set_cameras(self, th, ph=None):
+        """Render several cameras (viewing angles camera_th, camera_ph in degrees, as the .input file writes them) in one render
+        (bl_set_cameras). Scalars or sequences, broadcast against each other; ph=None: 0 for every camera; an empty sequence clears
+        them (the parameter block's camera again). With C cameras a full root-level render has C * res^2 rays, camera c's outputs are
+        the slice camera_slice(c) of every per-ray array, and the geodesics of all cameras are integrated as one set of rays."""
+        th, ph = np.broadcast_arrays(np.atleast_1d(np.asarray(th, dtype=np.float64)), np.atleast_1d(np.asarray(0.0 if ph is None else ph, dtype=np.float64)))
+        th, ph = np.ascontiguousarray(th.ravel()), np.ascontiguousarray(ph.ravel())
+        self._check(self._lib.bl_set_cameras(self._ctx, int(th.size), th.ctypes.data_as(C.c_void_p), ph.ctypes.data_as(C.c_void_p)))
+
+    @property
+    def cameras(self):
+        """The (th, ph) pairs in degrees of the camera list (bl_cameras_get); [] when the parameter block's camera is rendered."""
+        n = self.num_cameras
+        th, ph = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        self._check(self._lib.bl_cameras_get(self._ctx, n, th.ctypes.data_as(C.c_void_p), ph.ctypes.data_as(C.c_void_p)))
+        return [(float(th[c]), float(ph[c])) for c in range(n)]
+
+    @property
+    def num_cameras(self):
+        return self._lib.bl_num_cameras(self._ctx)
+
+    def camera_slice(self, camera):
+        """Where camera `camera` of the list lies in every per-ray output of a full root-level render: slice(c res^2, (c + 1) res^2)."""
+        n = max(1, self.num_cameras)
+        if not 0 <= int(camera) < n:
+            raise IndexError(f"camera_slice: camera {camera} outside 0 .. {n - 1}")
+        pixels = self.resolution * self.resolution
+        return slice(int(camera) * pixels, (int(camera) + 1) * pixels)
+
+    def camera_frame_of(self, camera):
+        """The frame of camera `camera` of the list (bl_camera_frame_get_camera); with no list, camera 0 is the parameter block's."""
+        frame = _capi.CameraFrame()
+        rc = self._lib.bl_camera_frame_get_camera(self._ctx, int(camera), C.byref(frame))
+        if rc != 0:
+            raise IndexError(f"camera_frame_of: camera {camera} outside the list")
+        return frame
 
     def close(self):
         if self._ctx:
@@ -257,6 +296,8 @@ class Context:
         fluxes straddle the target. With several electron models set, each model is fitted in turn. The context's models and units
         are restored on exit. Returns (rho_cgs, flux_jy, renders): floats, or lists by model with several models."""
         from . import flux as _flux
+        if self.num_cameras >= 2:
+            raise ValueError("fit_density_unit sums one camera's image: not with two or more cameras (set_cameras)")
         if not (0.0 < lo < hi) or not np.isfinite(hi):
             raise ValueError(f"fit_density_unit needs 0 < lo < hi, finite (got {lo}, {hi})")
         if not 2 <= per_render <= 16:
@@ -353,6 +394,8 @@ class Context:
         Returns ([(rho_cgs, flux_jy, m_net, v_net) per pair], renders)."""
         from . import flux as _flux
         pairs = [(float(h), float(l)) for h, l in pairs]
+        if self.num_cameras >= 2:
+            raise ValueError("fit_density_units_polarized sums one camera's image: not with two or more cameras (set_cameras)")
         if not pairs:
             raise ValueError("fit_density_units_polarized needs at least one (rat_high, rat_low) pair")
         if not (0.0 < lo < hi) or not np.isfinite(hi):
@@ -486,7 +529,7 @@ class Context:
     # ------------------------------------------------------------------ render
     def level_pixels(self, level=0, n_blocks=0):
         if level == 0:
-            return self.resolution * self.resolution
+            return max(1, self.num_cameras) * self.resolution * self.resolution   # (several cameras: "virtual pixels" c res^2 + m)
         bs = int(self.params.get("adaptive_block_size"))
         return n_blocks * bs * bs
 
@@ -615,10 +658,12 @@ class Context:
             out["block_locs"] = nxt
             levels.append(out)
 
-    def write_output(self, levels, path=None, snapshot=0, variant=None):
+    def write_output(self, levels, path=None, snapshot=0, variant=None, camera=None):
         """OutputWriter::Write (reference output_writer.cpp:169-274); `levels` as from render_adaptive. variant = v: image v of a
         render of several variants ([render()]: the rows of all of them) as a file of its own (bl_write_output_variant) - what a
-        context with that variant in its parameter block writes; without `path` the name is variant_output_path(snapshot, v)."""
+        context with that variant in its parameter block writes; without `path` the name is variant_output_path(snapshot, v).
+        camera = c: camera c of a render of several cameras (bl_write_output_camera; with variant = v, that variant of it) - what a
+        context with that camera's angles in its parameter block writes from the camera's slice of every row and record."""
         d = _capi.OutputDesc()
         d.adaptive_num_levels = len(levels) - 1
         d.snapshot = snapshot
@@ -637,13 +682,15 @@ class Context:
                 rendering = np.ascontiguousarray(lv["rendering"], dtype=np.float64)
                 keep.append(rendering)
                 d.level[index].render = rendering.ctypes.data_as(C.c_void_p)
-            camera = lv.get("camera_pos") if plane else lv.get("camera_dir")
-            if camera is not None:
-                camera = np.ascontiguousarray(camera, dtype=np.float64)
-                keep.append(camera)
-                d.level[index].camera = camera.ctypes.data_as(C.c_void_p)
+            records = lv.get("camera_pos") if plane else lv.get("camera_dir")
+            if records is not None:
+                records = np.ascontiguousarray(records, dtype=np.float64)
+                keep.append(records)
+                d.level[index].camera = records.ctypes.data_as(C.c_void_p)
         target = None if path is None else str(path).encode()
-        if variant is None:
+        if camera is not None:
+            self._check(self._lib.bl_write_output_camera(self._ctx, target, C.byref(d), int(camera), int(variant or 0)))
+        elif variant is None:
             self._check(self._lib.bl_write_output(self._ctx, target, C.byref(d)))
         else:
             self._check(self._lib.bl_write_output_variant(self._ctx, target, C.byref(d), int(variant)))

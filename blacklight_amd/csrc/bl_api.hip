@@ -414,6 +414,22 @@ const char *SigmaCutsRefusal(const bl_ctx *ctx, int n) {
   return nullptr;
 }
 
+// Why n cameras cannot be rendered by this context (nullptr: they can). bl_set_cameras and bl_render's plan both ask.
+const char *CamerasRefusal(const bl_ctx *ctx, int n) {
+  const bl_params &p = ctx->params;
+  if (n <= 0) return nullptr;
+  if (p.checkpoint_geodesic_load) return "Cameras: a geodesic checkpoint carries its own camera (checkpoint_geodesic_load = true).";
+  if (n < 2) return nullptr;
+  if (p.adaptive_max_level > 0) return "Cameras: adaptive refinement reads one image; n >= 2 cameras need adaptive_max_level = 0.";
+  if (p.model_type == BL_MODEL_SIMULATION && p.slow_light_on) return "Cameras: slow light renders one camera (slow_light_on = true).";
+  if (p.checkpoint_geodesic_save) return "Cameras: a geodesic checkpoint holds one camera; n >= 2 cameras need checkpoint_geodesic_save = false.";
+  if (p.model_type == BL_MODEL_SIMULATION && p.checkpoint_sample_save)
+    return "Cameras: a sample checkpoint holds one camera; n >= 2 cameras need checkpoint_sample_save = false.";
+  if (p.cut_omit_near || p.cut_omit_far) return "Cameras: cut_omit_near and cut_omit_far compare with one camera position; n >= 2 cameras need both off.";
+  if (p.image_crossings) return "Cameras: image_crossings counts crossings of one camera's plane; n >= 2 cameras need image_crossings = false.";
+  return nullptr;
+}
+
 // The variants of a render, in image-row order: the triples (each with its own cut_sigma_max where bl_set_polarized_variants_sigma gave
 // one), else models x units x sigma cuts, model-major, then unit, then cut, with the parameter block's pair, unit and cut_sigma_max
 // where an axis is not set. The one reader of what the four setters stored.
@@ -479,6 +495,7 @@ int bl_init(const bl_params *p, int device, bl_ctx **out) {
     ValidateRadiation(ctx);
     BuildFrequencies(ctx);
     bl_camera_frame_build(ctx->params, ctx->st, &ctx->frame);
+    ctx->block_frame = ctx->frame;
     if (device == BL_DEVICE_NONE) {   // host-only context: validation, camera frame, refinement, writer
       ctx->device = BL_DEVICE_NONE;
       *out = ctx;
@@ -1278,6 +1295,29 @@ int bl_set_sigma_cuts(bl_ctx *ctx, int n, const double *sigma_max) {
 
 int bl_num_sigma_cuts(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->sigma_cuts.size()) : -1; }
 
+int bl_set_cameras(bl_ctx *ctx, int n, const double *th_deg, const double *ph_deg) {
+  if (ctx == nullptr) return BL_E_ARG;
+  if (n < 0 || n > BL_MAX_CAMERAS || (n > 0 && (th_deg == nullptr || ph_deg == nullptr)))
+    return Fail(ctx, Failure{BL_E_ARG, "bl_set_cameras needs 0 <= n <= " + std::to_string(BL_MAX_CAMERAS) + " and both arrays of angles."});
+  return bl_internal_set_cameras(ctx, n, th_deg, ph_deg);
+}
+
+int bl_num_cameras(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->cameras.size()) : -1; }
+
+int bl_camera_frame_get_camera(const bl_ctx *ctx, int camera, bl_camera_frame *out) {
+  if (ctx == nullptr || out == nullptr) return BL_E_ARG;
+  const int n = static_cast<int>(ctx->cameras.size());
+  if (camera < 0 || camera >= std::max(1, n)) return BL_E_ARG;
+  *out = n == 0 ? ctx->block_frame : ctx->cameras[camera].frame;
+  return BL_OK;
+}
+
+int bl_cameras_get(const bl_ctx *ctx, int n, double *th_deg, double *ph_deg) {
+  if (ctx == nullptr || n < 0 || (n > 0 && (th_deg == nullptr || ph_deg == nullptr))) return BL_E_ARG;
+  for (int c = 0; c < n && c < static_cast<int>(ctx->cameras.size()); c++) th_deg[c] = ctx->cameras[c].th_deg, ph_deg[c] = ctx->cameras[c].ph_deg;
+  return BL_OK;
+}
+
 int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out) {
   if (ctx == nullptr || out == nullptr) return BL_E_ARG;
   *out = ctx->frame;
@@ -1435,7 +1475,7 @@ void bl_free(bl_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   ctx->d_cells.Free(); ctx->d_kappa.Free(); ctx->d_coords.Free(); ctx->d_buckets.Free(); ctx->slot[0].Free(); ctx->slot[1].Free();
   ctx->d_freq.Free(); ctx->d_pixel_map.Free();
-  ctx->d_block_locs.Free(); ctx->d_tile_order.Free(); ctx->d_render_params.Free(); ctx->d_render.Free(); ctx->d_shade_cold.Free(); ctx->d_pol_variant_table.Free(); ctx->d_image.Free(); ctx->d_camera_pos.Free(); ctx->d_camera_dir.Free();
+  ctx->d_block_locs.Free(); ctx->d_tile_order.Free(); ctx->d_cameras.Free(); ctx->d_render_params.Free(); ctx->d_render.Free(); ctx->d_shade_cold.Free(); ctx->d_pol_variant_table.Free(); ctx->d_image.Free(); ctx->d_camera_pos.Free(); ctx->d_camera_dir.Free();
   ctx->d_out_sample_num.Free(); ctx->d_out_flags.Free();
   for (auto &e : ctx->events)
     if (e != nullptr) (void)hipEventDestroy(e);
@@ -1459,6 +1499,37 @@ const bl_camera_frame *bl_internal_frame(const bl_ctx *ctx) { return &ctx->frame
 const double *bl_internal_frequencies(const bl_ctx *ctx, int *count) {
   *count = static_cast<int>(ctx->frequencies.size());
   return ctx->frequencies.data();
+}
+// bl_set_cameras behind its argument checks. th_deg == nullptr: every camera at the parameter block's own camera_th (its radians and
+// its camera_pole, which no degree value need give back); ph_deg == nullptr: at the block's camera_ph - what an absent sweep_camera_th
+// or sweep_camera_ph means (bl_apply_sweeps_cameras).
+int bl_internal_set_cameras(bl_ctx *ctx, int n, const double *th_deg, const double *ph_deg) {
+  for (int c = 0; c < n; c++)
+    if ((th_deg != nullptr && !std::isfinite(th_deg[c])) || (ph_deg != nullptr && !std::isfinite(ph_deg[c])))
+      return Fail(ctx, Failure{BL_E_ARG, "bl_set_cameras: camera " + std::to_string(c) + " has an angle that is not finite."});
+  if (const char *why = CamerasRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
+  // Each camera's frame: what bl_init builds from the parameters with the three fields a written camera_th and camera_ph set
+  // (bl_params.cpp: degrees * pi / 180; camera_pole for a written th of exactly 0 or 180)
+  std::vector<bl_ctx::Camera> list(n);
+  for (int c = 0; c < n; c++) {
+    bl_params p = ctx->params;
+    list[c] = {p.camera_th * 180.0 / kPi, p.camera_ph * 180.0 / kPi, ctx->block_frame};
+    if (th_deg != nullptr) {
+      p.camera_th = th_deg[c] * kPi / 180.0;
+      p.camera_pole = (th_deg[c] == 0.0 || th_deg[c] == 180.0) ? 1 : 0;
+      list[c].th_deg = th_deg[c];
+    }
+    if (ph_deg != nullptr) {
+      p.camera_ph = ph_deg[c] * kPi / 180.0;
+      list[c].ph_deg = ph_deg[c];
+    }
+    bl_camera_frame_build(p, ctx->st, &list[c].frame);
+  }
+  std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; the resident geodesics' key holds the list: another list integrates again)
+  ctx->cameras = std::move(list);
+  ctx->cameras_uploaded = false;
+  ctx->frame = n == 1 ? ctx->cameras[0].frame : ctx->block_frame;
+  return BL_OK;
 }
 int bl_internal_fail(bl_ctx *ctx, int code, const char *message) {
   ctx->last_error = std::string("Error: ") + message + "\n";

@@ -141,6 +141,7 @@ void LoadGeodesicCheckpoint(bl_ctx *ctx) {
   bl_camera_frame &f = ctx->frame;
   double *vectors[7] = {f.cam_x, f.u_con, f.u_cov, f.norm_con, f.norm_con_c, f.hor_con_c, f.vert_con_c};
   for (int v = 0; v < 7; v++) std::memcpy(vectors[v], loaded->frame[v], 4 * sizeof(double));
+  ctx->block_frame = ctx->frame;   // (no camera list beside a loaded checkpoint: bl_set_cameras)
   ctx->frequencies = loaded->frequencies;   // LoadGeodesics() replaces what InitializeCamera() would have computed
   ctx->checkpoint = loaded;
 }

@@ -170,6 +170,19 @@ struct bl_ctx {
   std::vector<Variant> models, units, triples;
   bool triples_cut = false;          // the triples carry a cut_sigma_max each (bl_set_polarized_variants_sigma); else the parameter block's
   std::vector<double> sigma_cuts;
+  // bl_set_cameras(): the viewing angles as given (degrees) and each camera's frame; empty: the parameter block's camera. `frame`
+  // above is what a one-camera render starts its rays from - the block's own frame (block_frame), or the one camera of a list of
+  // one, so that such a render plans and runs exactly as a context with those angles in its block; two cameras or more reach the
+  // kernels through d_cameras (BlTraceArgs::cameras), uploaded when the list changes.
+  struct Camera {
+    double th_deg, ph_deg;
+    bl_camera_frame frame;
+  };
+  std::vector<Camera> cameras;
+  bl_camera_frame block_frame;
+  DeviceBuffer<BlCameraDevice> d_cameras;
+  bool cameras_uploaded = false;
+  int tile_order_cameras = 0;        // cameras d_tile_order interleaves (with tile_order_res, tile_order_xcd)
   BlAuxImages aux_images{};          // which image rows exist; .any = an auxiliary image or a rendering is requested
   int render_num_images = 0;         // false-colour renderings (0 in formula mode)
   DeviceBuffer<BlRenderDevice> d_render_params;
@@ -381,6 +394,7 @@ const char *ElectronModelsRefusal(const bl_ctx *ctx, int n);   // bl_set_electro
 const char *DensityUnitsRefusal(const bl_ctx *ctx, int n);     // bl_set_density_units (bl_api.hip)
 const char *PolarizedVariantsRefusal(const bl_ctx *ctx, int n);   // bl_set_polarized_variants (bl_api.hip)
 const char *SigmaCutsRefusal(const bl_ctx *ctx, int n);        // bl_set_sigma_cuts (bl_api.hip)
+const char *CamerasRefusal(const bl_ctx *ctx, int n);          // bl_set_cameras (bl_api.hip)
 }  // namespace blhost
 
 #endif  // BLACKLIGHT_AMD_BL_CTX_H_

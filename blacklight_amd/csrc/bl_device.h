@@ -358,6 +358,10 @@ struct BlTraceArgs {
   unsigned long long *xcd_state;
   unsigned int *xcd_lists;
   long long xcd_list_capacity;
+  // Several cameras as one set of rays (bl_set_cameras with n >= 2): the level's pixels are "virtual pixels" v = c pixels_per_camera + m;
+  // bl_ray_init_kernel starts ray v from cameras[c] at pixel m of that camera. Null: every ray is `cam`'s (pixels_per_camera unread).
+  const BlCameraDevice *cameras;
+  long long pixels_per_camera;
 };
 #define BL_RAY_START_FIELDS 17
 // A parked ray (BlTraceArgs::parked): everything bl_geodesic_kernel holds of a ray between two steps, BL_PARK_DOUBLES doubles
@@ -539,6 +543,11 @@ struct BlTransferArgs {
   BlSpacetime st;
   int simulation_coord, rotation_split;
   double cam_u_con[4], cam_u_cov[4], cam_vert_con_c[4];
+  // ... several cameras (BlTraceArgs::cameras): the ray with output index r is camera (pixel_map ? pixel_map[r] : r) / pixels_per_camera's,
+  // whose three vectors take the place of the ones above. Null: one camera.
+  const BlCameraDevice *cameras;
+  const int *pixel_map;
+  long long pixels_per_camera;
   const double2 *transfer;
   int ja_stride;                           // records between the (j, alpha) of consecutive (sample, frequency) pairs as bl_transfer_aux_kernel reads them:
                                            // 1, or 4 in polarized runs, where `transfer` is pol_coeffs

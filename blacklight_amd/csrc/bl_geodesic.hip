@@ -75,16 +75,16 @@ __device__ __forceinline__ long long xcd_queue_rays(int chunk_rays, int r) {
 // instruction stream) and kept the camera frame - 28 doubles - in scalar registers through every step of every ray. Here
 // every lane is busy, and the stepping kernel fetches 17 doubles per new ray instead. Same functions of the same inputs:
 // same bits.
+// Several cameras (BlTraceArgs::cameras): the level's pixel v = c pixels_per_camera + m is pixel m of camera c, whose frame comes from
+// the table instead of the argument block. Where every lane of the wave has the same camera - always so for a full frame whose
+// cameras hold a multiple of 64 pixels each - the index is made visibly uniform (readfirstlane) and the frame stays in scalar
+// registers as the argument block's does; where a camera boundary falls inside the wave, each lane loads its own (a struct copy
+// with fixed member indices: registers, no scratch). The same function of the same numbers either way.
 template <bool kDormandPrince, bool kSpinZero>
-__global__ void __launch_bounds__(256) bl_ray_init_kernel(BlTraceArgs P) {
-  const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= (long long)P.chunk_rays) return;
-  const BlSpacetime st = P.st;
-  const long long ray = traversal_to_ray(P.chunk_begin + q, P.swizzle_tiles, P.tile_order);
-  const long long pixel = P.pixel_map != nullptr ? (long long)P.pixel_map[ray] : ray;
+__device__ __forceinline__ void bl_start_ray(const BlTraceArgs &P, const BlSpacetime &st, const BlCameraDevice &cam, long long pixel, long long ray, long long q) {
   double u_ind, v_ind, position[4], direction[4], factor;
-  bl_pixel_indices(P.cam, pixel, P.block_locs, &u_ind, &v_ind);
-  bl_pixel_ray(st, P.cam, u_ind, v_ind, position, direction, &factor);
+  bl_pixel_indices(cam, pixel, P.block_locs, &u_ind, &v_ind);
+  bl_pixel_ray(st, cam, u_ind, v_ind, position, direction, &factor);
   P.ray_kt[q] = direction[0];
   P.ray_factor[q] = factor;
   P.ray_out_index[q] = ray;
@@ -111,6 +111,29 @@ __global__ void __launch_bounds__(256) bl_ray_init_kernel(BlTraceArgs P) {
     double k0[8], r_unused;
     rhs<true, kSpinZero>(st, s.y, s.kt, k0, &r_unused);
     for (int p = 0; p < 8; p++) start[(9 + p) * stride] = k0[p];
+  }
+}
+
+template <bool kDormandPrince, bool kSpinZero>
+__global__ void __launch_bounds__(256) bl_ray_init_kernel(BlTraceArgs P) {
+  const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= (long long)P.chunk_rays) return;
+  const BlSpacetime st = P.st;
+  const long long ray = traversal_to_ray(P.chunk_begin + q, P.swizzle_tiles, P.tile_order);
+  const long long pixel = P.pixel_map != nullptr ? (long long)P.pixel_map[ray] : ray;
+  if (P.cameras == nullptr) {
+    bl_start_ray<kDormandPrince, kSpinZero>(P, st, P.cam, pixel, ray, q);
+    return;
+  }
+  const int camera = (int)(pixel / P.pixels_per_camera);
+  const long long within = pixel - (long long)camera * P.pixels_per_camera;
+  const int first = __builtin_amdgcn_readfirstlane(camera);
+  if (__all(camera == first)) {
+    const BlCameraDevice cam = P.cameras[first];
+    bl_start_ray<kDormandPrince, kSpinZero>(P, st, cam, within, ray, q);
+  } else {
+    const BlCameraDevice cam = P.cameras[camera];
+    bl_start_ray<kDormandPrince, kSpinZero>(P, st, cam, within, ray, q);
   }
 }
 

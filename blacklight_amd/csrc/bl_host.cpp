@@ -343,6 +343,8 @@ int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const i
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more polarized variants (bl_set_polarized_variants).");
   if (bl_num_sigma_cuts(ctx) >= 2)
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more sigma cuts (bl_set_sigma_cuts).");
+  if (bl_num_cameras(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more cameras (bl_set_cameras).");
   const bl_params &p = *bl_internal_params(ctx);
   *n_refined = 0;
   if (p.adaptive_max_level <= 0 || level >= p.adaptive_max_level) {   // radiation_adaptive.cpp:22-23
@@ -415,7 +417,7 @@ int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const i
 namespace {
 
 // The file's name (output_writer.cpp:283-316 for a series) and, for one image of several, its tag (include/blacklight_amd.h)
-int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, std::string *path) {
+int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, int camera, int n_cameras, std::string *path) {
   const bl_params &p = *bl_internal_params(ctx);
   if (!p.has[BL_P_output_file]) return bl_internal_fail(ctx, BL_E_MISSING, "OutputWriter unable to find all needed values in input file.");
   *path = p.output_file.s;
@@ -424,20 +426,24 @@ int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, std::stri
     if (!FormatFilename(p.output_file.s, file_number, path))
       return bl_internal_fail(ctx, BL_E_INPUT, "Invalid output_file for multiple runs.");
   }
-  if (n_variants < 2) return BL_OK;
-  char tag[32];
-  if (bl_num_polarized_variants(ctx) >= 1) {
-    std::snprintf(tag, sizeof tag, ".v%02d", variant);
+  if (n_variants < 2 && n_cameras < 2) return BL_OK;
+  // (the camera's tag in front of the variant's, inside one dot group: .c01m00u02)
+  char camera_tag[16] = "", tag[32] = "";
+  if (n_cameras >= 2) std::snprintf(camera_tag, sizeof camera_tag, "c%02d", camera);
+  if (n_variants < 2) {
+  } else if (bl_num_polarized_variants(ctx) >= 1) {
+    std::snprintf(tag, sizeof tag, "v%02d", variant);
   } else {
     // (variant = (m U + u) S + s; the cut's tag only where cuts are set: names without cuts are as ever)
     const int n_units = std::max(1, bl_num_density_units(ctx)), n_cuts = bl_num_sigma_cuts(ctx), pair = variant / std::max(1, n_cuts);
-    if (n_cuts >= 1) std::snprintf(tag, sizeof tag, ".m%02du%02ds%02d", pair / n_units, pair % n_units, variant % n_cuts);
-    else std::snprintf(tag, sizeof tag, ".m%02du%02d", pair / n_units, pair % n_units);
+    if (n_cuts >= 1) std::snprintf(tag, sizeof tag, "m%02du%02ds%02d", pair / n_units, pair % n_units, variant % n_cuts);
+    else std::snprintf(tag, sizeof tag, "m%02du%02d", pair / n_units, pair % n_units);
   }
+  const std::string group = std::string(".") + camera_tag + tag;
   const std::string::size_type slash = path->find_last_of('/');
   const std::string::size_type dot = path->find_last_of('.');
-  if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) path->append(tag);
-  else path->insert(dot, tag);
+  if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) path->append(group);
+  else path->insert(dot, group);
   return BL_OK;
 }
 
@@ -448,9 +454,36 @@ std::string MessageOf(std::string text) {
   return text;
 }
 
-// bl_write_output and bl_write_output_variant: image `variant` of the n_variants the root level's rows hold
-int WriteOutput(bl_ctx *ctx, const char *path_override, const bl_output_desc *d, int variant, int n_variants) {
+// bl_write_output, bl_write_output_variant and bl_write_output_camera: image `variant` of the n_variants the root level's rows hold, and
+// of every row and record the slice of `camera` of the n_cameras that lie side by side in it
+int WriteOutput(bl_ctx *ctx, const char *path_override, const bl_output_desc *d_given, int variant, int n_variants, int camera = 0, int n_cameras = 1) {
+  const bl_output_desc *d = d_given;
   if (d->level[0].image == nullptr && bl_image_num_quantities(ctx) > 0) return bl_internal_fail(ctx, BL_E_ARG, "bl_write_output needs the root image.");
+  // Several cameras: the camera's share of the variant's rows, of the renderings and of the camera records, as the one-camera
+  // arrays everything below expects (rows of C res^2 entries -> rows of res^2; the records of a camera lie together already)
+  bl_output_desc sliced;
+  std::vector<double> camera_image, camera_render;
+  if (n_cameras >= 2) {
+    const bl_params &pp = *bl_internal_params(ctx);
+    const size_t pixels = static_cast<size_t>(pp.camera_resolution) * pp.camera_resolution, stride = pixels * n_cameras;
+    const size_t rows = static_cast<size_t>(bl_image_num_quantities(ctx) / n_variants), render_rows = static_cast<size_t>(bl_render_num_images(ctx)) * 3;
+    sliced = *d;
+    if (d->level[0].image != nullptr) {
+      camera_image.resize(rows * pixels);
+      const double *from = d->level[0].image + static_cast<size_t>(variant) * rows * stride + camera * pixels;
+      for (size_t q = 0; q < rows; q++) std::memcpy(camera_image.data() + q * pixels, from + q * stride, pixels * sizeof(double));
+      sliced.level[0].image = camera_image.data();
+    }
+    if (d->level[0].render != nullptr) {
+      camera_render.resize(render_rows * pixels);
+      for (size_t q = 0; q < render_rows; q++)
+        std::memcpy(camera_render.data() + q * pixels, d->level[0].render + q * stride + camera * pixels, pixels * sizeof(double));
+      sliced.level[0].render = camera_render.data();
+    }
+    if (d->level[0].camera != nullptr) sliced.level[0].camera = d->level[0].camera + static_cast<size_t>(camera) * pixels * 4;
+    d = &sliced;
+  }
+  const int row_variant = n_cameras >= 2 ? 0 : variant;   // (a camera's slice holds the one variant's rows alone)
   const bl_params &p = *bl_internal_params(ctx);
   const bl_camera_frame &frame = *bl_internal_frame(ctx);
   int n_nu = 0;
@@ -463,7 +496,7 @@ int WriteOutput(bl_ctx *ctx, const char *path_override, const bl_output_desc *d,
   if (path_override != nullptr && path_override[0] != '\0') {
     path = path_override;
   } else {
-    const int rc = OutputPath(ctx, d->snapshot, variant, n_variants, &path);
+    const int rc = OutputPath(ctx, d->snapshot, variant, n_variants, camera, n_cameras, &path);
     if (rc != BL_OK) return rc;
   }
   std::ofstream stream(path, std::ios_base::out | std::ios_base::binary);
@@ -471,7 +504,7 @@ int WriteOutput(bl_ctx *ctx, const char *path_override, const bl_output_desc *d,
 
   if (bl_render_num_images(ctx) > 0 && p.output_format != BL_OUTPUT_NPZ)
     return bl_internal_fail(ctx, BL_E_INPUT, "Only npz outputs support rendering.");
-  const double *image0 = d->level[0].image == nullptr ? nullptr : d->level[0].image + static_cast<size_t>(variant) * n_q * n_pix;
+  const double *image0 = d->level[0].image == nullptr ? nullptr : d->level[0].image + static_cast<size_t>(row_variant) * n_q * n_pix;
   if (p.output_format == BL_OUTPUT_RAW && p.model_type == BL_MODEL_SIMULATION && p.image_light && p.has[BL_P_image_polarization]
       && p.image_polarization)   // output_writer.cpp:64-70
     return bl_internal_fail(ctx, BL_E_INPUT, "Only npz or npy outputs support polarization.");
@@ -722,6 +755,8 @@ int bl_write_output(bl_ctx *ctx, const char *path_override, const bl_output_desc
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no variant axis (bl_set_polarized_variants with n >= 2).");
   if (bl_num_sigma_cuts(ctx) >= 2)
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no sigma-cut axis (bl_set_sigma_cuts with n >= 2).");
+  if (bl_num_cameras(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file holds one camera (bl_set_cameras with n >= 2; bl_write_output_camera).");
   return WriteOutput(ctx, path_override, d, 0, 1);
 }
 
@@ -732,7 +767,36 @@ int bl_write_output_variant(bl_ctx *ctx, const char *path_override, const bl_out
     return bl_internal_fail(ctx, BL_E_ARG, ("bl_write_output_variant: variant " + std::to_string(variant) + " outside 0 .. " + std::to_string(n_variants - 1) + ".").c_str());
   if (n_variants >= 2 && d->adaptive_num_levels != 0)
     return bl_internal_fail(ctx, BL_E_ARG, "bl_write_output_variant: a render of several variants has no adaptive levels.");
+  if (bl_num_cameras(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output_variant: the reference's file holds one camera (bl_set_cameras with n >= 2; bl_write_output_camera).");
   return WriteOutput(ctx, path_override, d, variant, n_variants);
+}
+
+int bl_write_output_camera(bl_ctx *ctx, const char *path_override, const bl_output_desc *d, int camera, int variant) {
+  if (ctx == nullptr || d == nullptr) return BL_E_ARG;
+  const int n_variants = bl_num_variants(ctx), n_cameras = std::max(1, bl_num_cameras(ctx));
+  if (camera < 0 || camera >= n_cameras)
+    return bl_internal_fail(ctx, BL_E_ARG, ("bl_write_output_camera: camera " + std::to_string(camera) + " outside 0 .. " + std::to_string(n_cameras - 1) + ".").c_str());
+  if (variant < 0 || variant >= n_variants)
+    return bl_internal_fail(ctx, BL_E_ARG, ("bl_write_output_camera: variant " + std::to_string(variant) + " outside 0 .. " + std::to_string(n_variants - 1) + ".").c_str());
+  if ((n_variants >= 2 || n_cameras >= 2) && d->adaptive_num_levels != 0)
+    return bl_internal_fail(ctx, BL_E_ARG, "bl_write_output_camera: a render of several cameras or variants has no adaptive levels.");
+  return WriteOutput(ctx, path_override, d, variant, n_variants, camera, n_cameras);
+}
+
+int bl_camera_output_path(bl_ctx *ctx, int snapshot, int camera, int variant, char *buf, size_t len) {
+  if (ctx == nullptr || buf == nullptr) return BL_E_ARG;
+  const int n_variants = bl_num_variants(ctx), n_cameras = std::max(1, bl_num_cameras(ctx));
+  if (camera < 0 || camera >= n_cameras)
+    return bl_internal_fail(ctx, BL_E_ARG, ("bl_camera_output_path: camera " + std::to_string(camera) + " outside 0 .. " + std::to_string(n_cameras - 1) + ".").c_str());
+  if (variant < 0 || variant >= n_variants)
+    return bl_internal_fail(ctx, BL_E_ARG, ("bl_camera_output_path: variant " + std::to_string(variant) + " outside 0 .. " + std::to_string(n_variants - 1) + ".").c_str());
+  std::string path;
+  const int rc = OutputPath(ctx, snapshot, variant, n_variants, camera, n_cameras, &path);
+  if (rc != BL_OK) return rc;
+  if (path.size() + 1 > len) return bl_internal_fail(ctx, BL_E_ARG, "bl_camera_output_path: the buffer is too short for the name.");
+  std::memcpy(buf, path.c_str(), path.size() + 1);
+  return BL_OK;
 }
 
 int bl_variant_output_path(bl_ctx *ctx, int snapshot, int variant, char *buf, size_t len) {
@@ -741,7 +805,7 @@ int bl_variant_output_path(bl_ctx *ctx, int snapshot, int variant, char *buf, si
   if (variant < 0 || variant >= n_variants)
     return bl_internal_fail(ctx, BL_E_ARG, ("bl_variant_output_path: variant " + std::to_string(variant) + " outside 0 .. " + std::to_string(n_variants - 1) + ".").c_str());
   std::string path;
-  const int rc = OutputPath(ctx, snapshot, variant, n_variants, &path);
+  const int rc = OutputPath(ctx, snapshot, variant, n_variants, 0, 1, &path);
   if (rc != BL_OK) return rc;
   if (path.size() + 1 > len) return bl_internal_fail(ctx, BL_E_ARG, "bl_variant_output_path: the buffer is too short for the name.");
   std::memcpy(buf, path.c_str(), path.size() + 1);
@@ -785,6 +849,30 @@ int bl_apply_sweeps(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cut
     if (polarized && (sweep->n_rat_low > 0 || sweep->n_rho_cgs > 0)) bl_set_polarized_variants(ctx, 0, nullptr, nullptr, nullptr);
     if (!polarized && sweep->n_rat_low > 0) bl_set_electron_models(ctx, 0, nullptr, nullptr);
     if (!polarized && sweep->n_rho_cgs > 0) bl_set_density_units(ctx, 0, nullptr);
+    bl_internal_fail(ctx, rc, MessageOf(why).c_str());
+  }
+  return rc;
+}
+
+int bl_apply_sweeps_cameras(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts, const bl_sweep_cameras *cameras) {
+  if (ctx == nullptr || sweep == nullptr) return BL_E_ARG;
+  int n = 0, th_given = 0, ph_given = 0;
+  double th[BL_MAX_SWEEP], ph[BL_MAX_SWEEP];
+  char err[512] = "";
+  if (cameras != nullptr && bl_sweep_cameras_resolve(cameras, &n, th, ph, &th_given, &ph_given, err, sizeof err) != BL_OK)
+    return bl_internal_fail(ctx, BL_E_INPUT, MessageOf(err).c_str());
+  // (the cameras first: their refusal leaves nothing behind, and a refusal of the lists after them takes the cameras back)
+  const int held = bl_num_cameras(ctx);
+  double held_th[BL_MAX_CAMERAS], held_ph[BL_MAX_CAMERAS];
+  (void)bl_cameras_get(ctx, held, held_th, held_ph);
+  if (n > 0) {
+    const int rc = bl_internal_set_cameras(ctx, n, th_given ? th : nullptr, ph_given ? ph : nullptr);
+    if (rc != BL_OK) return rc;
+  }
+  const int rc = bl_apply_sweeps(ctx, sweep, cuts);
+  if (rc != BL_OK && n > 0) {
+    const std::string why = bl_last_error(ctx);
+    (void)bl_internal_set_cameras(ctx, held, held > 0 ? held_th : nullptr, held > 0 ? held_ph : nullptr);
     bl_internal_fail(ctx, rc, MessageOf(why).c_str());
   }
   return rc;

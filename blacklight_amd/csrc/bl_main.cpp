@@ -190,7 +190,8 @@ int main(int argc, char *argv[]) {
   int num_runs = 1;
   static bl_sweep sweep;   // sweep_rat_low / sweep_rat_high / sweep_rho_cgs: several images per snapshot, one file each
   static bl_sweep_cuts sweep_cuts;   // ... and sweep_cut_sigma_max, an axis of its own
-  if (bl_params_read_file_sweeps(&params, &sweep, &sweep_cuts, argv[1], &num_runs, err, sizeof err) != BL_OK) {
+  static bl_sweep_cameras sweep_cameras;   // ... and sweep_camera_th / sweep_camera_ph: several cameras per render, one file per (camera, variant)
+  if (bl_params_read_file_sweeps_cameras(&params, &sweep, &sweep_cuts, &sweep_cameras, argv[1], &num_runs, err, sizeof err) != BL_OK) {
     std::cout << err;
     return 1;
   }
@@ -230,7 +231,7 @@ int main(int argc, char *argv[]) {
     // as the reference's do across thread counts. And so are runs over several devices: a frame and its tiles are then the same bits.
     if (params.adaptive_max_level > 0 || n_devices > 1) bl_set_reproducible(contexts[dev], 1);
     // the sweep on every device: a device's share of the frame then holds the rows of all variants, like the frame does
-    if (bl_apply_sweeps(contexts[dev], &sweep, &sweep_cuts) != BL_OK) {
+    if (bl_apply_sweeps_cameras(contexts[dev], &sweep, &sweep_cuts, &sweep_cameras) != BL_OK) {
       std::cout << bl_last_error(contexts[dev]);
       return 1;
     }
@@ -240,6 +241,7 @@ int main(int argc, char *argv[]) {
   const int res = params.camera_resolution;
   const int n_q = bl_image_num_quantities(ctx);   // rows of one render: those of every variant of a sweep, one after another
   const int n_variants = bl_num_variants(ctx);
+  const int n_cameras = std::max(1, bl_num_cameras(ctx));   // cameras of one render: the root level's rays are n_cameras x res^2 "virtual pixels"
   const int bs = params.adaptive_max_level > 0 ? params.adaptive_block_size : 1;
   const bool want_camera = params.has[BL_P_output_camera] && params.output_camera && params.output_format == BL_OUTPUT_NPZ;
 
@@ -321,7 +323,7 @@ int main(int argc, char *argv[]) {
     int level = 0;
     std::string shared_warnings;   // several devices: the levels' warnings with their totals
     while (true) {
-      const long long n_rays = level == 0 ? static_cast<long long>(res) * res
+      const long long n_rays = level == 0 ? static_cast<long long>(n_cameras) * res * res
                                           : static_cast<long long>(counts[level]) * bs * bs;
       if (level == 0 && have_root) {   // the root level's buffers: allocated once, pinned when a series fills them again and again
         images.push_back(std::move(root_image));
@@ -360,6 +362,9 @@ int main(int argc, char *argv[]) {
           LevelShare &sh = shares[dev];
           if (level == 0) {
             sh.pixels = TilePixels(res, dev, n_devices, tile);
+            const size_t per_camera = sh.pixels.size();   // (several cameras: the device's tiles of every camera, camera by camera)
+            for (int c = 1; c < n_cameras; c++)
+              for (size_t i = 0; i < per_camera; i++) sh.pixels.push_back(sh.pixels[i] + c * res * res);
             sh.where.assign(sh.pixels.begin(), sh.pixels.end());
           } else {
             for (int b = dev; b < counts[level]; b += n_devices) {
@@ -496,7 +501,15 @@ int main(int argc, char *argv[]) {
       out.level[l].render = n_render > 0 ? renders[l].data() : nullptr;
     }
     double t_write = Now();
-    if (n_variants == 1) {
+    if (n_cameras > 1) {
+      // one file of the reference's layout per (camera, variant): the camera's slice of the variant's rows
+      for (int camera = 0; camera < n_cameras; camera++)
+        for (int variant = 0; variant < n_variants; variant++)
+          if (bl_write_output_camera(ctx, nullptr, &out, camera, variant) != BL_OK) {
+            std::cout << bl_last_error(ctx);
+            return 1;
+          }
+    } else if (n_variants == 1) {
       if (bl_write_output(ctx, nullptr, &out) != BL_OK) {
         std::cout << bl_last_error(ctx);
         return 1;
@@ -547,5 +560,8 @@ int main(int argc, char *argv[]) {
     if (n_cuts > 0) std::cout << " x " << n_cuts << " sigma cuts";
     std::cout << "), one file each; writing outputs: " << time_write << " s\n";
   }
+  if (sweep_cameras.n_th > 0 || sweep_cameras.n_ph > 0)
+    std::cout << "blacklight_amd: " << n_cameras << " cameras per snapshot traced as one set of rays, one file per camera"
+              << (n_variants > 1 ? " and variant" : "") << "; writing outputs: " << time_write << " s\n";
   return 0;
 }

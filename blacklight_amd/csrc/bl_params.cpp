@@ -291,7 +291,7 @@ void ReadRender(bl_params *p, const std::string &key, const std::string &val) {
 
 // sweep_rat_low / sweep_rat_high / sweep_rho_cgs / sweep_cut_sigma_max: "a,b,c" (an extension: the reference has no lists). Stricter than the scalar keys:
 // every entry is a whole number text - nothing is left of it after the conversion -, none is empty, at most BL_MAX_SWEEP of them.
-enum ListKind { kNumbers, kUnits, kSigmaCuts };
+enum ListKind { kNumbers, kUnits, kSigmaCuts, kAngles };
 int ReadList(const std::string &key, const std::string &val, ListKind kind, double *out) {
   int count = 0;
   for (size_t at = 0; at <= val.size();) {
@@ -305,6 +305,8 @@ int ReadList(const std::string &key, const std::string &val, ListKind kind, doub
       throw ParseFailure{"Invalid density unit (" + entry + ") in list (" + key + ") in input file: must be finite and positive."};
     if (kind == kSigmaCuts && !std::isfinite(x))
       throw ParseFailure{"Invalid sigma cut (" + entry + ") in list (" + key + ") in input file: must be finite."};
+    if (kind == kAngles && !std::isfinite(x))
+      throw ParseFailure{"Invalid angle (" + entry + ") in list (" + key + ") in input file: must be finite."};
     if (count >= BL_MAX_SWEEP)
       throw ParseFailure{"Too many entries in list (" + key + ") in input file: at most " + std::to_string(BL_MAX_SWEEP) + " for this build."};
     out[count++] = x;
@@ -313,12 +315,14 @@ int ReadList(const std::string &key, const std::string &val, ListKind kind, doub
   return count;
 }
 
-// The sweep keys go beside the parameter block (bl_sweep, bl_sweep_cuts), never into it; false: not a sweep key
-bool SetSweepKey(bl_sweep *s, bl_sweep_cuts *c, const std::string &key, const std::string &val) {
+// The sweep keys go beside the parameter block (bl_sweep, bl_sweep_cuts, bl_sweep_cameras), never into it; false: not a sweep key
+bool SetSweepKey(bl_sweep *s, bl_sweep_cuts *c, bl_sweep_cameras *a, const std::string &key, const std::string &val) {
   if (key == "sweep_rat_low") s->n_rat_low = ReadList(key, val, kNumbers, s->rat_low);
   else if (key == "sweep_rat_high") s->n_rat_high = ReadList(key, val, kNumbers, s->rat_high);
   else if (key == "sweep_rho_cgs") s->n_rho_cgs = ReadList(key, val, kUnits, s->rho_cgs);
   else if (key == "sweep_cut_sigma_max") c->n_sigma_max = ReadList(key, val, kSigmaCuts, c->sigma_max);
+  else if (key == "sweep_camera_th") a->n_th = ReadList(key, val, kAngles, a->th);
+  else if (key == "sweep_camera_ph") a->n_ph = ReadList(key, val, kAngles, a->ph);
   else return false;
   return true;
 }
@@ -354,8 +358,18 @@ void ResolveSweep(const bl_sweep &s, const bl_params &p, bl_sweep *out, int *pol
   if (out != nullptr) *out = r;
 }
 
-void SetKeyValue(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, const std::string &key, const std::string &val) {
-  if (key.compare(0, 6, "sweep_") == 0 && SetSweepKey(sweep, cuts, key, val)) return;
+// What the two camera lists mean together (include/blacklight_amd.h, bl_sweep_cameras_resolve): the number of cameras
+int ResolveCameras(const bl_sweep_cameras &a) {
+  if (a.n_th < 0 || a.n_ph < 0 || a.n_th > BL_MAX_SWEEP || a.n_ph > BL_MAX_SWEEP)
+    throw ParseFailure{"Too many entries in a sweep list: at most " + std::to_string(BL_MAX_SWEEP) + " for this build."};
+  if (a.n_th > 0 && a.n_ph > 1 && a.n_ph != a.n_th)
+    throw ParseFailure{"sweep_camera_ph must have one entry or as many as sweep_camera_th (" + std::to_string(a.n_ph) + " and "
+                       + std::to_string(a.n_th) + ") in input file."};
+  return a.n_th > 0 ? a.n_th : a.n_ph;
+}
+
+void SetKeyValue(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_cameras *cameras, const std::string &key, const std::string &val) {
+  if (key.compare(0, 6, "sweep_") == 0 && SetSweepKey(sweep, cuts, cameras, key, val)) return;
   // Compound keys first
   if (key == "cut_plane_origin") return ReadTriple(val, p, BL_P_cut_plane_origin_x);
   if (key == "cut_plane_normal") return ReadTriple(val, p, BL_P_cut_plane_normal_x);
@@ -403,7 +417,7 @@ void SetKeyValue(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, const std::
   throw ParseFailure{"Unknown key (" + key + ") in input file."};
 }
 
-void ParseLine(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, std::string line) {
+void ParseLine(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_cameras *cameras, std::string line) {
   std::string stripped;
   stripped.reserve(line.size());
   for (unsigned char c : line)
@@ -413,7 +427,7 @@ void ParseLine(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, std::string l
   if (stripped.empty()) return;
   pos = stripped.find('=');
   if (pos == std::string::npos) throw ParseFailure{"Invalid assignment in input file."};
-  SetKeyValue(p, sweep, cuts, stripped.substr(0, pos), stripped.substr(pos + 1));
+  SetKeyValue(p, sweep, cuts, cameras, stripped.substr(0, pos), stripped.substr(pos + 1));
 }
 
 }  // namespace
@@ -427,11 +441,17 @@ void bl_params_clear(bl_params *p) {
 size_t bl_params_sizeof(void) { return sizeof(bl_params); }
 
 int bl_params_set_line_sweeps(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, const char *line, char *err, size_t err_len) {
+  return bl_params_set_line_sweeps_cameras(p, sweep, cuts, nullptr, line, err, err_len);
+}
+
+int bl_params_set_line_sweeps_cameras(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_cameras *cameras, const char *line, char *err,
+                                      size_t err_len) {
   if (p == nullptr || line == nullptr) return BL_E_ARG;
   bl_sweep unused = {};   // (no sweep asked for: the keys are accepted and validated all the same)
   bl_sweep_cuts unused_cuts = {};
+  bl_sweep_cameras unused_cameras = {};
   try {
-    ParseLine(p, sweep != nullptr ? sweep : &unused, cuts != nullptr ? cuts : &unused_cuts, line);
+    ParseLine(p, sweep != nullptr ? sweep : &unused, cuts != nullptr ? cuts : &unused_cuts, cameras != nullptr ? cameras : &unused_cameras, line);
   } catch (const ParseFailure &failure) {
     SetError(err, err_len, failure.message);
     return BL_E_INPUT;
@@ -452,22 +472,31 @@ int bl_params_read_file_sweep(bl_params *p, bl_sweep *sweep, const char *path, i
 }
 
 int bl_params_read_file_sweeps(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, const char *path, int *num_runs, char *err, size_t err_len) {
+  return bl_params_read_file_sweeps_cameras(p, sweep, cuts, nullptr, path, num_runs, err, err_len);
+}
+
+int bl_params_read_file_sweeps_cameras(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_cameras *cameras, const char *path, int *num_runs,
+                                       char *err, size_t err_len) {
   if (p == nullptr || path == nullptr) return BL_E_ARG;
   bl_params_clear(p);
   bl_sweep local = {};
   bl_sweep_cuts local_cuts = {};
+  bl_sweep_cameras local_cameras = {};
   if (sweep == nullptr) sweep = &local;
   if (cuts == nullptr) cuts = &local_cuts;
+  if (cameras == nullptr) cameras = &local_cameras;
   *sweep = bl_sweep{};
   *cuts = bl_sweep_cuts{};
+  *cameras = bl_sweep_cameras{};
   std::ifstream stream(path);
   if (!stream.is_open()) {
     SetError(err, err_len, "Could not open input file.");
     return BL_E_INPUT;
   }
   try {
-    for (std::string line; std::getline(stream, line);) ParseLine(p, sweep, cuts, line);
+    for (std::string line; std::getline(stream, line);) ParseLine(p, sweep, cuts, cameras, line);
     ResolveSweep(*sweep, *p, nullptr, nullptr);   // the lists against each other, once the whole file is known
+    (void)ResolveCameras(*cameras);
   } catch (const ParseFailure &failure) {
     SetError(err, err_len, failure.message);
     return BL_E_INPUT;
@@ -507,6 +536,25 @@ int bl_sweep_resolve(const bl_sweep *sweep, const bl_params *p, bl_sweep *resolv
   if (sweep == nullptr || p == nullptr) return BL_E_ARG;
   try {
     ResolveSweep(*sweep, *p, resolved, polarized);
+  } catch (const ParseFailure &failure) {
+    SetError(err, err_len, failure.message);
+    return BL_E_INPUT;
+  }
+  return BL_OK;
+}
+
+int bl_sweep_cameras_resolve(const bl_sweep_cameras *cameras, int *n, double *th_deg, double *ph_deg, int *th_given, int *ph_given, char *err,
+                             size_t err_len) {
+  if (cameras == nullptr) return BL_E_ARG;
+  try {
+    const int count = ResolveCameras(*cameras);
+    if (n != nullptr) *n = count;
+    if (th_given != nullptr) *th_given = cameras->n_th > 0 ? 1 : 0;
+    if (ph_given != nullptr) *ph_given = cameras->n_ph > 0 ? 1 : 0;
+    for (int c = 0; c < count; c++) {
+      if (th_deg != nullptr && cameras->n_th > 0) th_deg[c] = cameras->th[c];
+      if (ph_deg != nullptr && cameras->n_ph > 0) ph_deg[c] = cameras->ph[cameras->n_ph == 1 ? 0 : c];
+    }
   } catch (const ParseFailure &failure) {
     SetError(err, err_len, failure.message);
     return BL_E_INPUT;

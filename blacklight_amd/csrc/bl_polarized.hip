@@ -446,6 +446,28 @@ __device__ __forceinline__ void couple_sample(Coupling *cp, bool rotation_split,
   limit_polarization(ss_end);
 }
 
+// The camera's 4-velocity and vertical of the ray with output index `out_index` (camera.cpp's u_con, u_cov, vert_con_c): the argument
+// block's, or with several cameras (BlTransferArgs::cameras) those of the camera the ray's pixel belongs to. Fixed indices: registers.
+__device__ __forceinline__ void load_camera_vectors(const BlTransferArgs &P, long long out_index, double u_con[4], double u_cov[4], double vert[4]) {
+  if (P.cameras == nullptr) {
+#pragma unroll
+    for (int mu = 0; mu < 4; mu++) {
+      u_con[mu] = P.cam_u_con[mu];
+      u_cov[mu] = P.cam_u_cov[mu];
+      vert[mu] = P.cam_vert_con_c[mu];
+    }
+    return;
+  }
+  const long long pixel = P.pixel_map != nullptr ? (long long)P.pixel_map[out_index] : out_index;
+  const BlCameraDevice *cam = P.cameras + pixel / P.pixels_per_camera;
+#pragma unroll
+  for (int mu = 0; mu < 4; mu++) {
+    u_con[mu] = cam->u_con[mu];
+    u_cov[mu] = cam->u_cov[mu];
+    vert[mu] = cam->vert_con_c[mu];
+  }
+}
+
 }  // namespace
 
 __global__ void __launch_bounds__(64) bl_transfer_polarized_kernel(BlTransferArgs P) {
@@ -579,7 +601,8 @@ __global__ void __launch_bounds__(64) bl_transfer_polarized_kernel(BlTransferArg
         for (int nu = 0; nu < 4; nu++) acc += gcon[mu][nu] * kcov[nu];
         kcon[mu] = acc;
       }
-      const double *u_con = P.cam_u_con, *u_cov = P.cam_u_cov, *vert = P.cam_vert_con_c;
+      double u_con[4], u_cov[4], vert[4];
+      load_camera_vectors(P, out_index, u_con, u_cov, vert);
       up_con[0] = u_con[0] * vert[0] - (u_cov[1] * vert[1] + u_cov[2] * vert[2] + u_cov[3] * vert[3]) / u_cov[0];
       up_con[1] = vert[1] + u_con[1] * vert[0];
       up_con[2] = vert[2] + u_con[2] * vert[0];
@@ -971,7 +994,8 @@ __global__ void __launch_bounds__(64, 2) bl_transfer_polarized_matrix_kernel(BlT
       for (int nu = 0; nu < 4; nu++) acc += gcon[mu][nu] * kcov[nu];
       kcon[mu] = acc;
     }
-    const double *u_con = P.cam_u_con, *u_cov = P.cam_u_cov, *vert = P.cam_vert_con_c;
+    double u_con[4], u_cov[4], vert[4];
+    load_camera_vectors(P, out_index, u_con, u_cov, vert);
     up_con[0] = u_con[0] * vert[0] - (u_cov[1] * vert[1] + u_cov[2] * vert[2] + u_cov[3] * vert[3]) / u_cov[0];
     up_con[1] = vert[1] + u_con[1] * vert[0];
     up_con[2] = vert[2] + u_con[2] * vert[0];

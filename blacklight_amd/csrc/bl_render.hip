@@ -127,6 +127,8 @@ struct RenderJob {
   int cold_units = 1, cold_cuts = 1;   // ... n_cold = cold_units x cold_cuts, an axis of one where the passes do not differ along it
                                        // (polarized variants with cuts that differ: cold_cuts = the variants, each with its own)
   long long n_rays = 0, level_pixels = 0;
+  int n_cameras = 1;          // cameras traced as one set of rays (bl_set_cameras): level_pixels = n_cameras x the camera's pixels
+  bool camera_table = false;  // ... two or more: the ray-start kernel reads each ray's frame from BlTraceArgs::cameras
   size_t redo_capacity = 0;
   // scratch
   ArrayUse use;
@@ -363,6 +365,10 @@ void PlanJob(RenderJob &job) {
   if (const char *why = DensityUnitsRefusal(ctx, vs.n_units)) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = PolarizedVariantsRefusal(ctx, vs.n_pol)) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = SigmaCutsRefusal(ctx, vs.n_cuts)) throw Failure{BL_E_UNSUPPORTED, why};
+  if (const char *why = CamerasRefusal(ctx, static_cast<int>(ctx->cameras.size()))) throw Failure{BL_E_UNSUPPORTED, why};
+  job.n_cameras = std::max<int>(1, static_cast<int>(ctx->cameras.size()));
+  job.camera_table = job.n_cameras >= 2;
+  // (two cameras or more render the root level only: adaptive_max_level is 0 with them, so the level check above has seen to it)
   // What BuildShadeArgs folds before a variant is bound: the first variant - one variant is a fresh render with it in the parameter
   // block, and the first triple's cut decisions are every triple's in one pass. But several (model, unit) variants keep the parameter
   // block's pair, and two or more units its unit too (so base_rho is the one set unit, the first triple's, else the parameter block's):
@@ -394,6 +400,11 @@ void PlanJob(RenderJob &job) {
 
   job.level_pixels = static_cast<long long>(p.camera_resolution) * p.camera_resolution;
   if (d->level > 0) job.level_pixels = static_cast<long long>(d->n_blocks) * p.adaptive_block_size * p.adaptive_block_size;
+  else job.level_pixels *= job.n_cameras;   // (virtual pixels v = c res^2 + m)
+  if (!ctx->cameras.empty() && d->pixel_map != nullptr)   // (a virtual pixel beyond the last camera would index past the camera table)
+    for (long long ray = 0; ray < job.n_rays; ray++)
+      if (d->pixel_map[ray] < 0 || d->pixel_map[ray] >= job.level_pixels)
+        throw Failure{BL_E_ARG, "pixel_map names a pixel outside 0 .. " + std::to_string(job.level_pixels - 1) + " (cameras x camera_resolution^2)."};
   if (d->pixel_map == nullptr && job.n_rays > job.level_pixels) throw Failure{BL_E_ARG, "n_rays exceeds the pixels of this level."};
   if (job.geo_save && (d->pixel_map != nullptr || job.n_rays != job.level_pixels))
     throw Failure{BL_E_ARG, "checkpoint_geodesic_save needs the whole root camera in one bl_render call."};
@@ -508,7 +519,8 @@ void PlanJob(RenderJob &job) {
   // the whole - and the critical curve is the circle b = 3 sqrt(3) M: no spin)
   const bool split_auto = ctx->tail_policy == BL_TAIL_AUTO && !ctx->split_unavailable && ctx->st.bh_a == 0.0 && !p.ray_flat
       && job.n_rays >= 32768 && job.n_rays <= 8ll * 256 * ctx->num_cus;
-  job.split_long = job.allow_split && parkable && !job.park && (split_forced || split_auto) && p.camera_type == BL_CAMERA_PLANE && d->level == 0;
+  job.split_long = job.allow_split && parkable && !job.park && (split_forced || split_auto) && p.camera_type == BL_CAMERA_PLANE && d->level == 0
+      && !job.camera_table;   // (several cameras: BL_TAIL_SPLIT resolves to BL_TAIL_WIDE - the split kernel knows one camera's pixels)
   // ... and in the exact coefficient kernel (plain images): the frequency loop as lanes of bl_coefficients_freq_kernel
   job.coef_split = !job.fast && job.simulation && !job.aux && !ctx->polarized && job.n_nu >= 4;
   // (polarized runs list the samples without coefficients there - cut samples, cut cells - which are many more)
@@ -590,6 +602,12 @@ void BuildReuseKeys(RenderJob &job) {
   for (const double (*v)[4] : {&f.cam_x, &f.u_con, &f.u_cov, &f.norm_con, &f.norm_con_c, &f.hor_con_c, &f.vert_con_c})
     for (int mu = 0; mu < 4; mu++) key.Put((*v)[mu]);
   key.Put(f.r_horizon); key.Put(f.r_terminate);
+  key.Put(job.n_cameras);
+  if (job.camera_table)   // (the list is part of what "the same camera" means; a list of one is `frame` above)
+    for (const bl_ctx::Camera &camera : ctx->cameras)
+      for (const double (*v)[4] : {&camera.frame.cam_x, &camera.frame.u_con, &camera.frame.u_cov, &camera.frame.norm_con, &camera.frame.norm_con_c,
+                                   &camera.frame.hor_con_c, &camera.frame.vert_con_c})
+        for (int mu = 0; mu < 4; mu++) key.Put((*v)[mu]);
   key.Put(p.camera_type); key.Put(p.camera_width); key.Put(p.camera_r); key.Put(p.camera_resolution); key.Put(p.image_normalization);
   key.Put(p.ray_integrator); key.Put(p.ray_step); key.Put(p.ray_tol_abs); key.Put(p.ray_tol_rel); key.Put(p.ray_max_steps); key.Put(p.ray_max_retries);
   key.Put(d->level); key.Put(d->n_rays);
@@ -939,7 +957,8 @@ bool XcdOrderApplies(const RenderJob &job) {
   const bl_params &p = ctx->params;
   return job.fused2 && !job.freq_split && !(ctx->switches & BL_SWITCH_FLAT_ORDER)
       && job.d->level == 0 && job.d->pixel_map == nullptr && p.camera_resolution % 8 == 0 && job.n_rays == job.level_pixels && !job.raster
-      && !job.reuse && !job.reuse_chunks && !job.kept && job.no_checkpoint && !job.park && !job.split_long;
+      && !job.reuse && !job.reuse_chunks && !job.kept && job.no_checkpoint && !job.park && !job.split_long
+      && !job.camera_table;   // (its super-tiles are one camera's: off for several cameras, which changes only speed)
 }
 
 // The geodesic stage's instantiation: decided here for PlanScratch - the persistent grid is sized by its occupancy - and for PlanKernels
@@ -1393,7 +1412,7 @@ void BuildTraceArgs(RenderJob &job) {
   if (ta.swizzle_tiles > 0) {
     const bool super_tiles = job.reuse ? ctx->resident.super_tiles : job.xcd_order;
     job.super_tiles = super_tiles;
-    if (ctx->tile_order_res != p.camera_resolution || ctx->tile_order_xcd != super_tiles) {
+    if (ctx->tile_order_res != p.camera_resolution || ctx->tile_order_xcd != super_tiles || ctx->tile_order_cameras != job.n_cameras) {
       const int tiles_per_row = p.camera_resolution / 8;
       const int n_tiles = tiles_per_row * tiles_per_row;
       const int unit = super_tiles ? 8 : 1;   // (tiles per side of the unit)
@@ -1411,10 +1430,26 @@ void BuildTraceArgs(RenderJob &job) {
         const double da = unit_dist2(a), db = unit_dist2(b);
         return da != db ? da < db : unit_index(a) < unit_index(b);
       });
-      ctx->d_tile_order.Ensure(n_tiles);
-      Check(hipMemcpy(ctx->d_tile_order.ptr, order.data(), n_tiles * sizeof(int), hipMemcpyHostToDevice), "tile order upload");
+      // Several cameras: the ray set is an image of res x C res pixels, camera c's tiles are c n_tiles + t. Interleaved - tile t of
+      // every camera, then the next tile of the one order - so that every camera's long rays near its centre come first and a chunk,
+      // and the call, ends on every camera's short ones.
+      if (job.n_cameras >= 2) {
+        std::vector<int> stacked;
+        stacked.reserve(static_cast<size_t>(n_tiles) * job.n_cameras);
+#ifdef BL_CAMERAS_CONSECUTIVE   // (A/B builds: camera after camera, each centre first - profiles/cameras.json has both orders' times)
+        for (int c = 0; c < job.n_cameras; c++)
+          for (int t = 0; t < n_tiles; t++) stacked.push_back(c * n_tiles + order[t]);
+#else
+        for (int t = 0; t < n_tiles; t++)
+          for (int c = 0; c < job.n_cameras; c++) stacked.push_back(c * n_tiles + order[t]);
+#endif
+        order.swap(stacked);
+      }
+      ctx->d_tile_order.Ensure(order.size());
+      Check(hipMemcpy(ctx->d_tile_order.ptr, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice), "tile order upload");
       ctx->tile_order_res = p.camera_resolution;
       ctx->tile_order_xcd = super_tiles;
+      ctx->tile_order_cameras = job.n_cameras;
     }
     ta.tile_order = ctx->d_tile_order.ptr;
   }
@@ -1423,6 +1458,31 @@ void BuildTraceArgs(RenderJob &job) {
   ta.camera_pos = job.cam_pos;
   ta.camera_dir = job.cam_dir;
   ta.ray_start_stride = job.n_rays;
+  // Several cameras: every camera's block as `cam` above with its own seven vectors, in HBM (uploaded when the list changes)
+  ta.cameras = nullptr;
+  ta.pixels_per_camera = 0;
+  if (job.camera_table) {
+    if (!ctx->cameras_uploaded) {
+      std::vector<BlCameraDevice> table(ctx->cameras.size(), cam);
+      for (size_t c = 0; c < table.size(); c++) {
+        const bl_camera_frame &f = ctx->cameras[c].frame;
+        for (int mu = 0; mu < 4; mu++) {
+          table[c].cam_x[mu] = f.cam_x[mu];
+          table[c].u_con[mu] = f.u_con[mu];
+          table[c].u_cov[mu] = f.u_cov[mu];
+          table[c].norm_con[mu] = f.norm_con[mu];
+          table[c].norm_con_c[mu] = f.norm_con_c[mu];
+          table[c].hor_con_c[mu] = f.hor_con_c[mu];
+          table[c].vert_con_c[mu] = f.vert_con_c[mu];
+        }
+      }
+      ctx->d_cameras.Ensure(table.size());
+      Check(hipMemcpy(ctx->d_cameras.ptr, table.data(), table.size() * sizeof(BlCameraDevice), hipMemcpyHostToDevice), "camera table upload");
+      ctx->cameras_uploaded = true;
+    }
+    ta.cameras = ctx->d_cameras.ptr;
+    ta.pixels_per_camera = static_cast<long long>(p.camera_resolution) * p.camera_resolution;
+  }
 }
 
 // Power-law and kappa-distribution constants of the coefficient formulas (simulation_coefficients.cpp:54-193); pow / exp / log
@@ -1822,6 +1882,9 @@ void BuildTransferArgs(RenderJob &job) {
       xa.cam_u_cov[mu] = ctx->frame.u_cov[mu];
       xa.cam_vert_con_c[mu] = ctx->frame.vert_con_c[mu];
     }
+    xa.cameras = job.ta.cameras;   // (several cameras: each ray's own - BuildTraceArgs made the table)
+    xa.pixel_map = job.ta.pixel_map;
+    xa.pixels_per_camera = job.ta.pixels_per_camera;
   }
 }
 
@@ -2406,6 +2469,7 @@ void FinishStats(RenderJob &job) {
   st.composed_maps = job.composed ? 1 : 0;
   st.xcd_order = job.xcd_order ? 1 : 0;
   st.local_angles = job.local_angles ? 1 : 0;
+  st.n_cameras = job.n_cameras;
   st.tail_policy = job.reuse ? ctx->resident.tail_policy : (job.park ? BL_TAIL_QUAD : (job.split_long ? BL_TAIL_SPLIT : BL_TAIL_WIDE));
   ctx->stats = st;
   if (ctx->debug_counters) {   // kernels built with -DBL_GEO_STATS fill these

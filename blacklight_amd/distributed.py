@@ -323,6 +323,8 @@ def render_level(ctx, comm, level=0, block_locs=None, want_camera=False, tile=No
     the other ranks. The per-rank "geodesics terminate unexpectedly" warnings are replaced by one with the level's totals.
     A failure on any rank (a refusal that depends on the rank's own rays, a full record buffer, no memory) is agreed on
     before the first data collective and raised on every rank (RankError)."""
+    if getattr(ctx, "num_cameras", 0) >= 2:   # (every rank alike, before any collective; render_tiled and render_adaptive come through here)
+        raise ValueError("distributed renders tile one camera over the ranks: not with two or more cameras (Context.set_cameras)")
     rank, world = comm.rank, comm.world
     bs = int(ctx.params.get("adaptive_block_size") or 1) if int(ctx.params.get("adaptive_max_level") or 0) > 0 else 1
     if level == 0:

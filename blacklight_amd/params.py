@@ -24,6 +24,7 @@ class Params:
         L.bl_params_clear(self._buf)
         self._sweep = _capi.Sweep()   # the sweep_* keys: lists beside the block (bl_sweep), never in it
         self._sweep_cuts = _capi.SweepCuts()   # ... sweep_cut_sigma_max (bl_sweep_cuts)
+        self._sweep_cameras = _capi.SweepCameras()   # ... sweep_camera_th, sweep_camera_ph (bl_sweep_cameras)
         self.num_runs = 1
 
     @property
@@ -36,8 +37,8 @@ class Params:
         self = cls()
         err = C.create_string_buffer(1024)
         runs = C.c_int(1)
-        rc = _capi.lib().bl_params_read_file_sweeps(self._buf, C.byref(self._sweep), C.byref(self._sweep_cuts), str(path).encode(), C.byref(runs), err,
-                                                    len(err))
+        rc = _capi.lib().bl_params_read_file_sweeps_cameras(self._buf, C.byref(self._sweep), C.byref(self._sweep_cuts), C.byref(self._sweep_cameras),
+                                                            str(path).encode(), C.byref(runs), err, len(err))
         if rc != 0:
             raise _capi.BlacklightError(rc, err.value.decode())
         self.num_runs = runs.value
@@ -59,7 +60,8 @@ class Params:
 
     def set_line(self, line):
         err = C.create_string_buffer(1024)
-        rc = _capi.lib().bl_params_set_line_sweeps(self._buf, C.byref(self._sweep), C.byref(self._sweep_cuts), line.encode(), err, len(err))
+        rc = _capi.lib().bl_params_set_line_sweeps_cameras(self._buf, C.byref(self._sweep), C.byref(self._sweep_cuts), C.byref(self._sweep_cameras),
+                                                           line.encode(), err, len(err))
         if rc != 0:
             raise _capi.BlacklightError(rc, err.value.decode())
 
@@ -76,6 +78,7 @@ class Params:
         C.memmove(other._buf, self._buf, len(self._buf))
         C.memmove(C.byref(other._sweep), C.byref(self._sweep), C.sizeof(_capi.Sweep))
         C.memmove(C.byref(other._sweep_cuts), C.byref(self._sweep_cuts), C.sizeof(_capi.SweepCuts))
+        C.memmove(C.byref(other._sweep_cameras), C.byref(self._sweep_cameras), C.sizeof(_capi.SweepCameras))
         other.num_runs = self.num_runs
         return other
 
@@ -107,8 +110,35 @@ class Params:
         return [float(x) for x in self._sweep_cuts.sigma_max[:self._sweep_cuts.n_sigma_max]]
 
     @property
+    def sweep_camera_lists(self):
+        """The bl_sweep_cameras filled by sweep_camera_th / sweep_camera_ph (what Context applies beside the sweep: bl_apply_sweeps_cameras)."""
+        return self._sweep_cameras
+
+    @property
+    def sweep_camera_th(self):
+        return [float(x) for x in self._sweep_cameras.th[:self._sweep_cameras.n_th]]
+
+    @property
+    def sweep_camera_ph(self):
+        return [float(x) for x in self._sweep_cameras.ph[:self._sweep_cameras.n_ph]]
+
+    @property
+    def sweep_cameras(self):
+        """The cameras sweep_camera_th / sweep_camera_ph mean (bl_sweep_cameras_resolve): a list of (th, ph) in degrees, None for an
+        angle that is the parameter block's own (a key that is absent); [] without the keys. Raises BlacklightError where the lists
+        do not fit each other."""
+        n, th_given, ph_given = C.c_int(0), C.c_int(0), C.c_int(0)
+        th, ph = (C.c_double * _capi.BL_MAX_SWEEP)(), (C.c_double * _capi.BL_MAX_SWEEP)()
+        err = C.create_string_buffer(1024)
+        rc = _capi.lib().bl_sweep_cameras_resolve(C.byref(self._sweep_cameras), C.byref(n), th, ph, C.byref(th_given), C.byref(ph_given), err, len(err))
+        if rc != 0:
+            raise _capi.BlacklightError(rc, err.value.decode())
+        return [(float(th[c]) if th_given.value else None, float(ph[c]) if ph_given.value else None) for c in range(n.value)]
+
+    @property
     def has_sweep(self):
-        return self._sweep.n_rat_low > 0 or self._sweep.n_rat_high > 0 or self._sweep.n_rho_cgs > 0 or self._sweep_cuts.n_sigma_max > 0
+        return (self._sweep.n_rat_low > 0 or self._sweep.n_rat_high > 0 or self._sweep.n_rho_cgs > 0 or self._sweep_cuts.n_sigma_max > 0
+                or self._sweep_cameras.n_th > 0 or self._sweep_cameras.n_ph > 0)
 
     def resolved_sweep(self):
         """The lists as the setters receive them (bl_sweep_resolve): (polarized, rat_low, rat_high, rho_cgs). A polarized block's

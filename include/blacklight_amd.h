@@ -214,6 +214,28 @@ typedef struct bl_sweep_cuts {
 BL_API int bl_params_set_line_sweeps(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, const char *line, char *err, size_t err_len);
 BL_API int bl_params_read_file_sweeps(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, const char *path, int *num_runs, char *err, size_t err_len);
 
+/* The fifth and sixth key, in a third struct beside the two above (whose sizes are part of the ABI):
+ *     sweep_camera_th = 17, 60, 163     cameras (bl_set_cameras): camera_th values in degrees - a list of (th, ph) pairs, not a product
+ *     sweep_camera_ph = 0, 0, 90        camera_ph values: the same length, or one entry (every th at that ph), or absent (every th at
+ *                                       the block's camera_ph); ph without th: the block's camera_th at each ph
+ * The same list forms and error texts with the key's name, and two of their own: "Invalid angle (<text>) in list (<key>) in input
+ * file: must be finite." and - at the end of bl_params_read_file*, in bl_sweep_cameras_resolve and in bl_apply_sweeps_cameras -
+ * "sweep_camera_ph must have one entry or as many as sweep_camera_th (<n_ph> and <n_th>) in input file." Every call above accepts
+ * and validates the keys and drops their values; the two below keep them (any of sweep, cuts, cameras may be NULL: dropped). */
+typedef struct bl_sweep_cameras {
+  int32_t n_th, n_ph;
+  double th[BL_MAX_SWEEP], ph[BL_MAX_SWEEP];
+} bl_sweep_cameras;
+BL_API int bl_params_set_line_sweeps_cameras(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_cameras *cameras, const char *line,
+                                             char *err, size_t err_len);
+BL_API int bl_params_read_file_sweeps_cameras(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_cameras *cameras, const char *path,
+                                              int *num_runs, char *err, size_t err_len);
+/* The cameras the two lists mean: *n of them (0: neither key given), th_deg[c] and ph_deg[c] filled for the angles the lists give
+ * (arrays of BL_MAX_SWEEP), *th_given / *ph_given = 0 where that angle is the parameter block's own for every camera. Any output may
+ * be NULL. */
+BL_API int bl_sweep_cameras_resolve(const bl_sweep_cameras *cameras, int *n, double *th_deg, double *ph_deg, int *th_given, int *ph_given,
+                                    char *err, size_t err_len);
+
 /* ------------------------------------------------------------------ grid view
  * What RadiationIntegrator::ObtainGridData() takes from SimulationReader
  * (simulation_sampling.cpp:26-95). All pointers are host pointers borrowed for the duration of
@@ -340,6 +362,7 @@ typedef struct bl_stats {
   int32_t xcd_order;          /* 1: the rays were traced and their records shaded in the trace order per XCD (BL_SWITCH_FLAT_ORDER: 0) */
   int32_t local_angles;       /* 1: bl_shade_fused2_kernel took theta and phi relative to the centre of the guessed cell; 0: acos / atan2
                                  (angular cells beyond the series' reach, a mesh with refinement, BL_SWITCH_GLOBAL_ANGLES, another kernel) */
+  int32_t n_cameras;          /* cameras the last bl_render traced as one set of rays (bl_set_cameras): max(1, n) */
   /* Several electron models (bl_set_electron_models) where they cannot share one pass: launches_shade / launches_transfer count one
      shading pass per model and chunk; n_gathers, n_deferred and the sample counts are those of one pass (every pass has the same
      samples); ms_shade runs from the first coefficient kernel to the last one, ms_transfer is the last transfer kernel's. */
@@ -494,6 +517,37 @@ BL_API int bl_num_polarized_variants(const bl_ctx *ctx);   /* 0 = unset: the par
 #define BL_MAX_SIGMA_CUTS 16
 BL_API int bl_set_sigma_cuts(bl_ctx *ctx, int n, const double *sigma_max);
 BL_API int bl_num_sigma_cuts(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own cut_sigma_max; -1: no context */
+/* Cameras (viewing angles: camera_th, camera_ph) rendered by one bl_render - the third axis of a model library beside snapshots and
+ * plasma variants. n = 0 (what a context starts with): the parameter block's own camera. 1 <= n <= BL_MAX_CAMERAS: n (th, ph) pairs in
+ * DEGREES, as camera_th and camera_ph are written in the .input file, converted exactly as those two keys are (val * pi / 180;
+ * camera_pole for a written th of exactly 0 or 180). Camera c's frame is the frame bl_init builds from the context's parameters with
+ * those three fields replaced (bl_camera_frame_get_camera). bl_init refuses no value of camera_th or camera_ph, so neither does this call.
+ * With C = max(1, n) a full root-level render has n_rays = C * res^2: ray, output index and "virtual pixel" v = c * res^2 + m are one
+ * number, m the reference's pixel index within camera c. Every per-ray output is indexed by v - image[row][v], sample_num, sample_flags,
+ * camera_pos / camera_dir, renderings, on the host or the device. bl_image_num_quantities does not change: cameras multiply rays, not
+ * rows (rows stay variant-major under every variant setter). pixel_map entries are virtual pixels (BL_E_ARG outside 0 .. C * res^2 - 1,
+ * checked while a camera list is set), and n_rays is checked against C * res^2. n = 1 renders that camera and plans exactly as a
+ * context whose block holds those angles (bl_camera_frame_get then returns that camera's frame).
+ * In the exact tier and under bl_set_reproducible the slice [:, c res^2 : (c + 1) res^2] of every output is bit for bit what a context
+ * renders that bl_init made with camera c's angles in its block, whatever the chunking; with composed maps every integer output and
+ * NaN mask is that render's and every finite pixel lies within the tier's per-pixel bound of it. The cameras are ONE set of rays:
+ * bl_stats.launches_geodesic = n_chunks whatever C is, the rays are traced 8 x 8 tile by tile with the cameras interleaved (tile t of
+ * every camera, then the next tile, each camera's tiles centre first). With n >= 2 the trace order per XCD stays off
+ * (bl_stats.xcd_order = 0) and BL_TAIL_SPLIT resolves to BL_TAIL_WIDE (bl_stats.tail_policy) - both change speed only. The reference's
+ * warning about geodesics that terminate unexpectedly is raised once per render and carries the totals over all cameras ("k out of
+ * M", M = C * res^2). The camera list is part of what "the same camera" means for bl_set_geodesic_reuse: another list integrates
+ * again, the same list after bl_set_grid shades the resident records (bl_stats.geodesics_reused = 1).
+ * BL_E_ARG: a non-finite angle (with the camera's index), n outside 0 .. BL_MAX_CAMERAS, a null array with n > 0. Refused
+ * (BL_E_UNSUPPORTED): with n >= 1 checkpoint_geodesic_load (the file carries its own camera); with n >= 2 adaptive_max_level > 0,
+ * slow light, checkpoint_geodesic_save, checkpoint_sample_save, and the three settings whose kernels read the one camera position of
+ * their argument block: cut_omit_near, cut_omit_far and image_crossings - as are bl_adaptive_refine, bl_write_output and
+ * bl_write_output_variant while n >= 2 (the reference's file holds one camera). A refused call changes nothing. Works on a
+ * BL_DEVICE_NONE context. */
+#define BL_MAX_CAMERAS 16
+BL_API int bl_set_cameras(bl_ctx *ctx, int n, const double *th_deg, const double *ph_deg);
+BL_API int bl_num_cameras(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own camera; -1: no context */
+/* The frame of camera `camera` of the list (0 .. max(1, n) - 1; with no list, camera 0 is the parameter block's). */
+BL_API int bl_camera_frame_get_camera(const bl_ctx *ctx, int camera, bl_camera_frame *out);
 /* The sweep of a .input file onto a context: bl_sweep_resolve against the context's parameters, then bl_set_polarized_variants
  * (polarized) or bl_set_electron_models and / or bl_set_density_units - one rule for the command-line driver, a bound reference
  * main() and Python. An empty sweep makes no call (what the context holds stays). On failure (bl_last_error: the resolver's text or
@@ -502,6 +556,13 @@ BL_API int bl_apply_sweep(bl_ctx *ctx, const bl_sweep *sweep);
 /* ... and with the sigma cuts of the file (bl_set_sigma_cuts after the calls above; cuts may be NULL or empty: bl_apply_sweep). On
  * failure the context holds no model, unit or cut the call brought. */
 BL_API int bl_apply_sweeps(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts);
+/* ... and with the cameras of the file (bl_set_cameras after the calls above, an angle a list does not give being the parameter
+ * block's own, to the bit; cameras may be NULL or empty: bl_apply_sweeps). On failure the context holds no model, unit, cut or camera
+ * the call brought. */
+BL_API int bl_apply_sweeps_cameras(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts, const bl_sweep_cameras *cameras);
+/* The angles of the camera list as given, in degrees (an angle taken from the parameter block: its radians x 180 / pi): the first
+ * min(n, bl_num_cameras) entries of both arrays. */
+BL_API int bl_cameras_get(const bl_ctx *ctx, int n, double *th_deg, double *ph_deg);
 /* Images one bl_render produces: max(1, electron models) * max(1, density units) * max(1, sigma cuts) * max(1, polarized variants)
  * - a polarized variant's own sigma cut (bl_set_polarized_variants_sigma) is part of the variant and adds no image; -1: no context. */
 BL_API int bl_num_variants(const bl_ctx *ctx);
@@ -689,6 +750,19 @@ BL_API int bl_write_output_variant(bl_ctx *ctx, const char *path_override, const
  * image.npz -> image.m00u00.npz, image.m00u01.npz, ... image.m02u01.npz: names sort in variant order. V = 1: no tag.
  * BL_E_ARG: variant outside 0 .. V - 1, or buf too short; BL_E_MISSING / BL_E_INPUT as bl_write_output. */
 BL_API int bl_variant_output_path(bl_ctx *ctx, int snapshot, int variant, char *buf, size_t len);
+
+/* One camera (and variant) of a render of several cameras as a file of the reference's layout. d->level[0] holds what bl_render
+ * wrote for all C = max(1, bl_num_cameras) cameras: image [V * n_q][C * res^2], camera records [C * res^2][4], renderings
+ * [render_num_images][3][C * res^2]. The file is, byte for byte in all three formats, what bl_write_output writes in a context with
+ * that camera's angles (and that variant's values) in its parameter block from the camera's slice [c res^2, (c + 1) res^2) of every
+ * row and record (a camera's rows are gathered into one block before they are written: they do not lie side by side in the
+ * caller's arrays). BL_E_ARG: camera outside 0 .. C - 1, variant outside 0 .. V - 1, adaptive levels with C >= 2. C = 1: the call is
+ * bl_write_output_variant. Works on a BL_DEVICE_NONE context. Name: path_override if given, else bl_camera_output_path. */
+BL_API int bl_write_output_camera(bl_ctx *ctx, const char *path_override, const bl_output_desc *d, int camera, int variant);
+/* The name bl_write_output_camera gives the file: bl_variant_output_path's, with - when C >= 2 - the camera's tag .cCC (two digits,
+ * from 00) in front of the variant's tag inside the same dot group: image.c01.npz, image.c01m00u02.npz, image.c01m00u02s03.npz,
+ * image.c01v03.npz; names sort in (camera, variant) order. C = 1: no camera tag. */
+BL_API int bl_camera_output_path(bl_ctx *ctx, int snapshot, int camera, int variant, char *buf, size_t len);
 
 /* Library self-description: "gfx950;hip" etc. Lets a loader verify the HIP path is the one built. */
 BL_API const char *bl_build_info(void);
