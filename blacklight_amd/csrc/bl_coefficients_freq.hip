@@ -40,7 +40,7 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
     if (ray == BL_DEAD_RAY) continue;
     const uint32_t n = (uint32_t)(tag >> 32);
     const BlCoefInputs ci = P.coef_inputs[idx];
-    const double momentum_factor = P.ray_factor[ray];
+    const double momentum_factor = bl_ray_factor(P.ray_constants, (size_t)ray);
     SampleShade sh;
     sh.have_coefficients = ci.have_coefficients != 0.0;
     sh.nu_fluid_over_nu = ci.nu_fluid_over_nu;
@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(256, 4) bl_coefficients_freq_kernel(const BlSh
     if (ray == BL_DEAD_RAY) continue;
     const uint32_t n = (uint32_t)(tag >> 32);
     const BlCoefInputs ci = P.coef_inputs[idx];
-    const double momentum_factor = P.ray_factor[ray];
+    const double momentum_factor = bl_ray_factor(P.ray_constants, (size_t)ray);
     SampleShade sh;
     sh.have_coefficients = ci.have_coefficients != 0.0;
     sh.nu_fluid_over_nu = ci.nu_fluid_over_nu;

@@ -287,11 +287,11 @@ struct bl_ctx {
   ChunkSlot slot[2];
   // per ray of a bl_render call (indexed by traversal position; a chunk's kernels get pointers to its first ray): the arrays set aside with the resident records
   struct RayArrays {
-    DeviceBuffer<double> kt, factor;
+    DeviceBuffer<double2> constants;   // (k_t, momentum factor): BlTraceArgs::ray_constants
     DeviceBuffer<int> sample_num, skipped, rows;
     DeviceBuffer<unsigned char> flags;
     DeviceBuffer<long long> out_index, offset;
-    uint64_t Bytes() const { return kt.Bytes() + factor.Bytes() + sample_num.Bytes() + skipped.Bytes() + rows.Bytes() + flags.Bytes() + out_index.Bytes() + offset.Bytes(); }
+    uint64_t Bytes() const { return constants.Bytes() + sample_num.Bytes() + skipped.Bytes() + rows.Bytes() + flags.Bytes() + out_index.Bytes() + offset.Bytes(); }
   };
   // bl_set_geodesic_reuse: the root level's geodesics as its last render left them (in one chunk, or in the kept layout below). The
   // buffers are the ones scratch set 0 and the

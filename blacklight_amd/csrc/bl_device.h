@@ -297,7 +297,7 @@ struct BlTraceArgs {
   // Rays it did not get to (BL_CNT_NEXT_RAY < chunk_rays at the end) are the next chunk's.
   long long record_gate;
   unsigned long long *counters;
-  double *ray_kt, *ray_factor;
+  double2 *ray_constants;     // [chunk_rays]: (k_t, momentum factor), written once at ray start (read: bl_ray_constants and its two halves)
   int *ray_sample_num;
   unsigned char *ray_flags;
   long long *ray_out_index;
@@ -488,7 +488,7 @@ struct BlShadeArgs {
   unsigned long long *xcd_state;
   const unsigned int *xcd_lists;
   long long xcd_list_capacity;
-  const double *ray_kt, *ray_factor;
+  const double2 *ray_constants;   // [chunk_rays]: (k_t, momentum factor) of BlTraceArgs::ray_constants
   const long long *ray_offset;   // [chunk_rays]: sample n of ray q has row ray_offset[q] + n in transfer, aux, pol_samples, freq_inputs, ...
   const double *frequencies;  // device [n_nu]
   int n_nu;
@@ -581,13 +581,17 @@ struct BlTransferArgs {
   // auxiliary-image mode only
   BlAuxImages aux_images;
   const BlAuxSample *aux;
-  const double *ray_factor;
+  const double2 *ray_constants;
   double x_unit, t_unit;
   const BlRenderDevice *render_params;   // device, or null
   double *render;                        // [n_images][3][n_rays_total], or null
 };
 
 #if defined(__HIPCC__) || defined(__HIP__)
+// A ray's constants (BlTraceArgs::ray_constants): both in one 16-byte read where a kernel wants both, or the one it wants
+__device__ __forceinline__ double2 bl_ray_constants(const double2 *rays, size_t ray) { return rays[ray]; }
+__device__ __forceinline__ double bl_ray_kt(const double2 *rays, size_t ray) { return rays[ray].x; }
+__device__ __forceinline__ double bl_ray_factor(const double2 *rays, size_t ray) { return rays[ray].y; }
 // Rays of a chunk the geodesic kernel traced: the rays after them did not fit the record buffers and go to the next chunk
 __device__ __forceinline__ int bl_rays_done(const unsigned long long *counters, int chunk_rays) {
   const unsigned long long taken = counters[BL_CNT_NEXT_RAY];

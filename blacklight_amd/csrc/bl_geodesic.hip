@@ -85,8 +85,7 @@ __device__ __forceinline__ void bl_start_ray(const BlTraceArgs &P, const BlSpace
   double u_ind, v_ind, position[4], direction[4], factor;
   bl_pixel_indices(cam, pixel, P.block_locs, &u_ind, &v_ind);
   bl_pixel_ray(st, cam, u_ind, v_ind, position, direction, &factor);
-  P.ray_kt[q] = direction[0];
-  P.ray_factor[q] = factor;
+  P.ray_constants[q] = make_double2(direction[0], factor);
   P.ray_out_index[q] = ray;
   if (P.camera_pos != nullptr)
     for (int mu = 0; mu < 4; mu++) P.camera_pos[4 * ray + mu] = position[mu];

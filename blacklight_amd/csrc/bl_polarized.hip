@@ -484,7 +484,7 @@ __global__ void __launch_bounds__(64) bl_transfer_polarized_kernel(BlTransferArg
   const BlSpacetime st = P.st;
   const int num = P.ray_sample_num[slot];
   const long long out_index = P.ray_out_index[slot];
-  const double momentum_factor = P.ray_factor[slot];
+  const double momentum_factor = bl_ray_factor(P.ray_constants, (size_t)slot);
   const size_t row = (size_t)P.n_rays_total;
   double *img = P.image + out_index + (size_t)variant * P.pol_variant_rows * row;
   const BlPolSample *samples = P.pol_samples + (size_t)P.ray_offset[slot];
@@ -971,7 +971,7 @@ __global__ void __launch_bounds__(64, 2) bl_transfer_polarized_matrix_kernel(BlT
   const BlSpacetime st = P.st;
   const int num = P.ray_sample_num[slot];
   const long long out_index = P.ray_out_index[slot];
-  const double momentum_factor = P.ray_factor[slot];
+  const double momentum_factor = bl_ray_factor(P.ray_constants, (size_t)slot);
   const size_t row = (size_t)P.n_rays_total;
   double *img = P.image + out_index + (size_t)variant * P.pol_variant_rows * row;
   const BlPolSample *samples = P.pol_samples + (size_t)P.ray_offset[slot];

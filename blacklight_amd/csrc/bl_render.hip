@@ -1266,7 +1266,7 @@ void EnsureScratchOnce(RenderJob &job) {
   }
   const size_t n_rays = static_cast<size_t>(job.n_rays);
   auto ensure = [n_rays](auto &...buffer) { (buffer.Ensure(n_rays), ...); };
-  ensure(ctx->rays.kt, ctx->rays.factor, ctx->rays.sample_num, ctx->rays.flags, ctx->rays.out_index, ctx->rays.offset);
+  ensure(ctx->rays.constants, ctx->rays.sample_num, ctx->rays.flags, ctx->rays.out_index, ctx->rays.offset);
   if (job.skip_shell) ctx->rays.skipped.Ensure(n_rays);
   if (job.composed) ctx->rays.rows.Ensure(n_rays);
   if (!job.geo_load) ctx->d_ray_start.Ensure(n_rays * BL_RAY_START_FIELDS);
@@ -1918,8 +1918,7 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   ta.record_capacity = static_cast<long long>(job.chunk_capacity);
   ta.record_gate = job.chunk_gate;
   ta.counters = sl.d_counters.ptr;
-  ta.ray_kt = ctx->rays.kt.ptr + begin;
-  ta.ray_factor = ctx->rays.factor.ptr + begin;
+  ta.ray_constants = ctx->rays.constants.ptr + begin;
   ta.ray_sample_num = ctx->rays.sample_num.ptr + begin;
   ta.ray_skipped = job.skip_shell ? ctx->rays.skipped.ptr + begin : nullptr;
   ta.segment_rows = job.composed ? 1 : 0;
@@ -1955,8 +1954,7 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   sa.freq_inputs = use.freq_inputs ? sl.d_freq_inputs.ptr : nullptr;
   sa.counters_in = sl.d_counters.ptr;
   sa.counters = sl.d_counters.ptr;
-  sa.ray_kt = ta.ray_kt;
-  sa.ray_factor = ta.ray_factor;
+  sa.ray_constants = ta.ray_constants;
   sa.ray_offset = ta.ray_offset;
   sa.ray_flags = ta.ray_flags;
   sa.transfer = use.pol ? nullptr : sl.d_transfer.ptr;   // (with per-sample factors instead: whatever an earlier render left, never read)
@@ -1987,7 +1985,7 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   xa.ray_flags = ta.ray_flags;
   xa.ray_out_index = ta.ray_out_index;
   xa.ray_offset = ta.ray_offset;
-  xa.ray_factor = ta.ray_factor;
+  xa.ray_constants = ta.ray_constants;
   xa.stats = sl.d_counters.ptr + BL_CNT_COUNT;
   xa.aux = sa.aux;
   if (use.pol) {
@@ -2011,8 +2009,9 @@ long long LoadChunkFromCheckpoint(RenderJob &job, int k, long long begin, int ra
   upload(sl.d_records_hot.ptr, chunk.hot);
   upload(sl.d_records_cold.ptr, chunk.cold);
   upload(sl.d_sample_t.ptr, chunk.sample_t);
-  upload(ctx->rays.kt.ptr + begin, chunk.kt);
-  upload(ctx->rays.factor.ptr + begin, chunk.factor);
+  std::vector<double2> constants(chunk.kt.size());   // (the files keep k_t and the momentum factor as two arrays)
+  for (size_t q = 0; q < constants.size(); q++) constants[q] = make_double2(chunk.kt[q], chunk.factor[q]);
+  upload(ctx->rays.constants.ptr + begin, constants);
   upload(ctx->rays.sample_num.ptr + begin, chunk.sample_num);
   upload(ctx->rays.flags.ptr + begin, chunk.flags);
   upload(ctx->rays.out_index.ptr + begin, chunk.out_index);
@@ -2037,8 +2036,14 @@ void SaveChunk(RenderJob &job, int k, long long begin, long long done) {
   unsigned long long n_written = 0;
   Check(hipMemcpy(&n_written, sl.d_counters.ptr + BL_CNT_RECORDS, sizeof n_written, hipMemcpyDeviceToHost), "checkpoint download");
   HostChunk chunk;
-  DownloadRows(&chunk.kt, ctx->rays.kt.ptr + begin, done);
-  DownloadRows(&chunk.factor, ctx->rays.factor.ptr + begin, done);
+  std::vector<double2> constants;   // (the files keep k_t and the momentum factor as two arrays)
+  DownloadRows(&constants, ctx->rays.constants.ptr + begin, done);
+  chunk.kt.resize(constants.size());
+  chunk.factor.resize(constants.size());
+  for (size_t q = 0; q < constants.size(); q++) {
+    chunk.kt[q] = constants[q].x;
+    chunk.factor[q] = constants[q].y;
+  }
   DownloadRows(&chunk.sample_num, ctx->rays.sample_num.ptr + begin, done);
   DownloadRows(&chunk.flags, ctx->rays.flags.ptr + begin, done);
   DownloadRows(&chunk.out_index, ctx->rays.out_index.ptr + begin, done);

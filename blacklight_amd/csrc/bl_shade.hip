@@ -102,8 +102,9 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
     double momentum_factor = 0.0;
     size_t row = 0;   // of this sample in the per-sample arrays: the ray's first row + n
     if (live) {
-      kcov[0] = P.ray_kt[ray];
-      momentum_factor = P.ray_factor[ray];
+      const double2 constants = bl_ray_constants(P.ray_constants, (size_t)ray);
+      kcov[0] = constants.x;
+      momentum_factor = constants.y;
       row = (size_t)P.ray_offset[ray] + n;
       if (kRedo && P.composed != nullptr) row = (size_t)idx_cur;   // composed transfer maps: per-sample records lie by record index
     }
@@ -322,7 +323,8 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact_kernel(const BlShadeArg
     // (a dead slot has tag 0 = kSampleNone from the locate kernel; a stage without a sample reads the last record's slot)
     const int status = live ? (int)(loc_prev.tag >> 32) : (int)kSampleNone;
     // per-ray constants of `prev`: requested before the next sample's cells
-    const double kt = P.ray_kt[live ? ray : 0u], momentum_factor = P.ray_factor[live ? ray : 0u];
+    const double2 constants = bl_ray_constants(P.ray_constants, live ? ray : 0u);
+    const double kt = constants.x, momentum_factor = constants.y;
     const uint32_t row = (uint32_t)P.ray_offset[live ? ray : 0u] + n;   // (rows are record counts: 32 bits as well)
     float pr[8];
     gather_finish(P, fallback_rho, fallback_pgas, status, lo, hi, loc_prev.l0.x, loc_prev.l0.y, loc_prev.l1.x, pr);

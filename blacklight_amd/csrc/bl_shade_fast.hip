@@ -421,7 +421,8 @@ __global__ void __launch_bounds__(256, BL_FAST_WAVES) bl_shade_fast_kernel(const
     const uint32_t n = (uint32_t)(((unsigned long long)__double_as_longlong(ray_prev.q1.y)) >> 32);
     const int status = (int)(loc_prev.tag >> 32) & 0xff;
     // per-ray constants of `prev`: requested before the next sample's cells, so that waiting for them does not wait for those
-    const double kt = P.ray_kt[live ? ray : 0u], momentum_factor = P.ray_factor[live ? ray : 0u];
+    const double2 constants = bl_ray_constants(P.ray_constants, live ? ray : 0u);
+    const double kt = constants.x, momentum_factor = constants.y;
     const size_t row = (size_t)P.ray_offset[live ? ray : 0u] + n;
     float pr[8];
     const bool on_slices = kSlices && slow_pipelined && live && (status == kSampleInterp || status == kSampleNearest);
@@ -504,7 +505,8 @@ __global__ void __launch_bounds__(256, 4) bl_shade_formula_fast_kernel(const BlS
     const double x = rec.q0.x, y = rec.q0.y, z = rec.q1.x;
     double kx = rec.q2.x, ky = rec.q2.y, kz = rec.q3.x;
     const double delta_lambda = -rec.q3.y;   // ReverseGeodesics: sample_len = -geodesic_len (geodesics.cpp:840)
-    const double kt = P.ray_kt[ray], momentum_factor = P.ray_factor[ray];
+    const double2 constants = bl_ray_constants(P.ray_constants, ray);
+    const double kt = constants.x, momentum_factor = constants.y;
     double2 *out = P.transfer + ((size_t)P.ray_offset[ray] + n) * P.n_nu;
     // ---- Kerr-Schild scalars
     const double pp2 = x * x + y * y, rr2 = pp2 + z * z;

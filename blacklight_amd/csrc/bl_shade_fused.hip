@@ -864,7 +864,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   const bool fallback_nan = P.plasma.fallback_nan != 0;
   const char *cells = reinterpret_cast<const char *>(P.grid.cells);
   const uint32_t row_bytes = (uint32_t)P.grid.stride_row * 32u, plane_bytes = (uint32_t)P.grid.stride_plane * 32u;
-  const char *ray_kt = reinterpret_cast<const char *>(P.ray_kt), *ray_factor = reinterpret_cast<const char *>(P.ray_factor);
+  const double2 *ray_constants = P.ray_constants;
   const char *ray_offset = reinterpret_cast<const char *>(P.ray_offset);
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   unsigned long long gathers_wave = 0ull;   // (wave-uniform: counted with ballots)
@@ -1010,13 +1010,14 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
       c.c0 = rec[2];
       c.c1 = rec[3];
     }
-    // ... and its per-ray constants (random 8-byte reads: a whole iteration ahead of their use, like the cells)
+    // ... and its per-ray constants (random reads, one of 16 bytes and one of 8: a whole iteration ahead of their use, like the cells)
     {
       const uint32_t ray_cur = (uint32_t)__double_as_longlong(c.h1.y);
-      const uint32_t ray_bytes = (ray_cur != BL_DEAD_RAY ? ray_cur : 0u) << 3;
-      c.kt = *reinterpret_cast<const double *>(ray_kt + (size_t)ray_bytes);
-      c.factor = *reinterpret_cast<const double *>(ray_factor + (size_t)ray_bytes);
-      c.row = *reinterpret_cast<const long long *>(ray_offset + (size_t)ray_bytes);
+      const uint32_t ray_slot = ray_cur != BL_DEAD_RAY ? ray_cur : 0u;
+      const double2 constants = bl_ray_constants(ray_constants, (size_t)ray_slot);
+      c.kt = constants.x;
+      c.factor = constants.y;
+      c.row = *reinterpret_cast<const long long *>(ray_offset + (size_t)(ray_slot << 3));
     }
     // ---- arithmetic of `prev` (ReverseGeodesics: sample_len = -geodesic_len, geodesics.cpp:840)
     // (Inside a branch - taken by every wave that holds a sample on the grid - not for the lanes it skips: a basic block is the
@@ -1329,7 +1330,7 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
   const float fallback_rho = P.cold->fallback_rho, fallback_pgas = P.cold->fallback_pgas;
   const char *cells = reinterpret_cast<const char *>(P.grid.cells);
   const uint32_t row_bytes = (uint32_t)P.grid.stride_row * 32u, plane_bytes = (uint32_t)P.grid.stride_plane * 32u;
-  const char *ray_kt = reinterpret_cast<const char *>(P.ray_kt), *ray_factor = reinterpret_cast<const char *>(P.ray_factor);
+  const double2 *ray_constants = P.ray_constants;
   const char *ray_offset = reinterpret_cast<const char *>(P.ray_offset);
   unsigned long long gathers_wave = 0ull;
   const double freq = uniform_value(P.frequencies[0]);
@@ -1385,10 +1386,11 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
     }
     {
       const uint32_t ray_cur = (uint32_t)__double_as_longlong(cur1.y);
-      const uint32_t ray_bytes = (ray_cur != BL_DEAD_RAY ? ray_cur : 0u) << 3;
-      kt_prev = *reinterpret_cast<const double *>(ray_kt + (size_t)ray_bytes);
-      factor_prev = *reinterpret_cast<const double *>(ray_factor + (size_t)ray_bytes);
-      row_prev = *reinterpret_cast<const long long *>(ray_offset + (size_t)ray_bytes);
+      const uint32_t ray_slot = ray_cur != BL_DEAD_RAY ? ray_cur : 0u;
+      const double2 constants = bl_ray_constants(ray_constants, (size_t)ray_slot);
+      kt_prev = constants.x;
+      factor_prev = constants.y;
+      row_prev = *reinterpret_cast<const long long *>(ray_offset + (size_t)(ray_slot << 3));
     }
     if (live) {
       // ---- bl_shade_exact_kernel's body (bl_shade.hip), call for call
@@ -1476,7 +1478,8 @@ __global__ void __launch_bounds__(256, 2) bl_shade_polarized2_kernel(const BlSha
   const bool nan_rays = P.plasma.fallback_nan != 0;
   const char *cells = reinterpret_cast<const char *>(P.grid.cells);
   const uint32_t row_bytes = (uint32_t)P.grid.stride_row * 32u, plane_bytes = (uint32_t)P.grid.stride_plane * 32u;
-  const char *ray_kt = reinterpret_cast<const char *>(P.ray_kt), *ray_offset = reinterpret_cast<const char *>(P.ray_offset);
+  const double2 *ray_constants = P.ray_constants;
+  const char *ray_offset = reinterpret_cast<const char *>(P.ray_offset);
   unsigned long long gathers_wave = 0ull;
   const char *records = reinterpret_cast<const char *>(P.records_hot);
   const uint32_t lane_index = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1532,8 +1535,13 @@ __global__ void __launch_bounds__(256, 2) bl_shade_polarized2_kernel(const BlSha
     {
       const uint32_t ray_cur = (uint32_t)__double_as_longlong(cur1.y);
       const uint32_t ray_slot = ray_cur != BL_DEAD_RAY ? ray_cur : 0u;
-      kt_prev = *reinterpret_cast<const double *>(ray_kt + (size_t)(ray_slot << 3));
-      if (kCoefficients) factor_prev = P.ray_factor[ray_slot];
+      if (kCoefficients) {
+        const double2 constants = bl_ray_constants(ray_constants, (size_t)ray_slot);
+        kt_prev = constants.x;
+        factor_prev = constants.y;
+      } else {
+        kt_prev = bl_ray_kt(ray_constants, (size_t)ray_slot);
+      }
       row_prev = *reinterpret_cast<const long long *>(ray_offset + (size_t)(ray_slot << 3));
       flag_prev = P.ray_flags[ray_slot];
     }

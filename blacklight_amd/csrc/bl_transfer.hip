@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(64) bl_transfer_aux_kernel(BlTransferArgs P) {
     if (P.out_sample_num != nullptr) P.out_sample_num[out_index] = num;
     if (P.out_flags != nullptr) P.out_flags[out_index] = flag ? 1 : 0;
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    const double momentum_factor = P.ray_factor[slot];
+    const double momentum_factor = bl_ray_factor(P.ray_constants, (size_t)slot);
     const size_t row = (size_t)P.n_rays_total;
     double *img = P.image + out_index;   // img[q * row] = image(q, pixel)
     for (int q = 0; q < A.n_q; q++) img[(size_t)q * row] = 0.0;
