@@ -53,6 +53,25 @@ class SweepCameras(C.Structure):
 BL_MAX_CAMERAS = 16
 
 
+class SweepElectrons(C.Structure):
+    """bl_sweep_electrons: the seven electron lists of a .input file (sweep_power_frac ... sweep_w), beside the three structs above."""
+    _fields_ = [("n_" + name, C.c_int32) for name in ("power_frac", "p", "gamma_min", "gamma_max", "kappa_frac", "kappa", "w")] + [("reserved", C.c_int32)] + \
+               [(name, C.c_double * BL_MAX_SWEEP) for name in ("power_frac", "p", "gamma_min", "gamma_max", "kappa_frac", "kappa", "w")]
+
+
+class SweepLists(C.Structure):
+    """bl_sweep_lists: pointers to the four structs (NULL: that struct's keys are validated and dropped)."""
+    _fields_ = [("sweep", C.POINTER(Sweep)), ("cuts", C.POINTER(SweepCuts)), ("cameras", C.POINTER(SweepCameras)), ("electrons", C.POINTER(SweepElectrons))]
+
+
+ELECTRON_MIX_KEYS = ("power_frac", "p", "gamma_min", "gamma_max", "kappa_frac", "kappa", "w")
+
+
+class ElectronMix(C.Structure):
+    """bl_electron_mix: the seven plasma_* values of an electron distribution (bl_set_polarized_variants_electrons)."""
+    _fields_ = [(name, C.c_double) for name in ELECTRON_MIX_KEYS + ("reserved",)]
+
+
 class CameraFrame(C.Structure):
     _fields_ = [(name, C.c_double * 4) for name in
                 ("cam_x", "u_con", "u_cov", "norm_con", "norm_con_c", "hor_con_c", "vert_con_c")] + \
@@ -136,6 +155,11 @@ def lib():
     L.bl_sweep_cameras_resolve.argtypes = [C.POINTER(SweepCameras), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
                                            C.c_char_p, C.c_size_t]
     L.bl_apply_sweeps_cameras.argtypes = [C.c_void_p, C.POINTER(Sweep), C.POINTER(SweepCuts), C.POINTER(SweepCameras)]
+    L.bl_params_set_line_sweep_lists.argtypes = [C.c_void_p, C.POINTER(SweepLists), C.c_char_p, C.c_char_p, C.c_size_t]
+    L.bl_params_read_file_sweep_lists.argtypes = [C.c_void_p, C.POINTER(SweepLists), C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+    L.bl_sweep_electrons_resolve.argtypes = [C.POINTER(SweepElectrons), C.POINTER(Sweep), C.c_void_p, C.POINTER(C.c_int), C.POINTER(Sweep), C.c_void_p,
+                                             C.c_char_p, C.c_size_t]
+    L.bl_apply_sweep_lists.argtypes = [C.c_void_p, C.POINTER(SweepLists)]
     L.bl_set_cameras.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.bl_num_cameras.argtypes = [C.c_void_p]
     L.bl_cameras_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -163,6 +187,8 @@ def lib():
     L.bl_set_polarized_variants.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bl_set_polarized_variants_sigma.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bl_num_polarized_variants.argtypes = [C.c_void_p]
+    L.bl_set_polarized_variants_electrons.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bl_polarized_variant_electrons.argtypes = [C.c_void_p, C.c_int, C.POINTER(ElectronMix)]
     L.bl_set_sigma_cuts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.bl_num_sigma_cuts.argtypes = [C.c_void_p]
     L.bl_host_alloc.argtypes = [C.c_void_p, C.c_size_t]

@@ -39,19 +39,22 @@ class Context:
         return cls(Params.from_file(path), device=device)
 
     def apply_sweep(self, params=None):
-        """bl_apply_sweeps: the sweep_rat_low / sweep_rat_high / sweep_rho_cgs lists of `params` (default: this context's) as electron
+        """bl_apply_sweep_lists: the sweep_rat_low / sweep_rat_high / sweep_rho_cgs lists of `params` (default: this context's) as electron
         models and density units, or as polarized triples, its sweep_cut_sigma_max list as sigma cuts and its sweep_camera_th /
         sweep_camera_ph lists as cameras (bl_apply_sweeps_cameras). An empty sweep changes nothing."""
         params = params or self.params
         if not params.has_sweep:
             return
         polarized, low, high, rho = params.resolved_sweep()
-        self._check(self._lib.bl_apply_sweeps_cameras(self._ctx, C.byref(params.sweep), C.byref(params.sweep_cuts), C.byref(params.sweep_camera_lists)))
+        if params.has_sweep_electrons:   # (polarized tuples: the triples with the electron lists' length)
+            low, high, rho, _ = params.resolved_electrons()
+        self._check(self._lib.bl_apply_sweep_lists(self._ctx, C.byref(params.sweep_lists)))
         if params.sweep_cut_sigma_max:
             self._sigma_cuts = params.sweep_cut_sigma_max
         if polarized:
             self._polarized_variants = [(h, lo, u) for h, lo, u in zip(high, low, rho)]
             self._polarized_cuts = None   # (bl_set_polarized_variants: the parameter block's cut for every triple)
+            self._polarized_electrons = params.has_sweep_electrons
         else:
             if low:
                 self._electron_models = [(h, lo) for h, lo in zip(high, low)]
@@ -342,13 +345,16 @@ class Context:
             self.set_electron_models([h for h, _ in models], rat_low=[lo_ for _, lo_ in models])
             self.set_density_units(units)
 
-    def set_polarized_variants(self, rat_high, rho_cgs, rat_low=1.0, sigma_max=None):
+    def set_polarized_variants(self, rat_high, rho_cgs, rat_low=1.0, sigma_max=None, electrons=None):
         """Render several (R_high, R_low, simulation_rho_cgs) triples of a polarized run in one render (bl_set_polarized_variants):
         a list of triples, not a product - scalars or sequences, broadcast against each other; empty sequences clear them (the
         parameter block's pair and unit again). The image then holds the variants one after another
         (render()["image_by_variant"]: (n_variants, n_q, n_rays)); geodesics stay resident.
         sigma_max: a sigma cut for every variant (bl_set_polarized_variants_sigma) - a scalar, or one cut_sigma_max value per
-        variant (a negative value switches the cut off); None: the parameter block's own cut_sigma_max for all of them."""
+        variant (a negative value switches the cut off); None: the parameter block's own cut_sigma_max for all of them.
+        electrons: an electron distribution for every variant (bl_set_polarized_variants_electrons) - one mapping, or one per variant,
+        with the keys power_frac, p, gamma_min, gamma_max, kappa_frac, kappa, w (the plasma_* keys without their prefix); a missing
+        key means the parameter block's value. None: the parameter block's own distribution for all of them."""
         high, unit, low = np.broadcast_arrays(np.atleast_1d(np.asarray(rat_high, dtype=np.float64)),
                                               np.atleast_1d(np.asarray(rho_cgs, dtype=np.float64)),
                                               np.atleast_1d(np.asarray(rat_low, dtype=np.float64)))
@@ -359,11 +365,28 @@ class Context:
             if cuts.size not in (1, high.size):
                 raise ValueError(f"set_polarized_variants: sigma_max needs a scalar or one value per variant (got {cuts.size} for {high.size} variants)")
             cuts = np.ascontiguousarray(np.broadcast_to(cuts, high.shape))
-        self._check(self._lib.bl_set_polarized_variants_sigma(self._ctx, int(high.size), low.ctypes.data_as(C.c_void_p),
-                                                              high.ctypes.data_as(C.c_void_p), unit.ctypes.data_as(C.c_void_p),
-                                                              cuts.ctypes.data_as(C.c_void_p) if cuts is not None else None))
+        mixes = None
+        if electrons is not None and high.size > 0:
+            given = [electrons] * int(high.size) if hasattr(electrons, "keys") else list(electrons)
+            if len(given) == 1:
+                given = given * int(high.size)
+            if len(given) != high.size:
+                raise ValueError(f"set_polarized_variants: electrons needs one mapping or one per variant (got {len(given)} for {high.size} variants)")
+            own = self._block_electrons()
+            mixes = (_capi.ElectronMix * int(high.size))()
+            for v, mapping in enumerate(given):
+                unknown = set(mapping) - set(_capi.ELECTRON_MIX_KEYS)
+                if unknown:
+                    raise ValueError(f"set_polarized_variants: unknown electron key(s) {sorted(unknown)}; the keys are {list(_capi.ELECTRON_MIX_KEYS)}")
+                for key in _capi.ELECTRON_MIX_KEYS:
+                    setattr(mixes[v], key, float(mapping.get(key, own[key])))
+        self._check(self._lib.bl_set_polarized_variants_electrons(self._ctx, int(high.size), low.ctypes.data_as(C.c_void_p),
+                                                                  high.ctypes.data_as(C.c_void_p), unit.ctypes.data_as(C.c_void_p),
+                                                                  cuts.ctypes.data_as(C.c_void_p) if cuts is not None else None,
+                                                                  C.cast(mixes, C.c_void_p) if mixes is not None else None))
         self._polarized_variants = [(float(h), float(lo), float(u)) for h, lo, u in zip(high, low, unit)]
         self._polarized_cuts = [float(c) for c in cuts] if cuts is not None and high.size > 0 else None
+        self._polarized_electrons = mixes is not None
 
     @property
     def polarized_variants(self):
@@ -379,6 +402,27 @@ class Context:
         under the parameter block's own cut_sigma_max."""
         held = getattr(self, "_polarized_cuts", None)
         return list(held) if held is not None else None
+
+    def _block_electrons(self):
+        """The parameter block's own electron distribution, as a mapping with set_polarized_variants()'s keys."""
+        values = {key: self.params.get("plasma_" + key) for key in _capi.ELECTRON_MIX_KEYS}
+        return {key: float(value) if value is not None else 0.0 for key, value in values.items()}   # (a key the block does not set is not read)
+
+    @property
+    def polarized_electrons(self):
+        """The electron distribution every variant renders with (bl_polarized_variant_electrons), one mapping per variant - the
+        parameter block's own where set_polarized_variants(electrons=...) set none; one entry when no variants are set."""
+        out = []
+        for v in range(max(1, self.num_polarized_variants)):
+            mix = _capi.ElectronMix()
+            self._check(self._lib.bl_polarized_variant_electrons(self._ctx, v, C.byref(mix)))
+            out.append({key: getattr(mix, key) for key in _capi.ELECTRON_MIX_KEYS})
+        return out
+
+    @property
+    def polarized_electrons_set(self):
+        """True when the variants carry distributions of their own (set_polarized_variants(electrons=...))."""
+        return bool(getattr(self, "_polarized_electrons", False))
 
     @property
     def num_polarized_variants(self):
@@ -403,6 +447,7 @@ class Context:
         if not (target_jy > 0.0 and rtol > 0.0):
             raise ValueError("fit_density_units_polarized needs target_jy > 0 and rtol > 0")
         saved, saved_cuts = self.polarized_variants, self.polarized_cuts
+        saved_electrons = self.polarized_electrons if self.polarized_electrons_set else None
         renders = 0
 
         def evaluate(trials):   # [(pair index, rho)] -> [(I, Q, U, V) in Jy]
@@ -471,7 +516,8 @@ class Context:
                 raise RuntimeError(f"fit_density_units_polarized: no unit within rtol = {rtol} of {target_jy} Jy after {renders} renders")
             return found, renders
         finally:
-            self.set_polarized_variants([h for h, _, _ in saved], [u for _, _, u in saved], rat_low=[l for _, l, _ in saved], sigma_max=saved_cuts)
+            self.set_polarized_variants([h for h, _, _ in saved], [u for _, _, u in saved], rat_low=[l for _, l, _ in saved], sigma_max=saved_cuts,
+                                        electrons=saved_electrons)
 
     def set_caller_stream(self, stream=None, enabled=True):
         """Every later render starts behind the work queued so far on `stream` (a raw hipStream_t handle, e.g.

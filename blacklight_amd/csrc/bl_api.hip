@@ -431,20 +431,22 @@ const char *CamerasRefusal(const bl_ctx *ctx, int n) {
 }
 
 // The variants of a render, in image-row order: the triples (each with its own cut_sigma_max where bl_set_polarized_variants_sigma gave
-// one), else models x units x sigma cuts, model-major, then unit, then cut, with the parameter block's pair, unit and cut_sigma_max
+// one, and its own electron mix where bl_set_polarized_variants_electrons gave one), else models x units x sigma cuts, model-major, then unit, then cut, with the parameter block's pair, unit and cut_sigma_max
 // where an axis is not set. The one reader of what the four setters stored.
 Variants ResolveVariants(const bl_ctx *ctx) {
   const bl_params &p = ctx->params;
-  const std::vector<Variant> own = {{p.plasma_rat_low, p.plasma_rat_high, p.simulation_rho_cgs, p.cut_sigma_max}};
+  const std::vector<Variant> own = {{p.plasma_rat_low, p.plasma_rat_high, p.simulation_rho_cgs, p.cut_sigma_max, BlockMix(p)}};
   const std::vector<double> own_cut = {p.cut_sigma_max};
   Variants v{ctx->triples, static_cast<int>(ctx->models.size()), static_cast<int>(ctx->units.size()), static_cast<int>(ctx->triples.size()),
              static_cast<int>(ctx->sigma_cuts.size())};
   if (!ctx->triples_cut)
     for (Variant &triple : v.list) triple.sigma_max = p.cut_sigma_max;
+  if (!ctx->triples_mix)
+    for (Variant &triple : v.list) triple.mix = BlockMix(p);
   if (v.n_pol == 0)
     for (const Variant &model : v.n_models > 0 ? ctx->models : own)
       for (const Variant &unit : v.n_units > 0 ? ctx->units : own)
-        for (const double sigma_max : v.n_cuts > 0 ? ctx->sigma_cuts : own_cut) v.list.push_back({model.rat_low, model.rat_high, unit.rho, sigma_max});
+        for (const double sigma_max : v.n_cuts > 0 ? ctx->sigma_cuts : own_cut) v.list.push_back({model.rat_low, model.rat_high, unit.rho, sigma_max, BlockMix(p)});
   return v;
 }
 }  // namespace blhost
@@ -1254,7 +1256,8 @@ int bl_set_density_units(bl_ctx *ctx, int n, const double *rho_cgs) {
 
 int bl_num_density_units(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->units.size()) : -1; }
 
-int bl_set_polarized_variants_sigma(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs, const double *sigma_max) {
+int bl_set_polarized_variants_electrons(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs, const double *sigma_max,
+                                        const bl_electron_mix *mix) {
   if (ctx == nullptr) return BL_E_ARG;
   if (n < 0 || n > BL_MAX_POLARIZED_VARIANTS || (n > 0 && (rat_low == nullptr || rat_high == nullptr || rho_cgs == nullptr)))
     return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants needs 0 <= n <= " + std::to_string(BL_MAX_POLARIZED_VARIANTS) + " and the three arrays."});
@@ -1267,10 +1270,53 @@ int bl_set_polarized_variants_sigma(bl_ctx *ctx, int n, const double *rat_low, c
       return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants_sigma: the sigma cut of variant " + std::to_string(v) + " is not finite."});
   }
   if (const char *why = PolarizedVariantsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
+  // The mixes, as bl_init checks the parameter block's (radiation_integrator.cpp:283-311): what is read must be finite - the shape values
+  // of a distribution whose fraction is zero are not read - kappa within the range of the polarized fits, and the reference's warnings,
+  // each once per call and only when the call goes through
+  bool warn_power = false, warn_kappa = false, warn_thermal = false, warn_interpolate = false;
+  for (int v = 0; mix != nullptr && v < n; v++) {
+    const bl_electron_mix &m = mix[v];
+    const std::string which = "bl_set_polarized_variants_electrons: variant " + std::to_string(v);
+    if (!std::isfinite(m.power_frac)) return Fail(ctx, Failure{BL_E_ARG, which + " has a power_frac that is not finite."});
+    if (!std::isfinite(m.kappa_frac)) return Fail(ctx, Failure{BL_E_ARG, which + " has a kappa_frac that is not finite."});
+    if (m.power_frac != 0.0) {
+      if (!std::isfinite(m.p)) return Fail(ctx, Failure{BL_E_ARG, which + " has a p that is not finite."});
+      if (!std::isfinite(m.gamma_min)) return Fail(ctx, Failure{BL_E_ARG, which + " has a gamma_min that is not finite."});
+      if (!std::isfinite(m.gamma_max)) return Fail(ctx, Failure{BL_E_ARG, which + " has a gamma_max that is not finite."});
+    }
+    if (m.kappa_frac != 0.0) {
+      if (!std::isfinite(m.kappa)) return Fail(ctx, Failure{BL_E_ARG, which + " has a kappa that is not finite."});
+      if (!std::isfinite(m.w)) return Fail(ctx, Failure{BL_E_ARG, which + " has a w that is not finite."});
+      if (m.kappa < 3.5 || m.kappa > 5.0) return Fail(ctx, Failure{BL_E_ARG, which + ": Polarized transport only supports kappa in [3.5, 5]."});
+      warn_interpolate = warn_interpolate || (m.kappa != 3.5 && m.kappa != 4.0 && m.kappa != 4.5 && m.kappa != 5.0);
+    }
+    warn_power = warn_power || m.power_frac < 0.0 || m.power_frac > 1.0;
+    warn_kappa = warn_kappa || m.kappa_frac < 0.0 || m.kappa_frac > 1.0;
+    const double thermal_frac = ThermalFraction(m);
+    warn_thermal = warn_thermal || thermal_frac < 0.0 || thermal_frac > 1.0;
+  }
+  if (warn_power) Warn(ctx, "Fraction of power-law electrons outside [0, 1].");
+  if (warn_kappa) Warn(ctx, "Fraction of kappa-distribution electrons outside [0, 1].");
+  if (warn_interpolate) Warn(ctx, "Polarized transport will interpolate formulas based on kappa.");
+  if (warn_thermal) Warn(ctx, "Fraction of thermal electrons outside [0, 1].");
   std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: no variant enters them)
   ctx->triples.resize(n);
-  for (int v = 0; v < n; v++) ctx->triples[v] = {rat_low[v], rat_high[v], rho_cgs[v], sigma_max != nullptr ? sigma_max[v] : 0.0};
+  for (int v = 0; v < n; v++)
+    ctx->triples[v] = {rat_low[v], rat_high[v], rho_cgs[v], sigma_max != nullptr ? sigma_max[v] : 0.0, mix != nullptr ? mix[v] : bl_electron_mix{}};
   ctx->triples_cut = n > 0 && sigma_max != nullptr;
+  ctx->triples_mix = n > 0 && mix != nullptr;
+  return BL_OK;
+}
+
+int bl_set_polarized_variants_sigma(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs, const double *sigma_max) {
+  return bl_set_polarized_variants_electrons(ctx, n, rat_low, rat_high, rho_cgs, sigma_max, nullptr);
+}
+
+int bl_polarized_variant_electrons(const bl_ctx *ctx, int variant, bl_electron_mix *out) {
+  if (ctx == nullptr || out == nullptr) return BL_E_ARG;
+  const int n = static_cast<int>(ctx->triples.size());
+  if (variant < 0 || variant >= std::max(1, n)) return BL_E_ARG;
+  *out = (n > 0 && ctx->triples_mix) ? ctx->triples[variant].mix : BlockMix(ctx->params);
   return BL_OK;
 }
 
@@ -1475,7 +1521,7 @@ void bl_free(bl_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   ctx->d_cells.Free(); ctx->d_kappa.Free(); ctx->d_coords.Free(); ctx->d_buckets.Free(); ctx->slot[0].Free(); ctx->slot[1].Free();
   ctx->d_freq.Free(); ctx->d_pixel_map.Free();
-  ctx->d_block_locs.Free(); ctx->d_tile_order.Free(); ctx->d_cameras.Free(); ctx->d_render_params.Free(); ctx->d_render.Free(); ctx->d_shade_cold.Free(); ctx->d_pol_variant_table.Free(); ctx->d_image.Free(); ctx->d_camera_pos.Free(); ctx->d_camera_dir.Free();
+  ctx->d_block_locs.Free(); ctx->d_tile_order.Free(); ctx->d_cameras.Free(); ctx->d_render_params.Free(); ctx->d_render.Free(); ctx->d_shade_cold.Free(); ctx->d_pol_variant_table.Free(); ctx->d_pol_variant_args.Free(); ctx->d_image.Free(); ctx->d_camera_pos.Free(); ctx->d_camera_dir.Free();
   ctx->d_out_sample_num.Free(); ctx->d_out_flags.Free();
   for (auto &e : ctx->events)
     if (e != nullptr) (void)hipEventDestroy(e);

@@ -15,6 +15,27 @@
 #endif
 // kThermalOnly: no power-law and no kappa-distribution electrons (the host knows): without their formulas the exact kernel fits three
 // waves per SIMD instead of two (168 registers), which is worth 8 ms of a 1024^2 frame's 106.
+// Polarized variants with an electron mix each (BlShadeArgs::pol_variant_args): the block whose electron constants - thermal fraction,
+// power-law constants, BlShadeCold::kappa behind its `cold` - variant v's formulas read. The table is written before the launch and
+// read-only during it, and v is uniform over the wave: read through the constant address space, as the kernel's own arguments are, its
+// fields are scalar loads where they are used. The thermal-only instantiation reads no electron constant but the thermal fraction,
+// which is then the same for every variant: its own arguments.
+template <bool kThermalOnly>
+__device__ __forceinline__ const BlShadeArgs &variant_electrons(const BlShadeArgs &P, unsigned int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (!kThermalOnly) {
+    // (one pointer in that address space behind the barrier kernel_arguments_in_place uses: the optimiser sees neither of its two
+    // origins, so the reads through it stay scalar loads and the reads through P stay what they were)
+    typedef const __attribute__((address_space(4))) BlShadeArgs *InConstant;
+    const BlPolVariantArgs *table = P.pol_variant_args;
+    InConstant e = table != nullptr ? (InConstant)&table[v].args : (InConstant)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(e));
+    return *(const BlShadeArgs *)e;
+  }
+#endif
+  return P;
+}
+
 template <bool kTolerant, bool kThermalOnly>
 __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POLCOEF_WAVES) bl_polarized_coefficients_kernel(const BlShadeArgs P_at_entry) {
   // (with power-law or kappa electrons the kernel holds ~45 more scalars than there are registers for: it reads its arguments where it uses them)
@@ -41,6 +62,8 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
     const uint32_t n = (uint32_t)(tag >> 32);
     const BlCoefInputs ci = P.coef_inputs[idx];
     const double momentum_factor = bl_ray_factor(P.ray_constants, (size_t)ray);
+    // the electron constants of the wave's variant (a mix per variant: its copy of the block; else the render's own, for every variant)
+    const BlShadeArgs &E = variant_electrons<kThermalOnly>(P, v);
     SampleShade sh;
     sh.have_coefficients = ci.have_coefficients != 0.0;
     sh.nu_fluid_over_nu = ci.nu_fluid_over_nu;
@@ -60,7 +83,7 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
       sh.n_e_cgs = cgs.n_e_cgs;
       sh.nu_c_cgs = plasma_cyclotron_frequency(plasma_field_cgs(b_sq, pv.b_unit));
       sh.theta_e = sh.kb_tt_e_cgs = __longlong_as_double(0x7ff8000000000000ll);
-      if (P.plasma.plasma_thermal_frac != 0.0)
+      if (E.plasma.plasma_thermal_frac != 0.0)
         plasma_electron_temperature(P, pv.rat_high, pv.rat_low, plasma_beta_inverse(b_sq, pgas), cgs, &sh.theta_e, &sh.kb_tt_e_cgs);
     }
     // :453-455 from cos^2: the same operations the coefficient kernel applies to the same value
@@ -70,7 +93,7 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
     sh.cos_theta_b = bl_sqrt_g(ci.cos2_theta_b) * ci.cos_sign;
     // what does not depend on the frequency, once per sample (the reference recomputes it for every frequency)
     sh.theta_e_096 = sh.kk_0 = sh.kk_1 = sh.kk_2 = 0.0;
-    if (sh.have_coefficients && P.plasma.plasma_thermal_frac != 0.0) {
+    if (sh.have_coefficients && E.plasma.plasma_thermal_frac != 0.0) {
       sh.theta_e_096 = kTolerant ? fastmath::pow(sh.theta_e, 0.96) : bl_pow(sh.theta_e, 0.96);
       if (sh.theta_e >= 0.01) {   // theta_e_zero, radiation_integrator.hpp:190
         if (kTolerant) fastmath::bessel_k012(1.0 / sh.theta_e, &sh.kk_0, &sh.kk_1, &sh.kk_2);
@@ -83,11 +106,11 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
       double j_val = 0.0, alpha_val = 0.0;
       double2 pc[3] = {make_double2(0.0, 0.0), make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
       if (kTolerant) {
-        if (sh.have_coefficients) simulation_coefficients_fast<!kThermalOnly>(P, sh, freq, momentum_factor, &j_val, &alpha_val);
-        polarized_coefficients_fast<!kThermalOnly>(P, sh, freq, momentum_factor, j_val, alpha_val, pc);
+        if (sh.have_coefficients) simulation_coefficients_fast<!kThermalOnly>(E, sh, freq, momentum_factor, &j_val, &alpha_val);
+        polarized_coefficients_fast<!kThermalOnly>(E, sh, freq, momentum_factor, j_val, alpha_val, pc);
       } else {
-        if (sh.have_coefficients) simulation_coefficients<!kThermalOnly>(P, sh, freq, momentum_factor, &j_val, &alpha_val);
-        polarized_coefficients<!kThermalOnly>(P, sh, freq, momentum_factor, j_val, alpha_val, pc);
+        if (sh.have_coefficients) simulation_coefficients<!kThermalOnly>(E, sh, freq, momentum_factor, &j_val, &alpha_val);
+        polarized_coefficients<!kThermalOnly>(E, sh, freq, momentum_factor, j_val, alpha_val, pc);
       }
 #ifdef BL_POL_CONDITION_STATS
       // (a measurement build, tools/build_variant.sh -DBL_POL_CONDITION_STATS: how many samples' joint coupling step - polarized.cpp:
@@ -340,8 +363,12 @@ __global__ void bl_debug_math_kernel(int op, long long n, const double *x, const
 // magnitude in optically and Faraday thick cells - docs/notebook.md - so a tolerant kernel here moved rows with the reference's own
 // conditioning; it was a measurement switch until round 6)
 extern "C" hipError_t bl_launch_polarized_coefficients(const BlShadeArgs *args, const KernelPlan::PerFrequency &plan, int grid, hipStream_t stream) {
+  // (the thermal-only kernel needs thermal electrons in the block it reads - and no table of mixes, which it does not read; the
+  // all-electrons kernel renders thermal ones to the same bits: a pass of a variant without a power law or kappa electrons among others with)
   const bool thermal_only = args->plasma.power_frac == 0.0 && args->plasma.kappa_unpolarized == 0 && args->plasma.kappa_frac_zero != 0;
-  if (!plan.polarized_coefficients || plan.thermal_only != thermal_only || args->pol_samples == nullptr) return hipErrorInvalidValue;
+  if (!plan.polarized_coefficients || (plan.thermal_only && (!thermal_only || args->pol_variant_args != nullptr)) || args->pol_samples == nullptr)
+    return hipErrorInvalidValue;
+  if (args->pol_variant_args != nullptr && args->pol_variants < 2) return hipErrorInvalidValue;
   void (*kernel)(BlShadeArgs) = plan.thermal_only ? bl_polarized_coefficients_kernel<false, true> : bl_polarized_coefficients_kernel<false, false>;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, stream, *args);
   return hipGetLastError();

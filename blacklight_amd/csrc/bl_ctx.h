@@ -125,7 +125,12 @@ using namespace blhost;
 // One image of a render: an electron model (R_low, R_high), a density unit (simulation_rho_cgs) and a sigma cut (cut_sigma_max).
 // Variants: a render's, in image-row order and never empty (ResolveVariants), with the number of models, units, polarized triples
 // and sigma cuts as set - 0: the parameter block's.
-struct Variant { double rat_low, rat_high, rho, sigma_max; };
+// ... and, for a polarized variant, an electron distribution (bl_set_polarized_variants_electrons); ResolveVariants gives every
+// variant one - the parameter block's where none was set (what the setters store without one is zero and not read).
+struct Variant {
+  double rat_low, rat_high, rho, sigma_max;
+  bl_electron_mix mix;
+};
 struct Variants {
   std::vector<Variant> list;
   int n_models, n_units, n_pol, n_cuts;
@@ -169,6 +174,7 @@ struct bl_ctx {
   // units (the pair unused), bl_set_polarized_variants() triples, bl_set_sigma_cuts() thresholds; read through ResolveVariants only
   std::vector<Variant> models, units, triples;
   bool triples_cut = false;          // the triples carry a cut_sigma_max each (bl_set_polarized_variants_sigma); else the parameter block's
+  bool triples_mix = false;          // ... and an electron mix each (bl_set_polarized_variants_electrons); else the parameter block's
   std::vector<double> sigma_cuts;
   // bl_set_cameras(): the viewing angles as given (degrees) and each camera's frame; empty: the parameter block's camera. `frame`
   // above is what a one-camera render starts its rays from - the block's own frame (block_frame), or the one camera of a list of
@@ -236,7 +242,6 @@ struct bl_ctx {
   std::vector<SlowSlice> slow_slices;
   bl_slow_state slow_state{};            // reader-side bookkeeping of bl_slow_light_read (bl_snapshot.cpp)
   bool polarized = false;                // image_light and image_polarization in simulation mode
-  double power_pol[7] = {};              // polarized power-law constants (simulation_coefficients.cpp:67-80)
   int snapshot = 0;                      // index of the image being rendered (warning texts, camera time)
   long long stats_slow_count[4] = {0, 0, 0, 0};    // pixels needing extrapolation in the last render, by kind
   double stats_slow_val[4] = {0.0, 0.0, 0.0, 0.0};
@@ -356,6 +361,8 @@ struct bl_ctx {
   DeviceBuffer<BlShadeCold> d_shade_cold;
   DeviceBuffer<BlPolVariant> d_pol_variant_table;   // polarized variants in one pass: every variant's folded constants (BuildShadeArgs)
   std::vector<unsigned char> pol_variant_host;   // the bytes d_pol_variant_table holds
+  DeviceBuffer<BlPolVariantArgs> d_pol_variant_args;   // ... and every variant's electron constants, where a mix has non-thermal electrons (BuildShadeArgs)
+  std::vector<unsigned char> pol_variant_args_host;   // the bytes d_pol_variant_args holds
   std::vector<unsigned char> shade_cold_host;   // the bytes d_shade_cold holds (BuildShadeArgs uploads on change only)
   // host-output staging
   DeviceBuffer<double> d_image, d_camera_pos, d_camera_dir;
@@ -389,6 +396,11 @@ inline bool UnitCut(const bl_params &p) {   // a cut the density unit enters is 
   return p.cut_rho_min >= 0.0 || p.cut_rho_max >= 0.0 || p.cut_n_e_min >= 0.0 || p.cut_n_e_max >= 0.0 || p.cut_p_gas_min >= 0.0 || p.cut_p_gas_max >= 0.0
       || p.cut_b_min >= 0.0 || p.cut_b_max >= 0.0;
 }
+// The parameter block's own electron mix, and a mix's thermal fraction (radiation_integrator.cpp:311: bl_init's expression)
+inline bl_electron_mix BlockMix(const bl_params &p) {
+  return bl_electron_mix{p.plasma_power_frac, p.plasma_p, p.plasma_gamma_min, p.plasma_gamma_max, p.plasma_kappa_frac, p.plasma_kappa, p.plasma_w, 0.0};
+}
+inline double ThermalFraction(const bl_electron_mix &mix) { return 1.0 - (mix.power_frac + mix.kappa_frac); }
 inline bool ThetaECut(const bl_params &p) { return p.cut_theta_e_min >= 0.0 || p.cut_theta_e_max >= 0.0; }
 const char *ElectronModelsRefusal(const bl_ctx *ctx, int n);   // bl_set_electron_models (bl_api.hip)
 const char *DensityUnitsRefusal(const bl_ctx *ctx, int n);     // bl_set_density_units (bl_api.hip)

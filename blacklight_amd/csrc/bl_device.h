@@ -529,6 +529,19 @@ struct BlShadeArgs {
   // sigma lies in one of them is the exact pass's. Read wave-uniform; an empty band (lo > hi) for a switched-off threshold.
   int n_sigma_bands;
   double sigma_band_lo[BL_SHADE_MAX_SIGMA_CUTS], sigma_band_hi[BL_SHADE_MAX_SIGMA_CUTS];
+  // polarized variants in one pass with an electron mix each (bl_set_polarized_variants_electrons): device [pol_variants], every variant's
+  // electron constants where bl_polarized_coefficients_kernel<*, false> reads them; null: the ones above, for every variant
+  const struct BlPolVariantArgs *pol_variant_args;
+};
+
+// ... and with an electron mix per variant (BlShadeArgs::pol_variant_args): the electron constants of a variant in a copy of the
+// argument block, so that the formulas of bl_coefficients.inc run on a reference to it as they run on the kernel's own arguments.
+// Of `args` only what those formulas read of the electrons is filled - plasma (plasma_thermal_frac, power_frac, plasma_p, power_jj,
+// power_aa), power_pol, plasma_gamma_min - and `cold`, which points at the `cold` member of the same element on the device (kappa
+// alone is read there); everything else is zero. A wave's variant is uniform, and so is every address read here.
+struct BlPolVariantArgs {
+  BlShadeArgs args;
+  BlShadeCold cold;
 };
 
 // Kernel arguments: transfer kernel

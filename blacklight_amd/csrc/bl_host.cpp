@@ -878,4 +878,36 @@ int bl_apply_sweeps_cameras(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_c
   return rc;
 }
 
+int bl_apply_sweep_lists(bl_ctx *ctx, const bl_sweep_lists *lists) {
+  if (ctx == nullptr || lists == nullptr) return BL_E_ARG;
+  const bl_sweep none = {};
+  const bl_sweep *sweep = lists->sweep != nullptr ? lists->sweep : &none;
+  const bl_sweep_electrons *e = lists->electrons;
+  const bool electrons = e != nullptr && (e->n_power_frac != 0 || e->n_p != 0 || e->n_gamma_min != 0 || e->n_gamma_max != 0 || e->n_kappa_frac != 0
+                                          || e->n_kappa != 0 || e->n_w != 0);
+  if (!electrons) return bl_apply_sweeps_cameras(ctx, sweep, lists->cuts, lists->cameras);
+  int n = 0;
+  bl_sweep triples;
+  bl_electron_mix mix[BL_MAX_SWEEP];
+  char err[512] = "";
+  if (bl_sweep_electrons_resolve(e, sweep, bl_internal_params(ctx), &n, &triples, mix, err, sizeof err) != BL_OK)
+    return bl_internal_fail(ctx, BL_E_INPUT, MessageOf(err).c_str());
+  // (the cameras and the cuts first, by the call that has their rules - the cuts of a polarized block are refused there, in the
+  // setter's words; then the tuples, whose refusal takes back what that call brought)
+  const int held = bl_num_cameras(ctx);
+  double held_th[BL_MAX_CAMERAS], held_ph[BL_MAX_CAMERAS];
+  (void)bl_cameras_get(ctx, held, held_th, held_ph);
+  int rc = bl_apply_sweeps_cameras(ctx, &none, lists->cuts, lists->cameras);
+  if (rc != BL_OK) return rc;
+  rc = bl_set_polarized_variants_electrons(ctx, n, triples.rat_low, triples.rat_high, triples.rho_cgs, nullptr, mix);
+  if (rc != BL_OK) {
+    const std::string why = bl_last_error(ctx);
+    if (lists->cuts != nullptr && lists->cuts->n_sigma_max > 0) (void)bl_set_sigma_cuts(ctx, 0, nullptr);
+    if (lists->cameras != nullptr && (lists->cameras->n_th > 0 || lists->cameras->n_ph > 0))
+      (void)bl_internal_set_cameras(ctx, held, held > 0 ? held_th : nullptr, held > 0 ? held_ph : nullptr);
+    bl_internal_fail(ctx, rc, MessageOf(why).c_str());
+  }
+  return rc;
+}
+
 }  // extern "C"

@@ -191,7 +191,9 @@ int main(int argc, char *argv[]) {
   static bl_sweep sweep;   // sweep_rat_low / sweep_rat_high / sweep_rho_cgs: several images per snapshot, one file each
   static bl_sweep_cuts sweep_cuts;   // ... and sweep_cut_sigma_max, an axis of its own
   static bl_sweep_cameras sweep_cameras;   // ... and sweep_camera_th / sweep_camera_ph: several cameras per render, one file per (camera, variant)
-  if (bl_params_read_file_sweeps_cameras(&params, &sweep, &sweep_cuts, &sweep_cameras, argv[1], &num_runs, err, sizeof err) != BL_OK) {
+  static bl_sweep_electrons sweep_electrons;   // ... and the seven electron lists: a polarized variant's distribution, no file of their own
+  const bl_sweep_lists sweep_lists = {&sweep, &sweep_cuts, &sweep_cameras, &sweep_electrons};
+  if (bl_params_read_file_sweep_lists(&params, &sweep_lists, argv[1], &num_runs, err, sizeof err) != BL_OK) {
     std::cout << err;
     return 1;
   }
@@ -231,7 +233,7 @@ int main(int argc, char *argv[]) {
     // as the reference's do across thread counts. And so are runs over several devices: a frame and its tiles are then the same bits.
     if (params.adaptive_max_level > 0 || n_devices > 1) bl_set_reproducible(contexts[dev], 1);
     // the sweep on every device: a device's share of the frame then holds the rows of all variants, like the frame does
-    if (bl_apply_sweeps_cameras(contexts[dev], &sweep, &sweep_cuts, &sweep_cameras) != BL_OK) {
+    if (bl_apply_sweep_lists(contexts[dev], &sweep_lists) != BL_OK) {
       std::cout << bl_last_error(contexts[dev]);
       return 1;
     }
@@ -553,7 +555,7 @@ int main(int argc, char *argv[]) {
             << (last_stats.arithmetic == BL_ARITH_TOLERANT ? (last_stats.composed_maps ? ", composed transfer maps (equal from run to run to rounding)" : ", bit-reproducible") : "")
             << (last_stats.geodesics_reused ? "; geodesics integrated once for the series" : "") << " (BLACKLIGHT_AMD_ARITHMETIC=exact|tolerant)\n";
   // (and, only with sweep keys in the input file, one line on what each snapshot's single render was written out as)
-  if (sweep.n_rat_low > 0 || sweep.n_rho_cgs > 0 || sweep_cuts.n_sigma_max > 0) {
+  if (sweep.n_rat_low > 0 || sweep.n_rho_cgs > 0 || sweep_cuts.n_sigma_max > 0 || (triples && sweep.n_rat_low == 0 && sweep.n_rho_cgs == 0)) {
     std::cout << "blacklight_amd: sweep of " << n_variants << " variants per snapshot (";
     if (triples) std::cout << n_variants << " polarized triples";
     else std::cout << std::max(1, n_models) << " electron models x " << std::max(1, n_units) << " density units";

@@ -291,7 +291,7 @@ void ReadRender(bl_params *p, const std::string &key, const std::string &val) {
 
 // sweep_rat_low / sweep_rat_high / sweep_rho_cgs / sweep_cut_sigma_max: "a,b,c" (an extension: the reference has no lists). Stricter than the scalar keys:
 // every entry is a whole number text - nothing is left of it after the conversion -, none is empty, at most BL_MAX_SWEEP of them.
-enum ListKind { kNumbers, kUnits, kSigmaCuts, kAngles };
+enum ListKind { kNumbers, kUnits, kSigmaCuts, kAngles, kElectrons };
 int ReadList(const std::string &key, const std::string &val, ListKind kind, double *out) {
   int count = 0;
   for (size_t at = 0; at <= val.size();) {
@@ -307,6 +307,8 @@ int ReadList(const std::string &key, const std::string &val, ListKind kind, doub
       throw ParseFailure{"Invalid sigma cut (" + entry + ") in list (" + key + ") in input file: must be finite."};
     if (kind == kAngles && !std::isfinite(x))
       throw ParseFailure{"Invalid angle (" + entry + ") in list (" + key + ") in input file: must be finite."};
+    if (kind == kElectrons && !std::isfinite(x))
+      throw ParseFailure{"Invalid value (" + entry + ") in list (" + key + ") in input file: must be finite."};
     if (count >= BL_MAX_SWEEP)
       throw ParseFailure{"Too many entries in list (" + key + ") in input file: at most " + std::to_string(BL_MAX_SWEEP) + " for this build."};
     out[count++] = x;
@@ -315,8 +317,31 @@ int ReadList(const std::string &key, const std::string &val, ListKind kind, doub
   return count;
 }
 
-// The sweep keys go beside the parameter block (bl_sweep, bl_sweep_cuts, bl_sweep_cameras), never into it; false: not a sweep key
-bool SetSweepKey(bl_sweep *s, bl_sweep_cuts *c, bl_sweep_cameras *a, const std::string &key, const std::string &val) {
+// The seven electron lists of a bl_sweep_electrons, in the order of bl_electron_mix: key, count, values
+struct ElectronList {
+  const char *key;
+  int32_t bl_sweep_electrons::*n;
+  double (bl_sweep_electrons::*values)[BL_MAX_SWEEP];
+};
+const ElectronList kElectronLists[7] = {
+    {"sweep_power_frac", &bl_sweep_electrons::n_power_frac, &bl_sweep_electrons::power_frac},
+    {"sweep_p", &bl_sweep_electrons::n_p, &bl_sweep_electrons::p},
+    {"sweep_gamma_min", &bl_sweep_electrons::n_gamma_min, &bl_sweep_electrons::gamma_min},
+    {"sweep_gamma_max", &bl_sweep_electrons::n_gamma_max, &bl_sweep_electrons::gamma_max},
+    {"sweep_kappa_frac", &bl_sweep_electrons::n_kappa_frac, &bl_sweep_electrons::kappa_frac},
+    {"sweep_kappa", &bl_sweep_electrons::n_kappa, &bl_sweep_electrons::kappa},
+    {"sweep_w", &bl_sweep_electrons::n_w, &bl_sweep_electrons::w}};
+
+// The sweep keys go beside the parameter block (the structs of a bl_sweep_lists, none of them null here), never into it; false: not a sweep key
+bool SetSweepKey(const bl_sweep_lists &lists, const std::string &key, const std::string &val) {
+  bl_sweep *s = lists.sweep;
+  bl_sweep_cuts *c = lists.cuts;
+  bl_sweep_cameras *a = lists.cameras;
+  for (const ElectronList &list : kElectronLists)
+    if (key == list.key) {
+      lists.electrons->*list.n = ReadList(key, val, kElectrons, lists.electrons->*list.values);
+      return true;
+    }
   if (key == "sweep_rat_low") s->n_rat_low = ReadList(key, val, kNumbers, s->rat_low);
   else if (key == "sweep_rat_high") s->n_rat_high = ReadList(key, val, kNumbers, s->rat_high);
   else if (key == "sweep_rho_cgs") s->n_rho_cgs = ReadList(key, val, kUnits, s->rho_cgs);
@@ -368,8 +393,47 @@ int ResolveCameras(const bl_sweep_cameras &a) {
   return a.n_th > 0 ? a.n_th : a.n_ph;
 }
 
-void SetKeyValue(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_cameras *cameras, const std::string &key, const std::string &val) {
-  if (key.compare(0, 6, "sweep_") == 0 && SetSweepKey(sweep, cuts, cameras, key, val)) return;
+// What the electron lists mean together with the three lists of `s` (include/blacklight_amd.h, bl_sweep_electrons_resolve): the number
+// of tuples, the triples and every tuple's mix
+int ResolveElectrons(const bl_sweep_electrons &e, const bl_sweep &s, const bl_params &p, bl_sweep *out, bl_electron_mix *mix) {
+  bl_sweep r;
+  int polarized = 0;
+  ResolveSweep(s, p, &r, &polarized);
+  int longest = 0;
+  const char *first_key = nullptr;
+  for (const ElectronList &list : kElectronLists) {
+    const int n = e.*list.n;
+    if (n < 0 || n > BL_MAX_SWEEP) throw ParseFailure{"Too many entries in a sweep list: at most " + std::to_string(BL_MAX_SWEEP) + " for this build."};
+    if (n > 0 && first_key == nullptr) first_key = list.key;
+    longest = std::max(longest, n);
+  }
+  if (first_key != nullptr && !polarized) throw ParseFailure{std::string(first_key) + " needs image_polarization = true in input file."};
+  const bool triples = polarized && (s.n_rat_low > 0 || s.n_rho_cgs > 0);
+  const int n = triples ? r.n_rho_cgs : longest;
+  for (const ElectronList &list : kElectronLists)
+    if (e.*list.n > 1 && e.*list.n != n)
+      throw ParseFailure{std::string(list.key) + " must have one entry or as many as the other sweep lists (" + std::to_string(e.*list.n) + " and "
+                         + std::to_string(n) + ") in input file."};
+  if (!triples && first_key != nullptr) {   // electron lists alone: the block's pair and unit at every mix
+    for (int v = 0; v < n; v++) r.rat_low[v] = p.plasma_rat_low, r.rat_high[v] = p.plasma_rat_high, r.rho_cgs[v] = p.simulation_rho_cgs;
+    r.n_rat_low = r.n_rat_high = r.n_rho_cgs = n;
+  }
+  if (out != nullptr) *out = r;
+  const double own[7] = {p.plasma_power_frac, p.plasma_p, p.plasma_gamma_min, p.plasma_gamma_max, p.plasma_kappa_frac, p.plasma_kappa, p.plasma_w};
+  for (int v = 0; mix != nullptr && polarized && v < n; v++) {
+    double values[7];
+    for (int k = 0; k < 7; k++) {
+      const ElectronList &list = kElectronLists[k];
+      const int count = e.*list.n;
+      values[k] = count == 0 ? own[k] : (e.*list.values)[count == 1 ? 0 : v];
+    }
+    mix[v] = bl_electron_mix{values[0], values[1], values[2], values[3], values[4], values[5], values[6], 0.0};
+  }
+  return (polarized && (triples || first_key != nullptr)) ? n : 0;
+}
+
+void SetKeyValue(bl_params *p, const bl_sweep_lists &lists, const std::string &key, const std::string &val) {
+  if (key.compare(0, 6, "sweep_") == 0 && SetSweepKey(lists, key, val)) return;
   // Compound keys first
   if (key == "cut_plane_origin") return ReadTriple(val, p, BL_P_cut_plane_origin_x);
   if (key == "cut_plane_normal") return ReadTriple(val, p, BL_P_cut_plane_normal_x);
@@ -417,7 +481,7 @@ void SetKeyValue(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_ca
   throw ParseFailure{"Unknown key (" + key + ") in input file."};
 }
 
-void ParseLine(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_cameras *cameras, std::string line) {
+void ParseLine(bl_params *p, const bl_sweep_lists &lists, std::string line) {
   std::string stripped;
   stripped.reserve(line.size());
   for (unsigned char c : line)
@@ -427,7 +491,7 @@ void ParseLine(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_came
   if (stripped.empty()) return;
   pos = stripped.find('=');
   if (pos == std::string::npos) throw ParseFailure{"Invalid assignment in input file."};
-  SetKeyValue(p, sweep, cuts, cameras, stripped.substr(0, pos), stripped.substr(pos + 1));
+  SetKeyValue(p, lists, stripped.substr(0, pos), stripped.substr(pos + 1));
 }
 
 }  // namespace
@@ -446,12 +510,23 @@ int bl_params_set_line_sweeps(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts
 
 int bl_params_set_line_sweeps_cameras(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_cameras *cameras, const char *line, char *err,
                                       size_t err_len) {
+  const bl_sweep_lists lists = {sweep, cuts, cameras, nullptr};
+  return bl_params_set_line_sweep_lists(p, &lists, line, err, err_len);
+}
+
+int bl_params_set_line_sweep_lists(bl_params *p, const bl_sweep_lists *lists, const char *line, char *err, size_t err_len) {
   if (p == nullptr || line == nullptr) return BL_E_ARG;
-  bl_sweep unused = {};   // (no sweep asked for: the keys are accepted and validated all the same)
+  bl_sweep unused = {};   // (a list not asked for: its keys are accepted and validated all the same)
   bl_sweep_cuts unused_cuts = {};
   bl_sweep_cameras unused_cameras = {};
+  bl_sweep_electrons unused_electrons = {};
+  bl_sweep_lists all = lists != nullptr ? *lists : bl_sweep_lists{};
+  if (all.sweep == nullptr) all.sweep = &unused;
+  if (all.cuts == nullptr) all.cuts = &unused_cuts;
+  if (all.cameras == nullptr) all.cameras = &unused_cameras;
+  if (all.electrons == nullptr) all.electrons = &unused_electrons;
   try {
-    ParseLine(p, sweep != nullptr ? sweep : &unused, cuts != nullptr ? cuts : &unused_cuts, cameras != nullptr ? cameras : &unused_cameras, line);
+    ParseLine(p, all, line);
   } catch (const ParseFailure &failure) {
     SetError(err, err_len, failure.message);
     return BL_E_INPUT;
@@ -477,26 +552,38 @@ int bl_params_read_file_sweeps(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cut
 
 int bl_params_read_file_sweeps_cameras(bl_params *p, bl_sweep *sweep, bl_sweep_cuts *cuts, bl_sweep_cameras *cameras, const char *path, int *num_runs,
                                        char *err, size_t err_len) {
+  const bl_sweep_lists lists = {sweep, cuts, cameras, nullptr};
+  return bl_params_read_file_sweep_lists(p, &lists, path, num_runs, err, err_len);
+}
+
+int bl_params_read_file_sweep_lists(bl_params *p, const bl_sweep_lists *lists, const char *path, int *num_runs, char *err, size_t err_len) {
   if (p == nullptr || path == nullptr) return BL_E_ARG;
   bl_params_clear(p);
   bl_sweep local = {};
   bl_sweep_cuts local_cuts = {};
   bl_sweep_cameras local_cameras = {};
-  if (sweep == nullptr) sweep = &local;
-  if (cuts == nullptr) cuts = &local_cuts;
-  if (cameras == nullptr) cameras = &local_cameras;
-  *sweep = bl_sweep{};
-  *cuts = bl_sweep_cuts{};
-  *cameras = bl_sweep_cameras{};
+  bl_sweep_electrons local_electrons = {};
+  bl_sweep_lists all = lists != nullptr ? *lists : bl_sweep_lists{};
+  if (all.sweep == nullptr) all.sweep = &local;
+  if (all.cuts == nullptr) all.cuts = &local_cuts;
+  if (all.cameras == nullptr) all.cameras = &local_cameras;
+  if (all.electrons == nullptr) all.electrons = &local_electrons;
+  bl_sweep *sweep = all.sweep;
+  bl_sweep_cameras *cameras = all.cameras;
+  *all.sweep = bl_sweep{};
+  *all.cuts = bl_sweep_cuts{};
+  *all.cameras = bl_sweep_cameras{};
+  *all.electrons = bl_sweep_electrons{};
   std::ifstream stream(path);
   if (!stream.is_open()) {
     SetError(err, err_len, "Could not open input file.");
     return BL_E_INPUT;
   }
   try {
-    for (std::string line; std::getline(stream, line);) ParseLine(p, sweep, cuts, cameras, line);
+    for (std::string line; std::getline(stream, line);) ParseLine(p, all, line);
     ResolveSweep(*sweep, *p, nullptr, nullptr);   // the lists against each other, once the whole file is known
     (void)ResolveCameras(*cameras);
+    (void)ResolveElectrons(*all.electrons, *sweep, *p, nullptr, nullptr);
   } catch (const ParseFailure &failure) {
     SetError(err, err_len, failure.message);
     return BL_E_INPUT;
@@ -536,6 +623,20 @@ int bl_sweep_resolve(const bl_sweep *sweep, const bl_params *p, bl_sweep *resolv
   if (sweep == nullptr || p == nullptr) return BL_E_ARG;
   try {
     ResolveSweep(*sweep, *p, resolved, polarized);
+  } catch (const ParseFailure &failure) {
+    SetError(err, err_len, failure.message);
+    return BL_E_INPUT;
+  }
+  return BL_OK;
+}
+
+int bl_sweep_electrons_resolve(const bl_sweep_electrons *e, const bl_sweep *sweep, const bl_params *p, int *n, bl_sweep *resolved, bl_electron_mix *mix,
+                               char *err, size_t err_len) {
+  if (e == nullptr || p == nullptr) return BL_E_ARG;
+  const bl_sweep none = {};
+  try {
+    const int count = ResolveElectrons(*e, sweep != nullptr ? *sweep : none, *p, resolved, mix);
+    if (n != nullptr) *n = count;
   } catch (const ParseFailure &failure) {
     SetError(err, err_len, failure.message);
     return BL_E_INPUT;

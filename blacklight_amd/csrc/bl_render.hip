@@ -125,7 +125,10 @@ struct RenderJob {
   bool pol_one_pass = false;
   int n_cold = 1;                   // BlShadeCold blocks on the device: one per (unit, sigma cut) where the passes' cut thresholds differ (BindVariant)
   int cold_units = 1, cold_cuts = 1;   // ... n_cold = cold_units x cold_cuts, an axis of one where the passes do not differ along it
-                                       // (polarized variants with cuts that differ: cold_cuts = the variants, each with its own)
+                                       // (polarized variants with cuts or mixes that differ: cold_cuts = the variants, each with its own)
+  bl_electron_mix base_mix{};       // the electron mix BuildShadeArgs folds: the first variant's (the parameter block's where none is set;
+                                    // one pass: what the frame-and-inputs kernel sees of it decides nothing - PlanJob; BindVariant each pass's)
+  bool all_thermal = false;         // the parameter block and every variant have thermal electrons only (PlanJob): the kernels chosen for that
   long long n_rays = 0, level_pixels = 0;
   int n_cameras = 1;          // cameras traced as one set of rays (bl_set_cameras): level_pixels = n_cameras x the camera's pixels
   bool camera_table = false;  // ... two or more: the ray-start kernel reads each ray's frame from BlTraceArgs::cameras
@@ -281,6 +284,34 @@ void FoldFastCuts(const bl_ctx *ctx, const BlPlasmaDevice &pl, BlShadeCold &cold
   }
 }
 
+// What the coefficient formulas read of an electron mix (FillElectronConstants below): BlPlasmaDevice's power-law constants and thermal
+// fraction, BlShadeArgs::power_pol and plasma_gamma_min, BlShadeCold::kappa. The parameter block's own mix and a variant's go through
+// the same function - the same calls on the same operands - which is where a variant's bits of a fresh render come from.
+struct ElectronConstants {
+  double thermal_frac;
+  double power_frac, plasma_p, power_jj, power_aa;
+  double power_pol[7];
+  double plasma_gamma_min;
+  BlKappaDevice kappa;
+};
+ElectronConstants FillElectronConstants(const bl_electron_mix &mix, bool polarized);
+// ... into an argument block (the render's own, a pass's, a variant's copy): everything of `pl` and `sa` a mix enters
+void BindElectronConstants(const ElectronConstants &ec, bool polarized, BlPlasmaDevice &pl, BlShadeArgs &sa) {
+  pl.plasma_thermal_frac = ec.thermal_frac;
+  pl.power_frac = ec.power_frac;
+  pl.plasma_p = ec.plasma_p;
+  pl.power_jj = ec.power_jj;
+  pl.power_aa = ec.power_aa;
+  pl.kappa_frac_zero = ec.kappa.frac == 0.0 ? 1 : 0;
+  pl.kappa_unpolarized = (ec.kappa.frac != 0.0 && !polarized) ? 1 : 0;
+  if (polarized) {
+    for (int c = 0; c < 7; c++) sa.power_pol[c] = ec.power_pol[c];
+    sa.plasma_gamma_min = ec.plasma_gamma_min;
+  }
+}
+bool SameMix(const bl_electron_mix &a, const bl_electron_mix &b) { return std::memcmp(&a, &b, sizeof a) == 0; }   // (as bits, like the cuts)
+bool ThermalOnly(const bl_electron_mix &mix) { return mix.power_frac == 0.0 && mix.kappa_frac == 0.0; }
+
 // Variant v of the render into the argument blocks: its pair where the coefficient kernels read R_low / R_high, its unit folded as
 // BuildShadeArgs folds the render's (FoldUnits), the cut thresholds of its unit and its sigma cut (its BlShadeCold, uploaded by
 // BuildShadeArgs; the cut's bit of the mask, which a negative value switches off), and its rows of the image. Nothing to do with one
@@ -293,6 +324,8 @@ void BindVariant(RenderJob &job, int v) {
   pl.plasma_rat_low = variant.rat_low;
   pl.plasma_rat_high = variant.rat_high;
   FoldUnits(job.ctx, variant.rho, pl, job.sa.fast_k);
+  // (a polarized variant's electron mix: the constants in the argument block here, kappa in the pass's BlShadeCold below)
+  if (job.variants.n_pol > 0) BindElectronConstants(FillElectronConstants(variant.mix, job.ctx->polarized), job.ctx->polarized, pl, job.sa);
   const int n_s = std::max(1, job.variants.n_cuts), n_u = std::max(1, job.variants.n_units);   // (v = (m n_u + u) n_s + s)
   const int u = (v / n_s) % n_u, s = job.variants.n_pol > 0 ? v : v % n_s;   // (polarized variants: a cut each, PlanVariantCuts)
   job.sa.cold = job.ctx->d_shade_cold.ptr + ((job.cold_units > 1 ? u : 0) * job.cold_cuts + (job.cold_cuts > 1 ? s : 0));
@@ -332,7 +365,10 @@ void PlanVariantCuts(RenderJob &job) {
   const bool cold_per_pass = job.simulation && job.variant_passes >= 2;
   job.cold_units = cold_per_pass && vs.n_units >= 2 ? vs.n_units : 1;
   job.cold_cuts = cold_per_pass && vs.n_cuts >= 2 ? vs.n_cuts : 1;
-  if (cold_per_pass && vs.n_pol >= 2 && cuts_differ) job.cold_cuts = vs.n_pol;
+  // (... or whose electron mixes differ: kappa lives in that block)
+  bool mixes_differ = false;
+  for (const Variant &v : vs.list) mixes_differ = mixes_differ || !SameMix(v.mix, first.mix);
+  if (cold_per_pass && vs.n_pol >= 2 && (cuts_differ || mixes_differ)) job.cold_cuts = vs.n_pol;
   job.n_cold = job.cold_units * job.cold_cuts;
 }
 
@@ -378,6 +414,10 @@ void PlanJob(RenderJob &job) {
   job.base_rho = first.rho, job.base_rat_low = first.rat_low, job.base_rat_high = first.rat_high;
   if (vs.n_pol == 0 && vs.list.size() >= 2) job.base_rat_low = p.plasma_rat_low, job.base_rat_high = p.plasma_rat_high;
   if (vs.n_units >= 2) job.base_rho = p.simulation_rho_cgs;
+  // (the electron mix: the first variant's - the parameter block's own unless bl_set_polarized_variants_electrons set one)
+  job.base_mix = first.mix;
+  job.all_thermal = p.plasma_power_frac == 0.0 && p.plasma_kappa_frac == 0.0;
+  for (const Variant &v : vs.list) job.all_thermal = job.all_thermal && ThermalOnly(v.mix);
   job.n_nu = p.image_num_frequencies;
   job.n_q_model = ctx->image_num_quantities;
   job.variant_passes = static_cast<int>(vs.list.size());
@@ -537,18 +577,25 @@ void PlanJob(RenderJob &job) {
   job.fill_present = fill_present;
   job.rows_only = ctx->polarized && ctx->render_num_images == 0 && !fill_present && !PerSampleRows(rows);
   // configuration 4's case: no BlCoefInputs through HBM, no bl_polarized_coefficients_kernel launch (bl_shade_fused.hip: kCoefficients)
-  job.pol_coefficients_inside = job.pol_fused && job.n_nu == 1 && job.rows_only && p.plasma_power_frac == 0.0 && p.plasma_kappa_frac == 0.0 && ctx->st.bh_a == 0.0;
+  // (thermal electrons: the mix the single pass renders with - n = 1 through bl_set_polarized_variants_electrons is that tuple in the
+  // block - and with a pass per variant every variant's, the kernel being chosen once)
+  bool variants_thermal = true;
+  for (const Variant &v : vs.list) variants_thermal = variants_thermal && ThermalOnly(v.mix);
+  job.pol_coefficients_inside = job.pol_fused && job.n_nu == 1 && job.rows_only && variants_thermal && ctx->st.bh_a == 0.0;
   // Polarized variants in one pass: where no decision differs between them - a rho, n_e, p_gas or B cut only with one unit, a Theta_e
   // cut only with one unit and one pair (the units reach Theta_e through roundings), Stokes rows and the optical-depth row only (the
   // rows the polarized transfer kernels write), Theta_e from R_high / R_low (code_kappa: passes) - and the lanes of a chunk fit one grid
   if (vs.n_pol >= 2) {
-    bool same_units = true, same_pairs = true;
+    bool same_units = true, same_pairs = true, same_mixes = true;
     for (const Variant &v : vs.list) {
       same_units = same_units && v.rho == first.rho;
       same_pairs = same_pairs && v.rat_low == first.rat_low && v.rat_high == first.rat_high;
+      same_mixes = same_mixes && SameMix(v.mix, first.mix);
     }
+    // (an electron mix enters no decision but one: Theta_e exists only where the thermal fraction is non-zero, and a Theta_e cut
+    // compares it - with such a cut, one pass asks for equal mixes as well)
     job.pol_one_pass = job.rows_only && p.plasma_model != BL_PLASMA_CODE_KAPPA && !(UnitCut(p) && !same_units)
-        && !(ThetaECut(p) && !(same_units && same_pairs)) && job.n_rays * vs.n_pol < (1ll << 31);
+        && !(ThetaECut(p) && !(same_units && same_pairs && same_mixes)) && job.n_rays * vs.n_pol < (1ll << 31);
     if (job.pol_one_pass) {
       job.variant_passes = 1;
       job.pol_coefficients_inside = false;   // (the samples go through the 64-byte row, which is where the variants part)
@@ -1206,7 +1253,7 @@ void PlanKernels(RenderJob &job) {
   }
   k.freq.polarized_frames = ctx->polarized;
   k.freq.polarized_coefficients = ctx->polarized && !job.pol_coefficients_inside;
-  k.freq.thermal_only = ctx->polarized && p.plasma_power_frac == 0.0 && p.plasma_kappa_frac == 0.0;
+  k.freq.thermal_only = ctx->polarized && job.all_thermal;   // (the parameter block and every variant)
   k.freq.coefficients_freq = job.coef_split;
   k.transfer.affine = job.fast || job.fast_formula;
   k.transfer.tau = job.tau_row;
@@ -1486,46 +1533,46 @@ void BuildTraceArgs(RenderJob &job) {
 }
 
 // Power-law and kappa-distribution constants of the coefficient formulas (simulation_coefficients.cpp:54-193); pow / exp / log
-// and K_nu are the pinned ones, tgamma the host libm's
-void FillElectronConstants(RenderJob &job, BlPlasmaDevice &pl, BlShadeCold &cold) {
-  bl_ctx *ctx = job.ctx;
-  const bl_params &p = ctx->params;
-  pl.power_frac = p.plasma_power_frac;
-  pl.plasma_p = 0.0;
-  pl.power_jj = pl.power_aa = 0.0;
-  if (p.plasma_power_frac != 0.0) {
+// and K_nu are the pinned ones, tgamma the host libm's. A function of the mix alone (and of whether the run is polarized): the shape
+// values of a distribution whose fraction is zero are not read.
+ElectronConstants FillElectronConstants(const bl_electron_mix &mix, bool polarized) {
+  ElectronConstants ec;
+  std::memset(static_cast<void *>(&ec), 0, sizeof ec);
+  ec.thermal_frac = ThermalFraction(mix);
+  ec.power_frac = mix.power_frac;
+  if (mix.power_frac != 0.0) {
     // simulation_coefficients.cpp:54-66 (unpolarized part)
-    const double plasma_p = p.plasma_p;
+    const double plasma_p = mix.p;
     const double var_a = bl_pow(3.0, plasma_p / 2.0) * (plasma_p - 1.0);
     const double var_b = 2.0 * (plasma_p + 1.0);
-    const double var_c = bl_pow(p.plasma_gamma_min, 1.0 - plasma_p) - bl_pow(p.plasma_gamma_max, 1.0 - plasma_p);
+    const double var_c = bl_pow(mix.gamma_min, 1.0 - plasma_p) - bl_pow(mix.gamma_max, 1.0 - plasma_p);
     const double var_d = std::tgamma((3.0 * plasma_p - 1.0) / 12.0);
     const double var_e = std::tgamma((3.0 * plasma_p + 19.0) / 12.0);
     const double var_f = bl_pow(3.0, (plasma_p + 1.0) / 2.0) * (plasma_p - 1.0) / 4.0;
     const double var_g = std::tgamma((3.0 * plasma_p + 2.0) / 12.0);
     const double var_h = std::tgamma((3.0 * plasma_p + 22.0) / 12.0);
-    pl.plasma_p = plasma_p;
-    pl.power_jj = var_a / var_b / var_c * var_d * var_e;
-    pl.power_aa = var_f / var_c * var_g * var_h;
-    if (ctx->polarized) {   // simulation_coefficients.cpp:67-80
+    ec.plasma_p = plasma_p;
+    ec.plasma_gamma_min = mix.gamma_min;
+    ec.power_jj = var_a / var_b / var_c * var_d * var_e;
+    ec.power_aa = var_f / var_c * var_g * var_h;
+    if (polarized) {   // simulation_coefficients.cpp:67-80
       const double var_i = 2.0 * (plasma_p + 2.0) / (plasma_p + 1.0);
-      const double var_j = bl_pow(p.plasma_gamma_min, -(plasma_p + 1.0));
-      const double var_k = bl_log(p.plasma_gamma_min);
-      ctx->power_pol[0] = -(plasma_p + 1.0) / (plasma_p + 7.0 / 3.0);
-      ctx->power_pol[1] = 0.684 * bl_pow(plasma_p, 0.49);
-      ctx->power_pol[2] = -bl_pow(0.034 * plasma_p - 0.0344, 0.086);
-      ctx->power_pol[3] = bl_pow(0.71 * plasma_p + 0.0352, 0.394);
-      ctx->power_pol[4] = (plasma_p - 1.0) / var_c;
-      ctx->power_pol[5] = -bl_pow(p.plasma_gamma_min, 2.0 - plasma_p) / (plasma_p / 2.0 - 1.0);
-      ctx->power_pol[6] = var_i * var_j * var_k;
+      const double var_j = bl_pow(mix.gamma_min, -(plasma_p + 1.0));
+      const double var_k = bl_log(mix.gamma_min);
+      ec.power_pol[0] = -(plasma_p + 1.0) / (plasma_p + 7.0 / 3.0);
+      ec.power_pol[1] = 0.684 * bl_pow(plasma_p, 0.49);
+      ec.power_pol[2] = -bl_pow(0.034 * plasma_p - 0.0344, 0.086);
+      ec.power_pol[3] = bl_pow(0.71 * plasma_p + 0.0352, 0.394);
+      ec.power_pol[4] = (plasma_p - 1.0) / var_c;
+      ec.power_pol[5] = -bl_pow(mix.gamma_min, 2.0 - plasma_p) / (plasma_p / 2.0 - 1.0);
+      ec.power_pol[6] = var_i * var_j * var_k;
     }
   }
-  cold.kappa = BlKappaDevice{};
-  if (p.plasma_kappa_frac != 0.0) {
+  if (mix.kappa_frac != 0.0) {
     // simulation_coefficients.cpp:82-193 for a polarized run
-    BlKappaDevice &kk = cold.kappa;
-    const double plasma_kappa = p.plasma_kappa, plasma_w = p.plasma_w;
-    kk.frac = p.plasma_kappa_frac;
+    BlKappaDevice &kk = ec.kappa;
+    const double plasma_kappa = mix.kappa, plasma_w = mix.w;
+    kk.frac = mix.kappa_frac;
     kk.kappa = plasma_kappa;
     kk.w = plasma_w;
     const double var_a = 4.0 * kPi * std::tgamma(plasma_kappa - 4.0 / 3.0);
@@ -1590,6 +1637,7 @@ void FillElectronConstants(RenderJob &job, BlPlasmaDevice &pl, BlShadeCold &cold
       kk.rho_v_high[c] = fit_v[lo + 1][c];
     }
   }
+  return ec;
 }
 
 // ---- the locate / coefficient kernels'
@@ -1624,9 +1672,10 @@ void BuildShadeArgs(RenderJob &job) {
     pl.plasma_ne_ni = p.plasma_ne_ni;
     pl.plasma_rat_low = job.base_rat_low;     // (the render's base, PlanJob; BindVariant each variant's)
     pl.plasma_rat_high = job.base_rat_high;
-    pl.plasma_thermal_frac = ctx->plasma_thermal_frac;
     FoldUnits(ctx, job.base_rho, pl, sa.fast_k);            // simulation_coefficients.cpp:237-239
-    FillElectronConstants(job, pl, cold);
+    const ElectronConstants ec = FillElectronConstants(job.base_mix, ctx->polarized);   // (the render's: PlanJob; BindVariant each pass's)
+    BindElectronConstants(ec, ctx->polarized, pl, sa);
+    cold.kappa = ec.kappa;
     cold.plasma_gamma = ctx->grid_meta.plasma_gamma;
     cold.plasma_gamma_i = ctx->grid_meta.plasma_gamma_i;
     cold.plasma_gamma_e = ctx->grid_meta.plasma_gamma_e;
@@ -1640,8 +1689,6 @@ void BuildShadeArgs(RenderJob &job) {
     cold.fallback_pgas = p.fallback_nan ? 0.0f : p.fallback_pgas;
     cold.fallback_kappa = p.fallback_nan ? 0.0f : p.fallback_kappa;
     pl.code_kappa = p.plasma_model == BL_PLASMA_CODE_KAPPA ? 1 : 0;
-    pl.kappa_frac_zero = p.plasma_kappa_frac == 0.0 ? 1 : 0;
-    pl.kappa_unpolarized = (p.plasma_kappa_frac != 0.0 && !ctx->polarized) ? 1 : 0;
     // cell cuts (simulation_coefficients.cpp:361-375): "cut >= 0 and value < cut". A disabled threshold goes to the
     // device as -inf (lower) / +inf (upper), against which no value - NaN included - compares true: same
     // decisions, one compare per threshold
@@ -1716,6 +1763,7 @@ void BuildShadeArgs(RenderJob &job) {
       const double sigma_max = job.cold_cuts > 1 ? variant.sigma_max : job.base_sigma_max;
       unit_cold.cut_sigma_max = sigma_max >= 0.0 ? sigma_max : std::numeric_limits<double>::infinity();
       FoldFastCuts(ctx, unit_pl, unit_cold, sigma_max);
+      if (job.variants.n_pol > 0) unit_cold.kappa = FillElectronConstants(variant.mix, ctx->polarized).kappa;   // (polarized variants: the pass's mix)
       std::memcpy(colds.data() + b * sizeof(BlShadeCold), &unit_cold, sizeof(BlShadeCold));
     }
   }
@@ -1758,6 +1806,28 @@ void BuildShadeArgs(RenderJob &job) {
     sa.pol_variants = job.variants.n_pol;
     sa.pol_variant_table = ctx->d_pol_variant_table.ptr;
   }
+  // ... and, unless every electron is thermal, every variant's electron constants in a copy of the argument block with a BlShadeCold
+  // of its own behind it (BlPolVariantArgs), uploaded like the table above when its bytes differ from what the device holds
+  sa.pol_variant_args = nullptr;
+  if (job.pol_one_pass && !job.all_thermal) {
+    ctx->d_pol_variant_args.Ensure(BL_POL_MAX_VARIANTS);   // (before the elements are made: each holds the device address of its own `cold`)
+    std::vector<unsigned char> bytes(job.variants.list.size() * sizeof(BlPolVariantArgs), 0);
+    for (size_t v = 0; v < job.variants.list.size(); v++) {
+      BlPolVariantArgs *at = reinterpret_cast<BlPolVariantArgs *>(bytes.data() + v * sizeof(BlPolVariantArgs));
+      const ElectronConstants variant_ec = FillElectronConstants(job.variants.list[v].mix, ctx->polarized);
+      at->args.plasma = sa.plasma;
+      BindElectronConstants(variant_ec, ctx->polarized, at->args.plasma, at->args);
+      at->cold.kappa = variant_ec.kappa;
+      at->args.cold = &ctx->d_pol_variant_args.ptr[v].cold;
+    }
+    if (ctx->pol_variant_args_host != bytes) {
+      ctx->pol_variant_args_host.clear();
+      Check(hipMemcpyAsync(ctx->d_pol_variant_args.ptr, bytes.data(), bytes.size(), hipMemcpyHostToDevice, stream), "variant electron constants upload");
+      Check(hipStreamSynchronize(stream), "variant electron constants upload");
+      ctx->pol_variant_args_host = bytes;
+    }
+    sa.pol_variant_args = ctx->d_pol_variant_args.ptr;
+  }
   sa.frequencies = ctx->d_freq.ptr;
   sa.n_nu = job.n_nu;
   sa.ray_max_steps = job.max_steps;
@@ -1793,10 +1863,6 @@ void BuildShadeArgs(RenderJob &job) {
     sa.slow.kappa = reinterpret_cast<const float *const *>(ctx->d_slow_table.ptr + chunk_size);
     sa.slow.times = reinterpret_cast<const double *>(ctx->d_slow_table.ptr + 2 * static_cast<size_t>(chunk_size));
     sa.slow.extrap_max = ctx->d_slow_table.ptr + 3 * static_cast<size_t>(chunk_size);
-  }
-  if (ctx->polarized) {
-    for (int c = 0; c < 7; c++) sa.power_pol[c] = ctx->power_pol[c];
-    sa.plasma_gamma_min = p.plasma_power_frac != 0.0 ? p.plasma_gamma_min : 0.0;
   }
   // Locate kernel: 256-thread workgroups. Alone it runs 4 waves per SIMD; beside the next chunk's geodesic kernel
   // (bl_set_overlap) one workgroup per CU, so that whichever of the two kernels is dispatched first cannot fill the

@@ -25,6 +25,7 @@ class Params:
         self._sweep = _capi.Sweep()   # the sweep_* keys: lists beside the block (bl_sweep), never in it
         self._sweep_cuts = _capi.SweepCuts()   # ... sweep_cut_sigma_max (bl_sweep_cuts)
         self._sweep_cameras = _capi.SweepCameras()   # ... sweep_camera_th, sweep_camera_ph (bl_sweep_cameras)
+        self._sweep_electrons = _capi.SweepElectrons()   # ... sweep_power_frac ... sweep_w (bl_sweep_electrons)
         self.num_runs = 1
 
     @property
@@ -37,8 +38,7 @@ class Params:
         self = cls()
         err = C.create_string_buffer(1024)
         runs = C.c_int(1)
-        rc = _capi.lib().bl_params_read_file_sweeps_cameras(self._buf, C.byref(self._sweep), C.byref(self._sweep_cuts), C.byref(self._sweep_cameras),
-                                                            str(path).encode(), C.byref(runs), err, len(err))
+        rc = _capi.lib().bl_params_read_file_sweep_lists(self._buf, C.byref(self.sweep_lists), str(path).encode(), C.byref(runs), err, len(err))
         if rc != 0:
             raise _capi.BlacklightError(rc, err.value.decode())
         self.num_runs = runs.value
@@ -60,8 +60,7 @@ class Params:
 
     def set_line(self, line):
         err = C.create_string_buffer(1024)
-        rc = _capi.lib().bl_params_set_line_sweeps_cameras(self._buf, C.byref(self._sweep), C.byref(self._sweep_cuts), C.byref(self._sweep_cameras),
-                                                           line.encode(), err, len(err))
+        rc = _capi.lib().bl_params_set_line_sweep_lists(self._buf, C.byref(self.sweep_lists), line.encode(), err, len(err))
         if rc != 0:
             raise _capi.BlacklightError(rc, err.value.decode())
 
@@ -79,6 +78,7 @@ class Params:
         C.memmove(C.byref(other._sweep), C.byref(self._sweep), C.sizeof(_capi.Sweep))
         C.memmove(C.byref(other._sweep_cuts), C.byref(self._sweep_cuts), C.sizeof(_capi.SweepCuts))
         C.memmove(C.byref(other._sweep_cameras), C.byref(self._sweep_cameras), C.sizeof(_capi.SweepCameras))
+        C.memmove(C.byref(other._sweep_electrons), C.byref(self._sweep_electrons), C.sizeof(_capi.SweepElectrons))
         other.num_runs = self.num_runs
         return other
 
@@ -136,9 +136,46 @@ class Params:
         return [(float(th[c]) if th_given.value else None, float(ph[c]) if ph_given.value else None) for c in range(n.value)]
 
     @property
+    def sweep_lists(self):
+        """A bl_sweep_lists that names this object's four structs (what the parser fills and Context applies: bl_apply_sweep_lists)."""
+        return _capi.SweepLists(C.pointer(self._sweep), C.pointer(self._sweep_cuts), C.pointer(self._sweep_cameras), C.pointer(self._sweep_electrons))
+
+    @property
+    def sweep_electron_lists(self):
+        """The bl_sweep_electrons filled by sweep_power_frac ... sweep_w."""
+        return self._sweep_electrons
+
+    @property
+    def sweep_electrons(self):
+        """The seven electron lists as written, by the key without its sweep_ prefix: {"power_frac": [...], ...}; [] for an absent key."""
+        e = self._sweep_electrons
+        return {key: [float(x) for x in getattr(e, key)[:getattr(e, "n_" + key)]] for key in _capi.ELECTRON_MIX_KEYS}
+
+    @property
+    def has_sweep_electrons(self):
+        return any(getattr(self._sweep_electrons, "n_" + key) > 0 for key in _capi.ELECTRON_MIX_KEYS)
+
+    def resolved_electrons(self):
+        """The tuples the electron lists and the three sweep lists mean together (bl_sweep_electrons_resolve): (rat_low, rat_high,
+        rho_cgs, mixes) with one entry per variant, a mix being a mapping with Context.set_polarized_variants()'s keys; four empty lists
+        when no key that makes polarized variants is written. Raises BlacklightError where the lists do not fit each other or the
+        block is not polarized."""
+        n = C.c_int(0)
+        out = _capi.Sweep()
+        mixes = (_capi.ElectronMix * _capi.BL_MAX_SWEEP)()
+        err = C.create_string_buffer(1024)
+        rc = _capi.lib().bl_sweep_electrons_resolve(C.byref(self._sweep_electrons), C.byref(self._sweep), self.ptr, C.byref(n), C.byref(out),
+                                                    C.cast(mixes, C.c_void_p), err, len(err))
+        if rc != 0:
+            raise _capi.BlacklightError(rc, err.value.decode())
+        count = n.value
+        return ([float(x) for x in out.rat_low[:count]], [float(x) for x in out.rat_high[:count]], [float(x) for x in out.rho_cgs[:count]],
+                [{key: getattr(mixes[v], key) for key in _capi.ELECTRON_MIX_KEYS} for v in range(count)])
+
+    @property
     def has_sweep(self):
         return (self._sweep.n_rat_low > 0 or self._sweep.n_rat_high > 0 or self._sweep.n_rho_cgs > 0 or self._sweep_cuts.n_sigma_max > 0
-                or self._sweep_cameras.n_th > 0 or self._sweep_cameras.n_ph > 0)
+                or self._sweep_cameras.n_th > 0 or self._sweep_cameras.n_ph > 0 or self.has_sweep_electrons)
 
     def resolved_sweep(self):
         """The lists as the setters receive them (bl_sweep_resolve): (polarized, rat_low, rat_high, rho_cgs). A polarized block's

@@ -236,6 +236,45 @@ BL_API int bl_params_read_file_sweeps_cameras(bl_params *p, bl_sweep *sweep, bl_
 BL_API int bl_sweep_cameras_resolve(const bl_sweep_cameras *cameras, int *n, double *th_deg, double *ph_deg, int *th_given, int *ph_given,
                                     char *err, size_t err_len);
 
+/* Seven more keys, in a fourth struct beside the three above (whose sizes are part of the ABI) - each is "sweep_" and a plasma_ key
+ * without its prefix, the electron distribution of a polarized variant (bl_set_polarized_variants_electrons):
+ *     sweep_power_frac = 0, 0.3, 0.2        plasma_power_frac      sweep_kappa_frac = 0.4, 0, 0.25     plasma_kappa_frac
+ *     sweep_p          = 2.5                plasma_p               sweep_kappa      = 4, 4, 4.3        plasma_kappa
+ *     sweep_gamma_min  = 2                  plasma_gamma_min       sweep_w          = 1.5, 1.5, 2.5    plasma_w
+ *     sweep_gamma_max  = 1000               plasma_gamma_max
+ * The same list forms and error texts with the key's name, and one of their own: "Invalid value (<text>) in list (<key>) in input
+ * file: must be finite." Polarized blocks only; with sweep_rat_low, sweep_rat_high and sweep_rho_cgs they form a LIST OF TUPLES, not
+ * a product. N is the number of triples those three keys give where pairs or units are written (the rule above), else the longest
+ * electron list. Every electron list has N entries, or one (every variant at that value), or is absent (the block's value). Anything
+ * else: "sweep_<key> must have one entry or as many as the other sweep lists (<n> and <N>) in input file."; an electron key in a
+ * block that is not polarized: "sweep_<key> needs image_polarization = true in input file." - both BL_E_INPUT, raised at the end of
+ * every bl_params_read_file*, in bl_sweep_electrons_resolve and in bl_apply_sweep_lists, as the camera lists' are. What the setter
+ * checks (kappa within [3.5, 5], ...) it checks, in its words. n_* = 0: key absent.
+ * Every parser call above accepts and validates the seven keys and drops their values; a file without them parses, applies and
+ * renders exactly as before. The calls below keep every list, and are the ones a next key will be added to: bl_sweep_lists names
+ * the structs (a NULL member: that struct's keys are validated and dropped). */
+typedef struct bl_sweep_electrons {
+  int32_t n_power_frac, n_p, n_gamma_min, n_gamma_max, n_kappa_frac, n_kappa, n_w;
+  int32_t reserved;
+  double power_frac[BL_MAX_SWEEP], p[BL_MAX_SWEEP], gamma_min[BL_MAX_SWEEP], gamma_max[BL_MAX_SWEEP];
+  double kappa_frac[BL_MAX_SWEEP], kappa[BL_MAX_SWEEP], w[BL_MAX_SWEEP];
+} bl_sweep_electrons;
+typedef struct bl_sweep_lists {
+  bl_sweep *sweep;
+  bl_sweep_cuts *cuts;
+  bl_sweep_cameras *cameras;
+  bl_sweep_electrons *electrons;
+} bl_sweep_lists;   /* NULL member: dropped */
+BL_API int bl_params_set_line_sweep_lists(bl_params *p, const bl_sweep_lists *lists, const char *line, char *err, size_t err_len);
+BL_API int bl_params_read_file_sweep_lists(bl_params *p, const bl_sweep_lists *lists, const char *path, int *num_runs, char *err, size_t err_len);
+/* The tuples the electron lists and the three lists of `sweep` (NULL: none written) mean together: *n of them (0: no list of either
+ * kind that makes variants), *resolved the N triples as bl_sweep_resolve gives them - the block's pair and unit N times where only
+ * electron lists are written - and mix[v] variant v's distribution (an array of BL_MAX_SWEEP), the block's value where a list is
+ * absent. Without an electron list this is bl_sweep_resolve with the block's mix N times. Any output may be NULL. */
+struct bl_electron_mix;
+BL_API int bl_sweep_electrons_resolve(const bl_sweep_electrons *e, const bl_sweep *sweep, const bl_params *p, int *n, bl_sweep *resolved,
+                                      struct bl_electron_mix *mix, char *err, size_t err_len);
+
 /* ------------------------------------------------------------------ grid view
  * What RadiationIntegrator::ObtainGridData() takes from SimulationReader
  * (simulation_sampling.cpp:26-95). All pointers are host pointers borrowed for the duration of
@@ -480,7 +519,8 @@ BL_API int bl_num_density_units(const bl_ctx *ctx);   /* 0 = unset: the paramete
  * coefficient-kernel wave per (64 samples, variant) and a transfer lane per (ray, variant). Everything else: one shading pass per
  * variant over the shared samples (launches_shade = n_chunks * n).
  * bl_set_polarized_variants is bl_set_polarized_variants_sigma (below) with sigma_max = NULL: every variant is rendered under the
- * parameter block's own cut_sigma_max, and the cuts an earlier call of that function set are gone. */
+ * parameter block's own cut_sigma_max, and the cuts an earlier call of that function set are gone - as are, after either call, the
+ * electron mixes an earlier bl_set_polarized_variants_electrons set. */
 #define BL_MAX_POLARIZED_VARIANTS 16
 BL_API int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs);
 /* ... with a sigma cut each: (R_low, R_high, simulation_rho_cgs, cut_sigma_max) quadruples, a list like the triples and not a
@@ -497,6 +537,37 @@ BL_API int bl_set_polarized_variants(bl_ctx *ctx, int n, const double *rat_low, 
 BL_API int bl_set_polarized_variants_sigma(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs,
                                            const double *sigma_max);
 BL_API int bl_num_polarized_variants(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own pair and unit; -1: no context */
+/* ... with an electron distribution each: (R_low, R_high, simulation_rho_cgs, cut_sigma_max, mix) tuples, a list and not a product.
+ * A mix is the seven plasma_* values that say which share of the electrons is a power law and which a kappa distribution (the rest
+ * is thermal: 1 - (power_frac + kappa_frac), formed as bl_init forms it). sigma_max = NULL: the parameter block's cut_sigma_max for
+ * every variant; mix = NULL: the parameter block's own seven values for every variant - the call is then exactly
+ * bl_set_polarized_variants or bl_set_polarized_variants_sigma. n = 0 clears; n = 1 plans as a fresh render with that tuple in the
+ * parameter block. The range of n, the refusals, image rows (row v * n_q + q is row q of variant v), bl_num_variants and the .vNN
+ * tags are those of the triples: a mix adds no rows, it changes what variant v is. Variant v's rows are the bits of a render with
+ * its R_low, R_high, unit, cut and seven plasma_* values in the parameter block - in the exact tier, and in the tolerant one under
+ * the conditions stated for the triples above; sample_num, sample_flags and the camera outputs come out once.
+ * Checked per variant when the call is made: every value that is read must be finite (BL_E_ARG, the variant's number in the text);
+ * with kappa_frac != 0 a kappa outside [3.5, 5] is refused (BL_E_ARG: "Polarized transport only supports kappa in [3.5, 5]."); the
+ * reference's warnings - a fraction of power-law, kappa-distribution or thermal electrons outside [0, 1], and "Polarized transport
+ * will interpolate formulas based on kappa." for a kappa that is none of 3.5, 4, 4.5, 5 - go to bl_warnings, each at most once per
+ * call. With power_frac == 0 (kappa_frac == 0) that distribution's shape values - p, gamma_min, gamma_max (kappa, w) - are neither
+ * read nor checked, and bl_polarized_variant_electrons returns them as given. No other range is checked: the reference checks none.
+ * A refused or failed call changes nothing. A later bl_set_polarized_variants or bl_set_polarized_variants_sigma drops the mixes.
+ * No decision of a render depends on a mix - sample counts, flags, cells and cuts do not - except that Theta_e exists only where
+ * the thermal fraction is non-zero: where the triples render in one pass the tuples do too (bl_stats.launches_shade = n_chunks),
+ * unless a Theta_e cut is set and the mixes differ (one shading pass per variant then, launches_shade = n_chunks * n); every wave
+ * of bl_polarized_coefficients_kernel reads its variant's electron constants from a device table. The mixes are no part of what the
+ * resident geodesics depend on: changing them between renders of a camera reuses the records. */
+typedef struct bl_electron_mix {
+  double power_frac, p, gamma_min, gamma_max;   /* plasma_power_frac, plasma_p, plasma_gamma_min, plasma_gamma_max */
+  double kappa_frac, kappa, w;                  /* plasma_kappa_frac, plasma_kappa, plasma_w */
+  double reserved;                              /* 0 */
+} bl_electron_mix;
+BL_API int bl_set_polarized_variants_electrons(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high,
+                                               const double *rho_cgs, const double *sigma_max, const bl_electron_mix *mix);
+/* The mix variant `variant` renders with - the parameter block's own where none was set. BL_E_ARG: variant outside
+ * [0, max(1, bl_num_polarized_variants)). */
+BL_API int bl_polarized_variant_electrons(const bl_ctx *ctx, int variant, bl_electron_mix *out);
 /* Sigma cuts (cut_sigma_max, the magnetisation above which a cell is left out: sigma = b.b / rho in code units,
  * simulation_coefficients.cpp:361-375) rendered by one bl_render - the standard way to take the jet funnel out of an image. n = 0
  * (what a context starts with): the parameter block's own cut_sigma_max. 1 <= n <= BL_MAX_SIGMA_CUTS: n values with the reference's
@@ -560,6 +631,11 @@ BL_API int bl_apply_sweeps(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cu
  * block's own, to the bit; cameras may be NULL or empty: bl_apply_sweeps). On failure the context holds no model, unit, cut or camera
  * the call brought. */
 BL_API int bl_apply_sweeps_cameras(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts, const bl_sweep_cameras *cameras);
+/* ... and with the electron lists of the file: every list of `lists` (a NULL member: none). Without an electron list this is
+ * bl_apply_sweeps_cameras; with one, the tuples of bl_sweep_electrons_resolve go to bl_set_polarized_variants_electrons under the
+ * parameter block's cut_sigma_max. On failure - a list error (BL_E_INPUT), a setter's refusal in its words - the context holds
+ * nothing the call brought. */
+BL_API int bl_apply_sweep_lists(bl_ctx *ctx, const bl_sweep_lists *lists);
 /* The angles of the camera list as given, in degrees (an angle taken from the parameter block: its radians x 180 / pi): the first
  * min(n, bl_num_cameras) entries of both arrays. */
 BL_API int bl_cameras_get(const bl_ctx *ctx, int n, double *th_deg, double *ph_deg);
