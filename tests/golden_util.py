@@ -9,7 +9,7 @@ import numpy as np
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 CASES = sorted(f[:-4] for f in os.listdir(GOLDEN_DIR)
-               if f.endswith(".npz") and not f.startswith(("mock_", "window_", "slow_")))
+               if f.endswith(".npz") and not f.startswith(("mock_", "window_", "slow_", "cut_")))
 # cases whose parameters are inside the scope of the HIP path today
 GPU_CASES = list(CASES)
 
@@ -21,6 +21,15 @@ def load_case(name):
     params = json.loads(str(fx["params"]))
     mock_args = json.loads(str(fx["mock_args"])) if "mock_args" in fx.files else None
     return fx, params, mock_args
+
+
+def load_cut_cases():
+    """tests/golden/cut_each.npz (tools/make_goldens.py make_cut_fixture): the stock reference's 16^2 image with every optional cut
+    switched on alone. {case name: dict(params, mock_args (None in formula mode), I_nu, sample_num, sample_flags)} in the file's order."""
+    fx = np.load(os.path.join(GOLDEN_DIR, "cut_each.npz"), allow_pickle=False)
+    return {name: dict(params=json.loads(str(fx[f"{name}_params"])), mock_args=json.loads(str(fx[f"{name}_mock_args"])),
+                       I_nu=fx[f"{name}_I_nu"], sample_num=fx[f"{name}_sample_num"], sample_flags=fx[f"{name}_sample_flags"])
+            for name in json.loads(str(fx["cases"]))}
 
 
 def golden_grid(mock_args):

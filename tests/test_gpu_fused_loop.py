@@ -27,6 +27,7 @@ import oracle_api
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+PER_PIXEL = 1.0e-10   # the fused kernel against the exact tier: per pixel, relative to the pixel's own value (tests/test_gpu_cuts_each.py imports it)
 NO_CUT = dict(cut_sigma_max=-1.0)
 CUTS = {
     "none": dict(NO_CUT),
@@ -125,7 +126,7 @@ def test_cut_forms_give_the_same_frame(frame_grid, name):
     assert gu.same_bits(default["image"], general["image"]).all()
     for tolerant in (default, general):
         _same_rays(tolerant, exact)
-        assert _relative_per_pixel(tolerant, exact) <= 1.0e-10
+        assert _relative_per_pixel(tolerant, exact) <= PER_PIXEL
     if name != "none":   # (the cut is seen: the frame is not the frame without it)
         assert not gu.same_bits(exact["image"], _exact_frame(frame_grid, "none", CUTS["none"])["image"]).all()
 
@@ -162,6 +163,6 @@ def test_a_frame_with_spin(frame_grid):
     print(f"a = 0.9: vs exact {_relative_per_pixel(tolerant, exact):.2e}, local_angles {tolerant['stats'].local_angles}, "
           f"deferred {tolerant['stats'].n_deferred} of {tolerant['stats'].n_samples}")
     _same_rays(tolerant, exact)
-    assert _relative_per_pixel(tolerant, exact) <= 1.0e-10
+    assert _relative_per_pixel(tolerant, exact) <= PER_PIXEL
     _same_rays(tolerant, general)
     assert gu.same_bits(tolerant["image"], general["image"]).all()

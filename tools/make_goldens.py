@@ -12,6 +12,7 @@ with checkpoint_geodesic_save = true, and the fixture records, for both tiers, t
 sample_num, sample_flags, the camera frame, and complete per-sample data for a few rays.
 
 Usage:  /opt/conda/bin/python3.9 tools/make_goldens.py [case ...]
+        (`cut_each`: tests/golden/cut_each.npz, every optional cut alone - the stock build only, images and counts, no ray dumps)
 """
 import json
 import os
@@ -1294,10 +1295,92 @@ def make_binding_adaptive_fixture():
           "warnings:", repr(expected["B_warnings"]))
 
 
+# ------------------------------------------------------------------------------------------------
+# Every optional cut alone (tests/golden/cut_each.npz): 16^2 images of the stock reference over the small mock (formula cases: no
+# grid) with one cut switched on per case - the fourteen cell thresholds (simulation_coefficients.cpp:361-374), the nine geometric
+# settings (simulation_sampling.cpp:246-292), three of them in formula mode (formula_coefficients.cpp:78-116) and two with spin, where
+# r is the Kerr-Schild radius. Tier A only: the pinned-math comparison of these cases is the oracle's (tests/test_cuts_each_host.py).
+# No formula-mode case has cut_midplane_theta or cut_midplane_z: for a sample they cut, formula_coefficients.cpp:97 and :104 store into
+# sample_cut, which only simulation_sampling.cpp:155 allocates, and the stock binary ends in a segmentation fault - the reference has no
+# image to record there (the tests compare those two with the oracle only: tests/cut_cases.py UNRECORDED).
+# Every value was chosen on the CPU oracle so that the cut alone leaves between CUT_SHARE[0] and CUT_SHARE[1] of the flux of the
+# image without a cut; a recording outside that says nothing about its cut and is not written (checked here on the recorded images,
+# and again on the oracle by tests/test_cuts_each_host.py).
+CUT_SHARE = (0.05, 0.95)
+CUT_PLANE = dict(cut_plane="true", cut_plane_origin="1.0,-2.0,0.5", cut_plane_normal="1.0,0.2,0.1")
+CUT_SPIN = dict(simulation_a=0.5, fallback_nan="false", fallback_rho=1.0e-6, fallback_pgas=1.0e-8)   # (no NaN pixel: a sum to take a share of)
+CUT_THRESHOLDS = dict(cut_rho_min=3.2e-17, cut_rho_max=2.7e-17, cut_n_e_min=1.9e7, cut_n_e_max=1.6e7, cut_p_gas_min=770.0,
+                      cut_p_gas_max=620.0, cut_theta_e_min=4.7, cut_theta_e_max=4.4, cut_b_min=36.0, cut_b_max=31.0,
+                      cut_sigma_min=0.0038, cut_sigma_max=0.0031, cut_beta_inverse_min=0.071, cut_beta_inverse_max=0.06)
+CUT_CASES = dict(
+    [("sim_none", ("sim", {}))]
+    + [(key, ("sim", {key: value})) for key, value in CUT_THRESHOLDS.items()]
+    + [("cut_omit_near", ("sim", dict(cut_omit_near="true"))), ("cut_omit_far", ("sim", dict(cut_omit_far="true"))),
+       ("cut_omit_in", ("sim", dict(cut_omit_in=6.0))), ("cut_omit_out", ("sim", dict(cut_omit_out=6.0))),
+       ("cut_midplane_theta_pos", ("sim", dict(cut_midplane_theta=6.0))), ("cut_midplane_theta_neg", ("sim", dict(cut_midplane_theta=-10.0))),
+       ("cut_midplane_z_pos", ("sim", dict(cut_midplane_z=0.6))), ("cut_midplane_z_neg", ("sim", dict(cut_midplane_z=-1.0))),
+       ("cut_plane", ("sim", CUT_PLANE)),
+       ("formula_none", ("formula", {})),
+       ("formula_cut_omit_far", ("formula", dict(cut_omit_far="true"))), ("formula_cut_omit_in", ("formula", dict(cut_omit_in=12.0))),
+       ("formula_cut_plane", ("formula", CUT_PLANE)),
+       ("spin_cut_midplane_theta", ("sim", dict(CUT_SPIN, cut_midplane_theta=6.0))),
+       ("spin_cut_omit_out", ("sim", dict(CUT_SPIN, cut_omit_out=6.0)))])
+
+
+def cut_case_params(name):
+    """The .input parameters of one case of CUT_CASES: the base's own cut_sigma_max = 1.0 is off wherever it is not the cut under test."""
+    kind, overrides = CUT_CASES[name]
+    params = dict(SIM_BASE if kind == "sim" else FORMULA_BASE, camera_resolution=16)
+    if kind == "sim":
+        params["cut_sigma_max"] = -1.0
+    params.update(overrides)
+    return params
+
+
+def make_cut_fixture():
+    workdir = os.path.join(WORK, "cut_each")
+    os.makedirs(os.path.join(workdir, "data"), exist_ok=True)
+    os.makedirs(os.path.join(workdir, "output"), exist_ok=True)
+    mock_path = os.path.join(workdir, "data", "mock.athdf")
+    args = [sys.executable, "-W", "ignore", MOCK_SCRIPT, mock_path]
+    for key, value in SMALL_MOCK.items():
+        args += [f"--{key}", str(value)]
+    subprocess.run(args, check=True)
+    fixture = {"cases": json.dumps(list(CUT_CASES))}
+    flux = {}
+    for name, (kind, _) in CUT_CASES.items():
+        params = cut_case_params(name)
+        write_input(os.path.join(workdir, "case.input"), params)
+        run_reference(workdir, "case.input", preload=False)   # tier A: the stock build, nothing preloaded
+        npz = np.load(os.path.join(workdir, "output", "out.npz"))
+        chk = read_checkpoint(os.path.join(workdir, "data", "geo.dat"), [])
+        os.remove(os.path.join(workdir, "data", "geo.dat"))
+        test_params = {k: v for k, v in params.items() if k not in ("checkpoint_geodesic_save", "checkpoint_geodesic_file")}
+        test_params["checkpoint_geodesic_save"] = "false"
+        fixture[f"{name}_params"] = json.dumps(test_params)
+        fixture[f"{name}_mock_args"] = json.dumps(SMALL_MOCK if kind == "sim" else None)
+        fixture[f"{name}_I_nu"] = npz["I_nu"].reshape(-1)
+        fixture[f"{name}_sample_num"] = chk["sample_num"]
+        fixture[f"{name}_sample_flags"] = chk["sample_flags"]
+        assert not np.isnan(fixture[f"{name}_I_nu"]).any(), name
+        flux[name] = float(fixture[f"{name}_I_nu"].sum())
+    for name, (kind, _) in CUT_CASES.items():
+        if name.endswith("_none"):
+            continue
+        share = flux[name] / flux["sim_none" if kind == "sim" else "formula_none"]
+        print(f"{name}: {share:.3f} of the flux left")
+        if not CUT_SHARE[0] <= share <= CUT_SHARE[1]:
+            raise RuntimeError(f"{name}: the cut leaves {share:.3f} of the flux, outside {CUT_SHARE}: fixture not written")
+    np.savez_compressed(os.path.join(OUT, "cut_each.npz"), **fixture)
+    print(f"cut_each: {len(CUT_CASES)} cases written")
+
+
 if __name__ == "__main__":
     names = sys.argv[1:] or (["mock"] + list(CASES))
     for case_name in names:
-        if case_name == "mock":
+        if case_name == "cut_each":
+            make_cut_fixture()
+        elif case_name == "mock":
             make_mock_fixture()
         elif case_name == "window_1024":
             make_window_fixture()
