@@ -167,6 +167,7 @@ def lib():
     L.bl_write_output_camera.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(OutputDesc), C.c_int, C.c_int]
     L.bl_camera_output_path.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.bl_num_variants.argtypes = [C.c_void_p]
+    L.bl_variants_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     L.bl_write_output_variant.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(OutputDesc), C.c_int]
     L.bl_variant_output_path.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.bl_init.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]

@@ -40,31 +40,26 @@ class Context:
 
     def apply_sweep(self, params=None):
         """bl_apply_sweep_lists: the sweep_rat_low / sweep_rat_high / sweep_rho_cgs lists of `params` (default: this context's) as electron
-        models and density units, or as polarized triples, its sweep_cut_sigma_max list as sigma cuts and its sweep_camera_th /
-        sweep_camera_ph lists as cameras (bl_apply_sweeps_cameras). An empty sweep changes nothing."""
+        models and density units, or as polarized triples (with the electron lists: tuples), its sweep_cut_sigma_max list as sigma cuts
+        and its sweep_camera_th / sweep_camera_ph lists as cameras - all of them or, where one is refused, none. An empty sweep changes
+        nothing."""
         params = params or self.params
-        if not params.has_sweep:
-            return
-        polarized, low, high, rho = params.resolved_sweep()
-        if params.has_sweep_electrons:   # (polarized tuples: the triples with the electron lists' length)
-            low, high, rho, _ = params.resolved_electrons()
-        self._check(self._lib.bl_apply_sweep_lists(self._ctx, C.byref(params.sweep_lists)))
-        if params.sweep_cut_sigma_max:
-            self._sigma_cuts = params.sweep_cut_sigma_max
-        if polarized:
-            self._polarized_variants = [(h, lo, u) for h, lo, u in zip(high, low, rho)]
-            self._polarized_cuts = None   # (bl_set_polarized_variants: the parameter block's cut for every triple)
-            self._polarized_electrons = params.has_sweep_electrons
-        else:
-            if low:
-                self._electron_models = [(h, lo) for h, lo in zip(high, low)]
-            if rho:
-                self._density_units = list(rho)
+        if params.has_sweep:
+            self._check(self._lib.bl_apply_sweep_lists(self._ctx, C.byref(params.sweep_lists)))
 
     @property
     def num_variants(self):
         """Images one render produces (bl_num_variants): models x units x sigma cuts, or polarized triples."""
         return self._lib.bl_num_variants(self._ctx)
+
+    def _variants(self):
+        """What the context renders (bl_variants_get), the one record of it: the columns rat_low, rat_high, rho_cgs, sigma_max over the
+        images in row order - model-major, then unit, then cut, or the triples - and the flags (1: the triples carry their own cuts,
+        2: their own electron mixes)."""
+        n = self.num_variants
+        columns, flags = np.zeros((4, n)), C.c_int(0)
+        self._check(self._lib.bl_variants_get(self._ctx, n, *(column.ctypes.data_as(C.c_void_p) for column in columns), C.byref(flags)))
+        return columns.tolist(), flags.value
 
     def variant_output_path(self, snapshot=0, variant=0, camera=0):
         """The file name write_output(variant=..., camera=...) uses without `path` (bl_camera_output_path): output_file, the file number
@@ -246,12 +241,13 @@ class Context:
         low = np.ascontiguousarray(low)
         self._check(self._lib.bl_set_electron_models(self._ctx, int(high.size), low.ctypes.data_as(C.c_void_p),
                                                      high.ctypes.data_as(C.c_void_p)))
-        self._electron_models = [(float(h), float(lo)) for h, lo in zip(high, low)]
 
     @property
     def electron_models(self):
         """The (rat_high, rat_low) pairs set_electron_models() set; [] when the parameter block's pair is rendered."""
-        return list(getattr(self, "_electron_models", []))
+        (low, high, _, _), _ = self._variants()
+        stride = max(1, self.num_density_units) * max(1, self.num_sigma_cuts)
+        return [(high[m * stride], low[m * stride]) for m in range(self.num_electron_models)]
 
     @property
     def num_electron_models(self):
@@ -263,12 +259,12 @@ class Context:
         its units one after another (render()["image_by_unit"]: (n_models, n_units, n_q, n_rays)); geodesics stay resident."""
         units = np.ascontiguousarray(np.atleast_1d(np.asarray(rho_cgs, dtype=np.float64)).ravel())
         self._check(self._lib.bl_set_density_units(self._ctx, int(units.size), units.ctypes.data_as(C.c_void_p)))
-        self._density_units = [float(u) for u in units]
 
     @property
     def density_units(self):
         """The simulation_rho_cgs values set_density_units() set; [] when the parameter block's unit is rendered."""
-        return list(getattr(self, "_density_units", []))
+        (_, _, rho, _), _ = self._variants()
+        return [rho[u * max(1, self.num_sigma_cuts)] for u in range(self.num_density_units)]
 
     @property
     def num_density_units(self):
@@ -281,12 +277,11 @@ class Context:
         another (render()["image_by_cut"]: (n_models, n_units, n_cuts, n_q, n_rays)); geodesics stay resident."""
         cuts = np.ascontiguousarray(np.atleast_1d(np.asarray(sigma_max, dtype=np.float64)).ravel())
         self._check(self._lib.bl_set_sigma_cuts(self._ctx, int(cuts.size), cuts.ctypes.data_as(C.c_void_p)))
-        self._sigma_cuts = [float(c) for c in cuts]
 
     @property
     def sigma_cuts(self):
         """The cut_sigma_max values set_sigma_cuts() set; [] when the parameter block's cut is rendered."""
-        return list(getattr(self, "_sigma_cuts", []))
+        return self._variants()[0][3][:self.num_sigma_cuts]
 
     @property
     def num_sigma_cuts(self):
@@ -384,24 +379,19 @@ class Context:
                                                                   high.ctypes.data_as(C.c_void_p), unit.ctypes.data_as(C.c_void_p),
                                                                   cuts.ctypes.data_as(C.c_void_p) if cuts is not None else None,
                                                                   C.cast(mixes, C.c_void_p) if mixes is not None else None))
-        self._polarized_variants = [(float(h), float(lo), float(u)) for h, lo, u in zip(high, low, unit)]
-        self._polarized_cuts = [float(c) for c in cuts] if cuts is not None and high.size > 0 else None
-        self._polarized_electrons = mixes is not None
 
     @property
     def polarized_variants(self):
         """The (rat_high, rat_low, rho_cgs) triples set_polarized_variants() set; [] when the parameter block's are rendered."""
-        held = list(getattr(self, "_polarized_variants", []))
-        if len(held) != self.num_polarized_variants:   # (set behind this object's back, through the C interface)
-            raise RuntimeError("polarized_variants: the context holds variants that set_polarized_variants() did not set")
-        return held
+        (low, high, rho, _), _ = self._variants()
+        return [(high[v], low[v], rho[v]) for v in range(self.num_polarized_variants)]
 
     @property
     def polarized_cuts(self):
         """The variants' sigma cuts set_polarized_variants(sigma_max=...) set, one per variant; None when every variant is rendered
         under the parameter block's own cut_sigma_max."""
-        held = getattr(self, "_polarized_cuts", None)
-        return list(held) if held is not None else None
+        (_, _, _, sigma_max), flags = self._variants()
+        return sigma_max if flags & 1 else None
 
     def _block_electrons(self):
         """The parameter block's own electron distribution, as a mapping with set_polarized_variants()'s keys."""
@@ -422,7 +412,7 @@ class Context:
     @property
     def polarized_electrons_set(self):
         """True when the variants carry distributions of their own (set_polarized_variants(electrons=...))."""
-        return bool(getattr(self, "_polarized_electrons", False))
+        return bool(self._variants()[1] & 2)
 
     @property
     def num_polarized_variants(self):

@@ -8,6 +8,8 @@
 // back to a CPU path.
 #include "bl_ctx.h"
 
+#include <optional>
+
 namespace {
 
 thread_local std::string g_global_error;
@@ -449,6 +451,139 @@ Variants ResolveVariants(const bl_ctx *ctx) {
         for (const double sigma_max : v.n_cuts > 0 ? ctx->sigma_cuts : own_cut) v.list.push_back({model.rat_low, model.rat_high, unit.rho, sigma_max, BlockMix(p)});
   return v;
 }
+
+// The five lists a context holds, each as a check and a store. A check reads the parameter block and the call's arguments and nothing a
+// setter stored, and gives the Failure the setter reports - nothing when the call can go through. A store needs render_lock held
+// (between renders; geodesics and located samples stay: no model, unit, cut or triple enters them) and cannot fail. A setter is
+// check, store; bl_apply_sweep_lists checks every list it carries, then stores them all.
+namespace {
+using Refused = std::optional<Failure>;
+
+Refused CheckElectronModels(const bl_ctx *ctx, int n, const double *rat_low, const double *rat_high) {
+  if (n < 0 || n > BL_MAX_ELECTRON_MODELS || (n > 0 && (rat_low == nullptr || rat_high == nullptr)))
+    return Failure{BL_E_ARG, "bl_set_electron_models needs 0 <= n <= " + std::to_string(BL_MAX_ELECTRON_MODELS) + " and both ratio arrays."};
+  for (int m = 0; m < n; m++)
+    if (!std::isfinite(rat_low[m]) || !std::isfinite(rat_high[m]))
+      return Failure{BL_E_ARG, "bl_set_electron_models: model " + std::to_string(m) + " has a ratio that is not finite."};
+  if (const char *why = ElectronModelsRefusal(ctx, n)) return Failure{BL_E_UNSUPPORTED, why};
+  return std::nullopt;
+}
+void StoreElectronModels(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high) {
+  ctx->models.resize(n);
+  for (int m = 0; m < n; m++) ctx->models[m] = {rat_low[m], rat_high[m], 0.0, 0.0};
+}
+
+Refused CheckDensityUnits(const bl_ctx *ctx, int n, const double *rho_cgs) {
+  if (n < 0 || n > BL_MAX_DENSITY_UNITS || (n > 0 && rho_cgs == nullptr))
+    return Failure{BL_E_ARG, "bl_set_density_units needs 0 <= n <= " + std::to_string(BL_MAX_DENSITY_UNITS) + " and the array of units."};
+  for (int u = 0; u < n; u++)
+    if (!std::isfinite(rho_cgs[u]) || !(rho_cgs[u] > 0.0))
+      return Failure{BL_E_ARG, "bl_set_density_units: unit " + std::to_string(u) + " is not a finite value > 0."};
+  if (const char *why = DensityUnitsRefusal(ctx, n)) return Failure{BL_E_UNSUPPORTED, why};
+  return std::nullopt;
+}
+void StoreDensityUnits(bl_ctx *ctx, int n, const double *rho_cgs) {
+  ctx->units.resize(n);
+  for (int u = 0; u < n; u++) ctx->units[u] = {0.0, 0.0, rho_cgs[u], 0.0};
+}
+
+// ... the triples, with a cut and a mix each where the arrays are given; *warnings: the reference's, for a call that goes through
+Refused CheckPolarizedVariants(const bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs, const double *sigma_max,
+                               const bl_electron_mix *mix, std::vector<const char *> *warnings) {
+  if (n < 0 || n > BL_MAX_POLARIZED_VARIANTS || (n > 0 && (rat_low == nullptr || rat_high == nullptr || rho_cgs == nullptr)))
+    return Failure{BL_E_ARG, "bl_set_polarized_variants needs 0 <= n <= " + std::to_string(BL_MAX_POLARIZED_VARIANTS) + " and the three arrays."};
+  for (int v = 0; v < n; v++) {
+    if (!std::isfinite(rat_low[v]) || !std::isfinite(rat_high[v]))
+      return Failure{BL_E_ARG, "bl_set_polarized_variants: variant " + std::to_string(v) + " has a non-finite R_low or R_high."};
+    if (!std::isfinite(rho_cgs[v]) || !(rho_cgs[v] > 0.0))
+      return Failure{BL_E_ARG, "bl_set_polarized_variants: the unit of variant " + std::to_string(v) + " is not a finite value > 0."};
+    if (sigma_max != nullptr && !std::isfinite(sigma_max[v]))
+      return Failure{BL_E_ARG, "bl_set_polarized_variants_sigma: the sigma cut of variant " + std::to_string(v) + " is not finite."};
+  }
+  if (const char *why = PolarizedVariantsRefusal(ctx, n)) return Failure{BL_E_UNSUPPORTED, why};
+  // The mixes, as bl_init checks the parameter block's (radiation_integrator.cpp:283-311): what is read must be finite - the shape values
+  // of a distribution whose fraction is zero are not read - kappa within the range of the polarized fits, and the reference's warnings,
+  // each once per call
+  bool warn_power = false, warn_kappa = false, warn_thermal = false, warn_interpolate = false;
+  for (int v = 0; mix != nullptr && v < n; v++) {
+    const bl_electron_mix &m = mix[v];
+    const std::string which = "bl_set_polarized_variants_electrons: variant " + std::to_string(v);
+    if (!std::isfinite(m.power_frac)) return Failure{BL_E_ARG, which + " has a power_frac that is not finite."};
+    if (!std::isfinite(m.kappa_frac)) return Failure{BL_E_ARG, which + " has a kappa_frac that is not finite."};
+    if (m.power_frac != 0.0) {
+      if (!std::isfinite(m.p)) return Failure{BL_E_ARG, which + " has a p that is not finite."};
+      if (!std::isfinite(m.gamma_min)) return Failure{BL_E_ARG, which + " has a gamma_min that is not finite."};
+      if (!std::isfinite(m.gamma_max)) return Failure{BL_E_ARG, which + " has a gamma_max that is not finite."};
+    }
+    if (m.kappa_frac != 0.0) {
+      if (!std::isfinite(m.kappa)) return Failure{BL_E_ARG, which + " has a kappa that is not finite."};
+      if (!std::isfinite(m.w)) return Failure{BL_E_ARG, which + " has a w that is not finite."};
+      if (m.kappa < 3.5 || m.kappa > 5.0) return Failure{BL_E_ARG, which + ": Polarized transport only supports kappa in [3.5, 5]."};
+      warn_interpolate = warn_interpolate || (m.kappa != 3.5 && m.kappa != 4.0 && m.kappa != 4.5 && m.kappa != 5.0);
+    }
+    warn_power = warn_power || m.power_frac < 0.0 || m.power_frac > 1.0;
+    warn_kappa = warn_kappa || m.kappa_frac < 0.0 || m.kappa_frac > 1.0;
+    const double thermal_frac = ThermalFraction(m);
+    warn_thermal = warn_thermal || thermal_frac < 0.0 || thermal_frac > 1.0;
+  }
+  if (warn_power) warnings->push_back("Fraction of power-law electrons outside [0, 1].");
+  if (warn_kappa) warnings->push_back("Fraction of kappa-distribution electrons outside [0, 1].");
+  if (warn_interpolate) warnings->push_back("Polarized transport will interpolate formulas based on kappa.");
+  if (warn_thermal) warnings->push_back("Fraction of thermal electrons outside [0, 1].");
+  return std::nullopt;
+}
+void StorePolarizedVariants(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs, const double *sigma_max,
+                            const bl_electron_mix *mix) {
+  ctx->triples.resize(n);
+  for (int v = 0; v < n; v++)
+    ctx->triples[v] = {rat_low[v], rat_high[v], rho_cgs[v], sigma_max != nullptr ? sigma_max[v] : 0.0, mix != nullptr ? mix[v] : bl_electron_mix{}};
+  ctx->triples_cut = n > 0 && sigma_max != nullptr;
+  ctx->triples_mix = n > 0 && mix != nullptr;
+}
+
+Refused CheckSigmaCuts(const bl_ctx *ctx, int n, const double *sigma_max) {
+  if (n < 0 || n > BL_MAX_SIGMA_CUTS || (n > 0 && sigma_max == nullptr))
+    return Failure{BL_E_ARG, "bl_set_sigma_cuts needs 0 <= n <= " + std::to_string(BL_MAX_SIGMA_CUTS) + " and the array of cuts."};
+  for (int s = 0; s < n; s++)
+    if (!std::isfinite(sigma_max[s])) return Failure{BL_E_ARG, "bl_set_sigma_cuts: cut " + std::to_string(s) + " is not finite."};
+  if (const char *why = SigmaCutsRefusal(ctx, n)) return Failure{BL_E_UNSUPPORTED, why};
+  return std::nullopt;
+}
+void StoreSigmaCuts(bl_ctx *ctx, int n, const double *sigma_max) { ctx->sigma_cuts.assign(sigma_max, sigma_max + n); }
+
+// ... the cameras, 0 <= n <= BL_MAX_CAMERAS; *list: the cameras with their frames. th_deg == nullptr: every camera at the parameter
+// block's own camera_th (its radians and its camera_pole, which no degree value need give back); ph_deg == nullptr: at the block's
+// camera_ph - what an absent sweep_camera_th or sweep_camera_ph means.
+Refused CheckCameras(const bl_ctx *ctx, int n, const double *th_deg, const double *ph_deg, std::vector<bl_ctx::Camera> *list) {
+  for (int c = 0; c < n; c++)
+    if ((th_deg != nullptr && !std::isfinite(th_deg[c])) || (ph_deg != nullptr && !std::isfinite(ph_deg[c])))
+      return Failure{BL_E_ARG, "bl_set_cameras: camera " + std::to_string(c) + " has an angle that is not finite."};
+  if (const char *why = CamerasRefusal(ctx, n)) return Failure{BL_E_UNSUPPORTED, why};
+  // Each camera's frame: what bl_init builds from the parameters with the three fields a written camera_th and camera_ph set
+  // (bl_params.cpp: degrees * pi / 180; camera_pole for a written th of exactly 0 or 180)
+  list->resize(n);
+  for (int c = 0; c < n; c++) {
+    bl_params p = ctx->params;
+    (*list)[c] = {p.camera_th * 180.0 / kPi, p.camera_ph * 180.0 / kPi, ctx->block_frame};
+    if (th_deg != nullptr) {
+      p.camera_th = th_deg[c] * kPi / 180.0;
+      p.camera_pole = (th_deg[c] == 0.0 || th_deg[c] == 180.0) ? 1 : 0;
+      (*list)[c].th_deg = th_deg[c];
+    }
+    if (ph_deg != nullptr) {
+      p.camera_ph = ph_deg[c] * kPi / 180.0;
+      (*list)[c].ph_deg = ph_deg[c];
+    }
+    bl_camera_frame_build(p, ctx->st, &(*list)[c].frame);
+  }
+  return std::nullopt;
+}
+void StoreCameras(bl_ctx *ctx, std::vector<bl_ctx::Camera> list) {   // (the resident geodesics' key holds the list: another list integrates again)
+  ctx->cameras = std::move(list);
+  ctx->cameras_uploaded = false;
+  ctx->frame = ctx->cameras.size() == 1 ? ctx->cameras[0].frame : ctx->block_frame;
+}
+}  // namespace
 }  // namespace blhost
 
 extern "C" {
@@ -1226,15 +1361,9 @@ int bl_num_variants(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int
 
 int bl_set_electron_models(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high) {
   if (ctx == nullptr) return BL_E_ARG;
-  if (n < 0 || n > BL_MAX_ELECTRON_MODELS || (n > 0 && (rat_low == nullptr || rat_high == nullptr)))
-    return Fail(ctx, Failure{BL_E_ARG, "bl_set_electron_models needs 0 <= n <= " + std::to_string(BL_MAX_ELECTRON_MODELS) + " and both ratio arrays."});
-  for (int m = 0; m < n; m++)
-    if (!std::isfinite(rat_low[m]) || !std::isfinite(rat_high[m]))
-      return Fail(ctx, Failure{BL_E_ARG, "bl_set_electron_models: model " + std::to_string(m) + " has a ratio that is not finite."});
-  if (const char *why = ElectronModelsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
-  std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: they do not depend on the model)
-  ctx->models.resize(n);
-  for (int m = 0; m < n; m++) ctx->models[m] = {rat_low[m], rat_high[m], 0.0, 0.0};
+  if (const Refused refused = CheckElectronModels(ctx, n, rat_low, rat_high)) return Fail(ctx, *refused);
+  std::lock_guard<std::mutex> guard(ctx->render_lock);
+  StoreElectronModels(ctx, n, rat_low, rat_high);
   return BL_OK;
 }
 
@@ -1242,15 +1371,9 @@ int bl_num_electron_models(const bl_ctx *ctx) { return ctx != nullptr ? static_c
 
 int bl_set_density_units(bl_ctx *ctx, int n, const double *rho_cgs) {
   if (ctx == nullptr) return BL_E_ARG;
-  if (n < 0 || n > BL_MAX_DENSITY_UNITS || (n > 0 && rho_cgs == nullptr))
-    return Fail(ctx, Failure{BL_E_ARG, "bl_set_density_units needs 0 <= n <= " + std::to_string(BL_MAX_DENSITY_UNITS) + " and the array of units."});
-  for (int u = 0; u < n; u++)
-    if (!std::isfinite(rho_cgs[u]) || !(rho_cgs[u] > 0.0))
-      return Fail(ctx, Failure{BL_E_ARG, "bl_set_density_units: unit " + std::to_string(u) + " is not a finite value > 0."});
-  if (const char *why = DensityUnitsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
-  std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: they do not depend on the unit)
-  ctx->units.resize(n);
-  for (int u = 0; u < n; u++) ctx->units[u] = {0.0, 0.0, rho_cgs[u], 0.0};
+  if (const Refused refused = CheckDensityUnits(ctx, n, rho_cgs)) return Fail(ctx, *refused);
+  std::lock_guard<std::mutex> guard(ctx->render_lock);
+  StoreDensityUnits(ctx, n, rho_cgs);
   return BL_OK;
 }
 
@@ -1259,52 +1382,11 @@ int bl_num_density_units(const bl_ctx *ctx) { return ctx != nullptr ? static_cas
 int bl_set_polarized_variants_electrons(bl_ctx *ctx, int n, const double *rat_low, const double *rat_high, const double *rho_cgs, const double *sigma_max,
                                         const bl_electron_mix *mix) {
   if (ctx == nullptr) return BL_E_ARG;
-  if (n < 0 || n > BL_MAX_POLARIZED_VARIANTS || (n > 0 && (rat_low == nullptr || rat_high == nullptr || rho_cgs == nullptr)))
-    return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants needs 0 <= n <= " + std::to_string(BL_MAX_POLARIZED_VARIANTS) + " and the three arrays."});
-  for (int v = 0; v < n; v++) {
-    if (!std::isfinite(rat_low[v]) || !std::isfinite(rat_high[v]))
-      return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants: variant " + std::to_string(v) + " has a non-finite R_low or R_high."});
-    if (!std::isfinite(rho_cgs[v]) || !(rho_cgs[v] > 0.0))
-      return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants: the unit of variant " + std::to_string(v) + " is not a finite value > 0."});
-    if (sigma_max != nullptr && !std::isfinite(sigma_max[v]))
-      return Fail(ctx, Failure{BL_E_ARG, "bl_set_polarized_variants_sigma: the sigma cut of variant " + std::to_string(v) + " is not finite."});
-  }
-  if (const char *why = PolarizedVariantsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
-  // The mixes, as bl_init checks the parameter block's (radiation_integrator.cpp:283-311): what is read must be finite - the shape values
-  // of a distribution whose fraction is zero are not read - kappa within the range of the polarized fits, and the reference's warnings,
-  // each once per call and only when the call goes through
-  bool warn_power = false, warn_kappa = false, warn_thermal = false, warn_interpolate = false;
-  for (int v = 0; mix != nullptr && v < n; v++) {
-    const bl_electron_mix &m = mix[v];
-    const std::string which = "bl_set_polarized_variants_electrons: variant " + std::to_string(v);
-    if (!std::isfinite(m.power_frac)) return Fail(ctx, Failure{BL_E_ARG, which + " has a power_frac that is not finite."});
-    if (!std::isfinite(m.kappa_frac)) return Fail(ctx, Failure{BL_E_ARG, which + " has a kappa_frac that is not finite."});
-    if (m.power_frac != 0.0) {
-      if (!std::isfinite(m.p)) return Fail(ctx, Failure{BL_E_ARG, which + " has a p that is not finite."});
-      if (!std::isfinite(m.gamma_min)) return Fail(ctx, Failure{BL_E_ARG, which + " has a gamma_min that is not finite."});
-      if (!std::isfinite(m.gamma_max)) return Fail(ctx, Failure{BL_E_ARG, which + " has a gamma_max that is not finite."});
-    }
-    if (m.kappa_frac != 0.0) {
-      if (!std::isfinite(m.kappa)) return Fail(ctx, Failure{BL_E_ARG, which + " has a kappa that is not finite."});
-      if (!std::isfinite(m.w)) return Fail(ctx, Failure{BL_E_ARG, which + " has a w that is not finite."});
-      if (m.kappa < 3.5 || m.kappa > 5.0) return Fail(ctx, Failure{BL_E_ARG, which + ": Polarized transport only supports kappa in [3.5, 5]."});
-      warn_interpolate = warn_interpolate || (m.kappa != 3.5 && m.kappa != 4.0 && m.kappa != 4.5 && m.kappa != 5.0);
-    }
-    warn_power = warn_power || m.power_frac < 0.0 || m.power_frac > 1.0;
-    warn_kappa = warn_kappa || m.kappa_frac < 0.0 || m.kappa_frac > 1.0;
-    const double thermal_frac = ThermalFraction(m);
-    warn_thermal = warn_thermal || thermal_frac < 0.0 || thermal_frac > 1.0;
-  }
-  if (warn_power) Warn(ctx, "Fraction of power-law electrons outside [0, 1].");
-  if (warn_kappa) Warn(ctx, "Fraction of kappa-distribution electrons outside [0, 1].");
-  if (warn_interpolate) Warn(ctx, "Polarized transport will interpolate formulas based on kappa.");
-  if (warn_thermal) Warn(ctx, "Fraction of thermal electrons outside [0, 1].");
-  std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: no variant enters them)
-  ctx->triples.resize(n);
-  for (int v = 0; v < n; v++)
-    ctx->triples[v] = {rat_low[v], rat_high[v], rho_cgs[v], sigma_max != nullptr ? sigma_max[v] : 0.0, mix != nullptr ? mix[v] : bl_electron_mix{}};
-  ctx->triples_cut = n > 0 && sigma_max != nullptr;
-  ctx->triples_mix = n > 0 && mix != nullptr;
+  std::vector<const char *> warnings;
+  if (const Refused refused = CheckPolarizedVariants(ctx, n, rat_low, rat_high, rho_cgs, sigma_max, mix, &warnings)) return Fail(ctx, *refused);
+  for (const char *warning : warnings) Warn(ctx, warning);
+  std::lock_guard<std::mutex> guard(ctx->render_lock);
+  StorePolarizedVariants(ctx, n, rat_low, rat_high, rho_cgs, sigma_max, mix);
   return BL_OK;
 }
 
@@ -1328,14 +1410,9 @@ int bl_num_polarized_variants(const bl_ctx *ctx) { return ctx != nullptr ? stati
 
 int bl_set_sigma_cuts(bl_ctx *ctx, int n, const double *sigma_max) {
   if (ctx == nullptr) return BL_E_ARG;
-  if (n < 0 || n > BL_MAX_SIGMA_CUTS || (n > 0 && sigma_max == nullptr))
-    return Fail(ctx, Failure{BL_E_ARG, "bl_set_sigma_cuts needs 0 <= n <= " + std::to_string(BL_MAX_SIGMA_CUTS) + " and the array of cuts."});
-  for (int s = 0; s < n; s++)
-    if (!std::isfinite(sigma_max[s]))
-      return Fail(ctx, Failure{BL_E_ARG, "bl_set_sigma_cuts: cut " + std::to_string(s) + " is not finite."});
-  if (const char *why = SigmaCutsRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
-  std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; geodesics and located samples stay: they do not depend on the cut)
-  ctx->sigma_cuts.assign(sigma_max, sigma_max + n);
+  if (const Refused refused = CheckSigmaCuts(ctx, n, sigma_max)) return Fail(ctx, *refused);
+  std::lock_guard<std::mutex> guard(ctx->render_lock);
+  StoreSigmaCuts(ctx, n, sigma_max);
   return BL_OK;
 }
 
@@ -1345,7 +1422,11 @@ int bl_set_cameras(bl_ctx *ctx, int n, const double *th_deg, const double *ph_de
   if (ctx == nullptr) return BL_E_ARG;
   if (n < 0 || n > BL_MAX_CAMERAS || (n > 0 && (th_deg == nullptr || ph_deg == nullptr)))
     return Fail(ctx, Failure{BL_E_ARG, "bl_set_cameras needs 0 <= n <= " + std::to_string(BL_MAX_CAMERAS) + " and both arrays of angles."});
-  return bl_internal_set_cameras(ctx, n, th_deg, ph_deg);
+  std::vector<bl_ctx::Camera> list;
+  if (const Refused refused = CheckCameras(ctx, n, th_deg, ph_deg, &list)) return Fail(ctx, *refused);
+  std::lock_guard<std::mutex> guard(ctx->render_lock);
+  StoreCameras(ctx, std::move(list));
+  return BL_OK;
 }
 
 int bl_num_cameras(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->cameras.size()) : -1; }
@@ -1363,6 +1444,83 @@ int bl_cameras_get(const bl_ctx *ctx, int n, double *th_deg, double *ph_deg) {
   for (int c = 0; c < n && c < static_cast<int>(ctx->cameras.size()); c++) th_deg[c] = ctx->cameras[c].th_deg, ph_deg[c] = ctx->cameras[c].ph_deg;
   return BL_OK;
 }
+
+int bl_variants_get(const bl_ctx *ctx, int n, double *rat_low, double *rat_high, double *rho_cgs, double *sigma_max, int *flags) {
+  if (ctx == nullptr || n < 0) return BL_E_ARG;
+  const Variants variants = ResolveVariants(ctx);
+  for (int v = 0; v < n && v < static_cast<int>(variants.list.size()); v++) {
+    if (rat_low != nullptr) rat_low[v] = variants.list[v].rat_low;
+    if (rat_high != nullptr) rat_high[v] = variants.list[v].rat_high;
+    if (rho_cgs != nullptr) rho_cgs[v] = variants.list[v].rho;
+    if (sigma_max != nullptr) sigma_max[v] = variants.list[v].sigma_max;
+  }
+  if (flags != nullptr) *flags = (ctx->triples_cut ? BL_VARIANTS_TRIPLES_CUT : 0) | (ctx->triples_mix ? BL_VARIANTS_TRIPLES_MIX : 0);
+  return BL_OK;
+}
+
+int bl_apply_sweep_lists(bl_ctx *ctx, const bl_sweep_lists *lists) {
+  if (ctx == nullptr || lists == nullptr) return BL_E_ARG;
+  const bl_sweep none = {};
+  const bl_sweep *sweep = lists->sweep != nullptr ? lists->sweep : &none;
+  const bl_sweep_cuts *cuts = lists->cuts;
+  const bl_sweep_electrons *e = lists->electrons;
+  const bool electrons = e != nullptr && (e->n_power_frac != 0 || e->n_p != 0 || e->n_gamma_min != 0 || e->n_gamma_max != 0 || e->n_kappa_frac != 0
+                                          || e->n_kappa != 0 || e->n_w != 0);
+  // 1. What the lists mean (bl_params.cpp; a list error is BL_E_INPUT in the resolver's words). With an electron list the tuples come
+  // first: triples with a mix each, all three lists of `s` of their number. Without one the three lists wait behind the cut-count bound.
+  char err[512] = "";
+  const auto list_error = [&]() {   // (err is in Fail's form already)
+    ctx->last_error = err;
+    return BL_E_INPUT;
+  };
+  bl_sweep s;
+  bl_electron_mix mix[BL_MAX_SWEEP];
+  int polarized = 0, n_cameras = 0, th_given = 0, ph_given = 0;
+  double th[BL_MAX_SWEEP], ph[BL_MAX_SWEEP];
+  if (electrons && bl_sweep_electrons_resolve(e, sweep, &ctx->params, nullptr, &s, mix, err, sizeof err) != BL_OK) return list_error();
+  if (lists->cameras != nullptr && bl_sweep_cameras_resolve(lists->cameras, &n_cameras, th, ph, &th_given, &ph_given, err, sizeof err) != BL_OK)
+    return list_error();
+  // 2. Every check, in the order the calls of the older entry points made them; the first failure is the call's, and nothing is stored
+  std::vector<bl_ctx::Camera> cameras;
+  Refused refused;
+  if (n_cameras > 0) refused = CheckCameras(ctx, n_cameras, th_given ? th : nullptr, ph_given ? ph : nullptr, &cameras);
+  if (refused) return Fail(ctx, *refused);
+  if (cuts != nullptr && (cuts->n_sigma_max < 0 || cuts->n_sigma_max > BL_MAX_SWEEP))
+    return Fail(ctx, Failure{BL_E_INPUT, "Too many entries in a sweep list: at most " + std::to_string(BL_MAX_SWEEP) + " for this build."});
+  if (!electrons && bl_sweep_resolve(sweep, &ctx->params, &s, &polarized, err, sizeof err) != BL_OK) return list_error();
+  const bool has_triples = electrons || (polarized && (s.n_rat_low > 0 || s.n_rho_cgs > 0)), has_cuts = cuts != nullptr && cuts->n_sigma_max > 0;
+  const bool has_models = !has_triples && s.n_rat_low > 0, has_units = !has_triples && s.n_rho_cgs > 0;
+  std::vector<const char *> warnings;
+  if (electrons && has_cuts) refused = CheckSigmaCuts(ctx, cuts->n_sigma_max, cuts->sigma_max);   // (with tuples the cuts come first)
+  if (!refused && has_triples)
+    refused = CheckPolarizedVariants(ctx, s.n_rho_cgs, s.rat_low, s.rat_high, s.rho_cgs, nullptr, electrons ? mix : nullptr, &warnings);
+  if (!refused && has_models) refused = CheckElectronModels(ctx, s.n_rat_low, s.rat_low, s.rat_high);
+  if (!refused && has_units) refused = CheckDensityUnits(ctx, s.n_rho_cgs, s.rho_cgs);
+  if (!refused && !electrons && has_cuts) refused = CheckSigmaCuts(ctx, cuts->n_sigma_max, cuts->sigma_max);
+  if (refused) return Fail(ctx, *refused);
+  // 3. Every list the call carries, under one hold of the lock: no render sees half a sweep. A list it does not carry stays.
+  {
+    std::lock_guard<std::mutex> guard(ctx->render_lock);
+    if (n_cameras > 0) StoreCameras(ctx, std::move(cameras));
+    if (has_triples) StorePolarizedVariants(ctx, s.n_rho_cgs, s.rat_low, s.rat_high, s.rho_cgs, nullptr, electrons ? mix : nullptr);
+    if (has_models) StoreElectronModels(ctx, s.n_rat_low, s.rat_low, s.rat_high);
+    if (has_units) StoreDensityUnits(ctx, s.n_rho_cgs, s.rho_cgs);
+    if (has_cuts) StoreSigmaCuts(ctx, cuts->n_sigma_max, cuts->sigma_max);
+  }
+  for (const char *warning : warnings) Warn(ctx, warning);
+  return BL_OK;
+}
+
+// The three older entry points: forwards
+int bl_apply_sweeps_cameras(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts, const bl_sweep_cameras *cameras) {
+  if (ctx == nullptr || sweep == nullptr) return BL_E_ARG;
+  const bl_sweep_lists lists = {const_cast<bl_sweep *>(sweep), const_cast<bl_sweep_cuts *>(cuts), const_cast<bl_sweep_cameras *>(cameras), nullptr};
+  return bl_apply_sweep_lists(ctx, &lists);
+}
+
+int bl_apply_sweeps(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts) { return bl_apply_sweeps_cameras(ctx, sweep, cuts, nullptr); }
+
+int bl_apply_sweep(bl_ctx *ctx, const bl_sweep *sweep) { return bl_apply_sweeps_cameras(ctx, sweep, nullptr, nullptr); }
 
 int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out) {
   if (ctx == nullptr || out == nullptr) return BL_E_ARG;
@@ -1545,37 +1703,6 @@ const bl_camera_frame *bl_internal_frame(const bl_ctx *ctx) { return &ctx->frame
 const double *bl_internal_frequencies(const bl_ctx *ctx, int *count) {
   *count = static_cast<int>(ctx->frequencies.size());
   return ctx->frequencies.data();
-}
-// bl_set_cameras behind its argument checks. th_deg == nullptr: every camera at the parameter block's own camera_th (its radians and
-// its camera_pole, which no degree value need give back); ph_deg == nullptr: at the block's camera_ph - what an absent sweep_camera_th
-// or sweep_camera_ph means (bl_apply_sweeps_cameras).
-int bl_internal_set_cameras(bl_ctx *ctx, int n, const double *th_deg, const double *ph_deg) {
-  for (int c = 0; c < n; c++)
-    if ((th_deg != nullptr && !std::isfinite(th_deg[c])) || (ph_deg != nullptr && !std::isfinite(ph_deg[c])))
-      return Fail(ctx, Failure{BL_E_ARG, "bl_set_cameras: camera " + std::to_string(c) + " has an angle that is not finite."});
-  if (const char *why = CamerasRefusal(ctx, n)) return Fail(ctx, Failure{BL_E_UNSUPPORTED, why});
-  // Each camera's frame: what bl_init builds from the parameters with the three fields a written camera_th and camera_ph set
-  // (bl_params.cpp: degrees * pi / 180; camera_pole for a written th of exactly 0 or 180)
-  std::vector<bl_ctx::Camera> list(n);
-  for (int c = 0; c < n; c++) {
-    bl_params p = ctx->params;
-    list[c] = {p.camera_th * 180.0 / kPi, p.camera_ph * 180.0 / kPi, ctx->block_frame};
-    if (th_deg != nullptr) {
-      p.camera_th = th_deg[c] * kPi / 180.0;
-      p.camera_pole = (th_deg[c] == 0.0 || th_deg[c] == 180.0) ? 1 : 0;
-      list[c].th_deg = th_deg[c];
-    }
-    if (ph_deg != nullptr) {
-      p.camera_ph = ph_deg[c] * kPi / 180.0;
-      list[c].ph_deg = ph_deg[c];
-    }
-    bl_camera_frame_build(p, ctx->st, &list[c].frame);
-  }
-  std::lock_guard<std::mutex> guard(ctx->render_lock);   // (between renders; the resident geodesics' key holds the list: another list integrates again)
-  ctx->cameras = std::move(list);
-  ctx->cameras_uploaded = false;
-  ctx->frame = n == 1 ? ctx->cameras[0].frame : ctx->block_frame;
-  return BL_OK;
 }
 int bl_internal_fail(bl_ctx *ctx, int code, const char *message) {
   ctx->last_error = std::string("Error: ") + message + "\n";

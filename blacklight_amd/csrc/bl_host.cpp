@@ -447,13 +447,6 @@ int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, int camer
   return BL_OK;
 }
 
-// "Error: ...\n" -> the message alone (what bl_internal_fail wraps again)
-std::string MessageOf(std::string text) {
-  if (text.compare(0, 7, "Error: ") == 0) text.erase(0, 7);
-  if (!text.empty() && text.back() == '\n') text.pop_back();
-  return text;
-}
-
 // bl_write_output, bl_write_output_variant and bl_write_output_camera: image `variant` of the n_variants the root level's rows hold, and
 // of every row and record the slice of `camera` of the n_cameras that lie side by side in it
 int WriteOutput(bl_ctx *ctx, const char *path_override, const bl_output_desc *d_given, int variant, int n_variants, int camera = 0, int n_cameras = 1) {
@@ -810,104 +803,6 @@ int bl_variant_output_path(bl_ctx *ctx, int snapshot, int variant, char *buf, si
   if (path.size() + 1 > len) return bl_internal_fail(ctx, BL_E_ARG, "bl_variant_output_path: the buffer is too short for the name.");
   std::memcpy(buf, path.c_str(), path.size() + 1);
   return BL_OK;
-}
-
-int bl_apply_sweep(bl_ctx *ctx, const bl_sweep *sweep) {
-  if (ctx == nullptr || sweep == nullptr) return BL_E_ARG;
-  bl_sweep s;
-  int polarized = 0;
-  char err[512] = "";
-  if (bl_sweep_resolve(sweep, bl_internal_params(ctx), &s, &polarized, err, sizeof err) != BL_OK) {
-    return bl_internal_fail(ctx, BL_E_INPUT, MessageOf(err).c_str());
-  }
-  if (s.n_rat_low == 0 && s.n_rho_cgs == 0) return BL_OK;
-  if (polarized) return bl_set_polarized_variants(ctx, s.n_rho_cgs, s.rat_low, s.rat_high, s.rho_cgs);
-  int rc = BL_OK;
-  if (s.n_rat_low > 0) rc = bl_set_electron_models(ctx, s.n_rat_low, s.rat_low, s.rat_high);
-  if (rc == BL_OK && s.n_rho_cgs > 0) {
-    rc = bl_set_density_units(ctx, s.n_rho_cgs, s.rho_cgs);
-    if (rc != BL_OK && s.n_rat_low > 0) {   // neither list stays behind a refusal of the second
-      const std::string why = bl_last_error(ctx);
-      bl_set_electron_models(ctx, 0, nullptr, nullptr);
-      bl_internal_fail(ctx, rc, MessageOf(why).c_str());
-    }
-  }
-  return rc;
-}
-
-int bl_apply_sweeps(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts) {
-  if (ctx == nullptr || sweep == nullptr) return BL_E_ARG;
-  if (cuts != nullptr && (cuts->n_sigma_max < 0 || cuts->n_sigma_max > BL_MAX_SWEEP))
-    return bl_internal_fail(ctx, BL_E_INPUT, ("Too many entries in a sweep list: at most " + std::to_string(BL_MAX_SWEEP) + " for this build.").c_str());
-  int rc = bl_apply_sweep(ctx, sweep);
-  if (rc != BL_OK || cuts == nullptr || cuts->n_sigma_max == 0) return rc;
-  rc = bl_set_sigma_cuts(ctx, cuts->n_sigma_max, cuts->sigma_max);
-  if (rc != BL_OK) {   // no list of this call stays behind a refusal of the cuts
-    const std::string why = bl_last_error(ctx);
-    int polarized = 0;
-    (void)bl_sweep_resolve(sweep, bl_internal_params(ctx), nullptr, &polarized, nullptr, 0);
-    if (polarized && (sweep->n_rat_low > 0 || sweep->n_rho_cgs > 0)) bl_set_polarized_variants(ctx, 0, nullptr, nullptr, nullptr);
-    if (!polarized && sweep->n_rat_low > 0) bl_set_electron_models(ctx, 0, nullptr, nullptr);
-    if (!polarized && sweep->n_rho_cgs > 0) bl_set_density_units(ctx, 0, nullptr);
-    bl_internal_fail(ctx, rc, MessageOf(why).c_str());
-  }
-  return rc;
-}
-
-int bl_apply_sweeps_cameras(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts, const bl_sweep_cameras *cameras) {
-  if (ctx == nullptr || sweep == nullptr) return BL_E_ARG;
-  int n = 0, th_given = 0, ph_given = 0;
-  double th[BL_MAX_SWEEP], ph[BL_MAX_SWEEP];
-  char err[512] = "";
-  if (cameras != nullptr && bl_sweep_cameras_resolve(cameras, &n, th, ph, &th_given, &ph_given, err, sizeof err) != BL_OK)
-    return bl_internal_fail(ctx, BL_E_INPUT, MessageOf(err).c_str());
-  // (the cameras first: their refusal leaves nothing behind, and a refusal of the lists after them takes the cameras back)
-  const int held = bl_num_cameras(ctx);
-  double held_th[BL_MAX_CAMERAS], held_ph[BL_MAX_CAMERAS];
-  (void)bl_cameras_get(ctx, held, held_th, held_ph);
-  if (n > 0) {
-    const int rc = bl_internal_set_cameras(ctx, n, th_given ? th : nullptr, ph_given ? ph : nullptr);
-    if (rc != BL_OK) return rc;
-  }
-  const int rc = bl_apply_sweeps(ctx, sweep, cuts);
-  if (rc != BL_OK && n > 0) {
-    const std::string why = bl_last_error(ctx);
-    (void)bl_internal_set_cameras(ctx, held, held > 0 ? held_th : nullptr, held > 0 ? held_ph : nullptr);
-    bl_internal_fail(ctx, rc, MessageOf(why).c_str());
-  }
-  return rc;
-}
-
-int bl_apply_sweep_lists(bl_ctx *ctx, const bl_sweep_lists *lists) {
-  if (ctx == nullptr || lists == nullptr) return BL_E_ARG;
-  const bl_sweep none = {};
-  const bl_sweep *sweep = lists->sweep != nullptr ? lists->sweep : &none;
-  const bl_sweep_electrons *e = lists->electrons;
-  const bool electrons = e != nullptr && (e->n_power_frac != 0 || e->n_p != 0 || e->n_gamma_min != 0 || e->n_gamma_max != 0 || e->n_kappa_frac != 0
-                                          || e->n_kappa != 0 || e->n_w != 0);
-  if (!electrons) return bl_apply_sweeps_cameras(ctx, sweep, lists->cuts, lists->cameras);
-  int n = 0;
-  bl_sweep triples;
-  bl_electron_mix mix[BL_MAX_SWEEP];
-  char err[512] = "";
-  if (bl_sweep_electrons_resolve(e, sweep, bl_internal_params(ctx), &n, &triples, mix, err, sizeof err) != BL_OK)
-    return bl_internal_fail(ctx, BL_E_INPUT, MessageOf(err).c_str());
-  // (the cameras and the cuts first, by the call that has their rules - the cuts of a polarized block are refused there, in the
-  // setter's words; then the tuples, whose refusal takes back what that call brought)
-  const int held = bl_num_cameras(ctx);
-  double held_th[BL_MAX_CAMERAS], held_ph[BL_MAX_CAMERAS];
-  (void)bl_cameras_get(ctx, held, held_th, held_ph);
-  int rc = bl_apply_sweeps_cameras(ctx, &none, lists->cuts, lists->cameras);
-  if (rc != BL_OK) return rc;
-  rc = bl_set_polarized_variants_electrons(ctx, n, triples.rat_low, triples.rat_high, triples.rho_cgs, nullptr, mix);
-  if (rc != BL_OK) {
-    const std::string why = bl_last_error(ctx);
-    if (lists->cuts != nullptr && lists->cuts->n_sigma_max > 0) (void)bl_set_sigma_cuts(ctx, 0, nullptr);
-    if (lists->cameras != nullptr && (lists->cameras->n_th > 0 || lists->cameras->n_ph > 0))
-      (void)bl_internal_set_cameras(ctx, held, held > 0 ? held_th : nullptr, held > 0 ? held_ph : nullptr);
-    bl_internal_fail(ctx, rc, MessageOf(why).c_str());
-  }
-  return rc;
 }
 
 }  // extern "C"

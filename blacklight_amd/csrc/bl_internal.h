@@ -18,6 +18,5 @@ void bl_internal_warn(bl_ctx *ctx, const char *message);   // appends "Warning: 
 const bl_camera_frame *bl_internal_frame(const bl_ctx *ctx);
 const double *bl_internal_frequencies(const bl_ctx *ctx, int *count);
 int bl_internal_fail(bl_ctx *ctx, int code, const char *message);   // sets bl_last_error, returns code
-int bl_internal_set_cameras(bl_ctx *ctx, int n, const double *th_deg, const double *ph_deg);   // bl_set_cameras; a null array: the block's own angle
 
 #endif

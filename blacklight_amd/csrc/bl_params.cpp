@@ -130,17 +130,23 @@ void SetDouble(bl_params *p, int index, double v) {
   p->has[index] = 1;
 }
 
-// "x,y,z" (input_reader.cpp:468-482)
-void ReadTriple(const std::string &val, bl_params *p, int first_index) {
+// "x,y,z" into three doubles (input_reader.cpp:468-482)
+void ReadTripleValues(const std::string &val, double *x, double *y, double *z) {
   size_t pos_1 = 0, pos_2 = 0;
-  double x = ToDouble(val, &pos_1);
+  *x = ToDouble(val, &pos_1);
   if (pos_1 + 1 > val.size()) throw ParseFailure{"Could not read input file."};
   std::string rest_1 = val.substr(pos_1 + 1);
-  double y = ToDouble(rest_1, &pos_2);
+  *y = ToDouble(rest_1, &pos_2);
   if (pos_1 + pos_2 + 2 > val.size()) throw ParseFailure{"Could not read input file."};
-  double z = ToDouble(val.substr(pos_1 + pos_2 + 2));
+  *z = ToDouble(val.substr(pos_1 + pos_2 + 2));
   if (val[pos_1] != ',' || val[pos_1 + pos_2 + 1] != ',')
     throw ParseFailure{"Invalid triple (" + val + ") in input file."};
+}
+
+// ... into three consecutive fields of the block, once all three are read
+void ReadTriple(const std::string &val, bl_params *p, int first_index) {
+  double x = 0.0, y = 0.0, z = 0.0;
+  ReadTripleValues(val, &x, &y, &z);
   SetDouble(p, first_index, x);
   SetDouble(p, first_index + 1, y);
   SetDouble(p, first_index + 2, z);
@@ -185,19 +191,6 @@ void RgbToXyz(double r, double g, double b, double *x, double *y, double *z) {
   *x = 0.4123955889674142 * lr + 0.3575834307637148 * lg + 0.18049264738170154 * lb;
   *y = 0.21258623078559552 * lr + 0.715170303703411 * lg + 0.0722004986433362 * lb;
   *z = 0.019297215491746938 * lr + 0.11918386458084851 * lg + 0.9504971251315798 * lb;
-}
-
-// "x,y,z" into three doubles (input_reader.cpp:468-482)
-void ReadTripleValues(const std::string &val, double *x, double *y, double *z) {
-  size_t pos_1 = 0, pos_2 = 0;
-  *x = ToDouble(val, &pos_1);
-  if (pos_1 + 1 > val.size()) throw ParseFailure{"Could not read input file."};
-  std::string rest_1 = val.substr(pos_1 + 1);
-  *y = ToDouble(rest_1, &pos_2);
-  if (pos_1 + pos_2 + 2 > val.size()) throw ParseFailure{"Could not read input file."};
-  *z = ToDouble(val.substr(pos_1 + pos_2 + 2));
-  if (val[pos_1] != ',' || val[pos_1 + pos_2 + 1] != ',')
-    throw ParseFailure{"Invalid triple (" + val + ") in input file."};
 }
 
 bool EndsWith(const std::string &key, const char *suffix, size_t min_size) {
@@ -291,7 +284,9 @@ void ReadRender(bl_params *p, const std::string &key, const std::string &val) {
 
 // sweep_rat_low / sweep_rat_high / sweep_rho_cgs / sweep_cut_sigma_max: "a,b,c" (an extension: the reference has no lists). Stricter than the scalar keys:
 // every entry is a whole number text - nothing is left of it after the conversion -, none is empty, at most BL_MAX_SWEEP of them.
+// A kind of list beyond plain numbers names its entries in the error text and wants them finite (a unit: and positive).
 enum ListKind { kNumbers, kUnits, kSigmaCuts, kAngles, kElectrons };
+const char *const kListNoun[] = {nullptr, "density unit", "sigma cut", "angle", "value"};
 int ReadList(const std::string &key, const std::string &val, ListKind kind, double *out) {
   int count = 0;
   for (size_t at = 0; at <= val.size();) {
@@ -301,14 +296,9 @@ int ReadList(const std::string &key, const std::string &val, ListKind kind, doub
     char *end = nullptr;
     const double x = std::strtod(entry.c_str(), &end);
     if (end == entry.c_str() || *end != '\0') throw ParseFailure{"Invalid number (" + entry + ") in list (" + key + ") in input file."};
-    if (kind == kUnits && !(std::isfinite(x) && x > 0.0))
-      throw ParseFailure{"Invalid density unit (" + entry + ") in list (" + key + ") in input file: must be finite and positive."};
-    if (kind == kSigmaCuts && !std::isfinite(x))
-      throw ParseFailure{"Invalid sigma cut (" + entry + ") in list (" + key + ") in input file: must be finite."};
-    if (kind == kAngles && !std::isfinite(x))
-      throw ParseFailure{"Invalid angle (" + entry + ") in list (" + key + ") in input file: must be finite."};
-    if (kind == kElectrons && !std::isfinite(x))
-      throw ParseFailure{"Invalid value (" + entry + ") in list (" + key + ") in input file: must be finite."};
+    if (kind != kNumbers && !(std::isfinite(x) && (kind != kUnits || x > 0.0)))
+      throw ParseFailure{std::string("Invalid ") + kListNoun[kind] + " (" + entry + ") in list (" + key + ") in input file: must be finite"
+                         + (kind == kUnits ? " and positive." : ".")};
     if (count >= BL_MAX_SWEEP)
       throw ParseFailure{"Too many entries in list (" + key + ") in input file: at most " + std::to_string(BL_MAX_SWEEP) + " for this build."};
     out[count++] = x;
@@ -481,6 +471,20 @@ void SetKeyValue(bl_params *p, const bl_sweep_lists &lists, const std::string &k
   throw ParseFailure{"Unknown key (" + key + ") in input file."};
 }
 
+// The structs of `lists` with a spare for every NULL member (and for all four without `lists`): the keys of a list not asked for are
+// accepted and validated all the same
+struct SpareLists {
+  bl_sweep sweep; bl_sweep_cuts cuts; bl_sweep_cameras cameras; bl_sweep_electrons electrons;
+};
+bl_sweep_lists AllLists(const bl_sweep_lists *lists, SpareLists *spare) {
+  bl_sweep_lists all = lists != nullptr ? *lists : bl_sweep_lists{};
+  if (all.sweep == nullptr) all.sweep = &spare->sweep;
+  if (all.cuts == nullptr) all.cuts = &spare->cuts;
+  if (all.cameras == nullptr) all.cameras = &spare->cameras;
+  if (all.electrons == nullptr) all.electrons = &spare->electrons;
+  return all;
+}
+
 void ParseLine(bl_params *p, const bl_sweep_lists &lists, std::string line) {
   std::string stripped;
   stripped.reserve(line.size());
@@ -516,15 +520,8 @@ int bl_params_set_line_sweeps_cameras(bl_params *p, bl_sweep *sweep, bl_sweep_cu
 
 int bl_params_set_line_sweep_lists(bl_params *p, const bl_sweep_lists *lists, const char *line, char *err, size_t err_len) {
   if (p == nullptr || line == nullptr) return BL_E_ARG;
-  bl_sweep unused = {};   // (a list not asked for: its keys are accepted and validated all the same)
-  bl_sweep_cuts unused_cuts = {};
-  bl_sweep_cameras unused_cameras = {};
-  bl_sweep_electrons unused_electrons = {};
-  bl_sweep_lists all = lists != nullptr ? *lists : bl_sweep_lists{};
-  if (all.sweep == nullptr) all.sweep = &unused;
-  if (all.cuts == nullptr) all.cuts = &unused_cuts;
-  if (all.cameras == nullptr) all.cameras = &unused_cameras;
-  if (all.electrons == nullptr) all.electrons = &unused_electrons;
+  SpareLists spare = {};
+  const bl_sweep_lists all = AllLists(lists, &spare);
   try {
     ParseLine(p, all, line);
   } catch (const ParseFailure &failure) {
@@ -559,17 +556,8 @@ int bl_params_read_file_sweeps_cameras(bl_params *p, bl_sweep *sweep, bl_sweep_c
 int bl_params_read_file_sweep_lists(bl_params *p, const bl_sweep_lists *lists, const char *path, int *num_runs, char *err, size_t err_len) {
   if (p == nullptr || path == nullptr) return BL_E_ARG;
   bl_params_clear(p);
-  bl_sweep local = {};
-  bl_sweep_cuts local_cuts = {};
-  bl_sweep_cameras local_cameras = {};
-  bl_sweep_electrons local_electrons = {};
-  bl_sweep_lists all = lists != nullptr ? *lists : bl_sweep_lists{};
-  if (all.sweep == nullptr) all.sweep = &local;
-  if (all.cuts == nullptr) all.cuts = &local_cuts;
-  if (all.cameras == nullptr) all.cameras = &local_cameras;
-  if (all.electrons == nullptr) all.electrons = &local_electrons;
-  bl_sweep *sweep = all.sweep;
-  bl_sweep_cameras *cameras = all.cameras;
+  SpareLists spare = {};
+  const bl_sweep_lists all = AllLists(lists, &spare);
   *all.sweep = bl_sweep{};
   *all.cuts = bl_sweep_cuts{};
   *all.cameras = bl_sweep_cameras{};
@@ -581,9 +569,9 @@ int bl_params_read_file_sweep_lists(bl_params *p, const bl_sweep_lists *lists, c
   }
   try {
     for (std::string line; std::getline(stream, line);) ParseLine(p, all, line);
-    ResolveSweep(*sweep, *p, nullptr, nullptr);   // the lists against each other, once the whole file is known
-    (void)ResolveCameras(*cameras);
-    (void)ResolveElectrons(*all.electrons, *sweep, *p, nullptr, nullptr);
+    ResolveSweep(*all.sweep, *p, nullptr, nullptr);   // the lists against each other, once the whole file is known
+    (void)ResolveCameras(*all.cameras);
+    (void)ResolveElectrons(*all.electrons, *all.sweep, *p, nullptr, nullptr);
   } catch (const ParseFailure &failure) {
     SetError(err, err_len, failure.message);
     return BL_E_INPUT;

@@ -619,29 +619,35 @@ BL_API int bl_set_cameras(bl_ctx *ctx, int n, const double *th_deg, const double
 BL_API int bl_num_cameras(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own camera; -1: no context */
 /* The frame of camera `camera` of the list (0 .. max(1, n) - 1; with no list, camera 0 is the parameter block's). */
 BL_API int bl_camera_frame_get_camera(const bl_ctx *ctx, int camera, bl_camera_frame *out);
-/* The sweep of a .input file onto a context: bl_sweep_resolve against the context's parameters, then bl_set_polarized_variants
- * (polarized) or bl_set_electron_models and / or bl_set_density_units - one rule for the command-line driver, a bound reference
- * main() and Python. An empty sweep makes no call (what the context holds stays). On failure (bl_last_error: the resolver's text or
- * the refusing setter's) the context holds no model or unit the call brought. */
-BL_API int bl_apply_sweep(bl_ctx *ctx, const bl_sweep *sweep);
-/* ... and with the sigma cuts of the file (bl_set_sigma_cuts after the calls above; cuts may be NULL or empty: bl_apply_sweep). On
- * failure the context holds no model, unit or cut the call brought. */
-BL_API int bl_apply_sweeps(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts);
-/* ... and with the cameras of the file (bl_set_cameras after the calls above, an angle a list does not give being the parameter
- * block's own, to the bit; cameras may be NULL or empty: bl_apply_sweeps). On failure the context holds no model, unit, cut or camera
- * the call brought. */
-BL_API int bl_apply_sweeps_cameras(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts, const bl_sweep_cameras *cameras);
-/* ... and with the electron lists of the file: every list of `lists` (a NULL member: none). Without an electron list this is
- * bl_apply_sweeps_cameras; with one, the tuples of bl_sweep_electrons_resolve go to bl_set_polarized_variants_electrons under the
- * parameter block's cut_sigma_max. On failure - a list error (BL_E_INPUT), a setter's refusal in its words - the context holds
- * nothing the call brought. */
+/* The sweep of a .input file onto a context, as one checked step - one rule for the command-line driver, a bound reference main()
+ * and Python. Every list of `lists` (a NULL member: none) is resolved against the context's parameters (bl_sweep_cameras_resolve,
+ * bl_sweep_resolve or, with an electron list, bl_sweep_electrons_resolve), then checked with the checks of the setter it belongs to -
+ * bl_set_cameras, then bl_set_polarized_variants (polarized) or bl_set_electron_models and bl_set_density_units, then
+ * bl_set_sigma_cuts; with an electron list the tuples are resolved first of all, and the cuts are checked before
+ * bl_set_polarized_variants_electrons, which takes the tuples under the parameter block's cut_sigma_max. The first failure is the
+ * call's: a list error (BL_E_INPUT, the resolver's text) or a setter's refusal in its words. All or nothing: only when every check
+ * has passed are the lists stored, all under one hold of the lock bl_render holds, so a render on another thread sees the context
+ * before the call or after it; a refused call leaves the context exactly as it was. A list the call does not carry leaves its axis
+ * as it is, and an empty sweep changes nothing. */
 BL_API int bl_apply_sweep_lists(bl_ctx *ctx, const bl_sweep_lists *lists);
+/* Forwards to bl_apply_sweep_lists with the lists they name (cuts, cameras may be NULL), kept for their callers: BL_E_ARG without a
+ * context or a sweep. */
+BL_API int bl_apply_sweep(bl_ctx *ctx, const bl_sweep *sweep);
+BL_API int bl_apply_sweeps(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts);
+BL_API int bl_apply_sweeps_cameras(bl_ctx *ctx, const bl_sweep *sweep, const bl_sweep_cuts *cuts, const bl_sweep_cameras *cameras);
 /* The angles of the camera list as given, in degrees (an angle taken from the parameter block: its radians x 180 / pi): the first
  * min(n, bl_num_cameras) entries of both arrays. */
 BL_API int bl_cameras_get(const bl_ctx *ctx, int n, double *th_deg, double *ph_deg);
 /* Images one bl_render produces: max(1, electron models) * max(1, density units) * max(1, sigma cuts) * max(1, polarized variants)
  * - a polarized variant's own sigma cut (bl_set_polarized_variants_sigma) is part of the variant and adds no image; -1: no context. */
 BL_API int bl_num_variants(const bl_ctx *ctx);
+/* What every image of a render is rendered with: the first min(n, bl_num_variants) rows, in image-row order - the triples, else
+ * models x units x sigma cuts, model-major, then unit, then cut, with the parameter block's value where an axis is not set (the counts:
+ * bl_num_electron_models, ...). *flags: whether the triples carry cuts and mixes of their own (bl_polarized_variant_electrons reads
+ * the mixes). Any output may be NULL. */
+#define BL_VARIANTS_TRIPLES_CUT 1
+#define BL_VARIANTS_TRIPLES_MIX 2
+BL_API int bl_variants_get(const bl_ctx *ctx, int n, double *rat_low, double *rat_high, double *rho_cgs, double *sigma_max, int *flags);
 /* Number of false-colour renderings bl_render produces (render_num_images; 0 in formula mode). */
 BL_API int bl_render_num_images(const bl_ctx *ctx);
 BL_API int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out);
