@@ -309,23 +309,6 @@ void ValidateRadiation(bl_ctx *ctx) {
   ctx->image_num_quantities = n_q;
 }
 
-void BuildBuckets(const double *xf, int n, int n_bucket, std::vector<int> *table, double *x0, double *inv_w) {
-  // bucket b covers [x0 + b w, x0 + (b+1) w); table[b] = first cell c with xf[c+1] >= x0 + (b-1) w,
-  // i.e. a start index that is never beyond the reference's linear-scan result for any x whose
-  // bucket index evaluates to b (one bucket of slack covers rounding of the index computation)
-  double lo = xf[0], hi = xf[n];
-  double w = (hi - lo) / n_bucket;
-  *x0 = lo;
-  *inv_w = 1.0 / w;
-  table->resize(n_bucket);
-  int c = 0;
-  for (int b = 0; b < n_bucket; b++) {
-    double edge = lo + (b - 1) * w;
-    while (c < n - 1 && !(xf[c + 1] >= edge)) c++;
-    (*table)[b] = c;
-  }
-}
-
 }  // namespace
 
 namespace blhost {
@@ -664,12 +647,6 @@ int bl_init(const bl_params *p, int device, bl_ctx **out) {
 
 namespace {
 
-// Grid of equal blocks at one refinement level tiling a box, in any order (simulation_sampling.cpp:352-394
-// searches the blocks per sample): merged into one global array at upload; the locate kernel keeps the
-// reference's per-block anchor rules through the block size. Throws kIrregular when the blocks are not such
-// a tiling (bl_set_grid then takes the refined-mesh path).
-const char *const kIrregular = "Multi-block grid is not a regular tiling by equal blocks of one level.";
-
 // The cells into their HBM layout on the device. The caller's arrays are [variable][block][k][j][i] (simulation_reader.cpp:767-780);
 // the kernels read [cell][8 variables]. Eight planes are uploaded as they lie (a copy each, no pass over them on the host) and
 // one kernel interleaves them - a lane per cell: eight coalesced reads, 32 contiguous bytes written - placing a block's cells at the
@@ -696,643 +673,128 @@ __global__ void __launch_bounds__(256) bl_interleave_cells_kernel(const float *p
   out[1] = make_float4(v[4], v[5], v[6], v[7]);
 }
 
-// planes[v] = the caller's variable order[v]; block_origin (host, n_blocks entries) or null
-// The planes of `g` into `d_cells` as ctx->placement says, on `stream`; returns when the cells are in place (the caller's arrays are
-// borrowed for the duration of bl_set_grid)
+// The planes of `g` into `d_cells` as the grid's placement says, on `stream`; returns when the cells are in place (the caller's arrays
+// are borrowed for the duration of bl_set_grid)
 void UploadCellsAs(bl_ctx *ctx, const bl_grid_desc *g, DeviceBuffer<float> &d_cells, hipStream_t stream, bool upload_origin) {
-  const bl_ctx::CellPlacement &pl = ctx->placement;
+  bl_ctx::Grid &G = ctx->grid;
+  const CellPlacement &pl = G.tables.placement;
   const size_t n_cells = pl.n_cells;
   d_cells.Ensure(n_cells * 8);
-  ctx->d_cell_planes.Ensure(n_cells * 8);
+  G.d_cell_planes.Ensure(n_cells * 8);
   for (int v = 0; v < 8; v++)
-    Check(hipMemcpyAsync(ctx->d_cell_planes.ptr + static_cast<size_t>(v) * n_cells, g->prim + static_cast<size_t>(pl.order[v]) * n_cells, n_cells * sizeof(float),
+    Check(hipMemcpyAsync(G.d_cell_planes.ptr + static_cast<size_t>(v) * n_cells, g->prim + static_cast<size_t>(pl.order[v]) * n_cells, n_cells * sizeof(float),
                          hipMemcpyHostToDevice, stream), "grid upload");
   const unsigned long long *origin = nullptr;
   if (pl.has_origin) {
     if (upload_origin) {
-      ctx->d_block_origin.Ensure(pl.origin.size());
-      Check(hipMemcpyAsync(ctx->d_block_origin.ptr, pl.origin.data(), pl.origin.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream), "grid upload");
+      G.d_block_origin.Ensure(pl.origin.size());
+      Check(hipMemcpyAsync(G.d_block_origin.ptr, pl.origin.data(), pl.origin.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream), "grid upload");
     }
-    origin = ctx->d_block_origin.ptr;
+    origin = G.d_block_origin.ptr;
   }
-  hipLaunchKernelGGL(bl_interleave_cells_kernel, dim3(static_cast<unsigned int>((n_cells + 255) / 256)), dim3(256), 0, stream, ctx->d_cell_planes.ptr, d_cells.ptr,
+  hipLaunchKernelGGL(bl_interleave_cells_kernel, dim3(static_cast<unsigned int>((n_cells + 255) / 256)), dim3(256), 0, stream, G.d_cell_planes.ptr, d_cells.ptr,
                      static_cast<unsigned long long>(n_cells), pl.nb[0], pl.nb[1], pl.nb[2], origin, pl.row_stride, pl.plane_stride);
   Check(hipGetLastError(), "cell interleave kernel launch");
   Check(hipStreamSynchronize(stream), "grid upload");
 }
 
-// planes[v] = the caller's variable order[v]; block_origin (host, n_blocks entries) or null
-void UploadCells(bl_ctx *ctx, const bl_grid_desc *g, const int order[8], size_t n_cells, DeviceBuffer<float> &d_cells, const int nb[3],
-                 const std::vector<unsigned long long> *block_origin, unsigned long long row_stride, unsigned long long plane_stride) {
-  EnsureStreams(ctx);
-  bl_ctx::CellPlacement &pl = ctx->placement;
-  pl.valid = false;
-  pl.n_cells = n_cells;
-  for (int a = 0; a < 3; a++) pl.nb[a] = nb[a];
-  for (int v = 0; v < 8; v++) pl.order[v] = order[v];
-  pl.has_origin = block_origin != nullptr;
-  pl.origin = block_origin != nullptr ? *block_origin : std::vector<unsigned long long>();
-  pl.row_stride = row_stride;
-  pl.plane_stride = plane_stride;
-  UploadCellsAs(ctx, g, d_cells, ctx->stream, true);
-  pl.valid = ctx->cells_target == nullptr;   // (the time slices of slow light have no second array to change places with)
-}
-
-void UploadMergedGrid(bl_ctx *ctx, const bl_grid_desc *g) {
-    // Several blocks (simulation_sampling.cpp:352-394 searches them per sample): supported when they are
-    // equal blocks at one refinement level tiling a box, in any order. They are merged into one global
-    // array at upload; the locate kernel keeps the reference's per-block anchor rules through the block
-    // size. Mesh refinement (blocks of different levels) is not built.
-    const int nb_cells[3] = {g->n_i, g->n_j, g->n_k};
-    const double *block_xf[3] = {g->x1f, g->x2f, g->x3f};
-    const double *block_xv[3] = {g->x1v, g->x2v, g->x3v};
-    const int n_b = g->n_blocks;
-    std::vector<double> starts[3];          // distinct first faces along each axis, ascending
-    std::vector<int> block_pos[3];          // position of every block along each axis
-    for (int a = 0; a < 3; a++) {
-      for (int blk = 0; blk < n_b; blk++) starts[a].push_back(block_xf[a][static_cast<size_t>(blk) * (nb_cells[a] + 1)]);
-      std::sort(starts[a].begin(), starts[a].end());
-      starts[a].erase(std::unique(starts[a].begin(), starts[a].end()), starts[a].end());
-      block_pos[a].resize(n_b);
-      for (int blk = 0; blk < n_b; blk++) {
-        const double first = block_xf[a][static_cast<size_t>(blk) * (nb_cells[a] + 1)];
-        block_pos[a][blk] = static_cast<int>(std::lower_bound(starts[a].begin(), starts[a].end(), first) - starts[a].begin());
-      }
-    }
-    const int nbl[3] = {static_cast<int>(starts[0].size()), static_cast<int>(starts[1].size()), static_cast<int>(starts[2].size())};
-    if (static_cast<long long>(nbl[0]) * nbl[1] * nbl[2] != n_b) throw Failure{BL_E_UNSUPPORTED, kIrregular};
-    std::vector<int> block_at(n_b, -1);     // lattice position -> block
-    for (int blk = 0; blk < n_b; blk++) {
-      const int at = (block_pos[2][blk] * nbl[1] + block_pos[1][blk]) * nbl[0] + block_pos[0][blk];
-      if (block_at[at] != -1) throw Failure{BL_E_UNSUPPORTED, kIrregular};
-      block_at[at] = blk;
-    }
-    ctx->merged_block_at = block_at;        // (sample checkpoints name cells by MeshBlock and block-local indices)
-    for (int a = 0; a < 3; a++) ctx->merged_blocks[a] = nbl[a];
-    // global coordinate tables; every block at the same position along an axis must carry the same rows,
-    // and neighbouring rows must meet bit for bit (no gaps, no overlaps)
-    const int n_i = nbl[0] * nb_cells[0], n_j = nbl[1] * nb_cells[1], n_k = nbl[2] * nb_cells[2];
-    const int n[3] = {n_i, n_j, n_k};
-    std::vector<double> global_xf[3], global_xv[3];
-    for (int a = 0; a < 3; a++) {
-      global_xf[a].assign(n[a] + 1, 0.0);
-      global_xv[a].assign(n[a], 0.0);
-      std::vector<char> seen(nbl[a], 0);
-      for (int blk = 0; blk < n_b; blk++) {
-        const int pos = block_pos[a][blk];
-        const double *f = block_xf[a] + static_cast<size_t>(blk) * (nb_cells[a] + 1);
-        const double *v = block_xv[a] + static_cast<size_t>(blk) * nb_cells[a];
-        double *gf = global_xf[a].data() + static_cast<size_t>(pos) * nb_cells[a];
-        double *gv = global_xv[a].data() + static_cast<size_t>(pos) * nb_cells[a];
-        if (!seen[pos]) {
-          if (pos > 0 && seen[pos - 1] && std::memcmp(gf, f, sizeof(double)) != 0) throw Failure{BL_E_UNSUPPORTED, kIrregular};
-          std::memcpy(gf, f, sizeof(double) * (nb_cells[a] + 1));
-          std::memcpy(gv, v, sizeof(double) * nb_cells[a]);
-          seen[pos] = 1;
-        } else if (std::memcmp(gf, f, sizeof(double) * (nb_cells[a] + 1)) != 0 || std::memcmp(gv, v, sizeof(double) * nb_cells[a]) != 0) {
-          throw Failure{BL_E_UNSUPPORTED, kIrregular};
-        }
-      }
-      // joins written by a later block: the first face of block pos must equal the last face of pos - 1
-      for (int blk = 0; blk < n_b; blk++) {
-        const int pos = block_pos[a][blk];
-        const double *f = block_xf[a] + static_cast<size_t>(blk) * (nb_cells[a] + 1);
-        if (std::memcmp(global_xf[a].data() + static_cast<size_t>(pos) * nb_cells[a], f, sizeof(double)) != 0
-            || std::memcmp(global_xf[a].data() + static_cast<size_t>(pos + 1) * nb_cells[a], f + nb_cells[a], sizeof(double)) != 0)
-          throw Failure{BL_E_UNSUPPORTED, kIrregular};
-      }
-    }
-    const size_t n_cells = static_cast<size_t>(n_i) * n_j * n_k;
-    const size_t block_cells = static_cast<size_t>(nb_cells[0]) * nb_cells[1] * nb_cells[2];
-    // Repack [var][block][k][j][i] -> global [k][j][i][8]: rho, pgas, uu1, uu2, uu3, bb1, bb2, bb3
-    const int order[8] = {g->ind_rho, g->ind_pgas, g->ind_uu1, g->ind_uu2, g->ind_uu3, g->ind_bb1, g->ind_bb2, g->ind_bb3};
-    for (int v : order)
-      if (v < 0 || v >= g->n_var) throw Failure{BL_E_ARG, "Grid variable index out of range."};
-    DeviceBuffer<float> &d_cells = ctx->cells_target != nullptr ? *ctx->cells_target : ctx->d_cells;
-    DeviceBuffer<float> &d_kappa = ctx->kappa_target != nullptr ? *ctx->kappa_target : ctx->d_kappa;
-    {
-      std::vector<unsigned long long> origin(n_b);   // first cell of every block in the merged array
-      for (int blk = 0; blk < n_b; blk++)
-        origin[blk] = (static_cast<unsigned long long>(block_pos[2][blk]) * nb_cells[2] * n_j + static_cast<unsigned long long>(block_pos[1][blk]) * nb_cells[1]) * n_i
-            + static_cast<unsigned long long>(block_pos[0][blk]) * nb_cells[0];
-      UploadCells(ctx, g, order, n_cells, d_cells, nb_cells, n_b > 1 ? &origin : nullptr, static_cast<unsigned long long>(n_i), static_cast<unsigned long long>(n_i) * n_j);
-    }
-    const bool code_kappa = ctx->params.plasma_model == BL_PLASMA_CODE_KAPPA;
-    if (code_kappa) {
-      // the ninth value of a cell (simulation_reader.cpp:1164-1172) in its own [k][j][i] array: only the
-      // extended coefficient kernel reads it
-      if (g->ind_kappa < 0 || g->ind_kappa >= g->n_var) throw Failure{BL_E_ARG, "Grid variable index out of range."};
-      std::vector<float> kappa(n_cells);
-      for (int blk = 0; blk < n_b; blk++) {
-        const int pi = block_pos[0][blk], pj = block_pos[1][blk], pk = block_pos[2][blk];
-        const float *src = g->prim + (static_cast<size_t>(g->ind_kappa) * n_b + blk) * block_cells;
-        for (int k = 0; k < nb_cells[2]; k++)
-          for (int j = 0; j < nb_cells[1]; j++) {
-            const size_t row = (static_cast<size_t>(pk * nb_cells[2] + k) * n_j + (pj * nb_cells[1] + j)) * n_i + static_cast<size_t>(pi) * nb_cells[0];
-            std::memcpy(kappa.data() + row, src + (static_cast<size_t>(k) * nb_cells[1] + j) * nb_cells[0], sizeof(float) * nb_cells[0]);
-          }
-      }
-      d_kappa.Ensure(kappa.size());
-      Check(hipMemcpy(d_kappa.ptr, kappa.data(), kappa.size() * sizeof(float), hipMemcpyHostToDevice), "grid upload");
-    }
-    // coordinates
-    const double *xf[3] = {global_xf[0].data(), global_xf[1].data(), global_xf[2].data()};
-    const double *xv[3] = {global_xv[0].data(), global_xv[1].data(), global_xv[2].data()};
-    std::vector<double> coords;
-    size_t off_f[3], off_v[3];
-    for (int a = 0; a < 3; a++) {
-      off_f[a] = coords.size();
-      coords.insert(coords.end(), xf[a], xf[a] + n[a] + 1);
-      off_v[a] = coords.size();
-      coords.insert(coords.end(), xv[a], xv[a] + n[a]);
-    }
-    // cosine and sine of every theta and phi centre, and how far a cell reaches from its centre: what the tolerant coefficient kernel's
-    // angles relative to the cell centre ask for (bl_local_angles.h)
-    size_t off_trig[2];
-    double angle_reach = 0.0;
-    for (int a = 1; a < 3; a++) {
-      off_trig[a - 1] = coords.size();
-      for (int c = 0; c < n[a]; c++) {
-        double sine, cosine;
-        bl_sincos(xv[a][c], &sine, &cosine);
-        coords.push_back(cosine);
-        coords.push_back(sine);
-        angle_reach = std::max(angle_reach, std::max(xv[a][c] - xf[a][c], xf[a][c + 1] - xv[a][c]));
-      }
-    }
-    ctx->d_coords.Ensure(coords.size());
-    Check(hipMemcpy(ctx->d_coords.ptr, coords.data(), coords.size() * sizeof(double), hipMemcpyHostToDevice), "coordinate upload");
-    // bucket tables for the cell search
-    if (n_i > 65535 || n_j > 65535 || n_k > 65535)
-      throw Failure{BL_E_UNSUPPORTED, "More than 65535 cells along an axis of the merged grid."};
-    std::vector<unsigned short> buckets;
-    size_t off_b[3];
-    BlGridDevice dev{};
-    for (int a = 0; a < 3; a++) {
-      int n_bucket = std::max(512, 8 * n[a]);
-      std::vector<int> table;
-      BuildBuckets(xf[a], n[a], n_bucket, &table, &dev.bucket_x0[a], &dev.bucket_inv_w[a]);
-      {   // evenly spaced faces?
-        const double width = (xf[a][n[a]] - xf[a][0]) / n[a];
-        bool even = width > 0.0;
-        for (int c = 0; c <= n[a] && even; c++) even = std::abs(xf[a][c] - (xf[a][0] + c * width)) <= 1.0e-4 * width;
-        dev.cell_x0[a] = xf[a][0];
-        dev.cell_inv_w[a] = even ? 1.0 / width : 0.0;
-        if (even) dev.uniform_mask |= 1 << a;
-      }
-      if (a == 0) {   // radial faces evenly spaced in log r? (bl_shade_fused2_kernel guesses the cell from log2 r and confirms it by the faces)
-        dev.r_face_in = xf[0][0];
-        dev.r_face_out = xf[0][n[0]];
-        bool even = xf[0][0] > 0.0 && xf[0][n[0]] > xf[0][0];
-        const double l0 = even ? std::log2(xf[0][0]) : 0.0, width = even ? (std::log2(xf[0][n[0]]) - l0) / n[0] : 1.0;
-        for (int c = 0; c <= n[0] && even; c++) even = std::abs(std::log2(xf[0][c]) - (l0 + c * width)) <= 1.0e-4 * width;
-        dev.log_uniform = even ? 1 : 0;
-        dev.log_l0 = static_cast<float>(l0);
-        dev.log_inv_w = static_cast<float>(1.0 / width);
-      }
-      dev.n_bucket[a] = n_bucket;
-      off_b[a] = buckets.size();
-      buckets.insert(buckets.end(), table.begin(), table.end());
-    }
-    // theta from pole to pole and phi all the way round: no sample is off the grid in angle
-    dev.full_sphere = (xf[1][0] <= 0.0 && xf[1][n[1]] >= kPi && xf[2][0] <= 0.0 && xf[2][n[2]] >= 2.0 * kPi) ? 1 : 0;
-    ctx->d_buckets.Ensure(buckets.size());
-    Check(hipMemcpy(ctx->d_buckets.ptr, buckets.data(), buckets.size() * sizeof(unsigned short), hipMemcpyHostToDevice), "bucket upload");
-    dev.cells = d_cells.ptr;
-    dev.kappa = code_kappa ? d_kappa.ptr : nullptr;
-    dev.n_blocks = 0;
-    dev.stride_row = n_i;
-    dev.stride_plane = n_i * n_j;
-    for (int a = 0; a < 3; a++) {
-      dev.xf[a] = ctx->d_coords.ptr + off_f[a];
-      dev.xv[a] = ctx->d_coords.ptr + off_v[a];
-      dev.bucket[a] = ctx->d_buckets.ptr + off_b[a];
-      dev.n[a] = n[a];
-      dev.nb[a] = nb_cells[a];
-    }
-    dev.angle_trig[0] = ctx->d_coords.ptr + off_trig[0];
-    dev.angle_trig[1] = ctx->d_coords.ptr + off_trig[1];
-    dev.angle_reach = angle_reach;
-    for (int a = 1; a < 3; a++) {
-      dev.angle_guess[2 * a - 2] = static_cast<float>(dev.cell_x0[a]);
-      dev.angle_guess[2 * a - 1] = static_cast<float>(dev.cell_inv_w[a]);
-    }
-    if (ctx->params.simulation_coord == BL_COORD_FMKS) {
-      // FMKS grid (simulation_sampling.cpp:66-73): native coordinates above, plus the reader's map and bounds
-      if (n_b != 1 || g->sks_map == nullptr || g->sks_map_n1 < 2 || g->sks_map_n2 < 2)
-        throw Failure{BL_E_ARG, "simulation_coord = fmks needs a single block and the reader's sks_map in bl_grid_desc."};
-      const size_t map_count = static_cast<size_t>(2) * g->sks_map_n1 * g->sks_map_n2;
-      ctx->d_sks_map.Ensure(map_count);
-      Check(hipMemcpy(ctx->d_sks_map.ptr, g->sks_map, map_count * sizeof(double), hipMemcpyHostToDevice), "sks_map upload");
-      dev.fmks = 1;
-      dev.sks_map = ctx->d_sks_map.ptr;
-      dev.sks_map_n1 = g->sks_map_n1;
-      dev.sks_map_n2 = g->sks_map_n2;
-      dev.sks_map_r_in = g->sks_map_r_in;
-      dev.sks_map_dr = g->sks_map_dr;
-      dev.sks_map_dtheta = g->sks_map_dtheta;
-      for (int c = 0; c < 6; c++) dev.fmks_bounds[c] = g->simulation_bounds[c];
-      dev.fmks_x1_0 = xf[0][0];
-      dev.fmks_dx1 = xf[0][1] - xf[0][0];
-      dev.fmks_dx2 = xf[1][1] - xf[1][0];
-    }
-    ctx->grid_dev = dev;
-    {
-      // The locate kernel stages the tables in LDS when they fit 60 KiB: faces and centres as doubles and max(512, 8 n) 16-bit buckets
-      // per axis, 32 n + 8 bytes for an axis of 64 cells or more - about 640 cells on each of three axes, or 1 847 on one beside two
-      // of eight. (The kernels with the locate step inside have a budget of their own: 1 018 cells summed over the axes,
-      // bl_fused2_applicable.) Larger grids are searched in the same tables where they lie in HBM (lds_table_bytes = 0).
-      size_t bytes = 0;
-      for (int a = 0; a < 3; a++) bytes += (2 * static_cast<size_t>(n[a]) + 1) * sizeof(double) + static_cast<size_t>(dev.n_bucket[a]) * sizeof(unsigned short);
-      ctx->lds_table_bytes = bytes > 60 * 1024 ? 0 : static_cast<int>((bytes + 15) / 16 * 16);
-      if (ctx->lds_table_bytes == 0 && ctx->params.slow_light_on)
-        throw Failure{BL_E_UNSUPPORTED, "Slow light on a grid whose coordinate tables exceed the 60 KiB LDS budget is not built."};
-    }
-    ctx->n_i = n_i;
-    ctx->n_j = n_j;
-    ctx->n_k = n_k;
-}
-
-// Where the search along n ascending faces starts (BlGridDevice::row_guess, box_guess): kind (1: logarithmic), origin, cells per unit.
-// Logarithmic where every face is positive and the ratios of neighbouring faces agree better than their differences do.
-void SearchGuess(const double *f, int n, double guess[3]) {
-  bool positive = f[0] > 0.0;
-  double ratio_lo = 1.0e300, ratio_hi = 0.0, step_lo = 1.0e300, step_hi = 0.0;
-  for (int i = 0; i < n && positive; i++) {
-    ratio_lo = std::min(ratio_lo, f[i + 1] / f[i]); ratio_hi = std::max(ratio_hi, f[i + 1] / f[i]);
-    step_lo = std::min(step_lo, f[i + 1] - f[i]); step_hi = std::max(step_hi, f[i + 1] - f[i]);
-  }
-  const bool logarithmic = positive && n > 1 && (ratio_hi / ratio_lo - 1.0) < 0.5 * (step_hi / step_lo - 1.0);
-  if (logarithmic) {
-    guess[0] = 1.0;
-    guess[1] = std::log2(f[0]);
-    guess[2] = n / (std::log2(f[n]) - std::log2(f[0]));
-  } else {
-    guess[0] = 0.0;
-    guess[1] = f[0];
-    guess[2] = n / (f[n] - f[0]);
-  }
-}
-
-// Mesh with refinement (blocks of several levels), or any other set of non-overlapping equal-sized blocks:
-// cells stay block by block; the distinct block boundaries along each axis span a lattice of boxes, each
-// covered by at most one block, from which the locate kernel finds the block of a sample (the reference
-// scans all blocks per sample, simulation_sampling.cpp:352-394), then the cell from the block's own rows.
-void UploadRefinedGrid(bl_ctx *ctx, const bl_grid_desc *g) {
-  const int nb[3] = {g->n_i, g->n_j, g->n_k};
-  const double *block_xf[3] = {g->x1f, g->x2f, g->x3f};
-  const double *block_xv[3] = {g->x1v, g->x2v, g->x3v};
-  const int n_b = g->n_blocks;
-  const char *kBadMesh = "Multi-block grid has blocks that overlap or faces that do not ascend.";
-  std::vector<double> edge[3];
-  for (int a = 0; a < 3; a++) {
-    if (block_xf[a] == nullptr || block_xv[a] == nullptr) throw Failure{BL_E_ARG, "Bad grid description."};
-    for (int blk = 0; blk < n_b; blk++) {
-      const double *f = block_xf[a] + static_cast<size_t>(blk) * (nb[a] + 1);
-      for (int i = 0; i < nb[a]; i++)
-        if (!(f[i] < f[i + 1])) throw Failure{BL_E_UNSUPPORTED, kBadMesh};
-      edge[a].push_back(f[0]);
-      edge[a].push_back(f[nb[a]]);
-    }
-    std::sort(edge[a].begin(), edge[a].end());
-    edge[a].erase(std::unique(edge[a].begin(), edge[a].end()), edge[a].end());
-  }
-  const int n_edge[3] = {static_cast<int>(edge[0].size()) - 1, static_cast<int>(edge[1].size()) - 1,
-                         static_cast<int>(edge[2].size()) - 1};
-  const size_t n_boxes = static_cast<size_t>(n_edge[0]) * n_edge[1] * n_edge[2];
-  const size_t block_cells = static_cast<size_t>(nb[0]) * nb[1] * nb[2];
-  const size_t n_cells = block_cells * n_b;
-  if (n_boxes > (1ull << 28) || n_cells >= (1ull << 32))
-    throw Failure{BL_E_UNSUPPORTED, "Multi-block grid too large for the block lattice of this build."};
-  std::vector<int> lattice(n_boxes, -1);
-  for (int blk = 0; blk < n_b; blk++) {
-    int lo[3], hi[3];
-    for (int a = 0; a < 3; a++) {
-      const double *f = block_xf[a] + static_cast<size_t>(blk) * (nb[a] + 1);
-      lo[a] = static_cast<int>(std::lower_bound(edge[a].begin(), edge[a].end(), f[0]) - edge[a].begin());
-      hi[a] = static_cast<int>(std::lower_bound(edge[a].begin(), edge[a].end(), f[nb[a]]) - edge[a].begin());
-    }
-    for (int kk = lo[2]; kk < hi[2]; kk++)
-      for (int jj = lo[1]; jj < hi[1]; jj++)
-        for (int ii = lo[0]; ii < hi[0]; ii++) {
-          int &slot = lattice[(static_cast<size_t>(kk) * n_edge[1] + jj) * n_edge[0] + ii];
-          if (slot != -1) throw Failure{BL_E_UNSUPPORTED, kBadMesh};
-          slot = blk;
-        }
-  }
-  // cells: [var][block][k][j][i] -> [block][k][j][i][8]
-  const int order[8] = {g->ind_rho, g->ind_pgas, g->ind_uu1, g->ind_uu2, g->ind_uu3, g->ind_bb1, g->ind_bb2, g->ind_bb3};
-  for (int v : order)
-    if (v < 0 || v >= g->n_var) throw Failure{BL_E_ARG, "Grid variable index out of range."};
-  DeviceBuffer<float> &d_cells = ctx->cells_target != nullptr ? *ctx->cells_target : ctx->d_cells;
-  DeviceBuffer<float> &d_kappa = ctx->kappa_target != nullptr ? *ctx->kappa_target : ctx->d_kappa;
-  UploadCells(ctx, g, order, n_cells, d_cells, nb, nullptr, 0, 0);   // (the blocks stay one behind the other: the caller's order)
-  const bool code_kappa = ctx->params.plasma_model == BL_PLASMA_CODE_KAPPA;
-  if (code_kappa) {
-    if (g->ind_kappa < 0 || g->ind_kappa >= g->n_var) throw Failure{BL_E_ARG, "Grid variable index out of range."};
-    d_kappa.Ensure(n_cells);
-    Check(hipMemcpy(d_kappa.ptr, g->prim + static_cast<size_t>(g->ind_kappa) * n_cells, n_cells * sizeof(float),
-                    hipMemcpyHostToDevice), "grid upload");
-  }
-  // Coordinate rows, each distinct one once (faces and centres of a block along an axis, compared bit for bit: blocks of one level at
-  // one position share them), which row every block uses, the first centre of the next block of the file (what the reference reads one
-  // past a block's last centre), then the block boundaries
-  std::vector<double> coords;
-  std::vector<int> block_row(static_cast<size_t>(n_b) * 3);
-  size_t off_f[3], off_v[3], off_e[3], off_n[3], off_g[3];
-  int n_rows[3];
-  for (int a = 0; a < 3; a++) {
-    const size_t row_len = static_cast<size_t>(nb[a]) * 2 + 1;
-    std::map<std::vector<unsigned long long>, int> seen;   // (rows compared word for word: the same bits, not merely equal values)
-    std::vector<const double *> row_f, row_v;
-    for (int blk = 0; blk < n_b; blk++) {
-      const double *f = block_xf[a] + static_cast<size_t>(blk) * (nb[a] + 1), *v = block_xv[a] + static_cast<size_t>(blk) * nb[a];
-      std::vector<unsigned long long> key(row_len);
-      std::memcpy(key.data(), f, (static_cast<size_t>(nb[a]) + 1) * sizeof(double));
-      std::memcpy(key.data() + nb[a] + 1, v, static_cast<size_t>(nb[a]) * sizeof(double));
-      auto found = seen.find(key);
-      if (found == seen.end()) {
-        found = seen.emplace(std::move(key), static_cast<int>(row_f.size())).first;
-        row_f.push_back(f);
-        row_v.push_back(v);
-      }
-      block_row[static_cast<size_t>(a) * n_b + blk] = found->second;
-    }
-    n_rows[a] = static_cast<int>(row_f.size());
-    off_f[a] = coords.size();
-    for (const double *f : row_f) coords.insert(coords.end(), f, f + nb[a] + 1);
-    off_v[a] = coords.size();
-    for (const double *v : row_v) coords.insert(coords.end(), v, v + nb[a]);
-    off_n[a] = coords.size();
-    for (int blk = 0; blk < n_b; blk++)
-      coords.push_back(blk + 1 < n_b ? block_xv[a][static_cast<size_t>(blk + 1) * nb[a]] : std::numeric_limits<double>::quiet_NaN());
-    off_g[a] = coords.size();
-    for (const double *f : row_f) {
-      double guess[3];
-      SearchGuess(f, nb[a], guess);
-      coords.insert(coords.end(), guess, guess + 3);
-    }
-    off_e[a] = coords.size();
-    coords.insert(coords.end(), edge[a].begin(), edge[a].end());
-  }
-  ctx->d_coords.Ensure(coords.size());
-  Check(hipMemcpy(ctx->d_coords.ptr, coords.data(), coords.size() * sizeof(double), hipMemcpyHostToDevice), "coordinate upload");
-  // (the lattice, then the blocks' rows)
-  const size_t lattice_ints = lattice.size();
-  lattice.insert(lattice.end(), block_row.begin(), block_row.end());
-  ctx->d_lattice.Ensure(lattice.size());
-  Check(hipMemcpy(ctx->d_lattice.ptr, lattice.data(), lattice.size() * sizeof(int), hipMemcpyHostToDevice), "lattice upload");
-  BlGridDevice dev{};
-  dev.cells = d_cells.ptr;
-  dev.kappa = code_kappa ? d_kappa.ptr : nullptr;
-  dev.n_blocks = n_b;
-  dev.lattice = ctx->d_lattice.ptr;
-  dev.stride_row = nb[0];
-  dev.stride_plane = nb[0] * nb[1];
-  for (int a = 0; a < 3; a++) {
-    dev.bxf[a] = ctx->d_coords.ptr + off_f[a];
-    dev.bxv[a] = ctx->d_coords.ptr + off_v[a];
-    dev.xv_next[a] = ctx->d_coords.ptr + off_n[a];
-    dev.row_guess[a] = ctx->d_coords.ptr + off_g[a];
-    dev.block_row[a] = ctx->d_lattice.ptr + lattice_ints + static_cast<size_t>(a) * n_b;
-    dev.n_rows[a] = n_rows[a];
-    dev.edge[a] = ctx->d_coords.ptr + off_e[a];
-    dev.n_edge[a] = n_edge[a];
-    dev.edge_first[a] = edge[a].front();
-    dev.edge_last[a] = edge[a].back();
-    SearchGuess(edge[a].data(), n_edge[a], dev.box_guess[a]);
-    dev.n[a] = nb[a];
-    dev.nb[a] = nb[a];
-  }
-  if (ctx->params.simulation_interp && ctx->params.simulation_block_interp) {
-    // MeshBlock table for FindNearbyInds (simulation_sampling.cpp:36-39, :84-93) and a hash from (level, location)
-    // to block in place of its scans over all blocks
-    // n_3_root only enters through the periodic seam of spherical coordinates (simulation_sampling.cpp:1181-1219)
-    if (g->levels == nullptr || g->locations == nullptr || (g->n_3_root <= 0 && ctx->params.simulation_coord == BL_COORD_SKS))
-      throw Failure{BL_E_ARG, "simulation_block_interp = true needs the MeshBlock table (levels, locations, n_3_root) in bl_grid_desc."};
-    int max_level = 0;
-    for (int blk = 0; blk < n_b; blk++) {
-      if (g->levels[blk] < 0 || g->levels[blk] > 30) throw Failure{BL_E_ARG, "Bad MeshBlock level."};
-      max_level = std::max(max_level, g->levels[blk]);
-      for (int a = 0; a < 3; a++)
-        if (g->locations[3 * blk + a] < 0 || g->locations[3 * blk + a] >= (1 << 19)) throw Failure{BL_E_UNSUPPORTED, "MeshBlock location outside the range of this build."};
-    }
-    unsigned int slots = 16;
-    while (slots < 2u * static_cast<unsigned int>(n_b)) slots *= 2;
-    std::vector<unsigned long long> keys(slots, ~0ull);
-    std::vector<int> table(static_cast<size_t>(n_b) * 4 + slots, -1);
-    for (int blk = 0; blk < n_b; blk++) {
-      table[blk] = g->levels[blk];
-      for (int a = 0; a < 3; a++) table[n_b + 3 * blk + a] = g->locations[3 * blk + a];
-      const unsigned long long key = (static_cast<unsigned long long>(g->levels[blk]) << 57) | (static_cast<unsigned long long>(g->locations[3 * blk]) << 38)
-          | (static_cast<unsigned long long>(g->locations[3 * blk + 1]) << 19) | static_cast<unsigned long long>(g->locations[3 * blk + 2]);
-      unsigned int slot = static_cast<unsigned int>((key * 0x9e3779b97f4a7c15ull) >> 32) & (slots - 1);
-      while (keys[slot] != ~0ull) {
-        if (keys[slot] == key) throw Failure{BL_E_UNSUPPORTED, kBadMesh};   // two blocks at one place
-        slot = (slot + 1) & (slots - 1);
-      }
-      keys[slot] = key;
-      table[static_cast<size_t>(n_b) * 4 + slot] = blk;
-    }
-    ctx->d_block_table.Ensure(table.size());
-    ctx->d_block_keys.Ensure(keys.size());
-    Check(hipMemcpy(ctx->d_block_table.ptr, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice), "block table upload");
-    Check(hipMemcpy(ctx->d_block_keys.ptr, keys.data(), keys.size() * sizeof(unsigned long long), hipMemcpyHostToDevice), "block table upload");
-    dev.block_interp = 1;
-    dev.levels = ctx->d_block_table.ptr;
-    dev.locations = ctx->d_block_table.ptr + n_b;
-    dev.hash_blocks = ctx->d_block_table.ptr + static_cast<size_t>(n_b) * 4;
-    dev.hash_keys = ctx->d_block_keys.ptr;
-    dev.hash_mask = slots - 1;
-    dev.max_level = max_level;
-    dev.n_3_level0 = g->n_3_root / nb[2];
-  }
-  {
-    // what bl_locate_kernel<kRefined> stages in LDS when it fits (four workgroups to a compute unit up to 36 KiB, one of 1 024 lanes beyond): block boundaries,
-    // lattice, rows, the blocks' rows and next centres, and with inter-block interpolation the MeshBlock table and its hash
-    size_t doubles = 0, ints = lattice_ints + static_cast<size_t>(n_b) * 3;
-    for (int a = 0; a < 3; a++) doubles += static_cast<size_t>(n_edge[a]) + 1 + static_cast<size_t>(n_rows[a]) * (2 * nb[a] + 1 + 3) + n_b;
-    if (dev.block_interp) {
-      doubles += dev.hash_mask + 1;                                        // (the keys: 8 bytes each)
-      ints += static_cast<size_t>(n_b) * 4 + dev.hash_mask + 1;
-    }
-    const size_t bytes = doubles * sizeof(double) + (ints + 3) / 4 * 4 * sizeof(int);
-    dev.refined_lds_bytes = bytes <= static_cast<size_t>(BL_LOCATE_REFINED_LDS) ? static_cast<int>(bytes) : 0;
-  }
-  {
-    // what bl_shade_fused2_kernel<..., kRefined> asks of a mesh (bl_shade_fused.hip): boxes and rows evenly spaced in log r / theta / phi to
-    // 1e-4 of a cell (its guesses are then right wherever its margins let it decide), the sphere covered without a hole, 32-bit byte
-    // offsets into the cell array, room in LDS for the row chunks and one descriptor per box (one 512-lane workgroup to a compute unit)
-    auto evenly = [](const double *f, int n, bool logarithmic, double *origin, double *inv_w) {
-      if (n < 1 || (logarithmic && !(f[0] > 0.0))) return false;
-      const double first = logarithmic ? std::log2(f[0]) : f[0], last = logarithmic ? std::log2(f[n]) : f[n];
-      const double width = (last - first) / n;
-      if (!(width > 0.0)) return false;
-      for (int c = 0; c <= n; c++)
-        if (!(std::abs((logarithmic ? std::log2(f[c]) : f[c]) - (first + c * width)) <= 1.0e-4 * width)) return false;
-      *origin = first;
-      *inv_w = 1.0 / width;
-      return true;
-    };
-    bool ok = nb[0] >= 2 && nb[1] >= 2 && nb[2] >= 2 && n_cells * 32ull < (1ull << 32) && static_cast<unsigned long long>(nb[1]) * nb[2] < (1ull << 24);
-    for (size_t box = 0; box < n_boxes && ok; box++) ok = lattice[box] >= 0;
-    ok = ok && edge[1].front() <= 0.0 && edge[1].back() >= kPi && edge[2].front() <= 0.0 && edge[2].back() >= 2.0 * kPi;
-    double origin[3] = {0.0, 0.0, 0.0}, inv_w[3] = {0.0, 0.0, 0.0};
-    for (int a = 0; a < 3 && ok; a++) ok = evenly(edge[a].data(), n_edge[a], a == 0, &origin[a], &inv_w[a]);
-    size_t chunk_at[3] = {0, 0, 0}, bytes = 48 * sizeof(double);
-    for (int a = 0; a < 3 && ok; a++) {
-      chunk_at[a] = bytes - 48 * sizeof(double);   // (relative to the first chunk: the kernel adds where that lies)
-      for (int q = 0; q < n_rows[a] && ok; q++) {
-        const double *guess = coords.data() + off_g[a] + 3 * static_cast<size_t>(q);
-        double row_origin, row_inv_w;
-        ok = (guess[0] != 0.0) == (a == 0) && evenly(coords.data() + off_f[a] + static_cast<size_t>(q) * (nb[a] + 1), nb[a], a == 0, &row_origin, &row_inv_w);
-      }
-      bytes += static_cast<size_t>(n_rows[a]) * (16 + 64 * static_cast<size_t>(nb[a]));
-    }
-    bytes += 16 * n_boxes;
-    ok = ok && bytes <= static_cast<size_t>(BL_FUSED_REFINED_LDS);
-    if (ok) {
-      std::vector<unsigned int> desc(4 * n_boxes);
-      for (size_t box = 0; box < n_boxes; box++) {
-        const int blk = lattice[box];
-        desc[4 * box] = static_cast<unsigned int>(static_cast<size_t>(blk) * block_cells * 32);
-        for (int a = 0; a < 3; a++)
-          desc[4 * box + 1 + a] = static_cast<unsigned int>(chunk_at[a] + static_cast<size_t>(block_row[static_cast<size_t>(a) * n_b + blk]) * (16 + 64 * static_cast<size_t>(nb[a])));
-      }
-      ctx->d_fused_desc.Ensure(desc.size());
-      Check(hipMemcpy(ctx->d_fused_desc.ptr, desc.data(), desc.size() * sizeof(unsigned int), hipMemcpyHostToDevice), "lattice upload");
-      dev.fused_desc = ctx->d_fused_desc.ptr;
-      dev.fused_lds_bytes = static_cast<int>(bytes);
-      dev.box_l0 = static_cast<float>(origin[0]);
-      dev.box_linv = static_cast<float>(inv_w[0]);
-      for (int a = 1; a < 3; a++) {
-        dev.box_x0[a - 1] = origin[a];
-        dev.box_inv_w[a - 1] = inv_w[a];
-      }
-      dev.r_face_in = edge[0].front();
-      dev.r_face_out = edge[0].back();
-    }
-  }
-  ctx->grid_dev = dev;
-  ctx->lds_table_bytes = 0;
-  ctx->n_i = nb[0];
-  ctx->n_j = nb[1];
-  ctx->n_k = nb[2];
-}
-}  // namespace
-
-namespace {
-// Hash (FNV-1a, 64 bits) of everything about a grid that decides WHERE a sample lies on it: the block table, the coordinate arrays,
-// the FMKS look-up table. Two bl_set_grid calls with the same hash hand over the same geometry (the cells may differ): located
-// samples of the first stay valid for the second (the reference's `first_time`, radiation_integrator.cpp:693-704).
-unsigned long long GridGeometryHash(const bl_grid_desc *g) {
-  unsigned long long h = 1469598103934665603ull;
-  auto mix = [&h](const void *data, size_t bytes) {
-    const unsigned char *p = static_cast<const unsigned char *>(data);
-    // (eight bytes a step where they are there: coordinate arrays are doubles)
-    size_t at = 0;
-    for (; at + 8 <= bytes; at += 8) {
-      unsigned long long word;
-      std::memcpy(&word, p + at, 8);
-      h = (h ^ word) * 1099511628211ull;
-      h ^= h >> 29;
-    }
-    for (; at < bytes; at++) h = (h ^ p[at]) * 1099511628211ull;
+// The one upload step: each table of ctx->grid.tables into its buffer, once; the cells (into the time slice where there is one); then
+// every pointer of BlGridDevice, from buffer base plus offset (BindGridTables)
+void UploadGrid(bl_ctx *ctx, const bl_grid_desc *g, bl_ctx::SlowSlice *slice) {
+  bl_ctx::Grid &G = ctx->grid;
+  const GridTables &t = G.tables;
+  DeviceBuffer<float> &d_cells = slice != nullptr ? slice->cells : G.d_cells;
+  DeviceBuffer<float> &d_kappa = slice != nullptr ? slice->kappa : G.d_kappa;
+  auto put = [](auto &buffer, const auto *data, size_t count, const char *what) {
+    if (count == 0) return;
+    buffer.Ensure(count);
+    Check(hipMemcpy(buffer.ptr, data, count * sizeof(*data), hipMemcpyHostToDevice), what);
   };
-  const int32_t dims[5] = {g->n_blocks, g->n_i, g->n_j, g->n_k, g->n_3_root};
-  mix(dims, sizeof dims);
-  const size_t n_b = static_cast<size_t>(g->n_blocks);
-  mix(g->x1f, n_b * (g->n_i + 1) * sizeof(double)); mix(g->x1v, n_b * g->n_i * sizeof(double));
-  mix(g->x2f, n_b * (g->n_j + 1) * sizeof(double)); mix(g->x2v, n_b * g->n_j * sizeof(double));
-  mix(g->x3f, n_b * (g->n_k + 1) * sizeof(double)); mix(g->x3v, n_b * g->n_k * sizeof(double));
-  if (g->levels != nullptr) mix(g->levels, n_b * sizeof(int32_t));
-  if (g->locations != nullptr) mix(g->locations, n_b * 3 * sizeof(int32_t));
-  if (g->sks_map != nullptr) {
-    const int32_t map_dims[2] = {g->sks_map_n1, g->sks_map_n2};
-    mix(map_dims, sizeof map_dims);
-    mix(g->sks_map, 2 * static_cast<size_t>(g->sks_map_n1) * g->sks_map_n2 * sizeof(double));
-    const double scalars[3] = {g->sks_map_r_in, g->sks_map_dr, g->sks_map_dtheta};
-    mix(scalars, sizeof scalars);
-    mix(g->simulation_bounds, sizeof g->simulation_bounds);
-  }
-  return h != 0 ? h : 1;
+  EnsureStreams(ctx);
+  UploadCellsAs(ctx, g, d_cells, ctx->stream, true);
+  if (t.code_kappa)   // (its own [k][j][i] array; block by block it lies in the caller's plane as the kernels read it)
+    put(d_kappa, t.kappa.empty() ? g->prim + static_cast<size_t>(g->ind_kappa) * t.placement.n_cells : t.kappa.data(), t.placement.n_cells, "grid upload");
+  put(G.d_coords, t.coords.data(), t.coords.size(), "coordinate upload");
+  put(G.d_buckets, t.buckets.data(), t.buckets.size(), "bucket upload");
+  put(G.d_lattice, t.lattice.data(), t.lattice.size(), "lattice upload");
+  put(G.d_fused_desc, t.fused_desc.data(), t.fused_desc.size(), "lattice upload");
+  put(G.d_block_table, t.block_table.data(), t.block_table.size(), "block table upload");
+  put(G.d_block_keys, t.block_keys.data(), t.block_keys.size(), "block table upload");
+  if (t.dev.fmks) put(G.d_sks_map, g->sks_map, static_cast<size_t>(2) * g->sks_map_n1 * g->sks_map_n2, "sks_map upload");
+  G.dev = BindGridTables(t, GridBases{d_cells.ptr, d_kappa.ptr, G.d_coords.ptr, G.d_buckets.ptr, G.d_lattice.ptr, G.d_fused_desc.ptr, G.d_block_table.ptr,
+                                      G.d_block_keys.ptr, G.d_sks_map.ptr});
 }
-}  // namespace
 
-int bl_set_grid(bl_ctx *ctx, const bl_grid_desc *g) {
-  if (ctx == nullptr || g == nullptr) return BL_E_ARG;
+int FailBetweenRenders(bl_ctx *ctx, const Failure &failure) {   // (last_error is the render's to write while it runs)
+  std::lock_guard<std::mutex> guard(ctx->render_lock);
+  return Fail(ctx, failure);
+}
+
+// bl_set_grid, and bl_set_grid_slice with the time slice the cells go to
+int SetGrid(bl_ctx *ctx, const bl_grid_desc *g, bl_ctx::SlowSlice *slice) {
+  bl_ctx::Grid &G = ctx->grid;
   try {
     if (ctx->device == BL_DEVICE_NONE) throw Failure{BL_E_DEVICE, "Host-only context: no HIP device selected (the hot path has no CPU fallback)."};
     if (ctx->params.model_type != BL_MODEL_SIMULATION) throw Failure{BL_E_STATE, "bl_set_grid called in formula mode."};
-    if (ctx->params.slow_light_on && ctx->cells_target == nullptr)
+    if (ctx->params.slow_light_on && slice == nullptr)
       throw Failure{BL_E_STATE, "slow_light_on = true: hand the time slices over with bl_set_grid_slice (or bl_slow_light_read)."};
-    if (g->n_blocks < 1) throw Failure{BL_E_ARG, "Bad grid description."};
-    if (g->n_i < 2 || g->n_j < 2 || g->n_k < 2 || g->prim == nullptr) throw Failure{BL_E_ARG, "Bad grid description."};
+    ValidateGridDescription(*g);
+    if (g->prim == nullptr) throw Failure{BL_E_ARG, "Bad grid description."};
     Check(hipSetDevice(ctx->device), "hipSetDevice");
     // The next snapshot of a series - the geometry in place, to the bit, and the same variables: only the cells are new. They go up on
     // a stream of their own into the second cell array while a render of this context may be running on another host thread, and the
     // arrays change places once that render has ended. (With electron entropy from the grid there is a second array to double: the
     // long way.)
     const bool code_kappa = ctx->params.plasma_model == BL_PLASMA_CODE_KAPPA;
-    const int order_now[8] = {g->ind_rho, g->ind_pgas, g->ind_uu1, g->ind_uu2, g->ind_uu3, g->ind_bb1, g->ind_bb2, g->ind_bb3};
-    if (ctx->have_grid && ctx->cells_target == nullptr && ctx->placement.valid && !code_kappa && ctx->grid_geometry != 0 && GridGeometryHash(g) == ctx->grid_geometry
-        && std::equal(order_now, order_now + 8, ctx->placement.order) && g->n_var == ctx->grid_meta.n_var
-        && g->plasma_gamma == ctx->grid_meta.plasma_gamma && g->plasma_gamma_i == ctx->grid_meta.plasma_gamma_i && g->plasma_gamma_e == ctx->grid_meta.plasma_gamma_e) {
-      if (ctx->stream_upload == nullptr) Check(hipStreamCreateWithFlags(&ctx->stream_upload, hipStreamNonBlocking), "hipStreamCreate");
-      UploadCellsAs(ctx, g, ctx->d_cells_back, ctx->stream_upload, false);
+    int order_now[8];
+    if (G.have && slice == nullptr && G.swappable && !code_kappa && SameGeometry(G.tables, *g) && GridVariableOrder(*g, false, order_now)
+        && std::equal(order_now, order_now + 8, G.tables.placement.order) && g->n_var == G.meta.n_var
+        && g->plasma_gamma == G.meta.plasma_gamma && g->plasma_gamma_i == G.meta.plasma_gamma_i && g->plasma_gamma_e == G.meta.plasma_gamma_e) {
+      if (G.stream_upload == nullptr) Check(hipStreamCreateWithFlags(&G.stream_upload, hipStreamNonBlocking), "hipStreamCreate");
+      UploadCellsAs(ctx, g, G.d_cells_back, G.stream_upload, false);
       std::lock_guard<std::mutex> guard(ctx->render_lock);
-      std::swap(ctx->d_cells, ctx->d_cells_back);
-      ctx->grid_dev.cells = ctx->d_cells.ptr;
-      ctx->grid_meta = *g;
+      std::swap(G.d_cells, G.d_cells_back);
+      G.dev.cells = G.d_cells.ptr;
+      G.meta = *g;
       return BL_OK;
     }
     std::lock_guard<std::mutex> guard(ctx->render_lock);   // (everything about the grid changes: not beside a render)
-    ctx->have_grid = false;   // a failed upload leaves no grid behind (the previous one may be half overwritten)
-    ctx->grid_geometry = 0;
-    ctx->placement.valid = false;
-    if (ctx->params.simulation_interp && ctx->params.simulation_block_interp) {
-      UploadRefinedGrid(ctx, g);   // inter-block interpolation works on the MeshBlocks as they are
-    } else {
-      try {
-        UploadMergedGrid(ctx, g);
-      } catch (const Failure &failure) {
-        if (failure.message != kIrregular) throw;
-        UploadRefinedGrid(ctx, g);   // blocks of several levels, or a tiling with holes
-      }
-    }
-    ctx->grid_meta = *g;
-    if (ctx->cells_target == nullptr) ctx->grid_geometry = GridGeometryHash(g);   // (slow light locates per snapshot: no located samples are kept)
-    ctx->grid_outer_x1 = g->x1f[g->n_i];
-    for (int blk = 1; blk < g->n_blocks; blk++)
-      ctx->grid_outer_x1 = std::max(ctx->grid_outer_x1, g->x1f[static_cast<size_t>(blk) * (g->n_i + 1) + g->n_i]);
-    ctx->have_grid = true;
+    G.have = false;   // a refused or failed grid leaves no grid behind (the previous one may be half overwritten)
+    G.swappable = false;
+    G.tables.geometry = 0;
+    GridTables tables = BuildGridTables(ctx->params, *g);
+    const unsigned long long geometry = slice == nullptr ? tables.geometry : 0;   // (slow light locates per snapshot: no located samples are kept)
+    tables.geometry = 0;
+    G.tables = std::move(tables);
+    UploadGrid(ctx, g, slice);
+    G.tables.kappa = std::vector<float>();   // (as large as a cell plane, and on the device now)
+    G.tables.geometry = geometry;
+    G.meta = *g;
+    G.swappable = slice == nullptr;   // (the time slices of slow light have no second array to change places with)
+    G.have = true;
   } catch (const Failure &failure) {
-    return Fail(ctx, failure);
+    return FailBetweenRenders(ctx, failure);
   }
   return BL_OK;
+}
+}  // namespace
+
+int bl_set_grid(bl_ctx *ctx, const bl_grid_desc *g) {
+  if (ctx == nullptr || g == nullptr) return BL_E_ARG;
+  return SetGrid(ctx, g, nullptr);
 }
 
 int bl_set_grid_slice(bl_ctx *ctx, int slice, const bl_grid_desc *g, double time) {
   if (ctx == nullptr || g == nullptr) return BL_E_ARG;
-  try {
-    const bl_params &p = ctx->params;
-    if (p.model_type != BL_MODEL_SIMULATION || !p.slow_light_on) throw Failure{BL_E_STATE, "bl_set_grid_slice needs slow_light_on = true."};
-    if (slice < 0 || slice >= p.slow_chunk_size) throw Failure{BL_E_ARG, "Time slice index outside slow_chunk_size."};
-    ctx->slow_slices.resize(p.slow_chunk_size);
-    bl_ctx::SlowSlice &target = ctx->slow_slices[slice];
-    ctx->cells_target = &target.cells;
-    ctx->kappa_target = &target.kappa;
-    const int rc = bl_set_grid(ctx, g);
-    ctx->cells_target = nullptr;
-    ctx->kappa_target = nullptr;
-    if (rc != BL_OK) return rc;
-    target.time = time;
-    target.set = true;
-  } catch (const Failure &failure) {
-    ctx->cells_target = nullptr;
-    ctx->kappa_target = nullptr;
-    return Fail(ctx, failure);
-  }
+  const bl_params &p = ctx->params;
+  if (p.model_type != BL_MODEL_SIMULATION || !p.slow_light_on) return FailBetweenRenders(ctx, Failure{BL_E_STATE, "bl_set_grid_slice needs slow_light_on = true."});
+  if (slice < 0 || slice >= p.slow_chunk_size) return FailBetweenRenders(ctx, Failure{BL_E_ARG, "Time slice index outside slow_chunk_size."});
+  ctx->slow_slices.resize(p.slow_chunk_size);
+  bl_ctx::SlowSlice &target = ctx->slow_slices[slice];
+  const int rc = SetGrid(ctx, g, &target);
+  if (rc != BL_OK) return rc;
+  target.time = time;
+  target.set = true;
   return BL_OK;
 }
 
@@ -1677,7 +1139,7 @@ void bl_free(bl_ctx *ctx) {
     return;
   }
   (void)hipSetDevice(ctx->device);
-  ctx->d_cells.Free(); ctx->d_kappa.Free(); ctx->d_coords.Free(); ctx->d_buckets.Free(); ctx->slot[0].Free(); ctx->slot[1].Free();
+  ctx->grid.d_cells.Free(); ctx->grid.d_kappa.Free(); ctx->grid.d_coords.Free(); ctx->grid.d_buckets.Free(); ctx->slot[0].Free(); ctx->slot[1].Free();
   ctx->d_freq.Free(); ctx->d_pixel_map.Free();
   ctx->d_block_locs.Free(); ctx->d_tile_order.Free(); ctx->d_cameras.Free(); ctx->d_render_params.Free(); ctx->d_render.Free(); ctx->d_shade_cold.Free(); ctx->d_pol_variant_table.Free(); ctx->d_pol_variant_args.Free(); ctx->d_image.Free(); ctx->d_camera_pos.Free(); ctx->d_camera_dir.Free();
   ctx->d_out_sample_num.Free(); ctx->d_out_flags.Free();
@@ -1687,7 +1149,7 @@ void bl_free(bl_ctx *ctx) {
   if (ctx->caller_event != nullptr) (void)hipEventDestroy(ctx->caller_event);
   if (ctx->stream != nullptr) (void)hipStreamDestroy(ctx->stream);
   if (ctx->stream_geo != nullptr) (void)hipStreamDestroy(ctx->stream_geo);
-  if (ctx->stream_upload != nullptr) (void)hipStreamDestroy(ctx->stream_upload);
+  if (ctx->grid.stream_upload != nullptr) (void)hipStreamDestroy(ctx->grid.stream_upload);
   // (stream_few / stream_most are the process's, borrowed: EnsureSplitStreams)
   delete ctx;
 }

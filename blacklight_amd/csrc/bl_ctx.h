@@ -1,7 +1,7 @@
 // bl_ctx.h - the context behind the C-ABI handle (include/blacklight_amd.h) and the few helpers the host-side
 // translation units of the HIP path share: bl_api.hip (construction, validation, grid upload, settings),
-// bl_render.hip (bl_render: chunk planning, kernel pipeline, statistics) and bl_checkpoint.cpp (the checkpoint files and their
-// conversions, host code only). Internal, hidden visibility.
+// bl_render.hip (bl_render: chunk planning, kernel pipeline, statistics), bl_grid.cpp (a grid's tables) and bl_checkpoint.cpp (the
+// checkpoint files and their conversions) - the last two host code only. Internal, hidden visibility.
 #ifndef BLACKLIGHT_AMD_BL_CTX_H_
 #define BLACKLIGHT_AMD_BL_CTX_H_
 #include <hip/hip_runtime.h>
@@ -24,6 +24,7 @@
 #include "bl_bessel.h"
 #include "bl_camera.h"
 #include "bl_device.h"
+#include "bl_grid.h"
 #include "bl_internal.h"
 
 // The launch wrappers (at the end of each kernel file): each takes its part of the render's KernelPlan (bl_kernel_plan.h), maps it to a
@@ -195,43 +196,32 @@ struct bl_ctx {
   DeviceBuffer<double> d_render;     // staging for host output
   double plasma_thermal_frac = 0.0;
 
-  // grid
-  bool have_grid = false;
-  int n_i = 0, n_j = 0, n_k = 0;
-  bl_grid_desc grid_meta{};
-  DeviceBuffer<float> d_cells;
   // bl_set_grid beside bl_render (another host thread: the next snapshot of a series staged while this one renders). The render holds
   // render_lock from start to end; a bl_set_grid whose geometry is the one in place uploads its cells into d_cells_back on a stream of
   // its own without the lock, then takes it - waiting for the render to end - to let the two cell arrays change places.
   std::mutex render_lock;
-  DeviceBuffer<float> d_cells_back;
-  hipStream_t stream_upload = nullptr;
-  struct CellPlacement {   // how the caller's planes become d_cells, as the full upload decided (UploadCells)
-    bool valid = false, code_kappa = false;
-    size_t n_cells = 0;
-    int nb[3] = {0, 0, 0};
-    int order[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool has_origin = false;
-    std::vector<unsigned long long> origin;
-    unsigned long long row_stride = 0, plane_stride = 0;
-  } placement;
-  DeviceBuffer<float> d_cell_planes;                 // bl_set_grid: the caller's eight variable planes as uploaded, before bl_interleave_cells_kernel
-  DeviceBuffer<unsigned long long> d_block_origin;   // ... and where every block's cells go in a merged array
-  DeviceBuffer<float> d_kappa;   // electron entropy per cell (plasma_model = code_kappa)
-  DeviceBuffer<double> d_coords;   // x1f x1v x2f x2v x3f x3v packed
-  DeviceBuffer<unsigned short> d_buckets;
-  DeviceBuffer<int> d_lattice;   // refined mesh: box of the block-boundary lattice -> block
-  DeviceBuffer<unsigned int> d_fused_desc;   // ... -> what bl_shade_fused2_kernel<..., kRefined> needs of the block (BlGridDevice::fused_desc)
-  DeviceBuffer<double> d_sks_map;   // simulation_coord = fmks: the reader's SKS -> FMKS look-up table
-  DeviceBuffer<int> d_block_table;                  // inter-block interpolation: levels, locations, hash blocks
-  DeviceBuffer<unsigned long long> d_block_keys;    // ... and hash keys
-  BlGridDevice grid_dev{};
-  double grid_outer_x1 = 0.0;   // largest outer x1 face of the grid's blocks (bl_set_grid)
-  std::vector<int> merged_block_at;   // merged grid: lattice position (k, j, i of the block) -> MeshBlock of the file
-  int merged_blocks[3] = {1, 1, 1};   // ... and the lattice's extent
+  // The grid as bl_set_grid left it: what the host built of the caller's description (bl_grid.h), the device's copy of each table, and
+  // the kernels' view of both. A refused or failed bl_set_grid leaves `have` false.
+  struct Grid {
+    bool have = false;
+    bool swappable = false;            // d_cells was filled as tables.placement says, and d_cells_back may take its place (not so for a time slice of slow light)
+    bl_grid_desc meta{};               // the description's scalars (its pointers were the caller's, for the duration of the call)
+    GridTables tables;                 // host tables, placement, extents, budgets, the geometry as given and its hash (0: none kept)
+    BlGridDevice dev{};                // tables.dev with every pointer bound to the buffers below
+    DeviceBuffer<float> d_cells, d_cells_back;
+    DeviceBuffer<float> d_cell_planes;                 // the caller's eight variable planes as uploaded, before bl_interleave_cells_kernel
+    DeviceBuffer<unsigned long long> d_block_origin;   // ... and where every block's cells go in a merged array
+    DeviceBuffer<float> d_kappa;       // electron entropy per cell (plasma_model = code_kappa)
+    DeviceBuffer<double> d_coords;
+    DeviceBuffer<unsigned short> d_buckets;
+    DeviceBuffer<int> d_lattice;       // refined mesh: box of the block-boundary lattice -> block, the blocks' rows
+    DeviceBuffer<unsigned int> d_fused_desc;   // ... -> what bl_shade_fused2_kernel<..., kRefined> needs of the block (BlGridDevice::fused_desc)
+    DeviceBuffer<double> d_sks_map;    // simulation_coord = fmks: the reader's SKS -> FMKS look-up table
+    DeviceBuffer<int> d_block_table;                  // inter-block interpolation: levels, locations, hash blocks
+    DeviceBuffer<unsigned long long> d_block_keys;    // ... and hash keys
+    hipStream_t stream_upload = nullptr;
+  } grid;
   bool sample_checkpoint_saved = false;   // checkpoint_sample_save: written with the first image only (radiation_integrator.cpp:699-704)
-  int lds_table_bytes = 0;
-  DeviceBuffer<float> *cells_target = nullptr, *kappa_target = nullptr;   // where the grid upload puts the cells
 
   // slow light: the reader's window of time slices (prim[n], time[n]; n = 0 latest) on one geometry
   struct SlowSlice {
@@ -350,7 +340,6 @@ struct bl_ctx {
     } store;
   } resident;
   int geodesic_reuse = 1;             // bl_set_geodesic_reuse()
-  unsigned long long grid_geometry = 0;   // hash of the grid's geometry as bl_set_grid last saw it (block table, coordinates, look-up tables)
   RayArrays rays;
   DeviceBuffer<double> d_ray_start;              // BL_RAY_START_FIELDS rows: start state of every ray (bl_ray_init_kernel -> geodesic kernel); never set aside
   uint64_t RayBytes() const { return rays.Bytes() + d_ray_start.Bytes(); }

@@ -249,7 +249,7 @@ static void (*locate_kernel(const KernelPlan::Locate &l))(BlShadeArgs) {
   return l.slow ? bl_locate_kernel<false, true, false> : bl_locate_kernel<false, false, false>;
 }
 
-// Where the locate kernel reads the tables and the launch that follows (lds_bytes: the merged grid's tables, bl_ctx::lds_table_bytes).
+// Where the locate kernel reads the tables and the launch that follows (lds_bytes: the merged grid's tables, GridTables::lds_table_bytes).
 // A mesh with refinement - tables that fit four times into a compute unit's LDS (36 KiB): 256-lane workgroups. Larger ones (up to
 // BL_LOCATE_REFINED_LDS): one 1 024-lane workgroup to a compute unit, one round of them. Beyond that the tables are searched where they
 // lie in HBM (refined_lds_bytes = 0). Behind the tables: the waves' lists of samples that wait for FindNearbyInds, 1 KiB each.

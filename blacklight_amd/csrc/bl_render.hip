@@ -250,9 +250,9 @@ void FoldUnits(const bl_ctx *ctx, double rho_cgs, BlPlasmaDevice &pl, double (&f
   pl.e_unit = pl.d_unit * kC * kC;
   pl.b_unit = blm_sqrt(4.0 * kPi * pl.e_unit);
   const bool use_p = p.plasma_use_p != 0;
-  const double g0 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma - 1.0);
-  const double g1 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_i - 1.0);
-  const double g2 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_e - 1.0);
+  const double g0 = use_p ? 1.0 : 1.0 / (ctx->grid.meta.plasma_gamma - 1.0);
+  const double g1 = use_p ? 1.0 : 1.0 / (ctx->grid.meta.plasma_gamma_i - 1.0);
+  const double g2 = use_p ? 1.0 : 1.0 / (ctx->grid.meta.plasma_gamma_e - 1.0);
   const double n_e_per_rho = pl.d_unit / (p.plasma_mu * kMp * (1.0 + 1.0 / p.plasma_ne_ni));
   const double nu_c_over_b = kE * pl.b_unit / (2.0 * kPi * kMe * kC);
   fast_k[0] = (1.0 + p.plasma_ne_ni) * p.plasma_mu * kMp * pl.e_unit / pl.d_unit * g0;
@@ -379,7 +379,7 @@ void PlanJob(RenderJob &job) {
   const bl_params &p = ctx->params;
   job.simulation = p.model_type == BL_MODEL_SIMULATION;
   if (ctx->device == BL_DEVICE_NONE) throw Failure{BL_E_DEVICE, "Host-only context: no HIP device selected (the hot path has no CPU fallback)."};
-  if (job.simulation && !ctx->have_grid) throw Failure{BL_E_STATE, "bl_render called before bl_set_grid."};
+  if (job.simulation && !ctx->grid.have) throw Failure{BL_E_STATE, "bl_render called before bl_set_grid."};
   if (d->n_rays <= 0 || (d->image == nullptr && ctx->image_num_quantities > 0))
     throw Failure{BL_E_ARG, "bl_render needs n_rays > 0 and an image buffer."};
   if (ctx->render_num_images > 0 && d->render == nullptr) throw Failure{BL_E_ARG, "bl_render needs a render buffer when render_num_images > 0."};
@@ -454,7 +454,7 @@ void PlanJob(RenderJob &job) {
       if (d->pixel_map[ray] < 0 || static_cast<size_t>(d->pixel_map[ray]) >= n_pix)
         throw Failure{BL_E_ARG, "pixel_map names a pixel the geodesic checkpoint does not hold."};
   }
-  job.block_interp = job.simulation && ctx->grid_dev.block_interp != 0;
+  job.block_interp = job.simulation && ctx->grid.dev.block_interp != 0;
   // SaveSampling() (sample_checkpoint.cpp:22-46): with the first image of the root level only (radiation_integrator.cpp:693-704)
   job.sample_save = job.simulation && p.checkpoint_sample_save && d->level == 0 && !ctx->sample_checkpoint_saved;
   if (job.sample_save && (d->pixel_map != nullptr || job.n_rays != job.level_pixels))
@@ -500,9 +500,9 @@ void PlanJob(RenderJob &job) {
   // Plain images of a spherical Kerr-Schild simulation with fallback values beyond the grid: nothing is recorded of the steps that
   // lie in the empty shell between the grid's outer edge and the camera's sphere (both tiers; the samples count as ever)
   job.skip_shell = job.simulation && !job.aux && !ctx->polarized && !job.slow && job.no_checkpoint
-      && !job.need_time && p.simulation_coord == BL_COORD_SKS && !ctx->grid_dev.fmks && !p.fallback_nan && ctx->grid_outer_x1 > 0.0
+      && !job.need_time && p.simulation_coord == BL_COORD_SKS && !ctx->grid.dev.fmks && !p.fallback_nan && ctx->grid.tables.outer_x1 > 0.0
       && p.ray_integrator == BL_INTEGRATOR_DP   // (the fixed-step steppers have no instantiation for it: bl_launch_geodesic)
-      && ctx->grid_outer_x1 < p.camera_r && !(ctx->switches & BL_SWITCH_RECORD_EVERY_STEP);
+      && ctx->grid.tables.outer_x1 < p.camera_r && !(ctx->switches & BL_SWITCH_RECORD_EVERY_STEP);
   // The fast path over one grid (or equal blocks merged into one) with its coordinate tables in LDS, trilinear sampling and no
   // optional geometric cut locates its samples inside the coefficient kernel: no located samples in HBM at all
   // (one frequency - with four or more it ends at the sample's factors, which no frequency enters: BlFreqInputs - over a single block
@@ -510,33 +510,33 @@ void PlanJob(RenderJob &job) {
   // (a mesh with refinement whose blocks and rows are evenly spaced has an instantiation of that kernel too - one frequency, composed
   // maps: bl_fused2_refined_applicable and the conditions of job.composed below)
   const bool records_every_sample = ctx->reproducible || (ctx->switches & BL_SWITCH_SAMPLE_RECORDS) != 0;
-  const bool fused2_grid = ctx->grid_dev.n_blocks == 0
-      ? ctx->lds_table_bytes > 0 && bl_fused2_applicable(&ctx->grid_dev, job.freq_split ? 1 : job.n_nu, job.n_rays) != 0
-      : !job.freq_split && !records_every_sample && !job.skip_shell && bl_fused2_refined_applicable(&ctx->grid_dev, job.n_nu, job.n_rays) != 0;
+  const bool fused2_grid = ctx->grid.dev.n_blocks == 0
+      ? ctx->grid.tables.lds_table_bytes > 0 && bl_fused2_applicable(&ctx->grid.dev, job.freq_split ? 1 : job.n_nu, job.n_rays) != 0
+      : !job.freq_split && !records_every_sample && !job.skip_shell && bl_fused2_refined_applicable(&ctx->grid.dev, job.n_nu, job.n_rays) != 0;
   // What the three kernels with the locate step inside ask for alike: a simulation on a spherical Kerr-Schild grid (their locate step is
   // the spherical one: Cartesian grids go through the locate kernel, FMKS grids too), trilinear sampling, one time slice, no optional
   // geometric cut, no geodesic checkpoint loaded or saved (interleaved records whose momenta are not renormalised yet), no sample
   // checkpoint (it is made of the located samples), neither measurement switch
-  const bool locate_inside_possible = job.simulation && !job.slow && !ctx->grid_dev.fmks && p.simulation_interp && p.simulation_coord == BL_COORD_SKS
+  const bool locate_inside_possible = job.simulation && !job.slow && !ctx->grid.dev.fmks && p.simulation_interp && p.simulation_coord == BL_COORD_SKS
       && !GeometricCut(p) && job.no_checkpoint && !(ctx->switches & (BL_SWITCH_NO_FUSED_LOCATE | BL_SWITCH_SPLIT_RECORDS));
   // (its own: the tolerant tier's scope - only this one reads job.fast, which leaves it plain images and so no sample times - without
   // the optical-depth row and power-law electrons; it alone takes inter-block interpolation, which its grid predicate decides)
   job.fused2 = locate_inside_possible && job.fast && !job.tau_row && fused2_grid && p.plasma_power_frac == 0.0;
   // ... with theta and phi relative to the centre of the guessed cell where the series behind them reaches every point of every angular
   // cell (bl_local_angles.h: 1 / 16 rad from the centre; one block - the mesh with refinement keeps acos / atan2)
-  job.local_angles = job.fused2 && ctx->grid_dev.n_blocks == 0 && ctx->grid_dev.angle_trig[0] != nullptr && ctx->grid_dev.angle_reach <= kLocalAngleReach && !(ctx->switches & BL_SWITCH_GLOBAL_ANGLES);
+  job.local_angles = job.fused2 && ctx->grid.dev.n_blocks == 0 && ctx->grid.dev.angle_trig[0] != nullptr && ctx->grid.dev.angle_reach <= kLocalAngleReach && !(ctx->switches & BL_SWITCH_GLOBAL_ANGLES);
   // The exact tier's plain image at one frequency over such a grid: the locate step inside bl_shade_exact2_kernel (bit-identical
   // to bl_locate_plain_kernel + bl_shade_exact_kernel, whose conditions these are: job.fast's electrons, restated because it is off)
   job.exact_fused = locate_inside_possible && !job.fast && !job.aux && !ctx->polarized && !job.block_interp && job.n_nu == 1
       && p.plasma_kappa_frac == 0.0 && p.plasma_power_frac == 0.0 && p.plasma_model != BL_PLASMA_CODE_KAPPA && !p.ray_flat
       && ctx->plasma_thermal_frac != 0.0
-      && (ctx->grid_dev.n_blocks == 0 ? bl_fused2_applicable(&ctx->grid_dev, job.n_nu, job.n_rays) != 0 : bl_polarized2_refined_applicable(&ctx->grid_dev, job.n_rays) != 0);
+      && (ctx->grid.dev.n_blocks == 0 ? bl_fused2_applicable(&ctx->grid.dev, job.n_nu, job.n_rays) != 0 : bl_polarized2_refined_applicable(&ctx->grid.dev, job.n_rays) != 0);
   // Polarized runs over such a grid: the frame-and-inputs kernel with the locate step inside (bit-identical to bl_locate_plain_kernel +
   // bl_shade_kernel<polarized>, whose conditions these are; electron entropy from the grid is a ninth value it does not gather)
   // (... or a mesh with refinement whose tables the tolerant tier's fused kernel takes: the polarized kernel's locate step knows them too)
   // (only this one tests need_time: its runs may carry auxiliary rows - image_time - which the other two exclude altogether)
   job.pol_fused = locate_inside_possible && ctx->polarized && !job.block_interp && p.plasma_model != BL_PLASMA_CODE_KAPPA && !p.ray_flat && !job.need_time
-      && (ctx->grid_dev.n_blocks == 0 ? bl_fused2_applicable(&ctx->grid_dev, 1, job.n_rays) != 0 : bl_polarized2_refined_applicable(&ctx->grid_dev, job.n_rays) != 0);
+      && (ctx->grid.dev.n_blocks == 0 ? bl_fused2_applicable(&ctx->grid.dev, 1, job.n_rays) != 0 : bl_polarized2_refined_applicable(&ctx->grid.dev, job.n_rays) != 0);
   job.interleaved = (job.fused2 || job.exact_fused || job.pol_fused || !job.simulation) && job.no_checkpoint && !(ctx->switches & BL_SWITCH_SPLIT_RECORDS);
   job.locate_inside = job.fused2 || job.exact_fused || job.pol_fused;
   // The benchmark's kernel also composes the affine maps of a ray's neighbouring samples before they leave it (the geodesic kernel
@@ -662,13 +662,13 @@ void BuildReuseKeys(RenderJob &job) {
   key.Put(d->pixel_map != nullptr ? 1 : 0); key.Put(map_hash);
   // the layout of the records and what the stepper leaves out of them
   key.Put(job.need_time ? 1 : 0); key.Put(job.interleaved ? 1 : 0); key.Put(job.composed ? 1 : 0); key.Put(job.skip_shell ? 1 : 0); key.Put(job.raster ? 1 : 0);
-  key.Put(job.skip_shell ? ctx->grid_outer_x1 : 0.0);
+  key.Put(job.skip_shell ? ctx->grid.tables.outer_x1 : 0.0);
   // who steps which rays (the records' order; bl_stats says it)
   key.Put(ctx->tail_policy); key.Put(ctx->switches); key.Put(ctx->overlap_chunks); key.Put(ctx->num_cus);
   key.Put(ctx->scratch_limit);   // (a caller that lowers the cap wants the memory back: the records are integrated again, in as many chunks as it takes)
   job.located_key = job.geo_key;
   KeyWriter located{&job.located_key};
-  located.Put(ctx->grid_geometry); located.Put(ctx->undefined_policy); located.Put(job.fast ? 1 : 0); located.Put(job.block_interp ? 1 : 0);
+  located.Put(ctx->grid.tables.geometry); located.Put(ctx->undefined_policy); located.Put(job.fast ? 1 : 0); located.Put(job.block_interp ? 1 : 0);
   located.Put(ctx->guard_band); located.Put(p.simulation_interp); located.Put(p.simulation_coord);
 }
 
@@ -1182,7 +1182,7 @@ void PlanKernels(RenderJob &job) {
   KernelPlan &k = job.kernels;
   k = KernelPlan{};
   const bool spin_zero = ctx->st.bh_a == 0.0;
-  const bool refined = job.simulation && ctx->grid_dev.n_blocks > 0;
+  const bool refined = job.simulation && ctx->grid.dev.n_blocks > 0;
   const bool slices = job.slow && p.slow_chunk_size > 0;
   const bool sks = p.simulation_coord != BL_COORD_CKS;   // (FMKS: everything but the cell search treats the grid as sks, BuildShadeArgs)
   const bool power_law = job.simulation && p.plasma_power_frac != 0.0;
@@ -1192,13 +1192,13 @@ void PlanKernels(RenderJob &job) {
   k.quad.spin_zero = spin_zero;
   if (job.simulation && !job.locate_inside && !job.reuse_located) {
     // the common case has a kernel of its own: one grid with its tables in LDS, spherical, trilinear, no optional geometric cut
-    const bool plain = !refined && !slices && ctx->lds_table_bytes > 0 && !ctx->grid_dev.fmks && p.simulation_interp && !GeometricCut(p) && sks
+    const bool plain = !refined && !slices && ctx->grid.tables.lds_table_bytes > 0 && !ctx->grid.dev.fmks && p.simulation_interp && !GeometricCut(p) && sks
         && !use.anchors && !(ctx->switches & BL_SWITCH_GENERAL_LOCATE);
     k.locate.kind = plain ? KernelPlan::Locate::kPlain : KernelPlan::Locate::kGeneral;
     k.locate.spin_zero = plain && spin_zero;
     k.locate.refined = refined;
     k.locate.slow = slices;
-    k.locate.tables_in_hbm = !plain && !refined && ctx->lds_table_bytes == 0;
+    k.locate.tables_in_hbm = !plain && !refined && ctx->grid.tables.lds_table_bytes == 0;
   }
   KernelPlan::Shade &c = k.shade;
   c.model = p.model_type;
@@ -1247,7 +1247,7 @@ void PlanKernels(RenderJob &job) {
       r.extended = job.fused2 ? job.block_interp : (!sks || power_law || job.tau_row || use.anchors || slices);
       r.sks = job.fused2 || sks;
       r.spin_zero = !r.extended && spin_zero;
-      const int tables = ctx->grid_dev.refined_lds_bytes;   // (the mesh's tables in LDS, if they are small enough)
+      const int tables = ctx->grid.dev.refined_lds_bytes;   // (the mesh's tables in LDS, if they are small enough)
       r.table_bytes = (r.extended && job.fused2 && refined && tables > 0 && tables <= BL_REDO_TABLES_LDS) ? tables : 0;
     }
   }
@@ -1435,7 +1435,7 @@ void BuildTraceArgs(RenderJob &job) {
   ta.skip_high = 0.0;
   if (job.skip_shell) {
     const double a = ctx->st.bh_a;
-    ta.skip_low = std::sqrt(ctx->grid_outer_x1 * ctx->grid_outer_x1 * (1.0 + 1.0e-9) + a * a) * (1.0 + 1.0e-12);
+    ta.skip_low = std::sqrt(ctx->grid.tables.outer_x1 * ctx->grid.tables.outer_x1 * (1.0 + 1.0e-9) + a * a) * (1.0 + 1.0e-12);
     ta.skip_high = p.camera_r * (1.0 - 1.0e-9);
   }
   ta.ray_step = p.ray_step;
@@ -1676,9 +1676,9 @@ void BuildShadeArgs(RenderJob &job) {
     const ElectronConstants ec = FillElectronConstants(job.base_mix, ctx->polarized);   // (the render's: PlanJob; BindVariant each pass's)
     BindElectronConstants(ec, ctx->polarized, pl, sa);
     cold.kappa = ec.kappa;
-    cold.plasma_gamma = ctx->grid_meta.plasma_gamma;
-    cold.plasma_gamma_i = ctx->grid_meta.plasma_gamma_i;
-    cold.plasma_gamma_e = ctx->grid_meta.plasma_gamma_e;
+    cold.plasma_gamma = ctx->grid.meta.plasma_gamma;
+    cold.plasma_gamma_i = ctx->grid.meta.plasma_gamma_i;
+    cold.plasma_gamma_e = ctx->grid.meta.plasma_gamma_e;
     pl.plasma_use_p = p.plasma_use_p;
     pl.simulation_interp = p.simulation_interp;
     // fmks: the reader has put vectors on the spherical Kerr-Schild basis; everything but the cell search treats the
@@ -1728,8 +1728,8 @@ void BuildShadeArgs(RenderJob &job) {
       }
       sa.fast_angle_band = std::max(1.0e-12, ctx->guard_band > 1.0e-8 ? ctx->guard_band : 0.0);   // (the debug switch widens both kinds of band)
     }
-    sa.grid = ctx->grid_dev;
-    sa.lds_table_bytes = ctx->lds_table_bytes;
+    sa.grid = ctx->grid.dev;
+    sa.lds_table_bytes = ctx->grid.tables.lds_table_bytes;
     sa.undefined_edge = (ctx->undefined_policy & BL_UNDEFINED_EDGE) ? 1 : 0;
     // Polarized runs in the tolerant tier keep the exact tier's per-frequency coefficient kernel: the reference's polarized step
     // amplifies last-place differences of the coefficients by up to ten orders of magnitude in optically and Faraday thick
@@ -1895,8 +1895,8 @@ void BuildTransferArgs(RenderJob &job) {
     static_assert(BL_TRANSFER_MAX_MODELS == BL_MAX_ELECTRON_MODELS, "model constants");
     static_assert(BL_TRANSFER_MAX_UNITS == BL_MAX_DENSITY_UNITS, "unit constants");
     const bool use_p = p.plasma_use_p != 0;
-    const double g1 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_i - 1.0);
-    const double g2 = use_p ? 1.0 : 1.0 / (ctx->grid_meta.plasma_gamma_e - 1.0);
+    const double g1 = use_p ? 1.0 : 1.0 / (ctx->grid.meta.plasma_gamma_i - 1.0);
+    const double g2 = use_p ? 1.0 : 1.0 / (ctx->grid.meta.plasma_gamma_e - 1.0);
     const Variants &vs = job.variants;
     // (model-major, then unit, then cut: model m's variants start at m n_u n_s, the first model's are the (unit, cut) pairs)
     const int n_u = std::max(1, vs.n_units), n_s = std::max(1, vs.n_cuts);
@@ -2127,8 +2127,8 @@ void SaveChunk(RenderJob &job, int k, long long begin, long long done) {
     DownloadRows(&located, sl.d_located.ptr, n_written);
     if (!job.fast) DownloadRows(&tags, sl.d_located_tag.ptr, n_written);
     if (job.block_interp) DownloadRows(&anchors, sl.d_anchors.ptr, n_written * 8);
-    AddChunkToSampleSave(chunk, located, tags, anchors, job.interleaved, job.fast, job.block_interp, ctx->params, ctx->grid_dev, ctx->merged_blocks,
-                         ctx->merged_block_at, job.n_rays, &job.sampling);
+    AddChunkToSampleSave(chunk, located, tags, anchors, job.interleaved, job.fast, job.block_interp, ctx->params, ctx->grid.dev, ctx->grid.tables.merged_blocks,
+                         ctx->grid.tables.merged_block_at, job.n_rays, &job.sampling);
   }
 }
 
@@ -2226,9 +2226,9 @@ void LaunchShadingStage(RenderJob &job, int k, bool geodesic_beside, hipStream_t
   Check(hipEventRecord(e[2], stream), "event");
   if (plan.locate.kind != KernelPlan::Locate::kNone) {
     const int locate_grid = geodesic_beside ? job.locate_grid_shared : job.locate_grid_alone;
-    Check(bl_launch_locate(&sa, plan.locate, locate_grid, ctx->lds_table_bytes, stream), "locate kernel launch");
+    Check(bl_launch_locate(&sa, plan.locate, locate_grid, ctx->grid.tables.lds_table_bytes, stream), "locate kernel launch");
     if (ctx->debug_counters) {
-      bl_locate_tables(&sa, plan.locate, locate_grid, ctx->lds_table_bytes, &job.tables_locate_last);
+      bl_locate_tables(&sa, plan.locate, locate_grid, ctx->grid.tables.lds_table_bytes, &job.tables_locate_last);
       if (job.tables_locate.where == TableLaunch::kNone) job.tables_locate = job.tables_locate_last;
     }
   }

@@ -179,7 +179,7 @@ assert 64 * (N_FUSED_FITS + 16) + 384 == 64 * KIB
 
 
 def _lds_table_bytes(n):
-    """bl_api.hip: faces and centres as doubles, max(512, 8 n) 16-bit buckets per axis; rounded up to 16 where it is staged"""
+    """bl_grid.cpp: faces and centres as doubles, max(512, 8 n) 16-bit buckets per axis; rounded up to 16 where it is staged"""
     return sum((2 * m + 1) * 8 + max(512, 8 * m) * 2 for m in n)
 
 
@@ -361,7 +361,7 @@ def test_same_tables_as_equal_blocks(spin, interp, capfd, monkeypatch, built_lib
 MESH_CAMERA = dict(camera_r=50.0)
 
 def _mesh_bytes(block, split, block_interp=False):
-    """BlGridDevice::refined_lds_bytes and ::fused_lds_bytes of _mesh(block, split) as UploadRefinedGrid (bl_api.hip) computes them: the
+    """BlGridDevice::refined_lds_bytes and ::fused_lds_bytes of _mesh(block, split) as BuildLatticeTables (bl_grid.cpp) computes them: the
     two-level mesh has 36 blocks on a 4 x 4 x 4 lattice of fine boxes and six distinct coordinate rows per axis, each times the split.
     (0: beyond BL_LOCATE_REFINED_LDS / not a mesh for the fused kernel)"""
     nb = [b // s for b, s in zip(block, split)]
