@@ -31,6 +31,15 @@ class GridDesc(C.Structure):
     ]
 
 
+BL_CELLS_F32, BL_CELLS_F64 = 0, 1
+
+
+class DeviceCells(C.Structure):
+    """bl_device_cells: the caller's cells in device memory (bl_set_grid_device); strides and extent in elements."""
+    _fields_ = [("prim", C.c_void_p), ("dtype", C.c_int32), ("wait", C.c_int32), ("var_stride", C.c_int64), ("block_stride", C.c_int64),
+                ("n_elements", C.c_int64), ("stream", C.c_void_p)]
+
+
 BL_MAX_SWEEP = 16
 
 
@@ -172,6 +181,12 @@ def lib():
     L.bl_variant_output_path.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.bl_init.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     L.bl_set_grid.argtypes = [C.c_void_p, C.POINTER(GridDesc)]
+    L.bl_set_grid_device.argtypes = [C.c_void_p, C.POINTER(GridDesc), C.POINTER(DeviceCells)]
+    L.bl_set_grid_slice_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(GridDesc), C.POINTER(DeviceCells), C.c_double]
+    L.bl_device_cells_sizeof.restype = C.c_size_t
+    L.bl_grid_host_bytes.argtypes = [C.c_void_p]
+    L.bl_grid_host_bytes.restype = C.c_int64
+    L.bl_context_device.argtypes = [C.c_void_p]
     L.bl_image_num_quantities.argtypes = [C.c_void_p]
     L.bl_camera_frame_get.argtypes = [C.c_void_p, C.POINTER(CameraFrame)]
     L.bl_frequencies.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]

@@ -542,6 +542,62 @@ class Context:
         self._grid_keepalive = grid
         self._check(self._lib.bl_set_grid(self._ctx, C.byref(desc)))
 
+    def _device_cells(self, grid, prim, stream, dims):
+        """bl_device_cells for a torch tensor on this context's device; ValueError for anything the C call must not be handed."""
+        import torch
+        if dims not in ("vb", "bv"):
+            raise ValueError('dims must be "vb" ([variable][block][k][j][i]) or "bv" ([block][variable][k][j][i])')
+        if not isinstance(prim, torch.Tensor):
+            raise ValueError("prim must be a torch.Tensor in device memory (host arrays go through set_grid)")
+        if not prim.is_cuda:
+            raise ValueError("prim lies in host memory: host arrays go through set_grid")
+        device = self._lib.bl_context_device(self._ctx)
+        if device >= 0 and prim.device.index != device:
+            raise ValueError(f"prim lies on device {prim.device.index}, the context renders on device {device}")
+        if prim.dtype not in (torch.float32, torch.float64):
+            raise ValueError("prim must be float32 or float64")
+        if prim.dim() != 5:
+            raise ValueError("prim must have five dimensions: (variable, block) in the order `dims` says, then k, j, i")
+        desc = grid.desc()
+        n_k, n_j, n_i = desc.n_k, desc.n_j, desc.n_i
+        if tuple(prim.shape[2:]) != (n_k, n_j, n_i):
+            raise ValueError(f"prim's last three dimensions are {tuple(prim.shape[2:])}, the grid's blocks have {(n_k, n_j, n_i)} cells")
+        if tuple(prim.stride()[2:]) != (n_j * n_i, n_i, 1):
+            raise ValueError("the cells of one (variable, block) must be contiguous [k][j][i]")
+        n_var, n_blocks = (prim.shape[0], prim.shape[1]) if dims == "vb" else (prim.shape[1], prim.shape[0])
+        if n_blocks != desc.n_blocks:
+            raise ValueError(f"prim holds {n_blocks} blocks, the grid {desc.n_blocks}")
+        var_stride, block_stride = (prim.stride(0), prim.stride(1)) if dims == "vb" else (prim.stride(1), prim.stride(0))
+        if (n_var > 1 and var_stride < 1) or (n_blocks > 1 and block_stride < 1):
+            raise ValueError("prim's variable and block strides must be positive")
+        desc.n_var = n_var
+        cells = _capi.DeviceCells()
+        cells.prim = prim.data_ptr()
+        cells.dtype = _capi.BL_CELLS_F32 if prim.dtype == torch.float32 else _capi.BL_CELLS_F64
+        cells.var_stride, cells.block_stride = max(int(var_stride), 1), max(int(block_stride), 1)
+        cells.n_elements = prim.untyped_storage().nbytes() // prim.element_size() - prim.storage_offset()
+        if stream == "torch":
+            cells.wait, cells.stream = 1, torch.cuda.current_stream(prim.device).cuda_stream
+        elif stream is not None:
+            cells.wait, cells.stream = 1, int(stream)
+        return desc, cells
+
+    def set_grid_device(self, grid, prim, stream="torch", dims="vb"):
+        """set_grid with the cells in device memory (bl_set_grid_device). grid: geometry and variable indices (a mock.Grid or anything
+        with .desc(); its own prim may be None). prim: a torch tensor on this context's device, float32 or float64 (rounded to float32
+        on the device), five dimensions: (variable, block) for dims="vb" or (block, variable) for dims="bv", then (n_k, n_j, n_i)
+        contiguous; the first two strides may be anything positive. stream: "torch" - the staging waits for torch's current stream
+        on that device; a raw hipStream_t handle - for that stream; None - for nothing (the caller has synchronised). The tensor may
+        be overwritten as soon as the call returns."""
+        desc, cells = self._device_cells(grid, prim, stream, dims)
+        self._grid_keepalive = grid
+        self._check(self._lib.bl_set_grid_device(self._ctx, C.byref(desc), C.byref(cells)))
+
+    @property
+    def grid_host_bytes(self):
+        """Bytes the last set_grid* call copied from host memory (after set_grid_device: the tables only)."""
+        return int(self._lib.bl_grid_host_bytes(self._ctx))
+
     # ------------------------------------------------------------------ slow light
     def slow_light_read(self, snapshot):
         """SimulationReader::Read(snapshot) with slow_light_on: advance the window of files to the camera time of
@@ -552,6 +608,11 @@ class Context:
         """Slice n of the slow-light window (n = 0: latest file) from a caller-side reader."""
         desc = grid.desc()
         self._check(self._lib.bl_set_grid_slice(self._ctx, int(n), C.byref(desc), float(time)))
+
+    def set_grid_slice_device(self, n, grid, prim, time, stream="torch", dims="vb"):
+        """set_grid_slice with the cells in device memory: set_grid_device's arguments."""
+        desc, cells = self._device_cells(grid, prim, stream, dims)
+        self._check(self._lib.bl_set_grid_slice_device(self._ctx, int(n), C.byref(desc), C.byref(cells), float(time)))
 
     def shift_grid_slices(self, count):
         self._check(self._lib.bl_shift_grid_slices(self._ctx, int(count)))

@@ -653,67 +653,161 @@ namespace {
 // block's position in the merged array where there is one (block_origin: first target cell of every block, and the target's row
 // and plane strides; null: the blocks stay one behind the other). On the host this repack was 0.3 s per 256^3 snapshot, ten times
 // the render of a series' frame over resident geodesics.
-__global__ void __launch_bounds__(256) bl_interleave_cells_kernel(const float *planes, float *cells, unsigned long long n_cells, int nb_i, int nb_j, int nb_k,
+// The planes are wherever `src` says: the upload buffer above (block_stride == block_cells: plane q's cell c at base[q] + c, the
+// addresses this kernel always read), or the caller's own device array (bl_set_grid_device) with its block stride and element type -
+// float, or double rounded to the nearest float as a conversion on the host rounds it. count == 1 places one plane instead of
+// eight: `cells` is then a [k][j][i] float array with the same targets (the electron entropy of plasma_model = code_kappa).
+// Everything but the cell index is wave-uniform.
+struct BlCellPlanes {
+  const void *base[8];                            // first element of each plane (count of them), already at its variable
+  unsigned long long block_stride, block_cells;   // elements from a block to the next in the source; cells of a block
+  int f64, count;                                 // elements are doubles; planes: 8 or 1
+};
+__device__ __forceinline__ float bl_plane_cell(const void *base, unsigned long long at, int f64) {
+  return f64 ? static_cast<float>(static_cast<const double *>(base)[at]) : static_cast<const float *>(base)[at];
+}
+__global__ void __launch_bounds__(256) bl_interleave_cells_kernel(BlCellPlanes src, float *cells, unsigned long long n_cells, int nb_i, int nb_j, int nb_k,
                                                                   const unsigned long long *block_origin, unsigned long long row_stride,
                                                                   unsigned long long plane_stride) {
   const unsigned long long c = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_cells) return;
-  unsigned long long target = c;
-  if (block_origin != nullptr) {
-    const unsigned long long block_cells = (unsigned long long)nb_i * nb_j * nb_k;
-    const unsigned long long blk = c / block_cells, rest = c - blk * block_cells;
-    const unsigned long long k = rest / ((unsigned long long)nb_i * nb_j), j = (rest / nb_i) % nb_j, i = rest % nb_i;
-    target = block_origin[blk] + k * plane_stride + j * row_stride + i;
+  unsigned long long target = c, from = c;
+  if (block_origin != nullptr || src.block_stride != src.block_cells) {
+    const unsigned long long blk = c / src.block_cells, rest = c - blk * src.block_cells;
+    from = blk * src.block_stride + rest;
+    if (block_origin != nullptr) {
+      const unsigned long long k = rest / ((unsigned long long)nb_i * nb_j), j = (rest / nb_i) % nb_j, i = rest % nb_i;
+      target = block_origin[blk] + k * plane_stride + j * row_stride + i;
+    }
+  }
+  if (src.count == 1) {
+    cells[target] = bl_plane_cell(src.base[0], from, src.f64);
+    return;
   }
   float v[8];
+  if (src.f64) {   // (one branch around the eight loads, so that either kind is issued back to back)
+    double wide[8];
 #pragma unroll
-  for (int q = 0; q < 8; q++) v[q] = planes[(unsigned long long)q * n_cells + c];
+    for (int q = 0; q < 8; q++) wide[q] = static_cast<const double *>(src.base[q])[from];
+#pragma unroll
+    for (int q = 0; q < 8; q++) v[q] = static_cast<float>(wide[q]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 8; q++) v[q] = static_cast<const float *>(src.base[q])[from];
+  }
   float4 *out = reinterpret_cast<float4 *>(cells + target * 8);
   out[0] = make_float4(v[0], v[1], v[2], v[3]);
   out[1] = make_float4(v[4], v[5], v[6], v[7]);
 }
 
-// The planes of `g` into `d_cells` as the grid's placement says, on `stream`; returns when the cells are in place (the caller's arrays
-// are borrowed for the duration of bl_set_grid)
-void UploadCellsAs(bl_ctx *ctx, const bl_grid_desc *g, DeviceBuffer<float> &d_cells, hipStream_t stream, bool upload_origin) {
+// bl_set_grid_device's array on the device's side, before anything reads it: device memory of this context's device, and n_elements
+// elements from prim inside one allocation (CheckDeviceCells has held the strides to n_elements)
+void CheckDevicePointer(bl_ctx *ctx, const bl_device_cells &cells) {
+  const Failure refusal{BL_E_ARG, "bl_device_cells: prim must be device memory of the context's device, with n_elements elements inside one allocation; host arrays go "
+                                  "through bl_set_grid."};
+  const size_t element = cells.dtype == BL_CELLS_F64 ? sizeof(double) : sizeof(float);
+  if (cells.n_elements < 1 || static_cast<unsigned long long>(cells.n_elements) > (~0ull >> 1) / element) throw refusal;
+  hipPointerAttribute_t attributes{};
+  if (hipPointerGetAttributes(&attributes, cells.prim) != hipSuccess) {
+    (void)hipGetLastError();   // (an address the runtime does not know: not an error of this context's)
+    throw refusal;
+  }
+  if (attributes.type != hipMemoryTypeDevice || attributes.device != ctx->device) throw refusal;
+  hipDeviceptr_t first = nullptr;
+  size_t bytes = 0;
+  if (hipMemGetAddressRange(&first, &bytes, const_cast<void *>(cells.prim)) != hipSuccess) {
+    (void)hipGetLastError();
+    throw refusal;
+  }
+  const unsigned long long lo = reinterpret_cast<unsigned long long>(first), at = reinterpret_cast<unsigned long long>(cells.prim);
+  if (at < lo || at - lo > bytes || static_cast<unsigned long long>(cells.n_elements) * element > bytes - (at - lo)) throw refusal;
+}
+
+// One launch of the staging kernel on `stream`: `count` planes of `src` (8: into the cell array; 1: into a [k][j][i] plane) at the
+// grid's placement
+void LaunchCellStaging(bl_ctx *ctx, BlCellPlanes src, int count, float *target, hipStream_t stream) {
+  const CellPlacement &pl = ctx->grid.tables.placement;
+  src.block_cells = static_cast<unsigned long long>(pl.nb[0]) * pl.nb[1] * pl.nb[2];
+  src.count = count;
+  hipLaunchKernelGGL(bl_interleave_cells_kernel, dim3(static_cast<unsigned int>((pl.n_cells + 255) / 256)), dim3(256), 0, stream, src, target,
+                     static_cast<unsigned long long>(pl.n_cells), pl.nb[0], pl.nb[1], pl.nb[2], pl.has_origin ? ctx->grid.d_block_origin.ptr : nullptr, pl.row_stride,
+                     pl.plane_stride);
+  Check(hipGetLastError(), "cell interleave kernel launch");
+}
+
+// The variables `order` of the caller's device array as the staging kernel's planes
+BlCellPlanes DevicePlanes(const bl_device_cells &cells, const int *order, int count) {
+  BlCellPlanes src{};
+  const size_t element = cells.dtype == BL_CELLS_F64 ? sizeof(double) : sizeof(float);
+  for (int v = 0; v < count; v++)
+    src.base[v] = static_cast<const char *>(cells.prim) + static_cast<unsigned long long>(order[v]) * static_cast<unsigned long long>(cells.var_stride) * element;
+  src.block_stride = static_cast<unsigned long long>(cells.block_stride);
+  src.f64 = cells.dtype == BL_CELLS_F64 ? 1 : 0;
+  return src;
+}
+
+// The staging on `stream` starts behind the work queued so far on the caller's stream (bl_device_cells::wait): an event, no host wait
+void WaitForCallerCells(bl_ctx *ctx, const bl_device_cells &cells, hipStream_t stream) {
+  if (cells.wait == 0) return;
+  bl_ctx::Grid &G = ctx->grid;
+  if (G.source_event == nullptr) Check(hipEventCreateWithFlags(&G.source_event, hipEventDisableTiming), "hipEventCreate");
+  Check(hipEventRecord(G.source_event, static_cast<hipStream_t>(cells.stream)), "hipEventRecord");
+  Check(hipStreamWaitEvent(stream, G.source_event, 0), "hipStreamWaitEvent");
+}
+
+// The planes of `g` - or, with `device_cells`, of the caller's device array - into `d_cells` as the grid's placement says, on `stream`;
+// returns when the cells are in place (the caller's arrays are borrowed for the duration of bl_set_grid)
+void UploadCellsAs(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_cells, DeviceBuffer<float> &d_cells, hipStream_t stream, bool upload_origin) {
   bl_ctx::Grid &G = ctx->grid;
   const CellPlacement &pl = G.tables.placement;
   const size_t n_cells = pl.n_cells;
   d_cells.Ensure(n_cells * 8);
-  G.d_cell_planes.Ensure(n_cells * 8);
-  for (int v = 0; v < 8; v++)
-    Check(hipMemcpyAsync(G.d_cell_planes.ptr + static_cast<size_t>(v) * n_cells, g->prim + static_cast<size_t>(pl.order[v]) * n_cells, n_cells * sizeof(float),
-                         hipMemcpyHostToDevice, stream), "grid upload");
-  const unsigned long long *origin = nullptr;
-  if (pl.has_origin) {
-    if (upload_origin) {
-      G.d_block_origin.Ensure(pl.origin.size());
-      Check(hipMemcpyAsync(G.d_block_origin.ptr, pl.origin.data(), pl.origin.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream), "grid upload");
+  BlCellPlanes src{};
+  if (device_cells != nullptr) {
+    src = DevicePlanes(*device_cells, pl.order, 8);
+    WaitForCallerCells(ctx, *device_cells, stream);
+  } else {
+    G.d_cell_planes.Ensure(n_cells * 8);
+    for (int v = 0; v < 8; v++) {
+      Check(hipMemcpyAsync(G.d_cell_planes.ptr + static_cast<size_t>(v) * n_cells, g->prim + static_cast<size_t>(pl.order[v]) * n_cells, n_cells * sizeof(float),
+                           hipMemcpyHostToDevice, stream), "grid upload");
+      src.base[v] = G.d_cell_planes.ptr + static_cast<size_t>(v) * n_cells;
     }
-    origin = G.d_block_origin.ptr;
+    src.block_stride = static_cast<unsigned long long>(pl.nb[0]) * pl.nb[1] * pl.nb[2];
+    G.host_bytes += static_cast<int64_t>(n_cells * 8 * sizeof(float));
   }
-  hipLaunchKernelGGL(bl_interleave_cells_kernel, dim3(static_cast<unsigned int>((n_cells + 255) / 256)), dim3(256), 0, stream, G.d_cell_planes.ptr, d_cells.ptr,
-                     static_cast<unsigned long long>(n_cells), pl.nb[0], pl.nb[1], pl.nb[2], origin, pl.row_stride, pl.plane_stride);
-  Check(hipGetLastError(), "cell interleave kernel launch");
+  if (pl.has_origin && upload_origin) {
+    G.d_block_origin.Ensure(pl.origin.size());
+    Check(hipMemcpyAsync(G.d_block_origin.ptr, pl.origin.data(), pl.origin.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream), "grid upload");
+    G.host_bytes += static_cast<int64_t>(pl.origin.size() * sizeof(unsigned long long));
+  }
+  LaunchCellStaging(ctx, src, 8, d_cells.ptr, stream);
   Check(hipStreamSynchronize(stream), "grid upload");
 }
 
 // The one upload step: each table of ctx->grid.tables into its buffer, once; the cells (into the time slice where there is one); then
 // every pointer of BlGridDevice, from buffer base plus offset (BindGridTables)
-void UploadGrid(bl_ctx *ctx, const bl_grid_desc *g, bl_ctx::SlowSlice *slice) {
+void UploadGrid(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_cells, bl_ctx::SlowSlice *slice) {
   bl_ctx::Grid &G = ctx->grid;
   const GridTables &t = G.tables;
   DeviceBuffer<float> &d_cells = slice != nullptr ? slice->cells : G.d_cells;
   DeviceBuffer<float> &d_kappa = slice != nullptr ? slice->kappa : G.d_kappa;
-  auto put = [](auto &buffer, const auto *data, size_t count, const char *what) {
+  auto put = [&G](auto &buffer, const auto *data, size_t count, const char *what) {
     if (count == 0) return;
     buffer.Ensure(count);
     Check(hipMemcpy(buffer.ptr, data, count * sizeof(*data), hipMemcpyHostToDevice), what);
+    G.host_bytes += static_cast<int64_t>(count * sizeof(*data));
   };
   EnsureStreams(ctx);
-  UploadCellsAs(ctx, g, d_cells, ctx->stream, true);
-  if (t.code_kappa)   // (its own [k][j][i] array; block by block it lies in the caller's plane as the kernels read it)
+  UploadCellsAs(ctx, g, device_cells, d_cells, ctx->stream, true);
+  if (t.code_kappa && device_cells != nullptr) {
+    // the caller's plane where it lies, through the staging kernel: to the blocks' places in a merged array, else cell by cell
+    d_kappa.Ensure(t.placement.n_cells);
+    LaunchCellStaging(ctx, DevicePlanes(*device_cells, &g->ind_kappa, 1), 1, d_kappa.ptr, ctx->stream);
+    Check(hipStreamSynchronize(ctx->stream), "grid upload");
+  } else if (t.code_kappa) {   // (its own [k][j][i] array; block by block it lies in the caller's plane as the kernels read it)
     put(d_kappa, t.kappa.empty() ? g->prim + static_cast<size_t>(g->ind_kappa) * t.placement.n_cells : t.kappa.data(), t.placement.n_cells, "grid upload");
+  }
   put(G.d_coords, t.coords.data(), t.coords.size(), "coordinate upload");
   put(G.d_buckets, t.buckets.data(), t.buckets.size(), "bucket upload");
   put(G.d_lattice, t.lattice.data(), t.lattice.size(), "lattice upload");
@@ -730,17 +824,21 @@ int FailBetweenRenders(bl_ctx *ctx, const Failure &failure) {   // (last_error i
   return Fail(ctx, failure);
 }
 
-// bl_set_grid, and bl_set_grid_slice with the time slice the cells go to
-int SetGrid(bl_ctx *ctx, const bl_grid_desc *g, bl_ctx::SlowSlice *slice) {
+// bl_set_grid, and bl_set_grid_slice with the time slice the cells go to. The cells come from the host planes g->prim, or with
+// `device_cells` from the caller's device array (bl_set_grid_device, bl_set_grid_slice_device): everything else is one path.
+int SetGrid(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_cells, bl_ctx::SlowSlice *slice) {
   bl_ctx::Grid &G = ctx->grid;
   try {
+    G.host_bytes = 0;
+    if (device_cells != nullptr) CheckDeviceCells(*g, ctx->params.plasma_model == BL_PLASMA_CODE_KAPPA, device_cells);
     if (ctx->device == BL_DEVICE_NONE) throw Failure{BL_E_DEVICE, "Host-only context: no HIP device selected (the hot path has no CPU fallback)."};
     if (ctx->params.model_type != BL_MODEL_SIMULATION) throw Failure{BL_E_STATE, "bl_set_grid called in formula mode."};
     if (ctx->params.slow_light_on && slice == nullptr)
       throw Failure{BL_E_STATE, "slow_light_on = true: hand the time slices over with bl_set_grid_slice (or bl_slow_light_read)."};
     ValidateGridDescription(*g);
-    if (g->prim == nullptr) throw Failure{BL_E_ARG, "Bad grid description."};
+    if (device_cells == nullptr && g->prim == nullptr) throw Failure{BL_E_ARG, "Bad grid description."};
     Check(hipSetDevice(ctx->device), "hipSetDevice");
+    if (device_cells != nullptr) CheckDevicePointer(ctx, *device_cells);
     // The next snapshot of a series - the geometry in place, to the bit, and the same variables: only the cells are new. They go up on
     // a stream of their own into the second cell array while a render of this context may be running on another host thread, and the
     // arrays change places once that render has ended. (With electron entropy from the grid there is a second array to double: the
@@ -751,7 +849,7 @@ int SetGrid(bl_ctx *ctx, const bl_grid_desc *g, bl_ctx::SlowSlice *slice) {
         && std::equal(order_now, order_now + 8, G.tables.placement.order) && g->n_var == G.meta.n_var
         && g->plasma_gamma == G.meta.plasma_gamma && g->plasma_gamma_i == G.meta.plasma_gamma_i && g->plasma_gamma_e == G.meta.plasma_gamma_e) {
       if (G.stream_upload == nullptr) Check(hipStreamCreateWithFlags(&G.stream_upload, hipStreamNonBlocking), "hipStreamCreate");
-      UploadCellsAs(ctx, g, G.d_cells_back, G.stream_upload, false);
+      UploadCellsAs(ctx, g, device_cells, G.d_cells_back, G.stream_upload, false);
       std::lock_guard<std::mutex> guard(ctx->render_lock);
       std::swap(G.d_cells, G.d_cells_back);
       G.dev.cells = G.d_cells.ptr;
@@ -762,11 +860,13 @@ int SetGrid(bl_ctx *ctx, const bl_grid_desc *g, bl_ctx::SlowSlice *slice) {
     G.have = false;   // a refused or failed grid leaves no grid behind (the previous one may be half overwritten)
     G.swappable = false;
     G.tables.geometry = 0;
-    GridTables tables = BuildGridTables(ctx->params, *g);
+    bl_grid_desc described = *g;
+    if (device_cells != nullptr) described.prim = nullptr;   // (no host planes: the electron entropy plane is placed on the device)
+    GridTables tables = BuildGridTables(ctx->params, described);
     const unsigned long long geometry = slice == nullptr ? tables.geometry : 0;   // (slow light locates per snapshot: no located samples are kept)
     tables.geometry = 0;
     G.tables = std::move(tables);
-    UploadGrid(ctx, g, slice);
+    UploadGrid(ctx, g, device_cells, slice);
     G.tables.kappa = std::vector<float>();   // (as large as a cell plane, and on the device now)
     G.tables.geometry = geometry;
     G.meta = *g;
@@ -777,25 +877,58 @@ int SetGrid(bl_ctx *ctx, const bl_grid_desc *g, bl_ctx::SlowSlice *slice) {
   }
   return BL_OK;
 }
+
+int RefuseNoCells(bl_ctx *ctx, const bl_grid_desc *g) {   // (SetGrid reads a null description as "host planes")
+  try {
+    CheckDeviceCells(*g, false, nullptr);
+  } catch (const Failure &failure) {
+    return FailBetweenRenders(ctx, failure);
+  }
+  return BL_E_ARG;
+}
 }  // namespace
 
 int bl_set_grid(bl_ctx *ctx, const bl_grid_desc *g) {
   if (ctx == nullptr || g == nullptr) return BL_E_ARG;
-  return SetGrid(ctx, g, nullptr);
+  return SetGrid(ctx, g, nullptr, nullptr);
 }
 
-int bl_set_grid_slice(bl_ctx *ctx, int slice, const bl_grid_desc *g, double time) {
+int bl_set_grid_device(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *cells) {
   if (ctx == nullptr || g == nullptr) return BL_E_ARG;
+  if (cells == nullptr) return RefuseNoCells(ctx, g);
+  return SetGrid(ctx, g, cells, nullptr);
+}
+
+size_t bl_device_cells_sizeof(void) { return sizeof(bl_device_cells); }
+
+int64_t bl_grid_host_bytes(const bl_ctx *ctx) { return ctx != nullptr ? ctx->grid.host_bytes : 0; }
+
+int bl_context_device(const bl_ctx *ctx) { return ctx != nullptr ? ctx->device : BL_DEVICE_NONE; }
+
+namespace {
+int SetGridSlice(bl_ctx *ctx, int slice, const bl_grid_desc *g, const bl_device_cells *device_cells, double time) {
   const bl_params &p = ctx->params;
   if (p.model_type != BL_MODEL_SIMULATION || !p.slow_light_on) return FailBetweenRenders(ctx, Failure{BL_E_STATE, "bl_set_grid_slice needs slow_light_on = true."});
   if (slice < 0 || slice >= p.slow_chunk_size) return FailBetweenRenders(ctx, Failure{BL_E_ARG, "Time slice index outside slow_chunk_size."});
   ctx->slow_slices.resize(p.slow_chunk_size);
   bl_ctx::SlowSlice &target = ctx->slow_slices[slice];
-  const int rc = SetGrid(ctx, g, &target);
+  const int rc = SetGrid(ctx, g, device_cells, &target);
   if (rc != BL_OK) return rc;
   target.time = time;
   target.set = true;
   return BL_OK;
+}
+}  // namespace
+
+int bl_set_grid_slice(bl_ctx *ctx, int slice, const bl_grid_desc *g, double time) {
+  if (ctx == nullptr || g == nullptr) return BL_E_ARG;
+  return SetGridSlice(ctx, slice, g, nullptr, time);
+}
+
+int bl_set_grid_slice_device(bl_ctx *ctx, int slice, const bl_grid_desc *g, const bl_device_cells *cells, double time) {
+  if (ctx == nullptr || g == nullptr) return BL_E_ARG;
+  if (cells == nullptr) return RefuseNoCells(ctx, g);
+  return SetGridSlice(ctx, slice, g, cells, time);
 }
 
 int bl_shift_grid_slices(bl_ctx *ctx, int count) {
@@ -1150,6 +1283,7 @@ void bl_free(bl_ctx *ctx) {
   if (ctx->stream != nullptr) (void)hipStreamDestroy(ctx->stream);
   if (ctx->stream_geo != nullptr) (void)hipStreamDestroy(ctx->stream_geo);
   if (ctx->grid.stream_upload != nullptr) (void)hipStreamDestroy(ctx->grid.stream_upload);
+  if (ctx->grid.source_event != nullptr) (void)hipEventDestroy(ctx->grid.source_event);
   // (stream_few / stream_most are the process's, borrowed: EnsureSplitStreams)
   delete ctx;
 }

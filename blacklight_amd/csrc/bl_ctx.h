@@ -220,6 +220,8 @@ struct bl_ctx {
     DeviceBuffer<int> d_block_table;                  // inter-block interpolation: levels, locations, hash blocks
     DeviceBuffer<unsigned long long> d_block_keys;    // ... and hash keys
     hipStream_t stream_upload = nullptr;
+    hipEvent_t source_event = nullptr; // bl_set_grid_device with wait: recorded on the caller's stream, awaited by the staging stream
+    int64_t host_bytes = 0;            // what the last bl_set_grid* call copied from host memory (bl_grid_host_bytes)
   } grid;
   bool sample_checkpoint_saved = false;   // checkpoint_sample_save: written with the first image only (radiation_integrator.cpp:699-704)
 

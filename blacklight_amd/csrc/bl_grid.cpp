@@ -175,9 +175,9 @@ bool BuildMergedTables(const bl_params &p, const bl_grid_desc &g, GridTables *t)
       pl.origin[blk] = (static_cast<unsigned long long>(block_pos[2][blk]) * nb_cells[2] * n_j + static_cast<unsigned long long>(block_pos[1][blk]) * nb_cells[1]) * n_i
           + static_cast<unsigned long long>(block_pos[0][blk]) * nb_cells[0];
   }
-  if (t->code_kappa && n_b > 1) {
+  if (t->code_kappa && n_b > 1 && g.prim != nullptr) {
     // the ninth value of a cell (simulation_reader.cpp:1164-1172) in its own [k][j][i] array: only the
-    // extended coefficient kernel reads it
+    // extended coefficient kernel reads it (cells in device memory: the staging kernel places the plane at pl.origin)
     t->kappa.resize(n_cells);
     for (int blk = 0; blk < n_b; blk++) {
       const int pi = block_pos[0][blk], pj = block_pos[1][blk], pk = block_pos[2][blk];
@@ -555,6 +555,27 @@ bool GridVariableOrder(const bl_grid_desc &g, bool code_kappa, int order[8]) {
     in_range = in_range && given[v] >= 0 && given[v] < g.n_var;
   }
   return in_range;
+}
+
+void CheckDeviceCells(const bl_grid_desc &g, bool code_kappa, const bl_device_cells *cells) {
+  if (cells == nullptr) throw Failure{BL_E_ARG, "bl_device_cells: the description is NULL."};
+  if (cells->prim == nullptr) throw Failure{BL_E_ARG, "bl_device_cells: prim is NULL."};
+  if (cells->dtype != BL_CELLS_F32 && cells->dtype != BL_CELLS_F64) throw Failure{BL_E_ARG, "bl_device_cells: dtype must be BL_CELLS_F32 or BL_CELLS_F64."};
+  if (reinterpret_cast<uintptr_t>(cells->prim) % (cells->dtype == BL_CELLS_F64 ? sizeof(double) : sizeof(float)) != 0)
+    throw Failure{BL_E_ARG, "bl_device_cells: prim is not aligned to its element type."};
+  if (cells->var_stride < 1) throw Failure{BL_E_ARG, "bl_device_cells: var_stride must be at least 1."};
+  if (cells->block_stride < 1) throw Failure{BL_E_ARG, "bl_device_cells: block_stride must be at least 1."};
+  int order[8];
+  if (g.n_blocks < 1 || g.n_i < 1 || g.n_j < 1 || g.n_k < 1 || !GridVariableOrder(g, code_kappa, order)) return;   // (refused further on)
+  int last_var = code_kappa ? g.ind_kappa : 0;
+  for (int v = 0; v < 8; v++) last_var = std::max(last_var, order[v]);
+  // last_var * var_stride + (n_blocks - 1) * block_stride + n_i * n_j * n_k - 1, the index of the furthest element read
+  int64_t reach = 0, term = 0;
+  bool overflow = __builtin_mul_overflow(static_cast<int64_t>(g.n_i), static_cast<int64_t>(g.n_j), &reach) || __builtin_mul_overflow(reach, static_cast<int64_t>(g.n_k), &reach);
+  reach -= 1;
+  overflow = overflow || __builtin_mul_overflow(static_cast<int64_t>(g.n_blocks) - 1, cells->block_stride, &term) || __builtin_add_overflow(reach, term, &reach);
+  overflow = overflow || __builtin_mul_overflow(static_cast<int64_t>(last_var), cells->var_stride, &term) || __builtin_add_overflow(reach, term, &reach);
+  if (overflow || reach >= cells->n_elements) throw Failure{BL_E_ARG, "bl_device_cells: n_elements is smaller than what the strides and the grid's extents reach."};
 }
 
 void ValidateGridDescription(const bl_grid_desc &g) {

@@ -62,7 +62,8 @@ struct GridTables {
 };
 
 // Validates `g` and builds the tables: the merged tiling, else (or with simulation_block_interp) the block lattice. Throws Failure
-// with the refusal's code and text. Reads g.prim for the repacked kappa plane only.
+// with the refusal's code and text. Reads g.prim for the repacked kappa plane only; with g.prim null (cells in device memory) kappa
+// stays empty and the staging kernel places that plane.
 GridTables BuildGridTables(const bl_params &p, const bl_grid_desc &g);
 // ... its first step, which bl_set_grid takes before it reads the arrays: extents of at least 1 block of 2 x 2 x 2 cells, the six
 // coordinate arrays there
@@ -83,6 +84,12 @@ BlGridDevice BindGridTables(const GridTables &t, const GridBases &base);
 unsigned long long GridGeometryHash(const bl_grid_desc &g);
 // The eight variables in the kernels' order; false: an index (ind_kappa too, where `code_kappa`) lies outside [0, n_var)
 bool GridVariableOrder(const bl_grid_desc &g, bool code_kappa, int order[8]);
+// bl_set_grid_device's description of the caller's device array, checked as far as the host can (Failure with BL_E_ARG and a text
+// each): `cells` and its prim there, prim aligned to its element, dtype one of the two, both strides at least 1, and the furthest
+// element the staging kernel reads - over the eight variables of GridVariableOrder, ind_kappa too where `code_kappa`, every block,
+// a block's cells - below n_elements, in 64-bit arithmetic that notices its overflows. A description whose extents or indices are
+// themselves out of range is left to ValidateGridDescription and GridVariableOrder, which refuse it before anything is launched.
+void CheckDeviceCells(const bl_grid_desc &g, bool code_kappa, const bl_device_cells *cells);
 // `g` carries the geometry `t` was built from, bit for bit (hash first, then the arrays themselves)
 bool SameGeometry(const GridTables &t, const bl_grid_desc &g);
 

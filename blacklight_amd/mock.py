@@ -61,9 +61,12 @@ class Grid:
     levels: np.ndarray = None
     locations: np.ndarray = None
     n_3_root: int = 0
+    n_var: int = 0        # prim = None (the cells lie in device memory, Context.set_grid_device): variables per cell there; 0: 8, or ind_kappa + 1
 
     @property
     def shape(self):
+        if self.prim is None:
+            return (self.x3v.shape[1], self.x2v.shape[1], self.x1v.shape[1])
         return self.prim.shape[2:]
 
     def save_raw(self, path):
@@ -85,10 +88,16 @@ class Grid:
     def desc(self):
         """bl_grid_desc borrowing this object's arrays (keep `self` alive while it is used)."""
         d = _capi.GridDesc()
-        n_var, n_b, n_k, n_j, n_i = self.prim.shape
+        if self.prim is None:   # geometry and variable indices only (d.prim stays NULL)
+            (n_b, n_i), n_j, n_k = self.x1v.shape, self.x2v.shape[1], self.x3v.shape[1]
+            n_var = int(self.n_var) or max(8, self.ind_kappa + 1)
+        else:
+            n_var, n_b, n_k, n_j, n_i = self.prim.shape
         d.n_blocks, d.n_i, d.n_j, d.n_k, d.n_var = n_b, n_i, n_j, n_k, n_var
         for name in ("prim", "x1f", "x2f", "x3f", "x1v", "x2v", "x3v"):
             arr = getattr(self, name)
+            if arr is None and name == "prim":
+                continue
             assert arr.flags["C_CONTIGUOUS"]
             setattr(d, name, arr.ctypes.data_as(C.c_void_p))
         # VerifyVariablesAthena (simulation_reader.cpp:1141-1216) for the order written above

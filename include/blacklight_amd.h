@@ -453,6 +453,40 @@ BL_API int bl_device_count(void);
  * cell array, and the call returns once that render has ended and the arrays have changed places - the new cells are what the NEXT
  * bl_render reads. One bl_set_grid at a time per context; any other change of the grid waits for the render and excludes it. */
 BL_API int bl_set_grid(bl_ctx *ctx, const bl_grid_desc *g);
+/* The same call for cells that already lie in device memory (a GRMHD code in the same process, a torch pipeline, a series kept
+ * resident): the staging kernel reads the caller's array where it lies - no copy through the host, none into a plane buffer.
+ * `g` is what bl_set_grid takes with g->prim ignored (NULL is fine); the coordinate arrays, the MeshBlock table and sks_map stay host
+ * pointers. The cells of one (variable, block) are contiguous [n_k][n_j][n_i]; variable v of block b starts at
+ * prim + v * var_stride + b * block_stride (elements):
+ *   [var][block][k][j][i] (the reference's)      var_stride = n_blocks * block_cells, block_stride = block_cells
+ *   [block][var][k][j][i] (AthenaK-style codes)  var_stride = block_cells,            block_stride = n_var * block_cells
+ * BL_CELLS_F64 cells are rounded to the nearest float (ties to even) on the device - what writing them to a float32 file and reading
+ * it back does - so everything downstream sees the bytes of bl_set_grid with the array converted to float32.
+ * Ordering: with wait != 0 the staging waits, on the device, for the work queued so far on `stream` (an event, no host wait); with
+ * wait == 0 the caller has synchronised. The call returns once the cells are in place: the array may be overwritten then. Beside a
+ * render, slow-light slices, refusals: as bl_set_grid / bl_set_grid_slice.
+ * Checked before anything is launched (BL_E_ARG, a text each): cells / prim NULL, prim not aligned to its element, dtype, a stride
+ * below 1, n_elements below what the strides reach (the eight variables read, ind_kappa with plasma_model = code_kappa); then, on the
+ * device, that prim is device memory of the context's device and that n_elements elements from it lie within one allocation. Host
+ * arrays, pinned or not, go through bl_set_grid. */
+#define BL_CELLS_F32 0
+#define BL_CELLS_F64 1
+typedef struct bl_device_cells {
+  const void *prim;       /* device memory of the context's device                                          */
+  int32_t dtype;          /* BL_CELLS_F32 | BL_CELLS_F64                                                     */
+  int32_t wait;           /* != 0: the staging first waits, on the device, for the work queued on `stream`  */
+  int64_t var_stride;     /* elements between variable v and v + 1 of one block                              */
+  int64_t block_stride;   /* elements between block b and b + 1 of one variable                              */
+  int64_t n_elements;     /* extent of the caller's array from `prim`, in elements                           */
+  void *stream;           /* hipStream_t (NULL: the NULL stream); read only with wait != 0                   */
+} bl_device_cells;
+BL_API int bl_set_grid_device(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *cells);
+BL_API size_t bl_device_cells_sizeof(void);
+/* Bytes the last bl_set_grid* call of this context copied from host memory: variable planes, tables, block origins. After a
+ * device call: the tables only. */
+BL_API int64_t bl_grid_host_bytes(const bl_ctx *ctx);
+/* The HIP device of the context (what bl_init selected; BL_DEVICE_NONE for a host-only context): where bl_device_cells::prim must lie. */
+BL_API int bl_context_device(const bl_ctx *ctx);
 /* ---- slow light (slow_light_on = true): the reader keeps a window of slow_chunk_size files, latest first
  * (simulation_reader.cpp:211-303), all on the geometry of the first; every sample reads the slice(s) around
  * its own coordinate time (simulation_sampling.cpp:296-349, :736-786, :840-912).
@@ -467,6 +501,7 @@ BL_API int bl_set_grid(bl_ctx *ctx, const bl_grid_desc *g);
  *   warnings / errors (simulation_sampling.cpp:577-617) follow from it. */
 BL_API int bl_slow_light_read(bl_ctx *ctx, int snapshot);
 BL_API int bl_set_grid_slice(bl_ctx *ctx, int slice, const bl_grid_desc *g, double time);
+BL_API int bl_set_grid_slice_device(bl_ctx *ctx, int slice, const bl_grid_desc *g, const bl_device_cells *cells, double time);   /* (cells in device memory: bl_set_grid_device) */
 BL_API int bl_shift_grid_slices(bl_ctx *ctx, int count);
 BL_API int bl_set_snapshot(bl_ctx *ctx, int snapshot);
 /* Number of image rows n_q and their offsets (radiation_integrator.cpp:436-520). */
