@@ -99,7 +99,7 @@ class RenderDesc(C.Structure):
 # BL_SWITCH_* of include/blacklight_amd.h: measurement switches (bl_stats.switches, bl_debug_set_switches)
 SWITCHES = {"TENSOR_TRANSPORT": 1 << 0, "SPLIT_RECORDS": 1 << 1, "RECORD_EVERY_STEP": 1 << 2,
             "GENERAL_LOCATE": 1 << 4, "LANE_TRANSFER": 1 << 5, "NO_FUSED_LOCATE": 1 << 6, "SAMPLE_RECORDS": 1 << 8, "QUAD_EVERY_RAY": 1 << 11,
-            "FLAT_ORDER": 1 << 12, "GLOBAL_ANGLES": 1 << 13, "GENERAL_CUTS": 1 << 14}
+            "FLAT_ORDER": 1 << 12, "GLOBAL_ANGLES": 1 << 13, "GENERAL_CUTS": 1 << 14, "NO_MIRROR_PAIRS": 1 << 15}
 
 BL_MAX_LEVELS = 16
 
@@ -124,7 +124,7 @@ class Stats(C.Structure):
         ("launches_geodesic", C.c_int32), ("launches_shade", C.c_int32),
         ("launches_transfer", C.c_int32),
         ("ms_locate", C.c_float), ("ms_wall", C.c_float), ("launches_locate", C.c_int32),
-        ("arithmetic", C.c_int32), ("n_deferred", C.c_int64), ("n_undefined", C.c_int64),
+        ("arithmetic", C.c_int32), ("mirror_pairs", C.c_int32), ("n_deferred", C.c_int64), ("n_undefined", C.c_int64),
         ("switches", C.c_uint32), ("fused_variant", C.c_int32), ("n_parked", C.c_int64),
         ("composed_maps", C.c_int32), ("tail_policy", C.c_int32), ("geodesics_reused", C.c_int32), ("sampling_reused", C.c_int32),
         ("xcd_order", C.c_int32), ("local_angles", C.c_int32), ("n_cameras", C.c_int32),

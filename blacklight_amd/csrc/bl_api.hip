@@ -583,7 +583,8 @@ int bl_init(const bl_params *p, int device, bl_ctx **out) {
         {"BLACKLIGHT_AMD_GENERAL_LOCATE", BL_SWITCH_GENERAL_LOCATE}, {"BLACKLIGHT_AMD_LANE_TRANSFER", BL_SWITCH_LANE_TRANSFER},
         {"BLACKLIGHT_AMD_NO_FUSED_LOCATE", BL_SWITCH_NO_FUSED_LOCATE}, {"BLACKLIGHT_AMD_SAMPLE_RECORDS", BL_SWITCH_SAMPLE_RECORDS},
         {"BLACKLIGHT_AMD_QUAD_EVERY_RAY", BL_SWITCH_QUAD_EVERY_RAY}, {"BLACKLIGHT_AMD_FLAT_ORDER", BL_SWITCH_FLAT_ORDER},
-        {"BLACKLIGHT_AMD_GLOBAL_ANGLES", BL_SWITCH_GLOBAL_ANGLES}, {"BLACKLIGHT_AMD_GENERAL_CUTS", BL_SWITCH_GENERAL_CUTS}};
+        {"BLACKLIGHT_AMD_GLOBAL_ANGLES", BL_SWITCH_GLOBAL_ANGLES}, {"BLACKLIGHT_AMD_GENERAL_CUTS", BL_SWITCH_GENERAL_CUTS},
+        {"BLACKLIGHT_AMD_NO_MIRROR_PAIRS", BL_SWITCH_NO_MIRROR_PAIRS}};
     for (const auto &sw : kSwitches)
       if (std::getenv(sw.name) != nullptr) ctx->switches |= sw.bit;
     ctx->debug_counters = std::getenv("BLACKLIGHT_AMD_DEBUG_COUNTERS") != nullptr;
@@ -1274,7 +1275,7 @@ void bl_free(bl_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   ctx->grid.d_cells.Free(); ctx->grid.d_kappa.Free(); ctx->grid.d_coords.Free(); ctx->grid.d_buckets.Free(); ctx->slot[0].Free(); ctx->slot[1].Free();
   ctx->d_freq.Free(); ctx->d_pixel_map.Free();
-  ctx->d_block_locs.Free(); ctx->d_tile_order.Free(); ctx->d_cameras.Free(); ctx->d_render_params.Free(); ctx->d_render.Free(); ctx->d_shade_cold.Free(); ctx->d_pol_variant_table.Free(); ctx->d_pol_variant_args.Free(); ctx->d_image.Free(); ctx->d_camera_pos.Free(); ctx->d_camera_dir.Free();
+  ctx->d_block_locs.Free(); ctx->d_tile_order.Free(); ctx->d_mirror_out.Free(); ctx->d_cameras.Free(); ctx->d_render_params.Free(); ctx->d_render.Free(); ctx->d_shade_cold.Free(); ctx->d_pol_variant_table.Free(); ctx->d_pol_variant_args.Free(); ctx->d_image.Free(); ctx->d_camera_pos.Free(); ctx->d_camera_dir.Free();
   ctx->d_out_sample_num.Free(); ctx->d_out_flags.Free();
   for (auto &e : ctx->events)
     if (e != nullptr) (void)hipEventDestroy(e);

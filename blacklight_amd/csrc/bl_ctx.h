@@ -298,6 +298,7 @@ struct bl_ctx {
   struct ResidentGeodesics {
     bool valid = false, parked = false;
     bool super_tiles = false;                 // the tile order the records were traced in (bl_render.hip: BuildTraceArgs)
+    bool mirror = false;                      // ... of the left half only: mirror pairs, every later frame shades them for both halves
     bool located_valid = false;               // ... and d_located / d_located_tag / d_anchors hold the samples as located on `geometry`
     std::vector<unsigned char> key;           // everything the records depend on (bl_render.hip: GeodesicKey)
     std::vector<unsigned char> located_key;   // ... and the located samples besides (LocatedKey)
@@ -349,6 +350,13 @@ struct bl_ctx {
   DeviceBuffer<int> d_pixel_map, d_block_locs, d_tile_order;
   int tile_order_res = 0;
   bool tile_order_xcd = false;   // d_tile_order in super-tiles of 8 x 8 tiles (the trace order per XCD, bl_render.hip) or tile by tile
+  // Mirror pairs (bl_render.hip: MirrorPairsApply). d_tile_order lists the left half's tiles only (tile_order_half), d_mirror_out holds, per
+  // traced slot of that order, the output index of its mirror pixel. The camera check's verdict is kept with everything it depends on -
+  // spacetime, camera frame, camera parameters, resolution (mirror_key): any change of those has it made again.
+  bool tile_order_half = false;
+  DeviceBuffer<long long> d_mirror_out;
+  std::vector<unsigned char> mirror_key;
+  bool mirror_ok = false;
   DeviceBuffer<BlShadeCold> d_shade_cold;
   DeviceBuffer<BlPolVariant> d_pol_variant_table;   // polarized variants in one pass: every variant's folded constants (BuildShadeArgs)
   std::vector<unsigned char> pol_variant_host;   // the bytes d_pol_variant_table holds

@@ -488,6 +488,13 @@ struct BlShadeArgs {
   unsigned long long *xcd_state;
   const unsigned int *xcd_lists;
   long long xcd_list_capacity;
+  // Mirror pairs (bl_render.hip: MirrorPairsApply; 0: off): only the left half of a frame whose camera lies in the mirror plane y = 0 of
+  // a zero-spin spacetime was traced, and bl_shade_fused2_kernel, bl_shade_exact2_kernel and bl_shade_kernel<..., kRedo> walk the record
+  // indices [0, 2 n) of the n = BL_CNT_RECORDS records (a multiple of 64): index i >= n is record i - n as the mirror pixel's ray - the sign
+  // bits of y and k_y flipped, everything else the traced ray's - with its rows row_add (the rows the traced half may fill) beyond the
+  // traced ray's in `composed` / `transfer`. What a kernel writes by record index (the per-sample records behind BL_COMPOSED_EXPANDED,
+  // redo_list) it writes by the index walked.
+  unsigned int row_add;
   const double2 *ray_constants;   // [chunk_rays]: (k_t, momentum factor) of BlTraceArgs::ray_constants
   const long long *ray_offset;   // [chunk_rays]: sample n of ray q has row ray_offset[q] + n in transfer, aux, pol_samples, freq_inputs, ...
   const double *frequencies;  // device [n_nu]
@@ -579,6 +586,12 @@ struct BlTransferArgs {
   int lane_transfer;          // measurement switch (bl_stats.switches): one lane per ray where four lanes per ray apply
   const double2 *composed;    // composed transfer maps (BlShadeArgs::composed): [ray_offset + segment], ray_rows[ray] of them per ray; `transfer` by record
   const int *ray_rows;
+  // Mirror pairs (BlShadeArgs::row_add; mirror_rays = 0: off): bl_transfer_kernel, bl_transfer_quad_kernel and bl_transfer_composed_kernel
+  // run over 2 mirror_rays slots; slot s >= mirror_rays is the mirror pixel of traced ray s - mirror_rays: that ray's per-ray values, its
+  // rows row_add further on, its outputs at mirror_out_index[s - mirror_rays] (bl_mirror_slot)
+  int mirror_rays;
+  long long row_add;
+  const long long *mirror_out_index;
   const BlFreqInputs *freq_inputs;            // bl_transfer_freq_kernel
   int n_models;                               // ... > 0: electron models in one pass, one lane per (ray, model, frequency), image row m n_nu + l
   double model_k1[BL_TRANSFER_MAX_MODELS], model_k2[BL_TRANSFER_MAX_MODELS], model_k3;   // ... R_high g1, R_low g1 of model m; n_e / n_i g2
@@ -609,6 +622,13 @@ __device__ __forceinline__ double bl_ray_factor(const double2 *rays, size_t ray)
 __device__ __forceinline__ int bl_rays_done(const unsigned long long *counters, int chunk_rays) {
   const unsigned long long taken = counters[BL_CNT_NEXT_RAY];
   return taken < (unsigned long long)chunk_rays ? (int)taken : chunk_rays;
+}
+// Mirror pairs (BlTransferArgs::mirror_rays): the traced ray a transfer slot stands for, whether as its mirror pixel, and then where
+// that pixel's rows start (relative to the traced ray's) and where its outputs go
+__device__ __forceinline__ bool bl_mirror_slot(const BlTransferArgs &P, int *slot) {
+  const bool mirror = P.mirror_rays > 0 && *slot >= P.mirror_rays;
+  if (mirror) *slot -= P.mirror_rays;
+  return mirror;
 }
 #endif
 

@@ -94,6 +94,8 @@ struct RenderJob {
   bool kept = false;          // integrating in the kept layout: every chunk's records side by side in a store (bl_ctx::ResidentGeodesics)
   bool kept_spilled = false;  // ... the store ran out before the last ray: the remaining chunks overwrite it from its start, nothing is kept
   bool xcd_order = false;     // trace order per XCD (BlTraceArgs::xcd_state, XcdOrderApplies)
+  bool mirror = false;        // mirror pairs (MirrorPairsApply): the left half of the frame is traced, both halves are shaded from its records
+  long long n_traced = 0;     // rays the geodesic stage traces and the per-ray arrays hold: n_rays, or half of them with mirror pairs
   bool local_angles = false;  // fused2 over one block: theta and phi relative to the centre of the guessed cell (BlShadeArgs::local_angles)
   bool super_tiles = false;   // ... the tile order in super-tiles (BuildTraceArgs)
   bool raster = false;        // large host outputs (many image rows): rays in pixel order, so that a chunk is a range of columns of
@@ -168,7 +170,7 @@ struct RenderJob {
   // totals
   int n_chunks = 0;
   float ms_geo = 0.0f, ms_locate = 0.0f, ms_shade = 0.0f, ms_transfer = 0.0f;
-  unsigned long long total_samples = 0, total_flagged = 0, total_records = 0, total_gathers = 0, total_redo = 0, total_undefined = 0, total_parked = 0, max_num = 0;
+  unsigned long long total_samples = 0, total_flagged = 0, total_records = 0, total_emitted = 0, total_gathers = 0, total_redo = 0, total_undefined = 0, total_parked = 0, max_num = 0;
   unsigned long long debug_counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // (BLACKLIGHT_AMD_DEBUG_COUNTERS: the tables and launch of the locate kernel - the first chunk's and the last one's, which differ
   // when chunks overlap - of the coefficient kernel and of the exact second pass)
@@ -609,6 +611,7 @@ void PlanJob(RenderJob &job) {
   // (one variant's rows decide: the trace order is part of the resident geodesics' key, which the models and units must not change)
   job.raster = !d->outputs_on_device && d->level == 0 && d->pixel_map == nullptr && job.n_q_model >= 8
       && static_cast<uint64_t>(job.n_q_model) * static_cast<uint64_t>(job.n_rays) * sizeof(double) >= (256ull << 20) && job.no_checkpoint;
+  job.n_traced = job.n_rays;   // (mirror pairs: halved once they are decided, bl_render)
 }
 
 // ---- geodesics once per series (bl_set_geodesic_reuse; reference: blacklight.cpp:93-94 against its run loop :178-250, and the
@@ -714,8 +717,11 @@ void DecideReuse(RenderJob &job) {
   bl_ctx::ResidentGeodesics &res = ctx->resident;
   job.keepable = ctx->geodesic_reuse != 0 && job.d->level == 0 && !job.geo_load;
   if (job.keepable) BuildReuseKeys(job);
-  job.reuse = job.keepable && job.allow_reuse && res.valid && res.key == job.geo_key;
+  // (resident records of mirror pairs serve a render that could be paired itself - MirrorPairsApply has said so in job.mirror; unpaired
+  // records serve any render. Either way the render goes the way the records were traced.)
+  job.reuse = job.keepable && job.allow_reuse && res.valid && res.key == job.geo_key && (!res.mirror || job.mirror);
   if (job.reuse) {
+    job.mirror = res.mirror;
     if (res.parked) SwapResidentBuffers(ctx);
     job.reuse_chunks = !res.chunks.empty();
     // (kept layout: the located samples lived in one chunk's arrays and are gone)
@@ -729,6 +735,8 @@ void DecideReuse(RenderJob &job) {
   // The render after one of this camera that took several chunks and kept nothing: integrated in the kept layout (PlanScratch decides
   // whether it fits). Not with two scratch sets, nor where a checkpoint is written from the chunks' records.
   job.kept = job.keepable && !job.reuse && res.pending && res.pending_key == job.geo_key && ctx->overlap_chunks == 0 && !job.geo_save && !job.sample_save;
+  if (job.kept) job.mirror = false;   // (more than one chunk: every ray is traced)
+  job.n_traced = job.mirror ? job.n_rays / 2 : job.n_rays;
 }
 
 // What the shading stage adds to a chunk's counters: cleared, so that a render over the kept records counts it again
@@ -752,6 +760,7 @@ void KeepResident(RenderJob &job) {
   if (job.keepable && !job.reuse) {
     res.valid = false;
     res.super_tiles = job.super_tiles;
+    res.mirror = job.mirror;
     if (job.kept && !job.kept_spilled) {
       res.valid = true;
       res.parked = false;
@@ -838,8 +847,11 @@ void ForEachRecordArray(const RenderJob &job, Slot &sl, Visitor &&visit) {
   const size_t n_nu = static_cast<size_t>(job.n_nu);
   if (use.located) visit(sl.d_located, 1, true), visit(sl.d_located_tag, 1, true);
   if (use.freq_inputs) visit(sl.d_freq_inputs, 1, true);
-  if (use.transfer) visit(sl.d_transfer, n_nu, true);
-  if (use.composed) visit(sl.d_composed, 1, true);
+  // (mirror pairs: the two arrays the shading stage fills hold the traced half's rows and, row_add = the record capacity further on,
+  // the mirror half's)
+  const size_t halves = job.mirror ? 2 : 1;
+  if (use.transfer) visit(sl.d_transfer, n_nu * halves, true);
+  if (use.composed) visit(sl.d_composed, halves, true);
   if (use.tau_inc) visit(sl.d_tau_inc, n_nu, true);
   if (use.aux) visit(sl.d_aux, 1, true);
   if (use.slow_frac) visit(sl.d_slow_frac, 1, true);
@@ -1022,6 +1034,101 @@ KernelPlan::Geodesic PlanGeodesicKernel(const RenderJob &job) {
   return g;
 }
 
+// Mirror pairs. With zero spin the Kerr-Schild geometry is symmetric under y -> -y, and a camera in that plane without roll or azimuthal
+// velocity starts pixel (row, res - 1 - col) as the mirror image of pixel (row, col). The zero-spin Dormand-Prince stepper is equivariant
+// under the reflection bit for bit (every quantity has a parity in y, every sum adds terms of one parity in a fixed order,
+// correctly rounded operations commute with negation, the controller sees absolute values), so the right half's records would be the
+// left half's with the sign bits of y and k_y flipped: only the left half is traced, and the shading stage walks its records twice
+// (BlShadeArgs::row_add, BlTransferArgs::mirror_rays). That the start states are mirror images is not inferred from the parameters:
+// bl_ray_init_kernel's own results are compared on the host, once per camera (the verdict is kept in the context with its inputs).
+void BuildCameraArgs(const bl_ctx *ctx, const bl_render_desc *d, int max_steps, BlTraceArgs &ta);
+bool MirrorCameraPasses(RenderJob &job) {
+  bl_ctx *ctx = job.ctx;
+  const bl_params &p = ctx->params;
+  std::vector<unsigned char> inputs;
+  KeyWriter key{&inputs};
+  key.Put(ctx->st.bh_m); key.Put(ctx->st.bh_a); key.Put(ctx->st.ray_flat);
+  const bl_camera_frame &f = ctx->frame;
+  for (const double (*v)[4] : {&f.cam_x, &f.u_con, &f.u_cov, &f.norm_con, &f.norm_con_c, &f.hor_con_c, &f.vert_con_c})
+    for (int mu = 0; mu < 4; mu++) key.Put((*v)[mu]);
+  key.Put(p.camera_type); key.Put(p.camera_width); key.Put(p.camera_r); key.Put(p.camera_resolution); key.Put(p.image_normalization);
+  key.Put(p.ray_integrator);
+  if (ctx->mirror_key == inputs) return ctx->mirror_ok;
+  const size_t n = static_cast<size_t>(job.n_rays), res = static_cast<size_t>(p.camera_resolution);
+  DeviceBuffer<double2> d_constants;
+  DeviceBuffer<long long> d_out_index;
+  DeviceBuffer<double> d_start;
+  d_constants.Ensure(n);
+  d_out_index.Ensure(n);
+  d_start.Ensure(n * BL_RAY_START_FIELDS);
+  BlTraceArgs ta{};   // (no tile order, pixel map, block list, camera rows or camera table: slot = pixel of the one camera)
+  BuildCameraArgs(ctx, job.d, job.max_steps, ta);
+  ta.chunk_begin = 0;
+  ta.chunk_rays = static_cast<int>(n);
+  ta.ray_constants = d_constants.ptr;
+  ta.ray_out_index = d_out_index.ptr;
+  ta.ray_start = d_start.ptr;
+  ta.ray_start_stride = static_cast<long long>(n);
+  Check(bl_launch_ray_init(&ta, PlanGeodesicKernel(job), ctx->stream), "ray start kernel launch");
+  Check(hipStreamSynchronize(ctx->stream), "kernel execution");
+  std::vector<uint64_t> start(n * BL_RAY_START_FIELDS), constants(2 * n);
+  Check(hipMemcpy(start.data(), d_start.ptr, start.size() * sizeof(uint64_t), hipMemcpyDeviceToHost), "start state download");
+  Check(hipMemcpy(constants.data(), d_constants.ptr, constants.size() * sizeof(uint64_t), hipMemcpyDeviceToHost), "start state download");
+  // rows of the start state: t x y z k_x k_y k_z | k_t | r | d/dlambda of (t x y z k_x k_y k_z s): odd in y are y, k_y, dy, dk_y
+  constexpr uint64_t kSign = 1ull << 63;
+  bool ok = true;
+  for (size_t field = 0; field < BL_RAY_START_FIELDS && ok; field++) {
+    const uint64_t flip = (field == 2 || field == 5 || field == 11 || field == 14) ? kSign : 0ull;
+    const uint64_t *values = start.data() + field * n;
+    for (size_t row = 0; row < res && ok; row++)
+      for (size_t col = 0; col < res / 2; col++)
+        // (an odd component may be a zero of either sign on both sides: a sum whose terms cancel exactly is +0 whatever their signs -
+        // dy/dlambda of a plane camera's rays, whose directions have no y. A zero's sign changes no sum with a non-zero term and no
+        // product's magnitude, and the stepper divides by nothing odd: the paths stay mirror images, the zeros may differ in sign.)
+        // (The four odd components only: an even one must have the same bits on both sides, zeros included. DESIGN.md section 5.)
+        if (values[row * res + col] != (values[row * res + res - 1 - col] ^ flip)
+            && !(flip != 0ull && ((values[row * res + col] | values[row * res + res - 1 - col]) << 1) == 0ull)) {
+          ok = false;
+          if (ctx->debug_counters)
+            std::fprintf(stderr, "mirror pairs: start field %zu of pixel (%zu, %zu) is %016llx, of its mirror pixel %016llx\n", field, row, col,
+                         static_cast<unsigned long long>(values[row * res + col]), static_cast<unsigned long long>(values[row * res + res - 1 - col]));
+          break;
+        }
+  }
+  for (size_t row = 0; row < res && ok; row++)
+    for (size_t col = 0; col < res / 2; col++) {
+      const size_t a = row * res + col, b = row * res + res - 1 - col;
+      if (constants[2 * a] != constants[2 * b] || constants[2 * a + 1] != constants[2 * b + 1]) {
+        ok = false;
+        break;
+      }
+    }
+  ctx->mirror_key = inputs;
+  ctx->mirror_ok = ok;
+  return ok;
+}
+
+// Whether this render traces one ray per mirror pair: the plan's part (the paths whose kernels know the second walk - a full root frame of
+// one camera in tile order, one frequency, one variant, unpolarized, no auxiliary row, no sample times, every step recorded, one block,
+// nothing parked or split, no checkpoint, no camera rows - everything else takes the path it took), then the camera's. PlanScratch
+// still drops it where one scratch set does not take the half frame's worst case in one chunk.
+bool MirrorPairsApply(RenderJob &job) {
+  const bl_ctx *ctx = job.ctx;
+  const bl_params &p = ctx->params;
+  const bl_render_desc *d = job.d;
+  const Variants &vs = job.variants;
+  const bool kernels = ((job.fused2 && !job.freq_split) || job.exact_fused) && ctx->grid.dev.n_blocks == 0;
+  const bool plan = d->level == 0 && d->pixel_map == nullptr && job.n_rays == job.level_pixels && !job.camera_table && !job.raster
+      && p.camera_resolution % 16 == 0 && ctx->st.bh_a == 0.0 && p.ray_integrator == BL_INTEGRATOR_DP
+      && !ctx->polarized && job.n_nu == 1 && vs.list.size() == 1 && vs.n_models == 0 && vs.n_units == 0 && vs.n_cuts == 0 && vs.n_pol == 0
+      && !job.aux && !job.tau_row && !job.need_time && !job.skip_shell && !job.park && !job.split_long
+      && job.no_checkpoint && d->camera_pos == nullptr && d->camera_dir == nullptr
+      && !(ctx->switches & BL_SWITCH_NO_MIRROR_PAIRS);
+  const bool camera = kernels && plan && MirrorCameraPasses(job);
+  if (ctx->debug_counters) std::fprintf(stderr, "mirror pairs: kernels %d, plan %d, camera %d\n", kernels ? 1 : 0, plan ? 1 : 0, camera ? 1 : 0);
+  return camera;
+}
+
 // ---- scratch: what a sample record costs, how many fit, how many persistent waves trace rays into them
 void PlanScratch(RenderJob &job) {
   bl_ctx *ctx = job.ctx;
@@ -1081,14 +1188,14 @@ void PlanScratch(RenderJob &job) {
   // No more lanes than half the rays: a lane that traces one ray only leaves its wave idling behind the longest of 64 rays, and
   // with fewer waves per SIMD each of them is faster - an eighth of the benchmark frame (131 072 rays) takes 4.3 ms on 1 024 waves,
   // 4.7 to 5.3 ms on 2 048 (and the coefficient kernel 5.0 instead of 5.2 ms over the more compact records)
-  const long long max_grid = std::min<long long>(static_cast<long long>(ctx->num_cus) * waves_per_cu, std::max<long long>(1, (job.n_rays + 127) / 128));
+  const long long max_grid = std::min<long long>(static_cast<long long>(ctx->num_cus) * waves_per_cu, std::max<long long>(1, (job.n_traced + 127) / 128));
   // (the waves of bl_geodesic_quad_kernel take blocks of record slots as well: a wave per SIMD)
   // (one to a SIMD: with three - as many as fit its registers - every ray runs at a third of the speed, the longest ones too, and
   // configuration 2 takes 94 ms instead of 67)
   const long long quad_waves = job.park ? static_cast<long long>(ctx->num_cus) * 4
       : (job.split_long ? 64ll * 4 : 0);   // (split: at most 64 compute units, sized below)
-  const uint64_t worst_case = static_cast<uint64_t>(job.n_rays) * job.max_steps + static_cast<uint64_t>(max_grid + quad_waves) * BL_RECORD_BLOCK;
-  const uint64_t fixed = per_ray * static_cast<uint64_t>(job.n_rays);
+  const uint64_t worst_case = static_cast<uint64_t>(job.n_traced) * job.max_steps + static_cast<uint64_t>(max_grid + quad_waves) * BL_RECORD_BLOCK;
+  const uint64_t fixed = per_ray * static_cast<uint64_t>(job.n_traced);
   if (job.kept && PlanKeptLayout(job, max_grid, quad_waves, waves_per_cu)) return;
   job.kept = false;   // (it does not fit: planned as any render, nothing kept)
   auto capacity_for = [&](int n_slots) -> uint64_t {
@@ -1108,6 +1215,17 @@ void PlanScratch(RenderJob &job) {
   // capacity stays 2^22 records below 2^32. Clamped BEFORE the persistent grid and the reservation gate are derived from it
   // (they were once computed from the unclamped value: a gate beyond the buffers EnsureScratch allocates).
   capacity = std::min<uint64_t>(capacity, (1ull << 32) - (1ull << 22));
+  // Mirror pairs: the shading stage walks 2 n record indices with 32 bits, and the traced half must be sure to fit one chunk of one
+  // scratch set. Where it is not, every ray is traced, as without pairs.
+  if (job.mirror) {
+    capacity = std::min<uint64_t>(capacity, ((1ull << 32) - (1ull << 22)) / 2);
+    if (job.n_slots != 1 || capacity < worst_case) {
+      job.mirror = false;
+      job.n_traced = job.n_rays;
+      PlanScratch(job);
+      return;
+    }
+  }
   // Persistent waves: every lane in flight holds ray_max_steps record slots until its ray ends, so no more lanes than the
   // buffer can cover at once. (A chunk still takes about capacity / samples-per-ray rays: a finished ray gives back what it
   // did not emit and the lanes that were refused ask again. Fewer waves than that would only trace the same rays more
@@ -1311,7 +1429,7 @@ void EnsureScratchOnce(RenderJob &job) {
     sl.d_counters.Ensure(BL_CNT_TOTAL);
     if (job.use.redo) sl.d_redo.Ensure(job.redo_capacity);
   }
-  const size_t n_rays = static_cast<size_t>(job.n_rays);
+  const size_t n_rays = static_cast<size_t>(job.n_traced);
   auto ensure = [n_rays](auto &...buffer) { (buffer.Ensure(n_rays), ...); };
   ensure(ctx->rays.constants, ctx->rays.sample_num, ctx->rays.flags, ctx->rays.out_index, ctx->rays.offset);
   if (job.skip_shell) ctx->rays.skipped.Ensure(n_rays);
@@ -1402,12 +1520,11 @@ void StageInputsAndOutputs(RenderJob &job) {
   }
 }
 
-// ---- kernel arguments common to all chunks: the geodesic kernel's
-void BuildTraceArgs(RenderJob &job) {
-  bl_ctx *ctx = job.ctx;
-  const bl_render_desc *d = job.d;
+// ---- kernel arguments common to all chunks: the geodesic kernel's. First what the context alone decides - spacetime, the camera's
+// block, the stepper's settings: all bl_ray_init_kernel reads besides the arrays it is pointed at (MirrorCameraPasses launches it on
+// these before the call is planned)
+void BuildCameraArgs(const bl_ctx *ctx, const bl_render_desc *d, int max_steps, BlTraceArgs &ta) {
   const bl_params &p = ctx->params;
-  BlTraceArgs &ta = job.ta;
   ta.st = ctx->st;
   BlCameraDevice &cam = ta.cam;
   for (int mu = 0; mu < 4; mu++) {
@@ -1431,6 +1548,21 @@ void BuildTraceArgs(RenderJob &job) {
   ta.r_terminate = ctx->frame.r_terminate;
   ta.r_horizon = ctx->frame.r_horizon;
   ta.camera_r = p.camera_r;
+  ta.ray_step = p.ray_step;
+  ta.ray_tol_abs = p.ray_integrator == BL_INTEGRATOR_DP ? p.ray_tol_abs : 0.0;
+  ta.ray_tol_rel = p.ray_integrator == BL_INTEGRATOR_DP ? p.ray_tol_rel : 0.0;
+  ta.ray_max_steps = max_steps;
+  ta.ray_max_retries = p.ray_integrator == BL_INTEGRATOR_DP ? p.ray_max_retries : 0;
+}
+
+// ... then what the plan decides: which rays in which order, the skipped shell, the camera table
+void BuildTraceArgs(RenderJob &job) {
+  bl_ctx *ctx = job.ctx;
+  const bl_render_desc *d = job.d;
+  const bl_params &p = ctx->params;
+  BlTraceArgs &ta = job.ta;
+  BuildCameraArgs(ctx, d, job.max_steps, ta);
+  const BlCameraDevice &cam = ta.cam;
   ta.skip_low = std::numeric_limits<double>::infinity();
   ta.skip_high = 0.0;
   if (job.skip_shell) {
@@ -1438,11 +1570,6 @@ void BuildTraceArgs(RenderJob &job) {
     ta.skip_low = std::sqrt(ctx->grid.tables.outer_x1 * ctx->grid.tables.outer_x1 * (1.0 + 1.0e-9) + a * a) * (1.0 + 1.0e-12);
     ta.skip_high = p.camera_r * (1.0 - 1.0e-9);
   }
-  ta.ray_step = p.ray_step;
-  ta.ray_tol_abs = p.ray_integrator == BL_INTEGRATOR_DP ? p.ray_tol_abs : 0.0;
-  ta.ray_tol_rel = p.ray_integrator == BL_INTEGRATOR_DP ? p.ray_tol_rel : 0.0;
-  ta.ray_max_steps = job.max_steps;
-  ta.ray_max_retries = p.ray_integrator == BL_INTEGRATOR_DP ? p.ray_max_retries : 0;
   ta.n_rays_total = job.n_rays;
   ta.swizzle_tiles = (d->level == 0 && d->pixel_map == nullptr && p.camera_resolution % 8 == 0 && job.n_rays == job.level_pixels && !job.raster)
       ? p.camera_resolution : 0;
@@ -1459,12 +1586,16 @@ void BuildTraceArgs(RenderJob &job) {
   if (ta.swizzle_tiles > 0) {
     const bool super_tiles = job.reuse ? ctx->resident.super_tiles : job.xcd_order;
     job.super_tiles = super_tiles;
-    if (ctx->tile_order_res != p.camera_resolution || ctx->tile_order_xcd != super_tiles || ctx->tile_order_cameras != job.n_cameras) {
+    if (ctx->tile_order_res != p.camera_resolution || ctx->tile_order_xcd != super_tiles || ctx->tile_order_cameras != job.n_cameras
+        || ctx->tile_order_half != job.mirror) {
       const int tiles_per_row = p.camera_resolution / 8;
       const int n_tiles = tiles_per_row * tiles_per_row;
       const int unit = super_tiles ? 8 : 1;   // (tiles per side of the unit)
-      std::vector<int> order(n_tiles);
-      for (int t = 0; t < n_tiles; t++) order[t] = t;
+      // (mirror pairs: the tiles of the left half only, in the order they have in the whole frame's)
+      std::vector<int> order;
+      order.reserve(n_tiles);
+      for (int t = 0; t < n_tiles; t++)
+        if (!job.mirror || t % tiles_per_row < tiles_per_row / 2) order.push_back(t);
       const int units_per_row = (tiles_per_row + unit - 1) / unit;
       const double centre = 0.5 * (units_per_row - 1);
       auto unit_index = [&](int t) { return (t / tiles_per_row / unit) * units_per_row + t % tiles_per_row / unit; };
@@ -1494,9 +1625,21 @@ void BuildTraceArgs(RenderJob &job) {
       }
       ctx->d_tile_order.Ensure(order.size());
       Check(hipMemcpy(ctx->d_tile_order.ptr, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice), "tile order upload");
+      if (job.mirror) {   // where the mirror pixel of every traced slot goes (the geodesic kernel's traversal_to_ray, reflected)
+        const long long res = p.camera_resolution;
+        std::vector<long long> mirror_out(order.size() * 64);
+        for (size_t q = 0; q < mirror_out.size(); q++) {
+          const long long tile = order[q >> 6], within = static_cast<long long>(q & 63);
+          const long long m2 = tile / tiles_per_row * 8 + (within >> 3), m1 = tile % tiles_per_row * 8 + (within & 7);
+          mirror_out[q] = m2 * res + (res - 1 - m1);
+        }
+        ctx->d_mirror_out.Ensure(mirror_out.size());
+        Check(hipMemcpy(ctx->d_mirror_out.ptr, mirror_out.data(), mirror_out.size() * sizeof(long long), hipMemcpyHostToDevice), "mirror pixel upload");
+      }
       ctx->tile_order_res = p.camera_resolution;
       ctx->tile_order_xcd = super_tiles;
       ctx->tile_order_cameras = job.n_cameras;
+      ctx->tile_order_half = job.mirror;
     }
     ta.tile_order = ctx->d_tile_order.ptr;
   }
@@ -1504,7 +1647,7 @@ void BuildTraceArgs(RenderJob &job) {
   ta.block_locs = job.d_block_locs;
   ta.camera_pos = job.cam_pos;
   ta.camera_dir = job.cam_dir;
-  ta.ray_start_stride = job.n_rays;
+  ta.ray_start_stride = job.n_traced;
   // Several cameras: every camera's block as `cam` above with its own seven vectors, in HBM (uploaded when the list changes)
   ta.cameras = nullptr;
   ta.pixels_per_camera = 0;
@@ -1841,6 +1984,7 @@ void BuildShadeArgs(RenderJob &job) {
   sa.freq_split = job.freq_split ? (job.variants_one_pass ? 2 : 1) : 0;
   sa.coef_split = job.coef_split ? 1 : 0;
   sa.redo_capacity = job.use.redo ? job.redo_capacity : 0;
+  sa.row_add = job.mirror ? static_cast<unsigned int>(job.record_capacity) : 0u;   // (at most 2^31: PlanScratch)
 
   job.snapshot_time = job.slow ? p.slow_t_start + p.slow_dt * ctx->snapshot : 0.0;   // simulation_reader.cpp:214
   if (job.slow) {
@@ -1885,6 +2029,9 @@ void BuildTransferArgs(RenderJob &job) {
   xa.affine = (job.fast || job.fast_formula) ? 1 : 0;
   xa.lane_transfer = (ctx->switches & BL_SWITCH_LANE_TRANSFER) ? 1 : 0;
   xa.n_rays_total = job.n_rays;
+  xa.mirror_rays = job.mirror ? static_cast<int>(job.n_traced) : 0;
+  xa.row_add = job.mirror ? static_cast<long long>(job.record_capacity) : 0;
+  xa.mirror_out_index = job.mirror ? ctx->d_mirror_out.ptr : nullptr;
   xa.image = job.image;
   xa.n_models = 0;
   xa.n_units = 0;
@@ -2323,6 +2470,10 @@ void CollectChunk(RenderJob &job, int k) {
   }
   job.total_undefined += hc[BL_CNT_UNDEFINED];
   job.total_records += hc[BL_CNT_RECORDS];
+  // (records the rays emitted: what is left of the steppers' reservations once every ray has given back what it did not emit - less the
+  // gate's mark, kGateClosed = 2^46 per refusal. The record slots above also count each wave's partly filled last block, which differs
+  // from launch to launch; this does not. Zero where the records came from a checkpoint: the slots are the records there.)
+  job.total_emitted += hc[BL_CNT_COMMITTED] & ((1ull << 46) - 1ull);
   job.total_gathers += hc[BL_CNT_GATHERS];
   job.total_parked += std::min<unsigned long long>(hc[BL_CNT_PARKED] + hc[BL_CNT_PARKED_YOUNG], job.park_capacity);
   if (job.fast || job.fast_formula) job.total_redo += hc[BL_CNT_REDO];   // (polarized runs use the list for something else: bl_polarized_frame_kernel)
@@ -2365,12 +2516,12 @@ void RunChunks(RenderJob &job) {
     hipEvent_t *e = SlotEvents(job, 0);
     job.chunk_segment = 0;
     job.chunk_base = 0;
-    BindChunk(job, 0, 0, static_cast<int>(job.n_rays));
+    BindChunk(job, 0, 0, static_cast<int>(job.n_traced));
     if (job.cam_pos != nullptr || job.cam_dir != nullptr) Check(bl_launch_ray_init(&job.ta, job.kernels.geodesic, stream), "ray start kernel launch");
     const size_t n_kept = job.reuse_chunks ? res.chunks.size() : 1;
     for (size_t c = 0; c < n_kept; c++) {
       const long long begin = job.reuse_chunks ? res.chunks[c].begin : 0;
-      const int rays = static_cast<int>(job.n_rays - begin);
+      const int rays = static_cast<int>(job.n_traced - begin);
       const unsigned long long *counters = job.reuse_chunks ? res.chunks[c].counters : res.counters;
       job.chunk_segment = job.reuse_chunks ? res.chunks[c].segment : 0;
       job.chunk_base = job.reuse_chunks ? res.chunks[c].record_base : 0;
@@ -2386,7 +2537,7 @@ void RunChunks(RenderJob &job) {
       job.in_flight[0].begin = begin;
       job.in_flight[0].rays = rays;
       job.in_flight[0].done = job.reuse_chunks ? static_cast<long long>(std::min<unsigned long long>(counters[BL_CNT_NEXT_RAY], static_cast<unsigned long long>(rays)))
-                                               : job.n_rays;
+                                               : job.n_traced;
       const long long done = job.in_flight[0].done;
       LaunchShadingStage(job, 0, false, stream);
       SaveChunk(job, 0, begin, done);
@@ -2399,10 +2550,10 @@ void RunChunks(RenderJob &job) {
   }
   if (!job.geo_load) {
     // start states of every ray of the call, once (bl_ray_init_kernel; the geodesic kernel of each chunk reads its share)
-    BindChunk(job, 0, 0, static_cast<int>(job.n_rays));
+    BindChunk(job, 0, 0, static_cast<int>(job.n_traced));
     Check(bl_launch_ray_init(&job.ta, job.kernels.geodesic, stream_geo), "ray start kernel launch");
   }
-  const long long n_rays = job.n_rays;
+  const long long n_rays = job.n_traced;
   auto no_progress = []() {
     return Failure{BL_E_ARG, "Scratch budget too small: no ray fits the sample record buffers (bl_set_scratch_limit)."};
   };
@@ -2517,7 +2668,8 @@ void FinishStats(RenderJob &job) {
   st.launches_shade = job.n_chunks * job.variant_passes;   // (polarized variants in one pass: the coefficient kernel once per chunk)
   st.launches_transfer = job.n_chunks * job.variant_passes;
   st.n_samples = static_cast<int64_t>(job.total_samples);
-  st.n_samples_emitted = static_cast<int64_t>(job.total_records);
+  // (mirror pairs: every record stands for two)
+  st.n_samples_emitted = static_cast<int64_t>(job.total_emitted != 0 ? job.total_emitted : job.total_records) * (job.mirror ? 2 : 1);
   st.n_gathers = static_cast<int64_t>(job.total_gathers);
   st.n_flagged = static_cast<int64_t>(job.total_flagged);
   st.max_sample_num = static_cast<int32_t>(job.max_num);
@@ -2539,6 +2691,7 @@ void FinishStats(RenderJob &job) {
   st.n_parked = static_cast<int64_t>(job.reuse ? ctx->resident.n_parked : job.total_parked);
   st.composed_maps = job.composed ? 1 : 0;
   st.xcd_order = job.xcd_order ? 1 : 0;
+  st.mirror_pairs = job.mirror ? 1 : 0;
   st.local_angles = job.local_angles ? 1 : 0;
   st.n_cameras = job.n_cameras;
   st.tail_policy = job.reuse ? ctx->resident.tail_policy : (job.park ? BL_TAIL_QUAD : (job.split_long ? BL_TAIL_SPLIT : BL_TAIL_WIDE));
@@ -2649,6 +2802,7 @@ extern "C" int bl_render(bl_ctx *ctx, const bl_render_desc *d) {
         PlanJob(job);
         Check(hipSetDevice(ctx->device), "hipSetDevice");
         EnsureStreams(ctx);
+        job.mirror = MirrorPairsApply(job);
         DecideReuse(job);
         PlanScratch(job);
         if (job.split_long && !EnsureSplitStreams(ctx, job.split_cus)) {

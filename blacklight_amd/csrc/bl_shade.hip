@@ -44,13 +44,17 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
   const unsigned long long n_all = P.counters_in[BL_CNT_RECORDS];
   const unsigned long long n_listed = kRedo ? P.counters_in[BL_CNT_REDO] : 0ull;
   const bool listed = kRedo && n_listed <= P.redo_capacity;
-  const unsigned long long n_records = listed ? n_listed : n_all;   // work items: list entries or records
+  // (mirror pairs, BlShadeArgs::row_add != 0: the list's entries, or the walk that replaces it, are indices in [0, 2 n_all) - index
+  // i >= n_all is record i - n_all as its ray's mirror image in y = 0, rows row_add further on)
+  const bool pairs = kRedo && kSpinZero && P.row_add != 0u;   // (zero spin: the instantiation a paired render launches)
+  const unsigned long long n_records = listed ? n_listed : (pairs ? 2ull * n_all : n_all);   // work items: list entries or records
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
   // The record and the located sample of the next iteration are requested at the top of this one, behind
   // this sample's grid reads, so they arrive while the arithmetic runs.
   unsigned long long pos = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (pos >= n_records) return;
-  unsigned long long idx = listed ? P.redo_list[pos] : first_record + pos;
+  unsigned long long idx_walked = listed ? P.redo_list[pos] : first_record + pos;
+  unsigned long long idx = (pairs && idx_walked >= n_all) ? idx_walked - n_all : idx_walked;
   double2 nq0, nq1, nq2, nq3, nl0 = make_double2(0.0, 0.0), nl1 = nl0;
   unsigned long long ntag = 0ull;
   {
@@ -65,7 +69,13 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
   }
   for (bool more = true; more;) {
     const unsigned long long idx_cur = idx;
-    const double2 q0 = nq0, q1 = nq1, q2 = nq2, q3 = nq3;
+    const bool mirror = pairs && idx_walked != idx;
+    const unsigned long long idx_walked_cur = idx_walked;
+    double2 q0 = nq0, q1 = nq1, q2 = nq2, q3 = nq3;
+    if (mirror) {
+      q0.y = -q0.y;   // (sign bit only: y)
+      q2.y = -q2.y;   // (k_y)
+    }
     double2 l0 = nl0, l1 = nl1;
     unsigned long long tag = ntag;
     const uint32_t ray = (uint32_t)__double_as_longlong(q1.y);
@@ -105,8 +115,8 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
       const double2 constants = bl_ray_constants(P.ray_constants, (size_t)ray);
       kcov[0] = constants.x;
       momentum_factor = constants.y;
-      row = (size_t)P.ray_offset[ray] + n;
-      if (kRedo && P.composed != nullptr) row = (size_t)idx_cur;   // composed transfer maps: per-sample records lie by record index
+      row = (size_t)P.ray_offset[ray] + n + (mirror ? (size_t)P.row_add : 0);
+      if (kRedo && P.composed != nullptr) row = (size_t)idx_walked_cur;   // composed transfer maps: per-sample records lie by record index
     }
     float pr[8];
     float kappa_f = 0.0f;
@@ -128,7 +138,8 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
     pos += stride;
     more = pos < n_records;
     if (more) {
-      idx = listed ? P.redo_list[pos] : first_record + pos;
+      idx_walked = listed ? P.redo_list[pos] : first_record + pos;
+      idx = (pairs && idx_walked >= n_all) ? idx_walked - n_all : idx_walked;
       const double2 *hot = reinterpret_cast<const double2 *>(P.records_hot + (idx) * P.record_stride);
       const double2 *cold = reinterpret_cast<const double2 *>(P.records_cold + (idx) * P.record_stride);
       nq0 = hot[0]; nq1 = hot[1]; nq2 = cold[0]; nq3 = cold[1];

@@ -845,6 +845,11 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   if (n_records <= first_record) return;
   const uint32_t stride = gridDim.x * blockDim.x;
   const uint32_t last = n_records - 1u;
+  // Mirror pairs (BlShadeArgs::row_add != 0): the record indices walked are [0, 2 n_records). A wave whose first index is at or beyond
+  // n_records - a multiple of 64, so this is wave-uniform - shades record index - n_records as the ray's mirror image in y = 0.
+  // (Zero spin, one block, transfer records or composed maps: the instantiations a paired render launches. The others are compiled without it.)
+  constexpr bool kPairs = kSpinZero && !kFactors && !kRefined;
+  const uint32_t n_virtual = (kPairs && P.row_add != 0u) ? 2u * n_records : n_records;
   const BlSpacetime st = P.st;
   const GridScalars G = kRefined ? grid_scalars_refined(P.grid, lds_base + 48u * 8u) : grid_scalars(P.grid, lds_base + 48u * 8u);
   const uint32_t cut_table = lds_base;
@@ -877,7 +882,14 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   const uint32_t lane_bytes = lane_in_wave << 6;
   const uint32_t wave_offset = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * blockDim.x + (threadIdx.x & ~63u)));
   uint32_t base_index = first_record;   // record index of lane 0 of block 0 for the sample `next` ... (wave-uniform, grid-stride walk)
-  auto record_base = [&](uint32_t first) { return records + ((size_t)(first < last ? first : last) << 6); };
+  auto record_base = [&](uint32_t first) {
+    const uint32_t real = (kPairs && first >= n_records) ? first - n_records : first;
+    return records + ((size_t)(real < last ? real : last) << 6);
+  };
+  // (a mirror wave: the sign bit of y and of k_y flipped - wave-uniform mask; any other wave: the value as it is)
+  auto mirrored = [&](double value, uint32_t first) {
+    return kPairs ? __hiloint2double(__double2hiint(value) ^ (int)(first >= n_records ? 0x80000000u : 0u), __double2loint(value)) : value;
+  };
   // The list walk: batches of BL_XCD_BATCH groups claimed with one atomic on a list's cursor, lane b of `batch` holding group b.
   // The claim for the next batch is made when a batch begins and its groups are read one group later, so that neither the
   // atomic nor the read is waited for where it is used. A list that has nothing left passes the wave on to the next one.
@@ -896,17 +908,27 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     // (what a claim found; past a list's end, claims on the next lists until one has groups left or all have been tried)
     unsigned long long at = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(claim >> 32), 0) << 32)
         | (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)claim, 0);
-    unsigned long long length = P.xcd_state[BL_XCD_QUEUES + list];
+    // (mirror pairs: a list of `plain` groups is walked twice - positions [plain, 2 plain) are its groups again, as mirror groups,
+    // n_records / 64 further on in the index space; the switch is read where it is used, not held across the loop)
+    const unsigned long long twice = (kPairs && kernargs()->row_add != 0u) ? 2ull : 1ull;
+    unsigned long long plain = P.xcd_state[BL_XCD_QUEUES + list];
+    unsigned long long length = plain * twice;
     while (at >= length && tried < BL_XCD_QUEUES - 1) {
       tried++;
       list = (list + 1) & (BL_XCD_QUEUES - 1);
       claim_issue();
       at = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(claim >> 32), 0) << 32)
           | (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)claim, 0);
-      length = P.xcd_state[BL_XCD_QUEUES + list];
+      plain = P.xcd_state[BL_XCD_QUEUES + list];
+      length = plain * twice;
     }
     next_n = at < length ? (int)(length - at < (unsigned long long)BL_XCD_BATCH ? length - at : (unsigned long long)BL_XCD_BATCH) : 0;
-    next_batch = (int)lane_in_wave < next_n ? P.xcd_lists[(size_t)list * (size_t)P.xcd_list_capacity + at + lane_in_wave] : 0u;
+    {
+      const unsigned long long position = at + lane_in_wave;
+      const bool again = kPairs && position >= plain;
+      const uint32_t group = (int)lane_in_wave < next_n ? P.xcd_lists[(size_t)list * (size_t)P.xcd_list_capacity + (again ? position - plain : position)] : 0u;
+      next_batch = group + (again ? n_records >> 6 : 0u);
+    }
     claim_pending = false;
   };
   // the wave's first record for the next iteration's `next`
@@ -957,11 +979,12 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   // (32-bit record indices: the launcher keeps n_records + 3 strides below 2^32)
   s0.first = kNoRecords;
   s1.first = walk_next();
-  s1.in = s1.first + lane_in_wave < n_records;
+  s1.in = s1.first + lane_in_wave < n_virtual;
   {
     const double2 *rec = reinterpret_cast<const double2 *>(record_base(s1.first) + (size_t)(s1.in ? lane_bytes : 0u));
     s1.h0 = rec[0];
     s1.h1 = rec[1];
+    s1.h0.y = mirrored(s1.h0.y, s1.first);
     s1.h1.y = s1.in ? s1.h1.y : __longlong_as_double((long long)BL_DEAD_RAY);
   }
   s1.loc = locate<kSpinZero, kRefined>(st, G, camera_r, band, (uint32_t)__double_as_longlong(s1.h1.y) != BL_DEAD_RAY, s1.h0.x, s1.h0.y, s1.h1.x, local_angles);
@@ -987,14 +1010,15 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     const bool interp = status == (uint32_t)kSampleInterp;
     // the position record of `next`: the oldest request of the iteration, used at its end
     x.first = walk_next();
-    x.in = x.first + lane_in_wave < n_records;
+    x.in = x.first + lane_in_wave < n_virtual;
     {
       const double2 *rec = reinterpret_cast<const double2 *>(record_base(x.first) + (size_t)(x.in ? lane_bytes : 0u));
       x.h0 = rec[0];
       x.h1 = rec[1];
     }
     const double kt = p.kt, momentum_factor = p.factor;
-    const long long row_first = p.row;
+    // (a mirror wave's rows: the second half of the per-sample row arrays)
+    const long long row_first = kPairs ? p.row + (long long)(p.first >= n_records ? P.row_add : 0u) : p.row;
     float pr[8];
     const bool near_midpoint = trilinear(lo, hi, p.loc.f_i, p.loc.f_j, p.loc.f_k, pr);
     if (kFactors) {
@@ -1028,7 +1052,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     double2 factors[4];
     if (kFactors) factors[0] = factors[1] = factors[2] = factors[3] = make_double2(0.0, 0.0);
     if (interp)
-      rec = shade<kSpinZero, kFactors>(st, K, freq, freq_inv, x_unit, cut_mask, cut_table, pr, p.h0.x, p.h0.y, p.h1.x, p.c0.x, p.c0.y, p.c1.x, kt, momentum_factor,
+      rec = shade<kSpinZero, kFactors>(st, K, freq, freq_inv, x_unit, cut_mask, cut_table, pr, p.h0.x, p.h0.y, p.h1.x, p.c0.x, mirrored(p.c0.y, p.first), p.c1.x, kt, momentum_factor,
                                        -p.c1.y, &have, &undecided_cut, kFactors ? &factors : nullptr, kFactors && model_rows,
                                        kFactors ? P.n_sigma_bands : 0, P.sigma_band_lo, P.sigma_band_hi);
     // a sample off the grid has fallback primitives without a field (no coefficients: I <- I) or NaN ones (I <- I + NaN,
@@ -1123,6 +1147,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
       if (at < args->redo_capacity) args->redo_list[at] = (unsigned long long)(p.first + lane_in_wave);
     }
     // ---- the search for `next`
+    x.h0.y = mirrored(x.h0.y, x.first);
     x.loc = locate<kSpinZero, kRefined, decltype(kLocal)::value ? kAnglesLocal : kAnglesGlobal>(st, G, camera_r, band, x.in && (uint32_t)__double_as_longlong(x.h1.y) != BL_DEAD_RAY,
                                                                                                x.h0.x, x.h0.y, x.h1.x, local_angles);
     x.h1.y = x.in ? x.h1.y : __longlong_as_double((long long)BL_DEAD_RAY);
@@ -1338,11 +1363,23 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
   const uint32_t lane_index = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lane_bytes = lane_index << 6;
   uint32_t base_index = first_record;
+  // Mirror pairs (BlShadeArgs::row_add != 0, bl_shade_fused2_kernel): the indices walked are [0, 2 n_records); index i >= n_records - for
+  // all lanes of a wave or none, n_records being a multiple of 64 - is record i - n_records as its ray's mirror image in y = 0: the
+  // sign bits of y and k_y flipped, its rows row_add further on.
+  // (the zero-spin instantiation only: no other is launched by a paired render)
+  const uint32_t n_virtual = (kSpinZero && P.row_add != 0u) ? 2u * n_records : n_records;
+  auto is_mirror = [&](uint32_t first, bool in) { return kSpinZero && in && first + lane_index >= n_records; };
   auto record_base = [&](uint32_t first) { return records + ((size_t)(first < last ? first : last) << 6); };
+  auto record_of = [&](uint32_t first, bool in) {
+    const bool mirror = is_mirror(first, in);
+    return reinterpret_cast<const double2 *>(mirror ? records + ((size_t)(first + lane_index - n_records) << 6) : record_base(first) + (size_t)(in ? lane_bytes : 0u));
+  };
+  auto mirrored = [](double value, bool mirror) { return __hiloint2double(__double2hiint(value) ^ (int)(mirror ? 0x80000000u : 0u), __double2loint(value)); };
   double2 prev0 = make_double2(0.0, 0.0), prev1 = make_double2(0.0, __longlong_as_double((long long)BL_DEAD_RAY)), prev2 = prev0, prev3 = prev0;
   double2 cur0, cur1;
   double kt_prev = 0.0, factor_prev = 1.0;
   long long row_prev = 0;
+  bool mirror_prev = false;
   LocatedExact loc_prev, loc_cur;
   loc_prev.f_i = loc_prev.f_j = loc_prev.f_k = loc_prev.ph_unwrapped = 0.0;
   loc_prev.status = kSampleNone;
@@ -1350,11 +1387,12 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
   float4 lo[8], hi[8];
 #pragma unroll
   for (int c = 0; c < 8; c++) lo[c] = hi[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  bool cur_in = first_record + lane_index < n_records;
+  bool cur_in = first_record + lane_index < n_virtual;
   {
-    const double2 *rec = reinterpret_cast<const double2 *>(record_base(first_record) + (size_t)(cur_in ? lane_bytes : 0u));
+    const double2 *rec = record_of(first_record, cur_in);
     cur0 = rec[0];
     cur1 = rec[1];
+    cur0.y = mirrored(cur0.y, is_mirror(first_record, cur_in));
     cur1.y = cur_in ? cur1.y : __longlong_as_double((long long)BL_DEAD_RAY);
   }
   loc_cur = locate_exact<kSpinZero, true>(st, P.grid, G, camera_r, (uint32_t)__double_as_longlong(cur1.y) != BL_DEAD_RAY, cur0.x, cur0.y, cur1.x);
@@ -1365,22 +1403,22 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
     const uint32_t n = (uint32_t)(((unsigned long long)__double_as_longlong(prev1.y)) >> 32);
     const int status = (int)loc_prev.status;
     const uint32_t next_first = base_index + stride;
-    const bool next_in = next_first + lane_index < n_records;
+    const bool next_in = next_first + lane_index < n_virtual;
     double2 next0, next1;
     {
-      const double2 *rec = reinterpret_cast<const double2 *>(record_base(next_first) + (size_t)(next_in ? lane_bytes : 0u));
+      const double2 *rec = record_of(next_first, next_in);
       next0 = rec[0];
       next1 = rec[1];
     }
     const double kt = kt_prev, momentum_factor = factor_prev;
-    const long long row_first = row_prev;
+    const long long row_first = row_prev + (long long)(mirror_prev ? P.row_add : 0u);
     float pr[8];
     gather_finish(P, fallback_rho, fallback_pgas, status, lo, hi, loc_prev.f_i, loc_prev.f_j, loc_prev.f_k, pr);
     gathers_wave += (unsigned long long)__popcll(__ballot(status == (int)kSampleInterp));
     fused2::gather_issue(cells, loc_cur.cell_bytes, loc_cur.status == (uint32_t)kSampleInterp, row_bytes, plane_bytes, lo, hi);
     double2 cold0, cold1;
     {
-      const double2 *rec = reinterpret_cast<const double2 *>(record_base(base_index) + (size_t)(cur_in ? lane_bytes : 0u));
+      const double2 *rec = record_of(base_index, cur_in);
       cold0 = rec[2];
       cold1 = rec[3];
     }
@@ -1396,7 +1434,7 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
       // ---- bl_shade_exact_kernel's body (bl_shade.hip), call for call
       const double x1 = prev0.x, x2 = prev0.y, x3 = prev1.x;
       const double delta_lambda = -prev3.y;   // ReverseGeodesics: sample_len = -geodesic_len (geodesics.cpp:840)
-      double kcov[4] = {kt, prev2.x, prev2.y, prev3.x};
+      double kcov[4] = {kt, prev2.x, mirrored(prev2.y, mirror_prev), prev3.x};
       BlKerrSchild ks;
       bl_kerr_schild<kSpinZero>(st, x1, x2, x3, &ks);
       {   // per-sample renormalisation of the stored momentum (geodesics.cpp:352-371)
@@ -1423,6 +1461,7 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
       P.transfer[(size_t)(row_first + (long long)n)] = transfer_record(j_val, alpha_val, delta_lambda_cgs);
     }
     const bool live_next = next_in && (uint32_t)__double_as_longlong(next1.y) != BL_DEAD_RAY;
+    next0.y = mirrored(next0.y, is_mirror(next_first, next_in));
     LocatedExact loc_next = loc_cur;
     if (__any(live_next)) loc_next = locate_exact<kSpinZero, true>(st, P.grid, G, camera_r, live_next, next0.x, next0.y, next1.x);
     else loc_next.status = kSampleNone, loc_next.cell_bytes = 0u;
@@ -1432,6 +1471,7 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
     prev3 = cold1;
     loc_prev = loc_cur;
     prev_in = cur_in;
+    mirror_prev = is_mirror(base_index, cur_in);
     cur0 = next0;
     cur1 = next1;
     cur1.y = next_in ? next1.y : __longlong_as_double((long long)BL_DEAD_RAY);

@@ -153,14 +153,15 @@ __global__ void __launch_bounds__(256) bl_transfer_kernel(BlTransferArgs P) {
   // One lane per (ray, frequency): consecutive lanes are the frequencies of one ray, whose records of a
   // sample are contiguous, so multi-frequency loads coalesce and the parallelism grows with n_nu.
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int slot = (int)(t / P.n_nu);
+  int slot = (int)(t / P.n_nu);
   const int l = (int)(t % P.n_nu);
+  const bool mirror = bl_mirror_slot(P, &slot);
   unsigned long long samples = 0ull, flagged = 0ull;
   int max_num = 0;
   if (slot < bl_rays_done(P.counters, P.chunk_rays)) {
     int num = P.ray_sample_num[slot];
     bool flag = P.ray_flags[slot] != 0;
-    long long out_index = P.ray_out_index[slot];
+    long long out_index = mirror ? P.mirror_out_index[slot] : P.ray_out_index[slot];
     if (l == 0) {
       const int all = num + (P.ray_skipped != nullptr ? P.ray_skipped[slot] : 0);   // the ray's samples, with or without a record
       samples = (unsigned long long)all;
@@ -179,7 +180,7 @@ __global__ void __launch_bounds__(256) bl_transfer_kernel(BlTransferArgs P) {
         bool nan_row = P.model_type == BL_MODEL_SIMULATION || l == 0;
         intensity = (num > 0 && nan_row) ? nan : 0.0;
       } else {
-        const double2 *rec = P.transfer + (size_t)P.ray_offset[slot] * P.n_nu + l;
+        const double2 *rec = P.transfer + (size_t)(P.ray_offset[slot] + (mirror ? P.row_add : 0ll)) * P.n_nu + l;
         // reference sample order is reversed integration order (geodesics.cpp:832-840). The
         // recurrence is sequential but the loads are not: fetch 8 records (one 128-byte line of
         // this ray's row when n_nu = 1) at a time so 8 loads are in flight per lane.
@@ -426,14 +427,15 @@ __global__ void __launch_bounds__(256) bl_transfer_quad_kernel(BlTransferArgs P)
   constexpr int kLanes = 4, kShift = 2;
   constexpr int kBatch = 8;   // records per lane in flight
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int slot = (int)(t >> kShift);
+  int slot = (int)(t >> kShift);
   const int q = (int)(t & (kLanes - 1));
+  const bool mirror = bl_mirror_slot(P, &slot);
   unsigned long long samples = 0ull, flagged = 0ull;
   int max_num = 0;
   if (slot < bl_rays_done(P.counters, P.chunk_rays)) {
     const int num = P.ray_sample_num[slot];
     const bool flag = P.ray_flags[slot] != 0;
-    const long long out_index = P.ray_out_index[slot];
+    const long long out_index = mirror ? P.mirror_out_index[slot] : P.ray_out_index[slot];
     const int all = num + (P.ray_skipped != nullptr ? P.ray_skipped[slot] : 0);
     if (q == 0) {
       samples = (unsigned long long)all;
@@ -446,7 +448,7 @@ __global__ void __launch_bounds__(256) bl_transfer_quad_kernel(BlTransferArgs P)
     if (P.fallback_nan && flag) {
       intensity = num > 0 ? __longlong_as_double(0x7ff8000000000000ll) : 0.0;   // simulation_sampling.cpp:211-216
     } else {
-      const double2 *rec = P.transfer + (size_t)P.ray_offset[slot];
+      const double2 *rec = P.transfer + (size_t)(P.ray_offset[slot] + (mirror ? P.row_add : 0ll));
       for (int top = num - 1; top >= 0; top -= kLanes * kBatch) {   // far -> near (geodesics.cpp:832-840)
         double2 m[kBatch];
 #pragma unroll
@@ -496,13 +498,14 @@ __global__ void __launch_bounds__(256) bl_transfer_quad_kernel(BlTransferArgs P)
 // about a seventh of the per-sample records, already composed by the coefficient kernel. A row that stands for per-sample
 // records (BL_COMPOSED_EXPANDED: its wave held a sample for the exact kernel or a thick step) is replayed from those.
 __global__ void __launch_bounds__(256) bl_transfer_composed_kernel(BlTransferArgs P) {
-  const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+  int slot = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool mirror = bl_mirror_slot(P, &slot);
   unsigned long long samples = 0ull, flagged = 0ull;
   int max_num = 0;
   if (slot < bl_rays_done(P.counters, P.chunk_rays)) {
     const int num = P.ray_sample_num[slot];
     const bool flag = P.ray_flags[slot] != 0;
-    const long long out_index = P.ray_out_index[slot];
+    const long long out_index = mirror ? P.mirror_out_index[slot] : P.ray_out_index[slot];
     const int all = num + (P.ray_skipped != nullptr ? P.ray_skipped[slot] : 0);   // the ray's samples, with or without a record
     samples = (unsigned long long)all;
     flagged = flag ? 1ull : 0ull;
@@ -514,7 +517,7 @@ __global__ void __launch_bounds__(256) bl_transfer_composed_kernel(BlTransferArg
     if (P.fallback_nan && flag) {
       intensity = num > 0 ? nan : 0.0;   // every sample of a flagged ray carries NaN primitives (simulation_sampling.cpp:211-216)
     } else {
-      const double2 *rows = P.composed + (size_t)P.ray_offset[slot];
+      const double2 *rows = P.composed + (size_t)(P.ray_offset[slot] + (mirror ? P.row_add : 0ll));
       auto apply = [&](const double2 map) {
         if (__builtin_expect(BL_COMPOSED_EXPANDED(map.x), 0)) {
           const int length = (int)(-map.x);
@@ -582,6 +585,11 @@ extern "C" hipError_t bl_launch_transfer(const BlTransferArgs *args, const Kerne
       break;
   }
   if (plan.affine != (args->affine != 0)) return hipErrorInvalidValue;
+  if (args->mirror_rays > 0) {   // mirror pairs: the three kernels that know them, a second set of lanes for the mirror pixels
+    if ((plan.kind != Transfer::kComposed && plan.kind != Transfer::kQuad && plan.kind != Transfer::kLane) || args->mirror_rays != args->chunk_rays
+        || args->mirror_out_index == nullptr) return hipErrorInvalidValue;
+    lanes *= 2;
+  }
   hipLaunchKernelGGL(kernel, dim3((unsigned int)((lanes + block - 1) / block)), dim3(block), 0, stream, *args);
   return hipGetLastError();
 }

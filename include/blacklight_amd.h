@@ -370,7 +370,11 @@ typedef struct bl_render_desc {
 typedef struct bl_stats {
   int64_t n_rays;             /* rays traced by the last bl_render                                 */
   int64_t n_samples;          /* kept samples (sum of sample_num)                                  */
-  int64_t n_samples_emitted;  /* samples written by the geodesic kernel (before truncation)        */
+  int64_t n_samples_emitted;  /* sample records the geodesic kernel wrote (before truncation; a paired render's count twice: the
+                                 whole frame's). The records themselves, the same from launch to launch - not the record slots its
+                                 waves took, which count every wave's partly filled last block of 1 024 as well and which this
+                                 field reported before mirror pairs (up to a block per wave more; still so where the records come
+                                 from a geodesic checkpoint). A scratch limit sized from it wants that margin on top.             */
   int64_t n_gathers;          /* S_in: samples that read the grid (8 var x 8 corners, or x1)        */
   int64_t n_flagged;          /* rays with sample_flags set                                        */
   int32_t max_sample_num;     /* geodesic_num_steps                                                */
@@ -384,6 +388,9 @@ typedef struct bl_stats {
                                  kernel of one chunk overlaps the shading of the previous one          */
   int32_t launches_locate;
   int32_t arithmetic;         /* BL_ARITH_EXACT or BL_ARITH_TOLERANT: the tier the last bl_render ran in          */
+  int32_t mirror_pairs;       /* 1: only the left half of the frame was traced and every sample record shaded for its pixel and for the
+                                 mirror pixel (zero spin, camera in the mirror plane; BL_SWITCH_NO_MIRROR_PAIRS: 0). In the four bytes
+                                 that were padding in front of n_deferred: no other member moves, n_cameras stays the last one.       */
   int64_t n_deferred;         /* tolerant tier: samples whose cut decision was left to the exact kernel           */
   int64_t n_undefined;        /* BL_UNDEFINED_EDGE: samples where the reference reads past its arrays (edge cell used)     */
   uint32_t switches;          /* BL_SWITCH_* bits active in this context (measurement switches, below); 0 in production  */
@@ -429,7 +436,9 @@ typedef struct bl_stats {
                                                                angles relative to the cell centre apply (bl_stats.local_angles)     */
 #define BL_SWITCH_GENERAL_CUTS (1u << 14)                   /* tolerant coefficient kernel: the general block of cell cuts where
                                                                cut_sigma_max is the only active threshold (its short form)         */
-/* (Eleven switches. Rounds 3 - 5 had eight more for experiments the measurements buried - a second pre-fused2 kernel, pre-gathered
+#define BL_SWITCH_NO_MIRROR_PAIRS (1u << 15)                /* every ray of the frame traced where one ray per mirror pair applies
+                                                               (bl_stats.mirror_pairs)                                              */
+/* (Twelve switches. Rounds 3 - 5 had eight more for experiments the measurements buried - a second pre-fused2 kernel, pre-gathered
  * cell bricks, the coefficient kernel beside a chunk's last rays, repacked tails - and for what bl_set_tail_policy now says; their
  * numbers are in docs/notebook.md, their code in the history.) */
 
