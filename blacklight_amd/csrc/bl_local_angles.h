@@ -81,6 +81,21 @@ __device__ __forceinline__ double rsqrt1(double x) {
 struct Direction {
   double cos_th, sin_th, cos_ph, sin_ph;
 };
+// (phi's half alone: with zero spin it takes nothing but x and y, and under y -> -y its cosine keeps its bits and its sine changes
+// the sign bit - rho2's y * y does not see the sign, and neither does the rounding of y * rho_inv)
+template <bool kSpinZero>
+__device__ __forceinline__ void direction_phi(double a, double r, double x, double y, double *sin_ph, double *cos_ph) {
+  const double rho2 = __builtin_fma(x, x, y * y);
+  if (kSpinZero) {
+    const double rho_inv = rsqrt1(rho2);
+    *sin_ph = y * rho_inv;
+    *cos_ph = x * rho_inv;
+  } else {
+    const double q = rsqrt1(rho2 * __builtin_fma(r, r, a * a));
+    *sin_ph = __builtin_fma(y, r, -(x * a)) * q;
+    *cos_ph = __builtin_fma(x, r, y * a) * q;
+  }
+}
 template <bool kSpinZero>
 __device__ __forceinline__ Direction direction(double a, double r, double r_inv, double x, double y, double z) {
   Direction u;
@@ -92,16 +107,7 @@ __device__ __forceinline__ Direction direction(double a, double r, double r_inv,
   const double ac = __builtin_fabs(c);
   const double w = __builtin_fmax((1.0 - ac) * (1.0 + ac), 0x1p-1000);   // (on the axis: theta = 1e-151, closer to the face than any band)
   u.sin_th = w * rsqrt1(w);
-  const double rho2 = __builtin_fma(x, x, y * y);
-  if (kSpinZero) {
-    const double rho_inv = rsqrt1(rho2);
-    u.sin_ph = y * rho_inv;
-    u.cos_ph = x * rho_inv;
-  } else {
-    const double q = rsqrt1(rho2 * __builtin_fma(r, r, a * a));
-    u.sin_ph = __builtin_fma(y, r, -(x * a)) * q;
-    u.cos_ph = __builtin_fma(x, r, y * a) * q;
-  }
+  direction_phi<kSpinZero>(a, r, x, y, &u.sin_ph, &u.cos_ph);
   return u;
 }
 

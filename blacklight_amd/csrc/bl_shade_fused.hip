@@ -198,6 +198,11 @@ struct Located {
   double f_i, f_j, f_k;
   uint32_t status;        // kSample... | kPlainUndecided
   uint32_t cell_bytes;    // byte offset of cell (k_m, j_m, i_m) in the cell array; 0 without a cell to read
+  // What the sample's mirror image in y = 0 takes over instead of working it out again (locate_mirror): functions of r and
+  // theta alone, which are even in y bit for bit. (Read by the paired walk only; in every other instantiation they are never computed.)
+  double m_even;          // theta's margin: its distance to the nearest face - and, with global angles, to the centre - of its cell
+  uint32_t cell_ij;       // j_m n_i + i_m: the cell's index without its phi plane
+  bool r_decided;         // the radial cell is confirmed (m_i > 0)
 };
 
 // What the loop keeps of the grid in scalar registers
@@ -403,6 +408,51 @@ __device__ __forceinline__ void axis_lookup(uint32_t row_addr, double s, double 
   *centre_margin = __builtin_fabs(s - xv);
 }
 
+// ---- phi's share of the locate step, and the step's last lines: what locate() and locate_mirror() both run
+// Local angles: phi's cell guessed from its sine and cosine (guess_x0, guess_inv_w: BlGridDevice::angle_guess[2], [3]), then fraction,
+// anchor shift and margin relative to the centre of that cell
+__device__ __forceinline__ void phi_local(const GridScalars &G, double sin_ph, double cos_ph, float guess_x0, float guess_inv_w, int *gk, double *f_k, uint32_t *dk,
+                                          double *m_k) {
+  const float ph_guess = local_angles::angle_guess<true>((float)sin_ph, (float)cos_ph);
+  int g = (int)((ph_guess - guess_x0) * guess_inv_w);
+  g = g < 0 ? 0 : (g > G.n_k1 ? G.n_k1 : g);
+  const local_angles::AngleRow row_k = read_angle_row(G.lds_ph + ((uint32_t)g << 6));
+  local_angles::lookup(row_k, local_angles::offset_from_centre(sin_ph, cos_ph, row_k.cos_c, row_k.sin_c), f_k, dk, m_k);
+  *gk = g;
+}
+// Global angles: phi itself, wrapped to [0, 2 pi) as the exact tier wraps it, with what it was before each wrap (the seam margins)
+struct PhiAngle {
+  double ph, unwrapped, once;
+  double two_pi;   // (the constant as a scalar operand, made where it is first used and handed on: KS)
+};
+template <bool kSpinZero>
+__device__ __forceinline__ PhiAngle phi_global(const BlSpacetime &st, double r, double x, double y) {
+  PhiAngle a;
+  double ph = kSpinZero ? atan2_k(y, x) : atan2_k(y, x) - atan2_k(st.bh_a, r);
+  a.unwrapped = ph;
+  const double two_pi = KS(2.0 * kPi);
+  a.two_pi = two_pi;
+  ph += ph < 0.0 ? two_pi : 0.0;
+  a.once = ph;
+  ph -= ph >= two_pi ? two_pi : 0.0;
+  a.ph = ph;
+  return a;
+}
+// The located sample from its parts. what: kSample...; cell: the anchor's index (k_m n_j + j_m) n_i + i_m; cell_ij: j_m n_i + i_m
+__device__ __forceinline__ Located located(uint32_t what, bool sampled, bool undecided, double f_i, double f_j, double f_k, uint32_t cell, uint32_t cell_ij,
+                                           uint32_t block_bytes, double m_even, bool r_decided) {
+  Located out;
+  out.f_i = f_i;
+  out.f_j = f_j;
+  out.f_k = f_k;
+  out.cell_bytes = sampled ? (cell << 5) + block_bytes : 0u;
+  out.status = what | (undecided ? kPlainUndecided : 0u);
+  out.m_even = m_even;
+  out.cell_ij = cell_ij;
+  out.r_decided = r_decided;
+  return out;
+}
+
 // The locate step (locate_plain_sample_tolerant's results; bl_sampling_fast.h) for the grids this kernel takes
 // kRefined: mesh with refinement - the sample's box of the block lattice is guessed like a cell, the box's descriptor names the block's
 // three rows, and the cell is guessed and confirmed in those. A wrong box names a block whose rows do not hold the coordinate: the
@@ -440,7 +490,7 @@ __device__ __forceinline__ Located locate(const BlSpacetime &st, const GridScala
   const bool off_grid = r < G.r_in || r > G.r_out;                 // :352-394 (theta and phi cover the sphere)
   const float log2_r = __builtin_amdgcn_logf((float)r);
   int gi, gj, gk;
-  double f_i, f_j, f_k, m_i, c_i, m;
+  double f_i, f_j, f_k, m_i, c_i, m, m_even;
   uint32_t di, dj, dk, block_bytes = 0u;
   bool beyond_the_block = false;
   bool take = local;
@@ -452,25 +502,23 @@ __device__ __forceinline__ Located locate(const BlSpacetime &st, const GridScala
   if (!kRefined && kAngles != kAnglesGlobal && take) {
     const local_angles::Direction u = local_angles::direction<kSpinZero>(st.bh_a, r, r_inv, x, y, z);
     const float th_guess = local_angles::angle_guess<false>((float)u.sin_th, (float)u.cos_th);
-    const float ph_guess = local_angles::angle_guess<true>((float)u.sin_ph, (float)u.cos_ph);
     gi = (int)((log2_r - G.r_l0) * G.r_linv);
     KernArgs args = kernargs();   // (the guess's origin and cells per radian: read here, not held across the loop)
     gj = (int)((th_guess - args->grid.angle_guess[0]) * args->grid.angle_guess[1]);
-    gk = (int)((ph_guess - args->grid.angle_guess[2]) * args->grid.angle_guess[3]);
     gi = gi < 0 ? 0 : (gi > G.n_i1 ? G.n_i1 : gi);
     gj = gj < 0 ? 0 : (gj > G.n_j1 ? G.n_j1 : gj);
-    gk = gk < 0 ? 0 : (gk > G.n_k1 ? G.n_k1 : gk);
-    const local_angles::AngleRow row_j = read_angle_row(G.lds_th + ((uint32_t)gj << 6)), row_k = read_angle_row(G.lds_ph + ((uint32_t)gk << 6));
-    axis_lookup(G.lds_r + ((uint32_t)gi << 6), r, &f_i, &di, &m_i, &c_i);
+    const local_angles::AngleRow row_j = read_angle_row(G.lds_th + ((uint32_t)gj << 6));
     double m_j, m_k;
+    phi_local(G, u.sin_ph, u.cos_ph, args->grid.angle_guess[2], args->grid.angle_guess[3], &gk, &f_k, &dk, &m_k);
+    axis_lookup(G.lds_r + ((uint32_t)gi << 6), r, &f_i, &di, &m_i, &c_i);
     local_angles::lookup(row_j, local_angles::offset_from_centre(u.sin_th, u.cos_th, row_j.cos_c, row_j.sin_c), &f_j, &dj, &m_j);
-    local_angles::lookup(row_k, local_angles::offset_from_centre(u.sin_ph, u.cos_ph, row_k.cos_c, row_k.sin_c), &f_k, &dk, &m_k);
+    m_even = m_j;
     m = m_j < m_k ? m_j : m_k;   // (on the polar axis phi is NaN: the comparison is false and m is NaN, which no band lets pass)
   } else if (kAngles == kAnglesLocal || (kAngles == kAnglesGlobal && !kRefined && !take)) {   // (never taken)
     gi = gj = gk = 0;
     di = dj = dk = 0u;
     f_i = f_j = f_k = m_i = c_i = 0.0;
-    m = __longlong_as_double(0x7ff8000000000000ll);
+    m = m_even = __longlong_as_double(0x7ff8000000000000ll);
   } else {
     // ConvertFromCKS (radiation_geometry.cpp:37-57) with the tier's inverse trigonometric functions
     // (cos theta = z / r: the product with the reciprocal, corrected once by its residual, is the correctly rounded quotient - the
@@ -478,12 +526,8 @@ __device__ __forceinline__ Located locate(const BlSpacetime &st, const GridScala
     double cth = z * r_inv;
     cth = __builtin_fma(__builtin_fma(-r, cth, z), r_inv, cth);
     const double th = acos_k(cth);
-    double ph = kSpinZero ? atan2_k(y, x) : atan2_k(y, x) - atan2_k(st.bh_a, r);
-    const double ph_unwrapped = ph;
-    const double two_pi = KS(2.0 * kPi);
-    ph += ph < 0.0 ? two_pi : 0.0;
-    const double ph_once = ph;
-    ph -= ph >= two_pi ? two_pi : 0.0;
+    const PhiAngle angle = phi_global<kSpinZero>(st, r, x, y);
+    const double ph = angle.ph;
     // guessed cells
     uint32_t rows_r = G.lds_r, rows_th = G.lds_th, rows_ph = G.lds_ph;
     if (kRefined) {
@@ -525,23 +569,61 @@ __device__ __forceinline__ Located locate(const BlSpacetime &st, const GridScala
     m = m_j < m_k ? m_j : m_k;
     m = m < c_j ? m : c_j;
     m = m < c_k ? m : c_k;
-    const double e0 = __builtin_fabs(ph_unwrapped), e1 = __builtin_fabs(ph_once - two_pi);
+    const double e0 = __builtin_fabs(angle.unwrapped), e1 = __builtin_fabs(angle.once - angle.two_pi);
     m = m < e0 ? m : e0;
     m = m < e1 ? m : e1;
+    m_even = m_j < c_j ? m_j : c_j;
   }
   // r is the exact tier's r: its cell is confirmed exactly (first c with xf[c + 1] >= r: xf[c] < r <= xf[c + 1]; m_i is
   // min(r - xf[c], xf[c + 1] - r)) - except on a face itself, where the signed minimum is zero either way: left to the exact pass
   const bool sampled = live && !cut && !off_grid;
-  const bool undecided = sampled && (!(m > band) || !(m_i > 0.0) || beyond_the_block);
-  Located out;
-  out.f_i = f_i;
-  out.f_j = f_j;
-  out.f_k = f_k;
+  const bool r_decided = m_i > 0.0;
+  const bool undecided = sampled && (!(m > band) || !r_decided || beyond_the_block);
+  const uint32_t what = !live ? (uint32_t)kSampleNone : (cut ? (uint32_t)kSampleCut : (off_grid ? (uint32_t)kSampleOffGrid : (uint32_t)kSampleInterp));
   const uint32_t cell = __umul24(__umul24((uint32_t)gk - dk, G.n_j) + ((uint32_t)gj - dj), G.n_i) + ((uint32_t)gi - di);
-  out.cell_bytes = sampled ? (cell << 5) + block_bytes : 0u;
-  out.status = (!live ? (uint32_t)kSampleNone : (cut ? (uint32_t)kSampleCut : (off_grid ? (uint32_t)kSampleOffGrid : (uint32_t)kSampleInterp)))
-      | (undecided ? kPlainUndecided : 0u);
-  return out;
+  return located(what, sampled, undecided, f_i, f_j, f_k, cell, __umul24((uint32_t)gj - dj, G.n_i) + ((uint32_t)gi - di), block_bytes, m_even, r_decided);
+}
+
+// The locate step for the mirror image in y = 0 of a sample already located (`plain`; zero spin, one block: the paired walk of
+// bl_shade_fused2_kernel). r and theta are even in y, and so are their cells, fractions and margins and the sample's status: they are the
+// plain sample's. phi is looked up as locate() looks it up, through the table, from (x, -y) - the caller hands in y with its sign bit
+// flipped - and not reflected: the cell, the fraction and the decision are those of locating (x, -y, z) from scratch, whatever the phi
+// faces are (DESIGN.md 5d has the argument value by value).
+template <int kAngles>
+__device__ __forceinline__ Located locate_mirror(const BlSpacetime &st, const GridScalars &G, double band, const Located &plain, double x, double y) {
+  static_assert(kAngles == kAnglesLocal || kAngles == kAnglesGlobal, "the loops' paths: the prologue locates no mirror sample");
+  const uint32_t what = plain.status & 0xffu;
+  const bool live = what != (uint32_t)kSampleNone, sampled = what == (uint32_t)kSampleInterp;
+  x = live ? x : 1.0;
+  y = live ? y : -1.0;
+  int gk;
+  double f_k, m_k, m;
+  uint32_t dk;
+  if (kAngles == kAnglesLocal) {
+    double sin_ph, cos_ph;
+    local_angles::direction_phi<true>(0.0, 0.0, x, y, &sin_ph, &cos_ph);
+    KernArgs args = kernargs();
+    phi_local(G, sin_ph, cos_ph, args->grid.angle_guess[2], args->grid.angle_guess[3], &gk, &f_k, &dk, &m_k);
+    m = plain.m_even < m_k ? plain.m_even : m_k;
+  } else {
+    const PhiAngle angle = phi_global<true>(st, 0.0, x, y);
+    gk = (int)((angle.ph - G.ph_x0) * G.ph_inv_w);
+    gk = gk < 0 ? 0 : (gk > G.n_k1 ? G.n_k1 : gk);
+    double c_k;
+    axis_lookup(G.lds_ph + ((uint32_t)gk << 6), angle.ph, &f_k, &dk, &m_k, &c_k);
+    // (locate()'s minima with theta's two as one. No NaN on this path - acos_k and atan2_k give none for finite arguments - so the order
+    // of the minima does not matter to the one comparison the result meets. Written out in both places: as a function of its own the
+    // six lines cost the instantiations over a mesh with refinement 132 bytes of scratch a lane)
+    m = plain.m_even < m_k ? plain.m_even : m_k;
+    m = m < c_k ? m : c_k;
+    const double e0 = __builtin_fabs(angle.unwrapped), e1 = __builtin_fabs(angle.once - angle.two_pi);
+    m = m < e0 ? m : e0;
+    m = m < e1 ? m : e1;
+  }
+  const bool undecided = sampled && (!(m > band) || !plain.r_decided);
+  // ((k_m n_j + j_m) n_i + i_m with the plain sample's j_m n_i + i_m: the same integer - k_m n_j is below 2^24 as k_m n_j + j_m is)
+  const uint32_t cell = __umul24(__umul24((uint32_t)gk - dk, G.n_j), G.n_i) + plain.cell_ij;
+  return located(what, sampled, undecided, plain.f_i, plain.f_j, f_k, cell, plain.cell_ij, 0u, plain.m_even, plain.r_decided);
 }
 
 // The eight corner cells of a located sample: sixteen 16-byte loads at 32-bit offsets from the scalar base pointer
@@ -616,16 +698,21 @@ __device__ __forceinline__ int cut_selection(int cut_mask, int general_cuts) {
 // sigma_bands (model_rows with sigma cuts in one pass, BlShadeArgs::n_sigma_bands; wave-uniform): the sigma upper cut is off here, the
 // row carries sigma for the transfer kernel's lanes to compare, and a sample whose sigma lies in the guard band of any of the
 // thresholds is undecided - the exact pass writes its row.
-template <bool kSpinZero, bool kFactors = false>
-__device__ __forceinline__ double2 shade(const BlSpacetime &st, const double (&K)[6], double freq, double freq_inv, double x_unit, int cut_mask,
-                                         uint32_t cut_table, const float pr[8], double x, double y, double z, double kx, double ky, double kz, double kt,
-                                         double momentum_factor, double delta_lambda, bool *have_out, bool *undecided_out, double2 (*factors)[4] = nullptr,
-                                         bool model_rows = false, int sigma_bands = 0, const double *sigma_band_lo = nullptr,
-                                         const double *sigma_band_hi = nullptr) {
+// shade() in two halves, split where the cell values first enter. What the first half works out of a sample's position and momentum
+// alone: the simulation metric there and k_i in the simulation's coordinates. With zero spin g_tph = g_rph = 0, g_thth = r^2 and
+// g_phph = pp2 = x^2 + y^2, and seven numbers are all of it: hh, g_rr, g_thth, g_phph, k_r, k_th, k_ph. Under the mirror in y = 0 (the sign
+// bits of y and k_y flipped) k_ph changes its sign bit and the other six keep their bits: the paired walk runs this half for
+// the plain sample and hands its results to the mirror sample.
+struct Geometry {
+  double hh, g_rr, g_thth, g_tph, g_rph, g_phph;   // 2 m r / Sigma; the metric's components (g_rr = 1 + hh, worked out beside hh: see below)
+  double k_r, k_th, k_ph;
+  double pp2;                                // x^2 + y^2: zero on the polar axis
+};
+template <bool kSpinZero>
+__device__ __forceinline__ Geometry shade_geometry(const BlSpacetime &st, double x, double y, double z, double kx, double ky, double kz, double kt) {
   const double bh_m = st.bh_m;
   const double bh_a = kSpinZero ? 0.0 : st.bh_a;
   const double a2 = bh_a * bh_a;
-  const double rho = pr[0], pgas = pr[1], uu1 = pr[2], uu2 = pr[3], uu3 = pr[4], bb1 = pr[5], bb2 = pr[6], bb3 = pr[7];
   // ---- Kerr-Schild scalars (radiation_geometry.cpp:18-25, :138-262)
   const double pp2 = x * x + y * y;
   const double rr2 = pp2 + z * z;
@@ -665,6 +752,31 @@ __device__ __forceinline__ double2 shade(const BlSpacetime &st, const double (&K
   const double g_tph = kSpinZero ? 0.0 : -hh * bh_a * sth2;
   const double g_rph = kSpinZero ? 0.0 : -g_rr * bh_a * sth2;
   const double g_phph = kSpinZero ? pp2 : (ra2 + hh * a2 * sth2) * sth2;
+  // ---- k_i in the simulation's coordinates (Jacobian of radiation_geometry.cpp:69-126)
+  const double sth_inv = rsqrt_k(sth2);
+  Geometry g;
+  g.hh = hh;
+  g.g_rr = g_rr;   // (here, not in the second half: hh is a product, and 1 + hh is contracted with it only where both stand in one basic block)
+  g.g_thth = g_thth;
+  g.g_tph = g_tph;
+  g.g_rph = g_rph;
+  g.g_phph = g_phph;
+  g.k_r = lk;
+  g.k_th = (lz * (x * kx + y * ky) - r * sth2 * kz) * sth_inv;
+  g.k_ph = x * ky - y * kx;
+  g.pp2 = pp2;
+  return g;
+}
+// The second half: the plasma's frame, the cuts, the coefficients and the transfer record, from the first half's results and the cell values
+template <bool kSpinZero, bool kFactors = false>
+__device__ __forceinline__ double2 shade_plasma(const double (&K)[6], double freq, double freq_inv, double x_unit, int cut_mask, uint32_t cut_table,
+                                                const float pr[8], const Geometry &geometry, double kt, double momentum_factor, double delta_lambda,
+                                                bool *have_out, bool *undecided_out, double2 (*factors)[4] = nullptr, bool model_rows = false,
+                                                int sigma_bands = 0, const double *sigma_band_lo = nullptr, const double *sigma_band_hi = nullptr) {
+  const double rho = pr[0], pgas = pr[1], uu1 = pr[2], uu2 = pr[3], uu3 = pr[4], bb1 = pr[5], bb2 = pr[6], bb3 = pr[7];
+  const double hh = geometry.hh, g_rr = geometry.g_rr, g_thth = geometry.g_thth, g_tph = kSpinZero ? 0.0 : geometry.g_tph;
+  const double g_rph = kSpinZero ? 0.0 : geometry.g_rph, g_phph = geometry.g_phph, pp2 = geometry.pp2;
+  const double k_r = geometry.k_r, k_th = geometry.k_th, k_ph = geometry.k_ph;
   // ---- u^mu from the normal-frame velocities (simulation_coefficients.cpp:297-313): u^t and 1 / u^t from one reciprocal square root
   const double u0n2 = 1.0 + g_rr * uu1 * uu1 + 2.0 * g_rph * uu1 * uu3 + g_thth * uu2 * uu2 + g_phph * uu3 * uu3;
   const double ut2 = u0n2 * g_rr;
@@ -681,11 +793,6 @@ __device__ __forceinline__ double2 shade(const BlSpacetime &st, const double (&K
   const double bph = (bb3 + bt * uu3) * ut_inv;
   const double bb_sq_lab = g_rr * bb1 * bb1 + 2.0 * g_rph * bb1 * bb3 + g_thth * bb2 * bb2 + g_phph * bb3 * bb3;
   const double b_sq = (bb_sq_lab + bt * bt) * ut_inv * ut_inv;
-  // ---- k_i in the simulation's coordinates (Jacobian of radiation_geometry.cpp:69-126)
-  const double sth_inv = rsqrt_k(sth2);
-  const double k_r = lk;
-  const double k_th = (lz * (x * kx + y * ky) - r * sth2 * kz) * sth_inv;
-  const double k_ph = x * ky - y * kx;
   const double k_u = kt * ut + k_r * ur + k_th * uu2 + k_ph * uu3;
   const double k_b = kt * bt + k_r * br + k_th * bth + k_ph * bph;
   // ---- plasma state (:274-358), constants folded on the host (BlShadeArgs::fast_k)
@@ -794,6 +901,17 @@ __device__ __forceinline__ double2 shade(const BlSpacetime &st, const double (&K
   }
   return rec;
 }
+// Both halves for one sample (every walk but the paired one)
+template <bool kSpinZero, bool kFactors = false>
+__device__ __forceinline__ double2 shade(const BlSpacetime &st, const double (&K)[6], double freq, double freq_inv, double x_unit, int cut_mask,
+                                         uint32_t cut_table, const float pr[8], double x, double y, double z, double kx, double ky, double kz, double kt,
+                                         double momentum_factor, double delta_lambda, bool *have_out, bool *undecided_out, double2 (*factors)[4] = nullptr,
+                                         bool model_rows = false, int sigma_bands = 0, const double *sigma_band_lo = nullptr,
+                                         const double *sigma_band_hi = nullptr) {
+  const Geometry geometry = shade_geometry<kSpinZero>(st, x, y, z, kx, ky, kz, kt);
+  return shade_plasma<kSpinZero, kFactors>(K, freq, freq_inv, x_unit, cut_mask, cut_table, pr, geometry, kt, momentum_factor, delta_lambda, have_out,
+                                           undecided_out, factors, model_rows, sigma_bands, sigma_band_lo, sigma_band_hi);
+}
 
 }  // namespace fused2
 
@@ -845,11 +963,13 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   if (n_records <= first_record) return;
   const uint32_t stride = gridDim.x * blockDim.x;
   const uint32_t last = n_records - 1u;
-  // Mirror pairs (BlShadeArgs::row_add != 0): the record indices walked are [0, 2 n_records). A wave whose first index is at or beyond
-  // n_records - a multiple of 64, so this is wave-uniform - shades record index - n_records as the ray's mirror image in y = 0.
+  // Mirror pairs (BlShadeArgs::row_add != 0): the record indices walked are [0, 2 n_records), and index n_records + i - n_records is a
+  // multiple of 64, so a wave's 64 are of one kind - is record i shaded as its ray's mirror image in y = 0. Every group of 64 enters the
+  // pipeline twice in succession, as it is and then as its mirror (walk_pair): the mirror entry is one stage behind the plain one and takes
+  // from its slot what the mirror does not change - the record, the per-ray constants, r and theta of the locate step, the geometry of
+  // shade() - so that it loads nothing but its cells and locates nothing but phi.
   // (Zero spin, one block, transfer records or composed maps: the instantiations a paired render launches. The others are compiled without it.)
   constexpr bool kPairs = kSpinZero && !kFactors && !kRefined;
-  const uint32_t n_virtual = (kPairs && P.row_add != 0u) ? 2u * n_records : n_records;
   const BlSpacetime st = P.st;
   const GridScalars G = kRefined ? grid_scalars_refined(P.grid, lds_base + 48u * 8u) : grid_scalars(P.grid, lds_base + 48u * 8u);
   const uint32_t cut_table = lds_base;
@@ -882,14 +1002,7 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   const uint32_t lane_bytes = lane_in_wave << 6;
   const uint32_t wave_offset = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * blockDim.x + (threadIdx.x & ~63u)));
   uint32_t base_index = first_record;   // record index of lane 0 of block 0 for the sample `next` ... (wave-uniform, grid-stride walk)
-  auto record_base = [&](uint32_t first) {
-    const uint32_t real = (kPairs && first >= n_records) ? first - n_records : first;
-    return records + ((size_t)(real < last ? real : last) << 6);
-  };
-  // (a mirror wave: the sign bit of y and of k_y flipped - wave-uniform mask; any other wave: the value as it is)
-  auto mirrored = [&](double value, uint32_t first) {
-    return kPairs ? __hiloint2double(__double2hiint(value) ^ (int)(first >= n_records ? 0x80000000u : 0u), __double2loint(value)) : value;
-  };
+  auto record_base = [&](uint32_t first) { return records + ((size_t)(first < last ? first : last) << 6); };   // (of a plain entry)
   // The list walk: batches of BL_XCD_BATCH groups claimed with one atomic on a list's cursor, lane b of `batch` holding group b.
   // The claim for the next batch is made when a batch begins and its groups are read one group later, so that neither the
   // atomic nor the read is waited for where it is used. A list that has nothing left passes the wave on to the next one.
@@ -908,27 +1021,17 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     // (what a claim found; past a list's end, claims on the next lists until one has groups left or all have been tried)
     unsigned long long at = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(claim >> 32), 0) << 32)
         | (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)claim, 0);
-    // (mirror pairs: a list of `plain` groups is walked twice - positions [plain, 2 plain) are its groups again, as mirror groups,
-    // n_records / 64 further on in the index space; the switch is read where it is used, not held across the loop)
-    const unsigned long long twice = (kPairs && kernargs()->row_add != 0u) ? 2ull : 1ull;
-    unsigned long long plain = P.xcd_state[BL_XCD_QUEUES + list];
-    unsigned long long length = plain * twice;
+    unsigned long long length = P.xcd_state[BL_XCD_QUEUES + list];
     while (at >= length && tried < BL_XCD_QUEUES - 1) {
       tried++;
       list = (list + 1) & (BL_XCD_QUEUES - 1);
       claim_issue();
       at = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(claim >> 32), 0) << 32)
           | (unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)claim, 0);
-      plain = P.xcd_state[BL_XCD_QUEUES + list];
-      length = plain * twice;
+      length = P.xcd_state[BL_XCD_QUEUES + list];
     }
     next_n = at < length ? (int)(length - at < (unsigned long long)BL_XCD_BATCH ? length - at : (unsigned long long)BL_XCD_BATCH) : 0;
-    {
-      const unsigned long long position = at + lane_in_wave;
-      const bool again = kPairs && position >= plain;
-      const uint32_t group = (int)lane_in_wave < next_n ? P.xcd_lists[(size_t)list * (size_t)P.xcd_list_capacity + (again ? position - plain : position)] : 0u;
-      next_batch = group + (again ? n_records >> 6 : 0u);
-    }
+    next_batch = (int)lane_in_wave < next_n ? P.xcd_lists[(size_t)list * (size_t)P.xcd_list_capacity + at + lane_in_wave] : 0u;
     claim_pending = false;
   };
   // the wave's first record for the next iteration's `next`
@@ -957,11 +1060,34 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   // with 46 copies an iteration (the compiler does not unroll a loop whose exit is a wave vote by itself).
   struct Slot {
     double2 h0, h1, c0, c1;   // the sample's record: x y | z (ray, row) | k_x k_y | k_z length
+                              // (a mirror entry: of these (ray, row) and length alone - its coordinates are the plain entry's, whose slot is
+                              // still there when it is located - and in the other six places and loc.m_even the geometry: keep_geometry)
     Located loc;
     double kt, factor;        // per-ray constants, requested with the cells
     long long row;
     uint32_t first;           // record of the wave's lane 0 (wave-uniform)
     bool in;
+  };
+  // shade()'s first half for a mirror entry, as the plain entry worked it out (k_ph with its sign changed), in the places of the
+  // record words a mirror entry has no use for: no register more than the record took
+  auto keep_geometry = [](Slot &s, const Geometry &g) __attribute__((always_inline)) {
+    s.h0 = make_double2(g.hh, g.g_thth);
+    s.h1.x = g.g_phph;
+    s.c0 = make_double2(g.k_r, g.k_th);
+    s.c1.x = -g.k_ph;
+    s.loc.m_even = g.g_rr;   // (theta's margin has served: nothing is mirrored twice)
+  };
+  auto kept_geometry = [](const Slot &s) __attribute__((always_inline)) {
+    Geometry g;
+    g.hh = s.h0.x;
+    g.g_thth = s.h0.y;
+    g.g_phph = g.pp2 = s.h1.x;
+    g.k_r = s.c0.x;
+    g.k_th = s.c0.y;
+    g.k_ph = s.c1.x;
+    g.g_rr = s.loc.m_even;
+    g.g_tph = g.g_rph = 0.0;
+    return g;
   };
   Slot s0, s1, s2;
   s0.h0 = s0.c0 = s0.c1 = make_double2(0.0, 0.0);
@@ -972,19 +1098,21 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
   s0.loc.f_i = s0.loc.f_j = s0.loc.f_k = 0.0;
   s0.loc.status = kSampleNone;
   s0.loc.cell_bytes = 0u;
+  s0.loc.m_even = 0.0;
+  s0.loc.cell_ij = 0u;
+  s0.loc.r_decided = false;
   s0.in = false;
   float4 lo[8], hi[8];
 #pragma unroll
   for (int c = 0; c < 8; c++) lo[c] = hi[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   // (32-bit record indices: the launcher keeps n_records + 3 strides below 2^32)
   s0.first = kNoRecords;
-  s1.first = walk_next();
-  s1.in = s1.first + lane_in_wave < n_virtual;
+  s1.first = walk_next();   // (a plain entry, whatever the walk)
+  s1.in = s1.first + lane_in_wave < n_records;
   {
     const double2 *rec = reinterpret_cast<const double2 *>(record_base(s1.first) + (size_t)(s1.in ? lane_bytes : 0u));
     s1.h0 = rec[0];
     s1.h1 = rec[1];
-    s1.h0.y = mirrored(s1.h0.y, s1.first);
     s1.h1.y = s1.in ? s1.h1.y : __longlong_as_double((long long)BL_DEAD_RAY);
   }
   s1.loc = locate<kSpinZero, kRefined>(st, G, camera_r, band, (uint32_t)__double_as_longlong(s1.h1.y) != BL_DEAD_RAY, s1.h0.x, s1.h0.y, s1.h1.x, local_angles);
@@ -1002,23 +1130,34 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     if (lane < count && at + lane < args->redo_capacity) args->redo_list[at + lane] = (unsigned long long)deferred_here[first + lane];
   };
   // kLocal (std::true_type / std::false_type): the angle path of the search, a constant of the loop the body is written into
-  auto iteration = [&](Slot &p, Slot &c, Slot &x, auto kLocal) __attribute__((always_inline)) {
+  // kWalk (an integral constant): which entries the three are, a constant of the body as well - kWalkPlain: all of them plain (every
+  // unpaired render); kWalkMirrorNext: `next` is the mirror entry of `cur`, which is plain, and `prev` a mirror entry; kWalkPlainNext:
+  // `next` is a group from the walk, `cur` the mirror entry of `prev`. In a paired walk the two alternate.
+  constexpr int kWalkPlain = 0, kWalkMirrorNext = 1, kWalkPlainNext = 2;
+  auto iteration = [&](Slot &p, Slot &c, Slot &x, auto kLocal, auto kWalkIs) __attribute__((always_inline)) {
+    constexpr int kWalk = decltype(kWalkIs)::value;
+    constexpr bool kMirrorNext = kWalk == kWalkMirrorNext, kMirrorCur = kWalk == kWalkPlainNext, kMirrorPrev = kWalk == kWalkMirrorNext;
     const uint32_t ray = (uint32_t)__double_as_longlong(p.h1.y);
     const bool live = ray != BL_DEAD_RAY;
     const uint32_t n = (uint32_t)(((unsigned long long)__double_as_longlong(p.h1.y)) >> 32);
     const uint32_t status = p.loc.status & 0xffu;
     const bool interp = status == (uint32_t)kSampleInterp;
     // the position record of `next`: the oldest request of the iteration, used at its end
-    x.first = walk_next();
-    x.in = x.first + lane_in_wave < n_virtual;
-    {
+    // (a mirror entry requests nothing: it is `cur`'s record, and all it keeps of it is the word with the ray and the row)
+    if constexpr (kMirrorNext) {
+      x.first = c.first < n_records ? c.first + n_records : c.first;   // (beyond the walk's end: kNoRecords, as `cur`)
+      x.in = c.in;
+      x.h1.y = c.h1.y;
+    } else {
+      x.first = walk_next();
+      x.in = x.first + lane_in_wave < n_records;
       const double2 *rec = reinterpret_cast<const double2 *>(record_base(x.first) + (size_t)(x.in ? lane_bytes : 0u));
       x.h0 = rec[0];
       x.h1 = rec[1];
     }
     const double kt = p.kt, momentum_factor = p.factor;
-    // (a mirror wave's rows: the second half of the per-sample row arrays)
-    const long long row_first = kPairs ? p.row + (long long)(p.first >= n_records ? P.row_add : 0u) : p.row;
+    // (a mirror entry's rows: the second half of the per-sample row arrays)
+    const long long row_first = kMirrorPrev ? p.row + (long long)P.row_add : p.row;
     float pr[8];
     const bool near_midpoint = trilinear(lo, hi, p.loc.f_i, p.loc.f_j, p.loc.f_k, pr);
     if (kFactors) {
@@ -1029,13 +1168,17 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     }
     gathers_wave += (unsigned long long)__popcll(__ballot(interp));
     fused2::gather_issue(cells, c.loc.cell_bytes, (c.loc.status & 0xffu) == (uint32_t)kSampleInterp, row_bytes, plane_bytes, lo, hi);
-    {
+    if constexpr (kMirrorCur) {
+      // (a mirror entry: the length and the per-ray constants are `prev`'s, the plain entry's; its momentum comes as geometry, below)
+      c.c1.y = p.c1.y;
+      c.kt = p.kt;
+      c.factor = p.factor;
+      c.row = p.row;
+    } else {
       const double2 *rec = reinterpret_cast<const double2 *>(record_base(c.first) + (size_t)(c.in ? lane_bytes : 0u));
       c.c0 = rec[2];
       c.c1 = rec[3];
-    }
-    // ... and its per-ray constants (random reads, one of 16 bytes and one of 8: a whole iteration ahead of their use, like the cells)
-    {
+      // ... and its per-ray constants (random reads, one of 16 bytes and one of 8: a whole iteration ahead of their use, like the cells)
       const uint32_t ray_cur = (uint32_t)__double_as_longlong(c.h1.y);
       const uint32_t ray_slot = ray_cur != BL_DEAD_RAY ? ray_cur : 0u;
       const double2 constants = bl_ray_constants(ray_constants, (size_t)ray_slot);
@@ -1051,10 +1194,24 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
     double2 rec = make_double2(1.0, 0.0);
     double2 factors[4];
     if (kFactors) factors[0] = factors[1] = factors[2] = factors[3] = make_double2(0.0, 0.0);
-    if (interp)
-      rec = shade<kSpinZero, kFactors>(st, K, freq, freq_inv, x_unit, cut_mask, cut_table, pr, p.h0.x, p.h0.y, p.h1.x, p.c0.x, mirrored(p.c0.y, p.first), p.c1.x, kt, momentum_factor,
-                                       -p.c1.y, &have, &undecided_cut, kFactors ? &factors : nullptr, kFactors && model_rows,
-                                       kFactors ? P.n_sigma_bands : 0, P.sigma_band_lo, P.sigma_band_hi);
+    if (interp) {
+      if constexpr (kWalk != kWalkPlain) {
+        // shade() in its halves: the first for a plain entry, which leaves the results with its mirror entry (`cur`, whose status is the
+        // same: what a lane skips here its mirror skips as well); the second for both
+        Geometry geometry;
+        if constexpr (kMirrorPrev) {
+          geometry = kept_geometry(p);
+        } else {
+          geometry = shade_geometry<kSpinZero>(st, p.h0.x, p.h0.y, p.h1.x, p.c0.x, p.c0.y, p.c1.x, kt);
+          keep_geometry(c, geometry);
+        }
+        rec = shade_plasma<kSpinZero, kFactors>(K, freq, freq_inv, x_unit, cut_mask, cut_table, pr, geometry, kt, momentum_factor, -p.c1.y, &have, &undecided_cut);
+      } else {
+        rec = shade<kSpinZero, kFactors>(st, K, freq, freq_inv, x_unit, cut_mask, cut_table, pr, p.h0.x, p.h0.y, p.h1.x, p.c0.x, p.c0.y, p.c1.x, kt, momentum_factor,
+                                         -p.c1.y, &have, &undecided_cut, kFactors ? &factors : nullptr, kFactors && model_rows,
+                                         kFactors ? P.n_sigma_bands : 0, P.sigma_band_lo, P.sigma_band_hi);
+      }
+    }
     // a sample off the grid has fallback primitives without a field (no coefficients: I <- I) or NaN ones (I <- I + NaN,
     // simulation_sampling.cpp:377-384); a cut sample has none either
     const bool defer = interp && (undecided_cut || near_midpoint || (p.loc.status & kPlainUndecided) != 0u);
@@ -1147,28 +1304,55 @@ __global__ void __launch_bounds__(kRefined ? 512 : 256, kRefined ? 1 : BL_FAST_W
       if (at < args->redo_capacity) args->redo_list[at] = (unsigned long long)(p.first + lane_in_wave);
     }
     // ---- the search for `next`
-    x.h0.y = mirrored(x.h0.y, x.first);
-    x.loc = locate<kSpinZero, kRefined, decltype(kLocal)::value ? kAnglesLocal : kAnglesGlobal>(st, G, camera_r, band, x.in && (uint32_t)__double_as_longlong(x.h1.y) != BL_DEAD_RAY,
-                                                                                               x.h0.x, x.h0.y, x.h1.x, local_angles);
+    // (a mirror entry: phi alone, from `cur`'s x and y with y's sign bit flipped; r and theta are `cur`'s)
+    constexpr int kAngles = decltype(kLocal)::value ? kAnglesLocal : kAnglesGlobal;
+    if constexpr (kMirrorNext)
+      x.loc = locate_mirror<kAngles>(st, G, band, c.loc, c.h0.x, -c.h0.y);
+    else
+      x.loc = locate<kSpinZero, kRefined, kAngles>(st, G, camera_r, band, x.in && (uint32_t)__double_as_longlong(x.h1.y) != BL_DEAD_RAY, x.h0.x, x.h0.y, x.h1.x, local_angles);
     x.h1.y = x.in ? x.h1.y : __longlong_as_double((long long)BL_DEAD_RAY);
   };
   // One loop per angle path, chosen here once (wave-uniform): a loop holds the instructions of the path its waves execute and
   // nothing of the other, which is 500 instructions less for the instruction cache to hold per three samples.
-  auto loop = [&](auto kLocal) __attribute__((always_inline)) {
+  // ... and, where a render may be paired, one more per path for the paired walk: plain and mirror entries alternate over the three roles,
+  // so its body is written out for the six combinations of roles and kinds. Written out and not branched on "this entry is a mirror":
+  // with wave-uniform branches in one body a slot's record words and the geometry kept in their places are both live wherever either
+  // may be, and the instantiation needs 340 to 400 bytes of scratch a lane; as constants of the body they cost no register.
+  auto loop = [&](auto kLocal, auto kPaired) __attribute__((always_inline)) {
+    constexpr int kFirst = decltype(kPaired)::value ? kWalkMirrorNext : kWalkPlain, kSecond = decltype(kPaired)::value ? kWalkPlainNext : kWalkPlain;
+    const std::integral_constant<int, kFirst> first;
+    const std::integral_constant<int, kSecond> second;
     for (;;) {
       if (!__any(s0.in || s1.in)) break;
-      iteration(s0, s1, s2, kLocal);
+      iteration(s0, s1, s2, kLocal, first);
       if (!__any(s1.in || s2.in)) break;
-      iteration(s1, s2, s0, kLocal);
+      iteration(s1, s2, s0, kLocal, second);
       if (!__any(s2.in || s0.in)) break;
-      iteration(s2, s0, s1, kLocal);
+      iteration(s2, s0, s1, kLocal, first);
+      if constexpr (decltype(kPaired)::value) {
+        if (!__any(s0.in || s1.in)) break;
+        iteration(s0, s1, s2, kLocal, second);
+        if (!__any(s1.in || s2.in)) break;
+        iteration(s1, s2, s0, kLocal, first);
+        if (!__any(s2.in || s0.in)) break;
+        iteration(s2, s0, s1, kLocal, second);
+      }
     }
   };
+  auto walk = [&](auto kLocal) __attribute__((always_inline)) {
+    if constexpr (kPairs) {
+      if (P.row_add != 0u) {
+        loop(kLocal, std::true_type{});
+        return;
+      }
+    }
+    loop(kLocal, std::false_type{});
+  };
 #if defined(BLV_ANGLES)
-  loop(std::integral_constant<bool, !kRefined && BLV_ANGLES == 1>{});
+  walk(std::integral_constant<bool, !kRefined && BLV_ANGLES == 1>{});
 #else
-  if (!kRefined && local_angles) loop(std::integral_constant<bool, !kRefined>{});
-  else loop(std::false_type{});
+  if (!kRefined && local_angles) walk(std::integral_constant<bool, !kRefined>{});
+  else walk(std::false_type{});
 #endif
   if (kRefined && n_deferred_here != 0u) hand_over_deferred(0u, n_deferred_here);
   if ((threadIdx.x & 63) == 0 && gathers_wave != 0ull) atomicAdd(&P.counters[BL_CNT_GATHERS], gathers_wave);
