@@ -130,6 +130,16 @@ class Stats(C.Structure):
         ("xcd_order", C.c_int32), ("local_angles", C.c_int32), ("n_cameras", C.c_int32),
     ]
 
+    @property
+    def n_mixes(self):
+        """bl_stats.n_mixes, the struct's last member: the int32 behind n_cameras, in what were the struct's four bytes of tail
+        padding - so the field list above, whose last entry the cameras' host test pins, and the struct's size stay as they are."""
+        return C.c_int32.from_buffer(self, Stats.N_MIXES_OFFSET).value
+
+
+Stats.N_MIXES_OFFSET = Stats.n_cameras.offset + 4
+assert Stats.N_MIXES_OFFSET + 4 <= C.sizeof(Stats)
+
 
 _lib = None
 
@@ -207,6 +217,9 @@ def lib():
     L.bl_polarized_variant_electrons.argtypes = [C.c_void_p, C.c_int, C.POINTER(ElectronMix)]
     L.bl_set_sigma_cuts.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.bl_num_sigma_cuts.argtypes = [C.c_void_p]
+    L.bl_set_electron_mixes.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.bl_num_electron_mixes.argtypes = [C.c_void_p]
+    L.bl_electron_mix_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.bl_host_alloc.argtypes = [C.c_void_p, C.c_size_t]
     L.bl_host_alloc.restype = C.c_void_p
     L.bl_host_free.argtypes = [C.c_void_p, C.c_void_p]

@@ -49,7 +49,7 @@ class Context:
 
     @property
     def num_variants(self):
-        """Images one render produces (bl_num_variants): models x units x sigma cuts, or polarized triples."""
+        """Images one render produces (bl_num_variants): electron mixes x models x units x sigma cuts, or polarized triples."""
         return self._lib.bl_num_variants(self._ctx)
 
     def _variants(self):
@@ -63,7 +63,7 @@ class Context:
 
     def variant_output_path(self, snapshot=0, variant=0, camera=0):
         """The file name write_output(variant=..., camera=...) uses without `path` (bl_camera_output_path): output_file, the file number
-        of a series, and in front of the extension a tag .mMMuUU (.mMMuUUsSS with sigma cuts set) / .vVV when the context renders
+        of a series, and in front of the extension a tag .mMMuUU (.mMMuUUsSS with sigma cuts set, .eEE in front with electron mixes set) / .vVV when the context renders
         several variants, with .cCC in front of it when it renders several cameras (image.c01m00u02.npz)."""
         buf = C.create_string_buffer(4096)
         self._check(self._lib.bl_camera_output_path(self._ctx, int(snapshot), int(camera), int(variant), buf, len(buf)))
@@ -286,6 +286,36 @@ class Context:
     @property
     def num_sigma_cuts(self):
         return self._lib.bl_num_sigma_cuts(self._ctx)
+
+    def set_electron_mixes(self, mixes):
+        """Render several electron distributions of an unpolarized run - thermal plus power-law mixes - in one render
+        (bl_set_electron_mixes): one mapping or a sequence of them with the keys power_frac, p, gamma_min, gamma_max; a missing key
+        takes the parameter block's value. An empty sequence clears them (the parameter block's mix again). The mixes are the
+        outermost axis of the image rows (render()["image_by_mix"]: (n_mixes, rows of one mix, n_rays)); geodesics stay resident."""
+        given = [mixes] if hasattr(mixes, "keys") else list(mixes)
+        own = self._block_electrons()
+        array = (_capi.ElectronMix * max(1, len(given)))()
+        for e, mapping in enumerate(given):
+            unknown = set(mapping) - set(_capi.ELECTRON_MIX_KEYS)
+            if unknown:
+                raise ValueError(f"set_electron_mixes: unknown electron key(s) {sorted(unknown)}; the keys are {list(_capi.ELECTRON_MIX_KEYS)}")
+            for key in _capi.ELECTRON_MIX_KEYS:
+                setattr(array[e], key, float(mapping.get(key, own[key])))
+        self._check(self._lib.bl_set_electron_mixes(self._ctx, len(given), C.cast(array, C.c_void_p)))
+
+    @property
+    def electron_mixes(self):
+        """The mixes set_electron_mixes() set (bl_electron_mix_get), one mapping each; [] when the parameter block's mix is rendered."""
+        out = []
+        for e in range(self.num_electron_mixes):
+            mix = _capi.ElectronMix()
+            self._check(self._lib.bl_electron_mix_get(self._ctx, e, C.byref(mix)))
+            out.append({key: getattr(mix, key) for key in _capi.ELECTRON_MIX_KEYS})
+        return out
+
+    @property
+    def num_electron_mixes(self):
+        return self._lib.bl_num_electron_mixes(self._ctx)
 
     def fit_density_unit(self, target_jy, distance_pc, lo, hi, frequency=0, rtol=1.0e-3, per_render=16):
         """The density unit (simulation_rho_cgs) in [lo, hi] at which the root image's total flux (flux.total_flux_jy) at image
@@ -693,10 +723,15 @@ class Context:
         n_models, n_units = max(1, self.num_electron_models), max(1, self.num_density_units)
         n_variants = max(1, self.num_polarized_variants)
         n_cuts = max(1, self.num_sigma_cuts)
-        return dict(image=image, image_by_model=image.reshape(n_models, n_q // n_models, n_rays),
+        # (electron mixes, the outermost axis: the three views below gain a leading axis of them while a list is set, and only then)
+        n_mixes = max(1, self.num_electron_mixes)
+        lead = (n_mixes,) if self.num_electron_mixes > 0 else ()
+        rows = n_q // n_mixes
+        return dict(image=image, image_by_model=image.reshape(lead + (n_models, rows // n_models, n_rays)),
                     image_by_variant=image.reshape(n_variants, n_q // n_variants, n_rays),
-                    image_by_unit=image.reshape(n_models, n_units, n_q // (n_models * n_units), n_rays),
-                    image_by_cut=image.reshape(n_models, n_units, n_cuts, n_q // (n_models * n_units * n_cuts), n_rays), sample_num=sample_num,
+                    image_by_unit=image.reshape(lead + (n_models, n_units, rows // (n_models * n_units), n_rays)),
+                    image_by_cut=image.reshape(lead + (n_models, n_units, n_cuts, rows // (n_models * n_units * n_cuts), n_rays)),
+                    image_by_mix=image.reshape(n_mixes, rows, n_rays), sample_num=sample_num,
                     sample_flags=sample_flags, camera_pos=camera_pos, camera_dir=camera_dir, rendering=rendering, stats=self.stats)
 
     # ------------------------------------------------------------------ host steps of the reference loop

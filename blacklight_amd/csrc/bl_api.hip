@@ -415,6 +415,27 @@ const char *CamerasRefusal(const bl_ctx *ctx, int n) {
   return nullptr;
 }
 
+// Why n electron mixes cannot be rendered by this context (nullptr: they can). bl_set_electron_mixes and bl_render's plan both ask.
+const char *ElectronMixesRefusal(const bl_ctx *ctx, int n, const bl_electron_mix *mix) {
+  const bl_params &p = ctx->params;
+  if (n <= 0) return nullptr;
+  if (p.model_type != BL_MODEL_SIMULATION) return "Electron mixes: formula mode has no electron distribution (model_type = formula).";
+  if (ctx->polarized)
+    return "Electron mixes: a polarized run takes its electron distributions with its variants (image_polarization = true): "
+           "bl_set_polarized_variants_electrons.";
+  if (p.slow_light_on) return "Electron mixes: slow light renders one electron mix (slow_light_on = true).";
+  for (int e = 0; e < n; e++)
+    if (mix[e].kappa_frac != 0.0)
+      return "Electron mixes: kappa-distribution electrons (kappa_frac != 0) in an unpolarized run - the reference's absorptivity reads "
+             "kappa_aa_high_i, which it only initialises for polarized runs: no defined result to reproduce.";
+  if (n >= 2 && p.adaptive_max_level > 0)
+    return "Electron mixes: adaptive refinement reads one image; n >= 2 mixes need adaptive_max_level = 0.";
+  if (n >= 2 && ctx->render_num_images > 0) return "Electron mixes: renderings come out once; n >= 2 mixes need render_num_images = 0.";
+  if (n >= 2 && p.checkpoint_geodesic_save) return "Electron mixes: a geodesic checkpoint is saved by a render of one image; n >= 2 mixes need checkpoint_geodesic_save = false.";
+  if (n >= 2 && p.checkpoint_sample_save) return "Electron mixes: a sample checkpoint is saved by a render of one image; n >= 2 mixes need checkpoint_sample_save = false.";
+  return nullptr;
+}
+
 // The variants of a render, in image-row order: the triples (each with its own cut_sigma_max where bl_set_polarized_variants_sigma gave
 // one, and its own electron mix where bl_set_polarized_variants_electrons gave one), else models x units x sigma cuts, model-major, then unit, then cut, with the parameter block's pair, unit and cut_sigma_max
 // where an axis is not set. The one reader of what the four setters stored.
@@ -423,15 +444,18 @@ Variants ResolveVariants(const bl_ctx *ctx) {
   const std::vector<Variant> own = {{p.plasma_rat_low, p.plasma_rat_high, p.simulation_rho_cgs, p.cut_sigma_max, BlockMix(p)}};
   const std::vector<double> own_cut = {p.cut_sigma_max};
   Variants v{ctx->triples, static_cast<int>(ctx->models.size()), static_cast<int>(ctx->units.size()), static_cast<int>(ctx->triples.size()),
-             static_cast<int>(ctx->sigma_cuts.size())};
+             static_cast<int>(ctx->sigma_cuts.size()), static_cast<int>(ctx->mixes.size())};
+  const std::vector<bl_electron_mix> own_mix = {BlockMix(p)};
   if (!ctx->triples_cut)
     for (Variant &triple : v.list) triple.sigma_max = p.cut_sigma_max;
   if (!ctx->triples_mix)
     for (Variant &triple : v.list) triple.mix = BlockMix(p);
+  // (an unpolarized run's electron mixes are the outermost axis: the rows of models x units x cuts repeat per mix)
   if (v.n_pol == 0)
-    for (const Variant &model : v.n_models > 0 ? ctx->models : own)
-      for (const Variant &unit : v.n_units > 0 ? ctx->units : own)
-        for (const double sigma_max : v.n_cuts > 0 ? ctx->sigma_cuts : own_cut) v.list.push_back({model.rat_low, model.rat_high, unit.rho, sigma_max, BlockMix(p)});
+    for (const bl_electron_mix &mix : v.n_mixes > 0 ? ctx->mixes : own_mix)
+      for (const Variant &model : v.n_models > 0 ? ctx->models : own)
+        for (const Variant &unit : v.n_units > 0 ? ctx->units : own)
+          for (const double sigma_max : v.n_cuts > 0 ? ctx->sigma_cuts : own_cut) v.list.push_back({model.rat_low, model.rat_high, unit.rho, sigma_max, mix});
   return v;
 }
 
@@ -533,6 +557,34 @@ Refused CheckSigmaCuts(const bl_ctx *ctx, int n, const double *sigma_max) {
   return std::nullopt;
 }
 void StoreSigmaCuts(bl_ctx *ctx, int n, const double *sigma_max) { ctx->sigma_cuts.assign(sigma_max, sigma_max + n); }
+
+// ... the electron mixes of an unpolarized run, checked as CheckPolarizedVariants checks a variant's mix (what is read must be finite; the
+// reference's two warnings, each once per call); a mix with kappa electrons is refused, not checked
+Refused CheckElectronMixes(const bl_ctx *ctx, int n, const bl_electron_mix *mix, std::vector<const char *> *warnings) {
+  if (n < 0 || n > BL_MAX_ELECTRON_MIXES || (n > 0 && mix == nullptr))
+    return Failure{BL_E_ARG, "bl_set_electron_mixes needs 0 <= n <= " + std::to_string(BL_MAX_ELECTRON_MIXES) + " and the array of mixes."};
+  bool warn_power = false, warn_thermal = false;
+  for (int e = 0; e < n; e++) {
+    const bl_electron_mix &m = mix[e];
+    const std::string which = "bl_set_electron_mixes: mix " + std::to_string(e);
+    if (!std::isfinite(m.power_frac)) return Failure{BL_E_ARG, which + " has a power_frac that is not finite."};
+    if (m.power_frac != 0.0) {
+      if (!std::isfinite(m.p)) return Failure{BL_E_ARG, which + " has a p that is not finite."};
+      if (!std::isfinite(m.gamma_min)) return Failure{BL_E_ARG, which + " has a gamma_min that is not finite."};
+      if (!std::isfinite(m.gamma_max)) return Failure{BL_E_ARG, which + " has a gamma_max that is not finite."};
+    }
+  }
+  if (const char *why = ElectronMixesRefusal(ctx, n, mix)) return Failure{BL_E_UNSUPPORTED, why};
+  for (int e = 0; e < n; e++) {
+    warn_power = warn_power || mix[e].power_frac < 0.0 || mix[e].power_frac > 1.0;
+    const double thermal_frac = ThermalFraction(mix[e]);
+    warn_thermal = warn_thermal || thermal_frac < 0.0 || thermal_frac > 1.0;
+  }
+  if (warn_power) warnings->push_back("Fraction of power-law electrons outside [0, 1].");
+  if (warn_thermal) warnings->push_back("Fraction of thermal electrons outside [0, 1].");
+  return std::nullopt;
+}
+void StoreElectronMixes(bl_ctx *ctx, int n, const bl_electron_mix *mix) { ctx->mixes.assign(mix, mix + n); }
 
 // ... the cameras, 0 <= n <= BL_MAX_CAMERAS; *list: the cameras with their frames. th_deg == nullptr: every camera at the parameter
 // block's own camera_th (its radians and its camera_pole, which no degree value need give back); ph_deg == nullptr: at the block's
@@ -1013,6 +1065,26 @@ int bl_set_sigma_cuts(bl_ctx *ctx, int n, const double *sigma_max) {
 }
 
 int bl_num_sigma_cuts(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->sigma_cuts.size()) : -1; }
+
+int bl_set_electron_mixes(bl_ctx *ctx, int n, const bl_electron_mix *mix) {
+  if (ctx == nullptr) return BL_E_ARG;
+  std::vector<const char *> warnings;
+  if (const Refused refused = CheckElectronMixes(ctx, n, mix, &warnings)) return Fail(ctx, *refused);
+  for (const char *warning : warnings) Warn(ctx, warning);
+  std::lock_guard<std::mutex> guard(ctx->render_lock);
+  StoreElectronMixes(ctx, n, mix);
+  return BL_OK;
+}
+
+int bl_num_electron_mixes(const bl_ctx *ctx) { return ctx != nullptr ? static_cast<int>(ctx->mixes.size()) : -1; }
+
+int bl_electron_mix_get(const bl_ctx *ctx, int e, bl_electron_mix *out) {
+  if (ctx == nullptr || out == nullptr) return BL_E_ARG;
+  const int n = static_cast<int>(ctx->mixes.size());
+  if (e < 0 || e >= std::max(1, n)) return BL_E_ARG;
+  *out = n > 0 ? ctx->mixes[e] : BlockMix(ctx->params);
+  return BL_OK;
+}
 
 int bl_set_cameras(bl_ctx *ctx, int n, const double *th_deg, const double *ph_deg) {
   if (ctx == nullptr) return BL_E_ARG;

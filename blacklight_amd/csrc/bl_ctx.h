@@ -132,9 +132,10 @@ struct Variant {
   double rat_low, rat_high, rho, sigma_max;
   bl_electron_mix mix;
 };
+// ... or, for an unpolarized one, the mix of the outermost axis (bl_set_electron_mixes): n_mixes of them, 0: the parameter block's.
 struct Variants {
   std::vector<Variant> list;
-  int n_models, n_units, n_pol, n_cuts;
+  int n_models, n_units, n_pol, n_cuts, n_mixes;
 };
 
 struct bl_ctx {
@@ -177,6 +178,8 @@ struct bl_ctx {
   bool triples_cut = false;          // the triples carry a cut_sigma_max each (bl_set_polarized_variants_sigma); else the parameter block's
   bool triples_mix = false;          // ... and an electron mix each (bl_set_polarized_variants_electrons); else the parameter block's
   std::vector<double> sigma_cuts;
+  std::vector<bl_electron_mix> mixes;   // bl_set_electron_mixes(): the outermost axis of an unpolarized run's variants; empty: the parameter block's mix
+  bool mix_runs = false;             // bl_render is rendering the list run by run (it holds a mix without a thermal part): a pass per variant
   // bl_set_cameras(): the viewing angles as given (degrees) and each camera's frame; empty: the parameter block's camera. `frame`
   // above is what a one-camera render starts its rays from - the block's own frame (block_frame), or the one camera of a list of
   // one, so that such a render plans and runs exactly as a context with those angles in its block; two cameras or more reach the
@@ -406,6 +409,7 @@ const char *DensityUnitsRefusal(const bl_ctx *ctx, int n);     // bl_set_density
 const char *PolarizedVariantsRefusal(const bl_ctx *ctx, int n);   // bl_set_polarized_variants (bl_api.hip)
 const char *SigmaCutsRefusal(const bl_ctx *ctx, int n);        // bl_set_sigma_cuts (bl_api.hip)
 const char *CamerasRefusal(const bl_ctx *ctx, int n);          // bl_set_cameras (bl_api.hip)
+const char *ElectronMixesRefusal(const bl_ctx *ctx, int n, const bl_electron_mix *mix);   // bl_set_electron_mixes (bl_api.hip)
 }  // namespace blhost
 
 #endif  // BLACKLIGHT_AMD_BL_CTX_H_

@@ -410,6 +410,9 @@ struct alignas(16) BlFreqInputs {
 // sigma > sigma_max[s]. The tolerant kernels leave a sample whose sigma lies in the guard band of any threshold to the exact pass
 // (BlShadeArgs::sigma_band_lo / _hi), whose row holds the exact tier's sigma.
 #define BL_TRANSFER_MAX_CUTS 16
+// ... and with electron mixes (BlTransferArgs::n_mixes): the coefficient kernels folded a thermal fraction of 1 into s_j, and the lane
+// applies its own mix - the thermal fraction on the thermal line, the power-law terms from the same row (bl_transfer_freq_kernel)
+#define BL_TRANSFER_MAX_MIXES 16
 #define BL_SHADE_MAX_SIGMA_CUTS 16
 
 // Polarized runs: what the per-frequency coefficient formulas need of a sample (simulation_coefficients.cpp:458-698),
@@ -611,6 +614,17 @@ struct BlTransferArgs {
   double x_unit, t_unit;
   const BlRenderDevice *render_params;   // device, or null
   double *render;                        // [n_images][3][n_rays_total], or null
+  // bl_transfer_freq_kernel, electron mixes in one pass (with n_models > 0; behind everything else: no older member moves). > 0: a lane
+  // per ray in a workgroup per (256 rays, mix, model, unit, cut, frequency) - what the lane needs of its channel is the workgroup's -
+  // row (((e n_models + m) n_units + u) n_cuts + s) n_nu + l; the rows hold a thermal fraction of 1. Mix e's tables, of what
+  // FillElectronConstants gives of it and of fast_k at the base unit with a thermal fraction of 1 (the rows' constants):
+  //   mix_thermal 1 - power_frac, mix_power_frac, mix_pw_e = -(p - 1) / 2,
+  //   mix_pw_j = power_frac power_jj e^2 k6 k7 / (c k5), mix_pw_a = power_frac power_aa e^2 k6 k7 / (m_e c h k5)
+  // (the last three 0 where power_frac == 0: p, power_jj and power_aa are not defined there), and power_k0 = 1 / (k4 k7).
+  int n_mixes;
+  double mix_thermal[BL_TRANSFER_MAX_MIXES], mix_power_frac[BL_TRANSFER_MAX_MIXES], mix_pw_e[BL_TRANSFER_MAX_MIXES];
+  double mix_pw_j[BL_TRANSFER_MAX_MIXES], mix_pw_a[BL_TRANSFER_MAX_MIXES];
+  double power_k0;
 };
 
 #if defined(__HIPCC__) || defined(__HIP__)

@@ -345,6 +345,8 @@ int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const i
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more sigma cuts (bl_set_sigma_cuts).");
   if (bl_num_cameras(ctx) >= 2)
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more cameras (bl_set_cameras).");
+  if (bl_num_electron_mixes(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more electron mixes (bl_set_electron_mixes).");
   const bl_params &p = *bl_internal_params(ctx);
   *n_refined = 0;
   if (p.adaptive_max_level <= 0 || level >= p.adaptive_max_level) {   // radiation_adaptive.cpp:22-23
@@ -434,10 +436,14 @@ int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, int camer
   } else if (bl_num_polarized_variants(ctx) >= 1) {
     std::snprintf(tag, sizeof tag, "v%02d", variant);
   } else {
-    // (variant = (m U + u) S + s; the cut's tag only where cuts are set: names without cuts are as ever)
-    const int n_units = std::max(1, bl_num_density_units(ctx)), n_cuts = bl_num_sigma_cuts(ctx), pair = variant / std::max(1, n_cuts);
-    if (n_cuts >= 1) std::snprintf(tag, sizeof tag, "m%02du%02ds%02d", pair / n_units, pair % n_units, variant % n_cuts);
-    else std::snprintf(tag, sizeof tag, "m%02du%02d", pair / n_units, pair % n_units);
+    // (variant = ((e M + m) U + u) S + s; the cut's tag only where cuts are set, the mix's - in front - only where mixes are: names
+    // without either are as ever)
+    const int n_mixes = bl_num_electron_mixes(ctx), per_mix = n_variants / std::max(1, n_mixes), inner = variant % per_mix;
+    const int n_units = std::max(1, bl_num_density_units(ctx)), n_cuts = bl_num_sigma_cuts(ctx), pair = inner / std::max(1, n_cuts);
+    char mix_tag[8] = "";
+    if (n_mixes >= 1) std::snprintf(mix_tag, sizeof mix_tag, "e%02d", variant / per_mix);
+    if (n_cuts >= 1) std::snprintf(tag, sizeof tag, "%sm%02du%02ds%02d", mix_tag, pair / n_units, pair % n_units, inner % n_cuts);
+    else std::snprintf(tag, sizeof tag, "%sm%02du%02d", mix_tag, pair / n_units, pair % n_units);
   }
   const std::string group = std::string(".") + camera_tag + tag;
   const std::string::size_type slash = path->find_last_of('/');
@@ -748,6 +754,8 @@ int bl_write_output(bl_ctx *ctx, const char *path_override, const bl_output_desc
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no variant axis (bl_set_polarized_variants with n >= 2).");
   if (bl_num_sigma_cuts(ctx) >= 2)
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no sigma-cut axis (bl_set_sigma_cuts with n >= 2).");
+  if (bl_num_electron_mixes(ctx) >= 2)
+    return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file layout has no electron-mix axis (bl_set_electron_mixes with n >= 2).");
   if (bl_num_cameras(ctx) >= 2)
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_write_output: the reference's file holds one camera (bl_set_cameras with n >= 2; bl_write_output_camera).");
   return WriteOutput(ctx, path_override, d, 0, 1);

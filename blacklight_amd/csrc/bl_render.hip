@@ -131,6 +131,11 @@ struct RenderJob {
   bl_electron_mix base_mix{};       // the electron mix BuildShadeArgs folds: the first variant's (the parameter block's where none is set;
                                     // one pass: what the frame-and-inputs kernel sees of it decides nothing - PlanJob; BindVariant each pass's)
   bool all_thermal = false;         // the parameter block and every variant have thermal electrons only (PlanJob): the kernels chosen for that
+  // What the plan asks of the electrons, over the render's variants where bl_set_electron_mixes set a list (PlanJob): some variant has
+  // a power law (the kernels that know power laws - a thermal variant goes through them with zero fractions), some has kappa
+  // electrons, every one has a thermal part. Without a list: the parameter block's plasma_power_frac != 0, plasma_kappa_frac != 0 and
+  // the context's thermal fraction != 0, as ever.
+  bool any_power = false, any_kappa = false, every_thermal = false;
   long long n_rays = 0, level_pixels = 0;
   int n_cameras = 1;          // cameras traced as one set of rays (bl_set_cameras): level_pixels = n_cameras x the camera's pixels
   bool camera_table = false;  // ... two or more: the ray-start kernel reads each ray's frame from BlTraceArgs::cameras
@@ -246,7 +251,8 @@ hipEvent_t *SlotEvents(RenderJob &job, int k) { return job.ctx->events.data() + 
 // A density unit (simulation_rho_cgs) and the electron model in pl.plasma_rat_low / _high into what the coefficient kernels read:
 // BlPlasmaDevice's units (simulation_coefficients.cpp:237-239) and the tolerant tier's constants fast_k. BuildShadeArgs folds the
 // render's, BindVariant each variant's - one arithmetic, so that a variant has the bits of a fresh render with that unit and pair.
-void FoldUnits(const bl_ctx *ctx, double rho_cgs, BlPlasmaDevice &pl, double (&fast_k)[8]) {
+// (thermal_frac: the thermal fraction of the electron mix the constants are for - MixThermal below; only fast_k[5] reads it)
+void FoldUnits(const bl_ctx *ctx, double rho_cgs, double thermal_frac, BlPlasmaDevice &pl, double (&fast_k)[8]) {
   const bl_params &p = ctx->params;
   pl.d_unit = rho_cgs;
   pl.e_unit = pl.d_unit * kC * kC;
@@ -262,7 +268,7 @@ void FoldUnits(const bl_ctx *ctx, double rho_cgs, BlPlasmaDevice &pl, double (&f
   fast_k[2] = pl.plasma_rat_low * g1;
   fast_k[3] = p.plasma_ne_ni * g2;
   fast_k[4] = (kMe * kC * kC) * (kMe * kC * kC) * 4.5 / nu_c_over_b;
-  fast_k[5] = ctx->plasma_thermal_frac * n_e_per_rho * kE * kE * nu_c_over_b / kC * (kSqrt2 * kPi / 27.0);
+  fast_k[5] = thermal_frac * n_e_per_rho * kE * kE * nu_c_over_b / kC * (kSqrt2 * kPi / 27.0);
   fast_k[6] = n_e_per_rho;
   fast_k[7] = nu_c_over_b;
 }
@@ -313,6 +319,9 @@ void BindElectronConstants(const ElectronConstants &ec, bool polarized, BlPlasma
 }
 bool SameMix(const bl_electron_mix &a, const bl_electron_mix &b) { return std::memcmp(&a, &b, sizeof a) == 0; }   // (as bits, like the cuts)
 bool ThermalOnly(const bl_electron_mix &mix) { return mix.power_frac == 0.0 && mix.kappa_frac == 0.0; }
+// The thermal fraction FoldUnits folds for a variant: its mix's where bl_set_electron_mixes set a list (formed as bl_init forms the
+// parameter block's, so that a variant has the constants of a context with that mix in its block), else the context's own as ever
+double MixThermal(const RenderJob &job, const bl_electron_mix &mix) { return job.variants.n_mixes > 0 ? ThermalFraction(mix) : job.ctx->plasma_thermal_frac; }
 
 // Variant v of the render into the argument blocks: its pair where the coefficient kernels read R_low / R_high, its unit folded as
 // BuildShadeArgs folds the render's (FoldUnits), the cut thresholds of its unit and its sigma cut (its BlShadeCold, uploaded by
@@ -325,10 +334,11 @@ void BindVariant(RenderJob &job, int v) {
   BlPlasmaDevice &pl = job.sa.plasma;
   pl.plasma_rat_low = variant.rat_low;
   pl.plasma_rat_high = variant.rat_high;
-  FoldUnits(job.ctx, variant.rho, pl, job.sa.fast_k);
-  // (a polarized variant's electron mix: the constants in the argument block here, kappa in the pass's BlShadeCold below)
-  if (job.variants.n_pol > 0) BindElectronConstants(FillElectronConstants(variant.mix, job.ctx->polarized), job.ctx->polarized, pl, job.sa);
-  const int n_s = std::max(1, job.variants.n_cuts), n_u = std::max(1, job.variants.n_units);   // (v = (m n_u + u) n_s + s)
+  FoldUnits(job.ctx, variant.rho, MixThermal(job, variant.mix), pl, job.sa.fast_k);
+  // (a polarized variant's electron mix: the constants in the argument block here, kappa in the pass's BlShadeCold below; an
+  // unpolarized variant's likewise where bl_set_electron_mixes set a list - none of those has kappa electrons)
+  if (job.variants.n_pol > 0 || job.variants.n_mixes > 0) BindElectronConstants(FillElectronConstants(variant.mix, job.ctx->polarized), job.ctx->polarized, pl, job.sa);
+  const int n_s = std::max(1, job.variants.n_cuts), n_u = std::max(1, job.variants.n_units);   // (v = ((e n_m + m) n_u + u) n_s + s)
   const int u = (v / n_s) % n_u, s = job.variants.n_pol > 0 ? v : v % n_s;   // (polarized variants: a cut each, PlanVariantCuts)
   job.sa.cold = job.ctx->d_shade_cold.ptr + ((job.cold_units > 1 ? u : 0) * job.cold_cuts + (job.cold_cuts > 1 ? s : 0));
   pl.cut_mask = (pl.cut_mask & ~(1 << 11)) | (variant.sigma_max >= 0.0 ? 1 << 11 : 0);   // (bit 11: cut_sigma_max, FoldFastCuts' order)
@@ -388,7 +398,18 @@ void PlanJob(RenderJob &job) {
   if (d->n_rays > 0x7fffffffll) throw Failure{BL_E_ARG, "Too many rays in one bl_render call."};
   if (d->level < 0 || d->level > p.adaptive_max_level) throw Failure{BL_E_ARG, "Adaptive level out of range."};
   if (d->level > 0 && (d->block_locs == nullptr || d->n_blocks <= 0)) throw Failure{BL_E_ARG, "Refined level needs block_locs."};
-  if (job.simulation && p.plasma_kappa_frac != 0.0 && !ctx->polarized) {
+  job.variants = ResolveVariants(ctx);
+  const Variants &vs = job.variants;
+  job.any_power = p.plasma_power_frac != 0.0, job.any_kappa = p.plasma_kappa_frac != 0.0, job.every_thermal = ctx->plasma_thermal_frac != 0.0;
+  if (vs.n_mixes > 0) {
+    job.any_power = job.any_kappa = false, job.every_thermal = true;
+    for (const Variant &v : vs.list) {
+      job.any_power = job.any_power || v.mix.power_frac != 0.0;
+      job.any_kappa = job.any_kappa || v.mix.kappa_frac != 0.0;
+      job.every_thermal = job.every_thermal && ThermalFraction(v.mix) != 0.0;
+    }
+  }
+  if (job.simulation && job.any_kappa && !ctx->polarized && vs.n_mixes == 0) {
     if (!(ctx->undefined_policy & BL_UNDEFINED_KAPPA))
       throw Failure{BL_E_UNSUPPORTED, "Kappa-distribution electrons (plasma_kappa_frac != 0) in an unpolarized run: the reference's absorptivity reads "
                                       "kappa_aa_high_i, which it only initialises for polarized runs - no defined result to reproduce. "
@@ -397,8 +418,7 @@ void PlanJob(RenderJob &job) {
       Warn(ctx, "Unpolarized kappa-distribution electrons: kappa_aa_high_i, which the reference leaves uninitialised here, is (3 / kappa)^4.75 + 0.6.");
     ctx->kappa_warned = true;
   }
-  job.variants = ResolveVariants(ctx);
-  const Variants &vs = job.variants;
+  if (const char *why = ElectronMixesRefusal(ctx, vs.n_mixes, ctx->mixes.data())) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = ElectronModelsRefusal(ctx, vs.n_models)) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = DensityUnitsRefusal(ctx, vs.n_units)) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = PolarizedVariantsRefusal(ctx, vs.n_pol)) throw Failure{BL_E_UNSUPPORTED, why};
@@ -471,8 +491,8 @@ void PlanJob(RenderJob &job) {
       && !PerSampleRows(rows);
   // (inter-block interpolation and slow light: bl_shade_fast_kernel behind their locate kernels, primitives by the exact tier's sampling)
   job.fast = ctx->arithmetic == BL_ARITH_TOLERANT && job.simulation && (!job.aux || tau_only) && !ctx->polarized && !(job.slow && job.block_interp)
-      && p.plasma_kappa_frac == 0.0 && p.plasma_model != BL_PLASMA_CODE_KAPPA
-      && !p.ray_flat && ctx->plasma_thermal_frac != 0.0
+      && !job.any_kappa && p.plasma_model != BL_PLASMA_CODE_KAPPA
+      && !p.ray_flat && job.every_thermal
       && job.n_nu <= 1024;   // (its LDS table holds five numbers per frequency)
   if (job.fast && job.aux) {
     job.tau_row = true;
@@ -487,17 +507,27 @@ void PlanJob(RenderJob &job) {
   job.matrix_transport = job.tolerant_polarized && !p.ray_flat && !(ctx->switches & BL_SWITCH_TENSOR_TRANSPORT);
   // Several frequencies in the fast path: per-sample factors (BlFreqInputs) instead of per-frequency transfer records,
   // evaluated by bl_transfer_freq_kernel with one lane per ray and frequency
-  job.freq_split = job.fast && job.n_nu >= 4 && p.plasma_power_frac == 0.0 && !job.tau_row;   // (the factors are the thermal formulas')
+  job.freq_split = job.fast && job.n_nu >= 4 && !job.any_power && !job.tau_row;   // (the factors are the thermal formulas')
   // Electron models and density units in one pass: where the factors would apply, the image holds intensities only and no Theta_e cut
   // decides differently between models - nor, with two units or more, a rho, n_e, p_gas or B cut between units - a sample's row holds
   // what no model enters (BlFreqInputs, built with base_rho) and the transfer kernel forms each model's 1 / (k T_e) and scales the row
   // to each unit (everything else: one shading pass per variant over the shared samples, LaunchShadingStage)
-  job.variants_one_pass = job.variant_passes >= 2 && job.fast && p.plasma_power_frac == 0.0 && !job.tau_row && !job.aux && ctx->render_num_images == 0
+  // (two electron mixes or more: the rows fold a thermal fraction of 1 and every transfer workgroup applies its own mix, power law
+  // included - every mix has a thermal part, or job.fast is off. One mix is a context with it in its block. A list rendered run by run -
+  // bl_render: it holds a mix without a thermal part - runs a pass per variant.)
+  const bool mixes_one_pass = vs.n_mixes >= 2 && !ctx->mix_runs;
+  job.variants_one_pass = job.variant_passes >= 2 && job.fast && (mixes_one_pass || (!job.any_power && vs.n_mixes < 2)) && !job.tau_row && !job.aux && ctx->render_num_images == 0
       && !ThetaECut(p) && !(vs.n_units >= 2 && UnitCut(p))
-      && !((vs.n_units >= 2 || vs.n_cuts >= 2) && job.n_rays * job.n_nu * job.variant_passes >= (1ll << 31));   // (the transfer kernel's lanes of a chunk fit one grid)
+      && !((vs.n_units >= 2 || vs.n_cuts >= 2 || mixes_one_pass) && job.n_rays * job.n_nu * job.variant_passes >= (1ll << 31));   // (the transfer kernel's lanes of a chunk fit one grid)
   if (job.variants_one_pass) {
     job.freq_split = true;
     job.variant_passes = 1;
+    // (mixes in one pass: no power law reaches the coefficient kernels, which write the mix-free row - the thermal kernels, the fused one
+    // included, with a mix of thermal electrons alone, fraction 1, in their argument block)
+    if (mixes_one_pass) {
+      job.any_power = false;
+      job.base_mix = bl_electron_mix{};
+    }
   }
   // Plain images of a spherical Kerr-Schild simulation with fallback values beyond the grid: nothing is recorded of the steps that
   // lie in the empty shell between the grid's outer edge and the camera's sphere (both tiers; the samples count as ever)
@@ -523,15 +553,15 @@ void PlanJob(RenderJob &job) {
       && !GeometricCut(p) && job.no_checkpoint && !(ctx->switches & (BL_SWITCH_NO_FUSED_LOCATE | BL_SWITCH_SPLIT_RECORDS));
   // (its own: the tolerant tier's scope - only this one reads job.fast, which leaves it plain images and so no sample times - without
   // the optical-depth row and power-law electrons; it alone takes inter-block interpolation, which its grid predicate decides)
-  job.fused2 = locate_inside_possible && job.fast && !job.tau_row && fused2_grid && p.plasma_power_frac == 0.0;
+  job.fused2 = locate_inside_possible && job.fast && !job.tau_row && fused2_grid && !job.any_power;
   // ... with theta and phi relative to the centre of the guessed cell where the series behind them reaches every point of every angular
   // cell (bl_local_angles.h: 1 / 16 rad from the centre; one block - the mesh with refinement keeps acos / atan2)
   job.local_angles = job.fused2 && ctx->grid.dev.n_blocks == 0 && ctx->grid.dev.angle_trig[0] != nullptr && ctx->grid.dev.angle_reach <= kLocalAngleReach && !(ctx->switches & BL_SWITCH_GLOBAL_ANGLES);
   // The exact tier's plain image at one frequency over such a grid: the locate step inside bl_shade_exact2_kernel (bit-identical
   // to bl_locate_plain_kernel + bl_shade_exact_kernel, whose conditions these are: job.fast's electrons, restated because it is off)
   job.exact_fused = locate_inside_possible && !job.fast && !job.aux && !ctx->polarized && !job.block_interp && job.n_nu == 1
-      && p.plasma_kappa_frac == 0.0 && p.plasma_power_frac == 0.0 && p.plasma_model != BL_PLASMA_CODE_KAPPA && !p.ray_flat
-      && ctx->plasma_thermal_frac != 0.0
+      && !job.any_kappa && !job.any_power && p.plasma_model != BL_PLASMA_CODE_KAPPA && !p.ray_flat
+      && job.every_thermal
       && (ctx->grid.dev.n_blocks == 0 ? bl_fused2_applicable(&ctx->grid.dev, job.n_nu, job.n_rays) != 0 : bl_polarized2_refined_applicable(&ctx->grid.dev, job.n_rays) != 0);
   // Polarized runs over such a grid: the frame-and-inputs kernel with the locate step inside (bit-identical to bl_locate_plain_kernel +
   // bl_shade_kernel<polarized>, whose conditions these are; electron entropy from the grid is a ninth value it does not gather)
@@ -1303,7 +1333,7 @@ void PlanKernels(RenderJob &job) {
   const bool refined = job.simulation && ctx->grid.dev.n_blocks > 0;
   const bool slices = job.slow && p.slow_chunk_size > 0;
   const bool sks = p.simulation_coord != BL_COORD_CKS;   // (FMKS: everything but the cell search treats the grid as sks, BuildShadeArgs)
-  const bool power_law = job.simulation && p.plasma_power_frac != 0.0;
+  const bool power_law = job.simulation && job.any_power;   // (some variant's: PlanJob)
   k.geodesic = PlanGeodesicKernel(job);
   k.quad.park = job.park;
   k.quad.split = job.split_long;
@@ -1348,7 +1378,7 @@ void PlanKernels(RenderJob &job) {
     const bool sks_curved = sks && !ctx->st.ray_flat;
     c.polarized = ctx->polarized;
     c.aux = ctx->polarized || use.aux;   // (a polarized run is an auxiliary-image run whether or not it keeps BlAuxSample records)
-    c.extended = ctx->polarized || power_law || p.plasma_model == BL_PLASMA_CODE_KAPPA || slices || use.anchors || p.plasma_kappa_frac != 0.0;
+    c.extended = ctx->polarized || power_law || p.plasma_model == BL_PLASMA_CODE_KAPPA || slices || use.anchors || job.any_kappa;
     c.sks = ctx->polarized && sks_curved;
     // plain image of a spherical Kerr-Schild simulation in a curved spacetime: the software-pipelined kernel
     if (!c.aux && !c.extended && sks_curved) {
@@ -1815,7 +1845,7 @@ void BuildShadeArgs(RenderJob &job) {
     pl.plasma_ne_ni = p.plasma_ne_ni;
     pl.plasma_rat_low = job.base_rat_low;     // (the render's base, PlanJob; BindVariant each variant's)
     pl.plasma_rat_high = job.base_rat_high;
-    FoldUnits(ctx, job.base_rho, pl, sa.fast_k);            // simulation_coefficients.cpp:237-239
+    FoldUnits(ctx, job.base_rho, MixThermal(job, job.base_mix), pl, sa.fast_k);            // simulation_coefficients.cpp:237-239
     const ElectronConstants ec = FillElectronConstants(job.base_mix, ctx->polarized);   // (the render's: PlanJob; BindVariant each pass's)
     BindElectronConstants(ec, ctx->polarized, pl, sa);
     cold.kappa = ec.kappa;
@@ -1902,7 +1932,7 @@ void BuildShadeArgs(RenderJob &job) {
       std::memcpy(static_cast<void *>(&unit_cold), &cold, sizeof(BlShadeCold));
       BlPlasmaDevice unit_pl = sa.plasma;
       double unit_k[8];
-      FoldUnits(ctx, job.cold_units > 1 ? variant.rho : job.base_rho, unit_pl, unit_k);
+      FoldUnits(ctx, job.cold_units > 1 ? variant.rho : job.base_rho, ctx->plasma_thermal_frac, unit_pl, unit_k);   // (unit_k is not read)
       const double sigma_max = job.cold_cuts > 1 ? variant.sigma_max : job.base_sigma_max;
       unit_cold.cut_sigma_max = sigma_max >= 0.0 ? sigma_max : std::numeric_limits<double>::infinity();
       FoldFastCuts(ctx, unit_pl, unit_cold, sigma_max);
@@ -1930,7 +1960,7 @@ void BuildShadeArgs(RenderJob &job) {
       double variant_k[8];
       variant_pl.plasma_rat_low = variant.rat_low;
       variant_pl.plasma_rat_high = variant.rat_high;
-      FoldUnits(ctx, variant.rho, variant_pl, variant_k);
+      FoldUnits(ctx, variant.rho, ctx->plasma_thermal_frac, variant_pl, variant_k);
       // (the variant's threshold where the shared pass ran with the sigma upper cut off - PlanVariantCuts - else +inf: nothing to compare)
       const bool cut_here = job.base_sigma_max < 0.0 && variant.sigma_max >= 0.0;
       table.push_back(BlPolVariant{variant_pl.d_unit, variant_pl.e_unit, variant_pl.b_unit, variant_pl.plasma_rat_high, variant_pl.plasma_rat_low,
@@ -2036,6 +2066,7 @@ void BuildTransferArgs(RenderJob &job) {
   xa.n_models = 0;
   xa.n_units = 0;
   xa.n_cuts = 0;
+  xa.n_mixes = 0;
   xa.pol_variants = job.pol_one_pass ? job.variants.n_pol : 0;
   xa.pol_variant_rows = job.n_q_model;
   if (job.variants_one_pass) {   // every model's R_high / R_low folded as BuildShadeArgs folds the parameter block's (fast_k[1..3])
@@ -2047,7 +2078,8 @@ void BuildTransferArgs(RenderJob &job) {
     const Variants &vs = job.variants;
     // (model-major, then unit, then cut: model m's variants start at m n_u n_s, the first model's are the (unit, cut) pairs)
     const int n_u = std::max(1, vs.n_units), n_s = std::max(1, vs.n_cuts);
-    xa.n_models = static_cast<int>(vs.list.size()) / (n_u * n_s);   // (no models set: the parameter block's pair is model 0)
+    const int n_e = vs.n_mixes >= 2 ? vs.n_mixes : 1;   // (mix-major above the models: the first mix's variants are the (model, unit, cut) triples)
+    xa.n_models = static_cast<int>(vs.list.size()) / (n_e * n_u * n_s);   // (no models set: the parameter block's pair is model 0)
     for (int m = 0; m < xa.n_models; m++) {
       xa.model_k1[m] = vs.list[m * n_u * n_s].rat_high * g1;
       xa.model_k2[m] = vs.list[m * n_u * n_s].rat_low * g1;
@@ -2059,10 +2091,10 @@ void BuildTransferArgs(RenderJob &job) {
     if (vs.n_units >= 2) {
       BlPlasmaDevice base{}, unit{};
       double k[8];
-      FoldUnits(ctx, job.base_rho, base, k);
+      FoldUnits(ctx, job.base_rho, ctx->plasma_thermal_frac, base, k);   // (k is not read)
       xa.n_units = vs.n_units;
       for (int u = 0; u < vs.n_units; u++) {
-        FoldUnits(ctx, vs.list[u * n_s].rho, unit, k);
+        FoldUnits(ctx, vs.list[u * n_s].rho, ctx->plasma_thermal_frac, unit, k);
         xa.unit_x[u] = base.b_unit / unit.b_unit;
         xa.unit_j[u] = (unit.d_unit * unit.b_unit) / (base.d_unit * base.b_unit);
       }
@@ -2074,6 +2106,28 @@ void BuildTransferArgs(RenderJob &job) {
       xa.n_cuts = vs.n_cuts;
       for (int c = 0; c < vs.n_cuts; c++)
         xa.sigma_max[c] = vs.list[c].sigma_max >= 0.0 ? vs.list[c].sigma_max : std::numeric_limits<double>::infinity();
+    }
+    // Two electron mixes or more: the rows hold a thermal fraction of 1 (PlanJob); of mix e what FillElectronConstants gives of it,
+    // folded with the products of fast_k - at base_rho, thermal fraction 1: the rows' - that turn a row into the power-law terms
+    // (bl_transfer_freq_kernel has the algebra)
+    if (vs.n_mixes >= 2) {
+      static_assert(BL_TRANSFER_MAX_MIXES == BL_MAX_ELECTRON_MIXES, "mix constants");
+      xa.n_mixes = vs.n_mixes;
+      const int per_mix = xa.n_models * n_u * n_s;
+      constexpr double kPlanck = 6.62607015e-27;   // (the kernels' kH, bl_kernel_util.h: the rows' q1.x is kH s_nu)
+      BlPlasmaDevice base{};
+      double k[8];
+      FoldUnits(ctx, job.base_rho, 1.0, base, k);
+      xa.power_k0 = 1.0 / (k[4] * k[7]);
+      for (int e = 0; e < vs.n_mixes; e++) {
+        const ElectronConstants ec = FillElectronConstants(vs.list[e * per_mix].mix, false);
+        const bool power = ec.power_frac != 0.0;   // (else p, power_jj and power_aa are not defined: zeros, which the kernel selects past)
+        xa.mix_thermal[e] = ec.thermal_frac;
+        xa.mix_power_frac[e] = ec.power_frac;
+        xa.mix_pw_e[e] = power ? -(ec.plasma_p - 1.0) * 0.5 : 0.0;
+        xa.mix_pw_j[e] = power ? ec.power_frac * ec.power_jj * (kE * kE * k[6] * k[7] / (kC * k[5])) : 0.0;
+        xa.mix_pw_a[e] = power ? ec.power_frac * ec.power_aa * (kE * kE * k[6] * k[7] / (kMe * kC * kPlanck * k[5])) : 0.0;
+      }
     }
   }
   xa.out_sample_num = job.out_num;
@@ -2694,6 +2748,7 @@ void FinishStats(RenderJob &job) {
   st.mirror_pairs = job.mirror ? 1 : 0;
   st.local_angles = job.local_angles ? 1 : 0;
   st.n_cameras = job.n_cameras;
+  st.n_mixes = std::max(1, job.variants.n_mixes);
   st.tail_policy = job.reuse ? ctx->resident.tail_policy : (job.park ? BL_TAIL_QUAD : (job.split_long ? BL_TAIL_SPLIT : BL_TAIL_WIDE));
   ctx->stats = st;
   if (ctx->debug_counters) {   // kernels built with -DBL_GEO_STATS fill these
@@ -2779,9 +2834,9 @@ void EnsureStreams(bl_ctx *ctx) {
 }
 }  // namespace blhost
 
-extern "C" int bl_render(bl_ctx *ctx, const bl_render_desc *d) {
-  if (ctx == nullptr || d == nullptr) return BL_E_ARG;
-  std::lock_guard<std::mutex> render_guard(ctx->render_lock);   // (bl_set_grid on another host thread stages the next snapshot meanwhile: bl_api.hip)
+namespace {
+// One render of the context as it stands, render_lock held (bl_render below)
+int RenderLocked(bl_ctx *ctx, const bl_render_desc *d) {
   auto drain = [ctx]() {   // leave no chunk half collected behind: a later call starts from idle streams
     if (ctx->stream_few != nullptr) (void)hipStreamSynchronize(ctx->stream_few);
     if (ctx->stream_most != nullptr) (void)hipStreamSynchronize(ctx->stream_most);
@@ -2847,5 +2902,55 @@ extern "C" int bl_render(bl_ctx *ctx, const bl_render_desc *d) {
     drain();
     return Fail(ctx, failure);
   }
+  return BL_OK;
+}
+
+// What kind of electrons a mix has, as far as the tolerant tier's choice of kernels goes: no thermal part (no tolerant kernel: the exact
+// tier's), thermal electrons alone, thermal electrons and a power law
+int MixKind(const bl_electron_mix &mix) { return ThermalFraction(mix) == 0.0 ? 0 : (mix.power_frac == 0.0 ? 1 : 2); }
+}  // namespace
+
+extern "C" int bl_render(bl_ctx *ctx, const bl_render_desc *d) {
+  if (ctx == nullptr || d == nullptr) return BL_E_ARG;
+  std::lock_guard<std::mutex> render_guard(ctx->render_lock);   // (bl_set_grid on another host thread stages the next snapshot meanwhile: bl_api.hip)
+  // Electron mixes in the tolerant tier: a render chooses its kernels once, and a mix without a thermal part has none in that tier (the
+  // exact tier's render it, as they render a context with that mix in its block), so a list that holds such a mix beside others cannot
+  // share the one pass, and a mix of thermal electrons alone has other kernels (the locate step inside, the factors of several
+  // frequencies) than one with a power law. So that every mix's rows are then what a context with that mix in its block renders in this
+  // tier, such a list is rendered run by run, a pass per variant - the runs of neighbouring mixes of one kind, each a render of its
+  // own into its rows of the image (the mixes are the outermost axis: a run's rows lie together), the later ones from the resident
+  // geodesics where their record layout is the same. The statistics are the last run's, with the launches and kernel times summed.
+  // (The exact tier has one set of kernels for all, and a list whose mixes all have a thermal part one pass or one choice: one render.)
+  const std::vector<bl_electron_mix> all = ctx->mixes;
+  bool one_kind = true, every_thermal = true;
+  for (const bl_electron_mix &mix : all) one_kind = one_kind && MixKind(mix) == MixKind(all[0]), every_thermal = every_thermal && MixKind(mix) != 0;
+  if (ctx->arithmetic != BL_ARITH_TOLERANT || one_kind || every_thermal || d->image == nullptr) return RenderLocked(ctx, d);
+  ctx->mix_runs = true;
+  const size_t rows_per_mix = static_cast<size_t>(bl_image_num_quantities(ctx)) / all.size();
+  bl_stats sum{};
+  int rc = BL_OK;
+  for (size_t begin = 0, end = 0; begin < all.size() && rc == BL_OK; begin = end) {
+    for (end = begin + 1; end < all.size() && MixKind(all[end]) == MixKind(all[begin]);) end++;
+    ctx->mixes.assign(all.begin() + begin, all.begin() + end);
+    bl_render_desc run = *d;
+    run.image = d->image + begin * rows_per_mix * static_cast<size_t>(d->n_rays);
+    rc = RenderLocked(ctx, &run);
+    const bl_stats &st = ctx->stats;
+    sum.launches_geodesic += st.launches_geodesic, sum.launches_locate += st.launches_locate;
+    sum.launches_shade += st.launches_shade, sum.launches_transfer += st.launches_transfer;
+    sum.ms_geodesic += st.ms_geodesic, sum.ms_locate += st.ms_locate, sum.ms_shade += st.ms_shade, sum.ms_transfer += st.ms_transfer;
+    sum.ms_total += st.ms_total, sum.ms_wall += st.ms_wall;
+    sum.arithmetic = (begin == 0 || st.arithmetic == BL_ARITH_TOLERANT) ? st.arithmetic : sum.arithmetic;
+  }
+  ctx->mixes = all;
+  ctx->mix_runs = false;
+  if (rc != BL_OK) return rc;
+  bl_stats &st = ctx->stats;
+  st.launches_geodesic = sum.launches_geodesic, st.launches_locate = sum.launches_locate;
+  st.launches_shade = sum.launches_shade, st.launches_transfer = sum.launches_transfer;
+  st.ms_geodesic = sum.ms_geodesic, st.ms_locate = sum.ms_locate, st.ms_shade = sum.ms_shade, st.ms_transfer = sum.ms_transfer;
+  st.ms_total = sum.ms_total, st.ms_wall = sum.ms_wall;
+  st.arithmetic = sum.arithmetic;
+  st.n_mixes = static_cast<int32_t>(all.size());
   return BL_OK;
 }

@@ -25,22 +25,67 @@
 // With sigma cuts as well (P.n_cuts > 0) a lane is a (ray, model, unit, cut, frequency): the rows carry the sample's sigma, and the
 // lane leaves out the samples above its own threshold - one compare per sample. (Without cuts the threshold is +inf, against which no
 // sigma compares greater - NaN included, as in the reference: the same decisions.)
-__global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P) {
+// With electron mixes as well (P.n_mixes > 0) a lane is a ray and a workgroup a (256 rays, mix, model, unit, cut, frequency): everything
+// the walk needs of its channel is the workgroup's, computed once into LDS and read where it is used, which costs the walk no vector
+// register across its loop - as lane constants they take 18, and the power-law terms on top of them 76 where 64 keep eight waves per
+// SIMD. (Consecutive workgroups are the channels of the same rays: the rows they all read come from L2.) The rows were
+// written with the thermal fraction folded as 1; the lane scales the thermal line by its mix's thermal fraction and adds its mix's
+// power-law emissivity and absorptivity (bl_shade_fast_kernel's terms, simulation_coefficients.cpp:556-584), which follow from the same
+// row: with k4, k5, k6, k7 of BlShadeArgs::fast_k at the base unit and a thermal fraction of 1, ratio = nu / (nu_c sin theta_B) =
+// q0.y f / (k4 k7), rho |b| sin theta_B / s_nu^2 = q1.y / k5 and rho = q1.y (q1.x / h) q0.y / (k4 k5), so that
+//   j     = power_frac power_jj (e^2 k6 k7 / (c k5)) q1.y f^-2 ratio^(-(p - 1) / 2)
+//   alpha = power_frac power_aa (e^2 k6 / (m_e c h k4 k5)) q1.y q1.x q0.y ratio^(-(p + 2) / 2)
+//         = power_frac power_aa (e^2 k6 k7 / (m_e c h k5)) q1.y q1.x f^-1 ratio^(-(p - 1) / 2) ratio^(-1/2)
+// (q0.y = ratio k4 k7 / f): one logarithm, one exponential and one reciprocal square root per sample and lane. Unit u: n_e ~ unit and
+// |b| ~ sqrt(unit) - ratio takes unit_x with f as x does, j's f^-2 is the lane's f_inv2 (unit_j in it), and alpha's f^-1 becomes
+// f_inv2 f, which carries unit_j / unit_x x unit_x = n_e's factor.
+// (what a workgroup with mixes keeps in LDS: f, its roots and reciprocals with the unit's factors, the cut's threshold, the model's
+// constants, and of the mix the thermal fraction, -(p - 1) / 2, the folded factors of j and alpha, and 1 / (k4 k7))
+enum { kGroupF, kGroupF12, kGroupF13, kGroupF16, kGroupFInv, kGroupFInv2, kGroupSigma, kGroupMk1, kGroupMk2, kGroupMk3, kGroupThermal, kGroupPwE, kGroupPwJ,
+       kGroupPwA, kGroupK0, kGroupConstants };
+// (the kernel's body twice, chosen by the wave-uniform P.n_mixes > 0 at its very top: without mixes it is, statement for statement, the
+// kernel as it was before the axis existed - kGroup folds everything else away)
+template <bool kGroup>
+__device__ __forceinline__ void bl_transfer_freq_body(const BlTransferArgs &P, double *group_k) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool models = P.n_models > 0;
   const int n_units = P.n_units > 0 ? P.n_units : 1;
   const int n_cuts = P.n_cuts > 0 ? P.n_cuts : 1;
   const int channels = models ? P.n_models * n_units * n_cuts * P.n_nu : P.n_nu;
-  const int slot = (int)(t / channels);
-  const int channel = (int)(t % channels);   // ((m n_units + u) n_cuts + s) n_nu + l: the image row
+  int slot = (int)(t / channels);
+  int channel = (int)(t % channels);   // ((m n_units + u) n_cuts + s) n_nu + l: the image row (with mixes: within the mix's rows)
+  int mix = 0;
+  if (kGroup) {   // a workgroup per (256 rays, mix, channel): both scalars, a lane per ray
+    const unsigned int all = (unsigned int)(P.n_mixes * channels), group = blockIdx.x / all, c = blockIdx.x - group * all;
+    mix = (int)(c / (unsigned int)channels);
+    channel = (int)(c - (unsigned int)(mix * channels));
+    slot = (int)(group * blockDim.x + threadIdx.x);
+  }
   const int l = channel % P.n_nu;
+  // With mixes the lane's constants are the workgroup's. They wait in LDS and are read where they are used, so that the power-law terms
+  // fit the vector registers of eight waves per SIMD (as lane constants they take 18 registers across the loop).
+  if (kGroup) {
+    if (threadIdx.x == 0) {
+      const int variant = channel / P.n_nu, pair = variant / n_cuts, m = pair / n_units, u = pair - m * n_units;
+      const double ux = P.n_units > 0 ? P.unit_x[u] : 1.0, uj = P.n_units > 0 ? P.unit_j[u] : 1.0;
+      const double f = P.frequencies[l], f_x = f * ux, f_1_3 = fastmath::cbrt(f_x), f_inv = fastmath::rcp(f);
+      group_k[kGroupF] = f, group_k[kGroupF12] = bl_sqrt_g(f_x), group_k[kGroupF13] = f_1_3, group_k[kGroupF16] = bl_sqrt_g(f_1_3);
+      group_k[kGroupFInv] = f_inv, group_k[kGroupFInv2] = f_inv * f_inv * uj;
+      group_k[kGroupSigma] = P.n_cuts > 0 ? P.sigma_max[variant - pair * n_cuts] : __builtin_inf();
+      group_k[kGroupMk1] = P.model_k1[m], group_k[kGroupMk2] = P.model_k2[m], group_k[kGroupMk3] = P.model_k3;
+      // (the mix's, as the host folded them - BuildTransferArgs; zeros where it has no power law)
+      group_k[kGroupThermal] = P.mix_thermal[mix], group_k[kGroupPwE] = P.mix_pw_e[mix], group_k[kGroupPwJ] = P.mix_pw_j[mix];
+      group_k[kGroupPwA] = P.mix_pw_a[mix], group_k[kGroupK0] = P.power_k0;
+    }
+    __syncthreads();
+  }
   unsigned long long samples = 0ull, flagged = 0ull;
   int max_num = 0;
   if (slot < bl_rays_done(P.counters, P.chunk_rays)) {
     const int num = P.ray_sample_num[slot];
     const bool flag = P.ray_flags[slot] != 0;
     const long long out_index = P.ray_out_index[slot];
-    if (channel == 0) {
+    if (channel == 0 && (!kGroup || mix == 0)) {
       const int all = num + (P.ray_skipped != nullptr ? P.ray_skipped[slot] : 0);
       samples = (unsigned long long)all;
       flagged = flag ? 1ull : 0ull;
@@ -49,24 +94,35 @@ __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P)
       if (P.out_flags != nullptr) P.out_flags[out_index] = flag ? 1 : 0;
     }
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    const double f = P.frequencies[l];
+    const double f_given = P.frequencies[l];
     double intensity = 0.0;
     if (P.fallback_nan && flag) {
       intensity = num > 0 ? nan : 0.0;   // every sample of a flagged ray carries NaN primitives (simulation_sampling.cpp:211-216)
     } else {
       // (the ray's walk twice, behind a wave-uniform branch: the one without sigma cuts is the code it was - a render that does not use
-      // the axis does not pay for it - the other holds the lane's threshold and one compare more per sample)
-      auto walk = [&](auto with_cuts) {
-        constexpr bool kCuts = decltype(with_cuts)::value;
-        const int variant = channel / P.n_nu, pair = kCuts ? variant / P.n_cuts : variant, m = pair / n_units, u = pair - m * n_units;
-        const double sigma_max = kCuts ? P.sigma_max[variant - pair * P.n_cuts] : 0.0;
+      // the axis does not pay for it - the other holds the lane's threshold and one compare more per sample; a third, with electron mixes,
+      // the mix's power-law terms per sample - it always compares, against +inf where no cuts are set)
+      auto walk = [&](auto with_cuts, auto with_mixes) {
+        constexpr bool kCuts = decltype(with_cuts)::value, kMixes = decltype(with_mixes)::value;
+        const int variant = channel / P.n_nu, pair = kCuts ? variant / (kMixes ? n_cuts : P.n_cuts) : variant, m = pair / n_units, u = pair - m * n_units;
+        const double f = f_given;
+        const double sigma_max = (!kCuts || kMixes) ? 0.0 : P.sigma_max[variant - pair * P.n_cuts];
+        // (with mixes: the workgroup's copy, read afresh at every use - K(i, lane's) is the lane's value in the two older forms)
+        const volatile double *group = kMixes ? group_k : nullptr;
+        auto K = [group](int i, double lanes) {
+          if constexpr (kMixes) return (double)group[i];
+          else return lanes;
+        };
         // Unit u's factors where no sample register holds them: x at unit frequency enters only as x f, so unit_x is a factor on the
         // frequency of the x terms (f_1_2, f_1_3, f_1_6), and s_j only as s_j f^-2, so unit_j is one on f_inv2 (without units: 1.0)
         const double ux = P.n_units > 0 ? P.unit_x[u] : 1.0, uj = P.n_units > 0 ? P.unit_j[u] : 1.0;
         const double f_x = f * ux;
-        const double f_1_2 = bl_sqrt_g(f_x), f_1_3 = fastmath::cbrt(f_x);
-        const double f_1_6 = bl_sqrt_g(f_1_3), f_inv = fastmath::rcp(f);
-        const double f_inv2 = f_inv * f_inv * uj;
+        const double f_1_2 = kMixes ? 0.0 : bl_sqrt_g(f_x), f_1_3 = kMixes ? 0.0 : fastmath::cbrt(f_x);
+        const double f_1_6 = kMixes ? 0.0 : bl_sqrt_g(f_1_3), f_inv = kMixes ? 0.0 : fastmath::rcp(f);
+        const double f_inv2 = kMixes ? 0.0 : f_inv * f_inv * uj;
+        // A mix without a power law (power_frac == 0: its p, power_jj and power_aa are not defined, the host leaves zeros in the tables)
+        // selects zeros below and never multiplies by them, so no 0 x inf forms; its thermal line is the row's times the thermal fraction.
+        const bool power = kMixes && P.mix_power_frac[mix] != 0.0;
         // (one exponential per sample and frequency is most of this loop: its constants stay in scalar registers across it)
         double exp_c[15];
   #pragma unroll
@@ -74,7 +130,7 @@ __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P)
         const double2 *in = reinterpret_cast<const double2 *>(P.freq_inputs + (size_t)P.ray_offset[slot]);
         const double kThird = fastmath::resident_constant(1.0 / 3.0), kInvPlanck = fastmath::resident_constant(kC * kC / (2.0 * kH));
         const double kRoot = fastmath::resident_constant(kPow2_11_12), kThin = fastmath::resident_constant(0x1p-10);
-        const double mk1 = models ? P.model_k1[m] : 0.0, mk2 = models ? P.model_k2[m] : 0.0, mk3 = P.model_k3;
+        const double mk1 = (models && !kMixes) ? P.model_k1[m] : 0.0, mk2 = (models && !kMixes) ? P.model_k2[m] : 0.0, mk3 = kMixes ? 0.0 : P.model_k3;
         for (int n = num - 1; n >= 0; n--) {   // reference sample order is reversed integration order (geodesics.cpp:832-840)
           const double2 q0 = in[4 * (size_t)n], q1 = in[4 * (size_t)n + 1], q2 = in[4 * (size_t)n + 2], q3 = in[4 * (size_t)n + 3];
           // bl_shade_fast_kernel's frequency loop (simulation_coefficients.cpp:464-523, unpolarized.cpp:74-110) as one straight line for
@@ -84,31 +140,44 @@ __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P)
           double s_1_3 = q1.x, s_1_6 = q1.y, s_1_2 = q0.y, s_planck = q2.x, s_j = q2.y, s_length = q3.x;
           if (models) {   // this model's 1 / (k T_e) (the fused kernel's kte_inv), then the sample's roots at unit frequency
             const double bi2 = q2.y, dd = 1.0 + bi2;
-            const double kte_inv = (mk1 + mk2 * bi2 + mk3 * dd) * fastmath::rcp(q3.x * dd);
+            const double kte_inv = (K(kGroupMk1, mk1) + K(kGroupMk2, mk2) * bi2 + K(kGroupMk3, mk3) * dd) * fastmath::rcp(q3.x * dd);
             s_1_3 = fastmath::cbrt(q0.y * (kte_inv * kte_inv));
             s_1_6 = bl_sqrt_g(s_1_3);
             s_1_2 = s_1_6 * s_1_3;
             s_planck = q1.x * kte_inv;
             s_j = q1.y;
             s_length = q2.x;
-            if (kCuts) have = have && !(q3.y > sigma_max);   // (the row's sigma)
+            if (kCuts) have = have && !(q3.y > K(kGroupSigma, sigma_max));   // (the row's sigma)
           }
-          const double xx_1_3 = s_1_3 * f_1_3;
-          const double var_c = s_1_2 * f_1_2 + kRoot * (s_1_6 * f_1_6);
-          const double j_val = s_j * f_inv2 * fastmath::exp(-xx_1_3, exp_c) * var_c * var_c;
-          const double xp = s_planck * f;
+          const double xx_1_3 = s_1_3 * K(kGroupF13, f_1_3);
+          const double var_c = s_1_2 * K(kGroupF12, f_1_2) + kRoot * (s_1_6 * K(kGroupF16, f_1_6));
+          double j_val = s_j * K(kGroupFInv2, f_inv2) * fastmath::exp(-xx_1_3, exp_c) * var_c * var_c;
+          if (kMixes) j_val *= group[kGroupThermal];
+          const double xp = s_planck * K(kGroupF, f);
           double planck = xp * (1.0 + 0.5 * xp * (1.0 + kThird * xp * (1.0 + 0.25 * xp)));
           if (__builtin_expect(have && !(xp < kThin), 0)) planck = fastmath::expm1(xp);
           double alpha_val = j_val * (planck * kInvPlanck);
           if (alpha_val * alpha_val <= 0x1p-1024) alpha_val = 0.0;
-          const double delta_lambda_cgs = s_length * f_inv;
+          double j_total = j_val;
+          if (kMixes) {
+            // the mix's power-law terms. Selected, not multiplied, where the mix has no power law and where the sample lies along the
+            // field (q0.y = inf: sin theta_B = 0, both terms are zero there as in bl_shade_fast_kernel, and rho would form inf x 0). A row
+            // without coefficients (q0.x != 1: nothing to add, or the NaN row) may hold anything here: `have` selects a and c below.
+            __builtin_amdgcn_sched_barrier(0);   // (the thermal line first, then this: interleaved, the two exponentials' temporaries cost a wave of occupancy)
+            const double root = K(kGroupF12, f_1_2), ratio = q0.y * (root * root) * group[kGroupK0];
+            const double to_e = fastmath::exp(group[kGroupPwE] * fastmath::log(ratio), exp_c) * q1.y;
+            const bool add = power && q0.y < __builtin_inf();
+            j_total += add ? group[kGroupPwJ] * K(kGroupFInv2, f_inv2) * to_e : 0.0;
+            alpha_val += add ? group[kGroupPwA] * (K(kGroupFInv2, f_inv2) * K(kGroupF, f)) * (q1.x * to_e) * fastmath::rsqrt(ratio) : 0.0;
+          }
+          const double delta_lambda_cgs = s_length * K(kGroupFInv, f_inv);
           const double delta_tau = alpha_val * delta_lambda_cgs;
           // optically thin step: expm1(-t) = -t p(t), p = 1 - t/2 (1 - t/3 (1 - t/4)) to 2^-53: a = 1 - t p, c = j dl p
           const double p = 1.0 - 0.5 * delta_tau * (1.0 - kThird * delta_tau * (1.0 - 0.25 * delta_tau));
           const bool absorbing = alpha_val > 0.0;
-          double a = absorbing ? 1.0 - delta_tau * p : 1.0, c = j_val * delta_lambda_cgs * (absorbing ? p : 1.0);
+          double a = absorbing ? 1.0 - delta_tau * p : 1.0, c = j_total * delta_lambda_cgs * (absorbing ? p : 1.0);
           if (__builtin_expect(have && absorbing && !(delta_tau < kThin), 0)) {
-            const double ss = j_val * fastmath::rcp(alpha_val);
+            const double ss = j_total * fastmath::rcp(alpha_val);
             if (delta_tau <= kDeltaTauMax) {
               const double e1 = fastmath::expm1(-delta_tau);
               a = 1.0 + e1;
@@ -124,10 +193,11 @@ __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P)
           intensity = __builtin_fma(a, intensity, c);
         }
       };
-      if (P.n_cuts > 0) walk(std::true_type{});
-      else walk(std::false_type{});
+      if (kGroup) walk(std::true_type{}, std::true_type{});
+      else if (P.n_cuts > 0) walk(std::true_type{}, std::false_type{});
+      else walk(std::false_type{}, std::false_type{});
     }
-    P.image[(size_t)channel * P.n_rays_total + out_index] = intensity * (f * f * f);   // unpolarized.cpp:206-207
+    P.image[(kGroup ? (size_t)mix * channels + (size_t)channel : (size_t)channel) * P.n_rays_total + out_index] = intensity * (f_given * f_given * f_given);   // unpolarized.cpp:206-207
   }
   // statistics: wave reduce, one atomic per wave
   for (int offset = 32; offset > 0; offset >>= 1) {
@@ -141,6 +211,11 @@ __global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P)
     if (flagged) atomicAdd(&P.stats[1], flagged);
     atomicMax(&P.stats[2], (unsigned long long)max_num);
   }
+}
+__global__ void __launch_bounds__(256) bl_transfer_freq_kernel(BlTransferArgs P) {
+  __shared__ double group_k[kGroupConstants];
+  if (P.n_mixes > 0) bl_transfer_freq_body<true>(P, group_k);
+  else bl_transfer_freq_body<false>(P, group_k);
 }
 #pragma clang fp contract(off)
 
@@ -571,6 +646,14 @@ extern "C" hipError_t bl_launch_transfer(const BlTransferArgs *args, const Kerne
     case Transfer::kFreq:   // ... and model and unit
       if (args->freq_inputs == nullptr) return hipErrorInvalidValue;
       kernel = bl_transfer_freq_kernel, lanes *= args->n_models > 0 ? args->n_models * (args->n_units > 0 ? args->n_units : 1) * (args->n_cuts > 0 ? args->n_cuts : 1) : 1;
+      if (args->n_mixes > 0) {   // a workgroup per (256 rays, mix, channel): the lane's constants are scalars in the kernel
+        // (the mixes ride on the model-free row; no mirror pairs here, as below)
+        if (args->n_models <= 0 || args->n_mixes > BL_TRANSFER_MAX_MIXES || plan.affine != (args->affine != 0) || args->mirror_rays > 0) return hipErrorInvalidValue;
+        const long long groups = (rays + block - 1) / block, per_group = lanes / (rays > 0 ? rays : 1) * args->n_mixes;
+        if (groups * per_group >= (1ll << 31)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(kernel, dim3((unsigned int)(groups * per_group)), dim3(block), 0, stream, *args);
+        return hipGetLastError();
+      }
       break;
     case Transfer::kComposed:
       if (args->composed == nullptr || !plan.affine) return hipErrorInvalidValue;

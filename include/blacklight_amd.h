@@ -416,6 +416,8 @@ typedef struct bl_stats {
      where every variant shares one pass, n_chunks. */
   /* ... and sigma cuts (bl_set_sigma_cuts): one shading pass per (model, unit, cut) and chunk, n_chunks * M * U * S launches; where
      every variant shares one pass, n_chunks whatever S is. */
+  int32_t n_mixes;            /* electron mixes the last bl_render rendered (bl_set_electron_mixes): max(1, n); one shading pass per
+                                 (mix, model, unit, cut) and chunk, or where every variant shares one pass n_chunks whatever E is */
 } bl_stats;
 
 /* Measurement switches: environment variables BLACKLIGHT_AMD_<NAME>, read ONCE by bl_init (never during a render) and echoed in
@@ -632,6 +634,41 @@ BL_API int bl_polarized_variant_electrons(const bl_ctx *ctx, int variant, bl_ele
 #define BL_MAX_SIGMA_CUTS 16
 BL_API int bl_set_sigma_cuts(bl_ctx *ctx, int n, const double *sigma_max);
 BL_API int bl_num_sigma_cuts(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own cut_sigma_max; -1: no context */
+/* Electron mixes of an UNPOLARIZED run (plasma_power_frac, plasma_p, plasma_gamma_min, plasma_gamma_max: which share of the electrons
+ * is a power law, the rest thermal) rendered by one bl_render - a fourth product axis, outermost. n = 0 (what a context starts with)
+ * clears the list: the parameter block's own four values apply. 1 <= n <= BL_MAX_ELECTRON_MIXES: with E = max(1, n) and M, U, S as
+ * above, bl_image_num_quantities is E * M * U * S times the single-render count and image row
+ * (((e * M + m) * U + u) * S + s) * n_q + q is row q of a render with mix e's four plasma_* values, model m, unit u and cut s in its
+ * parameter block; sample_num, sample_flags and the camera outputs come out once. Geodesics and located samples do not depend on the
+ * mix: changing the list between renders of a series keeps the records. n = 1 plans as a context with that mix in its block. Cameras
+ * multiply rays and compose unchanged.
+ * Checked when the call is made (BL_E_ARG, the mix's index in the text): power_frac must be finite, and p, gamma_min and gamma_max
+ * where power_frac != 0 - where it is zero they are not read, and bl_electron_mix_get returns them as given. The reference's warnings
+ * "Fraction of power-law electrons outside [0, 1]." and "Fraction of thermal electrons outside [0, 1]." go to bl_warnings, each at
+ * most once per call. Refused (BL_E_UNSUPPORTED): formula mode, polarized runs (bl_set_polarized_variants_electrons is their list),
+ * slow light, any mix with kappa_frac != 0 (the reference's unpolarized kappa absorptivity is undefined), and with n >= 2
+ * adaptive_max_level > 0 and render_num_images > 0 - as are bl_adaptive_refine, bl_write_output and the two checkpoint saves while
+ * n >= 2. A refused call changes nothing. Works on a BL_DEVICE_NONE context.
+ * Where the tolerant tier renders models, units and cuts in one pass it renders two mixes or more there too, provided every mix has a
+ * thermal part: the coefficient kernels write the sample's mix-free row with a thermal fraction of 1 (the kernels of a thermal run,
+ * the one with the locate step inside included: bl_stats.fused_variant stays 2), and bl_transfer_freq_kernel runs a workgroup per
+ * (256 rays, mix, model, unit, cut, frequency) that scales the thermal line by its mix's thermal fraction and adds its mix's power-law
+ * emissivity and absorptivity, formed from the same row (bl_stats.launches_shade = launches_transfer = n_chunks whatever E is) - each
+ * variant within the tier's tolerance of its exact image. Everything else runs one shading pass per variant over the shared samples
+ * (launches_shade = n_chunks * E * M * U * S): each variant's rows are the bits of a render with that mix in the parameter block, in
+ * the exact tier. The kernels of the passes are chosen once per render: a power law in any mix selects the ones that know power
+ * laws, and a thermal mix passes through them with zero fractions - in the exact tier the same bits. The tolerant tier has no kernel
+ * for a mix without a thermal part (power_frac = 1: the exact tier's render it, as they render a context with that mix in its block)
+ * and other kernels for thermal electrons alone than for a power law beside them; so a list that holds a mix without a thermal part
+ * beside others is rendered there run by run, a pass per variant - the neighbouring mixes of one of these three kinds as one render
+ * into their rows, each kind exactly as a context with such a mix in its block plans it (under bl_set_reproducible: that context's
+ * bits), the later runs from the resident geodesics where the record layout is the same. bl_stats then holds the last run's values
+ * with the launches and kernel times summed over the runs, arithmetic = BL_ARITH_TOLERANT if any run was tolerant, and n_mixes = E. */
+#define BL_MAX_ELECTRON_MIXES 16
+BL_API int bl_set_electron_mixes(bl_ctx *ctx, int n, const bl_electron_mix *mix);
+BL_API int bl_num_electron_mixes(const bl_ctx *ctx);             /* 0 = unset; -1: no context */
+/* Mix e of the list, 0 <= e < max(1, n); with no list, mix 0 is the parameter block's own. */
+BL_API int bl_electron_mix_get(const bl_ctx *ctx, int e, bl_electron_mix *out);
 /* Cameras (viewing angles: camera_th, camera_ph) rendered by one bl_render - the third axis of a model library beside snapshots and
  * plasma variants. n = 0 (what a context starts with): the parameter block's own camera. 1 <= n <= BL_MAX_CAMERAS: n (th, ph) pairs in
  * DEGREES, as camera_th and camera_ph are written in the .input file, converted exactly as those two keys are (val * pi / 180;
@@ -872,6 +909,7 @@ BL_API int bl_write_output_variant(bl_ctx *ctx, const char *path_override, const
  * component; appended where there is none):
  *     .mMMuUU   electron model MM (two digits, from 00) at density unit UU; both always present, 00 for a list that is not set
  *     .mMMuUUsSS  ... under sigma cut SS, where sigma cuts are set (bl_set_sigma_cuts): names without cuts are as above
+ *     .eEEmMMuUU[sSS]  ... with electron mix EE, where mixes are set (bl_set_electron_mixes): names without mixes are as above
  *     .vVV      polarized triple VV
  * image.npz -> image.m00u00.npz, image.m00u01.npz, ... image.m02u01.npz: names sort in variant order. V = 1: no tag.
  * BL_E_ARG: variant outside 0 .. V - 1, or buf too short; BL_E_MISSING / BL_E_INPUT as bl_write_output. */
