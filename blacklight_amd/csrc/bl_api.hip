@@ -437,25 +437,28 @@ const char *ElectronMixesRefusal(const bl_ctx *ctx, int n, const bl_electron_mix
 }
 
 // The variants of a render, in image-row order: the triples (each with its own cut_sigma_max where bl_set_polarized_variants_sigma gave
-// one, and its own electron mix where bl_set_polarized_variants_electrons gave one), else models x units x sigma cuts, model-major, then unit, then cut, with the parameter block's pair, unit and cut_sigma_max
-// where an axis is not set. The one reader of what the four setters stored.
-Variants ResolveVariants(const bl_ctx *ctx) {
+// one, and its own electron mix where bl_set_polarized_variants_electrons gave one), else the mixes of `mixes` x models x units x
+// sigma cuts - mix-major, then model, then unit, then cut (Variants::Index) - with the parameter block's mix, pair, unit and
+// cut_sigma_max where an axis is not set. The one reader of what the five setters stored.
+Variants ResolveVariants(const bl_ctx *ctx, MixRange mixes) {
   const bl_params &p = ctx->params;
   const std::vector<Variant> own = {{p.plasma_rat_low, p.plasma_rat_high, p.simulation_rho_cgs, p.cut_sigma_max, BlockMix(p)}};
   const std::vector<double> own_cut = {p.cut_sigma_max};
+  const int mix_end = std::min(mixes.end, static_cast<int>(ctx->mixes.size()));
+  const std::vector<bl_electron_mix> some_mixes(ctx->mixes.begin() + std::min(mixes.begin, mix_end), ctx->mixes.begin() + mix_end), own_mix = {BlockMix(p)};
   Variants v{ctx->triples, static_cast<int>(ctx->models.size()), static_cast<int>(ctx->units.size()), static_cast<int>(ctx->triples.size()),
-             static_cast<int>(ctx->sigma_cuts.size()), static_cast<int>(ctx->mixes.size())};
-  const std::vector<bl_electron_mix> own_mix = {BlockMix(p)};
+             static_cast<int>(ctx->sigma_cuts.size()), static_cast<int>(some_mixes.size()), {}};
   if (!ctx->triples_cut)
     for (Variant &triple : v.list) triple.sigma_max = p.cut_sigma_max;
   if (!ctx->triples_mix)
     for (Variant &triple : v.list) triple.mix = BlockMix(p);
-  // (an unpolarized run's electron mixes are the outermost axis: the rows of models x units x cuts repeat per mix)
   if (v.n_pol == 0)
-    for (const bl_electron_mix &mix : v.n_mixes > 0 ? ctx->mixes : own_mix)
+    for (const bl_electron_mix &mix : v.n_mixes > 0 ? some_mixes : own_mix)
       for (const Variant &model : v.n_models > 0 ? ctx->models : own)
         for (const Variant &unit : v.n_units > 0 ? ctx->units : own)
           for (const double sigma_max : v.n_cuts > 0 ? ctx->sigma_cuts : own_cut) v.list.push_back({model.rat_low, model.rat_high, unit.rho, sigma_max, mix});
+  const auto extent = [](int n_set) { return n_set > 0 ? n_set : 1; };   // (0, not set: the parameter block's one)
+  v.extent = {extent(v.n_mixes), extent(v.n_models), extent(v.n_units), extent(v.n_pol > 0 ? v.n_pol : v.n_cuts)};
   return v;
 }
 
@@ -1372,6 +1375,11 @@ const bl_camera_frame *bl_internal_frame(const bl_ctx *ctx) { return &ctx->frame
 const double *bl_internal_frequencies(const bl_ctx *ctx, int *count) {
   *count = static_cast<int>(ctx->frequencies.size());
   return ctx->frequencies.data();
+}
+bl_variant_place bl_internal_variant_place(const bl_ctx *ctx, int variant) {
+  const Variants vs = ResolveVariants(ctx);
+  const VariantPlace at = vs.At(variant);
+  return {at.e, at.m, at.u, at.s, vs.n_mixes > 0, vs.n_cuts > 0, vs.n_pol > 0};
 }
 int bl_internal_fail(bl_ctx *ctx, int code, const char *message) {
   ctx->last_error = std::string("Error: ") + message + "\n";

@@ -123,19 +123,40 @@ inline void Check(hipError_t err, const char *what) {
 }  // namespace blhost
 using namespace blhost;
 
-// One image of a render: an electron model (R_low, R_high), a density unit (simulation_rho_cgs) and a sigma cut (cut_sigma_max).
-// Variants: a render's, in image-row order and never empty (ResolveVariants), with the number of models, units, polarized triples
-// and sigma cuts as set - 0: the parameter block's.
-// ... and, for a polarized variant, an electron distribution (bl_set_polarized_variants_electrons); ResolveVariants gives every
-// variant one - the parameter block's where none was set (what the setters store without one is zero and not read).
+// One image of a render: an electron model (R_low, R_high), a density unit (simulation_rho_cgs), a sigma cut (cut_sigma_max) and an
+// electron mix. ResolveVariants gives every variant all four - the parameter block's where a setter stored none (what the setters
+// store of an axis that is not theirs is zero and not read).
 struct Variant {
   double rat_low, rat_high, rho, sigma_max;
   bl_electron_mix mix;
 };
-// ... or, for an unpolarized one, the mix of the outermost axis (bl_set_electron_mixes): n_mixes of them, 0: the parameter block's.
+// Where a variant lies on the four axes: electron mix e, model m, unit u, sigma cut s
+struct VariantPlace {
+  int e, m, u, s;
+};
+// The mixes of bl_ctx::mixes that one render covers: [begin, end), clipped to the list - by default all of it - and whether that
+// render runs a shading pass per variant whatever its variants could share (bl_render: a list rendered as several runs).
+struct MixRange {
+  int begin = 0, end = std::numeric_limits<int>::max();
+  bool pass_per_variant = false;
+};
+// A render's variants, in image-row order and never empty (ResolveVariants): the product electron mixes x models x units x sigma
+// cuts of an unpolarized run, or the triples of a polarized one.
+// n_mixes ... n_cuts and n_pol are the axes as set, 0: the parameter block's - what refusals and file tags ask. `extent` is the shape
+// as rendered, every axis at least 1. Index and At are the one place that knows the row order, v = ((e M + m) U + u) S + s; its
+// device-side counterpart, which must agree, is the channel decode of bl_transfer_freq_kernel (bl_transfer.hip).
+// Polarized triples are one flat axis of their own, with a pair, a unit, a cut and a mix per triple. It stands where the cuts stand:
+// extent = (1, 1, 1, n_pol) and triple t lies at (0, 0, 0, t), which is what the plan wants of it - a BlShadeCold block per cut is
+// then a block per triple (PlanVariantCuts).
 struct Variants {
   std::vector<Variant> list;
   int n_models, n_units, n_pol, n_cuts, n_mixes;
+  VariantPlace extent;
+  int Index(int e, int m, int u, int s) const { return ((e * extent.m + m) * extent.u + u) * extent.s + s; }
+  VariantPlace At(int v) const {
+    const int pair = v / extent.s, model = pair / extent.u;
+    return {model / extent.m, model % extent.m, pair % extent.u, v % extent.s};
+  }
 };
 
 struct bl_ctx {
@@ -179,7 +200,7 @@ struct bl_ctx {
   bool triples_mix = false;          // ... and an electron mix each (bl_set_polarized_variants_electrons); else the parameter block's
   std::vector<double> sigma_cuts;
   std::vector<bl_electron_mix> mixes;   // bl_set_electron_mixes(): the outermost axis of an unpolarized run's variants; empty: the parameter block's mix
-  bool mix_runs = false;             // bl_render is rendering the list run by run (it holds a mix without a thermal part): a pass per variant
+                                        // (written by StoreElectronMixes alone: a render reads the part of it that its MixRange names)
   // bl_set_cameras(): the viewing angles as given (degrees) and each camera's frame; empty: the parameter block's camera. `frame`
   // above is what a one-camera render starts its rays from - the block's own frame (block_frame), or the one camera of a list of
   // one, so that such a render plans and runs exactly as a context with those angles in its block; two cameras or more reach the
@@ -393,7 +414,8 @@ inline void Warn(bl_ctx *ctx, const std::string &message) { ctx->warnings += "Wa
 int Fail(bl_ctx *ctx, const Failure &failure);   // sets bl_last_error (or the global error when ctx is null), returns the code
 void EnsureStreams(bl_ctx *ctx);
 void DropResident(bl_ctx *ctx);   // the root level's kept geodesics go (bl_render.hip)
-Variants ResolveVariants(const bl_ctx *ctx);   // (bl_api.hip) what bl_render's plan, bl_num_variants and bl_image_num_quantities read
+// (bl_api.hip) what bl_render's plan, bl_num_variants and bl_image_num_quantities read; `mixes`: the part of the mix list to resolve
+Variants ResolveVariants(const bl_ctx *ctx, MixRange mixes = {});
 inline bool UnitCut(const bl_params &p) {   // a cut the density unit enters is set: rho, n_e, p_gas or B
   return p.cut_rho_min >= 0.0 || p.cut_rho_max >= 0.0 || p.cut_n_e_min >= 0.0 || p.cut_n_e_max >= 0.0 || p.cut_p_gas_min >= 0.0 || p.cut_p_gas_max >= 0.0
       || p.cut_b_min >= 0.0 || p.cut_b_max >= 0.0;

@@ -432,18 +432,16 @@ int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, int camer
   // (the camera's tag in front of the variant's, inside one dot group: .c01m00u02)
   char camera_tag[16] = "", tag[32] = "";
   if (n_cameras >= 2) std::snprintf(camera_tag, sizeof camera_tag, "c%02d", camera);
+  const bl_variant_place at = bl_internal_variant_place(ctx, variant);
   if (n_variants < 2) {
-  } else if (bl_num_polarized_variants(ctx) >= 1) {
+  } else if (at.polarized) {
     std::snprintf(tag, sizeof tag, "v%02d", variant);
   } else {
-    // (variant = ((e M + m) U + u) S + s; the cut's tag only where cuts are set, the mix's - in front - only where mixes are: names
-    // without either are as ever)
-    const int n_mixes = bl_num_electron_mixes(ctx), per_mix = n_variants / std::max(1, n_mixes), inner = variant % per_mix;
-    const int n_units = std::max(1, bl_num_density_units(ctx)), n_cuts = bl_num_sigma_cuts(ctx), pair = inner / std::max(1, n_cuts);
-    char mix_tag[8] = "";
-    if (n_mixes >= 1) std::snprintf(mix_tag, sizeof mix_tag, "e%02d", variant / per_mix);
-    if (n_cuts >= 1) std::snprintf(tag, sizeof tag, "%sm%02du%02ds%02d", mix_tag, pair / n_units, pair % n_units, inner % n_cuts);
-    else std::snprintf(tag, sizeof tag, "%sm%02du%02d", mix_tag, pair / n_units, pair % n_units);
+    // (the cut's tag only where cuts are set, the mix's - in front - only where mixes are: names without either are as ever)
+    char mix_tag[8] = "", cut_tag[8] = "";
+    if (at.mixes_set) std::snprintf(mix_tag, sizeof mix_tag, "e%02d", at.e);
+    if (at.cuts_set) std::snprintf(cut_tag, sizeof cut_tag, "s%02d", at.s);
+    std::snprintf(tag, sizeof tag, "%sm%02du%02d%s", mix_tag, at.m, at.u, cut_tag);
   }
   const std::string group = std::string(".") + camera_tag + tag;
   const std::string::size_type slash = path->find_last_of('/');

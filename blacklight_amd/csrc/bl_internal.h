@@ -17,6 +17,13 @@ bl_slow_state *bl_internal_slow_state(bl_ctx *ctx);
 void bl_internal_warn(bl_ctx *ctx, const char *message);   // appends "Warning: ...\n" to bl_warnings
 const bl_camera_frame *bl_internal_frame(const bl_ctx *ctx);
 const double *bl_internal_frequencies(const bl_ctx *ctx, int *count);
+// Where image `variant` of a render lies on the axes mix x model x unit x sigma cut (Variants::At, bl_ctx.h), and which axes a
+// file tag names: the mixes and the cuts where they are set, the triples of a polarized run as one axis of their own
+struct bl_variant_place {
+  int e, m, u, s;
+  bool mixes_set, cuts_set, polarized;
+};
+bl_variant_place bl_internal_variant_place(const bl_ctx *ctx, int variant);
 int bl_internal_fail(bl_ctx *ctx, int code, const char *message);   // sets bl_last_error, returns code
 
 #endif

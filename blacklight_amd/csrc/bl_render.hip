@@ -114,8 +114,9 @@ struct RenderJob {
   size_t park_capacity = 0;
   int quad_grid = 0;          // waves of bl_geodesic_quad_kernel
   int n_nu = 0, n_q = 0, max_steps = 0;
-  // The render's variants (ResolveVariants: models x units x sigma cuts, model-major, or the triples of a polarized run), each with n_q_model image
+  // The render's variants (ResolveVariants: mixes x models x units x sigma cuts, or the triples of a polarized run), each with n_q_model image
   // rows (n_q = variants x n_q_model); the shading stage runs once per variant over the chunk's samples (variant_passes)
+  MixRange mixes;                   // ... of these mixes of the context's list (bl_render: all of it, or one run of several)
   Variants variants;
   int n_q_model = 0, variant_passes = 1;
   bool variants_one_pass = false;   // ... or all of them in one pass: one gather, one lane per (ray, model, unit, cut, frequency) in the transfer kernel
@@ -338,9 +339,8 @@ void BindVariant(RenderJob &job, int v) {
   // (a polarized variant's electron mix: the constants in the argument block here, kappa in the pass's BlShadeCold below; an
   // unpolarized variant's likewise where bl_set_electron_mixes set a list - none of those has kappa electrons)
   if (job.variants.n_pol > 0 || job.variants.n_mixes > 0) BindElectronConstants(FillElectronConstants(variant.mix, job.ctx->polarized), job.ctx->polarized, pl, job.sa);
-  const int n_s = std::max(1, job.variants.n_cuts), n_u = std::max(1, job.variants.n_units);   // (v = ((e n_m + m) n_u + u) n_s + s)
-  const int u = (v / n_s) % n_u, s = job.variants.n_pol > 0 ? v : v % n_s;   // (polarized variants: a cut each, PlanVariantCuts)
-  job.sa.cold = job.ctx->d_shade_cold.ptr + ((job.cold_units > 1 ? u : 0) * job.cold_cuts + (job.cold_cuts > 1 ? s : 0));
+  const VariantPlace at = job.variants.At(v);   // (polarized variants: a cut each, PlanVariantCuts)
+  job.sa.cold = job.ctx->d_shade_cold.ptr + ((job.cold_units > 1 ? at.u : 0) * job.cold_cuts + (job.cold_cuts > 1 ? at.s : 0));
   pl.cut_mask = (pl.cut_mask & ~(1 << 11)) | (variant.sigma_max >= 0.0 ? 1 << 11 : 0);   // (bit 11: cut_sigma_max, FoldFastCuts' order)
   pl.any_cell_cut = pl.cut_mask != 0 ? 1 : 0;
   job.xa.image = job.image + static_cast<size_t>(v) * job.n_q_model * static_cast<size_t>(job.n_rays);
@@ -398,7 +398,7 @@ void PlanJob(RenderJob &job) {
   if (d->n_rays > 0x7fffffffll) throw Failure{BL_E_ARG, "Too many rays in one bl_render call."};
   if (d->level < 0 || d->level > p.adaptive_max_level) throw Failure{BL_E_ARG, "Adaptive level out of range."};
   if (d->level > 0 && (d->block_locs == nullptr || d->n_blocks <= 0)) throw Failure{BL_E_ARG, "Refined level needs block_locs."};
-  job.variants = ResolveVariants(ctx);
+  job.variants = ResolveVariants(ctx, job.mixes);
   const Variants &vs = job.variants;
   job.any_power = p.plasma_power_frac != 0.0, job.any_kappa = p.plasma_kappa_frac != 0.0, job.every_thermal = ctx->plasma_thermal_frac != 0.0;
   if (vs.n_mixes > 0) {
@@ -418,7 +418,7 @@ void PlanJob(RenderJob &job) {
       Warn(ctx, "Unpolarized kappa-distribution electrons: kappa_aa_high_i, which the reference leaves uninitialised here, is (3 / kappa)^4.75 + 0.6.");
     ctx->kappa_warned = true;
   }
-  if (const char *why = ElectronMixesRefusal(ctx, vs.n_mixes, ctx->mixes.data())) throw Failure{BL_E_UNSUPPORTED, why};
+  if (const char *why = ElectronMixesRefusal(ctx, vs.n_mixes, ctx->mixes.data() + job.mixes.begin)) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = ElectronModelsRefusal(ctx, vs.n_models)) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = DensityUnitsRefusal(ctx, vs.n_units)) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = PolarizedVariantsRefusal(ctx, vs.n_pol)) throw Failure{BL_E_UNSUPPORTED, why};
@@ -513,10 +513,10 @@ void PlanJob(RenderJob &job) {
   // what no model enters (BlFreqInputs, built with base_rho) and the transfer kernel forms each model's 1 / (k T_e) and scales the row
   // to each unit (everything else: one shading pass per variant over the shared samples, LaunchShadingStage)
   // (two electron mixes or more: the rows fold a thermal fraction of 1 and every transfer workgroup applies its own mix, power law
-  // included - every mix has a thermal part, or job.fast is off. One mix is a context with it in its block. A list rendered run by run -
-  // bl_render: it holds a mix without a thermal part - runs a pass per variant.)
-  const bool mixes_one_pass = vs.n_mixes >= 2 && !ctx->mix_runs;
-  job.variants_one_pass = job.variant_passes >= 2 && job.fast && (mixes_one_pass || (!job.any_power && vs.n_mixes < 2)) && !job.tau_row && !job.aux && ctx->render_num_images == 0
+  // included - every mix has a thermal part, or job.fast is off. One mix is a context with it in its block. A run of a list rendered as
+  // several - bl_render: it holds a mix without a thermal part - runs a pass per variant, whatever its own mixes could share.)
+  const bool mixes_one_pass = vs.n_mixes >= 2;
+  job.variants_one_pass = job.variant_passes >= 2 && job.fast && !job.mixes.pass_per_variant && (mixes_one_pass || (!job.any_power && vs.n_mixes < 2)) && !job.tau_row && !job.aux && ctx->render_num_images == 0
       && !ThetaECut(p) && !(vs.n_units >= 2 && UnitCut(p))
       && !((vs.n_units >= 2 || vs.n_cuts >= 2 || mixes_one_pass) && job.n_rays * job.n_nu * job.variant_passes >= (1ll << 31));   // (the transfer kernel's lanes of a chunk fit one grid)
   if (job.variants_one_pass) {
@@ -1925,9 +1925,9 @@ void BuildShadeArgs(RenderJob &job) {
   for (int b = 0; b < job.n_cold; b++) {
     std::memcpy(colds.data() + b * sizeof(BlShadeCold), &cold, sizeof(BlShadeCold));
     if (job.n_cold > 1) {
-      // (model-major, then unit, then cut: the first model's variants are the (unit, cut) pairs)
-      const int n_s = std::max(1, job.variants.n_cuts), u = b / job.cold_cuts, s = b % job.cold_cuts;
-      const Variant &variant = job.variants.list[(job.cold_units > 1 ? u : 0) * n_s + (job.cold_cuts > 1 ? s : 0)];
+      // (the first mix's and model's variant of the block's unit and cut)
+      const int u = job.cold_units > 1 ? b / job.cold_cuts : 0, s = job.cold_cuts > 1 ? b % job.cold_cuts : 0;
+      const Variant &variant = job.variants.list[job.variants.Index(0, 0, u, s)];
       BlShadeCold unit_cold;
       std::memcpy(static_cast<void *>(&unit_cold), &cold, sizeof(BlShadeCold));
       BlPlasmaDevice unit_pl = sa.plasma;
@@ -2076,13 +2076,11 @@ void BuildTransferArgs(RenderJob &job) {
     const double g1 = use_p ? 1.0 : 1.0 / (ctx->grid.meta.plasma_gamma_i - 1.0);
     const double g2 = use_p ? 1.0 : 1.0 / (ctx->grid.meta.plasma_gamma_e - 1.0);
     const Variants &vs = job.variants;
-    // (model-major, then unit, then cut: model m's variants start at m n_u n_s, the first model's are the (unit, cut) pairs)
-    const int n_u = std::max(1, vs.n_units), n_s = std::max(1, vs.n_cuts);
-    const int n_e = vs.n_mixes >= 2 ? vs.n_mixes : 1;   // (mix-major above the models: the first mix's variants are the (model, unit, cut) triples)
-    xa.n_models = static_cast<int>(vs.list.size()) / (n_e * n_u * n_s);   // (no models set: the parameter block's pair is model 0)
+    // (an axis' table: of the variants that lie at 0 on every other axis - Variants::Index)
+    xa.n_models = vs.extent.m;   // (no models set: the parameter block's pair is model 0)
     for (int m = 0; m < xa.n_models; m++) {
-      xa.model_k1[m] = vs.list[m * n_u * n_s].rat_high * g1;
-      xa.model_k2[m] = vs.list[m * n_u * n_s].rat_low * g1;
+      xa.model_k1[m] = vs.list[vs.Index(0, m, 0, 0)].rat_high * g1;
+      xa.model_k2[m] = vs.list[vs.Index(0, m, 0, 0)].rat_low * g1;
     }
     xa.model_k3 = p.plasma_ne_ni * g2;
     // Two units or more: the rows hold base_rho's x at unit frequency (1 / b_unit: x = nu / nu_s, nu_s ~ nu_c ~ |b| b_unit) and s_j
@@ -2094,7 +2092,7 @@ void BuildTransferArgs(RenderJob &job) {
       FoldUnits(ctx, job.base_rho, ctx->plasma_thermal_frac, base, k);   // (k is not read)
       xa.n_units = vs.n_units;
       for (int u = 0; u < vs.n_units; u++) {
-        FoldUnits(ctx, vs.list[u * n_s].rho, ctx->plasma_thermal_frac, unit, k);
+        FoldUnits(ctx, vs.list[vs.Index(0, 0, u, 0)].rho, ctx->plasma_thermal_frac, unit, k);
         xa.unit_x[u] = base.b_unit / unit.b_unit;
         xa.unit_j[u] = (unit.d_unit * unit.b_unit) / (base.d_unit * base.b_unit);
       }
@@ -2104,8 +2102,10 @@ void BuildTransferArgs(RenderJob &job) {
     if (vs.n_cuts >= 2) {
       static_assert(BL_TRANSFER_MAX_CUTS == BL_MAX_SIGMA_CUTS, "sigma cut constants");
       xa.n_cuts = vs.n_cuts;
-      for (int c = 0; c < vs.n_cuts; c++)
-        xa.sigma_max[c] = vs.list[c].sigma_max >= 0.0 ? vs.list[c].sigma_max : std::numeric_limits<double>::infinity();
+      for (int c = 0; c < vs.n_cuts; c++) {
+        const double sigma_max = vs.list[vs.Index(0, 0, 0, c)].sigma_max;
+        xa.sigma_max[c] = sigma_max >= 0.0 ? sigma_max : std::numeric_limits<double>::infinity();
+      }
     }
     // Two electron mixes or more: the rows hold a thermal fraction of 1 (PlanJob); of mix e what FillElectronConstants gives of it,
     // folded with the products of fast_k - at base_rho, thermal fraction 1: the rows' - that turn a row into the power-law terms
@@ -2113,14 +2113,13 @@ void BuildTransferArgs(RenderJob &job) {
     if (vs.n_mixes >= 2) {
       static_assert(BL_TRANSFER_MAX_MIXES == BL_MAX_ELECTRON_MIXES, "mix constants");
       xa.n_mixes = vs.n_mixes;
-      const int per_mix = xa.n_models * n_u * n_s;
       constexpr double kPlanck = 6.62607015e-27;   // (the kernels' kH, bl_kernel_util.h: the rows' q1.x is kH s_nu)
       BlPlasmaDevice base{};
       double k[8];
       FoldUnits(ctx, job.base_rho, 1.0, base, k);
       xa.power_k0 = 1.0 / (k[4] * k[7]);
       for (int e = 0; e < vs.n_mixes; e++) {
-        const ElectronConstants ec = FillElectronConstants(vs.list[e * per_mix].mix, false);
+        const ElectronConstants ec = FillElectronConstants(vs.list[vs.Index(e, 0, 0, 0)].mix, false);
         const bool power = ec.power_frac != 0.0;   // (else p, power_jj and power_aa are not defined: zeros, which the kernel selects past)
         xa.mix_thermal[e] = ec.thermal_frac;
         xa.mix_power_frac[e] = ec.power_frac;
@@ -2748,7 +2747,7 @@ void FinishStats(RenderJob &job) {
   st.mirror_pairs = job.mirror ? 1 : 0;
   st.local_angles = job.local_angles ? 1 : 0;
   st.n_cameras = job.n_cameras;
-  st.n_mixes = std::max(1, job.variants.n_mixes);
+  st.n_mixes = ResolveVariants(ctx).extent.e;   // (the whole list's, whichever of its mixes this render covers)
   st.tail_policy = job.reuse ? ctx->resident.tail_policy : (job.park ? BL_TAIL_QUAD : (job.split_long ? BL_TAIL_SPLIT : BL_TAIL_WIDE));
   ctx->stats = st;
   if (ctx->debug_counters) {   // kernels built with -DBL_GEO_STATS fill these
@@ -2835,8 +2834,8 @@ void EnsureStreams(bl_ctx *ctx) {
 }  // namespace blhost
 
 namespace {
-// One render of the context as it stands, render_lock held (bl_render below)
-int RenderLocked(bl_ctx *ctx, const bl_render_desc *d) {
+// One render of the context as it stands, over the mixes of `mixes`, render_lock held (bl_render below)
+int RenderLocked(bl_ctx *ctx, const bl_render_desc *d, MixRange mixes) {
   auto drain = [ctx]() {   // leave no chunk half collected behind: a later call starts from idle streams
     if (ctx->stream_few != nullptr) (void)hipStreamSynchronize(ctx->stream_few);
     if (ctx->stream_most != nullptr) (void)hipStreamSynchronize(ctx->stream_most);
@@ -2851,6 +2850,7 @@ int RenderLocked(bl_ctx *ctx, const bl_render_desc *d) {
       RenderJob job;
       job.ctx = ctx;
       job.d = d;
+      job.mixes = mixes;
       job.allow_split = allow_split;
       job.allow_reuse = allow_reuse;
       try {
@@ -2908,49 +2908,55 @@ int RenderLocked(bl_ctx *ctx, const bl_render_desc *d) {
 // What kind of electrons a mix has, as far as the tolerant tier's choice of kernels goes: no thermal part (no tolerant kernel: the exact
 // tier's), thermal electrons alone, thermal electrons and a power law
 int MixKind(const bl_electron_mix &mix) { return ThermalFraction(mix) == 0.0 ? 0 : (mix.power_frac == 0.0 ? 1 : 2); }
+
+// The renders that one bl_render call is made of: one over the whole mix list, but for the one case below.
+// Electron mixes in the tolerant tier: a render chooses its kernels once, and a mix without a thermal part has none in that tier (the
+// exact tier's render it, as they render a context with that mix in its block), so a list that holds such a mix beside others cannot
+// share the one pass, and a mix of thermal electrons alone has other kernels (the locate step inside, the factors of several
+// frequencies) than one with a power law. So that every mix's rows are then what a context with that mix in its block renders in this
+// tier, such a list is split into the runs of neighbouring mixes of one kind, each a render of its own with a pass per variant.
+// (The exact tier has one set of kernels for all, and a list whose mixes all have a thermal part one pass or one choice: one render.)
+std::vector<MixRange> MixRuns(const bl_ctx *ctx, const bl_render_desc *d) {
+  const std::vector<bl_electron_mix> &all = ctx->mixes;
+  bool one_kind = true, every_thermal = true;
+  for (const bl_electron_mix &mix : all) one_kind = one_kind && MixKind(mix) == MixKind(all[0]), every_thermal = every_thermal && MixKind(mix) != 0;
+  if (ctx->arithmetic != BL_ARITH_TOLERANT || one_kind || every_thermal || d->image == nullptr) return {MixRange{}};
+  std::vector<MixRange> runs;
+  const int n = static_cast<int>(all.size());
+  for (int begin = 0, end = 0; begin < n; begin = end) {
+    for (end = begin + 1; end < n && MixKind(all[end]) == MixKind(all[begin]);) end++;
+    runs.push_back({begin, end, true});
+  }
+  return runs;
+}
+
+// A run's statistics into the render's (zeros before the first run): the launches and kernel times summed over the runs, the
+// tolerant tier if any run ran in it, everything else the last run's
+void FoldRunStats(bl_stats &render, const bl_stats &run) {
+  const bl_stats before = render;
+  render = run;
+  for (int32_t bl_stats::*launches : {&bl_stats::launches_geodesic, &bl_stats::launches_locate, &bl_stats::launches_shade, &bl_stats::launches_transfer})
+    render.*launches += before.*launches;
+  for (float bl_stats::*ms : {&bl_stats::ms_geodesic, &bl_stats::ms_locate, &bl_stats::ms_shade, &bl_stats::ms_transfer, &bl_stats::ms_total, &bl_stats::ms_wall})
+    render.*ms += before.*ms;
+  if (before.arithmetic == BL_ARITH_TOLERANT) render.arithmetic = BL_ARITH_TOLERANT;
+}
 }  // namespace
 
+// A render is its runs (MixRuns: one, as a rule), each over its mixes of the context's list - which no render changes - into its rows
+// of the image (the mixes are the outermost axis: a run's rows lie together), a later run from the resident geodesics where its
+// record layout is the earlier one's. bl_stats is the runs' folded (FoldRunStats). A run that fails ends the call with its code.
 extern "C" int bl_render(bl_ctx *ctx, const bl_render_desc *d) {
   if (ctx == nullptr || d == nullptr) return BL_E_ARG;
   std::lock_guard<std::mutex> render_guard(ctx->render_lock);   // (bl_set_grid on another host thread stages the next snapshot meanwhile: bl_api.hip)
-  // Electron mixes in the tolerant tier: a render chooses its kernels once, and a mix without a thermal part has none in that tier (the
-  // exact tier's render it, as they render a context with that mix in its block), so a list that holds such a mix beside others cannot
-  // share the one pass, and a mix of thermal electrons alone has other kernels (the locate step inside, the factors of several
-  // frequencies) than one with a power law. So that every mix's rows are then what a context with that mix in its block renders in this
-  // tier, such a list is rendered run by run, a pass per variant - the runs of neighbouring mixes of one kind, each a render of its
-  // own into its rows of the image (the mixes are the outermost axis: a run's rows lie together), the later ones from the resident
-  // geodesics where their record layout is the same. The statistics are the last run's, with the launches and kernel times summed.
-  // (The exact tier has one set of kernels for all, and a list whose mixes all have a thermal part one pass or one choice: one render.)
-  const std::vector<bl_electron_mix> all = ctx->mixes;
-  bool one_kind = true, every_thermal = true;
-  for (const bl_electron_mix &mix : all) one_kind = one_kind && MixKind(mix) == MixKind(all[0]), every_thermal = every_thermal && MixKind(mix) != 0;
-  if (ctx->arithmetic != BL_ARITH_TOLERANT || one_kind || every_thermal || d->image == nullptr) return RenderLocked(ctx, d);
-  ctx->mix_runs = true;
-  const size_t rows_per_mix = static_cast<size_t>(bl_image_num_quantities(ctx)) / all.size();
-  bl_stats sum{};
-  int rc = BL_OK;
-  for (size_t begin = 0, end = 0; begin < all.size() && rc == BL_OK; begin = end) {
-    for (end = begin + 1; end < all.size() && MixKind(all[end]) == MixKind(all[begin]);) end++;
-    ctx->mixes.assign(all.begin() + begin, all.begin() + end);
-    bl_render_desc run = *d;
-    run.image = d->image + begin * rows_per_mix * static_cast<size_t>(d->n_rays);
-    rc = RenderLocked(ctx, &run);
-    const bl_stats &st = ctx->stats;
-    sum.launches_geodesic += st.launches_geodesic, sum.launches_locate += st.launches_locate;
-    sum.launches_shade += st.launches_shade, sum.launches_transfer += st.launches_transfer;
-    sum.ms_geodesic += st.ms_geodesic, sum.ms_locate += st.ms_locate, sum.ms_shade += st.ms_shade, sum.ms_transfer += st.ms_transfer;
-    sum.ms_total += st.ms_total, sum.ms_wall += st.ms_wall;
-    sum.arithmetic = (begin == 0 || st.arithmetic == BL_ARITH_TOLERANT) ? st.arithmetic : sum.arithmetic;
+  const Variants whole = ResolveVariants(ctx);
+  bl_stats stats{};
+  for (const MixRange &run : MixRuns(ctx, d)) {
+    bl_render_desc part = *d;
+    part.image = d->image + static_cast<size_t>(whole.Index(run.begin, 0, 0, 0)) * ctx->image_num_quantities * static_cast<size_t>(d->n_rays);
+    if (const int rc = RenderLocked(ctx, &part, run)) return rc;
+    FoldRunStats(stats, ctx->stats);
   }
-  ctx->mixes = all;
-  ctx->mix_runs = false;
-  if (rc != BL_OK) return rc;
-  bl_stats &st = ctx->stats;
-  st.launches_geodesic = sum.launches_geodesic, st.launches_locate = sum.launches_locate;
-  st.launches_shade = sum.launches_shade, st.launches_transfer = sum.launches_transfer;
-  st.ms_geodesic = sum.ms_geodesic, st.ms_locate = sum.ms_locate, st.ms_shade = sum.ms_shade, st.ms_transfer = sum.ms_transfer;
-  st.ms_total = sum.ms_total, st.ms_wall = sum.ms_wall;
-  st.arithmetic = sum.arithmetic;
-  st.n_mixes = static_cast<int32_t>(all.size());
+  ctx->stats = stats;
   return BL_OK;
 }

@@ -256,6 +256,29 @@ def test_variant_rows_are_mix_major(bl):
         assert (ctx.num_electron_mixes, ctx.num_variants) == (3, 12)
 
 
+def test_every_row_of_the_product_has_its_tag_and_its_values(bl, tmp_path):
+    """E x M x U x S = 3 x 2 x 2 x 2, all 24 rows: row v = ((e 2 + m) 2 + u) 2 + s is named eEEmMMuUUsSS and holds model m's pair,
+    unit u's value and cut s's value."""
+    params = _case("sim_multifreq", output_file=str(tmp_path / "image.npz"))
+    with bl.Context(bl.Params.from_dict(params), device=BL_DEVICE_NONE) as ctx:
+        ctx.set_electron_mixes(MIXES[:3])
+        ctx.set_electron_models(PAIRS_HIGH, rat_low=PAIRS_LOW)
+        ctx.set_density_units(UNITS)
+        ctx.set_sigma_cuts(CUTS)
+        assert ctx.num_variants == 24
+        (low, high, rho, cut), _ = ctx._variants()
+        assert len(low) == len(high) == len(rho) == len(cut) == 24
+        seen = set()
+        for v in range(24):
+            tag = re.fullmatch(r"image\.e(\d\d)m(\d\d)u(\d\d)s(\d\d)\.npz", os.path.basename(ctx.variant_output_path(0, v)))
+            assert tag, (v, ctx.variant_output_path(0, v))
+            e, m, u, s = (int(digits) for digits in tag.groups())
+            assert e < 3 and m < 2 and u < 2 and s < 2 and v == ((e * 2 + m) * 2 + u) * 2 + s, (v, e, m, u, s)
+            assert (low[v], high[v], rho[v], cut[v]) == (PAIRS_LOW[m], PAIRS_HIGH[m], UNITS[u], CUTS[s]), v
+            seen.add((e, m, u, s))
+        assert len(seen) == 24
+
+
 def test_names_carry_the_mix_in_front(bl, tmp_path):
     params = _case("sim_dp_interp", output_file=str(tmp_path / "image.npz"))
     with bl.Context(bl.Params.from_dict(params), device=BL_DEVICE_NONE) as ctx:

@@ -160,6 +160,36 @@ def test_tolerant_passes_equal_fresh_renders():
     assert got["stats"].launches_shade == len(mixes) * singles[0]["stats"].launches_shade
 
 
+def test_tolerant_runs_times_the_product():
+    """Two runs of different kinds - the second starts at row offset 8 n_q - over models x units x cuts: every row the bits of its
+    fresh render (a wrong row offset of a run, or a wrong (unit, cut) block of cut thresholds in a run's passes, shows here), and the
+    context holds after the render what was set before it.
+    (Before the runs became ranges the plan receives, the thermal run of this list still took the one pass over models x units x
+    cuts: launches_shade 9, its eight images within 1.0e-14 per pixel of their fresh renders and not their bits - DESIGN.md 4h.)"""
+    import blacklight_amd as bl
+    fx, params, grid = _case("sim_powerlaw")
+    mixes = [THERMAL, PURE]
+    with bl.Context(bl.Params.from_dict(params)) as ctx:
+        ctx.set_grid(grid)
+        ctx.set_arithmetic("tolerant")
+        ctx.set_reproducible(True)
+        n_q = ctx.num_quantities
+        ctx.set_electron_models([h for _, h in MODELS], rat_low=[lo for lo, _ in MODELS])
+        ctx.set_density_units(UNITS)
+        ctx.set_sigma_cuts(CUTS)
+        ctx.set_electron_mixes(mixes)
+        before = (ctx.num_electron_mixes, ctx.electron_mixes, ctx.num_variants, ctx.num_quantities, ctx._variants())
+        assert before[0] == 2 and before[2:4] == (16, 16 * n_q)
+        assert [{key: mix[key] for key in THERMAL} for mix in before[1]] == mixes
+        got = ctx.render()
+        assert (ctx.num_electron_mixes, ctx.electron_mixes, ctx.num_variants, ctx.num_quantities, ctx._variants()) == before
+    singles = _check_bits(got, ("sim_powerlaw", ()), params, grid, "tolerant", mixes, pairs=MODELS, units=UNITS, cuts=CUTS, reproducible=True)
+    st = got["stats"]
+    assert st.n_mixes == 2
+    assert st.launches_shade == 16 * singles[0]["stats"].launches_shade
+    assert 1 <= st.launches_geodesic <= 2
+
+
 # ---------------------------------------------------------------------------------------------------------------- 4, 5: one pass
 @pytest.mark.parametrize("case, overrides, switches", [
     ("sim_dp_interp", {}, ()),                                # one frequency, no spin
@@ -260,12 +290,13 @@ def test_no_list_renders_what_it_rendered(name, capfd, monkeypatch):
 def test_cameras_times_mixes():
     fx, params, grid = _case("sim_dp_interp", camera_resolution=16)
     cameras = [(60.0, 0.0), (30.0, 45.0)]
-    mixes = [MIXES[0], MIXES[1]]
     n_pix = 16 * 16
-    for tier, reproducible in (("exact", False), ("tolerant", True)):
+    # (the last input: a mix without a thermal part beside one with - the tolerant tier renders that list as two runs)
+    for tier, reproducible, mixes in (("exact", False, [MIXES[0], MIXES[1]]), ("tolerant", True, [MIXES[0], MIXES[1]]), ("tolerant", True, [OWN, PURE])):
+        runs = PURE in mixes
         got = _render(params, grid, tier, mixes, cameras=cameras, reproducible=reproducible)
-        assert got["image"].shape[1] == 2 * n_pix and got["stats"].n_cameras == 2
-        assert got["stats"].launches_geodesic == 1
+        assert got["image"].shape[1] == 2 * n_pix and got["stats"].n_cameras == 2 and got["stats"].n_mixes == 2
+        assert (1 <= got["stats"].launches_geodesic <= 2) if runs else got["stats"].launches_geodesic == 1
         for c, (th, ph) in enumerate(cameras):
             one = _render(dict(params, camera_th=th, camera_ph=ph), grid, tier, mixes, reproducible=reproducible)
             view = slice(c * n_pix, (c + 1) * n_pix)
@@ -275,6 +306,12 @@ def test_cameras_times_mixes():
             else:   # (the one pass, per-sample records under bl_set_reproducible: a ray's lane does what it does in the one-camera render)
                 assert np.array_equal(np.isnan(got["image_by_mix"][:, :, view]), np.isnan(one["image_by_mix"]))
                 assert gu.same_bits(got["image_by_mix"][:, :, view], one["image_by_mix"]).all(), (tier, c)
+            if runs:   # ... and every mix's slice against a context of one camera with that mix in its block
+                key = ("sim_dp_interp", (("camera", c), ("camera_resolution", 16)))
+                for e, mix in enumerate(mixes):
+                    fresh = _fresh(key, dict(params, camera_th=th, camera_ph=ph), grid, tier, mix, reproducible=reproducible)
+                    assert np.array_equal(got["sample_num"][view], fresh["sample_num"])
+                    assert gu.same_bits(got["image_by_mix"][e][:, view], fresh["image"]).all(), (tier, c, e)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 8: a series

@@ -2,7 +2,7 @@
 costs a render that does not use it.
 
     python tools/gpu_electron_mixes.py [--res 1024] [--grid 256] [--mixes 2,6,16] [--tiers exact,tolerant] [--parent TREE]
-                                       [--step-timeout 900] [--out profiles/electron_mixes.json]
+                                       [--runs 3] [--step-timeout 900] [--out profiles/electron_mixes.json]
 
 1024^2 camera over the 256^3 mock (blacklight_amd.mock), 230 GHz: bench.py's default workload. One invocation measures everything, step
 by step: every step is a child process of its own (this file with --step) under a time limit of its own, and the first step that fails or
@@ -16,6 +16,9 @@ runs out of time ends the run - nothing is started on the device after it. The s
                  alternating: three processes per tree. NAME is `frame` (bench.py's workload), `truecolor` (bench.py --workload
                  truecolor1024x64) or `models6` (six electron models in the tolerant tier's one pass). `within_parent_spread` says whether
                  this tree's median exceeds the parent's by no more than the parent's own min-to-max spread over its processes.
+  runs           one render of a list that the tolerant tier renders run by run (thermal, three power laws, a mix without a thermal part:
+                 three runs, a pass per variant), in this tree and in --parent's like `unused`: --runs processes per tree, alternating, each
+                 the median wall time of bl_render over five renders; geodesic reuse as a context starts with it.
 
 Both sides of a mixes comparison integrate their geodesics (bl_set_geodesic_reuse(0)); bl_set_grid is outside the timed region, and
 every timed render follows an untimed one of the same context (the first render of a context allocates its scratch). Times are host wall
@@ -67,9 +70,10 @@ def run_step(args):
     params = dict(bench.WORKLOAD, camera_resolution=args.res)
     grid = mock.generate(n_r=args.grid, n_th=args.grid, n_ph=args.grid)
 
-    def context(p, tier, mixes=None, highs=None):
+    def context(p, tier, mixes=None, highs=None, reuse=False):
         ctx = bl.Context(bl.Params.from_dict(p), device=0)
-        ctx.set_geodesic_reuse(False)
+        if not reuse:
+            ctx.set_geodesic_reuse(False)
         ctx.set_arithmetic(tier)
         ctx.set_grid(grid)
         if highs is not None:
@@ -93,6 +97,17 @@ def run_step(args):
             times.append(ms)
         return times, out
 
+    if kind == "runs":   # a list with a mix without a thermal part: tests/test_gpu_electron_mixes.py's MIXES + [PURE]
+        mixes = [dict(power_frac=0.0, p=2.5, gamma_min=1.0, gamma_max=1000.0), dict(power_frac=0.3, p=2.5, gamma_min=1.0, gamma_max=1000.0),
+                 dict(power_frac=0.5, p=3.5, gamma_min=10.0, gamma_max=1.0e5), dict(power_frac=0.05, p=2.2, gamma_min=2.0, gamma_max=500.0),
+                 dict(power_frac=1.0, p=2.8, gamma_min=5.0, gamma_max=1.0e4)]
+        ctx = context(params, "tolerant", mixes, reuse=True)
+        times, out = five(ctx)
+        st = out["stats"]
+        ctx.close()
+        print(json.dumps(dict(step=args.step, ms=float(np.median(times)), times_ms=times, n_mixes=st.n_mixes, launches_geodesic=st.launches_geodesic,
+                              launches_shade=st.launches_shade, n_chunks=st.n_chunks, arithmetic=st.arithmetic)))
+        return
     if kind == "unused":   # models6: six electron models, the tolerant tier's one pass
         ctx = context(params, "tolerant", None, [float(x) for x in np.geomspace(1.0, 160.0, 6)])
         times, out = five(ctx)
@@ -138,6 +153,7 @@ def main():
     ap.add_argument("--tiers", default="exact,tolerant")
     ap.add_argument("--unused", default="frame,truecolor,models6")
     ap.add_argument("--processes", type=int, default=3, help="processes per tree of an `unused` comparison")
+    ap.add_argument("--runs", type=int, default=3, help="processes per tree of the `runs` comparison (0: none)")
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit, for the `unused` comparisons")
     ap.add_argument("--step-timeout", type=int, default=900)
     ap.add_argument("--step", default=None)
@@ -149,19 +165,24 @@ def main():
     for name in [n for n in args.unused.split(",") if n]:
         for _ in range(args.processes):   # (alternating: parent, this, parent, this, ...)
             steps += ([(f"unused:{name}", args.parent)] if args.parent else []) + [(f"unused:{name}", HERE)]
+    for _ in range(args.runs):
+        steps += ([("runs", args.parent)] if args.parent else []) + [("runs", HERE)]
     results = []
 
     def save():   # (after every step: a run cut short keeps what it measured)
         doc = dict(res=args.res, grid=args.grid, results=[r for r in results if r["step"].startswith("mixes")], unused={})
-        for name in sorted({r["step"].split(":")[1] for r in results if r["step"].startswith("unused")}):
-            by_tree = {tree: [r["ms"] for r in results if r["step"] == f"unused:{name}" and r["tree"] == tree] for tree in ("this", "parent")}
+        for step in sorted({r["step"] for r in results if not r["step"].startswith("mixes")}):
+            by_tree = {tree: [r["ms"] for r in results if r["step"] == step and r["tree"] == tree] for tree in ("this", "parent")}
             row = {tree + "_ms": values for tree, values in by_tree.items() if values}
             if by_tree["this"] and by_tree["parent"]:
                 this_median, parent_median = sorted(by_tree["this"])[len(by_tree["this"]) // 2], sorted(by_tree["parent"])[len(by_tree["parent"]) // 2]
                 spread = max(by_tree["parent"]) - min(by_tree["parent"])
                 row.update(this_median_ms=this_median, parent_median_ms=parent_median, parent_spread_ms=spread,
                            within_parent_spread=bool(this_median - parent_median <= spread))
-            doc["unused"][name] = row
+            if step == "runs":
+                doc["runs"] = row
+            else:
+                doc["unused"][step.split(":")[1]] = row
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)
