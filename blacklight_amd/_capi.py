@@ -73,6 +73,19 @@ class SweepLists(C.Structure):
     _fields_ = [("sweep", C.POINTER(Sweep)), ("cuts", C.POINTER(SweepCuts)), ("cameras", C.POINTER(SweepCameras)), ("electrons", C.POINTER(SweepElectrons))]
 
 
+class SweepFrequencies(C.Structure):
+    """bl_sweep_frequencies: the sweep_frequency list of a .input file (Hz), in a struct of its own beside the four above."""
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("hz", C.c_double * BL_MAX_SWEEP)]
+
+
+class SweepAll(C.Structure):
+    """bl_sweep_all: pointers to all five structs (NULL: that struct's keys are validated and dropped)."""
+    _fields_ = [("sweep", C.POINTER(Sweep)), ("cuts", C.POINTER(SweepCuts)), ("cameras", C.POINTER(SweepCameras)), ("electrons", C.POINTER(SweepElectrons)),
+                ("frequencies", C.POINTER(SweepFrequencies))]
+
+
+BL_MAX_FREQUENCIES = 1024
+
 ELECTRON_MIX_KEYS = ("power_frac", "p", "gamma_min", "gamma_max", "kappa_frac", "kappa", "w")
 
 
@@ -179,6 +192,13 @@ def lib():
     L.bl_sweep_electrons_resolve.argtypes = [C.POINTER(SweepElectrons), C.POINTER(Sweep), C.c_void_p, C.POINTER(C.c_int), C.POINTER(Sweep), C.c_void_p,
                                              C.c_char_p, C.c_size_t]
     L.bl_apply_sweep_lists.argtypes = [C.c_void_p, C.POINTER(SweepLists)]
+    L.bl_params_set_line_sweep_all.argtypes = [C.c_void_p, C.POINTER(SweepAll), C.c_char_p, C.c_char_p, C.c_size_t]
+    L.bl_params_read_file_sweep_all.argtypes = [C.c_void_p, C.POINTER(SweepAll), C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t]
+    L.bl_apply_sweep_all.argtypes = [C.c_void_p, C.POINTER(SweepAll)]
+    L.bl_set_frequencies.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.bl_num_frequencies.argtypes = [C.c_void_p]
+    L.bl_write_output_frequency.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(OutputDesc), C.c_int, C.c_int, C.c_int]
+    L.bl_frequency_output_path.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.bl_set_cameras.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.bl_num_cameras.argtypes = [C.c_void_p]
     L.bl_cameras_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -24,7 +24,6 @@ class Context:
             raise _capi.BlacklightError(rc, L.bl_last_global_error().decode())
         self._ctx = handle
         self._grid_keepalive = None
-        self.n_freq = int(params.get("image_num_frequencies"))
         self.resolution = int(params.get("camera_resolution"))
         if getattr(params, "has_sweep", False):   # sweep_* keys of the .input grammar: the same call the command-line driver makes
             try:
@@ -39,13 +38,13 @@ class Context:
         return cls(Params.from_file(path), device=device)
 
     def apply_sweep(self, params=None):
-        """bl_apply_sweep_lists: the sweep_rat_low / sweep_rat_high / sweep_rho_cgs lists of `params` (default: this context's) as electron
+        """bl_apply_sweep_all: the sweep_rat_low / sweep_rat_high / sweep_rho_cgs lists of `params` (default: this context's) as electron
         models and density units, or as polarized triples (with the electron lists: tuples), its sweep_cut_sigma_max list as sigma cuts
-        and its sweep_camera_th / sweep_camera_ph lists as cameras - all of them or, where one is refused, none. An empty sweep changes
-        nothing."""
+        its sweep_camera_th / sweep_camera_ph lists as cameras and its sweep_frequency list as frequencies - all of them or, where one
+        is refused, none. An empty sweep changes nothing."""
         params = params or self.params
         if params.has_sweep:
-            self._check(self._lib.bl_apply_sweep_lists(self._ctx, C.byref(params.sweep_lists)))
+            self._check(self._lib.bl_apply_sweep_all(self._ctx, C.byref(params.sweep_all)))
 
     @property
     def num_variants(self):
@@ -61,13 +60,37 @@ class Context:
         self._check(self._lib.bl_variants_get(self._ctx, n, *(column.ctypes.data_as(C.c_void_p) for column in columns), C.byref(flags)))
         return columns.tolist(), flags.value
 
-    def variant_output_path(self, snapshot=0, variant=0, camera=0):
+    def variant_output_path(self, snapshot=0, variant=0, camera=0, frequency=None):
         """The file name write_output(variant=..., camera=...) uses without `path` (bl_camera_output_path): output_file, the file number
         of a series, and in front of the extension a tag .mMMuUU (.mMMuUUsSS with sigma cuts set, .eEE in front with electron mixes set) / .vVV when the context renders
-        several variants, with .cCC in front of it when it renders several cameras (image.c01m00u02.npz)."""
+        several variants, with .cCC in front of it when it renders several cameras (image.c01m00u02.npz). frequency = l: the name
+        write_output(frequency=l, ...) uses (bl_frequency_output_path), with the tag fFF after the camera's (image.c01f02m00u02.npz)."""
         buf = C.create_string_buffer(4096)
+        if frequency is not None:
+            self._check(self._lib.bl_frequency_output_path(self._ctx, int(snapshot), int(frequency), int(camera), int(variant), buf, len(buf)))
+            return buf.value.decode()
         self._check(self._lib.bl_camera_output_path(self._ctx, int(snapshot), int(camera), int(variant), buf, len(buf)))
         return buf.value.decode()
+
+    # ------------------------------------------------------------------ frequencies
+    def set_frequencies(self, hz):
+        """Render an explicit list of observing frequencies (Hz) in one render (bl_set_frequencies): a scalar or a sequence, in any
+        order, each with the meaning of image_frequency; an empty sequence restores the parameter block's own list. The list's length
+        is the context's frequency count from then on: frequencies, n_freq, num_quantities and the row offsets are those of a block
+        with image_num_frequencies = len(hz), and row l of a quantity is what a context with hz[l] as its one image_frequency
+        renders. Geodesics stay resident."""
+        values = np.ascontiguousarray(np.atleast_1d(np.asarray(hz, dtype=np.float64)).ravel())
+        self._check(self._lib.bl_set_frequencies(self._ctx, int(values.size), values.ctypes.data_as(C.c_void_p)))
+
+    @property
+    def num_frequencies(self):
+        """The length of the list set_frequencies() set (bl_num_frequencies); 0 when the parameter block's own list is rendered."""
+        return self._lib.bl_num_frequencies(self._ctx)
+
+    @property
+    def n_freq(self):
+        """Frequencies a render carries: the list's length, else the parameter block's image_num_frequencies."""
+        return self.num_frequencies or int(self.params.get("image_num_frequencies"))
 
     # ------------------------------------------------------------------ cameras
     def set_cameras(self, th, ph=None):
@@ -790,12 +813,15 @@ class Context:
             out["block_locs"] = nxt
             levels.append(out)
 
-    def write_output(self, levels, path=None, snapshot=0, variant=None, camera=None):
+    def write_output(self, levels, path=None, snapshot=0, variant=None, camera=None, frequency=None):
         """OutputWriter::Write (reference output_writer.cpp:169-274); `levels` as from render_adaptive. variant = v: image v of a
         render of several variants ([render()]: the rows of all of them) as a file of its own (bl_write_output_variant) - what a
         context with that variant in its parameter block writes; without `path` the name is variant_output_path(snapshot, v).
         camera = c: camera c of a render of several cameras (bl_write_output_camera; with variant = v, that variant of it) - what a
-        context with that camera's angles in its parameter block writes from the camera's slice of every row and record."""
+        context with that camera's angles in its parameter block writes from the camera's slice of every row and record.
+        frequency = l: the file of ONE frequency of the render (bl_write_output_frequency; with camera = c and variant = v, of that
+        camera and variant) - what a context with image_num_frequencies = 1 and that image_frequency writes; without `path` the name
+        is variant_output_path(snapshot, v, c, frequency=l)."""
         d = _capi.OutputDesc()
         d.adaptive_num_levels = len(levels) - 1
         d.snapshot = snapshot
@@ -820,7 +846,9 @@ class Context:
                 keep.append(records)
                 d.level[index].camera = records.ctypes.data_as(C.c_void_p)
         target = None if path is None else str(path).encode()
-        if camera is not None:
+        if frequency is not None:
+            self._check(self._lib.bl_write_output_frequency(self._ctx, target, C.byref(d), int(frequency), int(camera or 0), int(variant or 0)))
+        elif camera is not None:
             self._check(self._lib.bl_write_output_camera(self._ctx, target, C.byref(d), int(camera), int(variant or 0)))
         elif variant is None:
             self._check(self._lib.bl_write_output(self._ctx, target, C.byref(d)))

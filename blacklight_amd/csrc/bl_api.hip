@@ -267,10 +267,15 @@ void ValidateRadiation(bl_ctx *ctx) {
 
   // geometry data and image rows (:419-520)
   ctx->frame.mass_msun = simulation ? p.simulation_m_msun : p.formula_mass * kC * kC / kGGMsun;
-  // image rows and their offsets (radiation_integrator.cpp:436-520); polarization is rejected above
+}
+
+// Image rows and their offsets (radiation_integrator.cpp:436-520) for nf frequencies: the parameter block's image_num_frequencies in
+// bl_init, the length of bl_set_frequencies' list once one is set. Reads what ValidateRadiation left (polarized, render_num_images).
+void BuildImageRows(bl_ctx *ctx, int nf) {
+  const bl_params &p = ctx->params;
+  const bool simulation = p.model_type == BL_MODEL_SIMULATION;
   BlAuxImages &A = ctx->aux_images;
   A = BlAuxImages{};
-  const int nf = p.image_num_frequencies;
   A.image_light = p.image_light;
   A.image_time = p.image_time;
   A.image_length = p.image_length;
@@ -433,6 +438,14 @@ const char *ElectronMixesRefusal(const bl_ctx *ctx, int n, const bl_electron_mix
   if (n >= 2 && ctx->render_num_images > 0) return "Electron mixes: renderings come out once; n >= 2 mixes need render_num_images = 0.";
   if (n >= 2 && p.checkpoint_geodesic_save) return "Electron mixes: a geodesic checkpoint is saved by a render of one image; n >= 2 mixes need checkpoint_geodesic_save = false.";
   if (n >= 2 && p.checkpoint_sample_save) return "Electron mixes: a sample checkpoint is saved by a render of one image; n >= 2 mixes need checkpoint_sample_save = false.";
+  return nullptr;
+}
+
+// Why a list of n frequencies cannot be rendered by this context (nullptr: it can). bl_set_frequencies and bl_render's plan both ask.
+const char *FrequenciesRefusal(const bl_ctx *ctx, int n) {
+  if (n <= 0) return nullptr;
+  if (ctx->params.checkpoint_geodesic_load)
+    return "Frequencies: a geodesic checkpoint carries its own frequency list, which replaces the context's (checkpoint_geodesic_load = true).";
   return nullptr;
 }
 
@@ -621,6 +634,30 @@ void StoreCameras(bl_ctx *ctx, std::vector<bl_ctx::Camera> list) {   // (the res
   ctx->cameras_uploaded = false;
   ctx->frame = ctx->cameras.size() == 1 ? ctx->cameras[0].frame : ctx->block_frame;
 }
+
+// ... the frequencies, 0 <= n <= BL_MAX_FREQUENCIES (n = 0: the parameter block's own list again)
+Refused CheckFrequencies(const bl_ctx *ctx, int n, const double *hz) {
+  const bl_params &p = ctx->params;
+  if (n < 0 || n > BL_MAX_FREQUENCIES || (n > 0 && hz == nullptr))
+    return Failure{BL_E_ARG, "bl_set_frequencies needs 0 <= n <= " + std::to_string(BL_MAX_FREQUENCIES) + " and the array of frequencies."};
+  for (int l = 0; l < n; l++)
+    if (!std::isfinite(hz[l]) || !(hz[l] > 0.0))
+      return Failure{BL_E_ARG, "bl_set_frequencies: frequency " + std::to_string(l) + " is not a finite value > 0."};
+  if (const char *why = FrequenciesRefusal(ctx, n)) return Failure{BL_E_UNSUPPORTED, why};
+  // (bl_init's check of the block, radiation_integrator.cpp:231-236, with the list's length for image_num_frequencies)
+  if (p.adaptive_max_level > 0 && n >= 2 && (!Has(p, BL_P_adaptive_frequency_num) || p.adaptive_frequency_num < 1 || p.adaptive_frequency_num > n))
+    return Failure{BL_E_ARG, "Must choose adaptive_frequency_num from 1 to image_num_frequencies."};
+  return std::nullopt;
+}
+// (geodesics and located samples stay: no frequency enters them. The rows and their offsets follow the list's length through the code
+// bl_init built them with.)
+void StoreFrequencies(bl_ctx *ctx, int n, const double *hz) {
+  if (n == 0 && ctx->frequencies_set == 0) return;   // (nothing set: the list is bl_init's - or a loaded checkpoint's - as it stands)
+  if (n > 0) ctx->frequencies.assign(hz, hz + n);
+  else BuildFrequencies(ctx);
+  ctx->frequencies_set = n;
+  BuildImageRows(ctx, static_cast<int>(ctx->frequencies.size()));
+}
 }  // namespace
 }  // namespace blhost
 
@@ -670,6 +707,7 @@ int bl_init(const bl_params *p, int device, bl_ctx **out) {
     ValidateGeodesic(ctx);
     ValidateRadiation(ctx);
     BuildFrequencies(ctx);
+    BuildImageRows(ctx, static_cast<int>(ctx->frequencies.size()));
     bl_camera_frame_build(ctx->params, ctx->st, &ctx->frame);
     ctx->block_frame = ctx->frame;
     if (device == BL_DEVICE_NONE) {   // host-only context: validation, camera frame, refinement, writer
@@ -1129,7 +1167,23 @@ int bl_variants_get(const bl_ctx *ctx, int n, double *rat_low, double *rat_high,
   return BL_OK;
 }
 
+int bl_set_frequencies(bl_ctx *ctx, int n, const double *hz) {
+  if (ctx == nullptr) return BL_E_ARG;
+  if (const Refused refused = CheckFrequencies(ctx, n, hz)) return Fail(ctx, *refused);
+  std::lock_guard<std::mutex> guard(ctx->render_lock);
+  StoreFrequencies(ctx, n, hz);
+  return BL_OK;
+}
+
+int bl_num_frequencies(const bl_ctx *ctx) { return ctx != nullptr ? ctx->frequencies_set : -1; }
+
 int bl_apply_sweep_lists(bl_ctx *ctx, const bl_sweep_lists *lists) {
+  if (ctx == nullptr || lists == nullptr) return BL_E_ARG;
+  const bl_sweep_all all = {lists->sweep, lists->cuts, lists->cameras, lists->electrons, nullptr};
+  return bl_apply_sweep_all(ctx, &all);
+}
+
+int bl_apply_sweep_all(bl_ctx *ctx, const bl_sweep_all *lists) {
   if (ctx == nullptr || lists == nullptr) return BL_E_ARG;
   const bl_sweep none = {};
   const bl_sweep *sweep = lists->sweep != nullptr ? lists->sweep : &none;
@@ -1168,6 +1222,18 @@ int bl_apply_sweep_lists(bl_ctx *ctx, const bl_sweep_lists *lists) {
   if (!refused && has_models) refused = CheckElectronModels(ctx, s.n_rat_low, s.rat_low, s.rat_high);
   if (!refused && has_units) refused = CheckDensityUnits(ctx, s.n_rho_cgs, s.rho_cgs);
   if (!refused && !electrons && has_cuts) refused = CheckSigmaCuts(ctx, cuts->n_sigma_max, cuts->sigma_max);
+  // ... and the frequencies, last: the list's own bound (a struct the parser did not fill), the setter's checks, and the sweep's own
+  // refusal - its files are one-frequency files, and a one-frequency run refines by its own image
+  const bl_sweep_frequencies *freq = lists->frequencies;
+  const bool has_frequencies = freq != nullptr && freq->n != 0;
+  if (!refused && has_frequencies) {
+    if (freq->n < 0 || freq->n > BL_MAX_SWEEP)
+      refused = Failure{BL_E_INPUT, "Too many entries in a sweep list: at most " + std::to_string(BL_MAX_SWEEP) + " for this build."};
+    else if (freq->n >= 2 && ctx->params.adaptive_max_level > 0)
+      refused = Failure{BL_E_UNSUPPORTED, "Frequencies: adaptive refinement reads one image; a sweep of n >= 2 frequencies needs adaptive_max_level = 0."};
+    else
+      refused = CheckFrequencies(ctx, freq->n, freq->hz);
+  }
   if (refused) return Fail(ctx, *refused);
   // 3. Every list the call carries, under one hold of the lock: no render sees half a sweep. A list it does not carry stays.
   {
@@ -1177,6 +1243,7 @@ int bl_apply_sweep_lists(bl_ctx *ctx, const bl_sweep_lists *lists) {
     if (has_models) StoreElectronModels(ctx, s.n_rat_low, s.rat_low, s.rat_high);
     if (has_units) StoreDensityUnits(ctx, s.n_rho_cgs, s.rho_cgs);
     if (has_cuts) StoreSigmaCuts(ctx, cuts->n_sigma_max, cuts->sigma_max);
+    if (has_frequencies) StoreFrequencies(ctx, freq->n, freq->hz);
   }
   for (const char *warning : warnings) Warn(ctx, warning);
   return BL_OK;

@@ -163,7 +163,8 @@ struct bl_ctx {
   bl_params params;
   bl_camera_frame frame;
   BlSpacetime st;
-  std::vector<double> frequencies;
+  std::vector<double> frequencies;   // what every render, query and writer reads: bl_set_frequencies' list, else the parameter block's
+  int frequencies_set = 0;           // ... the list's length, 0: the block's own (BuildFrequencies); its size() is the frequency count everywhere
   std::string last_error, warnings;
   int device = 0;
   int num_cus = 256;
@@ -349,6 +350,7 @@ struct bl_ctx {
     };
     std::vector<Segment> segments;
     std::vector<Chunk> chunks;
+    int kept_n_nu = 0;   // the frequency count the kept layout was partitioned for: the shading arrays' share grows with it, into the store
     // A root-level render of more than one chunk whose records were not kept: its key and the records it used (including the
     // partly filled blocks). The next render with this key integrates in the kept layout, with a store sized from that count.
     bool pending = false;
@@ -432,6 +434,7 @@ const char *PolarizedVariantsRefusal(const bl_ctx *ctx, int n);   // bl_set_pola
 const char *SigmaCutsRefusal(const bl_ctx *ctx, int n);        // bl_set_sigma_cuts (bl_api.hip)
 const char *CamerasRefusal(const bl_ctx *ctx, int n);          // bl_set_cameras (bl_api.hip)
 const char *ElectronMixesRefusal(const bl_ctx *ctx, int n, const bl_electron_mix *mix);   // bl_set_electron_mixes (bl_api.hip)
+const char *FrequenciesRefusal(const bl_ctx *ctx, int n);      // bl_set_frequencies (bl_api.hip)
 }  // namespace blhost
 
 #endif  // BLACKLIGHT_AMD_BL_CTX_H_

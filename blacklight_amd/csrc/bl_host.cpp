@@ -364,7 +364,10 @@ int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const i
   const long long n_pix = level == 0 ? static_cast<long long>(p.camera_resolution) * p.camera_resolution
                                      : static_cast<long long>(n_blocks) * block_num_pix;
   // row of I_nu at the chosen frequency (radiation_adaptive.cpp:166-167): rows 4 l + (I, Q, U, V) when polarized
-  const int freq_index = p.image_num_frequencies > 1 ? p.adaptive_frequency_num - 1 : 0;
+  // (of the context's frequencies: bl_set_frequencies' list where one is set, whose length the setter held adaptive_frequency_num to)
+  int n_nu = 0;
+  (void)bl_internal_frequencies(ctx, &n_nu);
+  const int freq_index = n_nu > 1 ? p.adaptive_frequency_num - 1 : 0;
   const bool polarized = p.model_type == BL_MODEL_SIMULATION && p.image_light && p.has[BL_P_image_polarization] && p.image_polarization;
   const double *row = image + static_cast<size_t>(freq_index) * (polarized ? 4 : 1) * n_pix;
   std::vector<double> block(block_num_pix);
@@ -419,7 +422,8 @@ int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const i
 namespace {
 
 // The file's name (output_writer.cpp:283-316 for a series) and, for one image of several, its tag (include/blacklight_amd.h)
-int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, int camera, int n_cameras, std::string *path) {
+// (frequency >= 0: the file of one frequency, bl_write_output_frequency - its tag fFF whatever the list's length)
+int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, int camera, int n_cameras, std::string *path, int frequency = -1) {
   const bl_params &p = *bl_internal_params(ctx);
   if (!p.has[BL_P_output_file]) return bl_internal_fail(ctx, BL_E_MISSING, "OutputWriter unable to find all needed values in input file.");
   *path = p.output_file.s;
@@ -428,10 +432,11 @@ int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, int camer
     if (!FormatFilename(p.output_file.s, file_number, path))
       return bl_internal_fail(ctx, BL_E_INPUT, "Invalid output_file for multiple runs.");
   }
-  if (n_variants < 2 && n_cameras < 2) return BL_OK;
-  // (the camera's tag in front of the variant's, inside one dot group: .c01m00u02)
-  char camera_tag[16] = "", tag[32] = "";
+  if (n_variants < 2 && n_cameras < 2 && frequency < 0) return BL_OK;
+  // (the camera's tag in front of the frequency's, that in front of the variant's, inside one dot group: .c01m00u02, .c01f02m00u02)
+  char camera_tag[32] = "", tag[32] = "";
   if (n_cameras >= 2) std::snprintf(camera_tag, sizeof camera_tag, "c%02d", camera);
+  if (frequency >= 0) std::snprintf(camera_tag + std::strlen(camera_tag), sizeof camera_tag - std::strlen(camera_tag), "f%02d", frequency);
   const bl_variant_place at = bl_internal_variant_place(ctx, variant);
   if (n_variants < 2) {
   } else if (at.polarized) {
@@ -453,7 +458,10 @@ int OutputPath(bl_ctx *ctx, int snapshot, int variant, int n_variants, int camer
 
 // bl_write_output, bl_write_output_variant and bl_write_output_camera: image `variant` of the n_variants the root level's rows hold, and
 // of every row and record the slice of `camera` of the n_cameras that lie side by side in it
-int WriteOutput(bl_ctx *ctx, const char *path_override, const bl_output_desc *d_given, int variant, int n_variants, int camera = 0, int n_cameras = 1) {
+// (frequency >= 0: the one-frequency file of that entry of the context's frequencies - bl_write_output_frequency, which has held the index
+// to the list and refused adaptive levels beside two frequencies or more)
+int WriteOutput(bl_ctx *ctx, const char *path_override, const bl_output_desc *d_given, int variant, int n_variants, int camera = 0, int n_cameras = 1,
+                int frequency = -1) {
   const bl_output_desc *d = d_given;
   if (d->level[0].image == nullptr && bl_image_num_quantities(ctx) > 0) return bl_internal_fail(ctx, BL_E_ARG, "bl_write_output needs the root image.");
   // Several cameras: the camera's share of the variant's rows, of the renderings and of the camera records, as the one-camera
@@ -480,20 +488,58 @@ int WriteOutput(bl_ctx *ctx, const char *path_override, const bl_output_desc *d_
     if (d->level[0].camera != nullptr) sliced.level[0].camera = d->level[0].camera + static_cast<size_t>(camera) * pixels * 4;
     d = &sliced;
   }
-  const int row_variant = n_cameras >= 2 ? 0 : variant;   // (a camera's slice holds the one variant's rows alone)
+  int row_variant = n_cameras >= 2 ? 0 : variant;   // (a camera's slice holds the one variant's rows alone)
   const bl_params &p = *bl_internal_params(ctx);
   const bl_camera_frame &frame = *bl_internal_frame(ctx);
   int n_nu = 0;
   const double *frequencies = bl_internal_frequencies(ctx, &n_nu);
   const int res = p.camera_resolution;
-  const int n_q = bl_image_num_quantities(ctx) / n_variants;
+  int n_q = bl_image_num_quantities(ctx) / n_variants;
   const size_t n_pix = static_cast<size_t>(res) * res;
+  // One frequency of several: the variant's rows of that frequency, in the order of a block with image_num_frequencies = 1
+  // (radiation_integrator.cpp:436-520: Stokes rows 4 l + a, then time, length, lambda, emission, tau by frequency, the cell values
+  // 7 l + n, crossings), gathered into one block; everything below then writes a one-frequency context's file
+  std::vector<double> frequency_image;
+  if (frequency >= 0 && n_nu >= 2) {
+    const bool sim = p.model_type == BL_MODEL_SIMULATION;
+    const int stride = (sim && p.image_light && p.has[BL_P_image_polarization] && p.image_polarization) ? 4 : 1;
+    std::vector<int> rows;
+    int at = 0;
+    const auto take = [&](bool on, int per_frequency, bool has_axis) {   // a quantity's rows: per_frequency for every frequency, or that many in all
+      if (!on) return;
+      for (int k = 0; k < per_frequency; k++) rows.push_back(at + (has_axis ? frequency * per_frequency : 0) + k);
+      at += has_axis ? n_nu * per_frequency : per_frequency;
+    };
+    take(p.image_light, stride, true);
+    take(p.image_time, 1, false);
+    take(p.image_length, 1, false);
+    take(p.image_lambda, 1, true);
+    take(p.image_emission, 1, true);
+    take(p.image_tau, 1, true);
+    take(sim && p.image_lambda_ave, 7, true);
+    take(sim && p.image_emission_ave, 7, true);
+    take(sim && p.image_tau_int, 7, true);
+    take(p.image_crossings, 1, false);
+    if (at != n_q) return bl_internal_fail(ctx, BL_E_STATE, "bl_write_output_frequency: the image rows do not add up to bl_image_num_quantities.");
+    if (d->level[0].image != nullptr) {
+      const double *from = d->level[0].image + static_cast<size_t>(row_variant) * n_q * n_pix;
+      frequency_image.resize(rows.size() * n_pix);
+      for (size_t q = 0; q < rows.size(); q++) std::memcpy(frequency_image.data() + q * n_pix, from + static_cast<size_t>(rows[q]) * n_pix, n_pix * sizeof(double));
+      if (d != &sliced) sliced = *d;
+      sliced.level[0].image = frequency_image.data();
+      d = &sliced;
+    }
+    row_variant = 0;
+    n_q = static_cast<int>(rows.size());
+    frequencies += frequency;
+    n_nu = 1;
+  }
 
   std::string path;
   if (path_override != nullptr && path_override[0] != '\0') {
     path = path_override;
   } else {
-    const int rc = OutputPath(ctx, d->snapshot, variant, n_variants, camera, n_cameras, &path);
+    const int rc = OutputPath(ctx, d->snapshot, variant, n_variants, camera, n_cameras, &path, frequency);
     if (rc != BL_OK) return rc;
   }
   std::ofstream stream(path, std::ios_base::out | std::ios_base::binary);
@@ -794,6 +840,46 @@ int bl_camera_output_path(bl_ctx *ctx, int snapshot, int camera, int variant, ch
   const int rc = OutputPath(ctx, snapshot, variant, n_variants, camera, n_cameras, &path);
   if (rc != BL_OK) return rc;
   if (path.size() + 1 > len) return bl_internal_fail(ctx, BL_E_ARG, "bl_camera_output_path: the buffer is too short for the name.");
+  std::memcpy(buf, path.c_str(), path.size() + 1);
+  return BL_OK;
+}
+
+namespace {
+// What bl_write_output_frequency and bl_frequency_output_path check alike: the three indices
+int CheckFrequencyFile(bl_ctx *ctx, const char *who, int frequency, int camera, int variant) {
+  int n_nu = 0;
+  (void)bl_internal_frequencies(ctx, &n_nu);
+  const int n_variants = bl_num_variants(ctx), n_cameras = std::max(1, bl_num_cameras(ctx));
+  const auto outside = [&](const char *what, int index, int n) {
+    return bl_internal_fail(ctx, BL_E_ARG, (std::string(who) + ": " + what + " " + std::to_string(index) + " outside 0 .. " + std::to_string(n - 1) + ".").c_str());
+  };
+  if (frequency < 0 || frequency >= n_nu) return outside("frequency", frequency, n_nu);
+  if (camera < 0 || camera >= n_cameras) return outside("camera", camera, n_cameras);
+  if (variant < 0 || variant >= n_variants) return outside("variant", variant, n_variants);
+  return BL_OK;
+}
+}  // namespace
+
+int bl_write_output_frequency(bl_ctx *ctx, const char *path_override, const bl_output_desc *d, int frequency, int camera, int variant) {
+  if (ctx == nullptr || d == nullptr) return BL_E_ARG;
+  if (const int rc = CheckFrequencyFile(ctx, "bl_write_output_frequency", frequency, camera, variant)) return rc;
+  int n_nu = 0;
+  (void)bl_internal_frequencies(ctx, &n_nu);
+  const int n_variants = bl_num_variants(ctx), n_cameras = std::max(1, bl_num_cameras(ctx));
+  if (n_nu >= 2 && d->adaptive_num_levels != 0)
+    return bl_internal_fail(ctx, BL_E_ARG, "bl_write_output_frequency: a one-frequency run refines by its own image; the file of one frequency of several has no adaptive levels.");
+  if ((n_variants >= 2 || n_cameras >= 2) && d->adaptive_num_levels != 0)
+    return bl_internal_fail(ctx, BL_E_ARG, "bl_write_output_frequency: a render of several cameras or variants has no adaptive levels.");
+  return WriteOutput(ctx, path_override, d, variant, n_variants, camera, n_cameras, frequency);
+}
+
+int bl_frequency_output_path(bl_ctx *ctx, int snapshot, int frequency, int camera, int variant, char *buf, size_t len) {
+  if (ctx == nullptr || buf == nullptr) return BL_E_ARG;
+  if (const int rc = CheckFrequencyFile(ctx, "bl_frequency_output_path", frequency, camera, variant)) return rc;
+  std::string path;
+  const int rc = OutputPath(ctx, snapshot, variant, bl_num_variants(ctx), camera, std::max(1, bl_num_cameras(ctx)), &path, frequency);
+  if (rc != BL_OK) return rc;
+  if (path.size() + 1 > len) return bl_internal_fail(ctx, BL_E_ARG, "bl_frequency_output_path: the buffer is too short for the name.");
   std::memcpy(buf, path.c_str(), path.size() + 1);
   return BL_OK;
 }

@@ -192,8 +192,9 @@ int main(int argc, char *argv[]) {
   static bl_sweep_cuts sweep_cuts;   // ... and sweep_cut_sigma_max, an axis of its own
   static bl_sweep_cameras sweep_cameras;   // ... and sweep_camera_th / sweep_camera_ph: several cameras per render, one file per (camera, variant)
   static bl_sweep_electrons sweep_electrons;   // ... and the seven electron lists: a polarized variant's distribution, no file of their own
-  const bl_sweep_lists sweep_lists = {&sweep, &sweep_cuts, &sweep_cameras, &sweep_electrons};
-  if (bl_params_read_file_sweep_lists(&params, &sweep_lists, argv[1], &num_runs, err, sizeof err) != BL_OK) {
+  static bl_sweep_frequencies sweep_frequencies;   // ... and sweep_frequency: several frequencies per render, one file per (camera, frequency, variant)
+  const bl_sweep_all sweep_lists = {&sweep, &sweep_cuts, &sweep_cameras, &sweep_electrons, &sweep_frequencies};
+  if (bl_params_read_file_sweep_all(&params, &sweep_lists, argv[1], &num_runs, err, sizeof err) != BL_OK) {
     std::cout << err;
     return 1;
   }
@@ -233,7 +234,7 @@ int main(int argc, char *argv[]) {
     // as the reference's do across thread counts. And so are runs over several devices: a frame and its tiles are then the same bits.
     if (params.adaptive_max_level > 0 || n_devices > 1) bl_set_reproducible(contexts[dev], 1);
     // the sweep on every device: a device's share of the frame then holds the rows of all variants, like the frame does
-    if (bl_apply_sweep_lists(contexts[dev], &sweep_lists) != BL_OK) {
+    if (bl_apply_sweep_all(contexts[dev], &sweep_lists) != BL_OK) {
       std::cout << bl_last_error(contexts[dev]);
       return 1;
     }
@@ -244,6 +245,7 @@ int main(int argc, char *argv[]) {
   const int n_q = bl_image_num_quantities(ctx);   // rows of one render: those of every variant of a sweep, one after another
   const int n_variants = bl_num_variants(ctx);
   const int n_cameras = std::max(1, bl_num_cameras(ctx));   // cameras of one render: the root level's rays are n_cameras x res^2 "virtual pixels"
+  const int n_frequencies = bl_num_frequencies(ctx);   // sweep_frequency: the frequencies of one render, a file each (0: the key is absent)
   const int bs = params.adaptive_max_level > 0 ? params.adaptive_block_size : 1;
   const bool want_camera = params.has[BL_P_output_camera] && params.output_camera && params.output_format == BL_OUTPUT_NPZ;
 
@@ -503,7 +505,16 @@ int main(int argc, char *argv[]) {
       out.level[l].render = n_render > 0 ? renders[l].data() : nullptr;
     }
     double t_write = Now();
-    if (n_cameras > 1) {
+    if (n_frequencies > 0) {
+      // one file of the reference's layout per (camera, frequency, variant): the rows of that frequency, gathered
+      for (int camera = 0; camera < n_cameras; camera++)
+        for (int frequency = 0; frequency < n_frequencies; frequency++)
+          for (int variant = 0; variant < n_variants; variant++)
+            if (bl_write_output_frequency(ctx, nullptr, &out, frequency, camera, variant) != BL_OK) {
+              std::cout << bl_last_error(ctx);
+              return 1;
+            }
+    } else if (n_cameras > 1) {
       // one file of the reference's layout per (camera, variant): the camera's slice of the variant's rows
       for (int camera = 0; camera < n_cameras; camera++)
         for (int variant = 0; variant < n_variants; variant++)
@@ -565,5 +576,9 @@ int main(int argc, char *argv[]) {
   if (sweep_cameras.n_th > 0 || sweep_cameras.n_ph > 0)
     std::cout << "blacklight_amd: " << n_cameras << " cameras per snapshot traced as one set of rays, one file per camera"
               << (n_variants > 1 ? " and variant" : "") << "; writing outputs: " << time_write << " s\n";
+  if (sweep_frequencies.n > 0)
+    std::cout << "blacklight_amd: " << n_frequencies << " frequencies per snapshot rendered over one set of geodesics, one file per frequency"
+              << (n_cameras > 1 ? (n_variants > 1 ? ", camera and variant" : " and camera") : (n_variants > 1 ? " and variant" : ""))
+              << "; writing outputs: " << time_write << " s\n";
   return 0;
 }

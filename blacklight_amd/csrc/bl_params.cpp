@@ -285,8 +285,8 @@ void ReadRender(bl_params *p, const std::string &key, const std::string &val) {
 // sweep_rat_low / sweep_rat_high / sweep_rho_cgs / sweep_cut_sigma_max: "a,b,c" (an extension: the reference has no lists). Stricter than the scalar keys:
 // every entry is a whole number text - nothing is left of it after the conversion -, none is empty, at most BL_MAX_SWEEP of them.
 // A kind of list beyond plain numbers names its entries in the error text and wants them finite (a unit: and positive).
-enum ListKind { kNumbers, kUnits, kSigmaCuts, kAngles, kElectrons };
-const char *const kListNoun[] = {nullptr, "density unit", "sigma cut", "angle", "value"};
+enum ListKind { kNumbers, kUnits, kSigmaCuts, kAngles, kElectrons, kFrequencies };
+const char *const kListNoun[] = {nullptr, "density unit", "sigma cut", "angle", "value", "frequency"};
 int ReadList(const std::string &key, const std::string &val, ListKind kind, double *out) {
   int count = 0;
   for (size_t at = 0; at <= val.size();) {
@@ -296,9 +296,10 @@ int ReadList(const std::string &key, const std::string &val, ListKind kind, doub
     char *end = nullptr;
     const double x = std::strtod(entry.c_str(), &end);
     if (end == entry.c_str() || *end != '\0') throw ParseFailure{"Invalid number (" + entry + ") in list (" + key + ") in input file."};
-    if (kind != kNumbers && !(std::isfinite(x) && (kind != kUnits || x > 0.0)))
+    const bool positive = kind == kUnits || kind == kFrequencies;
+    if (kind != kNumbers && !(std::isfinite(x) && (!positive || x > 0.0)))
       throw ParseFailure{std::string("Invalid ") + kListNoun[kind] + " (" + entry + ") in list (" + key + ") in input file: must be finite"
-                         + (kind == kUnits ? " and positive." : ".")};
+                         + (positive ? " and positive." : ".")};
     if (count >= BL_MAX_SWEEP)
       throw ParseFailure{"Too many entries in list (" + key + ") in input file: at most " + std::to_string(BL_MAX_SWEEP) + " for this build."};
     out[count++] = x;
@@ -322,8 +323,8 @@ const ElectronList kElectronLists[7] = {
     {"sweep_kappa", &bl_sweep_electrons::n_kappa, &bl_sweep_electrons::kappa},
     {"sweep_w", &bl_sweep_electrons::n_w, &bl_sweep_electrons::w}};
 
-// The sweep keys go beside the parameter block (the structs of a bl_sweep_lists, none of them null here), never into it; false: not a sweep key
-bool SetSweepKey(const bl_sweep_lists &lists, const std::string &key, const std::string &val) {
+// The sweep keys go beside the parameter block (the structs of a bl_sweep_all, none of them null here), never into it; false: not a sweep key
+bool SetSweepKey(const bl_sweep_all &lists, const std::string &key, const std::string &val) {
   bl_sweep *s = lists.sweep;
   bl_sweep_cuts *c = lists.cuts;
   bl_sweep_cameras *a = lists.cameras;
@@ -338,6 +339,7 @@ bool SetSweepKey(const bl_sweep_lists &lists, const std::string &key, const std:
   else if (key == "sweep_cut_sigma_max") c->n_sigma_max = ReadList(key, val, kSigmaCuts, c->sigma_max);
   else if (key == "sweep_camera_th") a->n_th = ReadList(key, val, kAngles, a->th);
   else if (key == "sweep_camera_ph") a->n_ph = ReadList(key, val, kAngles, a->ph);
+  else if (key == "sweep_frequency") lists.frequencies->n = ReadList(key, val, kFrequencies, lists.frequencies->hz);
   else return false;
   return true;
 }
@@ -422,7 +424,7 @@ int ResolveElectrons(const bl_sweep_electrons &e, const bl_sweep &s, const bl_pa
   return (polarized && (triples || first_key != nullptr)) ? n : 0;
 }
 
-void SetKeyValue(bl_params *p, const bl_sweep_lists &lists, const std::string &key, const std::string &val) {
+void SetKeyValue(bl_params *p, const bl_sweep_all &lists, const std::string &key, const std::string &val) {
   if (key.compare(0, 6, "sweep_") == 0 && SetSweepKey(lists, key, val)) return;
   // Compound keys first
   if (key == "cut_plane_origin") return ReadTriple(val, p, BL_P_cut_plane_origin_x);
@@ -471,21 +473,22 @@ void SetKeyValue(bl_params *p, const bl_sweep_lists &lists, const std::string &k
   throw ParseFailure{"Unknown key (" + key + ") in input file."};
 }
 
-// The structs of `lists` with a spare for every NULL member (and for all four without `lists`): the keys of a list not asked for are
+// The structs of `lists` with a spare for every NULL member (and for all five without `lists`): the keys of a list not asked for are
 // accepted and validated all the same
 struct SpareLists {
-  bl_sweep sweep; bl_sweep_cuts cuts; bl_sweep_cameras cameras; bl_sweep_electrons electrons;
+  bl_sweep sweep; bl_sweep_cuts cuts; bl_sweep_cameras cameras; bl_sweep_electrons electrons; bl_sweep_frequencies frequencies;
 };
-bl_sweep_lists AllLists(const bl_sweep_lists *lists, SpareLists *spare) {
-  bl_sweep_lists all = lists != nullptr ? *lists : bl_sweep_lists{};
+bl_sweep_all AllLists(const bl_sweep_all *lists, SpareLists *spare) {
+  bl_sweep_all all = lists != nullptr ? *lists : bl_sweep_all{};
   if (all.sweep == nullptr) all.sweep = &spare->sweep;
   if (all.cuts == nullptr) all.cuts = &spare->cuts;
   if (all.cameras == nullptr) all.cameras = &spare->cameras;
   if (all.electrons == nullptr) all.electrons = &spare->electrons;
+  if (all.frequencies == nullptr) all.frequencies = &spare->frequencies;
   return all;
 }
 
-void ParseLine(bl_params *p, const bl_sweep_lists &lists, std::string line) {
+void ParseLine(bl_params *p, const bl_sweep_all &lists, std::string line) {
   std::string stripped;
   stripped.reserve(line.size());
   for (unsigned char c : line)
@@ -518,10 +521,17 @@ int bl_params_set_line_sweeps_cameras(bl_params *p, bl_sweep *sweep, bl_sweep_cu
   return bl_params_set_line_sweep_lists(p, &lists, line, err, err_len);
 }
 
+// (the four-member struct's calls: forwards, the frequency list validated and dropped)
 int bl_params_set_line_sweep_lists(bl_params *p, const bl_sweep_lists *lists, const char *line, char *err, size_t err_len) {
+  if (lists == nullptr) return bl_params_set_line_sweep_all(p, nullptr, line, err, err_len);
+  const bl_sweep_all all = {lists->sweep, lists->cuts, lists->cameras, lists->electrons, nullptr};
+  return bl_params_set_line_sweep_all(p, &all, line, err, err_len);
+}
+
+int bl_params_set_line_sweep_all(bl_params *p, const bl_sweep_all *lists, const char *line, char *err, size_t err_len) {
   if (p == nullptr || line == nullptr) return BL_E_ARG;
   SpareLists spare = {};
-  const bl_sweep_lists all = AllLists(lists, &spare);
+  const bl_sweep_all all = AllLists(lists, &spare);
   try {
     ParseLine(p, all, line);
   } catch (const ParseFailure &failure) {
@@ -554,14 +564,21 @@ int bl_params_read_file_sweeps_cameras(bl_params *p, bl_sweep *sweep, bl_sweep_c
 }
 
 int bl_params_read_file_sweep_lists(bl_params *p, const bl_sweep_lists *lists, const char *path, int *num_runs, char *err, size_t err_len) {
+  if (lists == nullptr) return bl_params_read_file_sweep_all(p, nullptr, path, num_runs, err, err_len);
+  const bl_sweep_all all = {lists->sweep, lists->cuts, lists->cameras, lists->electrons, nullptr};
+  return bl_params_read_file_sweep_all(p, &all, path, num_runs, err, err_len);
+}
+
+int bl_params_read_file_sweep_all(bl_params *p, const bl_sweep_all *lists, const char *path, int *num_runs, char *err, size_t err_len) {
   if (p == nullptr || path == nullptr) return BL_E_ARG;
   bl_params_clear(p);
   SpareLists spare = {};
-  const bl_sweep_lists all = AllLists(lists, &spare);
+  const bl_sweep_all all = AllLists(lists, &spare);
   *all.sweep = bl_sweep{};
   *all.cuts = bl_sweep_cuts{};
   *all.cameras = bl_sweep_cameras{};
   *all.electrons = bl_sweep_electrons{};
+  *all.frequencies = bl_sweep_frequencies{};
   std::ifstream stream(path);
   if (!stream.is_open()) {
     SetError(err, err_len, "Could not open input file.");

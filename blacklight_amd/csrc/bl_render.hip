@@ -424,6 +424,7 @@ void PlanJob(RenderJob &job) {
   if (const char *why = PolarizedVariantsRefusal(ctx, vs.n_pol)) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = SigmaCutsRefusal(ctx, vs.n_cuts)) throw Failure{BL_E_UNSUPPORTED, why};
   if (const char *why = CamerasRefusal(ctx, static_cast<int>(ctx->cameras.size()))) throw Failure{BL_E_UNSUPPORTED, why};
+  if (const char *why = FrequenciesRefusal(ctx, ctx->frequencies_set)) throw Failure{BL_E_UNSUPPORTED, why};
   job.n_cameras = std::max<int>(1, static_cast<int>(ctx->cameras.size()));
   job.camera_table = job.n_cameras >= 2;
   // (two cameras or more render the root level only: adaptive_max_level is 0 with them, so the level check above has seen to it)
@@ -440,7 +441,10 @@ void PlanJob(RenderJob &job) {
   job.base_mix = first.mix;
   job.all_thermal = p.plasma_power_frac == 0.0 && p.plasma_kappa_frac == 0.0;
   for (const Variant &v : vs.list) job.all_thermal = job.all_thermal && ThermalOnly(v.mix);
-  job.n_nu = p.image_num_frequencies;
+  // (the context's frequencies, not the block's count: bl_set_frequencies' list where one is set, else what bl_init built of the block -
+  // or a loaded checkpoint's, of the block's length. Everything below that reads n_nu - the d_freq upload, the LDS table's bound, the
+  // freq_split and coef_split switches at four, the rows ctx->aux_images offsets - follows the list's length; its values enter no key.)
+  job.n_nu = static_cast<int>(ctx->frequencies.size());
   job.n_q_model = ctx->image_num_quantities;
   job.variant_passes = static_cast<int>(vs.list.size());
   job.n_q = job.n_q_model * job.variant_passes;
@@ -749,7 +753,10 @@ void DecideReuse(RenderJob &job) {
   if (job.keepable) BuildReuseKeys(job);
   // (resident records of mirror pairs serve a render that could be paired itself - MirrorPairsApply has said so in job.mirror; unpaired
   // records serve any render. Either way the render goes the way the records were traced.)
-  job.reuse = job.keepable && job.allow_reuse && res.valid && res.key == job.geo_key && (!res.mirror || job.mirror);
+  // (the kept layout holds part of its store in the tails of the per-frequency shading arrays: a list of another length -
+  // bl_set_frequencies - would shade into it, so such a render integrates again; in one chunk's layout the arrays simply grow)
+  job.reuse = job.keepable && job.allow_reuse && res.valid && res.key == job.geo_key && (!res.mirror || job.mirror)
+      && (res.chunks.empty() || res.kept_n_nu == job.n_nu);
   if (job.reuse) {
     job.mirror = res.mirror;
     if (res.parked) SwapResidentBuffers(ctx);
@@ -797,6 +804,7 @@ void KeepResident(RenderJob &job) {
       res.pending = false;
       res.key = job.geo_key;
       res.record_capacity = job.record_capacity;
+      res.kept_n_nu = job.n_nu;
       res.segments = job.segments;
       res.tail_policy = job.park ? BL_TAIL_QUAD : BL_TAIL_WIDE;
       res.n_parked = job.total_parked;

@@ -26,6 +26,7 @@ class Params:
         self._sweep_cuts = _capi.SweepCuts()   # ... sweep_cut_sigma_max (bl_sweep_cuts)
         self._sweep_cameras = _capi.SweepCameras()   # ... sweep_camera_th, sweep_camera_ph (bl_sweep_cameras)
         self._sweep_electrons = _capi.SweepElectrons()   # ... sweep_power_frac ... sweep_w (bl_sweep_electrons)
+        self._sweep_frequencies = _capi.SweepFrequencies()   # ... sweep_frequency (bl_sweep_frequencies)
         self.num_runs = 1
 
     @property
@@ -38,7 +39,7 @@ class Params:
         self = cls()
         err = C.create_string_buffer(1024)
         runs = C.c_int(1)
-        rc = _capi.lib().bl_params_read_file_sweep_lists(self._buf, C.byref(self.sweep_lists), str(path).encode(), C.byref(runs), err, len(err))
+        rc = _capi.lib().bl_params_read_file_sweep_all(self._buf, C.byref(self.sweep_all), str(path).encode(), C.byref(runs), err, len(err))
         if rc != 0:
             raise _capi.BlacklightError(rc, err.value.decode())
         self.num_runs = runs.value
@@ -60,7 +61,7 @@ class Params:
 
     def set_line(self, line):
         err = C.create_string_buffer(1024)
-        rc = _capi.lib().bl_params_set_line_sweep_lists(self._buf, C.byref(self.sweep_lists), line.encode(), err, len(err))
+        rc = _capi.lib().bl_params_set_line_sweep_all(self._buf, C.byref(self.sweep_all), line.encode(), err, len(err))
         if rc != 0:
             raise _capi.BlacklightError(rc, err.value.decode())
 
@@ -79,6 +80,7 @@ class Params:
         C.memmove(C.byref(other._sweep_cuts), C.byref(self._sweep_cuts), C.sizeof(_capi.SweepCuts))
         C.memmove(C.byref(other._sweep_cameras), C.byref(self._sweep_cameras), C.sizeof(_capi.SweepCameras))
         C.memmove(C.byref(other._sweep_electrons), C.byref(self._sweep_electrons), C.sizeof(_capi.SweepElectrons))
+        C.memmove(C.byref(other._sweep_frequencies), C.byref(self._sweep_frequencies), C.sizeof(_capi.SweepFrequencies))
         other.num_runs = self.num_runs
         return other
 
@@ -141,6 +143,22 @@ class Params:
         return _capi.SweepLists(C.pointer(self._sweep), C.pointer(self._sweep_cuts), C.pointer(self._sweep_cameras), C.pointer(self._sweep_electrons))
 
     @property
+    def sweep_all(self):
+        """A bl_sweep_all that names this object's five structs (what the parser fills and Context applies: bl_apply_sweep_all)."""
+        return _capi.SweepAll(C.pointer(self._sweep), C.pointer(self._sweep_cuts), C.pointer(self._sweep_cameras), C.pointer(self._sweep_electrons),
+                              C.pointer(self._sweep_frequencies))
+
+    @property
+    def sweep_frequency_list(self):
+        """The bl_sweep_frequencies filled by sweep_frequency."""
+        return self._sweep_frequencies
+
+    @property
+    def sweep_frequency(self):
+        """The observing frequencies of sweep_frequency as written (Hz); [] for an absent key."""
+        return [float(x) for x in self._sweep_frequencies.hz[:self._sweep_frequencies.n]]
+
+    @property
     def sweep_electron_lists(self):
         """The bl_sweep_electrons filled by sweep_power_frac ... sweep_w."""
         return self._sweep_electrons
@@ -175,7 +193,7 @@ class Params:
     @property
     def has_sweep(self):
         return (self._sweep.n_rat_low > 0 or self._sweep.n_rat_high > 0 or self._sweep.n_rho_cgs > 0 or self._sweep_cuts.n_sigma_max > 0
-                or self._sweep_cameras.n_th > 0 or self._sweep_cameras.n_ph > 0 or self.has_sweep_electrons)
+                or self._sweep_cameras.n_th > 0 or self._sweep_cameras.n_ph > 0 or self.has_sweep_electrons or self._sweep_frequencies.n > 0)
 
     def resolved_sweep(self):
         """The lists as the setters receive them (bl_sweep_resolve): (polarized, rat_low, rat_high, rho_cgs). A polarized block's

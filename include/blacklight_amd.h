@@ -275,6 +275,29 @@ struct bl_electron_mix;
 BL_API int bl_sweep_electrons_resolve(const bl_sweep_electrons *e, const bl_sweep *sweep, const bl_params *p, int *n, bl_sweep *resolved,
                                       struct bl_electron_mix *mix, char *err, size_t err_len);
 
+/* One key more, in a fifth struct beside the four above (whose sizes, and bl_sweep_lists' four members, are part of the ABI):
+ *     sweep_frequency = 86e9, 230e9, 345e9     observing frequencies in Hz (bl_set_frequencies), each finite and > 0
+ * The same list forms and error texts with the key's name, and one of its own: "Invalid frequency (<text>) in list
+ * (sweep_frequency) in input file: must be finite and positive." The list replaces the block's frequencies for the run - the block
+ * must still be valid on its own - and is an axis of its own: one render per snapshot covers every frequency beside whatever variants
+ * and cameras the file also sweeps, and one file of the reference's layout is written per (camera, frequency, variant), tagged fFF
+ * (bl_write_output_frequency). Every parser call above accepts and validates the key and drops its values. bl_sweep_all names all
+ * five structs (a NULL member: that struct's keys are validated and dropped); the bl_sweep_lists calls forward to the calls below
+ * with `frequencies` NULL. n = 0: key absent. */
+typedef struct bl_sweep_frequencies {
+  int32_t n, reserved;
+  double hz[BL_MAX_SWEEP];
+} bl_sweep_frequencies;
+typedef struct bl_sweep_all {
+  bl_sweep *sweep;
+  bl_sweep_cuts *cuts;
+  bl_sweep_cameras *cameras;
+  bl_sweep_electrons *electrons;
+  bl_sweep_frequencies *frequencies;
+} bl_sweep_all;   /* NULL member: dropped */
+BL_API int bl_params_set_line_sweep_all(bl_params *p, const bl_sweep_all *lists, const char *line, char *err, size_t err_len);
+BL_API int bl_params_read_file_sweep_all(bl_params *p, const bl_sweep_all *lists, const char *path, int *num_runs, char *err, size_t err_len);
+
 /* ------------------------------------------------------------------ grid view
  * What RadiationIntegrator::ObtainGridData() takes from SimulationReader
  * (simulation_sampling.cpp:26-95). All pointers are host pointers borrowed for the duration of
@@ -711,6 +734,11 @@ BL_API int bl_camera_frame_get_camera(const bl_ctx *ctx, int camera, bl_camera_f
  * before the call or after it; a refused call leaves the context exactly as it was. A list the call does not carry leaves its axis
  * as it is, and an empty sweep changes nothing. */
 BL_API int bl_apply_sweep_lists(bl_ctx *ctx, const bl_sweep_lists *lists);
+/* ... with the frequency list (sweep_frequency) as a fifth: checked last, with bl_set_frequencies' checks, and stored under the same
+ * hold of the lock as the others - the same rule, all or nothing. Two frequencies or more on a block with adaptive_max_level > 0 are
+ * refused here (BL_E_UNSUPPORTED), as the other sweeps are on such blocks: the files of a sweep are one-frequency files, and a
+ * one-frequency run refines by its own image. bl_apply_sweep_lists forwards to this call with `frequencies` NULL. */
+BL_API int bl_apply_sweep_all(bl_ctx *ctx, const bl_sweep_all *lists);
 /* Forwards to bl_apply_sweep_lists with the lists they name (cuts, cameras may be NULL), kept for their callers: BL_E_ARG without a
  * context or a sweep. */
 BL_API int bl_apply_sweep(bl_ctx *ctx, const bl_sweep *sweep);
@@ -733,6 +761,26 @@ BL_API int bl_variants_get(const bl_ctx *ctx, int n, double *rat_low, double *ra
 BL_API int bl_render_num_images(const bl_ctx *ctx);
 BL_API int bl_camera_frame_get(const bl_ctx *ctx, bl_camera_frame *out);
 BL_API int bl_frequencies(const bl_ctx *ctx, double *out, int n);
+/* An explicit list of observing frequencies rendered by one bl_render - the frequency axis of a model library: 86, 230 and 345 GHz
+ * over one set of geodesics, which no spacing of image_frequency_start .. image_frequency_end gives. n = 0 (what a context starts
+ * with): the parameter block's own list, rebuilt exactly as bl_init built it. 1 <= n <= BL_MAX_FREQUENCIES: hz[0 .. n), each with the
+ * meaning of image_frequency - it goes through the same image_normalization and nothing else; the values need not be ordered or
+ * distinct. From then on n is the context's frequency count everywhere: bl_frequencies, bl_image_num_quantities and the auxiliary
+ * rows' offsets (those of a block with image_num_frequencies = n: within a variant, frequency l of a quantity sits where it sits
+ * there), the render's plan, the .npz / .npy / raw writer (bl_write_output writes one file with the reference's frequency axis of
+ * length n) and a geodesic checkpoint that is saved. For bl_adaptive_refine adaptive_frequency_num - 1 indexes the list (n = 1: 0).
+ * Row l of a list render is the row of a context with that one frequency in its block: bit for bit in the exact tier, within the
+ * tier's per-pixel bound in the tolerant one. Formula mode, slow light, polarized runs, every variant setter and the camera list
+ * compose with the list unchanged. The values are no part of what "the same camera" means for bl_set_geodesic_reuse: a render after
+ * other values of the same length shades the resident records (bl_stats.geodesics_reused = 1), and another length does wherever the
+ * plan chooses the same record layout (four frequencies or more leave the kernels as per-sample factors: another layout).
+ * BL_E_ARG: a value that is not finite and > 0 (with the entry's index), n outside 0 .. BL_MAX_FREQUENCIES, a null array with n > 0;
+ * adaptive_max_level > 0 with n >= 2 and adaptive_frequency_num absent or outside 1 .. n ("Must choose adaptive_frequency_num from 1
+ * to image_num_frequencies."). BL_E_UNSUPPORTED: checkpoint_geodesic_load with n >= 1 (the file carries its own frequency list, which
+ * replaces the context's). A refused call changes nothing. Works on a BL_DEVICE_NONE context. */
+#define BL_MAX_FREQUENCIES 1024     /* the fast path's LDS table bound, bl_render.hip: job.n_nu <= 1024 */
+BL_API int bl_set_frequencies(bl_ctx *ctx, int n, const double *hz);
+BL_API int bl_num_frequencies(const bl_ctx *ctx);   /* 0 = unset: the parameter block's own list; -1: no context */
 /* Arithmetic tier. BL_ARITH_TOLERANT (what a new context starts in, unless the environment says BLACKLIGHT_AMD_ARITHMETIC=exact): the
  * tolerance north_star grants for intensities ("within a stated fp64 tolerance", per-pixel L-infinity < 1e-6: every pixel relative to
  * its own intensity; measured 2e-14 per pixel - 6e-15 of the image maximum - on the benchmark frame's 1 048 576 pixels and against the
@@ -927,6 +975,23 @@ BL_API int bl_write_output_camera(bl_ctx *ctx, const char *path_override, const 
  * from 00) in front of the variant's tag inside the same dot group: image.c01.npz, image.c01m00u02.npz, image.c01m00u02s03.npz,
  * image.c01v03.npz; names sort in (camera, variant) order. C = 1: no camera tag. */
 BL_API int bl_camera_output_path(bl_ctx *ctx, int snapshot, int camera, int variant, char *buf, size_t len);
+
+/* ONE frequency (of one camera and variant) of a render as a file of the reference's layout. `frequency` indexes bl_frequencies -
+ * the list bl_set_frequencies set, or the block's own spaced list. For every quantity with a frequency axis (I_nu ... V_nu, lambda,
+ * emission, tau and the seven cell values of lambda_ave, emission_ave and tau_int) the file's rows are those of frequency `frequency`;
+ * the rows without one (time, length, crossings), the renderings and the camera records are copied as they are; its `frequency`
+ * record holds that one value. The file is, byte for byte in all three formats, what bl_write_output writes in a context whose block
+ * has image_num_frequencies = 1 and image_frequency = that value (and that camera's angles and that variant's values) - the rows are
+ * gathered into one block before they are written. BL_E_ARG: frequency outside the list, camera outside 0 .. C - 1, variant outside
+ * 0 .. V - 1, adaptive levels with C >= 2 or V >= 2, and adaptive levels (adaptive_num_levels != 0) while the context has two
+ * frequencies or more - a one-frequency run refines by its own image, so its file is not this one. Works on a BL_DEVICE_NONE
+ * context. Name: path_override if given, else bl_frequency_output_path. */
+BL_API int bl_write_output_frequency(bl_ctx *ctx, const char *path_override, const bl_output_desc *d, int frequency, int camera, int variant);
+/* The name bl_write_output_frequency gives the file: bl_camera_output_path's, with the frequency's tag fFF (two digits and more,
+ * from 00) inside the one dot group the other tags share, after the camera's and before the variant's: image.f02.npz,
+ * image.c01f02m00u01.npz, image.f00v03.npz. The tag is there whatever the list's length - a list of one writes image.f00.npz - and
+ * only in this call's names: every other name stays as it is. */
+BL_API int bl_frequency_output_path(bl_ctx *ctx, int snapshot, int frequency, int camera, int variant, char *buf, size_t len);
 
 /* Library self-description: "gfx950;hip" etc. Lets a loader verify the HIP path is the one built. */
 BL_API const char *bl_build_info(void);
