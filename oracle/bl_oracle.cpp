@@ -2980,6 +2980,12 @@ int blo_render(const bl_params *p, const bl_grid_desc *g, const bl_render_desc *
 int blo_render_dump(const bl_params *p, const bl_grid_desc *g, const bl_render_desc *d,
                     bl_camera_frame *frame, double *frequencies, blo_extra *extra,
                     const blo_dump_coefficients *dump, char *err, size_t err_len) {
+  return blo_render_dump_polarized(p, g, d, frame, frequencies, extra, dump, nullptr, err, err_len);
+}
+
+int blo_render_dump_polarized(const bl_params *p, const bl_grid_desc *g, const bl_render_desc *d,
+                              bl_camera_frame *frame, double *frequencies, blo_extra *extra,
+                              const blo_dump_coefficients *dump, const blo_dump_polarized *dump_pol, char *err, size_t err_len) {
   if (p == nullptr || d == nullptr) return BL_E_ARG;
   if (d->outputs_on_device) return Fail(err, err_len, "oracle works on host memory only", BL_E_ARG);
   Oracle o{};
@@ -3147,6 +3153,15 @@ int blo_render_dump(const bl_params *p, const bl_grid_desc *g, const bl_render_d
           if (dump->j != nullptr) dump->j[n] = b.j_i[n];
           if (dump->alpha != nullptr) dump->alpha[n] = b.alpha_i[n];
           if (dump->dtau != nullptr) dump->dtau[n] = b.alpha_i[n] * delta_lambda_cgs;
+        }
+      }
+      if (dump_pol != nullptr && extra != nullptr && extra->dump_ray == ray) {   // frequency 0's b.pol[0..5] as IntegratePolarizedOne reads them
+        double *const out[6] = {dump_pol->j_q, dump_pol->j_v, dump_pol->alpha_q, dump_pol->alpha_v, dump_pol->rho_q, dump_pol->rho_v};
+        const double x_unit = Physics::gg_msun * o.mass_msun / (Physics::c * Physics::c);
+        for (int n = 0; n < sample_num; n++) {
+          for (int c = 0; c < 6; c++)
+            if (out[c] != nullptr) out[c][n] = o.image_polarization ? b.pol[c][n] : 0.0;
+          if (dump_pol->dlambda != nullptr) dump_pol->dlambda[n] = b.sample_len[n] * x_unit / (o.image_frequencies[0] * factor);
         }
       }
       if (o.image_polarization)

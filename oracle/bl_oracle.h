@@ -68,6 +68,19 @@ int blo_render_dump(const bl_params *p, const bl_grid_desc *g, const bl_render_d
                     bl_camera_frame *frame, double *frequencies, blo_extra *extra,
                     const blo_dump_coefficients *dump, char *err, size_t err_len);
 
+/* Optional, beside blo_dump_coefficients (blo_render_dump_polarized): the dumped ray's six polarized coefficients at frequency 0 -
+   j_Q, j_V, alpha_Q, alpha_V, rho_Q, rho_V exactly as the polarized integration reads them - and the step's delta lambda_cgs, in the
+   order of dump_pos; buffers sized ray_max_steps, each may be NULL. All zero in an unpolarized run and for samples without
+   coefficients. A struct of its own for the reason blo_dump_coefficients is one. */
+typedef struct blo_dump_polarized {
+  double *j_q, *j_v, *alpha_q, *alpha_v, *rho_q, *rho_v, *dlambda;
+} blo_dump_polarized;
+
+/* blo_render_dump() that also fills pol (may be NULL) for the ray extra->dump_ray */
+int blo_render_dump_polarized(const bl_params *p, const bl_grid_desc *g, const bl_render_desc *d,
+                              bl_camera_frame *frame, double *frequencies, blo_extra *extra,
+                              const blo_dump_coefficients *dump, const blo_dump_polarized *pol, char *err, size_t err_len);
+
 /* number of image rows for these parameters (radiation_integrator.cpp:436-520) */
 int blo_image_num_quantities(const bl_params *p);
 int blo_image_num_frequencies(const bl_params *p);

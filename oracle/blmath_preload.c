@@ -8,6 +8,7 @@
  * precalculations, so they are left to glibc.
  */
 #include "blmath.h"
+#include "bl_bessel.h"
 
 #define EXPORT __attribute__((visibility("default")))
 
@@ -46,3 +47,10 @@ VEC1(blv_atan, bl_atan)
 VEC1(blv_sinh, bl_sinh)
 VEC1(blv_cosh, bl_cosh)
 VEC1(blv_tanh, bl_tanh)
+/* K_0, K_1, K_2 as single calls of bl_cyl_bessel_k(n, x) (tests/test_gpu_math.py: the device's bl_cyl_bessel_k012) */
+static double bessel_k0(double x) { return bl_cyl_bessel_k(0, x); }
+static double bessel_k1(double x) { return bl_cyl_bessel_k(1, x); }
+static double bessel_k2(double x) { return bl_cyl_bessel_k(2, x); }
+VEC1(blv_bessel_k0, bessel_k0)
+VEC1(blv_bessel_k1, bessel_k1)
+VEC1(blv_bessel_k2, bessel_k2)

@@ -29,6 +29,10 @@ class DumpCoefficients(C.Structure):   # blo_dump_coefficients
     _fields_ = [("kte", C.c_void_p), ("j", C.c_void_p), ("alpha", C.c_void_p), ("dtau", C.c_void_p)]
 
 
+class DumpPolarized(C.Structure):   # blo_dump_polarized
+    _fields_ = [(name, C.c_void_p) for name in ("j_q", "j_v", "alpha_q", "alpha_v", "rho_q", "rho_v", "dlambda")]
+
+
 def _host_has_fma():
     try:
         with open("/proc/cpuinfo") as f:
@@ -62,13 +66,15 @@ def load(variant="blmath"):
 
 def render(params_ptr, grid_desc, desc_cls, camera_frame_cls, *, n_rays, level=0, block_locs=None,
            pixel_map=None, variant="blmath", num_threads=0, dump_ray=-1, max_steps=0, n_freq=1,
-           want_camera=False, n_render=0, slow=None, define_kappa=False):
+           want_camera=False, n_render=0, slow=None, define_kappa=False, dump_polarized=False):
     """Run the oracle. Returns dict(image, sample_num, sample_flags, frame, frequencies, extra...).
     n_render > 0: also the false-colour renderings, (n_render, 3, n_rays).
     slow = dict(grids=[bl_grid_desc, ...] latest first, times=[...], snapshot_time=t): slow light.
     define_kappa: unpolarized kappa-distribution electrons with kappa_aa_high_i as in polarized runs (blo_extra).
     dump_ray >= 0 (buffers of max_steps samples): out["dump"] holds that ray's samples in reference order - pos, dir, len, and at
-    frequency 0 kte (k T_e in erg; NaN for samples without coefficients), j, alpha (j_nu, alpha_nu) and dtau (alpha_nu delta lambda_cgs)."""
+    frequency 0 kte (k T_e in erg; NaN for samples without coefficients), j, alpha (j_nu, alpha_nu) and dtau (alpha_nu delta lambda_cgs).
+    dump_polarized (with dump_ray >= 0): out["dump"] also holds j_q, j_v, alpha_q, alpha_v, rho_q, rho_v - frequency 0's polarized
+    coefficients as the polarized integration reads them - and dlambda, the steps' delta lambda_cgs (blo_dump_polarized)."""
     L = load(variant)
     n_q = L.blo_image_num_quantities(params_ptr)
     image = np.zeros((max(n_q, 1), n_rays), dtype=np.float64)
@@ -116,6 +122,9 @@ def render(params_ptr, grid_desc, desc_cls, camera_frame_cls, *, n_rays, level=0
         for name in ("pos", "dir", "len"):
             setattr(extra, f"dump_{name}", dump[name].ctypes.data_as(C.c_void_p))
         coefficients = DumpCoefficients(*[dump[name].ctypes.data_as(C.c_void_p) for name in ("kte", "j", "alpha", "dtau")])
+        if dump_polarized:
+            dump.update({name: np.zeros(max_steps) for name, _ in DumpPolarized._fields_})
+            polarized = DumpPolarized(*[dump[name].ctypes.data_as(C.c_void_p) for name, _ in DumpPolarized._fields_])
     if slow is not None:
         grid_ptrs = (C.c_void_p * len(slow["grids"]))(*[C.addressof(g) for g in slow["grids"]])
         times = np.ascontiguousarray(slow["times"], dtype=np.float64)
@@ -126,7 +135,10 @@ def render(params_ptr, grid_desc, desc_cls, camera_frame_cls, *, n_rays, level=0
         extra.slow_snapshot_time = float(slow["snapshot_time"])
     err = C.create_string_buffer(1024)
     grid_ptr = C.byref(grid_desc) if grid_desc is not None else None
-    if dump is not None:
+    if dump is not None and dump_polarized:
+        rc = L.blo_render_dump_polarized(params_ptr, grid_ptr, C.byref(d), C.byref(frame), freqs.ctypes.data_as(C.c_void_p), C.byref(extra),
+                                         C.byref(coefficients), C.byref(polarized), err, C.c_size_t(len(err)))
+    elif dump is not None:
         rc = L.blo_render_dump(params_ptr, grid_ptr, C.byref(d), C.byref(frame), freqs.ctypes.data_as(C.c_void_p), C.byref(extra),
                                C.byref(coefficients), err, C.c_size_t(len(err)))
     else:

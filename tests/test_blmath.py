@@ -66,6 +66,53 @@ CASES_1 = {
 }
 
 
+def _hyperbolic_arguments(limit):
+    """What the polarized coupling (alpha_p dl, lambda_1 dl) and f_e hand to sinh / cosh / tanh beyond |x| <= 20: 10^[-300, 0], |x| up to
+    `limit`, and neighbours of the seams of the implementations (2^-28, 2^-55, 1, 22, 709), both signs"""
+    rng = np.random.default_rng(2026)
+    seams = np.array([2.0 ** -28, 2.0 ** -55, 1.0, 22.0, 709.0])
+    near = np.concatenate([s * (1.0 + k * 2.0 ** -52) for s in seams for k in (np.arange(-8, 9), rng.uniform(-1.0e-3, 1.0e-3, 40) * 2.0 ** 52)])
+    x = np.concatenate([10.0 ** rng.uniform(-300, 0, N), rng.uniform(0.0, limit, N), rng.uniform(20.0, 30.0, N // 4), near])
+    x = x[x <= limit]
+    return np.concatenate([x, -x])
+
+
+CASES_WIDE = {"sinh": (745.0, mp.sinh, 2.0), "cosh": (745.0, mp.cosh, 2.0), "tanh": (800.0, mp.tanh, 2.5)}
+
+
+@pytest.mark.parametrize("name", sorted(CASES_WIDE))
+def test_hyperbolic_accuracy_over_the_coupling_range(lib, name):
+    """bl_sinh / bl_cosh / bl_tanh at the bounds of test_unary_accuracy over everything the coupling step and f_e pass them; overflow
+    where the exact value overflows, and the specials. Measured: 1.48, 1.48 and 1.85 ulp."""
+    limit, f, bound = CASES_WIDE[name]
+    x = _hyperbolic_arguments(limit)
+    got = _call1(lib, name, x)
+    exact = [f(mp.mpf(float(v))) for v in x]
+    finite = np.array([abs(e) < mp.mpf(1.7976931348623157e308) for e in exact])
+    assert np.all(np.isfinite(got[finite])) and np.all(np.isinf(got[~finite]))   # (finite up to 710.47...)
+    worst = _max_ulp(got[finite], [e for e, ok in zip(exact, finite) if ok])
+    print(f"{name}: {worst:.2f} ulp over {x.size} arguments")
+    assert worst <= bound
+    assert np.array_equal(np.sign(got), np.sign(x) if name != "cosh" else np.ones(x.size))
+    nan, inf = np.nan, np.inf
+    special = _call1(lib, name, np.array([0.0, -0.0, inf, -inf, nan, 5e-324, 1000.0, -1000.0]))
+    want = {"sinh": [0.0, -0.0, inf, -inf, nan, 5e-324, inf, -inf], "cosh": [1.0, 1.0, inf, inf, nan, 1.0, inf, inf],
+            "tanh": [0.0, -0.0, 1.0, -1.0, nan, 5e-324, 1.0, -1.0]}[name]
+    assert np.array_equal(special.view(np.uint64)[[0, 1, 2, 3, 5, 6, 7]], np.array(want).view(np.uint64)[[0, 1, 2, 3, 5, 6, 7]]) and np.isnan(special[4])
+
+
+def test_bessel_header_is_libstdcxx_operation_for_operation(tmp_path_factory):
+    """bl_bessel.h against std::cyl_bessel_k (GCC's libstdc++) run over the pinned log / exp / cosh / sinh: a stand-alone program
+    (tests/bessel_host_main.cpp) with the shim's object linked in, n = 0, 1, 2 over 400 000 arguments in [1e-300, 745], 1 / Theta_e, a
+    dense band around the series / continued-fraction switch at 2, 0 and NaN; and K_0, K_1, K_2 of one k012 call are three single calls"""
+    where = tmp_path_factory.mktemp("bessel_check")   # (not oracle/_ref: a program left there by another tree may be newer than this source)
+    subprocess.run(["make", "-C", os.path.join(REPO, "oracle"), f"OUT={where}", "bessel_check"], check=True, capture_output=True)
+    out = subprocess.run([os.path.join(str(where), "bessel_check")], check=True, capture_output=True, text=True).stdout
+    words = out.split()
+    assert words[-4] == "arguments" and int(words[-3]) >= 400000, out
+    assert words[-2:] == ["mismatches", "0"], out
+
+
 @pytest.mark.parametrize("name", sorted(CASES_1))
 def test_unary_accuracy(lib, name):
     x, f, bound = CASES_1[name]

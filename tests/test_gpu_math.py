@@ -1,9 +1,10 @@
 """The device build of the pinned math library (blmath.h) and the exact-arithmetic devices of
 bl_geometry.h (bl_div_g, bl_sqrt_g, bl_hypot_g) against the host, bit for bit, on random and special
-inputs. Host side: oracle/_ref/libblmath_preload.so (the same blmath.h compiled by gcc) and numpy's
+inputs. Host side: oracle/blmath_preload.c (the same blmath.h compiled by gcc, as in oracle/_ref/libblmath_preload.so) and numpy's
 IEEE-754 division / square root."""
 import ctypes
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -16,11 +17,12 @@ N = 1 << 20
 
 
 @pytest.fixture(scope="module")
-def host():
-    path = os.path.join(REPO, "oracle", "_ref", "libblmath_preload.so")
-    if not os.path.exists(path):
-        pytest.skip("libblmath_preload.so not built")
-    return ctypes.CDLL(path)
+def host(tmp_path_factory):
+    """The host build of oracle/blmath_preload.c by the Makefile's own recipe, into a directory of this session: a copy that came
+    to oracle/_ref with the compiled reference may be older than the source and lack its newest entry points."""
+    out = tmp_path_factory.mktemp("blmath_host")
+    subprocess.run(["make", "-C", os.path.join(REPO, "oracle"), f"OUT={out}", "preload"], check=True, capture_output=True)
+    return ctypes.CDLL(os.path.join(str(out), "libblmath_preload.so"))
 
 
 @pytest.fixture(scope="module")
@@ -97,6 +99,25 @@ def test_blmath_binary_device_equals_host(host, device):
     t = np.concatenate([rng.uniform(-1.0e4, 1.0e4, N), SPECIAL])
     assert _bits_equal(device.debug_math(16, t), _host1(host, "sin", t)).all()
     assert _bits_equal(device.debug_math(17, t), _host1(host, "cos", t)).all()
+
+
+def test_exact_bessel_functions_device_equals_host(host, device):
+    """bl_cyl_bessel_k012 on the device (ops 33-35: the K_0, K_1, K_2 behind factor_q and factor_v of rho_Q / rho_V) against three single
+    calls of bl_cyl_bessel_k(n, x) on the host, bit for bit: x log-spread over [1e-300, 745], 1 / Theta_e for Theta_e in [0.01, 1e4], a
+    dense band around the series / continued-fraction switch at x = 2 with 2 and its neighbours, 0 (inf) and NaN"""
+    rng = np.random.default_rng(33)
+    ulp = 2.0 ** -51   # of [2, 4); below 2 the neighbours step by half of it
+    x = np.concatenate([10.0 ** rng.uniform(-300.0, np.log10(745.0), N // 2), 1.0 / 10.0 ** rng.uniform(-2.0, 4.0, N // 2),
+                        rng.uniform(1.9, 2.1, N // 8), 2.0 + np.arange(0, 65) * ulp, 2.0 - np.arange(1, 65) * 0.5 * ulp,
+                        np.array([1.0e-300, 745.0, 0.01, 100.0, 1.0e-4, 0.0, -0.0, np.nan])])
+    x = np.ascontiguousarray(x)
+    assert (x == 2.0).any() and (x == np.nextafter(2.0, 0.0)).any() and (x == np.nextafter(2.0, 3.0)).any()
+    for op, order in ((33, 0), (34, 1), (35, 2)):
+        got = device.debug_math(op, x)
+        want = _host1(host, f"bessel_k{order}", x)
+        same = _bits_equal(got, want)
+        assert same.all(), f"K_{order}: {(~same).sum()} of {same.size} differ, first at x = {x[~same][:3]}"
+        assert np.all(np.isinf(got[x == 0.0])) and np.isnan(got[-1]) and np.all(np.isfinite(got[x > 0.0]) | (x[x > 0.0] < 1.0e-150))
 
 
 def test_exact_devices_inside_their_stated_domain(host, device):

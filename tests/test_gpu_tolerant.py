@@ -431,7 +431,7 @@ def test_deferred_cut_decisions(band, resolution, frequencies, variant, built_li
 
 def test_tolerant_functions_are_accurate(built_library):
     """exp, expm1, cbrt, reciprocal, reciprocal square root, acos and atan2 of the tolerant tier against numpy's long double, its
-    Bessel functions against scipy."""
+    Bessel functions against scipy, its log and pow against mpmath (_log_and_pow_are_accurate)."""
     import blacklight_amd as bl
     fx, params, _ = gu.load_case("formula_flat")
     rng = np.random.default_rng(3)
@@ -482,6 +482,49 @@ def test_tolerant_functions_are_accurate(built_library):
             want = sp.kn(order, xb)
             ok = want > 1.0e-300
             assert np.max(np.abs(got[ok] / want[ok] - 1.0)) < 5.0e-14, order
+        _log_and_pow_are_accurate(ctx)
+
+
+LOG_BOUND = 5.0e-15   # twice the measured 2.3e-15, rounded up to one digit (the tier's reciprocal in s = (m - 1) / (m + 1) carries it)
+POW_BOUND = 2.0       # twice the measured 0.90, in units of (1 + |y log x|) 2^-52
+
+
+def _log_and_pow_are_accurate(ctx):
+    """fastmath::log and fastmath::pow (bl_debug_math ops 36 and 37; bl_fastmath.h states "a few ulp" and ~|y log x| 2^-52) against mpmath
+    at 50 digits. log: x over 10^[-307, 308], subnormals, and [1 - 1e-3, 1 + 1e-3]; worst relative error measured 2.3e-15. pow: the
+    bases and exponents the coefficient formulas use - x in 10^[-40, 40] with y in [-8, 8] and with y = 0.96, and the kappa bridges'
+    pow(c, -x) and pow(sum, -1 / x) with coefficients c down to 1e-80; worst err / ((1 + |y log x|) 2^-52) measured 0.90. Each
+    asserted at twice the measured value, rounded up to one digit. Specials: pow(x, 0) = pow(1, y) = 1 also beside NaN, pow(0, +-y),
+    log(0), log(-1), inf."""
+    import mpmath as mp
+    mp.mp.dps = 50
+    rng = np.random.default_rng(36)
+    x = np.concatenate([10.0 ** rng.uniform(-307.0, 308.0, 20000), 5e-324 * rng.integers(1, 2 ** 52, 2000).astype(np.float64),
+                        np.array([5e-324, 2.2250738585072014e-308, 1.7976931348623157e308]),
+                        1.0 + rng.uniform(-1.0e-3, 1.0e-3, 20000), 1.0 + np.arange(-50, 51) * 2.0 ** -53])
+    x = x[x != 1.0]
+    got = ctx.debug_math(36, x)
+    worst_log = max(float(abs((mp.mpf(float(g)) - mp.log(mp.mpf(float(v)))) / mp.log(mp.mpf(float(v))))) for g, v in zip(got, x))
+    base = np.concatenate([10.0 ** rng.uniform(-40.0, 40.0, 12000), 10.0 ** rng.uniform(-40.0, 40.0, 4000),
+                           10.0 ** rng.uniform(-80.0, 0.0, 8000)])
+    power = np.concatenate([rng.uniform(-8.0, 8.0, 12000), np.full(4000, 0.96),
+                            rng.choice([-1.0, 1.0], 8000) * 10.0 ** rng.uniform(-1.0, 1.0, 8000)])
+    got = ctx.debug_math(37, base, power)
+    worst_pow = 0.0
+    for g, a, b in zip(got, base, power):
+        a, b = mp.mpf(float(a)), mp.mpf(float(b))
+        want = mp.power(a, b)
+        if not 2.3e-308 < want < 1.7e308:
+            continue
+        worst_pow = max(worst_pow, float(abs(mp.mpf(float(g)) - want) / want / ((1 + abs(b * mp.log(a))) * mp.mpf(2) ** -52)))
+    print(f"fastmath::log worst relative error {worst_log:.3e}; fastmath::pow worst err / ((1 + |y log x|) 2^-52) {worst_pow:.3f}")
+    nan, inf = np.nan, np.inf
+    sp = ctx.debug_math(36, np.array([0.0, -0.0, -1.0, inf, nan, 1.0, -inf]))
+    assert sp[0] == -inf and sp[1] == -inf and np.isnan(sp[2]) and sp[3] == inf and np.isnan(sp[4]) and sp[5] == 0.0 and np.isnan(sp[6])
+    sp = ctx.debug_math(37, np.array([nan, 1.0, 1.0, 0.0, 0.0, inf, inf, 2.0, 0.5, 0.0, 7.0]),
+                        np.array([0.0, nan, inf, 2.5, -2.5, 0.96, -0.96, inf, inf, 0.0, 0.0]))
+    assert np.array_equal(sp, np.array([1.0, 1.0, 1.0, 0.0, inf, inf, 0.0, inf, 0.0, 1.0, 1.0]))
+    assert worst_log < LOG_BOUND and worst_pow < POW_BOUND
 
 
 WINDOWS = os.path.join(gu.GOLDEN_DIR, "window_1024.npz")

@@ -91,3 +91,42 @@ def test_blo_render_reads_no_more_than_blo_extra(built_library):
     assert extra.dump_num == sample_num[528] > 0
     want = oracle_api.render(p.ptr, grid.desc(), _capi.RenderDesc, _capi.CameraFrame, n_rays=n, num_threads=4)
     assert gu.same_bits(image, want["image"]).all()
+
+
+@pytest.mark.parametrize("overrides", [{}, {"simulation_rho_cgs": 1.0e-12}, {"image_frequency": 1.0e15}, {"image_rotation_split": "true"}],
+                         ids=["fixture", "thick", "1e15hz", "split"])
+@pytest.mark.parametrize("ray", [300, 297])
+def test_polarized_dump_changes_nothing_and_is_what_the_ray_integrates(built_library, overrides, ray):
+    """blo_render_dump_polarized (blo_dump_polarized: j_Q, j_V, alpha_Q, alpha_V, rho_Q, rho_V, delta lambda_cgs), which
+    tests/test_gpu_polarized_edges.py reads: a render with both dumps on returns the image, sample_num and sample_flags of a render
+    without, bit for bit; the dumped values hang together with blo_dump_coefficients' and with the optical-depth row"""
+    import blacklight_amd as bl
+    from blacklight_amd import _capi
+    fx, params, mock_args = gu.load_case("sim_polarized")
+    params = dict(params, **overrides)
+    p = bl.Params.from_dict(params)
+    grid = gu.golden_grid(mock_args)
+    n, max_steps = int(params["camera_resolution"]) ** 2, int(params["ray_max_steps"])
+    plain = oracle_api.render(p.ptr, grid.desc(), _capi.RenderDesc, _capi.CameraFrame, n_rays=n, num_threads=4)
+    one = oracle_api.render(p.ptr, grid.desc(), _capi.RenderDesc, _capi.CameraFrame, n_rays=n, num_threads=4, dump_ray=ray, max_steps=max_steps)
+    out = oracle_api.render(p.ptr, grid.desc(), _capi.RenderDesc, _capi.CameraFrame, n_rays=n, num_threads=4, dump_ray=ray, max_steps=max_steps,
+                            dump_polarized=True)
+    for got in (one, out):
+        assert gu.same_bits(plain["image"], got["image"]).all()
+        assert np.array_equal(plain["sample_num"], got["sample_num"]) and np.array_equal(plain["sample_flags"], got["sample_flags"])
+    names = ("j_q", "j_v", "alpha_q", "alpha_v", "rho_q", "rho_v", "dlambda")
+    assert not any(name in one["dump"] for name in names)   # (only when asked for)
+    d = out["dump"]
+    count = int(out["sample_num"][ray])
+    assert count > 0 and all(len(d[name]) == count for name in names)
+    assert all(gu.same_bits(d[name], one["dump"][name]).all() for name in ("pos", "dir", "len", "kte", "j", "alpha", "dtau"))
+    assert gu.same_bits(d["dtau"], d["alpha"] * d["dlambda"]).all() and np.all(d["dlambda"] > 0.0)
+    tau = 0.0
+    for step in d["dtau"]:
+        tau += step
+    assert gu.same_bits(out["image"][4, ray], tau)   # rows I, Q, U, V, tau
+    formed = np.isfinite(d["kte"])
+    assert formed.any() and all(np.all(d[name][~formed] == 0.0) for name in names[:6])
+    # polarized emission and absorption never exceed the unpolarized ones; the fixture's plasma rotates wherever it has coefficients
+    assert np.all(np.hypot(d["j_q"], d["j_v"]) <= d["j"] * (1.0 + 1.0e-12)) and np.all(np.hypot(d["alpha_q"], d["alpha_v"]) <= d["alpha"] * (1.0 + 1.0e-12))
+    assert np.all(np.hypot(d["rho_q"], d["rho_v"])[formed] > 0.0)
