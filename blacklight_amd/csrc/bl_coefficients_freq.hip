@@ -6,7 +6,8 @@
 // =================================================================================================
 // Polarized coefficient kernel: the per-frequency part of CalculateSimulationCoefficients (simulation_coefficients.cpp:
 // 458-698) for polarized runs, one sample record per lane from the scalars the coefficient kernel left
-// (BlCoefInputs). Writes (j_I, alpha_I) and the three polarized pairs, [ray][n][frequency].
+// (BlCoefInputs). Writes (j_I, alpha_I) and the three polarized pairs, [ray][n][frequency]: polarized_sample_prelude() once and
+// polarized_sample_coefficients() per frequency (bl_sampling_fast.h; bl_shade_polarized2_kernel<.., kCoefficients> calls the same two).
 // =================================================================================================
 // kTolerant: the tolerant arithmetic tier's functions and fused multiply-adds in the formulas (bl_coefficients.inc,
 // second inclusion) - the kernel is almost entirely the double-double pow / log of the pinned library otherwise.
@@ -64,7 +65,7 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
     const double momentum_factor = bl_ray_factor(P.ray_constants, (size_t)ray);
     // the electron constants of the wave's variant (a mix per variant: its copy of the block; else the render's own, for every variant)
     const BlShadeArgs &E = variant_electrons<kThermalOnly>(P, v);
-    SampleShade sh;
+    SampleShade sh;   // (empty, then what the row holds)
     sh.have_coefficients = ci.have_coefficients != 0.0;
     sh.nu_fluid_over_nu = ci.nu_fluid_over_nu;
     sh.n_e_cgs = ci.n_e_cgs;
@@ -86,37 +87,21 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
       if (E.plasma.plasma_thermal_frac != 0.0)
         plasma_electron_temperature(P, pv.rat_high, pv.rat_low, plasma_beta_inverse(b_sq, pgas), cgs, &sh.theta_e, &sh.kb_tt_e_cgs);
     }
-    // :453-455 from cos^2: the same operations the coefficient kernel applies to the same value
     sh.cos2_theta_b = ci.cos2_theta_b;
-    sh.sin2_theta_b = 1.0 - ci.cos2_theta_b;
-    sh.sin_theta_b = bl_sqrt_g(sh.sin2_theta_b);
-    sh.cos_theta_b = bl_sqrt_g(ci.cos2_theta_b) * ci.cos_sign;
-    // what does not depend on the frequency, once per sample (the reference recomputes it for every frequency)
-    sh.theta_e_096 = sh.kk_0 = sh.kk_1 = sh.kk_2 = 0.0;
-    if (sh.have_coefficients && E.plasma.plasma_thermal_frac != 0.0) {
-      sh.theta_e_096 = kTolerant ? fastmath::pow(sh.theta_e, 0.96) : bl_pow(sh.theta_e, 0.96);
-      if (sh.theta_e >= 0.01) {   // theta_e_zero, radiation_integrator.hpp:190
-        if (kTolerant) fastmath::bessel_k012(1.0 / sh.theta_e, &sh.kk_0, &sh.kk_1, &sh.kk_2);
-        else bl_cyl_bessel_k012(1.0 / sh.theta_e, &sh.kk_0, &sh.kk_1, &sh.kk_2);
-      }
-    }
+    sh.cos_sign = ci.cos_sign;
+    polarized_sample_prelude<kTolerant>(E, &sh);
     const size_t at = (((size_t)P.ray_offset[ray] + n) * n_var + v) * P.n_nu;
     for (int l = 0; l < P.n_nu; l++) {
       const double freq = P.frequencies[l];
-      double j_val = 0.0, alpha_val = 0.0;
-      double2 pc[3] = {make_double2(0.0, 0.0), make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
-      if (kTolerant) {
-        if (sh.have_coefficients) simulation_coefficients_fast<!kThermalOnly>(E, sh, freq, momentum_factor, &j_val, &alpha_val);
-        polarized_coefficients_fast<!kThermalOnly>(E, sh, freq, momentum_factor, j_val, alpha_val, pc);
-      } else {
-        if (sh.have_coefficients) simulation_coefficients<!kThermalOnly>(E, sh, freq, momentum_factor, &j_val, &alpha_val);
-        polarized_coefficients<!kThermalOnly>(E, sh, freq, momentum_factor, j_val, alpha_val, pc);
-      }
+      double2 *out = P.pol_coeffs + (at + l) * 4;
+      polarized_sample_coefficients<kTolerant, !kThermalOnly>(E, sh, momentum_factor, freq, out);
 #ifdef BL_POL_CONDITION_STATS
       // (a measurement build, tools/build_variant.sh -DBL_POL_CONDITION_STATS: how many samples' joint coupling step - polarized.cpp:
       // 657-778 - loses more than 2, 3, 4, 6 digits to the cancellations in lambda_1, lambda_2 = sqrt(lambda_a +- lambda_b) and in
       // 1 / (alpha_I^2 - lambda_1^2); BL_CNT_DEBUG + 0 ... 3, samples with coefficients in + 4, with rho and alpha_P both non-zero in + 5)
       if (sh.have_coefficients) {
+        const double alpha_val = out[0].y;
+        const double2 pc[3] = {out[1], out[2], out[3]};
         const double a_sq = pc[1].x * pc[1].x + pc[1].y * pc[1].y, r_sq = pc[2].x * pc[2].x + pc[2].y * pc[2].y;
         const double a_r = pc[1].x * pc[2].x + pc[1].y * pc[2].y;
         const double lb = 0.5 * (a_sq - r_sq), la = sqrt(lb * lb + a_r * a_r);
@@ -135,19 +120,14 @@ __global__ void __launch_bounds__(256, (kThermalOnly && !kTolerant) ? 3 : BL_POL
         if (!(kappa < 1e6)) atomicAdd(&P.counters[BL_CNT_DEBUG + 3], 1ull);
       }
 #endif
-      double2 *out = P.pol_coeffs + (at + l) * 4;
-      out[0] = make_double2(j_val, alpha_val);
-      out[1] = pc[0];
-      out[2] = pc[1];
-      out[3] = pc[2];
     }
   }
 }
 
 // Exact tier, plain images with several frequencies: one lane per (sample record, frequency). The coefficient kernel's frequency
 // loop (simulation_coefficients.cpp:464-523, :556-584; unpolarized.cpp:74-110) with the loop turned into lanes: the lanes of a
-// record read the same 64 bytes of inputs, evaluate the pinned formulas at their own frequency - the same operations on the
-// same operands as in the loop, so the same bits - and write the record's transfer records side by side (one contiguous
+// record read the same 64 bytes of inputs (bl_unpack_plain_coef_inputs), evaluate the pinned formulas at their own frequency - the
+// loop's own body, write_transfer_records() at one frequency - and write the record's transfer records side by side (one contiguous
 // kilobyte per sample at 64 frequencies instead of 64 scattered 16-byte stores per lane), at four waves per SIMD.
 template <bool kExtended>
 __global__ void __launch_bounds__(256, 4) bl_coefficients_freq_kernel(const BlShadeArgs P) {
@@ -164,19 +144,8 @@ __global__ void __launch_bounds__(256, 4) bl_coefficients_freq_kernel(const BlSh
     const BlCoefInputs ci = P.coef_inputs[idx];
     const double momentum_factor = bl_ray_factor(P.ray_constants, (size_t)ray);
     SampleShade sh;
-    sh.have_coefficients = ci.have_coefficients != 0.0;
-    sh.nu_fluid_over_nu = ci.nu_fluid_over_nu;
-    sh.n_e_cgs = ci.n_e_cgs;
-    sh.nu_c_cgs = ci.nu_c_cgs;
-    sh.theta_e = ci.theta_e;
-    sh.kb_tt_e_cgs = ci.kb_tt_e_cgs;
-    sh.sin_theta_b = ci.cos2_theta_b;
-    const double delta_lambda = ci.cos_sign;
-    const double freq = P.frequencies[l];
-    double j_val = 0.0, alpha_val = 0.0;
-    if (sh.have_coefficients) simulation_coefficients<kExtended>(P, sh, freq, momentum_factor, &j_val, &alpha_val);
-    const double delta_lambda_cgs = bl_div_g(delta_lambda * P.x_unit, freq * momentum_factor);   // unpolarized.cpp:75-76
-    P.transfer[((size_t)P.ray_offset[ray] + n) * P.n_nu + l] = transfer_record(j_val, alpha_val, delta_lambda_cgs);
+    const double delta_lambda = bl_unpack_plain_coef_inputs(ci, &sh);
+    write_transfer_records<kExtended>(P, sh, P.frequencies[l], momentum_factor, delta_lambda, P.transfer + ((size_t)P.ray_offset[ray] + n) * P.n_nu + l);
   }
 }
 

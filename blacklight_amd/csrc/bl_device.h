@@ -424,6 +424,36 @@ struct alignas(16) BlCoefInputs {
   double cos_sign;           // +-1: sign of k.b in the fluid frame (:455)
   double have_coefficients;  // 1: the sample has coefficients; 0: j = alpha = rho = 0 at every frequency
 };
+#if defined(__HIPCC__) || defined(__HIP__)
+// ... and in plain images with several frequencies (BlShadeArgs::coef_split) what the unpolarized formulas need, left by the
+// coefficient kernel for bl_coefficients_freq_kernel. They take sin theta_B and neither the cosine nor its sign, and the transfer
+// record takes the sample's length: such a row carries sin theta_B in cos2_theta_b and the length in cos_sign. This pair is the
+// only code that knows. (Shade: SampleShade, bl_sampling.h. unpack returns the length.)
+template <class Shade>
+__device__ __forceinline__ BlCoefInputs bl_pack_plain_coef_inputs(const Shade &sh, double delta_lambda) {
+  BlCoefInputs ci;
+  ci.nu_fluid_over_nu = sh.nu_fluid_over_nu;
+  ci.n_e_cgs = sh.n_e_cgs;
+  ci.nu_c_cgs = sh.nu_c_cgs;
+  ci.theta_e = sh.theta_e;
+  ci.kb_tt_e_cgs = sh.kb_tt_e_cgs;
+  ci.cos2_theta_b = sh.sin_theta_b;
+  ci.cos_sign = delta_lambda;
+  ci.have_coefficients = sh.have_coefficients ? 1.0 : 0.0;
+  return ci;
+}
+template <class Shade>
+__device__ __forceinline__ double bl_unpack_plain_coef_inputs(const BlCoefInputs &ci, Shade *sh) {
+  sh->have_coefficients = ci.have_coefficients != 0.0;
+  sh->nu_fluid_over_nu = ci.nu_fluid_over_nu;
+  sh->n_e_cgs = ci.n_e_cgs;
+  sh->nu_c_cgs = ci.nu_c_cgs;
+  sh->theta_e = ci.theta_e;
+  sh->kb_tt_e_cgs = ci.kb_tt_e_cgs;
+  sh->sin_theta_b = ci.cos2_theta_b;
+  return ci.cos_sign;
+}
+#endif
 
 // ... and with several polarized variants in one pass (bl_set_polarized_variants, BlShadeArgs::pol_variants > 0) the row of a sample
 // with coefficients holds what no variant enters: n_e_cgs = the cell's rho and p_gas (two floats), nu_c_cgs = b_mu b^mu in code units,

@@ -134,16 +134,18 @@ __device__ __forceinline__ double2 transfer_record(double j, double alpha, doubl
   return rec;
 }
 
-// Everything the per-frequency loop needs from the per-sample (frequency independent) work
+// Everything the per-frequency loop needs from the per-sample (frequency independent) work. A SampleShade starts empty - a sample
+// without coefficients and without cell values, as a cut one stays: the initialisers below. The members without one are written
+// before they are read wherever have_coefficients or have_cell says they hold something.
 struct SampleShade {
-  bool have_coefficients;      // false: j = alpha = 0 at every frequency
-  double nu_fluid_over_nu;     // -k_mu u^mu (fluid-frame frequency per unit camera frequency*factor)
-  double n_e_cgs, nu_c_cgs, theta_e, sin_theta_b, kb_tt_e_cgs;   // simulation
-  double cos_theta_b, sin2_theta_b, cos2_theta_b, cos_sign;       // polarized coefficients only
+  bool have_coefficients = false;    // false: j = alpha = 0 at every frequency
+  double nu_fluid_over_nu = 0.0;     // -k_mu u^mu (fluid-frame frequency per unit camera frequency*factor)
+  double n_e_cgs = 0.0, nu_c_cgs = 0.0, theta_e = 0.0, sin_theta_b = 0.0, kb_tt_e_cgs = 0.0;   // simulation
+  double cos_theta_b = 0.0, sin2_theta_b = 0.0, cos2_theta_b = 0.0, cos_sign = 1.0;             // polarized coefficients only
   double b_sq;                 // b_mu b^mu in code units (polarized variants in one pass: write_polarized_inputs)
   double theta_e_096, kk_0, kk_1, kk_2;   // polarized, thermal: theta_e^0.96 and K_0,1,2(1 / theta_e) - the same at every frequency
-  double n_n0_fluid, fu[4];                                       // formula
-  bool have_cell;              // cell_values recorded (simulation_coefficients.cpp:377-387)
+  double n_n0_fluid = 0.0, fu[4] = {0.0, 0.0, 0.0, 0.0};                                       // formula
+  bool have_cell = false;      // cell_values recorded (simulation_coefficients.cpp:377-387)
   double cell[BL_NUM_CELL_VALUES];
 };
 
@@ -1613,6 +1615,63 @@ __device__ __forceinline__ void write_polarized_inputs(const BlShadeArgs &P, uns
     }
   }
   P.coef_inputs[idx_cur] = ci;
+}
+
+// ---- The exact tier's sample, once: what bl_shade_kernel, bl_shade_exact_kernel, bl_shade_exact2_kernel and
+// bl_shade_polarized2_kernel do between a record with its primitives and the sample's outputs. The reference's bits come from this
+// sequence of calls on these operands; the kernels differ in how they get a record there, not in this.
+
+// y or k_y of a record seen as its ray's mirror image in the plane y = 0 (mirror pairs): the sign bit flipped, whatever the value -
+// a NaN's too, as negation flips it
+__device__ __forceinline__ double mirror_y(double value, bool mirror) {
+  return __hiloint2double(__double2hiint(value) ^ (int)(mirror ? 0x80000000u : 0u), __double2loint(value));
+}
+
+// Per-sample renormalisation of the stored momentum (geodesics.cpp:352-371): k_i scaled so that k is null in the metric at the sample.
+// kMaybeFlat: the instantiations that do not know the spacetime curved at compile time ask st.ray_flat.
+// Whether it applies is the caller's question - BlShadeArgs::samples_renormalised: samples loaded from a geodesic checkpoint carry
+// the renormalised momentum already.
+template <bool kMaybeFlat>
+__device__ __forceinline__ void renormalise_momentum(const BlSpacetime &st, const BlKerrSchild &ks, double kcov[4]) {
+  double gcon[4][4];
+  if (kMaybeFlat && st.ray_flat)
+    bl_minkowski(gcon);
+  else
+    bl_gcon_ks(ks, gcon);
+  const double factor = bl_renormalization_factor_g(gcon, kcov[0], kcov[1], kcov[2], kcov[3]);
+  kcov[1] *= factor;
+  kcov[2] *= factor;
+  kcov[3] *= factor;
+}
+
+// A simulation sample from its record (position, stored momentum in kcov), its status and primitives: the Kerr-Schild scalars at the
+// sample - evaluated once, shared by the renormalisation, the simulation metric and the geodesic metric (the reference recomputes
+// them in each of those functions; identical inputs, identical bits), and left in *ks for write_aux_record - the renormalised
+// momentum left in kcov, and the frequency-independent part of the coefficients unless the sample was cut.
+template <bool kExtended, bool kSksCurved, bool kSpinZero>
+__device__ __forceinline__ SampleShade exact_sample(const BlShadeArgs &P, const BlSpacetime &st, double x1, double x2, double x3, double ph_unwrapped,
+                                                    int status, const float pr[8], bool renormalise, double kcov[4], int need_coefficients,
+                                                    BlPolSample *pol_out, BlKerrSchild *ks) {
+  bl_kerr_schild<kSpinZero>(st, x1, x2, x3, ks);   // r^2 as the locate step computed it: same operations, same bits
+  if (renormalise) renormalise_momentum<!kSksCurved>(st, *ks, kcov);
+  SampleShade sh;
+  if (status != kSampleCut) sample_finish_simulation<kExtended, kSksCurved>(P, st, *ks, x3 / ks->r, ph_unwrapped, pr, 0.0f, kcov, need_coefficients, &sh, pol_out);
+  return sh;
+}
+
+// The transfer record (a, b) of a plain image's sample at one frequency (simulation_coefficients.cpp:464-584, unpolarized.cpp:74-110) ...
+template <bool kExtended>
+__device__ __forceinline__ void write_transfer_records(const BlShadeArgs &P, const SampleShade &sh, double freq, double momentum_factor, double delta_lambda,
+                                                       double2 *out) {
+  double j_val = 0.0, alpha_val = 0.0;
+  if (sh.have_coefficients) simulation_coefficients<kExtended>(P, sh, freq, momentum_factor, &j_val, &alpha_val);
+  const double delta_lambda_cgs = bl_div_g(delta_lambda * P.x_unit, freq * momentum_factor);   // unpolarized.cpp:75-76
+  *out = transfer_record(j_val, alpha_val, delta_lambda_cgs);
+}
+// ... and at every frequency of the render, out[0 .. n_nu)
+template <bool kExtended>
+__device__ __forceinline__ void write_transfer_records(const BlShadeArgs &P, const SampleShade &sh, double momentum_factor, double delta_lambda, double2 *out) {
+  for (int l = 0; l < P.n_nu; l++) write_transfer_records<kExtended>(P, sh, P.frequencies[l], momentum_factor, delta_lambda, out + l);
 }
 
 // The corner cells of a located sample, requested (gather_issue) one sample ahead of their use (gather_finish): the two

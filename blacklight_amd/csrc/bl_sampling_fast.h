@@ -148,3 +148,42 @@ __device__ __forceinline__ void locate_sample_tolerant(const BlShadeArgs &P, con
 
 
 #pragma clang fp contract(off)
+
+// The polarized coefficients of a sample (simulation_coefficients.cpp:453-455, :458-698), for bl_polarized_coefficients_kernel and
+// for bl_shade_polarized2_kernel where it evaluates them itself. E: the block the electron constants are read from.
+// kTolerant: the tolerant tier's functions and fused multiply-adds in the formulas (bl_coefficients.inc, second inclusion - why these
+// two live here and not in bl_sampling.h); kElectrons: power-law and kappa-distribution electrons known to the formulas.
+// What does not depend on the frequency, once per sample (the reference recomputes it for every frequency): sine and cosine of
+// theta_B from sh->cos2_theta_b and sh->cos_sign - the same operations the coefficient kernel applies to the same value -
+// theta_e^0.96 and K_0,1,2(1 / theta_e) ...
+template <bool kTolerant>
+__device__ __forceinline__ void polarized_sample_prelude(const BlShadeArgs &E, SampleShade *sh) {
+  sh->sin2_theta_b = 1.0 - sh->cos2_theta_b;
+  sh->sin_theta_b = bl_sqrt_g(sh->sin2_theta_b);
+  sh->cos_theta_b = bl_sqrt_g(sh->cos2_theta_b) * sh->cos_sign;
+  sh->theta_e_096 = sh->kk_0 = sh->kk_1 = sh->kk_2 = 0.0;
+  if (sh->have_coefficients && E.plasma.plasma_thermal_frac != 0.0) {
+    sh->theta_e_096 = kTolerant ? fastmath::pow(sh->theta_e, 0.96) : bl_pow(sh->theta_e, 0.96);
+    if (sh->theta_e >= 0.01) {   // theta_e_zero, radiation_integrator.hpp:190
+      if (kTolerant) fastmath::bessel_k012(1.0 / sh->theta_e, &sh->kk_0, &sh->kk_1, &sh->kk_2);
+      else bl_cyl_bessel_k012(1.0 / sh->theta_e, &sh->kk_0, &sh->kk_1, &sh->kk_2);
+    }
+  }
+}
+// ... and the sample's row of pol_coeffs at one frequency: (j_I, alpha_I) and the three polarized pairs
+template <bool kTolerant, bool kElectrons>
+__device__ __forceinline__ void polarized_sample_coefficients(const BlShadeArgs &E, const SampleShade &sh, double momentum_factor, double freq, double2 *out_row) {
+  double j_val = 0.0, alpha_val = 0.0;
+  double2 pc[3] = {make_double2(0.0, 0.0), make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
+  if (kTolerant) {
+    if (sh.have_coefficients) simulation_coefficients_fast<kElectrons>(E, sh, freq, momentum_factor, &j_val, &alpha_val);
+    polarized_coefficients_fast<kElectrons>(E, sh, freq, momentum_factor, j_val, alpha_val, pc);
+  } else {
+    if (sh.have_coefficients) simulation_coefficients<kElectrons>(E, sh, freq, momentum_factor, &j_val, &alpha_val);
+    polarized_coefficients<kElectrons>(E, sh, freq, momentum_factor, j_val, alpha_val, pc);
+  }
+  out_row[0] = make_double2(j_val, alpha_val);
+  out_row[1] = pc[0];
+  out_row[2] = pc[1];
+  out_row[3] = pc[2];
+}

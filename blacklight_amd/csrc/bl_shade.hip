@@ -72,10 +72,8 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
     const bool mirror = pairs && idx_walked != idx;
     const unsigned long long idx_walked_cur = idx_walked;
     double2 q0 = nq0, q1 = nq1, q2 = nq2, q3 = nq3;
-    if (mirror) {
-      q0.y = -q0.y;   // (sign bit only: y)
-      q2.y = -q2.y;   // (k_y)
-    }
+    q0.y = mirror_y(q0.y, mirror);   // y
+    q2.y = mirror_y(q2.y, mirror);   // k_y
     double2 l0 = nl0, l1 = nl1;
     unsigned long long tag = ntag;
     const uint32_t ray = (uint32_t)__double_as_longlong(q1.y);
@@ -164,26 +162,8 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
       status = skip ? kSampleCut : kSampleFormula;
       for (int v = 0; v < 8; v++) pr[v] = 0.0f;
     }
-    if (!P.samples_renormalised) {   // per-sample renormalisation of the stored momentum (geodesics.cpp:352-371); samples
-      double gcon[4][4];             // loaded from a geodesic checkpoint carry the renormalised momentum already
-      if (!kSksCurved && st.ray_flat)
-        bl_minkowski(gcon);
-      else
-        bl_gcon_ks(ks, gcon);
-      double factor = bl_renormalization_factor_g(gcon, kcov[0], kcov[1], kcov[2], kcov[3]);
-      kcov[1] *= factor;
-      kcov[2] *= factor;
-      kcov[3] *= factor;
-    }
+    if (!P.samples_renormalised) renormalise_momentum<!kSksCurved>(st, ks, kcov);
     SampleShade sh;
-    sh.have_coefficients = false;
-    sh.nu_fluid_over_nu = 0.0;
-    sh.n_e_cgs = sh.nu_c_cgs = sh.theta_e = sh.sin_theta_b = sh.kb_tt_e_cgs = 0.0;
-    sh.cos_theta_b = sh.sin2_theta_b = sh.cos2_theta_b = 0.0;
-    sh.cos_sign = 1.0;
-    sh.n_n0_fluid = 0.0;
-    sh.fu[0] = sh.fu[1] = sh.fu[2] = sh.fu[3] = 0.0;
-    sh.have_cell = false;
     bool nan_ray = false;
     if (kAux) {
       // rays that ended on ray_max_steps / retries with fallback_nan: simulation mode samples NaN
@@ -214,17 +194,8 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
     }
     if (!kAux && !kPolarized && !kRedo && kModel == BL_MODEL_SIMULATION && P.coef_split) {
       // exact tier with several frequencies: the per-frequency formulas and transfer records are bl_coefficients_freq_kernel's,
-      // one lane per (record, frequency); it gets the six numbers they need, the sample's length in the sign's slot
-      BlCoefInputs ci;
-      ci.nu_fluid_over_nu = sh.nu_fluid_over_nu;
-      ci.n_e_cgs = sh.n_e_cgs;
-      ci.nu_c_cgs = sh.nu_c_cgs;
-      ci.theta_e = sh.theta_e;
-      ci.kb_tt_e_cgs = sh.kb_tt_e_cgs;
-      ci.cos2_theta_b = sh.sin_theta_b;   // (sin theta_B itself: nothing here needs the cosine)
-      ci.cos_sign = delta_lambda;
-      ci.have_coefficients = sh.have_coefficients ? 1.0 : 0.0;
-      P.coef_inputs[idx_cur] = ci;
+      // one lane per (record, frequency); it gets the six numbers they need and the sample's length
+      P.coef_inputs[idx_cur] = bl_pack_plain_coef_inputs(sh, delta_lambda);
       continue;
     }
     if (kRedo && kModel == BL_MODEL_SIMULATION && P.freq_split) {
@@ -260,7 +231,11 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
       }
       continue;
     }
-    // ---------------- per-frequency coefficients and transfer records
+    if (!kAux && !kRedo && kModel == BL_MODEL_SIMULATION) {   // a plain image: the transfer records as every exact kernel writes them
+      write_transfer_records<kExtended>(P, sh, momentum_factor, delta_lambda, out);
+      continue;
+    }
+    // ---------------- auxiliary images, formula mode, the second pass: per-frequency coefficients and what each keeps of them
     for (int l = 0; l < P.n_nu; l++) {
       const double freq = P.frequencies[l];
       double j_val = 0.0, alpha_val = 0.0;
@@ -291,10 +266,11 @@ __global__ void __launch_bounds__(256, 2) bl_shade_kernel(const BlShadeArgs P_at
 
 
 // ---- the exact tier's coefficient kernel for the benchmark's case (plain image of a spherical Kerr-Schild simulation in a
-// curved spacetime, thermal electrons): bl_shade_kernel<simulation, false, false, true, false, kSpinZero>'s arithmetic, call for
-// call, behind bl_shade_fast_kernel's software pipeline - located sample of `next` loading, corner cells and record of `cur`
-// requested, trilinear read and arithmetic of `prev` - with every load of the loop unconditional so that the waits are
-// exact. The unpipelined kernel waited for memory in 44 % of its wave cycles. No arithmetic changes: bit-identical.
+// curved spacetime, thermal electrons): the sample bl_shade_kernel<simulation, false, false, true, false, kSpinZero> would shade -
+// exact_sample() and write_transfer_records() or the row for bl_coefficients_freq_kernel (bl_sampling.h), which that kernel's
+// pieces are too - behind bl_shade_fast_kernel's software pipeline - located sample of `next` loading, corner cells and record of
+// `cur` requested, trilinear read and arithmetic of `prev` - with every load of the loop unconditional so that the waits are
+// exact. The unpipelined kernel waited for memory in 44 % of its wave cycles.
 template <bool kSpinZero>
 __global__ void __launch_bounds__(256, 2) bl_shade_exact_kernel(const BlShadeArgs P) {
   const BlSpacetime st = P.st;
@@ -356,52 +332,13 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact_kernel(const BlShadeArg
     // (with spin the arithmetic below needs the ten registers of the located sample in flight: requested behind it instead)
     if (kSpinZero) load_located(have_next ? idx : last, loc_next);
     if (live) {
-    // ---- from here on: bl_shade_kernel's body for this instantiation
-    const double x1 = rec.q0.x, x2 = rec.q0.y, x3 = rec.q1.x;
     const double delta_lambda = -rec.q3.y;   // ReverseGeodesics: sample_len = -geodesic_len (:840)
     double kcov[4] = {kt, rec.q2.x, rec.q2.y, rec.q3.x};
     BlKerrSchild ks;
-    bl_kerr_schild<kSpinZero>(st, x1, x2, x3, &ks);
-    if (!P.samples_renormalised) {   // per-sample renormalisation of the stored momentum (geodesics.cpp:352-371)
-      double gcon[4][4];
-      bl_gcon_ks(ks, gcon);
-      double factor = bl_renormalization_factor_g(gcon, kcov[0], kcov[1], kcov[2], kcov[3]);
-      kcov[1] *= factor;
-      kcov[2] *= factor;
-      kcov[3] *= factor;
-    }
-    SampleShade sh;
-    sh.have_coefficients = false;
-    sh.nu_fluid_over_nu = 0.0;
-    sh.n_e_cgs = sh.nu_c_cgs = sh.theta_e = sh.sin_theta_b = sh.kb_tt_e_cgs = 0.0;
-    sh.cos_theta_b = sh.sin2_theta_b = sh.cos2_theta_b = 0.0;
-    sh.cos_sign = 1.0;
-    sh.n_n0_fluid = 0.0;
-    sh.fu[0] = sh.fu[1] = sh.fu[2] = sh.fu[3] = 0.0;
-    sh.have_cell = false;
-    if (status != kSampleCut) sample_finish_simulation<false, true>(P, st, ks, x3 / ks.r, ph, pr, 0.0f, kcov, 1, &sh, nullptr);
-    double2 *out = P.transfer + (size_t)row * P.n_nu;
-    if (P.coef_split) {
-      // several frequencies: the per-frequency formulas and transfer records are bl_coefficients_freq_kernel's
-      BlCoefInputs ci;
-      ci.nu_fluid_over_nu = sh.nu_fluid_over_nu;
-      ci.n_e_cgs = sh.n_e_cgs;
-      ci.nu_c_cgs = sh.nu_c_cgs;
-      ci.theta_e = sh.theta_e;
-      ci.kb_tt_e_cgs = sh.kb_tt_e_cgs;
-      ci.cos2_theta_b = sh.sin_theta_b;   // (sin theta_B itself: nothing there needs the cosine)
-      ci.cos_sign = delta_lambda;
-      ci.have_coefficients = sh.have_coefficients ? 1.0 : 0.0;
-      P.coef_inputs[idx_rec] = ci;
-    } else {
-      for (int l = 0; l < P.n_nu; l++) {
-        const double freq = P.frequencies[l];
-        double j_val = 0.0, alpha_val = 0.0;
-        if (sh.have_coefficients) simulation_coefficients<false>(P, sh, freq, momentum_factor, &j_val, &alpha_val);
-        const double delta_lambda_cgs = bl_div_g(delta_lambda * P.x_unit, freq * momentum_factor);   // unpolarized.cpp:75-76
-        out[l] = transfer_record(j_val, alpha_val, delta_lambda_cgs);
-      }
-    }
+    const SampleShade sh = exact_sample<false, true, kSpinZero>(P, st, rec.q0.x, rec.q0.y, rec.q1.x, ph, status, pr, !P.samples_renormalised, kcov, 1, nullptr, &ks);
+    // (several frequencies: the per-frequency formulas and transfer records are bl_coefficients_freq_kernel's)
+    if (P.coef_split) P.coef_inputs[idx_rec] = bl_pack_plain_coef_inputs(sh, delta_lambda);
+    else write_transfer_records<false>(P, sh, momentum_factor, delta_lambda, P.transfer + (size_t)row * P.n_nu);
     }
     if (!kSpinZero) load_located(have_next ? idx : last, loc_next);
   }

@@ -1519,12 +1519,35 @@ __device__ __forceinline__ LocatedExact locate_exact(const BlSpacetime &st, cons
 
 }  // namespace fused2
 
-template <bool kSpinZero>
-__global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeArgs P) {
+// =================================================================================================
+// The record walk of the two exact-arithmetic kernels with the locate step inside (bl_shade_exact2_kernel, bl_shade_polarized2_kernel):
+// bl_shade_fused2_kernel's pipeline - three samples in flight per lane: the position record of `next` loading and then located, the
+// corner cells, the momentum record and the per-ray constants of `cur` requested, `prev` shaded by the kernel's own body - with
+// the exact tier's locate step (locate_exact). What the body gets of `prev`:
+// =================================================================================================
+struct WalkSample {
+  double2 q0, q1, q2, q3;       // the record: x, y | z, (ray, n) | k_x, k_y | k_z, -length. A mirror image's y and k_y are the image's
+  double kt, momentum_factor;   // of its ray (the factor only where the kernel asks for it: kFactor)
+  size_t row;                   // of the sample in the per-sample arrays (a mirror image's: row_add further on)
+  uint32_t index;               // of the record in the scratch set (not kept by a walk over mirror pairs)
+  unsigned char ray_flag;       // BlShadeArgs::ray_flags of its ray (kRayFlags)
+  int status;                   // LocatedExact::status
+  double ph_unwrapped;
+};
+// kMirrorPairs: BlShadeArgs::row_add != 0 (bl_shade_fused2_kernel) makes the indices walked [0, 2 n_records); index i >= n_records - for
+// all lanes of a wave or none, n_records being a multiple of 64 - is record i - n_records as its ray's mirror image in y = 0: the sign
+// bits of y and k_y flipped (mirror_y), its rows row_add further on.
+// kGatherBehind: the corner cells of `cur` are requested behind the body instead of in front of it - for a body whose arithmetic needs
+// the sixty-four registers they land in (a polarized sample's tetrad: with the requests in front of it that kernel keeps 3 ... 24
+// registers in scratch memory); the search for `next` and the other wave of the SIMD cover their way.
+// body(sample, pr): called for live samples only; pr: the sample's eight primitives (gather_finish).
+template <bool kSpinZero, bool kMirrorPairs, bool kGatherBehind, bool kFactor, bool kRayFlags, class Body>
+__device__ __forceinline__ void exact_record_walk(const BlShadeArgs &P, const BlSpacetime &st, double *lds, Body body) {
   using namespace fused2;
-  extern __shared__ double lds[];
   const uint32_t lds_base = lds_address(lds);
-  const bool mesh = P.grid.n_blocks > 0;   // (a mesh with refinement: as in the polarized kernel below)
+  // (a mesh with refinement that the tolerant tier's fused kernel would take - BlGridDevice::fused_lds_bytes - has its row chunks and box
+  // descriptors here too, with widths where that kernel keeps reciprocals: locate_exact<., true>)
+  const bool mesh = P.grid.n_blocks > 0;
   if (mesh) stage_refined_rows<false>(P.grid, reinterpret_cast<char *>(lds), lds_base);
   else stage_axis_rows<false>(P.grid, reinterpret_cast<AxisRow *>(lds));
   __syncthreads();
@@ -1533,7 +1556,6 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
   if (n_records <= first_record) return;
   const uint32_t stride = gridDim.x * blockDim.x;
   const uint32_t last = n_records - 1u;
-  const BlSpacetime st = P.st;
   const GridScalars G = mesh ? grid_scalars_refined(P.grid, lds_base) : grid_scalars(P.grid, lds_base);
   const double camera_r = P.cuts.camera_r;
   const float fallback_rho = P.cold->fallback_rho, fallback_pgas = P.cold->fallback_pgas;
@@ -1542,27 +1564,22 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
   const double2 *ray_constants = P.ray_constants;
   const char *ray_offset = reinterpret_cast<const char *>(P.ray_offset);
   unsigned long long gathers_wave = 0ull;
-  const double freq = uniform_value(P.frequencies[0]);
   const char *records = reinterpret_cast<const char *>(P.records_hot);
   const uint32_t lane_index = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lane_bytes = lane_index << 6;
   uint32_t base_index = first_record;
-  // Mirror pairs (BlShadeArgs::row_add != 0, bl_shade_fused2_kernel): the indices walked are [0, 2 n_records); index i >= n_records - for
-  // all lanes of a wave or none, n_records being a multiple of 64 - is record i - n_records as its ray's mirror image in y = 0: the
-  // sign bits of y and k_y flipped, its rows row_add further on.
-  // (the zero-spin instantiation only: no other is launched by a paired render)
-  const uint32_t n_virtual = (kSpinZero && P.row_add != 0u) ? 2u * n_records : n_records;
-  auto is_mirror = [&](uint32_t first, bool in) { return kSpinZero && in && first + lane_index >= n_records; };
+  const uint32_t n_virtual = (kMirrorPairs && P.row_add != 0u) ? 2u * n_records : n_records;
+  auto is_mirror = [&](uint32_t first, bool in) { return kMirrorPairs && in && first + lane_index >= n_records; };
   auto record_base = [&](uint32_t first) { return records + ((size_t)(first < last ? first : last) << 6); };
   auto record_of = [&](uint32_t first, bool in) {
     const bool mirror = is_mirror(first, in);
     return reinterpret_cast<const double2 *>(mirror ? records + ((size_t)(first + lane_index - n_records) << 6) : record_base(first) + (size_t)(in ? lane_bytes : 0u));
   };
-  auto mirrored = [](double value, bool mirror) { return __hiloint2double(__double2hiint(value) ^ (int)(mirror ? 0x80000000u : 0u), __double2loint(value)); };
   double2 prev0 = make_double2(0.0, 0.0), prev1 = make_double2(0.0, __longlong_as_double((long long)BL_DEAD_RAY)), prev2 = prev0, prev3 = prev0;
   double2 cur0, cur1;
   double kt_prev = 0.0, factor_prev = 1.0;
   long long row_prev = 0;
+  unsigned char flag_prev = 0;
   bool mirror_prev = false;
   LocatedExact loc_prev, loc_cur;
   loc_prev.f_i = loc_prev.f_j = loc_prev.f_k = loc_prev.ph_unwrapped = 0.0;
@@ -1576,7 +1593,7 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
     const double2 *rec = record_of(first_record, cur_in);
     cur0 = rec[0];
     cur1 = rec[1];
-    cur0.y = mirrored(cur0.y, is_mirror(first_record, cur_in));
+    if (kMirrorPairs) cur0.y = mirror_y(cur0.y, is_mirror(first_record, cur_in));
     cur1.y = cur_in ? cur1.y : __longlong_as_double((long long)BL_DEAD_RAY);
   }
   loc_cur = locate_exact<kSpinZero, true>(st, P.grid, G, camera_r, (uint32_t)__double_as_longlong(cur1.y) != BL_DEAD_RAY, cur0.x, cur0.y, cur1.x);
@@ -1595,11 +1612,12 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
       next1 = rec[1];
     }
     const double kt = kt_prev, momentum_factor = factor_prev;
-    const long long row_first = row_prev + (long long)(mirror_prev ? P.row_add : 0u);
+    const long long row_first = kMirrorPairs ? row_prev + (long long)(mirror_prev ? P.row_add : 0u) : row_prev;
+    const unsigned char ray_flag = flag_prev;
     float pr[8];
     gather_finish(P, fallback_rho, fallback_pgas, status, lo, hi, loc_prev.f_i, loc_prev.f_j, loc_prev.f_k, pr);
     gathers_wave += (unsigned long long)__popcll(__ballot(status == (int)kSampleInterp));
-    fused2::gather_issue(cells, loc_cur.cell_bytes, loc_cur.status == (uint32_t)kSampleInterp, row_bytes, plane_bytes, lo, hi);
+    if (!kGatherBehind) fused2::gather_issue(cells, loc_cur.cell_bytes, loc_cur.status == (uint32_t)kSampleInterp, row_bytes, plane_bytes, lo, hi);
     double2 cold0, cold1;
     {
       const double2 *rec = record_of(base_index, cur_in);
@@ -1609,43 +1627,34 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
     {
       const uint32_t ray_cur = (uint32_t)__double_as_longlong(cur1.y);
       const uint32_t ray_slot = ray_cur != BL_DEAD_RAY ? ray_cur : 0u;
-      const double2 constants = bl_ray_constants(ray_constants, (size_t)ray_slot);
-      kt_prev = constants.x;
-      factor_prev = constants.y;
+      if (kFactor) {
+        const double2 constants = bl_ray_constants(ray_constants, (size_t)ray_slot);
+        kt_prev = constants.x;
+        factor_prev = constants.y;
+      } else {
+        kt_prev = bl_ray_kt(ray_constants, (size_t)ray_slot);
+      }
       row_prev = *reinterpret_cast<const long long *>(ray_offset + (size_t)(ray_slot << 3));
+      if (kRayFlags) flag_prev = P.ray_flags[ray_slot];
     }
     if (live) {
-      // ---- bl_shade_exact_kernel's body (bl_shade.hip), call for call
-      const double x1 = prev0.x, x2 = prev0.y, x3 = prev1.x;
-      const double delta_lambda = -prev3.y;   // ReverseGeodesics: sample_len = -geodesic_len (geodesics.cpp:840)
-      double kcov[4] = {kt, prev2.x, mirrored(prev2.y, mirror_prev), prev3.x};
-      BlKerrSchild ks;
-      bl_kerr_schild<kSpinZero>(st, x1, x2, x3, &ks);
-      {   // per-sample renormalisation of the stored momentum (geodesics.cpp:352-371)
-        double gcon[4][4];
-        bl_gcon_ks(ks, gcon);
-        const double factor = bl_renormalization_factor_g(gcon, kcov[0], kcov[1], kcov[2], kcov[3]);
-        kcov[1] *= factor;
-        kcov[2] *= factor;
-        kcov[3] *= factor;
-      }
-      SampleShade sh;
-      sh.have_coefficients = false;
-      sh.nu_fluid_over_nu = 0.0;
-      sh.n_e_cgs = sh.nu_c_cgs = sh.theta_e = sh.sin_theta_b = sh.kb_tt_e_cgs = 0.0;
-      sh.cos_theta_b = sh.sin2_theta_b = sh.cos2_theta_b = 0.0;
-      sh.cos_sign = 1.0;
-      sh.n_n0_fluid = 0.0;
-      sh.fu[0] = sh.fu[1] = sh.fu[2] = sh.fu[3] = 0.0;
-      sh.have_cell = false;
-      if (status != kSampleCut) sample_finish_simulation<false, true>(P, st, ks, x3 / ks.r, loc_prev.ph_unwrapped, pr, 0.0f, kcov, 1, &sh, nullptr);
-      double j_val = 0.0, alpha_val = 0.0;
-      if (sh.have_coefficients) simulation_coefficients<false>(P, sh, freq, momentum_factor, &j_val, &alpha_val);
-      const double delta_lambda_cgs = bl_div_g(delta_lambda * P.x_unit, freq * momentum_factor);   // unpolarized.cpp:75-76
-      P.transfer[(size_t)(row_first + (long long)n)] = transfer_record(j_val, alpha_val, delta_lambda_cgs);
+      WalkSample s;
+      s.q0 = prev0;
+      s.q1 = prev1;
+      s.q2 = make_double2(prev2.x, kMirrorPairs ? mirror_y(prev2.y, mirror_prev) : prev2.y);
+      s.q3 = prev3;
+      s.kt = kt;
+      s.momentum_factor = momentum_factor;
+      s.row = (size_t)(row_first + (long long)n);
+      s.index = base_index - stride + lane_index;
+      s.ray_flag = ray_flag;
+      s.status = status;
+      s.ph_unwrapped = loc_prev.ph_unwrapped;
+      body(s, pr);
     }
+    if (kGatherBehind) fused2::gather_issue(cells, loc_cur.cell_bytes, loc_cur.status == (uint32_t)kSampleInterp, row_bytes, plane_bytes, lo, hi);
     const bool live_next = next_in && (uint32_t)__double_as_longlong(next1.y) != BL_DEAD_RAY;
-    next0.y = mirrored(next0.y, is_mirror(next_first, next_in));
+    if (kMirrorPairs) next0.y = mirror_y(next0.y, is_mirror(next_first, next_in));
     LocatedExact loc_next = loc_cur;
     if (__any(live_next)) loc_next = locate_exact<kSpinZero, true>(st, P.grid, G, camera_r, live_next, next0.x, next0.y, next1.x);
     else loc_next.status = kSampleNone, loc_next.cell_bytes = 0u;
@@ -1655,7 +1664,7 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
     prev3 = cold1;
     loc_prev = loc_cur;
     prev_in = cur_in;
-    mirror_prev = is_mirror(base_index, cur_in);
+    if (kMirrorPairs) mirror_prev = is_mirror(base_index, cur_in);
     cur0 = next0;
     cur1 = next1;
     cur1.y = next_in ? next1.y : __longlong_as_double((long long)BL_DEAD_RAY);
@@ -1666,11 +1675,31 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
   if ((threadIdx.x & 63) == 0 && gathers_wave != 0ull) atomicAdd(&P.counters[BL_CNT_GATHERS], gathers_wave);
 }
 
+// The exact tier's plain image at one frequency, locate step inside: bl_locate_plain_kernel + bl_shade_exact_kernel in one kernel -
+// locate_exact() in the walk above for the former, and the latter's sample: exact_sample() and write_transfer_records() (bl_sampling.h).
+// Mirror pairs: the zero-spin instantiation only (no other is launched by a paired render).
+template <bool kSpinZero>
+__global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeArgs P) {
+  extern __shared__ double lds[];
+  const BlSpacetime st = P.st;
+  const double freq = fused2::uniform_value(P.frequencies[0]);
+  exact_record_walk<kSpinZero, kSpinZero, false, true, false>(P, st, lds, [&](const WalkSample &s, const float (&pr)[8]) {
+    // (the stored momentum is renormalised here without asking BlShadeArgs::samples_renormalised: the plan gives this kernel no
+    // render of samples loaded from a geodesic checkpoint - locate_inside_possible needs no_checkpoint)
+    const double delta_lambda = -s.q3.y;   // ReverseGeodesics: sample_len = -geodesic_len (geodesics.cpp:840)
+    double kcov[4] = {s.kt, s.q2.x, s.q2.y, s.q3.x};
+    BlKerrSchild ks;
+    const SampleShade sh = exact_sample<false, true, kSpinZero>(P, st, s.q0.x, s.q0.y, s.q1.x, s.ph_unwrapped, s.status, pr, true, kcov, 1, nullptr, &ks);
+    write_transfer_records<false>(P, sh, freq, s.momentum_factor, delta_lambda, P.transfer + s.row);
+  });
+}
+
 // =================================================================================================
 // Polarized runs, locate step inside (bl_shade_polarized2_kernel): bl_locate_plain_kernel + bl_shade_kernel<simulation, aux, extended,
-// curved SKS, polarized> behind bl_shade_exact2_kernel's pipeline - the same calls on the same operands, so the same BlPolSample frames,
-// BlCoefInputs and auxiliary records, bit for bit (both tiers: the frame of a polarized sample is exact arithmetic in either) -
-// without the locate kernel's launch and the 40 bytes of located sample per record it writes and this kernel would read back.
+// curved SKS, polarized> behind the same walk - exact_sample(), write_aux_record() and write_polarized_inputs() of bl_sampling.h, as
+// there, so the same BlPolSample frames, BlCoefInputs and auxiliary records, bit for bit (both tiers: the frame of a polarized sample
+// is exact arithmetic in either) - without the locate kernel's launch and the 40 bytes of located sample per record it writes and
+// this kernel would read back.
 // Reference: simulation_sampling.cpp:201-575, :806-839; simulation_coefficients.cpp:253-455; polarized.cpp:163-265.
 // =================================================================================================
 // kAuxRecords: the run keeps BlAuxSample records (an auxiliary row besides tau, or a rendering); without them the kernel is 40
@@ -1678,189 +1707,50 @@ __global__ void __launch_bounds__(256, 2) bl_shade_exact2_kernel(const BlShadeAr
 // kCoefficients: one frequency, thermal electrons only (configuration 4): the sample's eight polarized coefficients are evaluated here,
 // from the scalars the frame's arithmetic has just left in registers, instead of by bl_polarized_coefficients_kernel from a 64-byte
 // BlCoefInputs written and read back through HBM (per 1024^2 frame: 48 GB written, 100 GB fetched - with the record's tag - and a
-// kernel's worth of launch and tail). The same functions on the same operands: the same bits.
+// kernel's worth of launch and tail). polarized_sample_prelude() and polarized_sample_coefficients() (bl_sampling_fast.h), which are
+// that kernel's arithmetic too: the same bits.
 template <bool kSpinZero, bool kAuxRecords, bool kCoefficients = false>
 __global__ void __launch_bounds__(256, 2) bl_shade_polarized2_kernel(const BlShadeArgs P) {
-  using namespace fused2;
   extern __shared__ double lds[];
-  const uint32_t lds_base = lds_address(lds);
-  // (a mesh with refinement that the tolerant tier's fused kernel would take - BlGridDevice::fused_lds_bytes - has its row chunks and box
-  // descriptors here too, with widths where that kernel keeps reciprocals: locate_exact<., true>)
-  const bool mesh = P.grid.n_blocks > 0;
-  if (mesh) stage_refined_rows<false>(P.grid, reinterpret_cast<char *>(lds), lds_base);
-  else stage_axis_rows<false>(P.grid, reinterpret_cast<AxisRow *>(lds));
-  __syncthreads();
-  const uint32_t n_records = (uint32_t)P.counters_in[BL_CNT_RECORDS];
-  const uint32_t first_record = 0u;
-  if (n_records <= first_record) return;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  const uint32_t last = n_records - 1u;
   const BlSpacetime st = P.st;
-  const GridScalars G = mesh ? grid_scalars_refined(P.grid, lds_base) : grid_scalars(P.grid, lds_base);
-  const double camera_r = P.cuts.camera_r;
-  const float fallback_rho = P.cold->fallback_rho, fallback_pgas = P.cold->fallback_pgas;
   const bool nan_rays = P.plasma.fallback_nan != 0;
-  const char *cells = reinterpret_cast<const char *>(P.grid.cells);
-  const uint32_t row_bytes = (uint32_t)P.grid.stride_row * 32u, plane_bytes = (uint32_t)P.grid.stride_plane * 32u;
-  const double2 *ray_constants = P.ray_constants;
-  const char *ray_offset = reinterpret_cast<const char *>(P.ray_offset);
-  unsigned long long gathers_wave = 0ull;
-  const char *records = reinterpret_cast<const char *>(P.records_hot);
-  const uint32_t lane_index = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t lane_bytes = lane_index << 6;
-  uint32_t base_index = first_record;
-  auto record_base = [&](uint32_t first) { return records + ((size_t)(first < last ? first : last) << 6); };
-  double2 prev0 = make_double2(0.0, 0.0), prev1 = make_double2(0.0, __longlong_as_double((long long)BL_DEAD_RAY)), prev2 = prev0, prev3 = prev0;
-  double2 cur0, cur1;
-  double kt_prev = 0.0, factor_prev = 1.0;
-  long long row_prev = 0;
-  unsigned char flag_prev = 0;
-  LocatedExact loc_prev, loc_cur;
-  loc_prev.f_i = loc_prev.f_j = loc_prev.f_k = loc_prev.ph_unwrapped = 0.0;
-  loc_prev.status = kSampleNone;
-  loc_prev.cell_bytes = 0u;
-  float4 lo[8], hi[8];
-#pragma unroll
-  for (int c = 0; c < 8; c++) lo[c] = hi[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  bool cur_in = first_record + lane_index < n_records;
-  {
-    const double2 *rec = reinterpret_cast<const double2 *>(record_base(first_record) + (size_t)(cur_in ? lane_bytes : 0u));
-    cur0 = rec[0];
-    cur1 = rec[1];
-    cur1.y = cur_in ? cur1.y : __longlong_as_double((long long)BL_DEAD_RAY);
-  }
-  loc_cur = locate_exact<kSpinZero, true>(st, P.grid, G, camera_r, (uint32_t)__double_as_longlong(cur1.y) != BL_DEAD_RAY, cur0.x, cur0.y, cur1.x);
-  bool prev_in = false;
-  while (__any(prev_in || cur_in)) {
-    const uint32_t ray = (uint32_t)__double_as_longlong(prev1.y);
-    const bool live = ray != BL_DEAD_RAY;
-    const uint32_t n = (uint32_t)(((unsigned long long)__double_as_longlong(prev1.y)) >> 32);
-    int status = (int)loc_prev.status;
-    const uint32_t next_first = base_index + stride;
-    const bool next_in = next_first + lane_index < n_records;
-    double2 next0, next1;
-    {
-      const double2 *rec = reinterpret_cast<const double2 *>(record_base(next_first) + (size_t)(next_in ? lane_bytes : 0u));
-      next0 = rec[0];
-      next1 = rec[1];
+  exact_record_walk<kSpinZero, false, true, kCoefficients, true>(P, st, lds, [&](const WalkSample &s, float (&pr)[8]) {
+    // (the stored momentum is renormalised here without asking BlShadeArgs::samples_renormalised: the plan gives this kernel no
+    // render of samples loaded from a geodesic checkpoint - locate_inside_possible needs no_checkpoint)
+    const unsigned long long idx_cur = (unsigned long long)s.index;
+    const size_t row = s.row;
+    const double x1 = s.q0.x, x2 = s.q0.y, x3 = s.q1.x;
+    const double delta_lambda = -s.q3.y;   // ReverseGeodesics: sample_len = -geodesic_len (geodesics.cpp:840)
+    double kcov[4] = {s.kt, s.q2.x, s.q2.y, s.q3.x};
+    int status = s.status;
+    // rays that ended on ray_max_steps / retries with fallback_nan sample NaN primitives at every sample, cuts not applied
+    // (simulation_sampling.cpp:211-216)
+    if (nan_rays && s.ray_flag != 0) {
+      const float fnan = __int_as_float(0x7fc00000);
+      for (int v = 0; v < 8; v++) pr[v] = fnan;
+      status = kSampleOffGrid;
     }
-    const double kt = kt_prev, momentum_factor = factor_prev;
-    const long long row_first = row_prev;
-    const unsigned char ray_flag = flag_prev;
-    float pr[8];
-    gather_finish(P, fallback_rho, fallback_pgas, status, lo, hi, loc_prev.f_i, loc_prev.f_j, loc_prev.f_k, pr);
-    gathers_wave += (unsigned long long)__popcll(__ballot(status == (int)kSampleInterp));
-    double2 cold0, cold1;
-    {
-      const double2 *rec = reinterpret_cast<const double2 *>(record_base(base_index) + (size_t)(cur_in ? lane_bytes : 0u));
-      cold0 = rec[2];
-      cold1 = rec[3];
+    BlKerrSchild ks;
+    SampleShade sh = exact_sample<true, true, kSpinZero>(P, st, x1, x2, x3, s.ph_unwrapped, status, pr, true, kcov, P.aux_need_coefficients,
+                                                         P.pol_samples + row, &ks);
+    // (what these two read of the arguments - output arrays, the list of samples without coefficients - they read where they use it)
+    const BlShadeArgs &A = kernel_arguments_in_place<BlShadeArgs>();
+    if (kAuxRecords) write_aux_record(A, st, ks, idx_cur, row, sh, kcov, x1, x2, x3, delta_lambda);
+    if (!kCoefficients) {
+      write_polarized_inputs(A, idx_cur, row, sh, kcov, pr, x1, x2, x3, delta_lambda);
+    } else {
+      // a sample with coefficients leaves them; one without leaves what bl_polarized_frame_kernel builds its frame from, as ever
+      if (!sh.have_coefficients) write_polarized_inputs(A, idx_cur, row, sh, kcov, pr, x1, x2, x3, delta_lambda);
+      else {
+        BlPolSample *ps = A.pol_samples + row;
+        ps->x[0] = x1; ps->x[1] = x2; ps->x[2] = x3;
+        ps->delta_lambda = delta_lambda;
+      }
+      A.have_flags[idx_cur] = sh.have_coefficients ? 1 : 0;
+      polarized_sample_prelude<false>(A, &sh);
+      polarized_sample_coefficients<false, false>(A, sh, s.momentum_factor, A.frequencies[0], A.pol_coeffs + row * 4);
     }
-    {
-      const uint32_t ray_cur = (uint32_t)__double_as_longlong(cur1.y);
-      const uint32_t ray_slot = ray_cur != BL_DEAD_RAY ? ray_cur : 0u;
-      if (kCoefficients) {
-        const double2 constants = bl_ray_constants(ray_constants, (size_t)ray_slot);
-        kt_prev = constants.x;
-        factor_prev = constants.y;
-      } else {
-        kt_prev = bl_ray_kt(ray_constants, (size_t)ray_slot);
-      }
-      row_prev = *reinterpret_cast<const long long *>(ray_offset + (size_t)(ray_slot << 3));
-      flag_prev = P.ray_flags[ray_slot];
-    }
-    if (live) {
-      // ---- bl_shade_kernel's body for a polarized run (bl_shade.hip), call for call
-      const unsigned long long idx_cur = (unsigned long long)(base_index - stride + lane_index);
-      const size_t row = (size_t)(row_first + (long long)n);
-      const double x1 = prev0.x, x2 = prev0.y, x3 = prev1.x;
-      const double delta_lambda = -prev3.y;   // ReverseGeodesics: sample_len = -geodesic_len (geodesics.cpp:840)
-      double kcov[4] = {kt, prev2.x, prev2.y, prev3.x};
-      BlKerrSchild ks;
-      bl_kerr_schild<kSpinZero>(st, x1, x2, x3, &ks);
-      {   // per-sample renormalisation of the stored momentum (geodesics.cpp:352-371)
-        double gcon[4][4];
-        bl_gcon_ks(ks, gcon);
-        const double factor = bl_renormalization_factor_g(gcon, kcov[0], kcov[1], kcov[2], kcov[3]);
-        kcov[1] *= factor;
-        kcov[2] *= factor;
-        kcov[3] *= factor;
-      }
-      SampleShade sh;
-      sh.have_coefficients = false;
-      sh.nu_fluid_over_nu = 0.0;
-      sh.n_e_cgs = sh.nu_c_cgs = sh.theta_e = sh.sin_theta_b = sh.kb_tt_e_cgs = 0.0;
-      sh.cos_theta_b = sh.sin2_theta_b = sh.cos2_theta_b = 0.0;
-      sh.cos_sign = 1.0;
-      sh.n_n0_fluid = 0.0;
-      sh.fu[0] = sh.fu[1] = sh.fu[2] = sh.fu[3] = 0.0;
-      sh.have_cell = false;
-      // rays that ended on ray_max_steps / retries with fallback_nan sample NaN primitives at every sample, cuts not applied
-      // (simulation_sampling.cpp:211-216)
-      if (nan_rays && ray_flag != 0) {
-        const float fnan = __int_as_float(0x7fc00000);
-        for (int v = 0; v < 8; v++) pr[v] = fnan;
-        status = kSampleOffGrid;
-      }
-      if (status != kSampleCut)
-        sample_finish_simulation<true, true>(P, st, ks, x3 / ks.r, loc_prev.ph_unwrapped, pr, 0.0f, kcov, P.aux_need_coefficients, &sh, P.pol_samples + row);
-      // (what these two read of the arguments - output arrays, the list of samples without coefficients - they read where they use it)
-      const BlShadeArgs &A = kernel_arguments_in_place<BlShadeArgs>();
-      if (kAuxRecords) write_aux_record(A, st, ks, idx_cur, row, sh, kcov, x1, x2, x3, delta_lambda);
-      if (!kCoefficients) {
-        write_polarized_inputs(A, idx_cur, row, sh, kcov, pr, x1, x2, x3, delta_lambda);
-      } else {
-        // a sample with coefficients leaves them; one without leaves what bl_polarized_frame_kernel builds its frame from, as ever
-        if (!sh.have_coefficients) write_polarized_inputs(A, idx_cur, row, sh, kcov, pr, x1, x2, x3, delta_lambda);
-        else {
-          BlPolSample *ps = A.pol_samples + row;
-          ps->x[0] = x1; ps->x[1] = x2; ps->x[2] = x3;
-          ps->delta_lambda = delta_lambda;
-        }
-        A.have_flags[idx_cur] = sh.have_coefficients ? 1 : 0;
-        // bl_polarized_coefficients_kernel<false, true>'s body (bl_coefficients_freq.hip), call for call
-        sh.sin2_theta_b = 1.0 - sh.cos2_theta_b;
-        sh.sin_theta_b = bl_sqrt_g(sh.sin2_theta_b);
-        sh.cos_theta_b = bl_sqrt_g(sh.cos2_theta_b) * sh.cos_sign;
-        sh.theta_e_096 = sh.kk_0 = sh.kk_1 = sh.kk_2 = 0.0;
-        if (sh.have_coefficients && A.plasma.plasma_thermal_frac != 0.0) {
-          sh.theta_e_096 = bl_pow(sh.theta_e, 0.96);
-          if (sh.theta_e >= 0.01) bl_cyl_bessel_k012(1.0 / sh.theta_e, &sh.kk_0, &sh.kk_1, &sh.kk_2);
-        }
-        const double freq = A.frequencies[0];
-        double j_val = 0.0, alpha_val = 0.0;
-        double2 pc[3] = {make_double2(0.0, 0.0), make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
-        if (sh.have_coefficients) simulation_coefficients<false>(A, sh, freq, momentum_factor, &j_val, &alpha_val);
-        polarized_coefficients<false>(A, sh, freq, momentum_factor, j_val, alpha_val, pc);
-        double2 *out = A.pol_coeffs + row * 4;
-        out[0] = make_double2(j_val, alpha_val);
-        out[1] = pc[0];
-        out[2] = pc[1];
-        out[3] = pc[2];
-      }
-    }
-    // the corner cells of `cur`: requested behind the frame's arithmetic, whose tetrad needs the sixty-four registers they land in
-    // (with the requests in front of it the kernel keeps 3 ... 24 registers in scratch memory); the search for `next` and the
-    // other wave of the SIMD cover their way
-    fused2::gather_issue(cells, loc_cur.cell_bytes, loc_cur.status == (uint32_t)kSampleInterp, row_bytes, plane_bytes, lo, hi);
-    const bool live_next = next_in && (uint32_t)__double_as_longlong(next1.y) != BL_DEAD_RAY;
-    LocatedExact loc_next = loc_cur;
-    if (__any(live_next)) loc_next = locate_exact<kSpinZero, true>(st, P.grid, G, camera_r, live_next, next0.x, next0.y, next1.x);
-    else loc_next.status = kSampleNone, loc_next.cell_bytes = 0u;
-    prev0 = cur0;
-    prev1 = cur1;
-    prev2 = cold0;
-    prev3 = cold1;
-    loc_prev = loc_cur;
-    prev_in = cur_in;
-    cur0 = next0;
-    cur1 = next1;
-    cur1.y = next_in ? next1.y : __longlong_as_double((long long)BL_DEAD_RAY);
-    loc_cur = loc_next;
-    cur_in = next_in;
-    base_index = next_first;
-  }
-  if ((threadIdx.x & 63) == 0 && gathers_wave != 0ull) atomicAdd(&P.counters[BL_CNT_GATHERS], gathers_wave);
+  });
 }
 
 using BlShadeKernel = void (*)(BlShadeArgs);

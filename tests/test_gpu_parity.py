@@ -537,6 +537,48 @@ def test_polarized_runs_over_a_refined_mesh(seed, built_library):
         assert np.nanmax(np.abs(tolerant["image"] - inside["image"]) / np.where(scale > 0, scale, 1.0)) < 1.0e-9, over
 
 
+@pytest.mark.parametrize("over,inside_kernel,outside_kernels", [
+    # one frequency, zero spin, thermal electrons, no auxiliary row: the eight coefficients evaluated inside the kernel
+    (dict(), "polarized2<1,0,1>", ("shade<0,1,1,1,1,0>", "polarized_coefficients=<0,1>")),
+    # ... and with a row that keeps BlAuxSample records, which leaves the coefficients to bl_polarized_coefficients_kernel either way
+    (dict(image_length="true"), "polarized2<1,1,0>", ("shade<0,1,1,1,1,0>", "polarized_coefficients=<0,1>")),
+], ids=["coefficients_inside", "sample_records"])
+def test_polarized_kernel_with_the_locate_step_inside_and_its_siblings(over, inside_kernel, outside_kernels, capfd, monkeypatch, built_library):
+    """bl_shade_polarized2_kernel over one block against the kernels it stands for - bl_locate_plain_kernel, bl_shade_kernel<polarized>
+    and bl_polarized_coefficients_kernel behind NO_FUSED_LOCATE - and against the CPU oracle: they share one sample body
+    (exact_sample, polarized_sample_coefficients), and every row of both renders has the oracle's bits."""
+    import blacklight_amd as bl
+    from blacklight_amd import _capi
+    import oracle_api
+    monkeypatch.setenv("BLACKLIGHT_AMD_DEBUG_COUNTERS", "1")   # (read when the context is created: one `kernels:` line per render)
+    fx, params, mock_args = gu.load_case("sim_polarized")
+    p = bl.Params.from_dict(dict(params, camera_resolution=14, **over))
+    grid = gu.golden_grid(mock_args)
+
+    def render(ctx):
+        capfd.readouterr()
+        out = ctx.render()
+        line, = [text for text in capfd.readouterr().err.splitlines() if text.startswith("kernels: ")]
+        return out, line
+
+    with bl.Context(p) as ctx:
+        ctx.set_grid(grid)
+        ctx.set_arithmetic("exact")
+        inside, inside_line = render(ctx)
+        ctx.debug_set_switches("NO_FUSED_LOCATE")
+        outside, outside_line = render(ctx)
+    assert f"shade={inside_kernel} " in inside_line
+    assert ("polarized_coefficients=" in inside_line) == (inside_kernel != "polarized2<1,0,1>")
+    assert f"shade={outside_kernels[0]} " in outside_line and f" {outside_kernels[1]} " in outside_line
+    assert inside["stats"].fused_variant == 4 and inside["stats"].launches_locate == 0
+    assert outside["stats"].fused_variant == 0 and outside["stats"].launches_locate == 1
+    want = oracle_api.render(p.ptr, grid.desc(), _capi.RenderDesc, _capi.CameraFrame, n_rays=14 * 14, max_steps=int(p.get("ray_max_steps")))
+    assert np.array_equal(inside["sample_num"], want["sample_num"]) and inside["stats"].n_gathers == outside["stats"].n_gathers
+    assert inside["image"].shape == want["image"].shape
+    assert gu.same_bits(inside["image"], outside["image"]).all()
+    assert gu.same_bits(inside["image"], want["image"]).all()
+
+
 @pytest.mark.parametrize("seed", range(8))
 def test_block_interpolation_against_oracle(seed, built_library):
     """simulation_block_interp = true (FindNearbyInds / InterpolateAdvanced) on equal blocks and on the two-level mesh,
