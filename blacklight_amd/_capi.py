@@ -112,7 +112,8 @@ class RenderDesc(C.Structure):
 # BL_SWITCH_* of include/blacklight_amd.h: measurement switches (bl_stats.switches, bl_debug_set_switches)
 SWITCHES = {"TENSOR_TRANSPORT": 1 << 0, "SPLIT_RECORDS": 1 << 1, "RECORD_EVERY_STEP": 1 << 2,
             "GENERAL_LOCATE": 1 << 4, "LANE_TRANSFER": 1 << 5, "NO_FUSED_LOCATE": 1 << 6, "SAMPLE_RECORDS": 1 << 8, "QUAD_EVERY_RAY": 1 << 11,
-            "FLAT_ORDER": 1 << 12, "GLOBAL_ANGLES": 1 << 13, "GENERAL_CUTS": 1 << 14, "NO_MIRROR_PAIRS": 1 << 15}
+            "FLAT_ORDER": 1 << 12, "GLOBAL_ANGLES": 1 << 13, "GENERAL_CUTS": 1 << 14, "NO_MIRROR_PAIRS": 1 << 15,
+            "EXACT_DISTANCE": 1 << 16, "WIDE_DISTANCE_BAND": 1 << 17}
 
 BL_MAX_LEVELS = 16
 

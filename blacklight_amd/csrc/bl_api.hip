@@ -676,7 +676,8 @@ int bl_init(const bl_params *p, int device, bl_ctx **out) {
         {"BLACKLIGHT_AMD_NO_FUSED_LOCATE", BL_SWITCH_NO_FUSED_LOCATE}, {"BLACKLIGHT_AMD_SAMPLE_RECORDS", BL_SWITCH_SAMPLE_RECORDS},
         {"BLACKLIGHT_AMD_QUAD_EVERY_RAY", BL_SWITCH_QUAD_EVERY_RAY}, {"BLACKLIGHT_AMD_FLAT_ORDER", BL_SWITCH_FLAT_ORDER},
         {"BLACKLIGHT_AMD_GLOBAL_ANGLES", BL_SWITCH_GLOBAL_ANGLES}, {"BLACKLIGHT_AMD_GENERAL_CUTS", BL_SWITCH_GENERAL_CUTS},
-        {"BLACKLIGHT_AMD_NO_MIRROR_PAIRS", BL_SWITCH_NO_MIRROR_PAIRS}};
+        {"BLACKLIGHT_AMD_NO_MIRROR_PAIRS", BL_SWITCH_NO_MIRROR_PAIRS}, {"BLACKLIGHT_AMD_EXACT_DISTANCE", BL_SWITCH_EXACT_DISTANCE},
+        {"BLACKLIGHT_AMD_WIDE_DISTANCE_BAND", BL_SWITCH_WIDE_DISTANCE_BAND}};
     for (const auto &sw : kSwitches)
       if (std::getenv(sw.name) != nullptr) ctx->switches |= sw.bit;
     ctx->debug_counters = std::getenv("BLACKLIGHT_AMD_DEBUG_COUNTERS") != nullptr;

@@ -383,6 +383,9 @@ struct bl_ctx {
   DeviceBuffer<long long> d_mirror_out;
   std::vector<unsigned char> mirror_key;
   bool mirror_ok = false;
+  // Closed-form proper distance (bl_distance_closed.h): the geodesic keys (BuildReuseKeys) of the cameras whose frame had a step the
+  // closed form did not decide and was rendered again. Fresh renders of such a camera go straight to the reference's operations.
+  std::vector<std::vector<unsigned char>> distance_exact_keys;
   DeviceBuffer<BlShadeCold> d_shade_cold;
   DeviceBuffer<BlPolVariant> d_pol_variant_table;   // polarized variants in one pass: every variant's folded constants (BuildShadeArgs)
   std::vector<unsigned char> pol_variant_host;   // the bytes d_pol_variant_table holds

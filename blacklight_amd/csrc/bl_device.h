@@ -87,7 +87,8 @@ enum BlCounter {
 // per scratch set: the counters above, four transfer statistics, eight debug counters (kernels built with -DBL_GEO_STATS)
 #define BL_CNT_DEBUG (BL_CNT_COUNT + 4)
 #define BL_CNT_QUAD_NEXT (BL_CNT_COUNT + 12)   // work queue head of the launch that finishes the parked rays: parked rays handed out
-#define BL_CNT_PARKED_YOUNG (BL_CNT_COUNT + 14)   // parked rays with fewer than BlTraceArgs::park_age samples so far (BL_CNT_PARKED: the others)
+#define BL_CNT_UNDECIDED (BL_CNT_COUNT + 13)   // accepted steps whose sample count the closed-form distance did not decide (BlTraceArgs::distance_mode)
+#define BL_CNT_PARKED_YOUNG (BL_CNT_COUNT + 14)  // parked rays with fewer than BlTraceArgs::park_age samples so far (BL_CNT_PARKED: the others)
 #define BL_CNT_TOTAL (BL_CNT_COUNT + 15)
 
 // dynamic LDS the refined instantiation of bl_shade_fused2_kernel may take (one 512-lane workgroup to a compute unit of 160 KiB)
@@ -362,6 +363,12 @@ struct BlTraceArgs {
   // bl_ray_init_kernel starts ray v from cameras[c] at pixel m of that camera. Null: every ray is `cam`'s (pixels_per_camera unread).
   const BlCameraDevice *cameras;
   long long pixels_per_camera;
+  // The proper distance of bl_geodesic_kernel's Dormand-Prince steps (bl_distance_closed.h; the plan's choice, KernelPlan::Geodesic::
+  // distance). 0: the reference's operations in every stage, state component 7 its s. 1: the closed form; component 7 holds an upper
+  // bound of |s|, a step's sample count is taken from the closed form where the bound on its distance from the reference's leaves
+  // no integer in doubt, and every other accepted step adds one to BL_CNT_UNDECIDED - the host then discards the frame. 2: as 1 with
+  // a band of 0.25 in the count (BL_SWITCH_WIDE_DISTANCE_BAND: exercises the host's second render).
+  int distance_mode;
 };
 #define BL_RAY_START_FIELDS 17
 // A parked ray (BlTraceArgs::parked): everything bl_geodesic_kernel holds of a ray between two steps, BL_PARK_DOUBLES doubles

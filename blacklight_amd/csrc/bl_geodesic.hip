@@ -11,6 +11,7 @@
 // the recurrence the reference's while never materialising its per-sample arrays.
 #include "bl_kernel_util.h"
 #include "bl_geodesic_common.h"
+#include "bl_distance_closed.h"
 
 namespace {
 
@@ -23,11 +24,11 @@ struct RayState {
 };
 
 template <bool kWithDistance, bool kSpinZero>
-__device__ __forceinline__ void rhs(const BlSpacetime &st, const double y[8], double kt, double k[8], double *r) {
+__device__ __forceinline__ void rhs(const BlSpacetime &st, const double y[8], double kt, double k[8], double *r, int distance = BL_DISTANCE_EXACT) {
   double pos[3] = {y[1], y[2], y[3]};
   double kcov[4] = {kt, y[4], y[5], y[6]};
   double dpos[4], dk[3], ds = 0.0;
-  bl_geodesic_rhs<kWithDistance, kSpinZero>(st, pos, kcov, dpos, dk, &ds, r);
+  bl_geodesic_rhs<kWithDistance, kSpinZero>(st, pos, kcov, dpos, dk, &ds, r, distance);
   k[0] = dpos[0];
   k[1] = dpos[1];
   k[2] = dpos[2];
@@ -442,10 +443,26 @@ __global__ void __launch_bounds__(64, BL_GEO_ONE_WAVE(kIntegrator, kTime, kSpinZ
           // order solutions, whose terms are added in stage order. Those sums are advanced as soon as
           // each stage is known, so 2 x 6 stage values need not stay live through the later stages.
           double t5 = s.y[0], t4 = s.y[0], s5 = s.y[7];
+          // Closed distance (BlTraceArgs::distance_mode, bl_distance_closed.h; wave-uniform): s5 is the step's increment, summed from
+          // zero over the stages with a weight, s_abs the sum of the terms' absolute values; stage 1 has no weight and evaluates no
+          // derivative, stage 6 has none either but its derivative is the next step's first.
+#ifdef BL_DISTANCE_FORCED   // (tools/isa_profile.py --flags "-DBL_DISTANCE_FORCED=0|1": one mode's executed path as a static count)
+          const bool closed = BL_DISTANCE_FORCED != 0;
+#else
+          const bool closed = P.distance_mode != 0;
+#endif
+          double s_abs = 0.0, r_low = r_cur;
+          if (closed) s5 = 0.0;
 #define BL_FOLD(Q, K)                     \
           t5 += kB5[Q] * h * K[0];        \
           t4 += kB4[Q] * h * K[0];        \
-          s5 += kB5[Q] * h * K[7];
+          if (!closed) {                  \
+            s5 += kB5[Q] * h * K[7];      \
+          } else if (kB5[Q] != 0.0) {     \
+            const double term = kB5[Q] * h * K[7]; \
+            s5 += term;                   \
+            s_abs += blm_abs(term);       \
+          }
           BL_FOLD(0, k0)
           // stages 1..6 (:162-170): y_temp = y + sum_{q<s} a[s][q] * h * k[q], terms added in q order
 #define BL_STAGE(S, KOUT, ...)                                                  \
@@ -457,7 +474,8 @@ __global__ void __launch_bounds__(64, BL_GEO_ONE_WAVE(kIntegrator, kTime, kSpinZ
               yt[p] = acc;                                                       \
             }                                                                    \
             yt[0] = 0.0; yt[7] = 0.0;                                            \
-            rhs<true, kSpinZero>(st, yt, s.kt, KOUT, &r_stage);                             \
+            rhs<true, kSpinZero>(st, yt, s.kt, KOUT, &r_stage, !closed ? BL_DISTANCE_EXACT : (S == 1 ? BL_DISTANCE_NONE : BL_DISTANCE_CLOSED)); \
+            if (closed) r_low = std_min(r_low, r_stage);                         \
             BL_FOLD(S, KOUT)                                                     \
           }
           BL_STAGE(1, k1, k0, k0, k0, k0, k0, k0)
@@ -480,7 +498,7 @@ __global__ void __launch_bounds__(64, BL_GEO_ONE_WAVE(kIntegrator, kTime, kSpinZ
               a5 = t5;
               a4 = t4;
             } else if (p == 7) {
-              a5 = s5;
+              a5 = closed ? (s.y[7] + s_abs) * kDistanceInflate : s5;
             } else {
 #pragma unroll
               for (int q = 0; q < 7; q++) {
@@ -536,8 +554,20 @@ __global__ void __launch_bounds__(64, BL_GEO_ONE_WAVE(kIntegrator, kTime, kSpinZ
             }
             double r_mid = bl_radial_coordinate<kSpinZero>(st, y4m[1], y4m[2], y4m[3]);
             double delta_s_step = P.ray_step * r_mid;
-            double delta_s_full = y5[7] - s.y[7];
-            num_steps_ideal = (int)ceil(delta_s_full / delta_s_step);
+            if (!closed) {
+              double delta_s_full = y5[7] - s.y[7];
+              num_steps_ideal = (int)ceil(delta_s_full / delta_s_step);
+            } else {
+              // ceil(Q) is the reference's count where no integer lies within the band of Q (bl_distance_closed.h); a step in doubt goes
+              // on with ceil(Q) and is counted: the host renders the frame again with the reference's operations
+              const BlRecip rc_step = bl_recip(delta_s_step);
+              const double q_closed = bl_div_r(s5, rc_step);
+              const double derived = kDistanceBandFactor * bl_div_r(bl_distance_bound_numerator(s_abs, y5[7]), rc_step);
+              const double band = P.distance_mode == 2 ? std_max(derived, kDistanceWideBand) : derived;
+              const double n_closed = ceil(q_closed);
+              num_steps_ideal = (int)n_closed;
+              if (!bl_distance_decided(q_closed, n_closed, band, st.ray_flat ? P.r_horizon : r_low, P.r_horizon)) atomicAdd(&P.counters[BL_CNT_UNDECIDED], 1ull);
+            }
             int num_steps_max = P.ray_max_steps - sample_num;
             num_steps = num_steps_ideal;
             if (num_steps > num_steps_max) {

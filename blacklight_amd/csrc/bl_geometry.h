@@ -327,15 +327,31 @@ BL_HD double bl_distance_norm(const double fl[3], const double l[3], const doubl
   return acc;
 }
 
+// The same derivative in closed form. With g^{ij} = delta_ij - f l_i l_j, g^{0i} = f l_i, g^{00} = -(1 + f) the bracket of
+// bl_distance_row is gamma^{aj} = delta_aj - l_a l_j f / (1 + f), the inverse of the spatial metric (its k_t column is identically
+// zero), and bl_distance_norm contracts gamma_ab gamma^{ai} gamma^{bj} k_i k_j = gamma^{ij} k_i k_j:
+//   d s / d lambda = -sqrt(k.k - (l.k)^2 f / (1 + f))
+// for any spin, without the null condition. NOT the reference's bits: bl_distance_closed.h states how far the two may lie apart
+// and where the stepper may use this one. No cancellation beyond a factor 1 + f: f / (1 + f) < 1 and (l.k)^2 <= (l.l) (k.k).
+BL_HD double bl_distance_closed(double f, const double l[3], const double kcov[4]) {
+  const double kk = kcov[1] * kcov[1] + kcov[2] * kcov[2] + kcov[3] * kcov[3];
+  const double lk = l[0] * kcov[1] + l[1] * kcov[2] + l[2] * kcov[3];
+  return -bl_sqrt_g(kk - lk * lk * bl_div_g(f, 1.0 + f));
+}
+
+// bl_geodesic_rhs's distance argument (kWithDistance only): the reference's operations, the closed form, or no *ds at all
+enum { BL_DISTANCE_EXACT = 0, BL_DISTANCE_CLOSED = 1, BL_DISTANCE_NONE = 2 };
+
 // Right-hand side of the geodesic equations (geodesics.cpp:867-893 with distance, :909-925
 // without). State: pos = (x, y, z); kcov = (k_t, k_x, k_y, k_z).
 //   dpos[0..3] = d(t, x, y, z)/d lambda = g^{mu nu} k_nu
 //   dk[0..2]   = d(k_x, k_y, k_z)/d lambda = -1/2 d_i g^{mu nu} k_mu k_nu      (d k_t = 0)
-//   *ds        = d s / d lambda (proper distance), only if kWithDistance
+//   *ds        = d s / d lambda (proper distance), only if kWithDistance; `distance` (BL_DISTANCE_*, uniform across a wave where a
+//                kernel passes anything but the default) chooses the reference's operations or bl_distance_closed
 // Returns r at the evaluation point through *r_out.
 template <bool kWithDistance, bool kSpinZero = false>
 BL_HD void bl_geodesic_rhs(const BlSpacetime &st, const double pos[3], const double kcov[4],
-                           double dpos[4], double dk[3], double *ds, double *r_out) {
+                           double dpos[4], double dk[3], double *ds, double *r_out, int distance = BL_DISTANCE_EXACT) {
   if (st.ray_flat) {
     // Minkowski: g = diag(-1,1,1,1), all derivatives zero (geodesic_geometry.cpp:41-60, :177-184)
     dpos[0] = -kcov[0];
@@ -439,11 +455,15 @@ BL_HD void bl_geodesic_rhs(const BlSpacetime &st, const double pos[3], const dou
   }
 
   if (kWithDistance) {
-    double temp_a[3];
-    const BlRecip rc_g00 = bl_recip(g00);   // twelve quotients over g^{00}
-    for (int a = 0; a < 3; a++) temp_a[a] = bl_distance_row(fl[a], gij[a], fl, g00, rc_g00, kcov);
-    const double acc = bl_distance_norm(fl, l, temp_a);
-    *ds = -bl_sqrt_g(acc);
+    if (distance == BL_DISTANCE_EXACT) {
+      double temp_a[3];
+      const BlRecip rc_g00 = bl_recip(g00);   // twelve quotients over g^{00}
+      for (int a = 0; a < 3; a++) temp_a[a] = bl_distance_row(fl[a], gij[a], fl, g00, rc_g00, kcov);
+      const double acc = bl_distance_norm(fl, l, temp_a);
+      *ds = -bl_sqrt_g(acc);
+    } else if (distance == BL_DISTANCE_CLOSED) {
+      *ds = bl_distance_closed(f, l, kcov);
+    }
   }
 }
 

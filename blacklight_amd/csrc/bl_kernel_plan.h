@@ -12,6 +12,9 @@ struct KernelPlan {
     enum Source { kStepper, kCheckpoint, kResident } source = kStepper;
     int integrator = 0;
     bool with_time = false, spin_zero = false, shell = false;
+    // The proper distance of the stepper's stages (no template argument: BlTraceArgs::distance_mode, wave-uniform at run time). kNone: no
+    // stepper runs, or a fixed-step one, which has no distance; kExact: the reference's operations; kClosed: bl_distance_closed.h
+    enum Distance { kNone, kExact, kClosed } distance = kNone;
   } geodesic;
   // bl_geodesic_quad_kernel<spin_zero> behind the stepper (BL_TAIL_QUAD) or beside it, after bl_split_long_kernel (BL_TAIL_SPLIT)
   struct Quad {

@@ -8,6 +8,7 @@
 // holds `record_capacity` of each, and the geodesic kernel hands out rays only while the records of the rays in flight
 // are sure to fit (BlTraceArgs::record_gate). What it did not get to is the next chunk. The benchmark frame - 704 samples
 // per ray where ray_max_steps allows 2 000 - is one chunk this way; sized for the worst case it was two.
+#include <chrono>
 #include <thread>
 
 #include "bl_checkpoint.h"
@@ -49,6 +50,7 @@ void EnsureRenderResources(bl_ctx *ctx) {
 }
 
 struct SplitIncomplete {};   // BL_TAIL_SPLIT: the chunk ended before its last ray (RunChunks)
+struct DistanceUndecided {}; // closed-form proper distance: a step's sample count was left in doubt (CollectChunk; bl_distance_closed.h)
 struct ReuseImpossible {};   // scratch for a render over the resident records could not be allocated beside them (EnsureScratch)
 
 // Which of a scratch set's optional arrays (bl_ctx::ChunkSlot) a render uses: decided in one place (UsedArrays), read by the plan, the
@@ -87,6 +89,10 @@ struct RenderJob {
   bool split_long = false;    // BL_TAIL_SPLIT: rays predicted long on compute units of their own (bl_split_long_kernel)
   bool allow_split = true;    // false: the call is being rendered again after its split chunk closed the reservation gate early
   bool allow_reuse = true;    // false: ... after memory for a render over the resident records could not be had
+  bool allow_closed = true;   // false: ... after a step the closed-form distance did not decide, or this camera is remembered for one
+  bool distance_retried = false;              // ... the former: this is the second render of the call
+  unsigned long long undecided_before = 0;    // ... and the steps in doubt the discarded one had counted when it was given up
+  float ms_discarded = 0.0f;                  // ... and the time it took (bl_stats.ms_wall covers both)
   bool keepable = false;      // root level, geodesics integrated here: what this render leaves may serve the next (bl_set_geodesic_reuse)
   bool reuse = false;         // the resident records of an earlier render of this camera are shaded again: no geodesic stage
   bool reuse_located = false; // ... and its located samples: no locate kernel
@@ -177,6 +183,7 @@ struct RenderJob {
   int n_chunks = 0;
   float ms_geo = 0.0f, ms_locate = 0.0f, ms_shade = 0.0f, ms_transfer = 0.0f;
   unsigned long long total_samples = 0, total_flagged = 0, total_records = 0, total_emitted = 0, total_gathers = 0, total_redo = 0, total_undefined = 0, total_parked = 0, max_num = 0;
+  unsigned long long total_undecided = 0;
   unsigned long long debug_counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // (BLACKLIGHT_AMD_DEBUG_COUNTERS: the tables and launch of the locate kernel - the first chunk's and the last one's, which differ
   // when chunks overlap - of the coefficient kernel and of the exact second pass)
@@ -1069,6 +1076,11 @@ KernelPlan::Geodesic PlanGeodesicKernel(const RenderJob &job) {
   // general formulas, bit for bit the same; the empty shell: job.skip_shell asks for Dormand-Prince and no sample times)
   g.spin_zero = g.integrator == BL_INTEGRATOR_DP && ctx->st.bh_a == 0.0;
   g.shell = job.skip_shell;
+  // The stages' proper distance (bl_distance_closed.h). The closed form where nothing needs the reference's s itself: the quad kernel
+  // continues parked rays from it (parked or split rays), a checkpoint written or loaded goes with the exact stepper throughout.
+  const bool stepper = g.source == KernelPlan::Geodesic::kStepper && g.integrator == BL_INTEGRATOR_DP;
+  const bool closed = stepper && !job.park && !job.split_long && job.no_checkpoint && job.allow_closed && !(ctx->switches & BL_SWITCH_EXACT_DISTANCE);
+  g.distance = !stepper ? KernelPlan::Geodesic::kNone : (closed ? KernelPlan::Geodesic::kClosed : KernelPlan::Geodesic::kExact);
   return g;
 }
 
@@ -2210,6 +2222,7 @@ void BindChunk(RenderJob &job, int k, long long begin, int rays) {
   ta.park_age = job.max_steps / 8;
   ta.quad_first_round = ctx->num_cus * 4;
   ta.park_always = (job.park && (ctx->switches & BL_SWITCH_QUAD_EVERY_RAY)) ? 1 : 0;
+  ta.distance_mode = job.kernels.geodesic.distance != KernelPlan::Geodesic::kClosed ? 0 : ((ctx->switches & BL_SWITCH_WIDE_DISTANCE_BAND) ? 2 : 1);
   ta.xcd_state = use.xcd ? sl.d_xcd_state.ptr : nullptr;
   ta.xcd_lists = use.xcd ? sl.d_xcd_lists.ptr : nullptr;
   ta.xcd_list_capacity = use.xcd ? static_cast<long long>(job.record_capacity / 64 + 1) : 0;
@@ -2519,6 +2532,9 @@ void CollectChunk(RenderJob &job, int k) {
   fl.busy = false;
   if (fl.done < 0) fl.done = static_cast<long long>(std::min<unsigned long long>(hc[BL_CNT_NEXT_RAY], static_cast<unsigned long long>(fl.rays)));
   if (hc[BL_CNT_OVERFLOW] != 0) throw Failure{BL_E_DEVICE, "Sample record buffer overflow."};
+  // (closed-form distance: a step in doubt may have emitted another number of samples than the reference's - the frame is discarded)
+  job.total_undecided += job.kernels.geodesic.distance == KernelPlan::Geodesic::kClosed ? hc[BL_CNT_UNDECIDED] : 0ull;
+  if (job.total_undecided != 0) throw DistanceUndecided{};
   if (hc[BL_CNT_INTERP_FAILED] != 0) throw Failure{BL_E_INPUT, "Grid interpolation failed."};   // simulation_sampling.cpp:1319
   if (hc[BL_CNT_UNDEFINED] != 0 && !(ctx->undefined_policy & BL_UNDEFINED_EDGE)) {
     if (p.simulation_coord == BL_COORD_FMKS)
@@ -2743,7 +2759,7 @@ void FinishStats(RenderJob &job) {
   st.ms_total = job.ms_geo + job.ms_locate + job.ms_shade + job.ms_transfer;
   float ms_wall = 0.0f;
   Check(hipEventElapsedTime(&ms_wall, ctx->events[2 * kEventsPerChunk], ctx->events[2 * kEventsPerChunk + 1]), "event time");
-  st.ms_wall = ms_wall;
+  st.ms_wall = ms_wall + job.ms_discarded;   // (a render given up for an undecided step: both)
   st.arithmetic = (job.fast || job.fast_formula || job.tolerant_polarized) ? BL_ARITH_TOLERANT : BL_ARITH_EXACT;
   st.n_deferred = static_cast<int64_t>(job.total_redo);
   st.n_undefined = static_cast<int64_t>(job.total_undefined);
@@ -2758,6 +2774,10 @@ void FinishStats(RenderJob &job) {
   st.n_mixes = ResolveVariants(ctx).extent.e;   // (the whole list's, whichever of its mixes this render covers)
   st.tail_policy = job.reuse ? ctx->resident.tail_policy : (job.park ? BL_TAIL_QUAD : (job.split_long ? BL_TAIL_SPLIT : BL_TAIL_WIDE));
   ctx->stats = st;
+  if (ctx->debug_counters) {
+    static const char *const distances[] = {"none", "exact", "closed"};
+    std::fprintf(stderr, "stepper: distance=%s undecided=%llu retried=%d\n", distances[plan.geodesic.distance], job.undecided_before, job.distance_retried ? 1 : 0);
+  }
   if (ctx->debug_counters) {   // kernels built with -DBL_GEO_STATS fill these
     std::fprintf(stderr, "debug counters:");
     for (int k = 0; k < 8; k++) std::fprintf(stderr, " %llu", job.debug_counters[k]);
@@ -2853,7 +2873,10 @@ int RenderLocked(bl_ctx *ctx, const bl_render_desc *d, MixRange mixes) {
   try {
     // (planned again at most twice: without the split stepper after a chunk that closed its gate early, without the resident
     // records after scratch beside them could not be had)
-    bool allow_split = true, allow_reuse = true;
+    // (... and once more with the reference's proper distance after a step the closed form did not decide - a failure of its own kind)
+    bool allow_split = true, allow_reuse = true, allow_closed = true;
+    unsigned long long undecided_before = 0;
+    float ms_discarded = 0.0f;
     for (int attempt = 0;; attempt++) {
       RenderJob job;
       job.ctx = ctx;
@@ -2861,12 +2884,18 @@ int RenderLocked(bl_ctx *ctx, const bl_render_desc *d, MixRange mixes) {
       job.mixes = mixes;
       job.allow_split = allow_split;
       job.allow_reuse = allow_reuse;
+      job.distance_retried = !allow_closed;
+      job.undecided_before = undecided_before;
+      job.ms_discarded = ms_discarded;
+      const auto attempt_begin = std::chrono::steady_clock::now();
       try {
         PlanJob(job);
         Check(hipSetDevice(ctx->device), "hipSetDevice");
         EnsureStreams(ctx);
         job.mirror = MirrorPairsApply(job);
         DecideReuse(job);
+        if (!job.keepable) BuildReuseKeys(job);   // (the camera's key for the memory below, whether or not its records may be kept)
+        job.allow_closed = allow_closed && std::find(ctx->distance_exact_keys.begin(), ctx->distance_exact_keys.end(), job.geo_key) == ctx->distance_exact_keys.end();
         PlanScratch(job);
         if (job.split_long && !EnsureSplitStreams(ctx, job.split_cus)) {
           if (ctx->tail_policy == BL_TAIL_SPLIT) throw Failure{BL_E_DEVICE, "BL_TAIL_SPLIT: the runtime gave no stream with a CU mask (hipExtStreamCreateWithCUMask)."};
@@ -2894,6 +2923,17 @@ int RenderLocked(bl_ctx *ctx, const bl_render_desc *d, MixRange mixes) {
         if (job.keepable) DropResident(ctx);
         if (!allow_split || attempt >= 2) throw Failure{BL_E_DEVICE, "A chunk of rays ended early twice."};
         allow_split = false;
+      } catch (const DistanceUndecided &) {
+        // Nothing of this attempt is kept: its job's totals go with it, a closed-mode render writes no checkpoint, what its chunks
+        // sent to the caller's buffers is written again, and resident records it may have left half replaced are dropped.
+        drain();
+        if (job.keepable) DropResident(ctx);
+        if (!allow_closed) throw Failure{BL_E_DEVICE, "The exact proper distance reported an undecided step."};   // (it counts none)
+        allow_closed = false;
+        undecided_before = job.total_undecided;
+        ms_discarded += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - attempt_begin).count();
+        if (ctx->distance_exact_keys.size() >= 64) ctx->distance_exact_keys.erase(ctx->distance_exact_keys.begin());
+        ctx->distance_exact_keys.push_back(job.geo_key);
       } catch (const ReuseImpossible &) {
         drain();
         (void)hipGetLastError();

@@ -463,7 +463,12 @@ typedef struct bl_stats {
                                                                cut_sigma_max is the only active threshold (its short form)         */
 #define BL_SWITCH_NO_MIRROR_PAIRS (1u << 15)                /* every ray of the frame traced where one ray per mirror pair applies
                                                                (bl_stats.mirror_pairs)                                              */
-/* (Twelve switches. Rounds 3 - 5 had eight more for experiments the measurements buried - a second pre-fused2 kernel, pre-gathered
+#define BL_SWITCH_EXACT_DISTANCE (1u << 16)                 /* Dormand-Prince stepper: the reference's proper-distance operations in
+                                                               every stage where the closed form applies (`stepper:` debug line)    */
+#define BL_SWITCH_WIDE_DISTANCE_BAND (1u << 17)             /* ... the closed form with a band of 0.25 in the sample count: nearly
+                                                               every ray has an undecided step, so the frame is rendered a second
+                                                               time with the reference's operations (exercises that path)           */
+/* (Fourteen switches. Rounds 3 - 5 had eight more for experiments the measurements buried - a second pre-fused2 kernel, pre-gathered
  * cell bricks, the coefficient kernel beside a chunk's last rays, repacked tails - and for what bl_set_tail_policy now says; their
  * numbers are in docs/notebook.md, their code in the history.) */
 
