@@ -259,6 +259,8 @@ def lib():
     L.bl_warnings.restype = C.c_char_p
     L.bl_adaptive_refine.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_int32), C.c_void_p]
+    L.bl_adaptive_refine_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_int32), C.c_void_p]
     L.bl_write_output.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(OutputDesc)]
     L.bl_free.argtypes = [C.c_void_p]
     L.bl_snapshot_open.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]

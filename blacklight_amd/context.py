@@ -566,6 +566,7 @@ class Context:
         """Every later render starts behind the work queued so far on `stream` (a raw hipStream_t handle, e.g.
         torch.cuda.current_stream().cuda_stream; None / 0: the NULL stream) - bl_set_caller_stream."""
         self._check(self._lib.bl_set_caller_stream(self._ctx, C.c_void_p(int(stream or 0)), 1 if enabled else 0))
+        self._caller_stream = (int(stream or 0), bool(enabled))   # (what _render_level_device puts back)
 
     def follow_torch_stream(self, device=None):
         """set_caller_stream(torch's current stream on `device`): tensors torch filled, and collectives torch has waited for on
@@ -779,6 +780,47 @@ class Context:
                                                  nxt.ctypes.data_as(C.c_void_p)))
         return flags.astype(bool), nxt[: 4 * count.value].copy()
 
+    def adaptive_refine_device(self, level, image, block_locs=None, rows=None, pixels=None):
+        """adaptive_refine for a level whose image lies in device memory (bl_adaptive_refine_device): the same flags and the same
+        next list, decided by one kernel over all blocks; only the flags come down. image: a torch tensor on this context's
+        device, float64, contiguous, shape (rows, pixels) as render_device fills it - or a raw device pointer with `rows` and
+        `pixels`. With set_caller_stream / follow_torch_stream enabled the kernel starts behind the work queued on that stream
+        (what fills the tensor). ValueError for anything the C call must not be handed."""
+        if isinstance(image, int) and not isinstance(image, bool):
+            if rows is None or pixels is None or int(rows) < 1 or int(pixels) < 0 or image == 0:
+                raise ValueError("a raw device pointer needs rows and pixels, the shape of the image it points at")
+            pointer, rows, pixels = int(image), int(rows), int(pixels)
+        else:
+            import torch
+            if not isinstance(image, torch.Tensor):
+                raise ValueError("image must be a torch.Tensor in device memory or a raw device pointer (host arrays go through adaptive_refine)")
+            if not image.is_cuda:
+                raise ValueError("image lies in host memory: host arrays go through adaptive_refine")
+            device = self._lib.bl_context_device(self._ctx)
+            if device >= 0 and image.device.index != device:
+                raise ValueError(f"image lies on device {image.device.index}, the context renders on device {device}")
+            if image.dtype != torch.float64:
+                raise ValueError("image must be float64")
+            if image.dim() != 2 or not image.is_contiguous():
+                raise ValueError("image must be contiguous with shape (rows, pixels)")
+            pointer, (rows, pixels) = image.data_ptr(), image.shape
+        if level == 0:
+            bs = int(self.params.get("adaptive_block_size"))
+            n_blocks = (self.resolution // bs) ** 2
+            locs_ptr = None
+        else:
+            bl = np.ascontiguousarray(block_locs, dtype=np.int32).reshape(-1, 2)
+            n_blocks = bl.shape[0]
+            locs_ptr = bl.ctypes.data_as(C.c_void_p)
+        if rows != self.num_quantities or pixels != self.level_pixels(level, n_blocks):
+            raise ValueError(f"image has shape ({rows}, {pixels}), level {level} has ({self.num_quantities}, {self.level_pixels(level, n_blocks)})")
+        flags = np.zeros(n_blocks, dtype=np.uint8)
+        nxt = np.zeros((4 * n_blocks, 2), dtype=np.int32)
+        count = C.c_int32(0)
+        self._check(self._lib.bl_adaptive_refine_device(self._ctx, level, n_blocks, locs_ptr, C.c_void_p(pointer), flags.ctypes.data_as(C.c_void_p),
+                                                        C.byref(count), nxt.ctypes.data_as(C.c_void_p)))
+        return flags.astype(bool), nxt[: 4 * count.value].copy()
+
     def render_template(self, want_camera=False):
         """The per-pixel outputs of render() for zero rays: which rows a level has and their leading shapes
         (blacklight_amd.distributed uses it on a rank that holds no rays of a level)."""
@@ -810,6 +852,55 @@ class Context:
                 return levels
             level += 1
             out = self.render(level=level, block_locs=nxt, want_camera=want_camera)
+            out["block_locs"] = nxt
+            levels.append(out)
+
+    def _render_level_device(self, level=0, block_locs=None, want_camera=False):
+        """One level of render_adaptive_device: render_device into fresh torch tensors on the context's device - image (n_q, n_rays)
+        float64, sample_num int32, sample_flags uint8, camera_pos / camera_dir (n_rays, 4), rendering (n_images, 3, n_rays). The
+        render is queued behind the tensors' creation on torch's current stream; the caller-stream setting the context had
+        (set_caller_stream / follow_torch_stream, or none) is put back before the call returns."""
+        import torch
+        device = torch.device("cuda", self._lib.bl_context_device(self._ctx))
+        n_blocks = 0 if block_locs is None else int(np.asarray(block_locs).reshape(-1, 2).shape[0])
+        n_rays = self.level_pixels(level, n_blocks)
+        n_render = self.num_render_images
+        out = dict(image=torch.empty((self.num_quantities, n_rays), dtype=torch.float64, device=device),
+                   sample_num=torch.empty(n_rays, dtype=torch.int32, device=device), sample_flags=torch.empty(n_rays, dtype=torch.uint8, device=device),
+                   camera_pos=torch.empty((n_rays, 4), dtype=torch.float64, device=device) if want_camera else None,
+                   camera_dir=torch.empty((n_rays, 4), dtype=torch.float64, device=device) if want_camera else None,
+                   rendering=torch.empty((n_render, 3, n_rays), dtype=torch.float64, device=device) if n_render > 0 else None)
+        before = self.__dict__.get("_caller_stream", (0, False))
+        self.follow_torch_stream(device)
+        try:
+            pointer = {name: (0 if tensor is None else tensor.data_ptr()) for name, tensor in out.items()}
+            out["stats"] = self.render_device(pointer["image"], n_rays, level=level, block_locs=block_locs, sample_num_ptr=pointer["sample_num"],
+                                              sample_flags_ptr=pointer["sample_flags"], camera_pos_ptr=pointer["camera_pos"],
+                                              camera_dir_ptr=pointer["camera_dir"], render_ptr=pointer["rendering"])
+        finally:
+            self.set_caller_stream(*before)
+        return out
+
+    def render_adaptive_device(self, want_camera=False):
+        """render_adaptive with every level left in device memory: each level rendered by render_device into fresh torch tensors and
+        refined by adaptive_refine_device, so that no image crosses to the host. A list of per-level dicts as render_adaptive's:
+        image, sample_num, sample_flags, camera_pos, camera_dir and rendering as torch tensors on the device, block_locs and
+        refinement_flags as numpy arrays, stats. The reshaped views of render()'s dicts (image_by_model, image_by_variant,
+        image_by_unit, image_by_cut, image_by_mix) are not there: an adaptive run has one variant, and image.reshape gives them.
+        The decision needs no caller stream: bl_render has returned when it is made, on the stream the level was rendered on.
+        The context's caller-stream setting is left as it was."""
+        levels = [self._render_level_device(want_camera=want_camera)]
+        levels[0]["block_locs"] = None
+        if int(self.params.get("adaptive_max_level") or 0) <= 0:
+            return levels
+        level = 0
+        while True:
+            flags, nxt = self.adaptive_refine_device(level, levels[level]["image"], levels[level]["block_locs"])
+            levels[level]["refinement_flags"] = flags
+            if nxt.shape[0] == 0:
+                return levels
+            level += 1
+            out = self._render_level_device(level=level, block_locs=nxt, want_camera=want_camera)
             out["block_locs"] = nxt
             levels.append(out)
 

@@ -1351,6 +1351,83 @@ int bl_set_caller_stream(bl_ctx *ctx, void *stream, int enabled) {
   return BL_OK;
 }
 
+namespace {
+// bl_adaptive_refine_device's image on the device's side, before the kernel reads it: device memory of this context's device, and
+// `bytes_needed` bytes from `image` inside one allocation (what CheckDevicePointer asks of bl_set_grid_device's cells)
+void CheckDeviceImage(bl_ctx *ctx, const double *image, unsigned long long bytes_needed) {
+  const Failure refusal{BL_E_ARG, "bl_adaptive_refine_device: image must be device memory of the context's device that holds the examined row to its end inside one "
+                                  "allocation; an image in host memory goes through bl_adaptive_refine."};
+  hipPointerAttribute_t attributes{};
+  if (hipPointerGetAttributes(&attributes, image) != hipSuccess) {
+    (void)hipGetLastError();   // (an address the runtime does not know: not an error of this context's)
+    throw refusal;
+  }
+  if (attributes.type != hipMemoryTypeDevice || attributes.device != ctx->device) throw refusal;
+  hipDeviceptr_t first = nullptr;
+  size_t bytes = 0;
+  if (hipMemGetAddressRange(&first, &bytes, const_cast<double *>(image)) != hipSuccess) {
+    (void)hipGetLastError();
+    throw refusal;
+  }
+  const unsigned long long lo = reinterpret_cast<unsigned long long>(first), at = reinterpret_cast<unsigned long long>(image);
+  if (at < lo || at - lo > bytes || bytes_needed > bytes - (at - lo)) throw refusal;
+}
+}  // namespace
+
+int bl_adaptive_refine_device(bl_ctx *ctx, int level, int n_blocks, const int32_t *block_locs, const double *image, uint8_t *refine_flags,
+                              int32_t *n_refined, int32_t *next_locs) {
+  if (ctx == nullptr || image == nullptr || refine_flags == nullptr || n_refined == nullptr || n_blocks < 0) return BL_E_ARG;
+  std::lock_guard<std::mutex> guard(ctx->render_lock);   // (the context's stream and scratch: not beside a render of it)
+  try {
+    if (ctx->device == BL_DEVICE_NONE)
+      throw Failure{BL_E_DEVICE, "Host-only context: no HIP device selected (bl_adaptive_refine_device reads the image in device memory; bl_adaptive_refine decides on the host)."};
+    BlRefinePlan plan;
+    if (int rc = bl_refine_plan(ctx, level, n_blocks, block_locs, n_refined, &plan)) return rc;
+    if (!plan.decide || n_blocks == 0) {   // (no block refines: nothing to launch)
+      for (int b = 0; b < n_blocks; b++) refine_flags[b] = 0;
+      return BL_OK;
+    }
+    if (plan.bs == 1 && (plan.cuts.frac[BL_REFINE_ABS_GRAD] >= 0.0 || plan.cuts.frac[BL_REFINE_REL_GRAD] >= 0.0))
+      throw Failure{BL_E_UNSUPPORTED, "bl_adaptive_refine_device: with adaptive_block_size = 1 a gradient criterion reads the pixel beside its one-pixel block, outside "
+                                      "the block (as bl_adaptive_refine and the reference do): there is no defined result to reproduce."};
+    Check(hipSetDevice(ctx->device), "hipSetDevice");
+    const unsigned long long row_pixels = static_cast<unsigned long long>(plan.n_pix);
+    CheckDeviceImage(ctx, image, (static_cast<unsigned long long>(plan.row) + 1ull) * row_pixels * sizeof(double));
+    EnsureStreams(ctx);
+    hipStream_t stream = ctx->stream;
+    if (ctx->caller_stream_set) {   // bl_set_caller_stream: what the caller queued there so far (the fill of `image`) is ahead of the kernel
+      if (ctx->caller_event == nullptr) Check(hipEventCreateWithFlags(&ctx->caller_event, hipEventDisableTiming), "hipEventCreate");
+      Check(hipEventRecord(ctx->caller_event, ctx->caller_stream), "event on the caller's stream");
+      Check(hipStreamWaitEvent(stream, ctx->caller_event, 0), "stream wait");
+    }
+    BlRefineArgs args{};
+    args.row = image + plan.row * static_cast<size_t>(row_pixels);
+    if (level > 0) {
+      ctx->d_refine_locs.Ensure(static_cast<size_t>(n_blocks) * 2);
+      Check(hipMemcpyAsync(ctx->d_refine_locs.ptr, block_locs, static_cast<size_t>(n_blocks) * 2 * sizeof(int), hipMemcpyHostToDevice, stream), "block_locs upload");
+      args.block_locs = ctx->d_refine_locs.ptr;
+    }
+    ctx->d_refine_flags.Ensure(static_cast<size_t>(n_blocks));
+    args.flags = ctx->d_refine_flags.ptr;
+    args.n_blocks = n_blocks;
+    args.level = level;
+    args.bs = plan.bs;
+    args.res = plan.res;
+    args.root = plan.root;
+    args.linear_num_blocks = plan.linear_num_blocks;
+    args.camera_width = plan.camera_width;
+    args.cuts = plan.cuts;
+    args.regions = plan.regions;
+    Check(bl_launch_refine(&args, stream), "refinement kernel launch");
+    Check(hipMemcpyAsync(refine_flags, ctx->d_refine_flags.ptr, static_cast<size_t>(n_blocks), hipMemcpyDeviceToHost, stream), "refinement flags download");
+    Check(hipStreamSynchronize(stream), "kernel execution");
+    *n_refined = bl_refine_children(plan, level, n_blocks, block_locs, refine_flags, next_locs);
+  } catch (const Failure &failure) {
+    return Fail(ctx, failure);
+  }
+  return BL_OK;
+}
+
 int bl_debug_set_switches(bl_ctx *ctx, uint32_t switches) {
   if (ctx == nullptr) return BL_E_ARG;
   ctx->switches = switches;
@@ -1418,7 +1495,7 @@ void bl_free(bl_ctx *ctx) {
   (void)hipSetDevice(ctx->device);
   ctx->grid.d_cells.Free(); ctx->grid.d_kappa.Free(); ctx->grid.d_coords.Free(); ctx->grid.d_buckets.Free(); ctx->slot[0].Free(); ctx->slot[1].Free();
   ctx->d_freq.Free(); ctx->d_pixel_map.Free();
-  ctx->d_block_locs.Free(); ctx->d_tile_order.Free(); ctx->d_mirror_out.Free(); ctx->d_cameras.Free(); ctx->d_render_params.Free(); ctx->d_render.Free(); ctx->d_shade_cold.Free(); ctx->d_pol_variant_table.Free(); ctx->d_pol_variant_args.Free(); ctx->d_image.Free(); ctx->d_camera_pos.Free(); ctx->d_camera_dir.Free();
+  ctx->d_block_locs.Free(); ctx->d_refine_locs.Free(); ctx->d_refine_flags.Free(); ctx->d_tile_order.Free(); ctx->d_mirror_out.Free(); ctx->d_cameras.Free(); ctx->d_render_params.Free(); ctx->d_render.Free(); ctx->d_shade_cold.Free(); ctx->d_pol_variant_table.Free(); ctx->d_pol_variant_args.Free(); ctx->d_image.Free(); ctx->d_camera_pos.Free(); ctx->d_camera_dir.Free();
   ctx->d_out_sample_num.Free(); ctx->d_out_flags.Free();
   for (auto &e : ctx->events)
     if (e != nullptr) (void)hipEventDestroy(e);

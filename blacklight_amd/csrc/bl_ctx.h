@@ -26,6 +26,7 @@
 #include "bl_device.h"
 #include "bl_grid.h"
 #include "bl_internal.h"
+#include "bl_refine.h"
 
 // The launch wrappers (at the end of each kernel file): each takes its part of the render's KernelPlan (bl_kernel_plan.h), maps it to a
 // kernel through one selector per kernel family, and returns hipErrorInvalidValue where the argument block disagrees with the choice
@@ -57,6 +58,7 @@ extern "C" hipError_t bl_launch_tau(const BlTransferArgs *args, hipStream_t stre
 extern "C" hipError_t bl_launch_transfer_polarized(const BlTransferArgs *args, hipStream_t stream);
 extern "C" hipError_t bl_launch_transport_matrices(const BlTransferArgs *args, int num_cus, hipStream_t stream);
 extern "C" hipError_t bl_launch_transfer_polarized_rays(const BlTransferArgs *args, hipStream_t stream);
+extern "C" hipError_t bl_launch_refine(const BlRefineArgs *args, hipStream_t stream);   // bl_refine_kernel (bl_refine.hip)
 extern "C" hipError_t bl_launch_debug_math(int op, long long n, const double *x, const double *y, double *out, hipStream_t stream);
 
 namespace blhost {
@@ -374,6 +376,8 @@ struct bl_ctx {
   uint64_t RayBytes() const { return rays.Bytes() + d_ray_start.Bytes(); }
   DeviceBuffer<double> d_freq;
   DeviceBuffer<int> d_pixel_map, d_block_locs, d_tile_order;
+  DeviceBuffer<int> d_refine_locs;               // bl_adaptive_refine_device: the level's block list ...
+  DeviceBuffer<unsigned char> d_refine_flags;    // ... and its flags, grown as needed
   int tile_order_res = 0;
   bool tile_order_xcd = false;   // d_tile_order in super-tiles of 8 x 8 tiles (the trace order per XCD, bl_render.hip) or tile by tile
   // Mirror pairs (bl_render.hip: MirrorPairsApply). d_tile_order lists the left half's tiles only (tile_order_half), d_mirror_out holds, per

@@ -901,11 +901,13 @@ extern "C" hipError_t bl_launch_split_long(const BlTraceArgs *args, hipStream_t 
   return hipGetLastError();
 }
 
-// Start states of the rays [chunk_begin, chunk_begin + chunk_rays) (bl_ray_init_kernel)
+// Start states of the rays [chunk_begin, chunk_begin + chunk_rays) (bl_ray_init_kernel). The fixed-step steppers start from the
+// general Dormand-Prince instantiation: rows 0..8 are the same code, and the first-stage derivatives it also leaves in rows 9..16 of
+// ray_start (the buffer always has BL_RAY_START_FIELDS rows) are read by the Dormand-Prince stepper alone.
 extern "C" hipError_t bl_launch_ray_init(const BlTraceArgs *args, const KernelPlan::Geodesic &plan, hipStream_t stream) {
   const bool dp = plan.integrator == BL_INTEGRATOR_DP;
   if (plan.spin_zero && (!dp || args->st.bh_a != 0.0)) return hipErrorInvalidValue;
-  BlTraceKernel kernel = dp ? (plan.spin_zero ? bl_ray_init_kernel<true, true> : bl_ray_init_kernel<true, false>) : bl_ray_init_kernel<false, false>;
+  BlTraceKernel kernel = plan.spin_zero ? bl_ray_init_kernel<true, true> : bl_ray_init_kernel<true, false>;
   hipLaunchKernelGGL(kernel, dim3((args->chunk_rays + 255) / 256), dim3(256), 0, stream, *args);
   return hipGetLastError();
 }

@@ -20,96 +20,28 @@
 #include <vector>
 
 #include "bl_internal.h"
+#include "bl_refine.h"
 #include "blmath.h"
 
 namespace {
 
 // ------------------------------------------------------------------ adaptive refinement
-// EvaluateBlock (radiation_adaptive.cpp:163-312). q(row, col) = intensity of the block.
-bool EvaluateBlock(const bl_params &p, const double *block, int bs) {
+// EvaluateBlock (radiation_adaptive.cpp:163-312). q(row, col) = intensity of the block. The criteria's arithmetic is bl_refine.h's,
+// which the device call (bl_refine.hip) shares.
+bool EvaluateBlock(const BlRefineCuts &cuts, const double *block, int bs) {
   auto q_at = [&](int i, int j) { return block[i * bs + j]; };
-  auto exceeds = [](int num_exceeded, int num_examined, double frac_cut) {
-    double frac = static_cast<double>(num_exceeded) / static_cast<double>(num_examined);
-    return frac > frac_cut;
-  };
-  if (p.adaptive_val_frac >= 0.0) {
+  for (int c = 0; c < BL_REFINE_CRITERIA; c++) {
+    if (!(cuts.frac[c] >= 0.0)) continue;
+    const int margin = bl_refine_margin(c);
     int num_examined = 0, num_exceeded = 0;
-    for (int i = 0; i < bs; i++)
-      for (int j = 0; j < bs; j++) {
-        double q = std::abs(q_at(i, j));
-        if (!std::isfinite(q)) continue;
+    for (int i = margin; i < bs - margin; i++)
+      for (int j = margin; j < bs - margin; j++) {
+        double q = bl_refine_examined(c, q_at, i, j, bs);
+        if (!bl_refine_counts(q)) continue;
         num_examined++;
-        if (q > p.adaptive_val_cut) num_exceeded++;
+        if (q > cuts.cut[c]) num_exceeded++;
       }
-    if (exceeds(num_exceeded, num_examined, p.adaptive_val_frac)) return true;
-  }
-  if (p.adaptive_abs_grad_frac >= 0.0) {
-    int num_examined = 0, num_exceeded = 0;
-    for (int i = 0; i < bs; i++)
-      for (int j = 0; j < bs; j++) {
-        double q_x = j == 0 ? q_at(i, j + 1) - q_at(i, j)
-            : (j == bs - 1 ? q_at(i, j) - q_at(i, j - 1) : 0.5 * (q_at(i, j + 1) - q_at(i, j - 1)));
-        double q_y = i == 0 ? q_at(i + 1, j) - q_at(i, j)
-            : (i == bs - 1 ? q_at(i, j) - q_at(i - 1, j) : 0.5 * (q_at(i + 1, j) - q_at(i - 1, j)));
-        double q = bl_hypot(q_x, q_y);
-        if (!std::isfinite(q)) continue;
-        num_examined++;
-        if (q > p.adaptive_abs_grad_cut) num_exceeded++;
-      }
-    if (exceeds(num_exceeded, num_examined, p.adaptive_abs_grad_frac)) return true;
-  }
-  if (p.adaptive_rel_grad_frac >= 0.0) {
-    int num_examined = 0, num_exceeded = 0;
-    for (int i = 0; i < bs; i++)
-      for (int j = 0; j < bs; j++) {
-        double q_x;
-        if (j == 0)
-          q_x = 2.0 * (q_at(i, j + 1) - q_at(i, j)) / (q_at(i, j) + q_at(i, j + 1));
-        else if (j == bs - 1)
-          q_x = 2.0 * (q_at(i, j) - q_at(i, j - 1)) / (q_at(i, j - 1) + q_at(i, j));
-        else
-          q_x = 2.0 * (q_at(i, j + 1) - q_at(i, j - 1)) / (q_at(i, j - 1) + 2.0 * q_at(i, j) + q_at(i, j + 1));
-        double q_y;
-        if (i == 0)
-          q_y = 2.0 * (q_at(i + 1, j) - q_at(i, j)) / (q_at(i, j) + q_at(i + 1, j));
-        else if (i == bs - 1)
-          q_y = 2.0 * (q_at(i, j) - q_at(i - 1, j)) / (q_at(i - 1, j) + q_at(i, j));
-        else
-          q_y = 2.0 * (q_at(i + 1, j) - q_at(i - 1, j)) / (q_at(i - 1, j) + 2.0 * q_at(i, j) + q_at(i + 1, j));
-        double q = bl_hypot(q_x, q_y);
-        if (!std::isfinite(q)) continue;
-        num_examined++;
-        if (q > p.adaptive_rel_grad_cut) num_exceeded++;
-      }
-    if (exceeds(num_exceeded, num_examined, p.adaptive_rel_grad_frac)) return true;
-  }
-  if (p.adaptive_abs_lapl_frac >= 0.0) {
-    int num_examined = 0, num_exceeded = 0;
-    for (int i = 1; i < bs - 1; i++)
-      for (int j = 1; j < bs - 1; j++) {
-        double q_x = q_at(i, j - 1) - 2.0 * q_at(i, j) + q_at(i, j + 1);
-        double q_y = q_at(i - 1, j) - 2.0 * q_at(i, j) + q_at(i + 1, j);
-        double q = std::abs(q_x + q_y);
-        if (!std::isfinite(q)) continue;
-        num_examined++;
-        if (q > p.adaptive_abs_lapl_cut) num_exceeded++;
-      }
-    if (exceeds(num_exceeded, num_examined, p.adaptive_abs_lapl_frac)) return true;
-  }
-  if (p.adaptive_rel_lapl_frac >= 0.0) {
-    int num_examined = 0, num_exceeded = 0;
-    for (int i = 1; i < bs - 1; i++)
-      for (int j = 1; j < bs - 1; j++) {
-        double q_x = 4.0 * (q_at(i, j - 1) - 2.0 * q_at(i, j) + q_at(i, j + 1))
-            / (q_at(i, j - 1) + 2.0 * q_at(i, j) + q_at(i, j + 1));
-        double q_y = 4.0 * (q_at(i - 1, j) - 2.0 * q_at(i, j) + q_at(i + 1, j))
-            / (q_at(i - 1, j) + 2.0 * q_at(i, j) + q_at(i + 1, j));
-        double q = std::abs(q_x + q_y);
-        if (!std::isfinite(q)) continue;
-        num_examined++;
-        if (q > p.adaptive_rel_lapl_cut) num_exceeded++;
-      }
-    if (exceeds(num_exceeded, num_examined, p.adaptive_rel_lapl_frac)) return true;
+    if (bl_refine_verdict(num_exceeded, num_examined, cuts.frac[c])) return true;
   }
   return false;
 }
@@ -329,12 +261,9 @@ bool FormatFilename(const std::string &pattern, int file_number, std::string *ou
 
 }  // namespace
 
-extern "C" {
-
-int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const int32_t *block_locs,
-                       const double *image, uint8_t *refine_flags, int32_t *n_refined, int32_t *next_locs) {
-  bl_ctx *ctx = const_cast<bl_ctx *>(ctx_const);
-  if (ctx == nullptr || image == nullptr || refine_flags == nullptr || n_refined == nullptr) return BL_E_ARG;
+// ------------------------------------------------------------------ what bl_adaptive_refine and bl_adaptive_refine_device share (bl_refine.h)
+// The refusals and checks of both entry points, with the texts of bl_adaptive_refine. BL_OK: *plan is filled.
+int bl_refine_plan(bl_ctx *ctx, int level, int n_blocks, const int32_t *block_locs, int32_t *n_refined, BlRefinePlan *plan) {
   if (bl_num_electron_models(ctx) >= 2)
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more electron models (bl_set_electron_models).");
   if (bl_num_density_units(ctx) >= 2)
@@ -349,70 +278,100 @@ int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const i
     return bl_internal_fail(ctx, BL_E_UNSUPPORTED, "bl_adaptive_refine reads one image: not with two or more electron mixes (bl_set_electron_mixes).");
   const bl_params &p = *bl_internal_params(ctx);
   *n_refined = 0;
-  if (p.adaptive_max_level <= 0 || level >= p.adaptive_max_level) {   // radiation_adaptive.cpp:22-23
-    for (int b = 0; b < n_blocks; b++) refine_flags[b] = 0;
-    return BL_OK;
-  }
-  const int bs = p.adaptive_block_size;
-  const int linear_root_blocks = p.camera_resolution / bs;
-  if (level == 0 && n_blocks != linear_root_blocks * linear_root_blocks)
+  *plan = BlRefinePlan{};
+  if (p.adaptive_max_level <= 0 || level >= p.adaptive_max_level) return BL_OK;
+  plan->decide = true;
+  plan->bs = p.adaptive_block_size;
+  plan->res = p.camera_resolution;
+  plan->root = p.camera_resolution / plan->bs;
+  if (level == 0 && n_blocks != plan->root * plan->root)
     return bl_internal_fail(ctx, BL_E_ARG, "Level 0 must be evaluated with all root blocks.");
   if (level > 0 && block_locs == nullptr) return bl_internal_fail(ctx, BL_E_ARG, "Refined levels need block_locs.");
-  int linear_num_blocks = linear_root_blocks;
-  for (int n = 1; n <= level; n++) linear_num_blocks *= 2;
-  const int block_num_pix = bs * bs;
-  const long long n_pix = level == 0 ? static_cast<long long>(p.camera_resolution) * p.camera_resolution
-                                     : static_cast<long long>(n_blocks) * block_num_pix;
+  plan->linear_num_blocks = plan->root;
+  for (int n = 1; n <= level; n++) plan->linear_num_blocks *= 2;
+  plan->n_pix = level == 0 ? static_cast<long long>(p.camera_resolution) * p.camera_resolution
+                           : static_cast<long long>(n_blocks) * plan->bs * plan->bs;
   // row of I_nu at the chosen frequency (radiation_adaptive.cpp:166-167): rows 4 l + (I, Q, U, V) when polarized
   // (of the context's frequencies: bl_set_frequencies' list where one is set, whose length the setter held adaptive_frequency_num to)
   int n_nu = 0;
   (void)bl_internal_frequencies(ctx, &n_nu);
   const int freq_index = n_nu > 1 ? p.adaptive_frequency_num - 1 : 0;
   const bool polarized = p.model_type == BL_MODEL_SIMULATION && p.image_light && p.has[BL_P_image_polarization] && p.image_polarization;
-  const double *row = image + static_cast<size_t>(freq_index) * (polarized ? 4 : 1) * n_pix;
-  std::vector<double> block(block_num_pix);
+  plan->row = static_cast<size_t>(freq_index) * (polarized ? 4 : 1);
+  plan->camera_width = p.camera_width;
+  const double cut[BL_REFINE_CRITERIA] = {p.adaptive_val_cut, p.adaptive_abs_grad_cut, p.adaptive_rel_grad_cut, p.adaptive_abs_lapl_cut, p.adaptive_rel_lapl_cut};
+  const double frac[BL_REFINE_CRITERIA] = {p.adaptive_val_frac, p.adaptive_abs_grad_frac, p.adaptive_rel_grad_frac, p.adaptive_abs_lapl_frac, p.adaptive_rel_lapl_frac};
+  for (int c = 0; c < BL_REFINE_CRITERIA; c++) {
+    plan->cuts.cut[c] = cut[c];
+    plan->cuts.frac[c] = frac[c];
+  }
+  plan->regions.count = p.adaptive_num_regions > 0 ? p.adaptive_num_regions : 0;
+  for (int r = 0; r < plan->regions.count; r++) {
+    plan->regions.level[r] = p.adaptive_region_level[r];
+    plan->regions.x_min[r] = p.adaptive_region_x_min[r];
+    plan->regions.x_max[r] = p.adaptive_region_x_max[r];
+    plan->regions.y_min[r] = p.adaptive_region_y_min[r];
+    plan->regions.y_max[r] = p.adaptive_region_y_max[r];
+  }
+  return BL_OK;
+}
+
+// The next level's list from the flags (camera.cpp:453-458): parents in order, each with its four children; returns the parents' count
+int bl_refine_children(const BlRefinePlan &plan, int level, int n_blocks, const int32_t *block_locs, const uint8_t *refine_flags,
+                              int32_t *next_locs) {
   int count = 0;
   for (int b = 0; b < n_blocks; b++) {
-    const int loc_v = level == 0 ? b / linear_root_blocks : block_locs[2 * b + 0];
-    const int loc_u = level == 0 ? b % linear_root_blocks : block_locs[2 * b + 1];
-    bool flag = false;
-    bool decided = false;
-    if (p.adaptive_num_regions > 0) {   // forced regions (:52-69, :96-113)
-      double y = ((loc_v + 0.5) / linear_num_blocks - 0.5) * p.camera_width;
-      double x = ((loc_u + 0.5) / linear_num_blocks - 0.5) * p.camera_width;
-      for (int r = 0; r < p.adaptive_num_regions; r++)
-        if (level < p.adaptive_region_level[r] && x > p.adaptive_region_x_min[r] && x < p.adaptive_region_x_max[r]
-            && y > p.adaptive_region_y_min[r] && y < p.adaptive_region_y_max[r]) {
-          flag = true;
-          decided = true;
-          break;
+    if (!refine_flags[b]) continue;
+    if (next_locs != nullptr) {
+      int loc_v, loc_u;
+      bl_refine_block_loc(plan, level, b, block_locs, &loc_v, &loc_u);
+      int32_t *dst = next_locs + static_cast<size_t>(count) * 8;
+      int k = 0;
+      for (int v = 2 * loc_v; v <= 2 * loc_v + 1; v++)
+        for (int u = 2 * loc_u; u <= 2 * loc_u + 1; u++) {
+          dst[2 * k + 0] = v;
+          dst[2 * k + 1] = u;
+          k++;
         }
     }
-    if (!decided) {
+    count++;
+  }
+  return count;
+}
+
+extern "C" {
+
+int bl_adaptive_refine(const bl_ctx *ctx_const, int level, int n_blocks, const int32_t *block_locs,
+                       const double *image, uint8_t *refine_flags, int32_t *n_refined, int32_t *next_locs) {
+  bl_ctx *ctx = const_cast<bl_ctx *>(ctx_const);
+  if (ctx == nullptr || image == nullptr || refine_flags == nullptr || n_refined == nullptr) return BL_E_ARG;
+  BlRefinePlan plan;
+  if (int rc = bl_refine_plan(ctx, level, n_blocks, block_locs, n_refined, &plan)) return rc;
+  if (!plan.decide) {
+    for (int b = 0; b < n_blocks; b++) refine_flags[b] = 0;
+    return BL_OK;
+  }
+  const int bs = plan.bs;
+  const int block_num_pix = bs * bs;
+  const double *row = image + plan.row * static_cast<size_t>(plan.n_pix);
+  std::vector<double> block(block_num_pix);
+  for (int b = 0; b < n_blocks; b++) {
+    int loc_v, loc_u;
+    bl_refine_block_loc(plan, level, b, block_locs, &loc_v, &loc_u);
+    bool flag = bl_refine_forced(plan.regions, level, loc_v, loc_u, plan.linear_num_blocks, plan.camera_width);
+    if (!flag) {
       if (level == 0) {
         const int j0 = loc_v * bs, i0 = loc_u * bs;
         for (int j = 0; j < bs; j++)
-          for (int i = 0; i < bs; i++) block[j * bs + i] = row[static_cast<size_t>(j0 + j) * p.camera_resolution + i0 + i];
+          for (int i = 0; i < bs; i++) block[j * bs + i] = row[static_cast<size_t>(j0 + j) * plan.res + i0 + i];
       } else {
         std::memcpy(block.data(), row + static_cast<size_t>(b) * block_num_pix, sizeof(double) * block_num_pix);
       }
-      flag = EvaluateBlock(p, block.data(), bs);
+      flag = EvaluateBlock(plan.cuts, block.data(), bs);
     }
     refine_flags[b] = flag ? 1 : 0;
-    if (flag) {
-      if (next_locs != nullptr) {   // camera.cpp:453-458
-        int32_t *dst = next_locs + static_cast<size_t>(count) * 8;
-        int k = 0;
-        for (int v = 2 * loc_v; v <= 2 * loc_v + 1; v++)
-          for (int u = 2 * loc_u; u <= 2 * loc_u + 1; u++) {
-            dst[2 * k + 0] = v;
-            dst[2 * k + 1] = u;
-            k++;
-          }
-      }
-      count++;
-    }
   }
+  const int count = bl_refine_children(plan, level, n_blocks, block_locs, refine_flags, next_locs);
   *n_refined = count;
   return BL_OK;
 }

@@ -6,7 +6,8 @@
 #define BLACKLIGHT_AMD_BL_KERNEL_PLAN_H_
 
 struct KernelPlan {
-  // bl_ray_init_kernel<dp, spin_zero> and bl_geodesic_kernel<integrator, with_time, spin_zero, shell> (spin_zero: Dormand-Prince only;
+  // bl_ray_init_kernel<true, spin_zero> (the fixed-step steppers start from the Dormand-Prince instantiation and leave the first-stage
+  // derivatives it also writes unread) and bl_geodesic_kernel<integrator, with_time, spin_zero, shell> (spin_zero: Dormand-Prince only;
   // shell: ... without sample times only). source: who fills the chunk's records - only kStepper launches the geodesic kernel.
   struct Geodesic {
     enum Source { kStepper, kCheckpoint, kResident } source = kStepper;

@@ -9,6 +9,7 @@
 //   bl_coefficients_freq.hip  per-frequency coefficient kernels of polarized and many-frequency runs
 //   bl_transfer.hip           bl_transfer_kernel / _quad / _freq / _aux, bl_tau_kernel
 //   bl_polarized.hip          polarized transport
+//   bl_refine.hip             between renders: bl_refine_kernel, the refinement decision of a level in device memory
 // with the device functions they share in bl_sampling.h (exact tier) and bl_sampling_fast.h (tolerant tier).
 //
 // Compile with -ffp-contract=off: bit-exact sample counts depend on it (see blmath.h).

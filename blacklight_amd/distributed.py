@@ -316,13 +316,18 @@ def _render_into_buffers(ctx, comm, specs, n_local, n_padded, level, pixels, blo
     return buffers, out["stats"]
 
 
-def render_level(ctx, comm, level=0, block_locs=None, want_camera=False, tile=None):
+def render_level(ctx, comm, level=0, block_locs=None, want_camera=False, tile=None, keep_device_image=False):
     """One adaptive level over all ranks. Level 0: the camera in tiles (tile_pixels); refined levels: blocks
     rank, rank + world, ... of `block_locs`. Returns on rank 0 the dict Context.render returns for the whole level
     (image, sample_num, sample_flags, camera rows, rendering) plus max_sample_num / n_flagged of the level; None on
     the other ranks. The per-rank "geodesics terminate unexpectedly" warnings are replaced by one with the level's totals.
     A failure on any rank (a refusal that depends on the rank's own rays, a full record buffer, no memory) is agreed on
-    before the first data collective and raised on every rank (RankError)."""
+    before the first data collective and raised on every rank (RankError).
+    keep_device_image (render_adaptive's refine_on_device): where rank 0 de-tiles the outputs on a GPU, their downloads are queued on a
+    stream of their own behind each de-tiling - torch's current stream carries the gathers and the de-tiling alone, so that work
+    queued behind it does not wait for a download - and rank 0's dict comes back before they have been waited for, with the
+    de-tiled image tensor as "image_device" and, as "_land", the call that waits for the downloads and fills in the host arrays
+    (and the warning); every other case returns as ever."""
     if getattr(ctx, "num_cameras", 0) >= 2:   # (every rank alike, before any collective; render_tiled and render_adaptive come through here)
         raise ValueError("distributed renders tile one camera over the ranks: not with two or more cameras (Context.set_cameras)")
     rank, world = comm.rank, comm.world
@@ -367,7 +372,7 @@ def render_level(ctx, comm, level=0, block_locs=None, want_camera=False, tile=No
         max_num, n_flagged = comm.reduce_counts(max_num, n_flagged)
     result = dict(max_sample_num=max_num, n_flagged=n_flagged, n_rays=n_total) if rank == 0 else None
     import torch
-    landed = {}
+    landed, detiled_image, download_stream = {}, None, None
     for name, rows, dtype in specs:
         gathered = torch.stack([share[name] for share in shares]) if emulated else comm.gather_flat(buffers[name])
         if rank != 0:
@@ -377,28 +382,52 @@ def render_level(ctx, comm, level=0, block_locs=None, want_camera=False, tile=No
         ray_major = name in ("camera_pos", "camera_dir")          # the library writes rays x 4 there, rows x rays elsewhere
         whole = layout.detile(gathered, rows, ray_major=ray_major)
         if whole.is_cuda:
+            if name == "image":
+                detiled_image = whole
             host = torch.empty(whole.shape, dtype=whole.dtype, pin_memory=True)
-            host.copy_(whole, non_blocking=True)
+            if keep_device_image:
+                # (the download on a stream of its own, behind this de-tiling: what follows on torch's stream - the refinement
+                # decision on the de-tiled image - is ordered behind the de-tiling, not behind the copies to the host)
+                if download_stream is None:
+                    download_stream = torch.cuda.Stream(device=whole.device)
+                download_stream.wait_stream(torch.cuda.current_stream(whole.device))
+                whole.record_stream(download_stream)
+                with torch.cuda.stream(download_stream):
+                    host.copy_(whole, non_blocking=True)
+            else:
+                host.copy_(whole, non_blocking=True)
             whole = host
         landed[name] = whole
-    if any(t.is_pinned() for t in landed.values()):
-        torch.cuda.current_stream().synchronize()
-    for name, rows, dtype in specs:
-        if rank != 0:
-            continue
-        full = landed[name].numpy()
-        if name in ("sample_num", "sample_flags"):
-            result[name] = full[0]
-        elif name == "rendering":
-            result[name] = full.reshape(ctx.num_render_images, 3, -1)
-        else:
-            result[name] = full
-    if rank == 0:
-        for key in ROW_KEYS:
-            result.setdefault(key, None)
-        if n_flagged > 0:   # geodesics.cpp:389-394, with the totals of the level
-            result["warning"] = f"Warning: {n_flagged} out of {n_total} geodesics terminate unexpectedly.\n"
-    return result
+    device_image = None
+    if keep_device_image and rank == 0 and landed["image"].is_pinned():
+        device_image = detiled_image
+
+    def land():
+        if download_stream is not None:
+            download_stream.synchronize()
+        elif any(t.is_pinned() for t in landed.values()):
+            torch.cuda.current_stream().synchronize()
+        for name, rows, dtype in specs:
+            if rank != 0:
+                continue
+            full = landed[name].numpy()
+            if name in ("sample_num", "sample_flags"):
+                result[name] = full[0]
+            elif name == "rendering":
+                result[name] = full.reshape(ctx.num_render_images, 3, -1)
+            else:
+                result[name] = full
+        if rank == 0:
+            for key in ROW_KEYS:
+                result.setdefault(key, None)
+            if n_flagged > 0:   # geodesics.cpp:389-394, with the totals of the level
+                result["warning"] = f"Warning: {n_flagged} out of {n_total} geodesics terminate unexpectedly.\n"
+        return result
+
+    if device_image is not None:
+        result["image_device"], result["_land"] = device_image, land
+        return result
+    return land()
 
 
 ROW_KEYS = ("image", "sample_num", "sample_flags", "camera_pos", "camera_dir", "rendering")
@@ -409,14 +438,29 @@ def render_tiled(ctx, comm, want_camera=False, tile=None):
     return render_level(ctx, comm, 0, None, want_camera, tile)
 
 
-def render_adaptive(ctx, comm=None, want_camera=False, tile=None):
+def render_adaptive(ctx, comm=None, want_camera=False, tile=None, refine_on_device=False):
     """The reference's adaptive loop over all ranks. Rank 0 returns the list of per-level dicts Context.render_adaptive
-    returns on one GPU (block_locs, refinement_flags included) and the concatenated warnings; other ranks (None, "")."""
+    returns on one GPU (block_locs, refinement_flags included) and the concatenated warnings; other ranks (None, "").
+    refine_on_device: where rank 0 de-tiles a level's image on its GPU, it decides the refinement there
+    (Context.adaptive_refine_device). The level's downloads run on a stream of their own (render_level, keep_device_image), and the
+    kernel is ordered behind torch's current stream, which carries the level's gathers and de-tiling but none of the copies to the
+    host: the decision and the broadcast of the next list wait for neither the downloads nor the serial host decision, and the
+    downloads are waited for after the broadcast. Where the image is a CPU tensor the host call decides, as without the option.
+    The lists and the returned levels are the same either way."""
     comm = comm or Comm()
     rank = comm.rank
     warnings = ""
     levels = []
-    first = render_level(ctx, comm, 0, None, want_camera, tile)
+
+    def landed(out):   # (refine_on_device: the level's downloads are waited for once its successor's list is on its way)
+        nonlocal warnings
+        out.pop("image_device", None)
+        land = out.pop("_land", None)
+        if land is not None:
+            land()
+            warnings += out.pop("warning", "")
+
+    first = render_level(ctx, comm, 0, None, want_camera, tile, keep_device_image=refine_on_device)
     if rank == 0:
         first["block_locs"] = None
         warnings += first.pop("warning", "")
@@ -429,7 +473,12 @@ def render_adaptive(ctx, comm=None, want_camera=False, tile=None):
         error = None
         if rank == 0:
             try:
-                flags, nxt = ctx.adaptive_refine(level, levels[level]["image"], levels[level]["block_locs"])
+                on_device = levels[level].get("image_device")
+                if on_device is not None:
+                    ctx.follow_torch_stream(on_device.device)   # (the de-tiling was queued on torch's stream; the downloads were not)
+                    flags, nxt = ctx.adaptive_refine_device(level, on_device, levels[level]["block_locs"])
+                else:
+                    flags, nxt = ctx.adaptive_refine(level, levels[level]["image"], levels[level]["block_locs"])
                 levels[level]["refinement_flags"] = flags
             except Exception as failure:   # (a bad image, out of memory, a library error: every rank has to hear of it)
                 error = f"{type(failure).__name__}: {failure}"
@@ -438,12 +487,17 @@ def render_adaptive(ctx, comm=None, want_camera=False, tile=None):
         elif error is not None:
             raise RankError(f"rank 0: {error}")
         block_locs = comm.broadcast_blocks(nxt)
+        if rank == 0:
+            landed(levels[level])
         if block_locs.shape[0] == 0:
             break
         level += 1
-        out = render_level(ctx, comm, level, block_locs, want_camera, tile)
+        out = render_level(ctx, comm, level, block_locs, want_camera, tile, keep_device_image=refine_on_device)
         if rank == 0:
             out["block_locs"] = block_locs
             warnings += out.pop("warning", "")
             levels.append(out)
+    if rank == 0:
+        for out in levels:   # (max_level <= 0, or a level that is nobody's parent: nothing was decided on it)
+            landed(out)
     return (levels, warnings) if rank == 0 else (None, "")

@@ -914,8 +914,11 @@ BL_API const char *bl_warnings(const bl_ctx *ctx);
 BL_API void bl_warnings_clear(bl_ctx *ctx);   /* forget the warnings collected so far */
 BL_API void bl_free(bl_ctx *ctx);
 
-/* ------------------------------------------------------------------ host steps between / after renders
- * Kept on the host exactly like the reference does (tiny, serial per block). */
+/* ------------------------------------------------------------------ steps between / after renders
+ * The output writer runs on the host, as in the reference. The refinement decision exists twice with one result: bl_adaptive_refine
+ * on the host (tiny, serial per block: the call for a level whose image is in host memory already, and the only one a host-only
+ * context has) and bl_adaptive_refine_device on the GPU (one kernel launch over all blocks: the call for a level whose image lies in
+ * HBM - bl_render_desc.outputs_on_device = 1, a de-tiled level of a distributed run - which then need not come down to be decided). */
 #define BL_MAX_LEVELS 16
 
 /* RadiationIntegrator::CheckAdaptiveRefinement + EvaluateBlock (radiation_adaptive.cpp:19-312) for the
@@ -930,6 +933,21 @@ BL_API void bl_free(bl_ctx *ctx);
 BL_API int bl_adaptive_refine(const bl_ctx *ctx, int level, int n_blocks, const int32_t *block_locs,
                               const double *image, uint8_t *refine_flags, int32_t *n_refined,
                               int32_t *next_locs);
+
+/* bl_adaptive_refine with the image in this context's HBM: the same meaning, the same flags and the same list, always (one source for
+ * the criteria, csrc/bl_refine.h). block_locs, refine_flags and next_locs are host arrays as above; `image` is a device pointer to
+ * [n_q][n_pix of this level], of which the one row the decision reads must lie inside one allocation of the context's device to its
+ * end (the allocation as the runtime knows it, hipMemGetAddressRange: for memory handed out by a caching allocator that is the
+ * allocator's segment, not the tensor carved from it - a tensor too short by less than its segment's slack passes this check, and
+ * its extent is the caller's to get right, as Context.adaptive_refine_device does from the tensor's shape). One kernel launch decides every block and the flags (n_blocks bytes) come back with one copy; the list is built on the host
+ * from them. adaptive_max_level <= 0 or level >= adaptive_max_level: all flags 0, nothing is launched. With bl_set_caller_stream
+ * enabled the kernel starts behind the work queued so far on that stream (what fills `image`); the call returns when the flags are
+ * on the host. Refused: what bl_adaptive_refine refuses, with its texts; a host-only context (BL_E_DEVICE); an `image` in host
+ * memory, pinned or not, on another device, or too short (BL_E_ARG); adaptive_block_size = 1 with a gradient criterion on
+ * (BL_E_UNSUPPORTED: the host reads past its one-pixel block there, as the reference does - no defined result). */
+BL_API int bl_adaptive_refine_device(bl_ctx *ctx, int level, int n_blocks, const int32_t *block_locs /* host */,
+                                     const double *image /* device: [n_q][n_pix of this level] */,
+                                     uint8_t *refine_flags /* host out */, int32_t *n_refined, int32_t *next_locs /* host out, may be NULL */);
 
 /* OutputWriter::Write (output_writer.cpp:169-274): npz / npy / raw exactly in the reference's layout
  * (numpy_format.cpp, zip_format.cpp, raw_format.cpp), format and array selection from the parameters. */
