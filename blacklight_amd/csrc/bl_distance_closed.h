@@ -13,9 +13,12 @@
 //   f <= 4         every stage point has r >= half the horizon's r >= M / 2, and f <= 2 M / r: the kernel checks the stages' r (the last
 //                  step of a ray that falls in ends below r_terminate, a little above the horizon; its stages may lie a little below)
 //   |k_t| <= 2 |k| the null condition gives |k_t| <= |k| (f + sqrt(1 + f)) / (1 + f) <= 1.25 |k|; the momentum is renormalised to it
-//                  after every step and drifts by ray_tol within one
+//                  after every step and drifts by ray_tol within one. Needed of the stages of ACCEPTED steps only (a rejected step's
+//                  enter no count): at ray_tol = 1e-3 with ray_step = 0.3 the stages of accepted steps reach 1.81, those of the
+//                  rejected first tries near the hole 10.7 (the sets a0_loose, a09_loose of tests/distance_host_main.cpp)
 //   |l.l - 1| = |eps| <= 64 u   the computed l (a = 0: x_i r / r^2 with r^2 the rounded sum of squares, 9 u; the general formulas
-//                  through the rounded root of the quartic); tests/distance_host_main.cpp checks all three at every stage it evaluates
+//                  through the rounded root of the quartic); tests/distance_host_main.cpp checks all three at every stage it evaluates,
+//                  apart for accepted and for rejected steps
 //
 //   source                                         relative to A, in u     how
 //   ---------------------------------------------  ----------------------  -----------------------------------------------------

@@ -479,7 +479,8 @@ __global__ void __launch_bounds__(256, BL_FAST_WAVES) bl_shade_fast_kernel(const
 // metric and the Jacobian to Cartesian Kerr-Schild coordinates; with u_r = u_theta = 0 that Jacobian collapses - r (sin
 // theta sin phi) + a (sin theta cos phi) = y and r (sin theta cos phi) - a (sin theta sin phi) = x identically - to
 // u^mu = (u^t, -y u^phi, x u^phi, 0): no trigonometric function at all. Powers share one logarithm. The cut at camera_r is
-// not decided within 1e-9 of it, nor anything on the polar axis: those samples go to the exact kernel's second pass.
+// not decided within 1e-9 of it, nor anything on the polar axis or with a fluid-frame frequency that is not positive: those samples go to
+// the exact kernel's second pass.
 __global__ void __launch_bounds__(256, 4) bl_shade_formula_fast_kernel(const BlShadeArgs P) {
   const BlFormulaDevice fm = P.formula;
   const double bh_m = P.st.bh_m, bh_a = P.st.bh_a, a2 = bh_a * bh_a;
@@ -554,6 +555,13 @@ __global__ void __launch_bounds__(256, 4) bl_shade_formula_fast_kernel(const BlS
     const double ut = u_norm * (gtph * ll - gtt);
     const double uph = u_norm * (gphph * ll - gtph);
     const double nu_ratio = -(ut * kt + uph * (x * ky - y * kx));   // -u^mu k_mu with u^mu = (u^t, -y u^phi, x u^phi, 0)
+    // A frequency in the fluid frame that is not a positive number - next to the horizon at loose ray tolerances the stored momentum can
+    // give a negative one - is the exact kernel's: std::pow of a negative base is finite for the integral exponent -alpha and NaN for
+    // others (:172, :177), where a power through the logarithm is NaN throughout. (The frequencies and the factor are positive.)
+    if (!(nu_ratio * momentum_factor > 0.0)) {
+      fast_defer(P, idx_rec);
+      continue;
+    }
     const double n_n0 = fastmath::exp(-0.5 * (r2 * r0_inv2 + h2 * cth2));
     // ---- per frequency (:164-179) and the transfer record (unpolarized.cpp:74-110)
     for (int l = 0; l < P.n_nu; l++) {

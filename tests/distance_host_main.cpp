@@ -4,8 +4,11 @@
 // (the proper distance enters no right-hand side and no error norm, so both modes walk the same points). tests/test_distance_host.py
 // builds it with -ffp-contract=off, reads the figures below and holds them to the bounds of the header.
 //
-//   distance_host_main <set>      set = a0 | ring | a09 | a05 | flat
-// prints one `name value` line per figure; exit code 0 unless a ray set is unknown.
+//   distance_host_main <set>      set = a0 | ring | a09 | a05 | flat | a0_loose | a09_loose | a0_tight
+// (the last three: the controller away from tolerances of 1e-8 - 1e-3 with ray_step = 0.3, where an accepted step is long and its stages lie
+// far from the accepted path, and 1e-12, where nearly every step's error is near 1)
+// prints one `name value` line per figure; exit code 0 unless a ray set is unknown. What the header assumes of a stage's point is counted
+// for the stages of accepted steps - the ones whose d s / d lambda enter a count - and, under rejected_*, for those of rejected steps.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -45,6 +48,10 @@ struct Setup {
 struct Figures {
   long long rays = 0, steps = 0, undecided = 0, ceil_mismatch = 0, stages = 0, assumption_failures = 0, flagged = 0;
   double max_ratio = 0.0, max_derivative = 0.0, max_eps_l = 0.0, max_kt_over_k = 0.0, max_f = 0.0, max_s = 0.0, max_band = 0.0;
+  // the same of the stages of rejected steps, which enter no count: kept apart (a step of 0.3 r near the hole is rejected for what its
+  // stages look like)
+  long long rejected_assumption_failures = 0;
+  double rejected_max_eps_l = 0.0, rejected_max_kt_over_k = 0.0, rejected_max_f = 0.0;
 };
 
 // one stage: the derivatives of (t, x, y, z, k_x, k_y, k_z), the reference's d s / d lambda and the closed form's, r
@@ -123,6 +130,8 @@ void TraceRay(const Setup &su, double u, double v, Figures *fig) {
       return;
     }
     const double h = h_new;
+    const Figures before = *fig;   // (of the assumptions' figures: a rejected step gives its stages' back below)
+    fig->max_eps_l = fig->max_kt_over_k = fig->max_f = 0.0;
     double r_stage = r_cur, r_low = r_cur;
     for (int s = 1; s < 7; s++) {
       double yt[8];
@@ -149,12 +158,22 @@ void TraceRay(const Setup &su, double u, double v, Figures *fig) {
       }
     }
     const double r_new = r_stage;
+    const Figures step = *fig;
+    fig->max_eps_l = before.max_eps_l, fig->max_kt_over_k = before.max_kt_over_k, fig->max_f = before.max_f;
     if (!(error <= 1.0)) {
+      fig->rejected_assumption_failures += step.assumption_failures - before.assumption_failures;
+      fig->assumption_failures = before.assumption_failures;
+      if (!(step.max_eps_l <= fig->rejected_max_eps_l)) fig->rejected_max_eps_l = step.max_eps_l;
+      if (!(step.max_kt_over_k <= fig->rejected_max_kt_over_k)) fig->rejected_max_kt_over_k = step.max_kt_over_k;
+      if (!(step.max_f <= fig->rejected_max_f)) fig->rejected_max_f = step.max_f;
       h_new = h * (std::isfinite(error) ? std::fmax(0.9 * std::pow(error, -0.2), 0.2) : 0.2);
       num_retry++;
       previous_fail = true;
       continue;
     }
+    if (!(step.max_eps_l <= fig->max_eps_l)) fig->max_eps_l = step.max_eps_l;
+    if (!(step.max_kt_over_k <= fig->max_kt_over_k)) fig->max_kt_over_k = step.max_kt_over_k;
+    if (!(step.max_f <= fig->max_f)) fig->max_f = step.max_f;
     double h_factor = 10.0;
     if (error > 0.0) h_factor = std::fmin(std::fmax(0.9 * std::pow(error, -0.2), 0.2), 10.0);
     if (previous_fail) h_factor = std::fmin(h_factor, 1.0);
@@ -238,6 +257,21 @@ int main(int argc, char **argv) {
     su.inclination = 60.0;
     su.max_steps = 20000;
     Lattice(su, 64, &fig);
+  } else if (set == "a0_loose") {
+    su.tol_abs = su.tol_rel = 1.0e-3;
+    su.ray_step = 0.3;
+    Lattice(su, 64, &fig);
+  } else if (set == "a09_loose") {
+    su.st.bh_a = 0.9;
+    su.camera_r = 1000.0;
+    su.inclination = 60.0;
+    su.max_steps = 20000;
+    su.tol_abs = su.tol_rel = 1.0e-3;
+    su.ray_step = 0.3;
+    Lattice(su, 64, &fig);
+  } else if (set == "a0_tight") {
+    su.tol_abs = su.tol_rel = 1.0e-12;
+    Lattice(su, 64, &fig);
   } else if (set == "a05") {
     su.st.bh_a = 0.5;
     su.inclination = 80.0;
@@ -246,12 +280,14 @@ int main(int argc, char **argv) {
     su.st.ray_flat = 1;
     Lattice(su, 64, &fig);
   } else {
-    std::fprintf(stderr, "usage: distance_host_main a0|ring|a09|a05|flat\n");
+    std::fprintf(stderr, "usage: distance_host_main a0|ring|a09|a05|flat|a0_loose|a09_loose|a0_tight\n");
     return 2;
   }
   std::printf("rays %lld\nsteps %lld\nstages %lld\nundecided %lld\nceil_mismatch %lld\nassumption_failures %lld\nflagged %lld\n", fig.rays, fig.steps, fig.stages,
               fig.undecided, fig.ceil_mismatch, fig.assumption_failures, fig.flagged);
   std::printf("max_ratio %.6e\nmax_derivative %.6e\nderivative_bound %.6e\nmax_eps_l_in_u %.3f\nmax_kt_over_k %.6f\nmax_f %.6f\nmax_s %.6e\nmax_band %.6e\n",
               fig.max_ratio, fig.max_derivative, kDerivativeBound, fig.max_eps_l / kU, fig.max_kt_over_k, fig.max_f, fig.max_s, fig.max_band);
+  std::printf("rejected_assumption_failures %lld\nrejected_max_eps_l_in_u %.3f\nrejected_max_kt_over_k %.6f\nrejected_max_f %.6f\n", fig.rejected_assumption_failures,
+              fig.rejected_max_eps_l / kU, fig.rejected_max_kt_over_k, fig.rejected_max_f);
   return 0;
 }

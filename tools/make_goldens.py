@@ -11,7 +11,14 @@ For every case the unmodified reference binary is run twice:
 with checkpoint_geodesic_save = true, and the fixture records, for both tiers, the image rows,
 sample_num, sample_flags, the camera frame, and complete per-sample data for a few rays.
 
+The formula_ctl_* cases (CONTROLLER_CASES: the step controller away from ray_tol = 1e-8 and ray_max_retries = 20) take tier B from
+oracle/_ref/blacklight_blmath instead (`make -C oracle ref_blmath`): the reference's objects linked with the pinned math library's
+object, nothing preloaded. `--check-linked formula_dp` regenerates a committed case by that route into a temporary directory and
+compares its B_* arrays with the committed file's, bit for bit (exit code 1 otherwise).
+
 Usage:  /opt/conda/bin/python3.9 tools/make_goldens.py [case ...]
+        tools/make_goldens.py controller              (all of CONTROLLER_CASES; formula mode: any Python with numpy)
+        tools/make_goldens.py --check-linked formula_dp
         (`cut_each`: tests/golden/cut_each.npz, every optional cut alone - the stock build only, images and counts, no ray dumps)
 """
 import json
@@ -24,6 +31,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_BIN = os.path.join(REPO, "oracle", "_ref", "blacklight")
 PRELOAD = os.path.join(REPO, "oracle", "_ref", "libblmath_preload.so")
+REF_BLMATH = os.path.join(REPO, "oracle", "_ref", "blacklight_blmath")   # (tier B with nothing preloaded: preload="linked")
 MOCK_SCRIPT = "/root/reference/scripts/generate_mock_simulation.py"
 WORK = "/tmp/blgold"
 OUT = os.path.join(REPO, "tests", "golden")
@@ -226,6 +234,35 @@ CASES = {
 }
 
 
+# The Dormand-Prince step controller (geodesics.cpp:136-224) away from the one setting of everything above: FORMULA_BASE at 16^2.
+# name: (overrides, the ray to dump in full - or "retry": the first ray of the run that exhausts its retries -, what the case is there for)
+CONTROLLER_CASES = {
+    "formula_ctl_tol3": (dict(ray_tol_abs=1.0e-3, ray_tol_rel=1.0e-3), "retry",
+                         "loose tolerances: steps grown by the factor 10, accepted steps that emit many samples; one ray ends flagged short of "
+                         "ray_max_steps with ray_max_retries = 20 (a non-finite error: h_factor = 0.2 without the power) and its pixel is NaN"),
+    "formula_ctl_tol12": (dict(ray_tol_abs=1.0e-12, ray_tol_rel=1.0e-12), 136,
+                          "tight tolerances: the error is near 1 at nearly every step (pow(error, -0.2) near 1), frequent single rejections; no flag"),
+    "formula_ctl_abs9": (dict(ray_tol_abs=1.0e-9, ray_tol_rel=0.0), 136, "ray_tol_rel = 0: the scale of the error is the absolute tolerance alone"),
+    "formula_ctl_rel9": (dict(ray_tol_abs=1.0e-300, ray_tol_rel=1.0e-9), 136,
+                         "a scale that is almost only relative: components near zero (y, k_y in the camera's plane) divide by nearly nothing"),
+    "formula_ctl_retry1": (dict(ray_max_retries=1), "retry", "retries exhausted mid-ray (num_retry > ray_max_retries): flag, the ray ends with the samples it has"),
+    "formula_ctl_retry1_tol12": (dict(ray_max_retries=1, ray_tol_abs=1.0e-12, ray_tol_rel=1.0e-12), "retry", "retries exhausted at tight tolerances"),
+    "formula_ctl_retry2_tol13": (dict(ray_max_retries=2, ray_tol_abs=1.0e-13, ray_tol_rel=1.0e-13), "retry",
+                                 "retries exhausted after three rejections in a row, tolerances at the edge of what fp64 resolves"),
+    "formula_ctl_step03": (dict(ray_step=0.3), 136, "ray_step = 0.3: a first step of 0.3 r from r = 1000, rejected first tries (previous_fail at n = 0), few samples per step"),
+    "formula_ctl_step03_tol4": (dict(ray_step=0.3, ray_tol_abs=1.0e-4, ray_tol_rel=1.0e-4), 136,
+                                "ray_step = 0.3 with loose tolerances: rays of fewer than 200 samples, long accepted steps"),
+    "formula_ctl_a0_tol3": (dict(formula_spin=0.0, ray_tol_abs=1.0e-3, ray_tol_rel=1.0e-3), 136, "zero spin, loose tolerances"),
+    "formula_ctl_a0_retry2": (dict(formula_spin=0.0, ray_step=0.3, ray_tol_abs=1.0e-12, ray_tol_rel=1.0e-12, ray_max_retries=2), 136,
+                              "zero spin: the first step of every ray is rejected twice (previous_fail at n = 0), then the ray goes on; no flag"),
+    # every ray exhausts its retries on its first step. The reference has no image of such a frame: with geodesic_num_steps = 0 it stops in
+    # geodesics.cpp:814 ("Attempting to allocate empty array.", utils/array.cpp:163) after its warning. No fixture: the run is made and has
+    # to end that way (tests/test_controller_goldens_host.py and tests/test_gpu_controller.py hold the frame to the CPU oracle)
+    "formula_ctl_a0_retry1": (dict(formula_spin=0.0, ray_step=0.3, ray_tol_abs=1.0e-12, ray_tol_rel=1.0e-12, ray_max_retries=1), "refused",
+                              "zero spin: a frame of flagged rays with zero samples"),
+}
+
+
 def write_input(path, params):
     with open(path, "w") as f:
         for key, value in params.items():
@@ -281,10 +318,13 @@ def read_checkpoint(path, dump_rays):
 
 
 def run_reference(workdir, input_name, preload):
+    """preload: False (the stock build), True (the pinned math library preloaded into it) or "linked" (oracle/_ref/blacklight_blmath, the
+    pinned math library linked in and nothing preloaded)."""
     env = dict(os.environ)
-    if preload:
+    if preload is True:
         env["LD_PRELOAD"] = PRELOAD
-    result = subprocess.run([REF_BIN, input_name], cwd=workdir, env=env, capture_output=True, text=True)
+    binary = REF_BLMATH if preload == "linked" else REF_BIN
+    result = subprocess.run([binary, input_name], cwd=workdir, env=env, capture_output=True, text=True)
     if "Calculation completed" not in result.stdout:
         raise RuntimeError(f"reference failed: {result.stdout}\n{result.stderr}")
     return result.stderr
@@ -380,8 +420,17 @@ def split_refined(src, dst, last=None):
         g.create_dataset("B", data=blocks["prim"][n_hydro:], dtype=np.float32)
 
 
-def make_case(name):
-    base, overrides, mock, dump_rays = CASES[name]
+def make_case(name, out_dir=None, tier_b=True):
+    """tier_b: how tier B is run (run_reference's preload). A controller case dumps one ray; "retry" picks it from a first run."""
+    extra = {}
+    if name in CONTROLLER_CASES:
+        overrides, dump, note = CONTROLLER_CASES[name]
+        base, overrides, mock, dump_rays = FORMULA_BASE, dict(overrides, camera_resolution=16), None, [dump]
+        tier_b = "linked"
+        extra["controller_note"] = note
+    else:
+        base, overrides, mock, dump_rays = CASES[name]
+    out_dir = out_dir or OUT
     params = dict(base)
     params.update(overrides)
     workdir = os.path.join(WORK, name)
@@ -407,13 +456,33 @@ def make_case(name):
             split_into_blocks(single, mock_path, *mock["_blocks"], last=mock.get("_last"))
         fixture["mock_args"] = json.dumps(mock)
     write_input(os.path.join(workdir, "case.input"), params)
+    res = int(params["camera_resolution"])
     # what the test feeds to the build: same keys without file plumbing
     skip = {"checkpoint_geodesic_save", "checkpoint_geodesic_file"}
     test_params = {k: v for k, v in params.items() if k not in skip}
     test_params["checkpoint_geodesic_save"] = "false"
     fixture["params"] = json.dumps(test_params)
+    if dump_rays == ["refused"]:
+        try:
+            run_reference(workdir, "case.input", tier_b)
+        except RuntimeError as err:
+            if "Attempting to allocate empty array." in str(err) and f"Warning: {res * res} out of {res * res} geodesics terminate unexpectedly." in str(err):
+                print(f"{name}: no fixture - every geodesic ends flagged with no sample and the reference stops: Attempting to allocate empty array.")
+                return
+            raise
+        raise RuntimeError(f"{name}: the reference was expected to stop on a frame without samples, and did not")
+    if dump_rays == ["retry"]:   # the first ray that ends flagged short of ray_max_steps, from tier B's own run
+        run_reference(workdir, "case.input", tier_b)
+        chk = read_checkpoint(os.path.join(workdir, "data", "geo.dat"), [])
+        os.remove(os.path.join(workdir, "data", "geo.dat"))
+        exhausted = np.nonzero((chk["sample_flags"] != 0) & (chk["sample_num"] < int(params["ray_max_steps"])))[0]
+        if exhausted.size == 0:
+            raise RuntimeError(f"{name}: no ray exhausts its retries: fixture not written")
+        dump_rays = [int(exhausted[0])]
+        extra["controller_note"] += f" ({exhausted.size} such rays; ray {dump_rays[0]} is dumped)"
+    fixture.update(extra)
     fixture["dump_rays"] = np.array(dump_rays, dtype=np.int64)
-    for tier, preload in (("A", False), ("B", True)):
+    for tier, preload in (("A", False), ("B", tier_b)):
         warnings = run_reference(workdir, "case.input", preload)
         npz = np.load(os.path.join(workdir, "output", "out.npz"))
         fixture[f"{tier}_warnings"] = warnings
@@ -430,8 +499,8 @@ def make_case(name):
             else:
                 fixture[f"{tier}_{key}"] = value
         os.remove(os.path.join(workdir, "data", "geo.dat"))
-    os.makedirs(OUT, exist_ok=True)
-    np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **fixture)
+    os.makedirs(out_dir, exist_ok=True)
+    np.savez_compressed(os.path.join(out_dir, f"{name}.npz"), **fixture)
     key = "I_nu" if "A_npz_I_nu" in fixture else "rendering"
     a, b = fixture[f"A_npz_{key}"], fixture[f"B_npz_{key}"]
     same_num = np.array_equal(fixture["A_sample_num"], fixture["B_sample_num"])
@@ -1375,8 +1444,27 @@ def make_cut_fixture():
     print(f"cut_each: {len(CUT_CASES)} cases written")
 
 
+def check_linked(name):
+    """Tier B of a committed case again, from oracle/_ref/blacklight_blmath, into a temporary directory: every B_* array must have the
+    committed file's bits (the pinned-math reference is the same program with and without LD_PRELOAD)."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as scratch:
+        make_case(name, out_dir=scratch, tier_b="linked")
+        new, old = np.load(os.path.join(scratch, f"{name}.npz")), np.load(os.path.join(OUT, f"{name}.npz"))
+        keys = sorted(k for k in old.files if k.startswith("B_"))
+        differing = [k for k in keys if k not in new.files or new[k].dtype != old[k].dtype or new[k].shape != old[k].shape
+                     or new[k].tobytes() != old[k].tobytes()]
+        differing += [k for k in new.files if k.startswith("B_") and k not in old.files]
+    print(f"check-linked {name}: {len(keys)} B_* arrays of tests/golden/{name}.npz, {len(differing)} differ from oracle/_ref/blacklight_blmath's"
+          + (": " + ", ".join(differing) if differing else " (bit for bit)"))
+    return not differing
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["--check-linked"]:
+        sys.exit(0 if all([check_linked(case_name) for case_name in sys.argv[2:]]) and len(sys.argv) > 2 else 1)
     names = sys.argv[1:] or (["mock"] + list(CASES))
+    names = [n for name in names for n in (list(CONTROLLER_CASES) if name == "controller" else [name])]
     for case_name in names:
         if case_name == "cut_each":
             make_cut_fixture()
