@@ -40,6 +40,23 @@ class DeviceCells(C.Structure):
                 ("n_elements", C.c_int64), ("stream", C.c_void_p)]
 
 
+class HarmHeader(C.Structure):
+    """bl_harm_header: what the reader takes from an iharm3d file's header (absent adiabatic index: NaN; absent variable: -1)."""
+    _fields_ = [("n1", C.c_int32), ("n2", C.c_int32), ("n3", C.c_int32), ("n_prim", C.c_int32), ("startx", C.c_double * 3), ("dx", C.c_double * 3),
+                ("a", C.c_double), ("hslope", C.c_double), ("metric", C.c_int32), ("reserved", C.c_int32),
+                ("r_in", C.c_double), ("poly_xt", C.c_double), ("poly_alpha", C.c_double), ("mks_smooth", C.c_double),
+                ("gam", C.c_double), ("gam_p", C.c_double), ("gam_e", C.c_double)] + \
+               [(name, C.c_int32) for name in ("ind_rho", "ind_uu", "ind_u1", "ind_u2", "ind_u3", "ind_b1", "ind_b2", "ind_b3", "ind_kappa", "reserved2")]
+
+
+BL_HARM_MKS, BL_HARM_FMKS = 0, 1
+
+
+class HarmCells(C.Structure):
+    """bl_harm_cells: a harm-family code's prims[n1][n2][n3][n_prim] in device memory (bl_set_grid_device_harm)."""
+    _fields_ = [("prim", C.c_void_p), ("dtype", C.c_int32), ("wait", C.c_int32), ("n_elements", C.c_int64), ("stream", C.c_void_p)]
+
+
 BL_MAX_SWEEP = 16
 
 
@@ -275,6 +292,23 @@ def lib():
     L.bl_snapshot_blocks.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32))]
     L.bl_snapshot_close.argtypes = [C.c_void_p]
     L.bl_snapshot_open_number.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    L.bl_snapshot_open_raw.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    L.bl_snapshot_harm_header.argtypes = [C.c_void_p, C.POINTER(HarmHeader)]
+    L.bl_snapshot_harm_prims.argtypes = [C.c_void_p]
+    L.bl_snapshot_harm_prims.restype = C.c_void_p
+    L.bl_harm_header_sizeof.restype = C.c_size_t
+    L.bl_harm_cells_sizeof.restype = C.c_size_t
+    L.bl_harm_grid_create.argtypes = [C.c_void_p, C.POINTER(HarmHeader), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+    L.bl_harm_grid_desc.argtypes = [C.c_void_p, C.c_int]
+    L.bl_harm_grid_desc.restype = C.POINTER(GridDesc)
+    L.bl_harm_grid_warnings.argtypes = [C.c_void_p]
+    L.bl_harm_grid_warnings.restype = C.c_char_p
+    L.bl_harm_grid_planes.argtypes = [C.c_void_p]
+    L.bl_harm_grid_free.argtypes = [C.c_void_p]
+    L.bl_harm_convert_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bl_set_grid_device_harm.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(HarmCells)]
+    L.bl_set_grid_slice_device_harm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(HarmCells), C.c_double]
+    L.bl_harm_convert_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(HarmCells), C.c_void_p]
     L.bl_slow_light_read.argtypes = [C.c_void_p, C.c_int]
     L.bl_set_grid_slice.argtypes = [C.c_void_p, C.c_int, C.POINTER(GridDesc), C.c_double]
     L.bl_shift_grid_slices.argtypes = [C.c_void_p, C.c_int]

@@ -647,6 +647,61 @@ class Context:
         self._grid_keepalive = grid
         self._check(self._lib.bl_set_grid_device(self._ctx, C.byref(desc), C.byref(cells)))
 
+    def _harm_cells(self, grid, prims, stream):
+        """bl_harm_cells for a torch tensor on this context's device; ValueError for anything the C call must not be handed."""
+        import torch
+        if not isinstance(prims, torch.Tensor):
+            raise ValueError("prims must be a torch.Tensor in device memory (host arrays go through HarmGrid.convert_host and set_grid)")
+        if not prims.is_cuda:
+            raise ValueError("prims lies in host memory: host arrays go through HarmGrid.convert_host and set_grid")
+        device = self._lib.bl_context_device(self._ctx)
+        if device >= 0 and prims.device.index != device:
+            raise ValueError(f"prims lies on device {prims.device.index}, the context renders on device {device}")
+        if prims.dtype not in (torch.float32, torch.float64):
+            raise ValueError("prims must be float32 or float64")
+        if tuple(prims.shape) != tuple(grid.shape):
+            raise ValueError(f"prims has shape {tuple(prims.shape)}, the grid's header says {tuple(grid.shape)}: (n1, n2, n3, n_prim)")
+        if not prims.is_contiguous():
+            raise ValueError("prims must be contiguous [n1][n2][n3][n_prim]")
+        cells = _capi.HarmCells()
+        cells.prim = prims.data_ptr()
+        cells.dtype = _capi.BL_CELLS_F32 if prims.dtype == torch.float32 else _capi.BL_CELLS_F64
+        cells.n_elements = prims.untyped_storage().nbytes() // prims.element_size() - prims.storage_offset()
+        if stream == "torch":
+            cells.wait, cells.stream = 1, torch.cuda.current_stream(prims.device).cuda_stream
+        elif stream is not None:
+            cells.wait, cells.stream = 1, int(stream)
+        return cells
+
+    def set_grid_device_harm(self, grid, prims, stream="torch"):
+        """set_grid_device for the array an iharm3d-family code holds (bl_set_grid_device_harm). grid: a snapshot.HarmGrid; prims: a torch
+        tensor on this context's device, float32 or float64, contiguous (n1, n2, n3, n_prim). The staging kernel transposes and converts
+        the cells as the file reader does: the render reads the bits set_grid(Snapshot) would have put there. stream: as set_grid_device."""
+        cells = self._harm_cells(grid, prims, stream)
+        self._grid_keepalive = grid
+        self._check(self._lib.bl_set_grid_device_harm(self._ctx, grid.handle, C.byref(cells)))
+
+    def set_grid_slice_device_harm(self, n, grid, prims, time, stream="torch"):
+        """set_grid_slice with a harm-family array in device memory: set_grid_device_harm's arguments."""
+        cells = self._harm_cells(grid, prims, stream)
+        self._check(self._lib.bl_set_grid_slice_device_harm(self._ctx, int(n), grid.handle, C.byref(cells), float(time)))
+
+    def harm_convert_device(self, grid, prims, out=None, stream="torch"):
+        """The planes HarmGrid.convert_host makes, written on the device (bl_harm_convert_device): a float32 tensor
+        (grid.planes, n3, n2, n1) - `out` if given (contiguous, on this context's device), else a new one. With grid.desc(converted=True)
+        it is what set_grid_device takes. Returns when the planes are written."""
+        import torch
+        cells = self._harm_cells(grid, prims, stream)
+        n1, n2, n3, _ = grid.shape
+        shape = (grid.planes, n3, n2, n1)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=prims.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != prims.device or out.dtype != torch.float32 or tuple(out.shape) != shape
+              or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on the device of prims")
+        self._check(self._lib.bl_harm_convert_device(self._ctx, grid.handle, C.byref(cells), out.data_ptr()))
+        return out
+
     @property
     def grid_host_bytes(self):
         """Bytes the last set_grid* call copied from host memory (after set_grid_device: the tables only)."""

@@ -7,6 +7,7 @@
 // hot-path scope. Configurations outside it are rejected loudly (BL_E_UNSUPPORTED); nothing falls
 // back to a CPU path.
 #include "bl_ctx.h"
+#include "bl_harm.h"
 
 #include <optional>
 
@@ -761,9 +762,101 @@ struct BlCellPlanes {
 __device__ __forceinline__ float bl_plane_cell(const void *base, unsigned long long at, int f64) {
   return f64 ? static_cast<float>(static_cast<const double *>(base)[at]) : static_cast<const float *>(base)[at];
 }
-__global__ void __launch_bounds__(256) bl_interleave_cells_kernel(BlCellPlanes src, float *cells, unsigned long long n_cells, int nb_i, int nb_j, int nb_k,
+
+// The harm form of the same kernel (bl_set_grid_device_harm, bl_harm_convert_device): the source is one array [n1][n2][n3][n_prim] of a
+// harm-family code, the target the same cells transposed to [k][j][i] and converted as the reader converts a file's (bl_harm.h). The
+// source is contiguous along (k, variable) for fixed (i, j), the target along i: a workgroup takes a tile of kHarmTileI i's by
+// kHarmTileK k's at one j through LDS - the reads run along k * n_prim (256 bytes and more per i), a lane then converts one cell and
+// the stores run along i (whole 32-byte cells, 1 KB per half wave; plane by plane for bl_harm_convert_device) - and up to
+// kHarmChunkTiles such tiles one after the other in k, so that the point structs of its i's are read once, into LDS, for all of them.
+// A row of the tile (one i) is kHarmTileK * 9 + 1 words: the odd stride puts the lanes of a half wave, which read the same word of
+// 32 different rows, into 32 different banks. No atomics; every address is formed from i < n1, j < n2, k < n3 and an index < n_prim.
+struct BlHarmSource {
+  const void *prims;                  // null: the plain form (and nothing else of this struct is read)
+  const double *points;               // [n2][n1][BL_HARM_POINT_DOUBLES]: BlHarmPoint
+  float *kappa;                       // the entropy plane [k][j][i] (variable index[8]); null: none
+  unsigned long long plane_stride;    // 0: `cells` is [cell][8]; else eight planes, this many floats apart
+  int n1, n2, n3, n_prim;
+  int index[9];                       // rho, UU, U1..3, B1..3, entropy: where they lie in a cell's n_prim values
+  int f64;
+  float gamma_minus_one;
+  unsigned int i_tiles;               // tiles along i: block = (k_chunk * n2 + j) * i_tiles + i_tile
+};
+constexpr int kHarmTileI = 32, kHarmTileK = 8, kHarmSlots = 9, kHarmRow = kHarmTileK * kHarmSlots + 1, kHarmChunkTiles = 8;
+constexpr int kHarmPointRow = BL_HARM_POINT_DOUBLES + 1;   // a point's doubles and one of padding: the lanes of a half wave read one member of 32 points
+constexpr size_t kHarmLdsBytes = static_cast<size_t>(kHarmPointRow) * kHarmTileI * sizeof(double) + static_cast<size_t>(kHarmTileI) * kHarmRow * sizeof(float);
+static_assert(kHarmTileI * kHarmTileK == 256, "a lane per cell of the tile");
+
+__device__ __forceinline__ void bl_harm_stage(const BlHarmSource &h, float *cells) {
+  extern __shared__ double bl_stage_lds[];
+  double *points = bl_stage_lds;                                                    // [i of the tile][kHarmPointRow]
+  float *tile = reinterpret_cast<float *>(bl_stage_lds + kHarmPointRow * kHarmTileI);   // [i of the tile][kHarmRow]
+  const int t = threadIdx.x;
+  const unsigned int i_tile = blockIdx.x % h.i_tiles, rest = blockIdx.x / h.i_tiles;
+  const int j = static_cast<int>(rest % static_cast<unsigned int>(h.n2)), k_chunk = static_cast<int>(rest / static_cast<unsigned int>(h.n2));
+  const int i0 = static_cast<int>(i_tile) * kHarmTileI;
+  const int n_i = min(kHarmTileI, h.n1 - i0);
+  const int k_begin = k_chunk * (kHarmTileK * kHarmChunkTiles), k_end = min(h.n3, k_begin + kHarmTileK * kHarmChunkTiles);
+  const double *point_row = h.points + (static_cast<unsigned long long>(j) * h.n1 + i0) * BL_HARM_POINT_DOUBLES;
+  for (int e = t; e < n_i * BL_HARM_POINT_DOUBLES; e += 256) points[e + e / BL_HARM_POINT_DOUBLES] = point_row[e];
+  // reading: lane t takes variable t % 8 of the cell at k0 + (t / 8) % 8 of the tile's rows t / 64, t / 64 + 4, ... - the eight variables of
+  // a cell side by side, the cells of an i along k
+  const int q = t % 8, lk = (t / 8) % kHarmTileK, li0 = t / 64;
+  int variable = h.index[0];
+#pragma unroll
+  for (int s = 1; s < 8; s++) variable = q == s ? h.index[s] : variable;
+  const unsigned long long row_elements = static_cast<unsigned long long>(h.n2) * h.n3 * h.n_prim;   // from an i to the next
+  const unsigned long long read0 = (static_cast<unsigned long long>(i0 + li0) * h.n2 + j) * h.n3 * h.n_prim + variable;
+  const unsigned long long kappa0 = (static_cast<unsigned long long>(i0 + t / kHarmTileK) * h.n2 + j) * h.n3 * h.n_prim + h.index[8];
+  // converting: lane t takes the cell at row t % 32, k0 + t / 32
+  const int ii = t % kHarmTileI, kk = t / kHarmTileI;
+  const int i = i0 + ii;
+  const BlHarmPoint &pt = *reinterpret_cast<const BlHarmPoint *>(points + ii * kHarmPointRow);
+  for (int k0 = k_begin; k0 < k_end; k0 += kHarmTileK) {
+    __syncthreads();   // (the tile's previous cells have been read; the first time: the points are in place after the next one)
+    if (cells != nullptr && k0 + lk < k_end) {   // (cells null: the entropy plane alone is wanted, and read)
+      const unsigned long long at = read0 + static_cast<unsigned long long>(k0 + lk) * h.n_prim;
+#pragma unroll 2   // (two reads in flight per lane: unrolled further, the harm form needs more than the 64 registers that keep eight waves per SIMD)
+      for (int pass = 0; pass < 8; pass++) {
+        const int li = li0 + 4 * pass;
+        if (i0 + li < h.n1) tile[li * kHarmRow + lk * kHarmSlots + q] = bl_plane_cell(h.prims, at + 4 * pass * row_elements, h.f64);
+      }
+    }
+    if (h.kappa != nullptr && i0 + t / kHarmTileK < h.n1 && k0 + t % kHarmTileK < k_end)
+      tile[(t / kHarmTileK) * kHarmRow + (t % kHarmTileK) * kHarmSlots + 8] =
+          bl_plane_cell(h.prims, kappa0 + static_cast<unsigned long long>(k0 + t % kHarmTileK) * h.n_prim, h.f64);
+    __syncthreads();
+    const int k = k0 + kk;
+    if (i >= h.n1 || k >= k_end) continue;
+    const float *mine = tile + ii * kHarmRow + kk * kHarmSlots;
+    const unsigned long long target = (static_cast<unsigned long long>(k) * h.n2 + j) * h.n1 + i;
+    if (h.kappa != nullptr) h.kappa[target] = mine[8];
+    if (cells == nullptr) continue;   // (the entropy plane alone)
+    float in[6], converted[6];
+#pragma unroll
+    for (int s = 0; s < 6; s++) in[s] = mine[2 + s];
+    bl_harm_cell(pt, in, converted);
+    const float rho = mine[0], pgas = mine[1] * h.gamma_minus_one;   // internal energy to pressure, in float as the reader has it
+    if (h.plane_stride == 0) {
+      float4 *out = reinterpret_cast<float4 *>(cells + target * 8);
+      out[0] = make_float4(rho, pgas, converted[0], converted[1]);
+      out[1] = make_float4(converted[2], converted[3], converted[4], converted[5]);
+    } else {
+      cells[target] = rho;
+      cells[h.plane_stride + target] = pgas;
+#pragma unroll
+      for (int s = 0; s < 6; s++) cells[(2 + s) * h.plane_stride + target] = converted[s];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) bl_interleave_cells_kernel(BlCellPlanes src, float *cells, unsigned long long n_cells, int nb_i, int nb_j, int nb_k,
                                                                   const unsigned long long *block_origin, unsigned long long row_stride,
-                                                                  unsigned long long plane_stride) {
+                                                                  unsigned long long plane_stride, BlHarmSource harm) {
+  if (harm.prims != nullptr) {   // (wave-uniform: the form is the launch's)
+    bl_harm_stage(harm, cells);
+    return;
+  }
   const unsigned long long c = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_cells) return;
   unsigned long long target = c, from = c;
@@ -797,9 +890,10 @@ __global__ void __launch_bounds__(256) bl_interleave_cells_kernel(BlCellPlanes s
 
 // bl_set_grid_device's array on the device's side, before anything reads it: device memory of this context's device, and n_elements
 // elements from prim inside one allocation (CheckDeviceCells has held the strides to n_elements)
-void CheckDevicePointer(bl_ctx *ctx, const bl_device_cells &cells) {
-  const Failure refusal{BL_E_ARG, "bl_device_cells: prim must be device memory of the context's device, with n_elements elements inside one allocation; host arrays go "
-                                  "through bl_set_grid."};
+void CheckDevicePointer(bl_ctx *ctx, const bl_device_cells &cells, const char *text = nullptr) {
+  const Failure refusal{BL_E_ARG, text != nullptr ? text
+                                                  : "bl_device_cells: prim must be device memory of the context's device, with n_elements elements inside one allocation; "
+                                                    "host arrays go through bl_set_grid."};
   const size_t element = cells.dtype == BL_CELLS_F64 ? sizeof(double) : sizeof(float);
   if (cells.n_elements < 1 || static_cast<unsigned long long>(cells.n_elements) > (~0ull >> 1) / element) throw refusal;
   hipPointerAttribute_t attributes{};
@@ -826,7 +920,83 @@ void LaunchCellStaging(bl_ctx *ctx, BlCellPlanes src, int count, float *target, 
   src.count = count;
   hipLaunchKernelGGL(bl_interleave_cells_kernel, dim3(static_cast<unsigned int>((pl.n_cells + 255) / 256)), dim3(256), 0, stream, src, target,
                      static_cast<unsigned long long>(pl.n_cells), pl.nb[0], pl.nb[1], pl.nb[2], pl.has_origin ? ctx->grid.d_block_origin.ptr : nullptr, pl.row_stride,
-                     pl.plane_stride);
+                     pl.plane_stride, BlHarmSource{});
+  Check(hipGetLastError(), "cell interleave kernel launch");
+}
+
+// bl_set_grid_device_harm and its kin: the grid the cells belong to, and the caller's array
+struct HarmCells {
+  const bl_harm_grid *grid;
+  const bl_harm_cells *cells;
+};
+
+// What bl_device_cells' checks ask of a harm array before anything is launched (CheckDeviceCells)
+void CheckHarmCells(const bl_harm_grid *grid, const bl_harm_cells *cells) {
+  if (grid == nullptr) throw Failure{BL_E_ARG, "bl_harm_cells: the grid is NULL."};
+  if (cells == nullptr) throw Failure{BL_E_ARG, "bl_harm_cells: the description is NULL."};
+  if (cells->prim == nullptr) throw Failure{BL_E_ARG, "bl_harm_cells: prim is NULL."};
+  if (cells->dtype != BL_CELLS_F32 && cells->dtype != BL_CELLS_F64) throw Failure{BL_E_ARG, "bl_harm_cells: dtype must be BL_CELLS_F32 or BL_CELLS_F64."};
+  if (reinterpret_cast<uintptr_t>(cells->prim) % (cells->dtype == BL_CELLS_F64 ? sizeof(double) : sizeof(float)) != 0)
+    throw Failure{BL_E_ARG, "bl_harm_cells: prim is not aligned to its element type."};
+  const bl_harm_header &h = grid->header;   // (counts within 1 ... 65536 and indices within n_prim: bl_harm_grid_create)
+  int64_t needed = 0;
+  const bool overflow = __builtin_mul_overflow(static_cast<int64_t>(h.n1) * h.n2, static_cast<int64_t>(h.n3) * h.n_prim, &needed);
+  if (overflow || cells->n_elements < needed) throw Failure{BL_E_ARG, "bl_harm_cells: n_elements is smaller than n1 * n2 * n3 * n_prim."};
+}
+
+// The caller's array as bl_device_cells, for the checks and the ordering that read nothing but prim, dtype, n_elements, wait and stream
+bl_device_cells HarmAsDeviceCells(const bl_harm_cells &cells) {
+  bl_device_cells as{};
+  as.prim = cells.prim;
+  as.dtype = cells.dtype;
+  as.wait = cells.wait;
+  as.var_stride = as.block_stride = 1;
+  as.n_elements = cells.n_elements;
+  as.stream = cells.stream;
+  return as;
+}
+constexpr const char *kHarmPointerRefusal = "bl_harm_cells: prim must be device memory of the context's device, with n_elements elements inside one allocation.";
+
+// The grid's point table on the device: uploaded when this context sees the grid for the first time, kept for the cell arrays that follow
+const double *HarmPointsOnDevice(bl_ctx *ctx, const bl_harm_grid &grid, hipStream_t stream) {
+  bl_ctx::Grid &G = ctx->grid;
+  if (G.harm_points_serial != grid.serial) {
+    const size_t count = grid.points.size() * BL_HARM_POINT_DOUBLES;
+    G.harm_points_serial = 0;
+    G.d_harm_points.Ensure(count);
+    Check(hipMemcpyAsync(G.d_harm_points.ptr, grid.points.data(), count * sizeof(double), hipMemcpyHostToDevice, stream), "point table upload");
+    Check(hipStreamSynchronize(stream), "point table upload");
+    G.host_bytes += static_cast<int64_t>(count * sizeof(double));
+    G.harm_points_serial = grid.serial;
+  }
+  return G.d_harm_points.ptr;
+}
+
+// One launch of the staging kernel's harm form on `stream`: the eight variables into `cells` ([cell][8], or with plane_stride eight
+// planes; null: none) and the entropy into `kappa` (null: none)
+void LaunchHarmStaging(bl_ctx *ctx, const HarmCells &harm, float *cells, unsigned long long plane_stride, float *kappa, hipStream_t stream) {
+  const bl_harm_grid &grid = *harm.grid;
+  const bl_harm_header &h = grid.header;
+  const bl_grid_desc &d = grid.desc;
+  BlHarmSource src{};
+  src.points = HarmPointsOnDevice(ctx, grid, stream);
+  src.prims = harm.cells->prim;
+  src.kappa = kappa;
+  src.plane_stride = plane_stride;
+  src.n1 = h.n1; src.n2 = h.n2; src.n3 = h.n3; src.n_prim = h.n_prim;
+  const int index[9] = {d.ind_rho, d.ind_pgas, d.ind_uu1, d.ind_uu2, d.ind_uu3, d.ind_bb1, d.ind_bb2, d.ind_bb3, kappa != nullptr ? d.ind_kappa : 0};
+  for (int q = 0; q < 9; q++) {
+    if (index[q] < 0 || index[q] >= h.n_prim) throw Failure{BL_E_ARG, "bl_harm_cells: a variable index of the grid lies outside n_prim."};
+    src.index[q] = index[q];
+  }
+  src.f64 = harm.cells->dtype == BL_CELLS_F64 ? 1 : 0;
+  src.gamma_minus_one = static_cast<float>(d.plasma_gamma - 1.0);
+  src.i_tiles = static_cast<unsigned int>((h.n1 + kHarmTileI - 1) / kHarmTileI);
+  const unsigned long long k_chunks = (static_cast<unsigned long long>(h.n3) + kHarmTileK * kHarmChunkTiles - 1) / (kHarmTileK * kHarmChunkTiles);
+  const unsigned long long blocks = k_chunks * static_cast<unsigned long long>(h.n2) * src.i_tiles;
+  if (blocks >= (1ull << 24)) throw Failure{BL_E_ARG, "bl_harm_cells: the array has more tiles than one launch takes."};
+  hipLaunchKernelGGL(bl_interleave_cells_kernel, dim3(static_cast<unsigned int>(blocks)), dim3(256), kHarmLdsBytes, stream, BlCellPlanes{}, cells, 0ull, 0, 0, 0,
+                     static_cast<const unsigned long long *>(nullptr), 0ull, 0ull, src);
   Check(hipGetLastError(), "cell interleave kernel launch");
 }
 
@@ -852,12 +1022,20 @@ void WaitForCallerCells(bl_ctx *ctx, const bl_device_cells &cells, hipStream_t s
 
 // The planes of `g` - or, with `device_cells`, of the caller's device array - into `d_cells` as the grid's placement says, on `stream`;
 // returns when the cells are in place (the caller's arrays are borrowed for the duration of bl_set_grid)
-void UploadCellsAs(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_cells, DeviceBuffer<float> &d_cells, hipStream_t stream, bool upload_origin) {
+void UploadCellsAs(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_cells, const HarmCells *harm, DeviceBuffer<float> &d_cells, hipStream_t stream,
+                   bool upload_origin) {
   bl_ctx::Grid &G = ctx->grid;
   const CellPlacement &pl = G.tables.placement;
   const size_t n_cells = pl.n_cells;
   d_cells.Ensure(n_cells * 8);
   BlCellPlanes src{};
+  if (harm != nullptr) {   // (one block: the cells lie [k][j][i], no origins)
+    if (pl.has_origin || n_cells != static_cast<size_t>(g->n_i) * g->n_j * g->n_k) throw Failure{BL_E_ARG, "Bad grid description."};
+    WaitForCallerCells(ctx, *device_cells, stream);
+    LaunchHarmStaging(ctx, *harm, d_cells.ptr, 0, nullptr, stream);
+    Check(hipStreamSynchronize(stream), "grid upload");
+    return;
+  }
   if (device_cells != nullptr) {
     src = DevicePlanes(*device_cells, pl.order, 8);
     WaitForCallerCells(ctx, *device_cells, stream);
@@ -882,7 +1060,7 @@ void UploadCellsAs(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *de
 
 // The one upload step: each table of ctx->grid.tables into its buffer, once; the cells (into the time slice where there is one); then
 // every pointer of BlGridDevice, from buffer base plus offset (BindGridTables)
-void UploadGrid(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_cells, bl_ctx::SlowSlice *slice) {
+void UploadGrid(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_cells, const HarmCells *harm, bl_ctx::SlowSlice *slice) {
   bl_ctx::Grid &G = ctx->grid;
   const GridTables &t = G.tables;
   DeviceBuffer<float> &d_cells = slice != nullptr ? slice->cells : G.d_cells;
@@ -894,8 +1072,12 @@ void UploadGrid(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *devic
     G.host_bytes += static_cast<int64_t>(count * sizeof(*data));
   };
   EnsureStreams(ctx);
-  UploadCellsAs(ctx, g, device_cells, d_cells, ctx->stream, true);
-  if (t.code_kappa && device_cells != nullptr) {
+  UploadCellsAs(ctx, g, device_cells, harm, d_cells, ctx->stream, true);
+  if (t.code_kappa && harm != nullptr) {   // the entropy where the harm array has it, through the same transpose
+    d_kappa.Ensure(t.placement.n_cells);
+    LaunchHarmStaging(ctx, *harm, nullptr, 0, d_kappa.ptr, ctx->stream);
+    Check(hipStreamSynchronize(ctx->stream), "grid upload");
+  } else if (t.code_kappa && device_cells != nullptr) {
     // the caller's plane where it lies, through the staging kernel: to the blocks' places in a merged array, else cell by cell
     d_kappa.Ensure(t.placement.n_cells);
     LaunchCellStaging(ctx, DevicePlanes(*device_cells, &g->ind_kappa, 1), 1, d_kappa.ptr, ctx->stream);
@@ -921,11 +1103,16 @@ int FailBetweenRenders(bl_ctx *ctx, const Failure &failure) {   // (last_error i
 
 // bl_set_grid, and bl_set_grid_slice with the time slice the cells go to. The cells come from the host planes g->prim, or with
 // `device_cells` from the caller's device array (bl_set_grid_device, bl_set_grid_slice_device): everything else is one path.
-int SetGrid(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_cells, bl_ctx::SlowSlice *slice) {
+int SetGrid(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_cells, bl_ctx::SlowSlice *slice, const HarmCells *harm = nullptr) {
   bl_ctx::Grid &G = ctx->grid;
   try {
     G.host_bytes = 0;
-    if (device_cells != nullptr) CheckDeviceCells(*g, ctx->params.plasma_model == BL_PLASMA_CODE_KAPPA, device_cells);
+    if (harm != nullptr) {
+      CheckHarmCells(harm->grid, harm->cells);
+      // (the grid chose its variables, the entropy among them or not, under its own parameters: they must be this context's)
+      if (harm->grid->code_kappa != (ctx->params.plasma_model == BL_PLASMA_CODE_KAPPA))
+        throw Failure{BL_E_ARG, "bl_harm_grid: made with another plasma_model than the context's (one of them reads the electron entropy, plasma_model = code_kappa)."};
+    } else if (device_cells != nullptr) CheckDeviceCells(*g, ctx->params.plasma_model == BL_PLASMA_CODE_KAPPA, device_cells);
     if (ctx->device == BL_DEVICE_NONE) throw Failure{BL_E_DEVICE, "Host-only context: no HIP device selected (the hot path has no CPU fallback)."};
     if (ctx->params.model_type != BL_MODEL_SIMULATION) throw Failure{BL_E_STATE, "bl_set_grid called in formula mode."};
     if (ctx->params.slow_light_on && slice == nullptr)
@@ -933,7 +1120,7 @@ int SetGrid(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_ce
     ValidateGridDescription(*g);
     if (device_cells == nullptr && g->prim == nullptr) throw Failure{BL_E_ARG, "Bad grid description."};
     Check(hipSetDevice(ctx->device), "hipSetDevice");
-    if (device_cells != nullptr) CheckDevicePointer(ctx, *device_cells);
+    if (device_cells != nullptr) CheckDevicePointer(ctx, *device_cells, harm != nullptr ? kHarmPointerRefusal : nullptr);
     // The next snapshot of a series - the geometry in place, to the bit, and the same variables: only the cells are new. They go up on
     // a stream of their own into the second cell array while a render of this context may be running on another host thread, and the
     // arrays change places once that render has ended. (With electron entropy from the grid there is a second array to double: the
@@ -944,7 +1131,7 @@ int SetGrid(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_ce
         && std::equal(order_now, order_now + 8, G.tables.placement.order) && g->n_var == G.meta.n_var
         && g->plasma_gamma == G.meta.plasma_gamma && g->plasma_gamma_i == G.meta.plasma_gamma_i && g->plasma_gamma_e == G.meta.plasma_gamma_e) {
       if (G.stream_upload == nullptr) Check(hipStreamCreateWithFlags(&G.stream_upload, hipStreamNonBlocking), "hipStreamCreate");
-      UploadCellsAs(ctx, g, device_cells, G.d_cells_back, G.stream_upload, false);
+      UploadCellsAs(ctx, g, device_cells, harm, G.d_cells_back, G.stream_upload, false);
       std::lock_guard<std::mutex> guard(ctx->render_lock);
       std::swap(G.d_cells, G.d_cells_back);
       G.dev.cells = G.d_cells.ptr;
@@ -961,7 +1148,7 @@ int SetGrid(bl_ctx *ctx, const bl_grid_desc *g, const bl_device_cells *device_ce
     const unsigned long long geometry = slice == nullptr ? tables.geometry : 0;   // (slow light locates per snapshot: no located samples are kept)
     tables.geometry = 0;
     G.tables = std::move(tables);
-    UploadGrid(ctx, g, device_cells, slice);
+    UploadGrid(ctx, g, device_cells, harm, slice);
     G.tables.kappa = std::vector<float>();   // (as large as a cell plane, and on the device now)
     G.tables.geometry = geometry;
     G.meta = *g;
@@ -1001,13 +1188,13 @@ int64_t bl_grid_host_bytes(const bl_ctx *ctx) { return ctx != nullptr ? ctx->gri
 int bl_context_device(const bl_ctx *ctx) { return ctx != nullptr ? ctx->device : BL_DEVICE_NONE; }
 
 namespace {
-int SetGridSlice(bl_ctx *ctx, int slice, const bl_grid_desc *g, const bl_device_cells *device_cells, double time) {
+int SetGridSlice(bl_ctx *ctx, int slice, const bl_grid_desc *g, const bl_device_cells *device_cells, double time, const HarmCells *harm = nullptr) {
   const bl_params &p = ctx->params;
   if (p.model_type != BL_MODEL_SIMULATION || !p.slow_light_on) return FailBetweenRenders(ctx, Failure{BL_E_STATE, "bl_set_grid_slice needs slow_light_on = true."});
   if (slice < 0 || slice >= p.slow_chunk_size) return FailBetweenRenders(ctx, Failure{BL_E_ARG, "Time slice index outside slow_chunk_size."});
   ctx->slow_slices.resize(p.slow_chunk_size);
   bl_ctx::SlowSlice &target = ctx->slow_slices[slice];
-  const int rc = SetGrid(ctx, g, device_cells, &target);
+  const int rc = SetGrid(ctx, g, device_cells, &target, harm);
   if (rc != BL_OK) return rc;
   target.time = time;
   target.set = true;
@@ -1025,6 +1212,62 @@ int bl_set_grid_slice_device(bl_ctx *ctx, int slice, const bl_grid_desc *g, cons
   if (cells == nullptr) return RefuseNoCells(ctx, g);
   return SetGridSlice(ctx, slice, g, cells, time);
 }
+
+// The harm calls: the grid's own description (for simulation_coord = fmks with its look-up table built), the caller's array in place of planes
+int bl_set_grid_device_harm(bl_ctx *ctx, bl_harm_grid *grid, const bl_harm_cells *cells) {
+  if (ctx == nullptr) return BL_E_ARG;
+  try {
+    CheckHarmCells(grid, cells);
+  } catch (const Failure &failure) {
+    return FailBetweenRenders(ctx, failure);
+  }
+  const bl_device_cells as = HarmAsDeviceCells(*cells);
+  const HarmCells harm{grid, cells};
+  return SetGrid(ctx, bl_harm_grid_desc(grid, 0), &as, nullptr, &harm);
+}
+
+int bl_set_grid_slice_device_harm(bl_ctx *ctx, int slice, bl_harm_grid *grid, const bl_harm_cells *cells, double time) {
+  if (ctx == nullptr) return BL_E_ARG;
+  try {
+    CheckHarmCells(grid, cells);
+  } catch (const Failure &failure) {
+    return FailBetweenRenders(ctx, failure);
+  }
+  const bl_device_cells as = HarmAsDeviceCells(*cells);
+  const HarmCells harm{grid, cells};
+  return SetGridSlice(ctx, slice, bl_harm_grid_desc(grid, 0), &as, time, &harm);
+}
+
+int bl_harm_convert_device(bl_ctx *ctx, const bl_harm_grid *grid, const bl_harm_cells *cells, float *out_planes) {
+  if (ctx == nullptr) return BL_E_ARG;
+  try {
+    CheckHarmCells(grid, cells);
+    if (out_planes == nullptr || reinterpret_cast<uintptr_t>(out_planes) % sizeof(float) != 0)
+      throw Failure{BL_E_ARG, "bl_harm_convert_device: out_planes is NULL or not aligned to float."};
+    if (ctx->device == BL_DEVICE_NONE) throw Failure{BL_E_DEVICE, "Host-only context: no HIP device selected (the hot path has no CPU fallback)."};
+    Check(hipSetDevice(ctx->device), "hipSetDevice");
+    const bl_device_cells as = HarmAsDeviceCells(*cells);
+    CheckDevicePointer(ctx, as, kHarmPointerRefusal);
+    const bl_harm_header &h = grid->header;
+    const unsigned long long n_cells = static_cast<unsigned long long>(h.n1) * h.n2 * h.n3;
+    bl_device_cells target{};
+    target.prim = out_planes;
+    target.dtype = BL_CELLS_F32;
+    target.n_elements = static_cast<int64_t>(n_cells * (grid->code_kappa ? 9 : 8));
+    CheckDevicePointer(ctx, target, "bl_harm_convert_device: out_planes must be device memory of the context's device holding every plane inside one allocation.");
+    EnsureStreams(ctx);
+    std::lock_guard<std::mutex> guard(ctx->render_lock);   // (the point table is the context's: not beside a render or another staging)
+    WaitForCallerCells(ctx, as, ctx->stream);
+    const HarmCells harm{grid, cells};
+    LaunchHarmStaging(ctx, harm, out_planes, n_cells, grid->code_kappa ? out_planes + 8 * n_cells : nullptr, ctx->stream);
+    Check(hipStreamSynchronize(ctx->stream), "primitive conversion");
+  } catch (const Failure &failure) {
+    return FailBetweenRenders(ctx, failure);
+  }
+  return BL_OK;
+}
+
+size_t bl_harm_cells_sizeof(void) { return sizeof(bl_harm_cells); }
 
 int bl_shift_grid_slices(bl_ctx *ctx, int count) {
   if (ctx == nullptr) return BL_E_ARG;

@@ -249,6 +249,8 @@ struct bl_ctx {
     hipStream_t stream_upload = nullptr;
     hipEvent_t source_event = nullptr; // bl_set_grid_device with wait: recorded on the caller's stream, awaited by the staging stream
     int64_t host_bytes = 0;            // what the last bl_set_grid* call copied from host memory (bl_grid_host_bytes)
+    DeviceBuffer<double> d_harm_points;            // bl_set_grid_device_harm: the point table of the grid whose serial is ...
+    unsigned long long harm_points_serial = 0;     // ... this one (0: none)
   } grid;
   bool sample_checkpoint_saved = false;   // checkpoint_sample_save: written with the first image only (radiation_integrator.cpp:699-704)
 

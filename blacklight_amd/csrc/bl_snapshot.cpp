@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/blacklight_amd.h"
+#include "bl_harm.h"
 #include "bl_internal.h"
 #include "blmath.h"
 
@@ -494,11 +495,9 @@ constexpr double kAngularDomainTolerance = 0.1;         // simulation_reader.hpp
 
 // ------------------------------------------------------------------------------------------------
 
-// The last FMKS look-up table built in this process and what it was built from (ReadIharm3d)
-static std::mutex g_sks_map_mutex;
-static std::vector<double> g_sks_map_key, g_sks_map;
-
 struct bl_snapshot {
+  bool raw = false;                // bl_snapshot_open_raw: `prim` is the file's prims as they lie, [n1][n2][n3][n_prim]; desc.prim is NULL
+  bl_harm_header harm_header{};    // ... and what the file's header says
   bl_grid_desc desc{};
   std::vector<float> prim;
   std::vector<double> coords[6];   // x1f x2f x3f x1v x2v x3v
@@ -921,7 +920,10 @@ void ReadAthenaK(const bl_params &p, int file_number, bl_snapshot *s) {
 // FMKS / MMKS dumps read with simulation_coord = fmks keep their native coordinates and get the reader's SKS -> FMKS
 // look-up table and bounds instead (ConvertCoordinates, GenerateSKSMap, GetSKSCoordinates, SetJacobianFactors:
 // simulation_geometry.cpp:36-57, :321-419, :427-483).
-void ReadIharm3d(const bl_params &p, int file_number, bl_snapshot *s) {
+// What the reader makes of the header - checks, coordinates, map, variable indices - and the conversion of a cell are bl_harm.h's, run
+// here between the reads of the file in the order the reference has them. `raw` (bl_snapshot_open_raw): the header as a struct and the
+// file's prims as they lie, nothing transposed or converted and no look-up table built.
+void ReadIharm3d(const bl_params &p, int file_number, bl_snapshot *s, bool raw) {
   s->file = p.simulation_file.s;
   if (file_number >= 0) s->file = FormatFilename(s->file, file_number);
   const Hdf5File file(s->file);
@@ -935,227 +937,96 @@ void ReadIharm3d(const bl_params &p, int file_number, bl_snapshot *s) {
     if (v.empty()) Fail("Array dimension mismatch.");
     return v[0];
   };
-  s->time = scalar("t");
-  // metric (:364-428)
-  const std::vector<std::string> metric_names = DecodeStrings(file.Dataset("header/metric"));
-  if (metric_names.empty()) Fail("Array dimension mismatch.");
-  const std::string metric = metric_names[0];
-  if (p.simulation_coord != BL_COORD_SKS && p.simulation_coord != BL_COORD_FMKS) Fail("Invalid simulation_coord for Harm format.");
-  std::string metric_lower = metric;
-  for (char &c : metric_lower) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
-  if (metric != "MKS" && metric != "MMKS" && metric != "FMKS")
-    Warn(s, "Given metric mks does not match file value of " + metric + "; ignoring the latter.");
-  const double metric_a = scalar("header/geom/" + metric_lower + "/a");
-  const double metric_h = scalar("header/geom/" + metric_lower + "/hslope");
-  if (metric_a != p.simulation_a) {
-    std::ostringstream message;
-    message << "Given spin of " << p.simulation_a << " does not match file value of " << metric_a << "; ignoring the latter.";
-    Warn(s, message.str());
-  }
-  // FMKS / MMKS geometry (:396-427)
-  const bool fmks = p.simulation_coord == BL_COORD_FMKS;
-  if (fmks && metric != "MMKS" && metric != "FMKS")   // the reference would build its map from uninitialised parameters
-    Fail("simulation_coord = fmks needs a file whose header/metric is FMKS or MMKS.", BL_E_UNSUPPORTED);
-  double metric_r_in = 0.0, metric_poly_xt = 0.0, metric_poly_alpha = 0.0, metric_mks_smooth = 0.0, metric_derived_poly_norm = 0.0;
-  if (metric == "MMKS" || metric == "FMKS") {
-    bool found = true;
-    try {
-      metric_r_in = scalar("header/geom/" + metric_lower + "/r_in");
-    } catch (const ReadFailure &) {
-      found = false;
-    }
-    if (!found) {
+  bl_harm_grid grid;
+  grid.params = p;
+  grid.desc = s->desc;   // (the adiabatic indices the input gives: ReaderSetup)
+  bl_harm_header &h = grid.header;
+  try {
+    s->time = scalar("t");
+    // metric (:364-428)
+    const std::vector<std::string> metric_names = DecodeStrings(file.Dataset("header/metric"));
+    if (metric_names.empty()) Fail("Array dimension mismatch.");
+    const std::string metric = metric_names[0];
+    // (before the reads below, as the reference has it; CheckMetric says the same of a header that comes from no file)
+    if (p.simulation_coord != BL_COORD_SKS && p.simulation_coord != BL_COORD_FMKS) Fail("Invalid simulation_coord for Harm format.");
+    std::string metric_lower = metric;
+    for (char &c : metric_lower) c = static_cast<char>(std::tolower(static_cast<unsigned char>(c)));
+    if (metric != "MKS" && metric != "MMKS" && metric != "FMKS")
+      Warn(s, "Given metric mks does not match file value of " + metric + "; ignoring the latter.");
+    h.metric = metric == "MMKS" || metric == "FMKS" ? BL_HARM_FMKS : BL_HARM_MKS;
+    h.a = scalar("header/geom/" + metric_lower + "/a");
+    h.hslope = scalar("header/geom/" + metric_lower + "/hslope");
+    blharm::CheckMetric(&grid);
+    // FMKS / MMKS geometry (:396-427)
+    if (h.metric == BL_HARM_FMKS) {
+      bool found = true;
       try {
-        metric_r_in = scalar("header/geom/" + metric_lower + "/Rin");
+        h.r_in = scalar("header/geom/" + metric_lower + "/r_in");
       } catch (const ReadFailure &) {
-        Fail("Unable to identify r_in parameter for iharm3d-format file.");
+        found = false;
       }
-    }
-    metric_poly_xt = scalar("header/geom/" + metric_lower + "/poly_xt");
-    metric_poly_alpha = scalar("header/geom/" + metric_lower + "/poly_alpha");
-    metric_mks_smooth = scalar("header/geom/" + metric_lower + "/mks_smooth");
-    metric_derived_poly_norm = (metric_poly_alpha + 1.0) * bl_pow(metric_poly_xt, metric_poly_alpha);
-    metric_derived_poly_norm = 0.5 * kPi * metric_derived_poly_norm / (metric_derived_poly_norm + 1.0);
-  }
-  // SimulationReader::GetSKSCoordinates (simulation_geometry.cpp:427-443) and SetJacobianFactors (:451-483), FMKS branches
-  auto sks_coordinates = [&](double x1, double x2, double *r, double *theta) {
-    *r = bl_exp(x1);
-    const double y = 2.0 * x2 - 1.0;
-    const double theta_g = kPi * x2 + (1.0 - metric_h) / 2.0 * bl_sin(2.0 * kPi * x2);
-    const double theta_j = 0.5 * kPi + metric_derived_poly_norm * y * (1.0 + bl_pow(y / metric_poly_xt, metric_poly_alpha) / (metric_poly_alpha + 1.0));
-    *theta = theta_g + bl_exp(metric_mks_smooth * (bl_log(metric_r_in) - x1)) * (theta_j - theta_g);
-  };
-  auto fmks_jacobian = [&](double x1, double x2, double *dr_dx1, double *dth_dx1, double *dth_dx2) {
-    *dr_dx1 = bl_exp(x1);
-    const double var_a = bl_exp(metric_mks_smooth * (bl_log(metric_r_in) - x1));
-    const double var_b = kPi * (0.5 - x2);
-    const double var_c = bl_pow((2.0 * x2 - 1.0) / metric_poly_xt, metric_poly_alpha);
-    const double var_d = 1.0 + metric_poly_alpha;
-    const double var_e = metric_derived_poly_norm * (1.0 + var_c / var_d);
-    const double var_f = var_e * (2.0 * x2 - 1.0);
-    const double var_g = -0.5 * (1.0 - metric_h) * bl_sin(2.0 * kPi * x2);
-    *dth_dx1 = -metric_mks_smooth * var_a * (var_b + var_f + var_g);
-    const double var_h = kPi + (1.0 - metric_h) * kPi * bl_cos(2.0 * kPi * x2);
-    const double var_i = -kPi + 2.0 * var_e;
-    const double var_j = 2.0 * metric_derived_poly_norm * metric_poly_alpha * var_c / var_d;
-    const double var_k = -(1.0 - metric_h) * kPi * bl_cos(2.0 * kPi * x2);
-    *dth_dx2 = var_h + var_a * (var_i + var_j + var_k);
-  };
-
-  // coordinates (:622-656) and their conversion to r, theta (simulation_geometry.cpp:62-81)
-  const long n[3] = {integer("header/n1"), integer("header/n2"), integer("header/n3")};
-  std::vector<double> x2v_alt;
-  for (int a = 0; a < 3; a++) {
-    if (n[a] < 1 || n[a] > 65536) Fail("Array dimension mismatch.");
-    const double start = scalar("header/geom/startx" + std::to_string(a + 1)), dx = scalar("header/geom/dx" + std::to_string(a + 1));
-    std::vector<double> &xf = s->coords[a], &xv = s->coords[3 + a];
-    xf.assign(n[a] + 1, 0.0);
-    xv.assign(n[a], 0.0);
-    xf[0] = start;
-    for (long i = 0; i < n[a]; i++) {
-      xf[i + 1] = start + static_cast<double>(i + 1) * dx;
-      xv[i] = 0.5 * (xf[i] + xf[i + 1]);
-    }
-  }
-  x2v_alt = s->coords[4];
-  if (fmks) {
-    // ConvertCoordinates, FMKS case (simulation_geometry.cpp:36-57): the coordinates stay native; the map from (r, theta)
-    // to (x^1, x^2) and the grid's bounds in (r, theta, phi) are what the sampler works with. GenerateSKSMap (:321-419):
-    // 2048 x 2048 points, x^2 by bisection on theta(x^1, x^2) to 1e-8.
-    const int map_n1 = 2048, map_n2 = 2048, max_iter = 1000;
-    const double tol = 1.0e-8;
-    const double r_in = bl_exp(s->coords[0][0]), r_out = bl_exp(s->coords[0][n[0]]);
-    const double dr = (r_out - r_in) / (map_n1 - 1), dtheta = kPi / (map_n2 - 1);
-    // (The files of a series share their geometry - slow light opens a window of them - and the map is 4 million bisections:
-    // the last map built in this process is kept with everything it was built from, and copied when those numbers come again.)
-    const std::vector<double> map_key = {r_in, r_out, metric_h, metric_r_in, metric_poly_xt, metric_poly_alpha, metric_mks_smooth};
-    bool map_cached = false;
-    {
-      std::lock_guard<std::mutex> lock(g_sks_map_mutex);
-      if (g_sks_map_key == map_key && !g_sks_map.empty()) {
-        s->sks_map = g_sks_map;
-        map_cached = true;
-      }
-    }
-    if (!map_cached) s->sks_map.assign(static_cast<size_t>(2) * map_n2 * map_n1, 0.0);
-    double *map_x1 = s->sks_map.data(), *map_x2 = s->sks_map.data() + static_cast<size_t>(map_n2) * map_n1;
-    // (columns are independent: spread over the host's threads; the reference fills the map serially)
-    auto fill_columns = [&](int i_begin, int i_end) {
-    for (int i = i_begin; i < i_end; ++i) {
-      const double r = r_in + i * dr;
-      const double x1 = bl_log(r);
-      for (int j = 0; j < map_n2; ++j) {
-        const double theta = std::min(j * dtheta, kPi);
-        double x2 = 0.5;
-        if (theta > tol && std::abs(kPi - theta) > tol) {
-          double x2_a = 0.0, x2_b = 1.0;
-          x2 = (x2_b + x2_a) / 2.0;
-          double temp_r, theta_a = 0.0, theta_b = kPi, theta_c = kPi / 2.0;
-          sks_coordinates(x1, x2_a, &temp_r, &theta_a);
-          sks_coordinates(x1, x2_b, &temp_r, &theta_b);
-          for (int iter = 0; iter < max_iter; iter++) {
-            sks_coordinates(x1, x2, &temp_r, &theta_c);
-            if ((theta_c - theta) * (theta_b - theta) < 0.0) {
-              theta_a = theta_c;
-              x2_a = x2;
-            } else {
-              theta_b = theta_c;
-              x2_b = x2;
-            }
-            x2 = (x2_a + x2_b) / 2.0;
-            if (std::abs(theta - theta_c) < tol) break;
-          }
-          (void)theta_a;
-        } else if (theta < tol) {
-          x2 = 0.0;
-        } else if (theta > kPi - tol) {
-          x2 = 1.0;
+      if (!found) {
+        try {
+          h.r_in = scalar("header/geom/" + metric_lower + "/Rin");
+        } catch (const ReadFailure &) {
+          Fail("Unable to identify r_in parameter for iharm3d-format file.");
         }
-        map_x1[static_cast<size_t>(j) * map_n1 + i] = x1;
-        map_x2[static_cast<size_t>(j) * map_n1 + i] = x2;
       }
+      h.poly_xt = scalar("header/geom/" + metric_lower + "/poly_xt");
+      h.poly_alpha = scalar("header/geom/" + metric_lower + "/poly_alpha");
+      h.mks_smooth = scalar("header/geom/" + metric_lower + "/mks_smooth");
     }
-    };
-    if (!map_cached) {
-      const int n_threads = std::max(1, std::min(64, static_cast<int>(std::thread::hardware_concurrency())));
-      std::vector<std::thread> workers;
-      for (int t = 0; t < n_threads; t++)
-        workers.emplace_back(fill_columns, static_cast<int>(static_cast<long>(map_n1) * t / n_threads),
-                             static_cast<int>(static_cast<long>(map_n1) * (t + 1) / n_threads));
-      for (std::thread &w : workers) w.join();
-      std::lock_guard<std::mutex> lock(g_sks_map_mutex);
-      g_sks_map_key = map_key;
-      g_sks_map = s->sks_map;
+    // coordinates (:622-656) and their conversion (simulation_geometry.cpp:36-81)
+    const long n[3] = {integer("header/n1"), integer("header/n2"), integer("header/n3")};
+    for (int a = 0; a < 3; a++) {
+      if (n[a] < 1 || n[a] > 65536) Fail("Array dimension mismatch.");
+      h.startx[a] = scalar("header/geom/startx" + std::to_string(a + 1));
+      h.dx[a] = scalar("header/geom/dx" + std::to_string(a + 1));
     }
-    bl_grid_desc &gd = s->desc;
-    gd.sks_map = s->sks_map.data();
-    gd.sks_map_n1 = map_n1;
-    gd.sks_map_n2 = map_n2;
-    gd.sks_map_r_in = r_in;
-    gd.sks_map_dr = dr;
-    gd.sks_map_dtheta = dtheta;
-    double r_val, theta_val;
-    sks_coordinates(s->coords[0][0], 0.0, &r_val, &theta_val);
-    gd.simulation_bounds[0] = r_val;
-    gd.simulation_bounds[2] = theta_val;
-    gd.simulation_bounds[4] = 0.0;
-    sks_coordinates(s->coords[0][n[0]], 1.0, &r_val, &theta_val);
-    gd.simulation_bounds[1] = r_val;
-    gd.simulation_bounds[3] = theta_val;
-    gd.simulation_bounds[5] = 2.0 * kPi;
-  } else {
-    for (double &x : s->coords[0]) x = bl_exp(x);
-    for (double &x : s->coords[3]) x = bl_exp(x);
-    for (double &x : s->coords[1]) x = kPi * x + (1.0 - metric_h) / 2.0 * bl_sin(2.0 * kPi * x);
-    for (double &x : s->coords[4]) x = kPi * x + (1.0 - metric_h) / 2.0 * bl_sin(2.0 * kPi * x);
-  }
+    h.n1 = static_cast<int32_t>(n[0]);
+    h.n2 = static_cast<int32_t>(n[1]);
+    h.n3 = static_cast<int32_t>(n[2]);
+    blharm::BuildCoordinates(&grid);
+    if (!raw) blharm::BuildSksMap(&grid);
 
-  // VerifyVariablesHarm
-  const int n_prim = integer("header/n_prim");
-  const std::vector<std::string> names = DecodeStrings(file.Dataset("header/prim_names"));
-  if (n_prim != static_cast<int>(names.size())) Fail("Inconsistency in number of primitive variables.");
-  auto locate = [&](const std::string &name, const char *message) {
-    for (int v = 0; v < n_prim; v++)
-      if (names[v] == name) return v;
-    Fail(message);
-  };
-  bl_grid_desc &d = s->desc;
-  d.ind_rho = locate("RHO", "Unable to locate \"RHO\" slice of \"prims\" in data file.");
-  d.ind_pgas = locate("UU", "Unable to locate \"UU\" slice of \"prims\" in data file.");
-  d.ind_kappa = 0;
-  if (p.plasma_model == BL_PLASMA_CODE_KAPPA)
-    d.ind_kappa = locate(p.simulation_kappa_name.s, "Unable to locate electron entropy slice of \"prims\" in data file.");
-  d.ind_uu1 = locate("U1", "Unable to locate \"U1\" slice of \"prims\" in data file.");
-  d.ind_uu2 = locate("U2", "Unable to locate \"U2\" slice of \"prims\" in data file.");
-  d.ind_uu3 = locate("U3", "Unable to locate \"U3\" slice of \"prims\" in data file.");
-  d.ind_bb1 = locate("B1", "Unable to locate \"B1\" slice of \"prims\" in data file.");
-  d.ind_bb2 = locate("B2", "Unable to locate \"B2\" slice of \"prims\" in data file.");
-  d.ind_bb3 = locate("B3", "Unable to locate \"B3\" slice of \"prims\" in data file.");
-  auto adiabatic_index = [&](const char *path, bool given, double *value, const char *what, const char *missing) {
-    bool found = true;
-    double in_file = 0.0;
-    try {
-      in_file = scalar(path);
-    } catch (const ReadFailure &) {
-      found = false;
+    // VerifyVariablesHarm
+    const int n_prim = integer("header/n_prim");
+    const std::vector<std::string> names = DecodeStrings(file.Dataset("header/prim_names"));
+    if (n_prim != static_cast<int>(names.size())) Fail("Inconsistency in number of primitive variables.");
+    h.n_prim = n_prim;
+    auto locate = [&](const std::string &name) {
+      for (int v = 0; v < n_prim; v++)
+        if (names[v] == name) return v;
+      return -1;
+    };
+    h.ind_rho = locate("RHO");
+    h.ind_uu = locate("UU");
+    h.ind_kappa = p.plasma_model == BL_PLASMA_CODE_KAPPA ? locate(p.simulation_kappa_name.s) : -1;
+    h.ind_u1 = locate("U1"); h.ind_u2 = locate("U2"); h.ind_u3 = locate("U3");
+    h.ind_b1 = locate("B1"); h.ind_b2 = locate("B2"); h.ind_b3 = locate("B3");
+    auto optional_scalar = [&](const char *path) {
+      try {
+        return scalar(path);
+      } catch (const ReadFailure &) {
+        return std::nan("");
+      }
+    };
+    h.gam = optional_scalar("header/gam");
+    h.gam_p = h.gam_e = std::nan("");
+    if (p.plasma_model == BL_PLASMA_TI_TE_BETA && !p.plasma_use_p) {
+      h.gam_p = optional_scalar("header/gam_p");
+      h.gam_e = optional_scalar("header/gam_e");
     }
-    if (!found) {
-      if (!given) Fail(missing);
-      return;
-    }
-    if (!given) {
-      *value = in_file;
-    } else if (*value != in_file) {
-      std::ostringstream message;
-      message << "Given " << what << " adiabatic index of " << *value << " does not match file value of " << in_file << "; ignoring the latter.";
-      Warn(s, message.str());
-    }
-  };
-  adiabatic_index("header/gam", p.has[BL_P_plasma_gamma] != 0, &d.plasma_gamma, "total", "Could not find total adiabatic index in input or data file.");
-  if (p.plasma_model == BL_PLASMA_TI_TE_BETA && !p.plasma_use_p) {
-    adiabatic_index("header/gam_p", p.has[BL_P_plasma_gamma_i] != 0, &d.plasma_gamma_i, "ion", "Could not find ion adiabatic index in input or data file.");
-    adiabatic_index("header/gam_e", p.has[BL_P_plasma_gamma_e] != 0, &d.plasma_gamma_e, "electron", "Could not find electron adiabatic index in input or data file.");
+    blharm::CheckVariables(&grid);
+  } catch (const blharm::Refusal &refusal) {
+    s->warnings += grid.warnings;
+    Fail(refusal.message.c_str(), refusal.code);
   }
+  s->warnings += grid.warnings;
+  const long n[3] = {h.n1, h.n2, h.n3};
+  const int n_prim = h.n_prim;
+  bl_grid_desc &d = s->desc;
+  d = grid.desc;
 
   // cell data: [n1][n2][n3][n_prim] -> [n_prim][1][n3][n2][n1], u -> p (:792-805)
   const size_t cells = static_cast<size_t>(n[0]) * n[1] * n[2];
@@ -1165,91 +1036,33 @@ void ReadIharm3d(const bl_params &p, int file_number, bl_snapshot *s) {
   if (dims.size() != 4 || dims[0] != static_cast<uint64_t>(n[0]) || dims[1] != static_cast<uint64_t>(n[1])
       || dims[2] != static_cast<uint64_t>(n[2]) || dims[3] != static_cast<uint64_t>(n_prim))
     Fail("Array dimension mismatch.");
-  s->prim.assign(cells * n_prim, 0.0f);
-  auto at = [&](int v, long k, long j, long i) -> float & { return s->prim[((static_cast<size_t>(v) * n[2] + k) * n[1] + j) * n[0] + i]; };
-  for (int v = 0; v < n_prim; v++)
+  if (raw) {
+    s->prim = std::move(transposed);
+    s->raw = true;
+    s->harm_header = h;
+  } else {
+    s->prim.assign(cells * n_prim, 0.0f);
+    auto at = [&](int v, long k, long j, long i) -> float & { return s->prim[((static_cast<size_t>(v) * n[2] + k) * n[1] + j) * n[0] + i]; };
+    for (int v = 0; v < n_prim; v++)
+      for (long k = 0; k < n[2]; k++)
+        for (long j = 0; j < n[1]; j++)
+          for (long i = 0; i < n[0]; i++) at(v, k, j, i) = transposed[((static_cast<size_t>(i) * n[1] + j) * n[2] + k) * n_prim + v];
+    const float gamma_minus_one = static_cast<float>(d.plasma_gamma - 1.0);
+    for (size_t c = 0; c < cells; c++) s->prim[static_cast<size_t>(d.ind_pgas) * cells + c] *= gamma_minus_one;
+    // ConvertPrimitives3 (simulation_geometry.cpp:95-230): the point's part once per (i, j), the cell's part for every k
+    blharm::BuildPoints(&grid);
+    const int vector_index[6] = {d.ind_uu1, d.ind_uu2, d.ind_uu3, d.ind_bb1, d.ind_bb2, d.ind_bb3};
     for (long k = 0; k < n[2]; k++)
       for (long j = 0; j < n[1]; j++)
-        for (long i = 0; i < n[0]; i++) at(v, k, j, i) = transposed[((static_cast<size_t>(i) * n[1] + j) * n[2] + k) * n_prim + v];
-  const float gamma_minus_one = static_cast<float>(d.plasma_gamma - 1.0);
-  for (size_t c = 0; c < cells; c++) s->prim[static_cast<size_t>(d.ind_pgas) * cells + c] *= gamma_minus_one;
-
-  // ConvertPrimitives3 (simulation_geometry.cpp:95-230) for modified Kerr-Schild coordinates: the Jacobian is
-  // dr/dx1 = exp(x1), dtheta/dx1 = 0, dtheta/dx2 = pi + (1 - h) pi cos(2 pi x2) (:440-468)
-  const double a = p.simulation_a;
-  for (long k = 0; k < n[2]; k++)
-    for (long j = 0; j < n[1]; j++)
-      for (long i = 0; i < n[0]; i++) {
-        double r = s->coords[3][i], th = s->coords[4][j];
-        double x1, x2, dr_dx1, dth_dx1, dth_dx2;
-        if (fmks) {   // the cell centres are native coordinates (:118-124); Jacobian of the FMKS map (:463-475)
-          x1 = r;
-          x2 = th;
-          sks_coordinates(x1, x2, &r, &th);
-          fmks_jacobian(x1, x2, &dr_dx1, &dth_dx1, &dth_dx2);
-        } else {
-          x1 = bl_log(r);
-          x2 = x2v_alt[j];
-          dr_dx1 = bl_exp(x1);
-          dth_dx1 = 0.0;
-          dth_dx2 = kPi + (1.0 - metric_h) * kPi * bl_cos(2.0 * kPi * x2);
+        for (long i = 0; i < n[0]; i++) {
+          float in[6], out[6];
+          for (int q = 0; q < 6; q++) in[q] = at(vector_index[q], k, j, i);
+          bl_harm_cell(grid.points[static_cast<size_t>(j) * n[0] + i], in, out);
+          for (int q = 0; q < 6; q++) at(vector_index[q], k, j, i) = out[q];
         }
-        const double sth = bl_sin(th), cth = bl_cos(th);
-        const double uu1 = at(d.ind_uu1, k, j, i), uu2 = at(d.ind_uu2, k, j, i), uu3 = at(d.ind_uu3, k, j, i);
-        const double bb1 = at(d.ind_bb1, k, j, i), bb2 = at(d.ind_bb2, k, j, i), bb3 = at(d.ind_bb3, k, j, i);
-        const double sigma = r * r + a * a * cth * cth;
-        const double f = 2.0 * r / sigma;
-        const double g_tr = f, g_tth = 0.0, g_tph = -a * f * sth * sth;
-        const double g_rr = 1.0 + f, g_rth = 0.0, g_rph = -a * (1.0 + f) * sth * sth;
-        const double g_thth = sigma, g_thph = 0.0;
-        const double g_phph = (r * r + a * a + a * a * f * sth * sth) * sth * sth;
-        const double gtt = -(1.0 + f), gtr = f, gtth = 0.0, gtph = 0.0;
-        const double alpha = 1.0 / std::sqrt(-gtt);
-        const double g_01 = dr_dx1 * g_tr + dth_dx1 * g_tth;
-        const double g_02 = dth_dx2 * g_tth;
-        const double g_03 = g_tph;
-        const double g_11 = dr_dx1 * dr_dx1 * g_rr + 2.0 * dr_dx1 * dth_dx1 * g_rth + dth_dx1 * dth_dx1 * g_thth;
-        const double g_12 = dr_dx1 * dth_dx2 * g_rth + dth_dx1 * dth_dx2 * g_thth;
-        const double g_13 = dr_dx1 * g_rph + dth_dx1 * g_thph;
-        const double g_22 = dth_dx2 * dth_dx2 * g_thth;
-        const double g_23 = dth_dx2 * g_thph;
-        const double g_33 = g_phph;
-        const double g00 = gtt;
-        const double g01 = gtr / dr_dx1;
-        const double g02 = g_tth / dth_dx2 - dth_dx1 * g_tr / (dr_dx1 * dth_dx2);
-        const double g03 = gtph;
-        const double alpha_mod = 1.0 / std::sqrt(-g00);
-        const double uu0 = std::sqrt(1.0 + g_11 * uu1 * uu1 + 2.0 * g_12 * uu1 * uu2 + 2.0 * g_13 * uu1 * uu3 + g_22 * uu2 * uu2
-                                     + 2.0 * g_23 * uu2 * uu3 + g_33 * uu3 * uu3);
-        const double u0 = uu0 / alpha_mod;
-        const double u1 = uu1 - alpha_mod * g01 * uu0;
-        const double u2 = uu2 - alpha_mod * g02 * uu0;
-        const double u3 = uu3 - alpha_mod * g03 * uu0;
-        const double u_1 = g_01 * u0 + g_11 * u1 + g_12 * u2 + g_13 * u3;
-        const double u_2 = g_02 * u0 + g_12 * u1 + g_22 * u2 + g_23 * u3;
-        const double u_3 = g_03 * u0 + g_13 * u1 + g_23 * u2 + g_33 * u3;
-        const double ut = u0;
-        const double ur = dr_dx1 * u1;
-        const double uth = dth_dx1 * u1 + dth_dx2 * u2;
-        const double uph = u3;
-        const double uur = ur + alpha * alpha * gtr * ut;
-        const double uuth = uth + alpha * alpha * gtth * ut;
-        const double uuph = uph + alpha * alpha * gtph * ut;
-        const double b0 = u_1 * bb1 + u_2 * bb2 + u_3 * bb3;
-        const double b1 = (bb1 + b0 * u1) / u0;
-        const double b2 = (bb2 + b0 * u2) / u0;
-        const double b3 = (bb3 + b0 * u3) / u0;
-        const double bt = b0;
-        const double br = dr_dx1 * b1;
-        const double bth = dth_dx1 * b1 + dth_dx2 * b2;
-        const double bph = b3;
-        at(d.ind_uu1, k, j, i) = static_cast<float>(uur);
-        at(d.ind_uu2, k, j, i) = static_cast<float>(uuth);
-        at(d.ind_uu3, k, j, i) = static_cast<float>(uuph);
-        at(d.ind_bb1, k, j, i) = static_cast<float>(br * ut - bt * ur);
-        at(d.ind_bb2, k, j, i) = static_cast<float>(bth * ut - bt * uth);
-        at(d.ind_bb3, k, j, i) = static_cast<float>(bph * ut - bt * uph);
-      }
+  }
+  for (int a = 0; a < 6; a++) s->coords[a] = std::move(grid.coords[a]);
+  s->sks_map = std::move(grid.sks_map);
   s->levels.assign(1, 0);
   s->locations.assign(3, 0);
   d.n_blocks = 1;
@@ -1257,9 +1070,10 @@ void ReadIharm3d(const bl_params &p, int file_number, bl_snapshot *s) {
   d.n_j = static_cast<int32_t>(n[1]);
   d.n_k = static_cast<int32_t>(n[2]);
   d.n_var = n_prim;
-  d.prim = s->prim.data();
+  d.prim = raw ? nullptr : s->prim.data();
   d.x1f = s->coords[0].data(); d.x2f = s->coords[1].data(); d.x3f = s->coords[2].data();
   d.x1v = s->coords[3].data(); d.x2v = s->coords[4].data(); d.x3v = s->coords[5].data();
+  d.sks_map = s->sks_map.empty() ? nullptr : s->sks_map.data();
   d.levels = s->levels.data();
   d.locations = s->locations.data();
   d.n_3_root = 0;
@@ -1389,11 +1203,13 @@ void ReadHarm3d(const bl_params &p, int file_number, bl_snapshot *s) {
 }
 
 // Either format
-void ReadSnapshot(const bl_params &p, int file_number, bl_snapshot *s) {
+void ReadSnapshot(const bl_params &p, int file_number, bl_snapshot *s, bool raw = false) {
+  if (raw && p.simulation_format != BL_SIMFMT_IHARM3D)
+    Fail("bl_snapshot_open_raw reads simulation_format = iharm3d only.", BL_E_UNSUPPORTED);
   if (p.simulation_format == BL_SIMFMT_ATHENAK)
     ReadAthenaK(p, file_number, s);
   else if (p.simulation_format == BL_SIMFMT_IHARM3D)
-    ReadIharm3d(p, file_number, s);
+    ReadIharm3d(p, file_number, s, raw);
   else if (p.simulation_format == BL_SIMFMT_HARM3D)
     ReadHarm3d(p, file_number, s);
   else
@@ -1402,6 +1218,28 @@ void ReadSnapshot(const bl_params &p, int file_number, bl_snapshot *s) {
 
 void SetError(char *err, size_t err_len, const std::string &message) {
   if (err != nullptr && err_len > 0) std::snprintf(err, err_len, "Error: %s\n", message.c_str());
+}
+
+// File `file_number` of the series (-1: simulation_file as it stands) as a new snapshot; `raw`: stopped before the transpose
+int OpenFile(const bl_params &p, int file_number, bool raw, bl_snapshot **out, char *err, size_t err_len) {
+  *out = nullptr;
+  bl_snapshot *s = nullptr;
+  try {
+    s = new bl_snapshot;
+    ReaderSetup(p, s);
+    s->setup_warning_bytes = s->warnings.size();
+    ReadSnapshot(p, file_number, s, raw);
+    *out = s;
+    return BL_OK;
+  } catch (const ReadFailure &f) {
+    delete s;
+    SetError(err, err_len, f.message);
+    return f.code;
+  } catch (const std::exception &e) {
+    delete s;
+    SetError(err, err_len, std::string("Could not read simulation file (") + e.what() + ").");
+    return BL_E_INPUT;
+  }
 }
 
 }  // namespace
@@ -1439,25 +1277,24 @@ int bl_snapshot_open_number(const bl_params *p, int file_number, bl_snapshot **o
     SetError(err, err_len, "bl_snapshot_open_number: bad argument.");
     return BL_E_ARG;
   }
-  *out = nullptr;
-  bl_snapshot *s = nullptr;
-  try {
-    s = new bl_snapshot;
-    ReaderSetup(*p, s);
-    s->setup_warning_bytes = s->warnings.size();
-    ReadSnapshot(*p, file_number, s);
-    *out = s;
-    return BL_OK;
-  } catch (const ReadFailure &f) {
-    delete s;
-    SetError(err, err_len, f.message);
-    return f.code;
-  } catch (const std::exception &e) {
-    delete s;
-    SetError(err, err_len, std::string("Could not read simulation file (") + e.what() + ").");
-    return BL_E_INPUT;
-  }
+  return OpenFile(*p, file_number, false, out, err, err_len);
 }
+
+int bl_snapshot_open_raw(const bl_params *p, int file_number, bl_snapshot **out, char *err, size_t err_len) {
+  if (p == nullptr || out == nullptr || file_number < -1) {
+    SetError(err, err_len, "bl_snapshot_open_raw: bad argument.");
+    return BL_E_ARG;
+  }
+  return OpenFile(*p, file_number, true, out, err, err_len);
+}
+
+int bl_snapshot_harm_header(const bl_snapshot *s, bl_harm_header *out) {
+  if (s == nullptr || out == nullptr || !s->raw) return BL_E_STATE;
+  *out = s->harm_header;
+  return BL_OK;
+}
+
+const float *bl_snapshot_harm_prims(const bl_snapshot *s) { return s != nullptr && s->raw ? s->prim.data() : nullptr; }
 
 // SimulationReader::Read(snapshot) with slow light (simulation_reader.cpp:211-303, :313-861): advance the
 // window of slow_chunk_size files until its latest file is not earlier than the camera time.

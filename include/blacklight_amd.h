@@ -359,6 +359,54 @@ BL_API void bl_snapshot_close(bl_snapshot *s);
  * simulation_multiple / slow_light_on say: the building block of bl_slow_light_read(). */
 BL_API int bl_snapshot_open_number(const bl_params *p, int file_number, bl_snapshot **out, char *err, size_t err_len);
 
+/* ------------------------------------------------------------------ iharm3d-family primitives (host side; no HIP call)
+ * iharm3d, KHARMA and their kin hold prims[n1][n2][n3][n_prim]: density, internal energy UU, velocity U1..U3 and field B1..B3 on
+ * the basis of their modified (MKS) or funky modified (FMKS / MMKS) Kerr-Schild coordinates. What the sampler reads is
+ * [var][k][j][i] with pressure, normal-frame velocity and lab-frame field on the spherical Kerr-Schild basis: the reference's
+ * ConvertCoordinates and ConvertPrimitives3 (simulation_geometry.cpp:29-230). The calls below do to a header and a cell array in
+ * memory what the reader does to a file, with the reader's error and warning texts and cells equal to its cells bit for bit; the
+ * device calls (bl_set_grid_device_harm, further down) run the same conversion on arrays in device memory.
+ * bl_harm_header: the numbers the reader takes from the file. Absent adiabatic indices are NaN, an absent variable is index -1. */
+#define BL_HARM_MKS 0    /* header/metric = MKS                                                        */
+#define BL_HARM_FMKS 1   /* header/metric = FMKS or MMKS: r_in, poly_xt, poly_alpha, mks_smooth are read */
+typedef struct bl_harm_header {
+  int32_t n1, n2, n3, n_prim;
+  double startx[3], dx[3];       /* header/geom/startx1..3, dx1..3                                  */
+  double a, hslope;              /* header/geom/<metric>/a, hslope                                  */
+  int32_t metric, reserved;      /* BL_HARM_MKS | BL_HARM_FMKS                                      */
+  double r_in, poly_xt, poly_alpha, mks_smooth;
+  double gam, gam_p, gam_e;      /* header/gam, gam_p, gam_e; NaN: not in the file                  */
+  int32_t ind_rho, ind_uu, ind_u1, ind_u2, ind_u3, ind_b1, ind_b2, ind_b3;   /* "RHO", "UU", "U1" ... "B3" in header/prim_names */
+  int32_t ind_kappa, reserved2;  /* simulation_kappa_name; read with plasma_model = code_kappa      */
+} bl_harm_header;
+BL_API size_t bl_harm_header_sizeof(void);
+/* The grid of a header under the parameters `p` (simulation_coord = sks: coordinates converted to r, theta; fmks: kept native, with
+ * bounds and look-up table; simulation_a, the plasma model and the adiabatic indices as the reader treats them), and the table of the
+ * conversion's per-point factors. err receives "Error: ...\n" with the reader's texts ("Array dimension mismatch.", "Unable to locate
+ * \"U1\" slice of \"prims\" in data file.", "simulation_coord = fmks needs a file whose header/metric is FMKS or MMKS.", ...);
+ * bl_harm_grid_warnings the reader's "Warning: ...\n" lines (spin and adiabatic indices that differ from the input's). One refusal
+ * is this call's own (BL_E_UNSUPPORTED): with plasma_model = code_kappa, an ind_kappa that names UU or a vector component - the
+ * entropy plane is a copy of the variable as it lies, and the reader would hand over the converted one.
+ * bl_harm_grid_desc(g, 0): the description for bl_set_grid_device_harm - prim NULL, n_var = n_prim, the header's indices; (g, 1): for
+ * planes as bl_harm_convert_* write them - n_var 8 (9), indices 0 ... 7 (8) - which is what bl_set_grid / bl_set_grid_device take
+ * with those planes. Both are owned by the grid. The 2048 x 2048 look-up table of simulation_coord = fmks is built when a
+ * description is first asked for: a caller who only converts never pays for it. */
+typedef struct bl_harm_grid bl_harm_grid;
+BL_API int bl_harm_grid_create(const bl_params *p, const bl_harm_header *header, bl_harm_grid **out, char *err, size_t err_len);
+BL_API const bl_grid_desc *bl_harm_grid_desc(bl_harm_grid *g, int converted);
+BL_API const char *bl_harm_grid_warnings(const bl_harm_grid *g);
+BL_API int bl_harm_grid_planes(const bl_harm_grid *g);   /* 8, or 9 with plasma_model = code_kappa (the entropy plane last) */
+BL_API void bl_harm_grid_free(bl_harm_grid *g);
+/* prims: float32 [n1][n2][n3][n_prim] -> out: float32 [planes][n3][n2][n1] in the order rho, pgas, uu1, uu2, uu3, bb1, bb2, bb3
+ * (, kappa): p = (gamma - 1) u in float, the vectors converted in double and rounded, everything else copied. */
+BL_API int bl_harm_convert_host(const bl_harm_grid *g, const float *prims, float *out);
+/* The reader stopped before its transpose (simulation_format = iharm3d only): every check of bl_snapshot_open_number made, the header
+ * as a struct, the file's prims as they lie - float32 [n1][n2][n3][n_prim], owned by the snapshot - and no look-up table built.
+ * file_number = -1: simulation_file as it stands. bl_snapshot_grid()->prim is NULL for such a snapshot. */
+BL_API int bl_snapshot_open_raw(const bl_params *p, int file_number, bl_snapshot **out, char *err, size_t err_len);
+BL_API int bl_snapshot_harm_header(const bl_snapshot *s, bl_harm_header *out);   /* BL_E_STATE: not opened raw */
+BL_API const float *bl_snapshot_harm_prims(const bl_snapshot *s);                /* NULL: not opened raw       */
+
 /* ------------------------------------------------------------------ camera frame
  * The seven 4-vectors GeodesicIntegrator::InitializeCamera() derives (camera.cpp:61-380,
  * geodesic_integrator.hpp) and the frequency list (:30-50). Filled by bl_init. */
@@ -543,6 +591,35 @@ BL_API int bl_set_grid_slice(bl_ctx *ctx, int slice, const bl_grid_desc *g, doub
 BL_API int bl_set_grid_slice_device(bl_ctx *ctx, int slice, const bl_grid_desc *g, const bl_device_cells *cells, double time);   /* (cells in device memory: bl_set_grid_device) */
 BL_API int bl_shift_grid_slices(bl_ctx *ctx, int count);
 BL_API int bl_set_snapshot(bl_ctx *ctx, int snapshot);
+/* ---- iharm3d-family primitives in device memory: bl_set_grid_device / bl_set_grid_slice_device for the array a harm-family code
+ * holds, prims[n1][n2][n3][n_prim] contiguous, float or double. The staging kernel transposes it and converts every cell as the
+ * reader converts a file's (bl_harm_grid, above): F64 cells are rounded to float first, p = (gamma - 1) u in float, the vectors in
+ * double from the grid's point table (uploaded once per grid and context), the result rounded to float - the cells in HBM are, bit
+ * for bit, those of bl_set_grid with the snapshot the reader makes of the same data. prim, dtype, wait, stream and n_elements mean
+ * what they mean in bl_device_cells, and the same is checked (BL_E_ARG, a text each): prim NULL or not aligned to its element, dtype,
+ * n_elements below n1 n2 n3 n_prim, then on the device that prim is device memory of the context's device with n_elements elements
+ * inside one allocation. Beside a render, the series' fast path, slow-light slices, bl_grid_host_bytes (tables only): as
+ * bl_set_grid_device.
+ * The grid and the context: spin, adiabatic indices and the choice of variables are the grid's, fixed by the parameters it was made
+ * with - make it with the context's. A grid made with another plasma_model than the context's, where one of the two is code_kappa,
+ * is refused (BL_E_ARG): the entropy plane would be missing or come from a variable nobody named.
+ * Threads: these three calls are bl_set_grid calls - one at a time per context, bl_harm_convert_device included (the context keeps
+ * one copy of a grid's point table on the device, replaced when another grid comes; a render of the same context may run beside
+ * the setters as beside bl_set_grid, and bl_harm_convert_device waits for it).
+ * bl_harm_convert_device writes the planes of bl_harm_convert_host - float32 [planes][n3][n2][n1], planes = bl_harm_grid_planes() -
+ * into out_planes, caller-owned device memory of the context's device holding at least that many floats: with
+ * bl_harm_grid_desc(g, 1) they are what bl_set_grid_device takes. Any n1, n2, n3 >= 1. Returns when the planes are written. */
+typedef struct bl_harm_cells {
+  const void *prim;       /* device memory of the context's device: [n1][n2][n3][n_prim], contiguous         */
+  int32_t dtype;          /* BL_CELLS_F32 | BL_CELLS_F64                                                     */
+  int32_t wait;           /* != 0: the staging first waits, on the device, for the work queued on `stream`  */
+  int64_t n_elements;     /* extent of the caller's array from `prim`, in elements                           */
+  void *stream;           /* hipStream_t (NULL: the NULL stream); read only with wait != 0                   */
+} bl_harm_cells;
+BL_API size_t bl_harm_cells_sizeof(void);
+BL_API int bl_set_grid_device_harm(bl_ctx *ctx, bl_harm_grid *grid, const bl_harm_cells *cells);
+BL_API int bl_set_grid_slice_device_harm(bl_ctx *ctx, int slice, bl_harm_grid *grid, const bl_harm_cells *cells, double time);
+BL_API int bl_harm_convert_device(bl_ctx *ctx, const bl_harm_grid *grid, const bl_harm_cells *cells, float *out_planes);
 /* Number of image rows n_q and their offsets (radiation_integrator.cpp:436-520). */
 BL_API int bl_image_num_quantities(const bl_ctx *ctx);
 /* Electron-temperature models (the R_high / R_low prescription: plasma_rat_high, plasma_rat_low) rendered by one bl_render.

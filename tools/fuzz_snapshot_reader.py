@@ -5,7 +5,7 @@ bytes flipped, fields overwritten by extreme integers, files truncated. A damage
 if the damage is harmless) - never in a read or write outside the file's mapping or the reader's arrays.
 
     g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -fPIC -shared -pthread -Iinclude -Iblacklight_amd/csrc \\
-        blacklight_amd/csrc/bl_snapshot.cpp blacklight_amd/csrc/bl_params.cpp -o /tmp/snapfuzz/libsnap_asan.so
+        blacklight_amd/csrc/bl_snapshot.cpp blacklight_amd/csrc/bl_harm.cpp blacklight_amd/csrc/bl_params.cpp -o /tmp/snapfuzz/libsnap_asan.so
     LD_PRELOAD="$(gcc -print-file-name=libasan.so) $(gcc -print-file-name=libstdc++.so)" ASAN_OPTIONS=detect_leaks=0 \\
         python3 tools/fuzz_snapshot_reader.py /tmp/snapfuzz/libsnap_asan.so [mutations per fixture] [seed]
 
